@@ -19,6 +19,8 @@ Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel: algori
 its HIP-event duration on the call's stream vs the chip peak), "cpu_baseline" (the oracle restatement of the
 reference CPU path on this box's host cores, bounded sample, median of 3), "parity_vs_oracle", "stages".
 Other BASELINE.json configs are reachable with flags (e.g. config 2: --docs 1000000), they are not the default line.
+`--dump-outputs DIR` writes what the last timed step returned (ids, scores, counts as .npy) so that two builds can be compared output
+for output on the same seeded inputs.
 """
 import argparse
 import ctypes as C
@@ -103,7 +105,38 @@ def parse():
                          "format (np_hip_index_write_dir), the HBM copy dropped, and the bench runs on np_hip_index_open of that "
                          "directory (= MmapIndex::load).  The line gains `disk_open` (seconds, bytes, GB/s: warm page cache and, "
                          "when the box lets us drop caches, cold)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="directory: after the timed steps, rank 0 writes what the LAST timed step returned as DIR/passage_ids.npy "
+                         "(f64 [batch, top_k]), DIR/scores.npy (f32 [batch, top_k]) and DIR/counts.npy (f64 [batch]); slots at or past "
+                         "a query's count hold id -1 and score -inf.  Above 64 MB in all, a fixed seeded sample of the queries is "
+                         "written and DIR/query_rows.npy names them")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, ids, scores, counts):
+    """The last timed step's (ids, scores, counts) as float arrays, padding masked so that builds compare slot for slot."""
+    ids = ids.astype(np.float64)
+    scores = scores.astype(np.float32)
+    counts = counts.astype(np.float64)
+    pad = np.arange(ids.shape[1])[None, :] >= counts[:, None]
+    ids[pad] = -1.0
+    scores[pad] = -np.inf
+    arrs = dict(passage_ids=ids, scores=scores, counts=counts)
+    row_bytes = sum(v[0].nbytes for v in arrs.values())
+    if row_bytes * len(counts) > DUMP_MAX_BYTES - 4096:           # 4096: the .npy headers
+        n = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)             # + 8: the row's entry in query_rows
+        rows = np.sort(np.random.default_rng(0).choice(len(counts), n, replace=False))
+        arrs = {k: v[rows] for k, v in arrs.items()}
+        arrs["query_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
 
 
 def kernels_sha():
@@ -379,9 +412,11 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        step(i)
+        last = step(i)
     barrier()
     dt = time.perf_counter() - t0
+    # copied out before the latency batches below reuse the per-stream output buffers
+    last = [t.cpu().numpy() for t in last] if a.dump_outputs and rank == 0 else None
     if use_shards and dist_impl == "c":
         for cm in comms:   # a rank that failed locally empties the batch everywhere and leaves its status here (np_dist.hip)
             fr, code = cm.status()
@@ -675,6 +710,8 @@ def main():
         "index_build_s": round(t_build, 2), "hbm_index_bytes": int(ix.info.device_bytes),
         "hbm_bytes_per_token": round(ix.info.device_bytes / max(int(ix.info.shard_embeddings), 1), 2),
     }
+    if last is not None:
+        dump_outputs(a.dump_outputs, *last)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
