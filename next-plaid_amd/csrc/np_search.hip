@@ -12,6 +12,8 @@
 #include <cmath>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
+#include <utility>
 
 namespace np {
 
@@ -196,7 +198,7 @@ static int validate(const DeviceIndex* ix, int32_t B, int32_t dim, const np_sear
 // record of the two-level filter + 16-B survivor record), which is sized by the
 // budget, not by n_docs: B x n_docs entries only when that fits workspace_bytes, otherwise what is left of the
 // budget after the per-query scratch (never less than 2 x n_docs entries, one query's worst case twice).
-#define NP_POOL_ENTRY 60
+constexpr int NP_POOL_ENTRY = 60;
 struct WsPlan {
   int S = 1;            // queries per slice
   int64_t pool = 1;     // candidate-pool entries
@@ -244,74 +246,115 @@ static WsPlan plan_workspace(const DeviceIndex* ix, int B, int LQP, const np_sea
   return w;
 }
 
-template <int DIM>
+// The longest query of the batch in tokens (at least 1)
+static int max_tokens(const int32_t* h_qoff, int B) {
+  int maxLq = 1;
+  for (int b = 0; b < B; ++b) maxLq = std::max(maxLq, h_qoff[b + 1] - h_qoff[b]);
+  return maxLq;
+}
+
+// ---- typed dispatch: a runtime value becomes a std::integral_constant handed to a generic lambda -------------------------
+// f(std::integral_constant<int, V>) for the first V of Vs equal to v; the last of Vs takes every other value
+template <int V, int... Vs, class F>
+static decltype(auto) with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V>{});
+  else if (v == V) return f(std::integral_constant<int, V>{});
+  else return with_int<Vs...>(v, std::forward<F>(f));
+}
+template <class F>
+static decltype(auto) with_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+// storage dim (validate(): 32, 64, 96 or 128)
+template <class F>
+static decltype(auto) with_dim(int dim, F&& f) {
+  return with_int<32, 64, 96, 128>(dim, std::forward<F>(f));
+}
+// row bytes of the u8 score table (LQP rounded up to a power of two)
+template <class F>
+static decltype(auto) with_rowb(int rb, F&& f) {
+  return with_int<32, 64, 128, 256>(rb, std::forward<F>(f));
+}
+// code type of the list blocks: u16, or u32 for indices with more than 65536 centroids; f(CT{})
+template <class F>
+static decltype(auto) with_codes(bool wide, F&& f) {
+  return wide ? f(uint32_t{}) : f(uint16_t{});
+}
+
 static void launch_gemm(hipStream_t st, const DeviceIndex* ix, const float* Qt, int B, int LQP, float* QCT,
                         uint32_t* gmax, uint8_t* QCU = nullptr, int RB = 0, const float* qinv = nullptr,
                         const int32_t* qoff = nullptr) {
   // one 32-centroid fragment per wave: 128 centroids per block, ~2 blocks per CU co-resident, so one wave's
   // epilogue (stores, key maxima) hides under another wave's MFMAs.  KP is a multiple of 64.
-  if (ix->tune.gemm_cpw == 2) {
-    const unsigned blocks = (unsigned)((ix->KP / 64 + 3) / 4);
-    qc_gemm_kernel<DIM, 2><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
-  } else {
-    const unsigned blocks = (unsigned)((ix->KP / 32 + 3) / 4);
-    qc_gemm_kernel<DIM, 1><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
+  with_dim(ix->dim, [&](auto DIM) {
+    if (ix->tune.gemm_cpw == 2) {
+      const unsigned blocks = (unsigned)((ix->KP / 64 + 3) / 4);
+      qc_gemm_kernel<DIM, 2><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
+    } else {
+      const unsigned blocks = (unsigned)((ix->KP / 32 + 3) / 4);
+      qc_gemm_kernel<DIM, 1><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
+    }
+  });
+}
+
+// grid of S6's transposed kernels: one XCD per query (see exact_qct_kernel) from 8 queries on
+static dim3 exact_grid(const DeviceIndex* ix, ExactP& px, unsigned gx, int B) {
+  if (B >= 8 && ix->tune.s6_xcd) {
+    px.xcd_B = B;
+    px.gx = (int)gx;
+    return dim3(8u * (unsigned)((B + 7) / 8) * gx, 1);
   }
+  return dim3(gx, B);
 }
 
 template <int DIM, int NBITS, int NQT>
 static int launch_exact(hipStream_t st, const DeviceIndex* ix, const ExactP& p, int B, int precision) {
   const unsigned gx = (unsigned)((p.n_sel + 4 * NP_EXACT_DPW - 1) / (4 * NP_EXACT_DPW));
   if (gx == 0 || B == 0) return NP_OK;
-  if (precision == 0) {
+  // nbits 8 (one dim per byte, 256 bucket weights): the all-f32 kernel at every precision (>= what was asked for)
+  if (NBITS == 8 || precision == 0) {
     const size_t lds = ((size_t)DIM * p.LQP + (1 << NBITS)) * sizeof(float);
     if (lds > 64 * 1024)
       NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_f32_kernel<DIM, NBITS, NQT>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     exact_f32_kernel<DIM, NBITS, NQT><<<dim3(gx, B), 256, lds, st>>>(p);
-  } else if (precision == 1 || precision == 2) {
-    // Transposed form (4 float4 QC loads per tile, no per-row shuffles), ONE LAUNCH PER 32-TOKEN QUERY TILE: the one-tile
-    // instantiation keeps three waves per SIMD; a two-tile one needs 242 VGPRs and ran 48-token queries 4x slower than
-    // 32-token ones (2.46 vs 0.60 ms at 10 M documents).  s6_tiles = 0 restores the multi-tile kernels.
-    if (!ix->tune.exact_rowmax && (NQT == 1 || ix->tune.s6_tiles)) {
-      ExactP px = p;
-      dim3 grid(gx, B);
-      if (B >= 8 && ix->tune.s6_xcd) {   // one XCD per query (see exact_qct_kernel)
-        px.xcd_B = B;
-        px.gx = (int)gx;
-        grid = dim3(8u * (unsigned)((B + 7) / 8) * gx, 1);
-      }
-      for (int qt = 0; qt < p.LQP / 32; ++qt) {
-        px.qt0 = qt;
-        px.acc = qt > 0;
-        if (ix->tune.s6_lds == 2) {   // query fragments in LDS, C-in rows one tile ahead; registers cut for 4 waves per SIMD
-          if (precision == 1) exact_qcl_kernel<DIM, NBITS, 1, 4><<<grid, 256, 0, st>>>(px);
-          else exact_qcl_kernel<DIM, NBITS, 3, 4><<<grid, 256, 0, st>>>(px);
-        } else if (ix->tune.s6_lds == 1) {   // the same at 3 waves per SIMD (no spills)
-          if (precision == 1) exact_qcl_kernel<DIM, NBITS, 1, 3><<<grid, 256, 0, st>>>(px);
-          else exact_qcl_kernel<DIM, NBITS, 3, 3><<<grid, 256, 0, st>>>(px);
-        } else {
-          if (precision == 1) exact_qct_kernel<DIM, NBITS, 1, 1><<<grid, 256, 0, st>>>(px);
-          else exact_qct_kernel<DIM, NBITS, 1, 3><<<grid, 256, 0, st>>>(px);
+    return NP_OK;
+  }
+  if constexpr (NBITS != 8) {
+    if (precision == 1 || precision == 2) {
+      // Transposed form (4 float4 QC loads per tile, no per-row shuffles), ONE LAUNCH PER 32-TOKEN QUERY TILE: the one-tile
+      // instantiation keeps three waves per SIMD; a two-tile one needs 242 VGPRs and ran 48-token queries 4x slower than
+      // 32-token ones (2.46 vs 0.60 ms at 10 M documents).  s6_tiles = 0 restores the multi-tile kernels.
+      if (!ix->tune.exact_rowmax && (NQT == 1 || ix->tune.s6_tiles)) {
+        ExactP px = p;
+        const dim3 grid = exact_grid(ix, px, gx, B);
+        for (int qt = 0; qt < p.LQP / 32; ++qt) {
+          px.qt0 = qt;
+          px.acc = qt > 0;
+          if (ix->tune.s6_lds == 2) {   // query fragments in LDS, C-in rows one tile ahead; registers cut for 4 waves per SIMD
+            if (precision == 1) exact_qcl_kernel<DIM, NBITS, 1, 4><<<grid, 256, 0, st>>>(px);
+            else exact_qcl_kernel<DIM, NBITS, 3, 4><<<grid, 256, 0, st>>>(px);
+          } else if (ix->tune.s6_lds == 1) {   // the same at 3 waves per SIMD (no spills)
+            if (precision == 1) exact_qcl_kernel<DIM, NBITS, 1, 3><<<grid, 256, 0, st>>>(px);
+            else exact_qcl_kernel<DIM, NBITS, 3, 3><<<grid, 256, 0, st>>>(px);
+          } else {
+            if (precision == 1) exact_qct_kernel<DIM, NBITS, 1, 1><<<grid, 256, 0, st>>>(px);
+            else exact_qct_kernel<DIM, NBITS, 1, 3><<<grid, 256, 0, st>>>(px);
+          }
         }
+      } else if (NQT <= 2 && !ix->tune.exact_rowmax) {
+        ExactP px = p;
+        const dim3 grid = exact_grid(ix, px, gx, B);
+        constexpr int NQ = NQT <= 2 ? NQT : 1;
+        if (precision == 1) exact_qct_kernel<DIM, NBITS, NQ, 1><<<grid, 256, 0, st>>>(px);
+        else exact_qct_kernel<DIM, NBITS, NQ, 3><<<grid, 256, 0, st>>>(px);
+      } else {
+        if (precision == 1) exact_qc_kernel<DIM, NBITS, NQT, 1><<<dim3(gx, B), 256, 0, st>>>(p);
+        else exact_qc_kernel<DIM, NBITS, NQT, 3><<<dim3(gx, B), 256, 0, st>>>(p);
       }
-    } else if (NQT <= 2 && !ix->tune.exact_rowmax) {
-      ExactP px = p;
-      dim3 grid(gx, B);
-      if (B >= 8 && ix->tune.s6_xcd) {
-        px.xcd_B = B;
-        px.gx = (int)gx;
-        grid = dim3(8u * (unsigned)((B + 7) / 8) * gx, 1);
-      }
-      constexpr int NQ = NQT <= 2 ? NQT : 1;
-      if (precision == 1) exact_qct_kernel<DIM, NBITS, NQ, 1><<<grid, 256, 0, st>>>(px);
-      else exact_qct_kernel<DIM, NBITS, NQ, 3><<<grid, 256, 0, st>>>(px);
     } else {
-      if (precision == 1) exact_qc_kernel<DIM, NBITS, NQT, 1><<<dim3(gx, B), 256, 0, st>>>(p);
-      else exact_qc_kernel<DIM, NBITS, NQT, 3><<<dim3(gx, B), 256, 0, st>>>(p);
+      exact_bf16_kernel<DIM, NBITS, NQT><<<dim3(gx, B), 256, 0, st>>>(p);
     }
-  } else {
-    exact_bf16_kernel<DIM, NBITS, NQT><<<dim3(gx, B), 256, 0, st>>>(p);
   }
   return NP_OK;
 }
@@ -321,29 +364,6 @@ static int launch_exact_qt(hipStream_t st, const DeviceIndex* ix, const ExactP& 
   if (p.LQP <= 32) return launch_exact<DIM, NBITS, 1>(st, ix, p, B, precision);
   if (p.LQP <= 64) return launch_exact<DIM, NBITS, 2>(st, ix, p, B, precision);
   return launch_exact<DIM, NBITS, NP_MAX_QT>(st, ix, p, B, precision);
-}
-
-template <int DIM>
-static int launch_exact_nb(hipStream_t st, const DeviceIndex* ix, const ExactP& p, int B, int precision, int nbits) {
-  if (nbits == 2) return launch_exact_qt<DIM, 2>(st, ix, p, B, precision);
-  if (nbits == 8) {   // one dim per byte, 256 bucket weights: the all-f32 kernel at every precision (>= what was asked for)
-    const unsigned gx = (unsigned)((p.n_sel + 4 * NP_EXACT_DPW - 1) / (4 * NP_EXACT_DPW));
-    if (gx == 0 || B == 0) return NP_OK;
-    const size_t lds = ((size_t)DIM * p.LQP + 256) * sizeof(float);
-#define NP_F32_NB8(NQT)                                                                                              \
-  do {                                                                                                               \
-    if (lds > 64 * 1024)                                                                                             \
-      NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&exact_f32_kernel<DIM, 8, NQT>),                      \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                             \
-    exact_f32_kernel<DIM, 8, NQT><<<dim3(gx, B), 256, lds, st>>>(p);                                                 \
-  } while (0)
-    if (p.LQP <= 32) NP_F32_NB8(1);
-    else if (p.LQP <= 64) NP_F32_NB8(2);
-    else NP_F32_NB8(NP_MAX_QT);
-#undef NP_F32_NB8
-    return NP_OK;
-  }
-  return launch_exact_qt<DIM, 4>(st, ix, p, B, precision);
 }
 
 // S4 for the queries of one round: exact f32 approximate scores of `n[b]` records at meta[cand_base[b]...]
@@ -357,95 +377,167 @@ static void launch_approx(hipStream_t st, const DeviceIndex* ix, Workspace& w, c
   const unsigned nbx = (unsigned)t.s4_nbx;   // workgroups per XCD
   const uint32_t slice_w = (uint32_t)((ix->K + 7) / 8);
   const int s4_p = std::min(t.s4_mode > 4 ? t.s4_mode - 4 : t.s4_mode, 4);   // phases = 8 >> (s4_p - 1)
+  // streamed form: u16 code-in-slice needs a phase's centroid range <= 65536
   const bool stream = t.s4_mode >= 5 && t.s4_mode <= 8 && ((uint64_t)slice_w << (t.s4_mode - 5)) <= 65536ull;
-  if (stream && ix->sliced_ok && B >= t.s4_minb) {
-    // streamed form (approx_stream_kernel): u16 code-in-slice needs a phase's centroid range <= 65536
-#define NP_LAUNCH_APPROX_S(LPR)                                                                                       \
-  approx_stream_kernel<LPR><<<8 * nbx, 256, 0, st>>>(w.QCT.as<float>(), KP, LQP, d_qoff, meta, n, rp, round,          \
-                                                     max_rounds, ix->ucodes(), ix->n_ucodes, ix->d_useg, w.approx.as<float>(), \
-                                                     t.s4_mode - 5, slice_w, ctr)
-    if (LQP <= 32) NP_LAUNCH_APPROX_S(8);
-    else if (LQP <= 64) NP_LAUNCH_APPROX_S(16);
-    else if (LQP <= 128) NP_LAUNCH_APPROX_S(32);
-    else NP_LAUNCH_APPROX_S(64);
-#undef NP_LAUNCH_APPROX_S
-  } else if (t.s4_mode > 0 && ix->sliced_ok && B >= t.s4_minb) {
-#define NP_LAUNCH_APPROX_X(LPR, SWZ)                                                                                  \
-  approx_xcd_kernel<LPR, SWZ><<<8 * nbx, 256, 0, st>>>(w.QCT.as<float>(), KP, LQP, d_qoff, meta, n, rp, round,        \
-                                                       max_rounds, ix->ucodes(), ix->n_ucodes, ix->d_useg,         \
-                                                       w.approx.as<float>(), s4_p - 1, ctr)
-    if (LQP <= 32) {
-      if (t.s4_swz) NP_LAUNCH_APPROX_X(8, true);
-      else NP_LAUNCH_APPROX_X(8, false);
-    } else if (LQP <= 64) NP_LAUNCH_APPROX_X(16, false);
-    else if (LQP <= 128) NP_LAUNCH_APPROX_X(32, false);
-    else NP_LAUNCH_APPROX_X(64, false);
-#undef NP_LAUNCH_APPROX_X
-  } else {
-    const unsigned grid = 768;
-#define NP_LAUNCH_APPROX(LPR)                                                                                          \
-  approx_kernel<LPR><<<grid, 256, 0, st>>>(w.QCT.as<float>(), KP, LQP, d_qoff, meta, n, rp, round, max_rounds,         \
-                                           ix->ucodes(), w.approx.as<float>(), ctr)
-    if (LQP <= 32) NP_LAUNCH_APPROX(8);
-    else if (LQP <= 64) NP_LAUNCH_APPROX(16);
-    else if (LQP <= 128) NP_LAUNCH_APPROX(32);
-    else NP_LAUNCH_APPROX(64);
-#undef NP_LAUNCH_APPROX
-  }
+  const bool per_xcd = ix->sliced_ok && B >= t.s4_minb;
+  const int lpr = LQP <= 32 ? 8 : (LQP <= 64 ? 16 : (LQP <= 128 ? 32 : 64));   // lanes per QCT row
+  const float* QCT = w.QCT.as<float>();
+  float* approx = w.approx.as<float>();
+  with_int<8, 16, 32, 64>(lpr, [&](auto LPR) {
+    if (stream && per_xcd) {
+      approx_stream_kernel<LPR><<<8 * nbx, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(),
+                                                         ix->n_ucodes, ix->d_useg, approx, t.s4_mode - 5, slice_w, ctr);
+    } else if (t.s4_mode > 0 && per_xcd) {
+      if constexpr (LPR == 8) {
+        if (t.s4_swz) {   // ds_swizzle code broadcast: 8 lanes per row only
+          approx_xcd_kernel<8, true><<<8 * nbx, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(),
+                                                              ix->n_ucodes, ix->d_useg, approx, s4_p - 1, ctr);
+          return;
+        }
+      }
+      approx_xcd_kernel<LPR, false><<<8 * nbx, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(),
+                                                             ix->n_ucodes, ix->d_useg, approx, s4_p - 1, ctr);
+    } else {
+      approx_kernel<LPR><<<768, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(), approx, ctr);
+    }
+  });
 }
 
 // Batched path (search.rs:259-272): approximate scores of the listed documents in the reference's mat-vec arithmetic
 static void launch_matvec(hipStream_t st, const DeviceIndex* ix, Workspace& w, const float* d_q, const int32_t* d_qoff, int B,
                           const uint4* meta, const int32_t* n, const RoundPlan& rp, int round) {
   const dim3 grid(512 / NP_MV_DOCS, (unsigned)B);      // a wave per NP_MV_DOCS documents: one pass over ~n_sel listed documents
-#define NP_MATVEC(D)                                                                                                   \
-  do {                                                                                                                 \
-    if (ix->ldim & 7)                                                                                                  \
-      approx_matvec_kernel<D, true><<<grid, 256, 0, st>>>(d_q, d_qoff, ix->d_centroids, meta, n, rp, round, ix->ucodes(), \
-                                                          w.approx.as<float>(), ix->ldim);                             \
-    else                                                                                                               \
-      approx_matvec_kernel<D, false><<<grid, 256, 0, st>>>(d_q, d_qoff, ix->d_centroids, meta, n, rp, round, ix->ucodes(), \
-                                                           w.approx.as<float>(), ix->ldim);                            \
-  } while (0)
-  switch (ix->dim) {
-    case 32: NP_MATVEC(32); break;
-    case 64: NP_MATVEC(64); break;
-    case 96: NP_MATVEC(96); break;
-    default: NP_MATVEC(128); break;
-  }
-#undef NP_MATVEC
+  with_dim(ix->dim, [&](auto DIM) {
+    with_bool(ix->ldim & 7, [&](auto TAIL) {
+      approx_matvec_kernel<DIM, TAIL><<<grid, 256, 0, st>>>(d_q, d_qoff, ix->d_centroids, meta, n, rp, round, ix->ucodes(),
+                                                            w.approx.as<float>(), ix->ldim);
+    });
+  });
 }
 
-// S1..S5 for queries [0,B) whose rows live in d_q (absolute offsets d_qoff/h_qoff).
-static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
-                        const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len, bool allow_grow);
+// ---- one pass of S1..S5 over a slice of the batch: its plan ----------------------------------------------------------------
+// Every decision the pass takes from the parameters, the index and the tuning knobs, taken before its first reservation.
+struct PassPlan {
+  int B = 0, maxLq = 1, LQP = 32;
+  int64_t KP = 0, G = 0, NW = 0;
+  int nchunks = 0;
+  int64_t row0 = 0, rows = 0;   // the slice's query rows (absolute)
+  int64_t pool = 1;             // candidate-pool entries
+  int max_rounds = 1;
+  int RB = 32;                  // u8 table row bytes
+  int hshift = 2;               // U <= 255 * RB fits NP_UB_BINS << hshift
+  int slack = 0;                // of the bound, in table units
+  int s4_warm = 1000;           // per-mille of the centroids the floored exact level still gathers
+  size_t slot_words = 0;        // hand-out slots + ticket of one filter launch
+  bool use_filter = false;      // the S4 upper-bound filter
+  bool two_level = false;       // ... with the hot level in front
+  bool use_planes = false;      // ... in bit-plane form
+  bool oob = false;             // the u8 table behind a 32-bit buffer offset
+  bool can_floor = false;       // the S2 list of the two-level filter floors the rows of cold centroids
+  bool ids_only = false;        // S3 hands the filter bare ids
+  bool have_subset = false, use_elig = false, batched = false, s1_split = false, have_cands = false;
+  // the zeroth filter level: its buffers are reserved whenever it MAY run (gain_possible); whether it runs (gain_path) is
+  // settled by the run / skip policy after the reservations
+  bool gain_possible = false, gain_path = false, deep_wanted = false, gain_deep = false;
+  int gain_depth = 32, s0_target = 0, s0cap = 0;
+};
 
-// A reservation that fails under the DEFAULT budget (another index or an encoder took the memory since open) is retried
-// with the pool released and the budget halved -- more candidate-pool rounds instead of OutOfMemory.  Every reservation of
-// a pass happens before its first launch touches the buffer concerned, so a failed pass leaves nothing half-done.
-static int phase_a(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
-                   const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len) {
-  for (int attempt = 0;; ++attempt) {
-    // (a retry never lets the budget grow back: the pass that just failed WAS the planned size)
-    const int rc = phase_a_once(ix, cs, d_q, d_qoff, h_qoff, d_subset, subset_len, attempt == 0);
-    if (rc != NP_ERR_OUT_OF_MEMORY || !ix->ws_auto || attempt >= 4) return rc;
-    const int64_t b = ix->ws_budget.load(std::memory_order_relaxed);
-    if (b <= ((int64_t)256 << 20)) return rc;
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(cs->stream);   // the pool may still be read by work queued before the failure
-    cs->ctx->ws->release_pool();
-    ix->ws_budget.store(std::max<int64_t>(b / 2, (int64_t)256 << 20), std::memory_order_relaxed);
+// w.gsmall, the zeroth level's per-query words (u32): [0, 4B) base / shift / floor bin / 0, then B each: n_raw, thr0, cut0, n_s0,
+// n_emit, n_direct, round_of0, order0, cursor0, n_hi, n_hi_emit, n_marg, lcut; 4 words round_tab0; 6 words = 3 x u64 batch
+// report (8-byte aligned); then (8-byte aligned) cand_base0 i64 [B]
+struct GSmall {
+  uint32_t *base, *thr0, *cut0, *cursor0, *lcut;
+  int32_t *n_raw, *n_s0, *n_emit, *n_direct, *round_of0, *order0, *n_hi, *n_hi_emit, *n_marg, *round_tab0;
+  unsigned long long* report;
+  int64_t* cand_base0;
+  static size_t words(int B) { return (size_t)17 * B + 4 + 8; }
+  static size_t bytes(int B) { return (words(B) + (words(B) & 1)) * 4 + (size_t)B * 8; }
+  GSmall(void* p, int B) {
+    uint32_t* gs = static_cast<uint32_t*>(p);
+    auto i32 = [&](int i) { return reinterpret_cast<int32_t*>(gs + (size_t)i * B); };
+    base = gs;
+    n_raw = i32(4);
+    thr0 = gs + (size_t)5 * B;
+    cut0 = gs + (size_t)6 * B;
+    n_s0 = i32(7);
+    n_emit = i32(8);
+    n_direct = i32(9);
+    round_of0 = i32(10);
+    order0 = i32(11);
+    cursor0 = gs + (size_t)12 * B;
+    n_hi = i32(13);
+    n_hi_emit = i32(14);
+    n_marg = i32(15);
+    lcut = gs + (size_t)16 * B;
+    round_tab0 = i32(17);
+    report = reinterpret_cast<unsigned long long*>(gs + (((size_t)17 * B + 4 + 1) & ~(size_t)1));
+    cand_base0 = reinterpret_cast<int64_t*>(gs + words(B) + (words(B) & 1));
   }
+};
+
+// w.gdeep, the zeroth level's own deeper probe (u32): marks [B][G], per-token thresholds [B][LQP], cell counts [B], the cells a
+// threshold kept [B][G] (a bitmap), cells [B][KP].  All but the cells are cleared with the pass.
+struct GDeep {
+  uint32_t *marks, *tauq, *kept, *cells;
+  int32_t* n_cells;
+  static size_t clear_bytes(const PassPlan& p) { return ((size_t)p.B * p.G + (size_t)p.B * p.LQP + (size_t)p.B + (size_t)p.B * p.G) * 4; }
+  static size_t bytes(const PassPlan& p) { return clear_bytes(p) + (size_t)p.B * p.KP * 4; }
+  GDeep(void* ptr, const PassPlan& p) {
+    uint32_t* gd = static_cast<uint32_t*>(ptr);
+    marks = gd;
+    tauq = gd + (size_t)p.B * p.G;
+    n_cells = reinterpret_cast<int32_t*>(gd + (size_t)p.B * p.G + (size_t)p.B * p.LQP);
+    kept = gd + (size_t)p.B * p.G + (size_t)p.B * p.LQP + (size_t)p.B;
+    cells = gd + (size_t)2 * p.B * p.G + (size_t)p.B * p.LQP + (size_t)p.B;
+  }
+};
+
+// The slice's workspace plan under the current budget.
+static WsPlan plan_budget(const DeviceIndex* ix, Workspace& w, int B, int LQP, const np_search_params& prm,
+                          int64_t probed_cells, bool allow_grow) {
+  WsPlan plan = plan_workspace(ix, B, LQP, &prm, probed_cells);
+  if (!ix->ws_auto) return plan;
+  // The default budget was what the device had free at open.  Before a pool GROWS, and whenever the budget stands below
+  // its value at open, look at what is free now: the budget covers this context's scratch AND pool, so what this context
+  // could hold in total is the free memory plus everything it already holds, minus a GiB for the other contexts' small
+  // buffers and the allocator's granularity.  The budget shrinks when the batch would not fit (another tenant took the
+  // memory since open: more rounds, not OutOfMemory) and returns to the open value only when a whole budget is FREE on the
+  // device again, whatever this context holds (never on the retry of a pass that just failed to reserve its plan).  A looser
+  // rule -- "a quarter more than the current budget is reachable" -- made the three contexts of a 12.5 M-document shard,
+  // which share ~36 GiB with nothing to spare, take turns shrinking and regrowing the shared budget and reallocating their
+  // pools: 466 instead of ~15 000 queries/s.
+  const int64_t want = std::min<int64_t>(plan.pool, (int64_t)std::max(B, 1) * std::max<int64_t>(ix->n_docs, 1));
+  const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
+  // (a context whose own pool fills the device never sees a whole budget free: it would pay hipMemGetInfo on every call for
+  // nothing, so the regrow probe runs on every 32nd call of the context; a pool that must GROW always looks)
+  const bool below = allow_grow && budget < ix->ws_budget_open && (w.probe_tick++ & 31u) == 0u;
+  if ((int64_t)w.cand.cap < want * 4 || below) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      const int64_t held = (int64_t)w.total_bytes();
+      const int64_t avail = (int64_t)free_b + held - ((int64_t)1 << 30);
+      const int64_t need = plan.S * per_query_bytes(ix, LQP, n_sel_of(&prm), prm.top_k) + want * NP_POOL_ENTRY;
+      int64_t nb = budget;
+      if (avail < budget && need > avail) nb = std::max<int64_t>(avail, (int64_t)256 << 20);
+      else if (below && (int64_t)free_b >= ix->ws_budget_open + ((int64_t)1 << 30)) nb = ix->ws_budget_open;
+      if (nb != budget) {
+        // concurrent contexts share the budget: only the context whose view is still current installs its value (a lost
+        // race re-plans from whatever the winner stored)
+        int64_t seen = budget;
+        (void)ix->ws_budget.compare_exchange_strong(seen, nb, std::memory_order_relaxed);
+        plan = plan_workspace(ix, B, LQP, &prm, probed_cells);
+      }
+    }
+  }
+  return plan;
 }
 
-static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
-                        const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len, bool allow_grow) {
-  Workspace& w = *cs->ctx->ws;
-  hipStream_t st = cs->stream;
+// Validates the slice's token offsets, sets the call's per-pass sizes and plans the pass.
+static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff, int64_t subset_len, bool allow_grow,
+                     PassPlan& p) {
   const int B = cs->B;
   const np_search_params& prm = cs->prm;
-  int maxLq = 1;
-  for (int b = 0; b < B; ++b) maxLq = std::max(maxLq, h_qoff[b + 1] - h_qoff[b]);
+  const int maxLq = max_tokens(h_qoff, B);
   for (int b = 0; b < B; ++b)
     if (h_qoff[b + 1] < h_qoff[b]) {
       set_error("Shape error: q_tok_offsets must be non-decreasing");
@@ -462,536 +554,520 @@ static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, 
               (long long)ix->K, LQP);
     return NP_ERR_SHAPE;
   }
-  if (ix->ldim != ix->dim) {   // caller rows -> storage rows; everything below sees ix->dim
-    const int64_t r0 = h_qoff[0], nr = (int64_t)h_qoff[B] - r0;
-    NP_TRY(w.qpad.reserve((size_t)std::max<int64_t>(nr, 1) * ix->dim * 4));
-    if (nr > 0)
-      pad_rows_kernel<<<(unsigned)((nr * ix->dim + 255) / 256), 256, 0, st>>>(d_q + r0 * ix->ldim, nr, ix->ldim, ix->dim,
-                                                                              w.qpad.as<float>());
-    d_q = w.qpad.as<float>() - r0 * ix->dim;   // offsets stay absolute
-  }
+  p.B = B;
+  p.maxLq = maxLq;
+  p.LQP = LQP;
+  p.row0 = h_qoff[0];
+  p.rows = (int64_t)h_qoff[B] - p.row0;
   cs->LQP = LQP;
   cs->n_sel = n_sel_of(&prm);
   cs->NSELP = next_pow2(std::max(cs->n_sel, 1));
   cs->empty_subset = (subset_len == 0);
-  const int64_t KP = ix->KP, G = KP / 32, NW = (ix->n_docs + 31) / 32;
-  const int nchunks = (int)((NW + NP_CHUNK_WORDS - 1) / NP_CHUNK_WORDS);
-  const int nsel1 = std::max(cs->n_sel, 1), topk1 = std::max(prm.top_k, 1);
+  const int64_t KP = ix->KP;
+  p.KP = KP;
+  p.G = KP / 32;
+  p.NW = (ix->n_docs + 31) / 32;
+  p.nchunks = (int)((p.NW + NP_CHUNK_WORDS - 1) / NP_CHUNK_WORDS);
   const int64_t probed_cells = subset_len < 0 ? (int64_t)std::max(prm.n_ivf_probe, 1) * maxLq : 0;
-  WsPlan plan = plan_workspace(ix, B, LQP, &prm, probed_cells);
-  if (ix->ws_auto) {
-    // The default budget was what the device had free at open.  Before a pool GROWS, and whenever the budget stands below
-    // its value at open, look at what is free now: the budget covers this context's scratch AND pool, so what this context
-    // could hold in total is the free memory plus everything it already holds, minus a GiB for the other contexts' small
-    // buffers and the allocator's granularity.  The budget shrinks when the batch would not fit (another tenant took the
-    // memory since open: more rounds, not OutOfMemory) and returns to the open value only when a whole budget is FREE on the
-    // device again, whatever this context holds (never on the retry of a pass that just failed to reserve its plan).  A looser
-    // rule -- "a quarter more than the current budget is reachable" -- made the three contexts of a 12.5 M-document shard,
-    // which share ~36 GiB with nothing to spare, take turns shrinking and regrowing the shared budget and reallocating their
-    // pools: 466 instead of ~15 000 queries/s.
-    const int64_t want = std::min<int64_t>(plan.pool, (int64_t)std::max(B, 1) * std::max<int64_t>(ix->n_docs, 1));
-    const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
-    // (a context whose own pool fills the device never sees a whole budget free: it would pay hipMemGetInfo on every call for
-    // nothing, so the regrow probe runs on every 32nd call of the context; a pool that must GROW always looks)
-    const bool below = allow_grow && budget < ix->ws_budget_open && (w.probe_tick++ & 31u) == 0u;
-    if ((int64_t)w.cand.cap < want * 4 || below) {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const int64_t held = (int64_t)w.total_bytes();
-        const int64_t avail = (int64_t)free_b + held - ((int64_t)1 << 30);
-        const int64_t need = plan.S * per_query_bytes(ix, LQP, n_sel_of(&prm), prm.top_k) + want * NP_POOL_ENTRY;
-        int64_t nb = budget;
-        if (avail < budget && need > avail) nb = std::max<int64_t>(avail, (int64_t)256 << 20);
-        else if (below && (int64_t)free_b >= ix->ws_budget_open + ((int64_t)1 << 30)) nb = ix->ws_budget_open;
-        if (nb != budget) {
-          // concurrent contexts share the budget: only the context whose view is still current installs its value (a lost
-          // race re-plans from whatever the winner stored)
-          int64_t seen = budget;
-          (void)ix->ws_budget.compare_exchange_strong(seen, nb, std::memory_order_relaxed);
-          plan = plan_workspace(ix, B, LQP, &prm, probed_cells);
-        }
-      }
-    }
-  }
-  const int64_t pool = std::min<int64_t>(plan.pool, (int64_t)std::max(B, 1) * std::max<int64_t>(ix->n_docs, 1));
-  const int max_rounds = std::max(1, std::min(plan.max_rounds, std::max(B, 1)));
+  const WsPlan plan = plan_budget(ix, *cs->ctx->ws, B, LQP, prm, probed_cells, allow_grow);
+  p.pool = std::min<int64_t>(plan.pool, (int64_t)std::max(B, 1) * std::max<int64_t>(ix->n_docs, 1));
+  p.max_rounds = std::max(1, std::min(plan.max_rounds, std::max(B, 1)));
 
-  NP_TRY(w.Qt.reserve((size_t)B * ix->dim * LQP * 4));
-  NP_TRY(w.Qb.reserve((size_t)B * ix->dim * LQP * 2));
-  NP_TRY(w.Qbl.reserve((size_t)B * ix->dim * LQP * 2));
-  NP_TRY(w.QCT.reserve((size_t)B * KP * LQP * 4));
-  NP_TRY(w.gmax.reserve((size_t)B * G * LQP * 4));
-  NP_TRY(w.cellbits.reserve((size_t)B * G * 4));
-  NP_TRY(w.tauq.reserve((size_t)B * LQP * 4));
-  NP_TRY(w.cells_tmp.reserve((size_t)B * KP * 4));
-  NP_TRY(w.cells.reserve((size_t)B * KP * 4));
-  NP_TRY(w.n_cells.reserve((size_t)B * 4));
-  NP_TRY(w.docbits.reserve((size_t)B * std::max<int64_t>(NW, 1) * 4));
-  NP_TRY(w.chunk_counts.reserve((size_t)B * std::max(nchunks, 1) * 4));
-  NP_TRY(w.cand.reserve((size_t)pool * 4));
-  NP_TRY(w.cand_meta.reserve((size_t)pool * 16));
-  NP_TRY(w.approx.reserve((size_t)pool * 4));
-  NP_TRY(w.n_cand.reserve((size_t)B * 4));
-  NP_TRY(w.cand_base.reserve((size_t)B * 8));
-  NP_TRY(w.round_of.reserve((size_t)B * 4));
-  NP_TRY(w.round_tab.reserve((size_t)(2 * max_rounds + 1) * 4));
-  NP_TRY(w.q_order.reserve((size_t)B * 4));
-  NP_TRY(w.n_list2.reserve((size_t)B * 4));
   // S4 upper-bound filter (np_kernels.h): off for debug traces (every candidate keeps its exact score) and for
   // indices with a non-finite centroid value
-  const bool use_filter = ix->tune.s4_filter && ix->filter_ok && !cs->trace && cs->n_sel > 0 && ix->T > 0;
-  const int RB = LQP <= 32 ? 32 : (LQP <= 64 ? 64 : (LQP <= 128 ? 128 : 256));   // u8 table row bytes
-  NP_TRY(w.qinv.reserve((size_t)B * 4));
-  NP_TRY(w.qflag.reserve((size_t)B * 4));
+  p.use_filter = ix->tune.s4_filter && ix->filter_ok && !cs->trace && cs->n_sel > 0 && ix->T > 0;
+  const int RB = LQP <= 32 ? 32 : (LQP <= 64 ? 64 : (LQP <= 128 ? 128 : 256));
+  p.RB = RB;
   // two-level filter (np_kernels.h, "S4, first filter level"): the hot bitmap of a query lives in LDS (K / 8 bytes)
   // bit-plane form of the first level (approx_hotp_kernel): rows of 32 / 64 query tokens; list blocks of up to 512 bytes
   // (staged by a whole wave, LPD = 4) exist only with it -- approx_hot_kernel stages at most 256-byte blocks
   const int old_cap = ix->code_wide ? 64 : 128;
-  const bool use_planes = ix->tune.s4_planes && RB <= 64;
-  const bool two_level = use_filter && ix->tune.s4_hot > 0 && KP / 8 <= 64 * 1024 && KP * RB < ((int64_t)1 << 31) &&
-                         ix->ublock_stride > 0 && (use_planes || ix->ublock_stride <= old_cap);
+  p.use_planes = ix->tune.s4_planes && RB <= 64;
+  p.two_level = p.use_filter && ix->tune.s4_hot > 0 && KP / 8 <= 64 * 1024 && KP * RB < ((int64_t)1 << 31) &&
+                ix->ublock_stride > 0 && (p.use_planes || ix->ublock_stride <= old_cap);
   // Share of the centroids whose rows the exact level still gathers (the rest: floored at Lambda2).  A token more is a floor
   // more and a longer list has a higher maximum per token, so the best share RISES with the query length and FALLS with the
   // documents' distinct-code count (tools/sim/s4_warm_sim.py: 50 % at 32 tokens / 68 codes, ~70 % at 48 tokens, ~30 % at 240
   // codes per document; measured at 48 tokens: 10.10 k -> 10.47 k queries/s with 70 %).  s4_warm > 0 pins one value.
-  const int s4_warm = ix->tune.s4_warm > 0
-                          ? ix->tune.s4_warm
-                          : (int)std::min(1000.f, std::max(300.f, 500.f + 12.5f * (float)std::max(0, maxLq - 32) -
-                                                                      1.16f * std::max(0.f, ix->ulen_mean - 68.f)));
-  const size_t slot_words = (size_t)(8 * (B + 1) + 1);   // hand-out slots + ticket of one filter launch
-  if (use_filter) {
-    NP_TRY(w.QCU.reserve((size_t)B * KP * RB));
-    NP_TRY(w.ub.reserve((size_t)pool * 2));
-    NP_TRY(w.ub_hist.reserve((size_t)B * NP_UB_BINS * 4));
-    NP_TRY(w.surv_meta.reserve((size_t)pool * 16));
-    NP_TRY(w.n_surv.reserve((size_t)B * 4));
-    NP_TRY(w.ub_thr.reserve((size_t)B * 4));
-    NP_TRY(w.ub_cursor.reserve((size_t)3 * B * 4));
-    NP_TRY(w.xcd_slots.reserve(((size_t)max_rounds * 3 + 1) * slot_words * 4));   // + the zeroth level's S0 launch
-  }
-  if (two_level) {
-    NP_TRY(w.cmaxu.reserve((size_t)B * KP));
-    NP_TRY(w.chist.reserve((size_t)B * 256 * 4));
-    NP_TRY(w.ub2.reserve((size_t)pool * 2));
-    NP_TRY(w.ub_hist2.reserve((size_t)B * NP_UB_BINS * 4));
-    NP_TRY(w.ub_thr2.reserve((size_t)3 * B * 4));   // [B] tau bins, [B] Lambda, [B] Lambda2 (floor of the exact level)
-    NP_TRY(w.list_meta.reserve((size_t)pool * 16));
-    NP_TRY(w.n_l1.reserve((size_t)B * 4));
-    NP_TRY(w.n_l2.reserve((size_t)B * 4));
-    if (use_planes) {
-      NP_TRY(w.planes.reserve((size_t)B * KP * RB));
-      NP_TRY(w.levels.reserve((size_t)B * 16 * 4));
-      NP_TRY(w.hotbits.reserve((size_t)2 * B * (KP / 32) * 4));   // hot bitmap, then the exact level's kept-centroid bitmap
-    }
-  }
+  p.s4_warm = ix->tune.s4_warm > 0
+                  ? ix->tune.s4_warm
+                  : (int)std::min(1000.f, std::max(300.f, 500.f + 12.5f * (float)std::max(0, maxLq - 32) -
+                                                              1.16f * std::max(0.f, ix->ulen_mean - 68.f)));
+  p.slot_words = (size_t)(8 * (B + 1) + 1);
   // Zeroth filter level (np_kernels.h, gain_sweep_kernel): per-document sums of the probed cells' gains prune the candidates
   // before any list block is read.  Only where no centroid_score_threshold is set (the cells a threshold removes would lift
   // the bound's floor above the cut: tools/sim/s3_gain_sim.py), on ascending posting lists (range table built at open), with
   // the bit-plane first level behind it (it takes the candidate ids in any order) and without a subset.
-  bool gain_path = two_level && use_planes && ix->d_ivf_split != nullptr && ix->tune.s3_gain &&
-                   subset_len < 0 && ix->n_docs > 0 && cs->n_sel > 0 && B > 0 &&
-                   (int64_t)std::max(prm.n_ivf_probe, 32) * maxLq <= 16384;   // probed cells per query: the scaled gains of all of
-                                                                               // them must fit a 15-bit accumulator (gain_prep_kernel)
-  const bool gain_possible = gain_path;   // the level's buffers are reserved whenever it MAY run: a first run in the middle of a
-                                          // service's life must not stall every stream on a dozen hipMalloc calls
-  if (gain_path && ix->tune.s3_gain == 1) {
-    // Run / skip policy.  The level costs about the same whatever it prunes -- one sweep of the probed lists (to depth 32; with a
-    // threshold also the cells it removes), a level byte per document and query written and read twice -- and what it buys is the
-    // filter's time per candidate it removes (~0.1 ns of GPU time per 192-byte list block).  The device leaves (candidates, kept,
-    // posting entries swept) of each batch in pinned words; a context reads the words of ITS previous batch here -- never waited
-    // for: a batch still in flight simply has not reported -- and when the removed candidates would not have paid for the level,
-    // the handle skips it for 31 batches (255 when it was not even close) and then tries again.  With a threshold the level starts
-    // skipped (the metric corpus: it does not pay) and is tried for the first time after 511 batches -- a trial costs a short-lived
-    // process more than the level's ~1.3 ms (the first launch of its kernels loads their code: ~40 ms measured inside a 300-batch
-    // bench), a service never notices.  Results do not depend on the decision.
-    const uint64_t key = ((uint64_t)(uint32_t)prm.n_ivf_probe << 40) ^ ((uint64_t)(uint32_t)cs->n_sel << 16) ^ (uint64_t)(uint32_t)LQP ^
-                         ((uint64_t)(prm.has_threshold ? 1u : 0u) << 63);
-    if (ix->gain_key.exchange(key, std::memory_order_relaxed) != key) {
-      ix->gain_run.store(0, std::memory_order_relaxed);
-      ix->gain_skip.store(prm.has_threshold ? 511 : 0, std::memory_order_relaxed);
-    }
-    if (w.h_gain) {
-      const unsigned long long v = __atomic_exchange_n(&w.h_gain[0], 0ull, __ATOMIC_ACQUIRE);
-      const double raw = (double)(v >> 32), kept = (double)(v & 0xFFFFFFFFull), swept = (double)w.h_gain[1];
-      const double block_b = (double)ix->ublock_stride * (double)ix->code_bytes();
-      const double benefit_ms = (raw - kept) * 1e-7 * std::max(1.0, block_b / 192.0);   // 8 ms per 130 M candidates at K = 2^16
-      const double cost_ms = 0.8 * ((double)ix->n_docs / 1e7) * ((double)B / 64.0) + swept * 3e-9;   // passes + ~330 M entries per ms
-      // (a report of a batch with other parameters says nothing about these)
-      if (raw > 0 && w.h_gain_key == key) {
-        if (benefit_ms < cost_ms) {
-          ix->gain_run.store(0, std::memory_order_relaxed);
-          ix->gain_skip.store(benefit_ms > 0.7 * cost_ms ? 31 : 255, std::memory_order_relaxed);
-        } else {
-          ix->gain_run.store(1, std::memory_order_relaxed);
-        }
-      }
-    } else if (hipHostMalloc((void**)&w.h_gain, 64, hipHostMallocDefault) == hipSuccess) {
-      w.h_gain[0] = w.h_gain[1] = 0;
-    } else {
-      w.h_gain = nullptr;
-      (void)hipGetLastError();
-    }
-    if (ix->gain_skip.load(std::memory_order_relaxed) > 0) {
-      ix->gain_skip.fetch_sub(1, std::memory_order_relaxed);
-      gain_path = false;
-    } else {
-      w.h_gain_key = key;
-      // a trial run: the other contexts wait for its report instead of each paying for one
-      if (!ix->gain_run.load(std::memory_order_relaxed)) ix->gain_skip.store(3, std::memory_order_relaxed);
-    }
-  }
+  p.gain_possible = p.two_level && p.use_planes && ix->d_ivf_split != nullptr && ix->tune.s3_gain &&
+                    subset_len < 0 && ix->n_docs > 0 && cs->n_sel > 0 && B > 0 &&
+                    (int64_t)std::max(prm.n_ivf_probe, 32) * maxLq <= 16384;   // probed cells per query: the scaled gains of all
+                                                                               // of them must fit a 15-bit accumulator (gain_prep_kernel)
   // the level probes on its own to depth 32 where the search stops earlier: the bound's floor falls with the depth (np_kernels.h)
   // ... and with a threshold it sweeps the cells the threshold removes too (bound-only): its own probe, without the threshold
-  const int gain_depth = std::max(32, prm.n_ivf_probe);
-  const bool deep_wanted = (prm.n_ivf_probe < gain_depth || prm.has_threshold) && ix->K > gain_depth;
-  const bool gain_deep = gain_path && deep_wanted;
-  if (gain_path && prm.has_threshold && !gain_deep) gain_path = false;
-  const int s0_target = ix->tune.s3_gain_mult * cs->n_sel;
-  // S0 takes whole histogram bins: the marginal bin may hold a few whole posting lists (documents in ONE probed cell share a bound)
+  p.gain_depth = std::max(32, prm.n_ivf_probe);
+  p.deep_wanted = (prm.n_ivf_probe < p.gain_depth || prm.has_threshold) && ix->K > p.gain_depth;
+  p.s0_target = ix->tune.s3_gain_mult * cs->n_sel;
   // S0 takes the bins above the marginal one whole and fills the rest of its slice from the marginal bin (documents in ONE probed
   // cell share a bound: a bin may hold whole posting lists)
-  const int s0cap = s0_target + cs->n_sel;
-  // u32 words of w.gsmall: [0, 4B) base / shift / floor bin / 0, then B each: n_raw, thr0, cut0, n_s0, n_emit, n_direct, round_of0, order0, cursor0,
-  // n_hi, n_hi_emit, n_marg, lcut; 4 words round_tab0; 6 words = 3 x u64 batch report; then (8-byte aligned) cand_base0 i64 [B]
-  const size_t gs_words = (size_t)17 * B + 4 + 8, gs_bytes = (gs_words + (gs_words & 1)) * 4 + (size_t)B * 8;
-  if (gain_possible) {
-    NP_TRY(w.gain.reserve((size_t)B * KP * 2));
-    NP_TRY(w.gsmall.reserve(gs_bytes));
-    NP_TRY(w.ghist.reserve((size_t)B * (256 + NP_UB_BINS) * 4));   // levels of all candidates; exact lower bounds of S0
-    NP_TRY(w.s0_meta.reserve((size_t)B * s0cap * 16));
-    NP_TRY(w.s0_u.reserve((size_t)B * s0cap * 2));
-    NP_TRY(w.gacc.reserve((size_t)B * ix->n_ranges * NP_GAIN_RANGE));   // one level byte per document and query
-    if (deep_wanted) NP_TRY(w.gdeep.reserve(((size_t)B * G + (size_t)B * LQP + (size_t)B + (size_t)B * G + (size_t)B * KP) * 4));
-  }
-  NP_TRY(w.sel_keys.reserve((size_t)B * nsel1 * 8));
-  NP_TRY(w.sel_doc.reserve((size_t)B * nsel1 * 4));
-  NP_TRY(w.nsel.reserve((size_t)B * 4));
-  NP_TRY(w.exact.reserve((size_t)B * nsel1 * 4));
-  NP_TRY(w.out_ids.reserve((size_t)B * topk1 * 8));
-  NP_TRY(w.out_scores.reserve((size_t)B * topk1 * 4));
-  NP_TRY(w.out_keys.reserve((size_t)B * topk1 * 8));
-  NP_TRY(w.out_counts.reserve((size_t)B * 4));
-  NP_TRY(w.ctr.reserve(sizeof(Counters)));
-  NP_TRY(w.misc.reserve(64));
-
-  if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[0], st));
-  {
-    // every small region of the call in ONE launch (a dozen stream memsets were ~50 us per batch)
-    ClearList cl;
-    cl.n = 0;
-    auto add = [&](void* p, size_t bytes, uint32_t fill) {
-      if (bytes == 0) return;
-      cl.p[cl.n] = static_cast<uint32_t*>(p);
-      cl.words[cl.n] = (uint32_t)(bytes / 4);
-      cl.fill[cl.n] = fill;
-      ++cl.n;
-    };
-    static_assert(sizeof(Counters) % 4 == 0, "Counters is cleared by words");
-    add(w.ctr.p, sizeof(Counters), 0);
-    add(w.n_cells.p, (size_t)B * 4, 0);
-    add(w.n_cand.p, (size_t)B * 4, 0);
-    add(w.nsel.p, (size_t)B * 4, 0);
-    add(w.cellbits.p, (size_t)B * G * 4, 0);
-    add(w.tauq.p, (size_t)B * LQP * 4, 0);
-    if (cs->n_sel > 0) add(w.sel_keys.p, (size_t)B * cs->n_sel * 8, 0);
-    if (use_filter && B > 0) {
-      add(w.ub_hist.p, (size_t)B * NP_UB_BINS * 4, 0);
-      add(w.n_surv.p, (size_t)B * 4, 0);
-      add(w.ub_cursor.p, (size_t)3 * B * 4, 0);
-      add(w.xcd_slots.p, ((size_t)max_rounds * 3 + 1) * slot_words * 4, 0xFFFFFFFFu);   // slots and tickets of every launch: -1
-    }
-    if (gain_deep) add(w.gdeep.p, ((size_t)B * G + (size_t)B * LQP + (size_t)B + (size_t)B * G) * 4, 0);   // marks, per-token thresholds, cell counts, kept-cell bitmap
-    if (gain_path) {
-      add(w.gsmall.p, gs_bytes, 0);
-      add(w.ghist.p, (size_t)B * (256 + NP_UB_BINS) * 4, 0);
-    }
-    if (two_level && B > 0) {
-      add(w.chist.p, (size_t)B * 256 * 4, 0);
-      add(w.ub_hist2.p, (size_t)B * NP_UB_BINS * 4, 0);
-      add(w.n_l1.p, (size_t)B * 4, 0);
-      add(w.n_l2.p, (size_t)B * 4, 0);
-    }
-    if (cl.n > 0) clear_regions_kernel<<<128, 256, 0, st>>>(cl);
-  }
-  if (NW > 0 && !ix->tune.s3_slices) NP_HIP(hipMemsetAsync(w.docbits.p, 0, (size_t)B * NW * 4, st));   // mark_slices_kernel writes every word
-  if (use_filter && B > 0 && RB != LQP) NP_HIP(hipMemsetAsync(w.QCU.p, 0, (size_t)B * KP * RB, st));   // row bytes LQP .. RB-1 stay 0
-  if (B == 0) return NP_OK;
-
-  // ---- S1
-  prep_queries_kernel<<<B, 256, 0, st>>>(d_q, d_qoff, ix->dim, LQP, w.Qt.as<float>(), w.Qb.as<__bf16>(),
-                                         w.Qbl.as<__bf16>(), ix->cmax, w.qinv.as<float>(), w.qflag.as<uint32_t>());
+  p.s0cap = p.s0_target + cs->n_sel;
   // split-bf16 S1 (qc_gemm_b3_kernel): opt-in, only where the crate itself leaves the dense path (K > centroid_batch_size)
   // and the caller asked for a reduced-precision mode; precision 0 keeps the exact-f32 chain everywhere
   // (with it the approximate scores stay the GEMM's: the batched path's mat-vec re-scoring -- there to reproduce the
   // reference's non-FMA summation order bit for bit, 1.6 ms of packed-f32 VALU work per batch at K = 2^19 -- has nothing
   // left to reproduce)
-  const bool s1_split = ix->tune.s1_split && prm.precision >= 1 && prm.centroid_batch_size > 0 &&
-                        ix->K > prm.centroid_batch_size && !cs->trace;
-  if (s1_split) {
-    uint8_t* qcu = use_filter ? w.QCU.as<uint8_t>() : nullptr;
-    const unsigned blocks = (unsigned)((ix->KP / 32 + 3) / 4);
-#define NP_GEMM_B3(D)                                                                                                     \
-  qc_gemm_b3_kernel<D><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, w.Qb.as<__bf16>(), w.Qbl.as<__bf16>(), B, LQP, \
-                                               w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, RB, w.qinv.as<float>(), d_qoff)
-    switch (ix->dim) {
-      case 32: NP_GEMM_B3(32); break;
-      case 64: NP_GEMM_B3(64); break;
-      case 96: NP_GEMM_B3(96); break;
-      default: NP_GEMM_B3(128); break;
-    }
-#undef NP_GEMM_B3
-  } else {
-    uint8_t* qcu = use_filter ? w.QCU.as<uint8_t>() : nullptr;
-    const float* qinv = w.qinv.as<float>();
-    switch (ix->dim) {
-      case 32: launch_gemm<32>(st, ix, w.Qt.as<float>(), B, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, RB, qinv, d_qoff); break;
-      case 64: launch_gemm<64>(st, ix, w.Qt.as<float>(), B, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, RB, qinv, d_qoff); break;
-      case 96: launch_gemm<96>(st, ix, w.Qt.as<float>(), B, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, RB, qinv, d_qoff); break;
-      default: launch_gemm<128>(st, ix, w.Qt.as<float>(), B, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, RB, qinv, d_qoff); break;
-    }
-  }
-  if (two_level) {   // per-centroid maxima of the u8 table, their histogram, the hot level's Lambda
-    hot_prep_kernel<<<dim3((unsigned)std::min<int64_t>((KP + 255) / 256, 64), B), 256, 0, st>>>(
-        w.QCU.as<uint8_t>(), ix->K, KP, RB, w.cmaxu.as<uint8_t>(), w.chist.as<uint32_t>());
-    if (!use_planes) hot_lam_kernel<<<B, 256, 0, st>>>(w.chist.as<uint32_t>(), ix->K, ix->tune.s4_hot, w.ub_thr2.as<uint32_t>() + B);
-  }
-  if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[1], st));
-
-  // ---- subset pre-filter (search.rs:350-382); the batched path only filters candidates (:542-545)
-  const bool have_subset = subset_len > 0;
-  const bool batched = prm.centroid_batch_size > 0 && ix->K > prm.centroid_batch_size;  // search.rs:337
-  const bool use_elig = have_subset && !batched;
-  const uint32_t* elig_bits = nullptr;
-  if (have_subset) {
-    NP_TRY(w.subset_bits.reserve((size_t)std::max<int64_t>(NW, 1) * 4));
-    NP_TRY(w.elig.reserve((size_t)G * 4));
-    NP_HIP(hipMemsetAsync(w.subset_bits.p, 0, (size_t)std::max<int64_t>(NW, 1) * 4, st));
-    NP_HIP(hipMemsetAsync(w.elig.p, 0, (size_t)G * 4, st));
-    // a document shard sees only its own documents' codes: the sharded host ORs the shards' bitmaps
-    // (np_hip_subset_eligible + one small all-gather) and hands the global one in
-    const bool local_elig = use_elig && !cs->elig_global;
-    subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(
-        d_subset, subset_len, ix->doc_begin, ix->n_docs, ix->d_doc_offsets, ix->codes(), w.subset_bits.as<uint32_t>(),
-        local_elig ? w.elig.as<uint32_t>() : nullptr);
-    if (use_elig) {
-      elig_bits = cs->elig_global ? cs->elig_global : w.elig.as<uint32_t>();
-      subset_nprobe_kernel<<<1, 256, 0, st>>>(elig_bits, G, prm.n_ivf_probe, ix->N_total, subset_len,
-                                              w.misc.as<int32_t>(), w.misc.as<int32_t>() + 1);
-      // the probe prunes by group maxima: restrict them to the eligible centroids
-      masked_gmax_kernel<<<dim3((unsigned)((G + 3) / 4), B), 256, 0, st>>>(w.QCT.as<float>(), KP, ix->K, LQP, elig_bits,
-                                                                           w.gmax.as<uint32_t>());
-    }
-  }
-
-  // ---- S2
-  if (!cs->empty_subset) {
-    ProbeP pp;
-    pp.QCT = w.QCT.as<float>();
-    pp.gmax = w.gmax.as<uint32_t>();
-    pp.qoff = d_qoff;
-    pp.K = ix->K;
-    pp.KP = KP;
-    pp.LQP = LQP;
-    pp.nprobe = prm.n_ivf_probe;
-    pp.nprobe_dev = use_elig ? w.misc.as<int32_t>() + 1 : nullptr;
-    pp.elig = use_elig ? elig_bits : nullptr;
-    pp.n_elig = use_elig ? w.misc.as<int32_t>() : nullptr;
-    pp.has_thr = prm.has_threshold;
-    pp.thr = prm.centroid_score_threshold;
-    pp.slab = batched ? (int64_t)prm.centroid_batch_size : 0;
-    pp.cellbits = w.cellbits.as<uint32_t>();
-    pp.tauq = w.tauq.as<uint32_t>();
-    pp.cells_tmp = w.cells_tmp.as<uint32_t>();
-    pp.cells = w.cells.as<uint32_t>();
-    pp.n_cells = w.n_cells.as<int32_t>();
-    pp.ctr = w.ctr.as<Counters>();
-    // K <= 65536: the block's group maxima (KP/32 x 4 tokens x 4 B <= 32 KB) are staged in LDS once
-    const size_t gm_lds = (size_t)(KP / 32) * 4 * 4;
-    pp.lds_gm = gm_lds <= 32 * 1024 ? 1 : 0;
-    if (pp.lds_gm) probe_mark_kernel<4><<<dim3((unsigned)(LQP / 4), B), 256, gm_lds, st>>>(pp);
-    else probe_mark_kernel<8><<<dim3((unsigned)(LQP / 8), B), 256, 0, st>>>(pp);
-    probe_finish_kernel<<<dim3(NP_PROBE_NF, B), 256, 0, st>>>(pp);
-    if (gain_deep) {   // the zeroth level's own, deeper probe: bound-only cells beyond the search's
-      ProbeP p2 = pp;
-      uint32_t* gd = w.gdeep.as<uint32_t>();
-      p2.nprobe = gain_depth;
-      p2.has_thr = 0;          // every probed cell: the ones a threshold removes are swept as bound-only cells
-      p2.cellbits = gd;
-      p2.tauq = gd + (size_t)B * G;
-      p2.n_cells = reinterpret_cast<int32_t*>(gd + (size_t)B * G + (size_t)B * LQP);
-      p2.cells = gd + (size_t)2 * B * G + (size_t)B * LQP + (size_t)B;   // (the kept-cell bitmap sits in between)
-      p2.ctr = nullptr;
-      if (p2.lds_gm) probe_mark_kernel<4><<<dim3((unsigned)(LQP / 4), B), 256, gm_lds, st>>>(p2);
-      else probe_mark_kernel<8><<<dim3((unsigned)(LQP / 8), B), 256, 0, st>>>(p2);
-      probe_finish_kernel<<<dim3(NP_PROBE_NF, B), 256, 0, st>>>(p2);
-      if (prm.has_threshold)   // which of them make candidates: the cells the threshold kept
-        cells_to_bits_kernel<<<B, 256, 0, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), KP,
-                                                gd + (size_t)B * G + (size_t)B * LQP + (size_t)B);
-    }
-  }
-  if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[2], st));
-
-  // ---- the filter's launch helper and its loop-invariant parameters (used by the zeroth level before the round plan, and by
-  // every round)
-  const int hshift = RB == 32 ? 2 : (RB == 64 ? 3 : (RB == 128 ? 4 : 5));   // U <= 255 * RB fits NP_UB_BINS << hshift
-  const unsigned nbx = (unsigned)ix->tune.ub_nbx;
-  const bool oob = ix->tune.ub_nt == 2 && KP * RB < ((int64_t)1 << 30);   // the table behind a 32-bit buffer offset
-  // exact u8 bound of the records meta[begin[b] .. begin[b] + count[b]) -> U, histogram (optional)
-  // direct_wpq > 0: a short list per query (S1, about n_sel documents): wpq workgroups per query, every query at once,
-  // instead of one query per XCD at a time (8 hand-out steps of ~25 us each for a handful of claims)
-  // floor: the S2 list of the two-level filter with u16 codes -- rows of the centroids no query token is close to are
-  // skipped, U = the floored upper bound, the histogram counts the lower bound (approx_ub_kernel, FLOOR)
-  const bool can_floor = two_level && use_planes && oob && RB <= 64 && s4_warm < 1000;
-  auto launch_ub_at = [&](const RoundPlan& rpx, int r, int max_rounds, int32_t* sl, int32_t* tk, uint32_t* cursor, const uint4* meta,
-                          const int32_t* begin, const int32_t* count, const int32_t* n_all, uint16_t* U, uint32_t* hist,
-                          int count_tokens, int direct_wpq, bool floor_rows) {
-    const unsigned grid = direct_wpq > 0 ? (unsigned)(B * direct_wpq) : 8 * nbx;
-    if (floor_rows && can_floor) {
-#define NP_LAUNCH_UBF(ROWB, CT)                                                                                               \
-  approx_ub_kernel<ROWB, CT, 2, 1><<<grid, 256, 0, st>>>(                                                                       \
-  w.QCU.as<uint8_t>(), KP, meta, begin, count, n_all, rpx, r, max_rounds, (const CT*)ix->d_ucodes,           \
-  w.qflag.as<uint32_t>(), cs->n_sel, U, hist, hshift, cursor, sl, tk, B, ix->tune.ub_steal, w.ctr.as<Counters>(),      \
-  count_tokens, direct_wpq, ix->tune.ub_static, w.hotbits.as<uint32_t>() + (size_t)B * (KP / 32),                           \
-  w.ub_thr2.as<uint32_t>() + 2 * B, d_qoff)
-      if (!ix->code_wide) {
-        if (RB == 32) NP_LAUNCH_UBF(32, uint16_t);
-        else NP_LAUNCH_UBF(64, uint16_t);
-      } else {
-        if (RB == 32) NP_LAUNCH_UBF(32, uint32_t);
-        else NP_LAUNCH_UBF(64, uint32_t);
-      }
-#undef NP_LAUNCH_UBF
-      return;
-    }
-#define NP_LAUNCH_UB(ROWB, CT, NT)                                                                                        \
-  approx_ub_kernel<ROWB, CT, NT><<<grid, 256, 0, st>>>(w.QCU.as<uint8_t>(), KP, meta, begin, count, n_all,   \
-                                                   rpx, r, max_rounds, (const CT*)ix->d_ucodes, w.qflag.as<uint32_t>(),   \
-                                                   cs->n_sel, U, hist, hshift, cursor, sl, tk, B,                \
-                                                   ix->tune.ub_steal, w.ctr.as<Counters>(), count_tokens, direct_wpq,   \
-                                                   ix->tune.ub_static)
-#define NP_LAUNCH_UB_RB(CT, NT)                 \
-  do {                                          \
-    if (RB == 32) NP_LAUNCH_UB(32, CT, NT);     \
-    else if (RB == 64) NP_LAUNCH_UB(64, CT, NT);   \
-    else if (RB == 128) NP_LAUNCH_UB(128, CT, NT); \
-    else NP_LAUNCH_UB(256, CT, NT);             \
-  } while (0)
-    if (!ix->code_wide) {
-      if (oob) NP_LAUNCH_UB_RB(uint16_t, 2);
-      else if (ix->tune.ub_nt == 1) NP_LAUNCH_UB_RB(uint16_t, 1);
-      else NP_LAUNCH_UB_RB(uint16_t, 0);
-    } else {
-      if (oob) NP_LAUNCH_UB_RB(uint32_t, 2);
-      else if (ix->tune.ub_nt == 1) NP_LAUNCH_UB_RB(uint32_t, 1);
-      else NP_LAUNCH_UB_RB(uint32_t, 0);
-    }
-#undef NP_LAUNCH_UB_RB
-#undef NP_LAUNCH_UB
-  };
-
+  p.s1_split = ix->tune.s1_split && prm.precision >= 1 && prm.centroid_batch_size > 0 &&
+               ix->K > prm.centroid_batch_size && !cs->trace;
+  // subset pre-filter (search.rs:350-382); the batched path only filters candidates (:542-545)
+  p.have_subset = subset_len > 0;
+  p.batched = prm.centroid_batch_size > 0 && ix->K > prm.centroid_batch_size;  // search.rs:337
+  p.use_elig = p.have_subset && !p.batched;
+  p.hshift = RB == 32 ? 2 : (RB == 64 ? 3 : (RB == 128 ? 4 : 5));
+  p.oob = ix->tune.ub_nt == 2 && KP * RB < ((int64_t)1 << 30);
+  p.can_floor = p.two_level && p.use_planes && p.oob && RB <= 64 && p.s4_warm < 1000;
   // slack of the bound (np_kernels.h); the batched path's mat-vec scores differ from the GEMM's by < 1 more unit
   // (per query the bracket is Lq + 2 with its OWN token count: padding tokens contribute exactly 0 to both sides, so the
   // slice's longest query bounds it -- 48-token queries in 64-token rows keep 50, not 66)
   // (that unit count follows gcut_kernel's bound e >= |G - R| = 1.5 (152 Lq + 2 Lq^2) 2^-24 s, in table units of s / 254:
   // below one unit up to 64 tokens, four at 256)
   const float lqf = (float)maxLq;
-  const int slack = maxLq + 2 +
-                    (batched ? std::max(1, (int)std::ceil(1.5f * (152.0f * lqf + 2.0f * lqf * lqf) * 5.9604645e-8f * 254.0f)) : 0);
-  // ---- S3: posting-list union (bitmap), per-chunk counts, round plan
+  p.slack = maxLq + 2 +
+            (p.batched ? std::max(1, (int)std::ceil(1.5f * (152.0f * lqf + 2.0f * lqf * lqf) * 5.9604645e-8f * 254.0f)) : 0);
+  p.have_cands = !cs->empty_subset && ix->n_docs > 0;
+  // two-level filter: bare ids only -- the hot level finds a document's list block from the id and writes the 16-B records
+  // itself (no record gather here: a 128-B line per candidate at 1.9 % density was this kernel's whole cost)
+  p.ids_only = p.two_level && ix->ublock_stride > 0;
+  return NP_OK;
+}
+
+// Run / skip policy of the zeroth level; true: this pass runs it.  The level costs about the same whatever it prunes -- one sweep
+// of the probed lists (to depth 32; with a threshold also the cells it removes), a level byte per document and query written and
+// read twice -- and what it buys is the filter's time per candidate it removes (~0.1 ns of GPU time per 192-byte list block).
+// The device leaves (candidates, kept, posting entries swept) of each batch in pinned words; a context reads the words of ITS
+// previous batch here -- never waited for: a batch still in flight simply has not reported -- and when the removed candidates
+// would not have paid for the level, the handle skips it for 31 batches (255 when it was not even close) and then tries again.
+// With a threshold the level starts skipped (the metric corpus: it does not pay) and is tried for the first time after 511
+// batches -- a trial costs a short-lived process more than the level's ~1.3 ms (the first launch of its kernels loads their
+// code: ~40 ms measured inside a 300-batch bench), a service never notices.  Results do not depend on the decision.
+static bool gain_level_runs(const DeviceIndex* ix, Workspace& w, const CallState* cs, int B, int LQP) {
+  const np_search_params& prm = cs->prm;
+  const uint64_t key = ((uint64_t)(uint32_t)prm.n_ivf_probe << 40) ^ ((uint64_t)(uint32_t)cs->n_sel << 16) ^ (uint64_t)(uint32_t)LQP ^
+                       ((uint64_t)(prm.has_threshold ? 1u : 0u) << 63);
+  if (ix->gain_key.exchange(key, std::memory_order_relaxed) != key) {
+    ix->gain_run.store(0, std::memory_order_relaxed);
+    ix->gain_skip.store(prm.has_threshold ? 511 : 0, std::memory_order_relaxed);
+  }
+  if (w.h_gain) {
+    const unsigned long long v = __atomic_exchange_n(&w.h_gain[0], 0ull, __ATOMIC_ACQUIRE);
+    const double raw = (double)(v >> 32), kept = (double)(v & 0xFFFFFFFFull), swept = (double)w.h_gain[1];
+    const double block_b = (double)ix->ublock_stride * (double)ix->code_bytes();
+    const double benefit_ms = (raw - kept) * 1e-7 * std::max(1.0, block_b / 192.0);   // 8 ms per 130 M candidates at K = 2^16
+    const double cost_ms = 0.8 * ((double)ix->n_docs / 1e7) * ((double)B / 64.0) + swept * 3e-9;   // passes + ~330 M entries per ms
+    // (a report of a batch with other parameters says nothing about these)
+    if (raw > 0 && w.h_gain_key == key) {
+      if (benefit_ms < cost_ms) {
+        ix->gain_run.store(0, std::memory_order_relaxed);
+        ix->gain_skip.store(benefit_ms > 0.7 * cost_ms ? 31 : 255, std::memory_order_relaxed);
+      } else {
+        ix->gain_run.store(1, std::memory_order_relaxed);
+      }
+    }
+  } else if (hipHostMalloc((void**)&w.h_gain, 64, hipHostMallocDefault) == hipSuccess) {
+    w.h_gain[0] = w.h_gain[1] = 0;
+  } else {
+    w.h_gain = nullptr;
+    (void)hipGetLastError();
+  }
+  if (ix->gain_skip.load(std::memory_order_relaxed) > 0) {
+    ix->gain_skip.fetch_sub(1, std::memory_order_relaxed);
+    return false;
+  }
+  w.h_gain_key = key;
+  // a trial run: the other contexts wait for its report instead of each paying for one
+  if (!ix->gain_run.load(std::memory_order_relaxed)) ix->gain_skip.store(3, std::memory_order_relaxed);
+  return true;
+}
+
+// Whether the zeroth level runs in this pass, and with its own deeper probe
+static void settle_zeroth_level(const DeviceIndex* ix, Workspace& w, const CallState* cs, PassPlan& p) {
+  p.gain_path = p.gain_possible && (ix->tune.s3_gain != 1 || gain_level_runs(ix, w, cs, p.B, p.LQP));
+  p.gain_deep = p.gain_path && p.deep_wanted;
+  if (p.gain_path && cs->prm.has_threshold && !p.gain_deep) p.gain_path = false;
+}
+
+// Every device buffer of the pass, before its first launch
+static int reserve_pass(const DeviceIndex* ix, const CallState* cs, const PassPlan& p, Workspace& w) {
+  const size_t B = (size_t)p.B, KP = (size_t)p.KP, G = (size_t)p.G, LQP = (size_t)p.LQP, dim = (size_t)ix->dim;
+  const size_t pool = (size_t)p.pool, RB = (size_t)p.RB;
+  const size_t nsel1 = (size_t)std::max(cs->n_sel, 1), topk1 = (size_t)std::max(cs->prm.top_k, 1);
+  const size_t nw1 = (size_t)std::max<int64_t>(p.NW, 1);
+  if (ix->ldim != ix->dim) NP_TRY(w.qpad.reserve((size_t)std::max<int64_t>(p.rows, 1) * dim * 4));
+  NP_TRY(w.Qt.reserve(B * dim * LQP * 4));
+  NP_TRY(w.Qb.reserve(B * dim * LQP * 2));
+  NP_TRY(w.Qbl.reserve(B * dim * LQP * 2));
+  NP_TRY(w.QCT.reserve(B * KP * LQP * 4));
+  NP_TRY(w.gmax.reserve(B * G * LQP * 4));
+  NP_TRY(w.cellbits.reserve(B * G * 4));
+  NP_TRY(w.tauq.reserve(B * LQP * 4));
+  NP_TRY(w.cells_tmp.reserve(B * KP * 4));
+  NP_TRY(w.cells.reserve(B * KP * 4));
+  NP_TRY(w.n_cells.reserve(B * 4));
+  NP_TRY(w.docbits.reserve(B * nw1 * 4));
+  NP_TRY(w.chunk_counts.reserve(B * (size_t)std::max(p.nchunks, 1) * 4));
+  NP_TRY(w.cand.reserve(pool * 4));
+  NP_TRY(w.cand_meta.reserve(pool * 16));
+  NP_TRY(w.approx.reserve(pool * 4));
+  NP_TRY(w.n_cand.reserve(B * 4));
+  NP_TRY(w.cand_base.reserve(B * 8));
+  NP_TRY(w.round_of.reserve(B * 4));
+  NP_TRY(w.round_tab.reserve((size_t)(2 * p.max_rounds + 1) * 4));
+  NP_TRY(w.q_order.reserve(B * 4));
+  NP_TRY(w.n_list2.reserve(B * 4));
+  NP_TRY(w.qinv.reserve(B * 4));
+  NP_TRY(w.qflag.reserve(B * 4));
+  if (p.use_filter) {
+    NP_TRY(w.QCU.reserve(B * KP * RB));
+    NP_TRY(w.ub.reserve(pool * 2));
+    NP_TRY(w.ub_hist.reserve(B * NP_UB_BINS * 4));
+    NP_TRY(w.surv_meta.reserve(pool * 16));
+    NP_TRY(w.n_surv.reserve(B * 4));
+    NP_TRY(w.ub_thr.reserve(B * 4));
+    NP_TRY(w.ub_cursor.reserve(3 * B * 4));
+    NP_TRY(w.xcd_slots.reserve(((size_t)p.max_rounds * 3 + 1) * p.slot_words * 4));   // + the zeroth level's S0 launch
+  }
+  if (p.two_level) {
+    NP_TRY(w.cmaxu.reserve(B * KP));
+    NP_TRY(w.chist.reserve(B * 256 * 4));
+    NP_TRY(w.ub2.reserve(pool * 2));
+    NP_TRY(w.ub_hist2.reserve(B * NP_UB_BINS * 4));
+    NP_TRY(w.ub_thr2.reserve(3 * B * 4));   // [B] tau bins, [B] Lambda, [B] Lambda2 (floor of the exact level)
+    NP_TRY(w.list_meta.reserve(pool * 16));
+    NP_TRY(w.n_l1.reserve(B * 4));
+    NP_TRY(w.n_l2.reserve(B * 4));
+    if (p.use_planes) {
+      NP_TRY(w.planes.reserve(B * KP * RB));
+      NP_TRY(w.levels.reserve(B * 16 * 4));
+      NP_TRY(w.hotbits.reserve(2 * B * (KP / 32) * 4));   // hot bitmap, then the exact level's kept-centroid bitmap
+    }
+  }
+  if (p.gain_possible) {   // (a first run in the middle of a service's life must not stall every stream on a dozen hipMalloc calls)
+    NP_TRY(w.gain.reserve(B * KP * 2));
+    NP_TRY(w.gsmall.reserve(GSmall::bytes(p.B)));
+    NP_TRY(w.ghist.reserve(B * (256 + NP_UB_BINS) * 4));   // levels of all candidates; exact lower bounds of S0
+    NP_TRY(w.s0_meta.reserve(B * (size_t)p.s0cap * 16));
+    NP_TRY(w.s0_u.reserve(B * (size_t)p.s0cap * 2));
+    NP_TRY(w.gacc.reserve(B * (size_t)ix->n_ranges * NP_GAIN_RANGE));   // one level byte per document and query
+    if (p.deep_wanted) NP_TRY(w.gdeep.reserve(GDeep::bytes(p)));
+  }
+  NP_TRY(w.sel_keys.reserve(B * nsel1 * 8));
+  NP_TRY(w.sel_doc.reserve(B * nsel1 * 4));
+  NP_TRY(w.nsel.reserve(B * 4));
+  NP_TRY(w.exact.reserve(B * nsel1 * 4));
+  NP_TRY(w.out_ids.reserve(B * topk1 * 8));
+  NP_TRY(w.out_scores.reserve(B * topk1 * 4));
+  NP_TRY(w.out_keys.reserve(B * topk1 * 8));
+  NP_TRY(w.out_counts.reserve(B * 4));
+  NP_TRY(w.ctr.reserve(sizeof(Counters)));
+  NP_TRY(w.misc.reserve(64));
+  if (p.have_subset) {
+    NP_TRY(w.subset_bits.reserve(nw1 * 4));
+    NP_TRY(w.elig.reserve(G * 4));
+  }
+  return NP_OK;
+}
+
+// ---- one pass of S1..S5: its stages, in stream order ----------------------------------------------------------------------
+struct Pass {
+  const DeviceIndex* ix;
+  CallState* cs;
+  Workspace& w;
+  const PassPlan& p;
+  hipStream_t st;
+  const float* d_q;         // storage rows, absolute offsets
+  const int32_t* d_qoff;
+  const int64_t* d_subset;
+  int64_t subset_len;
+
+  int clear() const;
+  void s1() const;
+  int subset() const;
+  void s2() const;
+  RoundPlan round_plan() const;
+  int zeroth_level(const RoundPlan& rp, GainP& gp) const;
+  int s3_plan(const RoundPlan& rp) const;
+  int rounds(const RoundPlan& rp, const GainP& gp) const;
+  int round(int r, const RoundPlan& rp, const GainP& gp, SelectP sp) const;
+  int single_level_cut(int r, const RoundPlan& rp) const;
+  int two_level_cut(int r, const RoundPlan& rp) const;
+  int hot_level(int r, const RoundPlan& rp) const;
+  template <int RB, class CT, int LPD, int PF, int DPI, int QM, int WPB = 4>
+  int hotp(int r, const RoundPlan& rp, unsigned nbx) const;
+  int ub_bounds(const RoundPlan& rpx, int r, int max_rounds, int32_t* slots, uint32_t* cursor, const uint4* meta,
+                const int32_t* begin, const int32_t* count, const int32_t* n_all, uint16_t* U, uint32_t* hist,
+                int count_tokens, int direct_wpq, bool floor_rows) const;
+  // hand-out state of filter launch i (round r's three levels at 3 r .. 3 r + 2, the zeroth level's S0 launch last): slots = -1
+  // (empty), then the ticket (-1)
+  int32_t* slots(size_t i) const { return w.xcd_slots.as<int32_t>() + i * p.slot_words; }
+  uint32_t* cursor(int lvl) const { return w.ub_cursor.as<uint32_t>() + (size_t)lvl * p.B; }
+  unsigned n_cut() const { return (unsigned)std::min<int64_t>(ix->tune.ub_ncut, std::max<int64_t>(1, ix->n_docs / 16384)); }
+};
+
+// every small region of the call in ONE launch (a dozen stream memsets were ~50 us per batch)
+int Pass::clear() const {
+  const int B = p.B;
+  ClearList cl;
+  cl.n = 0;
+  auto add = [&](void* ptr, size_t bytes, uint32_t fill) {
+    if (bytes == 0) return;
+    cl.p[cl.n] = static_cast<uint32_t*>(ptr);
+    cl.words[cl.n] = (uint32_t)(bytes / 4);
+    cl.fill[cl.n] = fill;
+    ++cl.n;
+  };
+  static_assert(sizeof(Counters) % 4 == 0, "Counters is cleared by words");
+  add(w.ctr.p, sizeof(Counters), 0);
+  add(w.n_cells.p, (size_t)B * 4, 0);
+  add(w.n_cand.p, (size_t)B * 4, 0);
+  add(w.nsel.p, (size_t)B * 4, 0);
+  add(w.cellbits.p, (size_t)B * p.G * 4, 0);
+  add(w.tauq.p, (size_t)B * p.LQP * 4, 0);
+  if (cs->n_sel > 0) add(w.sel_keys.p, (size_t)B * cs->n_sel * 8, 0);
+  if (p.use_filter && B > 0) {
+    add(w.ub_hist.p, (size_t)B * NP_UB_BINS * 4, 0);
+    add(w.n_surv.p, (size_t)B * 4, 0);
+    add(w.ub_cursor.p, (size_t)3 * B * 4, 0);
+    add(w.xcd_slots.p, ((size_t)p.max_rounds * 3 + 1) * p.slot_words * 4, 0xFFFFFFFFu);   // slots and tickets of every launch: -1
+  }
+  if (p.gain_deep) add(w.gdeep.p, GDeep::clear_bytes(p), 0);   // marks, per-token thresholds, cell counts, kept-cell bitmap
+  if (p.gain_path) {
+    add(w.gsmall.p, GSmall::bytes(B), 0);
+    add(w.ghist.p, (size_t)B * (256 + NP_UB_BINS) * 4, 0);
+  }
+  if (p.two_level && B > 0) {
+    add(w.chist.p, (size_t)B * 256 * 4, 0);
+    add(w.ub_hist2.p, (size_t)B * NP_UB_BINS * 4, 0);
+    add(w.n_l1.p, (size_t)B * 4, 0);
+    add(w.n_l2.p, (size_t)B * 4, 0);
+  }
+  if (cl.n > 0) clear_regions_kernel<<<128, 256, 0, st>>>(cl);
+  if (p.NW > 0 && !ix->tune.s3_slices) NP_HIP(hipMemsetAsync(w.docbits.p, 0, (size_t)B * p.NW * 4, st));   // mark_slices_kernel writes every word
+  if (p.use_filter && B > 0 && p.RB != p.LQP) NP_HIP(hipMemsetAsync(w.QCU.p, 0, (size_t)B * p.KP * p.RB, st));   // row bytes LQP .. RB-1 stay 0
+  return NP_OK;
+}
+
+// ---- S1: query prep, Q.C^T (dense or split-bf16 GEMM), the u8 table's per-centroid maxima
+void Pass::s1() const {
+  const int B = p.B;
+  prep_queries_kernel<<<B, 256, 0, st>>>(d_q, d_qoff, ix->dim, p.LQP, w.Qt.as<float>(), w.Qb.as<__bf16>(),
+                                         w.Qbl.as<__bf16>(), ix->cmax, w.qinv.as<float>(), w.qflag.as<uint32_t>());
+  uint8_t* qcu = p.use_filter ? w.QCU.as<uint8_t>() : nullptr;
+  if (p.s1_split) {
+    const unsigned blocks = (unsigned)((ix->KP / 32 + 3) / 4);
+    with_dim(ix->dim, [&](auto DIM) {
+      qc_gemm_b3_kernel<DIM><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, w.Qb.as<__bf16>(), w.Qbl.as<__bf16>(), B,
+                                                     p.LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, p.RB,
+                                                     w.qinv.as<float>(), d_qoff);
+    });
+  } else {
+    launch_gemm(st, ix, w.Qt.as<float>(), B, p.LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, p.RB, w.qinv.as<float>(),
+                d_qoff);
+  }
+  if (p.two_level) {   // per-centroid maxima of the u8 table, their histogram, the hot level's Lambda
+    hot_prep_kernel<<<dim3((unsigned)std::min<int64_t>((p.KP + 255) / 256, 64), B), 256, 0, st>>>(
+        w.QCU.as<uint8_t>(), ix->K, p.KP, p.RB, w.cmaxu.as<uint8_t>(), w.chist.as<uint32_t>());
+    if (!p.use_planes)
+      hot_lam_kernel<<<B, 256, 0, st>>>(w.chist.as<uint32_t>(), ix->K, ix->tune.s4_hot, w.ub_thr2.as<uint32_t>() + B);
+  }
+}
+
+// ---- subset pre-filter (search.rs:350-382); the batched path only filters candidates (:542-545)
+int Pass::subset() const {
+  if (!p.have_subset) return NP_OK;
+  NP_HIP(hipMemsetAsync(w.subset_bits.p, 0, (size_t)std::max<int64_t>(p.NW, 1) * 4, st));
+  NP_HIP(hipMemsetAsync(w.elig.p, 0, (size_t)p.G * 4, st));
+  // a document shard sees only its own documents' codes: the sharded host ORs the shards' bitmaps
+  // (np_hip_subset_eligible + one small all-gather) and hands the global one in
+  const bool local_elig = p.use_elig && !cs->elig_global;
+  subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(
+      d_subset, subset_len, ix->doc_begin, ix->n_docs, ix->d_doc_offsets, ix->codes(), w.subset_bits.as<uint32_t>(),
+      local_elig ? w.elig.as<uint32_t>() : nullptr);
+  if (p.use_elig) {
+    const uint32_t* elig_bits = cs->elig_global ? cs->elig_global : w.elig.as<uint32_t>();
+    subset_nprobe_kernel<<<1, 256, 0, st>>>(elig_bits, p.G, cs->prm.n_ivf_probe, ix->N_total, subset_len,
+                                            w.misc.as<int32_t>(), w.misc.as<int32_t>() + 1);
+    // the probe prunes by group maxima: restrict them to the eligible centroids
+    masked_gmax_kernel<<<dim3((unsigned)((p.G + 3) / 4), p.B), 256, 0, st>>>(w.QCT.as<float>(), p.KP, ix->K, p.LQP, elig_bits,
+                                                                             w.gmax.as<uint32_t>());
+  }
+  return NP_OK;
+}
+
+// ---- S2: per-token top-nprobe, threshold, cell list; then the zeroth level's own deeper probe
+void Pass::s2() const {
+  if (cs->empty_subset) return;
+  const int B = p.B;
+  const np_search_params& prm = cs->prm;
+  ProbeP pp;
+  pp.QCT = w.QCT.as<float>();
+  pp.gmax = w.gmax.as<uint32_t>();
+  pp.qoff = d_qoff;
+  pp.K = ix->K;
+  pp.KP = p.KP;
+  pp.LQP = p.LQP;
+  pp.nprobe = prm.n_ivf_probe;
+  pp.nprobe_dev = p.use_elig ? w.misc.as<int32_t>() + 1 : nullptr;
+  pp.elig = p.use_elig ? (cs->elig_global ? cs->elig_global : w.elig.as<uint32_t>()) : nullptr;
+  pp.n_elig = p.use_elig ? w.misc.as<int32_t>() : nullptr;
+  pp.has_thr = prm.has_threshold;
+  pp.thr = prm.centroid_score_threshold;
+  pp.slab = p.batched ? (int64_t)prm.centroid_batch_size : 0;
+  pp.cellbits = w.cellbits.as<uint32_t>();
+  pp.tauq = w.tauq.as<uint32_t>();
+  pp.cells_tmp = w.cells_tmp.as<uint32_t>();
+  pp.cells = w.cells.as<uint32_t>();
+  pp.n_cells = w.n_cells.as<int32_t>();
+  pp.ctr = w.ctr.as<Counters>();
+  // K <= 65536: the block's group maxima (KP/32 x 4 tokens x 4 B <= 32 KB) are staged in LDS once
+  const size_t gm_lds = (size_t)(p.KP / 32) * 4 * 4;
+  pp.lds_gm = gm_lds <= 32 * 1024 ? 1 : 0;
+  auto probe = [&](const ProbeP& pr) {
+    if (pr.lds_gm) probe_mark_kernel<4><<<dim3((unsigned)(p.LQP / 4), B), 256, gm_lds, st>>>(pr);
+    else probe_mark_kernel<8><<<dim3((unsigned)(p.LQP / 8), B), 256, 0, st>>>(pr);
+    probe_finish_kernel<<<dim3(NP_PROBE_NF, B), 256, 0, st>>>(pr);
+  };
+  probe(pp);
+  if (!p.gain_deep) return;
+  // the zeroth level's own, deeper probe: bound-only cells beyond the search's
+  const GDeep gd(w.gdeep.p, p);
+  ProbeP p2 = pp;
+  p2.nprobe = p.gain_depth;
+  p2.has_thr = 0;          // every probed cell: the ones a threshold removes are swept as bound-only cells
+  p2.cellbits = gd.marks;
+  p2.tauq = gd.tauq;
+  p2.n_cells = gd.n_cells;
+  p2.cells = gd.cells;
+  p2.ctr = nullptr;
+  probe(p2);
+  if (prm.has_threshold)   // which of them make candidates: the cells the threshold kept
+    cells_to_bits_kernel<<<B, 256, 0, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP, gd.kept);
+}
+
+RoundPlan Pass::round_plan() const {
   RoundPlan rp;
   rp.n_cand = w.n_cand.as<int32_t>();
   rp.cand_base = w.cand_base.as<int64_t>();
   rp.round_of = w.round_of.as<int32_t>();
   rp.round_tab = w.round_tab.as<int32_t>();
   rp.order = w.q_order.as<int32_t>();
-  const bool have_cands = !cs->empty_subset && ix->n_docs > 0;
-  GainP gp{};
-  if (have_cands && gain_path) {
-    uint32_t* gs = w.gsmall.as<uint32_t>();
-    uint32_t* g_base = gs;
-    int32_t* g_nraw = reinterpret_cast<int32_t*>(gs + 4 * B);
-    uint32_t* g_thr0 = gs + 5 * B;
-    uint32_t* g_cut0 = gs + 6 * B;
-    int32_t* g_ns0 = reinterpret_cast<int32_t*>(gs + 7 * B);
-    int32_t* g_nemit = reinterpret_cast<int32_t*>(gs + 8 * B);
-    int32_t* g_ndirect = reinterpret_cast<int32_t*>(gs + 9 * B);
-    uint32_t* g_cursor0 = gs + 12 * B;
-    RoundPlan rp0;          // the S0 launch: one round, identity order, slices of s0cap records
-    rp0.n_cand = g_ns0;
-    rp0.round_of = reinterpret_cast<int32_t*>(gs + 10 * B);
-    rp0.order = reinterpret_cast<int32_t*>(gs + 11 * B);
-    int32_t* g_nhi = reinterpret_cast<int32_t*>(gs + 13 * B);
-    int32_t* g_nhi_emit = reinterpret_cast<int32_t*>(gs + 14 * B);
-    int32_t* g_nmarg = reinterpret_cast<int32_t*>(gs + 15 * B);
-    uint32_t* g_lcut = gs + 16 * B;
-    rp0.round_tab = reinterpret_cast<int32_t*>(gs + 17 * B);
-    unsigned long long* g_report = reinterpret_cast<unsigned long long*>(gs + ((17 * (size_t)B + 4 + 1) & ~(size_t)1));
-    rp0.cand_base = reinterpret_cast<int64_t*>(gs + gs_words + (gs_words & 1));
-    uint32_t* hist0 = w.ghist.as<uint32_t>();
-    uint32_t* hist_s0 = hist0 + (size_t)B * 256;
-    const uint32_t* g_tauq = w.tauq.as<uint32_t>();
-    gp.cells = w.cells.as<uint32_t>();
-    gp.n_cells = w.n_cells.as<int32_t>();
-    if (gain_deep) {
-      const uint32_t* gd = w.gdeep.as<uint32_t>();
-      g_tauq = gd + (size_t)B * G;
-      gp.n_cells = reinterpret_cast<const int32_t*>(gd + (size_t)B * G + (size_t)B * LQP);
-      gp.cells = gd + (size_t)2 * B * G + (size_t)B * LQP + (size_t)B;
-    }
-    // the cells whose documents are candidates: the search's own marks, or -- with a threshold -- the cells it kept
-    const uint32_t* g_real = !gain_deep ? nullptr
-                             : (prm.has_threshold ? w.gdeep.as<uint32_t>() + (size_t)B * G + (size_t)B * LQP + (size_t)B : w.cellbits.as<uint32_t>());
-    gp.KP = KP;
-    gp.ivf_off = ix->d_ivf_offsets;
-    gp.ivf = ix->d_ivf;
-    gp.split = ix->d_ivf_split;
-    gp.R1 = ix->n_ranges + 1;
-    gp.gain = w.gain.as<uint16_t>();
-    gp.gbase = g_base;
-    gp.hshift = hshift;
-    gp.hist0 = hist0;
-    gp.n_raw = g_nraw;
-    gp.thr = g_thr0;
-    gp.s0_meta = w.s0_meta.as<uint4>();
-    gp.s0cap = s0cap;
-    gp.ucodes = ix->d_ucodes;
-    gp.code_wide = ix->code_wide;
-    gp.ublock_stride = ix->ublock_stride;
-    gp.ovf_base = (int64_t)ix->n_docs * ix->ublock_stride;
-    gp.cand = w.cand.as<uint32_t>();
-    gp.n_emit = g_nemit;
-    gp.rp = rp;
-    gp.ctr = w.ctr.as<Counters>();
-    gp.lvl = w.gacc.as<uint8_t>();
-    gp.n_ranges = ix->n_ranges;
-    gp.n_hi = g_nhi;
-    gp.n_marg = g_nmarg;
-    const size_t glds = (size_t)NP_GAIN_RANGE * 2;
-    NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
-    if (RB == 32)
-      gain_prep_kernel<32><<<B, 256, 0, st>>>(w.QCU.as<uint8_t>(), KP, gp.cells, gp.n_cells, g_tauq, LQP, w.qinv.as<float>(),
-                                              d_qoff, w.gain.as<uint16_t>(), g_base, B, s0cap, rp0, hshift, g_real);
-    else
-      gain_prep_kernel<64><<<B, 256, 0, st>>>(w.QCU.as<uint8_t>(), KP, gp.cells, gp.n_cells, g_tauq, LQP, w.qinv.as<float>(),
-                                              d_qoff, w.gain.as<uint16_t>(), g_base, B, s0cap, rp0, hshift, g_real);
-    const dim3 ggrid((unsigned)ix->n_ranges, (unsigned)B), egrid((unsigned)ix->n_ranges, (unsigned)B);
-    gain_sweep_kernel<<<ggrid, 1024, glds, st>>>(gp);                                         // accumulators, histogram of U0, counts
-    gain_thr_kernel<<<B, 64, 0, st>>>(hist0, s0_target, s0cap, g_nraw, w.qflag.as<uint32_t>(), g_thr0, g_nhi, g_ns0);
-    gp.n_emit = g_nhi_emit;
-    gain_emit_kernel<1><<<egrid, 256, 0, st>>>(gp, 0);                                        // S0: records of the best bounds
-    gp.n_emit = g_nemit;
-    {
-      int32_t* sl0 = w.xcd_slots.as<int32_t>() + (size_t)max_rounds * 3 * slot_words;
-      launch_ub_at(rp0, 0, 1, sl0, sl0 + 8 * (B + 1), g_cursor0, w.s0_meta.as<uint4>(), nullptr, g_ns0, g_ns0, w.s0_u.as<uint16_t>(), hist_s0,
-                   0, ix->tune.s3_gain_direct, false);                                        // exact bounds of S0 (histogram: lower bounds)
-    }
-    ub_thr_kernel<<<B, 256, 0, st>>>(hist_s0, hshift, slack, cs->n_sel, g_ns0, rp0, 0, w.qflag.as<uint32_t>(), g_cut0);   // tau0 - slack
-    gain_count_kernel<<<B, 64, 0, st>>>(g_cut0, hist0, g_base, g_nraw, g_lcut, g_ndirect, w.ctr.as<Counters>(),
-                                        ix->tune.s3_gain == 1 ? w.h_gain : nullptr, g_report, B);   // the cut in levels, candidates kept
-    plan_rounds_kernel<<<1, 256, 0, st>>>(nullptr, 0, B, pool, max_rounds, rp, w.ctr.as<Counters>(), g_ndirect);
-    gp.thr = g_lcut;
+  return rp;
+}
+
+// The exact u8 bound (approx_ub_kernel) of the records meta[begin[b] .. begin[b] + count[b]) -> U, histogram (optional).
+// direct_wpq > 0: a short list per query (S1, about n_sel documents): wpq workgroups per query, every query at once,
+// instead of one query per XCD at a time (8 hand-out steps of ~25 us each for a handful of claims)
+// floor: the S2 list of the two-level filter with u16 codes -- rows of the centroids no query token is close to are
+// skipped, U = the floored upper bound, the histogram counts the lower bound (approx_ub_kernel, FLOOR)
+int Pass::ub_bounds(const RoundPlan& rpx, int r, int max_rounds, int32_t* sl, uint32_t* cur, const uint4* meta,
+                    const int32_t* begin, const int32_t* count, const int32_t* n_all, uint16_t* U, uint32_t* hist,
+                    int count_tokens, int direct_wpq, bool floor_rows) const {
+  const int B = p.B;
+  const unsigned grid = direct_wpq > 0 ? (unsigned)(B * direct_wpq) : 8 * (unsigned)ix->tune.ub_nbx;
+  const int nt = p.oob ? 2 : (ix->tune.ub_nt == 1 ? 1 : 0);
+  int32_t* tk = sl + 8 * (B + 1);
+  with_codes(ix->code_wide, [&](auto ct) {
+    using CT = decltype(ct);
+    with_rowb(p.RB, [&](auto RB) {
+      with_int<2, 1, 0>(nt, [&](auto NT) {
+        with_bool(floor_rows && p.can_floor, [&](auto FLOOR) {
+          if constexpr (!FLOOR || (NT == 2 && RB <= 64))   // (can_floor: oob, RB <= 64)
+            approx_ub_kernel<RB, CT, NT, FLOOR><<<grid, 256, 0, st>>>(
+                w.QCU.as<uint8_t>(), p.KP, meta, begin, count, n_all, rpx, r, max_rounds, (const CT*)ix->d_ucodes,
+                w.qflag.as<uint32_t>(), cs->n_sel, U, hist, p.hshift, cur, sl, tk, B, ix->tune.ub_steal, w.ctr.as<Counters>(),
+                count_tokens, direct_wpq, ix->tune.ub_static,
+                FLOOR ? w.hotbits.as<uint32_t>() + (size_t)B * (p.KP / 32) : nullptr,
+                FLOOR ? w.ub_thr2.as<uint32_t>() + 2 * B : nullptr, FLOOR ? d_qoff : nullptr);
+        });
+      });
+    });
+  });
+  return NP_OK;
+}
+
+// ---- the zeroth filter level (gain_sweep_kernel and its passes), then the round plan of the candidates it keeps
+int Pass::zeroth_level(const RoundPlan& rp, GainP& gp) const {
+  const int B = p.B;
+  const GSmall g(w.gsmall.p, B);
+  RoundPlan rp0;          // the S0 launch: one round, identity order, slices of s0cap records
+  rp0.n_cand = g.n_s0;
+  rp0.round_of = g.round_of0;
+  rp0.order = g.order0;
+  rp0.round_tab = g.round_tab0;
+  rp0.cand_base = g.cand_base0;
+  uint32_t* hist0 = w.ghist.as<uint32_t>();
+  uint32_t* hist_s0 = hist0 + (size_t)B * 256;
+  const uint32_t* g_tauq = w.tauq.as<uint32_t>();
+  gp.cells = w.cells.as<uint32_t>();
+  gp.n_cells = w.n_cells.as<int32_t>();
+  // the cells whose documents are candidates: the search's own marks, or -- with a threshold -- the cells it kept
+  const uint32_t* g_real = nullptr;
+  if (p.gain_deep) {
+    const GDeep gd(w.gdeep.p, p);
+    g_tauq = gd.tauq;
+    gp.n_cells = gd.n_cells;
+    gp.cells = gd.cells;
+    g_real = cs->prm.has_threshold ? gd.kept : w.cellbits.as<uint32_t>();
   }
-  if (have_cands && !gain_path) {
+  gp.KP = p.KP;
+  gp.ivf_off = ix->d_ivf_offsets;
+  gp.ivf = ix->d_ivf;
+  gp.split = ix->d_ivf_split;
+  gp.R1 = ix->n_ranges + 1;
+  gp.gain = w.gain.as<uint16_t>();
+  gp.gbase = g.base;
+  gp.hshift = p.hshift;
+  gp.hist0 = hist0;
+  gp.n_raw = g.n_raw;
+  gp.thr = g.thr0;
+  gp.s0_meta = w.s0_meta.as<uint4>();
+  gp.s0cap = p.s0cap;
+  gp.ucodes = ix->d_ucodes;
+  gp.code_wide = ix->code_wide;
+  gp.ublock_stride = ix->ublock_stride;
+  gp.ovf_base = (int64_t)ix->n_docs * ix->ublock_stride;
+  gp.cand = w.cand.as<uint32_t>();
+  gp.n_emit = g.n_emit;
+  gp.rp = rp;
+  gp.ctr = w.ctr.as<Counters>();
+  gp.lvl = w.gacc.as<uint8_t>();
+  gp.n_ranges = ix->n_ranges;
+  gp.n_hi = g.n_hi;
+  gp.n_marg = g.n_marg;
+  const size_t glds = (size_t)NP_GAIN_RANGE * 2;
+  NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gain_sweep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
+  with_int<32, 64>(p.RB, [&](auto RB) {
+    gain_prep_kernel<RB><<<B, 256, 0, st>>>(w.QCU.as<uint8_t>(), p.KP, gp.cells, gp.n_cells, g_tauq, p.LQP, w.qinv.as<float>(),
+                                            d_qoff, w.gain.as<uint16_t>(), g.base, B, p.s0cap, rp0, p.hshift, g_real);
+  });
+  const dim3 ggrid((unsigned)ix->n_ranges, (unsigned)B);
+  gain_sweep_kernel<<<ggrid, 1024, glds, st>>>(gp);                                         // accumulators, histogram of U0, counts
+  gain_thr_kernel<<<B, 64, 0, st>>>(hist0, p.s0_target, p.s0cap, g.n_raw, w.qflag.as<uint32_t>(), g.thr0, g.n_hi, g.n_s0);
+  gp.n_emit = g.n_hi_emit;
+  gain_emit_kernel<1><<<ggrid, 256, 0, st>>>(gp, 0);                                        // S0: records of the best bounds
+  gp.n_emit = g.n_emit;
+  NP_TRY(ub_bounds(rp0, 0, 1, slots((size_t)p.max_rounds * 3), g.cursor0, w.s0_meta.as<uint4>(), nullptr, g.n_s0, g.n_s0,
+                   w.s0_u.as<uint16_t>(), hist_s0, 0, ix->tune.s3_gain_direct, false));   // exact bounds of S0 (histogram: lower bounds)
+  ub_thr_kernel<<<B, 256, 0, st>>>(hist_s0, p.hshift, p.slack, cs->n_sel, g.n_s0, rp0, 0, w.qflag.as<uint32_t>(), g.cut0);   // tau0 - slack
+  gain_count_kernel<<<B, 64, 0, st>>>(g.cut0, hist0, g.base, g.n_raw, g.lcut, g.n_direct, w.ctr.as<Counters>(),
+                                      ix->tune.s3_gain == 1 ? w.h_gain : nullptr, g.report, B);   // the cut in levels, candidates kept
+  plan_rounds_kernel<<<1, 256, 0, st>>>(nullptr, 0, B, p.pool, p.max_rounds, rp, w.ctr.as<Counters>(), g.n_direct);
+  gp.thr = g.lcut;
+  return NP_OK;
+}
+
+// ---- S3: posting-list union (bitmap), per-chunk counts, round plan (the zeroth level plans its own); then the hot level's
+// thresholds and plane rows
+int Pass::s3_plan(const RoundPlan& rp) const {
+  const int B = p.B, nchunks = p.nchunks;
+  if (!p.gain_path) {
     if (ix->tune.s3_slices) {
       // bitmap ranges in LDS (mark_slices_kernel): ranges of <= 32 chunks, enough of them to fill the chip, at most 16
       // sweeps of the posting lists per query beyond what the range size forces
@@ -1003,41 +1079,44 @@ static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, 
       if (lds > 32 * 1024)
         NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mark_slices_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      mark_slices_kernel<<<dim3(nslices, B), 1024, lds, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), KP,
+      mark_slices_kernel<<<dim3(nslices, B), 1024, lds, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP,
                                                               ix->d_ivf_offsets, ix->d_ivf,
-                                                              have_subset ? w.subset_bits.as<uint32_t>() : nullptr, NW,
+                                                              p.have_subset ? w.subset_bits.as<uint32_t>() : nullptr, p.NW,
                                                               slice_chunks, nchunks, w.docbits.as<uint32_t>(),
                                                               w.chunk_counts.as<int32_t>(), w.ctr.as<Counters>(),
                                                               (ix->ivf_sorted && ix->tune.s3_bisect) ? 1 : 0);
     } else {
-      mark_candidates_kernel<<<dim3(128, B), 256, 0, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), KP,
+      mark_candidates_kernel<<<dim3(128, B), 256, 0, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP,
                                                            ix->d_ivf_offsets, ix->d_ivf,
-                                                           have_subset ? w.subset_bits.as<uint32_t>() : nullptr, NW,
+                                                           p.have_subset ? w.subset_bits.as<uint32_t>() : nullptr, p.NW,
                                                            w.docbits.as<uint32_t>(), w.ctr.as<Counters>());
-      count_chunks_kernel<<<dim3(nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), NW, nchunks,
+      count_chunks_kernel<<<dim3(nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), p.NW, nchunks,
                                                             w.chunk_counts.as<int32_t>());
     }
-    plan_rounds_kernel<<<1, 256, 0, st>>>(w.chunk_counts.as<int32_t>(), nchunks, B, pool, max_rounds, rp,
+    plan_rounds_kernel<<<1, 256, 0, st>>>(w.chunk_counts.as<int32_t>(), nchunks, B, p.pool, p.max_rounds, rp,
                                           w.ctr.as<Counters>());
   }
-  if (have_cands) {
-    // Lambda, the thresholds of the 8 planes and the hot bitmap in one launch, then the plane rows of the hot centroids -- AFTER
-    // the round plan: the hot share of a query follows its candidate count (hot_levels_kernel), which S3 has just counted
-    if (two_level && use_planes) {
-      hot_levels_kernel<<<dim3((unsigned)std::min<int64_t>(std::max<int64_t>((KP >> 5) / 256, 1), 16), B), 256, 0, st>>>(
-          w.chist.as<uint32_t>(), ix->K, ix->tune.s4_hot, w.cmaxu.as<uint8_t>(), KP, ix->tune.s4_pexp, w.ub_thr2.as<uint32_t>() + B,
-          w.levels.as<uint32_t>(), w.hotbits.as<uint32_t>(), s4_warm, w.ub_thr2.as<uint32_t>() + 2 * B,
-          w.hotbits.as<uint32_t>() + (size_t)B * (KP / 32), ix->tune.s4_hot_auto ? w.n_cand.as<int32_t>() : nullptr,
-          ix->tune.s4_hot_auto);
-      const dim3 pg((unsigned)std::min<int64_t>((KP + 2047) / 2048, 64), B);
-      if (RB == 32)
-        hot_planes_kernel<32><<<pg, 256, 0, st>>>(w.QCU.as<uint8_t>(), KP, w.cmaxu.as<uint8_t>(), w.ub_thr2.as<uint32_t>() + B,
-                                                  w.levels.as<uint32_t>(), w.planes.as<uint32_t>());
-      else
-        hot_planes_kernel<64><<<pg, 256, 0, st>>>(w.QCU.as<uint8_t>(), KP, w.cmaxu.as<uint8_t>(), w.ub_thr2.as<uint32_t>() + B,
-                                                  w.levels.as<uint32_t>(), w.planes.as<uint32_t>());
-    }
+  // Lambda, the thresholds of the 8 planes and the hot bitmap in one launch, then the plane rows of the hot centroids -- AFTER
+  // the round plan: the hot share of a query follows its candidate count (hot_levels_kernel), which S3 has just counted
+  if (p.two_level && p.use_planes) {
+    const int64_t KP = p.KP;
+    hot_levels_kernel<<<dim3((unsigned)std::min<int64_t>(std::max<int64_t>((KP >> 5) / 256, 1), 16), B), 256, 0, st>>>(
+        w.chist.as<uint32_t>(), ix->K, ix->tune.s4_hot, w.cmaxu.as<uint8_t>(), KP, ix->tune.s4_pexp, w.ub_thr2.as<uint32_t>() + B,
+        w.levels.as<uint32_t>(), w.hotbits.as<uint32_t>(), p.s4_warm, w.ub_thr2.as<uint32_t>() + 2 * B,
+        w.hotbits.as<uint32_t>() + (size_t)B * (KP / 32), ix->tune.s4_hot_auto ? w.n_cand.as<int32_t>() : nullptr,
+        ix->tune.s4_hot_auto);
+    const dim3 pg((unsigned)std::min<int64_t>((KP + 2047) / 2048, 64), B);
+    with_int<32, 64>(p.RB, [&](auto RB) {
+      hot_planes_kernel<RB><<<pg, 256, 0, st>>>(w.QCU.as<uint8_t>(), KP, w.cmaxu.as<uint8_t>(), w.ub_thr2.as<uint32_t>() + B,
+                                                w.levels.as<uint32_t>(), w.planes.as<uint32_t>());
+    });
   }
+  return NP_OK;
+}
+
+// ---- per round: S3 compaction -> S4 -> S5 (stage events bracket round 0, which holds the whole batch unless
+// the candidates overflow the pool; later rounds are charged to S5)
+int Pass::rounds(const RoundPlan& rp, const GainP& gp) const {
   SelectP sp;
   sp.approx = w.approx.as<float>();
   sp.cand = w.cand.as<uint32_t>();
@@ -1055,214 +1134,265 @@ static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, 
   if (cs->n_sel > 0 && sel_lds > 48 * 1024)
     NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&select_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_lds));
-  // ---- per round: S3 compaction -> S4 -> S5 (stage events bracket round 0, which holds the whole batch unless
-  // the candidates overflow the pool; later rounds are charged to S5)
-  for (int r = 0; r < (have_cands ? max_rounds : 0); ++r) {
-    // two-level filter: bare ids only -- the hot level finds a document's list block from the id and writes the 16-B records
-    // itself (no record gather here: a 128-B line per candidate at 1.9 % density was this kernel's whole cost)
-    const bool ids_only = two_level && ix->ublock_stride > 0;
-    if (gain_path)   // the candidates that pass the zeroth level's cut (every candidate where it does not apply), bare ids
-      gain_emit_kernel<2><<<dim3((unsigned)ix->n_ranges, (unsigned)B), 256, 0, st>>>(gp, r);
-    else
-    compact_kernel<<<dim3(nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), NW, nchunks, w.chunk_counts.as<int32_t>(),
-                                                     (use_filter && !ids_only) ? nullptr : w.cand.as<uint32_t>(), rp, r,
-                                                     ids_only ? nullptr : ix->d_doc_meta, w.cand_meta.as<uint4>());
-    if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[3], st));
-    if (use_filter) {
-      // hand-out state of the (up to three) filter launches of this round: slots = -1 (empty), ticket = -1; cursors 0
-      auto xslots = [&](int lvl) { return w.xcd_slots.as<int32_t>() + ((size_t)r * 3 + lvl) * slot_words; };
-      auto xcursor = [&](int lvl) { return w.ub_cursor.as<uint32_t>() + (size_t)lvl * B; };
-      auto launch_ub = [&](int lvl, const uint4* meta, const int32_t* begin, const int32_t* count, uint16_t* U, uint32_t* hist,
-                           int count_tokens, int direct_wpq, bool floor_rows = false) {
-        launch_ub_at(rp, r, max_rounds, xslots(lvl), xslots(lvl) + 8 * (B + 1), xcursor(lvl), meta, begin, count, w.n_cand.as<int32_t>(), U,
-                     hist, count_tokens, direct_wpq, floor_rows);
-      };
-      const unsigned ncut = (unsigned)std::min<int64_t>(ix->tune.ub_ncut, std::max<int64_t>(1, ix->n_docs / 16384));
-      CutP cp{};
-      cp.hshift = hshift;
-      cp.all_src = w.cand_meta.as<uint4>();
-      cp.n_all = w.n_cand.as<int32_t>();
-      if (!two_level) {
-        launch_ub(0, w.cand_meta.as<uint4>(), nullptr, w.n_cand.as<int32_t>(), w.ub.as<uint16_t>(), w.ub_hist.as<uint32_t>(), 1, 0);
-        ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist.as<uint32_t>(), hshift, slack, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
-                                         w.qflag.as<uint32_t>(), w.ub_thr.as<uint32_t>());
-        cp.src = w.cand_meta.as<uint4>();
-        cp.n_src_a = w.n_cand.as<int32_t>();
-        cp.U = w.ub.as<uint16_t>();
-        cp.lo = w.ub_thr.as<uint32_t>();
-        cp.zero_mode = 0;
-        cp.dst = w.surv_meta.as<uint4>();
-        cp.n_dst = w.n_surv.as<int32_t>();
-        cp.ctr = w.ctr.as<Counters>();
-        ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
-      } else {
-        // level 1: the hot bound U' of every candidate
-        {
-          int32_t* sl = xslots(0);
-          const size_t dyn = (size_t)(KP / 8);
-#define NP_LAUNCH_HOT(ROWB, CT)                                                                                          \
-  do {                                                                                                                   \
-    if (dyn > 16 * 1024)                                                                                                 \
-      NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&approx_hot_kernel<ROWB, CT>),                             \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));                                 \
-    approx_hot_kernel<ROWB, CT><<<8 * nbx, 256, dyn, st>>>(w.QCU.as<uint8_t>(), ix->K, KP, w.cmaxu.as<uint8_t>(),         \
-                                                           w.ub_thr2.as<uint32_t>() + B, w.cand.as<uint32_t>(),                \
-                                                           w.cand_meta.as<uint4>(), ix->ublock_stride,                         \
-                                                           (int64_t)ix->n_docs * ix->ublock_stride,                            \
-                                                           w.n_cand.as<int32_t>(), rp, r, max_rounds, (const CT*)ix->d_ucodes, \
-                                                           w.qflag.as<uint32_t>(), d_qoff, cs->n_sel, w.ub.as<uint16_t>(),  \
-                                                           w.ub_hist.as<uint32_t>(), hshift, xcursor(0), sl, sl + 8 * (B + 1), \
-                                                           B, ix->tune.ub_steal, w.ctr.as<Counters>(), ix->tune.s4_probe,   \
-                                                           ix->tune.hot_static);                                           \
-  } while (0)
-#define NP_LAUNCH_HOT_RB(CT)                    \
-  do {                                          \
-    if (RB == 32) NP_LAUNCH_HOT(32, CT);        \
-    else if (RB == 64) NP_LAUNCH_HOT(64, CT);   \
-    else if (RB == 128) NP_LAUNCH_HOT(128, CT); \
-    else NP_LAUNCH_HOT(256, CT);                \
-  } while (0)
-#define NP_LAUNCH_HOTP_W(ROWB, CT, LPDV, PFV, DPIV, QMV, WPBV, NBX)                                                        \
-  do {                                                                                                                   \
-    const size_t bm = sizeof(CT) == 2 ? 0 : (size_t)(((KP >> 5) + 3) & ~(int64_t)3) * 4;   /* u16 codes: static bitmap */   \
-    /* idle lanes of the last packed staging instruction write 16 B each past the rows it fills (1 KiB per instruction);     \
-       the one-block-per-instruction fallback overruns by at most 256 B */                                                  \
-    const size_t rowb = (size_t)ix->ublock_stride * sizeof(CT) + 16;                                                          \
-    const int slack = (int)std::max<int64_t>(256, 1024 - (int64_t)(DPIV) * (int64_t)rowb);                                   \
-    const size_t dynp = bm + (size_t)(WPBV) * ((64 / LPDV) * rowb + (size_t)slack);                                          \
-    if (dynp > 16 * 1024)                                                                                                \
-      NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&approx_hotp_kernel<ROWB, CT, LPDV, PFV, DPIV, QMV, WPBV>), \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynp));                                \
-    approx_hotp_kernel<ROWB, CT, LPDV, PFV, DPIV, QMV, WPBV><<<8 * (NBX), 64 * (WPBV), dynp, st>>>(                 \
-        w.planes.as<uint32_t>(), ix->K, KP, w.hotbits.as<uint32_t>(), w.ub_thr2.as<uint32_t>() + B, w.levels.as<uint32_t>(), \
-        w.cand.as<uint32_t>(), w.cand_meta.as<uint4>(), ix->ublock_stride, (int64_t)ix->n_docs * ix->ublock_stride,        \
-        w.n_cand.as<int32_t>(), rp, r, max_rounds, (const CT*)ix->d_ucodes, w.qflag.as<uint32_t>(), d_qoff, cs->n_sel,     \
-        w.ub.as<uint16_t>(), w.ub_hist.as<uint32_t>(), hshift, sl, sl + 8 * (B + 1), B, w.ctr.as<Counters>(), slack,       \
-        ix->tune.s4_probe, gain_path ? 1 : 0);                                                                                            \
-  } while (0)
-#define NP_LAUNCH_HOTP(ROWB, CT, LPDV, PFV, DPIV, QMV) NP_LAUNCH_HOTP_W(ROWB, CT, LPDV, PFV, DPIV, QMV, 4, pnbx)
+  for (int r = 0; r < (p.have_cands ? p.max_rounds : 0); ++r) NP_TRY(round(r, rp, gp, sp));
+  return NP_OK;
+}
+
+int Pass::round(int r, const RoundPlan& rp, const GainP& gp, SelectP sp) const {
+  const int B = p.B;
+  if (p.gain_path)   // the candidates that pass the zeroth level's cut (every candidate where it does not apply), bare ids
+    gain_emit_kernel<2><<<dim3((unsigned)ix->n_ranges, (unsigned)B), 256, 0, st>>>(gp, r);
+  else
+    compact_kernel<<<dim3(p.nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), p.NW, p.nchunks, w.chunk_counts.as<int32_t>(),
+                                                       (p.use_filter && !p.ids_only) ? nullptr : w.cand.as<uint32_t>(), rp, r,
+                                                       p.ids_only ? nullptr : ix->d_doc_meta, w.cand_meta.as<uint4>());
+  if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[3], st));
+  const bool matvec = p.batched && !p.s1_split;
+  if (p.use_filter) {
+    NP_TRY(p.two_level ? two_level_cut(r, rp) : single_level_cut(r, rp));
+    // exact f32 approximate scores of the survivors only
+    launch_approx(st, ix, w, d_qoff, B, p.LQP, w.surv_meta.as<uint4>(), w.n_surv.as<int32_t>(), rp, r, p.max_rounds, nullptr);
+    sp.cand = reinterpret_cast<const uint32_t*>(w.surv_meta.p);
+    sp.cand_step = 4;
+    sp.n_cand = w.n_surv.as<int32_t>();
+    sp.ctr = w.ctr.as<Counters>();
+    if (matvec) {
+      // reference arithmetic of the batched path: G-valued cut with a rounding margin, then the mat-vec scores
+      // of what is left (the candidate records of this round are consumed: their array takes the second list)
+      gcut_kernel<<<B, 1024, 0, st>>>(w.approx.as<float>(), w.surv_meta.as<uint4>(), w.n_surv.as<int32_t>(), rp, r, cs->n_sel,
+                                      w.qinv.as<float>(), w.qflag.as<uint32_t>(), d_qoff, w.cand_meta.as<uint4>(),
+                                      w.n_list2.as<int32_t>());
+      launch_matvec(st, ix, w, d_q, d_qoff, B, w.cand_meta.as<uint4>(), w.n_list2.as<int32_t>(), rp, r);
+      sp.cand = reinterpret_cast<const uint32_t*>(w.cand_meta.p);
+      sp.n_cand = w.n_list2.as<int32_t>();
+    }
+  } else if (ix->T > 0) {
+    if (matvec) {   // debug trace / filter off: the mat-vec score of every candidate
+      launch_matvec(st, ix, w, d_q, d_qoff, B, w.cand_meta.as<uint4>(), w.n_cand.as<int32_t>(), rp, r);
+      count_work_kernel<<<dim3(32, (unsigned)B), 256, 0, st>>>(w.cand_meta.as<uint4>(), w.n_cand.as<int32_t>(), rp, r,
+                                                               w.ctr.as<Counters>());
+    } else {
+      launch_approx(st, ix, w, d_qoff, B, p.LQP, w.cand_meta.as<uint4>(), w.n_cand.as<int32_t>(), rp, r, p.max_rounds,
+                    w.ctr.as<Counters>());
+    }
+  }
+  if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[4], st));
+  if (cs->n_sel > 0) {
+    sp.round = r;
+    select_kernel<<<B, 1024, (size_t)cs->NSELP * 8, st>>>(sp);
+  }
+  return NP_OK;
+}
+
+// single-level filter: the exact bound of every candidate, its cut -> survivors
+int Pass::single_level_cut(int r, const RoundPlan& rp) const {
+  const int B = p.B;
+  NP_TRY(ub_bounds(rp, r, p.max_rounds, slots((size_t)r * 3), cursor(0), w.cand_meta.as<uint4>(), nullptr, w.n_cand.as<int32_t>(),
+                   w.n_cand.as<int32_t>(), w.ub.as<uint16_t>(), w.ub_hist.as<uint32_t>(), 1, 0, false));
+  ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist.as<uint32_t>(), p.hshift, p.slack, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
+                                   w.qflag.as<uint32_t>(), w.ub_thr.as<uint32_t>());
+  CutP cp{};
+  cp.hshift = p.hshift;
+  cp.all_src = w.cand_meta.as<uint4>();
+  cp.n_all = w.n_cand.as<int32_t>();
+  cp.src = w.cand_meta.as<uint4>();
+  cp.n_src_a = w.n_cand.as<int32_t>();
+  cp.U = w.ub.as<uint16_t>();
+  cp.lo = w.ub_thr.as<uint32_t>();
+  cp.zero_mode = 0;
+  cp.dst = w.surv_meta.as<uint4>();
+  cp.n_dst = w.n_surv.as<int32_t>();
+  cp.ctr = w.ctr.as<Counters>();
+  ub_cut_kernel<<<dim3(n_cut(), B), 256, 0, st>>>(cp, rp, r);
+  return NP_OK;
+}
+
+// two-level filter: the hot bound U' of every candidate, then the exact bound of S1 (the n_sel largest U') and of S2 (the rest
+// with U' >= tau) -> survivors
+int Pass::two_level_cut(int r, const RoundPlan& rp) const {
+  const int B = p.B;
+  const unsigned ncut = n_cut();
+  auto ub = [&](int lvl, const int32_t* begin, const int32_t* count, int direct_wpq, bool floor_rows) {
+    return ub_bounds(rp, r, p.max_rounds, slots((size_t)r * 3 + lvl), cursor(lvl), w.list_meta.as<uint4>(), begin, count,
+                     w.n_cand.as<int32_t>(), w.ub2.as<uint16_t>(), w.ub_hist2.as<uint32_t>(), 0, direct_wpq, floor_rows);
+  };
+  CutP cp{};
+  cp.hshift = p.hshift;
+  cp.all_src = w.cand_meta.as<uint4>();
+  cp.n_all = w.n_cand.as<int32_t>();
+  // level 1: the hot bound U' of every candidate
+  if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[8], st));
+  NP_TRY(hot_level(r, rp));
+  if (cs->timed && r == 0) {
+    NP_HIP(hipEventRecord(cs->ctx->ev[9], st));
+    cs->hot_timed = true;
+  }
+  // S1 = the n_sel documents with the largest U' (whole bins): exact bound -> tau
+  ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist.as<uint32_t>(), p.hshift, 0, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
+                                   w.qflag.as<uint32_t>(), w.ub_thr.as<uint32_t>());
+  cp.src = w.cand_meta.as<uint4>();
+  cp.n_src_a = w.n_cand.as<int32_t>();
+  cp.U = w.ub.as<uint16_t>();
+  cp.lo = w.ub_thr.as<uint32_t>();
+  cp.zero_mode = 1;
+  cp.dst = w.list_meta.as<uint4>();
+  cp.n_dst = w.n_l1.as<int32_t>();
+  ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
+  NP_TRY(ub(1, nullptr, w.n_l1.as<int32_t>(), ix->tune.ub_direct, false));
+  ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist2.as<uint32_t>(), p.hshift, p.slack, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
+                                   w.qflag.as<uint32_t>(), w.ub_thr2.as<uint32_t>());
+  // S2 = the other documents with U' >= tau: exact bound too (appended behind S1)
+  cp.lo = w.ub_thr2.as<uint32_t>();
+  cp.hi = w.ub_thr.as<uint32_t>();
+  cp.dst_begin = w.n_l1.as<int32_t>();
+  cp.n_dst = w.n_l2.as<int32_t>();
+  ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
+  NP_TRY(ub(2, w.n_l1.as<int32_t>(), w.n_l2.as<int32_t>(), 0, true));
+  // every document with U' >= tau now has its exact bound in the histogram: the cut over S1 + S2 is the single-level
+  // filter's cut (the n_sel-th largest exact U of ALL candidates lies in S1 + S2), tau can only rise
+  ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist2.as<uint32_t>(), p.hshift, p.slack, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
+                                   w.qflag.as<uint32_t>(), w.ub_thr2.as<uint32_t>());
+  // survivors: the documents of S1 + S2 whose exact bound reaches tau (every candidate where the filter does not apply)
+  cp.src = w.list_meta.as<uint4>();
+  cp.n_src_a = w.n_l1.as<int32_t>();
+  cp.n_src_b = w.n_l2.as<int32_t>();
+  cp.U = w.ub2.as<uint16_t>();
+  cp.lo = w.ub_thr2.as<uint32_t>();
+  cp.hi = nullptr;
+  cp.zero_mode = 0;
+  cp.dst = w.surv_meta.as<uint4>();
+  cp.dst_begin = nullptr;
+  cp.n_dst = w.n_surv.as<int32_t>();
+  cp.ctr = w.ctr.as<Counters>();
+  ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
+  return NP_OK;
+}
+
+// the first filter level: byte maxima (approx_hot_kernel) or bit planes (approx_hotp_kernel) of the hot centroids
+int Pass::hot_level(int r, const RoundPlan& rp) const {
+  const int B = p.B;
+  const int64_t KP = p.KP;
   // lanes per document: 2 (32 documents per claim; blocks of at most 256 bytes) or 4 (16 per claim: half the LDS rows per
   // wave; the only choice for 512-byte blocks).  Documents per staging instruction from the block size (16 B per lane,
   // block + 16 B of padding per row)
-#define NP_LAUNCH_HOTP_L(ROWB, CT)                                      \
-  do {                                                                  \
-    const int sb = ix->ublock_stride * (int)sizeof(CT);                 \
-    if (plpd == 2) {                                                    \
-      if (sb <= 240 && ix->tune.s4_qm) NP_LAUNCH_HOTP(ROWB, CT, 2, 2, 4, 1);   \
-      else if (sb <= 240) NP_LAUNCH_HOTP(ROWB, CT, 2, 2, 4, 0);         \
-      else NP_LAUNCH_HOTP(ROWB, CT, 2, 2, 2, 0);                        \
-    } else if (sb <= 240) NP_LAUNCH_HOTP(ROWB, CT, 4, 1, 4, 0);         \
-    else if (sb <= 496) NP_LAUNCH_HOTP(ROWB, CT, 4, 1, 2, 0);           \
-    else NP_LAUNCH_HOTP(ROWB, CT, 4, 1, 1, 0);                          \
-  } while (0)
-          const int plpd = (ix->ublock_stride > old_cap || ix->tune.s4_lpd == 4) ? 4 : 2;
-          const unsigned pnbx = (unsigned)ix->tune.s4_pnbx;   // workgroups per XCD of the plane kernel
-          if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[8], st));
-          if (use_planes) {
-            if (!ix->code_wide) {
-              if (RB == 32) NP_LAUNCH_HOTP_L(32, uint16_t);
-              else NP_LAUNCH_HOTP_L(64, uint16_t);
-            } else if ((KP >> 3) >= 32 * 1024 && plpd == 4 && ix->ublock_stride * 4 > 240 && ix->ublock_stride * 4 <= 496) {
-              // u32 code lists with a hot bitmap of 32 KB or more (K >= 2^18), the usual 4-lane form: ONE workgroup of 12 waves per
-              // CU shares the bitmap (with 4-wave workgroups the 64 KB of K = 2^19 left one per CU: 4 waves)
-              if (RB == 32) NP_LAUNCH_HOTP_W(32, uint32_t, 4, 1, 2, 0, 12, 32);
-              else NP_LAUNCH_HOTP_W(64, uint32_t, 4, 1, 2, 0, 12, 32);
-            } else {
-              if (RB == 32) NP_LAUNCH_HOTP_L(32, uint32_t);
-              else NP_LAUNCH_HOTP_L(64, uint32_t);
-            }
-          } else if (!ix->code_wide) NP_LAUNCH_HOT_RB(uint16_t);
-          else NP_LAUNCH_HOT_RB(uint32_t);
-#undef NP_LAUNCH_HOTP_L
-#undef NP_LAUNCH_HOTP
-#undef NP_LAUNCH_HOTP_W
-#undef NP_LAUNCH_HOT_RB
-#undef NP_LAUNCH_HOT
-          if (cs->timed && r == 0) {
-            NP_HIP(hipEventRecord(cs->ctx->ev[9], st));
-            cs->hot_timed = true;
-          }
-        }
-        // S1 = the n_sel documents with the largest U' (whole bins): exact bound -> tau
-        ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist.as<uint32_t>(), hshift, 0, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
-                                         w.qflag.as<uint32_t>(), w.ub_thr.as<uint32_t>());
-        cp.src = w.cand_meta.as<uint4>();
-        cp.n_src_a = w.n_cand.as<int32_t>();
-        cp.U = w.ub.as<uint16_t>();
-        cp.lo = w.ub_thr.as<uint32_t>();
-        cp.zero_mode = 1;
-        cp.dst = w.list_meta.as<uint4>();
-        cp.n_dst = w.n_l1.as<int32_t>();
-        ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
-        launch_ub(1, w.list_meta.as<uint4>(), nullptr, w.n_l1.as<int32_t>(), w.ub2.as<uint16_t>(), w.ub_hist2.as<uint32_t>(), 0,
-                  ix->tune.ub_direct);
-        ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist2.as<uint32_t>(), hshift, slack, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
-                                         w.qflag.as<uint32_t>(), w.ub_thr2.as<uint32_t>());
-        // S2 = the other documents with U' >= tau: exact bound too (appended behind S1)
-        cp.lo = w.ub_thr2.as<uint32_t>();
-        cp.hi = w.ub_thr.as<uint32_t>();
-        cp.dst_begin = w.n_l1.as<int32_t>();
-        cp.n_dst = w.n_l2.as<int32_t>();
-        ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
-        launch_ub(2, w.list_meta.as<uint4>(), w.n_l1.as<int32_t>(), w.n_l2.as<int32_t>(), w.ub2.as<uint16_t>(), w.ub_hist2.as<uint32_t>(), 0, 0,
-                  true);
-        // every document with U' >= tau now has its exact bound in the histogram: the cut over S1 + S2 is the single-level
-        // filter's cut (the n_sel-th largest exact U of ALL candidates lies in S1 + S2), tau can only rise
-        ub_thr_kernel<<<B, 256, 0, st>>>(w.ub_hist2.as<uint32_t>(), hshift, slack, cs->n_sel, w.n_cand.as<int32_t>(), rp, r,
-                                         w.qflag.as<uint32_t>(), w.ub_thr2.as<uint32_t>());
-        // survivors: the documents of S1 + S2 whose exact bound reaches tau (every candidate where the filter does not apply)
-        cp.src = w.list_meta.as<uint4>();
-        cp.n_src_a = w.n_l1.as<int32_t>();
-        cp.n_src_b = w.n_l2.as<int32_t>();
-        cp.U = w.ub2.as<uint16_t>();
-        cp.lo = w.ub_thr2.as<uint32_t>();
-        cp.hi = nullptr;
-        cp.zero_mode = 0;
-        cp.dst = w.surv_meta.as<uint4>();
-        cp.dst_begin = nullptr;
-        cp.n_dst = w.n_surv.as<int32_t>();
-        cp.ctr = w.ctr.as<Counters>();
-        ub_cut_kernel<<<dim3(ncut, B), 256, 0, st>>>(cp, rp, r);
-      }
-      // exact f32 approximate scores of the survivors only
-      launch_approx(st, ix, w, d_qoff, B, LQP, w.surv_meta.as<uint4>(), w.n_surv.as<int32_t>(), rp, r, max_rounds, nullptr);
-      sp.cand = reinterpret_cast<const uint32_t*>(w.surv_meta.p);
-      sp.cand_step = 4;
-      sp.n_cand = w.n_surv.as<int32_t>();
-      sp.ctr = w.ctr.as<Counters>();
-      if (batched && !s1_split) {
-        // reference arithmetic of the batched path: G-valued cut with a rounding margin, then the mat-vec scores
-        // of what is left (the candidate records of this round are consumed: their array takes the second list)
-        gcut_kernel<<<B, 1024, 0, st>>>(w.approx.as<float>(), w.surv_meta.as<uint4>(), w.n_surv.as<int32_t>(), rp, r, cs->n_sel,
-                                        w.qinv.as<float>(), w.qflag.as<uint32_t>(), d_qoff, w.cand_meta.as<uint4>(),
-                                        w.n_list2.as<int32_t>());
-        launch_matvec(st, ix, w, d_q, d_qoff, B, w.cand_meta.as<uint4>(), w.n_list2.as<int32_t>(), rp, r);
-        sp.cand = reinterpret_cast<const uint32_t*>(w.cand_meta.p);
-        sp.n_cand = w.n_list2.as<int32_t>();
-      }
-    } else if (ix->T > 0) {
-      if (batched && !s1_split) {   // debug trace / filter off: the mat-vec score of every candidate
-        launch_matvec(st, ix, w, d_q, d_qoff, B, w.cand_meta.as<uint4>(), w.n_cand.as<int32_t>(), rp, r);
-        count_work_kernel<<<dim3(32, (unsigned)B), 256, 0, st>>>(w.cand_meta.as<uint4>(), w.n_cand.as<int32_t>(), rp, r,
-                                                                 w.ctr.as<Counters>());
-      } else {
-        launch_approx(st, ix, w, d_qoff, B, LQP, w.cand_meta.as<uint4>(), w.n_cand.as<int32_t>(), rp, r, max_rounds,
-                      w.ctr.as<Counters>());
-      }
+  const int old_cap = ix->code_wide ? 64 : 128;
+  const int plpd = (ix->ublock_stride > old_cap || ix->tune.s4_lpd == 4) ? 4 : 2;
+  const unsigned pnbx = (unsigned)ix->tune.s4_pnbx;   // workgroups per XCD of the plane kernel
+  return with_codes(ix->code_wide, [&](auto ct) -> int {
+    using CT = decltype(ct);
+    if (!p.use_planes) {
+      return with_rowb(p.RB, [&](auto RB) -> int {
+        int32_t* sl = slots((size_t)r * 3);
+        const size_t dyn = (size_t)(KP / 8);
+        if (dyn > 16 * 1024)
+          NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&approx_hot_kernel<RB, CT>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        approx_hot_kernel<RB, CT><<<8 * (unsigned)ix->tune.ub_nbx, 256, dyn, st>>>(
+            w.QCU.as<uint8_t>(), ix->K, KP, w.cmaxu.as<uint8_t>(), w.ub_thr2.as<uint32_t>() + B, w.cand.as<uint32_t>(),
+            w.cand_meta.as<uint4>(), ix->ublock_stride, (int64_t)ix->n_docs * ix->ublock_stride, w.n_cand.as<int32_t>(), rp, r,
+            p.max_rounds, (const CT*)ix->d_ucodes, w.qflag.as<uint32_t>(), d_qoff, cs->n_sel, w.ub.as<uint16_t>(),
+            w.ub_hist.as<uint32_t>(), p.hshift, cursor(0), sl, sl + 8 * (B + 1), B, ix->tune.ub_steal, w.ctr.as<Counters>(),
+            ix->tune.s4_probe, ix->tune.hot_static);
+        return NP_OK;
+      });
     }
-    if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[4], st));
-    if (cs->n_sel > 0) {
-      sp.round = r;
-      select_kernel<<<B, 1024, sel_lds, st>>>(sp);
-    }
+    return with_int<32, 64>(p.RB, [&](auto RB) -> int {
+      const int sb = ix->ublock_stride * (int)sizeof(CT);
+      if constexpr (sizeof(CT) == 4) {
+        if ((KP >> 3) >= 32 * 1024 && plpd == 4 && sb > 240 && sb <= 496)
+          // u32 code lists with a hot bitmap of 32 KB or more (K >= 2^18), the usual 4-lane form: ONE workgroup of 12 waves per
+          // CU shares the bitmap (with 4-wave workgroups the 64 KB of K = 2^19 left one per CU: 4 waves)
+          return hotp<RB, CT, 4, 1, 2, 0, 12>(r, rp, 32);
+      }
+      if (plpd == 2) {
+        if (sb <= 240 && ix->tune.s4_qm) return hotp<RB, CT, 2, 2, 4, 1>(r, rp, pnbx);
+        if (sb <= 240) return hotp<RB, CT, 2, 2, 4, 0>(r, rp, pnbx);
+        return hotp<RB, CT, 2, 2, 2, 0>(r, rp, pnbx);
+      }
+      if (sb <= 240) return hotp<RB, CT, 4, 1, 4, 0>(r, rp, pnbx);
+      if (sb <= 496) return hotp<RB, CT, 4, 1, 2, 0>(r, rp, pnbx);
+      return hotp<RB, CT, 4, 1, 1, 0>(r, rp, pnbx);
+    });
+  });
+}
+
+template <int RB, class CT, int LPD, int PF, int DPI, int QM, int WPB>
+int Pass::hotp(int r, const RoundPlan& rp, unsigned nbx) const {
+  const int B = p.B;
+  const int64_t KP = p.KP;
+  int32_t* sl = slots((size_t)r * 3);
+  const size_t bm = sizeof(CT) == 2 ? 0 : (size_t)(((KP >> 5) + 3) & ~(int64_t)3) * 4;   // u16 codes: static bitmap
+  // idle lanes of the last packed staging instruction write 16 B each past the rows it fills (1 KiB per instruction);
+  // the one-block-per-instruction fallback overruns by at most 256 B
+  const size_t rowb = (size_t)ix->ublock_stride * sizeof(CT) + 16;
+  const int slack = (int)std::max<int64_t>(256, 1024 - (int64_t)DPI * (int64_t)rowb);
+  const size_t dynp = bm + (size_t)WPB * ((64 / LPD) * rowb + (size_t)slack);
+  if (dynp > 16 * 1024)
+    NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&approx_hotp_kernel<RB, CT, LPD, PF, DPI, QM, WPB>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynp));
+  approx_hotp_kernel<RB, CT, LPD, PF, DPI, QM, WPB><<<8 * nbx, 64 * WPB, dynp, st>>>(
+      w.planes.as<uint32_t>(), ix->K, KP, w.hotbits.as<uint32_t>(), w.ub_thr2.as<uint32_t>() + B, w.levels.as<uint32_t>(),
+      w.cand.as<uint32_t>(), w.cand_meta.as<uint4>(), ix->ublock_stride, (int64_t)ix->n_docs * ix->ublock_stride,
+      w.n_cand.as<int32_t>(), rp, r, p.max_rounds, (const CT*)ix->d_ucodes, w.qflag.as<uint32_t>(), d_qoff, cs->n_sel,
+      w.ub.as<uint16_t>(), w.ub_hist.as<uint32_t>(), p.hshift, sl, sl + 8 * (B + 1), B, w.ctr.as<Counters>(), slack,
+      ix->tune.s4_probe, p.gain_path ? 1 : 0);
+  return NP_OK;
+}
+
+// S1..S5 for queries [0,B) whose rows live in d_q (absolute offsets d_qoff/h_qoff).
+static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
+                        const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len, bool allow_grow) {
+  Workspace& w = *cs->ctx->ws;
+  hipStream_t st = cs->stream;
+  PassPlan p;
+  NP_TRY(plan_pass(ix, cs, h_qoff, subset_len, allow_grow, p));
+  NP_TRY(reserve_pass(ix, cs, p, w));
+  settle_zeroth_level(ix, w, cs, p);
+  if (ix->ldim != ix->dim) {   // caller rows -> storage rows; everything below sees ix->dim
+    if (p.rows > 0)
+      pad_rows_kernel<<<(unsigned)((p.rows * ix->dim + 255) / 256), 256, 0, st>>>(d_q + p.row0 * ix->ldim, p.rows, ix->ldim,
+                                                                                  ix->dim, w.qpad.as<float>());
+    d_q = w.qpad.as<float>() - p.row0 * ix->dim;   // offsets stay absolute
   }
-  if (cs->timed && !have_cands) {
+  const Pass a{ix, cs, w, p, st, d_q, d_qoff, d_subset, subset_len};
+  if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[0], st));
+  NP_TRY(a.clear());
+  if (p.B == 0) return NP_OK;
+  a.s1();
+  if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[1], st));
+  NP_TRY(a.subset());
+  a.s2();
+  if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[2], st));
+  const RoundPlan rp = a.round_plan();
+  GainP gp{};
+  if (p.have_cands && p.gain_path) NP_TRY(a.zeroth_level(rp, gp));
+  if (p.have_cands) NP_TRY(a.s3_plan(rp));
+  NP_TRY(a.rounds(rp, gp));
+  if (cs->timed && !p.have_cands) {
     NP_HIP(hipEventRecord(cs->ctx->ev[3], st));
     NP_HIP(hipEventRecord(cs->ctx->ev[4], st));
   }
   if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[5], st));
   NP_HIP(hipGetLastError());
   return NP_OK;
+}
+
+// A reservation that fails under the DEFAULT budget (another index or an encoder took the memory since open) is retried
+// with the pool released and the budget halved -- more candidate-pool rounds instead of OutOfMemory.  Every reservation of
+// a pass happens before its first launch (reserve_pass), so a failed pass leaves nothing half-done.
+static int phase_a(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
+                   const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len) {
+  for (int attempt = 0;; ++attempt) {
+    // (a retry never lets the budget grow back: the pass that just failed WAS the planned size)
+    const int rc = phase_a_once(ix, cs, d_q, d_qoff, h_qoff, d_subset, subset_len, attempt == 0);
+    if (rc != NP_ERR_OUT_OF_MEMORY || !ix->ws_auto || attempt >= 4) return rc;
+    const int64_t b = ix->ws_budget.load(std::memory_order_relaxed);
+    if (b <= ((int64_t)256 << 20)) return rc;
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(cs->stream);   // the pool may still be read by work queued before the failure
+    cs->ctx->ws->release_pool();
+    ix->ws_budget.store(std::max<int64_t>(b / 2, (int64_t)256 << 20), std::memory_order_relaxed);
+  }
 }
 
 // S6..S7.  d_cut may be NULL (keep every locally selected document).
@@ -1301,12 +1431,9 @@ static int phase_b(const DeviceIndex* ix, CallState* cs, const int32_t* d_qoff, 
     ep.qt0 = 0;
     ep.acc = 0;
     ep.pad_ss = ix->pad_ss;
-    switch (ix->dim) {
-      case 32: NP_TRY((launch_exact_nb<32>(st, ix, ep, B, cs->prm.precision, ix->nbits))); break;
-      case 64: NP_TRY((launch_exact_nb<64>(st, ix, ep, B, cs->prm.precision, ix->nbits))); break;
-      case 96: NP_TRY((launch_exact_nb<96>(st, ix, ep, B, cs->prm.precision, ix->nbits))); break;
-      default: NP_TRY((launch_exact_nb<128>(st, ix, ep, B, cs->prm.precision, ix->nbits))); break;
-    }
+    NP_TRY(with_dim(ix->dim, [&](auto DIM) {
+      return with_int<2, 8, 4>(ix->nbits, [&](auto NBITS) { return launch_exact_qt<DIM, NBITS>(st, ix, ep, B, cs->prm.precision); });
+    }));
   }
   if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[6], st));
   {
@@ -1363,9 +1490,7 @@ struct UseGuard {
 };
 
 static int lqp_of(const int32_t* h_qoff, int B) {
-  int maxLq = 1;
-  for (int b = 0; b < B; ++b) maxLq = std::max(maxLq, h_qoff[b + 1] - h_qoff[b]);
-  return std::min((maxLq + 31) / 32 * 32, 32 * NP_MAX_QT);
+  return std::min((max_tokens(h_qoff, B) + 31) / 32 * 32, 32 * NP_MAX_QT);
 }
 
 static int slice_size(const DeviceIndex* ix, const int32_t* h_qoff, int B, const np_search_params* prm) {
@@ -1944,12 +2069,7 @@ int np_hip_encode_tokens(const np_index* ix, const float* embeddings, int64_t n_
     }
     prep_queries_kernel<<<Sb, 256, 0, st>>>(xs, w.qoff.as<int32_t>(), sdim, LQP, w.Qt.as<float>(),
                                             w.Qb.as<__bf16>(), w.Qbl.as<__bf16>(), 0.f, nullptr, nullptr);
-    switch (ix->dim) {
-      case 32: launch_gemm<32>(st, ix, w.Qt.as<float>(), Sb, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>()); break;
-      case 64: launch_gemm<64>(st, ix, w.Qt.as<float>(), Sb, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>()); break;
-      case 96: launch_gemm<96>(st, ix, w.Qt.as<float>(), Sb, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>()); break;
-      default: launch_gemm<128>(st, ix, w.Qt.as<float>(), Sb, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>()); break;
-    }
+    launch_gemm(st, ix, w.Qt.as<float>(), Sb, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>());
     encode_argmax_kernel<<<(unsigned)((nb + 3) / 4), 256, 0, st>>>(w.QCT.as<float>(), w.gmax.as<uint32_t>(), ix->K, KP,
                                                                   LQP, nb, w.out_ids.as<int64_t>());
     encode_pack_kernel<<<(unsigned)((nb * pd + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids,
