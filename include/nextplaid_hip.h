@@ -159,7 +159,11 @@ typedef struct np_index_arrays {
   int32_t dim, nbits;
   const float* centroids;       /* [K, dim] */
   const float* bucket_weights;  /* [2^nbits] */
-  const int64_t* ivf;           /* concatenated posting lists, global doc ids ascending per list */
+  const int64_t* ivf;           /* concatenated posting lists of global doc ids: any entries give the reference's
+                                   answer (candidates = union of the probed lists, scores from the codes).  The crate
+                                   writes list c = the ascending ids of the documents holding code c; only lists that
+                                   strictly ascend AND hold every (document, code) pair of the shard enable the zeroth
+                                   filter level (checked at open), other lists are served without it */
   const int32_t* ivf_lengths;   /* [K] */
   const int64_t* doc_lengths;   /* [num_docs] */
   const int64_t* codes;         /* [sum doc_lengths] */

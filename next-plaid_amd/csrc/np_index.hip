@@ -545,13 +545,67 @@ static void set_ivf_bound(DeviceIndex* ix, const int64_t* ioff) {
   for (int64_t c = 0; c < K; ++c) ix->ivf_top_prefix[(size_t)c + 1] = ix->ivf_top_prefix[(size_t)c] + len[(size_t)c];
 }
 
-static int build_ivf_split(DeviceIndex* ix) {
+// ---- derived: do the posting lists cover the codes? ------------------------------------------------------------------
+// The zeroth filter level bounds a document's approximate score by the gains of the probed cells WHOSE LISTS HOLD IT, which
+// is a bound only if every (document, distinct code c) pair is in list c.  The crate writes exactly these pairs
+// (index.rs:479-504), but the reference only forms the candidate set from the lists (index.rs:1142-1156) and scores from the
+// codes, so lists that miss a pair still make a defined index -- one the level would prune wrongly.  One wave per document
+// bisects the document's id in the (ascending) list of each of its distinct codes and flags a pair that is not there.  The
+// lists of documents longer than NP_UNIQ_MAX tokens are unsorted and keep duplicates: every entry is looked up all the same.
+// Extra entries (a document in a list of a code it does not hold) only loosen the bound and are not flagged.
+__global__ void __launch_bounds__(256) ivf_cover_kernel(int64_t n_docs, const uint4* __restrict__ meta, CodeArr ucodes,
+                                                        const uint32_t* __restrict__ ivf, const int64_t* __restrict__ ivf_off,
+                                                        int* __restrict__ missing) {
+  const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (d >= n_docs) return;
+  const uint4 m = meta[d];
+  const int64_t off = (int64_t)m.z | ((int64_t)(m.w & 0xFFu) << 32);
+  bool miss = false;
+  for (uint32_t j = threadIdx.x & 63; j < m.y; j += 64) {
+    const uint32_t c = ucodes[off + j];
+    const int64_t s0 = ivf_off[c], len = ivf_off[c + 1] - s0;
+    int64_t a = 0, z = len;
+    while (a < z) {
+      const int64_t mid = (a + z) >> 1;
+      if ((int64_t)ivf[s0 + mid] < d) a = mid + 1;
+      else z = mid;
+    }
+    miss |= a == len || (int64_t)ivf[s0 + a] != d;
+  }
+  if (miss) *missing = 1;
+}
+
+static int ivf_covers_codes(const DeviceIndex* ix, bool* covers) {
+  *covers = false;
+  int* d_missing = nullptr;
+  NP_HIP(hipMalloc(&d_missing, sizeof(int)));
+  hipError_t e = hipMemset(d_missing, 0, sizeof(int));
+  if (e == hipSuccess) {
+    ivf_cover_kernel<<<(unsigned)((ix->n_docs + 3) / 4), 256>>>(ix->n_docs, ix->d_doc_meta, ix->ucodes(), ix->d_ivf,
+                                                                ix->d_ivf_offsets, d_missing);
+    e = hipGetLastError();
+  }
+  int missing = 1;
+  if (e == hipSuccess) e = hipMemcpy(&missing, d_missing, sizeof(int), hipMemcpyDeviceToHost);
+  (void)hipFree(d_missing);
+  NP_HIP(e);
+  *covers = missing == 0;
+  return NP_OK;
+}
+
+// lists_from_codes: the caller built the lists from the distinct codes (build_ivf_from_ucodes), so they cover them
+static int build_ivf_split(DeviceIndex* ix, bool lists_from_codes) {
   ix->d_ivf_split = nullptr;
   ix->n_ranges = 0;
   if (!ix->tune.s3_gain || !ix->tune.s4_planes || !ix->ivf_sorted || ix->n_docs <= 0 || ix->K <= 0 || ix->ublock_stride <= 0) return NP_OK;
   const int R = (int)((ix->n_docs + NP_SPLIT_RANGE - 1) / NP_SPLIT_RANGE), R1 = R + 1;
   const size_t n = (size_t)ix->K * (size_t)R1;
   if (n * 4 > ((size_t)2 << 30)) return NP_OK;   // a table beyond 2 GiB (K x n_docs both huge) is not worth its HBM: the level stays off
+  if (!lists_from_codes) {   // lists that miss a (document, code) pair: no table, so the level stays off (np_search.hip gain_possible)
+    bool covers = false;
+    NP_TRY(ivf_covers_codes(ix, &covers));
+    if (!covers) return NP_OK;
+  }
   NP_TRY(dev_alloc(&ix->d_ivf_split, n, &ix->device_bytes));
   ivf_split_kernel<<<(unsigned)((n + 255) / 256), 256>>>(ix->d_ivf, ix->d_ivf_offsets, ix->K, R1, ix->d_ivf_split);
   NP_HIP(hipGetLastError());
@@ -1153,7 +1207,8 @@ int build_device_index(const HostIndex& h, const np_open_opts* opts_in, DeviceIn
     NP_TRY(rc);
   }
   trace.mark("distinct-code blocks");
-  NP_TRY(build_ivf_split(ix));
+  NP_TRY(build_ivf_split(ix, false));
+  trace.mark("list coverage + range table");
   NP_TRY(build_inv_norm(ix));
   trace.mark("inverse norms");
   default_workspace(ix);
@@ -1527,7 +1582,7 @@ static int synth_build(const np_synth_spec* s, const np_open_opts* opts_in, Devi
     (void)hipFree(d_uoff);
     NP_TRY(rc);
   }
-  NP_TRY(build_ivf_split(ix));
+  NP_TRY(build_ivf_split(ix, true));
   NP_TRY(build_inv_norm(ix));
   default_workspace(ix);
   cleanup.p = nullptr;

@@ -193,10 +193,12 @@ def probe(QC, nprobe):
     return marks, theta
 
 
-def gain_bound(QC, s, docs, nprobe, depth, acc_bits=15, thr=None):
+def gain_bound(QC, s, docs, nprobe, depth, acc_bits=15, thr=None, lists=None):
     """The level's arithmetic: ut_q = u(theta_q at the DEPTH), G(c) = sum_q max(0, u[q,c] - ut_q) for the cells marked at that
-    depth, scaled by 2^-sh (rounded up) so that the sum over all of them fits the accumulator; U0 = base + (sum of the document's
-    marked cells' scaled gains << sh).  Candidates = documents holding a cell the SEARCH probes (depth nprobe)."""
+    depth, scaled by 2^-sh (rounded up) so that the sum over all of them fits the accumulator; U0 = base + (sum of the scaled
+    gains of the marked cells whose posting lists hold the document << sh).  Candidates = documents in a list of a cell the
+    SEARCH probes (depth nprobe).  lists[i] = the cells whose lists hold document i (None: the crate's lists, its codes)."""
+    lists = docs if lists is None else lists
     u = u8_table(QC, s)
     real, _ = probe(QC, nprobe)
     if thr is not None:        # search.rs:417-425: a probed cell is kept iff its best score over the tokens reaches the threshold;
@@ -211,8 +213,8 @@ def gain_bound(QC, s, docs, nprobe, depth, acc_bits=15, thr=None):
         sh += 1
     Gs = np.where(deep, (G + (1 << sh) - 1) >> sh, 0)
     base = int(ut.sum())
-    U0 = np.array([base + (int(Gs[c].sum()) << sh) for c in docs])
-    cand = np.array([bool(real[c].any()) for c in docs])
+    U0 = np.array([base + (int(Gs[c].sum()) << sh) for c in lists])
+    cand = np.array([bool(real[c].any()) for c in lists])
     return U0, cand, base, sh, real, deep
 
 
@@ -260,3 +262,40 @@ def test_zeroth_level_bound_and_cut(seed, nprobe, depth, acc_bits, thr):
     if not seed % 2 and ci.size > 200 and depth >= 8 and thr is None:
         tau0 = nth_largest(Lb[order[:15]], 5) - slack
         assert (U0[ci] < tau0).any()
+
+
+@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("nprobe,depth,thr", [(4, 4, None), (2, 8, None), (8, 32, None), (4, 16, 0.3)])
+def test_zeroth_level_bound_with_extra_list_entries(seed, nprobe, depth, thr):
+    """Posting lists that hold every (document, code) pair and MORE (a document in lists of cells it holds no code in): the
+    extra entries make more candidates and add gains to the sum, so U0 >= U still holds for every candidate -- the lists the
+    zeroth level accepts (np_index.hip ivf_cover_kernel)."""
+    rng = np.random.default_rng(9100 + seed)
+    Lq = int(rng.integers(1, 33))
+    K = 256
+    QC, s, docs = make_instance(rng, K=K, n_docs=500, Lq=Lq, ties=(seed % 3 == 2), codes_per_doc=(1, 4) if seed % 2 else (3, 30))
+    lists = [np.union1d(c, rng.integers(0, K, int(rng.integers(0, 6)))) for c in docs]
+    U0, cand, *_ = gain_bound(QC, s, docs, nprobe, depth, thr=thr, lists=lists)
+    _, cand_codes, *_ = gain_bound(QC, s, docs, nprobe, depth, thr=thr)
+    assert (cand | ~cand_codes).all(), "extra entries only add candidates"
+    u = u8_table(QC, s)
+    U = np.array([u[:, c].max(axis=1).sum() for c in docs])     # the document's bound is set by its CODES
+    assert (U0[cand] >= U[cand]).all(), "the gain sum must dominate the exact bound"
+    assert cand.sum() > cand_codes.sum() or seed % 2, "the extra entries were meant to add candidates"
+
+
+def test_zeroth_level_bound_breaks_on_a_missing_pair():
+    """Why the open checks that the lists cover the codes: one token, cells scoring 1.0, 0.8, 0 and -1, both top cells probed
+    (theta = 0.8, so the best cell carries gain u(1.0) - u(0.8) and the other none).  A document holding both codes but
+    listed only under the second cell is still a candidate and the reference still scores it from its codes (u(1.0)), while
+    the gain sum of the lists that hold it stops at u(0.8): the level would prune a document it must keep."""
+    QC = np.array([[1.0, 0.8, 0.0, -1.0]], np.float32)
+    s = 1.001
+    docs = [np.array([0, 1])]
+    u = u8_table(QC, s)
+    U = u[0, 0]
+    assert U > u[0, 1]
+    U0, cand, *_ = gain_bound(QC, s, docs, nprobe=2, depth=2)
+    assert cand[0] and U0[0] >= U                    # the crate's lists: the bound holds (here with equality)
+    U0, cand, *_ = gain_bound(QC, s, docs, nprobe=2, depth=2, lists=[np.array([1])])
+    assert cand[0] and U0[0] == u[0, 1] < U          # one missing pair: still a candidate, bound broken
