@@ -40,7 +40,8 @@ typedef enum np_status {
   NP_ERR_IO = 5,                 /* Error::Io / Json  (error.rs:21,25) */
   NP_ERR_DEVICE_UNAVAILABLE = 6, /* no usable gfx950 device / HIP runtime failure */
   NP_ERR_OUT_OF_MEMORY = 7,
-  NP_ERR_INVALID_ARGUMENT = 8
+  NP_ERR_INVALID_ARGUMENT = 8,
+  NP_ERR_INDEX_CREATION = 9      /* Error::IndexCreation (error.rs:13) */
 } np_status;
 
 typedef struct np_index np_index; /* opaque: device-resident index (or one document shard of it) */
@@ -135,7 +136,8 @@ const char* np_hip_last_error(void);
  * caller-allocated and have grown (v5: np_info.workspace_bytes, np_stats.ms_hot_level): a host compiled against an older
  * header would have bytes written past its structs before it could read np_info.abi_version.  A host binds this first and
  * refuses a library whose version differs from the header it was built with; np_hip_struct_size lets it check the two
- * layouts it allocates (which: 0 = np_info, 1 = np_stats, 2 = np_search_params, 3 = np_open_opts; -1 for an unknown id). */
+ * layouts it allocates (which: 0 = np_info, 1 = np_stats, 2 = np_search_params, 3 = np_open_opts, 4 = np_kmeans_opts,
+ * 5 = np_kmeans_report, 6 = np_index_config, 7 = np_kmeans_plan; -1 for an unknown id). */
 int np_hip_abi_version(void);
 int64_t np_hip_struct_size(int32_t which);
 
@@ -391,6 +393,104 @@ int np_hip_encode_tokens(const np_index* index, const float* embeddings, int64_t
 int np_hip_rerank_maxsim(int32_t device, const float* query, int32_t n_query_tokens, int32_t dim,
                          const float* doc_embeddings, const int64_t* doc_tok_offsets, int64_t n_docs,
                          float* out_scores, int64_t* out_order);
+
+/* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
+ * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
+ * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.
+ *
+ * k-means is fastkmeans' Lloyd (FastKMeans::train; fastkmeans-rs is not vendored, so the rules are restated here):
+ *  - subsample: n > k * max_points_per_centroid keeps m = k * max_points_per_centroid points, drawn by a partial
+ *    Fisher-Yates (for i in 0..m: j = i + below(n - i), swap) over 0..n-1; the subset is a[0..m) in draw order;
+ *  - init: without an explicit init, centroid c = subset[p[c]] where p is the same partial Fisher-Yates of k over 0..m-1;
+ *  - assign: dist = max(fma(-2, x.c, |x|^2 + |c|^2), 0) in f32 (x.c and the norms as k-ordered f32 FMA chains), argmin
+ *    with the LOWEST centroid index winning equal distances (np_hip_encode_tokens is the opposite: a dot-product argmax,
+ *    last index wins);
+ *  - update: a non-empty cluster takes the mean of its points (exact fixed-point sum, so the bytes never depend on the
+ *    order the GPU visits points in); an empty cluster takes subset[below(m)], drawn in ascending cluster order;
+ *  - shift = sum_k |new_k - old_k| (f32 per cluster, summed in f64 in a fixed order); stop once shift < tol or after
+ *    max_iters iterations.
+ * Random numbers: ONE SplitMix64 stream seeded with `seed` (state += 0x9E3779B97F4A7C15, the standard output mix),
+ * below(b) = the first draw r with r >= (2^64 - b) % b, taken mod b (unbiased).  Draw order: subsample, init,
+ * re-initialisations.  This is NOT the crate's ChaCha8Rng + rand 0.8.5 shuffle stream: for the same seed the document
+ * sample, the point subsample and the init differ from the crate's (the resulting index is equally valid).
+ * Inputs: dim 1..128 (NP_ERR_SHAPE above, as search); non-finite values are refused with NP_ERR_INDEX_CREATION (the
+ * crate would train on them and write garbage). */
+typedef struct np_kmeans_opts {
+  int64_t k;                        /* centroids (> 0, <= points) */
+  int64_t max_points_per_centroid;  /* subsample cap (fastkmeans default 256); 0 = no subsample */
+  uint64_t seed;
+  double tol;                       /* stop once shift < tol (compute_kmeans: 1e-8) */
+  int32_t max_iters;                /* Lloyd iterations at most (compute_kmeans: kmeans_niters) */
+  int32_t reserved0;
+} np_kmeans_opts;
+
+typedef struct np_kmeans_report {
+  int32_t iterations;       /* Lloyd iterations run */
+  int32_t reserved0;
+  double shift;             /* shift of the last iteration */
+  int64_t n_points;         /* points k-means ran on (after the subsample) */
+  int64_t n_reinit;         /* empty clusters re-initialised, summed over the iterations */
+  double ms_assign;         /* device time of the assign step (distance GEMM + argmin), summed over the iterations */
+  double ms_update;         /* device time of the update step (count, scatter, means, re-init, shift) */
+} np_kmeans_report;
+
+/* The IndexConfig fields that apply (index.rs:60-112; defaults in parentheses; 0 selects the default). */
+typedef struct np_index_config {
+  int32_t nbits;                    /* 4 */
+  int32_t kmeans_niters;            /* 4 */
+  int64_t batch_size;               /* 50 000: documents per chunk */
+  uint64_t seed;                    /* 42 (a seed is required: there is no entropy-seeded mode) */
+  int64_t max_points_per_centroid;  /* 256 */
+  int64_t n_samples_kmeans;         /* 0 = the heuristic */
+  int64_t num_partitions;           /* 0 = the heuristic (ComputeKmeansConfig.num_partitions) */
+  int64_t start_from_scratch;       /* 999; < 0 = never write embeddings.npy */
+} np_index_config;
+
+/* What compute_kmeans / prepare_codec_artifacts will do for these document lengths (host only, no device). */
+typedef struct np_kmeans_plan {
+  int64_t n_samples;        /* documents sampled for k-means: min(floor(1 + 16 sqrt(120 N)), N) or n_samples_kmeans */
+  int64_t sample_tokens;    /* tokens of those documents */
+  int64_t num_partitions;   /* 2^floor(log2(16 sqrt(avg_tokens_per_sampled_doc * N))) or cfg->num_partitions */
+  int64_t k;                /* min(num_partitions, sample_tokens): the centroids k-means computes */
+  int64_t codec_samples;    /* max(1, min(N, floor(16 sqrt(120 N)))) (prepare_codec_artifacts) */
+  int64_t heldout_size;     /* floor(min(0.05 T, 50000)) */
+  int64_t heldout_tokens;   /* tokens the held-out walk collects (<= heldout_size) */
+} np_kmeans_plan;
+
+/* kmeans.rs:261-311 + index.rs:199-226 formulas.  out_sample_ids (nullable, capacity n_docs): the k-means document
+ * sample, the first n_samples entries of the seeded document shuffle (prepare_codec_artifacts takes the first
+ * codec_samples entries of the same shuffle). */
+int np_hip_kmeans_plan(const int64_t* doc_lengths, int64_t n_docs, const np_index_config* cfg, np_kmeans_plan* out,
+                       int64_t* out_sample_ids);
+
+/* FastKMeans::train on flat points [n][dim] (host pointers).  init (nullable): [k][dim] initial centroids.
+ * out_centroids [k][dim] (NOT normalised).  out_assign (nullable) [n]: the last iteration's assignment of every input
+ * point, -1 for points outside the subsample.  report nullable. */
+int np_hip_kmeans(int32_t device, const float* points, int64_t n, int32_t dim, const np_kmeans_opts* opts,
+                  const float* init, float* out_centroids, int64_t* out_assign, np_kmeans_report* report);
+
+/* compute_kmeans (kmeans.rs:261-421): document sample, K heuristic, k-means (tol 1e-8), rows L2-normalised by
+ * max(|row|, 1e-12).  embeddings = every document's tokens concatenated ([sum doc_lengths][dim]).  out_centroids has
+ * room for capacity_k rows (np_hip_kmeans_plan's k); *out_k = the rows written. */
+int np_hip_compute_kmeans(int32_t device, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs,
+                          int32_t dim, const np_index_config* cfg, float* out_centroids, int64_t capacity_k,
+                          int64_t* out_k, np_kmeans_report* report);
+
+/* prepare_codec_artifacts (index.rs:182-287): held-out tokens of the codec sample walked in reverse, codes by
+ * np_hip_encode_tokens' rule, f32 residuals x - c, cluster_threshold = quantile(|r|, 0.75), avg_residual[j] = sequential
+ * f32 sum of |r_j| / rows, bucket_cutoffs [2^nbits - 1] at i / 2^nbits, bucket_weights [2^nbits] at (i + 0.5) / 2^nbits
+ * (quantile rule of utils.rs:94-149).  Any output pointer may be NULL. */
+int np_hip_prepare_codec_artifacts(int32_t device, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs,
+                                   int32_t dim, const float* centroids, int64_t k, const np_index_config* cfg,
+                                   float* out_bucket_cutoffs, float* out_bucket_weights, float* out_avg_residual,
+                                   float* out_cluster_threshold);
+
+/* MmapIndex::create_with_kmeans (index.rs:927-967, 551-...): compute_kmeans, prepare_codec_artifacts, every token
+ * encoded on the GPU (np_hip_encode_tokens), the directory written by np_hip_index_write_dir in chunks of batch_size
+ * documents, embeddings.npy + embeddings_lengths.json when n_docs <= start_from_scratch (update.rs:308-346).
+ * opts->device selects the GPU (opts nullable: device 0).  out (nullable): the created index, opened with opts. */
+int np_hip_index_create(const char* index_dir, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs,
+                        int32_t dim, const np_index_config* cfg, const np_open_opts* opts, np_index** out);
 
 /* Stage-level debug access for parity tests: runs S1-S5 for ONE query and copies out the probed
  * cells (ascending), candidate doc ids (ascending, global), their approximate scores, and the

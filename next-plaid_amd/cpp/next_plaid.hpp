@@ -41,7 +41,8 @@
 namespace next_plaid {
 
 struct Error : std::runtime_error {  // error.rs:9-66
-  enum Kind { IndexLoad = 1, Search = 2, Shape = 3, Codec = 4, Io = 5, DeviceUnavailable = 6, OutOfMemory = 7, Config = 8 };
+  enum Kind { IndexLoad = 1, Search = 2, Shape = 3, Codec = 4, Io = 5, DeviceUnavailable = 6, OutOfMemory = 7, Config = 8,
+              IndexCreation = 9 };
   Kind kind;
   Error(int code, const char* msg) : std::runtime_error(msg && *msg ? msg : "next-plaid error"), kind((Kind)code) {}
 };
@@ -116,8 +117,106 @@ inline CpuSearchFn& cpu_fallback() {
 }
 inline void set_cpu_fallback(CpuSearchFn f) { cpu_fallback() = std::move(f); }
 
+// IndexConfig (index.rs:60-112): the fields index creation reads, same defaults.  start_from_scratch < 0: never write
+// embeddings.npy.
+struct IndexConfig {
+  int nbits = 4;
+  int64_t batch_size = 50000;
+  uint64_t seed = 42;
+  int kmeans_niters = 4;
+  int64_t max_points_per_centroid = 256;
+  std::optional<int64_t> n_samples_kmeans;
+  int64_t start_from_scratch = 999;
+  np_index_config c(int64_t num_partitions = 0) const {
+    np_index_config o{};
+    o.nbits = nbits;
+    o.kmeans_niters = kmeans_niters;
+    o.batch_size = batch_size;
+    o.seed = seed;
+    o.max_points_per_centroid = max_points_per_centroid;
+    o.n_samples_kmeans = n_samples_kmeans.value_or(0);
+    o.num_partitions = num_partitions;
+    o.start_from_scratch = start_from_scratch == 0 ? -1 : start_from_scratch;
+    return o;
+  }
+};
+
+// Documents for index creation: every document's token rows concatenated ([sum doc_lengths][dim], row-major).
+struct Documents {
+  const float* embeddings = nullptr;
+  std::vector<int64_t> doc_lengths;
+  size_t dim = 0;
+};
+
+// kmeans.rs:423-...: the number of centroids compute_kmeans computes (host only)
+inline int64_t estimate_num_partitions(const std::vector<int64_t>& doc_lengths, const IndexConfig& cfg = {}) {
+  np_index_config c = cfg.c();
+  np_kmeans_plan p{};
+  check(np_hip_kmeans_plan(doc_lengths.data(), (int64_t)doc_lengths.size(), &c, &p, nullptr));
+  return p.k;
+}
+
+// FastKMeans::train on the GPU: centroids [k][dim] (not normalised); assign (optional) = the last iteration's assignment,
+// -1 outside the subsample
+inline std::vector<float> kmeans(const float* points, int64_t n, size_t dim, const np_kmeans_opts& opts,
+                                 const float* init = nullptr, std::vector<int64_t>* assign = nullptr,
+                                 np_kmeans_report* report = nullptr, int device = 0) {
+  std::vector<float> out((size_t)std::max<int64_t>(opts.k, 1) * dim);
+  if (assign) assign->assign((size_t)std::max<int64_t>(n, 1), -1);
+  check(np_hip_kmeans(device, points, n, (int32_t)dim, &opts, init, out.data(), assign ? assign->data() : nullptr, report));
+  out.resize((size_t)std::max<int64_t>(opts.k, 0) * dim);
+  if (assign) assign->resize((size_t)n);
+  return out;
+}
+
+// compute_kmeans (kmeans.rs:261-421): L2-normalised centroids [K][dim]
+inline std::vector<float> compute_kmeans(const Documents& docs, const IndexConfig& cfg = {}, int64_t num_partitions = 0,
+                                         int device = 0) {
+  np_index_config c = cfg.c(num_partitions);
+  np_kmeans_plan p{};
+  check(np_hip_kmeans_plan(docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(), &c, &p, nullptr));
+  std::vector<float> out((size_t)std::max<int64_t>(p.k, 1) * docs.dim);
+  int64_t k = 0;
+  check(np_hip_compute_kmeans(device, docs.embeddings, docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(),
+                              (int32_t)docs.dim, &c, out.data(), p.k, &k, nullptr));
+  out.resize((size_t)k * docs.dim);
+  return out;
+}
+
+// prepare_codec_artifacts (index.rs:182-287)
+struct CodecArtifacts {
+  std::vector<float> bucket_cutoffs, bucket_weights, avg_residual;
+  float cluster_threshold = 0.f;
+};
+inline CodecArtifacts prepare_codec_artifacts(const Documents& docs, const std::vector<float>& centroids,
+                                              const IndexConfig& cfg = {}, int device = 0) {
+  np_index_config c = cfg.c();
+  CodecArtifacts a;
+  a.bucket_cutoffs.resize(((size_t)1 << cfg.nbits) - 1);
+  a.bucket_weights.resize((size_t)1 << cfg.nbits);
+  a.avg_residual.resize(docs.dim);
+  check(np_hip_prepare_codec_artifacts(device, docs.embeddings, docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(),
+                                       (int32_t)docs.dim, centroids.data(), (int64_t)(centroids.size() / std::max<size_t>(docs.dim, 1)),
+                                       &c, a.bucket_cutoffs.data(), a.bucket_weights.data(), a.avg_residual.data(),
+                                       &a.cluster_threshold));
+  return a;
+}
+
 class MmapIndex {
  public:
+  // MmapIndex::create_with_kmeans (index.rs:927-967): k-means and codec training on the GPU, the crate's file set written
+  // under index_path, then the index opened with `opts`.  Index creation has no CPU fallback here: a device failure is
+  // the caller's to route to the crate's CPU path.
+  static MmapIndex create_with_kmeans(const Documents& docs, const std::string& index_path, const IndexConfig& cfg = {},
+                                      const np_open_opts* opts = nullptr) {
+    check_abi();
+    np_index_config c = cfg.c();
+    np_index* h = nullptr;
+    check(np_hip_index_create(index_path.c_str(), docs.embeddings, docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(),
+                              (int32_t)docs.dim, &c, opts, &h));
+    return MmapIndex(h, index_path);
+  }
+
   // MmapIndex::load (index.rs:1026).  `opts` selects the device / document shard.
   // Policy: FORCE_CPU or a raised broken flag never touch the device (the handle stays empty and searches go to the
   // CPU hook); a device failure raises the flag and falls back unless FORCE_GPU; every other error is the caller's.

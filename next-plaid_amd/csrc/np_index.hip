@@ -1605,6 +1605,10 @@ int64_t np_hip_struct_size(int32_t which) {
     case 1: return (int64_t)sizeof(np_stats);
     case 2: return (int64_t)sizeof(np_search_params);
     case 3: return (int64_t)sizeof(np_open_opts);
+    case 4: return (int64_t)sizeof(np_kmeans_opts);
+    case 5: return (int64_t)sizeof(np_kmeans_report);
+    case 6: return (int64_t)sizeof(np_index_config);
+    case 7: return (int64_t)sizeof(np_kmeans_plan);
     default: return -1;
   }
 }

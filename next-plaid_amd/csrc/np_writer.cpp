@@ -125,6 +125,14 @@ static std::string fmt_double(double v) {   // shortest decimal that parses back
 }
 
 }  // namespace
+
+// for np_build.hip (embeddings.npy / embeddings_lengths.json of the create path): the same temporary-name writers
+int write_npy_file(const std::string& path, const char* descr, const int64_t* shape, int ndim, const void* data,
+                   size_t bytes) {
+  return write_npy(path, descr, shape, ndim, data, bytes);
+}
+int write_text_file(const std::string& path, const std::string& text) { return write_text(path, text); }
+
 }  // namespace np
 
 using namespace np;

@@ -53,8 +53,12 @@ class DeviceUnavailableError(NextPlaidError):
     """No usable gfx950 device or the HIP library is missing."""
 
 
+class IndexCreationError(NextPlaidError):
+    """Error::IndexCreation"""
+
+
 _ERR = {1: IndexLoadError, 2: SearchError, 3: ShapeError, 4: CodecError, 5: IoError,
-        6: DeviceUnavailableError, 7: MemoryError, 8: ValueError}
+        6: DeviceUnavailableError, 7: MemoryError, 8: ValueError, 9: IndexCreationError}
 
 
 # ---- C structs -----------------------------------------------------------------------------------
@@ -113,6 +117,30 @@ class np_synth_spec(C.Structure):
                 ("bucket_weights", C.c_void_p), ("len_table", C.c_void_p), ("len_table_size", C.c_int32)]
 
 
+class np_kmeans_opts(C.Structure):
+    _fields_ = [("k", C.c_int64), ("max_points_per_centroid", C.c_int64), ("seed", C.c_uint64), ("tol", C.c_double),
+                ("max_iters", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class np_kmeans_report(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("reserved0", C.c_int32), ("shift", C.c_double), ("n_points", C.c_int64),
+                ("n_reinit", C.c_int64), ("ms_assign", C.c_double), ("ms_update", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+class np_index_config(C.Structure):
+    _fields_ = [("nbits", C.c_int32), ("kmeans_niters", C.c_int32), ("batch_size", C.c_int64), ("seed", C.c_uint64),
+                ("max_points_per_centroid", C.c_int64), ("n_samples_kmeans", C.c_int64), ("num_partitions", C.c_int64),
+                ("start_from_scratch", C.c_int64)]
+
+
+class np_kmeans_plan(C.Structure):
+    _fields_ = [("n_samples", C.c_int64), ("sample_tokens", C.c_int64), ("num_partitions", C.c_int64), ("k", C.c_int64),
+                ("codec_samples", C.c_int64), ("heldout_size", C.c_int64), ("heldout_tokens", C.c_int64)]
+
+
 # np_all_gather_host_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes)
 ALL_GATHER_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 NP_COMM_DEFERRED_STATUS = 1
@@ -129,6 +157,7 @@ EXPORTS = [
     "np_hip_comm_unique_id", "np_hip_comm_create", "np_hip_comm_create_hosted", "np_hip_comm_status", "np_hip_comm_destroy",
     "np_hip_search_batch_sharded",
     "np_hip_decompress_documents", "np_hip_encode_tokens", "np_hip_rerank_maxsim", "np_hip_debug_trace",
+    "np_hip_kmeans_plan", "np_hip_kmeans", "np_hip_compute_kmeans", "np_hip_prepare_codec_artifacts", "np_hip_index_create",
 ]
 
 _lib = None
@@ -180,7 +209,8 @@ def lib():
     ver = int(L.np_hip_abi_version())
     if ver != NP_ABI_VERSION:
         raise DeviceUnavailableError(f"{path} speaks ABI v{ver}, this mirror v{NP_ABI_VERSION}: rebuild the library")
-    for which, st in ((0, np_info), (1, np_stats), (2, np_search_params), (3, np_open_opts)):
+    for which, st in ((0, np_info), (1, np_stats), (2, np_search_params), (3, np_open_opts), (4, np_kmeans_opts),
+                      (5, np_kmeans_report), (6, np_index_config), (7, np_kmeans_plan)):
         if int(L.np_hip_struct_size(which)) != C.sizeof(st):
             raise DeviceUnavailableError(f"{path}: sizeof({st.__name__}) is {int(L.np_hip_struct_size(which))} in the library, "
                                          f"{C.sizeof(st)} in this mirror")
@@ -230,6 +260,13 @@ def lib():
     L.np_hip_rerank_maxsim.argtypes = [i32, vp, i32, i32, vp, vp, i64, vp, vp]
     L.np_hip_debug_trace.argtypes = [vp, vp, i32, i32, C.POINTER(np_search_params), vp, i64,
                                      vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]
+    L.np_hip_kmeans_plan.argtypes = [vp, i64, C.POINTER(np_index_config), C.POINTER(np_kmeans_plan), vp]
+    L.np_hip_kmeans.argtypes = [i32, vp, i64, i32, C.POINTER(np_kmeans_opts), vp, vp, vp, C.POINTER(np_kmeans_report)]
+    L.np_hip_compute_kmeans.argtypes = [i32, vp, vp, i64, i32, C.POINTER(np_index_config), vp, i64, C.POINTER(i64),
+                                        C.POINTER(np_kmeans_report)]
+    L.np_hip_prepare_codec_artifacts.argtypes = [i32, vp, vp, i64, i32, vp, i64, C.POINTER(np_index_config), vp, vp, vp, vp]
+    L.np_hip_index_create.argtypes = [C.c_char_p, vp, vp, i64, i32, C.POINTER(np_index_config), C.POINTER(np_open_opts),
+                                      C.POINTER(vp)]
     _lib = L
     return L
 
@@ -360,6 +397,140 @@ class SearchParameters:
 
 
 @dataclass
+class IndexConfig:
+    """IndexConfig (index.rs:60-112): the fields that apply to index creation, same names and defaults.  `seed` is
+    required here (the crate's None = an entropy seed has no counterpart); start_from_scratch < 0 never writes
+    embeddings.npy."""
+    nbits: int = 4
+    batch_size: int = 50_000
+    seed: int = 42
+    kmeans_niters: int = 4
+    max_points_per_centroid: int = 256
+    n_samples_kmeans: int | None = None
+    start_from_scratch: int = 999
+
+    # serde (index.rs:60-112): every field but nbits has a default; unknown fields (force_cpu, fts_tokenizer) are ignored
+    @classmethod
+    def from_json(cls, text) -> "IndexConfig":
+        import json
+        d = json.loads(text) if isinstance(text, (str, bytes)) else dict(text)
+        if "nbits" not in d:
+            raise ValueError("missing field `nbits`")
+        for k in ("nbits", "batch_size", "kmeans_niters", "max_points_per_centroid", "start_from_scratch"):
+            if k in d and (isinstance(d[k], bool) or not isinstance(d[k], int) or d[k] < 0):
+                raise ValueError(f"invalid type for `{k}`: expected usize")
+        seed = d.get("seed", 42)
+        ns = d.get("n_samples_kmeans")
+        return cls(nbits=d["nbits"], batch_size=d.get("batch_size", 50_000), seed=42 if seed is None else int(seed),
+                   kmeans_niters=d.get("kmeans_niters", 4), max_points_per_centroid=d.get("max_points_per_centroid", 256),
+                   n_samples_kmeans=None if ns is None else int(ns), start_from_scratch=d.get("start_from_scratch", 999))
+
+    def to_json(self) -> str:
+        import json
+        return json.dumps(dict(nbits=self.nbits, batch_size=self.batch_size, seed=self.seed, kmeans_niters=self.kmeans_niters,
+                               max_points_per_centroid=self.max_points_per_centroid, n_samples_kmeans=self.n_samples_kmeans,
+                               start_from_scratch=self.start_from_scratch))
+
+    def _c(self, num_partitions: int | None = None) -> np_index_config:
+        for k in ("nbits", "batch_size", "kmeans_niters", "max_points_per_centroid"):
+            if int(getattr(self, k)) <= 0:
+                raise ValueError(f"IndexConfig.{k} must be > 0")
+        return np_index_config(int(self.nbits), int(self.kmeans_niters), int(self.batch_size), int(self.seed) & (2**64 - 1),
+                               int(self.max_points_per_centroid), int(self.n_samples_kmeans or 0), int(num_partitions or 0),
+                               -1 if int(self.start_from_scratch) == 0 else int(self.start_from_scratch))
+
+
+def _docs(documents):
+    """List of [n_i, dim] arrays -> (flat f32 [sum n_i, dim], lengths i64, dim)."""
+    docs = [np.ascontiguousarray(d, np.float32) for d in documents]
+    if not docs:
+        raise IndexCreationError("Index creation failed: No documents provided")
+    dim = docs[0].shape[1] if docs[0].ndim == 2 else -1
+    for d in docs:
+        if d.ndim != 2 or d.shape[1] != dim:
+            raise ShapeError(f"Shape error: document has shape {d.shape}, expected [n, {dim}]")
+    lens = np.array([d.shape[0] for d in docs], np.int64)
+    flat = np.concatenate(docs, 0) if lens.sum() > 0 else np.zeros((1, max(dim, 1)), np.float32)
+    return np.ascontiguousarray(flat, np.float32), lens, dim
+
+
+def kmeans_plan(doc_lengths, config: IndexConfig | None = None, num_partitions: int | None = None):
+    """Host only: what compute_kmeans / prepare_codec_artifacts do for these document lengths (kmeans.rs:261-311,
+    index.rs:199-226).  Returns (np_kmeans_plan as a dict, sampled document ids in shuffled order)."""
+    cfg = (config or IndexConfig())._c(num_partitions)
+    dl = np.ascontiguousarray(doc_lengths, np.int64)
+    p = np_kmeans_plan()
+    ids = np.zeros(max(dl.size, 1), np.int64)
+    _check(lib().np_hip_kmeans_plan(_ptr(dl), dl.size, C.byref(cfg), C.byref(p), _ptr(ids)))
+    return {k: int(getattr(p, k)) for k, _ in p._fields_}, ids[: p.n_samples].copy()
+
+
+def estimate_num_partitions(documents, config: IndexConfig | None = None) -> int:
+    """The number of centroids compute_kmeans computes for these documents (kmeans.rs:423-...)."""
+    lens = np.array([np.shape(d)[0] for d in documents], np.int64)
+    if lens.size == 0:
+        raise IndexCreationError("Index creation failed: No documents provided")
+    return kmeans_plan(lens, config)[0]["k"]
+
+
+def kmeans(points, k: int, max_iters: int = 4, tol: float = 1e-8, seed: int = 0, max_points_per_centroid: int = 256,
+           init=None, device: int = 0, return_assign: bool = False):
+    """FastKMeans::train on the GPU (rules: include/nextplaid_hip.h).  Returns (centroids [k, dim], report dict) or,
+    with return_assign, (centroids, assignment i64 [n] with -1 outside the subsample, report)."""
+    x = np.ascontiguousarray(points, np.float32)
+    if x.ndim != 2:
+        raise ShapeError(f"Shape error: points have shape {x.shape}")
+    n, dim = x.shape
+    o = np_kmeans_opts(int(k), int(max_points_per_centroid), int(seed) & (2**64 - 1), float(tol), int(max_iters), 0)
+    ini = None
+    if init is not None:
+        ini = np.ascontiguousarray(init, np.float32)
+        if ini.shape != (int(k), dim):
+            raise ShapeError(f"Shape error: init has shape {ini.shape}, expected {(int(k), dim)}")
+    out = np.zeros((max(int(k), 1), max(dim, 1)), np.float32)
+    asg = np.zeros(max(n, 1), np.int64) if return_assign else None
+    rep = np_kmeans_report()
+    _check(lib().np_hip_kmeans(int(device), _ptr(x) if n else None, n, dim, C.byref(o), _ptr(ini), _ptr(out), _ptr(asg),
+                               C.byref(rep)))
+    cen = out[: int(k), :dim]
+    if return_assign:
+        return cen, asg[:n], rep.as_dict()
+    return cen, rep.as_dict()
+
+
+def compute_kmeans(documents, config: IndexConfig | None = None, num_partitions: int | None = None, device: int = 0,
+                   return_report: bool = False):
+    """compute_kmeans (kmeans.rs:261-421) on the GPU: L2-normalised centroids [K, dim]."""
+    flat, lens, dim = _docs(documents)
+    cfg = (config or IndexConfig())._c(num_partitions)
+    p, _ = kmeans_plan(lens, config, num_partitions)
+    out = np.zeros((max(p["k"], 1), max(dim, 1)), np.float32)
+    k = C.c_int64(0)
+    rep = np_kmeans_report()
+    _check(lib().np_hip_compute_kmeans(int(device), _ptr(flat), _ptr(lens), lens.size, dim, C.byref(cfg), _ptr(out),
+                                       out.shape[0], C.byref(k), C.byref(rep)))
+    cen = out[: k.value]
+    return (cen, rep.as_dict()) if return_report else cen
+
+
+def prepare_codec_artifacts(documents, centroids, config: IndexConfig | None = None, device: int = 0) -> dict:
+    """prepare_codec_artifacts (index.rs:182-287): bucket_cutoffs, bucket_weights, avg_residual, cluster_threshold."""
+    flat, lens, dim = _docs(documents)
+    cfg = (config or IndexConfig())._c()
+    cen = np.ascontiguousarray(centroids, np.float32)
+    if cen.ndim != 2 or cen.shape[1] != dim:
+        raise ShapeError(f"Shape error: centroids have shape {cen.shape}, documents dim {dim}")
+    nb = 1 << int(cfg.nbits)
+    cut = np.zeros(nb - 1, np.float32)
+    w = np.zeros(nb, np.float32)
+    avg = np.zeros(max(dim, 1), np.float32)
+    thr = C.c_float(0.0)
+    _check(lib().np_hip_prepare_codec_artifacts(int(device), _ptr(flat), _ptr(lens), lens.size, dim, _ptr(cen), cen.shape[0],
+                                                C.byref(cfg), _ptr(cut), _ptr(w), _ptr(avg), C.byref(thr)))
+    return dict(bucket_cutoffs=cut, bucket_weights=w, avg_residual=avg[:dim], cluster_threshold=np.float32(thr.value))
+
+
+@dataclass
 class QueryResult:
     """search.rs:71-80"""
     query_id: int
@@ -390,6 +561,18 @@ class MmapIndex:
         h = C.c_void_p()
         o = _opts(**opts)
         _check(lib().np_hip_index_open(os.fsencode(index_path), C.byref(o), C.byref(h)))
+        return cls(h, index_path, opts)
+
+    @classmethod
+    def create_with_kmeans(cls, documents, index_path: str, config: IndexConfig | None = None, **opts) -> "MmapIndex":
+        """MmapIndex::create_with_kmeans (index.rs:927-967): k-means and codec training on the GPU, every token encoded by
+        np_hip_encode_tokens, the crate's file set written under index_path, then the index opened with opts (as load)."""
+        flat, lens, dim = _docs(documents)
+        cfg = (config or IndexConfig())._c()
+        o = _opts(**opts)
+        h = C.c_void_p()
+        _check(lib().np_hip_index_create(os.fsencode(index_path), _ptr(flat), _ptr(lens), lens.size, dim, C.byref(cfg),
+                                         C.byref(o), C.byref(h)))
         return cls(h, index_path, opts)
 
     def reload(self):
