@@ -405,8 +405,11 @@ int np_hip_rerank_maxsim(int32_t device, const float* query, int32_t n_query_tok
  *  - assign: dist = max(fma(-2, x.c, |x|^2 + |c|^2), 0) in f32 (x.c and the norms as k-ordered f32 FMA chains), argmin
  *    with the LOWEST centroid index winning equal distances (np_hip_encode_tokens is the opposite: a dot-product argmax,
  *    last index wins);
- *  - update: a non-empty cluster takes the mean of its points (exact fixed-point sum, so the bytes never depend on the
- *    order the GPU visits points in); an empty cluster takes subset[below(m)], drawn in ascending cluster order;
+ *  - update: a non-empty cluster takes the mean of its points: a 64-bit fixed-point sum on the cluster's own scale
+ *    2^S, S = 62 - e - ceil(log2 count) with max |x_j| < 2^e over the cluster's points (exact, so the bytes never depend
+ *    on the order the GPU visits points in), divided by the count in f64 and rounded to f32.  The mean is within 1 f32
+ *    ulp of the exact mean plus 2^(-S-1) < 2 max|x_j| count 2^-62, which depends only on the cluster's own points; an
+ *    empty cluster takes subset[below(m)], drawn in ascending cluster order;
  *  - shift = sum_k |new_k - old_k| (f32 per cluster, summed in f64 in a fixed order); stop once shift < tol or after
  *    max_iters iterations.
  * Random numbers: ONE SplitMix64 stream seeded with `seed` (state += 0x9E3779B97F4A7C15, the standard output mix),
@@ -414,7 +417,8 @@ int np_hip_rerank_maxsim(int32_t device, const float* query, int32_t n_query_tok
  * re-initialisations.  This is NOT the crate's ChaCha8Rng + rand 0.8.5 shuffle stream: for the same seed the document
  * sample, the point subsample and the init differ from the crate's (the resulting index is equally valid).
  * Inputs: dim 1..128 (NP_ERR_SHAPE above, as search); non-finite values are refused with NP_ERR_INDEX_CREATION (the
- * crate would train on them and write garbage). */
+ * crate would train on them and write garbage), and so are values above min(1e18, sqrt(0.999 FLT_MAX / (4 dim))): below
+ * that bound no f32 distance can overflow to +inf. */
 typedef struct np_kmeans_opts {
   int64_t k;                        /* centroids (> 0, <= points) */
   int64_t max_points_per_centroid;  /* subsample cap (fastkmeans default 256); 0 = no subsample */

@@ -4,21 +4,23 @@
 //   compute_kmeans (kmeans.rs:261-421) -> prepare_codec_artifacts (index.rs:182-287) -> encode + write (index.rs:551-...)
 // and k-means is the only heavy computation in it: one Lloyd iteration is 2 n k d FLOP (1.8e16 at the crate's heuristic for
 // 10 M documents x 300 tokens).  Rules of each piece: include/nextplaid_hip.h; the kernels (DESIGN.md "k-means kernels"):
-//   km_norm_kernel        |x|^2 per point as a k-ordered f32 FMA chain (once per call)
+//   km_norm_kernel        |x|^2 per point as a k-ordered f32 FMA chain, and max |x_j| (once per call)
 //   km_tiles_kernel       centroids -> k-major 32-centroid tiles [d][32] + their |c|^2 (once per iteration)
 //   km_assign_kernel      fused distance GEMM + argmin on exact-f32 MFMA 32x32x2: a wave holds 2 x 32 points as B fragments in
 //                         registers and streams the centroid tiles through LDS as A fragments; the epilogue forms
 //                         max(fma(-2, x.c, |x|^2 + |c|^2), 0) and keeps each point's minimum of (distance bits << 32 | index);
 //                         centroid chunks of a point combine by a 64-bit atomicMin: the minimum distance, the lowest index on
 //                         ties, in any order.  No n x k matrix is written.
-//   km_count_kernel       assignment + cluster sizes (integer atomics: order-free)
+//   km_count_kernel       assignment, cluster sizes and each cluster's max |x_j| (integer atomics: order-free)
 //   km_scatter_kernel     counting sort of the point ids by cluster (the order inside a cluster is arbitrary ...)
-//   km_mean_kernel        ... because each cluster sums its points in 64-bit fixed point (exact, so associative): the means,
-//                         the re-initialised empty clusters and |new - old| per cluster, one workgroup per cluster
+//   km_mean_kernel        ... because each cluster sums its points in 64-bit fixed point (exact, so associative) on a scale
+//                         set by its own max |x_j| and size: the means, the re-initialised empty clusters and |new - old|
+//                         per cluster, one workgroup per cluster
 //   km_shift_kernel       shift = the sum of |new - old| in f64 in a fixed order
 // Held-out statistics, sorting and quantiles are host code (at most 50 000 tokens).
 #include "np_internal.h"
 
+#include <float.h>
 #include <math.h>
 #include <string.h>
 
@@ -87,13 +89,18 @@ float quantile_sorted(const std::vector<float>& v, double q) {
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) km_norm_kernel(const float* __restrict__ X, int64_t n, int D, float* __restrict__ out) {
+__global__ void __launch_bounds__(256) km_norm_kernel(const float* __restrict__ X, int64_t n, int D, float* __restrict__ out,
+                                                      float* __restrict__ amax) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float* x = X + i * D;
-  float s = 0.f;
-  for (int d = 0; d < D; ++d) s = fmaf(x[d], x[d], s);
+  float s = 0.f, m = 0.f;
+  for (int d = 0; d < D; ++d) {
+    s = fmaf(x[d], x[d], s);
+    m = fmaxf(m, fabsf(x[d]));
+  }
   out[i] = s;
+  amax[i] = m;
 }
 
 // tile t = centroids 32t .. 32t+31: [D][32] k-major values, then 32 squared norms (+inf for the padding rows past k:
@@ -209,13 +216,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D == 1
   }
 }
 
-__global__ void __launch_bounds__(256) km_count_kernel(const unsigned long long* __restrict__ best, int64_t n,
-                                                       int32_t* __restrict__ assign, int32_t* __restrict__ counts) {
+// cmax[c] = the bits of max |x_j| over the cluster's points (non-negative floats order as their bit patterns)
+__global__ void __launch_bounds__(256) km_count_kernel(const unsigned long long* __restrict__ best, const float* __restrict__ amax,
+                                                       int64_t n, int32_t* __restrict__ assign, int32_t* __restrict__ counts,
+                                                       uint32_t* __restrict__ cmax) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int32_t c = (int32_t)(uint32_t)best[i];
   assign[i] = c;
   atomicAdd(counts + c, 1);
+  atomicMax(cmax + c, __float_as_uint(amax[i]));
 }
 
 __global__ void __launch_bounds__(256) km_scatter_kernel(const int32_t* __restrict__ assign, int64_t n,
@@ -227,13 +237,15 @@ __global__ void __launch_bounds__(256) km_scatter_kernel(const int32_t* __restri
   order[off[c] + atomicAdd(cursor + c, 1)] = (int32_t)i;
 }
 
-// One workgroup per cluster.  Sum of the points in fixed point q = rint(x 2^S) (exact: |sum| < 2^62 by the choice of S),
-// mean = (f64) sum 2^-S / count rounded to f32.  An empty cluster takes row reinit[c] of X.  part[c] = |new - old| (f32,
+// One workgroup per cluster.  Sum of the points in fixed point q = rint(x 2^S) with the cluster's own scale
+// S = 62 - e - ceil(log2 count), max |x_j| < 2^e: every |q| <= 2^(62 - ceil(log2 count)), so |sum| <= 2^62 and the sum is
+// exact.  mean = (f64) sum 2^-S / count rounded to f32: within 1 ulp of the exact mean plus the quantisation
+// 2^(-S-1) < 2 max|x_j| count 2^-62, which depends only on the cluster's own points.  An empty cluster takes row reinit[c] of X.  part[c] = |new - old| (f32,
 // k-ordered FMA chain of the squared differences).
 template <int D>
 __global__ void __launch_bounds__(256) km_mean_kernel(const float* __restrict__ X, const int32_t* __restrict__ order,
                                                       const int32_t* __restrict__ off, const int32_t* __restrict__ reinit,
-                                                      double scale, double inv_scale, const float* __restrict__ Cold,
+                                                      const uint32_t* __restrict__ cmax, const float* __restrict__ Cold,
                                                       float* __restrict__ Cnew, float* __restrict__ part) {
   constexpr int DL = (D + 63) / 64;   // dims per lane
   __shared__ long long s_sum[4][D];
@@ -243,6 +255,10 @@ __global__ void __launch_bounds__(256) km_mean_kernel(const float* __restrict__ 
   const float* old = Cold + (int64_t)c * D;
   float* nw = Cnew + (int64_t)c * D;
   if (e > b) {
+    int ex = 0, lg = 0;
+    (void)frexpf(__uint_as_float(cmax[c]), &ex);   // max |x_j| < 2^ex (ex = 0 for an all-zero cluster: any scale is exact)
+    while (((int64_t)1 << lg) < (int64_t)(e - b)) ++lg;
+    const double scale = ldexp(1.0, 62 - ex - lg), inv_scale = ldexp(1.0, ex + lg - 62);
     long long acc[DL];
 #pragma unroll
     for (int j = 0; j < DL; ++j) acc[j] = 0;
@@ -345,8 +361,13 @@ int check_dim(int dim) {
   return NP_OK;
 }
 
-// non-finite values are refused: the crate would train on them and write an index of NaN centroids.  Also returns max |x|
-int check_finite(const float* x, int64_t count, float* amax) {
+// the largest |x_j| index creation takes at this dim: |x - c|^2 <= 4 dim B^2 stays below FLT_MAX (with 0.1 % left for
+// the rounding of the f32 chains), so no distance is +inf; never above 1e18
+double magnitude_bound(int dim) { return std::min(1.0e18, sqrt(0.999 * (double)FLT_MAX / (4.0 * (double)dim))); }
+
+// non-finite values are refused: the crate would train on them and write an index of NaN centroids.  So are values
+// above magnitude_bound(dim), whose f32 distances could overflow
+int check_finite(const float* x, int64_t count, int dim) {
   float m = 0.f;
   for (int64_t i = 0; i < count; ++i) {
     const float a = fabsf(x[i]);
@@ -356,12 +377,11 @@ int check_finite(const float* x, int64_t count, float* amax) {
     }
     m = std::max(m, a);
   }
-  // |x|^2 and the distances must not overflow f32
-  if (m > 1.0e18f) {
-    set_error("Index creation failed: embedding values up to %g overflow the f32 distances", (double)m);
+  if ((double)m > magnitude_bound(dim)) {
+    set_error("Index creation failed: embedding values up to %g overflow the f32 distances at dim %d (bound %g)",
+              (double)m, dim, magnitude_bound(dim));
     return NP_ERR_INDEX_CREATION;
   }
-  *amax = m;
   return NP_OK;
 }
 
@@ -374,9 +394,9 @@ void launch_assign(const float* X, const float* xn, int64_t n, const float* Ct, 
 }
 
 template <int D>
-void launch_mean(const float* X, const int32_t* order, const int32_t* off, const int32_t* reinit, double scale,
-                 double inv_scale, const float* Cold, float* Cnew, float* part, int64_t k, hipStream_t st) {
-  km_mean_kernel<D><<<(unsigned)k, 256, 0, st>>>(X, order, off, reinit, scale, inv_scale, Cold, Cnew, part);
+void launch_mean(const float* X, const int32_t* order, const int32_t* off, const int32_t* reinit, const uint32_t* cmax,
+                 const float* Cold, float* Cnew, float* part, int64_t k, hipStream_t st) {
+  km_mean_kernel<D><<<(unsigned)k, 256, 0, st>>>(X, order, off, reinit, cmax, Cold, Cnew, part);
 }
 
 // FastKMeans::train.  points [n][dim] host; out_centroids [k][dim]; out_assign nullable [n]
@@ -404,12 +424,8 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
     set_error("kmeans: invalid argument");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  float amax = 0.f;
-  NP_TRY(check_finite(points, n * dim, &amax));
-  if (init) {
-    float ia = 0.f;
-    NP_TRY(check_finite(init, k * dim, &ia));
-  }
+  NP_TRY(check_finite(points, n * dim, dim));
+  if (init) NP_TRY(check_finite(init, k * dim, dim));
   NP_TRY(check_build_device(device));
   DeviceGuard g(device);
 
@@ -434,12 +450,14 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
   for (hipEvent_t& e : dm.ev) NP_HIP(hipEventCreate(&e));
   hipStream_t st = dm.st;
   const int64_t ntiles = (k + 31) / 32;
-  float *dX, *dxn, *dC[2], *dCt, *dpart;
+  float *dX, *dxn, *damax, *dC[2], *dCt, *dpart;
   unsigned long long* dbest;
   int32_t *dassign, *dcount, *doff, *dcursor, *dorder, *dreinit;
+  uint32_t* dcmax;
   double* dshift;
   NP_TRY(dm.alloc(&dX, (size_t)m * Dp));
   NP_TRY(dm.alloc(&dxn, (size_t)m));
+  NP_TRY(dm.alloc(&damax, (size_t)m));
   NP_TRY(dm.alloc(&dC[0], (size_t)k * Dp));
   NP_TRY(dm.alloc(&dC[1], (size_t)k * Dp));
   NP_TRY(dm.alloc(&dCt, (size_t)ntiles * (Dp * 32 + 32) + 256));   // + 1 KiB: the last DMA piece reads past the tile
@@ -447,6 +465,7 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
   NP_TRY(dm.alloc(&dbest, (size_t)m));
   NP_TRY(dm.alloc(&dassign, (size_t)m));
   NP_TRY(dm.alloc(&dcount, (size_t)k));
+  NP_TRY(dm.alloc(&dcmax, (size_t)k));
   NP_TRY(dm.alloc(&doff, (size_t)k + 1));
   NP_TRY(dm.alloc(&dcursor, (size_t)k));
   NP_TRY(dm.alloc(&dorder, (size_t)m));
@@ -465,16 +484,8 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
     }
   }
   NP_HIP(hipMemcpyAsync(dC[0], c0.data(), (size_t)k * Dp * 4, hipMemcpyHostToDevice, st));
-  km_norm_kernel<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(dX, m, Dp, dxn);
+  km_norm_kernel<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(dX, m, Dp, dxn, damax);
   NP_HIP(hipGetLastError());
-
-  // fixed-point scale of the sums: |x| < 2^e, m points -> |sum 2^S| < 2^62
-  int e = 0;
-  if (amax > 0.f) e = ilogbf(amax) + 1;
-  int lgm = 0;
-  while (((int64_t)1 << lgm) < m) ++lgm;
-  const int S = 62 - e - lgm;
-  const double scale = ldexp(1.0, S), inv_scale = ldexp(1.0, -S);
 
   // centroid chunks: enough workgroups for the device when the points alone do not fill it
   int n_cu = 256;
@@ -503,7 +514,8 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
     NP_HIP(hipGetLastError());
     NP_HIP(hipEventRecord(dm.ev[1], st));
     NP_HIP(hipMemsetAsync(dcount, 0, (size_t)k * 4, st));
-    km_count_kernel<<<nb, 256, 0, st>>>(dbest, m, dassign, dcount);
+    NP_HIP(hipMemsetAsync(dcmax, 0, (size_t)k * 4, st));
+    km_count_kernel<<<nb, 256, 0, st>>>(dbest, damax, m, dassign, dcount, dcmax);
     NP_HIP(hipGetLastError());
     NP_HIP(hipMemcpyAsync(counts.data(), dcount, (size_t)k * 4, hipMemcpyDeviceToHost, st));
     NP_HIP(hipStreamSynchronize(st));
@@ -522,10 +534,10 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
     NP_HIP(hipMemsetAsync(dcursor, 0, (size_t)k * 4, st));
     km_scatter_kernel<<<nb, 256, 0, st>>>(dassign, m, doff, dcursor, dorder);
     switch (Dp) {
-      case 32: launch_mean<32>(dX, dorder, doff, dreinit, scale, inv_scale, dC[cur], dC[cur ^ 1], dpart, k, st); break;
-      case 64: launch_mean<64>(dX, dorder, doff, dreinit, scale, inv_scale, dC[cur], dC[cur ^ 1], dpart, k, st); break;
-      case 96: launch_mean<96>(dX, dorder, doff, dreinit, scale, inv_scale, dC[cur], dC[cur ^ 1], dpart, k, st); break;
-      default: launch_mean<128>(dX, dorder, doff, dreinit, scale, inv_scale, dC[cur], dC[cur ^ 1], dpart, k, st); break;
+      case 32: launch_mean<32>(dX, dorder, doff, dreinit, dcmax, dC[cur], dC[cur ^ 1], dpart, k, st); break;
+      case 64: launch_mean<64>(dX, dorder, doff, dreinit, dcmax, dC[cur], dC[cur ^ 1], dpart, k, st); break;
+      case 96: launch_mean<96>(dX, dorder, doff, dreinit, dcmax, dC[cur], dC[cur ^ 1], dpart, k, st); break;
+      default: launch_mean<128>(dX, dorder, doff, dreinit, dcmax, dC[cur], dC[cur ^ 1], dpart, k, st); break;
     }
     km_shift_kernel<<<1, 1024, 0, st>>>(dpart, k, dshift);
     NP_HIP(hipGetLastError());
@@ -737,8 +749,7 @@ int codec_artifacts_impl(int device, const float* emb, const int64_t* doc_length
     memcpy(&held[(size_t)(got * dim)], emb + off[(size_t)d] * dim, (size_t)(take * dim) * 4);
     got += take;
   }
-  float amax = 0.f;
-  NP_TRY(check_finite(held.data(), H * dim, &amax));
+  NP_TRY(check_finite(held.data(), H * dim, dim));
   std::vector<int64_t> codes((size_t)std::max<int64_t>(H, 1));
   if (H > 0) {
     NP_TRY(check_build_device(device));
@@ -858,8 +869,7 @@ int np_hip_index_create(const char* index_dir, const float* embeddings, const in
     set_error("np_hip_index_create: embeddings are NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  float amax = 0.f;
-  NP_TRY(check_finite(embeddings, T * dim, &amax));
+  NP_TRY(check_finite(embeddings, T * dim, dim));
   NP_TRY(check_build_device(device));
   std::vector<float> cen;
   int64_t k = 0;

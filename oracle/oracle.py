@@ -78,6 +78,8 @@ def lib():
         L.po_encode_tokens.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_void_p]
         L.po_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.po_kmeans_assign.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        L.po_kmeans_shift_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.po_index_create.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 7
         L.po_index_create.restype = C.c_void_p
         L.po_index_destroy.argtypes = [C.c_void_p]
@@ -218,6 +220,27 @@ def encode_tokens(embeddings, centroids, nbits, cutoffs):
     packed = np.zeros((n, dim * nbits // 8), np.uint8)
     lib().po_encode_tokens(_ptr(x), n, _ptr(c), c.shape[0], dim, nbits, _ptr(cut), cut.size, _ptr(codes), _ptr(packed))
     return codes, packed
+
+
+def kmeans_assign(points, centroids):
+    """The k-means assign rule of include/nextplaid_hip.h: (assignment i64 [n], f32 distance [n]), lowest index on
+    equal distances."""
+    x, c = _f32(points), _f32(centroids)
+    n, d = x.shape
+    assert c.ndim == 2 and c.shape[1] == d
+    a = np.zeros(n, np.int64)
+    dist = np.zeros(n, np.float32)
+    lib().po_kmeans_assign(_ptr(x), n, _ptr(c), c.shape[0], d, _ptr(a), _ptr(dist))
+    return a, dist
+
+
+def kmeans_shift_parts(old, new):
+    """Per cluster |new - old| as the k-means update computes it (f32 [k])."""
+    o, w = _f32(old), _f32(new)
+    assert o.shape == w.shape
+    out = np.zeros(o.shape[0], np.float32)
+    lib().po_kmeans_shift_parts(_ptr(o), _ptr(w), o.shape[0], o.shape[1], _ptr(out))
+    return out
 
 
 def decompress(packed, codes, centroids, bucket_weights, nbits):

@@ -221,6 +221,43 @@ PO_API void po_encode_tokens(const float* X, int64_t n, const float* C, int64_t 
   free(res);
 }
 
+/* k-means assign (include/nextplaid_hip.h "assign:"): dist = max(fma(-2, x.c, |x|^2 + |c|^2), 0) in f32 with x.c and
+ * both norms as k-ordered fmaf chains; the LOWEST index wins equal f32 distances.  Not a crate function: the rule the
+ * GPU's Lloyd step states, restated so its argmin can be compared bit for bit. */
+PO_API void po_kmeans_assign(const float* X, int64_t n, const float* C, int64_t k, int64_t d, int64_t* out_assign,
+                             float* out_dist) {
+  float* cn = (float*)malloc((size_t)(k > 0 ? k : 1) * sizeof(float));
+  for (int64_t c = 0; c < k; ++c) cn[c] = po_dot_fma(C + c * d, C + c * d, d);
+#pragma omp parallel for schedule(static)
+  for (int64_t t = 0; t < n; ++t) {
+    const float* x = X + t * d;
+    const float xn = po_dot_fma(x, x, d);
+    int64_t best = 0;
+    float bd = 0.0f;
+    for (int64_t c = 0; c < k; ++c) {
+      float dist = __builtin_fmaf(-2.0f, po_dot_fma(x, C + c * d, d), xn + cn[c]);
+      dist = dist > 0.0f ? dist : 0.0f;
+      if (c == 0 || dist < bd) { best = c; bd = dist; }
+    }
+    if (out_assign) out_assign[t] = best;
+    if (out_dist) out_dist[t] = bd;
+  }
+  free(cn);
+}
+
+/* k-means shift parts (include/nextplaid_hip.h "shift"): per cluster sqrtf of the k-ordered fmaf chain of the squared
+ * f32 differences new - old. */
+PO_API void po_kmeans_shift_parts(const float* old_c, const float* new_c, int64_t k, int64_t d, float* out) {
+  for (int64_t c = 0; c < k; ++c) {
+    float s = 0.0f;
+    for (int64_t j = 0; j < d; ++j) {
+      const float df = new_c[c * d + j] - old_c[c * d + j];
+      s = __builtin_fmaf(df, df, s);
+    }
+    out[c] = sqrtf(s);
+  }
+}
+
 /* codec.rs:423-470 decompress: out[i,j] = centroid[codes[i]][j] + weights[bucket(i,j)];
  * then each row /= max(sqrt(row.row), 1e-12).  codes are i64 (as usize in the reference). */
 PO_API void po_decompress(const uint8_t* packed, const int64_t* codes, int64_t n, int64_t dim,

@@ -60,7 +60,7 @@ def _files(path):
     return {f: open(os.path.join(path, f), "rb").read() for f in sorted(os.listdir(path))}
 
 
-@pytest.mark.parametrize("dim,nbits", [(96, 2), (128, 4)])
+@pytest.mark.parametrize("dim,nbits", [(96, 2), (128, 4), (104, 1), (48, 8), (8, 2)])
 def test_create_with_kmeans(tmp_path, dim, nbits):
     docs, emb, lens = _corpus(1200, dim, nbits, seed=dim + nbits)
     cfg = npa.IndexConfig(nbits=nbits, batch_size=500, seed=7)
@@ -102,6 +102,55 @@ def test_create_with_kmeans(tmp_path, dim, nbits):
     assert _files(d1) == _files(d2)
     assert not os.path.exists(os.path.join(d1, "embeddings.npy"))
     assert not os.path.exists(os.path.join(d1, "embeddings_lengths.json"))
+    for h in (hx, lx):
+        h.close()
+
+
+@pytest.mark.parametrize("dim", [128, 100])
+def test_compute_kmeans_is_kmeans_on_the_sample(dim):
+    """compute_kmeans = np_hip_kmeans on the sampled documents' tokens (shuffled order), tol 1e-8, then every row
+    divided by max(sqrtf(k-ordered fmaf chain of its squares), 1e-12): bit for bit"""
+    docs, _, lens = _corpus(1500, dim, 4, seed=dim)
+    cfg = npa.IndexConfig(seed=13, kmeans_niters=3, max_points_per_centroid=8)
+    cen, rep = npa.compute_kmeans(docs, cfg, return_report=True)
+    plan, ids = npa.kmeans_plan(lens, cfg)
+    pts = np.concatenate([docs[i] for i in ids])
+    raw, r2 = npa.kmeans(pts, plan["k"], max_iters=3, tol=1e-8, seed=13, max_points_per_centroid=8)
+    assert r2["n_points"] < pts.shape[0]                      # the subsample is active
+    nrm = np.maximum(O.kmeans_shift_parts(np.zeros_like(raw), raw), np.float32(1e-12))
+    assert cen.tobytes() == (raw / nrm[:, None]).astype(np.float32).tobytes()
+    for f in ("iterations", "shift", "n_points", "n_reinit"):
+        assert rep[f] == r2[f], f
+
+
+def test_corpus_without_heldout_tokens(tmp_path):
+    """19 tokens: heldout_size = floor(0.05 * 19) = 0, so the codec statistics are those of no rows: avg_residual 0 / 0
+    = NaN, cutoffs, weights and threshold the quantile of an empty array (0).  The index is still written and opens."""
+    rng = np.random.default_rng(19)
+    lens = np.array([3, 0, 5, 4, 7], np.int64)
+    emb = rng.standard_normal((int(lens.sum()), 64)).astype(np.float32)
+    emb /= np.linalg.norm(emb, axis=1, keepdims=True)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    docs = [emb[off[i]:off[i + 1]] for i in range(lens.size)]
+    cfg = npa.IndexConfig(nbits=2, seed=5)
+    plan, _ = npa.kmeans_plan(lens, cfg)
+    assert plan["heldout_size"] == 0 and plan["heldout_tokens"] == 0
+    cen = npa.compute_kmeans(docs, cfg)
+    art = npa.prepare_codec_artifacts(docs, cen, cfg)
+    assert np.all(np.isnan(art["avg_residual"])) and art["avg_residual"].shape == (64,)
+    assert np.all(art["bucket_cutoffs"] == 0) and np.all(art["bucket_weights"] == 0) and art["cluster_threshold"] == 0
+    d = str(tmp_path / "t")
+    hx = npa.MmapIndex.create_with_kmeans(docs, d, cfg)
+    assert np.array_equal(np.load(os.path.join(d, "centroids.npy")), cen)
+    assert np.all(np.isnan(np.load(os.path.join(d, "avg_residual.npy"))))
+    assert np.all(np.load(os.path.join(d, "bucket_cutoffs.npy")) == 0)
+    assert np.all(np.load(os.path.join(d, "bucket_weights.npy")) == 0)
+    rc, rp = O.encode_tokens(emb, cen, 2, np.zeros(3, np.float32))
+    e = hx.export()
+    assert np.array_equal(e["codes"], rc) and np.array_equal(e["residuals"], rp)
+    assert np.array_equal(np.load(os.path.join(d, "embeddings.npy")), emb)
+    lx = npa.MmapIndex.load(d)
+    assert lx.num_partitions() == cen.shape[0]
     for h in (hx, lx):
         h.close()
 

@@ -738,7 +738,8 @@ def test_batched_probe_semantics():
 
 
 # ---- index-time encode, N4: /rerank MaxSim -------------------------------------------------------
-@pytest.mark.parametrize("dim,nbits,K,n", [(128, 4, 1024, 3001), (64, 2, 300, 257)])
+@pytest.mark.parametrize("dim,nbits,K,n", [(128, 4, 1024, 3001), (64, 2, 300, 257), (128, 1, 512, 700),
+                                            (96, 1, 300, 333), (100, 8, 257, 517), (100, 2, 300, 1001)])
 def test_encode_tokens_matches_oracle(dim, nbits, K, n):
     """codec.rs:297-411 / index.rs:289-371: nearest-centroid codes (last of equal maxima, non-finite below finite)
     and packed residual buckets, bit for bit; more tokens than one workspace slice, ragged tail."""
