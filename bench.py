@@ -15,9 +15,12 @@ A "step" is ONE pass of the hot path (S1 centroid scoring -> S7 top-k) over one 
 embeddings are already resident in HBM; value = queries / second, whole job (`value_pcie_inclusive` = the same batches through
 np_hip_search_batch -- host query buffers in, host results out -- from as many host threads as `value` uses streams).
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel: algorithmic bytes or flops per launch /
-its HIP-event duration on the call's stream vs the chip peak), "cpu_baseline" (the oracle restatement of the
-reference CPU path on this box's host cores, bounded sample, median of 3), "parity_vs_oracle", "stages".
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it builds the index, warms up, times the
+steps, times `p50_batch_latency_ms` (20 batches, the metric's second figure) and prints the line.  `--full` adds what takes
+runs of its own: "stages" (per-stage HIP events and work counters), `value_pcie_inclusive`, "roofline" (dominant kernel:
+algorithmic bytes or flops per launch / its HIP-event duration on the call's stream vs the chip peak), "cpu_baseline" (the
+oracle restatement of the reference CPU path on the host's cores, bounded sample, median of 3) and "parity_vs_oracle";
+without it those fields are null.
 Other BASELINE.json configs are reachable with flags (e.g. config 2: --docs 1000000), they are not the default line.
 `--dump-outputs DIR` writes what the last timed step returned (ids, scores, counts as .npy) so that two builds can be compared output
 for output on the same seeded inputs.
@@ -71,15 +74,18 @@ def parse():
     ap.add_argument("--precision", type=int, default=2,
                     help="exact MaxSim arithmetic: 2 QC-reuse split-bf16 (f32-class, the library default), 0 exact-f32 MFMA, "
                          "1 QC-reuse bf16, 3 plain bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-stage times, the PCIe-inclusive rate, the roofline, the CPU "
+                         "baseline and parity with the CPU oracle (a plain run prints null for them)")
     ap.add_argument("--cpu-queries", type=int, default=64,
-                    help="queries per repeat of the CPU-oracle leg (0 = skip).  64 = one batch, BASELINE.md section 3: the oracle's outer "
+                    help="--full: queries per repeat of the CPU-oracle leg (0 = skip).  64 = one batch, BASELINE.md section 3: the oracle's outer "
                          "OpenMP level runs min(queries, threads) queries at once like the reference's rayon par_iter (search.rs:650-664), "
                          "so a batch of 64 fills a 128-thread box with 2 inner threads each; 16 queries left the inner level to do it")
     ap.add_argument("--cpu-repeats", type=int, default=3)
     ap.add_argument("--cpu-outer", type=int, default=16,
                     help="queries the CPU oracle takes at once (its outer OpenMP width; the inner level gets threads / this).  The batch of "
                          "--cpu-queries goes through in pieces of this size; the whole batch at once is timed too and the faster split reported")
-    ap.add_argument("--parity-queries", type=int, default=64, help="queries compared with the oracle at full size")
+    ap.add_argument("--parity-queries", type=int, default=64, help="--full: queries compared with the oracle at full size")
     ap.add_argument("--cpu-docs", type=int, default=0,
                     help="CPU leg on the first N docs only (0 = the whole corpus; used automatically if the export fails)")
     ap.add_argument("--query-batches", type=int, default=4)
@@ -443,26 +449,28 @@ def main():
     p50 = float(np.median(lat)) if lat else None
 
     # ---- per-stage durations (HIP events on the call's stream) + work counters; the same calls, timed on the host
-    # clock, are the PCIe-inclusive rate: np_hip_search_batch takes host query buffers and returns host results ---------
-    nprof = max(2, min(a.steps, 6))
-    acc = {}
-    host_t = []
-    for i in range(nprof):
-        b = i % a.query_batches
-        t1 = time.perf_counter()
-        ix.search_batch(qs[b * a.batch:(b + 1) * a.batch], prm)
-        host_t.append(time.perf_counter() - t1)
-        for k, v in ix.last_stats.items():
-            acc[k] = acc.get(k, 0) + v
-    stages = {k: v / nprof for k, v in acc.items()}
-    qps_pcie_1 = a.batch / float(np.median(host_t)) if world == 1 else None   # ONE call in flight, host buffers
+    # clock, are the PCIe-inclusive rate: np_hip_search_batch takes host query buffers and returns host results (--full) --
+    stages, qps_pcie_1 = None, None
+    if a.full:
+        nprof = max(2, min(a.steps, 6))
+        acc = {}
+        host_t = []
+        for i in range(nprof):
+            b = i % a.query_batches
+            t1 = time.perf_counter()
+            ix.search_batch(qs[b * a.batch:(b + 1) * a.batch], prm)
+            host_t.append(time.perf_counter() - t1)
+            for k, v in ix.last_stats.items():
+                acc[k] = acc.get(k, 0) + v
+        stages = {k: v / nprof for k, v in acc.items()}
+        qps_pcie_1 = a.batch / float(np.median(host_t)) if world == 1 else None   # ONE call in flight, host buffers
 
     # ---- SURVEY 8(d)'s protocol at the SAME concurrency as `value`: np_hip_search_batch (host query buffers in, host results
     # out: H2D + S1..S7 + D2H inside the call) from as many host threads as `value` uses streams -- the way the API's tokio
     # workers call MmapIndex::search_batch (next-plaid-api/src/handlers/search.rs:219-229).  Each thread has its own host
     # buffers; the library hands each concurrent call its own context (stream + workspace + pinned result staging).
     qps_pcie, pcie_calls = None, 0
-    if world == 1:
+    if a.full and world == 1:
         import threading
         hq = [np.ascontiguousarray(np.concatenate(qs[i * a.batch:(i + 1) * a.batch], 0), np.float32) for i in range(a.query_batches)]
         hoff = np.ascontiguousarray(off, np.int32)
@@ -510,7 +518,7 @@ def main():
     # ---- N > 1: the merged result of the sharded protocol against the oracle on the WHOLE corpus (small corpora only: rank 0
     # builds the unsharded corpus next to its shard to export it for the CPU oracle).  Collective: every rank takes part.
     got_sharded = None
-    if use_shards and world > 1 and a.parity_queries > 0 and a.docs <= 1_000_000:
+    if a.full and use_shards and world > 1 and a.parity_queries > 0 and a.docs <= 1_000_000:
         got_sharded = ss.search_batch(qs[:min(a.parity_queries, nq)], prm)
 
     if rank != 0:
@@ -519,85 +527,87 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- roofline of the dominant kernel (rank 0's shard) ------------------------------------------------------------------
-    Lq, d = a.query_tokens, dim
-    cand_tokens, exact_tokens = stages["n_cand_tokens"], stages["n_exact_tokens"]
-    lvl0 = stages.get("n_level0", 0)
-    if lvl0 and lvl0 < stages["n_candidates"]:
-        # the zeroth filter level ran: the hot level -- which counts the candidates' tokens -- saw only what it handed over; the
-        # contract's Tc is the token count of EVERY candidate (exact for fixed-length corpora, scaled by the counts otherwise)
-        cand_tokens = stages["n_candidates"] * a.doc_len if len_min == a.doc_len else cand_tokens * stages["n_candidates"] / lvl0
-    per_stage = {
-        # name: (ms, bound, algorithmic units per launch, unit, peak)
-        # split-bf16 S1: three bf16 MFMAs per product, priced against the dense bf16 peak
-        "qc_gemm(S1)": ((stages["ms_centroid"], "mfma", 3 * 2.0 * a.batch * Lq * d * a.centroids / 1e12, "TFLOP/s", MFMA_BF16_PEAK_TF)
-                        if s1_split else
-                        (stages["ms_centroid"], "mfma", 2.0 * a.batch * Lq * d * a.centroids / 1e12, "TFLOP/s", MFMA_F32_PEAK_TF)),
-        "probe(S2)": (stages["ms_probe"], "hbm", (a.batch * (a.centroids / 32) * Lq * 4) / 1e9, "GB/s", HBM_PEAK_GBS),
-        "candidates(S3)": (stages["ms_candidates"], "hbm", (stages["n_ivf_ids"] * 4 + stages["n_candidates"] * 4) / 1e9, "GB/s", HBM_PEAK_GBS),
-        "approx(S4)": (stages["ms_approx"], "hbm", (cand_tokens * 4 + stages["n_candidates"] * 8) / 1e9, "GB/s", HBM_PEAK_GBS),
-        "select(S5)": (stages["ms_select"], "hbm", (stages["n_candidates"] * 8) / 1e9, "GB/s", HBM_PEAK_GBS),
-        "exact(S6)": (stages["ms_exact"], "hbm", exact_tokens * (pd + 4) / 1e9, "GB/s", HBM_PEAK_GBS),
-    }
-    dom = max(per_stage, key=lambda k: per_stage[k][0])
-    ms, bound, units, unit, peak = per_stage[dom]
-    achieved = units / (ms * 1e-3) if ms > 0 else 0.0
-    traffic, traffic_src, tj_ok = None, None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")     # PMC-derived HBM bytes per launch, if collected
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            # counters belong to one workload AND one build of the kernels: never carried over to another
-            default_workload = (a.rand256 == 51 and a.centroids == 65536 and a.nbits == 4 and a.nprobe == 32 and a.batch == 64 and
-                                a.query_tokens == 32 and a.n_full_scores == 4096 and a.threshold == 0.4 and a.precision == 2 and
-                                a.hot < 0 and a.doc_len == 300 and a.doc_len_min == 0 and a.len_dist == "uniform" and not s1_split and
-                                not any(k.startswith("NP_S") for k in os.environ))
-            if default_workload and tj.get("docs_per_gpu") == docs_local and tj.get("kernels_sha") == kernels_sha():
-                traffic = tj.get(dom)
-                traffic_src = {"commit": tj.get("commit"), "kernels_sha": tj.get("kernels_sha")}
-                tj_ok = tj
-        except Exception:
-            traffic = None
-    # `frac` prices the contract's ALGORITHMIC bytes (Tc*4 + C*8 for S4) against the stage's duration; the filter
-    # never reads most of them, so the bytes the stage really moved (PMC `traffic`) give the PHYSICAL fraction beside it
-    frac_phys = None
-    if traffic and ms > 0 and bound == "hbm":
-        frac_phys = round(traffic / 1e9 / (ms * 1e-3) / peak, 5)
-    # The dominant KERNEL of that stage by itself: the first filter level (one launch per batch, timed by its own pair of HIP events
-    # on the call's stream, np_stats.ms_hot_level).  Its algorithmic bytes are what ITS algorithm has to move per launch -- per
-    # candidate the id (4 B in), the list block's header (16 B) and distinct codes, the 16-B record and the u16 bound it writes,
-    # plus one plane row per hot (document, code) pair it gathers -- not the contract's per-token figure, which this kernel exists
-    # to avoid; `traffic` = what the PMC counters saw for this kernel alone.
-    dom_kernel = None
-    ms_hot = stages.get("ms_hot_level", 0.0)
-    if dom == "approx(S4)" and ms_hot > 0:
-        code_b = 2 if a.centroids <= 65536 else 4
-        row_b = 32 if Lq <= 32 else 64
-        # rows gathered by the hot level alone are not counted separately (n_cand_codes = both levels): the upper bound of its
-        # share is all of them
-        alg = stages["n_candidates"] * (4 + 16 + 16 + 2) + stages.get("n_cand_dcodes", 0) * code_b
-        kname = "approx_hotp_kernel" if os.environ.get("NP_S4_PLANES", "1") != "0" else "approx_hot_kernel"
-        ktr = None
-        if tj_ok is not None:
-            ktr = (tj_ok.get("per_kernel", {}).get(kname) or {}).get("bytes_per_batch")
-        dom_kernel = dict(kernel=kname, ms_per_launch=round(ms_hot, 4), bound="hbm", algorithmic_bytes=int(alg),
-                          achieved=round(alg / 1e9 / (ms_hot * 1e-3), 2), unit="GB/s", peak=HBM_PEAK_GBS,
-                          frac=round(alg / 1e9 / (ms_hot * 1e-3) / HBM_PEAK_GBS, 5), traffic=ktr,
-                          frac_physical=None if not ktr else round(ktr / 1e9 / (ms_hot * 1e-3) / HBM_PEAK_GBS, 5),
-                          note="algorithmic bytes = candidates x (4 B id + 16 B block header + 16 B record + 2 B bound) + distinct "
-                               "(document, code) pairs x code bytes; plane rows (L2-resident) not counted")
-    roofline = dict(kernel=dom, bound=bound, achieved=round(achieved, 3), peak=peak, unit=unit,
-                    frac=round(achieved / peak, 5), frac_physical=frac_phys, traffic=traffic, traffic_source=traffic_src,
-                    ms_per_launch=round(ms, 4), dominant_kernel=dom_kernel,
-                    all={k: dict(ms=round(v[0], 4), bound=v[1], achieved=round(v[2] / (v[0] * 1e-3), 2) if v[0] > 0 else None,
-                                 unit=v[3], frac=round(v[2] / (v[0] * 1e-3) / v[4], 4) if v[0] > 0 else None)
-                         for k, v in per_stage.items()},
-                    s6_mfma_tflops=round(2.0 * Lq * d * exact_tokens / 1e12 / (stages["ms_exact"] * 1e-3), 2) if stages["ms_exact"] > 0 else None)
+    # ---- roofline of the dominant kernel (rank 0's shard; --full) ------------------------------------------------------------
+    roofline = None
+    if a.full:
+        Lq, d = a.query_tokens, dim
+        cand_tokens, exact_tokens = stages["n_cand_tokens"], stages["n_exact_tokens"]
+        lvl0 = stages.get("n_level0", 0)
+        if lvl0 and lvl0 < stages["n_candidates"]:
+            # the zeroth filter level ran: the hot level -- which counts the candidates' tokens -- saw only what it handed over; the
+            # contract's Tc is the token count of EVERY candidate (exact for fixed-length corpora, scaled by the counts otherwise)
+            cand_tokens = stages["n_candidates"] * a.doc_len if len_min == a.doc_len else cand_tokens * stages["n_candidates"] / lvl0
+        per_stage = {
+            # name: (ms, bound, algorithmic units per launch, unit, peak)
+            # split-bf16 S1: three bf16 MFMAs per product, priced against the dense bf16 peak
+            "qc_gemm(S1)": ((stages["ms_centroid"], "mfma", 3 * 2.0 * a.batch * Lq * d * a.centroids / 1e12, "TFLOP/s", MFMA_BF16_PEAK_TF)
+                            if s1_split else
+                            (stages["ms_centroid"], "mfma", 2.0 * a.batch * Lq * d * a.centroids / 1e12, "TFLOP/s", MFMA_F32_PEAK_TF)),
+            "probe(S2)": (stages["ms_probe"], "hbm", (a.batch * (a.centroids / 32) * Lq * 4) / 1e9, "GB/s", HBM_PEAK_GBS),
+            "candidates(S3)": (stages["ms_candidates"], "hbm", (stages["n_ivf_ids"] * 4 + stages["n_candidates"] * 4) / 1e9, "GB/s", HBM_PEAK_GBS),
+            "approx(S4)": (stages["ms_approx"], "hbm", (cand_tokens * 4 + stages["n_candidates"] * 8) / 1e9, "GB/s", HBM_PEAK_GBS),
+            "select(S5)": (stages["ms_select"], "hbm", (stages["n_candidates"] * 8) / 1e9, "GB/s", HBM_PEAK_GBS),
+            "exact(S6)": (stages["ms_exact"], "hbm", exact_tokens * (pd + 4) / 1e9, "GB/s", HBM_PEAK_GBS),
+        }
+        dom = max(per_stage, key=lambda k: per_stage[k][0])
+        ms, bound, units, unit, peak = per_stage[dom]
+        achieved = units / (ms * 1e-3) if ms > 0 else 0.0
+        traffic, traffic_src, tj_ok = None, None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")     # PMC-derived HBM bytes per launch, if collected
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                # counters belong to one workload AND one build of the kernels: never carried over to another
+                default_workload = (a.rand256 == 51 and a.centroids == 65536 and a.nbits == 4 and a.nprobe == 32 and a.batch == 64 and
+                                    a.query_tokens == 32 and a.n_full_scores == 4096 and a.threshold == 0.4 and a.precision == 2 and
+                                    a.hot < 0 and a.doc_len == 300 and a.doc_len_min == 0 and a.len_dist == "uniform" and not s1_split and
+                                    not any(k.startswith("NP_S") for k in os.environ))
+                if default_workload and tj.get("docs_per_gpu") == docs_local and tj.get("kernels_sha") == kernels_sha():
+                    traffic = tj.get(dom)
+                    traffic_src = {"commit": tj.get("commit"), "kernels_sha": tj.get("kernels_sha")}
+                    tj_ok = tj
+            except Exception:
+                traffic = None
+        # `frac` prices the contract's ALGORITHMIC bytes (Tc*4 + C*8 for S4) against the stage's duration; the filter
+        # never reads most of them, so the bytes the stage really moved (PMC `traffic`) give the PHYSICAL fraction beside it
+        frac_phys = None
+        if traffic and ms > 0 and bound == "hbm":
+            frac_phys = round(traffic / 1e9 / (ms * 1e-3) / peak, 5)
+        # The dominant KERNEL of that stage by itself: the first filter level (one launch per batch, timed by its own pair of HIP events
+        # on the call's stream, np_stats.ms_hot_level).  Its algorithmic bytes are what ITS algorithm has to move per launch -- per
+        # candidate the id (4 B in), the list block's header (16 B) and distinct codes, the 16-B record and the u16 bound it writes,
+        # plus one plane row per hot (document, code) pair it gathers -- not the contract's per-token figure, which this kernel exists
+        # to avoid; `traffic` = what the PMC counters saw for this kernel alone.
+        dom_kernel = None
+        ms_hot = stages.get("ms_hot_level", 0.0)
+        if dom == "approx(S4)" and ms_hot > 0:
+            code_b = 2 if a.centroids <= 65536 else 4
+            row_b = 32 if Lq <= 32 else 64
+            # rows gathered by the hot level alone are not counted separately (n_cand_codes = both levels): the upper bound of its
+            # share is all of them
+            alg = stages["n_candidates"] * (4 + 16 + 16 + 2) + stages.get("n_cand_dcodes", 0) * code_b
+            kname = "approx_hotp_kernel" if os.environ.get("NP_S4_PLANES", "1") != "0" else "approx_hot_kernel"
+            ktr = None
+            if tj_ok is not None:
+                ktr = (tj_ok.get("per_kernel", {}).get(kname) or {}).get("bytes_per_batch")
+            dom_kernel = dict(kernel=kname, ms_per_launch=round(ms_hot, 4), bound="hbm", algorithmic_bytes=int(alg),
+                              achieved=round(alg / 1e9 / (ms_hot * 1e-3), 2), unit="GB/s", peak=HBM_PEAK_GBS,
+                              frac=round(alg / 1e9 / (ms_hot * 1e-3) / HBM_PEAK_GBS, 5), traffic=ktr,
+                              frac_physical=None if not ktr else round(ktr / 1e9 / (ms_hot * 1e-3) / HBM_PEAK_GBS, 5),
+                              note="algorithmic bytes = candidates x (4 B id + 16 B block header + 16 B record + 2 B bound) + distinct "
+                                   "(document, code) pairs x code bytes; plane rows (L2-resident) not counted")
+        roofline = dict(kernel=dom, bound=bound, achieved=round(achieved, 3), peak=peak, unit=unit,
+                        frac=round(achieved / peak, 5), frac_physical=frac_phys, traffic=traffic, traffic_source=traffic_src,
+                        ms_per_launch=round(ms, 4), dominant_kernel=dom_kernel,
+                        all={k: dict(ms=round(v[0], 4), bound=v[1], achieved=round(v[2] / (v[0] * 1e-3), 2) if v[0] > 0 else None,
+                                     unit=v[3], frac=round(v[2] / (v[0] * 1e-3) / v[4], 4) if v[0] > 0 else None)
+                             for k, v in per_stage.items()},
+                        s6_mfma_tflops=round(2.0 * Lq * d * exact_tokens / 1e12 / (stages["ms_exact"] * 1e-3), 2) if stages["ms_exact"] > 0 else None)
 
     # ---- CPU baseline + parity at full size: the oracle restatement on this box's host cores ----------------------------
     cpu = None
     parity = None
-    if ((a.cpu_queries > 0 or a.parity_queries > 0) and world == 1) or got_sharded is not None:
+    if (a.full and (a.cpu_queries > 0 or a.parity_queries > 0) and world == 1) or got_sharded is not None:
         try:
             from oracle import oracle as O
             cix, cdocs, e = ix, a.docs, None
@@ -674,7 +684,7 @@ def main():
         "value": round(qps, 2), "unit": "queries/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(dt / a.steps * 1e3, 4), "p50_batch_latency_ms": None if p50 is None else round(p50, 4),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "hosted": bool(a.hosted),
+        "hosted": bool(a.hosted), "full": bool(a.full),
         # what the communicator of rank 0's replica group really is (np_hip_comm_info): transport "rccl" with rccl_ranks_seen =
         # ncclCommCount == shards on a healthy multi-GPU run; "hosted" = gloo on one GPU; None = no sharded protocol in this run
         "transport": (comm_info or {}).get("transport") if use_shards and dist_impl == "c" else ("torch.distributed" if use_shards else None),
@@ -705,7 +715,7 @@ def main():
                                    + (f", x{n_repl} replica groups on different batches" if n_repl > 1 else ""))
                                   if use_dist else "single GPU"},
         "roofline": roofline, "cpu_baseline": cpu, "parity_vs_oracle": parity,
-        "stages": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in stages.items()},
+        "stages": None if stages is None else {k: (round(v, 4) if isinstance(v, float) else v) for k, v in stages.items()},
         "disk_open": disk_open,
         "index_build_s": round(t_build, 2), "hbm_index_bytes": int(ix.info.device_bytes),
         "hbm_bytes_per_token": round(ix.info.device_bytes / max(int(ix.info.shard_embeddings), 1), 2),

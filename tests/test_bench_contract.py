@@ -122,6 +122,7 @@ def test_stage_traffic_is_the_sum_over_all_kernels_of_the_stage():
 def test_bench_argument_parsing_needs_no_gpu():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert "--full" in out.stdout
 
 
 def test_make_traffic_refuses_a_kernel_without_a_stage(tmp_path):

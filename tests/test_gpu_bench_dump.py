@@ -38,6 +38,9 @@ def test_dump_is_the_last_timed_step(tmp_path):
         out = tmp_path / f"s{steps}"
         d = _bench(out, steps)
         assert d["steps"] == steps and d["ms_per_step"] > 0
+        # a plain run (no --full) measures nothing beyond the steps and their p50 latency
+        assert d["full"] is False and d["p50_batch_latency_ms"] > 0
+        assert d["stages"] is d["roofline"] is d["cpu_baseline"] is d["parity_vs_oracle"] is d["value_pcie_inclusive"] is None
         ids, sc, cnt = (np.load(out / f"{n}.npy") for n in ("passage_ids", "scores", "counts"))
         assert ids.dtype == np.float64 and sc.dtype == np.float32 and cnt.dtype == np.float64
         assert ids.shape == sc.shape == (BATCH, 10) and cnt.shape == (BATCH,)

@@ -31,8 +31,8 @@ def _run(nproc, extra, launcher=True):
     pre = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port())] if launcher else [sys.executable]
     cmd = pre + [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--hosted", "--docs", "120000",
-           "--doc-len", "120", "--centroids", "8192", "--steps", "6", "--warmup", "2", "--cpu-queries", "0", "--parity-queries", "16",
-           "--workspace-gib", "1"] + extra
+           "--doc-len", "120", "--centroids", "8192", "--steps", "6", "--warmup", "2", "--full", "--cpu-queries", "0",
+           "--parity-queries", "16", "--workspace-gib", "1"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

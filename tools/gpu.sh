@@ -8,7 +8,7 @@
 #   build                        __graft_entry__.build()                            -> build.log
 #   test  <name> [pytest args]   python -m pytest tests -m gpu <args>               -> test_<name>.log
 #   smoke                        __graft_entry__.smoke()                            -> smoke.log
-#   bench <name> [bench args]    python bench.py <args>                             -> b_<name>.json (+ .err), one summary line
+#   bench <name> [bench args]    python bench.py --full <args>                      -> b_<name>.json (+ .err), one summary line
 #   stats <name> [bench args]    rocprofv3 --kernel-trace --stats of a short bench  -> stats_<name>/ (+ kernel table .md)
 #   pmc   <name> [bench args]    separate rocprofv3 --pmc passes of a short bench   -> pmc_<name>/  (+ traffic json)
 #   probe <name> <binary> [args] tools/probes/<binary> alone (stdout -> probe_<name>.log), then under separate rocprofv3 --pmc passes
@@ -50,11 +50,11 @@ for job in "$@"; do
       echo "test $name rc=$? : $(tail -n 1 $O/test_$name.log)";;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?";;
     bench) shift 2
-      timeout $T python bench.py "$@" > $O/b_$name.json 2> $O/b_$name.err
+      timeout $T python bench.py --full "$@" > $O/b_$name.json 2> $O/b_$name.err
       summ $name $O/b_$name.json | tee -a $O/summary.txt;;
     stats) shift 2
       ( cd /tmp && export TMPDIR=/tmp && timeout $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$name -o s -- \
-          python $REPO/bench.py --steps 6 --warmup 2 --cpu-queries 0 --parity-queries 0 "$@" > $O/stats_$name.json 2> $O/stats_$name.err )
+          python $REPO/bench.py --steps 6 --warmup 2 --full --cpu-queries 0 --parity-queries 0 "$@" > $O/stats_$name.json 2> $O/stats_$name.err )
       csv=$(find $O/stats_$name -name "*kernel_stats.csv" | head -1)
       python3 tools/prof_summary.py "$csv" $O/stats_$name.md "rocprofv3 --kernel-trace --stats: bench.py $*" | head -n 34
       cp "$csv" $O/stats_$name.csv 2>/dev/null;;
@@ -68,7 +68,7 @@ for job in "$@"; do
       for set in "${sets[@]}"; do
         i=$((i+1))
         ( cd /tmp && export TMPDIR=/tmp && timeout $T rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc_$name/p$i -o p -- \
-            python $REPO/bench.py --steps 3 --warmup 1 --cpu-queries 0 --parity-queries 0 "$@" > /dev/null 2> $O/pmc_$name/p$i.err )
+            python $REPO/bench.py --steps 3 --warmup 1 --full --cpu-queries 0 --parity-queries 0 "$@" > /dev/null 2> $O/pmc_$name/p$i.err )
         echo "$set" > $O/pmc_$name/p$i.set
       done
       python3 tools/pmc_summary.py $O/pmc_$name $O/pmc_$name.md > /dev/null 2>&1

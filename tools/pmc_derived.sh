@@ -8,7 +8,7 @@ i=0
 for set in "VALUBusy SALUBusy" "MemUnitBusy MemUnitStalled" "LdsUtil LDSBankConflict" "LdsLatency VmemLatency" "OccupancyPercent MeanOccupancyPerActiveCU"; do
   i=$((i+1))
   ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/d$i -o p -- \
-      python $REPO/bench.py --steps 3 --warmup 1 --cpu-queries 0 --parity-queries 0 --streams 1 "$@" > /dev/null 2> $O/d$i.err )
+      python $REPO/bench.py --steps 3 --warmup 1 --full --cpu-queries 0 --parity-queries 0 --streams 1 "$@" > /dev/null 2> $O/d$i.err )
 done
 python3 - $O <<'PY'
 import csv, glob, sys, re, collections
