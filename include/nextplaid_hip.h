@@ -137,7 +137,8 @@ const char* np_hip_last_error(void);
  * header would have bytes written past its structs before it could read np_info.abi_version.  A host binds this first and
  * refuses a library whose version differs from the header it was built with; np_hip_struct_size lets it check the two
  * layouts it allocates (which: 0 = np_info, 1 = np_stats, 2 = np_search_params, 3 = np_open_opts, 4 = np_kmeans_opts,
- * 5 = np_kmeans_report, 6 = np_index_config, 7 = np_kmeans_plan; -1 for an unknown id). */
+ * 5 = np_kmeans_report, 6 = np_index_config, 7 = np_kmeans_plan, 8 = np_update_config, 9 = np_update_report; -1 for an
+ * unknown id). */
 int np_hip_abi_version(void);
 int64_t np_hip_struct_size(int32_t which);
 
@@ -495,6 +496,86 @@ int np_hip_prepare_codec_artifacts(int32_t device, const float* embeddings, cons
  * opts->device selects the GPU (opts nullable: device 0).  out (nullable): the created index, opened with opts. */
 int np_hip_index_create(const char* index_dir, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs,
                         int32_t dim, const np_index_config* cfg, const np_open_opts* opts, np_index** out);
+
+/* ---- index update and delete: MmapIndex::update / update_append / delete (np_update.cpp, np_build.hip) ----------------
+ * Directory-level calls like np_hip_index_create: they read the crate's file set under index_dir and rewrite it in place;
+ * a handle open on the directory keeps serving the old index until it is reopened (MmapIndex.reload in the mirrors).
+ *
+ * np_hip_index_update (index.rs:1431-1590) takes the crate's three modes, chosen as the crate chooses them:
+ *  - start from scratch: num_documents <= start_from_scratch and embeddings.npy holds exactly num_documents documents:
+ *    np_hip_index_create on old ++ new (nbits of the index, the other fields from cfg); embeddings.npy is removed when
+ *    the total passes start_from_scratch.  Otherwise:
+ *  - buffer: buffered + new < buffer_size: buffer.npy / buffer_lengths.json / buffer_info.json hold buffer ++ new, and
+ *    the new documents are appended (update_index, update.rs:771-1120) without a threshold update;
+ *  - expansion: the buffer_info.num_docs buffered documents are deleted from the tail (the buffer files stay), the
+ *    outliers of buffer ++ new (tokens whose f32(min_c f64 |x - c|^2) > cluster_threshold^2 in f32) are clustered by
+ *    compute_kmeans as one-token documents with num_partitions = min(max(1, ceil(n_out / max_points_per_centroid)) * 4,
+ *    n_out), the new centroids are appended to centroids.npy, the buffer is cleared and buffer ++ new are appended with
+ *    the threshold update (update.rs:385-416: the 0.75 quantile of the new residual norms, averaged in f32 with the old
+ *    threshold by count).  Without cluster_threshold.npy there is no expansion, as in the crate.
+ * All device work (outliers, k-means, encoding with the expanded codec, residual norms) is done before the first file is
+ * written, so a refused input or a missing device leaves the directory unchanged.  The k-means draws come from the
+ * SplitMix64 stream of np_hip_kmeans, not the crate's ChaCha8: the new centroids equal np_hip_compute_kmeans on the same
+ * outliers, not the crate's bytes.  Residual norms are |x - c[code]| with the sum of squares as a sequential f32 sum
+ * without contraction, the rule np_hip_prepare_codec_artifacts uses for cluster_threshold (the crate's ndarray dot may
+ * sum in another order).
+ * update_index: when the last chunk holds fewer than 2000 documents the first batch_size new documents join it, the rest
+ * go to new chunks of batch_size; each chunk's metadata carries embedding_offset; posting list c gains the ids of the
+ * new documents holding code c (a list that ascends below the first new id is appended to, any other is sorted and
+ * deduplicated with its new entries, as the crate does); avg_doclen = (old_avg * old_n + new_tokens) / n in f64; the
+ * merged_* caches are removed.  Inputs are checked as np_hip_index_create checks them (dim mismatch with the index:
+ * NP_ERR_SHAPE; non-finite or oversized values: NP_ERR_INDEX_CREATION); n_docs == 0 changes nothing.  The new documents'
+ * ids are report->first_doc_id + i. */
+typedef struct np_update_config {   /* UpdateConfig (update.rs:75-107); 0 selects the default */
+  int64_t batch_size;               /* 50 000: documents per new chunk */
+  int32_t kmeans_niters;            /* 4 */
+  int32_t reserved0;
+  int64_t max_points_per_centroid;  /* 256 */
+  int64_t n_samples_kmeans;         /* 0 = the heuristic */
+  uint64_t seed;                    /* 42 (taken as given; only a NULL cfg selects 42) */
+  int64_t start_from_scratch;       /* 999; < 0 = never */
+  int64_t buffer_size;              /* 100; < 0 = 0 (every update expands) */
+  int64_t reserved[4];
+} np_update_config;
+
+#define NP_UPDATE_NONE 0      /* no documents: nothing changed */
+#define NP_UPDATE_SCRATCH 1
+#define NP_UPDATE_BUFFER 2
+#define NP_UPDATE_EXPAND 3
+#define NP_UPDATE_APPEND 4    /* np_hip_index_update_append */
+
+typedef struct np_update_report {
+  int32_t mode;                 /* NP_UPDATE_* */
+  int32_t reserved0;
+  int64_t first_doc_id;         /* id of the first new document */
+  int64_t n_outliers;           /* expansion: outlier tokens found */
+  int64_t n_rechecked;          /* expansion: tokens the f64 recheck decided */
+  int64_t n_new_centroids;      /* expansion: centroids appended */
+  int64_t n_reindexed;          /* expansion: buffered documents deleted and appended again */
+  double ms_encode;             /* host wall time of each stage */
+  double ms_outliers;
+  double ms_kmeans;
+  double ms_files;              /* reading and rewriting the directory (start from scratch: the whole create) */
+  int64_t reserved[4];
+} np_update_report;
+
+/* MmapIndex::update (index.rs:1431-1590).  embeddings = the new documents' tokens concatenated ([sum doc_lengths][dim]);
+ * device = the GPU; cfg and report nullable. */
+int np_hip_index_update(const char* index_dir, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs,
+                        int32_t dim, const np_update_config* cfg, int32_t device, np_update_report* report);
+
+/* MmapIndex::update_append (index.rs:1675-1700): update_index only (no mode choice, no buffer, no threshold update). */
+int np_hip_index_update_append(const char* index_dir, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs,
+                               int32_t dim, const np_update_config* cfg, int32_t device, np_update_report* report);
+
+/* MmapIndex::delete (delete.rs:43-398), host only: every chunk that loses documents gets its doclens, codes, residuals
+ * and {i}.metadata.json rewritten (embedding_offset unchanged; a chunk may become empty and stays), posting lists drop
+ * the ids and renumber the rest, metadata.json gets the new counts and avg_doclen = tokens / documents, the merged_*
+ * caches are removed, and embeddings.npy / buffer.npy lose the deleted documents' rows (clean_embeddings_files).
+ * *out_deleted (nullable) = distinct ids removed.  Divergence from the crate: ids < 0 or >= num_documents are ignored.
+ * The crate's renumbering counts every listed id below a posting-list entry, negative ones included, so a negative
+ * id shifts every entry by one and its posting lists no longer match its codes; here delete([-1, 3]) equals delete([3]). */
+int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n_ids, int64_t* out_deleted);
 
 /* Stage-level debug access for parity tests: runs S1-S5 for ONE query and copies out the probed
  * cells (ascending), candidate doc ids (ascending, global), their approximate scores, and the

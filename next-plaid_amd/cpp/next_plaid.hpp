@@ -202,6 +202,35 @@ inline CodecArtifacts prepare_codec_artifacts(const Documents& docs, const std::
   return a;
 }
 
+// UpdateConfig (update.rs:75-107), same defaults.  start_from_scratch = 0 / buffer_size = 0 keep the crate's meaning (only an
+// empty index starts from scratch; every update expands).
+struct UpdateConfig {
+  int64_t batch_size = 50000;
+  int kmeans_niters = 4;
+  int64_t max_points_per_centroid = 256;
+  std::optional<int64_t> n_samples_kmeans;
+  uint64_t seed = 42;
+  int64_t start_from_scratch = 999;
+  int64_t buffer_size = 100;
+  np_update_config c() const {
+    np_update_config o{};
+    o.batch_size = batch_size;
+    o.kmeans_niters = kmeans_niters;
+    o.max_points_per_centroid = max_points_per_centroid;
+    o.n_samples_kmeans = n_samples_kmeans.value_or(0);
+    o.seed = seed;
+    o.start_from_scratch = start_from_scratch == 0 ? -1 : start_from_scratch;
+    o.buffer_size = buffer_size == 0 ? -1 : buffer_size;
+    return o;
+  }
+};
+
+inline std::vector<int64_t> update_ids(const np_update_report& r, size_t n) {
+  std::vector<int64_t> ids(n);
+  for (size_t i = 0; i < n; ++i) ids[i] = r.first_doc_id + (int64_t)i;
+  return ids;
+}
+
 class MmapIndex {
  public:
   // MmapIndex::create_with_kmeans (index.rs:927-967): k-means and codec training on the GPU, the crate's file set written
@@ -250,6 +279,50 @@ class MmapIndex {
   void reload(const np_open_opts* opts = nullptr) {
     MmapIndex fresh = (close(), load(path, opts));
     *this = std::move(fresh);
+  }
+  // MmapIndex::update (index.rs:1431-1590): the new documents' ids; the handle is reloaded from the rewritten directory
+  std::vector<int64_t> update(const Documents& docs, const UpdateConfig& cfg = {}, const np_open_opts* opts = nullptr,
+                              np_update_report* report = nullptr) {
+    check_abi();
+    const np_update_config c = cfg.c();
+    np_update_report r{};
+    check(np_hip_index_update(path.c_str(), docs.embeddings, docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(),
+                              (int32_t)docs.dim, &c, opts ? opts->device : 0, &r));
+    if (report) *report = r;
+    reload(opts);
+    return update_ids(r, docs.doc_lengths.size());
+  }
+  // MmapIndex::update_append (index.rs:1675-1700): no mode choice, no reload
+  static std::vector<int64_t> update_append(const Documents& docs, const std::string& index_path, const UpdateConfig& cfg = {},
+                                            int device = 0) {
+    check_abi();
+    const np_update_config c = cfg.c();
+    np_update_report r{};
+    check(np_hip_index_update_append(index_path.c_str(), docs.embeddings, docs.doc_lengths.data(),
+                                     (int64_t)docs.doc_lengths.size(), (int32_t)docs.dim, &c, device, &r));
+    return update_ids(r, docs.doc_lengths.size());
+  }
+  // MmapIndex::update_or_create (index.rs:1644-1673): created when metadata.json is absent, ids 0..n then
+  static MmapIndex update_or_create(const Documents& docs, const std::string& index_path, std::vector<int64_t>* ids,
+                                    const IndexConfig& icfg = {}, const UpdateConfig& ucfg = {},
+                                    const np_open_opts* opts = nullptr) {
+    if (std::FILE* f = std::fopen((index_path + "/metadata.json").c_str(), "rb")) {
+      std::fclose(f);
+      MmapIndex ix = load(index_path, opts);
+      std::vector<int64_t> got = ix.update(docs, ucfg, opts);
+      if (ids) *ids = std::move(got);
+      return ix;
+    }
+    MmapIndex ix = create_with_kmeans(docs, index_path, icfg, opts);
+    if (ids) *ids = update_ids(np_update_report{}, docs.doc_lengths.size());
+    return ix;
+  }
+  // MmapIndex::delete (delete.rs:43-268): the count removed; no reload, as the crate (ids outside the index are ignored)
+  int64_t delete_documents(const std::vector<int64_t>& doc_ids) {
+    check_abi();
+    int64_t n = 0;
+    check(np_hip_index_delete(path.c_str(), doc_ids.data(), (int64_t)doc_ids.size(), &n));
+    return n;
   }
   bool on_device() const { return h_ != nullptr; }
   MmapIndex(MmapIndex&& o) noexcept : path(std::move(o.path)), h_(o.h_), info_(o.info_) { o.h_ = nullptr; }

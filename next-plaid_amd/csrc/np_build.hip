@@ -29,12 +29,6 @@
 #include <vector>
 
 namespace np {
-int write_npy_file(const std::string& path, const char* descr, const int64_t* shape, int ndim, const void* data,
-                   size_t bytes);   // np_writer.cpp
-int write_text_file(const std::string& path, const std::string& text);
-}  // namespace np
-
-namespace np {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -308,6 +302,58 @@ __global__ void __launch_bounds__(1024) km_shift_kernel(const float* __restrict_
   if (threadIdx.x == 0) *out = s[0];
 }
 
+// find_outliers (update.rs:490-619) after one nearest_step over all K centroids.  The f32 minimum d of a row is decided
+// here when it lies outside the window |d - thr2| <= w; w covers the crate's own recheck window max(|thr2|, 1) 1e-5
+// and this path's f32 error: |x|^2, |c|^2 and x.c are Dp-term f32 chains and the epilogue adds three roundings, so
+// |d - |x - c|^2| <= 4 (Dp + 2) 2^-24 (|x|^2 + max |c|^2) for every centroid, hence for the minimum.  Rows inside the
+// window go to a list for the f64 recheck.
+__global__ void __launch_bounds__(256) ol_flag_kernel(const unsigned long long* __restrict__ best, const float* __restrict__ xn,
+                                                      int64_t n, float thr2, float rel, float cn_max, uint8_t* __restrict__ flag,
+                                                      int32_t* __restrict__ list, int32_t* __restrict__ n_list) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float d = __uint_as_float((uint32_t)(best[i] >> 32));
+  const float w = fmaxf(fmaxf(fabsf(thr2), 1.f) * 1e-5f, rel * (xn[i] + cn_max));
+  if (fabsf(d - thr2) <= w) {
+    flag[i] = 0;
+    list[atomicAdd(n_list, 1)] = (int32_t)i;
+  } else {
+    flag[i] = d > thr2 ? 1 : 0;
+  }
+}
+
+// min_distance_sq_precise (update.rs:457-473) for one listed row per workgroup: per centroid the f64 sum of (x_j - c_j)^2 in
+// dimension order (no contraction), cast to f32, minimum over all k centroids; the row is an outlier when it exceeds thr2.
+// The zero padding of the storage rows adds exact zeros.
+__global__ void __launch_bounds__(256) ol_recheck_kernel(const float* __restrict__ X, int Dp, const float* __restrict__ C,
+                                                         int64_t k, const int32_t* __restrict__ list, float thr2,
+                                                         uint8_t* __restrict__ flag) {
+#pragma clang fp contract(off)
+  __shared__ double sx[128];
+  __shared__ float smin[256];
+  const int tid = threadIdx.x;
+  const int64_t row = list[blockIdx.x];
+  if (tid < Dp) sx[tid] = (double)X[row * Dp + tid];
+  __syncthreads();
+  float mn = __int_as_float(0x7F800000);
+  for (int64_t c = tid; c < k; c += 256) {
+    const float* cr = C + c * Dp;
+    double s = 0.0;
+    for (int j = 0; j < Dp; ++j) {
+      const double df = sx[j] - (double)cr[j];
+      s += df * df;
+    }
+    mn = fminf(mn, (float)s);
+  }
+  smin[tid] = mn;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) smin[tid] = fminf(smin[tid], smin[tid + w]);
+    __syncthreads();
+  }
+  if (tid == 0) flag[row] = smin[0] > thr2 ? 1 : 0;
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------
 struct DevMem {   // every device buffer of one call, freed on every exit path
   std::vector<void*> ptrs;
@@ -399,6 +445,47 @@ void launch_mean(const float* X, const int32_t* order, const int32_t* off, const
   km_mean_kernel<D><<<(unsigned)k, 256, 0, st>>>(X, order, off, reinit, cmax, Cold, Cnew, part);
 }
 
+// points [m][dim] (host; row j = points[subset[j]] with a subset) -> HBM in storage rows zero-padded to Dp, through a
+// bounded staging buffer
+int upload_rows(float* dX, const float* points, int64_t m, int dim, int Dp, const uint32_t* subset, hipStream_t st) {
+  const int64_t rows = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)Dp * 4));
+  std::vector<float> stage((size_t)std::min(rows, m) * Dp, 0.f);
+  for (int64_t r0 = 0; r0 < m; r0 += rows) {
+    const int64_t nr = std::min(rows, m - r0);
+    for (int64_t r = 0; r < nr; ++r) {
+      const int64_t src = subset ? (int64_t)subset[r0 + r] : r0 + r;
+      memcpy(&stage[(size_t)(r * Dp)], points + src * dim, (size_t)dim * 4);
+    }
+    NP_HIP(hipMemcpyAsync(dX + r0 * Dp, stage.data(), (size_t)nr * Dp * 4, hipMemcpyHostToDevice, st));
+    NP_HIP(hipStreamSynchronize(st));   // the staging buffer is reused
+  }
+  return NP_OK;
+}
+
+// centroid chunks of the assign grid: enough workgroups for the device when the points alone do not fill it
+int assign_chunks(int device, int64_t m, int64_t ntiles) {
+  int n_cu = 256;
+  hipDeviceProp_t p;
+  if (hipGetDeviceProperties(&p, device) == hipSuccess && p.multiProcessorCount > 0) n_cu = p.multiProcessorCount;
+  const int64_t pblocks = (m + 255) / 256;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * n_cu + pblocks - 1) / pblocks));
+}
+
+// best[i] = min over the k centroids of (distance bits << 32 | index) for the m points (tiles, then the fused assign)
+int nearest_step(const float* dX, const float* dxn, int64_t m, int Dp, const float* dC, int64_t k, int64_t ntiles,
+                 int chunks, float* dCt, unsigned long long* dbest, hipStream_t st) {
+  km_tiles_kernel<<<(unsigned)((ntiles * 32 + 255) / 256), 256, 0, st>>>(dC, k, Dp, ntiles, dCt);
+  NP_HIP(hipMemsetAsync(dbest, 0xFF, (size_t)m * 8, st));
+  switch (Dp) {
+    case 32: launch_assign<32>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
+    case 64: launch_assign<64>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
+    case 96: launch_assign<96>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
+    default: launch_assign<128>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
+  }
+  NP_HIP(hipGetLastError());
+  return NP_OK;
+}
+
 // FastKMeans::train.  points [n][dim] host; out_centroids [k][dim]; out_assign nullable [n]
 int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kmeans_opts& o, const float* init,
                float* out_centroids, int64_t* out_assign, np_kmeans_report* rep) {
@@ -472,29 +559,12 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
   NP_TRY(dm.alloc(&dreinit, (size_t)k));
   NP_TRY(dm.alloc(&dshift, 1));
 
-  // points -> HBM in storage rows (zero-padded to Dp), through a bounded staging buffer
-  {
-    const int64_t rows = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)Dp * 4));
-    std::vector<float> stage((size_t)std::min(rows, m) * Dp, 0.f);
-    for (int64_t r0 = 0; r0 < m; r0 += rows) {
-      const int64_t nr = std::min(rows, m - r0);
-      for (int64_t r = 0; r < nr; ++r) memcpy(&stage[(size_t)(r * Dp)], points + src_row(r0 + r) * dim, (size_t)dim * 4);
-      NP_HIP(hipMemcpyAsync(dX + r0 * Dp, stage.data(), (size_t)nr * Dp * 4, hipMemcpyHostToDevice, st));
-      NP_HIP(hipStreamSynchronize(st));   // the staging buffer is reused
-    }
-  }
+  NP_TRY(upload_rows(dX, points, m, dim, Dp, sub ? subset.data() : nullptr, st));
   NP_HIP(hipMemcpyAsync(dC[0], c0.data(), (size_t)k * Dp * 4, hipMemcpyHostToDevice, st));
   km_norm_kernel<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(dX, m, Dp, dxn, damax);
   NP_HIP(hipGetLastError());
 
-  // centroid chunks: enough workgroups for the device when the points alone do not fill it
-  int n_cu = 256;
-  {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) == hipSuccess && p.multiProcessorCount > 0) n_cu = p.multiProcessorCount;
-  }
-  const int64_t pblocks = (m + 255) / 256;
-  const int chunks = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, (2 * n_cu + pblocks - 1) / pblocks));
+  const int chunks = assign_chunks(device, m, ntiles);
 
   std::vector<int32_t> counts((size_t)k), off((size_t)k + 1), reinit((size_t)k);
   int cur = 0, it = 0;
@@ -503,15 +573,7 @@ int kmeans_run(int device, const float* points, int64_t n, int dim, const np_kme
   const unsigned nb = (unsigned)((m + 255) / 256);
   while (it < o.max_iters) {
     NP_HIP(hipEventRecord(dm.ev[0], st));
-    km_tiles_kernel<<<(unsigned)((ntiles * 32 + 255) / 256), 256, 0, st>>>(dC[cur], k, Dp, ntiles, dCt);
-    NP_HIP(hipMemsetAsync(dbest, 0xFF, (size_t)m * 8, st));
-    switch (Dp) {
-      case 32: launch_assign<32>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
-      case 64: launch_assign<64>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
-      case 96: launch_assign<96>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
-      default: launch_assign<128>(dX, dxn, m, dCt, (int)ntiles, chunks, dbest, st); break;
-    }
-    NP_HIP(hipGetLastError());
+    NP_TRY(nearest_step(dX, dxn, m, Dp, dC[cur], k, ntiles, chunks, dCt, dbest, st));
     NP_HIP(hipEventRecord(dm.ev[1], st));
     NP_HIP(hipMemsetAsync(dcount, 0, (size_t)k * 4, st));
     NP_HIP(hipMemsetAsync(dcmax, 0, (size_t)k * 4, st));
@@ -789,6 +851,99 @@ int codec_artifacts_impl(int device, const float* emb, const int64_t* doc_length
 }
 
 }  // namespace
+
+// ---- the update path's device work (np_update.cpp) ----------------------------------------------------------------------
+int build_check_device(int device) { return check_build_device(device); }
+int build_check_dim(int dim) { return check_dim(dim); }
+int build_check_finite(const float* x, int64_t count, int dim) { return check_finite(x, count, dim); }
+float quantile_of_sorted(const std::vector<float>& v, double q) { return quantile_sorted(v, q); }
+
+int find_outliers(int device, const float* X, int64_t n, int dim, const float* C, int64_t k, float thr,
+                  std::vector<int64_t>* out, int64_t* n_rechecked) {
+  out->clear();
+  if (n_rechecked) *n_rechecked = 0;
+  if (n <= 0 || k <= 0) return NP_OK;
+  NP_TRY(check_dim(dim));
+  if (n >= ((int64_t)1 << 31)) {
+    set_error("Update failed: the outlier search takes fewer than 2^31 tokens, got %lld", (long long)n);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  NP_TRY(check_build_device(device));
+  DeviceGuard g(device);
+  const int Dp = storage_dim(dim);
+  const int64_t ntiles = (k + 31) / 32;
+  std::vector<float> cpad((size_t)k * Dp, 0.f);
+  float cn_max = 0.f;
+  for (int64_t c = 0; c < k; ++c) {
+    float ss = 0.f;
+    for (int j = 0; j < dim; ++j) {
+      const float v = C[c * dim + j];
+      cpad[(size_t)(c * Dp + j)] = v;
+      ss = fmaf(v, v, ss);
+    }
+    cn_max = std::max(cn_max, ss);
+  }
+  cn_max *= 1.0f + 1e-3f;   // the host chain's own rounding
+  DevMem dm;
+  NP_HIP(hipStreamCreateWithFlags(&dm.st, hipStreamNonBlocking));
+  hipStream_t st = dm.st;
+  float *dX, *dxn, *damax, *dC, *dCt;
+  unsigned long long* dbest;
+  uint8_t* dflag;
+  int32_t *dlist, *dnlist;
+  NP_TRY(dm.alloc(&dX, (size_t)n * Dp));
+  NP_TRY(dm.alloc(&dxn, (size_t)n));
+  NP_TRY(dm.alloc(&damax, (size_t)n));
+  NP_TRY(dm.alloc(&dC, (size_t)k * Dp));
+  NP_TRY(dm.alloc(&dCt, (size_t)ntiles * (Dp * 32 + 32) + 256));   // + 1 KiB: the last DMA piece reads past the tile
+  NP_TRY(dm.alloc(&dbest, (size_t)n));
+  NP_TRY(dm.alloc(&dflag, (size_t)n));
+  NP_TRY(dm.alloc(&dlist, (size_t)n));
+  NP_TRY(dm.alloc(&dnlist, 1));
+  NP_TRY(upload_rows(dX, X, n, dim, Dp, nullptr, st));
+  NP_HIP(hipMemcpyAsync(dC, cpad.data(), cpad.size() * 4, hipMemcpyHostToDevice, st));
+  NP_HIP(hipMemsetAsync(dnlist, 0, 4, st));
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  km_norm_kernel<<<nb, 256, 0, st>>>(dX, n, Dp, dxn, damax);
+  NP_HIP(hipGetLastError());
+  NP_TRY(nearest_step(dX, dxn, n, Dp, dC, k, ntiles, assign_chunks(device, n, ntiles), dCt, dbest, st));
+  const float thr2 = thr * thr;
+  const float rel = 4.0f * (float)(Dp + 2) * 0x1p-24f;
+  ol_flag_kernel<<<nb, 256, 0, st>>>(dbest, dxn, n, thr2, rel, cn_max, dflag, dlist, dnlist);
+  NP_HIP(hipGetLastError());
+  int32_t nl = 0;
+  NP_HIP(hipMemcpyAsync(&nl, dnlist, 4, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipStreamSynchronize(st));
+  if (nl > 0) {
+    ol_recheck_kernel<<<(unsigned)nl, 256, 0, st>>>(dX, Dp, dC, k, dlist, thr2, dflag);
+    NP_HIP(hipGetLastError());
+  }
+  std::vector<uint8_t> flag((size_t)n);
+  NP_HIP(hipMemcpyAsync(flag.data(), dflag, (size_t)n, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < n; ++i)
+    if (flag[(size_t)i]) out->push_back(i);
+  if (n_rechecked) *n_rechecked = nl;
+  return NP_OK;
+}
+
+int kmeans_points_as_docs(int device, const float* pts, int64_t n, int dim, const np_index_config& cfg, int64_t k,
+                          std::vector<float>* cen) {
+  np_index_config c = with_defaults(&cfg);
+  c.num_partitions = k;
+  const std::vector<int64_t> ones((size_t)n, 1);
+  int64_t kk = 0;
+  return compute_kmeans_impl(device, pts, ones.data(), n, dim, c, cen, &kk, nullptr);
+}
+
+int encode_with_codec(int device, const float* C, int64_t K, int dim, int nbits, const float* weights, const float* cutoffs,
+                      const float* X, int64_t T, int64_t* codes, uint8_t* packed, float* norms) {
+  if (T <= 0) return NP_OK;
+  HandleCloser hc;
+  NP_TRY(codec_handle(device, C, K, dim, nbits, weights, &hc.h));
+  return encode_tokens_impl(hc.h, X, T, dim, cutoffs, codes, packed, norms);
+}
+
 }  // namespace np
 
 using namespace np;

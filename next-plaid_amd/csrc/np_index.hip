@@ -1609,6 +1609,8 @@ int64_t np_hip_struct_size(int32_t which) {
     case 5: return (int64_t)sizeof(np_kmeans_report);
     case 6: return (int64_t)sizeof(np_index_config);
     case 7: return (int64_t)sizeof(np_kmeans_plan);
+    case 8: return (int64_t)sizeof(np_update_config);
+    case 9: return (int64_t)sizeof(np_update_report);
     default: return -1;
   }
 }

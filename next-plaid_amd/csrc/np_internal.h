@@ -94,6 +94,35 @@ struct HostIndex {
 // np_loader.cpp: MmapIndex::load's file parsing (index.rs:1026-1139, mmap.rs:659-749)
 int load_index_dir(const char* dir, HostIndex* out);
 
+// np_loader.cpp: the loader's parsers for the update path (np_update.cpp), over files read whole
+int read_text_file(const std::string& path, std::string* out);
+bool json_number_field(const std::string& j, const char* key, double* out);
+int json_int_list(const std::string& path, const std::string& j, std::vector<int64_t>* out);
+// NPY v1 / v2: *data points into *bytes; descr and shape as in the header (fortran order refused)
+int read_npy_file(const std::string& path, std::vector<uint8_t>* bytes, std::string* descr, std::vector<int64_t>* shape,
+                  const uint8_t** data);
+
+// np_writer.cpp: the writer's temporary-name + fsync + rename files, and serde's f64 text
+int write_npy_file(const std::string& path, const char* descr, const int64_t* shape, int ndim, const void* data,
+                   size_t bytes);
+int write_text_file(const std::string& path, const std::string& text);
+std::string format_f64(double v);
+
+// np_build.hip: the device work of the update path (np_update.cpp), with the create path's rules and input checks
+int build_check_device(int device);
+int build_check_dim(int dim);
+int build_check_finite(const float* x, int64_t count, int dim);
+// rows of X [n][dim] whose f32(min_c f64 |x - c|^2) > thr * thr (f32), ascending; *n_rechecked = rows the f64 pass decided
+int find_outliers(int device, const float* X, int64_t n, int dim, const float* C, int64_t k, float thr,
+                  std::vector<int64_t>* out, int64_t* n_rechecked);
+// compute_kmeans on the points as one-token documents with num_partitions = k (update.rs:700-730)
+int kmeans_points_as_docs(int device, const float* pts, int64_t n, int dim, const np_index_config& cfg, int64_t k,
+                          std::vector<float>* cen);
+// every token encoded against a codec (np_hip_encode_tokens' rules); norms (nullable) = |x - c[code]| per token
+int encode_with_codec(int device, const float* C, int64_t K, int dim, int nbits, const float* weights, const float* cutoffs,
+                      const float* X, int64_t T, int64_t* codes, uint8_t* packed, float* norms);
+float quantile_of_sorted(const std::vector<float>& v, double q);   // utils.rs:94-149
+
 // ---- device buffers ------------------------------------------------------------------------
 struct DevBuf {
   void* p = nullptr;
@@ -262,6 +291,9 @@ void shard_range(int64_t n_total, int rank, int count, int64_t* b, int64_t* e);
 
 // np_search.hip
 void destroy_context(Context* c);
+// np_hip_encode_tokens with an optional third output: norms[t] = |x_t - c[code_t]| (sequential f32 sum, no contraction)
+int encode_tokens_impl(const np_index* index, const float* embeddings, int64_t n_tokens, int32_t dim,
+                       const float* bucket_cutoffs, int64_t* out_codes, uint8_t* out_packed, float* out_norms);
 // document-sharded exchange on records with a per-rank status trailer (np_dist.hip); the C ABI's np_hip_select_cut /
 // np_hip_merge_packed are the status-free cases
 int select_cut_strided(const DeviceIndex* ix, const uint64_t* d_all_keys, int64_t rank_stride, int64_t status_off, int G,

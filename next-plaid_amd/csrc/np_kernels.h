@@ -5772,6 +5772,25 @@ __global__ void __launch_bounds__(256) encode_pack_kernel(const float* __restric
   packed[i] = (uint8_t)byte;
 }
 
+// the update path's residual norms (update.rs:870-876): |x - centroid[code]| per token from the codes encode_argmax left on
+// the device, one thread per token.  The sum of squares is a sequential f32 sum without contraction, the rule
+// prepare_codec_artifacts uses for cluster_threshold (np_build.hip), so both thresholds come from one formula
+__global__ void __launch_bounds__(256) encode_norm_kernel(const float* __restrict__ x, const float* __restrict__ C,
+                                                          const int64_t* __restrict__ codes, int64_t n_tokens, int dim,
+                                                          int cdim, float* __restrict__ norms) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_tokens) return;
+  const float* xr = x + t * dim;
+  const float* cr = C + codes[t] * cdim;
+  float ss = 0.f;
+  for (int j = 0; j < dim; ++j) {
+    const float r = xr[j] - cr[j];
+    ss += r * r;
+  }
+  norms[t] = __fsqrt_rn(ss);
+}
+
 // ---------------------------------------------------------------------------------------------
 // N4  /rerank MaxSim on caller-supplied embeddings (next-plaid-api handlers/rerank.rs:57-94):
 // sim = sequential sum of q*d products (multiply, then add: no FMA), max over document tokens, sum over query

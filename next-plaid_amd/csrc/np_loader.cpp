@@ -441,4 +441,41 @@ int load_index_dir(const char* dir, HostIndex* hi) {
   return NP_OK;
 }
 
+
+// ---- the same parsers for the update path (np_update.cpp) ----------------------------------------------------------
+int read_text_file(const std::string& path, std::string* out) { return read_text(path, out, NP_ERR_IO); }
+bool json_number_field(const std::string& j, const char* key, double* out) { return json_number(j, key, out); }
+int json_int_list(const std::string& path, const std::string& j, std::vector<int64_t>* out) {
+  return json_int_array(path, j, out);
+}
+
+int read_npy_file(const std::string& path, std::vector<uint8_t>* bytes, std::string* descr, std::vector<int64_t>* shape,
+                  const uint8_t** data) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) {
+    set_error("Failed to open %s: %s", path.c_str(), strerror(errno));
+    return NP_ERR_IO;
+  }
+  bytes->clear();
+  uint8_t buf[1 << 16];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) bytes->insert(bytes->end(), buf, buf + n);
+  fclose(f);
+  Npy np_;
+  NP_TRY(parse_npy(path, bytes->data(), bytes->size(), &np_));
+  if (np_.fortran && np_.shape.size() > 1) {
+    set_error("fortran_order NPY not supported: %s", path.c_str());
+    return NP_ERR_INDEX_LOAD;
+  }
+  const int es = elem_size(np_.descr);
+  if (np_.descr.size() < 3 || np_.descr[0] == '>' || es <= 0 || (size_t)np_.count() * (size_t)es > np_.data_bytes) {
+    set_error("Unexpected dtype '%s' or short data in %s", np_.descr.c_str(), path.c_str());
+    return NP_ERR_INDEX_LOAD;
+  }
+  *descr = np_.descr;
+  *shape = np_.shape;
+  *data = np_.data;
+  return NP_OK;
+}
+
 }  // namespace np

@@ -2010,6 +2010,12 @@ int np_hip_debug_trace(const np_index* ix, const float* query, int32_t n_tokens,
 int np_hip_encode_tokens(const np_index* ix, const float* embeddings, int64_t n_tokens, int32_t dim,
                          const float* bucket_cutoffs, int64_t* out_codes, uint8_t* out_packed) {
   clear_error();
+  return np::encode_tokens_impl(ix, embeddings, n_tokens, dim, bucket_cutoffs, out_codes, out_packed, nullptr);
+}
+}  // extern "C"
+
+int np::encode_tokens_impl(const np_index* ix, const float* embeddings, int64_t n_tokens, int32_t dim,
+                           const float* bucket_cutoffs, int64_t* out_codes, uint8_t* out_packed, float* out_norms) {
   if (!ix || n_tokens < 0 || (n_tokens > 0 && (!embeddings || !out_codes || !out_packed)) || !bucket_cutoffs) {
     set_error("encode_tokens: invalid argument");
     return NP_ERR_INVALID_ARGUMENT;
@@ -2054,6 +2060,7 @@ int np_hip_encode_tokens(const np_index* ix, const float* embeddings, int64_t n_
   NP_TRY(w.out_ids.reserve((size_t)TB * 8));
   NP_TRY(w.cand.reserve((size_t)TB * pd));
   NP_TRY(w.misc.reserve(std::max<size_t>(64, (size_t)ncut * 4)));
+  if (out_norms) NP_TRY(w.approx.reserve((size_t)TB * 4));
   NP_HIP(hipMemcpyAsync(w.misc.p, bucket_cutoffs, (size_t)ncut * 4, hipMemcpyHostToDevice, st));
   std::vector<int32_t> h_off((size_t)S + 1);
   for (int64_t t0 = 0; t0 < n_tokens; t0 += TB) {
@@ -2075,14 +2082,20 @@ int np_hip_encode_tokens(const np_index* ix, const float* embeddings, int64_t n_
     encode_pack_kernel<<<(unsigned)((nb * pd + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids,
                                                                          w.out_ids.as<int64_t>(), w.misc.as<float>(), nb,
                                                                          dim, sdim, ix->lnbits, w.cand.as<uint8_t>());
+    if (out_norms)
+      encode_norm_kernel<<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids, w.out_ids.as<int64_t>(),
+                                                                        nb, dim, sdim, w.approx.as<float>());
     NP_HIP(hipGetLastError());
     NP_HIP(hipMemcpyAsync(out_codes + t0, w.out_ids.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
     NP_HIP(hipMemcpyAsync(out_packed + t0 * pd, w.cand.p, (size_t)nb * pd, hipMemcpyDeviceToHost, st));
+    if (out_norms) NP_HIP(hipMemcpyAsync(out_norms + t0, w.approx.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
     NP_HIP(hipStreamSynchronize(st));   // h_off / the workspace are reused by the next slice
   }
   NP_TRY(end_use(&cs));
   return NP_OK;
 }
+
+extern "C" {
 
 // ---- N4: /rerank MaxSim on caller-supplied embeddings (next-plaid-api handlers/rerank.rs:57-94,139-170) ---------
 int np_hip_rerank_maxsim(int32_t device, const float* query, int32_t n_query_tokens, int32_t dim,

@@ -132,6 +132,7 @@ int write_npy_file(const std::string& path, const char* descr, const int64_t* sh
   return write_npy(path, descr, shape, ndim, data, bytes);
 }
 int write_text_file(const std::string& path, const std::string& text) { return write_text(path, text); }
+std::string format_f64(double v) { return fmt_double(v); }
 
 }  // namespace np
 

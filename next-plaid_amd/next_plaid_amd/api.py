@@ -141,6 +141,26 @@ class np_kmeans_plan(C.Structure):
                 ("codec_samples", C.c_int64), ("heldout_size", C.c_int64), ("heldout_tokens", C.c_int64)]
 
 
+class np_update_config(C.Structure):
+    _fields_ = [("batch_size", C.c_int64), ("kmeans_niters", C.c_int32), ("reserved0", C.c_int32),
+                ("max_points_per_centroid", C.c_int64), ("n_samples_kmeans", C.c_int64), ("seed", C.c_uint64),
+                ("start_from_scratch", C.c_int64), ("buffer_size", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
+class np_update_report(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("reserved0", C.c_int32), ("first_doc_id", C.c_int64), ("n_outliers", C.c_int64),
+                ("n_rechecked", C.c_int64), ("n_new_centroids", C.c_int64), ("n_reindexed", C.c_int64),
+                ("ms_encode", C.c_double), ("ms_outliers", C.c_double), ("ms_kmeans", C.c_double), ("ms_files", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+    MODES = {0: "none", 1: "start_from_scratch", 2: "buffer", 3: "expansion", 4: "append"}
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+        d["mode"] = self.MODES.get(self.mode, str(self.mode))
+        return d
+
+
 # np_all_gather_host_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes)
 ALL_GATHER_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 NP_COMM_DEFERRED_STATUS = 1
@@ -158,6 +178,7 @@ EXPORTS = [
     "np_hip_search_batch_sharded",
     "np_hip_decompress_documents", "np_hip_encode_tokens", "np_hip_rerank_maxsim", "np_hip_debug_trace",
     "np_hip_kmeans_plan", "np_hip_kmeans", "np_hip_compute_kmeans", "np_hip_prepare_codec_artifacts", "np_hip_index_create",
+    "np_hip_index_update", "np_hip_index_update_append", "np_hip_index_delete",
 ]
 
 _lib = None
@@ -210,7 +231,8 @@ def lib():
     if ver != NP_ABI_VERSION:
         raise DeviceUnavailableError(f"{path} speaks ABI v{ver}, this mirror v{NP_ABI_VERSION}: rebuild the library")
     for which, st in ((0, np_info), (1, np_stats), (2, np_search_params), (3, np_open_opts), (4, np_kmeans_opts),
-                      (5, np_kmeans_report), (6, np_index_config), (7, np_kmeans_plan)):
+                      (5, np_kmeans_report), (6, np_index_config), (7, np_kmeans_plan), (8, np_update_config),
+                      (9, np_update_report)):
         if int(L.np_hip_struct_size(which)) != C.sizeof(st):
             raise DeviceUnavailableError(f"{path}: sizeof({st.__name__}) is {int(L.np_hip_struct_size(which))} in the library, "
                                          f"{C.sizeof(st)} in this mirror")
@@ -267,6 +289,9 @@ def lib():
     L.np_hip_prepare_codec_artifacts.argtypes = [i32, vp, vp, i64, i32, vp, i64, C.POINTER(np_index_config), vp, vp, vp, vp]
     L.np_hip_index_create.argtypes = [C.c_char_p, vp, vp, i64, i32, C.POINTER(np_index_config), C.POINTER(np_open_opts),
                                       C.POINTER(vp)]
+    for f in (L.np_hip_index_update, L.np_hip_index_update_append):
+        f.argtypes = [C.c_char_p, vp, vp, i64, i32, C.POINTER(np_update_config), i32, C.POINTER(np_update_report)]
+    L.np_hip_index_delete.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     _lib = L
     return L
 
@@ -440,6 +465,92 @@ class IndexConfig:
                                -1 if int(self.start_from_scratch) == 0 else int(self.start_from_scratch))
 
 
+@dataclass
+class UpdateConfig:
+    """UpdateConfig (update.rs:75-107): same field names and defaults.  start_from_scratch = 0 and buffer_size = 0 keep the
+    crate's meaning (only an empty index starts from scratch; every update expands)."""
+    batch_size: int = 50_000
+    kmeans_niters: int = 4
+    max_points_per_centroid: int = 256
+    n_samples_kmeans: int | None = None
+    seed: int = 42
+    start_from_scratch: int = 999
+    buffer_size: int = 100
+
+    _USIZE = ("batch_size", "kmeans_niters", "max_points_per_centroid", "seed", "start_from_scratch", "buffer_size")
+
+    # serde (update.rs:75-93): no #[serde(default)] on the struct, so every field but the Option and force_cpu is required;
+    # force_cpu (and any other unknown field) is ignored
+    @classmethod
+    def from_json(cls, text) -> "UpdateConfig":
+        import json
+        d = json.loads(text) if isinstance(text, (str, bytes)) else dict(text)
+        for k in cls._USIZE:
+            if k not in d:
+                raise ValueError(f"missing field `{k}`")
+        for k in cls._USIZE:
+            if isinstance(d[k], bool) or not isinstance(d[k], int) or d[k] < 0:
+                raise ValueError(f"invalid type for `{k}`: expected usize")
+        ns = d.get("n_samples_kmeans")
+        if ns is not None and (isinstance(ns, bool) or not isinstance(ns, int) or ns < 0):
+            raise ValueError("invalid type for `n_samples_kmeans`: expected usize")
+        return cls(**{k: d[k] for k in cls._USIZE}, n_samples_kmeans=ns)
+
+    def to_json(self) -> str:
+        import json
+        return json.dumps(dict(batch_size=self.batch_size, kmeans_niters=self.kmeans_niters,
+                               max_points_per_centroid=self.max_points_per_centroid, n_samples_kmeans=self.n_samples_kmeans,
+                               seed=self.seed, start_from_scratch=self.start_from_scratch, buffer_size=self.buffer_size,
+                               force_cpu=False))
+
+    def _c(self) -> np_update_config:
+        for k in ("batch_size", "kmeans_niters", "max_points_per_centroid"):
+            if int(getattr(self, k)) <= 0:
+                raise ValueError(f"UpdateConfig.{k} must be > 0")
+        return np_update_config(int(self.batch_size), int(self.kmeans_niters), 0, int(self.max_points_per_centroid),
+                                int(self.n_samples_kmeans or 0), int(self.seed) & (2**64 - 1),
+                                -1 if int(self.start_from_scratch) == 0 else int(self.start_from_scratch),
+                                -1 if int(self.buffer_size) == 0 else int(self.buffer_size))
+
+
+def _update_docs(documents):
+    """Like _docs, but an empty list is allowed (an update with no documents changes nothing)."""
+    if len(documents) == 0:
+        return np.zeros((1, 1), np.float32), np.zeros(0, np.int64), None
+    return _docs(documents)
+
+
+def _update_call(fn, index_path: str, documents, config, device: int):
+    flat, lens, dim = _update_docs(documents)
+    rep = np_update_report()
+    cfg = (config or UpdateConfig())._c()
+    if lens.size == 0:
+        dim = 0
+    _check(fn(os.fsencode(index_path), _ptr(flat), _ptr(lens), lens.size, int(dim or 0), C.byref(cfg), int(device),
+              C.byref(rep)))
+    ids = np.arange(rep.first_doc_id, rep.first_doc_id + lens.size, dtype=np.int64)
+    return ids, rep.as_dict()
+
+
+def update_index_dir(index_path: str, documents, config: UpdateConfig | None = None, device: int = 0):
+    """MmapIndex::update on a directory (index.rs:1431-1590): returns (new document ids, report dict)."""
+    return _update_call(lib().np_hip_index_update, index_path, documents, config, device)
+
+
+def update_append_dir(index_path: str, documents, config: UpdateConfig | None = None, device: int = 0):
+    """MmapIndex::update_append (index.rs:1675-1700): returns (new document ids, report dict)."""
+    return _update_call(lib().np_hip_index_update_append, index_path, documents, config, device)
+
+
+def delete_from_index_dir(index_path: str, doc_ids) -> int:
+    """MmapIndex::delete (delete.rs:43-268), host only: the number of distinct ids removed.  Ids outside
+    [0, num_documents) are ignored (include/nextplaid_hip.h)."""
+    ids = np.ascontiguousarray(np.asarray(doc_ids, np.int64).reshape(-1))
+    out = C.c_int64(0)
+    _check(lib().np_hip_index_delete(os.fsencode(index_path), _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
+    return int(out.value)
+
+
 def _docs(documents):
     """List of [n_i, dim] arrays -> (flat f32 [sum n_i, dim], lengths i64, dim)."""
     docs = [np.ascontiguousarray(d, np.float32) for d in documents]
@@ -553,6 +664,7 @@ class MmapIndex:
         self._info = np_info()
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         self.last_stats: dict | None = None
+        self.last_update: dict | None = None
 
     # -- constructors ---------------------------------------------------------------------------------
     @classmethod
@@ -590,6 +702,40 @@ class MmapIndex:
         self._h = h
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         self.last_stats = None
+
+    # -- update / delete (index.rs:1431-1775) ----------------------------------------------------------------
+    def _dir(self, what: str) -> str:
+        if not self.path or self.path.startswith("<"):
+            raise IndexLoadError(f"Index load failed: {what}() needs an index opened from a directory")
+        return self.path
+
+    def update(self, documents, config: UpdateConfig | None = None) -> np.ndarray:
+        """MmapIndex::update (index.rs:1431-1590): the new documents' ids; the handle is reloaded from the rewritten
+        directory.  The report of the call is kept in self.last_update."""
+        path = self._dir("update")
+        ids, self.last_update = update_index_dir(path, documents, config, self._open_opts.get("device", 0))
+        self.reload()
+        return ids
+
+    @staticmethod
+    def update_append(documents, index_path: str, config: UpdateConfig | None = None, device: int = 0) -> np.ndarray:
+        """MmapIndex::update_append (index.rs:1675-1700): appends without a mode choice and without loading the index."""
+        return update_append_dir(index_path, documents, config, device)[0]
+
+    @classmethod
+    def update_or_create(cls, documents, index_path: str, index_config: IndexConfig | None = None,
+                         update_config: UpdateConfig | None = None, **opts):
+        """MmapIndex::update_or_create (index.rs:1644-1673): (index, ids); created when metadata.json is absent."""
+        if os.path.exists(os.path.join(index_path, "metadata.json")):
+            index = cls.load(index_path, **opts)
+            return index, index.update(documents, update_config)
+        index = cls.create_with_kmeans(documents, index_path, index_config, **opts)
+        return index, np.arange(len(documents), dtype=np.int64)
+
+    def delete(self, doc_ids) -> int:
+        """MmapIndex::delete (index.rs:1731-1765): rewrites the directory and returns the count removed; like the crate
+        it does not reload (call reload())."""
+        return delete_from_index_dir(self._dir("delete"), doc_ids)
 
     @classmethod
     def from_arrays(cls, centroids, bucket_weights, ivf, ivf_lengths, doc_lengths, codes, residuals, nbits,

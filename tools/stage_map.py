@@ -49,6 +49,7 @@ OTHER = {
     "select_cut_kernel": "sharded protocol (global cut)", "merge_topk_kernel": "sharded protocol (merge)",
     "set_status_kernel": "sharded protocol (status word)", "or_reduce_kernel": "sharded protocol (subset bitmaps)",
     "decompress_kernel": "N2 decompress_documents", "encode_argmax_kernel": "N3 encode", "encode_pack_kernel": "N3 encode",
+    "encode_norm_kernel": "index update: residual norms of the encode",
     "rerank_kernel": "N4 /rerank",
 }
 
