@@ -814,8 +814,10 @@ __global__ void __launch_bounds__(256) probe_finish_kernel(ProbeP p) {
   //   LAST of equal maxima, so an all-non-finite column yields QC[Lq-1, c].  One LANE per cell.
   // batched path (search.rs:184-196,243-251): the max runs only over (q,c) pairs that were ever
   //   pushed into token q's slab-local heap: pushed <=> fewer than n_probe earlier centroids of the
-  //   same slab score >= QC[q,c].  Pairs inside token q's global top-n_probe are always pushed, so
-  //   the slab prefix is only counted for a token with QC[q,c] >= t_cs outside its top-n_probe.  One WAVE per cell.
+  //   same slab score >= QC[q,c].  Pairs strictly above token q's cut are always pushed, so the slab
+  //   prefix is only counted for a token with QC[q,c] >= t_cs at or below its cut: a centroid TIED with
+  //   the cut may be one the token did not take, and then it entered the heap only if its slab prefix
+  //   lets it (the taken ties pass the same count).  One WAVE per cell.
   const uint32_t ntmp = s_ntmp;
   uint32_t* lst = tmp;   // survivors are compacted in place (reads of entry i happen before any write to slot <= i)
   if (!p.has_thr) {
@@ -861,15 +863,15 @@ __global__ void __launch_bounds__(256) probe_finish_kernel(ProbeP p) {
           const bool qv = qx < Lq;
           const float v = qv ? row[qx] : 0.f;
           const uint32_t k = qv ? okey(v) : 0u;
-          const bool sel = qv && k >= s_tauq[qx];
+          const bool sel = qv && k > s_tauq[qx];            // strictly above the cut: always pushed
           uint32_t kk2 = sel ? k : 0u;
 #pragma unroll
           for (int o = 32; o > 0; o >>= 1) kk2 = max(kk2, (uint32_t)__shfl_xor((int)kk2, o));
           km = max(km, kk2);
-          const unsigned long long selb = __ballot(sel);
-          if (selb && first_sel == 0x7FFFFFFF) first_sel = q0 + (__ffsll((long long)selb) - 1);
+          const unsigned long long nfb = __ballot(qv && k == 0u && s_tauq[qx] == 0u);   // non-finite, cut non-finite
+          if (nfb && first_sel == 0x7FFFFFFF) first_sel = q0 + (__ffsll((long long)nfb) - 1);
           if (km != 0 && unkey(km) >= p.thr) { pass = true; break; }
-          // tokens outside their top-n_probe whose score alone would pass: count the slab prefix
+          // tokens at or below their cut whose score alone would pass: count the slab prefix
           unsigned long long cand = __ballot(qv && !sel && finitef(v) && v >= p.thr);
           while (cand && !pass) {
             const int ql = __ffsll((long long)cand) - 1;

@@ -44,6 +44,21 @@ def to_oracle_params(p):
                               centroid_score_threshold=p.centroid_score_threshold)
 
 
+def assert_ties_strict(ids, groups=(), pairs=(), what=""):
+    """The exact tie rules, where assert_ranking_close lets near-ties swap.  groups: sorted id arrays of byte-identical
+    documents (equal at every stage): inside a result their members ascend and are the group's lowest ids (a cut
+    keeps the lowest).  pairs: (first, second) documents with equal exact scores whose approximate ranks put `first`
+    ahead: when both are in the result, `first` comes first."""
+    ids = np.asarray(ids).tolist()
+    for g in groups:
+        g = np.asarray(g)
+        got = [i for i in ids if i in set(g.tolist())]
+        assert got == g[: len(got)].tolist(), f"{what}: duplicate group {g[:6]}...: result holds {got}"
+    for a, b in pairs:
+        if a in ids and b in ids:
+            assert ids.index(a) < ids.index(b), f"{what}: {a} (better approximate rank) after {b}: {ids}"
+
+
 def assert_ranking_close(ids, scores, ref_ids, ref_scores, rtol, what=""):
     """Same length; scores within rtol; ids identical except inside groups of reference scores that are
     closer than the tolerance (where summation order may legitimately swap neighbours)."""
