@@ -9,6 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <memory>
 #include <thread>
 #include <math.h>
 #include <stdio.h>
@@ -155,39 +156,18 @@ static int check_device(int dev) {
   return NP_OK;
 }
 
-template <class T>
-static int dev_alloc(T** p, size_t n, size_t* acct) {
-  size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  hipError_t e = hipMalloc((void**)p, bytes);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-    return NP_ERR_OUT_OF_MEMORY;
-  }
-  if (acct) *acct += bytes;
-  return NP_OK;
+void destroy_device_index(np_index* ix) {
+  if (!ix) return;
+  DeviceGuard g(ix->device);   // the arrays' owners free them on the current device
+  for (Context* c : ix->contexts) destroy_context(c);
+  delete ix;
 }
 
-void destroy_device_index(DeviceIndex* ix) {
-  if (!ix) return;
-  DeviceGuard g(ix->device);
-  for (Context* c : ix->contexts) destroy_context(c);
-  ix->contexts.clear();
-  (void)hipFree(ix->d_centroids);
-  (void)hipFree(ix->d_wlut);
-  (void)hipFree(ix->d_codes);
-  (void)hipFree(ix->d_ucodes);
-  (void)hipFree(ix->d_ulen);
-  (void)hipFree(ix->d_useg);
-  (void)hipFree(ix->d_doc_meta);
-  (void)hipFree(ix->d_inv_norm);
-  (void)hipFree(ix->d_tok_pos);
-  (void)hipFree(ix->d_residuals);
-  (void)hipFree(ix->d_doc_offsets);
-  (void)hipFree(ix->d_ivf);
-  (void)hipFree(ix->d_ivf_offsets);
-  (void)hipFree(ix->d_ivf_split);
-}
+// a handle being opened: closed on every early return, handed out with release() when the open succeeds
+struct CloseIndex {
+  void operator()(np_index* p) const { destroy_device_index(p); }
+};
+using IndexHandle = std::unique_ptr<np_index, CloseIndex>;
 
 static uint32_t bitrev(uint32_t v, int nbits) {
   uint32_t r = 0;
@@ -237,23 +217,21 @@ __global__ void __launch_bounds__(256) centroid_bound_kernel(const float* __rest
 }
 
 static int upload_codec(DeviceIndex* ix, const float* centroids, const float* bucket_weights) {
-  NP_TRY(dev_alloc(&ix->d_centroids, (size_t)ix->K * ix->dim, &ix->device_bytes));
+  NP_TRY(ix->d_centroids.alloc((size_t)ix->K * ix->dim, &ix->device_bytes));
   if (ix->ldim == ix->dim) {
-    NP_HIP(hipMemcpy(ix->d_centroids, centroids, (size_t)ix->K * ix->dim * sizeof(float), hipMemcpyHostToDevice));
+    NP_HIP(hipMemcpy(ix->d_centroids.get(), centroids, (size_t)ix->K * ix->dim * sizeof(float), hipMemcpyHostToDevice));
   } else {   // rows zero-padded to the storage width (np_internal.h storage_dim)
-    NP_HIP(hipMemset(ix->d_centroids, 0, (size_t)ix->K * ix->dim * sizeof(float)));
-    NP_HIP(hipMemcpy2D(ix->d_centroids, (size_t)ix->dim * sizeof(float), centroids, (size_t)ix->ldim * sizeof(float),
+    NP_HIP(hipMemset(ix->d_centroids.get(), 0, (size_t)ix->K * ix->dim * sizeof(float)));
+    NP_HIP(hipMemcpy2D(ix->d_centroids.get(), (size_t)ix->dim * sizeof(float), centroids, (size_t)ix->ldim * sizeof(float),
                        (size_t)ix->ldim * sizeof(float), (size_t)ix->K, hipMemcpyHostToDevice));
   }
   {
-    uint32_t* d_b = nullptr;
+    DevPtr<uint32_t> d_b;
     uint32_t h_b[2] = {0, 0};
-    NP_HIP(hipMalloc(&d_b, 8));
-    NP_HIP(hipMemset(d_b, 0, 8));
-    centroid_bound_kernel<<<(unsigned)((ix->K + 3) / 4), 256>>>(ix->d_centroids, ix->K, ix->dim, d_b);
-    hipError_t e = hipMemcpy(h_b, d_b, 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_b);
-    NP_HIP(e);
+    NP_TRY(d_b.alloc(2));
+    NP_HIP(hipMemset(d_b.get(), 0, 8));
+    centroid_bound_kernel<<<(unsigned)((ix->K + 3) / 4), 256>>>(ix->d_centroids.get(), ix->K, ix->dim, d_b.get());
+    NP_HIP(hipMemcpy(h_b, d_b.get(), 8, hipMemcpyDeviceToHost));
     float ss;
     memcpy(&ss, &h_b[0], 4);
     ix->cmax = sqrtf(ss) * 1.0001f;   // the f32 sum of squares is within ~dim * 2^-24 of the real one
@@ -269,8 +247,8 @@ static int upload_codec(DeviceIndex* ix, const float* centroids, const float* bu
   for (int s = 0; s < nb; ++s) wok = wok && std::isfinite(wl[s]) && std::fabs(wl[s]) < 1e6f;
   ix->s6_fast_ok = ix->filter_ok && ix->cmax < 1e6f && wok;
   ix->pad_ss = ix->dim > ix->ldim ? (float)(ix->dim - ix->ldim) * (wl[0] * wl[0]) : 0.f;
-  NP_TRY(dev_alloc(&ix->d_wlut, nb, &ix->device_bytes));
-  NP_HIP(hipMemcpy(ix->d_wlut, wl.data(), nb * sizeof(float), hipMemcpyHostToDevice));
+  NP_TRY(ix->d_wlut.alloc(nb, &ix->device_bytes));
+  NP_HIP(hipMemcpy(ix->d_wlut.get(), wl.data(), nb * sizeof(float), hipMemcpyHostToDevice));
   return NP_OK;
 }
 
@@ -460,11 +438,11 @@ static int permute_tokens(const DeviceIndex* ix, int to_sorted) {
   for (int64_t d0 = 0; d0 < ix->n_docs; d0 += (int64_t)1 << 30) {
     const int64_t n = std::min<int64_t>((int64_t)1 << 30, ix->n_docs - d0);
     if (ix->code_wide)
-      sort_doc_tokens_kernel<uint32_t><<<(unsigned)n, 256, lds>>>(ix->d_doc_offsets + d0, (uint32_t*)ix->d_codes, ix->d_residuals,
-                                                                  ix->d_tok_pos, ix->pd, to_sorted);
+      sort_doc_tokens_kernel<uint32_t><<<(unsigned)n, 256, lds>>>(ix->d_doc_offsets.get() + d0, (uint32_t*)ix->d_codes.get(),
+                                                                  ix->d_residuals.get(), ix->d_tok_pos.get(), ix->pd, to_sorted);
     else
-      sort_doc_tokens_kernel<uint16_t><<<(unsigned)n, 256, lds>>>(ix->d_doc_offsets + d0, (uint16_t*)ix->d_codes, ix->d_residuals,
-                                                                  ix->d_tok_pos, ix->pd, to_sorted);
+      sort_doc_tokens_kernel<uint16_t><<<(unsigned)n, 256, lds>>>(ix->d_doc_offsets.get() + d0, (uint16_t*)ix->d_codes.get(),
+                                                                  ix->d_residuals.get(), ix->d_tok_pos.get(), ix->pd, to_sorted);
   }
   NP_HIP(hipGetLastError());
   NP_HIP(hipDeviceSynchronize());
@@ -475,7 +453,7 @@ static int sort_tokens(DeviceIndex* ix) {
   const char* e = getenv("NP_TOK_SORT");
   // opt-in (NP_TOK_SORT=1): measured 1 % on S6 at 1M docs for 2 B/token of HBM, so the default keeps the on-disk order
   if (!(e && *e && atoi(e) != 0) || (ix->pd & 3)) return NP_OK;
-  NP_TRY(dev_alloc(&ix->d_tok_pos, (size_t)ix->T, &ix->device_bytes));
+  NP_TRY(ix->d_tok_pos.alloc((size_t)ix->T, &ix->device_bytes));
   NP_TRY(permute_tokens(ix, 1));
   ix->tok_sorted = true;
   return NP_OK;
@@ -577,25 +555,20 @@ __global__ void __launch_bounds__(256) ivf_cover_kernel(int64_t n_docs, const ui
 
 static int ivf_covers_codes(const DeviceIndex* ix, bool* covers) {
   *covers = false;
-  int* d_missing = nullptr;
-  NP_HIP(hipMalloc(&d_missing, sizeof(int)));
-  hipError_t e = hipMemset(d_missing, 0, sizeof(int));
-  if (e == hipSuccess) {
-    ivf_cover_kernel<<<(unsigned)((ix->n_docs + 3) / 4), 256>>>(ix->n_docs, ix->d_doc_meta, ix->ucodes(), ix->d_ivf,
-                                                                ix->d_ivf_offsets, d_missing);
-    e = hipGetLastError();
-  }
+  DevPtr<int> d_missing;
+  NP_TRY(d_missing.alloc(1));
+  NP_HIP(hipMemset(d_missing.get(), 0, sizeof(int)));
+  ivf_cover_kernel<<<(unsigned)((ix->n_docs + 3) / 4), 256>>>(ix->n_docs, ix->d_doc_meta.get(), ix->ucodes(), ix->d_ivf.get(),
+                                                              ix->d_ivf_offsets.get(), d_missing.get());
+  NP_HIP(hipGetLastError());
   int missing = 1;
-  if (e == hipSuccess) e = hipMemcpy(&missing, d_missing, sizeof(int), hipMemcpyDeviceToHost);
-  (void)hipFree(d_missing);
-  NP_HIP(e);
+  NP_HIP(hipMemcpy(&missing, d_missing.get(), sizeof(int), hipMemcpyDeviceToHost));
   *covers = missing == 0;
   return NP_OK;
 }
 
 // lists_from_codes: the caller built the lists from the distinct codes (build_ivf_from_ucodes), so they cover them
 static int build_ivf_split(DeviceIndex* ix, bool lists_from_codes) {
-  ix->d_ivf_split = nullptr;
   ix->n_ranges = 0;
   if (!ix->tune.s3_gain || !ix->tune.s4_planes || !ix->ivf_sorted || ix->n_docs <= 0 || ix->K <= 0 || ix->ublock_stride <= 0) return NP_OK;
   const int R = (int)((ix->n_docs + NP_SPLIT_RANGE - 1) / NP_SPLIT_RANGE), R1 = R + 1;
@@ -606,8 +579,8 @@ static int build_ivf_split(DeviceIndex* ix, bool lists_from_codes) {
     NP_TRY(ivf_covers_codes(ix, &covers));
     if (!covers) return NP_OK;
   }
-  NP_TRY(dev_alloc(&ix->d_ivf_split, n, &ix->device_bytes));
-  ivf_split_kernel<<<(unsigned)((n + 255) / 256), 256>>>(ix->d_ivf, ix->d_ivf_offsets, ix->K, R1, ix->d_ivf_split);
+  NP_TRY(ix->d_ivf_split.alloc(n, &ix->device_bytes));
+  ivf_split_kernel<<<(unsigned)((n + 255) / 256), 256>>>(ix->d_ivf.get(), ix->d_ivf_offsets.get(), ix->K, R1, ix->d_ivf_split.get());
   NP_HIP(hipGetLastError());
   NP_HIP(hipDeviceSynchronize());
   ix->n_ranges = R;
@@ -615,15 +588,15 @@ static int build_ivf_split(DeviceIndex* ix, bool lists_from_codes) {
 }
 
 static int build_inv_norm(DeviceIndex* ix) {
-  if (ix->d_inv_norm) {
+  if (ix->d_inv_norm.get()) {
     set_error("internal: inv_norm built twice");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  NP_TRY(dev_alloc(&ix->d_inv_norm, (size_t)ix->T, &ix->device_bytes));
+  NP_TRY(ix->d_inv_norm.alloc((size_t)ix->T, &ix->device_bytes));
   if (ix->T > 0) {
     const int64_t nblk = (ix->T + 255) / 256;
-    inv_norm_kernel<<<(unsigned)nblk, 256>>>(ix->T, ix->dim, ix->ldim, ix->nbits, ix->pd, ix->d_centroids, ix->d_wlut, ix->codes(),
-                                             ix->d_residuals, ix->d_inv_norm);
+    inv_norm_kernel<<<(unsigned)nblk, 256>>>(ix->T, ix->dim, ix->ldim, ix->nbits, ix->pd, ix->d_centroids.get(), ix->d_wlut.get(),
+                                             ix->codes(), ix->d_residuals.get(), ix->d_inv_norm.get());
   }
   NP_HIP(hipGetLastError());
   NP_HIP(hipDeviceSynchronize());
@@ -667,49 +640,21 @@ __global__ void doc_meta_kernel(int64_t n_docs, const int64_t* __restrict__ doc_
   meta[d] = make_uint4((uint32_t)d, (uint32_t)ulen[d], (uint32_t)(o & 0xFFFFFFFFll), (uint32_t)((o >> 32) & 0xFF) | (dl << 8));
 }
 
-// d_uoff (list offsets, [n_docs + 1]) is returned to the caller: the IVF build of the synthetic path reads the lists
-// through it; whoever receives it frees it.
-static int build_unique_codes(DeviceIndex* ix, int64_t** d_uoff_out) {
-  *d_uoff_out = nullptr;
+// block stride of the lists (ublock_stride / ublock_hdr) from a histogram of their lengths, and ulen_mean
+static int choose_ublock_stride(DeviceIndex* ix) {
   const int64_t N = ix->n_docs;
-  NP_TRY(dev_alloc(&ix->d_ulen, (size_t)N, &ix->device_bytes));
-  NP_TRY(dev_alloc(&ix->d_useg, (size_t)N, &ix->device_bytes));
-  NP_TRY(dev_alloc(&ix->d_doc_meta, (size_t)N, &ix->device_bytes));
-  int64_t* d_uoff = nullptr;
-  NP_TRY(dev_alloc(&d_uoff, (size_t)N + 1, nullptr));
-  struct FreeOnError {
-    int64_t** p;
-    bool armed = true;
-    ~FreeOnError() {
-      if (armed) {
-        (void)hipFree(*p);
-        *p = nullptr;
-      }
-    }
-  } guard{&d_uoff};
-  NP_HIP(hipMemset(d_uoff, 0, 8));
-  // pass 1: list lengths
-  for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
-    const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
-    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets + d0, ix->codes(), nullptr, nullptr, ix->d_ulen + d0);
-  }
-  NP_HIP(hipGetLastError());
-  // block stride: the smallest multiple of 16 bytes that holds the header and 99.9 % of the lists (at most the staging row)
+  // the smallest multiple of 16 bytes that holds the header and 99.9 % of the lists (at most the staging row)
   const int hdr = (int)(16 / ix->code_bytes());
   const int smax = ix->tune.s4_planes ? (ix->code_wide ? NP_UBLOCK_BIG_U32 : NP_UBLOCK_BIG_U16)
                                       : (ix->code_wide ? NP_UBLOCK_MAX_U32 : NP_UBLOCK_MAX_U16);
   int fit = smax - hdr;
   if (N > 0) {
-    uint32_t* d_hist = nullptr;
+    DevPtr<uint32_t> d_hist;
     uint32_t h_hist[NP_ULEN_BINS];
-    NP_HIP(hipMalloc(&d_hist, sizeof h_hist));
-    hipError_t e = hipMemset(d_hist, 0, sizeof h_hist);
-    if (e == hipSuccess) {
-      ulen_hist_kernel<<<(unsigned)std::min<int64_t>((N + 255) / 256, 1024), 256>>>(ix->d_ulen, N, d_hist);
-      e = hipMemcpy(h_hist, d_hist, sizeof h_hist, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_hist);
-    NP_HIP(e);
+    NP_TRY(d_hist.alloc(NP_ULEN_BINS));
+    NP_HIP(hipMemset(d_hist.get(), 0, sizeof h_hist));
+    ulen_hist_kernel<<<(unsigned)std::min<int64_t>((N + 255) / 256, 1024), 256>>>(ix->d_ulen.get(), N, d_hist.get());
+    NP_HIP(hipMemcpy(h_hist, d_hist.get(), sizeof h_hist, hipMemcpyDeviceToHost));
     double usum = 0;
     for (int q2 = 0; q2 < NP_ULEN_BINS; ++q2) usum += (double)q2 * h_hist[q2];
     ix->ulen_mean = (float)(usum / (double)N);
@@ -722,37 +667,53 @@ static int build_unique_codes(DeviceIndex* ix, int64_t** d_uoff_out) {
   // the stride is a multiple of 64 bytes (blocks start on 64-B sectors: a 192-B block is three sectors, a 16-B aligned
   // 208-B one 4.1 on average), at most 256 bytes
   const int per64 = (int)(64 / ix->code_bytes());
-  const int S = std::max(per64, std::min(smax, (hdr + fit + per64 - 1) / per64 * per64));
-  fit = S - hdr;
-  ix->ublock_stride = S;
+  ix->ublock_stride = std::max(per64, std::min(smax, (hdr + fit + per64 - 1) / per64 * per64));
   ix->ublock_hdr = hdr;
-  const int64_t base_b = N * (int64_t)S;   // first entry of the overflow region
-  int64_t ovf_total = 0;
-  int64_t* d_ovf = nullptr;                // inclusive scan of the overflow sizes
-  struct FreeOvf {
-    int64_t** p;
-    ~FreeOvf() { (void)hipFree(*p); }
-  } free_ovf{&d_ovf};
-  if (N > 0) {
-    int64_t* d_pad = nullptr;
-    void* d_temp = nullptr;
-    NP_TRY(dev_alloc(&d_pad, (size_t)N, nullptr));
-    hipError_t e = hipMalloc(&d_ovf, (size_t)N * 8);
-    if (e == hipSuccess) {
-      ulen_overflow_kernel<<<(unsigned)((N + 255) / 256), 256>>>(ix->d_ulen, N, fit, d_pad);
-      size_t tb = 0;
-      e = hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_pad, d_ovf, (int)N);
-      if (e == hipSuccess) e = hipMalloc(&d_temp, std::max<size_t>(tb, 16));
-      if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_pad, d_ovf, (int)N);
-      if (e == hipSuccess) e = hipMemcpy(&ovf_total, d_ovf + (N - 1), 8, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_pad);
-    (void)hipFree(d_temp);
-    if (e != hipSuccess) {
-      set_error("distinct-code list scan failed: %s", hipGetErrorString(e));
-      return e == hipErrorOutOfMemory ? NP_ERR_OUT_OF_MEMORY : NP_ERR_DEVICE_UNAVAILABLE;
-    }
+  return NP_OK;
+}
+
+// inclusive scan of the overflow lists' sizes (lists longer than `fit`) into d_ovf [n_docs], and their total
+static int scan_overflow(const DeviceIndex* ix, int fit, DevPtr<int64_t>* d_ovf, int64_t* ovf_total) {
+  const int64_t N = ix->n_docs;
+  *ovf_total = 0;
+  if (N == 0) return NP_OK;
+  DevPtr<int64_t> d_pad;   // scan input; it and the scan's temp storage go before the lists are allocated
+  DevPtr<uint8_t> d_temp;
+  NP_TRY(d_pad.alloc((size_t)N));
+  NP_TRY(d_ovf->alloc((size_t)N));
+  ulen_overflow_kernel<<<(unsigned)((N + 255) / 256), 256>>>(ix->d_ulen.get(), N, fit, d_pad.get());
+  size_t tb = 0;
+  hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_pad.get(), d_ovf->get(), (int)N);
+  if (e == hipSuccess) NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, d_pad.get(), d_ovf->get(), (int)N);
+  if (e == hipSuccess) e = hipMemcpy(ovf_total, d_ovf->get() + (N - 1), 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    set_error("distinct-code list scan failed: %s", hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? NP_ERR_OUT_OF_MEMORY : NP_ERR_DEVICE_UNAVAILABLE;
   }
+  return NP_OK;
+}
+
+// d_uoff (list offsets, [n_docs + 1]) goes back to the caller: the IVF build of the synthetic path reads the lists through it
+static int build_unique_codes(DeviceIndex* ix, DevPtr<int64_t>* d_uoff) {
+  const int64_t N = ix->n_docs;
+  NP_TRY(ix->d_ulen.alloc((size_t)N, &ix->device_bytes));
+  NP_TRY(ix->d_useg.alloc((size_t)N, &ix->device_bytes));
+  NP_TRY(ix->d_doc_meta.alloc((size_t)N, &ix->device_bytes));
+  NP_TRY(d_uoff->alloc((size_t)N + 1));
+  NP_HIP(hipMemset(d_uoff->get(), 0, 8));
+  // pass 1: list lengths
+  for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
+    const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
+    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), nullptr, nullptr, ix->d_ulen.get() + d0);
+  }
+  NP_HIP(hipGetLastError());
+  NP_TRY(choose_ublock_stride(ix));
+  const int S = ix->ublock_stride, hdr = ix->ublock_hdr, fit = S - hdr;
+  const int64_t base_b = N * (int64_t)S;   // first entry of the overflow region
+  DevPtr<int64_t> d_ovf;                    // inclusive scan of the overflow sizes
+  int64_t ovf_total = 0;
+  NP_TRY(scan_overflow(ix, fit, &d_ovf, &ovf_total));
   const int64_t total = base_b + ovf_total;
   if (total >= ((int64_t)1 << 40)) {   // candidate records carry a 40-bit list offset
     set_error("Index load failed: %lld distinct-code list entries exceed the 40-bit list offset; use more shards",
@@ -766,44 +727,34 @@ static int build_unique_codes(DeviceIndex* ix, int64_t** d_uoff_out) {
   }
   ix->n_ucodes = total;
   // pass 2: headers, then the lists (+8 entries: list readers fetch up to 8 bytes past a list's last code)
-  {
-    const size_t bytes = ((size_t)total + 8) * ix->code_bytes();
-    hipError_t e = hipMalloc(&ix->d_ucodes, bytes);
-    if (e != hipSuccess) {
-      ix->d_ucodes = nullptr;
-      set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-      return NP_ERR_OUT_OF_MEMORY;
-    }
-    ix->device_bytes += bytes;
-    NP_HIP(hipMemset(ix->d_ucodes, 0, bytes));
-  }
+  const size_t bytes = ((size_t)total + 8) * ix->code_bytes();
+  NP_TRY(ix->d_ucodes.alloc(bytes, &ix->device_bytes));
+  NP_HIP(hipMemset(ix->d_ucodes.get(), 0, bytes));
   if (N > 0)
-    ublock_layout_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets, ix->d_ulen, d_ovf, S, hdr, fit, base_b,
-                                                               ix->d_ucodes, ix->code_wide, d_uoff);
+    ublock_layout_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), ix->d_ulen.get(), d_ovf.get(), S, hdr,
+                                                               fit, base_b, ix->d_ucodes.get(), ix->code_wide, d_uoff->get());
   for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
     const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
-    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets + d0, ix->codes(), ix->d_ucodes, d_uoff + d0, ix->d_ulen + d0);
+    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), ix->d_ucodes.get(), d_uoff->get() + d0,
+                                              ix->d_ulen.get() + d0);
   }
   if (N > 0)
-    doc_meta_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets, d_uoff, ix->d_ulen, ix->d_doc_meta);
+    doc_meta_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(), ix->d_ulen.get(),
+                                                          ix->d_doc_meta.get());
   NP_HIP(hipGetLastError());
   ix->sliced_ok = false;
   if (N > 0) {
-    int* d_bad = nullptr;
-    NP_HIP(hipMalloc(&d_bad, sizeof(int)));
-    NP_HIP(hipMemset(d_bad, 0, sizeof(int)));
+    DevPtr<int> d_bad;
+    NP_TRY(d_bad.alloc(1));
+    NP_HIP(hipMemset(d_bad.get(), 0, sizeof(int)));
     const uint32_t slice_w = (uint32_t)((ix->K + 7) / 8);
-    useg_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets, d_uoff, ix->ucodes(), ix->d_ulen, slice_w,
-                                                      ix->d_useg, d_bad);
+    useg_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(), ix->ucodes(), ix->d_ulen.get(),
+                                                      slice_w, ix->d_useg.get(), d_bad.get());
     int bad = 1;
-    hipError_t e = hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    NP_HIP(e);
+    NP_HIP(hipMemcpy(&bad, d_bad.get(), sizeof(int), hipMemcpyDeviceToHost));
     ix->sliced_ok = (bad == 0);
   }
   NP_HIP(hipDeviceSynchronize());
-  guard.armed = false;
-  *d_uoff_out = d_uoff;
   return NP_OK;
 }
 
@@ -946,22 +897,244 @@ __global__ void __launch_bounds__(256) narrow_codes_kernel(const int64_t* __rest
   else static_cast<uint16_t*>(dst)[i] = (uint16_t)v;
 }
 
-static int upload_repacked(DeviceIndex* ix, const uint8_t* rows, int64_t first_tok, int64_t n_tok) {
-  const int64_t PIECE = (int64_t)1 << 20;   // tokens per staging piece
-  uint8_t* d_stage = nullptr;
-  NP_HIP(hipMalloc(&d_stage, (size_t)std::min(PIECE, n_tok) * ix->lpd));
-  hipError_t e = hipSuccess;
-  const int widen = ix->lnbits != ix->nbits;
-  for (int64_t s = 0; s < n_tok && e == hipSuccess; s += PIECE) {
-    const int64_t n = std::min(PIECE, n_tok - s);
-    e = hipMemcpy(d_stage, rows + s * ix->lpd, (size_t)n * ix->lpd, hipMemcpyHostToDevice);
-    if (e != hipSuccess) break;
-    repack_rows_kernel<<<(unsigned)((n * ix->pd + 255) / 256), 256>>>(d_stage, n, ix->lpd, ix->pd, widen,
-                                                                     ix->d_residuals + (first_tok + s) * ix->pd);
-    e = hipDeviceSynchronize();
+// ---- the steps every open shares -------------------------------------------------------------------------------------
+static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff);   // the synthetic corpus' posting lists (below)
+
+// head: once the options and the device are checked (and the device made current by the caller's guard for the whole
+// open), a fresh handle with the shard's document range of n_total documents and the tuning environment
+static int start_index(const DeviceGuard& g, const np_open_opts& o, int64_t n_total, IndexHandle* out) {
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", o.device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
   }
-  (void)hipFree(d_stage);
-  NP_HIP(e);
+  out->reset(new np_index());
+  DeviceIndex* ix = out->get();
+  ix->device = o.device;
+  ix->opts = o;
+  read_tuning_env(&ix->tune);
+  ix->N_total = n_total;
+  int64_t sb, se;
+  shard_range(n_total, o.shard_rank, o.shard_count, &sb, &se);
+  ix->doc_begin = sb;
+  ix->n_docs = se - sb;
+  return NP_OK;
+}
+
+// geometry and codec tables.  Files and caller arrays are stored in storage geometry (np_internal.h storage_dim /
+// storage_nbits); as_stored: the rows are storage rows already (the synthetic generator: dim == ldim, nbits == lnbits)
+static int set_geometry(DeviceIndex* ix, int64_t K, int dim, int nbits, bool as_stored, const float* centroids,
+                        const float* bucket_weights) {
+  ix->K = K;
+  ix->KP = (K + 63) / 64 * 64;
+  ix->code_wide = K > 65536 ? 1 : 0;   // u16 codes whenever every centroid id fits (2 B per token instead of 4)
+  ix->ldim = dim;
+  ix->lnbits = nbits;
+  ix->lpd = dim * nbits / 8;
+  ix->dim = as_stored ? dim : storage_dim(dim);
+  ix->nbits = as_stored ? nbits : storage_nbits(dim, nbits);
+  ix->pd = ix->dim * ix->nbits / 8;
+  return upload_codec(ix, centroids, bucket_weights);
+}
+
+// the codes and residuals of the shard's ix->T tokens (the caller fills them)
+static int alloc_tokens(DeviceIndex* ix) {
+  NP_TRY(ix->d_codes.alloc((size_t)std::max<int64_t>(ix->T, 1) * ix->code_bytes(), &ix->device_bytes));
+  return ix->d_residuals.alloc((size_t)ix->T * ix->pd, &ix->device_bytes);
+}
+
+// tail: the derived structures (np_internal.h) and the default workspace.  lists_from_codes: the index has no posting
+// lists of its own (the synthetic corpus); they are built here from the distinct codes (index.rs:479-499)
+static int build_derived(DeviceIndex* ix, bool lists_from_codes, OpenTrace& trace) {
+  NP_TRY(sort_tokens(ix));
+  {
+    DevPtr<int64_t> d_uoff;
+    NP_TRY(build_unique_codes(ix, &d_uoff));
+    trace.mark("distinct-code blocks");
+    if (lists_from_codes) {
+      NP_TRY(build_ivf_from_ucodes(ix, d_uoff.get()));
+      trace.mark("posting lists from the codes");
+    }
+  }
+  NP_TRY(build_ivf_split(ix, lists_from_codes));
+  trace.mark("list coverage + range table");
+  NP_TRY(build_inv_norm(ix));
+  trace.mark("inverse norms");
+  default_workspace(ix);
+  return NP_OK;
+}
+
+// ---- from host arrays / files ----------------------------------------------------------------------------------------
+// the shard's doc offsets (prefix sum of its lengths) -> HBM, T and max_doc_len; *tb = its first token in the host arrays
+static int doc_offsets_from_lengths(const HostIndex& h, DeviceIndex* ix, int64_t* tb) {
+  const int64_t hb = h.doc_begin, sb = ix->doc_begin;
+  *tb = 0;
+  for (int64_t d = hb; d < sb; ++d) *tb += h.doc_lengths[d - hb];
+  std::vector<int64_t> off((size_t)ix->n_docs + 1);
+  off[0] = 0;
+  int64_t maxlen = 0;
+  for (int64_t d = 0; d < ix->n_docs; ++d) {
+    int64_t l = h.doc_lengths[sb - hb + d];
+    if (l < 0) {
+      set_error("Index load failed: negative doc length");
+      return NP_ERR_INDEX_LOAD;
+    }
+    maxlen = std::max(maxlen, l);
+    off[d + 1] = off[d] + l;
+  }
+  ix->T = off[ix->n_docs];
+  ix->max_doc_len = maxlen;
+  NP_TRY(ix->d_doc_offsets.alloc(off.size(), &ix->device_bytes));
+  NP_HIP(hipMemcpy(ix->d_doc_offsets.get(), off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  return NP_OK;
+}
+
+// the shard's tokens [tb, tb + T) of the host chunks -> d_codes (i64 -> u16 / u32, range-checked) and d_residuals,
+// pipelined through the Uploader
+static int upload_tokens(const HostIndex& h, DeviceIndex* ix, int64_t tb) {
+  const int64_t te = tb + ix->T;
+  // device-side staging of raw pieces that need a kernel (i64 codes; residual rows in file geometry); declared before the
+  // uploader, whose destructor waits for its stream, so that they outlive the work queued on them
+  DevPtr<char> d_stage[NP_UP_SLOTS];
+  DevPtr<long long> d_bad;
+  Uploader up;
+  NP_TRY(up.init());
+  for (DevPtr<char>& st : d_stage) NP_TRY(st.alloc(NP_UP_PIECE));
+  NP_TRY(d_bad.alloc(2));
+  NP_HIP(hipMemset(d_bad.get(), 0, 16));
+  const bool repack = ix->pd != ix->lpd;
+  const int widen = ix->lnbits != ix->nbits;
+  int64_t pos = 0;  // token position of the current chunk's first token in the host arrays
+  for (const HostChunk& c : h.chunks) {
+    const int64_t a = std::max(pos, tb), b = std::min(pos + c.n_tokens, te);
+    // codes: raw i64 pieces, narrowed and range-checked on the device
+    const int64_t CP = (int64_t)(NP_UP_PIECE / 8);
+    for (int64_t t0 = a; t0 < b; t0 += CP) {
+      const int64_t n = std::min(CP, b - t0);
+      int slot;
+      NP_TRY(up.fill((const char*)c.codes + (t0 - pos) * 8, (size_t)n * 8, &slot));
+      NP_TRY(up.send(slot, (size_t)n * 8, d_stage[slot].get(), [&](hipStream_t st) -> int {
+        narrow_codes_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
+            (const int64_t*)d_stage[slot].get(), n, ix->K, ix->d_codes.get() + (t0 - tb) * (int64_t)ix->code_bytes(), ix->code_wide,
+            d_bad.get());
+        NP_HIP(hipGetLastError());
+        return (int)NP_OK;
+      }));
+    }
+    // residuals: straight into place, or through the staging area + repack (file rows -> storage rows: zero-padded,
+    // 1-bit buckets widened to 2-bit segments)
+    const int64_t RP = (int64_t)(NP_UP_PIECE / std::max(ix->lpd, 1));
+    for (int64_t t0 = a; t0 < b; t0 += RP) {
+      const int64_t n = std::min(RP, b - t0);
+      uint8_t* dst = ix->d_residuals.get() + (t0 - tb) * ix->pd;
+      int slot;
+      NP_TRY(up.fill(c.residuals + (t0 - pos) * ix->lpd, (size_t)n * ix->lpd, &slot));
+      if (!repack) {
+        NP_TRY(up.send(slot, (size_t)n * ix->lpd, dst, [](hipStream_t) -> int { return NP_OK; }));
+      } else {
+        NP_TRY(up.send(slot, (size_t)n * ix->lpd, d_stage[slot].get(), [&](hipStream_t st) -> int {
+          repack_rows_kernel<<<(unsigned)((n * ix->pd + 255) / 256), 256, 0, st>>>((const uint8_t*)d_stage[slot].get(), n, ix->lpd,
+                                                                                  ix->pd, widen, dst);
+          NP_HIP(hipGetLastError());
+          return (int)NP_OK;
+        }));
+      }
+    }
+    pos += c.n_tokens;
+  }
+  NP_TRY(up.finish());
+  if (pos < te) {
+    set_error("Index load failed: chunks hold %lld tokens, doclens need %lld", (long long)pos, (long long)te);
+    return NP_ERR_INDEX_LOAD;
+  }
+  long long bad[2] = {0, 0};
+  NP_HIP(hipMemcpy(bad, d_bad.get(), 16, hipMemcpyDeviceToHost));
+  if (bad[0] != 0) {
+    set_error("Index load failed: code %lld out of range [0,%lld)", bad[1], (long long)ix->K);
+    return NP_ERR_INDEX_LOAD;
+  }
+  return NP_OK;
+}
+
+// IVF restricted to the shard, re-based to shard-local u32 ids: two passes over the posting lists (count, then fill), the
+// centroid range split over host threads (680 M i64 entries at 10 M x 300-token documents)
+static int build_posting_lists(const HostIndex& h, DeviceIndex* ix) {
+  const int64_t sb = ix->doc_begin, se = ix->doc_begin + ix->n_docs;
+  std::vector<int64_t> ioff((size_t)ix->K + 1, 0), lstart((size_t)ix->K + 1, 0);
+  for (int64_t c = 0; c < ix->K; ++c) {
+    const int64_t l = h.ivf_lengths[c];
+    if (l < 0 || lstart[c] + l > h.ivf_size) {
+      set_error("Index load failed: ivf_lengths inconsistent with ivf.npy at centroid %lld", (long long)c);
+      return NP_ERR_INDEX_LOAD;
+    }
+    lstart[c + 1] = lstart[c] + l;
+  }
+  const int NT = (int)std::max<int64_t>(1, std::min<int64_t>(NP_UP_THREADS, ix->K / 1024));
+  const bool whole = sb == 0 && se == h.num_documents_total;
+  std::vector<int64_t> bad_id((size_t)NT, -1);
+  auto run = [&](auto&& body) {
+    std::vector<std::thread> th;
+    for (int t = 1; t < NT; ++t) th.emplace_back([&, t] { body(t); });
+    body(0);
+    for (auto& x : th) x.join();
+  };
+  auto range = [&](int t, int64_t* c0, int64_t* c1) {   // centroid ranges of about equal posting volume
+    const int64_t tot = lstart[ix->K];
+    *c0 = std::lower_bound(lstart.begin(), lstart.end(), tot * t / NT) - lstart.begin();
+    *c1 = t + 1 == NT ? ix->K : std::lower_bound(lstart.begin(), lstart.end(), tot * (t + 1) / NT) - lstart.begin();
+    *c0 = std::min<int64_t>(*c0, ix->K);
+    *c1 = std::min<int64_t>(std::max(*c1, *c0), ix->K);
+  };
+  run([&](int t) {   // pass 1: entries of every list that fall into the shard, ids range-checked
+    int64_t c0, c1;
+    range(t, &c0, &c1);
+    for (int64_t c = c0; c < c1; ++c) {
+      int64_t cnt = 0;
+      const char* src = (const char*)h.ivf + lstart[c] * 8;
+      for (int64_t i = 0, l = lstart[c + 1] - lstart[c]; i < l; ++i) {
+        int64_t id;
+        memcpy(&id, src + i * 8, 8);
+        if (id < 0 || id >= h.num_documents_total) {
+          bad_id[t] = id;
+          return;
+        }
+        cnt += whole || (id >= sb && id < se);
+      }
+      ioff[c + 1] = cnt;
+    }
+  });
+  for (int t = 0; t < NT; ++t)
+    if (bad_id[t] != -1) {
+      set_error("Index load failed: ivf doc id %lld out of range", (long long)bad_id[t]);
+      return NP_ERR_INDEX_LOAD;
+    }
+  for (int64_t c = 0; c < ix->K; ++c) ioff[c + 1] += ioff[c];
+  std::vector<uint32_t> ivf((size_t)ioff[ix->K]);
+  std::vector<int> unsorted((size_t)NT, 0);   // the crate writes ascending unique ids (index.rs:479-504); S3 relies on it only if true
+  run([&](int t) {   // pass 2
+    int64_t c0, c1;
+    range(t, &c0, &c1);
+    for (int64_t c = c0; c < c1; ++c) {
+      uint32_t* out = ivf.data() + ioff[c];
+      const char* src = (const char*)h.ivf + lstart[c] * 8;
+      int64_t prev = -1;
+      for (int64_t i = 0, l = lstart[c + 1] - lstart[c]; i < l; ++i) {
+        int64_t id;
+        memcpy(&id, src + i * 8, 8);
+        if (id <= prev) unsorted[(size_t)t] = 1;
+        prev = id;
+        if (whole || (id >= sb && id < se)) *out++ = (uint32_t)(id - sb);
+      }
+    }
+  });
+  ix->ivf_sorted = true;
+  for (int t = 0; t < NT; ++t)
+    if (unsorted[(size_t)t]) ix->ivf_sorted = false;
+  ix->ivf_size = (int64_t)ivf.size();
+  NP_TRY(ix->d_ivf.alloc(ivf.size(), &ix->device_bytes));
+  if (!ivf.empty()) NP_HIP(hipMemcpy(ix->d_ivf.get(), ivf.data(), ivf.size() * 4, hipMemcpyHostToDevice));
+  NP_TRY(ix->d_ivf_offsets.alloc(ioff.size(), &ix->device_bytes));
+  NP_HIP(hipMemcpy(ix->d_ivf_offsets.get(), ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
+  set_ivf_bound(ix, ioff.data());
   return NP_OK;
 }
 
@@ -980,240 +1153,26 @@ int build_device_index(const HostIndex& h, const np_open_opts* opts_in, DeviceIn
     return NP_ERR_INDEX_LOAD;
   }
   DeviceGuard g(o.device);
-  if (!g.ok) {
-    set_error("hipSetDevice(%d) failed", o.device);
-    return NP_ERR_DEVICE_UNAVAILABLE;
-  }
-  np_index* nix = new np_index();
-  DeviceIndex* ix = nix;
-  struct Cleanup {
-    np_index* p;
-    ~Cleanup() {
-      if (p) {
-        destroy_device_index(p);
-        delete p;
-      }
-    }
-  } cleanup{nix};
-
-  ix->device = o.device;
-  ix->opts = o;
-  read_tuning_env(&ix->tune);
-  ix->N_total = h.num_documents_total;
+  IndexHandle ix;
+  NP_TRY(start_index(g, o, h.num_documents_total, &ix));
   ix->n_emb_total = h.num_embeddings_total;
   ix->avg_doclen = h.avg_doclen;
-  ix->doc_begin = sb;
-  ix->n_docs = se - sb;
   if (ix->n_docs >= ((int64_t)1 << 31)) {
     set_error("Index load failed: a shard holds < 2^31 documents (got %lld); use more shards", (long long)ix->n_docs);
     return NP_ERR_INDEX_LOAD;
   }
-  ix->K = h.K;
-  ix->KP = (h.K + 63) / 64 * 64;
-  ix->code_wide = h.K > 65536 ? 1 : 0;   // u16 codes whenever every centroid id fits (2 B per token instead of 4)
-  ix->ldim = h.dim;
-  ix->lnbits = h.nbits;
-  ix->lpd = h.dim * h.nbits / 8;
-  ix->dim = storage_dim(h.dim);
-  ix->nbits = storage_nbits(h.dim, h.nbits);
-  ix->pd = ix->dim * ix->nbits / 8;
   OpenTrace trace;
-  NP_TRY(upload_codec(ix, h.centroids, h.bucket_weights));
+  NP_TRY(set_geometry(ix.get(), h.K, h.dim, h.nbits, false, h.centroids, h.bucket_weights));
   trace.mark("codec");
-
-  // doc offsets of the shard + its token range inside the host arrays
   int64_t tb = 0;
-  for (int64_t d = hb; d < sb; ++d) tb += h.doc_lengths[d - hb];
-  std::vector<int64_t> off((size_t)ix->n_docs + 1);
-  off[0] = 0;
-  int64_t maxlen = 0;
-  for (int64_t d = 0; d < ix->n_docs; ++d) {
-    int64_t l = h.doc_lengths[sb - hb + d];
-    if (l < 0) {
-      set_error("Index load failed: negative doc length");
-      return NP_ERR_INDEX_LOAD;
-    }
-    maxlen = std::max(maxlen, l);
-    off[d + 1] = off[d] + l;
-  }
-  ix->T = off[ix->n_docs];
-  ix->max_doc_len = maxlen;
-  const int64_t te = tb + ix->T;
-  NP_TRY(dev_alloc(&ix->d_doc_offsets, off.size(), &ix->device_bytes));
-  NP_HIP(hipMemcpy(ix->d_doc_offsets, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-
-  // codes (i64 -> u32, range-checked) and residuals, chunk by chunk
-  {
-    uint8_t* cbuf = nullptr;
-    NP_TRY(dev_alloc(&cbuf, (size_t)std::max<int64_t>(ix->T, 1) * ix->code_bytes(), &ix->device_bytes));
-    ix->d_codes = cbuf;
-  }
-  NP_TRY(dev_alloc(&ix->d_residuals, (size_t)ix->T * ix->pd, &ix->device_bytes));
-  {
-    Uploader up;
-    NP_TRY(up.init());
-    // device-side staging of raw pieces that need a kernel (i64 codes; residual rows in file geometry)
-    char* d_stage[NP_UP_SLOTS] = {};
-    long long* d_bad = nullptr;
-    struct FreeStage {
-      char** p;
-      long long** b;
-      ~FreeStage() {
-        for (int i = 0; i < NP_UP_SLOTS; ++i) (void)hipFree(p[i]);
-        (void)hipFree(*b);
-      }
-    } free_stage{d_stage, &d_bad};
-    for (int i = 0; i < NP_UP_SLOTS; ++i) NP_HIP(hipMalloc(&d_stage[i], NP_UP_PIECE));
-    NP_HIP(hipMalloc(&d_bad, 16));
-    NP_HIP(hipMemset(d_bad, 0, 16));
-    const bool repack = ix->pd != ix->lpd;
-    const int widen = ix->lnbits != ix->nbits;
-    int64_t pos = 0;  // token position of the current chunk's first token in the host arrays
-    for (const HostChunk& c : h.chunks) {
-      const int64_t a = std::max(pos, tb), b = std::min(pos + c.n_tokens, te);
-      // codes: raw i64 pieces, narrowed and range-checked on the device
-      const int64_t CP = (int64_t)(NP_UP_PIECE / 8);
-      for (int64_t t0 = a; t0 < b; t0 += CP) {
-        const int64_t n = std::min(CP, b - t0);
-        int slot;
-        NP_TRY(up.fill((const char*)c.codes + (t0 - pos) * 8, (size_t)n * 8, &slot));
-        NP_TRY(up.send(slot, (size_t)n * 8, d_stage[slot], [&](hipStream_t st) -> int {
-          narrow_codes_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
-              (const int64_t*)d_stage[slot], n, ix->K, (char*)ix->d_codes + (t0 - tb) * (int64_t)ix->code_bytes(), ix->code_wide, d_bad);
-          NP_HIP(hipGetLastError());
-          return (int)NP_OK;
-        }));
-      }
-      // residuals: straight into place, or through the staging area + repack (file rows -> storage rows: zero-padded,
-      // 1-bit buckets widened to 2-bit segments)
-      const int64_t RP = (int64_t)(NP_UP_PIECE / std::max(ix->lpd, 1));
-      for (int64_t t0 = a; t0 < b; t0 += RP) {
-        const int64_t n = std::min(RP, b - t0);
-        int slot;
-        NP_TRY(up.fill(c.residuals + (t0 - pos) * ix->lpd, (size_t)n * ix->lpd, &slot));
-        if (!repack) {
-          NP_TRY(up.send(slot, (size_t)n * ix->lpd, ix->d_residuals + (t0 - tb) * ix->pd, [](hipStream_t) -> int { return NP_OK; }));
-        } else {
-          NP_TRY(up.send(slot, (size_t)n * ix->lpd, d_stage[slot], [&](hipStream_t st) -> int {
-            repack_rows_kernel<<<(unsigned)((n * ix->pd + 255) / 256), 256, 0, st>>>((const uint8_t*)d_stage[slot], n, ix->lpd, ix->pd,
-                                                                                    widen, ix->d_residuals + (t0 - tb) * ix->pd);
-            NP_HIP(hipGetLastError());
-            return (int)NP_OK;
-          }));
-        }
-      }
-      pos += c.n_tokens;
-    }
-    NP_TRY(up.finish());
-    if (pos < te) {
-      set_error("Index load failed: chunks hold %lld tokens, doclens need %lld", (long long)pos, (long long)te);
-      return NP_ERR_INDEX_LOAD;
-    }
-    long long bad[2] = {0, 0};
-    NP_HIP(hipMemcpy(bad, d_bad, 16, hipMemcpyDeviceToHost));
-    if (bad[0] != 0) {
-      set_error("Index load failed: code %lld out of range [0,%lld)", bad[1], (long long)ix->K);
-      return NP_ERR_INDEX_LOAD;
-    }
-  }
-
+  NP_TRY(doc_offsets_from_lengths(h, ix.get(), &tb));
+  NP_TRY(alloc_tokens(ix.get()));
+  NP_TRY(upload_tokens(h, ix.get(), tb));
   trace.mark("codes + residuals -> HBM");
-  // IVF restricted to the shard, re-based to shard-local u32 ids: two passes over the posting lists (count, then fill), the
-  // centroid range split over host threads (680 M i64 entries at 10 M x 300-token documents)
-  {
-    std::vector<int64_t> ioff((size_t)ix->K + 1, 0), lstart((size_t)ix->K + 1, 0);
-    for (int64_t c = 0; c < ix->K; ++c) {
-      const int64_t l = h.ivf_lengths[c];
-      if (l < 0 || lstart[c] + l > h.ivf_size) {
-        set_error("Index load failed: ivf_lengths inconsistent with ivf.npy at centroid %lld", (long long)c);
-        return NP_ERR_INDEX_LOAD;
-      }
-      lstart[c + 1] = lstart[c] + l;
-    }
-    const int NT = (int)std::max<int64_t>(1, std::min<int64_t>(NP_UP_THREADS, ix->K / 1024));
-    const bool whole = sb == 0 && se == h.num_documents_total;
-    std::vector<int64_t> bad_id((size_t)NT, -1);
-    auto run = [&](auto&& body) {
-      std::vector<std::thread> th;
-      for (int t = 1; t < NT; ++t) th.emplace_back([&, t] { body(t); });
-      body(0);
-      for (auto& x : th) x.join();
-    };
-    auto range = [&](int t, int64_t* c0, int64_t* c1) {   // centroid ranges of about equal posting volume
-      const int64_t tot = lstart[ix->K];
-      *c0 = std::lower_bound(lstart.begin(), lstart.end(), tot * t / NT) - lstart.begin();
-      *c1 = t + 1 == NT ? ix->K : std::lower_bound(lstart.begin(), lstart.end(), tot * (t + 1) / NT) - lstart.begin();
-      *c0 = std::min<int64_t>(*c0, ix->K);
-      *c1 = std::min<int64_t>(std::max(*c1, *c0), ix->K);
-    };
-    run([&](int t) {   // pass 1: entries of every list that fall into the shard, ids range-checked
-      int64_t c0, c1;
-      range(t, &c0, &c1);
-      for (int64_t c = c0; c < c1; ++c) {
-        int64_t cnt = 0;
-        const char* src = (const char*)h.ivf + lstart[c] * 8;
-        for (int64_t i = 0, l = lstart[c + 1] - lstart[c]; i < l; ++i) {
-          int64_t id;
-          memcpy(&id, src + i * 8, 8);
-          if (id < 0 || id >= h.num_documents_total) {
-            bad_id[t] = id;
-            return;
-          }
-          cnt += whole || (id >= sb && id < se);
-        }
-        ioff[c + 1] = cnt;
-      }
-    });
-    for (int t = 0; t < NT; ++t)
-      if (bad_id[t] != -1) {
-        set_error("Index load failed: ivf doc id %lld out of range", (long long)bad_id[t]);
-        return NP_ERR_INDEX_LOAD;
-      }
-    for (int64_t c = 0; c < ix->K; ++c) ioff[c + 1] += ioff[c];
-    std::vector<uint32_t> ivf((size_t)ioff[ix->K]);
-    std::vector<int> unsorted((size_t)NT, 0);   // the crate writes ascending unique ids (index.rs:479-504); S3 relies on it only if true
-    run([&](int t) {   // pass 2
-      int64_t c0, c1;
-      range(t, &c0, &c1);
-      for (int64_t c = c0; c < c1; ++c) {
-        uint32_t* out = ivf.data() + ioff[c];
-        const char* src = (const char*)h.ivf + lstart[c] * 8;
-        int64_t prev = -1;
-        for (int64_t i = 0, l = lstart[c + 1] - lstart[c]; i < l; ++i) {
-          int64_t id;
-          memcpy(&id, src + i * 8, 8);
-          if (id <= prev) unsorted[(size_t)t] = 1;
-          prev = id;
-          if (whole || (id >= sb && id < se)) *out++ = (uint32_t)(id - sb);
-        }
-      }
-    });
-    ix->ivf_sorted = true;
-    for (int t = 0; t < NT; ++t)
-      if (unsorted[(size_t)t]) ix->ivf_sorted = false;
-    ix->ivf_size = (int64_t)ivf.size();
-    NP_TRY(dev_alloc(&ix->d_ivf, ivf.size(), &ix->device_bytes));
-    if (!ivf.empty()) NP_HIP(hipMemcpy(ix->d_ivf, ivf.data(), ivf.size() * 4, hipMemcpyHostToDevice));
-    NP_TRY(dev_alloc(&ix->d_ivf_offsets, ioff.size(), &ix->device_bytes));
-    NP_HIP(hipMemcpy(ix->d_ivf_offsets, ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
-    set_ivf_bound(ix, ioff.data());
-  }
+  NP_TRY(build_posting_lists(h, ix.get()));
   trace.mark("posting lists");
-  NP_TRY(sort_tokens(ix));
-  {
-    int64_t* d_uoff = nullptr;
-    const int rc = build_unique_codes(ix, &d_uoff);
-    (void)hipFree(d_uoff);
-    NP_TRY(rc);
-  }
-  trace.mark("distinct-code blocks");
-  NP_TRY(build_ivf_split(ix, false));
-  trace.mark("list coverage + range table");
-  NP_TRY(build_inv_norm(ix));
-  trace.mark("inverse norms");
-  default_workspace(ix);
-  cleanup.p = nullptr;
-  *out = ix;
+  NP_TRY(build_derived(ix.get(), false, trace));
+  *out = ix.release();
   return NP_OK;
 }
 
@@ -1332,30 +1291,21 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
   const int64_t K = ix->K, N = ix->n_docs;
   std::vector<int64_t> ioff((size_t)K + 1, 0);
   ix->ivf_size = 0;
-  int64_t* d_upfx = nullptr;
-  uint64_t *d_k1 = nullptr, *d_k2 = nullptr;
-  int64_t *d_start = nullptr, *d_base = nullptr;
-  void* d_temp = nullptr;
-  struct Free {
-    void** p[6];
-    ~Free() {
-      for (void** q : p) (void)hipFree(*q);
-    }
-  } fr{{(void**)&d_upfx, (void**)&d_k1, (void**)&d_k2, (void**)&d_start, (void**)&d_base, &d_temp}};
+  DevPtr<int64_t> d_upfx, d_start, d_base;
+  DevPtr<uint64_t> d_k1, d_k2;
+  DevPtr<uint8_t> d_temp;
   std::vector<int64_t> upfx((size_t)N);
   if (N > 0) {
-    NP_TRY(dev_alloc(&d_upfx, (size_t)N, nullptr));
-    NP_TRY(dev_alloc(&d_start, (size_t)N, nullptr));   // scan input (freed below; d_start is re-allocated per code later)
-    ulen_to_i64_kernel<<<(unsigned)((N + 255) / 256), 256>>>(ix->d_ulen, N, d_start);
+    NP_TRY(d_upfx.alloc((size_t)N));
+    NP_TRY(d_start.alloc((size_t)N));   // scan input (released below; d_start is re-allocated per code later)
+    ulen_to_i64_kernel<<<(unsigned)((N + 255) / 256), 256>>>(ix->d_ulen.get(), N, d_start.get());
     size_t tb = 0;
-    NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_start, d_upfx, (int)N));
-    NP_HIP(hipMalloc(&d_temp, std::max<size_t>(tb, 16)));
-    NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_start, d_upfx, (int)N));
-    NP_HIP(hipMemcpy(upfx.data(), d_upfx, (size_t)N * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(d_temp);
-    d_temp = nullptr;
-    (void)hipFree(d_start);
-    d_start = nullptr;
+    NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_start.get(), d_upfx.get(), (int)N));
+    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+    NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, d_start.get(), d_upfx.get(), (int)N));
+    NP_HIP(hipMemcpy(upfx.data(), d_upfx.get(), (size_t)N * 8, hipMemcpyDeviceToHost));
+    d_temp.reset();
+    d_start.reset();
   }
   const int64_t total = N > 0 ? upfx[(size_t)N - 1] : 0;
   // document ranges of at most NP_IVF_SEG pairs (a single document never exceeds 65535 distinct codes... any size fits)
@@ -1378,28 +1328,28 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
     return NP_ERR_INDEX_LOAD;
   }
   ix->ivf_size = total;
-  NP_TRY(dev_alloc(&ix->d_ivf, (size_t)total, &ix->device_bytes));
+  NP_TRY(ix->d_ivf.alloc((size_t)total, &ix->device_bytes));
   if (total > 0) {
     int kbits = 1;
     while (((int64_t)1 << kbits) < K) ++kbits;
-    NP_TRY(dev_alloc(&d_k1, (size_t)max_pairs, nullptr));
-    NP_TRY(dev_alloc(&d_k2, (size_t)max_pairs, nullptr));
-    NP_TRY(dev_alloc(&d_start, (size_t)K + 1, nullptr));
-    NP_TRY(dev_alloc(&d_base, (size_t)K + 1, nullptr));
+    NP_TRY(d_k1.alloc((size_t)max_pairs));
+    NP_TRY(d_k2.alloc((size_t)max_pairs));
+    NP_TRY(d_start.alloc((size_t)K + 1));
+    NP_TRY(d_base.alloc((size_t)K + 1));
     size_t tb = 0;
-    NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k1, d_k2, (int)max_pairs, 0, 32 + kbits));
-    NP_HIP(hipMalloc(&d_temp, std::max<size_t>(tb, 16)));
+    NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k1.get(), d_k2.get(), (int)max_pairs, 0, 32 + kbits));
+    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
     std::vector<std::vector<int64_t>> seg_start((size_t)nseg, std::vector<int64_t>((size_t)K + 1));
     auto sort_segment = [&](int s, int64_t* n_out) -> int {
       const int64_t d0 = seg_d0[s], d1 = seg_d0[s + 1];
       const int64_t base = d0 > 0 ? upfx[(size_t)d0 - 1] : 0, n = upfx[(size_t)d1 - 1] - base;
       *n_out = n;
       if (n == 0) return NP_OK;
-      ivf_emit_pairs_kernel<<<(unsigned)((d1 - d0 + 3) / 4), 256>>>(d0, d1, d_uoff, ix->ucodes(), ix->d_ulen,
-                                                                   d_upfx, base, d_k1);
+      ivf_emit_pairs_kernel<<<(unsigned)((d1 - d0 + 3) / 4), 256>>>(d0, d1, d_uoff, ix->ucodes(), ix->d_ulen.get(),
+                                                                   d_upfx.get(), base, d_k1.get());
       size_t tbs = tb;
-      NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp, tbs, d_k1, d_k2, (int)n, 0, 32 + kbits));
-      ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2, n, K, d_start);
+      NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tbs, d_k1.get(), d_k2.get(), (int)n, 0, 32 + kbits));
+      ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2.get(), n, K, d_start.get());
       NP_HIP(hipGetLastError());
       return NP_OK;
     };
@@ -1408,7 +1358,7 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
       int64_t n = 0;
       NP_TRY(sort_segment(s, &n));
       if (n == 0) std::fill(seg_start[(size_t)s].begin(), seg_start[(size_t)s].end(), 0);
-      else NP_HIP(hipMemcpy(seg_start[(size_t)s].data(), d_start, ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
+      else NP_HIP(hipMemcpy(seg_start[(size_t)s].data(), d_start.get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
     }
     for (int64_t c = 0; c < K; ++c) {
       int64_t len = 0;
@@ -1422,19 +1372,50 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
       if (nseg > 1) NP_TRY(sort_segment(s, &n));
       else n = total;
       if (n > 0) {
-        NP_HIP(hipMemcpy(d_base, base_c.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice));
-        ivf_scatter_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d_k2, n, d_start, d_base, ix->d_ivf);
+        NP_HIP(hipMemcpy(d_base.get(), base_c.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice));
+        ivf_scatter_kernel<<<(unsigned)((n + 255) / 256), 256>>>(d_k2.get(), n, d_start.get(), d_base.get(), ix->d_ivf.get());
         NP_HIP(hipGetLastError());
         NP_HIP(hipDeviceSynchronize());
       }
       for (int64_t c = 0; c < K; ++c) base_c[(size_t)c] += seg_start[(size_t)s][(size_t)c + 1] - seg_start[(size_t)s][(size_t)c];
     }
   }
-  NP_TRY(dev_alloc(&ix->d_ivf_offsets, ioff.size(), &ix->device_bytes));
-  NP_HIP(hipMemcpy(ix->d_ivf_offsets, ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
+  NP_TRY(ix->d_ivf_offsets.alloc(ioff.size(), &ix->device_bytes));
+  NP_HIP(hipMemcpy(ix->d_ivf_offsets.get(), ioff.data(), ioff.size() * 8, hipMemcpyHostToDevice));
   set_ivf_bound(ix, ioff.data());
   NP_HIP(hipDeviceSynchronize());
   ix->ivf_sorted = true;   // (code, document) pairs radix-sorted, ranges ascending: every list ascends
+  return NP_OK;
+}
+
+// doc lengths -> d_doc_offsets (an inclusive scan written one entry in)
+static int synth_doc_offsets(const np_synth_spec* s, const SynthP& p, DeviceIndex* ix) {
+  NP_TRY(ix->d_doc_offsets.alloc((size_t)ix->n_docs + 1, &ix->device_bytes));
+  NP_HIP(hipMemset(ix->d_doc_offsets.get(), 0, sizeof(int64_t)));
+  if (ix->n_docs == 0) return NP_OK;
+  DevPtr<int64_t> d_lens;
+  DevPtr<int32_t> d_tab;
+  DevPtr<uint8_t> d_temp;
+  NP_TRY(d_lens.alloc((size_t)ix->n_docs));
+  if (s->len_table_size > 0) {
+    NP_TRY(d_tab.alloc((size_t)s->len_table_size));
+    const hipError_t e = hipMemcpy(d_tab.get(), s->len_table, (size_t)s->len_table_size * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      set_error("synth: length table upload failed: %s", hipGetErrorString(e));
+      return NP_ERR_DEVICE_UNAVAILABLE;
+    }
+  }
+  synth_lens_kernel<<<(unsigned)((ix->n_docs + 255) / 256), 256>>>(p, d_tab.get(), s->len_table_size, d_lens.get());
+  int64_t* d_incl = ix->d_doc_offsets.get() + 1;
+  size_t tb = 0;
+  hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_lens.get(), d_incl, (int)ix->n_docs);
+  if (e == hipSuccess) NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, d_lens.get(), d_incl, (int)ix->n_docs);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    set_error("synth: doc offset scan failed: %s", hipGetErrorString(e));
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
   return NP_OK;
 }
 
@@ -1462,52 +1443,24 @@ static int synth_build(const np_synth_spec* s, const np_open_opts* opts_in, Devi
     table_max = std::max(table_max, s->len_table[i]);
   }
   DeviceGuard g(o.device);
-  if (!g.ok) {
-    set_error("hipSetDevice(%d) failed", o.device);
-    return NP_ERR_DEVICE_UNAVAILABLE;
-  }
-  np_index* nix = new np_index();
-  DeviceIndex* ix = nix;
-  void* d_temp = nullptr;
-  struct Cleanup {
-    np_index* p;
-    void** c;
-    ~Cleanup() {
-      (void)hipFree(*c);
-      if (p) {
-        destroy_device_index(p);
-        delete p;
-      }
-    }
-  } cleanup{nix, &d_temp};
-
-  int64_t sb, se;
-  shard_range(s->num_docs, o.shard_rank, o.shard_count, &sb, &se);
-  ix->device = o.device;
-  ix->opts = o;
-  read_tuning_env(&ix->tune);
-  ix->N_total = s->num_docs;
-  ix->doc_begin = sb;
-  ix->n_docs = se - sb;
+  IndexHandle ix;
+  NP_TRY(start_index(g, o, s->num_docs, &ix));
   if (ix->n_docs >= ((int64_t)1 << 31)) {
     set_error("synth: a shard holds < 2^31 documents (got %lld); use more shards", (long long)ix->n_docs);
     return NP_ERR_INVALID_ARGUMENT;
   }
-  ix->K = s->num_centroids;
-  ix->KP = (ix->K + 63) / 64 * 64;
-  ix->code_wide = ix->K > 65536 ? 1 : 0;
-  ix->dim = ix->ldim = s->dim;        // the generator writes storage geometry directly (spec checked above)
-  ix->nbits = ix->lnbits = s->nbits;
-  ix->pd = ix->lpd = s->dim * s->nbits / 8;
   ix->max_doc_len = s->len_table_size > 0 ? table_max : s->doc_len_max;
-  NP_TRY(upload_codec(ix, s->centroids, s->bucket_weights));
+  OpenTrace trace;
+  // the generator writes storage geometry directly (spec checked above)
+  NP_TRY(set_geometry(ix.get(), s->num_centroids, s->dim, s->nbits, true, s->centroids, s->bucket_weights));
+  trace.mark("codec");
 
   SynthP p;
   p.b_len = mix64(s->seed + S_LEN);
   p.b_topic = mix64(s->seed + S_TOPIC);
   p.b_tok = mix64(s->seed + S_TOK);
   p.b_res = mix64(s->seed + S_RES);
-  p.doc_begin = sb;
+  p.doc_begin = ix->doc_begin;
   p.n_docs = ix->n_docs;
   p.K = (uint32_t)ix->K;
   p.len_min = s->doc_len_min;
@@ -1516,56 +1469,19 @@ static int synth_build(const np_synth_spec* s, const np_open_opts* opts_in, Devi
   p.rand256 = s->rand256;
   p.pd = ix->pd;
   p.nw = (ix->pd + 7) / 8;
-
-  // doc lengths -> offsets (inclusive scan shifted by one)
-  NP_TRY(dev_alloc(&ix->d_doc_offsets, (size_t)ix->n_docs + 1, &ix->device_bytes));
-  NP_HIP(hipMemset(ix->d_doc_offsets, 0, sizeof(int64_t)));
-  if (ix->n_docs > 0) {
-    int64_t* d_lens = nullptr;
-    int32_t* d_tab = nullptr;
-    NP_TRY(dev_alloc(&d_lens, (size_t)ix->n_docs, nullptr));
-    if (s->len_table_size > 0) {
-      hipError_t e0 = hipMalloc(&d_tab, (size_t)s->len_table_size * 4);
-      if (e0 == hipSuccess) e0 = hipMemcpy(d_tab, s->len_table, (size_t)s->len_table_size * 4, hipMemcpyHostToDevice);
-      if (e0 != hipSuccess) {
-        (void)hipFree(d_lens);
-        (void)hipFree(d_tab);
-        set_error("synth: length table upload failed: %s", hipGetErrorString(e0));
-        return NP_ERR_DEVICE_UNAVAILABLE;
-      }
-    }
-    synth_lens_kernel<<<(unsigned)((ix->n_docs + 255) / 256), 256>>>(p, d_tab, s->len_table_size, d_lens);
-    size_t tb = 0;
-    hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_lens, ix->d_doc_offsets + 1, (int)ix->n_docs);
-    if (e == hipSuccess) e = hipMalloc(&d_temp, std::max<size_t>(tb, 16));
-    if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_lens, ix->d_doc_offsets + 1, (int)ix->n_docs);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d_lens);
-    (void)hipFree(d_tab);
-    (void)hipFree(d_temp);
-    d_temp = nullptr;
-    if (e != hipSuccess) {
-      set_error("synth: doc offset scan failed: %s", hipGetErrorString(e));
-      return NP_ERR_DEVICE_UNAVAILABLE;
-    }
-  }
-  NP_HIP(hipMemcpy(&ix->T, ix->d_doc_offsets + ix->n_docs, sizeof(int64_t), hipMemcpyDeviceToHost));
+  NP_TRY(synth_doc_offsets(s, p, ix.get()));
+  NP_HIP(hipMemcpy(&ix->T, ix->d_doc_offsets.get() + ix->n_docs, sizeof(int64_t), hipMemcpyDeviceToHost));
   if (ix->T >= ((int64_t)1 << 40)) {   // candidate records carry a 40-bit token offset
     set_error("synth: shard holds %lld tokens; a shard addresses < 2^40 tokens (use more shards)", (long long)ix->T);
     return NP_ERR_INVALID_ARGUMENT;
   }
-  ix->n_emb_total = 0;  // filled below for unsharded corpora; sharded: avg-based estimate
-  {
-    uint8_t* cbuf = nullptr;
-    NP_TRY(dev_alloc(&cbuf, (size_t)std::max<int64_t>(ix->T, 1) * ix->code_bytes(), &ix->device_bytes));
-    ix->d_codes = cbuf;
-  }
-  NP_TRY(dev_alloc(&ix->d_residuals, (size_t)ix->T * ix->pd, &ix->device_bytes));
+  NP_TRY(alloc_tokens(ix.get()));
   if (ix->n_docs > 0)
-    synth_tokens_kernel<<<(unsigned)((ix->n_docs + 3) / 4), 256>>>(p, ix->d_doc_offsets, ix->d_codes, ix->code_wide,
-                                                                   ix->d_residuals);
+    synth_tokens_kernel<<<(unsigned)((ix->n_docs + 3) / 4), 256>>>(p, ix->d_doc_offsets.get(), ix->d_codes.get(), ix->code_wide,
+                                                                   ix->d_residuals.get());
   NP_HIP(hipGetLastError());
   NP_HIP(hipDeviceSynchronize());
+  trace.mark("generated tokens");
 
   // whole-corpus token count: exact when unsharded or fixed-length, else extrapolated
   const bool fixed_len = s->len_table_size == 0 && s->doc_len_min == s->doc_len_max;
@@ -1574,19 +1490,8 @@ static int synth_build(const np_synth_spec* s, const np_open_opts* opts_in, Devi
   else
     ix->n_emb_total = ix->n_docs > 0 ? (int64_t)((double)ix->T / (double)ix->n_docs * (double)s->num_docs) : 0;
   ix->avg_doclen = s->num_docs > 0 ? (double)ix->n_emb_total / (double)s->num_docs : 0.0;
-  NP_TRY(sort_tokens(ix));
-  {
-    int64_t* d_uoff = nullptr;
-    int rc = build_unique_codes(ix, &d_uoff);
-    if (rc == NP_OK) rc = build_ivf_from_ucodes(ix, d_uoff);   // index.rs:479-499
-    (void)hipFree(d_uoff);
-    NP_TRY(rc);
-  }
-  NP_TRY(build_ivf_split(ix, true));
-  NP_TRY(build_inv_norm(ix));
-  default_workspace(ix);
-  cleanup.p = nullptr;
-  *out = ix;
+  NP_TRY(build_derived(ix.get(), true, trace));
+  *out = ix.release();
   return NP_OK;
 }
 
@@ -1731,7 +1636,7 @@ int np_hip_index_export(const np_index* ix, int64_t* doc_lengths, int64_t* codes
   DeviceGuard g(ix->device);
   if (doc_lengths) {
     std::vector<int64_t> off((size_t)ix->n_docs + 1);
-    NP_HIP(hipMemcpy(off.data(), ix->d_doc_offsets, off.size() * 8, hipMemcpyDeviceToHost));
+    NP_HIP(hipMemcpy(off.data(), ix->d_doc_offsets.get(), off.size() * 8, hipMemcpyDeviceToHost));
     for (int64_t d = 0; d < ix->n_docs; ++d) doc_lengths[d] = off[d + 1] - off[d];
   }
   // codes / residuals are kept in per-document code order (np_internal.h): put the on-disk order back for the copy
@@ -1753,43 +1658,39 @@ int np_hip_index_export(const np_index* ix, int64_t* doc_lengths, int64_t* codes
     for (int64_t s = 0; s < ix->T; s += PIECE) {
       int64_t n = std::min(PIECE, ix->T - s);
       if (ix->code_wide) {
-        NP_HIP(hipMemcpy(tmp.data(), (const uint32_t*)ix->d_codes + s, (size_t)n * 4, hipMemcpyDeviceToHost));
+        NP_HIP(hipMemcpy(tmp.data(), (const uint32_t*)ix->d_codes.get() + s, (size_t)n * 4, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) codes[s + i] = (int64_t)tmp[i];
       } else {
         uint16_t* t16 = reinterpret_cast<uint16_t*>(tmp.data());
-        NP_HIP(hipMemcpy(t16, (const uint16_t*)ix->d_codes + s, (size_t)n * 2, hipMemcpyDeviceToHost));
+        NP_HIP(hipMemcpy(t16, (const uint16_t*)ix->d_codes.get() + s, (size_t)n * 2, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < n; ++i) codes[s + i] = (int64_t)t16[i];
       }
     }
   }
   if (residuals && ix->T > 0 && ix->pd == ix->lpd) {
-    NP_HIP(hipMemcpy(residuals, ix->d_residuals, (size_t)ix->T * ix->pd, hipMemcpyDeviceToHost));
+    NP_HIP(hipMemcpy(residuals, ix->d_residuals.get(), (size_t)ix->T * ix->pd, hipMemcpyDeviceToHost));
   } else if (residuals && ix->T > 0) {   // storage rows -> file rows
-    uint8_t* d_rows = nullptr;
-    NP_HIP(hipMalloc(&d_rows, (size_t)ix->T * ix->lpd));
-    unpack_rows_kernel<<<(unsigned)((ix->T * ix->lpd + 255) / 256), 256>>>(ix->d_residuals, ix->T, ix->lpd, ix->pd,
-                                                                          ix->lnbits != ix->nbits, d_rows);
-    hipError_t e = hipMemcpy(residuals, d_rows, (size_t)ix->T * ix->lpd, hipMemcpyDeviceToHost);
-    (void)hipFree(d_rows);
-    NP_HIP(e);
+    DevPtr<uint8_t> d_rows;
+    NP_TRY(d_rows.alloc((size_t)ix->T * ix->lpd));
+    unpack_rows_kernel<<<(unsigned)((ix->T * ix->lpd + 255) / 256), 256>>>(ix->d_residuals.get(), ix->T, ix->lpd, ix->pd,
+                                                                          ix->lnbits != ix->nbits, d_rows.get());
+    NP_HIP(hipMemcpy(residuals, d_rows.get(), (size_t)ix->T * ix->lpd, hipMemcpyDeviceToHost));
   }
   if (ivf && ix->ivf_size > 0) {
     std::vector<uint32_t> tmp((size_t)ix->ivf_size);
-    NP_HIP(hipMemcpy(tmp.data(), ix->d_ivf, tmp.size() * 4, hipMemcpyDeviceToHost));
+    NP_HIP(hipMemcpy(tmp.data(), ix->d_ivf.get(), tmp.size() * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < ix->ivf_size; ++i) ivf[i] = (int64_t)tmp[i] + ix->doc_begin;
   }
   if (ivf_lengths) {
     std::vector<int64_t> off((size_t)ix->K + 1);
-    NP_HIP(hipMemcpy(off.data(), ix->d_ivf_offsets, off.size() * 8, hipMemcpyDeviceToHost));
+    NP_HIP(hipMemcpy(off.data(), ix->d_ivf_offsets.get(), off.size() * 8, hipMemcpyDeviceToHost));
     for (int64_t c = 0; c < ix->K; ++c) ivf_lengths[c] = (int32_t)(off[c + 1] - off[c]);
   }
   return NP_OK;
 }
 
 void np_hip_index_close(np_index* index) {
-  if (!index) return;
   destroy_device_index(index);
-  delete index;
 }
 
 int np_hip_index_info(const np_index* ix, np_info* out) {

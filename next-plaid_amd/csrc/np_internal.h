@@ -20,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <condition_variable>
@@ -124,6 +125,45 @@ int encode_with_codec(int device, const float* C, int64_t K, int dim, int nbits,
 float quantile_of_sorted(const std::vector<float>& v, double q);   // utils.rs:94-149
 
 // ---- device buffers ------------------------------------------------------------------------
+// One device allocation and its only owner: move-only, freed on destruction or reset().  alloc(n) takes max(n, 1)
+// elements (an empty array still has an address) and adds the bytes to *acct when given (DeviceIndex::device_bytes).
+// hipFree acts on the current device: the arrays of a DeviceIndex go under destroy_device_index's DeviceGuard.
+template <class T>
+class DevPtr {
+ public:
+  DevPtr() = default;
+  DevPtr(DevPtr&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevPtr& operator=(DevPtr&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_;
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  ~DevPtr() { reset(); }
+  int alloc(size_t n, size_t* acct = nullptr) {
+    reset();
+    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+    hipError_t e = hipMalloc((void**)&p_, bytes);
+    if (e != hipSuccess) {
+      p_ = nullptr;
+      set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+      return NP_ERR_OUT_OF_MEMORY;
+    }
+    if (acct) *acct += bytes;
+    return NP_OK;
+  }
+  T* get() const { return p_; }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+
+ private:
+  T* p_ = nullptr;
+};
+
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
@@ -215,17 +255,18 @@ struct DeviceIndex {
   float pad_ss = 0.f;                     // (dim - ldim) * wlut[0]^2, see ExactP::pad_ss
   int64_t T = 0;
   int64_t max_doc_len = 0;
-  float* d_centroids = nullptr;
-  float* d_wlut = nullptr;
-  void* d_codes = nullptr;        // [T] u16 when code_wide == 0 (K <= 65536), else u32
+  // device arrays: owned, freed when destroy_device_index deletes the handle
+  DevPtr<float> d_centroids;
+  DevPtr<float> d_wlut;
+  DevPtr<uint8_t> d_codes;        // [T] u16 when code_wide == 0 (K <= 65536), else u32
   int code_wide = 0;
-  void* d_ucodes = nullptr;       // [n_ucodes] dense per-document sorted distinct-code lists, same element type (derived)
+  DevPtr<uint8_t> d_ucodes;       // [n_ucodes] dense per-document sorted distinct-code lists, same element type (derived)
   int64_t n_ucodes = 0;           // entries of d_ucodes without the tail padding
   int ublock_stride = 0;          // entries per document block of d_ucodes (header + codes; lists that do not fit: overflow region)
   int ublock_hdr = 0;             // entries of a block's 16-byte header {#distinct, doc length, overflow index, 0}
-  int32_t* d_ulen = nullptr;      // [n_docs] number of distinct codes per document (derived)
-  uint4* d_useg = nullptr;        // [n_docs] 8 x u16: distinct codes below each eighth of the centroid range (derived)
-  uint4* d_doc_meta = nullptr;    // [n_docs] the 16-B candidate record of every document {doc, n distinct codes, offset of its
+  DevPtr<int32_t> d_ulen;         // [n_docs] number of distinct codes per document (derived)
+  DevPtr<uint4> d_useg;           // [n_docs] 8 x u16: distinct codes below each eighth of the centroid range (derived)
+  DevPtr<uint4> d_doc_meta;       // [n_docs] the 16-B candidate record of every document {doc, n distinct codes, offset of its
                                   // distinct-code list in d_ucodes: low 32 bits, bits 32..39 | doc length << 8} (derived)
   float ulen_mean = 0.f;          // mean number of distinct codes per document (derived; scales the exact level's floor)
   bool sliced_ok = false;         // every document's distinct-code list is sorted and < 65536 long
@@ -233,16 +274,16 @@ struct DeviceIndex {
   bool filter_ok = false;         // every centroid value is finite: the S4 upper-bound filter may run
   bool s6_fast_ok = false;        // centroids and bucket weights finite and < 1e6 in magnitude: with an unflagged query no S6
                                   // product can overflow, so the QC-reuse kernel drops its non-finite guard
-  float* d_inv_norm = nullptr;    // [T] 1 / max(||centroid[code] + residual||, 1e-12) per token (derived)
-  uint16_t* d_tok_pos = nullptr;  // [T] original position (inside its document) of the token stored here (derived; see below)
+  DevPtr<float> d_inv_norm;       // [T] 1 / max(||centroid[code] + residual||, 1e-12) per token (derived)
+  DevPtr<uint16_t> d_tok_pos;     // [T] original position (inside its document) of the token stored here (derived; see below)
   bool tok_sorted = false;        // codes / residuals / inv_norm hold every document's tokens ORDERED BY CODE
-  uint8_t* d_residuals = nullptr;
-  int64_t* d_doc_offsets = nullptr;
-  uint32_t* d_ivf = nullptr;
-  int64_t* d_ivf_offsets = nullptr;
+  DevPtr<uint8_t> d_residuals;
+  DevPtr<int64_t> d_doc_offsets;
+  DevPtr<uint32_t> d_ivf;
+  DevPtr<int64_t> d_ivf_offsets;
   int64_t ivf_size = 0;
   bool ivf_sorted = false;        // every posting list ascends (what the crate writes): S3 may bisect a list for a document range
-  uint32_t* d_ivf_split = nullptr;   // [K][n_ranges + 1] (derived, ascending lists only): entries of list c with id < 32768 r -- the
+  DevPtr<uint32_t> d_ivf_split;   // [K][n_ranges + 1] (derived, ascending lists only): entries of list c with id < 32768 r -- the
                                   // zeroth filter level's blocks read their range's part of a posting list without a bisection
   int n_ranges = 0;               // ceil(n_docs / 32768)
   // ivf_top_prefix[i] = entries of the i longest posting lists together (host side, i <= K): a query that probes c cells cannot
@@ -263,8 +304,8 @@ struct DeviceIndex {
   mutable std::atomic<int> gain_skip{0};
   mutable std::atomic<int> gain_run{0};    // 1: the last report of these parameters said the level pays (no guard between batches)
   mutable std::atomic<uint64_t> gain_key{0};
-  CodeArr codes() const { return CodeArr{d_codes, code_wide}; }
-  CodeArr ucodes() const { return CodeArr{d_ucodes, code_wide}; }
+  CodeArr codes() const { return CodeArr{d_codes.get(), code_wide}; }
+  CodeArr ucodes() const { return CodeArr{d_ucodes.get(), code_wide}; }
   size_t code_bytes() const { return code_wide ? 4 : 2; }
   // context pool
   mutable std::mutex mu;
@@ -283,7 +324,7 @@ static inline int storage_nbits(int dim, int nbits) { return (nbits == 1 && dim 
 
 // np_index.hip
 int build_device_index(const HostIndex& h, const np_open_opts* opts, DeviceIndex** out);
-void destroy_device_index(DeviceIndex* ix);
+void destroy_device_index(np_index* ix);   // the contexts, then the handle and its arrays, on the index's device
 int normalise_opts(const np_open_opts* in, np_open_opts* out);
 void read_tuning_env(Tuning* t);
 bool set_tuning(Tuning* t, const std::string& name, int value);   // shared clamp table (environment + np_hip_index_tune)

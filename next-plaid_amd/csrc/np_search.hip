@@ -211,7 +211,7 @@ static int64_t per_query_bytes(const DeviceIndex* ix, int LQP, int n_sel, int to
   return KP * LQP * 6                      // QCT (f32) + QCU (u8, rows padded to a power of two)
          + KP + 1024                       // per-centroid maxima of the u8 table + their histogram (hot level)
          + KP * 6 + G * 4 + NP_UB_BINS * 8   // zeroth level: gains of the probed cells, its own deeper cell list, two histograms,
-         + (ix->d_ivf_split ? (int64_t)ix->n_ranges * NP_GAIN_RANGE : 0)   // ... the documents' level bytes
+         + (ix->d_ivf_split.get() ? (int64_t)ix->n_ranges * NP_GAIN_RANGE : 0)   // ... the documents' level bytes
          + NP_UB_BINS * 8
          + G * LQP * 4 + G * 4             // gmax, cellbits
          + KP * 8                          // cells_tmp, cells
@@ -289,10 +289,10 @@ static void launch_gemm(hipStream_t st, const DeviceIndex* ix, const float* Qt, 
   with_dim(ix->dim, [&](auto DIM) {
     if (ix->tune.gemm_cpw == 2) {
       const unsigned blocks = (unsigned)((ix->KP / 64 + 3) / 4);
-      qc_gemm_kernel<DIM, 2><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
+      qc_gemm_kernel<DIM, 2><<<blocks, 256, 0, st>>>(ix->d_centroids.get(), ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
     } else {
       const unsigned blocks = (unsigned)((ix->KP / 32 + 3) / 4);
-      qc_gemm_kernel<DIM, 1><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
+      qc_gemm_kernel<DIM, 1><<<blocks, 256, 0, st>>>(ix->d_centroids.get(), ix->K, ix->KP, Qt, B, LQP, QCT, gmax, QCU, RB, qinv, qoff);
     }
   });
 }
@@ -386,17 +386,17 @@ static void launch_approx(hipStream_t st, const DeviceIndex* ix, Workspace& w, c
   with_int<8, 16, 32, 64>(lpr, [&](auto LPR) {
     if (stream && per_xcd) {
       approx_stream_kernel<LPR><<<8 * nbx, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(),
-                                                         ix->n_ucodes, ix->d_useg, approx, t.s4_mode - 5, slice_w, ctr);
+                                                         ix->n_ucodes, ix->d_useg.get(), approx, t.s4_mode - 5, slice_w, ctr);
     } else if (t.s4_mode > 0 && per_xcd) {
       if constexpr (LPR == 8) {
         if (t.s4_swz) {   // ds_swizzle code broadcast: 8 lanes per row only
           approx_xcd_kernel<8, true><<<8 * nbx, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(),
-                                                              ix->n_ucodes, ix->d_useg, approx, s4_p - 1, ctr);
+                                                              ix->n_ucodes, ix->d_useg.get(), approx, s4_p - 1, ctr);
           return;
         }
       }
       approx_xcd_kernel<LPR, false><<<8 * nbx, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(),
-                                                             ix->n_ucodes, ix->d_useg, approx, s4_p - 1, ctr);
+                                                             ix->n_ucodes, ix->d_useg.get(), approx, s4_p - 1, ctr);
     } else {
       approx_kernel<LPR><<<768, 256, 0, st>>>(QCT, KP, LQP, d_qoff, meta, n, rp, round, max_rounds, ix->ucodes(), approx, ctr);
     }
@@ -409,7 +409,7 @@ static void launch_matvec(hipStream_t st, const DeviceIndex* ix, Workspace& w, c
   const dim3 grid(512 / NP_MV_DOCS, (unsigned)B);      // a wave per NP_MV_DOCS documents: one pass over ~n_sel listed documents
   with_dim(ix->dim, [&](auto DIM) {
     with_bool(ix->ldim & 7, [&](auto TAIL) {
-      approx_matvec_kernel<DIM, TAIL><<<grid, 256, 0, st>>>(d_q, d_qoff, ix->d_centroids, meta, n, rp, round, ix->ucodes(),
+      approx_matvec_kernel<DIM, TAIL><<<grid, 256, 0, st>>>(d_q, d_qoff, ix->d_centroids.get(), meta, n, rp, round, ix->ucodes(),
                                                             w.approx.as<float>(), ix->ldim);
     });
   });
@@ -598,7 +598,7 @@ static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff
   // before any list block is read.  Only where no centroid_score_threshold is set (the cells a threshold removes would lift
   // the bound's floor above the cut: tools/sim/s3_gain_sim.py), on ascending posting lists (range table built at open), with
   // the bit-plane first level behind it (it takes the candidate ids in any order) and without a subset.
-  p.gain_possible = p.two_level && p.use_planes && ix->d_ivf_split != nullptr && ix->tune.s3_gain &&
+  p.gain_possible = p.two_level && p.use_planes && ix->d_ivf_split.get() != nullptr && ix->tune.s3_gain &&
                     subset_len < 0 && ix->n_docs > 0 && cs->n_sel > 0 && B > 0 &&
                     (int64_t)std::max(prm.n_ivf_probe, 32) * maxLq <= 16384;   // probed cells per query: the scaled gains of all
                                                                                // of them must fit a 15-bit accumulator (gain_prep_kernel)
@@ -863,7 +863,7 @@ void Pass::s1() const {
   if (p.s1_split) {
     const unsigned blocks = (unsigned)((ix->KP / 32 + 3) / 4);
     with_dim(ix->dim, [&](auto DIM) {
-      qc_gemm_b3_kernel<DIM><<<blocks, 256, 0, st>>>(ix->d_centroids, ix->K, ix->KP, w.Qb.as<__bf16>(), w.Qbl.as<__bf16>(), B,
+      qc_gemm_b3_kernel<DIM><<<blocks, 256, 0, st>>>(ix->d_centroids.get(), ix->K, ix->KP, w.Qb.as<__bf16>(), w.Qbl.as<__bf16>(), B,
                                                      p.LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>(), qcu, p.RB,
                                                      w.qinv.as<float>(), d_qoff);
     });
@@ -888,7 +888,7 @@ int Pass::subset() const {
   // (np_hip_subset_eligible + one small all-gather) and hands the global one in
   const bool local_elig = p.use_elig && !cs->elig_global;
   subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(
-      d_subset, subset_len, ix->doc_begin, ix->n_docs, ix->d_doc_offsets, ix->codes(), w.subset_bits.as<uint32_t>(),
+      d_subset, subset_len, ix->doc_begin, ix->n_docs, ix->d_doc_offsets.get(), ix->codes(), w.subset_bits.as<uint32_t>(),
       local_elig ? w.elig.as<uint32_t>() : nullptr);
   if (p.use_elig) {
     const uint32_t* elig_bits = cs->elig_global ? cs->elig_global : w.elig.as<uint32_t>();
@@ -980,7 +980,7 @@ int Pass::ub_bounds(const RoundPlan& rpx, int r, int max_rounds, int32_t* sl, ui
         with_bool(floor_rows && p.can_floor, [&](auto FLOOR) {
           if constexpr (!FLOOR || (NT == 2 && RB <= 64))   // (can_floor: oob, RB <= 64)
             approx_ub_kernel<RB, CT, NT, FLOOR><<<grid, 256, 0, st>>>(
-                w.QCU.as<uint8_t>(), p.KP, meta, begin, count, n_all, rpx, r, max_rounds, (const CT*)ix->d_ucodes,
+                w.QCU.as<uint8_t>(), p.KP, meta, begin, count, n_all, rpx, r, max_rounds, (const CT*)ix->d_ucodes.get(),
                 w.qflag.as<uint32_t>(), cs->n_sel, U, hist, p.hshift, cur, sl, tk, B, ix->tune.ub_steal, w.ctr.as<Counters>(),
                 count_tokens, direct_wpq, ix->tune.ub_static,
                 FLOOR ? w.hotbits.as<uint32_t>() + (size_t)B * (p.KP / 32) : nullptr,
@@ -1017,9 +1017,9 @@ int Pass::zeroth_level(const RoundPlan& rp, GainP& gp) const {
     g_real = cs->prm.has_threshold ? gd.kept : w.cellbits.as<uint32_t>();
   }
   gp.KP = p.KP;
-  gp.ivf_off = ix->d_ivf_offsets;
-  gp.ivf = ix->d_ivf;
-  gp.split = ix->d_ivf_split;
+  gp.ivf_off = ix->d_ivf_offsets.get();
+  gp.ivf = ix->d_ivf.get();
+  gp.split = ix->d_ivf_split.get();
   gp.R1 = ix->n_ranges + 1;
   gp.gain = w.gain.as<uint16_t>();
   gp.gbase = g.base;
@@ -1029,7 +1029,7 @@ int Pass::zeroth_level(const RoundPlan& rp, GainP& gp) const {
   gp.thr = g.thr0;
   gp.s0_meta = w.s0_meta.as<uint4>();
   gp.s0cap = p.s0cap;
-  gp.ucodes = ix->d_ucodes;
+  gp.ucodes = ix->d_ucodes.get();
   gp.code_wide = ix->code_wide;
   gp.ublock_stride = ix->ublock_stride;
   gp.ovf_base = (int64_t)ix->n_docs * ix->ublock_stride;
@@ -1080,14 +1080,14 @@ int Pass::s3_plan(const RoundPlan& rp) const {
         NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mark_slices_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       mark_slices_kernel<<<dim3(nslices, B), 1024, lds, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP,
-                                                              ix->d_ivf_offsets, ix->d_ivf,
+                                                              ix->d_ivf_offsets.get(), ix->d_ivf.get(),
                                                               p.have_subset ? w.subset_bits.as<uint32_t>() : nullptr, p.NW,
                                                               slice_chunks, nchunks, w.docbits.as<uint32_t>(),
                                                               w.chunk_counts.as<int32_t>(), w.ctr.as<Counters>(),
                                                               (ix->ivf_sorted && ix->tune.s3_bisect) ? 1 : 0);
     } else {
       mark_candidates_kernel<<<dim3(128, B), 256, 0, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP,
-                                                           ix->d_ivf_offsets, ix->d_ivf,
+                                                           ix->d_ivf_offsets.get(), ix->d_ivf.get(),
                                                            p.have_subset ? w.subset_bits.as<uint32_t>() : nullptr, p.NW,
                                                            w.docbits.as<uint32_t>(), w.ctr.as<Counters>());
       count_chunks_kernel<<<dim3(nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), p.NW, nchunks,
@@ -1145,7 +1145,7 @@ int Pass::round(int r, const RoundPlan& rp, const GainP& gp, SelectP sp) const {
   else
     compact_kernel<<<dim3(p.nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), p.NW, p.nchunks, w.chunk_counts.as<int32_t>(),
                                                        (p.use_filter && !p.ids_only) ? nullptr : w.cand.as<uint32_t>(), rp, r,
-                                                       p.ids_only ? nullptr : ix->d_doc_meta, w.cand_meta.as<uint4>());
+                                                       p.ids_only ? nullptr : ix->d_doc_meta.get(), w.cand_meta.as<uint4>());
   if (cs->timed && r == 0) NP_HIP(hipEventRecord(cs->ctx->ev[3], st));
   const bool matvec = p.batched && !p.s1_split;
   if (p.use_filter) {
@@ -1290,7 +1290,7 @@ int Pass::hot_level(int r, const RoundPlan& rp) const {
         approx_hot_kernel<RB, CT><<<8 * (unsigned)ix->tune.ub_nbx, 256, dyn, st>>>(
             w.QCU.as<uint8_t>(), ix->K, KP, w.cmaxu.as<uint8_t>(), w.ub_thr2.as<uint32_t>() + B, w.cand.as<uint32_t>(),
             w.cand_meta.as<uint4>(), ix->ublock_stride, (int64_t)ix->n_docs * ix->ublock_stride, w.n_cand.as<int32_t>(), rp, r,
-            p.max_rounds, (const CT*)ix->d_ucodes, w.qflag.as<uint32_t>(), d_qoff, cs->n_sel, w.ub.as<uint16_t>(),
+            p.max_rounds, (const CT*)ix->d_ucodes.get(), w.qflag.as<uint32_t>(), d_qoff, cs->n_sel, w.ub.as<uint16_t>(),
             w.ub_hist.as<uint32_t>(), p.hshift, cursor(0), sl, sl + 8 * (B + 1), B, ix->tune.ub_steal, w.ctr.as<Counters>(),
             ix->tune.s4_probe, ix->tune.hot_static);
         return NP_OK;
@@ -1333,7 +1333,7 @@ int Pass::hotp(int r, const RoundPlan& rp, unsigned nbx) const {
   approx_hotp_kernel<RB, CT, LPD, PF, DPI, QM, WPB><<<8 * nbx, 64 * WPB, dynp, st>>>(
       w.planes.as<uint32_t>(), ix->K, KP, w.hotbits.as<uint32_t>(), w.ub_thr2.as<uint32_t>() + B, w.levels.as<uint32_t>(),
       w.cand.as<uint32_t>(), w.cand_meta.as<uint4>(), ix->ublock_stride, (int64_t)ix->n_docs * ix->ublock_stride,
-      w.n_cand.as<int32_t>(), rp, r, p.max_rounds, (const CT*)ix->d_ucodes, w.qflag.as<uint32_t>(), d_qoff, cs->n_sel,
+      w.n_cand.as<int32_t>(), rp, r, p.max_rounds, (const CT*)ix->d_ucodes.get(), w.qflag.as<uint32_t>(), d_qoff, cs->n_sel,
       w.ub.as<uint16_t>(), w.ub_hist.as<uint32_t>(), p.hshift, sl, sl + 8 * (B + 1), B, w.ctr.as<Counters>(), slack,
       ix->tune.s4_probe, p.gain_path ? 1 : 0);
   return NP_OK;
@@ -1409,14 +1409,14 @@ static int phase_b(const DeviceIndex* ix, CallState* cs, const int32_t* d_qoff, 
     ep.Qb_lo = w.Qbl.as<__bf16>();
     ep.QCT = w.QCT.as<float>();
     ep.KP = ix->KP;
-    ep.inv_norm = ix->d_inv_norm;
+    ep.inv_norm = ix->d_inv_norm.get();
     ep.qoff = d_qoff;
     ep.LQP = cs->LQP;
-    ep.centroids = ix->d_centroids;
-    ep.wlut = ix->d_wlut;
+    ep.centroids = ix->d_centroids.get();
+    ep.wlut = ix->d_wlut.get();
     ep.codes = ix->codes();
-    ep.residuals = ix->d_residuals;
-    ep.doc_off = ix->d_doc_offsets;
+    ep.residuals = ix->d_residuals.get();
+    ep.doc_off = ix->d_doc_offsets.get();
     ep.sel_keys = w.sel_keys.as<uint64_t>();
     ep.sel_doc = w.sel_doc.as<uint32_t>();
     ep.nsel = w.nsel.as<int32_t>();
@@ -1447,7 +1447,7 @@ static int phase_b(const DeviceIndex* ix, CallState* cs, const int32_t* d_qoff, 
     tp.NSELP = cs->NSELP;
     tp.top_k = cs->prm.top_k;
     tp.doc_begin = ix->doc_begin;
-    tp.doc_off = ix->d_doc_offsets;
+    tp.doc_off = ix->d_doc_offsets.get();
     tp.ctr = w.ctr.as<Counters>();
     tp.out_ids = d_out_ids;
     tp.out_scores = d_out_scores;
@@ -1826,7 +1826,7 @@ int np_hip_subset_eligible(const np_index* ix, const int64_t* d_subset, int64_t 
   NP_HIP(hipMemsetAsync(d_elig_bits, 0, (size_t)(ix->KP / 32) * 4, st));
   if (subset_len > 0)
     subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(d_subset, subset_len, ix->doc_begin, ix->n_docs,
-                                                                     ix->d_doc_offsets, ix->codes(), nullptr, d_elig_bits);
+                                                                     ix->d_doc_offsets.get(), ix->codes(), nullptr, d_elig_bits);
   NP_HIP(hipGetLastError());
   return NP_OK;
 }
@@ -1887,7 +1887,7 @@ int np_hip_decompress_documents(const np_index* ix, const int64_t* doc_ids, int6
   }
   DeviceGuard g(ix->device);
   std::vector<int64_t> off((size_t)ix->n_docs + 1);
-  NP_HIP(hipMemcpy(off.data(), ix->d_doc_offsets, off.size() * 8, hipMemcpyDeviceToHost));
+  NP_HIP(hipMemcpy(off.data(), ix->d_doc_offsets.get(), off.size() * 8, hipMemcpyDeviceToHost));
   std::vector<int64_t> toks, bases;
   for (int64_t i = 0; i < n_docs; ++i) {
     const int64_t d = doc_ids[i] - ix->doc_begin;
@@ -1909,27 +1909,20 @@ int np_hip_decompress_documents(const np_index* ix, const int64_t* doc_ids, int6
     set_error("decompress_documents: output holds %lld rows, %zu needed", (long long)out_capacity_rows, toks.size());
     return NP_ERR_INVALID_ARGUMENT;
   }
-  int64_t* d_tok = nullptr;
-  float* d_out = nullptr;
-  NP_HIP(hipMalloc(&d_tok, toks.size() * 16));
-  hipError_t e = hipMalloc(&d_out, toks.size() * (size_t)ix->ldim * 4);
-  if (e != hipSuccess) {
-    (void)hipFree(d_tok);
-    set_error("hipMalloc failed: %s", hipGetErrorString(e));
-    return NP_ERR_OUT_OF_MEMORY;
-  }
-  e = hipMemcpy(d_tok, toks.data(), toks.size() * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_tok + toks.size(), bases.data(), toks.size() * 8, hipMemcpyHostToDevice);
+  DevPtr<int64_t> d_tok;   // the tokens, then their rows' bases
+  DevPtr<float> d_out;
+  NP_TRY(d_tok.alloc(toks.size() * 2));
+  NP_TRY(d_out.alloc(toks.size() * (size_t)ix->ldim));
+  hipError_t e = hipMemcpy(d_tok.get(), toks.data(), toks.size() * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_tok.get() + toks.size(), bases.data(), toks.size() * 8, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    decompress_kernel<<<(unsigned)((toks.size() + 3) / 4), 256>>>(d_tok, d_tok + toks.size(),
-                                                                  ix->tok_sorted ? ix->d_tok_pos : nullptr,
+    decompress_kernel<<<(unsigned)((toks.size() + 3) / 4), 256>>>(d_tok.get(), d_tok.get() + toks.size(),
+                                                                  ix->tok_sorted ? ix->d_tok_pos.get() : nullptr,
                                                                   (int64_t)toks.size(), ix->dim, ix->ldim, ix->nbits, ix->pd,
-                                                                  ix->d_centroids, ix->d_wlut, ix->codes(), ix->d_residuals,
-                                                                  d_out);
-    e = hipMemcpy(out_embeddings, d_out, toks.size() * (size_t)ix->ldim * 4, hipMemcpyDeviceToHost);
+                                                                  ix->d_centroids.get(), ix->d_wlut.get(), ix->codes(), ix->d_residuals.get(),
+                                                                  d_out.get());
+    e = hipMemcpy(out_embeddings, d_out.get(), toks.size() * (size_t)ix->ldim * 4, hipMemcpyDeviceToHost);
   }
-  (void)hipFree(d_tok);
-  (void)hipFree(d_out);
   if (e != hipSuccess) {
     set_error("decompress_documents failed: %s", hipGetErrorString(e));
     return NP_ERR_DEVICE_UNAVAILABLE;
@@ -2079,11 +2072,11 @@ int np::encode_tokens_impl(const np_index* ix, const float* embeddings, int64_t 
     launch_gemm(st, ix, w.Qt.as<float>(), Sb, LQP, w.QCT.as<float>(), w.gmax.as<uint32_t>());
     encode_argmax_kernel<<<(unsigned)((nb + 3) / 4), 256, 0, st>>>(w.QCT.as<float>(), w.gmax.as<uint32_t>(), ix->K, KP,
                                                                   LQP, nb, w.out_ids.as<int64_t>());
-    encode_pack_kernel<<<(unsigned)((nb * pd + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids,
+    encode_pack_kernel<<<(unsigned)((nb * pd + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids.get(),
                                                                          w.out_ids.as<int64_t>(), w.misc.as<float>(), nb,
                                                                          dim, sdim, ix->lnbits, w.cand.as<uint8_t>());
     if (out_norms)
-      encode_norm_kernel<<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids, w.out_ids.as<int64_t>(),
+      encode_norm_kernel<<<(unsigned)((nb + 255) / 256), 256, 0, st>>>(w.q.as<float>(), ix->d_centroids.get(), w.out_ids.as<int64_t>(),
                                                                         nb, dim, sdim, w.approx.as<float>());
     NP_HIP(hipGetLastError());
     NP_HIP(hipMemcpyAsync(out_codes + t0, w.out_ids.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
@@ -2131,34 +2124,23 @@ int np_hip_rerank_maxsim(int32_t device, const float* query, int32_t n_query_tok
     return NP_ERR_DEVICE_UNAVAILABLE;
   }
   DeviceGuard g(device);
-  float *d_q = nullptr, *d_d = nullptr, *d_s = nullptr;
-  int64_t* d_off = nullptr;
-  int* d_f = nullptr;
-  struct Free {
-    float **a, **b, **c;
-    int64_t** d;
-    int** e;
-    ~Free() {
-      (void)hipFree(*a);
-      (void)hipFree(*b);
-      (void)hipFree(*c);
-      (void)hipFree(*d);
-      (void)hipFree(*e);
-    }
-  } fr{&d_q, &d_d, &d_s, &d_off, &d_f};
-  NP_HIP(hipMalloc(&d_q, std::max<size_t>((size_t)n_query_tokens * dim * 4, 4)));
-  NP_HIP(hipMalloc(&d_d, std::max<size_t>((size_t)T * dim * 4, 4)));
-  NP_HIP(hipMalloc(&d_s, (size_t)n_docs * 4));
-  NP_HIP(hipMalloc(&d_off, (size_t)(n_docs + 1) * 8));
-  NP_HIP(hipMalloc(&d_f, (size_t)n_docs * 4));
-  if (n_query_tokens > 0) NP_HIP(hipMemcpy(d_q, query, (size_t)n_query_tokens * dim * 4, hipMemcpyHostToDevice));
-  if (T > 0) NP_HIP(hipMemcpy(d_d, doc_embeddings, (size_t)T * dim * 4, hipMemcpyHostToDevice));
-  NP_HIP(hipMemcpy(d_off, doc_tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-  rerank_kernel<<<(unsigned)n_docs, 256, (size_t)8 * dim * 4>>>(d_q, n_query_tokens, dim, d_d, d_off, d_s, d_f);
+  DevPtr<float> d_q, d_d, d_s;
+  DevPtr<int64_t> d_off;
+  DevPtr<int> d_f;
+  NP_TRY(d_q.alloc((size_t)n_query_tokens * dim));
+  NP_TRY(d_d.alloc((size_t)T * dim));
+  NP_TRY(d_s.alloc((size_t)n_docs));
+  NP_TRY(d_off.alloc((size_t)n_docs + 1));
+  NP_TRY(d_f.alloc((size_t)n_docs));
+  if (n_query_tokens > 0) NP_HIP(hipMemcpy(d_q.get(), query, (size_t)n_query_tokens * dim * 4, hipMemcpyHostToDevice));
+  if (T > 0) NP_HIP(hipMemcpy(d_d.get(), doc_embeddings, (size_t)T * dim * 4, hipMemcpyHostToDevice));
+  NP_HIP(hipMemcpy(d_off.get(), doc_tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+  rerank_kernel<<<(unsigned)n_docs, 256, (size_t)8 * dim * 4>>>(d_q.get(), n_query_tokens, dim, d_d.get(), d_off.get(), d_s.get(),
+                                                                d_f.get());
   NP_HIP(hipGetLastError());
   std::vector<int> flags((size_t)n_docs);
-  NP_HIP(hipMemcpy(out_scores, d_s, (size_t)n_docs * 4, hipMemcpyDeviceToHost));
-  NP_HIP(hipMemcpy(flags.data(), d_f, (size_t)n_docs * 4, hipMemcpyDeviceToHost));
+  NP_HIP(hipMemcpy(out_scores, d_s.get(), (size_t)n_docs * 4, hipMemcpyDeviceToHost));
+  NP_HIP(hipMemcpy(flags.data(), d_f.get(), (size_t)n_docs * 4, hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < n_docs; ++i)
     if (flags[(size_t)i]) {  // rerank.rs:71-75,85-89
       set_error("Rerank score contains non-finite value");

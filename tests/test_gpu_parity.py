@@ -580,6 +580,44 @@ def test_open_rejects_an_out_of_range_code(bad):
     hip_index(a).close()                                   # the untouched arrays still open
 
 
+def test_refused_opens_return_their_device_memory():
+    """An open refused after the token upload (a code or a posting-list id out of range) frees every device buffer it
+    took: codec, doc offsets, ~300 MB of residuals and 384 MiB of upload staging.  After a first refused open, two more
+    and a successful open + close leave free device memory within TOL of that reading.  Measured on an MI355X before the
+    index arrays had one owner: a drop of 0 bytes.  One leaked open would hold ~700 MB; TOL = 64 MiB only absorbs what the
+    runtime may keep for code objects loaded by the successful open's first kernel launches."""
+    import torch
+    TOL = 64 << 20
+    n_docs, doc_len, K, dim, nbits = 50_000, 96, 256, 128, 4
+    rng = np.random.default_rng(11)
+    T = n_docs * doc_len
+    good = dict(centroids=rng.standard_normal((K, dim)).astype(np.float32),
+                bucket_weights=np.linspace(-0.5, 0.5, 1 << nbits, dtype=np.float32),
+                ivf=np.concatenate([np.arange(c, n_docs, K) for c in range(K)]).astype(np.int64),
+                ivf_lengths=np.array([len(range(c, n_docs, K)) for c in range(K)], np.int32),
+                doc_lengths=np.full(n_docs, doc_len, np.int64),
+                codes=rng.integers(0, K, T, dtype=np.int64),
+                residuals=rng.integers(0, 256, (T, dim * nbits // 8), dtype=np.uint8), nbits=nbits)
+    bad_code = dict(good, codes=good["codes"].copy())
+    bad_code["codes"][-1] = K                              # the last piece of the upload fails the range check
+    bad_id = dict(good, ivf=good["ivf"].copy())
+    bad_id["ivf"][-1] = n_docs                             # the posting lists fail after the whole upload
+
+    def refused(b, what):
+        with pytest.raises(npa.IndexLoadError) as e:
+            hip_index(b)
+        assert what in str(e.value)
+
+    refused(bad_code, "out of range")
+    free0, _ = torch.cuda.mem_get_info()
+    refused(bad_code, "out of range")
+    refused(bad_id, "out of range")
+    hip_index(good).close()
+    free1, _ = torch.cuda.mem_get_info()
+    print(f"free device memory after the first refused open {free0}, at the end {free1}: drop {free0 - free1} bytes")
+    assert free1 >= free0 - TOL, f"{(free0 - free1) / 2**20:.1f} MiB of device memory not returned"
+
+
 def test_reload_after_the_directory_changed(tmp_path):
     """MmapIndex::reload (index.rs:1767-1775): delete() rewrites the chunk files and re-sequences the ids
     (delete.rs:66-120); reload() must serve the new directory -- here: the same corpus without its first 100 documents."""
