@@ -382,8 +382,8 @@ def _ptr(a):
 @dataclass
 class SearchParameters:
     """search.rs:26-69 (same field names and defaults) + `precision`, the arithmetic of the exact MaxSim stage
-    (S1-S5 are always exact f32): 2 (default) = QC-reuse form with split-bf16 MFMA on the residual term, f32-class
-    accuracy (max relative score error 5e-7 measured, the same as mode 0); 0 = exact-f32 MFMA on decompressed rows;
+    (S1-S5 are always exact f32): 2 (default) = QC-reuse form with split-bf16 MFMA on the residual term (error bound
+    against float64 derived in tests/exact_restate.py, measured in profiles/s6_error_bounds.md); 0 = exact-f32 MFMA on decompressed rows;
     1 = QC-reuse with plain bf16 on the residual term (<= 1e-3 relative); 3 = bf16 MFMA on decompressed rows."""
     batch_size: int = 2000
     n_full_scores: int = 4096

@@ -15,6 +15,7 @@ from oracle import oracle as O  # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 # Stated tolerances (north_star allows 1e-3 relative; the fp32 path is far inside it).
+# For RANKING comparisons with the f32 oracle; score accuracy against float64 is bounded in tests/exact_restate.py.
 RTOL_F32 = 2e-5   # fp32 MFMA path vs oracle: summation-order differences only
 RTOL_BF16 = 1e-3  # bf16 on the residual term only (precision=1): north_star's bound
 RTOL_BF16_PLAIN = 4e-3  # precision=3: BOTH operands of the whole dot product rounded to bf16 (2^-8 per product); the
