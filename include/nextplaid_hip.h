@@ -137,8 +137,8 @@ const char* np_hip_last_error(void);
  * header would have bytes written past its structs before it could read np_info.abi_version.  A host binds this first and
  * refuses a library whose version differs from the header it was built with; np_hip_struct_size lets it check the two
  * layouts it allocates (which: 0 = np_info, 1 = np_stats, 2 = np_search_params, 3 = np_open_opts, 4 = np_kmeans_opts,
- * 5 = np_kmeans_report, 6 = np_index_config, 7 = np_kmeans_plan, 8 = np_update_config, 9 = np_update_report; -1 for an
- * unknown id). */
+ * 5 = np_kmeans_report, 6 = np_index_config, 7 = np_kmeans_plan, 8 = np_update_config, 9 = np_update_report,
+ * 10 = np_pool_opts, 11 = np_pool_report; -1 for an unknown id). */
 int np_hip_abi_version(void);
 int64_t np_hip_struct_size(int32_t which);
 
@@ -576,6 +576,59 @@ int np_hip_index_update_append(const char* index_dir, const float* embeddings, c
  * The crate's renumbering counts every listed id below a posting-list entry, negative ones included, so a negative
  * id shifts every entry by one and its posting lists no longer match its codes; here delete([-1, 3]) equals delete([3]). */
 int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n_ids, int64_t* out_deleted);
+
+/* ---- token pooling: pool_document_embeddings (np_pool.hip) --------------------------------------------------------------
+ * next-plaid-onnx pools every document before it reaches the index (src/lib.rs:1632-1643 pool_document_embeddings ->
+ * :2249-2317 pool_embeddings_hierarchical -> hierarchy.rs:599-653 pdist_cosine, :128-284 Ward linkage by nearest-neighbour
+ * chain, :426-517 fcluster_maxclust).  Per document of n tokens, with p = protected_tokens and f = pool_factor:
+ *  - n <= p + 1, or k = max((n - p) / f, 1) >= n - p, or f <= 1: the document is returned unchanged;
+ *  - otherwise the first p rows are copied and the other m = n - p rows are clustered into k clusters; a cluster's row is the
+ *    f32 sum of its members in token order divided by the count as f32 (not renormalised); clusters are ordered by the first
+ *    token that belongs to them.
+ * Distances: norms and dot products are f64 sums over the features in feature order of the f32 inputs widened to f64,
+ * cos = dot / (ni nj) (0 when a norm is 0), d = clamp(1 - cos, 0, 2); Ward's Lance-Williams update runs on d * d in f64 without
+ * contraction.  Linkage: a chain starts at the lowest active id, a nearest neighbour is the strict minimum (ties to the lowest
+ * id), and the reference's nearest-neighbour CACHE is kept: an entry is recomputed only for the new cluster and for a cluster
+ * whose cached neighbour was one of the two just merged.  Merges are recorded as [min id, max id, sqrt(d^2), size] in the
+ * order the chain finds them.  The results equal the reference's bit for bit and never depend on the chunking or on the
+ * other documents of the call.
+ * cut_order: 0 (the reference, and what an index built by the crate holds) applies the first m - k merges IN CHAIN ORDER
+ * (fcluster_maxclust reads the unsorted list); 1 applies the first m - k merges of a stable sort by merge distance: the
+ * dendrogram cut of scipy's fcluster(linkage(., 'ward'), k, 'maxclust') and of PyLate.  The two partitions differ on most
+ * documents ("Token pooling"). */
+typedef struct np_pool_opts {
+  int32_t pool_factor;       /* <= 1: every document is copied through */
+  int32_t protected_tokens;  /* leading rows kept as they are (the reference fixes 1) */
+  int32_t cut_order;         /* 0 = chain order (the reference), 1 = stable order by merge distance (scipy / PyLate) */
+  int32_t reserved0;
+  int64_t chunk_docs;        /* documents per device chunk at most; 0 = as many as the free device memory takes */
+  int64_t reserved[3];
+} np_pool_opts;
+
+typedef struct np_pool_report {
+  int64_t n_docs;            /* documents in */
+  int64_t n_pooled;          /* documents that were clustered (the others were copied through) */
+  int64_t tokens_in;
+  int64_t tokens_out;
+  double ms_distances;       /* device time of the three stages, summed over the chunks */
+  double ms_linkage;
+  double ms_means;
+  int64_t n_chunks;
+  int64_t reserved[3];
+} np_pool_report;
+
+/* Host only: out_lengths[i] = tokens of document i after pooling. */
+int np_hip_pooled_lengths(const int64_t* doc_lengths, int64_t n_docs, const np_pool_opts* opts, int64_t* out_lengths);
+
+/* embeddings = every document's tokens concatenated ([sum doc_lengths][dim]); out_embeddings has room for
+ * out_rows_capacity rows (sum of np_hip_pooled_lengths); out_lengths [n_docs].  out_labels (nullable) [sum doc_lengths]:
+ * 0 for a protected token or a token of an unchanged document, 1.. for the clusters in output order.  out_linkage
+ * (nullable): [m - 1][4] f64 per CLUSTERED document, concatenated in document order.  report nullable.  Host pointers; needs
+ * no index.  Non-finite inputs: NP_ERR_INVALID_ARGUMENT (the reference would index with usize::MAX).  A document that hands
+ * more than 2048 tokens to the clustering: NP_ERR_SHAPE. */
+int np_hip_pool_documents(int32_t device, const float* embeddings, const int64_t* doc_lengths, int64_t n_docs, int32_t dim,
+                          const np_pool_opts* opts, float* out_embeddings, int64_t out_rows_capacity, int64_t* out_lengths,
+                          int32_t* out_labels, double* out_linkage, np_pool_report* report);
 
 /* Stage-level debug access for parity tests: runs S1-S5 for ONE query and copies out the probed
  * cells (ascending), candidate doc ids (ascending, global), their approximate scores, and the

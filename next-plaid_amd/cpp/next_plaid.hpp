@@ -506,4 +506,51 @@ inline std::pair<std::vector<int64_t>, std::vector<float>> rerank_maxsim(const f
   return {std::move(order), std::move(scores)};
 }
 
+// ---- token pooling: next-plaid-onnx src/lib.rs:1632-1643 pool_document_embeddings, :2249-2317, hierarchy.rs ------------
+enum class PoolCut { Reference = 0, Distance = 1 };   // chain order (the crate) / stable order by merge distance (scipy, PyLate)
+
+inline np_pool_opts pool_opts(size_t pool_factor, size_t protected_tokens, PoolCut cut, int64_t chunk_docs = 0) {
+  np_pool_opts o{};
+  o.pool_factor = (int32_t)pool_factor;
+  o.protected_tokens = (int32_t)protected_tokens;
+  o.cut_order = (int32_t)cut;
+  o.chunk_docs = chunk_docs;
+  return o;
+}
+
+// every document's token count after pooling (host only)
+inline std::vector<int64_t> pooled_lengths(const std::vector<int64_t>& doc_lengths, size_t pool_factor,
+                                           size_t protected_tokens = 1) {
+  const np_pool_opts o = pool_opts(pool_factor, protected_tokens, PoolCut::Reference);
+  std::vector<int64_t> out(doc_lengths.size());
+  check(np_hip_pooled_lengths(doc_lengths.data(), (int64_t)doc_lengths.size(), &o, out.data()));
+  return out;
+}
+
+struct PooledDocuments {
+  std::vector<float> embeddings;       // every pooled document's rows concatenated
+  std::vector<int64_t> doc_lengths;
+  std::vector<int32_t> labels;         // per INPUT token (only with want_labels): 0 = protected / unchanged, 1.. = cluster
+  np_pool_report report{};
+};
+
+inline PooledDocuments pool_document_embeddings(const Documents& docs, size_t pool_factor, size_t protected_tokens = 1,
+                                                PoolCut cut = PoolCut::Reference, int device = 0, bool want_labels = false,
+                                                int64_t chunk_docs = 0) {
+  const np_pool_opts o = pool_opts(pool_factor, protected_tokens, cut, chunk_docs);
+  const int64_t n = (int64_t)docs.doc_lengths.size();
+  PooledDocuments r;
+  r.doc_lengths = pooled_lengths(docs.doc_lengths, pool_factor, protected_tokens);
+  int64_t rows = 0, tokens = 0;
+  for (int64_t v : r.doc_lengths) rows += v;
+  for (int64_t v : docs.doc_lengths) tokens += v;
+  r.embeddings.resize((size_t)std::max<int64_t>(rows, 1) * docs.dim);
+  if (want_labels) r.labels.resize((size_t)std::max<int64_t>(tokens, 1));
+  check(np_hip_pool_documents(device, docs.embeddings, docs.doc_lengths.data(), n, (int32_t)docs.dim, &o, r.embeddings.data(),
+                              rows, r.doc_lengths.data(), want_labels ? r.labels.data() : nullptr, nullptr, &r.report));
+  r.embeddings.resize((size_t)rows * docs.dim);
+  if (want_labels) r.labels.resize((size_t)tokens);
+  return r;
+}
+
 }  // namespace next_plaid

@@ -1516,6 +1516,8 @@ int64_t np_hip_struct_size(int32_t which) {
     case 7: return (int64_t)sizeof(np_kmeans_plan);
     case 8: return (int64_t)sizeof(np_update_config);
     case 9: return (int64_t)sizeof(np_update_report);
+    case 10: return (int64_t)sizeof(np_pool_opts);
+    case 11: return (int64_t)sizeof(np_pool_report);
     default: return -1;
   }
 }

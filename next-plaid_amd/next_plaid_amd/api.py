@@ -161,6 +161,20 @@ class np_update_report(C.Structure):
         return d
 
 
+class np_pool_opts(C.Structure):
+    _fields_ = [("pool_factor", C.c_int32), ("protected_tokens", C.c_int32), ("cut_order", C.c_int32), ("reserved0", C.c_int32),
+                ("chunk_docs", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+class np_pool_report(C.Structure):
+    _fields_ = [("n_docs", C.c_int64), ("n_pooled", C.c_int64), ("tokens_in", C.c_int64), ("tokens_out", C.c_int64),
+                ("ms_distances", C.c_double), ("ms_linkage", C.c_double), ("ms_means", C.c_double), ("n_chunks", C.c_int64),
+                ("reserved", C.c_int64 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 # np_all_gather_host_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes)
 ALL_GATHER_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 NP_COMM_DEFERRED_STATUS = 1
@@ -179,6 +193,7 @@ EXPORTS = [
     "np_hip_decompress_documents", "np_hip_encode_tokens", "np_hip_rerank_maxsim", "np_hip_debug_trace",
     "np_hip_kmeans_plan", "np_hip_kmeans", "np_hip_compute_kmeans", "np_hip_prepare_codec_artifacts", "np_hip_index_create",
     "np_hip_index_update", "np_hip_index_update_append", "np_hip_index_delete",
+    "np_hip_pooled_lengths", "np_hip_pool_documents",
 ]
 
 _lib = None
@@ -232,7 +247,7 @@ def lib():
         raise DeviceUnavailableError(f"{path} speaks ABI v{ver}, this mirror v{NP_ABI_VERSION}: rebuild the library")
     for which, st in ((0, np_info), (1, np_stats), (2, np_search_params), (3, np_open_opts), (4, np_kmeans_opts),
                       (5, np_kmeans_report), (6, np_index_config), (7, np_kmeans_plan), (8, np_update_config),
-                      (9, np_update_report)):
+                      (9, np_update_report), (10, np_pool_opts), (11, np_pool_report)):
         if int(L.np_hip_struct_size(which)) != C.sizeof(st):
             raise DeviceUnavailableError(f"{path}: sizeof({st.__name__}) is {int(L.np_hip_struct_size(which))} in the library, "
                                          f"{C.sizeof(st)} in this mirror")
@@ -292,6 +307,9 @@ def lib():
     for f in (L.np_hip_index_update, L.np_hip_index_update_append):
         f.argtypes = [C.c_char_p, vp, vp, i64, i32, C.POINTER(np_update_config), i32, C.POINTER(np_update_report)]
     L.np_hip_index_delete.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
+    L.np_hip_pooled_lengths.argtypes = [vp, i64, C.POINTER(np_pool_opts), vp]
+    L.np_hip_pool_documents.argtypes = [i32, vp, vp, i64, i32, C.POINTER(np_pool_opts), vp, i64, vp, vp, vp,
+                                        C.POINTER(np_pool_report)]
     _lib = L
     return L
 
@@ -563,6 +581,73 @@ def _docs(documents):
     lens = np.array([d.shape[0] for d in docs], np.int64)
     flat = np.concatenate(docs, 0) if lens.sum() > 0 else np.zeros((1, max(dim, 1)), np.float32)
     return np.ascontiguousarray(flat, np.float32), lens, dim
+
+
+_POOL_CUTS = {"reference": 0, "distance": 1}
+
+
+def _pool_opts(pool_factor, protected_tokens, cut, chunk_docs=0):
+    if cut not in _POOL_CUTS:
+        raise ValueError(f"cut must be 'reference' or 'distance', got {cut!r}")
+    return np_pool_opts(int(pool_factor), int(protected_tokens), _POOL_CUTS[cut], 0, int(chunk_docs))
+
+
+def pooled_lengths(doc_lengths, pool_factor: int, protected_tokens: int = 1):
+    """Host only: every document's token count after pool_document_embeddings (lib.rs:2254-2266)."""
+    dl = np.ascontiguousarray(doc_lengths, np.int64)
+    out = np.zeros(max(dl.size, 1), np.int64)
+    o = _pool_opts(pool_factor, protected_tokens, "reference")
+    _check(lib().np_hip_pooled_lengths(_ptr(dl), dl.size, C.byref(o), _ptr(out)))
+    return out[: dl.size]
+
+
+def pool_document_embeddings(documents, pool_factor: int, protected_tokens: int = 1, cut: str = "reference", device: int = 0,
+                             return_labels: bool = False, chunk_docs: int = 0, return_details: bool = False):
+    """pool_document_embeddings (next-plaid-onnx lib.rs:1632-1643, :2249-2317; hierarchy.rs) on the GPU, bit for bit: Ward
+    clustering of every document's tokens after the first `protected_tokens` into (n - protected) / pool_factor clusters,
+    each replaced by the mean of its members.  cut="reference" applies the merges in the order the crate's chain finds them
+    (an index built from the result equals one built by the crate); cut="distance" is the dendrogram cut of scipy / PyLate.
+    Returns the pooled documents (a list of [n_i', dim] f32 arrays); with return_labels also the per-token labels of every
+    document (0 = protected or unchanged, 1.. = cluster in output order); with return_details a dict with the linkage rows
+    of the clustered documents (f64 [m - 1, 4] each, None for the others) and the stage report."""
+    docs = [np.ascontiguousarray(d, np.float32) for d in documents]
+    if not docs:
+        return ([], []) if return_labels else []
+    dim = docs[0].shape[1] if docs[0].ndim == 2 else -1
+    for d in docs:
+        if d.ndim != 2 or d.shape[1] != dim:
+            raise ShapeError(f"Shape error: document has shape {d.shape}, expected [n, {dim}]")
+    lens = np.array([d.shape[0] for d in docs], np.int64)
+    flat = np.ascontiguousarray(np.concatenate(docs, 0), np.float32) if lens.sum() > 0 else np.zeros((1, max(dim, 1)), np.float32)
+    o = _pool_opts(pool_factor, protected_tokens, cut, chunk_docs)
+    plen = np.zeros(lens.size, np.int64)
+    _check(lib().np_hip_pooled_lengths(_ptr(lens), lens.size, C.byref(o), _ptr(plen)))
+    out = np.zeros((max(int(plen.sum()), 1), max(dim, 1)), np.float32)
+    olen = np.zeros(lens.size, np.int64)
+    labels = np.zeros(max(int(lens.sum()), 1), np.int32) if return_labels else None
+    clustered = plen != lens
+    nlink = int((lens[clustered] - int(protected_tokens) - 1).sum())
+    link = np.zeros((max(nlink, 1), 4), np.float64) if return_details else None
+    rep = np_pool_report()
+    _check(lib().np_hip_pool_documents(int(device), _ptr(flat), _ptr(lens), lens.size, dim, C.byref(o), _ptr(out),
+                                       int(plen.sum()), _ptr(olen), _ptr(labels), _ptr(link), C.byref(rep)))
+    oo = np.concatenate([[0], np.cumsum(olen)])
+    pooled = [out[oo[i]: oo[i + 1]].copy() for i in range(lens.size)]
+    res = [pooled]
+    if return_labels:
+        io = np.concatenate([[0], np.cumsum(lens)])
+        res.append([labels[io[i]: io[i + 1]].copy() for i in range(lens.size)])
+    if return_details:
+        links, r = [], 0
+        for i in range(lens.size):
+            if clustered[i]:
+                nr = int(lens[i]) - int(protected_tokens) - 1
+                links.append(link[r: r + nr].copy())
+                r += nr
+            else:
+                links.append(None)
+        res.append({"linkage": links, "report": rep.as_dict()})
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def kmeans_plan(doc_lengths, config: IndexConfig | None = None, num_partitions: int | None = None):
