@@ -266,6 +266,41 @@ int np_hip_search_batch_device(const np_index* index, const float* d_queries,
                                int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
                                void* stream);
 
+/* ---- one subset per query (per-request filters) -------------------------------------------------
+ * The crate's search_batch takes ONE subset because it batches inside one request; a GPU service batches ACROSS requests, and
+ * each request brings its own filter.  These entry points take, per batch,
+ *   subset_ids / subset_offsets   n_subsets distinct subsets in CSR form: subset s owns subset_ids[subset_offsets[s] ..
+ *                                 subset_offsets[s + 1]); subset_offsets has n_subsets + 1 entries, starts at 0 and never
+ *                                 decreases
+ *   query_subset                  [B]: the subset of query i, or -1 for none
+ * and give query i exactly what the single-subset call returns for query i and its subset alone (search.rs:350-382 and
+ * :434-437 on the dense path, :542-545 -- candidate retain only -- where K > centroid_batch_size): duplicate ids, ids outside
+ * [0, num_documents) and the subset's length as given count as they do there, an empty subset empties that query's result and
+ * no other, and a query with -1 is searched as in a batch without subsets.  Queries that share a filter should share one
+ * subset: its bitmaps are built once per pass, not once per query.  n_subsets == 0 is a batch without subsets.  The
+ * single-subset calls above are the case n_subsets = 1 with every query mapped to subset 0; all of them run the same pass.
+ * A pass in which any query has a subset plans its candidate pool for num_documents per query and runs without the
+ * zeroth filter level, as a single-subset pass does -- also for its queries without one.
+ * Errors, before any launch (NP_ERR_INVALID_ARGUMENT): subset_offsets[0] != 0 or decreasing offsets; a NULL array with a
+ * positive count (n_subsets > 0 without offsets or query_subset, ids counted without subset_ids); a query_subset entry
+ * < -1 or >= n_subsets.  The last is checked only where query_subset is a host array: on the device-side entry points an
+ * entry outside [0, n_subsets) reads as -1. */
+int np_hip_search_batch_subsets(const np_index* index, const float* queries, const int32_t* q_tok_offsets,
+                                int32_t B, int32_t dim, const np_search_params* params,
+                                const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                                const int32_t* query_subset,
+                                int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+/* The same with every buffer in HBM; the offsets are passed twice, on the device and as a host copy (as the queries' token
+ * offsets are).  Enqueues on `stream` and returns. */
+int np_hip_search_batch_subsets_device(const np_index* index, const float* d_queries,
+                                       const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets,
+                                       int32_t B, int32_t dim, const np_search_params* params,
+                                       const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                       const int64_t* h_subset_offsets, int64_t n_subsets,
+                                       const int32_t* d_query_subset,
+                                       int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                       void* stream);
+
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best
  * n_sel = min(n_full_scores, max(n_full_scores/4, top_k)) candidates as 64-bit rank keys in
@@ -289,6 +324,19 @@ int np_hip_subset_eligible(const np_index* index, const int64_t* d_subset, int64
                            void* stream);
 int np_hip_or_bitmaps(const np_index* index, const uint32_t* d_all, int32_t G, int64_t words, uint32_t* d_out,
                       void* stream);
+/* One subset per query, for hosts that run the phases themselves: np_hip_subsets_eligible writes this shard's bitmaps of
+ * all n_subsets subsets, d_elig_bits[n_subsets][np_hip_elig_words()], in one launch; the host all-gathers them (one
+ * all-gather, n_subsets times wider), np_hip_or_bitmaps combines d_all[G][n_subsets * words] (it ORs any word count) and the
+ * result goes into np_hip_search_phase_a_subsets as d_elig_global (NULL = the local bitmaps).  Phase B, np_hip_search_end and
+ * the merge are the ones below. */
+int np_hip_subsets_eligible(const np_index* index, const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                            const int64_t* h_subset_offsets, int64_t n_subsets, uint32_t* d_elig_bits, void* stream);
+int np_hip_search_phase_a_subsets(const np_index* index, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                  const int32_t* h_q_tok_offsets, int32_t B, int32_t dim,
+                                  const np_search_params* params, const int64_t* d_subset_ids,
+                                  const int64_t* d_subset_offsets, const int64_t* h_subset_offsets, int64_t n_subsets,
+                                  const int32_t* d_query_subset, const uint32_t* d_elig_global, uint64_t* d_sel_keys,
+                                  void* stream, void** call_state);
 int np_hip_search_phase_b(const np_index* index, void* call_state, const uint64_t* d_cut,
                           int64_t* d_out_ids, float* d_out_scores, uint64_t* d_out_keys,
                           int32_t* d_out_counts, void* stream);
@@ -362,6 +410,16 @@ int np_hip_search_batch_sharded(const np_index* index, np_comm* comm, const floa
                                 const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B, int32_t dim,
                                 const np_search_params* params, const int64_t* d_subset, int64_t subset_len,
                                 int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+
+/* np_hip_search_batch_sharded with one subset per query (see np_hip_search_batch_subsets): the eligible bitmaps of all
+ * n_subsets subsets are OR-ed over the ranks in the one all-gather the single-subset call has, n_subsets times wider.  All
+ * ranks pass the same subsets and the same map. */
+int np_hip_search_batch_sharded_subsets(const np_index* index, np_comm* comm, const float* d_queries,
+                                        const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                        int32_t dim, const np_search_params* params, const int64_t* d_subset_ids,
+                                        const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                        int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids,
+                                        float* d_out_scores, int32_t* d_out_counts, void* stream);
 
 /* Host-only validation of an index directory: parses and checks every file exactly as np_hip_index_open
  * does (MmapIndex::load, index.rs:1026-1139; NPY headers mmap.rs:659-749; fast-plaid dtypes mmap.rs:1780-1808)

@@ -8,6 +8,7 @@
 //   next_plaid::MmapIndex::load(path)                      index.rs:1026
 //   index.search(query, n_tokens, params, subset)          index.rs:1258  -> QueryResult, query_id = 0
 //   index.search_batch(queries, params, parallel, subset)  index.rs:1279  -> query_id = batch position
+//   index.search_batch_subsets(queries, n, params, parallel, subsets)   one subset per query (a server's batch of requests)
 //   SearchParameters (defaults search.rs:58-69), QueryResult (search.rs:71-80), Error (error.rs:9-66)
 //
 // Accelerator policy (the crate's precedent for its CUDA feature, lib.rs:71-84 and cuda.rs:52-182):
@@ -353,7 +354,61 @@ class MmapIndex {
   // parallel = true a failing search yields empty results instead of an error (search.rs:656-660).
   std::vector<QueryResult> search_batch(const Query* queries, size_t n, const SearchParameters& params, bool parallel,
                                         const std::vector<int64_t>* subset = nullptr) const {
-    if (!h_) return cpu_search(queries, n, params, parallel, subset);
+    return run_batch(
+        queries, n, params, parallel,
+        [&](const float* flat, const int32_t* off, const np_search_params* p, int64_t* ids, float* sc, int32_t* cnt) {
+          return np_hip_search_batch(h_, flat, off, (int32_t)n, (int32_t)embedding_dim(), p, subset ? subset->data() : nullptr,
+                                     subset ? (int64_t)subset->size() : -1, ids, sc, cnt, &last_stats);
+        },
+        [&] { return cpu_search(queries, n, params, parallel, subset); });
+  }
+
+  // One subset per query (np_hip_search_batch_subsets): subsets[i] is query i's, or nullptr for none; query i gets what
+  // search(queries[i], params, subsets[i]) returns.  Entries that point to the SAME vector share one subset (its bitmaps are
+  // built once); contents are never compared.  The CPU fallback takes one subset per call: it is called once per query.
+  std::vector<QueryResult> search_batch_subsets(const Query* queries, size_t n, const SearchParameters& params, bool parallel,
+                                                const std::vector<const std::vector<int64_t>*>& subsets) const {
+    if (subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_batch_subsets: one subset entry per query");
+    std::vector<const std::vector<int64_t>*> distinct;
+    std::vector<int32_t> qsub(n, -1);
+    for (size_t i = 0; i < n; ++i) {
+      if (!subsets[i]) continue;
+      size_t j = 0;
+      while (j < distinct.size() && distinct[j] != subsets[i]) ++j;
+      if (j == distinct.size()) distinct.push_back(subsets[i]);
+      qsub[i] = (int32_t)j;
+    }
+    std::vector<int64_t> soff(distinct.size() + 1, 0), sids;
+    for (size_t j = 0; j < distinct.size(); ++j) {
+      sids.insert(sids.end(), distinct[j]->begin(), distinct[j]->end());
+      soff[j + 1] = (int64_t)sids.size();
+    }
+    return run_batch(
+        queries, n, params, parallel,
+        [&](const float* flat, const int32_t* off, const np_search_params* p, int64_t* ids, float* sc, int32_t* cnt) {
+          return np_hip_search_batch_subsets(h_, flat, off, (int32_t)n, (int32_t)embedding_dim(), p, sids.data(), soff.data(),
+                                             (int64_t)distinct.size(), qsub.data(), ids, sc, cnt, &last_stats);
+        },
+        [&] {
+          std::vector<QueryResult> out;
+          for (size_t i = 0; i < n; ++i) {
+            auto r = cpu_search(queries + i, 1, params, parallel, subsets[i]);
+            QueryResult one;   // a hook that answers a failed query with nothing: an empty result (search.rs:656-660)
+            if (!r.empty()) one = std::move(r[0]);
+            one.query_id = i;
+            out.push_back(std::move(one));
+          }
+          return out;
+        });
+  }
+
+ private:
+  // The body of every batch call: pack the queries, `call` the library, apply the error and fallback policy (`cpu`: this
+  // batch on the CPU hand-off), unpack.
+  template <class Call, class Cpu>
+  std::vector<QueryResult> run_batch(const Query* queries, size_t n, const SearchParameters& params, bool parallel, Call&& call,
+                                     Cpu&& cpu) const {
+    if (!h_) return cpu();
     const size_t dim = embedding_dim();
     std::vector<int32_t> off(n + 1, 0);
     for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
@@ -365,15 +420,13 @@ class MmapIndex {
     std::vector<float> sc(std::max<size_t>(n * k, 1));
     std::vector<int32_t> cnt(std::max<size_t>(n, 1));
     np_search_params p = params.c();
-    int rc = np_hip_search_batch(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, &p,
-                                 subset ? subset->data() : nullptr, subset ? (int64_t)subset->size() : -1, ids.data(),
-                                 sc.data(), cnt.data(), &last_stats);
+    int rc = call(flat.data(), off.data(), &p, ids.data(), sc.data(), cnt.data());
     std::vector<QueryResult> out(n);
     for (size_t i = 0; i < n; ++i) out[i].query_id = i;
     if (rc != NP_OK) {
       if (is_device_failure(rc)) {   // mid-flight device loss: flag it, hand this call to the CPU unless FORCE_GPU
         if (rc == NP_ERR_DEVICE_UNAVAILABLE) mark_hip_broken();   // an OutOfMemory of one call leaves the device usable
-        if (!is_force_gpu() && cpu_fallback()) return cpu_search(queries, n, params, parallel, subset);
+        if (!is_force_gpu() && cpu_fallback()) return cpu();
       }
       if (parallel && rc == NP_ERR_SEARCH) return out;
       check(rc);
@@ -387,6 +440,7 @@ class MmapIndex {
     return out;
   }
 
+ public:
   // index.rs:1197-1245 decompress_documents: (embeddings [sum len, dim], lengths)
   std::pair<std::vector<float>, std::vector<int64_t>> decompress_documents(const std::vector<int64_t>& doc_ids) const {
     require_device("decompress_documents");

@@ -278,12 +278,21 @@ static uint64_t gathered_failure(const char* h_all, size_t rec, size_t off_statu
   return 0;
 }
 
-extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const float* d_queries,
-                                           const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
-                                           int32_t dim, const np_search_params* params, const int64_t* d_subset,
-                                           int64_t subset_len, int64_t* d_out_ids, float* d_out_scores,
-                                           int32_t* d_out_counts, void* stream) {
-  clear_error();
+// The subsets of a sharded call: the single-subset form (off == NULL: d_ids[len], len < 0 = None) or the CSR form with one
+// subset per query.  Either way the shards' eligible bitmaps -- one row per subset -- cross the ranks in ONE all-gather.
+struct ShardSubsets {
+  const int64_t* d_ids;
+  int64_t len;
+  const int64_t *d_off, *h_off;
+  int64_t n;
+  const int32_t* d_qsub;
+  int64_t rows() const { return h_off ? n : (len > 0 ? 1 : 0); }   // eligible bitmaps to exchange
+};
+
+static int search_batch_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                const ShardSubsets& ss, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                void* stream) {
   if (!ix || !c || !params || !stream) {
     set_error("search_batch_sharded: NULL index / communicator / params / stream (the collectives need the caller's stream)");
     return NP_ERR_INVALID_ARGUMENT;
@@ -313,16 +322,17 @@ extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const
   // gather 1 and returns NP_ERR_SEARCH there (flag NP_COMM_DEFERRED_STATUS keeps the device-side propagation).
   // What stays fatal is a failure to reserve the communicator's own few-hundred-KB buffers, before the first collective.
   const bool batched = params->centroid_batch_size > 0 && ix->K > params->centroid_batch_size;
-  const bool need_elig = subset_len > 0 && !batched;
+  const int64_t S = ss.rows();
+  const bool need_elig = S > 0 && !batched;
   const size_t o_keys = (size_t)B * k1 * 8, o_sc = o_keys * 2, o_cnt = o_sc + (size_t)B * k1 * 4;
   const size_t o_st2 = (o_cnt + (size_t)B * 4 + 15) / 16 * 16, rec2 = o_st2 + 16;
   const size_t o_st1 = (size_t)B * ns1 * 8, rec1 = o_st1 + 16;
   const int64_t words = np_hip_elig_words(ix);
   {
     if (need_elig) {
-      NP_TRY(c->elig_local.reserve((size_t)words * 4));
-      NP_TRY(c->elig_all.reserve((size_t)G * words * 4));
-      NP_TRY(c->elig_global.reserve((size_t)words * 4));
+      NP_TRY(c->elig_local.reserve((size_t)S * words * 4));
+      NP_TRY(c->elig_all.reserve((size_t)G * S * words * 4));
+      NP_TRY(c->elig_global.reserve((size_t)S * words * 4));
     }
     NP_TRY(c->keys_local.reserve(rec1));
     NP_TRY(c->keys_all.reserve((size_t)G * rec1));
@@ -348,18 +358,22 @@ extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const
   // ---- eligible centroids of the subset, OR-ed over the shards (dense path only: search.rs:350-364 vs :542-545)
   const uint32_t* elig = nullptr;
   if (need_elig) {
-    if (!local(np_hip_subset_eligible(ix, d_subset, subset_len, c->elig_local.as<uint32_t>(), st)))
-      (void)hipMemsetAsync(c->elig_local.p, 0, (size_t)words * 4, st);
-    NP_TRY(all_gather(c, c->elig_local.p, c->elig_all.p, (size_t)words * 4, st));
-    local(np_hip_or_bitmaps(ix, c->elig_all.as<uint32_t>(), G, words, c->elig_global.as<uint32_t>(), st));
+    if (!local(ss.h_off ? np_hip_subsets_eligible(ix, ss.d_ids, ss.d_off, ss.h_off, ss.n, c->elig_local.as<uint32_t>(), st)
+                        : np_hip_subset_eligible(ix, ss.d_ids, ss.len, c->elig_local.as<uint32_t>(), st)))
+      (void)hipMemsetAsync(c->elig_local.p, 0, (size_t)S * words * 4, st);
+    NP_TRY(all_gather(c, c->elig_local.p, c->elig_all.p, (size_t)S * words * 4, st));
+    local(np_hip_or_bitmaps(ix, c->elig_all.as<uint32_t>(), G, S * words, c->elig_global.as<uint32_t>(), st));
     elig = c->elig_global.as<uint32_t>();
   }
 
   // ---- phase A + gather 1 + cut
   void* state = nullptr;
   if (rc == NP_OK)
-    local(np_hip_search_phase_a(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, d_subset, subset_len,
-                                elig, c->keys_local.as<uint64_t>(), st, &state));
+    local(ss.h_off ? np_hip_search_phase_a_subsets(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss.d_ids,
+                                                   ss.d_off, ss.h_off, ss.n, ss.d_qsub, elig, c->keys_local.as<uint64_t>(),
+                                                   st, &state)
+                   : np_hip_search_phase_a(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss.d_ids, ss.len,
+                                           elig, c->keys_local.as<uint64_t>(), st, &state));
   struct End {
     const np_index* ix;
     void*& s;
@@ -411,4 +425,31 @@ extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const
     }
   }
   return NP_OK;
+}
+
+extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const float* d_queries,
+                                           const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                           int32_t dim, const np_search_params* params, const int64_t* d_subset,
+                                           int64_t subset_len, int64_t* d_out_ids, float* d_out_scores,
+                                           int32_t* d_out_counts, void* stream) {
+  clear_error();
+  return search_batch_sharded(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
+                              ShardSubsets{d_subset, subset_len, nullptr, nullptr, 0, nullptr}, d_out_ids, d_out_scores,
+                              d_out_counts, stream);
+}
+
+// Arguments every rank sees alike are checked before the first collective; `query_subset` lives on the device and is not.
+extern "C" int np_hip_search_batch_sharded_subsets(const np_index* ix, np_comm* c, const float* d_queries,
+                                                   const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets,
+                                                   int32_t B, int32_t dim, const np_search_params* params,
+                                                   const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                                   const int64_t* h_subset_offsets, int64_t n_subsets,
+                                                   const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                                                   int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
+  const ShardSubsets ss = n_subsets > 0 ? ShardSubsets{d_subset_ids, 0, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset}
+                                        : ShardSubsets{nullptr, -1, nullptr, nullptr, 0, nullptr};
+  return search_batch_sharded(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss, d_out_ids, d_out_scores,
+                              d_out_counts, stream);
 }

@@ -340,6 +340,10 @@ int encode_tokens_impl(const np_index* index, const float* embeddings, int64_t n
 int select_cut_strided(const DeviceIndex* ix, const uint64_t* d_all_keys, int64_t rank_stride, int64_t status_off, int G,
                        int B, int n_sel, uint64_t* d_cut, hipStream_t st);
 bool select_cut_fits(int G, int n_sel);
+// the CSR arguments of the per-query-subset entry points (np_search.hip), checked before any launch or collective
+int check_subsets(const void* ids, const int64_t* h_off, int64_t n_subsets, const void* qsub, const int32_t* h_qsub, int B);
+int check_device_subsets(const void* d_ids, const int64_t* d_off, const int64_t* h_off, int64_t n_subsets, const void* d_qsub,
+                         int B);
 int merge_packed_status(const DeviceIndex* ix, const void* d_records, int64_t record_bytes, int64_t off_keys,
                         int64_t off_scores, int64_t off_counts, int64_t off_status, uint64_t* h_status, int G, int B,
                         int top_k, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, hipStream_t st);

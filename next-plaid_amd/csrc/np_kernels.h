@@ -518,9 +518,12 @@ struct ProbeP {
   int64_t K, KP;
   int LQP;
   int nprobe;              // params.n_ivf_probe
-  const int32_t* nprobe_dev;   // effective nprobe with a subset (search.rs:370-382), else NULL
-  const uint32_t* elig;    // eligible-centroid bitmap [KP/32] (search.rs:350-364), else NULL
-  const int32_t* n_elig;   // popcount of elig, else NULL
+  // per-query subsets on the dense path (search.rs:350-382), else all NULL: query b reads row qrow[b] of the three tables
+  // below, or none of them with qrow[b] < 0 (it probes like a query of a batch without subsets)
+  const int32_t* qrow;         // [B]
+  const int32_t* nprobe_dev;   // [rows] effective nprobe (search.rs:370-382)
+  const uint32_t* elig;        // [rows][KP/32] eligible-centroid bitmaps (search.rs:350-364)
+  const int32_t* n_elig;       // [rows] popcounts of elig
   int has_thr;
   float thr;
   int lds_gm;              // probe_mark_kernel<4> was launched with KP/32 * 4 * 4 bytes of dynamic LDS
@@ -584,8 +587,11 @@ __global__ void __launch_bounds__(256) probe_mark_kernel(ProbeP p) {
   const float* QCT = p.QCT + (int64_t)b * p.KP * LQP;
   const uint32_t* gm = p.gmax + (int64_t)b * G * LQP;
   uint32_t* bits = p.cellbits + (int64_t)b * G;
-  const int64_t pool = p.elig ? (int64_t)*p.n_elig : p.K;
-  const int64_t eff = p.nprobe_dev ? (int64_t)*p.nprobe_dev : (int64_t)p.nprobe;
+  // the query's own subset row: b is the block's, so the row and the three values behind it are scalar loads, once per block
+  const int row = p.qrow ? p.qrow[b] : -1;
+  const uint32_t* elig = row >= 0 ? p.elig + (int64_t)row * G : nullptr;
+  const int64_t pool = row >= 0 ? (int64_t)p.n_elig[row] : p.K;
+  const int64_t eff = row >= 0 ? (int64_t)p.nprobe_dev[row] : (int64_t)p.nprobe;
   const uint32_t n_probe = (uint32_t)min(eff, pool);  // search.rs:405
   const bool take_all = pool <= (int64_t)n_probe;
   uint32_t* tauq = p.tauq + (int64_t)b * LQP;
@@ -594,7 +600,7 @@ __global__ void __launch_bounds__(256) probe_mark_kernel(ProbeP p) {
     if (qc != 0) return;   // one block marks the whole pool
     // every pooled centroid is selected by every token (search.rs:406: len <= n_probe)
     for (int64_t w = tid; w < G; w += 256) {
-      uint32_t m = p.elig ? p.elig[w] : 0xFFFFFFFFu;
+      uint32_t m = elig ? elig[w] : 0xFFFFFFFFu;
       const int64_t c0 = w * 32;
       if (c0 + 32 > p.K) m &= (c0 >= p.K) ? 0u : ((1u << (p.K - c0)) - 1u);
       if (m) atomicOr(&bits[w], m);
@@ -680,7 +686,7 @@ __global__ void __launch_bounds__(256) probe_mark_kernel(ProbeP p) {
 #pragma unroll
           for (int j = 0; j < 32; ++j) {
             const uint32_t c = cids[j];
-            const bool ok = c != 0xFFFFFFFFu && (!p.elig || ((p.elig[c >> 5] >> (c & 31)) & 1u));
+            const bool ok = c != 0xFFFFFFFFu && (!elig || ((elig[c >> 5] >> (c & 31)) & 1u));
             keys[j] = ok ? okey(raw[j]) + 1u : 0u;
             cids[j] = ok ? c : 0u;
           }
@@ -722,7 +728,7 @@ __global__ void __launch_bounds__(256) probe_mark_kernel(ProbeP p) {
               const int64_t g = g0 + lane;
               uint32_t mine = 0;
               if (g < G && gm[g * LQP + tq] >= taug) {
-                const uint32_t em = p.elig ? p.elig[g] : 0xFFFFFFFFu;
+                const uint32_t em = elig ? elig[g] : 0xFFFFFFFFu;
                 for (int i = 0; i < 32; ++i) {
                   const int64_t c = g * 32 + i;
                   if (c < p.K && ((em >> i) & 1u)) {
@@ -749,7 +755,7 @@ __global__ void __launch_bounds__(256) probe_mark_kernel(ProbeP p) {
           for (int64_t g0 = 0; g0 < G; g0 += 64) {
             const int64_t g = g0 + lane;
             const bool gv = g < G && gm[g * LQP + tq] >= taug;
-            const uint32_t em = gv ? (p.elig ? p.elig[g] : 0xFFFFFFFFu) : 0u;
+            const uint32_t em = gv ? (elig ? elig[g] : 0xFFFFFFFFu) : 0u;
             uint32_t eqm = 0, gtm = 0;
             for (int i = 0; i < 32; ++i) {
               const int64_t c = g * 32 + i;
@@ -791,8 +797,9 @@ __global__ void __launch_bounds__(256) probe_finish_kernel(ProbeP p) {
   const float* QCT = p.QCT + (int64_t)b * p.KP * LQP;
   uint32_t* bits = p.cellbits + (int64_t)b * G;
   const uint32_t* s_tauq = p.tauq + (int64_t)b * LQP;
-  const int64_t pool = p.elig ? (int64_t)*p.n_elig : p.K;
-  const int64_t eff = p.nprobe_dev ? (int64_t)*p.nprobe_dev : (int64_t)p.nprobe;
+  const int row = p.qrow ? p.qrow[b] : -1;
+  const int64_t pool = row >= 0 ? (int64_t)p.n_elig[row] : p.K;
+  const int64_t eff = row >= 0 ? (int64_t)p.nprobe_dev[row] : (int64_t)p.nprobe;
   const uint32_t n_probe = (uint32_t)min(eff, pool);
   if (tid == 0) { s_ntmp = 0; s_nfinal = 0; }
   __syncthreads();
@@ -910,15 +917,18 @@ __global__ void __launch_bounds__(256) probe_finish_kernel(ProbeP p) {
 }
 
 // Group maxima restricted to eligible centroids (subset path): gmax[b][g][q] = max over eligible
-// members of okey(QCT[b][g*32+i][q]).  One wave per (b, g); lanes = query tokens.
+// members of okey(QCT[b][g*32+i][q]).  One wave per (b, g); lanes = query tokens.  A query without a subset keeps the
+// unmasked maxima the S1 GEMM wrote.
 __global__ void __launch_bounds__(256) masked_gmax_kernel(const float* __restrict__ QCT, int64_t KP, int64_t K, int LQP,
+                                                          const int32_t* __restrict__ qrow,
                                                           const uint32_t* __restrict__ elig,
                                                           uint32_t* __restrict__ gmax) {
   const int64_t G = KP >> 5;
   const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int b = blockIdx.y, lane = threadIdx.x & 63;
-  if (g >= G) return;
-  const uint32_t em = elig[g];
+  const int row = qrow[b];
+  if (row < 0 || g >= G) return;
+  const uint32_t em = elig[(int64_t)row * G + g];
   for (int q0 = 0; q0 < LQP; q0 += 64) {
     const int q = q0 + lane;
     if (q >= LQP) break;
@@ -932,42 +942,120 @@ __global__ void __launch_bounds__(256) masked_gmax_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// subset pre-filter (search.rs:350-382, 434-437)
+// subset pre-filter (search.rs:350-382, 434-437), one subset per query
 // ---------------------------------------------------------------------------------------------
-// one wave per subset doc: doc bitmap (shard-local) + eligible-centroid bitmap
-__global__ void __launch_bounds__(256) subset_kernel(const int64_t* __restrict__ subset, int64_t n, int64_t doc_begin,
-                                                     int64_t n_docs, const int64_t* __restrict__ doc_off,
-                                                     CodeArr codes, uint32_t* __restrict__ docbits,
-                                                     uint32_t* __restrict__ elig) {
-  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+// A batch's subsets: n distinct id lists in CSR form (ids[off[n]], off[n + 1]) and the queries' map qsub[B] (-1 = none).  A
+// pass keeps one row of its tables -- document bitmap, eligible-centroid bitmap, n_elig, effective nprobe -- per distinct
+// subset its queries reference: the row of the FIRST query of the pass with that subset (qrow[b] <= b), so the tables
+// are bounded by the pass's B rows however many subsets the batch has, and queries that share a subset share its row.
+// off == NULL: the one subset [0, total); qsub == NULL: every query maps to subset 0 (the single-subset entry points).
+struct SubsetsP {
+  const int64_t* ids;
+  const int64_t* off;
+  const int32_t* qsub;
+  int64_t n, total;
+};
+
+// the subset of query b, -1 = none (an entry outside [0, n) counts as none: the device-side entry points cannot check it)
+__device__ __forceinline__ int64_t subset_of(const SubsetsP& sp, int b) {
+  if (!sp.qsub) return 0;
+  const int64_t s = sp.qsub[b];
+  return (s < 0 || s >= sp.n) ? -1 : s;
+}
+
+// grid (x, B): qrow[b]; the first query of a subset clears its row of the document bitmaps and clears its row of the eligible
+// bitmaps or -- sharded -- fills it from row `subset` of the bitmaps OR-ed over all shards
+__global__ void __launch_bounds__(256) subset_rows_kernel(SubsetsP sp, int64_t NW, int64_t G,
+                                                          const uint32_t* __restrict__ elig_global,
+                                                          uint32_t* __restrict__ docbits, uint32_t* __restrict__ elig,
+                                                          int32_t* __restrict__ qrow) {
+  __shared__ int s_first;
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int64_t s = subset_of(sp, b);
+  if (s < 0) {
+    if (blockIdx.x == 0 && tid == 0) qrow[b] = -1;
+    return;
+  }
+  if (tid == 0) s_first = b;
+  __syncthreads();
+  if (sp.qsub) {
+    for (int c = tid; c < b; c += 256)
+      if ((int64_t)sp.qsub[c] == s) atomicMin(&s_first, c);
+  } else if (tid == 0) {
+    s_first = 0;
+  }
+  __syncthreads();
+  const int first = s_first;
+  if (blockIdx.x == 0 && tid == 0) qrow[b] = first;
+  if (first != b) return;
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t w = (int64_t)blockIdx.x * 256 + tid; w < NW; w += step) docbits[(int64_t)b * NW + w] = 0;
+  if (elig)
+    for (int64_t w = (int64_t)blockIdx.x * 256 + tid; w < G; w += step)
+      elig[(int64_t)b * G + w] = elig_global ? elig_global[s * G + w] : 0u;
+}
+
+// one wave per id of any subset, all subsets (or the id range the pass references) in one launch: the wave finds its subset
+// from the offsets and the subset's row from the map (B < 0: row = subset, the layout np_hip_subsets_eligible hands out), then marks the document in the row's
+// bitmap (shard-local) and the document's centroids in the row's eligible bitmap.  docbits / elig may be NULL.
+__global__ void __launch_bounds__(256) subset_kernel(SubsetsP sp, int64_t id_lo, int64_t id_hi, int B, int64_t doc_begin,
+                                                     int64_t n_docs,
+                                                     const int64_t* __restrict__ doc_off, CodeArr codes,
+                                                     uint32_t* __restrict__ docbits, int64_t NW,
+                                                     uint32_t* __restrict__ elig, int64_t G) {
+  const int64_t i = id_lo + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // ids [id_lo, id_hi): what the launch covers
   const int lane = threadIdx.x & 63;
-  if (i >= n) return;
-  const int64_t d = subset[i] - doc_begin;
+  if (i >= id_hi) return;
+  int64_t s = 0;
+  if (sp.off) {   // off[s] <= i < off[s + 1]: empty subsets own no id
+    int64_t hi = sp.n;
+    while (hi - s > 1) {
+      const int64_t mid = (s + hi) >> 1;
+      if (sp.off[mid] <= i) s = mid;
+      else hi = mid;
+    }
+  }
+  int64_t row = -1;
+  if (B < 0) row = s;
+  else if (!sp.qsub) row = 0;
+  else
+    for (int b0 = 0; b0 < B && row < 0; b0 += 64) {   // the first query of the pass with this subset; none: not this pass's
+      const unsigned long long m = __ballot(b0 + lane < B && (int64_t)sp.qsub[min(b0 + lane, B - 1)] == s);
+      if (m) row = b0 + (__ffsll((long long)m) - 1);
+    }
+  if (row < 0) return;
+  const int64_t d = sp.ids[i] - doc_begin;
   if (d < 0 || d >= n_docs) return;
-  if (lane == 0 && docbits) atomicOr(&docbits[d >> 5], 1u << (d & 31));
+  if (lane == 0 && docbits) atomicOr(&docbits[row * NW + (d >> 5)], 1u << (d & 31));
   if (elig) {
-    const int64_t s = doc_off[d], e = doc_off[d + 1];
-    for (int64_t t = s + lane; t < e; t += 64) {
+    const int64_t t0 = doc_off[d], t1 = doc_off[d + 1];
+    for (int64_t t = t0 + lane; t < t1; t += 64) {
       const uint32_t c = codes[t];
-      atomicOr(&elig[c >> 5], 1u << (c & 31));
+      atomicOr(&elig[row * G + (c >> 5)], 1u << (c & 31));
     }
   }
 }
 
-// n_elig + effective nprobe = clamp(nprobe * N / |subset|, nprobe, n_elig)  (search.rs:370-382)
-__global__ void __launch_bounds__(256) subset_nprobe_kernel(const uint32_t* __restrict__ elig, int64_t words,
-                                                            int nprobe, int64_t n_total, int64_t subset_len,
+// one block per row: n_elig + effective nprobe = clamp(nprobe * N / |subset|, nprobe, n_elig) from the subset's own length as
+// given (search.rs:370-382)
+__global__ void __launch_bounds__(256) subset_nprobe_kernel(SubsetsP sp, const int32_t* __restrict__ qrow,
+                                                            const uint32_t* __restrict__ elig, int64_t words,
+                                                            int nprobe, int64_t n_total,
                                                             int32_t* __restrict__ n_elig, int32_t* __restrict__ eff) {
   __shared__ int s_cnt;
+  const int b = blockIdx.x;
+  if (qrow[b] != b) return;
+  const int64_t s = subset_of(sp, b);
+  const int64_t subset_len = sp.off ? sp.off[s + 1] - sp.off[s] : sp.total;
   if (threadIdx.x == 0) s_cnt = 0;
   __syncthreads();
   int c = 0;
-  for (int64_t w = threadIdx.x; w < words; w += 256) c += __popc(elig[w]);
+  for (int64_t w = threadIdx.x; w < words; w += 256) c += __popc(elig[(int64_t)b * words + w]);
   atomicAdd(&s_cnt, c);
   __syncthreads();
   if (threadIdx.x == 0) {
     const int ne = s_cnt;
-    *n_elig = ne;
+    n_elig[b] = ne;
     long long e = nprobe;
     if (ne > 0) {
       unsigned long long scaled =
@@ -978,7 +1066,7 @@ __global__ void __launch_bounds__(256) subset_nprobe_kernel(const uint32_t* __re
       if (sc > ne) sc = ne;
       e = sc;
     }
-    *eff = (int32_t)e;
+    eff[b] = (int32_t)e;
   }
 }
 
@@ -989,9 +1077,13 @@ __global__ void __launch_bounds__(256) mark_candidates_kernel(const uint32_t* __
                                                               const int32_t* __restrict__ n_cells, int64_t KP,
                                                               const int64_t* __restrict__ ivf_off,
                                                               const uint32_t* __restrict__ ivf,
-                                                              const uint32_t* __restrict__ subset_bits, int64_t NW,
+                                                              const int32_t* __restrict__ qrow,
+                                                              const uint32_t* __restrict__ subset_rows, int64_t NW,
                                                               uint32_t* __restrict__ docbits, Counters* ctr) {
   const int b = blockIdx.y;
+  // the query's own row of the subset bitmaps, or none (a scalar load and a scalar pointer: b is the block's)
+  const int row = qrow ? qrow[b] : -1;
+  const uint32_t* subset_bits = row >= 0 ? subset_rows + (int64_t)row * NW : nullptr;
   const int nc = n_cells[b];
   uint32_t* bits = docbits + (int64_t)b * NW;
   unsigned long long ids = 0;
@@ -1022,7 +1114,8 @@ __global__ void __launch_bounds__(1024) mark_slices_kernel(const uint32_t* __res
                                                            const int32_t* __restrict__ n_cells, int64_t KP,
                                                            const int64_t* __restrict__ ivf_off,
                                                            const uint32_t* __restrict__ ivf,
-                                                           const uint32_t* __restrict__ subset_bits, int64_t NW,
+                                                           const int32_t* __restrict__ qrow,
+                                                           const uint32_t* __restrict__ subset_rows, int64_t NW,
                                                            int slice_chunks, int nchunks, uint32_t* __restrict__ docbits,
                                                            int32_t* __restrict__ chunk_counts, Counters* ctr,
                                                            int sorted_lists /* every posting list ascends: a block reads only the
@@ -1035,6 +1128,9 @@ __global__ void __launch_bounds__(1024) mark_slices_kernel(const uint32_t* __res
   __shared__ uint32_t s_items[NP_MARK_CELLS + 1];   // exclusive prefix of the lists' item counts
   __shared__ uint32_t s_wsum[16];
   const int b = blockIdx.y, sl = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the query's own row of the subset bitmaps, or none (a scalar load and a scalar pointer: b is the block's)
+  const int row = qrow ? qrow[b] : -1;
+  const uint32_t* subset_bits = row >= 0 ? subset_rows + (int64_t)row * NW : nullptr;
   const int64_t w0 = (int64_t)sl * slice_chunks * NP_CHUNK_WORDS;
   const int nw = (int)min((int64_t)slice_chunks * NP_CHUNK_WORDS, NW - w0);
   const uint32_t lo = (uint32_t)(w0 * 32), span = (uint32_t)nw * 32u;

@@ -138,8 +138,98 @@ struct CallState {
   bool timed = false;
   bool hot_timed = false;   // ev[8] .. ev[9] bracket the first filter level of round 0 (np_stats.ms_hot_level)
   bool trace = false;   // debug_trace: every candidate keeps its exact approximate score
-  const uint32_t* elig_global = nullptr;   // sharded + subset: eligible-centroid bitmap OR-ed over all shards (search.rs:350-364)
+  const uint32_t* elig_global = nullptr;   // sharded + subsets: eligible-centroid bitmaps [n_subsets][KP/32] OR-ed over all shards (search.rs:350-364)
 };
+
+// A call's subsets (search.rs:350-382, 434-437, 542-545): SubsetsP on device pointers plus what the host knows about them.
+// The single-subset entry points are the case n = 1 with every query mapped to subset 0 (no offsets, no map).
+struct Subsets {
+  SubsetsP d{nullptr, nullptr, nullptr, 0, 0};
+  bool all_empty = false;   // the host knows that every query searches an empty subset: the pass has no candidates at all
+  // host copies where the caller has them (NULL otherwise): a pass then builds only the id range its own queries reference
+  const int64_t* h_off = nullptr;
+  const int32_t* h_qsub = nullptr;
+  bool any() const { return d.n > 0; }
+  bool per_query() const { return d.n > 0 && d.qsub != nullptr; }   // one table row per query of the pass, not one in all
+  Subsets slice(int s0) const {   // the same subsets seen by queries s0 ..
+    Subsets r = *this;
+    if (r.d.qsub) r.d.qsub += s0;
+    if (r.h_qsub) r.h_qsub += s0;
+    return r;
+  }
+  // ids [lo, hi) cover every subset that queries [0, B) reference; the whole array where the host cannot tell
+  void referenced(int B, int64_t& lo, int64_t& hi) const {
+    lo = 0;
+    hi = d.total;
+    if (!h_off || !h_qsub) return;
+    lo = d.total;
+    hi = 0;
+    for (int b = 0; b < B; ++b) {
+      const int32_t q = h_qsub[b];
+      if (q < 0 || h_off[q + 1] == h_off[q]) continue;
+      lo = std::min(lo, h_off[q]);
+      hi = std::max(hi, h_off[q + 1]);
+    }
+    if (hi < lo) lo = hi = 0;
+  }
+  static Subsets single(const int64_t* d_subset, int64_t subset_len) {   // subset_len < 0: None
+    Subsets r;
+    if (subset_len < 0) return r;
+    r.d.ids = d_subset;
+    r.d.n = 1;
+    r.d.total = subset_len;
+    r.all_empty = subset_len == 0;
+    return r;
+  }
+};
+
+// The CSR arguments of the per-query-subset entry points, checked on the host before any launch.  `query_subset` is checked
+// only where it is a host array (h_qsub).
+int check_subsets(const void* ids, const int64_t* h_off, int64_t n_subsets, const void* qsub, const int32_t* h_qsub, int B) {
+  if (n_subsets < 0) {
+    set_error("Search failed: negative n_subsets");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (n_subsets == 0) return NP_OK;
+  if (!h_off) {
+    set_error("Search failed: n_subsets > 0 but subset_offsets is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (h_off[0] != 0) {
+    set_error("Search failed: subset_offsets[0] must be 0");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (int64_t i = 0; i < n_subsets; ++i)
+    if (h_off[i + 1] < h_off[i]) {
+      set_error("Search failed: subset_offsets must be non-decreasing");
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  if (h_off[n_subsets] > 0 && !ids) {
+    set_error("Search failed: subset_offsets count %lld ids but subset_ids is NULL", (long long)h_off[n_subsets]);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B > 0 && !qsub) {
+    set_error("Search failed: n_subsets > 0 but query_subset is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (int b = 0; h_qsub && b < B; ++b)
+    if (h_qsub[b] < -1 || (int64_t)h_qsub[b] >= n_subsets) {
+      set_error("Search failed: query_subset[%d] = %d is not -1 or a subset below %lld", b, h_qsub[b], (long long)n_subsets);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  return NP_OK;
+}
+
+// ... and of the device-side entry points (np_dist.hip too): the offsets come twice, `query_subset` lives on the device
+int check_device_subsets(const void* d_ids, const int64_t* d_off, const int64_t* h_off, int64_t n_subsets, const void* d_qsub,
+                         int B) {
+  NP_TRY(check_subsets(d_ids, h_off, n_subsets, d_qsub, nullptr, B));
+  if (n_subsets > 0 && !d_off) {
+    set_error("Search failed: n_subsets > 0 but the device copy of subset_offsets is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
 
 static int next_pow2(int v) {
   int p = 1;
@@ -205,7 +295,8 @@ struct WsPlan {
   int max_rounds = 1;   // rounds the host enqueues for one slice (worst case; extra rounds exit immediately)
 };
 
-static int64_t per_query_bytes(const DeviceIndex* ix, int LQP, int n_sel, int top_k) {
+// sub_rows: the pass keeps a row of the subset tables (document bitmap, eligible bitmap) per query
+static int64_t per_query_bytes(const DeviceIndex* ix, int LQP, int n_sel, int top_k, bool sub_rows = false) {
   const int64_t KP = ix->KP, G = KP / 32, NW = (ix->n_docs + 31) / 32;
   const int64_t nchunks = (NW + NP_CHUNK_WORDS - 1) / NP_CHUNK_WORDS;
   return KP * LQP * 6                      // QCT (f32) + QCU (u8, rows padded to a power of two)
@@ -219,15 +310,17 @@ static int64_t per_query_bytes(const DeviceIndex* ix, int LQP, int n_sel, int to
          + std::max<int64_t>(NW, 1) * 4    // docbits
          + std::max<int64_t>(nchunks, 1) * 4
          + (int64_t)ix->dim * LQP * 8      // Qt, Qb, Qbl
+         + (sub_rows ? std::max<int64_t>(NW, 1) * 4 + G * 4 : 0)
          + (int64_t)std::max(n_sel, 1) * 16 + (int64_t)std::max(top_k, 1) * 20 + 64;
 }
 
 // `probed_cells`: the most cells one query of the batch can take candidates from (n_ivf_probe x its tokens), 0 = unknown (a
 // subset scales n_ivf_probe on the device, search.rs:350-382): the pool and its rounds are then planned for n_docs per query.
-static WsPlan plan_workspace(const DeviceIndex* ix, int B, int LQP, const np_search_params* prm, int64_t probed_cells = 0) {
+static WsPlan plan_workspace(const DeviceIndex* ix, int B, int LQP, const np_search_params* prm, int64_t probed_cells = 0,
+                             bool sub_rows = false) {
   WsPlan w;
   const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
-  const int64_t pq = std::max<int64_t>(per_query_bytes(ix, LQP, n_sel_of(prm), prm->top_k), 1);
+  const int64_t pq = std::max<int64_t>(per_query_bytes(ix, LQP, n_sel_of(prm), prm->top_k, sub_rows), 1);
   const int64_t nd = std::max<int64_t>(ix->n_docs, 1);
   const int cap = (int)std::min<int64_t>(std::min<int64_t>(ix->opts.max_batch, NP_S4_MAXB), std::max(B, 1));
   int64_t S = std::min<int64_t>(cap, std::max<int64_t>(1, (budget * 3 / 4) / pq));   // keep >= 1/4 of the budget for the pool
@@ -436,6 +529,7 @@ struct PassPlan {
   bool can_floor = false;       // the S2 list of the two-level filter floors the rows of cold centroids
   bool ids_only = false;        // S3 hands the filter bare ids
   bool have_subset = false, use_elig = false, batched = false, s1_split = false, have_cands = false;
+  bool sub_rows_per_query = false;   // the subset tables have B rows (a map query -> subset), not one
   // the zeroth filter level: its buffers are reserved whenever it MAY run (gain_possible); whether it runs (gain_path) is
   // settled by the run / skip policy after the reservations
   bool gain_possible = false, gain_path = false, deep_wanted = false, gain_deep = false;
@@ -494,8 +588,8 @@ struct GDeep {
 
 // The slice's workspace plan under the current budget.
 static WsPlan plan_budget(const DeviceIndex* ix, Workspace& w, int B, int LQP, const np_search_params& prm,
-                          int64_t probed_cells, bool allow_grow) {
-  WsPlan plan = plan_workspace(ix, B, LQP, &prm, probed_cells);
+                          int64_t probed_cells, bool allow_grow, bool sub_rows) {
+  WsPlan plan = plan_workspace(ix, B, LQP, &prm, probed_cells, sub_rows);
   if (!ix->ws_auto) return plan;
   // The default budget was what the device had free at open.  Before a pool GROWS, and whenever the budget stands below
   // its value at open, look at what is free now: the budget covers this context's scratch AND pool, so what this context
@@ -516,7 +610,7 @@ static WsPlan plan_budget(const DeviceIndex* ix, Workspace& w, int B, int LQP, c
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
       const int64_t held = (int64_t)w.total_bytes();
       const int64_t avail = (int64_t)free_b + held - ((int64_t)1 << 30);
-      const int64_t need = plan.S * per_query_bytes(ix, LQP, n_sel_of(&prm), prm.top_k) + want * NP_POOL_ENTRY;
+      const int64_t need = plan.S * per_query_bytes(ix, LQP, n_sel_of(&prm), prm.top_k, sub_rows) + want * NP_POOL_ENTRY;
       int64_t nb = budget;
       if (avail < budget && need > avail) nb = std::max<int64_t>(avail, (int64_t)256 << 20);
       else if (below && (int64_t)free_b >= ix->ws_budget_open + ((int64_t)1 << 30)) nb = ix->ws_budget_open;
@@ -525,7 +619,7 @@ static WsPlan plan_budget(const DeviceIndex* ix, Workspace& w, int B, int LQP, c
         // race re-plans from whatever the winner stored)
         int64_t seen = budget;
         (void)ix->ws_budget.compare_exchange_strong(seen, nb, std::memory_order_relaxed);
-        plan = plan_workspace(ix, B, LQP, &prm, probed_cells);
+        plan = plan_workspace(ix, B, LQP, &prm, probed_cells, sub_rows);
       }
     }
   }
@@ -533,7 +627,7 @@ static WsPlan plan_budget(const DeviceIndex* ix, Workspace& w, int B, int LQP, c
 }
 
 // Validates the slice's token offsets, sets the call's per-pass sizes and plans the pass.
-static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff, int64_t subset_len, bool allow_grow,
+static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff, const Subsets& sub, bool allow_grow,
                      PassPlan& p) {
   const int B = cs->B;
   const np_search_params& prm = cs->prm;
@@ -562,14 +656,15 @@ static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff
   cs->LQP = LQP;
   cs->n_sel = n_sel_of(&prm);
   cs->NSELP = next_pow2(std::max(cs->n_sel, 1));
-  cs->empty_subset = (subset_len == 0);
+  cs->empty_subset = sub.all_empty;
   const int64_t KP = ix->KP;
   p.KP = KP;
   p.G = KP / 32;
   p.NW = (ix->n_docs + 31) / 32;
   p.nchunks = (int)((p.NW + NP_CHUNK_WORDS - 1) / NP_CHUNK_WORDS);
-  const int64_t probed_cells = subset_len < 0 ? (int64_t)std::max(prm.n_ivf_probe, 1) * maxLq : 0;
-  const WsPlan plan = plan_budget(ix, *cs->ctx->ws, B, LQP, prm, probed_cells, allow_grow);
+  // (a pass in which ANY query has a subset plans for n_docs per query, as a single-subset pass does)
+  const int64_t probed_cells = !sub.any() ? (int64_t)std::max(prm.n_ivf_probe, 1) * maxLq : 0;
+  const WsPlan plan = plan_budget(ix, *cs->ctx->ws, B, LQP, prm, probed_cells, allow_grow, sub.per_query());
   p.pool = std::min<int64_t>(plan.pool, (int64_t)std::max(B, 1) * std::max<int64_t>(ix->n_docs, 1));
   p.max_rounds = std::max(1, std::min(plan.max_rounds, std::max(B, 1)));
 
@@ -599,7 +694,7 @@ static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff
   // the bound's floor above the cut: tools/sim/s3_gain_sim.py), on ascending posting lists (range table built at open), with
   // the bit-plane first level behind it (it takes the candidate ids in any order) and without a subset.
   p.gain_possible = p.two_level && p.use_planes && ix->d_ivf_split.get() != nullptr && ix->tune.s3_gain &&
-                    subset_len < 0 && ix->n_docs > 0 && cs->n_sel > 0 && B > 0 &&
+                    !sub.any() && ix->n_docs > 0 && cs->n_sel > 0 && B > 0 &&
                     (int64_t)std::max(prm.n_ivf_probe, 32) * maxLq <= 16384;   // probed cells per query: the scaled gains of all
                                                                                // of them must fit a 15-bit accumulator (gain_prep_kernel)
   // the level probes on its own to depth 32 where the search stops earlier: the bound's floor falls with the depth (np_kernels.h)
@@ -618,7 +713,9 @@ static int plan_pass(const DeviceIndex* ix, CallState* cs, const int32_t* h_qoff
   p.s1_split = ix->tune.s1_split && prm.precision >= 1 && prm.centroid_batch_size > 0 &&
                ix->K > prm.centroid_batch_size && !cs->trace;
   // subset pre-filter (search.rs:350-382); the batched path only filters candidates (:542-545)
-  p.have_subset = subset_len > 0;
+  // (batch facts: they choose kernel paths and buffers; which query has a subset, and which subset, is the device's qrow[])
+  p.have_subset = sub.any() && !sub.all_empty;
+  p.sub_rows_per_query = sub.per_query();
   p.batched = prm.centroid_batch_size > 0 && ix->K > prm.centroid_batch_size;  // search.rs:337
   p.use_elig = p.have_subset && !p.batched;
   p.hshift = RB == 32 ? 2 : (RB == 64 ? 3 : (RB == 128 ? 4 : 5));
@@ -767,10 +864,11 @@ static int reserve_pass(const DeviceIndex* ix, const CallState* cs, const PassPl
   NP_TRY(w.out_keys.reserve(B * topk1 * 8));
   NP_TRY(w.out_counts.reserve(B * 4));
   NP_TRY(w.ctr.reserve(sizeof(Counters)));
-  NP_TRY(w.misc.reserve(64));
-  if (p.have_subset) {
-    NP_TRY(w.subset_bits.reserve(nw1 * 4));
-    NP_TRY(w.elig.reserve(G * 4));
+  NP_TRY(w.misc.reserve(64 + 3 * B * 4));   // qrow, n_elig, eff: [B] each
+  if (p.have_subset) {   // one row per distinct subset of the pass: at most B; the single-subset entries: one
+    const size_t rows = p.sub_rows_per_query ? B : 1;
+    NP_TRY(w.subset_bits.reserve(rows * nw1 * 4));
+    if (p.use_elig) NP_TRY(w.elig.reserve(rows * G * 4));
   }
   return NP_OK;
 }
@@ -784,8 +882,7 @@ struct Pass {
   hipStream_t st;
   const float* d_q;         // storage rows, absolute offsets
   const int32_t* d_qoff;
-  const int64_t* d_subset;
-  int64_t subset_len;
+  Subsets sub;
 
   int clear() const;
   void s1() const;
@@ -808,6 +905,10 @@ struct Pass {
   // (empty), then the ticket (-1)
   int32_t* slots(size_t i) const { return w.xcd_slots.as<int32_t>() + i * p.slot_words; }
   uint32_t* cursor(int lvl) const { return w.ub_cursor.as<uint32_t>() + (size_t)lvl * p.B; }
+  // the pass's subset rows (subset_rows_kernel): qrow[B], then per row n_elig and the effective nprobe
+  int32_t* qrow() const { return w.misc.as<int32_t>(); }
+  int32_t* n_elig() const { return w.misc.as<int32_t>() + p.B; }
+  int32_t* eff() const { return w.misc.as<int32_t>() + 2 * (size_t)p.B; }
   unsigned n_cut() const { return (unsigned)std::min<int64_t>(ix->tune.ub_ncut, std::max<int64_t>(1, ix->n_docs / 16384)); }
 };
 
@@ -882,20 +983,25 @@ void Pass::s1() const {
 // ---- subset pre-filter (search.rs:350-382); the batched path only filters candidates (:542-545)
 int Pass::subset() const {
   if (!p.have_subset) return NP_OK;
-  NP_HIP(hipMemsetAsync(w.subset_bits.p, 0, (size_t)std::max<int64_t>(p.NW, 1) * 4, st));
-  NP_HIP(hipMemsetAsync(w.elig.p, 0, (size_t)p.G * 4, st));
+  const int64_t NW = p.NW;   // the rows' stride, here and in the S3 mark kernels
   // a document shard sees only its own documents' codes: the sharded host ORs the shards' bitmaps
-  // (np_hip_subset_eligible + one small all-gather) and hands the global one in
-  const bool local_elig = p.use_elig && !cs->elig_global;
-  subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(
-      d_subset, subset_len, ix->doc_begin, ix->n_docs, ix->d_doc_offsets.get(), ix->codes(), w.subset_bits.as<uint32_t>(),
-      local_elig ? w.elig.as<uint32_t>() : nullptr);
+  // (np_hip_subsets_eligible + one small all-gather) and hands the global ones in
+  uint32_t* elig = p.use_elig ? w.elig.as<uint32_t>() : nullptr;
+  const unsigned nx = (unsigned)std::min<int64_t>(64, (std::max<int64_t>(std::max(NW, p.G), 1) + 255) / 256);
+  subset_rows_kernel<<<dim3(nx, p.B), 256, 0, st>>>(sub.d, NW, p.G, p.use_elig ? cs->elig_global : nullptr,
+                                                    w.subset_bits.as<uint32_t>(), elig, qrow());
+  // only the ids of the subsets THIS pass's queries reference, where the host has the map (a batch in several slices does
+  // not build every subset in every slice, and a slice without a filtered query launches nothing)
+  int64_t lo, hi;
+  sub.referenced(p.B, lo, hi);
+  if (hi > lo)
+    subset_kernel<<<(unsigned)((hi - lo + 3) / 4), 256, 0, st>>>(
+        sub.d, lo, hi, p.B, ix->doc_begin, ix->n_docs, ix->d_doc_offsets.get(), ix->codes(), w.subset_bits.as<uint32_t>(), NW,
+        cs->elig_global ? nullptr : elig, p.G);
   if (p.use_elig) {
-    const uint32_t* elig_bits = cs->elig_global ? cs->elig_global : w.elig.as<uint32_t>();
-    subset_nprobe_kernel<<<1, 256, 0, st>>>(elig_bits, p.G, cs->prm.n_ivf_probe, ix->N_total, subset_len,
-                                            w.misc.as<int32_t>(), w.misc.as<int32_t>() + 1);
+    subset_nprobe_kernel<<<p.B, 256, 0, st>>>(sub.d, qrow(), elig, p.G, cs->prm.n_ivf_probe, ix->N_total, n_elig(), eff());
     // the probe prunes by group maxima: restrict them to the eligible centroids
-    masked_gmax_kernel<<<dim3((unsigned)((p.G + 3) / 4), p.B), 256, 0, st>>>(w.QCT.as<float>(), p.KP, ix->K, p.LQP, elig_bits,
+    masked_gmax_kernel<<<dim3((unsigned)((p.G + 3) / 4), p.B), 256, 0, st>>>(w.QCT.as<float>(), p.KP, ix->K, p.LQP, qrow(), elig,
                                                                              w.gmax.as<uint32_t>());
   }
   return NP_OK;
@@ -914,9 +1020,10 @@ void Pass::s2() const {
   pp.KP = p.KP;
   pp.LQP = p.LQP;
   pp.nprobe = prm.n_ivf_probe;
-  pp.nprobe_dev = p.use_elig ? w.misc.as<int32_t>() + 1 : nullptr;
-  pp.elig = p.use_elig ? (cs->elig_global ? cs->elig_global : w.elig.as<uint32_t>()) : nullptr;
-  pp.n_elig = p.use_elig ? w.misc.as<int32_t>() : nullptr;
+  pp.qrow = p.use_elig ? qrow() : nullptr;
+  pp.nprobe_dev = p.use_elig ? eff() : nullptr;
+  pp.elig = p.use_elig ? w.elig.as<uint32_t>() : nullptr;
+  pp.n_elig = p.use_elig ? n_elig() : nullptr;
   pp.has_thr = prm.has_threshold;
   pp.thr = prm.centroid_score_threshold;
   pp.slab = p.batched ? (int64_t)prm.centroid_batch_size : 0;
@@ -938,7 +1045,7 @@ void Pass::s2() const {
   if (!p.gain_deep) return;
   // the zeroth level's own, deeper probe: bound-only cells beyond the search's
   const GDeep gd(w.gdeep.p, p);
-  ProbeP p2 = pp;
+  ProbeP p2 = pp;   // (no subsets here: they leave the zeroth level off)
   p2.nprobe = p.gain_depth;
   p2.has_thr = 0;          // every probed cell: the ones a threshold removes are swept as bound-only cells
   p2.cellbits = gd.marks;
@@ -1081,14 +1188,14 @@ int Pass::s3_plan(const RoundPlan& rp) const {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       mark_slices_kernel<<<dim3(nslices, B), 1024, lds, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP,
                                                               ix->d_ivf_offsets.get(), ix->d_ivf.get(),
-                                                              p.have_subset ? w.subset_bits.as<uint32_t>() : nullptr, p.NW,
+                                                              p.have_subset ? qrow() : nullptr, w.subset_bits.as<uint32_t>(), p.NW,
                                                               slice_chunks, nchunks, w.docbits.as<uint32_t>(),
                                                               w.chunk_counts.as<int32_t>(), w.ctr.as<Counters>(),
                                                               (ix->ivf_sorted && ix->tune.s3_bisect) ? 1 : 0);
     } else {
       mark_candidates_kernel<<<dim3(128, B), 256, 0, st>>>(w.cells.as<uint32_t>(), w.n_cells.as<int32_t>(), p.KP,
                                                            ix->d_ivf_offsets.get(), ix->d_ivf.get(),
-                                                           p.have_subset ? w.subset_bits.as<uint32_t>() : nullptr, p.NW,
+                                                           p.have_subset ? qrow() : nullptr, w.subset_bits.as<uint32_t>(), p.NW,
                                                            w.docbits.as<uint32_t>(), w.ctr.as<Counters>());
       count_chunks_kernel<<<dim3(nchunks, B), 256, 0, st>>>(w.docbits.as<uint32_t>(), p.NW, nchunks,
                                                             w.chunk_counts.as<int32_t>());
@@ -1341,11 +1448,11 @@ int Pass::hotp(int r, const RoundPlan& rp, unsigned nbx) const {
 
 // S1..S5 for queries [0,B) whose rows live in d_q (absolute offsets d_qoff/h_qoff).
 static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
-                        const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len, bool allow_grow) {
+                        const int32_t* h_qoff, const Subsets& sub, bool allow_grow) {
   Workspace& w = *cs->ctx->ws;
   hipStream_t st = cs->stream;
   PassPlan p;
-  NP_TRY(plan_pass(ix, cs, h_qoff, subset_len, allow_grow, p));
+  NP_TRY(plan_pass(ix, cs, h_qoff, sub, allow_grow, p));
   NP_TRY(reserve_pass(ix, cs, p, w));
   settle_zeroth_level(ix, w, cs, p);
   if (ix->ldim != ix->dim) {   // caller rows -> storage rows; everything below sees ix->dim
@@ -1354,7 +1461,7 @@ static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, 
                                                                                   ix->dim, w.qpad.as<float>());
     d_q = w.qpad.as<float>() - p.row0 * ix->dim;   // offsets stay absolute
   }
-  const Pass a{ix, cs, w, p, st, d_q, d_qoff, d_subset, subset_len};
+  const Pass a{ix, cs, w, p, st, d_q, d_qoff, sub};
   if (cs->timed) NP_HIP(hipEventRecord(cs->ctx->ev[0], st));
   NP_TRY(a.clear());
   if (p.B == 0) return NP_OK;
@@ -1381,10 +1488,10 @@ static int phase_a_once(const DeviceIndex* ix, CallState* cs, const float* d_q, 
 // with the pool released and the budget halved -- more candidate-pool rounds instead of OutOfMemory.  Every reservation of
 // a pass happens before its first launch (reserve_pass), so a failed pass leaves nothing half-done.
 static int phase_a(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
-                   const int32_t* h_qoff, const int64_t* d_subset, int64_t subset_len) {
+                   const int32_t* h_qoff, const Subsets& sub) {
   for (int attempt = 0;; ++attempt) {
     // (a retry never lets the budget grow back: the pass that just failed WAS the planned size)
-    const int rc = phase_a_once(ix, cs, d_q, d_qoff, h_qoff, d_subset, subset_len, attempt == 0);
+    const int rc = phase_a_once(ix, cs, d_q, d_qoff, h_qoff, sub, attempt == 0);
     if (rc != NP_ERR_OUT_OF_MEMORY || !ix->ws_auto || attempt >= 4) return rc;
     const int64_t b = ix->ws_budget.load(std::memory_order_relaxed);
     if (b <= ((int64_t)256 << 20)) return rc;
@@ -1493,19 +1600,19 @@ static int lqp_of(const int32_t* h_qoff, int B) {
   return std::min((max_tokens(h_qoff, B) + 31) / 32 * 32, 32 * NP_MAX_QT);
 }
 
-static int slice_size(const DeviceIndex* ix, const int32_t* h_qoff, int B, const np_search_params* prm) {
-  return std::max(1, std::min(plan_workspace(ix, B, lqp_of(h_qoff, B), prm).S, std::max(B, 1)));
+static int slice_size(const DeviceIndex* ix, const int32_t* h_qoff, int B, const np_search_params* prm, const Subsets& sub) {
+  return std::max(1, std::min(plan_workspace(ix, B, lqp_of(h_qoff, B), prm, 0, sub.per_query()).S, std::max(B, 1)));
 }
 
 // Whole batch on device buffers, sliced.  No host synchronisation.
 static int run_device(const DeviceIndex* ix, CallState* cs, const float* d_q, const int32_t* d_qoff,
-                      const int32_t* h_qoff, int B, const np_search_params* prm, const int64_t* d_subset,
-                      int64_t subset_len, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts) {
-  const int S = slice_size(ix, h_qoff, B, prm);
+                      const int32_t* h_qoff, int B, const np_search_params* prm, const Subsets& sub,
+                      int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts) {
+  const int S = slice_size(ix, h_qoff, B, prm, sub);
   for (int s0 = 0; s0 < B; s0 += S) {
     cs->B = std::min(S, B - s0);
     cs->prm = *prm;
-    NP_TRY(phase_a(ix, cs, d_q, d_qoff + s0, h_qoff + s0, d_subset, subset_len));
+    NP_TRY(phase_a(ix, cs, d_q, d_qoff + s0, h_qoff + s0, sub.slice(s0)));   // the slice builds the rows ITS queries reference
     NP_TRY(phase_b(ix, cs, d_qoff + s0, nullptr, d_out_ids + (int64_t)s0 * prm->top_k,
                    d_out_scores + (int64_t)s0 * prm->top_k, nullptr, d_out_counts + s0));
   }
@@ -1572,19 +1679,23 @@ extern "C" {
 
 int32_t np_hip_n_sel(const np_search_params* p) { return p ? n_sel_of(p) : 0; }
 
-int np_hip_search_batch_device(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+// the device-side CSR arguments as a Subsets (checked; `query_subset` lives on the device and is not)
+static int device_subsets(const int64_t* d_ids, const int64_t* d_off, const int64_t* h_off, int64_t n_subsets,
+                          const int32_t* d_qsub, int B, Subsets& sub) {
+  NP_TRY(check_device_subsets(d_ids, d_off, h_off, n_subsets, d_qsub, B));
+  if (n_subsets > 0) {
+    sub.d = SubsetsP{d_ids, d_off, d_qsub, n_subsets, h_off[n_subsets]};
+    if (!d_qsub) sub.d.qsub = nullptr;   // (np_hip_subsets_eligible: no map, row = subset)
+  }
+  return NP_OK;
+}
+
+static int search_batch_device(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
                                const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
-                               const int64_t* d_subset, int64_t subset_len, int64_t* d_out_ids, float* d_out_scores,
-                               int32_t* d_out_counts, void* stream) {
-  clear_error();
-  NP_TRY(validate(ix, B, dim, params));
-  if (B == 0) return NP_OK;
+                               const Subsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                               void* stream) {
   if (!d_queries || !d_q_tok_offsets || !h_q_tok_offsets || !d_out_counts || (params->top_k > 0 && (!d_out_ids || !d_out_scores))) {
     set_error("Search failed: NULL buffer");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  if (subset_len > 0 && !d_subset) {
-    set_error("Search failed: subset_len > 0 but subset is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
   DeviceGuard g(ix->device);
@@ -1592,26 +1703,68 @@ int np_hip_search_batch_device(const np_index* ix, const float* d_queries, const
   NP_TRY(acquire_context(ix, &cs.ctx));
   int rc = begin_use(&cs, stream);
   if (rc == NP_OK)
-    rc = run_device(ix, &cs, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, params, d_subset, subset_len, d_out_ids,
-                    d_out_scores, d_out_counts);
+    rc = run_device(ix, &cs, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, params, sub, d_out_ids, d_out_scores,
+                    d_out_counts);
   int rc2 = end_use(&cs);
   release_context(ix, cs.ctx);
   return rc != NP_OK ? rc : rc2;
 }
 
-int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
-                        const np_search_params* params, const int64_t* subset, int64_t subset_len, int64_t* out_ids,
-                        float* out_scores, int32_t* out_counts, np_stats* stats) {
+int np_hip_search_batch_device(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                               const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                               const int64_t* d_subset, int64_t subset_len, int64_t* d_out_ids, float* d_out_scores,
+                               int32_t* d_out_counts, void* stream) {
   clear_error();
-  if (stats) memset(stats, 0, sizeof *stats);
   NP_TRY(validate(ix, B, dim, params));
   if (B == 0) return NP_OK;
-  if (!queries || !q_tok_offsets || !out_counts || (params->top_k > 0 && (!out_ids || !out_scores))) {
-    set_error("Search failed: NULL buffer");
+  if (subset_len > 0 && !d_subset) {
+    set_error("Search failed: subset_len > 0 but subset is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  if (subset_len > 0 && !subset) {
-    set_error("Search failed: subset_len > 0 but subset is NULL");
+  return search_batch_device(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
+                             Subsets::single(d_subset, subset_len), d_out_ids, d_out_scores, d_out_counts, stream);
+}
+
+int np_hip_search_batch_subsets_device(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                       const int32_t* h_q_tok_offsets, int32_t B, int32_t dim,
+                                       const np_search_params* params, const int64_t* d_subset_ids,
+                                       const int64_t* d_subset_offsets, const int64_t* h_subset_offsets, int64_t n_subsets,
+                                       const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                                       int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(validate(ix, B, dim, params));
+  Subsets sub;
+  NP_TRY(device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B, sub));
+  if (B == 0) return NP_OK;
+  return search_batch_device(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, sub, d_out_ids, d_out_scores,
+                             d_out_counts, stream);
+}
+
+// A call's subsets in host memory: `sub` holds host pointers until upload() has copied them behind the queries' buffers
+struct HostSubsets {
+  Subsets sub;
+  // ids [total] i64 | offsets [n + 1] i64 | query_subset [B] i32 in w.subset, on the call's stream
+  int upload(Workspace& w, int B, hipStream_t st) {
+    SubsetsP& d = sub.d;
+    if (d.n == 0 || (d.total == 0 && !d.off)) return NP_OK;
+    const size_t ib = (size_t)d.total * 8, ob = d.off ? (size_t)(d.n + 1) * 8 : 0, qb = d.qsub ? (size_t)B * 4 : 0;
+    NP_TRY(w.subset.reserve(ib + ob + qb));
+    char* base = w.subset.as<char>();
+    if (ib) NP_HIP(hipMemcpyAsync(base, d.ids, ib, hipMemcpyHostToDevice, st));
+    if (ob) NP_HIP(hipMemcpyAsync(base + ib, d.off, ob, hipMemcpyHostToDevice, st));
+    if (qb) NP_HIP(hipMemcpyAsync(base + ib + ob, d.qsub, qb, hipMemcpyHostToDevice, st));
+    d.ids = ib ? (const int64_t*)base : nullptr;
+    if (ob) d.off = (const int64_t*)(base + ib);
+    if (qb) d.qsub = (const int32_t*)(base + ib + ob);
+    return NP_OK;
+  }
+};
+
+static int search_batch_host(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                             const np_search_params* params, HostSubsets hs, int64_t* out_ids, float* out_scores,
+                             int32_t* out_counts, np_stats* stats) {
+  if (!queries || !q_tok_offsets || !out_counts || (params->top_k > 0 && (!out_ids || !out_scores))) {
+    set_error("Search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
   }
   if (q_tok_offsets[0] != 0) {
@@ -1635,7 +1788,6 @@ int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t*
   const int topk = params->top_k;
   NP_TRY(w.q.reserve((size_t)std::max<int64_t>(ntok, 1) * dim * 4));
   NP_TRY(w.qoff.reserve((size_t)(B + 1) * 4));
-  if (subset_len > 0) NP_TRY(w.subset.reserve((size_t)subset_len * 8));
   // results of the whole batch land in one pinned staging area
   const size_t ob_ids = (size_t)B * std::max(topk, 1) * 8, ob_sc = (size_t)B * std::max(topk, 1) * 4,
                ob_cnt = (size_t)B * 4;
@@ -1646,10 +1798,10 @@ int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t*
   NP_TRY(w.out_counts.reserve(ob_cnt));
   if (ntok > 0) NP_HIP(hipMemcpyAsync(w.q.p, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(w.qoff.p, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-  if (subset_len > 0) NP_HIP(hipMemcpyAsync(w.subset.p, subset, (size_t)subset_len * 8, hipMemcpyHostToDevice, st));
+  NP_TRY(hs.upload(w, B, st));
 
   // slices: each slice's outputs go to its rows of the batch-wide output buffers
-  const int S = slice_size(ix, q_tok_offsets, B, params);
+  const int S = slice_size(ix, q_tok_offsets, B, params, hs.sub);
   np_stats acc;
   memset(&acc, 0, sizeof acc);
   char* pin = (char*)w.h_pin;
@@ -1663,8 +1815,7 @@ int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t*
     cs.timed = stats != nullptr;
     // batch-wide output buffers must survive phase_a's reserve() calls: they only grow, and were
     // reserved above for the full batch, so phase_a's per-slice reserve is a no-op for them.
-    NP_TRY(phase_a(ix, &cs, w.q.as<float>(), w.qoff.as<int32_t>() + s0, q_tok_offsets + s0,
-                   subset_len > 0 ? w.subset.as<int64_t>() : nullptr, subset_len));
+    NP_TRY(phase_a(ix, &cs, w.q.as<float>(), w.qoff.as<int32_t>() + s0, q_tok_offsets + s0, hs.sub.slice(s0)));
     NP_TRY(phase_b(ix, &cs, w.qoff.as<int32_t>() + s0, nullptr, w.out_ids.as<int64_t>() + (int64_t)s0 * topk,
                    w.out_scores.as<float>() + (int64_t)s0 * topk, nullptr, w.out_counts.as<int32_t>() + s0));
     if (stats) {
@@ -1720,27 +1871,58 @@ int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t*
   return NP_OK;
 }
 
-// ---- document-sharded two-phase call -------------------------------------------------------------------
-int np_hip_search_phase_a(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
-                          const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
-                          const int64_t* d_subset, int64_t subset_len, const uint32_t* d_elig_global,
-                          uint64_t* d_sel_keys, void* stream, void** call_state) {
+int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                        const np_search_params* params, const int64_t* subset, int64_t subset_len, int64_t* out_ids,
+                        float* out_scores, int32_t* out_counts, np_stats* stats) {
   clear_error();
-  if (!call_state) {
-    set_error("Search failed: call_state is NULL");
+  if (stats) memset(stats, 0, sizeof *stats);
+  NP_TRY(validate(ix, B, dim, params));
+  if (B == 0) return NP_OK;
+  if (subset_len > 0 && !subset) {
+    set_error("Search failed: subset_len > 0 but subset is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  *call_state = nullptr;
+  return search_batch_host(ix, queries, q_tok_offsets, B, dim, params, HostSubsets{Subsets::single(subset, subset_len)},
+                           out_ids, out_scores, out_counts, stats);
+}
+
+int np_hip_search_batch_subsets(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B,
+                                int32_t dim, const np_search_params* params, const int64_t* subset_ids,
+                                const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset,
+                                int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats) {
+  clear_error();
+  if (stats) memset(stats, 0, sizeof *stats);
   NP_TRY(validate(ix, B, dim, params));
+  NP_TRY(check_subsets(subset_ids, subset_offsets, n_subsets, query_subset, query_subset, B));
+  if (B == 0) return NP_OK;
+  HostSubsets hs;
+  // what the host can see: a batch none of whose queries has a subset is a batch without subsets, and one whose queries all
+  // search empty subsets has no candidates at all
+  bool any = false, all_empty = true;
+  for (int b = 0; n_subsets > 0 && b < B; ++b) {
+    const int32_t q = query_subset[b];
+    any = any || q >= 0;
+    all_empty = all_empty && q >= 0 && subset_offsets[q + 1] == subset_offsets[q];
+  }
+  if (any) {
+    hs.sub.d = SubsetsP{subset_ids, subset_offsets, query_subset, n_subsets, subset_offsets[n_subsets]};
+    hs.sub.all_empty = all_empty;
+    hs.sub.h_off = subset_offsets;
+    hs.sub.h_qsub = query_subset;
+  }
+  return search_batch_host(ix, queries, q_tok_offsets, B, dim, params, hs, out_ids, out_scores, out_counts, stats);
+}
+
+// ---- document-sharded two-phase call -------------------------------------------------------------------
+static int search_phase_a(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                          const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                          const Subsets& sub, const uint32_t* d_elig_global, uint64_t* d_sel_keys, void* stream,
+                          void** call_state) {
   if (!d_queries || !d_q_tok_offsets || !h_q_tok_offsets || !d_sel_keys) {
     set_error("Search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  if (subset_len > 0 && !d_subset) {
-    set_error("Search failed: subset_len > 0 but subset is NULL");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  if (B > slice_size(ix, h_q_tok_offsets, B, params)) {
+  if (B > slice_size(ix, h_q_tok_offsets, B, params, sub)) {
     set_error("Search failed: a sharded call must fit one workspace slice (B=%d); raise workspace_bytes/max_batch", B);
     return NP_ERR_SEARCH;
   }
@@ -1755,7 +1937,7 @@ int np_hip_search_phase_a(const np_index* ix, const float* d_queries, const int3
   cs->prm = *params;
   cs->elig_global = d_elig_global;
   rc = begin_use(cs, stream);
-  if (rc == NP_OK) rc = phase_a(ix, cs, d_queries, d_q_tok_offsets, h_q_tok_offsets, d_subset, subset_len);
+  if (rc == NP_OK) rc = phase_a(ix, cs, d_queries, d_q_tok_offsets, h_q_tok_offsets, sub);
   if (rc == NP_OK && cs->n_sel > 0 && B > 0) {
     hipError_t e = hipMemcpyAsync(d_sel_keys, cs->ctx->ws->sel_keys.p, (size_t)B * cs->n_sel * 8,
                                   hipMemcpyDeviceToDevice, cs->stream);
@@ -1785,6 +1967,43 @@ int np_hip_search_phase_a(const np_index* ix, const float* d_queries, const int3
   }
   *call_state = cs;
   return NP_OK;
+}
+
+int np_hip_search_phase_a(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                          const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                          const int64_t* d_subset, int64_t subset_len, const uint32_t* d_elig_global,
+                          uint64_t* d_sel_keys, void* stream, void** call_state) {
+  clear_error();
+  if (!call_state) {
+    set_error("Search failed: call_state is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  *call_state = nullptr;
+  NP_TRY(validate(ix, B, dim, params));
+  if (subset_len > 0 && !d_subset) {
+    set_error("Search failed: subset_len > 0 but subset is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return search_phase_a(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, Subsets::single(d_subset, subset_len),
+                        d_elig_global, d_sel_keys, stream, call_state);
+}
+
+int np_hip_search_phase_a_subsets(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                  const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                  const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                  const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                                  const uint32_t* d_elig_global, uint64_t* d_sel_keys, void* stream, void** call_state) {
+  clear_error();
+  if (!call_state) {
+    set_error("Search failed: call_state is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  *call_state = nullptr;
+  NP_TRY(validate(ix, B, dim, params));
+  Subsets sub;
+  NP_TRY(device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B, sub));
+  return search_phase_a(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, sub, d_elig_global, d_sel_keys,
+                        stream, call_state);
 }
 
 int np_hip_search_phase_b(const np_index* ix, void* call_state, const uint64_t* d_cut, int64_t* d_out_ids,
@@ -1825,8 +2044,35 @@ int np_hip_subset_eligible(const np_index* ix, const int64_t* d_subset, int64_t 
   hipStream_t st = (hipStream_t)stream;
   NP_HIP(hipMemsetAsync(d_elig_bits, 0, (size_t)(ix->KP / 32) * 4, st));
   if (subset_len > 0)
-    subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(d_subset, subset_len, ix->doc_begin, ix->n_docs,
-                                                                     ix->d_doc_offsets.get(), ix->codes(), nullptr, d_elig_bits);
+    subset_kernel<<<(unsigned)((subset_len + 3) / 4), 256, 0, st>>>(SubsetsP{d_subset, nullptr, nullptr, 1, subset_len}, 0, subset_len, -1,
+                                                                     ix->doc_begin, ix->n_docs, ix->d_doc_offsets.get(),
+                                                                     ix->codes(), nullptr, 0, d_elig_bits, ix->KP / 32);
+  NP_HIP(hipGetLastError());
+  return NP_OK;
+}
+
+int np_hip_subsets_eligible(const np_index* ix, const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                            const int64_t* h_subset_offsets, int64_t n_subsets, uint32_t* d_elig_bits, void* stream) {
+  clear_error();
+  if (!ix) {
+    set_error("subsets_eligible: NULL index");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  Subsets sub;
+  NP_TRY(device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, nullptr, 0, sub));
+  if (n_subsets == 0) return NP_OK;
+  if (!d_elig_bits) {
+    set_error("subsets_eligible: n_subsets > 0 but the bitmaps are NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  DeviceGuard g(ix->device);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t G = ix->KP / 32;
+  NP_HIP(hipMemsetAsync(d_elig_bits, 0, (size_t)n_subsets * G * 4, st));
+  if (sub.d.total > 0)   // row = subset
+    subset_kernel<<<(unsigned)((sub.d.total + 3) / 4), 256, 0, st>>>(sub.d, 0, sub.d.total, -1, ix->doc_begin, ix->n_docs,
+                                                                      ix->d_doc_offsets.get(), ix->codes(), nullptr, 0,
+                                                                      d_elig_bits, G);
   NP_HIP(hipGetLastError());
   return NP_OK;
 }
@@ -1952,15 +2198,14 @@ int np_hip_debug_trace(const np_index* ix, const float* query, int32_t n_tokens,
   int32_t h_off[2] = {0, n_tokens};
   NP_TRY(w.q.reserve((size_t)std::max(n_tokens, 1) * dim * 4));
   NP_TRY(w.qoff.reserve(8));
-  if (subset_len > 0) NP_TRY(w.subset.reserve((size_t)subset_len * 8));
   if (n_tokens > 0) NP_HIP(hipMemcpyAsync(w.q.p, query, (size_t)n_tokens * dim * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(w.qoff.p, h_off, 8, hipMemcpyHostToDevice, st));
-  if (subset_len > 0) NP_HIP(hipMemcpyAsync(w.subset.p, subset, (size_t)subset_len * 8, hipMemcpyHostToDevice, st));
+  HostSubsets hs{Subsets::single(subset, subset_len)};
+  NP_TRY(hs.upload(w, 1, st));
   cs.B = 1;
   cs.prm = *params;
   cs.trace = true;
-  NP_TRY(phase_a(ix, &cs, w.q.as<float>(), w.qoff.as<int32_t>(), h_off, subset_len > 0 ? w.subset.as<int64_t>() : nullptr,
-                 subset_len));
+  NP_TRY(phase_a(ix, &cs, w.q.as<float>(), w.qoff.as<int32_t>(), h_off, hs.sub));
   NP_TRY(phase_b(ix, &cs, w.qoff.as<int32_t>(), nullptr, w.out_ids.as<int64_t>(), w.out_scores.as<float>(),
                  w.out_keys.as<uint64_t>(), w.out_counts.as<int32_t>()));
   NP_TRY(end_use(&cs));

@@ -190,6 +190,8 @@ EXPORTS = [
     "np_hip_merge_packed", "np_hip_elig_words", "np_hip_subset_eligible", "np_hip_or_bitmaps",
     "np_hip_comm_unique_id", "np_hip_comm_create", "np_hip_comm_create_hosted", "np_hip_comm_status", "np_hip_comm_destroy",
     "np_hip_search_batch_sharded",
+    "np_hip_search_batch_subsets", "np_hip_search_batch_subsets_device", "np_hip_search_phase_a_subsets",
+    "np_hip_subsets_eligible", "np_hip_search_batch_sharded_subsets",
     "np_hip_decompress_documents", "np_hip_encode_tokens", "np_hip_rerank_maxsim", "np_hip_debug_trace",
     "np_hip_kmeans_plan", "np_hip_kmeans", "np_hip_compute_kmeans", "np_hip_prepare_codec_artifacts", "np_hip_index_create",
     "np_hip_index_update", "np_hip_index_update_append", "np_hip_index_delete",
@@ -285,6 +287,15 @@ def lib():
     L.np_hip_comm_destroy.restype = None
     L.np_hip_search_batch_sharded.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, i64,
                                               vp, vp, vp, vp]
+    L.np_hip_search_batch_subsets.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, vp, i64, vp, vp, vp, vp,
+                                              C.POINTER(np_stats)]
+    L.np_hip_search_batch_subsets_device.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, vp, vp, i64,
+                                                     vp, vp, vp, vp, vp]
+    L.np_hip_search_phase_a_subsets.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, vp, vp, i64, vp,
+                                                vp, vp, vp, C.POINTER(vp)]
+    L.np_hip_subsets_eligible.argtypes = [vp, vp, vp, vp, i64, vp, vp]
+    L.np_hip_search_batch_sharded_subsets.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, vp, vp,
+                                                      i64, vp, vp, vp, vp, vp]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -393,6 +404,32 @@ def device_count() -> int:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def pack_subsets(subsets, n_queries: int):
+    """One subset per query -> the CSR arguments of np_hip_search_batch_subsets: (subset_ids i64, subset_offsets i64
+    [n_subsets + 1], query_subset i32 [n_queries], -1 = none).  `subsets` has n_queries entries, each None or an array of
+    document ids.  Entries that are the SAME OBJECT share one subset (by identity; contents are never compared or hashed),
+    so a server passes one array object per distinct filter and the device builds that filter's bitmaps once.  Pure host
+    code: no device, no library."""
+    subsets = list(subsets)
+    if len(subsets) != n_queries:
+        raise ValueError(f"subsets has {len(subsets)} entries for {n_queries} queries")
+    slot, arrays = {}, []
+    qsub = np.full(n_queries, -1, np.int32)
+    for i, sub in enumerate(subsets):   # (every entry stays alive in `subsets`: an id() names one object throughout)
+        if sub is None:
+            continue
+        j = slot.get(id(sub))
+        if j is None:
+            j = slot[id(sub)] = len(arrays)
+            arrays.append(np.ascontiguousarray(sub, np.int64).reshape(-1))
+        qsub[i] = j
+    off = np.zeros(len(arrays) + 1, np.int64)
+    if arrays:
+        off[1:] = np.cumsum([a.size for a in arrays])
+    ids = np.concatenate(arrays) if arrays else np.zeros(0, np.int64)
+    return np.ascontiguousarray(ids, np.int64), off, qsub
 
 
 # ---- crate mirror ------------------------------------------------------------------------------------
@@ -919,9 +956,17 @@ class MmapIndex:
         r.query_id = 0
         return r
 
-    def search_batch(self, queries, params: SearchParameters, parallel: bool = True, subset=None):
+    def search_batch(self, queries, params: SearchParameters, parallel: bool = True, subset=None, subsets=None):
         """MmapIndex::search_batch (index.rs:1279-1287).  `parallel` only selects the reference's
-        error policy (search.rs:650-674): the GPU path always runs the batch as one pipeline pass."""
+        error policy (search.rs:650-674): the GPU path always runs the batch as one pipeline pass.
+
+        `subset` is the crate's argument: one subset for the whole batch.  `subsets` gives every query its own: a sequence
+        of len(queries) entries, each None or an array of document ids; query i gets what search(queries[i], params,
+        subsets[i]) returns.  Entries that are the same object share one subset (see pack_subsets)."""
+        if subsets is not None:
+            if subset is not None:
+                raise ValueError("search_batch takes subset= (one for the batch) or subsets= (one per query), not both")
+            return self.search_batch_csr(queries, params, *pack_subsets(subsets, len(queries)), parallel=parallel)
         flat, off = self._pack(queries)
         B = len(queries)
         k = max(int(params.top_k), 0)
@@ -934,6 +979,38 @@ class MmapIndex:
         rc = lib().np_hip_search_batch(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p),
                                        _ptr(sub), -1 if sub is None else sub.size, _ptr(ids), _ptr(sc), _ptr(cnt),
                                        C.byref(st))
+        if rc:
+            if parallel and rc == 2:  # search.rs:656-660: a failed query yields an empty result
+                return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
+            _check(rc)
+        self.last_stats = st.as_dict()
+        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy())
+                for i in range(B)]
+
+    def search_batch_csr(self, queries, params: SearchParameters, subset_ids, subset_offsets, query_subset,
+                         parallel: bool = True):
+        """np_hip_search_batch_subsets as it is: the batch's distinct subsets in CSR form and the queries' map (-1 = none).
+        The arrays reach the library as given (None = NULL; n_subsets = len(subset_offsets) - 1), so its argument checks
+        are the ones that answer."""
+        flat, off = self._pack(queries)
+        B = len(queries)
+        k = max(int(params.top_k), 0)
+        ids = np.zeros(max(B * k, 1), np.int64)
+        sc = np.zeros(max(B * k, 1), np.float32)
+        cnt = np.zeros(max(B, 1), np.int32)
+        p = params._c()
+        sid = None if subset_ids is None else np.ascontiguousarray(subset_ids, np.int64)
+        soff = None if subset_offsets is None else np.ascontiguousarray(subset_offsets, np.int64)
+        qsub = None if query_subset is None else np.ascontiguousarray(query_subset, np.int32)
+        if qsub is not None and qsub.size != B:
+            raise ValueError(f"query_subset has {qsub.size} entries for {B} queries")
+        n_sub = 0 if soff is None else soff.size - 1
+        if sid is not None and soff is not None and soff.size and int(soff[-1]) > sid.size:
+            raise ValueError(f"subset_offsets count {int(soff[-1])} ids, subset_ids has {sid.size}")
+        st = np_stats()
+        rc = lib().np_hip_search_batch_subsets(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p),
+                                               _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), _ptr(ids), _ptr(sc), _ptr(cnt),
+                                               C.byref(st))
         if rc:
             if parallel and rc == 2:  # search.rs:656-660: a failed query yields an empty result
                 return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]

@@ -25,6 +25,32 @@ import numpy as np
 from . import api
 
 
+class DeviceSubsets:
+    """One subset per query on a shard's device: api.pack_subsets' three arrays as tensors, plus the host copy of the
+    offsets the C entry points take."""
+
+    def __init__(self, torch, device, ids, off, qsub):
+        self.h_off = np.ascontiguousarray(off, np.int64)
+        self.n = self.h_off.size - 1
+        self.ids = torch.from_numpy(np.ascontiguousarray(ids, np.int64)).to(device)
+        self.off = torch.from_numpy(self.h_off).to(device)
+        self.qsub = torch.from_numpy(np.ascontiguousarray(qsub, np.int32)).to(device)
+
+    def args(self):
+        """(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset) for the *_subsets entry points"""
+        return (C.c_void_p(self.ids.data_ptr()) if self.ids.numel() else None, C.c_void_p(self.off.data_ptr()),
+                self.h_off.ctypes.data_as(C.c_void_p), self.n, C.c_void_p(self.qsub.data_ptr()))
+
+
+def _packed_subsets(subset, subsets, n_queries):
+    """The packed per-query subsets of a search_batch call, or None; subset= and subsets= exclude each other."""
+    if subsets is None:
+        return None
+    if subset is not None:
+        raise ValueError("search_batch takes subset= (one for the batch) or subsets= (one per query), not both")
+    return api.pack_subsets(subsets, n_queries)
+
+
 class HipShardBackend:
     """One shard's device work through the C ABI, on torch tensors resident on the shard's GPU."""
 
@@ -50,9 +76,17 @@ class HipShardBackend:
         return C.c_void_p(self.stream.cuda_stream)
 
     def eligible(self, d_subset):
-        """This shard's eligible-centroid bitmap for a subset (search.rs:350-364), u32 words as an int32 tensor."""
+        """This shard's eligible-centroid bitmap for a subset (search.rs:350-364), u32 words as an int32 tensor; with a
+        DeviceSubsets the bitmaps of all its subsets, [n_subsets, words], from one launch."""
         t = self.torch
         words = int(api.lib().np_hip_elig_words(self.index._h))
+        if isinstance(d_subset, DeviceSubsets):
+            ds = d_subset
+            bits = t.zeros((max(ds.n, 1), max(words, 1)), dtype=t.int32, device=self.device)
+            a = ds.args()
+            api._check(api.lib().np_hip_subsets_eligible(self.index._h, a[0], a[1], a[2], a[3], C.c_void_p(bits.data_ptr()),
+                                                         self._stream()))
+            return bits
         bits = t.zeros(max(words, 1), dtype=t.int32, device=self.device)
         api._check(api.lib().np_hip_subset_eligible(self.index._h, C.c_void_p(d_subset.data_ptr()), d_subset.numel(),
                                                     C.c_void_p(bits.data_ptr()), self._stream()))
@@ -66,6 +100,13 @@ class HipShardBackend:
         st = C.c_void_p()
         p = params._c()
         hq = np.ascontiguousarray(h_qoff, np.int32)
+        if isinstance(d_subset, DeviceSubsets):   # one subset per query; elig: [n_subsets, words], OR-ed over the shards
+            api._check(api.lib().np_hip_search_phase_a_subsets(
+                self.index._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()), hq.ctypes.data_as(C.c_void_p),
+                B, self.index.embedding_dim(), C.byref(p), *d_subset.args(),
+                None if elig is None else C.c_void_p(elig.data_ptr()), C.c_void_p(keys.data_ptr()), self._stream(),
+                C.byref(st)))
+            return keys[:, : self.n_sel(params)], (st, B, params)
         api._check(api.lib().np_hip_search_phase_a(
             self.index._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()), hq.ctypes.data_as(C.c_void_p),
             B, self.index.embedding_dim(), C.byref(p),
@@ -158,7 +199,7 @@ class ShardedSearcher:
         cbs = params.centroid_batch_size
         if subs is None or (K is not None and cbs > 0 and K() > cbs):
             return None
-        if any(s.numel() == 0 for s in subs):
+        if any(not isinstance(s, DeviceSubsets) and s.numel() == 0 for s in subs):
             return None
         t = self.torch
         local = t.stack([be.eligible(s).to(self.backends[0].device) for be, s in zip(self.backends, subs)], 0)
@@ -166,7 +207,7 @@ class ShardedSearcher:
         glob = allb[0].clone()
         for g in range(1, allb.shape[0]):
             glob |= allb[g]
-        return glob
+        return glob.contiguous()
 
     def _search(self, d_q, d_qoff, h_qoff, params, d_subset=None):
         t = self.torch
@@ -194,9 +235,11 @@ class ShardedSearcher:
         all_packed = self._all_gather(t.stack([p.to(packed[0].device) for p in packed], 0))
         return self.backends[0].merge(all_packed.to(self.backends[0].device), params.top_k)
 
-    def search_batch(self, queries, params, subset=None):
-        """Host-side convenience: numpy queries in, list of QueryResult out (rank-identical)."""
+    def search_batch(self, queries, params, subset=None, subsets=None):
+        """Host-side convenience: numpy queries in, list of QueryResult out (rank-identical).  `subsets`: one subset per
+        query, as MmapIndex.search_batch takes it."""
         t = self.torch
+        packed = _packed_subsets(subset, subsets, len(queries))
         qs = [np.ascontiguousarray(q, np.float32) for q in queries]
         off = np.zeros(len(qs) + 1, np.int32)
         off[1:] = np.cumsum([q.shape[0] for q in qs])
@@ -206,6 +249,8 @@ class ShardedSearcher:
             do = [t.from_numpy(off).to(be.device) for be in self.backends]
             ds = None if subset is None else [t.from_numpy(np.ascontiguousarray(subset, np.int64)).to(be.device)
                                               for be in self.backends]
+            if packed is not None:
+                ds = [DeviceSubsets(t, be.device, *packed) for be in self.backends]
             ids, sc, cnt = self._search(dq, do, off, params, ds)
             ids, sc, cnt = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
         return [api.QueryResult(i, ids[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(len(qs))]
@@ -312,12 +357,19 @@ class CShardedSearcher:
                        t.zeros(B, dtype=t.int32, device=self.device))
         p = params._c()
         hq = np.ascontiguousarray(h_qoff, np.int32)
-        rc = api.lib().np_hip_search_batch_sharded(
-            self.index._h, self.comm._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()),
-            hq.ctypes.data_as(C.c_void_p), B, self.index.embedding_dim(), C.byref(p),
-            None if d_subset is None else C.c_void_p(d_subset.data_ptr()), -1 if d_subset is None else d_subset.numel(),
-            C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
-            C.c_void_p(self.stream.cuda_stream))
+        if isinstance(d_subset, DeviceSubsets):   # one subset per query
+            rc = api.lib().np_hip_search_batch_sharded_subsets(
+                self.index._h, self.comm._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()),
+                hq.ctypes.data_as(C.c_void_p), B, self.index.embedding_dim(), C.byref(p), *d_subset.args(),
+                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
+                C.c_void_p(self.stream.cuda_stream))
+        else:
+            rc = api.lib().np_hip_search_batch_sharded(
+                self.index._h, self.comm._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()),
+                hq.ctypes.data_as(C.c_void_p), B, self.index.embedding_dim(), C.byref(p),
+                None if d_subset is None else C.c_void_p(d_subset.data_ptr()), -1 if d_subset is None else d_subset.numel(),
+                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
+                C.c_void_p(self.stream.cuda_stream))
         if rc != 0:
             msg = api.last_error()
             # a failed batch must not leave its status word behind for the next healthy one: drain it before raising
@@ -326,8 +378,9 @@ class CShardedSearcher:
             api._check(rc, msg)
         return out
 
-    def search_batch(self, queries, params, subset=None):
+    def search_batch(self, queries, params, subset=None, subsets=None):
         t = self.torch
+        packed = _packed_subsets(subset, subsets, len(queries))
         qs = [np.ascontiguousarray(q, np.float32) for q in queries]
         off = np.zeros(len(qs) + 1, np.int32)
         off[1:] = np.cumsum([q.shape[0] for q in qs])
@@ -335,6 +388,8 @@ class CShardedSearcher:
             dq = t.from_numpy(np.concatenate(qs, 0)).to(self.device)
             do = t.from_numpy(off).to(self.device)
             ds = None if subset is None else t.from_numpy(np.ascontiguousarray(subset, np.int64)).to(self.device)
+            if packed is not None:
+                ds = DeviceSubsets(t, self.device, *packed)
             ids, sc, cnt = self.search_batch_device(dq, do, off, params, ds)
             ids, sc, cnt = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
         self.stream.synchronize()

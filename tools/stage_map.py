@@ -23,7 +23,7 @@ STAGE = {
     "clear_regions_kernel": S1, "pad_rows_kernel": S1, "prep_queries_kernel": S1, "qc_gemm_kernel": S1, "qc_gemm_b3_kernel": S1,
     "hot_prep_kernel": S1, "hot_lam_kernel": S1,
     # ev[1] .. ev[2]: subset pre-filter, per-token top-nprobe, threshold, cell list
-    "subset_kernel": S2, "subset_nprobe_kernel": S2, "masked_gmax_kernel": S2, "probe_mark_kernel": S2, "probe_finish_kernel": S2,
+    "subset_rows_kernel": S2, "subset_kernel": S2, "subset_nprobe_kernel": S2, "masked_gmax_kernel": S2, "probe_mark_kernel": S2, "probe_finish_kernel": S2,
     # ev[2] .. ev[3]: posting-list union, round plan, compaction
     # (round 5: the hot level's thresholds / bitmaps / plane rows follow the round plan -- the hot share depends on the candidate count)
     "mark_slices_kernel": S3, "mark_candidates_kernel": S3, "count_chunks_kernel": S3, "plan_rounds_kernel": S3, "compact_kernel": S3,
