@@ -225,7 +225,8 @@ int np_hip_index_write_dir(const char* index_dir, const np_index_arrays* arrays,
  * "ub_ncut" 1..512, "s3_bisect" 0/1, "s3_gain" 0/1/2 (zeroth filter level in S3: 0 = off -- read at open too: its range table is not built --, 2 = whenever it
  * applies, 1 = the default: 2 with a run / skip policy fed by the previous batches' pruning; with a centroid_score_threshold it starts skipped),
  * "s3_gain_mult" 1..16, "s3_gain_direct" 0..64, "s1_split" 0/1 (the only knob that changes values: see INTEGRATION.md),
- * "s3_slices" 0/1, "ub_nt" 0..2, "ub_steal" >= 1, "ub_nbx" 8..256, "ub_direct" 0..16, "ub_static" 0/1, "hot_static" 0/1, "s6_xcd" 0/1, "s6_tiles" 0/1, "s6_lds" 0..2, "gemm_cpw" 1/2, "exact_rowmax" 0/1.
+ * "s3_slices" 0/1, "ub_nt" 0..2, "ub_steal" >= 1, "ub_nbx" 8..256, "ub_direct" 0..16, "ub_static" 0/1, "hot_static" 0/1, "s6_xcd" 0/1, "s6_tiles" 0/1, "s6_lds" 0..2, "gemm_cpw" 1/2, "exact_rowmax" 0/1,
+ * "scan_tiles" 1..8 (np_hip_search_exact: 32-token query tiles per workgroup), "scan_docs" >= 0 (documents per pass; 0 = what the budget holds).
  * Results are identical for every setting except "s1_split"; not synchronised with concurrent searches.  Unknown name:
  * NP_ERR_INVALID_ARGUMENT.  (A library built with -DNP_DIAGNOSTICS also accepts "s4_probe" 0..7, a phase-skipping timing
  * probe whose results are invalid; production builds reject the name and never read it from the environment.) */
@@ -300,6 +301,48 @@ int np_hip_search_batch_subsets_device(const np_index* index, const float* d_que
                                        const int32_t* d_query_subset,
                                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
                                        void* stream);
+
+/* ---- exhaustive exact search ----------------------------------------------------------------------
+ * The exact answer (no reference counterpart: the crate only reaches documents through posting lists): for query i, the
+ * top_k documents IN ITS SCOPE by exact ColBERT MaxSim on the decompressed index -- the S6 score unchanged (codec.rs:423-470
+ * decompress, maxsim.rs:281-291: non-finite similarities are ignored, a query token without a finite maximum adds 0).
+ *   scope       without subsets (n_subsets == 0, or query_subset[i] == -1): every document the handle holds; with a subset:
+ *               those of them the subset names.  Duplicate ids count once, ids outside [0, num_documents) are ignored, an
+ *               empty subset empties that query's result and no other.  The CSR arguments, their checks and their errors
+ *               are those of np_hip_search_batch_subsets.
+ *   empty docs  a document without tokens is never returned (search cannot reach one either)
+ *   count       out_counts[i] = min(top_k, non-empty documents in scope)
+ *   order       score descending, finite first (as S7; a non-finite score comes back as NaN); bit-equal scores by ascending
+ *               global id; a cut keeps the lowest ids
+ *   independent query i's result is the same, bit for bit, alone, in any batch, in any number of query slices or
+ *               document passes ("scan_tiles", "scan_docs", max_batch, workspace_bytes), and from run to run
+ *   precision   0 = exact-f32 MFMA (the ground truth; bit-equal to what np_hip_search_batch(precision = 0) gives the same
+ *               (query, document) pair); 3 = bf16 MFMA on the decompressed rows (8-bit indexes take the f32 arithmetic at
+ *               either).  1 and 2 are not offered: their QC-reuse form gathers one table value per (token, query).
+ *   limits      1 <= top_k <= 16384; at most 256 tokens per query (NP_ERR_SHAPE); dim must match the index and the index
+ *               be at most 128 wide (NP_ERR_SHAPE); another precision or top_k: NP_ERR_INVALID_ARGUMENT.  All of it is checked
+ *               before any launch.
+ *   memory      the (query, document) key table, 8 bytes per pair, comes out of the context's workspace budget: the batch
+ *               runs in slices of at most max_batch queries and in passes over the documents, merged per query on the
+ *               device; nothing is allocated outside the context's arena, and a budget that does not hold one query
+ *               and one document is NP_ERR_OUT_OF_MEMORY, not a failed launch.
+ *   stats       ms_total, ms_exact (the scan), ms_topk (selection and merge), n_exact_docs ((query, document) pairs scored),
+ *               n_exact_tokens (tokens decompressed, once per query group), n_queries; everything else 0.  With stats the
+ *               call synchronises once per pass.
+ * A sharded handle scans its own documents and returns global ids; the caller merges shards by (score descending, id
+ * ascending).  Re-entrant on a shared handle (the context checkout of np_hip_search_batch). */
+int np_hip_search_exact(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                        int32_t top_k, int32_t precision,
+                        const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                        const int32_t* query_subset,
+                        int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+/* The same with every buffer in HBM and the two offset arrays also as host copies; enqueues on `stream` and returns.  A
+ * query_subset entry outside [0, n_subsets) reads as -1 here (it cannot be checked on the host). */
+int np_hip_search_exact_device(const np_index* index, const float* d_queries, const int32_t* d_q_tok_offsets,
+                               const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, int32_t top_k, int32_t precision,
+                               const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                               const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                               int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
 
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best

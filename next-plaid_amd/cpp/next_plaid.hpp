@@ -9,6 +9,7 @@
 //   index.search(query, n_tokens, params, subset)          index.rs:1258  -> QueryResult, query_id = 0
 //   index.search_batch(queries, params, parallel, subset)  index.rs:1279  -> query_id = batch position
 //   index.search_batch_subsets(queries, n, params, parallel, subsets)   one subset per query (a server's batch of requests)
+//   index.search_exact(queries, n, top_k, precision, subset) / search_exact_subsets(...)   every document scored: the exact top-k
 //   SearchParameters (defaults search.rs:58-69), QueryResult (search.rs:71-80), Error (error.rs:9-66)
 //
 // Accelerator policy (the crate's precedent for its CUDA feature, lib.rs:71-84 and cuda.rs:52-182):
@@ -369,25 +370,14 @@ class MmapIndex {
   std::vector<QueryResult> search_batch_subsets(const Query* queries, size_t n, const SearchParameters& params, bool parallel,
                                                 const std::vector<const std::vector<int64_t>*>& subsets) const {
     if (subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_batch_subsets: one subset entry per query");
-    std::vector<const std::vector<int64_t>*> distinct;
-    std::vector<int32_t> qsub(n, -1);
-    for (size_t i = 0; i < n; ++i) {
-      if (!subsets[i]) continue;
-      size_t j = 0;
-      while (j < distinct.size() && distinct[j] != subsets[i]) ++j;
-      if (j == distinct.size()) distinct.push_back(subsets[i]);
-      qsub[i] = (int32_t)j;
-    }
-    std::vector<int64_t> soff(distinct.size() + 1, 0), sids;
-    for (size_t j = 0; j < distinct.size(); ++j) {
-      sids.insert(sids.end(), distinct[j]->begin(), distinct[j]->end());
-      soff[j + 1] = (int64_t)sids.size();
-    }
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    const size_t n_distinct = pack_subsets(subsets, qsub, soff, sids);
     return run_batch(
         queries, n, params, parallel,
         [&](const float* flat, const int32_t* off, const np_search_params* p, int64_t* ids, float* sc, int32_t* cnt) {
           return np_hip_search_batch_subsets(h_, flat, off, (int32_t)n, (int32_t)embedding_dim(), p, sids.data(), soff.data(),
-                                             (int64_t)distinct.size(), qsub.data(), ids, sc, cnt, &last_stats);
+                                             (int64_t)n_distinct, qsub.data(), ids, sc, cnt, &last_stats);
         },
         [&] {
           std::vector<QueryResult> out;
@@ -402,7 +392,65 @@ class MmapIndex {
         });
   }
 
+  // The exact answer (np_hip_search_exact; the crate has no counterpart, so there is no CPU hand-off): for every query the
+  // true top_k of its scope by exact MaxSim, every document scored.  precision 0 = exact f32, 3 = bf16 MFMA.  Scores that are
+  // bit-equal come back by ascending id.  `subset`: one scope for the whole batch (nullptr: every document).
+  std::vector<QueryResult> search_exact(const Query* queries, size_t n, size_t top_k, int precision = 0,
+                                        const std::vector<int64_t>* subset = nullptr) const {
+    return search_exact_subsets(queries, n, top_k, precision, std::vector<const std::vector<int64_t>*>(n, subset));
+  }
+  // ... with one scope per query, as search_batch_subsets takes them
+  std::vector<QueryResult> search_exact_subsets(const Query* queries, size_t n, size_t top_k, int precision,
+                                                const std::vector<const std::vector<int64_t>*>& subsets) const {
+    require_device("search_exact");
+    if (subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_exact_subsets: one subset entry per query");
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    const size_t n_distinct = pack_subsets(subsets, qsub, soff, sids);
+    const size_t dim = embedding_dim();
+    std::vector<int32_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
+    std::vector<float> flat((size_t)off[n] * dim);
+    for (size_t i = 0; i < n; ++i)
+      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+    const size_t k = std::max<size_t>(top_k, 1);
+    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
+    std::vector<float> sc(std::max<size_t>(n * k, 1));
+    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
+    check(np_hip_search_exact(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)top_k, (int32_t)precision, sids.data(),
+                              soff.data(), (int64_t)n_distinct, qsub.data(), ids.data(), sc.data(), cnt.data(), &last_stats));
+    std::vector<QueryResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].query_id = i;
+      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
+      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
+    }
+    return out;
+  }
+
  private:
+  // One subset entry per query -> the CSR arguments of the per-query-subset entry points.  Entries that point to the SAME
+  // vector share one subset; contents are never compared.  Returns the number of distinct subsets.
+  static size_t pack_subsets(const std::vector<const std::vector<int64_t>*>& subsets, std::vector<int32_t>& qsub,
+                             std::vector<int64_t>& soff, std::vector<int64_t>& sids) {
+    std::vector<const std::vector<int64_t>*> distinct;
+    qsub.assign(subsets.size(), -1);
+    for (size_t i = 0; i < subsets.size(); ++i) {
+      if (!subsets[i]) continue;
+      size_t j = 0;
+      while (j < distinct.size() && distinct[j] != subsets[i]) ++j;
+      if (j == distinct.size()) distinct.push_back(subsets[i]);
+      qsub[i] = (int32_t)j;
+    }
+    soff.assign(distinct.size() + 1, 0);
+    sids.clear();
+    for (size_t j = 0; j < distinct.size(); ++j) {
+      sids.insert(sids.end(), distinct[j]->begin(), distinct[j]->end());
+      soff[j + 1] = (int64_t)sids.size();
+    }
+    return distinct.size();
+  }
+
   // The body of every batch call: pack the queries, `call` the library, apply the error and fallback policy (`cpu`: this
   // batch on the CPU hand-off), unpack.
   template <class Call, class Cpu>

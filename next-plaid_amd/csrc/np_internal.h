@@ -239,6 +239,9 @@ struct Tuning {
                          // centroid_batch_size -- S1-S5 are then no longer bit-equal to the f32 chain (near-ties < ~1e-5 can reorder)
   int gemm_cpw = 1;      // centroid fragments per wave in S1
   int exact_rowmax = 0;  // force the row-max form of the QC-reuse S6 kernel
+  int scan_tiles = 8;    // np_hip_search_exact: 32-token query tiles a workgroup of the scan stages in LDS (whole queries are packed
+                         // up to this many tiles; a longer query takes a group of its own)
+  int scan_docs = 0;     // ... documents per pass over the index; 0 = as many as the key table's share of the workspace budget holds
 };
 
 // documents per range of the posting lists' range table (d_ivf_split) = per block of the zeroth filter level's sweep (np_kernels.h)
@@ -348,6 +351,28 @@ int merge_packed_status(const DeviceIndex* ix, const void* d_records, int64_t re
                         int64_t off_scores, int64_t off_counts, int64_t off_status, uint64_t* h_status, int G, int B,
                         int top_k, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, hipStream_t st);
 int set_status_word(const DeviceIndex* ix, uint64_t* d_word, uint64_t value, hipStream_t st);
+
+// np_search.hip, for call paths outside the search pass (np_scan.hip): a context of the handle's pool checked out for one
+// call -- begin() waits for the workspace's previous use on the call's stream, the destructor records the end of this one
+// and hands the context back.  arena() is the context's one device allocation for such a call (grown on demand, never
+// shrunk, counted in the workspace like every other buffer); pin() its pinned host staging area.
+struct ContextUse {
+  const DeviceIndex* ix = nullptr;
+  Context* ctx = nullptr;
+  hipStream_t stream = nullptr;
+  bool began = false;
+  int begin(const DeviceIndex* index, void* user_stream);
+  DevBuf& arena() const;
+  int pin(size_t bytes, void** out) const;
+  int end();   // records the end of the use now (the destructor then only releases)
+  ~ContextUse();
+};
+// the document bitmaps of a pass's subsets (subset_rows_kernel + subset_kernel without the eligible-centroid side):
+// qrow[B] = the row of query b (-1: no subset), docbits[row][NW] over the shard's documents.  CSR arguments on the device,
+// ids [lo, hi) are the ones the pass's queries reference.
+int subset_doc_rows(const DeviceIndex* ix, hipStream_t st, const int64_t* d_ids, const int64_t* d_off, const int32_t* d_qsub,
+                    int64_t n_subsets, int64_t total, int64_t lo, int64_t hi, int B, int64_t NW, uint32_t* docbits,
+                    int32_t* qrow);
 
 struct DeviceGuard {
   int prev = -1;

@@ -17,31 +17,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "np_exact.h"   // okey / unkey, the MFMA vector types, the shared decompression of S6 and the scan
 
 namespace np {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define NP_NEG_INF (-__builtin_huge_valf())
-#define NP_MAX_QT 8      // query tiles of 32 tokens (LQP <= 256); exact kernels are instantiated for 1, 2 and 8
-
-// Orderable key of search.rs:110-117's comparator: finite values keep f32::total_cmp order in
-// [0x00800000, 0xFF7FFFFF]; every non-finite value maps to 0 (all Equal, below any finite).
-__device__ __forceinline__ uint32_t okey(float x) {
-  uint32_t b = __float_as_uint(x);
-  uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((b & 0x7F800000u) == 0x7F800000u) ? 0u : k;
-}
-__device__ __forceinline__ float unkey(uint32_t k) {  // inverse for k != 0
-  uint32_t b = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-  return __uint_as_float(b);
-}
-__device__ __forceinline__ bool finitef(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ float readlane_f(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-__device__ __forceinline__ int mfma_row(int r, int kk) { return (r & 3) + 8 * (r >> 2) + 4 * kk; }
 
 // Maximum of a non-negative int over the wave, wave-uniform result.  DPP row shifts / row broadcasts on the VALU (the
 // GFX9 reduction idiom) instead of six ds_bpermute round trips through the LDS pipe per __shfl_xor butterfly.
@@ -4663,7 +4641,8 @@ __global__ void __launch_bounds__(1024) select_kernel(SelectP p) {
 // S6  exact MaxSim.  One wave walks a document in 32-token tiles.  Lane (tok = lane&31,
 // half = lane>>5) unpacks its half of the token's residual bytes, adds the centroid row, the two
 // halves exchange their sum of squares with one shuffle, and the normalised values ARE the MFMA
-// A fragment (no LDS staging of D).  S = D.Q^T accumulates on the matrix cores with tokens as
+// A fragment (no LDS staging of D).  The decompression, the row scales and the masked maxima are np_exact.h's, shared
+// with the document-major scan (np_scan.hip).  S = D.Q^T accumulates on the matrix cores with tokens as
 // MFMA rows and query tokens as columns, so the row-max over document tokens is an in-lane max.
 //   decompress: out = centroid + wlut[segment]; row /= max(||row||, 1e-12)   codec.rs:443-467
 //   maxsim:     sum_q max_t S[q,t], non-finite entries ignored                maxsim.rs:281-291
@@ -4701,19 +4680,9 @@ struct ExactP {
 
 #define NP_EXACT_DPW 4   // documents per wave
 
-template <int NBITS>
-__device__ __forceinline__ float seg_weight(const float* sW, uint32_t byte, int e) {
-  constexpr uint32_t MASK = (1u << NBITS) - 1u;
-  return sW[(byte >> (8 - NBITS * (e + 1))) & MASK];  // segment e: 0 = highest bits = first dim
-}
-
 template <int DIM, int NBITS, int NQT>
 __global__ void __launch_bounds__(256) exact_f32_kernel(ExactP p) {
   constexpr int H = DIM / 2;              // dims per lane
-  constexpr int PD = DIM * NBITS / 8;     // bytes per token
-  constexpr int PH = PD / 2;              // bytes per lane
-  constexpr int PER = 8 / NBITS;          // dims per byte
-  static_assert(PH % 4 == 0 && H % 4 == 0, "unsupported DIM/NBITS");
   extern __shared__ float smem[];
   const int LQP = p.LQP;
   float* sQ = smem;                       // [DIM][LQP]
@@ -4749,34 +4718,10 @@ __global__ void __launch_bounds__(256) exact_f32_kernel(ExactP p) {
       const bool valid = tt < len;
       const int64_t tok = off + (valid ? tt : len - 1);
       const uint32_t code = p.codes[tok];
-      const uint32_t* rp = reinterpret_cast<const uint32_t*>(p.residuals + tok * PD + kk * PH);
-      const float4* cp = reinterpret_cast<const float4*>(p.centroids + (int64_t)code * DIM + kk * H);
       float v[H];
-      float ss = 0.f;
-#pragma unroll
-      for (int w = 0; w < PH / 4; ++w) {
-        const uint32_t word = rp[w];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t byte = (word >> (8 * i)) & 0xFFu;
-#pragma unroll
-          for (int e = 0; e < PER; ++e) {
-            const int jdim = (w * 4 + i) * PER + e;
-            const float c = reinterpret_cast<const float*>(cp)[jdim];
-            const float x = c + seg_weight<NBITS>(sW, byte, e);
-            v[jdim] = x;
-            ss = fmaf(x, x, ss);
-          }
-        }
-      }
-      // 1/||row|| is applied to the MFMA output rows (S[t][q] = rn[t] * <raw_t, q>) instead of to
-      // the 64 fragment values; lane li holds rn of token t0+li, row r of this lane needs token
-      // t0 + mfma_row(r, kk).
-      const float tot = ss + __shfl_xor(ss, 32) - p.pad_ss;
-      const float rn = valid ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 0.f;
+      const float ss = unpack_row_f32<DIM, NBITS>(sW, p.centroids, p.residuals, code, tok, kk, v);
       float rrow[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) rrow[r] = __shfl(rn, mfma_row(r, kk));
+      row_scales(ss, p.pad_ss, valid, kk, rrow);
 #pragma unroll
       for (int qt = 0; qt < NQT; ++qt) {
         if (qt < nqt) {
@@ -4786,28 +4731,14 @@ __global__ void __launch_bounds__(256) exact_f32_kernel(ExactP p) {
           const float* qb = sQ + (kk * H) * LQP + qt * 32 + li;
 #pragma unroll
           for (int s = 0; s < H; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(v[s], qb[s * LQP], acc, 0, 0, 0);
-          float mm = m[qt];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int trow = t0 + mfma_row(r, kk);
-            const float x = acc[r] * rrow[r];
-            if (trow < len && finitef(x)) mm = fmaxf(mm, x);
-          }
-          m[qt] = mm;
+          m[qt] = tile_row_max(acc, rrow, t0, len, kk, m[qt]);
         }
       }
     }
     float total = 0.f;
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
-      if (qt < nqt) {
-        const float mm = fmaxf(m[qt], __shfl_xor(m[qt], 32));
-        const int nq = min(32, Lq - qt * 32);
-        for (int qi = 0; qi < nq; ++qi) {
-          const float x = readlane_f(mm, qi);
-          if (x > NP_NEG_INF) total += x;
-        }
-      }
+      if (qt < nqt) total = tile_sum(m[qt], min(32, Lq - qt * 32), total);
     }
     if (lane == 0) p.exact[oj] = total;
   }
@@ -4819,9 +4750,6 @@ __global__ void __launch_bounds__(256) exact_f32_kernel(ExactP p) {
 template <int DIM, int NBITS, int NQT>
 __global__ void __launch_bounds__(256) exact_bf16_kernel(ExactP p) {
   constexpr int NS = DIM / 16;            // MFMA k-steps
-  constexpr int PD = DIM * NBITS / 8;
-  constexpr int PER = 8 / NBITS;
-  static_assert(DIM % 16 == 0 && (NBITS == 2 || NBITS == 4), "unsupported DIM/NBITS");
   __shared__ float sW[1 << NBITS];
   const int b = blockIdx.y, tid = threadIdx.x;
   if (tid < (1 << NBITS)) sW[tid] = p.wlut[tid];
@@ -4858,35 +4786,10 @@ __global__ void __launch_bounds__(256) exact_bf16_kernel(ExactP p) {
       const bool valid = tt < len;
       const int64_t tok = off + (valid ? tt : len - 1);
       const uint32_t code = p.codes[tok];
-      const uint8_t* rp = p.residuals + tok * PD;
-      const float* cp = p.centroids + (int64_t)code * DIM;
       bf16x8 a[NS];
-      float ss = 0.f;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const int d0 = 16 * s + 8 * kk;
-        const float4 c0 = *reinterpret_cast<const float4*>(cp + d0);
-        const float4 c1 = *reinterpret_cast<const float4*>(cp + d0 + 4);
-        const float cc[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        uint32_t word;
-        if (NBITS == 4) word = *reinterpret_cast<const uint32_t*>(rp + d0 / 2);
-        else word = *reinterpret_cast<const uint16_t*>(rp + d0 / 4);
-#pragma unroll
-        for (int i = 0; i < 8 / PER; ++i) {
-          const uint32_t byte = (word >> (8 * i)) & 0xFFu;
-#pragma unroll
-          for (int e = 0; e < PER; ++e) {
-            const float x = cc[i * PER + e] + seg_weight<NBITS>(sW, byte, e);
-            a[s][i * PER + e] = (__bf16)x;   // un-normalised; rows are scaled after the MFMA
-            ss = fmaf(x, x, ss);
-          }
-        }
-      }
-      const float tot = ss + __shfl_xor(ss, 32) - p.pad_ss;
-      const float rn = valid ? 1.0f / fmaxf(sqrtf(tot), 1e-12f) : 0.f;
+      const float ss = unpack_row_bf16<DIM, NBITS>(sW, p.centroids, p.residuals, code, tok, kk, a);
       float rrow[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) rrow[r] = __shfl(rn, mfma_row(r, kk));
+      row_scales(ss, p.pad_ss, valid, kk, rrow);
 #pragma unroll
       for (int qt = 0; qt < NQT; ++qt) {
         if (qt < nqt) {
@@ -4900,28 +4803,14 @@ __global__ void __launch_bounds__(256) exact_bf16_kernel(ExactP p) {
             else bq = *reinterpret_cast<const bf16x8*>(Qb + (int64_t)(qt * 32 + li) * DIM + 16 * s + 8 * kk);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bq, acc, 0, 0, 0);
           }
-          float mm = m[qt];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int trow = t0 + mfma_row(r, kk);
-            const float x = acc[r] * rrow[r];
-            if (trow < len && finitef(x)) mm = fmaxf(mm, x);
-          }
-          m[qt] = mm;
+          m[qt] = tile_row_max(acc, rrow, t0, len, kk, m[qt]);
         }
       }
     }
     float total = 0.f;
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
-      if (qt < nqt) {
-        const float mm = fmaxf(m[qt], __shfl_xor(m[qt], 32));
-        const int nq = min(32, Lq - qt * 32);
-        for (int qi = 0; qi < nq; ++qi) {
-          const float x = readlane_f(mm, qi);
-          if (x > NP_NEG_INF) total += x;
-        }
-      }
+      if (qt < nqt) total = tile_sum(m[qt], min(32, Lq - qt * 32), total);
     }
     if (lane == 0) p.exact[oj] = total;
   }

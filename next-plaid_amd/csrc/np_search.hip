@@ -21,16 +21,17 @@ struct Workspace {
   DevBuf q, qoff, Qt, Qb, Qbl, QCT, gmax, tauq, cellbits, cells_tmp, cells, n_cells, docbits, chunk_counts, cand, cand_meta, approx, n_cand,
       cand_base, round_of, round_tab, QCU, qinv, qflag, ub, ub_hist, ub_thr, ub_cursor, q_order, xcd_slots, surv_meta, n_surv, n_list2, sel_keys, sel_doc, nsel, exact, out_ids, out_scores, out_keys, out_counts, ctr, subset,
       subset_bits, elig, misc, cut, cmaxu, chist, ub2, ub_hist2, ub_thr2, list_meta, n_l1, n_l2, qpad, planes, levels, hotbits,
-      gain, gsmall, ghist, s0_meta, s0_u, gacc, gdeep;   // zeroth filter level (gain_sweep_kernel)
+      gain, gsmall, ghist, s0_meta, s0_u, gacc, gdeep,   // zeroth filter level (gain_sweep_kernel)
+      scan;   // np_hip_search_exact's arena (np_scan.hip carves it up)
   void* h_pin = nullptr;
   size_t h_pin_cap = 0;
   unsigned long long* h_gain = nullptr;   // pinned: the zeroth level's last (candidates << 32 | kept), written by the device
   uint64_t h_gain_key = 0;                // ... and the parameters of the batch that will write (or wrote) it
   hipEvent_t done = nullptr;  // recorded at the end of every use of this workspace
   bool done_valid = false;
-  static constexpr int NBUF = 66;
+  static constexpr int NBUF = 67;
   std::array<DevBuf*, NBUF> all_bufs() {   // no heap allocation: total_bytes() runs on the search path
-    return {&q, &qoff, &Qt, &Qb, &Qbl, &QCT, &gmax, &tauq, &cellbits, &cells_tmp, &cells, &n_cells, &docbits, &chunk_counts, &cand, &cand_meta, &approx, &n_cand, &cand_base, &round_of, &round_tab, &QCU, &qinv, &qflag, &ub, &ub_hist, &ub_thr, &ub_cursor, &q_order, &xcd_slots, &surv_meta, &n_surv, &n_list2, &sel_keys, &sel_doc, &nsel, &exact, &out_ids, &out_scores, &out_keys, &out_counts, &ctr, &subset, &subset_bits, &elig, &misc, &cut, &cmaxu, &chist, &ub2, &ub_hist2, &ub_thr2, &list_meta, &n_l1, &n_l2, &qpad, &planes, &levels, &hotbits, &gain, &gsmall, &ghist, &s0_meta, &s0_u, &gacc, &gdeep};
+    return {&q, &qoff, &Qt, &Qb, &Qbl, &QCT, &gmax, &tauq, &cellbits, &cells_tmp, &cells, &n_cells, &docbits, &chunk_counts, &cand, &cand_meta, &approx, &n_cand, &cand_base, &round_of, &round_tab, &QCU, &qinv, &qflag, &ub, &ub_hist, &ub_thr, &ub_cursor, &q_order, &xcd_slots, &surv_meta, &n_surv, &n_list2, &sel_keys, &sel_doc, &nsel, &exact, &out_ids, &out_scores, &out_keys, &out_counts, &ctr, &subset, &subset_bits, &elig, &misc, &cut, &cmaxu, &chist, &ub2, &ub_hist2, &ub_thr2, &list_meta, &n_l1, &n_l2, &qpad, &planes, &levels, &hotbits, &gain, &gsmall, &ghist, &s0_meta, &s0_u, &gacc, &gdeep, &scan};
   }
   void release_all() {
     for (DevBuf* b : all_bufs()) b->release();
@@ -1616,6 +1617,49 @@ static int run_device(const DeviceIndex* ix, CallState* cs, const float* d_q, co
     NP_TRY(phase_b(ix, cs, d_qoff + s0, nullptr, d_out_ids + (int64_t)s0 * prm->top_k,
                    d_out_scores + (int64_t)s0 * prm->top_k, nullptr, d_out_counts + s0));
   }
+  return NP_OK;
+}
+
+// ---- a context checked out by a call path outside the search pass (np_scan.hip) --------------------------------------
+int ContextUse::begin(const DeviceIndex* index, void* user_stream) {
+  ix = index;
+  NP_TRY(acquire_context(ix, &ctx));
+  CallState cs;
+  cs.ctx = ctx;
+  NP_TRY(begin_use(&cs, user_stream));
+  stream = cs.stream;
+  began = true;
+  return NP_OK;
+}
+DevBuf& ContextUse::arena() const { return ctx->ws->scan; }
+int ContextUse::pin(size_t bytes, void** out) const {
+  NP_TRY(ctx->ws->pin(bytes));
+  *out = ctx->ws->h_pin;
+  return NP_OK;
+}
+int ContextUse::end() {
+  if (!began) return NP_OK;
+  began = false;
+  CallState cs;
+  cs.ctx = ctx;
+  cs.stream = stream;
+  return end_use(&cs);
+}
+ContextUse::~ContextUse() {
+  (void)end();
+  if (ctx) release_context(ix, ctx);
+}
+
+int subset_doc_rows(const DeviceIndex* ix, hipStream_t st, const int64_t* d_ids, const int64_t* d_off, const int32_t* d_qsub,
+                    int64_t n_subsets, int64_t total, int64_t lo, int64_t hi, int B, int64_t NW, uint32_t* docbits,
+                    int32_t* qrow) {
+  const SubsetsP sp{d_ids, d_off, d_qsub, n_subsets, total};
+  const unsigned nx = (unsigned)std::min<int64_t>(64, (std::max<int64_t>(NW, 1) + 255) / 256);
+  subset_rows_kernel<<<dim3(nx, (unsigned)B), 256, 0, st>>>(sp, NW, 0, nullptr, docbits, nullptr, qrow);
+  if (hi > lo)
+    subset_kernel<<<(unsigned)((hi - lo + 3) / 4), 256, 0, st>>>(sp, lo, hi, B, ix->doc_begin, ix->n_docs,
+                                                                 ix->d_doc_offsets.get(), ix->codes(), docbits, NW, nullptr, 0);
+  NP_HIP(hipGetLastError());
   return NP_OK;
 }
 

@@ -196,6 +196,7 @@ EXPORTS = [
     "np_hip_kmeans_plan", "np_hip_kmeans", "np_hip_compute_kmeans", "np_hip_prepare_codec_artifacts", "np_hip_index_create",
     "np_hip_index_update", "np_hip_index_update_append", "np_hip_index_delete",
     "np_hip_pooled_lengths", "np_hip_pool_documents",
+    "np_hip_search_exact", "np_hip_search_exact_device",
 ]
 
 _lib = None
@@ -296,6 +297,8 @@ def lib():
     L.np_hip_subsets_eligible.argtypes = [vp, vp, vp, vp, i64, vp, vp]
     L.np_hip_search_batch_sharded_subsets.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, vp, vp,
                                                       i64, vp, vp, vp, vp, vp]
+    L.np_hip_search_exact.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_search_exact_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -1018,6 +1021,50 @@ class MmapIndex:
         self.last_stats = st.as_dict()
         return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy())
                 for i in range(B)]
+
+    def search_exact(self, queries, top_k: int, precision: int = 0, subset=None, subsets=None):
+        """np_hip_search_exact: for every query the true top_k of its scope by exact MaxSim over the decompressed index,
+        every document scored (no probe, no candidates).  Scope: the whole handle, `subset` (one for the batch) or
+        `subsets` (one entry per query, None or an array of ids, as search_batch takes them through pack_subsets).
+        precision 0 = exact f32 (the ground truth), 3 = bf16 MFMA.  Ties in score come back by ascending id.  A single
+        [tokens, dim] matrix is the batch of one.  Returns QueryResults."""
+        if isinstance(queries, np.ndarray) and queries.ndim == 2:
+            queries = [queries]
+        queries = list(queries)
+        B = len(queries)
+        if subsets is not None:
+            if subset is not None:
+                raise ValueError("search_exact takes subset= (one for the batch) or subsets= (one per query), not both")
+            sid, soff, qsub = pack_subsets(subsets, B)
+        elif subset is not None:
+            sid = np.ascontiguousarray(subset, np.int64).reshape(-1)
+            soff, qsub = np.array([0, sid.size], np.int64), np.zeros(B, np.int32)
+        else:
+            sid, soff, qsub = None, None, None
+        return self.search_exact_csr(queries, top_k, precision, sid, soff, qsub)
+
+    def search_exact_csr(self, queries, top_k: int, precision: int, subset_ids, subset_offsets, query_subset):
+        """np_hip_search_exact as it is: the CSR arrays reach the library as given (None = NULL), so its checks answer."""
+        flat, off = self._pack(queries)
+        B = len(queries)
+        k = max(int(top_k), 1)
+        ids = np.zeros(max(B * k, 1), np.int64)
+        sc = np.zeros(max(B * k, 1), np.float32)
+        cnt = np.zeros(max(B, 1), np.int32)
+        sid = None if subset_ids is None else np.ascontiguousarray(subset_ids, np.int64)
+        soff = None if subset_offsets is None else np.ascontiguousarray(subset_offsets, np.int64)
+        qsub = None if query_subset is None else np.ascontiguousarray(query_subset, np.int32)
+        if qsub is not None and qsub.size != B:
+            raise ValueError(f"query_subset has {qsub.size} entries for {B} queries")
+        n_sub = 0 if soff is None else soff.size - 1
+        if sid is not None and soff is not None and soff.size and int(soff[-1]) > sid.size:
+            raise ValueError(f"subset_offsets count {int(soff[-1])} ids, subset_ids has {sid.size}")
+        st = np_stats()
+        _check(lib().np_hip_search_exact(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), int(top_k), int(precision),
+                                         _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), _ptr(ids), _ptr(sc), _ptr(cnt),
+                                         C.byref(st)))
+        self.last_stats = st.as_dict()
+        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
 
     # -- adjacent rows ---------------------------------------------------------------------------------------
     def get_document_embeddings(self, doc_id: int) -> np.ndarray:
