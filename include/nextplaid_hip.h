@@ -344,6 +344,53 @@ int np_hip_search_exact_device(const np_index* index, const float* d_queries, co
                                const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
                                int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
 
+/* ---- given pairs, with the per-token matches ---------------------------------------------------------
+ * "Why did this document match?" (no reference counterpart): query i is scored against the documents
+ * pair_docs[pair_offsets[i] .. pair_offsets[i+1]) (global ids), exactly, and every query token reports its best document
+ * token.  P = pair_offsets[B] pairs, R = sum_i n_i * Lq_i row entries.  Rows are pair-major in the order given: the row of
+ * pair p of query i starts at sum_{j<i} n_j * Lq_j + (p - pair_offsets[i]) * Lq_i and holds Lq_i entries in query-token order.
+ * out_token_sims and out_token_pos may each be NULL (the launch then skips those stores).
+ *   score       out_scores[p]: the S6 score unchanged (codec.rs:423-470 decompress, maxsim.rs:281-291).  A finite score is
+ *               bit-equal to what np_hip_search_batch(precision = 0) and np_hip_search_exact(precision = 0) give the same
+ *               pair; a non-finite total comes back as NaN, as in S7.
+ *   token sim   max over the document's tokens of the scaled similarities of that query token, non-finite entries ignored
+ *               (maxsim.rs:281-291); -inf when no document token gives a finite one.  The score equals the f32 sum of the
+ *               row's entries greater than -inf, taken in token order starting from 0.0f, bit for bit.
+ *   token pos   (i32) the lowest document-token index whose device similarity equals (==) that maximum; -1 when the sim
+ *               is -inf.  Indexes are the document's on-disk token order.  (A handle opened with NP_TOK_SORT=1 keeps each
+ *               document's tokens by centroid id: it reports on-disk indexes too, but among equal similarities the token
+ *               that comes first in its stored order.)
+ *   empty doc   a document without tokens: score 0.0, sims -inf, positions -1
+ *   shards      an id inside [0, num_documents) that the handle's shard does not hold: score NaN, sims -inf, positions -1.
+ *               The caller takes each pair from the shard that owns it.
+ *   bad ids     an id outside [0, num_documents): NP_ERR_INVALID_ARGUMENT from the host entry before any launch, naming
+ *               the first one.  The device entry cannot see them: there they read as "outside the shard".
+ *   independent pairs are independent, duplicates allowed: a pair's three outputs are the same bits alone, in any batch, at
+ *               any position of the list, in any slicing or chunking (max_batch, workspace_bytes), and from run to run
+ *   precision   0 only; another value is NP_ERR_INVALID_ARGUMENT.  A position has no meaning under bf16 rounding: by the
+ *               derived bound of tests/exact_restate.py the winner is ambiguous for 21-27 % of (pair, token) entries at
+ *               precision 3, for fewer than 0.06 % at precision 0.
+ *   limits      at most 256 tokens per query; dim must match the index and the index be at most 128 wide (both
+ *               NP_ERR_SHAPE).  pair_offsets must start at 0 and be non-decreasing (NP_ERR_INVALID_ARGUMENT).  All of it is
+ *               checked before any launch.
+ *   memory      everything comes from the context's arena, nothing else is allocated: queries run in slices of at most
+ *               max_batch, and the host entry stages ids and outputs in chunks of pairs that fit the workspace budget (a
+ *               chunk may end inside a query's list).  A budget that cannot hold one query and one pair is
+ *               NP_ERR_OUT_OF_MEMORY, not a failed launch.
+ *   stats       ms_total, ms_exact (the kernel), n_exact_docs (pairs scored: those the shard holds), n_exact_tokens
+ *               (document tokens decompressed), n_queries; everything else 0.  With stats the call synchronises per slice.
+ * Re-entrant on a shared handle (the context checkout of np_hip_search_batch). */
+int np_hip_score_pairs(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                       int32_t precision, const int64_t* pair_docs, const int64_t* pair_offsets /* [B+1] */,
+                       float* out_scores /* [P] */, float* out_token_sims /* [R] or NULL */,
+                       int32_t* out_token_pos /* [R] or NULL */, np_stats* stats);
+/* The same with every buffer in HBM and the two offset arrays also as host copies (which must agree with the device
+ * copies); enqueues on `stream` and returns. */
+int np_hip_score_pairs_device(const np_index* index, const float* d_queries, const int32_t* d_q_tok_offsets,
+                              const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, int32_t precision,
+                              const int64_t* d_pair_docs, const int64_t* d_pair_offsets, const int64_t* h_pair_offsets,
+                              float* d_out_scores, float* d_out_token_sims, int32_t* d_out_token_pos, void* stream);
+
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best
  * n_sel = min(n_full_scores, max(n_full_scores/4, top_k)) candidates as 64-bit rank keys in

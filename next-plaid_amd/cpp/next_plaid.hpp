@@ -428,6 +428,48 @@ class MmapIndex {
     return out;
   }
 
+  // Given pairs with the per-token matches (np_hip_score_pairs; no crate counterpart, no CPU hand-off): query i against the
+  // documents doc_ids[i] (global ids; duplicates allowed).  scores[p] is the S6 score of the pair -- the bits search_batch and
+  // search_exact give it at precision 0 -- and, with return_matches, token_sims / token_pos hold one row of n_tokens entries
+  // per pair: each query token's best similarity (-inf: none finite) and the lowest document-token index that reaches it (-1).
+  struct PairScores {
+    std::vector<float> scores;        // [n_i]
+    std::vector<float> token_sims;    // [n_i][n_tokens of query i], or empty
+    std::vector<int32_t> token_pos;   // ...
+  };
+  std::vector<PairScores> score_pairs(const Query* queries, size_t n, const std::vector<std::vector<int64_t>>& doc_ids,
+                                      bool return_matches = true, int precision = 0) const {
+    require_device("score_pairs");
+    if (doc_ids.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "score_pairs: one list of document ids per query");
+    const size_t dim = embedding_dim();
+    std::vector<int32_t> off(n + 1, 0);
+    std::vector<int64_t> poff(n + 1, 0), roff(n + 1, 0), ids;
+    for (size_t i = 0; i < n; ++i) {
+      off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
+      poff[i + 1] = poff[i] + (int64_t)doc_ids[i].size();
+      roff[i + 1] = roff[i] + (int64_t)(doc_ids[i].size() * queries[i].n_tokens);
+      ids.insert(ids.end(), doc_ids[i].begin(), doc_ids[i].end());
+    }
+    std::vector<float> flat((size_t)off[n] * dim);
+    for (size_t i = 0; i < n; ++i)
+      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+    std::vector<float> sc(std::max<size_t>((size_t)poff[n], 1)), sims(return_matches ? std::max<size_t>((size_t)roff[n], 1) : 0);
+    std::vector<int32_t> pos(sims.size());
+    ids.resize(std::max<size_t>(ids.size(), 1));
+    check(np_hip_score_pairs(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)precision, ids.data(), poff.data(),
+                             sc.data(), return_matches ? sims.data() : nullptr, return_matches ? pos.data() : nullptr,
+                             &last_stats));
+    std::vector<PairScores> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].scores.assign(sc.begin() + poff[i], sc.begin() + poff[i + 1]);
+      if (return_matches) {
+        out[i].token_sims.assign(sims.begin() + roff[i], sims.begin() + roff[i + 1]);
+        out[i].token_pos.assign(pos.begin() + roff[i], pos.begin() + roff[i + 1]);
+      }
+    }
+    return out;
+  }
+
  private:
   // One subset entry per query -> the CSR arguments of the per-query-subset entry points.  Entries that point to the SAME
   // vector share one subset; contents are never compared.  Returns the number of distinct subsets.

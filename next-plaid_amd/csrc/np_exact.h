@@ -130,6 +130,22 @@ __device__ __forceinline__ float tile_row_max(const f32x16& acc, const float (&r
   return mm;
 }
 
+// The same with the position of the maximum (np_pairs.hip): mm takes tile_row_max's very updates, so it holds the same
+// bits; pos = the document token that first reached it.  mfma_row(r, kk) ascends in r and tiles ascend, so with the strict
+// `>` the lowest index of this lane's rows wins, within a tile and across tiles.  pos stays as given (-1) while no entry is finite.
+__device__ __forceinline__ void tile_row_argmax(const f32x16& acc, const float (&rrow)[16], int t0, int len, int kk, float& mm,
+                                                int& pos) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int trow = t0 + mfma_row(r, kk);
+    const float x = acc[r] * rrow[r];
+    if (trow < len && finitef(x)) {
+      pos = x > mm ? trow : pos;
+      mm = fmaxf(mm, x);
+    }
+  }
+}
+
 // ... and its q-ordered sum over the nq tokens of one query tile, continued from `total`: mm = the tile's running maxima
 // (both halves still apart); a token without a finite similarity adds nothing.
 __device__ __forceinline__ float tile_sum(float m, int nq, float total) {

@@ -197,6 +197,7 @@ EXPORTS = [
     "np_hip_index_update", "np_hip_index_update_append", "np_hip_index_delete",
     "np_hip_pooled_lengths", "np_hip_pool_documents",
     "np_hip_search_exact", "np_hip_search_exact_device",
+    "np_hip_score_pairs", "np_hip_score_pairs_device",
 ]
 
 _lib = None
@@ -299,6 +300,8 @@ def lib():
                                                       i64, vp, vp, vp, vp, vp]
     L.np_hip_search_exact.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_search_exact_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_score_pairs.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_score_pairs_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -1065,6 +1068,57 @@ class MmapIndex:
                                          C.byref(st)))
         self.last_stats = st.as_dict()
         return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+
+    def score_pairs(self, queries, doc_ids, return_matches: bool = True, precision: int = 0):
+        """np_hip_score_pairs: the exact MaxSim of given (query, document) pairs and, per query token, its best document
+        token.  `doc_ids` has one array of global document ids per query (duplicates allowed, any order).  Returns per query
+        (scores f32 [n_i], token_sims f32 [n_i, Lq_i], token_pos i32 [n_i, Lq_i]), or only the scores with
+        return_matches=False.  A score is the very bits search_batch / search_exact give the pair at precision 0 and the
+        ordered f32 sum of its row of sims; a position is the lowest document-token index that reaches the sim (-1 and -inf
+        where no similarity is finite).  A single [tokens, dim] matrix is the batch of one (doc_ids then one array)."""
+        if isinstance(queries, np.ndarray) and queries.ndim == 2:
+            queries, doc_ids = [queries], [doc_ids]
+        queries, doc_ids = list(queries), list(doc_ids)
+        if len(doc_ids) != len(queries):
+            raise ValueError(f"doc_ids has {len(doc_ids)} entries for {len(queries)} queries")
+        lists = [np.ascontiguousarray(d, np.int64).reshape(-1) for d in doc_ids]
+        off = np.zeros(len(lists) + 1, np.int64)
+        if lists:
+            off[1:] = np.cumsum([d.size for d in lists])
+        flat_ids = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        return self.score_pairs_csr(queries, flat_ids, off, return_matches, precision)
+
+    def score_pairs_csr(self, queries, pair_docs, pair_offsets, return_matches: bool = True, precision: int = 0):
+        """np_hip_score_pairs as it is: query i against pair_docs[pair_offsets[i]:pair_offsets[i + 1]].  The arrays reach the
+        library as given (None = NULL), so its checks answer.  Returns what score_pairs returns."""
+        flat, qoff = self._pack(queries)
+        B = len(queries)
+        ids = None if pair_docs is None else np.ascontiguousarray(pair_docs, np.int64).reshape(-1)
+        poff = None if pair_offsets is None else np.ascontiguousarray(pair_offsets, np.int64).reshape(-1)
+        if poff is not None and poff.size != B + 1:
+            raise ValueError(f"pair_offsets has {poff.size} entries for {B} queries")
+        n = np.zeros(B, np.int64) if poff is None else np.maximum(np.diff(poff), 0)
+        if ids is not None and poff is not None and poff.size and int(poff.max()) > ids.size:
+            raise ValueError(f"pair_offsets count {int(poff.max())} pairs, pair_docs has {ids.size}")
+        lq = np.diff(qoff).astype(np.int64)
+        P, R = int(n.sum()), int((n * lq).sum())
+        sc = np.zeros(max(P, 1), np.float32)
+        sims = np.zeros(max(R, 1), np.float32) if return_matches else None
+        pos = np.zeros(max(R, 1), np.int32) if return_matches else None
+        st = np_stats()
+        _check(lib().np_hip_score_pairs(self._h, _ptr(flat), _ptr(qoff), B, self.embedding_dim(), int(precision), _ptr(ids),
+                                        _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos), C.byref(st)))
+        self.last_stats = st.as_dict()
+        out, p0, r0 = [], 0, 0
+        for i in range(B):
+            ni, li = int(n[i]), int(lq[i])
+            s = sc[p0:p0 + ni].copy()
+            if return_matches:
+                out.append((s, sims[r0:r0 + ni * li].reshape(ni, li).copy(), pos[r0:r0 + ni * li].reshape(ni, li).copy()))
+            else:
+                out.append(s)
+            p0, r0 = p0 + ni, r0 + ni * li
+        return out
 
     # -- adjacent rows ---------------------------------------------------------------------------------------
     def get_document_embeddings(self, doc_id: int) -> np.ndarray:
