@@ -391,6 +391,96 @@ int np_hip_score_pairs_device(const np_index* index, const float* d_queries, con
                               const int64_t* d_pair_docs, const int64_t* d_pair_offsets, const int64_t* h_pair_offsets,
                               float* d_out_scores, float* d_out_token_sims, int32_t* d_out_token_pos, void* stream);
 
+/* ---- metadata filters: columns in HBM, WHERE evaluated to a subset on the device ---------------------
+ * The crate computes a request's subset with filtering::where_condition (filtering.rs:1880: a SQLite query over metadata.db)
+ * and hands the id list to search.  Here a few typed attributes per document live next to the index, a filter crosses the
+ * ABI as a postfix program over them (strings never do: the host resolves text against a dictionary into i32 codes), and
+ * the ids it selects are produced on the device, with SQLite's semantics including its three-valued logic for NULL.
+ *
+ * np_hip_index_set_columns replaces the handle's columns (n_cols = 0 drops them; at most NP_MAX_COLUMNS).  `data` and `valid`
+ * are host arrays over the WHOLE index; a sharded handle keeps its slice [shard_doc_begin, shard_doc_end).  An f64 NaN is NULL
+ * whatever `valid` says (what SQLite does with a bound NaN).  The bytes are added to np_info.device_bytes and freed at close.
+ * Needs exclusive access to the handle: no call may run on it meanwhile.  NP_ERR_INVALID_ARGUMENT (unknown type, NULL data,
+ * n_cols out of range) is reported before any allocation; NP_ERR_OUT_OF_MEMORY leaves the previous columns in place. */
+#define NP_COL_I64 0
+#define NP_COL_F64 1
+#define NP_COL_CODE 2   /* i32 dictionary codes */
+#define NP_MAX_COLUMNS 64
+typedef struct np_column {
+  int32_t type;            /* NP_COL_I64, NP_COL_F64, NP_COL_CODE */
+  int32_t reserved;
+  const void* data;        /* host, num_documents entries of the WHOLE index (i64 / f64 / i32) */
+  const uint8_t* valid;    /* host, num_documents bytes, 0 = NULL; NULL pointer = no NULLs */
+} np_column;
+int np_hip_index_set_columns(np_index* index, const np_column* cols, int32_t n_cols);
+
+/* A filter is a postfix program: leaves push a value, NOT replaces the top, AND / OR replace the top two.  Every value is
+ * TRUE, FALSE or UNKNOWN and a document is selected only where the program leaves TRUE:
+ *   CMP, BETWEEN   UNKNOWN on a NULL cell
+ *   IN             TRUE on a match; otherwise UNKNOWN if the cell is NULL or the list held a NULL (arg bit 0); otherwise FALSE
+ *   IS_NULL        always known
+ *   NOT            keeps UNKNOWN;  AND / OR are Kleene's (FALSE AND UNKNOWN = FALSE, TRUE OR UNKNOWN = TRUE)
+ * `x NOT IN`, `NOT BETWEEN` and `IS NOT NULL` are the leaf followed by NOT.  I64 and CODE columns compare as integers, exactly
+ * over the whole range; F64 columns compare as IEEE doubles (-0.0 == 0.0, infinities order as numbers; a cell is never NaN,
+ * and a NaN constant is refused).
+ * Limits (NP_ERR_INVALID_ARGUMENT before any launch, the message names the filter and the op): 1..NP_FILTER_MAX_OPS ops, stack
+ * depth at most NP_FILTER_MAX_DEPTH, exactly one value left at the end, column indexes inside the handle's columns, value
+ * ranges inside values[], IN lists ascending and distinct (in the column's order), known ops and args, at most
+ * NP_FILTER_MAX_VALUES values in one filter, and a handle that has columns. */
+#define NP_F_CMP 0
+#define NP_F_BETWEEN 1
+#define NP_F_IN 2
+#define NP_F_IS_NULL 3
+#define NP_F_CONST 4
+#define NP_F_AND 5
+#define NP_F_OR 6
+#define NP_F_NOT 7
+#define NP_FILTER_MAX_OPS 256
+#define NP_FILTER_MAX_DEPTH 32
+#define NP_FILTER_MAX_VALUES (1 << 20)
+typedef struct np_filter_op {
+  int32_t op;          /* NP_F_* */
+  int32_t column;      /* leaves: column index; otherwise -1 */
+  int32_t arg;         /* CMP: 0 ==, 1 !=, 2 <, 3 <=, 4 >, 5 >=;  CONST: 0 false, 1 true, 2 unknown;
+                          IN: bit 0 set = the list also held a NULL */
+  int32_t n_values;    /* CMP 1, BETWEEN 2 (lo, hi), IN n >= 0 (ascending, distinct) */
+  int64_t first_value; /* index into values[] */
+} np_filter_op;
+typedef struct np_filter {
+  const np_filter_op* ops;
+  int32_t n_ops;
+  const int64_t* values;   /* i64 as is, f64 as its bit pattern, codes sign-extended */
+  int64_t n_values;
+} np_filter;
+
+/* The documents each filter selects, as GLOBAL ids, ascending, each once: filter f's ids are
+ * out_ids[out_offsets[f] .. out_offsets[f + 1]).  A sharded handle returns the ids of its own documents.  out_ids may be NULL
+ * (counts only).  If ids_capacity is smaller than out_offsets[n_filters], out_offsets is still filled in full and the call
+ * returns NP_ERR_INVALID_ARGUMENT with the needed size in the message.  The result is the same bits from run to run and in any
+ * chunking: positions come from popcounts and an exclusive scan, never from atomics.  Scratch comes out of a context's arena
+ * (the checkout of np_hip_search_batch: re-entrant on a shared handle); the call runs in chunks of documents and filters that
+ * fit the workspace budget, and a budget that holds no chunk is NP_ERR_OUT_OF_MEMORY, not a failed launch. */
+int np_hip_filter_eval(const np_index* index, const np_filter* filters, int32_t n_filters,
+                       int64_t* out_ids /* may be NULL: counts only */, int64_t ids_capacity,
+                       int64_t* out_offsets /* [n_filters + 1] */);
+
+/* np_hip_search_batch_subsets and np_hip_search_exact with (filters, n_filters, query_filter[B]) in place of the subsets'
+ * CSR: the filters are evaluated into a CSR that stays in HBM (the host reads back only its n_filters + 1 offsets) and the
+ * existing pass runs on it.  Query i gets, bit for bit, what the subsets call returns for the same ids, ascending, as subset
+ * query_filter[i]: -1 = no filter; a filter that selects nothing empties that query's result and no other; one that selects
+ * everything is a subset of all documents, not "no subset".  A query_filter entry < -1 or >= n_filters is
+ * NP_ERR_INVALID_ARGUMENT, and so is a handle opened with shard_count > 1: the crate's probe scaling needs the global subset
+ * length, a collective these calls do not run (np_hip_filter_eval does work on a shard).  stats are those of the underlying
+ * call with the filter's time added to ms_total. */
+int np_hip_search_batch_filtered(const np_index* index, const float* queries, const int32_t* q_tok_offsets,
+                                 int32_t B, int32_t dim, const np_search_params* params,
+                                 const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                 int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+int np_hip_search_exact_filtered(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B,
+                                 int32_t dim, int32_t top_k, int32_t precision,
+                                 const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                 int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best
  * n_sel = min(n_full_scores, max(n_full_scores/4, top_k)) candidates as 64-bit rank keys in

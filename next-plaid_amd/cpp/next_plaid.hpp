@@ -233,6 +233,69 @@ inline std::vector<int64_t> update_ids(const np_update_report& r, size_t n) {
   return ids;
 }
 
+// A metadata filter as the postfix program of np_hip_filter_eval (include/nextplaid_hip.h): leaves push a value, not_()
+// replaces the top, and_() / or_() replace the top two; every value is TRUE, FALSE or UNKNOWN (SQLite's three-valued logic)
+// and a document is selected where the program leaves TRUE.  `x NOT IN (...)` is in(...) followed by not_().  There is no
+// WHERE parser here: a Rust caller keeps the crate's validator (filtering.rs:571-583), resolves text against its dictionary
+// and emits the program.  The library checks the program (stack, columns, value ranges, sorted IN lists).
+class FilterProgram {
+ public:
+  enum Cmp { EQ = 0, NE = 1, LT = 2, LE = 3, GT = 4, GE = 5 };
+  enum Const { FALSE_ = 0, TRUE_ = 1, UNKNOWN = 2 };
+  static int64_t bits(double v) {
+    int64_t b;
+    std::memcpy(&b, &v, 8);
+    return b;
+  }
+  // constants: i64 as they are, codes sign-extended, doubles through bits()
+  FilterProgram& cmp(int column, Cmp op, int64_t value) { return leaf(NP_F_CMP, column, op, {value}); }
+  FilterProgram& cmp(int column, Cmp op, double value) { return leaf(NP_F_CMP, column, op, {bits(value)}); }
+  FilterProgram& between(int column, int64_t lo, int64_t hi) { return leaf(NP_F_BETWEEN, column, 0, {lo, hi}); }
+  FilterProgram& between(int column, double lo, double hi) { return leaf(NP_F_BETWEEN, column, 0, {bits(lo), bits(hi)}); }
+  // `values` ascending and distinct (in the column's order); has_null: the list also held a NULL
+  FilterProgram& in(int column, std::vector<int64_t> values, bool has_null = false) {
+    return leaf(NP_F_IN, column, has_null ? 1 : 0, std::move(values));
+  }
+  FilterProgram& in(int column, const std::vector<double>& values, bool has_null = false) {
+    std::vector<int64_t> b;
+    for (double v : values) b.push_back(bits(v));
+    return leaf(NP_F_IN, column, has_null ? 1 : 0, std::move(b));
+  }
+  FilterProgram& is_null(int column) { return leaf(NP_F_IS_NULL, column, 0, {}); }
+  FilterProgram& constant(Const c) { return node(NP_F_CONST, c); }
+  FilterProgram& and_() { return node(NP_F_AND, 0); }
+  FilterProgram& or_() { return node(NP_F_OR, 0); }
+  FilterProgram& not_() { return node(NP_F_NOT, 0); }
+  np_filter c() const {
+    return np_filter{ops_.data(), (int32_t)ops_.size(), values_.empty() ? nullptr : values_.data(), (int64_t)values_.size()};
+  }
+
+ private:
+  FilterProgram& leaf(int op, int column, int arg, std::vector<int64_t> v) {
+    ops_.push_back(np_filter_op{op, column, arg, (int32_t)v.size(), v.empty() ? 0 : (int64_t)values_.size()});
+    values_.insert(values_.end(), v.begin(), v.end());
+    return *this;
+  }
+  FilterProgram& node(int op, int arg) {
+    ops_.push_back(np_filter_op{op, -1, arg, 0, 0});
+    return *this;
+  }
+  std::vector<np_filter_op> ops_;
+  std::vector<int64_t> values_;
+};
+
+// One metadata column over the WHOLE index for MmapIndex::set_columns: a typed span and an optional validity span
+// (one byte per document, 0 = NULL; nullptr = no NULLs; an f64 NaN is NULL either way).
+struct ColumnSpan {
+  int32_t type;
+  const void* data;
+  const uint8_t* valid;
+  size_t size;
+  static ColumnSpan i64(const int64_t* d, size_t n, const uint8_t* valid = nullptr) { return {NP_COL_I64, d, valid, n}; }
+  static ColumnSpan f64(const double* d, size_t n, const uint8_t* valid = nullptr) { return {NP_COL_F64, d, valid, n}; }
+  static ColumnSpan codes(const int32_t* d, size_t n, const uint8_t* valid = nullptr) { return {NP_COL_CODE, d, valid, n}; }
+};
+
 class MmapIndex {
  public:
   // MmapIndex::create_with_kmeans (index.rs:927-967): k-means and codec training on the GPU, the crate's file set written
@@ -419,6 +482,84 @@ class MmapIndex {
     std::vector<int32_t> cnt(std::max<size_t>(n, 1));
     check(np_hip_search_exact(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)top_k, (int32_t)precision, sids.data(),
                               soff.data(), (int64_t)n_distinct, qsub.data(), ids.data(), sc.data(), cnt.data(), &last_stats));
+    std::vector<QueryResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].query_id = i;
+      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
+      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
+    }
+    return out;
+  }
+
+  // Metadata columns (np_hip_index_set_columns): replaces any earlier set, an empty vector drops them.  Every span covers
+  // the whole index.  Needs exclusive access to the handle.  reload() / update() leave a handle without columns.
+  void set_columns(const std::vector<ColumnSpan>& columns) {
+    require_device("set_columns");
+    std::vector<np_column> c;
+    for (const ColumnSpan& s : columns) {
+      if (s.size != num_documents()) throw Error(NP_ERR_SHAPE, "Shape error: a column needs one entry per document");
+      c.push_back(np_column{s.type, 0, s.data, s.valid});
+    }
+    check(np_hip_index_set_columns(h_, c.data(), (int32_t)c.size()));
+    check(np_hip_index_info(h_, &info_));
+  }
+
+  // The global ids every filter selects among this handle's documents, ascending (np_hip_filter_eval).
+  std::vector<std::vector<int64_t>> filter_ids(const std::vector<FilterProgram>& filters) const {
+    require_device("filter_ids");
+    std::vector<np_filter> f;
+    for (const FilterProgram& p : filters) f.push_back(p.c());
+    std::vector<int64_t> off(filters.size() + 1, 0);
+    check(np_hip_filter_eval(h_, f.data(), (int32_t)f.size(), nullptr, 0, off.data()));
+    std::vector<int64_t> ids(std::max<size_t>((size_t)off.back(), 1));
+    check(np_hip_filter_eval(h_, f.data(), (int32_t)f.size(), ids.data(), (int64_t)ids.size(), off.data()));
+    std::vector<std::vector<int64_t>> out(filters.size());
+    for (size_t j = 0; j < filters.size(); ++j) out[j].assign(ids.begin() + off[j], ids.begin() + off[j + 1]);
+    return out;
+  }
+
+  // search_batch_subsets with the subsets computed on the device (np_hip_search_batch_filtered): query i takes
+  // filters[query_filter[i]], -1 = none, and gets what the subsets call returns for the ids that filter selects, ascending.
+  // Filters have no CPU hand-off: a missing device is an Error.
+  std::vector<QueryResult> search_batch_filtered(const Query* queries, size_t n, const SearchParameters& params, bool parallel,
+                                                 const std::vector<FilterProgram>& filters,
+                                                 const std::vector<int32_t>& query_filter) const {
+    require_device("search_batch_filtered");
+    if (query_filter.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_batch_filtered: one query_filter entry per query");
+    std::vector<np_filter> f;
+    for (const FilterProgram& p : filters) f.push_back(p.c());
+    return run_batch(
+        queries, n, params, parallel,
+        [&](const float* flat, const int32_t* off, const np_search_params* p, int64_t* ids, float* sc, int32_t* cnt) {
+          return np_hip_search_batch_filtered(h_, flat, off, (int32_t)n, (int32_t)embedding_dim(), p, f.data(), (int32_t)f.size(),
+                                              query_filter.data(), ids, sc, cnt, &last_stats);
+        },
+        [&]() -> std::vector<QueryResult> {
+          throw Error(NP_ERR_DEVICE_UNAVAILABLE, "search_batch_filtered: filters are evaluated on the device; no CPU hand-off");
+        });
+  }
+
+  // ... and the exact scan over each query's filter (np_hip_search_exact_filtered)
+  std::vector<QueryResult> search_exact_filtered(const Query* queries, size_t n, size_t top_k, int precision,
+                                                 const std::vector<FilterProgram>& filters,
+                                                 const std::vector<int32_t>& query_filter) const {
+    require_device("search_exact_filtered");
+    if (query_filter.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_exact_filtered: one query_filter entry per query");
+    std::vector<np_filter> f;
+    for (const FilterProgram& p : filters) f.push_back(p.c());
+    const size_t dim = embedding_dim();
+    std::vector<int32_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
+    std::vector<float> flat((size_t)off[n] * dim);
+    for (size_t i = 0; i < n; ++i)
+      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+    const size_t k = std::max<size_t>(top_k, 1);
+    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
+    std::vector<float> sc(std::max<size_t>(n * k, 1));
+    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
+    check(np_hip_search_exact_filtered(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)top_k, (int32_t)precision,
+                                       f.data(), (int32_t)f.size(), query_filter.data(), ids.data(), sc.data(), cnt.data(),
+                                       &last_stats));
     std::vector<QueryResult> out(n);
     for (size_t i = 0; i < n; ++i) {
       out[i].query_id = i;

@@ -1693,6 +1693,63 @@ int np_hip_index_export(const np_index* ix, int64_t* doc_lengths, int64_t* codes
   return NP_OK;
 }
 
+int np_hip_index_set_columns(np_index* ix, const np_column* cols, int32_t n_cols) {
+  clear_error();
+  if (!ix || n_cols < 0 || n_cols > NP_MAX_COLUMNS || (n_cols > 0 && !cols)) {
+    set_error("set_columns: %s", !ix ? "NULL index" : !cols && n_cols > 0 ? "NULL columns" : "n_cols must be in 0..64");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (int32_t c = 0; c < n_cols; ++c) {
+    if (cols[c].type != NP_COL_I64 && cols[c].type != NP_COL_F64 && cols[c].type != NP_COL_CODE) {
+      set_error("set_columns: column %d has unknown type %d", c, cols[c].type);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    if (!cols[c].data) {
+      set_error("set_columns: column %d has NULL data", c);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  }
+  DeviceGuard g(ix->device);
+  // the new set is built beside the old one and swapped in whole: a failed allocation leaves the handle as it was
+  std::vector<DeviceColumn> fresh((size_t)n_cols);
+  std::vector<FilterCol> tab((size_t)n_cols);
+  DevPtr<FilterCol> d_tab;
+  size_t bytes = 0;
+  const int64_t b = ix->doc_begin, n = ix->n_docs, nvw = (n + 31) / 32;
+  std::vector<uint32_t> bits;
+  for (int32_t c = 0; c < n_cols; ++c) {
+    DeviceColumn& dc = fresh[c];
+    dc.type = cols[c].type;
+    const size_t esz = dc.type == NP_COL_CODE ? 4 : 8;
+    NP_TRY(dc.data.alloc((size_t)n * esz, &bytes));
+    if (n > 0) NP_HIP(hipMemcpy(dc.data.get(), (const char*)cols[c].data + (size_t)b * esz, (size_t)n * esz, hipMemcpyHostToDevice));
+    // validity: the caller's bytes, and an f64 NaN is NULL whatever they say; no array at all where nothing is NULL
+    bits.assign((size_t)nvw, 0u);
+    bool any_null = false;
+    const double* f64 = dc.type == NP_COL_F64 ? (const double*)cols[c].data + b : nullptr;
+    const uint8_t* valid = cols[c].valid ? cols[c].valid + b : nullptr;
+    for (int64_t d = 0; d < n; ++d) {
+      const bool ok = (!valid || valid[d] != 0) && (!f64 || f64[d] == f64[d]);
+      if (ok) bits[d >> 5] |= 1u << (d & 31); else any_null = true;
+    }
+    dc.has_valid = any_null;
+    if (any_null) {
+      NP_TRY(dc.valid.alloc((size_t)nvw, &bytes));
+      NP_HIP(hipMemcpy(dc.valid.get(), bits.data(), (size_t)nvw * 4, hipMemcpyHostToDevice));
+    }
+    tab[c] = FilterCol{dc.data.get(), any_null ? dc.valid.get() : nullptr, dc.type, 0};
+  }
+  if (n_cols > 0) {
+    NP_TRY(d_tab.alloc((size_t)n_cols, &bytes));
+    NP_HIP(hipMemcpy(d_tab.get(), tab.data(), (size_t)n_cols * sizeof(FilterCol), hipMemcpyHostToDevice));
+  }
+  ix->columns = std::move(fresh);
+  ix->d_coltab = std::move(d_tab);
+  ix->device_bytes = ix->device_bytes - ix->column_bytes + bytes;
+  ix->column_bytes = bytes;
+  return NP_OK;
+}
+
 void np_hip_index_close(np_index* index) {
   destroy_device_index(index);
 }

@@ -247,6 +247,19 @@ struct Tuning {
 // documents per range of the posting lists' range table (d_ivf_split) = per block of the zeroth filter level's sweep (np_kernels.h)
 #define NP_IVF_SPLIT_RANGE 32768
 
+// what a filter kernel needs of one metadata column (np_filter.hip)
+struct FilterCol {
+  const void* data;        // i64 / f64 / i32 [n_docs]
+  const uint32_t* valid;   // bit d = document d is not NULL; nullptr = no NULLs
+  int32_t type, pad;
+};
+struct DeviceColumn {
+  int32_t type = 0;
+  DevPtr<uint8_t> data;
+  DevPtr<uint32_t> valid;
+  bool has_valid = false;
+};
+
 struct DeviceIndex {
   int device = 0;
   int64_t N_total = 0, n_emb_total = 0;
@@ -293,6 +306,11 @@ struct DeviceIndex {
   // have more candidates than ivf_top_prefix[c] (search.rs:427-452 unions the probed cells' lists), which is what the workspace
   // planner sizes the candidate pool and the number of pool rounds for -- n_docs per query only when the lists do not say less
   std::vector<int64_t> ivf_top_prefix;
+  // metadata columns (np_hip_index_set_columns, np_filter.hip): one SoA array per column over the shard's documents, validity
+  // packed to bits (absent: no NULLs), and the table the filter kernels read them through
+  std::vector<DeviceColumn> columns;
+  DevPtr<FilterCol> d_coltab;     // [columns.size()]
+  size_t column_bytes = 0;        // the columns' share of device_bytes
   size_t device_bytes = 0;
   np_open_opts opts{};
   // per-context scratch budget the planner uses.  A caller-given workspace_bytes is kept as it is; the default (what the device
@@ -363,6 +381,8 @@ struct ContextUse {
   bool began = false;
   int begin(const DeviceIndex* index, void* user_stream);
   DevBuf& arena() const;
+  DevBuf& filter_scratch() const;   // masks, counts and programs of a filter evaluation (np_filter.hip)
+  DevBuf& filter_csr() const;       // the CSR a filtered search evaluates its filters into
   int pin(size_t bytes, void** out) const;
   int end();   // records the end of the use now (the destructor then only releases)
   ~ContextUse();
@@ -373,6 +393,22 @@ struct ContextUse {
 int subset_doc_rows(const DeviceIndex* ix, hipStream_t st, const int64_t* d_ids, const int64_t* d_off, const int32_t* d_qsub,
                     int64_t n_subsets, int64_t total, int64_t lo, int64_t hi, int B, int64_t NW, uint32_t* docbits,
                     int32_t* qrow);
+
+// np_filter.hip: a call's filters evaluated on `st` into a CSR that stays on the device.  `out` receives ids [total] i64 |
+// offsets [n_filters + 1] i64 | query map [B] i32 (the arguments of the per-query-subset pass), `scratch` the masks and
+// counts; both are reserved here.  h_off gets the offsets; synchronises `st` once.  *ms = wall time of the evaluation.
+struct FilterCsr {
+  const int64_t* d_ids = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t* d_qsub = nullptr;
+  std::vector<int64_t> h_off;
+  float ms = 0.f;
+};
+// the checks of the filtered entry points that need no device: the programs, the query map, the handle (columns, no shards)
+int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B,
+                      bool for_search);
+int filter_eval_resident(const DeviceIndex* ix, hipStream_t st, DevBuf& scratch, DevBuf& out, const np_filter* filters,
+                         int32_t n_filters, const int32_t* h_query_filter, int B, FilterCsr* csr);
 
 struct DeviceGuard {
   int prev = -1;

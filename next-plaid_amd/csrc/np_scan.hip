@@ -563,10 +563,12 @@ int np_hip_search_exact_device(const np_index* ix, const float* d_queries, const
                   d_out_ids, d_out_scores, d_out_counts, nullptr);
 }
 
-int np_hip_search_exact(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
-                        int32_t top_k, int32_t precision, const int64_t* subset_ids, const int64_t* subset_offsets,
-                        int64_t n_subsets, const int32_t* query_subset, int64_t* out_ids, float* out_scores,
-                        int32_t* out_counts, np_stats* stats) {
+// np_hip_search_exact and np_hip_search_exact_filtered: the subsets come as a host CSR, or (filters != NULL) are evaluated
+// on the call's context into a CSR that stays on the device; query_subset is the query map of either
+static int scan_host(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                     int32_t top_k, int32_t precision, const int64_t* subset_ids, const int64_t* subset_offsets,
+                     int64_t n_subsets, const int32_t* query_subset, const np_filter* filters, int64_t* out_ids,
+                     float* out_scores, int32_t* out_counts, np_stats* stats) {
   clear_error();
   if (stats) memset(stats, 0, sizeof *stats);
   if (B > 0 && !q_tok_offsets) {
@@ -574,7 +576,10 @@ int np_hip_search_exact(const np_index* ix, const float* queries, const int32_t*
     return NP_ERR_INVALID_ARGUMENT;
   }
   NP_TRY(scan_validate(ix, B, dim, top_k, precision, B > 0 ? q_tok_offsets : nullptr));
-  NP_TRY(check_subsets(subset_ids, subset_offsets, n_subsets, query_subset, query_subset, B));
+  if (filters)
+    NP_TRY(filter_check_call(ix, filters, (int32_t)n_subsets, query_subset, B, true));
+  else
+    NP_TRY(check_subsets(subset_ids, subset_offsets, n_subsets, query_subset, query_subset, B));
   if (B == 0) return NP_OK;
   if (!queries || !out_ids || !out_scores || !out_counts) {
     set_error("Search failed: NULL buffer");
@@ -583,21 +588,29 @@ int np_hip_search_exact(const np_index* ix, const float* queries, const int32_t*
   // a batch none of whose queries has a subset is a batch without subsets
   bool any = false;
   for (int b = 0; n_subsets > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
+  const bool resident = any && filters;
+  DeviceGuard g(ix->device);
+  ContextUse use;
+  NP_TRY(use.begin(ix, nullptr));
+  hipStream_t st = use.stream;
+  FilterCsr csr;
+  if (resident) {
+    NP_TRY(filter_eval_resident(ix, st, use.filter_scratch(), use.filter_csr(), filters, (int32_t)n_subsets, query_subset, B, &csr));
+    subset_offsets = csr.h_off.data();
+  }
   const int64_t total = any ? subset_offsets[n_subsets] : 0;
   const int64_t ntok = q_tok_offsets[B];
   // behind the scan's own regions: queries, offsets, the subsets, the batch's results
   const size_t b_q = up256((size_t)std::max<int64_t>(ntok, 1) * dim * 4), b_qoff = up256((size_t)(B + 1) * 4);
-  const size_t b_ids = any ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = any ? up256((size_t)(n_subsets + 1) * 8) : 0;
-  const size_t b_qsub = any ? up256((size_t)B * 4) : 0;
+  const bool staged = any && !resident;   // the subsets' CSR is copied behind the queries; a filter's is on the device already
+  const size_t b_ids = staged ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = staged ? up256((size_t)(n_subsets + 1) * 8) : 0;
+  const size_t b_qsub = staged ? up256((size_t)B * 4) : 0;
   const size_t o_ids = up256((size_t)B * top_k * 8), o_sc = up256((size_t)B * top_k * 4), o_cnt = up256((size_t)B * 4);
   const size_t user = b_q + b_qoff + b_ids + b_off + b_qsub + o_ids + o_sc + o_cnt;
-  DeviceGuard g(ix->device);
   ScanPlan plan;
-  NP_TRY(scan_plan_for(ix, (int64_t)user, B, top_k, any, &plan));
-  ContextUse use;
-  NP_TRY(use.begin(ix, nullptr));
-  hipStream_t st = use.stream;
-  NP_TRY(use.arena().reserve(user + scan_arena_bytes(ix, plan, top_k, any)));
+  // (a filter's CSR lives outside the arena but inside the budget)
+  NP_TRY(scan_plan_for(ix, (int64_t)user + (resident ? total * 8 : 0), B, top_k, any, &plan));
+  NP_TRY(use.arena().reserve(user +scan_arena_bytes(ix, plan, top_k, any)));
   void* pinv = nullptr;
   NP_TRY(use.pin(o_ids + o_sc + o_cnt, &pinv));
   char* at = use.arena().as<char>();
@@ -609,7 +622,15 @@ int np_hip_search_exact(const np_index* ix, const float* queries, const int32_t*
   float* d_q = (float*)take(b_q);
   int32_t* d_qoff = (int32_t*)take(b_qoff);
   ScanSubsets sub;
-  if (any) {
+  if (resident) {
+    sub.d_ids = csr.d_ids;
+    sub.d_off = csr.d_off;
+    sub.d_qsub = csr.d_qsub;
+    sub.n = n_subsets;
+    sub.total = total;
+    sub.h_off = subset_offsets;
+    sub.h_qsub = query_subset;
+  } else if (any) {
     sub.d_ids = (const int64_t*)take(b_ids);
     sub.d_off = (const int64_t*)take(b_off);
     sub.d_qsub = (const int32_t*)take(b_qsub);
@@ -636,7 +657,25 @@ int np_hip_search_exact(const np_index* ix, const float* queries, const int32_t*
   memcpy(out_ids, pin, (size_t)B * top_k * 8);
   memcpy(out_scores, pin + o_ids, (size_t)B * top_k * 4);
   memcpy(out_counts, pin + o_ids + o_sc, (size_t)B * 4);
+  if (stats) stats->ms_total += csr.ms;
   return NP_OK;
+}
+
+int np_hip_search_exact(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                        int32_t top_k, int32_t precision, const int64_t* subset_ids, const int64_t* subset_offsets,
+                        int64_t n_subsets, const int32_t* query_subset, int64_t* out_ids, float* out_scores,
+                        int32_t* out_counts, np_stats* stats) {
+  return scan_host(ix, queries, q_tok_offsets, B, dim, top_k, precision, subset_ids, subset_offsets, n_subsets, query_subset,
+                   nullptr, out_ids, out_scores, out_counts, stats);
+}
+
+int np_hip_search_exact_filtered(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                                 int32_t top_k, int32_t precision, const np_filter* filters, int32_t n_filters,
+                                 const int32_t* query_filter, int64_t* out_ids, float* out_scores, int32_t* out_counts,
+                                 np_stats* stats) {
+  static const np_filter none{};   // n_filters == 0: nothing to check or evaluate, but still the filtered call's checks
+  return scan_host(ix, queries, q_tok_offsets, B, dim, top_k, precision, nullptr, nullptr, n_filters, query_filter,
+                   filters ? filters : &none, out_ids, out_scores, out_counts, stats);
 }
 
 }  // extern "C"

@@ -22,16 +22,17 @@ struct Workspace {
       cand_base, round_of, round_tab, QCU, qinv, qflag, ub, ub_hist, ub_thr, ub_cursor, q_order, xcd_slots, surv_meta, n_surv, n_list2, sel_keys, sel_doc, nsel, exact, out_ids, out_scores, out_keys, out_counts, ctr, subset,
       subset_bits, elig, misc, cut, cmaxu, chist, ub2, ub_hist2, ub_thr2, list_meta, n_l1, n_l2, qpad, planes, levels, hotbits,
       gain, gsmall, ghist, s0_meta, s0_u, gacc, gdeep,   // zeroth filter level (gain_sweep_kernel)
-      scan;   // np_hip_search_exact's arena (np_scan.hip carves it up)
+      scan,   // np_hip_search_exact's arena (np_scan.hip carves it up)
+      filt, filt_csr;   // a filter evaluation's scratch and the CSR of a filtered search (np_filter.hip)
   void* h_pin = nullptr;
   size_t h_pin_cap = 0;
   unsigned long long* h_gain = nullptr;   // pinned: the zeroth level's last (candidates << 32 | kept), written by the device
   uint64_t h_gain_key = 0;                // ... and the parameters of the batch that will write (or wrote) it
   hipEvent_t done = nullptr;  // recorded at the end of every use of this workspace
   bool done_valid = false;
-  static constexpr int NBUF = 67;
+  static constexpr int NBUF = 69;
   std::array<DevBuf*, NBUF> all_bufs() {   // no heap allocation: total_bytes() runs on the search path
-    return {&q, &qoff, &Qt, &Qb, &Qbl, &QCT, &gmax, &tauq, &cellbits, &cells_tmp, &cells, &n_cells, &docbits, &chunk_counts, &cand, &cand_meta, &approx, &n_cand, &cand_base, &round_of, &round_tab, &QCU, &qinv, &qflag, &ub, &ub_hist, &ub_thr, &ub_cursor, &q_order, &xcd_slots, &surv_meta, &n_surv, &n_list2, &sel_keys, &sel_doc, &nsel, &exact, &out_ids, &out_scores, &out_keys, &out_counts, &ctr, &subset, &subset_bits, &elig, &misc, &cut, &cmaxu, &chist, &ub2, &ub_hist2, &ub_thr2, &list_meta, &n_l1, &n_l2, &qpad, &planes, &levels, &hotbits, &gain, &gsmall, &ghist, &s0_meta, &s0_u, &gacc, &gdeep, &scan};
+    return {&q, &qoff, &Qt, &Qb, &Qbl, &QCT, &gmax, &tauq, &cellbits, &cells_tmp, &cells, &n_cells, &docbits, &chunk_counts, &cand, &cand_meta, &approx, &n_cand, &cand_base, &round_of, &round_tab, &QCU, &qinv, &qflag, &ub, &ub_hist, &ub_thr, &ub_cursor, &q_order, &xcd_slots, &surv_meta, &n_surv, &n_list2, &sel_keys, &sel_doc, &nsel, &exact, &out_ids, &out_scores, &out_keys, &out_counts, &ctr, &subset, &subset_bits, &elig, &misc, &cut, &cmaxu, &chist, &ub2, &ub_hist2, &ub_thr2, &list_meta, &n_l1, &n_l2, &qpad, &planes, &levels, &hotbits, &gain, &gsmall, &ghist, &s0_meta, &s0_u, &gacc, &gdeep, &scan, &filt, &filt_csr};
   }
   void release_all() {
     for (DevBuf* b : all_bufs()) b->release();
@@ -1632,6 +1633,8 @@ int ContextUse::begin(const DeviceIndex* index, void* user_stream) {
   return NP_OK;
 }
 DevBuf& ContextUse::arena() const { return ctx->ws->scan; }
+DevBuf& ContextUse::filter_scratch() const { return ctx->ws->filt; }
+DevBuf& ContextUse::filter_csr() const { return ctx->ws->filt_csr; }
 int ContextUse::pin(size_t bytes, void** out) const {
   NP_TRY(ctx->ws->pin(bytes));
   *out = ctx->ws->h_pin;
@@ -1787,10 +1790,11 @@ int np_hip_search_batch_subsets_device(const np_index* ix, const float* d_querie
 // A call's subsets in host memory: `sub` holds host pointers until upload() has copied them behind the queries' buffers
 struct HostSubsets {
   Subsets sub;
+  bool resident = false;   // a filtered call: the CSR was evaluated on the device (np_filter.hip) and `sub` points at it
   // ids [total] i64 | offsets [n + 1] i64 | query_subset [B] i32 in w.subset, on the call's stream
   int upload(Workspace& w, int B, hipStream_t st) {
     SubsetsP& d = sub.d;
-    if (d.n == 0 || (d.total == 0 && !d.off)) return NP_OK;
+    if (resident || d.n == 0 || (d.total == 0 && !d.off)) return NP_OK;
     const size_t ib = (size_t)d.total * 8, ob = d.off ? (size_t)(d.n + 1) * 8 : 0, qb = d.qsub ? (size_t)B * 4 : 0;
     NP_TRY(w.subset.reserve(ib + ob + qb));
     char* base = w.subset.as<char>();
@@ -1804,9 +1808,16 @@ struct HostSubsets {
   }
 };
 
+// the filters of np_hip_search_batch_filtered (checked): evaluated on the call's own context, ahead of the pass
+struct FilterCall {
+  const np_filter* filters;
+  int32_t n_filters;
+  const int32_t* query_filter;
+};
+
 static int search_batch_host(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
                              const np_search_params* params, HostSubsets hs, int64_t* out_ids, float* out_scores,
-                             int32_t* out_counts, np_stats* stats) {
+                             int32_t* out_counts, np_stats* stats, const FilterCall* fc = nullptr) {
   if (!queries || !q_tok_offsets || !out_counts || (params->top_k > 0 && (!out_ids || !out_scores))) {
     set_error("Search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
@@ -1842,6 +1853,20 @@ static int search_batch_host(const np_index* ix, const float* queries, const int
   NP_TRY(w.out_counts.reserve(ob_cnt));
   if (ntok > 0) NP_HIP(hipMemcpyAsync(w.q.p, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(w.qoff.p, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+  FilterCsr csr;   // outlives the pass: the subsets' host offsets point into it
+  if (fc) {
+    NP_TRY(filter_eval_resident(ix, st, w.filt, w.filt_csr, fc->filters, fc->n_filters, fc->query_filter, B, &csr));
+    bool all_empty = true;
+    for (int b = 0; b < B; ++b) {
+      const int32_t q = fc->query_filter[b];
+      all_empty = all_empty && q >= 0 && csr.h_off[q + 1] == csr.h_off[q];
+    }
+    hs.sub.d = SubsetsP{csr.d_ids, csr.d_off, csr.d_qsub, fc->n_filters, csr.h_off[fc->n_filters]};
+    hs.sub.all_empty = all_empty;
+    hs.sub.h_off = csr.h_off.data();
+    hs.sub.h_qsub = fc->query_filter;
+    hs.resident = true;
+  }
   NP_TRY(hs.upload(w, B, st));
 
   // slices: each slice's outputs go to its rows of the batch-wide output buffers
@@ -1910,9 +1935,27 @@ static int search_batch_host(const np_index* ix, const float* queries, const int
   memcpy(out_counts, h_cnt, (size_t)B * 4);
   if (stats) {
     acc.n_queries = B;
+    acc.ms_total += csr.ms;
     *stats = acc;
   }
   return NP_OK;
+}
+
+int np_hip_search_batch_filtered(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B,
+                                 int32_t dim, const np_search_params* params, const np_filter* filters, int32_t n_filters,
+                                 const int32_t* query_filter, int64_t* out_ids, float* out_scores, int32_t* out_counts,
+                                 np_stats* stats) {
+  clear_error();
+  if (stats) memset(stats, 0, sizeof *stats);
+  NP_TRY(validate(ix, B, dim, params));
+  NP_TRY(filter_check_call(ix, filters, n_filters, query_filter, B, true));
+  if (B == 0) return NP_OK;
+  // as in np_hip_search_batch_subsets: a batch none of whose queries has a filter is a batch without subsets
+  bool any = false;
+  for (int b = 0; n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
+  const FilterCall fc{filters, n_filters, query_filter};
+  return search_batch_host(ix, queries, q_tok_offsets, B, dim, params, HostSubsets{}, out_ids, out_scores, out_counts, stats,
+                           any ? &fc : nullptr);
 }
 
 int np_hip_search_batch(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,

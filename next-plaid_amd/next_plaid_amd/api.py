@@ -175,6 +175,19 @@ class np_pool_report(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class np_column(C.Structure):
+    _fields_ = [("type", C.c_int32), ("reserved", C.c_int32), ("data", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class np_filter_op(C.Structure):
+    _fields_ = [("op", C.c_int32), ("column", C.c_int32), ("arg", C.c_int32), ("n_values", C.c_int32),
+                ("first_value", C.c_int64)]
+
+
+class np_filter(C.Structure):
+    _fields_ = [("ops", C.POINTER(np_filter_op)), ("n_ops", C.c_int32), ("values", C.c_void_p), ("n_values", C.c_int64)]
+
+
 # np_all_gather_host_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes)
 ALL_GATHER_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 NP_COMM_DEFERRED_STATUS = 1
@@ -198,6 +211,7 @@ EXPORTS = [
     "np_hip_pooled_lengths", "np_hip_pool_documents",
     "np_hip_search_exact", "np_hip_search_exact_device",
     "np_hip_score_pairs", "np_hip_score_pairs_device",
+    "np_hip_index_set_columns", "np_hip_filter_eval", "np_hip_search_batch_filtered", "np_hip_search_exact_filtered",
 ]
 
 _lib = None
@@ -302,6 +316,12 @@ def lib():
     L.np_hip_search_exact_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.np_hip_score_pairs.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_score_pairs_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.np_hip_index_set_columns.argtypes = [vp, C.POINTER(np_column), i32]
+    L.np_hip_filter_eval.argtypes = [vp, C.POINTER(np_filter), i32, vp, i64, vp]
+    L.np_hip_search_batch_filtered.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_filter), i32, vp,
+                                               vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_search_exact_filtered.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(np_filter), i32, vp, vp, vp, vp,
+                                               C.POINTER(np_stats)]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -436,6 +456,45 @@ def pack_subsets(subsets, n_queries: int):
         off[1:] = np.cumsum([a.size for a in arrays])
     ids = np.concatenate(arrays) if arrays else np.zeros(0, np.int64)
     return np.ascontiguousarray(ids, np.int64), off, qsub
+
+
+def pack_filters(filters, n_queries: int, schema):
+    """One filter per query -> (compiled distinct filters, query_filter i32 [n_queries], -1 = none).  `filters` has n_queries
+    entries, each None, a (condition, params) pair, a bare condition string or a CompiledFilter.  Entries that compile to the
+    same program share one filter: it is evaluated once.  Pure host code."""
+    from . import filters as F
+    filters = list(filters)
+    if len(filters) != n_queries:
+        raise ValueError(f"filters has {len(filters)} entries for {n_queries} queries")
+    slot, progs = {}, []
+    qf = np.full(n_queries, -1, np.int32)
+    for i, f in enumerate(filters):
+        if f is None:
+            continue
+        if not isinstance(f, F.CompiledFilter):
+            cond, params = (f, ()) if isinstance(f, str) else f
+            f = F.compile_filter(cond, params, schema)
+        j = slot.get(f.key())
+        if j is None:
+            j = slot[f.key()] = len(progs)
+            progs.append(f)
+        qf[i] = j
+    return progs, qf
+
+
+class _CFilters:
+    """The ctypes form of compiled filters; keeps every array it points to alive."""
+
+    def __init__(self, progs):
+        self.n = len(progs)
+        self.arr = (np_filter * max(self.n, 1))()
+        self.keep = []
+        for j, p in enumerate(progs):
+            ops = (np_filter_op * max(len(p.ops), 1))(*[np_filter_op(*o) for o in p.ops])
+            vals = np.ascontiguousarray(p.values, np.int64)
+            self.keep += [ops, vals]
+            self.arr[j] = np_filter(C.cast(ops, C.POINTER(np_filter_op)), len(p.ops), vals.ctypes.data if vals.size else None,
+                                    vals.size)
 
 
 # ---- crate mirror ------------------------------------------------------------------------------------
@@ -793,6 +852,7 @@ class MmapIndex:
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         self.last_stats: dict | None = None
         self.last_update: dict | None = None
+        self.schema = None   # set_columns: the columns' names, types and dictionaries (filters.Schema)
 
     # -- constructors ---------------------------------------------------------------------------------
     @classmethod
@@ -820,7 +880,8 @@ class MmapIndex:
         (delete / update write new chunk files).  Like the crate -- which releases its maps first -- the old device copy is
         dropped BEFORE the new one is read: two 200 GB copies do not fit one GPU.  Exclusive access, as `&mut self` there;
         a service swaps handles instead.  If the directory no longer loads, the error is raised
-        and the handle stays closed."""
+        and the handle stays closed.  The reloaded handle has NO metadata columns: updates and deletes re-sequence the
+        document ids, so set_columns() has to be called again with the new rows."""
         if not self.path or self.path.startswith("<"):
             raise IndexLoadError("Index load failed: reload() needs an index opened from a directory")
         self.close()
@@ -828,6 +889,7 @@ class MmapIndex:
         o = _opts(**self._open_opts)
         _check(lib().np_hip_index_open(os.fsencode(self.path), C.byref(o), C.byref(h)))
         self._h = h
+        self.schema = None
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         self.last_stats = None
 
@@ -839,7 +901,8 @@ class MmapIndex:
 
     def update(self, documents, config: UpdateConfig | None = None) -> np.ndarray:
         """MmapIndex::update (index.rs:1431-1590): the new documents' ids; the handle is reloaded from the rewritten
-        directory.  The report of the call is kept in self.last_update."""
+        directory (without metadata columns: ids are re-sequenced, call set_columns() again).  The report of the call is
+        kept in self.last_update."""
         path = self._dir("update")
         ids, self.last_update = update_index_dir(path, documents, config, self._open_opts.get("device", 0))
         self.reload()
@@ -862,7 +925,7 @@ class MmapIndex:
 
     def delete(self, doc_ids) -> int:
         """MmapIndex::delete (index.rs:1731-1765): rewrites the directory and returns the count removed; like the crate
-        it does not reload (call reload())."""
+        it does not reload (call reload(); that drops the metadata columns, whose rows no longer match the new ids)."""
         return delete_from_index_dir(self._dir("delete"), doc_ids)
 
     @classmethod
@@ -943,6 +1006,98 @@ class MmapIndex:
         _check(lib().np_hip_index_info(self._h, C.byref(live)))
         return int(live.workspace_bytes)
 
+    # -- metadata columns and filters ---------------------------------------------------------------------
+    def set_columns(self, columns: dict):
+        """np_hip_index_set_columns: the handle's metadata columns, name -> one entry per document of the WHOLE index (a
+        sharded handle keeps its slice).  Integer and bool arrays become I64, float arrays F64, string sequences
+        dictionary codes (the dictionary, the distinct non-null strings sorted by their UTF-8 bytes, stays on this object in
+        self.schema).  None entries, numpy masked entries and NaN are NULL.  Replaces any earlier set; {} drops them.  A
+        length other than num_documents() is a ShapeError.  Needs exclusive access to the handle, as reload() does."""
+        from . import filters as F
+        sch = F.make_schema(dict(columns), self.num_documents())
+        cols = (np_column * max(len(sch), 1))()
+        for c in sch.columns.values():
+            cols[c.index] = np_column(c.type, 0, c.data.ctypes.data, None if c.valid is None else c.valid.ctypes.data)
+        _check(lib().np_hip_index_set_columns(self._h, cols, len(sch)))
+        self.schema = sch if len(sch) else None
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def _filters(self, filters, n_queries):
+        from . import filters as F
+        progs, qf = pack_filters(filters, n_queries, self.schema if self.schema is not None else F.Schema())
+        return _CFilters(progs), qf
+
+    def filter_ids(self, filters, counts_only: bool = False):
+        """np_hip_filter_eval: for every filter -- a (condition, params) pair, a condition string or a CompiledFilter -- the
+        global ids of the documents it selects (those this handle holds), ascending, as one int64 array each.  With
+        counts_only the arrays are not fetched and the counts come back instead."""
+        from . import filters as F
+        sch = self.schema if self.schema is not None else F.Schema()
+        progs = []
+        for f in filters:
+            if not isinstance(f, F.CompiledFilter):
+                cond, params = (f, ()) if isinstance(f, str) else f
+                f = F.compile_filter(cond, params, sch)
+            progs.append(f)
+        cf = _CFilters(progs)
+        off = np.zeros(len(progs) + 1, np.int64)
+        _check(lib().np_hip_filter_eval(self._h, cf.arr, cf.n, None, 0, _ptr(off)))
+        if counts_only:
+            return np.diff(off)
+        ids = np.zeros(max(int(off[-1]), 1), np.int64)
+        _check(lib().np_hip_filter_eval(self._h, cf.arr, cf.n, _ptr(ids), ids.size, _ptr(off)))
+        return [ids[off[j]: off[j + 1]].copy() for j in range(len(progs))]
+
+    def filter_eval_raw(self, compiled, ids_capacity: int, want_ids: bool = True):
+        """np_hip_filter_eval as it is: (rc, offsets, ids) for CompiledFilters and a caller-chosen ids_capacity."""
+        cf = _CFilters(list(compiled))
+        off = np.full(cf.n + 1, -1, np.int64)
+        ids = np.zeros(max(int(ids_capacity), 1), np.int64)
+        rc = lib().np_hip_filter_eval(self._h, cf.arr, cf.n, _ptr(ids) if want_ids else None, int(ids_capacity), _ptr(off))
+        return rc, off, ids
+
+    def search_batch_filtered(self, queries, params: "SearchParameters", compiled, query_filter, parallel: bool = True):
+        """np_hip_search_batch_filtered as it is: CompiledFilters and the queries' map (-1 = none) reach the library as given."""
+        flat, off = self._pack(queries)
+        B = len(queries)
+        k = max(int(params.top_k), 0)
+        ids = np.zeros(max(B * k, 1), np.int64)
+        sc = np.zeros(max(B * k, 1), np.float32)
+        cnt = np.zeros(max(B, 1), np.int32)
+        p = params._c()
+        cf = compiled if isinstance(compiled, _CFilters) else _CFilters(list(compiled))
+        qf = np.ascontiguousarray(query_filter, np.int32)
+        if qf.size != B:
+            raise ValueError(f"query_filter has {qf.size} entries for {B} queries")
+        st = np_stats()
+        rc = lib().np_hip_search_batch_filtered(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), cf.arr,
+                                                cf.n, _ptr(qf), _ptr(ids), _ptr(sc), _ptr(cnt), C.byref(st))
+        if rc:
+            if parallel and rc == 2:  # search.rs:656-660: a failed query yields an empty result
+                return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
+            _check(rc)
+        self.last_stats = st.as_dict()
+        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+
+    def search_exact_filtered(self, queries, top_k: int, precision: int, compiled, query_filter):
+        """np_hip_search_exact_filtered as it is."""
+        flat, off = self._pack(queries)
+        B = len(queries)
+        k = max(int(top_k), 1)
+        ids = np.zeros(max(B * k, 1), np.int64)
+        sc = np.zeros(max(B * k, 1), np.float32)
+        cnt = np.zeros(max(B, 1), np.int32)
+        cf = compiled if isinstance(compiled, _CFilters) else _CFilters(list(compiled))
+        qf = np.ascontiguousarray(query_filter, np.int32)
+        if qf.size != B:
+            raise ValueError(f"query_filter has {qf.size} entries for {B} queries")
+        st = np_stats()
+        _check(lib().np_hip_search_exact_filtered(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), int(top_k),
+                                                  int(precision), cf.arr, cf.n, _ptr(qf), _ptr(ids), _ptr(sc), _ptr(cnt),
+                                                  C.byref(st)))
+        self.last_stats = st.as_dict()
+        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+
     # -- search ------------------------------------------------------------------------------------------
     def _pack(self, queries):
         qs = [np.ascontiguousarray(q, np.float32) for q in queries]
@@ -956,19 +1111,32 @@ class MmapIndex:
         flat = np.concatenate(qs, 0) if qs else np.zeros((0, d), np.float32)
         return np.ascontiguousarray(flat, np.float32), off
 
-    def search(self, query, params: SearchParameters, subset=None) -> QueryResult:
-        """MmapIndex::search (index.rs:1258-1265); query_id is 0 (search.rs:511-515)."""
-        r = self.search_batch([query], params, parallel=False, subset=subset)[0]
+    def search(self, query, params: SearchParameters, subset=None, filter=None) -> QueryResult:
+        """MmapIndex::search (index.rs:1258-1265); query_id is 0 (search.rs:511-515).  `filter` = (condition, params) over
+        the handle's columns in place of a subset (not both)."""
+        if filter is not None and subset is not None:
+            raise ValueError("search takes subset= or filter=, not both")
+        r = self.search_batch([query], params, parallel=False, subset=subset, filters=None if filter is None else [filter])[0]
         r.query_id = 0
         return r
 
-    def search_batch(self, queries, params: SearchParameters, parallel: bool = True, subset=None, subsets=None):
+    def search_batch(self, queries, params: SearchParameters, parallel: bool = True, subset=None, subsets=None, filters=None):
         """MmapIndex::search_batch (index.rs:1279-1287).  `parallel` only selects the reference's
         error policy (search.rs:650-674): the GPU path always runs the batch as one pipeline pass.
 
         `subset` is the crate's argument: one subset for the whole batch.  `subsets` gives every query its own: a sequence
         of len(queries) entries, each None or an array of document ids; query i gets what search(queries[i], params,
-        subsets[i]) returns.  Entries that are the same object share one subset (see pack_subsets)."""
+        subsets[i]) returns.  Entries that are the same object share one subset (see pack_subsets).
+
+        `filters` gives every query a WHERE condition over the handle's columns instead (set_columns): one entry per query,
+        None or (condition, params); the ids are computed on the device and query i gets what subsets=[ids the filter
+        selects, ascending] returns.  Equal entries are compiled and evaluated once.  Not together with subset / subsets."""
+        if filters is not None:
+            if subset is not None or subsets is not None:
+                raise ValueError("search_batch takes filters= or subset= / subsets=, not both")
+            queries = list(queries)
+            cf, qf = self._filters(filters, len(queries))
+            return self.search_batch_filtered(queries, params, cf, qf, parallel=parallel)
         if subsets is not None:
             if subset is not None:
                 raise ValueError("search_batch takes subset= (one for the batch) or subsets= (one per query), not both")
@@ -1025,7 +1193,7 @@ class MmapIndex:
         return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy())
                 for i in range(B)]
 
-    def search_exact(self, queries, top_k: int, precision: int = 0, subset=None, subsets=None):
+    def search_exact(self, queries, top_k: int, precision: int = 0, subset=None, subsets=None, filters=None):
         """np_hip_search_exact: for every query the true top_k of its scope by exact MaxSim over the decompressed index,
         every document scored (no probe, no candidates).  Scope: the whole handle, `subset` (one for the batch) or
         `subsets` (one entry per query, None or an array of ids, as search_batch takes them through pack_subsets).
@@ -1035,6 +1203,11 @@ class MmapIndex:
             queries = [queries]
         queries = list(queries)
         B = len(queries)
+        if filters is not None:   # one WHERE condition per query (None or (condition, params)), as search_batch takes them
+            if subset is not None or subsets is not None:
+                raise ValueError("search_exact takes filters= or subset= / subsets=, not both")
+            cf, qf = self._filters(filters, B)
+            return self.search_exact_filtered(queries, top_k, precision, cf, qf)
         if subsets is not None:
             if subset is not None:
                 raise ValueError("search_exact takes subset= (one for the batch) or subsets= (one per query), not both")
