@@ -481,6 +481,127 @@ int np_hip_search_exact_filtered(const np_index* index, const float* queries, co
                                  const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
                                  int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
 
+/* ---- hybrid search: the keyword index in HBM, FTS5-exact BM25, fusion ---------------------------------
+ * The crate's /search handler runs, next to index.search, an SQLite FTS5 query (text_search.rs:1246-1342: MATCH ordered by
+ * -bm25()) and fuses the two lists (text_search.rs:1006-1075).  Here the FTS5 index lives next to the ColBERT index and
+ * the keyword search, the fusion and the whole hybrid request run on the device, with SQLite's results bit for bit.
+ *
+ * np_hip_index_set_text replaces the handle's keyword index (NULL, or an index without instances and rows, drops it).  The
+ * arrays are host arrays over the WHOLE index: the (term, document, position) instances of the FTS5 table as fts5vocab's
+ * 'instance' rows give them, sorted by (term, document, position), term t owning [term_offsets[t], term_offsets[t + 1]);
+ * n_rows is the row count of the FTS5 table (its nRow: rows without a token count, so it need not equal num_documents).
+ * Document ids are global ids in [0, num_documents).  Derived on the host and kept in HBM: per-term posting lists of
+ * (document, term frequency, first position), every document's token count (its instances), and on the host the total
+ * token count and every term's document frequency.  The bytes are added to np_info.device_bytes and freed at close.
+ * Needs exclusive access to the handle.  Checked on the host before any allocation (NP_ERR_INVALID_ARGUMENT, the message
+ * names the first offending term / instance): offsets that do not start at 0 or decrease, instances out of (document,
+ * position) order or repeated, a document outside [0, num_documents), a negative position, n_rows below the number of
+ * distinct documents, NULL arrays with a positive count.  NP_ERR_OUT_OF_MEMORY leaves the previous index in place.
+ * A handle opened with shard_count > 1 is refused (NP_ERR_INVALID_ARGUMENT), here and in every call below: nRow, the
+ * average length and a phrase's hit count are global figures and would need a collective that these calls do not run. */
+typedef struct np_text_index {
+  int64_t n_terms;
+  const int64_t* term_offsets;   /* [n_terms + 1] */
+  const int64_t* inst_doc;       /* [term_offsets[n_terms]] global document ids */
+  const int32_t* inst_pos;       /* [term_offsets[n_terms]] token positions inside the document */
+  int64_t n_rows;                /* FTS5's nRow */
+} np_text_index;
+int np_hip_index_set_text(np_index* index, const np_text_index* text);
+
+/* A keyword query: phrases of term ids (-1 = a token the vocabulary does not hold), all joined by AND or all by OR.  Phrase
+ * p owns terms[phrase_offsets[p] .. phrase_offsets[p + 1]).  The tokenising front end (FTS5 query text -> term ids) is host
+ * work (next_plaid_amd/text.py).
+ *   result    what SQLite returns for SELECT rowid, CAST(-bm25(t) AS REAL) ... WHERE t MATCH ? [AND rowid IN subset] ORDER BY
+ *             score DESC LIMIT top_k, read as f32
+ *   frequency of a phrase in a document: the number of positions p with token j of the phrase at p + j for every j
+ *   match     AND: every phrase has frequency >= 1; OR: any has.  A phrase holding a -1 has frequency 0 everywhere
+ *   score     nHit_i = documents of the WHOLE table holding phrase i (never the subset's);
+ *             idf_i = log((nRow - nHit_i + 0.5) / (nHit_i + 0.5)), 1e-6 where that is <= 0, on the host in f64 with libm's log;
+ *             avgdl = (double)total_tokens / (double)nRow; k1 = 1.2, b = 0.75, D = the document's token count, a = the
+ *             frequency; score = 0.0, then in phrase order score += idf_i * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / avgdl)));
+ *             every operation IEEE f64, in this order, none fused; repeated phrases score repeatedly; the result is (float)score
+ *   order     f64 score descending, ties by ascending id (SQLite leaves ties unspecified); out_counts[i] = min(top_k,
+ *             matches); the rest of a row is padded as np_hip_search_exact pads it (id 0, score 0)
+ *   independent  query i's result is the same bits alone, in any batch, at any position, in any chunking (max_batch,
+ *             workspace_bytes) and from run to run: no float atomic, integer atomics only for counters and for slots
+ *             whose order a total-order sort then decides
+ *   subsets   the CSR arguments, their checks and their meaning are those of np_hip_search_exact: -1 = none, an empty subset
+ *             empties that query's result and no other, duplicate ids count once, ids outside [0, num_documents) are ignored
+ *   limits    1..NP_TEXT_MAX_PHRASES phrases, at least one token per phrase, at most NP_TEXT_MAX_TOKENS tokens per query, term
+ *             ids in [-1, n_terms), a known mode, 1 <= top_k <= NP_TEXT_MAX_TOPK, B < 65536, a handle with a keyword index
+ *             and without shards: NP_ERR_INVALID_ARGUMENT before any launch, the message names the query
+ *   memory    scratch comes out of the context's arena; the call runs in chunks of queries and of document slices that fit
+ *             the workspace budget, merged per query on the device.  A budget that holds no chunk is NP_ERR_OUT_OF_MEMORY
+ *   stats     ms_total, n_queries, n_ivf_ids = postings visited by the scoring pass; everything else 0
+ * A batch with a phrase of several tokens runs a counting pass first (nHit) and synchronises once to compute the idf on the
+ * host; a batch of single-token phrases takes the document frequencies it already has.  Re-entrant on a shared handle. */
+#define NP_TEXT_AND 0
+#define NP_TEXT_OR 1
+#define NP_TEXT_MAX_PHRASES 64
+#define NP_TEXT_MAX_TOKENS 256
+#define NP_TEXT_MAX_TOPK 1024
+typedef struct np_text_query {
+  const int32_t* terms;            /* [phrase_offsets[n_phrases]] */
+  const int32_t* phrase_offsets;   /* [n_phrases + 1], starts at 0, strictly increasing */
+  int32_t n_phrases;
+  int32_t mode;                    /* NP_TEXT_AND, NP_TEXT_OR */
+} np_text_query;
+int np_hip_text_search(const np_index* index, const np_text_query* queries, int32_t B, int32_t top_k,
+                       const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                       const int32_t* query_subset,
+                       int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+/* The same with the subsets' CSR and the outputs in HBM (the queries stay host structs: they are programs, as filters are);
+ * enqueues on `stream`.  A batch with a multi-token phrase synchronises the stream once (the counting pass). */
+int np_hip_text_search_device(const np_index* index, const np_text_query* queries, int32_t B, int32_t top_k,
+                              const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                              const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                              int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+/* ... and with filters in place of the subsets, as np_hip_search_exact_filtered is to np_hip_search_exact. */
+int np_hip_text_search_filtered(const np_index* index, const np_text_query* queries, int32_t B, int32_t top_k,
+                                const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+
+/* Fusion of a semantic and a keyword list per query (text_search.rs:1006-1075), f32 in the reference's order, unfused.  List
+ * i of either side is ids / scores [i * stride .. i * stride + counts[i]); out rows have top_k entries, padded with id 0 and
+ * score 0; out_counts[i] = min(top_k, distinct ids of the two lists).
+ *   NP_FUSE_RRF             entry r (0-based) of the semantic list adds alpha / (60.0f + (float)r + 1.0f), entry r of the
+ *                           keyword list (1.0f - alpha) / (60.0f + (float)r + 1.0f); a document starts at 0.0f and the
+ *                           semantic term is added first.  Scores are not read (they may be NULL)
+ *   NP_FUSE_RELATIVE_SCORE  each list is min-max normalised over its own entries, (s - min) / (max - min), 1.0f for every
+ *                           entry when max == min, nothing from an empty list, min / max ignoring NaN as f32::min / max do;
+ *                           then 0.0f + alpha * s_sem, then + (1.0f - alpha) * s_kw
+ *   order                   fused score descending, ties by ascending id, a NaN score after every number (the reference's
+ *                           tie order is a HashMap's)
+ * An id occurs at most once per list (not checked).  NP_ERR_INVALID_ARGUMENT: alpha outside [0, 1] or NaN (the handler's
+ * BadRequest), an unknown mode, top_k outside 1 .. 2 * NP_TEXT_MAX_TOPK, a stride or (host form) a count outside
+ * 0 .. NP_TEXT_MAX_TOPK; the device form clamps a count to its stride.  `index` names the device and lends a context; NULL =
+ * the current device (the host form then allocates and frees its own scratch). */
+#define NP_FUSE_RRF 0
+#define NP_FUSE_RELATIVE_SCORE 1
+int np_hip_fuse(const np_index* index, int32_t mode, float alpha, int32_t top_k, int32_t B,
+                const int64_t* sem_ids, const float* sem_scores, const int32_t* sem_counts, int32_t sem_stride,
+                const int64_t* kw_ids, const float* kw_scores, const int32_t* kw_counts, int32_t kw_stride,
+                int64_t* out_ids, float* out_scores, int32_t* out_counts);
+int np_hip_fuse_device(const np_index* index, int32_t mode, float alpha, int32_t top_k, int32_t B,
+                       const int64_t* d_sem_ids, const float* d_sem_scores, const int32_t* d_sem_counts, int32_t sem_stride,
+                       const int64_t* d_kw_ids, const float* d_kw_scores, const int32_t* d_kw_counts, int32_t kw_stride,
+                       int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+
+/* The hybrid request in one call: the semantic pass (np_hip_search_batch_subsets_device's pass with top_k = fetch_k), the
+ * keyword pass with top_k = fetch_k and the fusion to params->top_k, on one stream; neither list leaves HBM.  Query i gets,
+ * byte for byte, what np_hip_fuse returns for the outputs of np_hip_search_batch_subsets (or _filtered) and
+ * np_hip_text_search (or _filtered) called separately with the same arguments and top_k = fetch_k.  The scope is the
+ * subsets' CSR, or -- filters != NULL -- n_filters filters with query_subset as the query map (then subset_ids and
+ * subset_offsets are ignored and n_subsets is not read).  1 <= fetch_k <= NP_TEXT_MAX_TOPK (the handler takes 3 * top_k);
+ * 1 <= params->top_k <= 2 * NP_TEXT_MAX_TOPK.  stats: ms_total and n_queries of the whole call, n_ivf_ids of the keyword
+ * pass; everything else 0. */
+int np_hip_search_hybrid(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                         const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
+                         int32_t fusion,
+                         const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                         const int32_t* query_subset, const np_filter* filters, int32_t n_filters,
+                         int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best
  * n_sel = min(n_full_scores, max(n_full_scores/4, top_k)) candidates as 64-bit rank keys in

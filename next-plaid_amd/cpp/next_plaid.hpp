@@ -10,6 +10,7 @@
 //   index.search_batch(queries, params, parallel, subset)  index.rs:1279  -> query_id = batch position
 //   index.search_batch_subsets(queries, n, params, parallel, subsets)   one subset per query (a server's batch of requests)
 //   index.search_exact(queries, n, top_k, precision, subset) / search_exact_subsets(...)   every document scored: the exact top-k
+//   index.set_text(...) / text_search(...) / fuse(...) / search_hybrid(...)   the keyword half of a hybrid search (text_search.rs)
 //   SearchParameters (defaults search.rs:58-69), QueryResult (search.rs:71-80), Error (error.rs:9-66)
 //
 // Accelerator policy (the crate's precedent for its CUDA feature, lib.rs:71-84 and cuda.rs:52-182):
@@ -296,6 +297,34 @@ struct ColumnSpan {
   static ColumnSpan codes(const int32_t* d, size_t n, const uint8_t* valid = nullptr) { return {NP_COL_CODE, d, valid, n}; }
 };
 
+// A compiled keyword query (np_text_query), as FilterProgram is a compiled filter: phrases of term ids (-1 = a token the
+// vocabulary does not hold), all joined by AND or all by OR.  Compiling FTS5 query text into term ids needs SQLite's own
+// tokenizer and stays in the Python front end (next_plaid_amd/text.py); a Rust host would do it with rusqlite.
+class TextQuery {
+ public:
+  explicit TextQuery(int mode = NP_TEXT_AND) : mode_(mode), off_{0} {}
+  TextQuery& phrase(const std::vector<int32_t>& term_ids) {
+    terms_.insert(terms_.end(), term_ids.begin(), term_ids.end());
+    off_.push_back((int32_t)terms_.size());
+    return *this;
+  }
+  np_text_query c() const { return np_text_query{terms_.data(), off_.data(), (int32_t)off_.size() - 1, mode_}; }
+
+ private:
+  int mode_;
+  std::vector<int32_t> terms_, off_;
+};
+
+// The keyword index for MmapIndex::set_text: the FTS5 table's (term, document, position) instances, sorted, term t owning
+// [term_offsets[t], term_offsets[t + 1]), and the table's row count.
+struct TextIndexSpan {
+  const int64_t* term_offsets;
+  size_t n_terms;
+  const int64_t* inst_doc;
+  const int32_t* inst_pos;
+  int64_t n_rows;
+};
+
 class MmapIndex {
  public:
   // MmapIndex::create_with_kmeans (index.rs:927-967): k-means and codec training on the GPU, the crate's file set written
@@ -569,6 +598,104 @@ class MmapIndex {
     return out;
   }
 
+  // The keyword index (np_hip_index_set_text): replaces any earlier one, nullptr drops it.  Needs exclusive access to the
+  // handle.  reload() / update() leave a handle without one.
+  void set_text(const TextIndexSpan* t) {
+    require_device("set_text");
+    if (t) {
+      const np_text_index c{(int64_t)t->n_terms, t->term_offsets, t->inst_doc, t->inst_pos, t->n_rows};
+      check(np_hip_index_set_text(h_, &c));
+    } else {
+      check(np_hip_index_set_text(h_, nullptr));
+    }
+    check(np_hip_index_info(h_, &info_));
+  }
+
+  // BM25 keyword search with SQLite FTS5's results (np_hip_text_search; text_search.rs:1246-1342): per query the top_k
+  // documents by -bm25(), ties by ascending id.  One scope per query as search_exact_subsets takes them (an empty vector of
+  // subsets: none).  No CPU hand-off: the crate's CPU path is SQLite itself.
+  std::vector<QueryResult> text_search(const std::vector<TextQuery>& queries, size_t top_k,
+                                       const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("text_search");
+    const size_t n = queries.size();
+    if (!subsets.empty() && subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "text_search: one subset entry per query");
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
+    std::vector<np_text_query> q;
+    for (const TextQuery& t : queries) q.push_back(t.c());
+    const size_t k = std::max<size_t>(top_k, 1);
+    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
+    std::vector<float> sc(std::max<size_t>(n * k, 1));
+    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
+    check(np_hip_text_search(h_, q.data(), (int32_t)n, (int32_t)top_k, sids.data(), soff.data(), (int64_t)n_distinct, qsub.data(),
+                             ids.data(), sc.data(), cnt.data(), &last_stats));
+    return rows(ids, sc, cnt, n, k);
+  }
+
+  // Fusion of per-query semantic and keyword lists (np_hip_fuse; text_search.rs:1006-1075): mode NP_FUSE_RRF or
+  // NP_FUSE_RELATIVE_SCORE, f32 in the reference's order; fused score descending, ties by ascending id.
+  std::vector<QueryResult> fuse(int mode, float alpha, size_t top_k, const std::vector<QueryResult>& sem,
+                                const std::vector<QueryResult>& kw) const {
+    require_device("fuse");
+    const size_t n = sem.size();
+    if (kw.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "fuse: one keyword list per semantic list");
+    auto pack = [n](const std::vector<QueryResult>& l, std::vector<int64_t>& ids, std::vector<float>& sc, std::vector<int32_t>& cnt) {
+      size_t w = 1;
+      for (const QueryResult& r : l) w = std::max(w, r.passage_ids.size());
+      ids.assign(std::max<size_t>(n, 1) * w, 0);
+      sc.assign(std::max<size_t>(n, 1) * w, 0.f);
+      cnt.assign(std::max<size_t>(n, 1), 0);
+      for (size_t i = 0; i < n; ++i) {
+        std::copy(l[i].passage_ids.begin(), l[i].passage_ids.end(), ids.begin() + i * w);
+        std::copy(l[i].scores.begin(), l[i].scores.end(), sc.begin() + i * w);
+        cnt[i] = (int32_t)l[i].passage_ids.size();
+      }
+      return w;
+    };
+    std::vector<int64_t> si, ki;
+    std::vector<float> ss, ks;
+    std::vector<int32_t> scnt, kcnt;
+    const size_t sw = pack(sem, si, ss, scnt), kw_w = pack(kw, ki, ks, kcnt);
+    const size_t k = std::max<size_t>(top_k, 1);
+    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
+    std::vector<float> sc(std::max<size_t>(n * k, 1));
+    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
+    check(np_hip_fuse(h_, mode, alpha, (int32_t)top_k, (int32_t)n, si.data(), ss.data(), scnt.data(), (int32_t)sw, ki.data(), ks.data(),
+                      kcnt.data(), (int32_t)kw_w, ids.data(), sc.data(), cnt.data()));
+    return rows(ids, sc, cnt, n, k);
+  }
+
+  // The /search handler's hybrid request in one call (np_hip_search_hybrid): the semantic and the keyword pass with
+  // top_k = fetch_k (0: the handler's 3 * params.top_k) and their fusion to params.top_k, all on the device.
+  std::vector<QueryResult> search_hybrid(const Query* queries, const std::vector<TextQuery>& text_queries, const SearchParameters& params,
+                                         float alpha = 0.75f, int fusion = NP_FUSE_RELATIVE_SCORE, size_t fetch_k = 0,
+                                         const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("search_hybrid");
+    const size_t n = text_queries.size();
+    if (!subsets.empty() && subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_hybrid: one subset entry per query");
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
+    std::vector<np_text_query> q;
+    for (const TextQuery& t : text_queries) q.push_back(t.c());
+    const size_t dim = embedding_dim();
+    std::vector<int32_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
+    std::vector<float> flat((size_t)off[n] * dim);
+    for (size_t i = 0; i < n; ++i)
+      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+    const np_search_params p = params.c();
+    const size_t k = std::max<size_t>(params.top_k, 1);
+    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
+    std::vector<float> sc(std::max<size_t>(n * k, 1));
+    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
+    check(np_hip_search_hybrid(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, &p, q.data(),
+                               (int32_t)(fetch_k ? fetch_k : 3 * params.top_k), alpha, fusion, sids.data(), soff.data(),
+                               (int64_t)n_distinct, qsub.data(), nullptr, 0, ids.data(), sc.data(), cnt.data(), &last_stats));
+    return rows(ids, sc, cnt, n, k);
+  }
+
   // Given pairs with the per-token matches (np_hip_score_pairs; no crate counterpart, no CPU hand-off): query i against the
   // documents doc_ids[i] (global ids; duplicates allowed).  scores[p] is the S6 score of the pair -- the bits search_batch and
   // search_exact give it at precision 0 -- and, with return_matches, token_sims / token_pos hold one row of n_tokens entries
@@ -632,6 +759,17 @@ class MmapIndex {
       soff[j + 1] = (int64_t)sids.size();
     }
     return distinct.size();
+  }
+
+  static std::vector<QueryResult> rows(const std::vector<int64_t>& ids, const std::vector<float>& sc, const std::vector<int32_t>& cnt,
+                                       size_t n, size_t k) {
+    std::vector<QueryResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].query_id = i;
+      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
+      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
+    }
+    return out;
   }
 
   // The body of every batch call: pack the queries, `call` the library, apply the error and fallback policy (`cpu`: this

@@ -260,6 +260,20 @@ struct DeviceColumn {
   bool has_valid = false;
 };
 
+// the keyword index of a handle (np_hip_index_set_text, np_text.hip): per-term posting lists, the positions behind them and
+// every document's token count in HBM; what only the host needs (document frequencies, totals) stays there
+struct DeviceText {
+  int64_t n_terms = 0, n_post = 0, n_inst = 0, n_rows = 0, total_tokens = 0;
+  DevPtr<int64_t> post_off;     // [n_terms + 1] a term's postings
+  DevPtr<int32_t> post_doc;     // [n_post] document, ascending inside a term
+  DevPtr<int32_t> post_tf;      // [n_post] term frequency
+  DevPtr<int64_t> post_first;   // [n_post] index of the posting's first position in pos
+  DevPtr<int32_t> pos;          // [n_inst] positions, ascending inside a posting
+  DevPtr<int32_t> doc_len;      // [n_docs] tokens of a document (its instances)
+  std::vector<int64_t> h_post_off;   // host copy: a term's document frequency is the length of its list
+  bool present = false;
+};
+
 struct DeviceIndex {
   int device = 0;
   int64_t N_total = 0, n_emb_total = 0;
@@ -311,6 +325,8 @@ struct DeviceIndex {
   std::vector<DeviceColumn> columns;
   DevPtr<FilterCol> d_coltab;     // [columns.size()]
   size_t column_bytes = 0;        // the columns' share of device_bytes
+  DeviceText text;                // the keyword index (np_hip_index_set_text)
+  size_t text_bytes = 0;          // ... and its share of device_bytes
   size_t device_bytes = 0;
   np_open_opts opts{};
   // per-context scratch budget the planner uses.  A caller-given workspace_bytes is kept as it is; the default (what the device
@@ -409,6 +425,14 @@ int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n
                       bool for_search);
 int filter_eval_resident(const DeviceIndex* ix, hipStream_t st, DevBuf& scratch, DevBuf& out, const np_filter* filters,
                          int32_t n_filters, const int32_t* h_query_filter, int B, FilterCsr* csr);
+
+// np_search.hip: the pass of np_hip_search_batch_subsets_device on a context the caller already holds (np_hip_search_hybrid
+// runs the semantic and the keyword pass on one context and one stream).  The CSR is on the device; h_off / h_qsub are the
+// host copies the host entry points hand their passes (NULL where there is none), n_subsets == 0 = no subsets.
+int search_batch_in_use(const DeviceIndex* ix, ContextUse& use, const float* d_q, const int32_t* d_qoff, const int32_t* h_qoff,
+                        int B, int dim, const np_search_params* prm, const int64_t* d_ids, const int64_t* d_off,
+                        const int64_t* h_off, int64_t n_subsets, const int32_t* d_qsub, const int32_t* h_qsub,
+                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts);
 
 struct DeviceGuard {
   int prev = -1;

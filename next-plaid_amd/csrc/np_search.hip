@@ -1666,6 +1666,27 @@ int subset_doc_rows(const DeviceIndex* ix, hipStream_t st, const int64_t* d_ids,
   return NP_OK;
 }
 
+int search_batch_in_use(const DeviceIndex* ix, ContextUse& use, const float* d_q, const int32_t* d_qoff, const int32_t* h_qoff,
+                        int B, int dim, const np_search_params* prm, const int64_t* d_ids, const int64_t* d_off,
+                        const int64_t* h_off, int64_t n_subsets, const int32_t* d_qsub, const int32_t* h_qsub,
+                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts) {
+  NP_TRY(validate(ix, B, dim, prm));
+  if (B == 0) return NP_OK;
+  Subsets sub;
+  if (n_subsets > 0) {   // what np_hip_search_batch_subsets tells its pass
+    bool all_empty = h_off && h_qsub;
+    for (int b = 0; all_empty && b < B; ++b) all_empty = h_qsub[b] >= 0 && h_off[h_qsub[b] + 1] == h_off[h_qsub[b]];
+    sub.d = SubsetsP{d_ids, d_off, d_qsub, n_subsets, h_off[n_subsets]};
+    sub.all_empty = all_empty;
+    sub.h_off = h_off;
+    sub.h_qsub = h_qsub;
+  }
+  CallState cs;
+  cs.ctx = use.ctx;
+  cs.stream = use.stream;
+  return run_device(ix, &cs, d_q, d_qoff, h_qoff, B, prm, sub, d_out_ids, d_out_scores, d_out_counts);
+}
+
 // ---- document-sharded exchange: the strided forms np_dist.hip uses (one record per rank with a status trailer) -----
 int select_cut_strided(const DeviceIndex* ix, const uint64_t* d_all_keys, int64_t rank_stride, int64_t status_off, int G,
                        int B, int n_sel, uint64_t* d_cut, hipStream_t st) {

@@ -1,0 +1,1182 @@
+// np_text.hip -- the keyword half of a hybrid search on the device: the FTS5 index in HBM (np_hip_index_set_text), BM25
+// keyword search with SQLite's bits (np_hip_text_search), the fusion of a semantic and a keyword list (np_hip_fuse) and the
+// whole hybrid request (np_hip_search_hybrid).
+//
+//   text_hit_kernel    nHit of every phrase of several tokens: the documents of the WHOLE table that hold it.  One lane per
+//                      posting of the phrase's first token; an integer atomic adds the block's count (order cannot show)
+//   text_score_kernel  a workgroup takes one (query, slice of NP_TEXT_SLICE_DOCS consecutive documents).  One f64 accumulator
+//                      and one match count per document of the slice in LDS; the phrases are walked in order with a barrier
+//                      between them, each lane takes one posting of the phrase's first token inside the slice (a document
+//                      occurs once per posting list: lanes never collide, and phrase order is the summation order), reads the
+//                      stored frequency or intersects positions, and adds the bm25 term.  The slice's matching, eligible
+//                      documents are then sorted by (score, id) and the best `keep` leave as the slice's list
+//   text_merge_kernel  per query: the lists of a chunk's slices and the result of the chunks before it, merged through a
+//                      2048-entry window in LDS by the same total order
+//   fuse_kernel        per query: the two lists in LDS, the fused scores in f32 in the reference's order, one sort
+// The f64 arithmetic of a score is SQLite's expression, operation for operation (this file is compiled with
+// -ffp-contract=off: no product and sum may be fused); the idf needs libm's log and is computed on the host.
+#include "np_internal.h"
+#include "np_text_plan.h"
+
+#include <chrono>
+#include <string.h>
+
+namespace np {
+
+constexpr int TEXT_TPB = 256;
+constexpr int TEXT_SLICE = (int)NP_TEXT_SLICE_DOCS;
+constexpr int TEXT_WINDOW = 2 * NP_TEXT_MAX_TOPK;   // entries of the merge window and of a fusion
+
+struct TextIxP {
+  const int64_t* post_off;
+  const int32_t* post_doc;
+  const int32_t* post_tf;
+  const int64_t* post_first;
+  const int32_t* pos;
+  const int32_t* doc_len;
+};
+
+// first index in [lo, hi) of an ascending i32 array with a[i] >= v
+__device__ __forceinline__ int64_t text_lower_bound(const int32_t* __restrict__ a, int64_t lo, int64_t hi, int64_t v) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// occurrences of the phrase terms[0 .. nt) in the document of posting j0 (a posting of terms[0]): positions p of terms[0]
+// with terms[k] at p + k for every k
+__device__ __forceinline__ int text_phrase_freq(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int64_t j0, int doc) {
+  const int tf0 = t.post_tf[j0];
+  if (nt == 1) return tf0;
+  const int64_t f0 = t.post_first[j0];
+  int freq = 0;
+  for (int x = 0; x < tf0; ++x) {
+    const int64_t p = t.pos[f0 + x];
+    bool ok = true;
+    for (int k = 1; k < nt && ok; ++k) {
+      const int term = terms[k];
+      const int64_t e = t.post_off[term + 1];
+      const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
+      if (jk >= e || t.post_doc[jk] != doc) return 0;   // the document lacks a token of the phrase
+      const int64_t pe = t.post_first[jk] + t.post_tf[jk];
+      const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, p + k);
+      ok = at < pe && (int64_t)t.pos[at] == p + k;
+    }
+    freq += ok ? 1 : 0;
+  }
+  return freq;
+}
+
+struct TextHitP {
+  TextIxP t;
+  const int32_t* phr_tok;
+  const int32_t* terms;
+  const int32_t* item_phr;         // [items] phrases of several known tokens
+  unsigned long long* nhit;        // [items]
+};
+
+__global__ void __launch_bounds__(TEXT_TPB) text_hit_kernel(TextHitP p) {
+  __shared__ uint32_t part[TEXT_TPB / 64];
+  const int item = blockIdx.y, tid = threadIdx.x;
+  const int phr = p.item_phr[item];
+  const int tb = p.phr_tok[phr], nt = p.phr_tok[phr + 1] - tb;
+  const int32_t* terms = p.terms + tb;
+  const int64_t lo = p.t.post_off[terms[0]], hi = p.t.post_off[terms[0] + 1];
+  uint32_t c = 0;
+  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
+    c += text_phrase_freq(p.t, terms, nt, j, p.t.post_doc[j]) > 0 ? 1u : 0u;
+  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
+  if ((tid & 63) == 0) part[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t all = part[0] + part[1] + part[2] + part[3];
+    if (all) atomicAdd(&p.nhit[item], (unsigned long long)all);
+  }
+}
+
+struct TextScoreP {
+  TextIxP t;
+  const int32_t* q_phr;      // [B + 1] a query's phrases
+  const int32_t* phr_tok;    // [phrases + 1] a phrase's tokens
+  const int32_t* terms;
+  const double* idf;         // [phrases]
+  const int32_t* mode;       // [B]
+  int q0;                    // first query of the chunk
+  int64_t s0;                // first slice of the chunk
+  int64_t n_docs;
+  double avgdl;
+  int keep;                  // entries a slice hands on
+  const int32_t* qrow;       // [chunk queries] row of docbits, -1 = no subset; NULL = no subsets at all
+  const uint32_t* docbits;   // [rows][NW]
+  int64_t NW;
+  int64_t S;                 // slices per query in the lists (the plan's)
+  unsigned long long* list_keys;   // [chunk queries][S][keep] bits of the f64 score (positive: they order as integers)
+  int32_t* list_ids;
+  int32_t* list_cnt;         // [chunk queries][S]
+  unsigned long long* ctr;   // postings visited, or NULL
+};
+
+__global__ void __launch_bounds__(TEXT_TPB) text_score_kernel(TextScoreP p) {
+  __shared__ double s_acc[TEXT_SLICE];
+  __shared__ uint8_t s_cnt[TEXT_SLICE];
+  __shared__ uint16_t s_idx[TEXT_SLICE];
+  __shared__ int64_t s_lo[NP_TEXT_MAX_PHRASES], s_hi[NP_TEXT_MAX_PHRASES];
+  __shared__ int s_any, s_all, s_n;
+  const int tid = threadIdx.x, ql = blockIdx.y, q = p.q0 + ql;
+  const int64_t sl = blockIdx.x;
+  const int64_t d0 = (p.s0 + sl) * TEXT_SLICE;
+  const int n = p.n_docs - d0 < TEXT_SLICE ? (int)(p.n_docs - d0) : TEXT_SLICE;
+  const int ph0 = p.q_phr[q], nph = p.q_phr[q + 1] - ph0;
+  const int row = p.qrow ? p.qrow[ql] : -1;
+  const int64_t o = (int64_t)ql * p.S + sl;
+  if (tid == 0) {
+    s_any = 0;
+    s_all = 1;
+    s_n = 0;
+  }
+  __syncthreads();
+  // the slice's part of every phrase's first posting list
+  if (tid < nph) {
+    const int tb = p.phr_tok[ph0 + tid], te = p.phr_tok[ph0 + tid + 1];
+    bool known = true;
+    for (int k = tb; k < te; ++k) known = known && p.terms[k] >= 0;
+    int64_t lo = 0, hi = 0;
+    if (known) {
+      const int term = p.terms[tb];
+      const int64_t e = p.t.post_off[term + 1];
+      lo = text_lower_bound(p.t.post_doc, p.t.post_off[term], e, d0);
+      hi = text_lower_bound(p.t.post_doc, lo, e, d0 + n);
+    }
+    s_lo[tid] = lo;
+    s_hi[tid] = hi;
+    if (hi > lo) atomicOr(&s_any, 1); else atomicAnd(&s_all, 0);
+  }
+  __syncthreads();
+  const bool is_and = p.mode[q] == NP_TEXT_AND;
+  if (!s_any || (is_and && !s_all)) {   // (block-uniform) nothing of the slice can match
+    if (tid == 0) p.list_cnt[o] = 0;
+    return;
+  }
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    s_acc[i] = 0.0;
+    s_cnt[i] = 0;
+  }
+  __syncthreads();
+  const double k1 = 1.2, b = 0.75;
+  unsigned long long visited = 0;
+  for (int ph = 0; ph < nph; ++ph) {
+    const int64_t lo = s_lo[ph], hi = s_hi[ph];
+    const int tb = p.phr_tok[ph0 + ph], nt = p.phr_tok[ph0 + ph + 1] - tb;
+    const double idf = p.idf[ph0 + ph];
+    for (int64_t j = lo + tid; j < hi; j += TEXT_TPB) {
+      const int doc = p.t.post_doc[j];
+      const int freq = text_phrase_freq(p.t, p.terms + tb, nt, j, doc);
+      if (freq > 0) {
+        const int l = (int)(doc - d0);
+        const double a = (double)freq, D = (double)p.t.doc_len[doc];
+        s_acc[l] = s_acc[l] + idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / p.avgdl)));
+        s_cnt[l] = (uint8_t)(s_cnt[l] + 1);
+      }
+    }
+    visited += (unsigned long long)(hi - lo);
+    __syncthreads();
+  }
+  if (p.ctr && tid == 0 && visited) atomicAdd(p.ctr, visited);
+  // the slice's matching documents in scope: slots from a counter, the order from the sort below
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    bool m = is_and ? s_cnt[i] == nph : s_cnt[i] > 0;
+    if (m && row >= 0) {
+      const int64_t d = d0 + i;
+      m = ((p.docbits[(int64_t)row * p.NW + (d >> 5)] >> (d & 31)) & 1u) != 0;
+    }
+    if (m) s_idx[atomicAdd(&s_n, 1)] = (uint16_t)i;
+  }
+  __syncthreads();
+  const int nm = s_n;
+  if (nm == 0) {
+    if (tid == 0) p.list_cnt[o] = 0;
+    return;
+  }
+  int P2 = 1;
+  while (P2 < nm) P2 <<= 1;
+  for (int i = nm + tid; i < P2; i += TEXT_TPB) s_idx[i] = 0xFFFF;
+  // bitonic sort of the indexes: score descending (a match's score is positive: its bits order as integers), then id
+  auto before = [&](uint16_t x, uint16_t y) {
+    if (x == 0xFFFF) return false;
+    if (y == 0xFFFF) return true;
+    const unsigned long long kx = (unsigned long long)__double_as_longlong(s_acc[x]), ky = (unsigned long long)__double_as_longlong(s_acc[y]);
+    return kx > ky || (kx == ky && x < y);
+  };
+  for (int k = 2; k <= P2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < P2; i += TEXT_TPB) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint16_t x = s_idx[i], y = s_idx[ixj];
+          if ((i & k) == 0 ? before(y, x) : before(x, y)) {
+            s_idx[i] = y;
+            s_idx[ixj] = x;
+          }
+        }
+      }
+    }
+  __syncthreads();
+  const int kept = min(nm, p.keep);
+  for (int r = tid; r < kept; r += TEXT_TPB) {
+    const int l = s_idx[r];
+    p.list_keys[o * p.keep + r] = (unsigned long long)__double_as_longlong(s_acc[l]);
+    p.list_ids[o * p.keep + r] = (int32_t)(d0 + l);
+  }
+  if (tid == 0) p.list_cnt[o] = kept;
+}
+
+// (key descending, id ascending) over the first `fill` entries of a window; entries up to the next power of two are padded
+// with key 0 (no match has it).  Returns min(fill, top_k).  Every thread of the block calls it.
+__device__ int text_sort_cut(unsigned long long* s_k, int32_t* s_i, int fill, int top_k, int tid) {
+  int P2 = 1;
+  while (P2 < fill) P2 <<= 1;
+  __syncthreads();
+  for (int i = fill + tid; i < P2; i += TEXT_TPB) {
+    s_k[i] = 0ull;
+    s_i[i] = 0x7FFFFFFF;
+  }
+  for (int k = 2; k <= P2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < P2; i += TEXT_TPB) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const unsigned long long ka = s_k[i], kb = s_k[ixj];
+          const int32_t ia = s_i[i], ib = s_i[ixj];
+          const bool a_first = ka > kb || (ka == kb && ia < ib);
+          const bool b_first = kb > ka || (ka == kb && ib < ia);
+          if ((i & k) == 0 ? b_first : a_first) {
+            s_k[i] = kb;
+            s_i[i] = ib;
+            s_k[ixj] = ka;
+            s_i[ixj] = ia;
+          }
+        }
+      }
+    }
+  __syncthreads();
+  return min(fill, top_k);
+}
+
+struct TextMergeP {
+  const unsigned long long* list_keys;
+  const int32_t* list_ids;
+  const int32_t* list_cnt;
+  int64_t S, Sn;             // slices per query in the lists; slices of this chunk
+  int keep;
+  int n_prev;                // 0 on a query's first chunk of slices, else best[] holds the result so far
+  unsigned long long* best_keys;   // [chunk queries][top_k]
+  int32_t* best_ids;
+  int32_t* best_cnt;
+  int top_k;
+  int64_t* out_ids;          // [chunk queries][top_k]
+  float* out_scores;
+  int32_t* out_counts;
+};
+
+__global__ void __launch_bounds__(TEXT_TPB) text_merge_kernel(TextMergeP p) {
+  __shared__ unsigned long long s_k[TEXT_WINDOW];
+  __shared__ int32_t s_i[TEXT_WINDOW];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int fill = 0;
+  if (p.n_prev) {
+    fill = p.best_cnt[b];
+    for (int i = tid; i < fill; i += TEXT_TPB) {
+      s_k[i] = p.best_keys[(int64_t)b * p.top_k + i];
+      s_i[i] = p.best_ids[(int64_t)b * p.top_k + i];
+    }
+  }
+  for (int64_t s = 0; s < p.Sn; ++s) {
+    const int64_t o = (int64_t)b * p.S + s;
+    const int c = p.list_cnt[o];   // block-uniform; at most keep <= 1024, and top_k + keep fits the window
+    if (c == 0) continue;
+    if (fill + c > TEXT_WINDOW) fill = text_sort_cut(s_k, s_i, fill, p.top_k, tid);
+    for (int i = tid; i < c; i += TEXT_TPB) {
+      s_k[fill + i] = p.list_keys[o * p.keep + i];
+      s_i[fill + i] = p.list_ids[o * p.keep + i];
+    }
+    fill += c;
+  }
+  fill = text_sort_cut(s_k, s_i, fill, p.top_k, tid);
+  for (int j = tid; j < p.top_k; j += TEXT_TPB) {
+    const int64_t at = (int64_t)b * p.top_k + j;
+    const bool in = j < fill;
+    p.best_keys[at] = in ? s_k[j] : 0ull;
+    p.best_ids[at] = in ? s_i[j] : 0;
+    p.out_ids[at] = in ? (int64_t)s_i[j] : 0;
+    p.out_scores[at] = in ? (float)__longlong_as_double((long long)s_k[j]) : 0.f;
+  }
+  if (tid == 0) {
+    p.best_cnt[b] = fill;
+    p.out_counts[b] = fill;
+  }
+}
+
+// ---- fusion ------------------------------------------------------------------------------------------------------------
+struct FuseP {
+  int mode;
+  float alpha;
+  int top_k;
+  const int64_t* sem_ids;
+  const float* sem_sc;
+  const int32_t* sem_cnt;
+  int sem_stride;
+  const int64_t* kw_ids;
+  const float* kw_sc;
+  const int32_t* kw_cnt;
+  int kw_stride;
+  int64_t* out_ids;
+  float* out_sc;
+  int32_t* out_cnt;
+};
+
+// min and max of a list ignoring NaN (f32::min / max), to every thread; INFINITY / -INFINITY for a list of NaNs
+__device__ void fuse_min_max(const float* __restrict__ v, int n, float* s_red, float* mn, float* mx) {
+  const int tid = threadIdx.x;
+  float lo = INFINITY, hi = -INFINITY;
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    lo = fminf(lo, v[i]);
+    hi = fmaxf(hi, v[i]);
+  }
+  for (int s = 32; s > 0; s >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, s));
+    hi = fmaxf(hi, __shfl_xor(hi, s));
+  }
+  __syncthreads();
+  if ((tid & 63) == 0) {
+    s_red[tid >> 6] = lo;
+    s_red[4 + (tid >> 6)] = hi;
+  }
+  __syncthreads();
+  *mn = fminf(fminf(s_red[0], s_red[1]), fminf(s_red[2], s_red[3]));
+  *mx = fmaxf(fmaxf(s_red[4], s_red[5]), fmaxf(s_red[6], s_red[7]));
+}
+
+// a fused score as an integer that orders like it: NaN lowest, then -inf .. +inf (both zeros alike); 0 is left for padding
+__device__ __forceinline__ uint32_t fuse_order(float s) {
+  if (s != s) return 1u;
+  if (s == 0.0f) s = 0.0f;
+  const uint32_t u = __float_as_uint(s);
+  return ((u & 0x80000000u) ? ~u : (u | 0x80000000u)) + 1u;
+}
+
+__global__ void __launch_bounds__(TEXT_TPB) fuse_kernel(FuseP p) {
+  __shared__ int64_t s_id[TEXT_WINDOW];
+  __shared__ float s_sc[TEXT_WINDOW];
+  __shared__ uint32_t s_key[TEXT_WINDOW];
+  __shared__ float s_red[8];
+  __shared__ int s_n;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int ns = max(0, min(p.sem_cnt[b], p.sem_stride)), nk = max(0, min(p.kw_cnt[b], p.kw_stride));
+  const int64_t* sid = p.sem_ids + (int64_t)b * p.sem_stride;
+  const int64_t* kid = p.kw_ids + (int64_t)b * p.kw_stride;
+  const float* ssc = p.sem_sc ? p.sem_sc + (int64_t)b * p.sem_stride : nullptr;
+  const float* ksc = p.kw_sc ? p.kw_sc + (int64_t)b * p.kw_stride : nullptr;
+  const bool rrf = p.mode == NP_FUSE_RRF;
+  const float alpha = p.alpha, beta = 1.0f - p.alpha;
+  float smin = 0.f, smax = 0.f, kmin = 0.f, kmax = 0.f;
+  if (!rrf) {
+    fuse_min_max(ssc, ns, s_red, &smin, &smax);
+    fuse_min_max(ksc, nk, s_red, &kmin, &kmax);
+  }
+  if (tid == 0) s_n = ns;
+  for (int r = tid; r < ns; r += TEXT_TPB) {
+    float x;
+    if (rrf) {
+      x = alpha / (60.0f + (float)r + 1.0f);
+    } else {
+      const float nrm = smax == smin ? 1.0f : (ssc[r] - smin) / (smax - smin);
+      x = alpha * nrm;
+    }
+    s_id[r] = sid[r];
+    s_sc[r] = 0.0f + x;
+  }
+  __syncthreads();
+  for (int r = tid; r < nk; r += TEXT_TPB) {
+    float y;
+    if (rrf) {
+      y = beta / (60.0f + (float)r + 1.0f);
+    } else {
+      const float nrm = kmax == kmin ? 1.0f : (ksc[r] - kmin) / (kmax - kmin);
+      y = beta * nrm;
+    }
+    const int64_t id = kid[r];
+    int m = -1;
+    for (int i = 0; i < ns; ++i)
+      if (s_id[i] == id) {
+        m = i;
+        break;
+      }
+    if (m >= 0) {   // (an id occurs once per list: no other lane has this entry)
+      s_sc[m] = s_sc[m] + y;
+    } else {        // slots from a counter, the order from the sort below
+      const int at = atomicAdd(&s_n, 1);
+      s_id[at] = id;
+      s_sc[at] = 0.0f + y;
+    }
+  }
+  __syncthreads();
+  const int n = s_n;
+  int P2 = 1;
+  while (P2 < n) P2 <<= 1;
+  for (int i = tid; i < P2; i += TEXT_TPB) {
+    if (i < n) {
+      s_key[i] = fuse_order(s_sc[i]);
+    } else {
+      s_key[i] = 0u;
+      s_id[i] = 0x7FFFFFFFFFFFFFFFll;
+      s_sc[i] = 0.f;
+    }
+  }
+  for (int k = 2; k <= P2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < P2; i += TEXT_TPB) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint32_t ka = s_key[i], kb = s_key[ixj];
+          const int64_t ia = s_id[i], ib = s_id[ixj];
+          const bool a_first = ka > kb || (ka == kb && ia < ib);
+          const bool b_first = kb > ka || (ka == kb && ib < ia);
+          if ((i & k) == 0 ? b_first : a_first) {
+            const float fa = s_sc[i], fb = s_sc[ixj];
+            s_key[i] = kb;
+            s_id[i] = ib;
+            s_sc[i] = fb;
+            s_key[ixj] = ka;
+            s_id[ixj] = ia;
+            s_sc[ixj] = fa;
+          }
+        }
+      }
+    }
+  __syncthreads();
+  const int cnt = min(n, p.top_k);
+  for (int j = tid; j < p.top_k; j += TEXT_TPB) {
+    const int64_t at = (int64_t)b * p.top_k + j;
+    p.out_ids[at] = j < cnt ? s_id[j] : 0;
+    p.out_sc[at] = j < cnt ? s_sc[j] : 0.f;
+  }
+  if (tid == 0) p.out_cnt[b] = cnt;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------
+
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+static int text_check_handle(const DeviceIndex* ix, bool need_text) {
+  if (!ix) {
+    set_error("Text search failed: NULL index");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (ix->opts.shard_count > 1) {
+    set_error("Text search failed: the keyword index needs the whole index on the handle (opened with shard_count = %d): nRow, "
+              "the average length and the hit counts are global figures",
+              ix->opts.shard_count);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (need_text && !ix->text.present) {
+    set_error("Text search failed: the handle has no keyword index (np_hip_index_set_text)");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+static int text_check_queries(const DeviceIndex* ix, const np_text_query* queries, int B, int top_k) {
+  NP_TRY(text_check_handle(ix, true));
+  const char* why = "";
+  if (text_check_call(B, top_k, &why) != 0) {
+    set_error("Text search failed: %s (B=%d top_k=%d)", why, B, top_k);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B > 0 && !queries) {
+    set_error("Text search failed: NULL queries");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  char msg[240];
+  for (int q = 0; q < B; ++q)
+    if (text_check_query(&queries[q], q, ix->text.n_terms, msg, sizeof msg) != 0) {
+      set_error("Text search failed: %s", msg);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  return NP_OK;
+}
+
+// A batch's queries as the kernels read them, one blob: q_phr | phr_tok | terms | mode | item_phr | nhit | idf
+struct TextProg {
+  int B = 0;
+  int64_t n_phr = 0, n_tok = 0, n_items = 0;
+  int64_t max_item_df = 0;
+  size_t o_qphr = 0, o_ptok = 0, o_terms = 0, o_mode = 0, o_item = 0, o_nhit = 0, o_idf = 0, bytes = 0;
+  std::vector<char> blob;
+  std::vector<int64_t> phr_hit;   // nHit where the host knows it, -1 where the counting pass says
+  int32_t* at32(size_t off) { return (int32_t*)(blob.data() + off); }
+  void build(const DeviceIndex* ix, const np_text_query* qs, int B_) {
+    B = B_;
+    for (int q = 0; q < B; ++q) {
+      n_phr += qs[q].n_phrases;
+      n_tok += qs[q].phrase_offsets[qs[q].n_phrases];
+    }
+    phr_hit.assign((size_t)n_phr, 0);
+    std::vector<int32_t> items;
+    // sizes first: the items are known only after a walk
+    o_qphr = 0;
+    o_ptok = o_qphr + up256((size_t)(B + 1) * 4);
+    o_terms = o_ptok + up256((size_t)(n_phr + 1) * 4);
+    o_mode = o_terms + up256((size_t)std::max<int64_t>(n_tok, 1) * 4);
+    o_item = o_mode + up256((size_t)std::max(B, 1) * 4);
+    o_nhit = o_item + up256((size_t)std::max<int64_t>(n_phr, 1) * 4);
+    o_idf = o_nhit + up256((size_t)std::max<int64_t>(n_phr, 1) * 8);
+    bytes = o_idf + up256((size_t)std::max<int64_t>(n_phr, 1) * 8);
+    blob.assign(bytes, 0);
+    int32_t *qphr = at32(o_qphr), *ptok = at32(o_ptok), *terms = at32(o_terms), *mode = at32(o_mode), *item = at32(o_item);
+    int64_t ph = 0, tk = 0;
+    const std::vector<int64_t>& off = ix->text.h_post_off;
+    for (int q = 0; q < B; ++q) {
+      qphr[q] = (int32_t)ph;
+      mode[q] = qs[q].mode;
+      for (int i = 0; i < qs[q].n_phrases; ++i, ++ph) {
+        ptok[ph] = (int32_t)tk;
+        const int tb = qs[q].phrase_offsets[i], te = qs[q].phrase_offsets[i + 1];
+        bool known = true;
+        for (int k = tb; k < te; ++k) {
+          terms[tk++] = qs[q].terms[k];
+          known = known && qs[q].terms[k] >= 0;
+        }
+        if (!known) {
+          phr_hit[ph] = 0;
+        } else if (te - tb == 1) {
+          phr_hit[ph] = off[qs[q].terms[tb] + 1] - off[qs[q].terms[tb]];
+        } else {
+          phr_hit[ph] = -1;
+          item[n_items++] = (int32_t)ph;
+          max_item_df = std::max(max_item_df, off[qs[q].terms[tb] + 1] - off[qs[q].terms[tb]]);
+        }
+      }
+    }
+    qphr[B] = (int32_t)ph;
+    ptok[ph] = (int32_t)tk;
+  }
+};
+
+struct TextSubsets {
+  const int64_t* d_ids = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t* d_qsub = nullptr;
+  int64_t n = 0, total = 0;
+  const int64_t* h_off = nullptr;    // host copies where the caller has them
+  const int32_t* h_qsub = nullptr;
+};
+
+// bytes of the arena that scale with the chunk's queries -- one expression for the plan and for the carve-up
+static int64_t text_per_query(const DeviceIndex* ix, int top_k, bool subsets) {
+  const int64_t NW = std::max<int64_t>((ix->n_docs + 31) / 32, 1);
+  return (int64_t)up256((size_t)top_k * 8) + (int64_t)up256((size_t)top_k * 4) + 8 + (subsets ? (int64_t)up256((size_t)NW * 4) : 0);
+}
+static int64_t text_n_slices(const DeviceIndex* ix) {
+  return std::max<int64_t>(1, (ix->n_docs + NP_TEXT_SLICE_DOCS - 1) / NP_TEXT_SLICE_DOCS);
+}
+static int64_t text_fixed_bytes(const TextProg& prog) { return (int64_t)prog.bytes + 4096; }
+static size_t text_arena_bytes(const DeviceIndex* ix, const TextPlan& plan, const TextProg& prog, int top_k, bool subsets) {
+  const size_t pairs = (size_t)plan.queries * (size_t)plan.slices, keep = (size_t)text_slice_keep(top_k);
+  return (size_t)text_fixed_bytes(prog) + (size_t)plan.queries * (size_t)text_per_query(ix, top_k, subsets) + up256(pairs * keep * 8) +
+         up256(pairs * keep * 4) + up256(pairs * 4);
+}
+static int text_plan_for(const DeviceIndex* ix, int64_t user, const TextProg& prog, int B, int top_k, bool subsets, TextPlan* plan) {
+  const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
+  // (the three list arrays are each rounded up to 256 bytes: 768 more than the plan's pairs)
+  if (!text_plan(budget, user + text_fixed_bytes(prog) + 1024, text_per_query(ix, top_k, subsets), text_n_slices(ix), B,
+                 ix->opts.max_batch, top_k, plan)) {
+    set_error("Text search failed: one query over one slice of %lld documents does not fit the workspace budget of %lld bytes",
+              (long long)NP_TEXT_SLICE_DOCS, (long long)budget);
+    return NP_ERR_OUT_OF_MEMORY;
+  }
+  return NP_OK;
+}
+
+// The whole batch on device buffers.  `base`: the part of the arena this function carves (text_arena_bytes).  `pin`: pinned
+// host staging of prog.bytes for the programs (the caller synchronises the stream before it reuses it), or NULL: pageable
+// copies, and the stream is synchronised after the upload.  *visited (nullable): postings the scoring pass visited
+// (synchronises).
+static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pin, const TextPlan& plan, TextProg& prog, int top_k,
+                    const TextSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited) {
+  hipStream_t st = use.stream;
+  const DeviceText& tx = ix->text;
+  const int B = prog.B;
+  const bool subsets = sub.n > 0;
+  const int64_t NW = std::max<int64_t>((ix->n_docs + 31) / 32, 1);
+  const int Q = plan.queries;
+  const int64_t S = plan.slices, n_slices = text_n_slices(ix);
+  const int keep = (int)text_slice_keep(top_k);
+  char* at = base;
+  auto take = [&](size_t bytes) {
+    char* r = at;
+    at += up256(bytes);
+    return r;
+  };
+  char* d_prog = take(prog.bytes);
+  unsigned long long* ctr = (unsigned long long*)take(8);
+  unsigned long long* best_keys = (unsigned long long*)take((size_t)Q * up256((size_t)top_k * 8));
+  int32_t* best_ids = (int32_t*)take((size_t)Q * up256((size_t)top_k * 4));
+  int32_t* best_cnt = (int32_t*)take((size_t)Q * 4);
+  int32_t* qrow = (int32_t*)take((size_t)Q * 4);
+  uint32_t* docbits = subsets ? (uint32_t*)take((size_t)Q * up256((size_t)NW * 4)) : nullptr;
+  unsigned long long* list_keys = (unsigned long long*)take((size_t)Q * S * keep * 8);
+  int32_t* list_ids = (int32_t*)take((size_t)Q * S * keep * 4);
+  int32_t* list_cnt = (int32_t*)take((size_t)Q * S * 4);
+  const TextIxP tp{tx.post_off.get(), tx.post_doc.get(), tx.post_tf.get(), tx.post_first.get(), tx.pos.get(), tx.doc_len.get()};
+  // the programs (everything before the hit counts), then the idf once every nHit is known
+  char* src = prog.blob.data();
+  if (pin) {
+    memcpy(pin, src, prog.bytes);
+    src = pin;
+  }
+  NP_HIP(hipMemcpyAsync(d_prog, src, prog.o_nhit, hipMemcpyHostToDevice, st));
+  unsigned long long* h_nhit = (unsigned long long*)(src + prog.o_nhit);
+  if (prog.n_items > 0) {
+    NP_HIP(hipMemsetAsync(d_prog + prog.o_nhit, 0, (size_t)prog.n_items * 8, st));
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(512, (prog.max_item_df + TEXT_TPB - 1) / TEXT_TPB));
+    for (int64_t i0 = 0; i0 < prog.n_items; i0 += 65535) {   // (the items are a grid dimension)
+      const TextHitP hp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
+                        (const int32_t*)(d_prog + prog.o_item) + i0, (unsigned long long*)(d_prog + prog.o_nhit) + i0};
+      text_hit_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0)), TEXT_TPB, 0, st>>>(hp);
+    }
+    NP_HIP(hipGetLastError());
+    NP_HIP(hipMemcpyAsync(h_nhit, d_prog + prog.o_nhit, (size_t)prog.n_items * 8, hipMemcpyDeviceToHost, st));
+    NP_HIP(hipStreamSynchronize(st));
+    const int32_t* item = (const int32_t*)(prog.blob.data() + prog.o_item);
+    for (int64_t i = 0; i < prog.n_items; ++i) prog.phr_hit[(size_t)item[i]] = (int64_t)h_nhit[i];
+  }
+  double* h_idf = (double*)(src + prog.o_idf);
+  for (int64_t ph = 0; ph < prog.n_phr; ++ph) h_idf[ph] = text_idf(tx.n_rows, prog.phr_hit[(size_t)ph]);
+  NP_HIP(hipMemcpyAsync(d_prog + prog.o_idf, h_idf, (size_t)std::max<int64_t>(prog.n_phr, 1) * 8, hipMemcpyHostToDevice, st));
+  if (!pin) NP_HIP(hipStreamSynchronize(st));   // pageable sources: the copies complete before the blob goes out of scope
+  if (visited) NP_HIP(hipMemsetAsync(ctr, 0, 8, st));
+  const double avgdl = (double)tx.total_tokens / (double)tx.n_rows;
+  for (int q0 = 0; q0 < B; q0 += Q) {
+    const int Qn = std::min(Q, B - q0);
+    bool chunk_subsets = subsets;
+    if (subsets) {
+      int64_t lo = 0, hi = sub.total;
+      if (sub.h_off && sub.h_qsub) {   // only the ids this chunk's queries reference
+        lo = sub.total;
+        hi = 0;
+        chunk_subsets = false;
+        for (int b = 0; b < Qn; ++b) {
+          const int32_t s = sub.h_qsub[q0 + b];
+          if (s < 0) continue;
+          chunk_subsets = true;
+          if (sub.h_off[s + 1] == sub.h_off[s]) continue;
+          lo = std::min(lo, sub.h_off[s]);
+          hi = std::max(hi, sub.h_off[s + 1]);
+        }
+        if (hi < lo) lo = hi = 0;
+      }
+      if (chunk_subsets)
+        NP_TRY(subset_doc_rows(ix, st, sub.d_ids, sub.d_off, sub.d_qsub + q0, sub.n, sub.total, lo, hi, Qn, NW, docbits, qrow));
+    }
+    for (int64_t s0 = 0; s0 < n_slices; s0 += S) {
+      const int64_t Sn = std::min(S, n_slices - s0);
+      TextScoreP sp;
+      sp.t = tp;
+      sp.q_phr = (const int32_t*)(d_prog + prog.o_qphr);
+      sp.phr_tok = (const int32_t*)(d_prog + prog.o_ptok);
+      sp.terms = (const int32_t*)(d_prog + prog.o_terms);
+      sp.idf = (const double*)(d_prog + prog.o_idf);
+      sp.mode = (const int32_t*)(d_prog + prog.o_mode);
+      sp.q0 = q0;
+      sp.s0 = s0;
+      sp.n_docs = ix->n_docs;
+      sp.avgdl = avgdl;
+      sp.keep = keep;
+      sp.qrow = chunk_subsets ? qrow : nullptr;
+      sp.docbits = docbits;
+      sp.NW = NW;
+      sp.S = S;
+      sp.list_keys = list_keys;
+      sp.list_ids = list_ids;
+      sp.list_cnt = list_cnt;
+      sp.ctr = visited ? ctr : nullptr;
+      if (ix->n_docs > 0)
+        text_score_kernel<<<dim3((unsigned)Sn, (unsigned)Qn), TEXT_TPB, 0, st>>>(sp);
+      TextMergeP mp;
+      mp.list_keys = list_keys;
+      mp.list_ids = list_ids;
+      mp.list_cnt = list_cnt;
+      mp.S = S;
+      mp.Sn = ix->n_docs > 0 ? Sn : 0;
+      mp.keep = keep;
+      mp.n_prev = s0 > 0 ? 1 : 0;
+      mp.best_keys = best_keys;
+      mp.best_ids = best_ids;
+      mp.best_cnt = best_cnt;
+      mp.top_k = top_k;
+      mp.out_ids = d_out_ids + (int64_t)q0 * top_k;
+      mp.out_scores = d_out_scores + (int64_t)q0 * top_k;
+      mp.out_counts = d_out_counts + q0;
+      text_merge_kernel<<<(unsigned)Qn, TEXT_TPB, 0, st>>>(mp);
+      NP_HIP(hipGetLastError());
+    }
+  }
+  if (visited) {
+    unsigned long long h = 0;
+    NP_HIP(hipMemcpyAsync(&h, ctr, 8, hipMemcpyDeviceToHost, st));
+    NP_HIP(hipStreamSynchronize(st));
+    *visited = (int64_t)h;
+  }
+  return NP_OK;
+}
+
+// np_hip_text_search and np_hip_text_search_filtered: the subsets come as a host CSR, or (filters != NULL) are evaluated on
+// the call's context into a CSR that stays on the device; query_subset is the query map of either
+static int text_host(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k, const int64_t* subset_ids,
+                     const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset, const np_filter* filters,
+                     int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats) {
+  clear_error();
+  if (stats) memset(stats, 0, sizeof *stats);
+  NP_TRY(text_check_queries(ix, queries, B, top_k));
+  if (filters)
+    NP_TRY(filter_check_call(ix, filters, (int32_t)n_subsets, query_subset, B, true));
+  else
+    NP_TRY(check_subsets(subset_ids, subset_offsets, n_subsets, query_subset, query_subset, B));
+  if (B == 0) return NP_OK;
+  if (!out_ids || !out_scores || !out_counts) {
+    set_error("Text search failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  bool any = false;
+  for (int b = 0; n_subsets > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
+  const bool resident = any && filters;
+  TextProg prog;
+  prog.build(ix, queries, B);
+  DeviceGuard g(ix->device);
+  ContextUse use;
+  NP_TRY(use.begin(ix, nullptr));
+  hipStream_t st = use.stream;
+  FilterCsr csr;
+  if (resident) {
+    NP_TRY(filter_eval_resident(ix, st, use.filter_scratch(), use.filter_csr(), filters, (int32_t)n_subsets, query_subset, B, &csr));
+    subset_offsets = csr.h_off.data();
+  }
+  const int64_t total = any ? subset_offsets[n_subsets] : 0;
+  const bool staged = any && !resident;
+  const size_t b_ids = staged ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = staged ? up256((size_t)(n_subsets + 1) * 8) : 0;
+  const size_t b_qsub = staged ? up256((size_t)B * 4) : 0;
+  const size_t o_ids = up256((size_t)B * top_k * 8), o_sc = up256((size_t)B * top_k * 4), o_cnt = up256((size_t)B * 4);
+  const size_t user = b_ids + b_off + b_qsub + o_ids + o_sc + o_cnt;
+  TextPlan plan;
+  NP_TRY(text_plan_for(ix, (int64_t)user + (resident ? total * 8 : 0), prog, B, top_k, any, &plan));
+  NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, top_k, any)));
+  void* pinv = nullptr;
+  NP_TRY(use.pin(o_ids + o_sc + o_cnt + prog.bytes, &pinv));
+  char* at = use.arena().as<char>();
+  auto take = [&](size_t bytes) {
+    char* r = at;
+    at += bytes;
+    return r;
+  };
+  TextSubsets sub;
+  if (resident) {
+    sub.d_ids = csr.d_ids;
+    sub.d_off = csr.d_off;
+    sub.d_qsub = csr.d_qsub;
+  } else if (any) {
+    sub.d_ids = (const int64_t*)take(b_ids);
+    sub.d_off = (const int64_t*)take(b_off);
+    sub.d_qsub = (const int32_t*)take(b_qsub);
+    if (total > 0) NP_HIP(hipMemcpyAsync((void*)sub.d_ids, subset_ids, (size_t)total * 8, hipMemcpyHostToDevice, st));
+    NP_HIP(hipMemcpyAsync((void*)sub.d_off, subset_offsets, (size_t)(n_subsets + 1) * 8, hipMemcpyHostToDevice, st));
+    NP_HIP(hipMemcpyAsync((void*)sub.d_qsub, query_subset, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  }
+  if (any) {
+    sub.n = n_subsets;
+    sub.total = total;
+    sub.h_off = subset_offsets;
+    sub.h_qsub = query_subset;
+  }
+  int64_t* d_ids = (int64_t*)take(o_ids);
+  float* d_sc = (float*)take(o_sc);
+  int32_t* d_cnt = (int32_t*)take(o_cnt);
+  char* pin = (char*)pinv;
+  int64_t visited = 0;
+  NP_TRY(text_run(ix, use, at, pin + o_ids + o_sc + o_cnt, plan, prog, top_k, sub, d_ids, d_sc, d_cnt, stats ? &visited : nullptr));
+  NP_HIP(hipMemcpyAsync(pin, d_ids, (size_t)B * top_k * 8, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_ids, d_sc, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_ids + o_sc, d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  NP_TRY(use.end());
+  NP_HIP(hipStreamSynchronize(st));
+  memcpy(out_ids, pin, (size_t)B * top_k * 8);
+  memcpy(out_scores, pin + o_ids, (size_t)B * top_k * 4);
+  memcpy(out_counts, pin + o_ids + o_sc, (size_t)B * 4);
+  if (stats) {
+    stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->n_queries = B;
+    stats->n_ivf_ids = visited;
+  }
+  return NP_OK;
+}
+
+static int fuse_launch(hipStream_t st, int mode, float alpha, int top_k, int B, const int64_t* sem_ids, const float* sem_sc,
+                       const int32_t* sem_cnt, int sem_stride, const int64_t* kw_ids, const float* kw_sc, const int32_t* kw_cnt,
+                       int kw_stride, int64_t* out_ids, float* out_sc, int32_t* out_cnt) {
+  const FuseP p{mode, alpha, top_k, sem_ids, sem_sc, sem_cnt, sem_stride, kw_ids, kw_sc, kw_cnt, kw_stride, out_ids, out_sc, out_cnt};
+  fuse_kernel<<<(unsigned)B, TEXT_TPB, 0, st>>>(p);
+  NP_HIP(hipGetLastError());
+  return NP_OK;
+}
+
+static int fuse_check(int mode, float alpha, int top_k, int B, int sem_stride, int kw_stride) {
+  const char* why = "";
+  if (fuse_check_call(mode, alpha, top_k, B, sem_stride, kw_stride, &why) != 0) {
+    set_error("Fusion failed: %s (mode=%d alpha=%g top_k=%d strides %d, %d)", why, mode, (double)alpha, top_k, sem_stride, kw_stride);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+}  // namespace np
+
+using namespace np;
+
+extern "C" {
+
+int np_hip_index_set_text(np_index* ix, const np_text_index* text) {
+  clear_error();
+  NP_TRY(text_check_handle(ix, false));
+  DeviceGuard g(ix->device);
+  DeviceText fresh;
+  size_t bytes = 0;
+  char why[240];
+  if (text && text_check_index(text, ix->n_docs, why, sizeof why) != 0) {
+    set_error("set_text: %s", why);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  // NULL, or an index without instances and rows, drops what the handle had
+  if (text && !((text->n_terms == 0 || text->term_offsets[text->n_terms] == 0) && text->n_rows == 0)) {
+    // postings and document lengths, derived on the host; the new index is built beside the old one and swapped in whole
+    const int64_t n_terms = text->n_terms, n_inst = n_terms > 0 ? text->term_offsets[n_terms] : 0;
+    std::vector<int64_t> post_off((size_t)n_terms + 1, 0), post_first;
+    std::vector<int32_t> post_doc, post_tf, doc_len((size_t)std::max<int64_t>(ix->n_docs, 1), 0);
+    for (int64_t k = 0; k < n_terms; ++k) {
+      for (int64_t i = text->term_offsets[k]; i < text->term_offsets[k + 1]; ++i) {
+        const int32_t d = (int32_t)text->inst_doc[i];
+        if (i == text->term_offsets[k] || post_doc.back() != d) {
+          post_doc.push_back(d);
+          post_tf.push_back(0);
+          post_first.push_back(i);
+        }
+        ++post_tf.back();
+        ++doc_len[(size_t)d];
+      }
+      post_off[(size_t)k + 1] = (int64_t)post_doc.size();
+    }
+    const size_t n_post = post_doc.size();
+    NP_TRY(fresh.post_off.alloc((size_t)n_terms + 1, &bytes));
+    NP_TRY(fresh.post_doc.alloc(n_post, &bytes));
+    NP_TRY(fresh.post_tf.alloc(n_post, &bytes));
+    NP_TRY(fresh.post_first.alloc(n_post, &bytes));
+    NP_TRY(fresh.pos.alloc((size_t)n_inst, &bytes));
+    NP_TRY(fresh.doc_len.alloc(doc_len.size(), &bytes));
+    NP_HIP(hipMemcpy(fresh.post_off.get(), post_off.data(), post_off.size() * 8, hipMemcpyHostToDevice));
+    if (n_post > 0) {
+      NP_HIP(hipMemcpy(fresh.post_doc.get(), post_doc.data(), n_post * 4, hipMemcpyHostToDevice));
+      NP_HIP(hipMemcpy(fresh.post_tf.get(), post_tf.data(), n_post * 4, hipMemcpyHostToDevice));
+      NP_HIP(hipMemcpy(fresh.post_first.get(), post_first.data(), n_post * 8, hipMemcpyHostToDevice));
+      NP_HIP(hipMemcpy(fresh.pos.get(), text->inst_pos, (size_t)n_inst * 4, hipMemcpyHostToDevice));
+    }
+    NP_HIP(hipMemcpy(fresh.doc_len.get(), doc_len.data(), doc_len.size() * 4, hipMemcpyHostToDevice));
+    fresh.n_terms = n_terms;
+    fresh.n_post = (int64_t)n_post;
+    fresh.n_inst = n_inst;
+    fresh.n_rows = text->n_rows;
+    fresh.total_tokens = n_inst;
+    fresh.h_post_off = std::move(post_off);
+    fresh.present = true;
+  }
+  ix->text = std::move(fresh);
+  ix->device_bytes = ix->device_bytes - ix->text_bytes + bytes;
+  ix->text_bytes = bytes;
+  return NP_OK;
+}
+
+int np_hip_text_search(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k, const int64_t* subset_ids,
+                       const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset, int64_t* out_ids,
+                       float* out_scores, int32_t* out_counts, np_stats* stats) {
+  return text_host(ix, queries, B, top_k, subset_ids, subset_offsets, n_subsets, query_subset, nullptr, out_ids, out_scores,
+                   out_counts, stats);
+}
+
+int np_hip_text_search_filtered(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k,
+                                const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int64_t* out_ids,
+                                float* out_scores, int32_t* out_counts, np_stats* stats) {
+  static const np_filter none{};   // n_filters == 0: nothing to check or evaluate, but still the filtered call's checks
+  return text_host(ix, queries, B, top_k, nullptr, nullptr, n_filters, query_filter, filters ? filters : &none, out_ids,
+                   out_scores, out_counts, stats);
+}
+
+int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k,
+                              const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                              int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                              int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(text_check_queries(ix, queries, B, top_k));
+  NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
+  if (B == 0) return NP_OK;
+  if (!d_out_ids || !d_out_scores || !d_out_counts) {
+    set_error("Text search failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  TextSubsets sub;
+  if (n_subsets > 0) {
+    sub.d_ids = d_subset_ids;
+    sub.d_off = d_subset_offsets;
+    sub.d_qsub = d_query_subset;
+    sub.n = n_subsets;
+    sub.total = h_subset_offsets[n_subsets];
+  }
+  TextProg prog;
+  prog.build(ix, queries, B);
+  DeviceGuard g(ix->device);
+  TextPlan plan;
+  NP_TRY(text_plan_for(ix, 0, prog, B, top_k, sub.n > 0, &plan));
+  ContextUse use;
+  NP_TRY(use.begin(ix, stream));
+  NP_TRY(use.arena().reserve(text_arena_bytes(ix, plan, prog, top_k, sub.n > 0)));
+  return text_run(ix, use, use.arena().as<char>(), nullptr, plan, prog, top_k, sub, d_out_ids, d_out_scores, d_out_counts, nullptr);
+}
+
+int np_hip_fuse_device(const np_index* ix, int32_t mode, float alpha, int32_t top_k, int32_t B, const int64_t* d_sem_ids,
+                       const float* d_sem_scores, const int32_t* d_sem_counts, int32_t sem_stride, const int64_t* d_kw_ids,
+                       const float* d_kw_scores, const int32_t* d_kw_counts, int32_t kw_stride, int64_t* d_out_ids,
+                       float* d_out_scores, int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(fuse_check(mode, alpha, top_k, B, sem_stride, kw_stride));
+  if (B == 0) return NP_OK;
+  if (!d_sem_ids || !d_sem_counts || !d_kw_ids || !d_kw_counts || !d_out_ids || !d_out_scores || !d_out_counts ||
+      (mode == NP_FUSE_RELATIVE_SCORE && (!d_sem_scores || !d_kw_scores))) {
+    set_error("Fusion failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (!ix)   // the current device: the kernel needs no scratch
+    return fuse_launch((hipStream_t)stream, mode, alpha, top_k, B, d_sem_ids, d_sem_scores, d_sem_counts, sem_stride, d_kw_ids,
+                       d_kw_scores, d_kw_counts, kw_stride, d_out_ids, d_out_scores, d_out_counts);
+  DeviceGuard g(ix->device);
+  ContextUse use;   // (a context's stream where `stream` is NULL)
+  NP_TRY(use.begin(ix, stream));
+  return fuse_launch(use.stream, mode, alpha, top_k, B, d_sem_ids, d_sem_scores, d_sem_counts, sem_stride, d_kw_ids, d_kw_scores,
+                     d_kw_counts, kw_stride, d_out_ids, d_out_scores, d_out_counts);
+}
+
+int np_hip_fuse(const np_index* ix, int32_t mode, float alpha, int32_t top_k, int32_t B, const int64_t* sem_ids,
+                const float* sem_scores, const int32_t* sem_counts, int32_t sem_stride, const int64_t* kw_ids,
+                const float* kw_scores, const int32_t* kw_counts, int32_t kw_stride, int64_t* out_ids, float* out_scores,
+                int32_t* out_counts) {
+  clear_error();
+  NP_TRY(fuse_check(mode, alpha, top_k, B, sem_stride, kw_stride));
+  if (B == 0) return NP_OK;
+  const bool rel = mode == NP_FUSE_RELATIVE_SCORE;
+  if (!sem_counts || !kw_counts || !out_ids || !out_scores || !out_counts || (sem_stride > 0 && (!sem_ids || (rel && !sem_scores))) ||
+      (kw_stride > 0 && (!kw_ids || (rel && !kw_scores)))) {
+    set_error("Fusion failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (int b = 0; b < B; ++b)
+    if (sem_counts[b] < 0 || sem_counts[b] > sem_stride || kw_counts[b] < 0 || kw_counts[b] > kw_stride) {
+      set_error("Fusion failed: the counts of query %d (%d, %d) are outside their strides (%d, %d)", b, sem_counts[b], kw_counts[b],
+                sem_stride, kw_stride);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  const size_t n_s = (size_t)B * sem_stride, n_k = (size_t)B * kw_stride, n_o = (size_t)B * top_k;
+  const size_t b_si = up256(n_s * 8), b_ss = up256(n_s * 4), b_ki = up256(n_k * 8), b_ks = up256(n_k * 4), b_c = up256((size_t)B * 4);
+  const size_t o_i = up256(n_o * 8), o_s = up256(n_o * 4);
+  const size_t dev_bytes = b_si + b_ss + b_ki + b_ks + 3 * b_c + o_i + o_s;
+  // with a handle: its device, a context's stream, arena and pinned staging; without: the current device, the call's own
+  int device = 0;
+  if (ix) device = ix->device; else (void)hipGetDevice(&device);
+  DeviceGuard g(device);
+  ContextUse use;
+  DevPtr<char> own;
+  std::vector<char> own_host;
+  hipStream_t st = nullptr;
+  void* pinv = nullptr;
+  char* at = nullptr;
+  if (ix) {
+    NP_TRY(use.begin(ix, nullptr));
+    st = use.stream;
+    NP_TRY(use.arena().reserve(dev_bytes));
+    NP_TRY(use.pin(o_i + o_s + b_c, &pinv));
+    at = use.arena().as<char>();
+  } else {
+    NP_TRY(own.alloc(dev_bytes));
+    own_host.resize(o_i + o_s + b_c);
+    pinv = own_host.data();
+    at = own.get();
+  }
+  auto take = [&](size_t bytes) {
+    char* r = at;
+    at += bytes;
+    return r;
+  };
+  int64_t* d_si = (int64_t*)take(b_si);
+  float* d_ss = (float*)take(b_ss);
+  int64_t* d_ki = (int64_t*)take(b_ki);
+  float* d_ks = (float*)take(b_ks);
+  int32_t *d_sc = (int32_t*)take(b_c), *d_kc = (int32_t*)take(b_c), *d_oc = (int32_t*)take(b_c);
+  int64_t* d_oi = (int64_t*)take(o_i);
+  float* d_os = (float*)take(o_s);
+  // pageable sources: the copies complete before the call returns (it synchronises below)
+  if (n_s > 0) NP_HIP(hipMemcpyAsync(d_si, sem_ids, n_s * 8, hipMemcpyHostToDevice, st));
+  if (n_s > 0 && sem_scores) NP_HIP(hipMemcpyAsync(d_ss, sem_scores, n_s * 4, hipMemcpyHostToDevice, st));
+  if (n_k > 0) NP_HIP(hipMemcpyAsync(d_ki, kw_ids, n_k * 8, hipMemcpyHostToDevice, st));
+  if (n_k > 0 && kw_scores) NP_HIP(hipMemcpyAsync(d_ks, kw_scores, n_k * 4, hipMemcpyHostToDevice, st));
+  NP_HIP(hipMemcpyAsync(d_sc, sem_counts, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  NP_HIP(hipMemcpyAsync(d_kc, kw_counts, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  NP_TRY(fuse_launch(st, mode, alpha, top_k, B, d_si, sem_scores ? d_ss : nullptr, d_sc, sem_stride, d_ki, kw_scores ? d_ks : nullptr,
+                     d_kc, kw_stride, d_oi, d_os, d_oc));
+  char* pin = (char*)pinv;
+  NP_HIP(hipMemcpyAsync(pin, d_oi, n_o * 8, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_i, d_os, n_o * 4, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_i + o_s, d_oc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  NP_TRY(use.end());
+  NP_HIP(hipStreamSynchronize(st));
+  memcpy(out_ids, pin, n_o * 8);
+  memcpy(out_scores, pin + o_i, n_o * 4);
+  memcpy(out_counts, pin + o_i + o_s, (size_t)B * 4);
+  return NP_OK;
+}
+
+int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                         const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
+                         int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                         const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int64_t* out_ids,
+                         float* out_scores, int32_t* out_counts, np_stats* stats) {
+  clear_error();
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (!params) {
+    set_error("Search failed: NULL index or params");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  NP_TRY(text_check_queries(ix, text_queries, B, fetch_k));
+  NP_TRY(fuse_check(fusion, alpha, params->top_k, B, fetch_k, fetch_k));
+  if (filters) n_subsets = n_filters;
+  if (filters)
+    NP_TRY(filter_check_call(ix, filters, n_filters, query_subset, B, true));
+  else
+    NP_TRY(check_subsets(subset_ids, subset_offsets, n_subsets, query_subset, query_subset, B));
+  if (B > 0 && (!queries || !q_tok_offsets || !out_ids || !out_scores || !out_counts)) {
+    set_error("Search failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B > 0 && q_tok_offsets[0] != 0) {
+    set_error("Shape error: q_tok_offsets[0] must be 0");
+    return NP_ERR_SHAPE;
+  }
+  for (int b = 0; b < B; ++b)
+    if (q_tok_offsets[b + 1] < q_tok_offsets[b]) {
+      set_error("Shape error: q_tok_offsets must be non-decreasing");
+      return NP_ERR_SHAPE;
+    }
+  np_search_params sem = *params;
+  sem.top_k = fetch_k;
+  const int top_k = params->top_k;
+  const auto t0 = std::chrono::steady_clock::now();
+  bool any = false;
+  for (int b = 0; n_subsets > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
+  const bool resident = any && filters;
+  TextProg prog;
+  prog.build(ix, text_queries, B);
+  DeviceGuard g(ix->device);
+  ContextUse use;
+  NP_TRY(use.begin(ix, nullptr));
+  hipStream_t st = use.stream;
+  if (B == 0) return search_batch_in_use(ix, use, nullptr, nullptr, nullptr, 0, dim, &sem, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr);   // (the semantic call's own checks)
+  FilterCsr csr;
+  if (resident) {
+    NP_TRY(filter_eval_resident(ix, st, use.filter_scratch(), use.filter_csr(), filters, n_filters, query_subset, B, &csr));
+    subset_offsets = csr.h_off.data();
+  }
+  const int64_t total = any ? subset_offsets[n_subsets] : 0;
+  const int64_t ntok = q_tok_offsets[B];
+  const bool staged = any && !resident;
+  const size_t b_q = up256((size_t)std::max<int64_t>(ntok, 1) * dim * 4), b_qoff = up256((size_t)(B + 1) * 4);
+  const size_t b_ids = staged ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = staged ? up256((size_t)(n_subsets + 1) * 8) : 0;
+  const size_t b_qsub = staged ? up256((size_t)B * 4) : 0;
+  const size_t l_ids = up256((size_t)B * fetch_k * 8), l_sc = up256((size_t)B * fetch_k * 4), b_cnt = up256((size_t)B * 4);
+  const size_t o_ids = up256((size_t)B * top_k * 8), o_sc = up256((size_t)B * top_k * 4);
+  const size_t user = b_q + b_qoff + b_ids + b_off + b_qsub + 2 * (l_ids + l_sc + b_cnt) + o_ids + o_sc + b_cnt;
+  TextPlan plan;
+  NP_TRY(text_plan_for(ix, (int64_t)user + (resident ? total * 8 : 0), prog, B, fetch_k, any, &plan));
+  NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, fetch_k, any)));
+  void* pinv = nullptr;
+  NP_TRY(use.pin(o_ids + o_sc + b_cnt + prog.bytes, &pinv));
+  char* at = use.arena().as<char>();
+  auto take = [&](size_t bytes) {
+    char* r = at;
+    at += bytes;
+    return r;
+  };
+  float* d_q = (float*)take(b_q);
+  int32_t* d_qoff = (int32_t*)take(b_qoff);
+  TextSubsets sub;
+  if (resident) {
+    sub.d_ids = csr.d_ids;
+    sub.d_off = csr.d_off;
+    sub.d_qsub = csr.d_qsub;
+  } else if (any) {
+    sub.d_ids = (const int64_t*)take(b_ids);
+    sub.d_off = (const int64_t*)take(b_off);
+    sub.d_qsub = (const int32_t*)take(b_qsub);
+    if (total > 0) NP_HIP(hipMemcpyAsync((void*)sub.d_ids, subset_ids, (size_t)total * 8, hipMemcpyHostToDevice, st));
+    NP_HIP(hipMemcpyAsync((void*)sub.d_off, subset_offsets, (size_t)(n_subsets + 1) * 8, hipMemcpyHostToDevice, st));
+    NP_HIP(hipMemcpyAsync((void*)sub.d_qsub, query_subset, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  }
+  if (any) {
+    sub.n = n_subsets;
+    sub.total = total;
+    sub.h_off = subset_offsets;
+    sub.h_qsub = query_subset;
+  }
+  int64_t* s_ids = (int64_t*)take(l_ids);
+  float* s_sc = (float*)take(l_sc);
+  int32_t* s_cnt = (int32_t*)take(b_cnt);
+  int64_t* k_ids = (int64_t*)take(l_ids);
+  float* k_sc = (float*)take(l_sc);
+  int32_t* k_cnt = (int32_t*)take(b_cnt);
+  int64_t* d_ids = (int64_t*)take(o_ids);
+  float* d_sc = (float*)take(o_sc);
+  int32_t* d_cnt = (int32_t*)take(b_cnt);
+  if (ntok > 0) NP_HIP(hipMemcpyAsync(d_q, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));
+  NP_HIP(hipMemcpyAsync(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+  NP_TRY(search_batch_in_use(ix, use, d_q, d_qoff, q_tok_offsets, B, dim, &sem, sub.d_ids, sub.d_off, sub.h_off, sub.n, sub.d_qsub,
+                             sub.h_qsub, s_ids, s_sc, s_cnt));
+  char* pin = (char*)pinv;
+  int64_t visited = 0;
+  NP_TRY(text_run(ix, use, at, pin + o_ids + o_sc + b_cnt, plan, prog, fetch_k, sub, k_ids, k_sc, k_cnt, stats ? &visited : nullptr));
+  NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, s_ids, s_sc, s_cnt, fetch_k, k_ids, k_sc, k_cnt, fetch_k, d_ids, d_sc, d_cnt));
+  NP_HIP(hipMemcpyAsync(pin, d_ids, (size_t)B * top_k * 8, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_ids, d_sc, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_ids + o_sc, d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  NP_TRY(use.end());
+  NP_HIP(hipStreamSynchronize(st));
+  memcpy(out_ids, pin, (size_t)B * top_k * 8);
+  memcpy(out_scores, pin + o_ids, (size_t)B * top_k * 4);
+  memcpy(out_counts, pin + o_ids + o_sc, (size_t)B * 4);
+  if (stats) {
+    stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    stats->n_queries = B;
+    stats->n_ivf_ids = visited;
+  }
+  return NP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,142 @@
+// np_text_plan.h -- the host side of the keyword index and the keyword search that needs no device: the checks of a keyword
+// index (np_hip_index_set_text refuses a malformed one before any allocation), of a query and of a call (refused before any
+// launch), the idf, and the plan of query chunks and document-slice chunks under a byte budget.  Plain C++;
+// tests/cpp/text_plan_check.cpp runs all of it stand-alone.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <vector>
+#include "../../include/nextplaid_hip.h"
+
+namespace np {
+
+// documents per slice of the scoring kernel: one f64 accumulator (32 KB), one match count (4 KB) and one sort index (8 KB)
+// per document of the slice in LDS -- 45 KB with the phrase ranges, three workgroups per CU of 160 KB
+constexpr int64_t NP_TEXT_SLICE_DOCS = 4096;
+
+// entries a slice hands to the merge: no slice holds more than its documents
+inline int64_t text_slice_keep(int32_t top_k) { return top_k < NP_TEXT_SLICE_DOCS ? top_k : NP_TEXT_SLICE_DOCS; }
+
+// The index against a handle of n_docs documents.  0 = well-formed; otherwise NP_ERR_INVALID_ARGUMENT with `why` naming the
+// first offender.  *n_distinct (nullable) = documents that hold a token.
+inline int text_check_index(const np_text_index* t, int64_t n_docs, char* why, size_t why_len, int64_t* n_distinct = nullptr) {
+  auto fail = [&](const char* what, long long a, long long b) {
+    snprintf(why, why_len, what, a, b);
+    return (int)NP_ERR_INVALID_ARGUMENT;
+  };
+  if (!t) return fail("NULL text index", 0, 0);
+  if (t->n_terms < 0) return fail("n_terms = %lld is negative", t->n_terms, 0);
+  if (t->n_rows < 0) return fail("n_rows = %lld is negative", t->n_rows, 0);
+  if (t->n_terms > 0x7FFFFFFF) return fail("n_terms = %lld does not fit an i32 term id", t->n_terms, 0);
+  if (t->n_terms > 0 && !t->term_offsets) return fail("n_terms = %lld but term_offsets is NULL", t->n_terms, 0);
+  if (t->n_terms == 0) {
+    if (n_distinct) *n_distinct = 0;
+    return 0;
+  }
+  if (t->term_offsets[0] != 0) return fail("term_offsets[0] = %lld must be 0", t->term_offsets[0], 0);
+  for (int64_t k = 0; k < t->n_terms; ++k)
+    if (t->term_offsets[k + 1] < t->term_offsets[k]) return fail("term_offsets decrease at term %lld", k, 0);
+  const int64_t n_inst = t->term_offsets[t->n_terms];
+  if (n_inst > 0 && (!t->inst_doc || !t->inst_pos)) return fail("%lld instances but inst_doc or inst_pos is NULL", n_inst, 0);
+  std::vector<bool> seen((size_t)(n_docs > 0 ? n_docs : 0), false);
+  int64_t distinct = 0;
+  for (int64_t k = 0; k < t->n_terms; ++k)
+    for (int64_t i = t->term_offsets[k]; i < t->term_offsets[k + 1]; ++i) {
+      const int64_t d = t->inst_doc[i];
+      if (d < 0 || d >= n_docs) return fail("instance %lld: document %lld is outside the index", i, d);
+      if (t->inst_pos[i] < 0) return fail("instance %lld: position %lld is negative", i, t->inst_pos[i]);
+      if (i > t->term_offsets[k]) {
+        const int64_t pd = t->inst_doc[i - 1];
+        if (pd > d || (pd == d && t->inst_pos[i - 1] >= t->inst_pos[i]))
+          return fail("instance %lld of term %lld is not after its predecessor in (document, position) order", i, k);
+      }
+      if (!seen[(size_t)d]) {
+        seen[(size_t)d] = true;
+        ++distinct;
+      }
+    }
+  if (t->n_rows < distinct) return fail("n_rows = %lld is below the %lld documents that hold a token", t->n_rows, distinct);
+  if (n_distinct) *n_distinct = distinct;
+  return 0;
+}
+
+// One query against a vocabulary of n_terms.  `q` only labels the message.
+inline int text_check_query(const np_text_query* tq, int32_t q, int64_t n_terms, char* why, size_t why_len) {
+  auto fail = [&](const char* what, long long a) {
+    char msg[160];
+    snprintf(msg, sizeof msg, what, a);
+    snprintf(why, why_len, "text query %d: %s", q, msg);
+    return (int)NP_ERR_INVALID_ARGUMENT;
+  };
+  if (!tq) return fail("NULL query", 0);
+  if (tq->n_phrases < 1 || tq->n_phrases > NP_TEXT_MAX_PHRASES) return fail("n_phrases = %lld must be in 1..64", tq->n_phrases);
+  if (tq->mode != NP_TEXT_AND && tq->mode != NP_TEXT_OR) return fail("unknown mode %lld", tq->mode);
+  if (!tq->phrase_offsets || !tq->terms) return fail("NULL phrase_offsets or terms", 0);
+  if (tq->phrase_offsets[0] != 0) return fail("phrase_offsets[0] = %lld must be 0", tq->phrase_offsets[0]);
+  for (int32_t p = 0; p < tq->n_phrases; ++p) {
+    if (tq->phrase_offsets[p + 1] <= tq->phrase_offsets[p]) return fail("phrase %lld has no token", p);
+    if (tq->phrase_offsets[p + 1] > NP_TEXT_MAX_TOKENS) return fail("more than 256 tokens (at phrase %lld)", p);
+  }
+  for (int32_t i = 0; i < tq->phrase_offsets[tq->n_phrases]; ++i)
+    if (tq->terms[i] < -1 || (int64_t)tq->terms[i] >= n_terms) return fail("token %lld names no term of the vocabulary", i);
+  return 0;
+}
+
+// B and top_k of a keyword search.  *why = a string literal.
+inline int text_check_call(int32_t B, int32_t top_k, const char** why) {
+  *why = "";
+  if (B < 0) return *why = "negative batch size", (int)NP_ERR_INVALID_ARGUMENT;
+  if (B >= 65536) return *why = "more than 65535 queries in one call", (int)NP_ERR_INVALID_ARGUMENT;
+  if (top_k < 1 || top_k > NP_TEXT_MAX_TOPK) return *why = "top_k must be in 1..1024", (int)NP_ERR_INVALID_ARGUMENT;
+  return 0;
+}
+
+// the arguments of a fusion that the host can see
+inline int fuse_check_call(int32_t mode, float alpha, int32_t top_k, int32_t B, int32_t sem_stride, int32_t kw_stride,
+                           const char** why) {
+  *why = "";
+  if (mode != NP_FUSE_RRF && mode != NP_FUSE_RELATIVE_SCORE) return *why = "unknown fusion mode", (int)NP_ERR_INVALID_ARGUMENT;
+  if (!(alpha >= 0.0f && alpha <= 1.0f)) return *why = "alpha must be in [0, 1]", (int)NP_ERR_INVALID_ARGUMENT;
+  if (B < 0) return *why = "negative batch size", (int)NP_ERR_INVALID_ARGUMENT;
+  if (top_k < 1 || top_k > 2 * NP_TEXT_MAX_TOPK) return *why = "top_k must be in 1..2048", (int)NP_ERR_INVALID_ARGUMENT;
+  if (sem_stride < 0 || sem_stride > NP_TEXT_MAX_TOPK || kw_stride < 0 || kw_stride > NP_TEXT_MAX_TOPK)
+    return *why = "a list stride must be in 0..1024", (int)NP_ERR_INVALID_ARGUMENT;
+  return 0;
+}
+
+// bm25's idf as SQLite computes it (fts5_aux.c): libm's log in f64, clamped to 1e-6 where it is not positive
+inline double text_idf(int64_t n_rows, int64_t n_hit) {
+  const double idf = log(((double)(n_rows - n_hit) + 0.5) / ((double)n_hit + 0.5));
+  return idf <= 0.0 ? 1e-6 : idf;
+}
+
+// Chunks: `queries` queries over `slices` document slices at a time, so that
+//     queries * per_query + queries * slices * (keep * 12 + 4) + fixed  <=  budget        (keep = text_slice_keep(top_k)).
+// queries starts at min(B, max_batch) and halves while a chunk could not hold min(n_slices, 8) slices; slices is then what
+// the rest of the budget holds, at most n_slices.  false: one query over one slice does not fit.
+struct TextPlan {
+  int32_t queries = 1;
+  int64_t slices = 1;
+};
+inline int64_t text_pair_bytes(int32_t top_k) { return text_slice_keep(top_k) * 12 + 4; }
+inline bool text_plan(int64_t budget, int64_t fixed, int64_t per_query, int64_t n_slices, int32_t B, int32_t max_batch,
+                      int32_t top_k, TextPlan* out) {
+  if (n_slices < 1) n_slices = 1;
+  int64_t Q = B < 1 ? 1 : B;
+  if (max_batch >= 1 && Q > max_batch) Q = max_batch;
+  const int64_t want = n_slices < 8 ? n_slices : 8;
+  for (;;) {
+    const int64_t left = budget - fixed - Q * per_query;
+    const int64_t S = left > 0 ? left / (Q * text_pair_bytes(top_k)) : 0;
+    if (S >= want || Q == 1) {
+      if (S < 1) return false;
+      out->queries = (int32_t)Q;
+      out->slices = S < n_slices ? S : n_slices;
+      return true;
+    }
+    Q = (Q + 1) / 2;
+  }
+}
+
+}  // namespace np

@@ -188,6 +188,15 @@ class np_filter(C.Structure):
     _fields_ = [("ops", C.POINTER(np_filter_op)), ("n_ops", C.c_int32), ("values", C.c_void_p), ("n_values", C.c_int64)]
 
 
+class np_text_index(C.Structure):
+    _fields_ = [("n_terms", C.c_int64), ("term_offsets", C.c_void_p), ("inst_doc", C.c_void_p), ("inst_pos", C.c_void_p),
+                ("n_rows", C.c_int64)]
+
+
+class np_text_query(C.Structure):
+    _fields_ = [("terms", C.c_void_p), ("phrase_offsets", C.c_void_p), ("n_phrases", C.c_int32), ("mode", C.c_int32)]
+
+
 # np_all_gather_host_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes)
 ALL_GATHER_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 NP_COMM_DEFERRED_STATUS = 1
@@ -212,6 +221,8 @@ EXPORTS = [
     "np_hip_search_exact", "np_hip_search_exact_device",
     "np_hip_score_pairs", "np_hip_score_pairs_device",
     "np_hip_index_set_columns", "np_hip_filter_eval", "np_hip_search_batch_filtered", "np_hip_search_exact_filtered",
+    "np_hip_index_set_text", "np_hip_text_search", "np_hip_text_search_device", "np_hip_text_search_filtered",
+    "np_hip_fuse", "np_hip_fuse_device", "np_hip_search_hybrid",
 ]
 
 _lib = None
@@ -322,6 +333,16 @@ def lib():
                                                vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_search_exact_filtered.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(np_filter), i32, vp, vp, vp, vp,
                                                C.POINTER(np_stats)]
+    L.np_hip_index_set_text.argtypes = [vp, C.POINTER(np_text_index)]
+    L.np_hip_text_search.argtypes = [vp, C.POINTER(np_text_query), i32, i32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_text_search_device.argtypes = [vp, C.POINTER(np_text_query), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_text_search_filtered.argtypes = [vp, C.POINTER(np_text_query), i32, i32, C.POINTER(np_filter), i32, vp, vp, vp, vp,
+                                              C.POINTER(np_stats)]
+    L.np_hip_fuse.argtypes = [vp, i32, C.c_float, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
+    L.np_hip_fuse_device.argtypes = [vp, i32, C.c_float, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.np_hip_search_hybrid.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_text_query), i32,
+                                       C.c_float, i32, vp, vp, i64, vp, C.POINTER(np_filter), i32, vp, vp, vp,
+                                       C.POINTER(np_stats)]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -495,6 +516,63 @@ class _CFilters:
             self.keep += [ops, vals]
             self.arr[j] = np_filter(C.cast(ops, C.POINTER(np_filter_op)), len(p.ops), vals.ctypes.data if vals.size else None,
                                     vals.size)
+
+
+class _CTextQueries:
+    """The ctypes form of compiled keyword queries (text.TextQuery); keeps every array it points to alive."""
+
+    def __init__(self, queries):
+        self.n = len(queries)
+        self.arr = (np_text_query * max(self.n, 1))()
+        self.keep = []
+        for j, q in enumerate(queries):
+            terms = np.ascontiguousarray(q.terms, np.int32).reshape(-1)
+            off = np.ascontiguousarray(q.phrase_offsets, np.int32).reshape(-1)
+            self.keep += [terms, off]
+            self.arr[j] = np_text_query(terms.ctypes.data if terms.size else None, off.ctypes.data if off.size else None,
+                                        max(off.size - 1, 0), int(q.mode))
+
+
+def _pad_lists(lists, dtype, width=None):
+    """Ragged per-query lists -> (flat [B * width] array, counts i32 [B], width)."""
+    arrs = [np.asarray(a, dtype).reshape(-1) for a in lists]
+    width = max([a.size for a in arrs] + [1]) if width is None else width
+    flat = np.zeros((max(len(arrs), 1), width), dtype)
+    for i, a in enumerate(arrs):
+        flat[i, :a.size] = a
+    return flat.reshape(-1), np.asarray([a.size for a in arrs], np.int32), width
+
+
+def fuse(mode, alpha: float, top_k: int, sem_ids, sem_scores, kw_ids, kw_scores, index=None):
+    """np_hip_fuse over a batch: per query a semantic and a keyword list (sequences of id / score arrays; the scores may be
+    None for "rrf").  mode is "rrf" or "relative_score".  Returns per query (ids int64, scores float32).  `index` names the
+    device (an MmapIndex; None = the current device)."""
+    from . import text as T
+    m = T.FUSION_MODES[mode] if isinstance(mode, str) else int(mode)
+    B = len(sem_ids)
+    if len(kw_ids) != B:
+        raise ValueError(f"{B} semantic lists and {len(kw_ids)} keyword lists")
+    si, sc, sw = _pad_lists(sem_ids, np.int64)
+    ki, kc, kw = _pad_lists(kw_ids, np.int64)
+    ss = None if sem_scores is None else _pad_lists(sem_scores, np.float32, sw)[0]
+    ks = None if kw_scores is None else _pad_lists(kw_scores, np.float32, kw)[0]
+    k = max(int(top_k), 1)
+    ids = np.zeros(max(B * k, 1), np.int64)
+    out = np.zeros(max(B * k, 1), np.float32)
+    cnt = np.zeros(max(B, 1), np.int32)
+    _check(lib().np_hip_fuse(None if index is None else index._h, m, float(alpha), int(top_k), B, _ptr(si), _ptr(ss), _ptr(sc), sw,
+                             _ptr(ki), _ptr(ks), _ptr(kc), kw, _ptr(ids), _ptr(out), _ptr(cnt)))
+    return [(ids[i * k: i * k + cnt[i]].copy(), out[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+
+
+def fuse_rrf(sem_ids, kw_ids, alpha: float, top_k: int, index=None):
+    """fuse_rrf (text_search.rs:1013-1033) with its argument order, batched: one list of ids per query on either side."""
+    return fuse("rrf", alpha, top_k, sem_ids, None, kw_ids, None, index=index)
+
+
+def fuse_relative_score(sem_ids, sem_scores, kw_ids, kw_scores, alpha: float, top_k: int, index=None):
+    """fuse_relative_score (text_search.rs:1040-1075) with its argument order, batched."""
+    return fuse("relative_score", alpha, top_k, sem_ids, sem_scores, kw_ids, kw_scores, index=index)
 
 
 # ---- crate mirror ------------------------------------------------------------------------------------
@@ -853,6 +931,7 @@ class MmapIndex:
         self.last_stats: dict | None = None
         self.last_update: dict | None = None
         self.schema = None   # set_columns: the columns' names, types and dictionaries (filters.Schema)
+        self.text = None     # set_text: the keyword index's arrays and vocabulary (text.TextIndexData)
 
     # -- constructors ---------------------------------------------------------------------------------
     @classmethod
@@ -890,6 +969,7 @@ class MmapIndex:
         _check(lib().np_hip_index_open(os.fsencode(self.path), C.byref(o), C.byref(h)))
         self._h = h
         self.schema = None
+        self.text = None     # (and no keyword index, for the same reason: set_text / load_text again)
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         self.last_stats = None
 
@@ -1095,6 +1175,124 @@ class MmapIndex:
         _check(lib().np_hip_search_exact_filtered(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), int(top_k),
                                                   int(precision), cf.arr, cf.n, _ptr(qf), _ptr(ids), _ptr(sc), _ptr(cnt),
                                                   C.byref(st)))
+        self.last_stats = st.as_dict()
+        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+
+    # -- keyword and hybrid search ------------------------------------------------------------------------
+    def set_text(self, data):
+        """np_hip_index_set_text: the handle's keyword index from a text.TextIndexData (its vocabulary stays on this object
+        in self.text); None drops it.  Document i of the FTS5 table is document i of the index.  Needs exclusive access to
+        the handle, as set_columns does."""
+        if data is None:
+            _check(lib().np_hip_index_set_text(self._h, None))
+        else:
+            off = np.ascontiguousarray(data.term_offsets, np.int64)
+            doc = np.ascontiguousarray(data.inst_doc, np.int64)
+            pos = np.ascontiguousarray(data.inst_pos, np.int32)
+            t = np_text_index(len(data.terms), off.ctypes.data, doc.ctypes.data if doc.size else None,
+                              pos.ctypes.data if pos.size else None, int(data.n_rows))
+            _check(lib().np_hip_index_set_text(self._h, C.byref(t)))
+        self.text = data
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def load_text(self, index_path: str | None = None):
+        """set_text from the metadata.db of an index directory (the crate's METADATA_FTS table); returns the TextIndexData."""
+        from . import text as T
+        data = T.TextIndexData.from_sqlite(os.path.join(index_path or self._dir("load_text"), "metadata.db"))
+        self.set_text(data)
+        return data
+
+    def _text_queries(self, text_queries, empty_matches_nothing: bool):
+        """Strings are compiled against self.text, TextQuery objects pass; '' (text_search.rs:1247: an empty query has an
+        empty result) -> None, or the query that matches nothing."""
+        from . import text as T
+        out = []
+        for q in text_queries:
+            if isinstance(q, str):
+                if q == "":
+                    q = T.TextQuery.from_phrases(T.MATCH_NOTHING) if empty_matches_nothing else None
+                else:
+                    if getattr(self, "text", None) is None:
+                        raise ValueError("the handle has no keyword index (set_text / load_text)")
+                    q = T.compile_text_query(q, self.text)
+            out.append(q)
+        return out
+
+    def _scope(self, B, subset, subsets, filters, what):
+        """(subset_ids, subset_offsets, n_subsets, query_subset, _CFilters or None) of the per-query scope arguments."""
+        if filters is not None:
+            if subset is not None or subsets is not None:
+                raise ValueError(f"{what} takes filters= or subset= / subsets=, not both")
+            cf, qf = self._filters(filters, B)
+            return None, None, cf.n, qf, cf
+        if subsets is not None:
+            if subset is not None:
+                raise ValueError(f"{what} takes subset= (one for the batch) or subsets= (one per query), not both")
+            sid, soff, qsub = pack_subsets(subsets, B)
+            return sid, soff, soff.size - 1, qsub, None
+        if subset is not None:
+            sid = np.ascontiguousarray(subset, np.int64).reshape(-1)
+            return sid, np.array([0, sid.size], np.int64), 1, np.zeros(max(B, 1), np.int32), None
+        return None, None, 0, None, None
+
+    def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None):
+        """np_hip_text_search: BM25 keyword search with SQLite FTS5's results (text_search.rs:1246-1342) -- for every query
+        the top_k documents by -bm25(), f64 score descending, ties by ascending id.  A query is FTS5 text (compiled by
+        text.compile_text_query against the handle's keyword index) or a text.TextQuery; '' returns an empty result.  Scope:
+        `subset`, `subsets` or `filters` as search_exact takes them.  Returns QueryResults."""
+        if isinstance(text_queries, str):
+            text_queries = [text_queries]
+        qs = self._text_queries(list(text_queries), False)
+        B = len(qs)
+        live = [i for i, q in enumerate(qs) if q is not None]
+        res = [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
+        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "text_search")
+        if qsub is not None:
+            qsub = np.ascontiguousarray(qsub[live], np.int32) if live else np.zeros(1, np.int32)
+        n = len(live)
+        tq = _CTextQueries([qs[i] for i in live])
+        k = max(int(top_k), 1)
+        ids = np.zeros(max(n * k, 1), np.int64)
+        sc = np.zeros(max(n * k, 1), np.float32)
+        cnt = np.zeros(max(n, 1), np.int32)
+        st = np_stats()
+        if cf is not None:
+            _check(lib().np_hip_text_search_filtered(self._h, tq.arr, n, int(top_k), cf.arr, cf.n, _ptr(qsub), _ptr(ids), _ptr(sc),
+                                                     _ptr(cnt), C.byref(st)))
+        else:
+            _check(lib().np_hip_text_search(self._h, tq.arr, n, int(top_k), _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), _ptr(ids),
+                                            _ptr(sc), _ptr(cnt), C.byref(st)))
+        self.last_stats = st.as_dict()
+        for j, i in enumerate(live):
+            res[i] = QueryResult(i, ids[j * k: j * k + cnt[j]].copy(), sc[j * k: j * k + cnt[j]].copy())
+        return res
+
+    def search_hybrid(self, queries, text_queries, params: "SearchParameters", alpha: float = 0.75,
+                      fusion: str = "relative_score", fetch_k: int | None = None, subset=None, subsets=None, filters=None):
+        """np_hip_search_hybrid: the /search handler's hybrid request (search.rs:134-375) in one call -- the semantic pass and
+        the keyword pass with top_k = fetch_k (default: the handler's 3 * params.top_k) and their fusion ("relative_score",
+        the default, or "rrf") to params.top_k, on the device.  Query i gets what fuse(...) returns for search_batch and
+        text_search with top_k = fetch_k.  An empty text query contributes an empty keyword list.  Returns QueryResults."""
+        from . import text as T
+        queries = list(queries)
+        flat, off = self._pack(queries)
+        B = len(queries)
+        qs = self._text_queries(list(text_queries), True)
+        if len(qs) != B:
+            raise ValueError(f"{B} queries and {len(qs)} text queries")
+        fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
+        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "search_hybrid")
+        tq = _CTextQueries(qs)
+        k = max(int(params.top_k), 1)
+        ids = np.zeros(max(B * k, 1), np.int64)
+        sc = np.zeros(max(B * k, 1), np.float32)
+        cnt = np.zeros(max(B, 1), np.int32)
+        p = params._c()
+        st = np_stats()
+        _check(lib().np_hip_search_hybrid(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), tq.arr, fk,
+                                          float(alpha), T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion),
+                                          _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), None if cf is None else cf.arr,
+                                          0 if cf is None else cf.n, _ptr(ids), _ptr(sc), _ptr(cnt), C.byref(st)))
         self.last_stats = st.as_dict()
         return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
 

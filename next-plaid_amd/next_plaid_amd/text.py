@@ -1,0 +1,391 @@
+"""The host side of the keyword half of a hybrid search (text_search.rs): reading an FTS5 index into the arrays
+np_hip_index_set_text takes, the crate's query sanitizers and identifier tokenizer, and the compiler from FTS5 query text to
+the term-id phrases np_hip_text_search takes.  Pure host code: sqlite3 and numpy, no device, no library.
+
+The keyword index is SQLite's own: fts5vocab(..., 'instance') lists every (term, document, position) of an FTS5 table, tokenised
+by SQLite itself, so the device scores exactly the tokens SQLite would.  Query text is tokenised the same way, through a
+scratch FTS5 table with the index's tokenize= clause."""
+from __future__ import annotations
+
+import sqlite3
+from dataclasses import dataclass, field
+
+import numpy as np
+
+FTS_TABLE = "METADATA_FTS"
+FTS_CONTENT_TABLE = "METADATA_FTS_CONTENT"
+FTS_CONTENT_COLUMN = "_fts_content_"
+FTS_CONFIG_TABLE = "_FTS_SETTINGS_"
+
+NP_TEXT_AND, NP_TEXT_OR = 0, 1
+NP_TEXT_MAX_PHRASES, NP_TEXT_MAX_TOKENS, NP_TEXT_MAX_TOPK = 64, 256, 1024
+NP_FUSE_RRF, NP_FUSE_RELATIVE_SCORE = 0, 1
+FUSION_MODES = {"rrf": NP_FUSE_RRF, "relative_score": NP_FUSE_RELATIVE_SCORE}
+
+# FtsTokenizer (text_search.rs:60-104): the name in the settings table -> the FTS5 tokenize= value
+TOKENIZERS = {"unicode61": "unicode61", "trigram": "trigram", "identifier_aware": "unicode61"}
+
+
+class TextQueryError(ValueError):
+    """An FTS5 query that compile_text_query does not translate (it never approximates one); the message names the construct."""
+
+
+# ---- the identifier-aware tokenizer (text_search.rs:118-258) -------------------------------------------------------------
+
+def _camel_split(token: str) -> list[str]:
+    """camelCase / PascalCase parts, lowercase: digit runs, an acronym before a capitalised word (HTTPResponse -> http,
+    response), capitalised or lowercase words.  ASCII only, as the reference works on bytes."""
+    parts, i, n = [], 0, len(token)
+    is_up = lambda ch: "A" <= ch <= "Z"
+    is_lo = lambda ch: "a" <= ch <= "z"
+    while i < n:
+        c = token[i]
+        if "0" <= c <= "9":
+            j = i
+            while i < n and "0" <= token[i] <= "9":
+                i += 1
+            parts.append(token[j:i])
+        elif is_up(c):
+            j = i
+            while i + 1 < n and is_up(token[i + 1]):
+                i += 1
+            if i + 1 < n and is_lo(token[i + 1]) and i > j:   # the last capital opens the next word
+                parts.append(token[j:i].lower())
+                continue
+            i += 1
+            while i < n and is_lo(token[i]):
+                i += 1
+            parts.append(token[j:i].lower())
+        elif is_lo(c):
+            j = i
+            while i < n and is_lo(token[i]):
+                i += 1
+            parts.append(token[j:i])
+        else:
+            i += 1
+    return parts
+
+
+def split_identifier(token: str) -> list[str]:
+    """The lowered compound, then -- if it has at least two parts -- every part and the adjacent pairs joined by '_':
+    HandlerStack -> handlerstack, handler, stack, handler_stack."""
+    lower = token.lower()
+    parts = [p for p in lower.split("_") if p] if "_" in token else _camel_split(token)
+    if len(parts) < 2:
+        return [lower]
+    return [lower] + parts + [f"{a}_{b}" for a, b in zip(parts, parts[1:])]
+
+
+def tokenize_identifiers(text: str) -> list[str]:
+    """tokenize_identifiers (text_search.rs:218-246): identifiers are [A-Za-z_][A-Za-z0-9_]*, ASCII only (the reference
+    scans bytes; no byte of a multi-byte UTF-8 character is an ASCII letter), everything else separates; each identifier is
+    expanded by split_identifier."""
+    out, i, n = [], 0, len(text)
+    head = lambda ch: ("a" <= ch <= "z") or ("A" <= ch <= "Z") or ch == "_"
+    while i < n:
+        if head(text[i]):
+            j = i
+            i += 1
+            while i < n and (head(text[i]) or "0" <= text[i] <= "9"):
+                i += 1
+            out.extend(split_identifier(text[j:i]))
+        else:
+            i += 1
+    return out
+
+
+def prepare_document_text(text: str, tokenizer: str) -> str:
+    """What the crate hands FTS5 for a document body (text_search.rs:252-257)."""
+    return " ".join(tokenize_identifiers(text)) if tokenizer == "identifier_aware" else text
+
+
+# ---- the query sanitizers (text_search.rs:949-993) -----------------------------------------------------------------------
+
+def sanitize_fts5_query(query: str) -> str:
+    """sanitize_fts5_query: whitespace-separated words, edges trimmed of non-alphanumeric characters, the FTS5 operators
+    dropped, each word double-quoted; implicit AND.  Edge trimming follows Rust's char::is_alphanumeric for ASCII and
+    Latin-1 (where str.isalnum agrees with it) and is unchecked beyond: the two may disagree on a few other code points."""
+    out = []
+    for word in query.split():
+        a, b = 0, len(word)
+        while a < b and not word[a].isalnum():
+            a += 1
+        while b > a and not word[b - 1].isalnum():
+            b -= 1
+        w = word[a:b]
+        if not w or w.upper() in ("AND", "OR", "NOT", "NEAR"):
+            continue
+        out.append('"' + w.replace('"', '""') + '"')
+    return " ".join(out)
+
+
+def sanitize_fts5_query_or(query: str) -> str:
+    """sanitize_fts5_query_or: the identifier tokens of the query, each once in order of first appearance, double-quoted
+    and joined by OR (for an identifier_aware index)."""
+    seen, out = set(), []
+    for tok in tokenize_identifiers(query):
+        if tok and tok not in seen:
+            seen.add(tok)
+            out.append('"' + tok.replace('"', '""') + '"')
+    return " OR ".join(out)
+
+
+# ---- the keyword index as arrays -----------------------------------------------------------------------------------------
+
+@dataclass
+class TextIndexData:
+    """An FTS5 index as np_hip_index_set_text takes it, plus the vocabulary (which stays on the host).  Term ids number the
+    terms in fts5vocab's order."""
+    tokenizer: str                    # the crate's name: unicode61, trigram, identifier_aware
+    terms: list                       # term id -> term
+    term_offsets: np.ndarray          # int64 [n_terms + 1]
+    inst_doc: np.ndarray              # int64 [instances] rowids
+    inst_pos: np.ndarray              # int32 [instances]
+    n_rows: int                       # FTS5's nRow
+    vocab: dict = field(default_factory=dict)
+    _scratch: object = field(default=None, repr=False, compare=False)
+    _cache: dict = field(default_factory=dict, repr=False, compare=False)
+
+    @property
+    def tokenize(self) -> str:
+        return TOKENIZERS[self.tokenizer]
+
+    @property
+    def n_terms(self) -> int:
+        return len(self.terms)
+
+    @classmethod
+    def _read(cls, conn, table: str, tokenizer: str, schema: str = "main") -> "TextIndexData":
+        conn.execute(f"CREATE VIRTUAL TABLE temp._np_vocab USING fts5vocab('{schema}', '{table}', 'instance')")
+        try:
+            rows = conn.execute("SELECT term, doc, offset FROM temp._np_vocab").fetchall()
+        finally:
+            conn.execute("DROP TABLE temp._np_vocab")
+        n_rows = int(conn.execute(f'SELECT count(*) FROM "{table}_docsize"').fetchone()[0])
+        terms, starts = [], []
+        for i, r in enumerate(rows):
+            if not terms or r[0] != terms[-1]:
+                terms.append(r[0])
+                starts.append(i)
+        vocab = {t: i for i, t in enumerate(terms)}
+        if len(vocab) != len(terms):
+            raise ValueError("fts5vocab did not list every term's instances together")
+        off = np.asarray(starts + [len(rows)], np.int64)
+        doc = np.asarray([r[1] for r in rows], np.int64).reshape(-1)
+        pos = np.asarray([r[2] for r in rows], np.int32).reshape(-1)
+        return cls(tokenizer, terms, off, doc, pos, n_rows, vocab)
+
+    @classmethod
+    def from_sqlite(cls, db_path: str) -> "TextIndexData":
+        """The METADATA_FTS table of a metadata.db the crate wrote (text_search.rs:306-500): its instances, the tokenizer
+        named in _FTS_SETTINGS_ (unicode61 where the table has no such row) and its row count.  The file is opened read-only."""
+        conn = sqlite3.connect(f"file:{db_path}?mode=ro", uri=True)
+        try:
+            if conn.execute("SELECT count(*) FROM sqlite_master WHERE name = ?", (FTS_TABLE,)).fetchone()[0] == 0:
+                raise ValueError(f"{db_path} has no {FTS_TABLE} table")
+            tok = "unicode61"
+            if conn.execute("SELECT count(*) FROM sqlite_master WHERE name = ?", (FTS_CONFIG_TABLE,)).fetchone()[0]:
+                row = conn.execute(f'SELECT value FROM "{FTS_CONFIG_TABLE}" WHERE key = \'tokenizer\'').fetchone()
+                if row is not None:
+                    tok = row[0]
+            if tok not in TOKENIZERS:
+                raise ValueError(f"{db_path}: unknown tokenizer {tok!r} in {FTS_CONFIG_TABLE}")
+            return cls._read(conn, FTS_TABLE, tok)
+        finally:
+            conn.close()
+
+    @classmethod
+    def from_texts(cls, texts, tokenizer: str = "unicode61", content_synced: bool = False) -> "TextIndexData":
+        """An in-memory FTS5 table over `texts` (document i = rowid i), read the same way.  identifier_aware passes every
+        text through tokenize_identifiers first, as the crate does.  content_synced builds the crate's layout (an
+        external-content table) instead of a plain FTS5 table; the index is the same."""
+        if tokenizer not in TOKENIZERS:
+            raise ValueError(f"unknown tokenizer {tokenizer!r}")
+        conn = sqlite3.connect(":memory:")
+        try:
+            create_fts_tables(conn, tokenizer, content_synced=content_synced)
+            insert_fts_rows(conn, list(texts), range(len(texts)), tokenizer, content_synced=content_synced)
+            return cls._read(conn, FTS_TABLE, tokenizer)
+        finally:
+            conn.close()
+
+    # -- tokenising query text with the index's tokenizer -------------------------------------------------
+    def tokens_of(self, phrase: str) -> list[str]:
+        """The tokens SQLite's tokenizer makes of a string, in position order (through a scratch FTS5 table)."""
+        got = self._cache.get(phrase)
+        if got is not None:
+            return got
+        if self._scratch is None:
+            self._scratch = sqlite3.connect(":memory:", check_same_thread=False)
+            self._scratch.execute(f"CREATE VIRTUAL TABLE s USING fts5(c, tokenize='{self.tokenize}')")
+            self._scratch.execute("CREATE VIRTUAL TABLE sv USING fts5vocab('s', 'instance')")
+        c = self._scratch
+        c.execute("DELETE FROM s")
+        c.execute("INSERT INTO s(rowid, c) VALUES (1, ?)", (phrase,))
+        got = [r[0] for r in c.execute("SELECT term FROM sv ORDER BY offset").fetchall()]
+        if len(self._cache) < 65536:
+            self._cache[phrase] = got
+        return got
+
+    def term_ids(self, phrase: str) -> list[int]:
+        return [self.vocab.get(t, -1) for t in self.tokens_of(phrase)]
+
+
+def create_fts_tables(conn, tokenizer: str, content_synced: bool = True):
+    """The tables of text_search.rs:306-384 (ensure_tables) in plain SQL: the settings table, the content table and the
+    FTS5 table over it -- or, content_synced=False, a plain FTS5 table of the same name and column."""
+    conn.execute(f'CREATE TABLE IF NOT EXISTS "{FTS_CONFIG_TABLE}" (key TEXT PRIMARY KEY, value TEXT NOT NULL)')
+    if content_synced:
+        conn.execute(f'CREATE TABLE IF NOT EXISTS "{FTS_CONTENT_TABLE}" (rowid INTEGER PRIMARY KEY, '
+                     f'"{FTS_CONTENT_COLUMN}" TEXT NOT NULL DEFAULT \'\')')
+        conn.execute(f'CREATE VIRTUAL TABLE IF NOT EXISTS "{FTS_TABLE}" USING fts5("{FTS_CONTENT_COLUMN}", '
+                     f"content='{FTS_CONTENT_TABLE}', content_rowid='rowid', tokenize='{TOKENIZERS[tokenizer]}')")
+    else:
+        conn.execute(f'CREATE VIRTUAL TABLE IF NOT EXISTS "{FTS_TABLE}" USING fts5("{FTS_CONTENT_COLUMN}", '
+                     f"tokenize='{TOKENIZERS[tokenizer]}')")
+    conn.execute(f'INSERT OR REPLACE INTO "{FTS_CONFIG_TABLE}"(key, value) VALUES (\'tokenizer\', ?)', (tokenizer,))
+
+
+def insert_fts_rows(conn, texts, doc_ids, tokenizer: str, content_synced: bool = True):
+    """insert_rows (text_search.rs:386-440): the raw text into the content table, the prepared text into the FTS5 table."""
+    with conn:
+        for doc_id, text in zip(doc_ids, texts):
+            if content_synced:
+                conn.execute(f'INSERT OR REPLACE INTO "{FTS_CONTENT_TABLE}"(rowid, "{FTS_CONTENT_COLUMN}") VALUES (?, ?)',
+                             (int(doc_id), text))
+            conn.execute(f'INSERT INTO "{FTS_TABLE}"(rowid, "{FTS_CONTENT_COLUMN}") VALUES (?, ?)',
+                         (int(doc_id), prepare_document_text(text, tokenizer)))
+
+
+# ---- FTS5 query text -> phrases of term ids --------------------------------------------------------------------------------
+
+@dataclass
+class TextQuery:
+    """A compiled keyword query (np_text_query): phrase p owns terms[phrase_offsets[p] : phrase_offsets[p + 1]], -1 = a token
+    the vocabulary does not hold; mode NP_TEXT_AND or NP_TEXT_OR."""
+    terms: np.ndarray            # int32
+    phrase_offsets: np.ndarray   # int32 [n_phrases + 1]
+    mode: int = NP_TEXT_AND
+
+    @property
+    def n_phrases(self) -> int:
+        return int(self.phrase_offsets.size) - 1
+
+    @classmethod
+    def from_phrases(cls, phrases, mode: int = NP_TEXT_AND) -> "TextQuery":
+        phrases = [list(p) for p in phrases]
+        off = np.zeros(len(phrases) + 1, np.int32)
+        if phrases:
+            off[1:] = np.cumsum([len(p) for p in phrases])
+        flat = [t for p in phrases for t in p]
+        return cls(np.asarray(flat, np.int32).reshape(-1), off, int(mode))
+
+    def phrases(self) -> list:
+        return [self.terms[self.phrase_offsets[i]: self.phrase_offsets[i + 1]].tolist() for i in range(self.n_phrases)]
+
+
+MATCH_NOTHING = [[-1]]   # one phrase of one unknown token: the compiled form of a query that matches no document
+
+
+def _bareword_char(ch: str) -> bool:
+    return ch.isascii() and (ch.isalnum() or ch == "_") or ord(ch) >= 0x80 or ch == "\x1a"
+
+
+def _lex(text: str):
+    """(kind, value) items: ('phrase', string) for a double-quoted string or a bareword, ('op', 'AND' | 'OR')."""
+    items, i, n = [], 0, len(text)
+    special = {"(": "parentheses", ")": "parentheses", "*": "a prefix query (*)", "^": "an initial-token query (^)",
+               ":": "a column filter (:)", "{": "a column filter ({})", "}": "a column filter ({})", "-": "a column filter (-)",
+               "+": "phrase concatenation (+)", ",": "a NEAR argument list (,)"}
+    while i < n:
+        ch = text[i]
+        if ch in " \t\n\r":
+            i += 1
+        elif ch == '"':
+            j, buf = i + 1, []
+            while True:
+                if j >= n:
+                    raise TextQueryError("an unterminated string")
+                if text[j] == '"':
+                    if j + 1 < n and text[j + 1] == '"':
+                        buf.append('"')
+                        j += 2
+                        continue
+                    break
+                buf.append(text[j])
+                j += 1
+            items.append(("phrase", "".join(buf)))
+            i = j + 1
+        elif _bareword_char(ch):
+            j = i
+            while j < n and _bareword_char(text[j]):
+                j += 1
+            word = text[i:j]
+            k = j
+            while k < n and text[k] in " \t\n\r":
+                k += 1
+            if word == "NOT":
+                raise TextQueryError("NOT")
+            if word == "NEAR" and k < n and text[k] == "(":
+                raise TextQueryError("NEAR")
+            items.append(("op", word) if word in ("AND", "OR") else ("phrase", word))
+            i = j
+        elif ch in special:
+            raise TextQueryError(special[ch])
+        else:
+            raise TextQueryError(f"the character {ch!r} outside a string (an FTS5 syntax error)")
+    return items
+
+
+def parse_text_query(text: str):
+    """The shape of a query compile_text_query accepts: (groups, mode) where mode is NP_TEXT_AND or NP_TEXT_OR and groups is
+    a list of lists of phrase strings -- for AND, the runs of adjacent phrases between explicit ANDs; for OR, one phrase per
+    group.  Raises TextQueryError for anything else."""
+    items = _lex(text)
+    if not items:
+        raise TextQueryError("an empty query (an FTS5 syntax error)")
+    groups, ops, want_phrase = [[]], set(), True
+    for kind, val in items:
+        if kind == "op":
+            if want_phrase:
+                raise TextQueryError(f"{val} without a phrase before it (an FTS5 syntax error)")
+            ops.add(val)
+            groups.append([])
+            want_phrase = True
+        else:
+            groups[-1].append(val)
+            want_phrase = False
+    if want_phrase:
+        raise TextQueryError("an operator without a phrase after it (an FTS5 syntax error)")
+    if len(ops) > 1:
+        raise TextQueryError("AND mixed with OR")
+    if ops == {"OR"} and any(len(g) > 1 for g in groups):
+        raise TextQueryError("OR mixed with implicit AND")
+    return groups, (NP_TEXT_OR if ops == {"OR"} else NP_TEXT_AND)
+
+
+def compile_text_query(text: str, data: TextIndexData) -> TextQuery:
+    """FTS5 query text -> TextQuery, for what the two sanitizers emit and what people type: double-quoted phrases or bare
+    words, joined all by AND (implicit, explicit or both) or all by OR.  Each phrase is tokenised by SQLite's own tokenizer
+    with the index's tokenize= clause, so a word the tokenizer splits (parse_request under unicode61, any word under
+    trigram) becomes a phrase of several tokens.  NOT, NEAR, *, ^, column filters, parentheses, + and AND mixed with OR
+    raise TextQueryError naming the construct; nothing is approximated.
+
+    A phrase without tokens ("" or "!!!", or fewer than three characters under trigram) does what SQLite 3.37 does with it:
+    among phrases joined by OR or by implicit AND it is dropped; a side of an explicit AND that holds nothing else makes the
+    whole query match nothing, and so does a query all of whose phrases are empty.  A query that matches nothing compiles
+    to one phrase of one unknown token."""
+    groups, mode = parse_text_query(text)
+    phrases, nothing = [], False
+    for g in groups:
+        kept = [ids for ids in (data.term_ids(p) for p in g) if ids]
+        if not kept and mode == NP_TEXT_AND:
+            nothing = True
+        phrases += kept
+    if nothing or not phrases:
+        return TextQuery.from_phrases(MATCH_NOTHING, NP_TEXT_AND)
+    if len(phrases) > NP_TEXT_MAX_PHRASES:
+        raise TextQueryError(f"more than {NP_TEXT_MAX_PHRASES} phrases")
+    if sum(len(p) for p in phrases) > NP_TEXT_MAX_TOKENS:
+        raise TextQueryError(f"more than {NP_TEXT_MAX_TOKENS} tokens")
+    return TextQuery.from_phrases(phrases, mode)
