@@ -643,7 +643,7 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
   unsigned long long* h_nhit = (unsigned long long*)(src + prog.o_nhit);
   if (prog.n_items > 0) {
     NP_HIP(hipMemsetAsync(d_prog + prog.o_nhit, 0, (size_t)prog.n_items * 8, st));
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(512, (prog.max_item_df + TEXT_TPB - 1) / TEXT_TPB));
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (prog.max_item_df + TEXT_TPB - 1) / TEXT_TPB));
     for (int64_t i0 = 0; i0 < prog.n_items; i0 += 65535) {   // (the items are a grid dimension)
       const TextHitP hp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
                         (const int32_t*)(d_prog + prog.o_item) + i0, (unsigned long long*)(d_prog + prog.o_nhit) + i0};

@@ -15,6 +15,10 @@ namespace np {
 // per document of the slice in LDS -- 45 KB with the phrase ranges, three workgroups per CU of 160 KB
 constexpr int64_t NP_TEXT_SLICE_DOCS = 4096;
 
+// workgroups (of 256 lanes) per phrase of the counting pass at most: a first posting list longer than 256 times this many
+// entries is walked in several grid strides
+constexpr int64_t NP_TEXT_HIT_BLOCKS = 512;
+
 // entries a slice hands to the merge: no slice holds more than its documents
 inline int64_t text_slice_keep(int32_t top_k) { return top_k < NP_TEXT_SLICE_DOCS ? top_k : NP_TEXT_SLICE_DOCS; }
 

@@ -131,6 +131,45 @@ def test_bm25_is_bit_equal_to_sqlite_and_the_matching_sets_are_equal(corpus):
     assert len(queries) * len(CORPORA) >= 300
 
 
+def test_queries_at_the_limits_are_bit_equal_to_sqlite():
+    """64 phrases, a phrase of 256 tokens, overlapping occurrences of a repeated token and position lists of 300 entries, on
+    a corpus of 40 documents: SQLite accepts every one of them, and the restatement has its bm25() bits and its rows.  The
+    GPU tests run the same queries (R.limit_queries) against the restatement."""
+    n = 40
+    texts = R.limit_texts(n)
+    data = T.TextIndexData.from_texts(texts)
+    conn = oracle_table(texts, "unicode61", False)
+    rs = R.Restated(data, n)
+    try:
+        queries = dict(R.limit_queries(data))
+        assert len(queries) == 8
+        # the frequencies the corpus was built for
+        f = rs.phrase_freqs(queries["256 x aa"].phrases()[0])
+        assert f == {1: 45, n - 3: 45, n - 1: 45}                          # positions 0 .. 44 of 300
+        f = rs.phrase_freqs(queries["128 x aa bb"].phrases()[0])
+        assert f == {3: 23, 4: 22, n - 2: 23}                              # every second position
+        f = rs.phrase_freqs(queries["aa aa aa"].phrases()[0])
+        assert f[2] == 3 and f[1] == 298 and f[9] == 1 and set(f) == {1, 2, 9, n - 3, n - 1}   # occurrences overlap
+        assert sorted(rs.scores(queries["64 words AND"])) == [5, 6, 8, n - 2, n - 1]
+        assert sorted(rs.scores(queries["64 words OR"])) == [5, 6, 7, 8, n - 2, n - 1]
+        assert sorted(rs.scores(queries["16 x 4 AND"])) == [5, 8, n - 2, n - 1]
+        assert rs.scores(queries["63 words and an unknown AND"]) == {}
+        assert len(rs.scores(queries["63 unknown OR aa"])) > 12
+        for name, q in queries.items():
+            assert q.n_phrases in (1, 16, 64) and max(len(p) for p in q.phrases()) in (1, 3, 4, 256)
+            s = R.match_string(q, data)
+            want = sqlite_rows(conn, s)
+            got = rs.scores(q)
+            assert set(got) == set(want), f"{name}: {sorted(got)} vs {sorted(want)}"
+            for d, v in want.items():
+                assert bits(got[d]) == bits(v), f"{name}: document {d}: {got[d]!r} vs {v!r}"
+            ids, sc = rs.search(q, 10)
+            norm = sorted(sqlite_topk(conn, s, 10), key=lambda r: (-r[1], r[0]))
+            assert [r[1] for r in norm] == [float(got[d]) for d in ids]
+    finally:
+        conn.close()
+
+
 def test_compiled_strings_match_what_sqlite_matches(corpus):
     tok, vocab, texts, data, rs, conn = corpus
     accepted = ["wo0", "wo0 wo1", "wo0 AND wo1", "wo0 OR wo1 OR zzq", '"wo0 wo1"', '"wo1 wo0" wo2', 'wo0 "wo1"wo2', "wo1 and wo0",

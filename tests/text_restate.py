@@ -76,7 +76,11 @@ class Restated:
 
     def search(self, query, top_k, subset=None):
         """(ids int64, scores float32): f64 score descending, ties by ascending id; `subset`: only these ids."""
-        sc = self.scores(query)
+        return self.rank(self.scores(query), top_k, subset)
+
+    @staticmethod
+    def rank(sc, top_k, subset=None):
+        """search() on the {document: f64 score} of scores(): one scoring serves several top_k and subsets."""
         if subset is not None:
             keep = set(int(x) for x in np.asarray(subset).reshape(-1))
             sc = {d: s for d, s in sc.items() if d in keep}
@@ -170,6 +174,42 @@ def random_queries(data, n, seed, unknown=True):
             phrases.append(list(phrases[0]))
         out.append(T.TextQuery.from_phrases(phrases, rng.choice([T.NP_TEXT_AND, T.NP_TEXT_OR])))
     return out
+
+
+LIMIT_WORDS = [f"lw{i:02d}" for i in range(64)]
+LIMIT_BASE = 10   # documents limit_texts() puts first
+
+
+def limit_texts(n):
+    """n >= 16 documents for the limits of a query (NP_TEXT_MAX_PHRASES = 64 phrases, NP_TEXT_MAX_TOKENS = 256 tokens of a
+    phrase).  The first LIMIT_BASE: 1 = "aa" 300 times, 2 = "aa" 5 times, 3 and 4 = "aa bb" / "bb aa" 150 times, 5 = the 64
+    words of LIMIT_WORDS in order, 6 = the same reversed (every word, none of the phrases), 7 = the first 32, 8 = the 64 twice
+    over, 9 = a short mix.  Then short filler documents, "aa" in every third; the last three hold copies: n - 3 = document 1,
+    n - 2 = 5 then 3, n - 1 = 1 then 5 (with n = one slice + 1 these sit at the slice boundary and in the last document)."""
+    words = " ".join(LIMIT_WORDS)
+    rep, alt = " ".join(["aa"] * 300), " ".join(["aa bb"] * 150)
+    base = ["", rep, " ".join(["aa"] * 5), alt, " ".join(["bb aa"] * 150), words, " ".join(reversed(LIMIT_WORDS)),
+            " ".join(LIMIT_WORDS[:32]), words + " " + words, "aa aa bb aa aa aa bb"]
+    assert len(base) == LIMIT_BASE and n >= LIMIT_BASE + 6
+    fill = [f"zz fill{i % 37}" + (" aa" if i % 3 == 0 else "") for i in range(n - LIMIT_BASE - 3)]
+    return base + fill + [rep, words + " " + alt, rep + " " + words]
+
+
+def limit_queries(data):
+    """[(name, TextQuery)] at the limits, over limit_texts(): the query shapes the CPU test pins to SQLite and the GPU test
+    runs."""
+    v = data.vocab
+    AND, OR = T.NP_TEXT_AND, T.NP_TEXT_OR
+    aa, bb = v["aa"], v["bb"]
+    w = [v[x] for x in LIMIT_WORDS]
+    return [("256 x aa", T.TextQuery.from_phrases([[aa] * 256], AND)),
+            ("128 x aa bb", T.TextQuery.from_phrases([[aa, bb] * 128], AND)),
+            ("aa aa aa", T.TextQuery.from_phrases([[aa] * 3], AND)),
+            ("64 words AND", T.TextQuery.from_phrases([[x] for x in w], AND)),
+            ("64 words OR", T.TextQuery.from_phrases([[x] for x in w], OR)),
+            ("16 x 4 AND", T.TextQuery.from_phrases([w[4 * i: 4 * i + 4] for i in range(16)], AND)),
+            ("63 words and an unknown AND", T.TextQuery.from_phrases([[x] for x in w[:40]] + [[-1]] + [[x] for x in w[40:63]], AND)),
+            ("63 unknown OR aa", T.TextQuery.from_phrases([[-1]] * 63 + [[aa]], OR))]
 
 
 def match_string(query, data):
