@@ -394,7 +394,8 @@ int np_hip_score_pairs_device(const np_index* index, const float* d_queries, con
 /* ---- metadata filters: columns in HBM, WHERE evaluated to a subset on the device ---------------------
  * The crate computes a request's subset with filtering::where_condition (filtering.rs:1880: a SQLite query over metadata.db)
  * and hands the id list to search.  Here a few typed attributes per document live next to the index, a filter crosses the
- * ABI as a postfix program over them (strings never do: the host resolves text against a dictionary into i32 codes), and
+ * ABI as a postfix program over them (pattern strings never do: the host resolves text against a dictionary into i32 codes,
+ * and a REGEXP / LIKE pattern crosses as a DFA table -- "text predicates" below), and
  * the ids it selects are produced on the device, with SQLite's semantics including its three-valued logic for NULL.
  *
  * np_hip_index_set_columns replaces the handle's columns (n_cols = 0 drops them; at most NP_MAX_COLUMNS).  `data` and `valid`
@@ -435,6 +436,7 @@ int np_hip_index_set_columns(np_index* index, const np_column* cols, int32_t n_c
 #define NP_F_AND 5
 #define NP_F_OR 6
 #define NP_F_NOT 7
+#define NP_F_MATCH 16   /* text predicates below; 8..15 stay unknown ops */
 #define NP_FILTER_MAX_OPS 256
 #define NP_FILTER_MAX_DEPTH 32
 #define NP_FILTER_MAX_VALUES (1 << 20)
@@ -480,6 +482,68 @@ int np_hip_search_exact_filtered(const np_index* index, const float* queries, co
                                  int32_t dim, int32_t top_k, int32_t precision,
                                  const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
                                  int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+
+/* ---- text predicates: the dictionary text of a CODE column in HBM, REGEXP and LIKE as byte DFAs ------
+ * The crate's grep side is filtering::where_condition_regexp (filtering.rs:1969): `col REGEXP ?` with the Rust regex crate's
+ * is_match behind it.  Here a pattern crosses the ABI as a dense DFA over bytes, not as a string: a Rust binding builds it
+ * exactly with regex-automata, the Python package compiles a stated dialect (next_plaid_amd/regexes.py) and refuses the rest.
+ *
+ * np_hip_index_set_column_text keeps the dictionary strings of one NP_COL_CODE column on the device, indexed by code: the
+ * strings' UTF-8 bytes concatenated and offsets[n_strings + 1] into them.  NP_ERR_INVALID_ARGUMENT before any allocation: the
+ * column is not a CODE column, n_strings does not exceed the largest code of the handle's rows (or a code is negative), the
+ * offsets do not ascend from 0, a string is longer than NP_MATCH_MAX_STRING_BYTES (4 MiB: one lane walks one string, so a longer
+ * one would hold its block of the launch without bound).  n_strings = 0 drops the text; np_hip_index_set_columns drops it with the columns.  The bytes
+ * count in np_info.device_bytes; NP_ERR_OUT_OF_MEMORY leaves the previous text in place.  A sharded handle keeps the whole
+ * dictionary (codes are global).  Needs exclusive access to the handle, as np_hip_index_set_columns does.
+ *
+ * A packed DFA is n_words 32-bit words:
+ *   [0] NP_DFA_MAGIC   [1] n_states (1..NP_DFA_MAX_STATES)   [2] n_classes (1..NP_DFA_MAX_CLASSES)   [3] start state
+ *   [4 .. 68)          class_of[256], one byte each, byte b in bits 8 (b & 3) of word 4 + b / 4
+ *   [68 .. 68 + F)     per-state flags, one byte each in the same way, F = ceil(n_states / 4)
+ *   [68 + F .. )       table[n_states][n_classes] of u16 next states, entry e in bits 16 (e & 1) of word e / 2; ceil(n_states * n_classes / 2) words
+ * A string matches if the walk from the start state over its bytes (state = table[state][class_of[byte]]) ends in a state with
+ * NP_DFA_ACCEPT_AT_END.  NP_DFA_MATCHED and NP_DFA_DEAD mark absorbing states (every / no continuation matches) at which a
+ * lane may stop.  Checked before any launch (the message names the DFA and the state): sizes consistent, every transition
+ * < n_states, every class < n_classes, MATCHED and DEAD rows point to themselves, MATCHED implies ACCEPT_AT_END, DEAD excludes
+ * it.  In a filter the same words are values[first_value .. first_value + n_values), one word per i64.
+ *
+ * np_hip_text_match: bit s of out_bits[d * ceil(n_strings / 32) + s / 32] = DFA d accepts dictionary string s (bits past the
+ * last string are zero).  The same bits from run to run and for any tiling: verdicts leave as ballot words, no atomics.
+ * Scratch comes out of a context's arena (re-entrant on a shared handle); the call runs in chunks that fit the workspace
+ * budget and a budget that holds no chunk is NP_ERR_OUT_OF_MEMORY.  A table within the plan's LDS budget is walked out of LDS,
+ * a larger one out of global memory (np_hip_index_tune "match_lds" = that budget in KiB, 0 = always global).
+ *
+ * NP_F_MATCH (op 16) is the filter leaf: column = a CODE column that has text, arg = 0, values = the packed DFA.  TRUE / FALSE
+ * by the cell's dictionary string, UNKNOWN on a NULL cell as LIKE gives, so NOT over a NULL cell selects nothing.  (The crate
+ * differs: its regexp function reads the argument as String, so a NULL cell fails the whole query.)  One match pass per
+ * distinct (column, DFA) of a call writes a bitmap over codes and the per-document leaf reads bit[code[d]].  A column without
+ * text or an invalid DFA is NP_ERR_INVALID_ARGUMENT before any launch. */
+#define NP_DFA_MAGIC 0x4146444Eu
+#define NP_DFA_HEADER_WORDS 68
+#define NP_DFA_MAX_STATES 4096
+#define NP_DFA_MAX_CLASSES 256
+#define NP_DFA_ACCEPT_AT_END 1
+#define NP_DFA_MATCHED 2
+#define NP_DFA_DEAD 4
+#define NP_MATCH_MAX_STRING_BYTES (4 << 20)
+typedef struct np_dfa {
+  const uint32_t* words;
+  int64_t n_words;
+} np_dfa;
+typedef struct np_match_report {
+  int32_t tile_bytes;        /* bytes of text a block stages at a time */
+  int32_t table_lds_bytes;   /* the plan's LDS budget for a table */
+  int32_t n_lds, n_global;   /* DFAs whose table was walked out of LDS / out of global memory */
+  int32_t n_chunks;          /* (DFA group, string chunk) passes */
+  int32_t reserved;
+  int64_t bytes_scanned;     /* text bytes x DFAs (lanes stop early at MATCHED and DEAD, so an upper bound of the lookups) */
+  float ms;                  /* wall time of the call */
+  int32_t reserved2;
+} np_match_report;
+int np_hip_index_set_column_text(np_index* index, int32_t column, const uint8_t* bytes, const int64_t* offsets /* [n_strings + 1] */,
+                                 int64_t n_strings);
+int np_hip_text_match(const np_index* index, int32_t column, const np_dfa* dfas, int32_t n_dfas,
+                      uint32_t* out_bits /* [n_dfas][ceil(n_strings / 32)] */, np_match_report* report /* may be NULL */);
 
 /* ---- hybrid search: the keyword index in HBM, FTS5-exact BM25, fusion ---------------------------------
  * The crate's /search handler runs, next to index.search, an SQLite FTS5 query (text_search.rs:1246-1342: MATCH ordered by

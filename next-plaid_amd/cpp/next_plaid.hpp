@@ -234,6 +234,30 @@ inline std::vector<int64_t> update_ids(const np_update_report& r, size_t n) {
   return ids;
 }
 
+// A packed byte DFA (include/nextplaid_hip.h, "text predicates"): what a REGEXP or LIKE pattern crosses the ABI as.  There is
+// no pattern compiler here, as there is no WHERE parser: a Rust host builds the table with regex-automata, the Python package
+// with next_plaid_amd/regexes.py.  The library checks every table before a launch.
+struct Dfa {
+  std::vector<uint32_t> words;
+  Dfa() = default;
+  explicit Dfa(std::vector<uint32_t> w) : words(std::move(w)) {}
+  // from its parts: class_of[256], flags[n_states] (NP_DFA_*), table[n_states * n_classes]
+  Dfa(uint32_t start, const std::vector<uint8_t>& class_of, const std::vector<uint8_t>& flags, const std::vector<uint16_t>& table) {
+    const size_t ns = flags.size(), nc = ns ? table.size() / ns : 0, f0 = NP_DFA_HEADER_WORDS, t0 = f0 + (ns + 3) / 4;
+    if (class_of.size() != 256 || ns == 0 || nc * ns != table.size())
+      throw Error(NP_ERR_INVALID_ARGUMENT, "Dfa: class_of needs 256 entries and table n_states * n_classes");
+    words.assign(t0 + (ns * nc + 1) / 2, 0u);
+    words[0] = NP_DFA_MAGIC;
+    words[1] = (uint32_t)ns;
+    words[2] = (uint32_t)nc;
+    words[3] = start;
+    for (size_t b = 0; b < 256; ++b) words[4 + b / 4] |= (uint32_t)class_of[b] << (8 * (b & 3));
+    for (size_t s = 0; s < ns; ++s) words[f0 + s / 4] |= (uint32_t)flags[s] << (8 * (s & 3));
+    for (size_t e = 0; e < table.size(); ++e) words[t0 + e / 2] |= (uint32_t)table[e] << (16 * (e & 1));
+  }
+  np_dfa c() const { return np_dfa{words.data(), (int64_t)words.size()}; }
+};
+
 // A metadata filter as the postfix program of np_hip_filter_eval (include/nextplaid_hip.h): leaves push a value, not_()
 // replaces the top, and_() / or_() replace the top two; every value is TRUE, FALSE or UNKNOWN (SQLite's three-valued logic)
 // and a document is selected where the program leaves TRUE.  `x NOT IN (...)` is in(...) followed by not_().  There is no
@@ -263,6 +287,10 @@ class FilterProgram {
     return leaf(NP_F_IN, column, has_null ? 1 : 0, std::move(b));
   }
   FilterProgram& is_null(int column) { return leaf(NP_F_IS_NULL, column, 0, {}); }
+  // `column` (CODE, with text on the device: MmapIndex::set_column_text) matches the DFA; UNKNOWN on a NULL cell
+  FilterProgram& match(int column, const Dfa& dfa) {
+    return leaf(NP_F_MATCH, column, 0, std::vector<int64_t>(dfa.words.begin(), dfa.words.end()));
+  }
   FilterProgram& constant(Const c) { return node(NP_F_CONST, c); }
   FilterProgram& and_() { return node(NP_F_AND, 0); }
   FilterProgram& or_() { return node(NP_F_OR, 0); }
@@ -531,6 +559,35 @@ class MmapIndex {
     }
     check(np_hip_index_set_columns(h_, c.data(), (int32_t)c.size()));
     check(np_hip_index_info(h_, &info_));
+  }
+
+  // The dictionary strings of a CODE column in HBM (np_hip_index_set_column_text): string c is the text of code c.  An empty
+  // vector drops the text; set_columns() drops it with the columns.  Needs exclusive access to the handle.
+  void set_column_text(int column, const std::vector<std::string>& dictionary) {
+    require_device("set_column_text");
+    std::vector<int64_t> off(dictionary.size() + 1, 0);
+    std::string bytes;
+    for (size_t i = 0; i < dictionary.size(); ++i) {
+      bytes += dictionary[i];
+      off[i + 1] = (int64_t)bytes.size();
+    }
+    check(np_hip_index_set_column_text(h_, column, (const uint8_t*)bytes.data(), off.data(), (int64_t)dictionary.size()));
+    check(np_hip_index_info(h_, &info_));
+  }
+
+  // Which of a column's n_strings dictionary strings every DFA accepts (np_hip_text_match): out[d][c] for DFA d and code c.
+  std::vector<std::vector<bool>> text_match(int column, const std::vector<Dfa>& dfas, size_t n_strings,
+                                            np_match_report* report = nullptr) const {
+    require_device("text_match");
+    std::vector<np_dfa> d;
+    for (const Dfa& x : dfas) d.push_back(x.c());
+    const size_t nw = (n_strings + 31) / 32;
+    std::vector<uint32_t> bits(std::max<size_t>(dfas.size() * nw, 1), 0u);
+    check(np_hip_text_match(h_, column, d.data(), (int32_t)d.size(), bits.data(), report));
+    std::vector<std::vector<bool>> out(dfas.size(), std::vector<bool>(n_strings));
+    for (size_t j = 0; j < dfas.size(); ++j)
+      for (size_t c = 0; c < n_strings; ++c) out[j][c] = (bits[j * nw + c / 32] >> (c & 31)) & 1u;
+    return out;
   }
 
   // The global ids every filter selects among this handle's documents, ascending (np_hip_filter_eval).

@@ -29,6 +29,7 @@ struct FilterEvalP {
   int64_t d0, n;                // the chunk's documents [d0, d0 + n) of the shard
   int64_t nw;                   // mask words per filter of the chunk (blocks * 256)
   unsigned long long* mask;     // [chunk filters][nw]
+  const uint32_t* match_bits;   // NP_F_MATCH: the bitmaps over codes of the call's match passes (first_value = a bitmap's word)
 };
 
 template <class T>
@@ -63,13 +64,17 @@ __global__ void __launch_bounds__(FILTER_TPB) filter_mask_kernel(FilterEvalP p) 
   int sp = 0;              // uniform
   for (int o = ob; o < oe; ++o) {
     const np_filter_op op = p.ops[o];   // uniform address
-    if (op.op <= NP_F_IS_NULL) {
+    if (op.op <= NP_F_IS_NULL || op.op == NP_F_MATCH) {
       const FilterCol c = p.cols[op.column];
       const bool valid = c.valid ? ((c.valid[d >> 5] >> (d & 31)) & 1u) != 0 : true;
       bool t = false, k = valid;
       if (op.op == NP_F_IS_NULL) {
         t = !valid;
         k = true;
+      } else if (op.op == NP_F_MATCH) {
+        // every code of the handle's rows is below the text's n_strings (np_hip_index_set_column_text), NULL rows included
+        const uint32_t code = (uint32_t) static_cast<const int32_t*>(c.data)[d];
+        t = k && ((p.match_bits[op.first_value + (code >> 5)] >> (code & 31)) & 1u);
       } else {
         const int64_t* __restrict__ v = p.values + op.first_value;
         if (c.type == NP_COL_F64) {
@@ -249,6 +254,7 @@ int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n
       set_error("Filter failed: %s", why);
       return NP_ERR_INVALID_ARGUMENT;
     }
+  NP_TRY(match_check_text(ix, filters, n_filters));
   if (for_search) {
     if (B > 0 && n_filters > 0 && !query_filter) {
       set_error("Filter failed: n_filters > 0 but query_filter is NULL");
@@ -281,13 +287,15 @@ struct FilterRun {
   uint32_t* d_counts = nullptr;
   int64_t* d_base = nullptr;
   int64_t* d_stage = nullptr;          // staged ids [plan.filters][plan.docs] (host output only)
+  uint32_t* d_match_bits = nullptr;    // the NP_F_MATCH leaves' bitmaps over codes, one per distinct (column, DFA)
   std::vector<int64_t> h_table;
 
   size_t program_bytes(int64_t* n_ops, int64_t* n_vals) const {
     int64_t o = 0, v = 0;
     for (int32_t f = 0; f < n_filters; ++f) {
       o += filters[f].n_ops;
-      v += filters[f].n_values;
+      for (int i = 0; i < filters[f].n_ops; ++i)   // a MATCH leaf's table stays on the host: the device reads its bitmap
+        if (filters[f].ops[i].op != NP_F_MATCH) v += std::max(filters[f].ops[i].n_values, 0);
     }
     *n_ops = o;
     *n_vals = v;
@@ -298,11 +306,16 @@ struct FilterRun {
   int prepare(DevBuf& scratch, bool stage) {
     int64_t n_ops = 0, n_vals = 0;
     const size_t b_prog = program_bytes(&n_ops, &n_vals);
+    std::vector<MatchJob> jobs;
+    std::vector<int64_t> match_at;   // per MATCH op, in program order: its bitmap's first word
+    int64_t match_words = 0, match_work = 0;
+    NP_TRY(match_collect(ix, filters, n_filters, &jobs, &match_at, &match_words, &match_work));
+    const size_t b_match = up256((size_t)match_words * 4) + up256((size_t)match_work);
     const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
     const int64_t all_blocks = std::max<int64_t>(1, (ix->n_docs + NP_FILTER_BLOCK_DOCS - 1) / NP_FILTER_BLOCK_DOCS);
     // the tables are sized for the worst chunking: one block per document chunk
     const size_t b_tab_max = 2 * up256((size_t)(n_filters * all_blocks + 1) * 8);
-    if (!filter_plan(budget, (int64_t)(b_prog + b_tab_max + 4096), ix->n_docs, n_filters, stage, &plan)) {
+    if (!filter_plan(budget, (int64_t)(b_prog + b_match + b_tab_max + 4096), ix->n_docs, n_filters, stage, &plan)) {
       set_error("Filter failed: one filter over %lld documents does not fit the workspace budget of %lld bytes",
                 (long long)NP_FILTER_BLOCK_DOCS, (long long)budget);
       return NP_ERR_OUT_OF_MEMORY;
@@ -315,7 +328,7 @@ struct FilterRun {
     const size_t b_mask = up256((size_t)plan.filters * blocks * FILTER_TPB * 8), b_cnt = up256((size_t)plan.filters * blocks * 4),
                  b_base = up256((size_t)plan.filters * blocks * 8);
     const size_t b_stage = stage ? up256((size_t)plan.filters * plan.docs * 8) : 0;
-    NP_TRY(scratch.reserve(b_prog + b_tot + b_tab + b_mask + b_cnt + b_base + b_stage));
+    NP_TRY(scratch.reserve(b_prog + b_tot + b_tab + b_mask + b_cnt + b_base + b_stage + b_match));
     char* at = scratch.as<char>();
     auto take = [&](size_t bytes) {
       char* r = at;
@@ -331,20 +344,29 @@ struct FilterRun {
     d_counts = (uint32_t*)take(b_cnt);
     d_base = (int64_t*)take(b_base);
     d_stage = stage ? (int64_t*)take(b_stage) : nullptr;
-    // the programs, with every op's first_value re-based into the concatenated values
+    d_match_bits = (uint32_t*)take(up256((size_t)match_words * 4));
+    char* d_match_work = take(up256((size_t)match_work));
+    // the programs, with every op's constants copied behind one another and its first_value re-based to them
     std::vector<np_filter_op> ops((size_t)n_ops);
     std::vector<int32_t> begin((size_t)n_filters + 1);
     std::vector<int64_t> vals((size_t)n_vals);
     int64_t o = 0, v = 0;
+    size_t m = 0;
     for (int32_t f = 0; f < n_filters; ++f) {
       begin[f] = (int32_t)o;
       for (int i = 0; i < filters[f].n_ops; ++i) {
         ops[o] = filters[f].ops[i];
-        ops[o].first_value = ops[o].n_values > 0 ? ops[o].first_value + v : 0;
+        if (ops[o].op == NP_F_MATCH) {
+          ops[o].first_value = match_at[m++];   // the leaf reads the bitmap, not the table
+        } else if (ops[o].n_values > 0) {
+          memcpy(vals.data() + v, filters[f].values + ops[o].first_value, (size_t)ops[o].n_values * 8);
+          ops[o].first_value = v;
+          v += ops[o].n_values;
+        } else {
+          ops[o].first_value = 0;
+        }
         ++o;
       }
-      if (filters[f].n_values > 0) memcpy(vals.data() + v, filters[f].values, (size_t)filters[f].n_values * 8);
-      v += filters[f].n_values;
     }
     begin[n_filters] = (int32_t)o;
     // pageable sources: the copies complete before the vectors go out of scope
@@ -352,6 +374,7 @@ struct FilterRun {
     NP_HIP(hipMemcpyAsync(d_op_begin, begin.data(), begin.size() * 4, hipMemcpyHostToDevice, st));
     if (n_vals > 0) NP_HIP(hipMemcpyAsync(d_values, vals.data(), (size_t)n_vals * 8, hipMemcpyHostToDevice, st));
     NP_HIP(hipStreamSynchronize(st));
+    NP_TRY(match_run_jobs(ix, st, jobs, d_match_bits, d_match_work));
     return NP_OK;
   }
 
@@ -359,7 +382,7 @@ struct FilterRun {
   int chunk_masks(int32_t f0, int32_t nf, int64_t dc) {
     const int64_t d0 = dc * plan.docs, n = std::min(plan.docs, ix->n_docs - d0), blocks = plan.blocks();
     const int64_t nw = blocks * FILTER_TPB, n_words = (n + 63) / 64;
-    FilterEvalP p{ix->d_coltab.get(), d_ops, d_op_begin, d_values, f0, d0, n, nw, d_mask};
+    FilterEvalP p{ix->d_coltab.get(), d_ops, d_op_begin, d_values, f0, d0, n, nw, d_mask, d_match_bits};
     filter_mask_kernel<<<dim3((unsigned)((n + FILTER_TPB - 1) / FILTER_TPB), (unsigned)nf), FILTER_TPB, 0, st>>>(p);
     // every block of the plan is counted (words past n_words count 0): the scan reads `blocks` counts per filter
     filter_count_kernel<<<dim3((unsigned)blocks, (unsigned)nf), FILTER_TPB, 0, st>>>(d_mask, nw, n_words, blocks, d_counts);

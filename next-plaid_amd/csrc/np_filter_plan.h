@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../../include/nextplaid_hip.h"
+#include "np_match_plan.h"
 
 namespace np {
 
@@ -58,6 +59,19 @@ inline int filter_check_program(const np_filter* f, int32_t filter, const int32_
           const bool asc = type == NP_COL_F64 ? filter_f64_of(v[k - 1]) < filter_f64_of(v[k]) : v[k - 1] < v[k];
           if (!asc) return fail(i, "IN list is not ascending and distinct");
         }
+      ++depth;
+    } else if (o.op == NP_F_MATCH) {
+      // the packed DFA is checked here; that the column has text on the device is the handle's to say (match_collect)
+      if (o.column < 0 || o.column >= n_cols) return fail(i, "column index out of range");
+      if (col_types[o.column] != NP_COL_CODE) return fail(i, "MATCH needs a CODE column");
+      if (o.arg != 0) return fail(i, "arg must be 0");
+      if (o.n_values < 1 || o.first_value < 0 || o.first_value > f->n_values || o.n_values > f->n_values - o.first_value)
+        return fail(i, "value range outside values[]");
+      char dfa_why[160];
+      if (match_check_dfa(f->values + o.first_value, (int64_t)o.n_values, 0, dfa_why, sizeof dfa_why, nullptr) != 0) {
+        snprintf(why, why_len, "filter %d, op %d: %s", filter, i, dfa_why);
+        return (int)NP_ERR_INVALID_ARGUMENT;
+      }
       ++depth;
     } else if (o.op == NP_F_CONST) {
       if (o.arg < 0 || o.arg > 2) return fail(i, "unknown constant");

@@ -105,6 +105,7 @@ bool set_tuning(Tuning* t, const std::string& n, int value) {
   else if (n == "exact_rowmax") t->exact_rowmax = value != 0;
   else if (n == "scan_tiles") t->scan_tiles = clamp(value, 1, 8);
   else if (n == "scan_docs") t->scan_docs = std::max(value, 0);
+  else if (n == "match_lds") t->match_lds = clamp(value, 0, 40);
   else return false;
   return true;
 }
@@ -114,7 +115,7 @@ void read_tuning_env(Tuning* t) {
       {"NP_S4_MODE", "s4_mode"}, {"NP_S4_MINB", "s4_minb"}, {"NP_S4_NBX", "s4_nbx"}, {"NP_S4_SWZ", "s4_swz"},
       {"NP_S4_FILTER", "s4_filter"}, {"NP_S4_HOT", "s4_hot"}, {"NP_S4_PLANES", "s4_planes"}, {"NP_S4_PEXP", "s4_pexp"}, {"NP_S4_LPD", "s4_lpd"}, {"NP_S4_QM", "s4_qm"}, {"NP_S4_PNBX", "s4_pnbx"}, {"NP_S4_WARM", "s4_warm"}, {"NP_UB_NCUT", "ub_ncut"}, {"NP_S3_BISECT", "s3_bisect"}, {"NP_S3_GAIN", "s3_gain"}, {"NP_S3_GAIN_MULT", "s3_gain_mult"}, {"NP_S3_GAIN_DIRECT", "s3_gain_direct"}, {"NP_S4_HOT_AUTO", "s4_hot_auto"}, {"NP_S3_SLICES", "s3_slices"}, {"NP_UB_NT", "ub_nt"},
       {"NP_UB_STEAL", "ub_steal"}, {"NP_UB_NBX", "ub_nbx"}, {"NP_UB_DIRECT", "ub_direct"}, {"NP_UB_STATIC", "ub_static"}, {"NP_HOT_STATIC", "hot_static"}, {"NP_S6_XCD", "s6_xcd"}, {"NP_S6_TILES", "s6_tiles"}, {"NP_S6_LDS", "s6_lds"}, {"NP_GEMM_CPW", "gemm_cpw"}, {"NP_S1_SPLIT", "s1_split"},
-      {"NP_EXACT_ROWMAX", "exact_rowmax"}, {"NP_SCAN_TILES", "scan_tiles"}, {"NP_SCAN_DOCS", "scan_docs"}};
+      {"NP_EXACT_ROWMAX", "exact_rowmax"}, {"NP_SCAN_TILES", "scan_tiles"}, {"NP_SCAN_DOCS", "scan_docs"}, {"NP_MATCH_LDS", "match_lds"}};
   for (const auto& k : knobs) {
     const char* e = getenv(k[0]);
     if (e && *e) (void)set_tuning(t, k[1], atoi(e));
@@ -1723,6 +1724,12 @@ int np_hip_index_set_columns(np_index* ix, const np_column* cols, int32_t n_cols
     const size_t esz = dc.type == NP_COL_CODE ? 4 : 8;
     NP_TRY(dc.data.alloc((size_t)n * esz, &bytes));
     if (n > 0) NP_HIP(hipMemcpy(dc.data.get(), (const char*)cols[c].data + (size_t)b * esz, (size_t)n * esz, hipMemcpyHostToDevice));
+    if (dc.type == NP_COL_CODE)
+      for (int64_t d = 0; d < n; ++d) {
+        const int32_t code = ((const int32_t*)cols[c].data)[b + d];
+        dc.min_code = std::min(dc.min_code, code);
+        dc.max_code = std::max(dc.max_code, code);
+      }
     // validity: the caller's bytes, and an f64 NaN is NULL whatever they say; no array at all where nothing is NULL
     bits.assign((size_t)nvw, 0u);
     bool any_null = false;
@@ -1745,8 +1752,9 @@ int np_hip_index_set_columns(np_index* ix, const np_column* cols, int32_t n_cols
   }
   ix->columns = std::move(fresh);
   ix->d_coltab = std::move(d_tab);
-  ix->device_bytes = ix->device_bytes - ix->column_bytes + bytes;
+  ix->device_bytes = ix->device_bytes - ix->column_bytes - ix->coltext_bytes + bytes;   // the old columns' text goes with them
   ix->column_bytes = bytes;
+  ix->coltext_bytes = 0;
   return NP_OK;
 }
 

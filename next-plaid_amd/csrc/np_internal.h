@@ -241,6 +241,8 @@ struct Tuning {
   int exact_rowmax = 0;  // force the row-max form of the QC-reuse S6 kernel
   int scan_tiles = 8;    // np_hip_search_exact: 32-token query tiles a workgroup of the scan stages in LDS (whole queries are packed
                          // up to this many tiles; a longer query takes a group of its own)
+  int match_lds = 32;    // np_hip_text_match / NP_F_MATCH: KiB of LDS a DFA table may take; a larger table is read from global
+                         // memory through the caches (0 = every table; at most 40: tile + classes + table stay within 64 KiB)
   int scan_docs = 0;     // ... documents per pass over the index; 0 = as many as the key table's share of the workspace budget holds
 };
 
@@ -258,6 +260,12 @@ struct DeviceColumn {
   DevPtr<uint8_t> data;
   DevPtr<uint32_t> valid;
   bool has_valid = false;
+  int32_t min_code = 0, max_code = -1;   // CODE columns: the range of the handle's rows (np_hip_index_set_column_text checks it)
+  // the dictionary text of a CODE column (np_hip_index_set_column_text, np_match.hip): string s = text[text_off[s] .. text_off[s + 1])
+  DevPtr<uint8_t> text;                  // the bytes, padded with zeros to a multiple of 16 (tiles are staged with 16-byte loads)
+  DevPtr<int64_t> text_off;              // [n_strings + 1]
+  int64_t n_strings = 0, n_text_bytes = 0;
+  size_t text_acct = 0;                  // this text's share of device_bytes
 };
 
 // the keyword index of a handle (np_hip_index_set_text, np_text.hip): per-term posting lists, the positions behind them and
@@ -325,6 +333,7 @@ struct DeviceIndex {
   std::vector<DeviceColumn> columns;
   DevPtr<FilterCol> d_coltab;     // [columns.size()]
   size_t column_bytes = 0;        // the columns' share of device_bytes
+  size_t coltext_bytes = 0;       // ... and that of the columns' dictionary text
   DeviceText text;                // the keyword index (np_hip_index_set_text)
   size_t text_bytes = 0;          // ... and its share of device_bytes
   size_t device_bytes = 0;
@@ -423,6 +432,22 @@ struct FilterCsr {
 // the checks of the filtered entry points that need no device: the programs, the query map, the handle (columns, no shards)
 int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B,
                       bool for_search);
+// np_match.hip: the NP_F_MATCH leaves of a call's filters, whose programs filter_check_program has passed (columns, value ranges,
+// well-formed DFAs: the tables are checked there, once).  match_check_text refuses a leaf over a column without text;
+// match_collect lists the distinct (column, DFA) jobs; bit_words = what their bitmaps over codes take together, work_bytes
+// the images of the largest one.  match_run_jobs writes the bitmaps to d_bits (job j at d_bits + jobs[j].bit_word0), one DFA at a
+// time through d_work; enqueues on st and synchronises it.
+struct MatchJob {
+  int32_t column;
+  const int64_t* words;   // host, inside the filter's values
+  int64_t n_words, image_bytes;
+  int64_t bit_word0;      // the job's bitmap: u32 words at this offset, one bit per code
+};
+int match_check_text(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters);
+int match_collect(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters, std::vector<MatchJob>* jobs,
+                  std::vector<int64_t>* op_bit_word0, int64_t* bit_words, int64_t* work_bytes);
+int match_run_jobs(const DeviceIndex* ix, hipStream_t st, const std::vector<MatchJob>& jobs, uint32_t* d_bits, char* d_work);
+
 int filter_eval_resident(const DeviceIndex* ix, hipStream_t st, DevBuf& scratch, DevBuf& out, const np_filter* filters,
                          int32_t n_filters, const int32_t* h_query_filter, int B, FilterCsr* csr);
 

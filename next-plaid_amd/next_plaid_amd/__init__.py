@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
     pack_filters, fuse, fuse_rrf, fuse_relative_score,
 )
 from .filters import compile_filter, make_schema, CompiledFilter, FilterError, Schema  # noqa: F401
+from .regexes import compile_regex, compile_like, Dfa  # noqa: F401
 from .text import (  # noqa: F401
     TextIndexData, TextQuery, TextQueryError, compile_text_query, sanitize_fts5_query, sanitize_fts5_query_or,
     tokenize_identifiers,

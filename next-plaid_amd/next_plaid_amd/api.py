@@ -188,6 +188,19 @@ class np_filter(C.Structure):
     _fields_ = [("ops", C.POINTER(np_filter_op)), ("n_ops", C.c_int32), ("values", C.c_void_p), ("n_values", C.c_int64)]
 
 
+class np_dfa(C.Structure):
+    _fields_ = [("words", C.c_void_p), ("n_words", C.c_int64)]
+
+
+class np_match_report(C.Structure):
+    _fields_ = [("tile_bytes", C.c_int32), ("table_lds_bytes", C.c_int32), ("n_lds", C.c_int32), ("n_global", C.c_int32),
+                ("n_chunks", C.c_int32), ("reserved", C.c_int32), ("bytes_scanned", C.c_int64), ("ms", C.c_float),
+                ("reserved2", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class np_text_index(C.Structure):
     _fields_ = [("n_terms", C.c_int64), ("term_offsets", C.c_void_p), ("inst_doc", C.c_void_p), ("inst_pos", C.c_void_p),
                 ("n_rows", C.c_int64)]
@@ -223,6 +236,7 @@ EXPORTS = [
     "np_hip_index_set_columns", "np_hip_filter_eval", "np_hip_search_batch_filtered", "np_hip_search_exact_filtered",
     "np_hip_index_set_text", "np_hip_text_search", "np_hip_text_search_device", "np_hip_text_search_filtered",
     "np_hip_fuse", "np_hip_fuse_device", "np_hip_search_hybrid",
+    "np_hip_index_set_column_text", "np_hip_text_match",
 ]
 
 _lib = None
@@ -333,6 +347,8 @@ def lib():
                                                vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_search_exact_filtered.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(np_filter), i32, vp, vp, vp, vp,
                                                C.POINTER(np_stats)]
+    L.np_hip_index_set_column_text.argtypes = [vp, i32, vp, vp, i64]
+    L.np_hip_text_match.argtypes = [vp, i32, C.POINTER(np_dfa), i32, vp, C.POINTER(np_match_report)]
     L.np_hip_index_set_text.argtypes = [vp, C.POINTER(np_text_index)]
     L.np_hip_text_search.argtypes = [vp, C.POINTER(np_text_query), i32, i32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_text_search_device.argtypes = [vp, C.POINTER(np_text_query), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
@@ -931,6 +947,7 @@ class MmapIndex:
         self.last_stats: dict | None = None
         self.last_update: dict | None = None
         self.schema = None   # set_columns: the columns' names, types and dictionaries (filters.Schema)
+        self.last_match_report = None   # match_text / text_match_raw: np_match_report of the last call
         self.text = None     # set_text: the keyword index's arrays and vocabulary (text.TextIndexData)
 
     # -- constructors ---------------------------------------------------------------------------------
@@ -1087,20 +1104,75 @@ class MmapIndex:
         return int(live.workspace_bytes)
 
     # -- metadata columns and filters ---------------------------------------------------------------------
-    def set_columns(self, columns: dict):
+    def set_columns(self, columns: dict, text_on_device=()):
         """np_hip_index_set_columns: the handle's metadata columns, name -> one entry per document of the WHOLE index (a
         sharded handle keeps its slice).  Integer and bool arrays become I64, float arrays F64, string sequences
         dictionary codes (the dictionary, the distinct non-null strings sorted by their UTF-8 bytes, stays on this object in
         self.schema).  None entries, numpy masked entries and NaN are NULL.  Replaces any earlier set; {} drops them.  A
-        length other than num_documents() is a ShapeError.  Needs exclusive access to the handle, as reload() does."""
+        length other than num_documents() is a ShapeError.  Needs exclusive access to the handle, as reload() does.
+
+        text_on_device names text columns whose dictionary strings are kept in HBM too (np_hip_index_set_column_text): over
+        those, `col REGEXP ?`, `col NOT REGEXP ?` and `col LIKE ?` run on the device as byte DFAs (regexes.py) and
+        match_text() answers for the dictionary directly.  Their strings must be UTF-8."""
         from . import filters as F
-        sch = F.make_schema(dict(columns), self.num_documents())
+        sch = F.make_schema(dict(columns), self.num_documents(), text_on_device)
         cols = (np_column * max(len(sch), 1))()
         for c in sch.columns.values():
             cols[c.index] = np_column(c.type, 0, c.data.ctypes.data, None if c.valid is None else c.valid.ctypes.data)
         _check(lib().np_hip_index_set_columns(self._h, cols, len(sch)))
+        try:
+            for c in sch.columns.values():
+                if c.text_on_device and c.dictionary:   # (an empty dictionary has no text: the compiler emits no MATCH over it)
+                    text, off = c.text_arrays()
+                    _check(lib().np_hip_index_set_column_text(self._h, c.index, text.ctypes.data if text.size else None,
+                                                              _ptr(off), len(c.dictionary)))
+        except Exception:
+            # the columns without their text would disagree with the schema: the handle is left without columns
+            lib().np_hip_index_set_columns(self._h, None, 0)
+            self.schema = None
+            lib().np_hip_index_info(self._h, C.byref(self._info))
+            raise
         self.schema = sch if len(sch) else None
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def match_text(self, column: str, patterns, like: bool = False):
+        """np_hip_text_match: for every pattern (a REGEXP pattern of regexes.py's dialect, a LIKE pattern with like=True, or a
+        regexes.Dfa) a boolean array over the dictionary of `column` (set_columns(..., text_on_device=[column])): entry c =
+        the string with code c matches.  The report of the call is in self.last_match_report."""
+        from . import filters as F, regexes as R
+        if self.schema is None or column not in self.schema:
+            raise F.FilterError(f"unknown column '{column}'")
+        col = self.schema[column]
+        if not col.text_on_device:
+            raise F.FilterError(f"column '{column}' has no text on the device (set_columns(..., text_on_device=['{column}']))")
+        dfas = [p if isinstance(p, R.Dfa) else R.compile_like(p) if like else
+                R.compile_regex(p, col.first_non_ascii is None, first_non_ascii=col.first_non_ascii) for p in patterns]
+        n = len(col.dictionary)
+        if n == 0:
+            return [np.zeros(0, bool) for _ in dfas]
+        bits = self.text_match_raw(col.index, [d.pack() for d in dfas], n)
+        return [np.unpackbits(row.view(np.uint8), bitorder="little")[:n].astype(bool) for row in bits]
+
+    def set_column_text_raw(self, column_index: int, strings):
+        """np_hip_index_set_column_text as it is: byte strings by code for column `column_index` ([] drops the text)."""
+        strings = [bytes(s) for s in strings]
+        off = np.zeros(len(strings) + 1, np.int64)
+        np.cumsum([len(s) for s in strings], out=off[1:])
+        text = np.frombuffer(b"".join(strings), np.uint8)
+        _check(lib().np_hip_index_set_column_text(self._h, int(column_index), text.ctypes.data if text.size else None, _ptr(off),
+                                                  len(strings)))
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def text_match_raw(self, column_index: int, packed, n_strings: int):
+        """np_hip_text_match as it is: packed DFAs (u32 word arrays) -> u32 [n_dfas][ceil(n_strings / 32)]."""
+        words = [np.ascontiguousarray(w, np.uint32) for w in packed]
+        arr = (np_dfa * max(len(words), 1))(*[np_dfa(w.ctypes.data, w.size) for w in words])
+        bits = np.zeros((len(words), (int(n_strings) + 31) // 32), np.uint32)
+        rep = np_match_report()
+        _check(lib().np_hip_text_match(self._h, int(column_index), arr, len(words), _ptr(bits) if bits.size else None,
+                                       C.byref(rep)))
+        self.last_match_report = rep.as_dict()
+        return bits
 
     def _filters(self, filters, n_queries):
         from . import filters as F

@@ -3,7 +3,9 @@
 The reference validates a condition against an allowlist grammar (filtering.rs:571-583) and lets SQLite evaluate it over
 metadata.db.  Here the same grammar is compiled to the postfix program of include/nextplaid_hip.h (np_filter): strings never
 cross the ABI, text columns are dictionary-coded with the dictionary sorted by UTF-8 bytes (= SQLite's BINARY collation), and
-every text leaf is resolved against the dictionary here.  Pure host code: no device, no library."""
+every text leaf is resolved against the dictionary here -- except over a column whose dictionary text is kept on the device
+(text_on_device): there REGEXP and LIKE compile to a byte DFA (regexes.py) that the NP_F_MATCH leaf runs over the dictionary
+in HBM.  Pure host code: no device, no library."""
 from __future__ import annotations
 
 import bisect
@@ -15,17 +17,16 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .api import NextPlaidError, ShapeError
+from . import regexes
+from .regexes import FilterError   # one class for the WHERE compiler and the pattern compiler
 
 NP_COL_I64, NP_COL_F64, NP_COL_CODE = 0, 1, 2
 NP_F_CMP, NP_F_BETWEEN, NP_F_IN, NP_F_IS_NULL, NP_F_CONST, NP_F_AND, NP_F_OR, NP_F_NOT = range(8)
+NP_F_MATCH = 16
 CMP_ARG = {"=": 0, "!=": 1, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
 CONST_FALSE, CONST_TRUE, CONST_UNKNOWN = 0, 1, 2
 MAX_COLUMNS, MAX_OPS, MAX_DEPTH, MAX_VALUES = 64, 256, 32, 1 << 20
 _I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
-
-
-class FilterError(NextPlaidError):
-    """A condition the compiler refuses (the crate's Error::Filtering)."""
 
 
 @dataclass
@@ -36,6 +37,14 @@ class Column:
     data: np.ndarray                # i64 / f64 / i32 [num_documents]
     valid: np.ndarray | None        # u8 [num_documents], 0 = NULL; None = no NULLs
     dictionary: list | None = None  # CODE columns: the distinct strings as UTF-8 bytes, ascending
+    text_on_device: bool = False    # the dictionary's text is kept in HBM: REGEXP and LIKE compile to NP_F_MATCH
+    first_non_ascii: int | None = None   # ... and the code of its first string that is not ASCII (None: all are)
+
+    def text_arrays(self):
+        """(bytes u8, offsets i64 [n + 1]) of the dictionary, as np_hip_index_set_column_text takes them"""
+        off = np.zeros(len(self.dictionary) + 1, np.int64)
+        np.cumsum([len(s) for s in self.dictionary], out=off[1:])
+        return np.frombuffer(b"".join(self.dictionary), np.uint8), off
 
 
 @dataclass
@@ -119,8 +128,10 @@ def _column(name: str, index: int, values, n_docs: int | None) -> Column:
     return Column(name, index, typ, np.ascontiguousarray(data), None if valid.all() else np.ascontiguousarray(valid), dic)
 
 
-def make_schema(columns: dict, n_docs: int | None = None) -> Schema:
-    """dict name -> array  =>  Schema (typed arrays, validity, dictionaries).  Lengths are checked against n_docs."""
+def make_schema(columns: dict, n_docs: int | None = None, text_on_device=()) -> Schema:
+    """dict name -> array  =>  Schema (typed arrays, validity, dictionaries).  Lengths are checked against n_docs.  The
+    columns named in text_on_device must be text; their strings must be UTF-8 (FilterError naming the row otherwise), and
+    REGEXP and LIKE over them compile to NP_F_MATCH."""
     if len(columns) > MAX_COLUMNS:
         raise FilterError(f"{len(columns)} columns, at most {MAX_COLUMNS}")
     sch = Schema()
@@ -128,6 +139,21 @@ def make_schema(columns: dict, n_docs: int | None = None) -> Schema:
         if not isinstance(name, str) or not re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*", name):
             raise FilterError(f"column name {name!r} is not an identifier")
         sch.columns[name] = _column(name, i, values, n_docs)
+    for name in text_on_device:
+        if name not in sch:
+            raise FilterError(f"text_on_device names '{name}', which is not one of the columns")
+        col = sch[name]
+        if col.type != NP_COL_CODE:
+            raise FilterError(f"text_on_device: column '{name}' is not a text column")
+        for code, s in enumerate(col.dictionary):
+            try:
+                s.decode("utf-8")
+            except UnicodeDecodeError:
+                row = int(np.flatnonzero((col.data == code) & (col.valid if col.valid is not None else 1))[0])
+                raise FilterError(f"text_on_device: column '{name}', row {row}: the string is not UTF-8") from None
+            if col.first_non_ascii is None and not s.isascii():
+                col.first_non_ascii = code
+        col.text_on_device = True
     return sch
 
 
@@ -177,6 +203,9 @@ class _Compiler:
     # -- token helpers
     def peek(self):
         return self.toks[self.i] if self.i < len(self.toks) else ("end", "", len(self.cond))
+
+    def peek2(self):
+        return self.toks[self.i + 1] if self.i + 1 < len(self.toks) else ("end", "", len(self.cond))
 
     def take(self, kind=None, text=None):
         t = self.peek()
@@ -253,9 +282,19 @@ class _Compiler:
             self.take()
             v, ppos = self.param()
             self.like(col, v, ppos)
-        elif t[:2] == ("kw", "REGEXP"):
-            raise FilterError(f"REGEXP at position {t[2]} is not supported: the crate's REGEXP is a Rust-regex function that "
-                              f"Python's re does not reproduce")
+        elif t[:2] == ("kw", "REGEXP") or (t[:2] == ("kw", "NOT") and self.peek2()[:2] == ("kw", "REGEXP")):
+            neg = t[1] == "NOT"
+            if neg:
+                self.take()
+            t = self.take()
+            if not col.text_on_device:
+                raise FilterError(f"REGEXP at position {t[2]} is not supported over column '{name}': the crate's REGEXP is a "
+                                  f"Rust-regex function that runs on the device as a DFA over the column's text; keep that "
+                                  f"text on the device with set_columns(..., text_on_device=['{name}'])")
+            v, ppos = self.param()
+            self.regexp(col, v, ppos)
+            if neg:
+                self.push(NP_F_NOT)
         elif t[:2] == ("kw", "IS"):
             self.take()
             neg = self.peek()[:2] == ("kw", "NOT")
@@ -388,9 +427,26 @@ class _Compiler:
         kind, c = self.constant(col, v, pos)
         if kind == "null":
             return self.push(NP_F_CONST, -1, CONST_UNKNOWN)
+        if col.text_on_device:
+            return self.match(col, regexes.compile_like(c))
         rx = like_to_regex(c.decode("utf-8", "surrogateescape"))
         self.push(NP_F_IN, col.index, 0, [i for i, s in enumerate(col.dictionary)
                                            if rx.fullmatch(s.decode("utf-8", "surrogateescape"))])
+
+    def regexp(self, col, v, pos):
+        kind, c = self.constant(col, v, pos)
+        if kind == "null":
+            return self.push(NP_F_CONST, -1, CONST_UNKNOWN)
+        try:
+            pattern = c.decode("utf-8")
+        except UnicodeDecodeError:
+            raise FilterError(f"the REGEXP pattern at position {pos} is not UTF-8") from None
+        self.match(col, regexes.compile_regex(pattern, col.first_non_ascii is None, first_non_ascii=col.first_non_ascii))
+
+    def match(self, col, dfa):
+        if not col.dictionary:   # every cell is NULL (there is no text to set on the device): UNKNOWN everywhere
+            return self.push(NP_F_CONST, -1, CONST_UNKNOWN)
+        self.push(NP_F_MATCH, col.index, 0, dfa.pack().tolist())   # one packed word per value
 
     def run(self) -> CompiledFilter:
         self.expr()
@@ -413,7 +469,8 @@ _NUMERIC_EQ = re.compile(r"^(\d+)\s*=\s*(\d+)$")   # filtering.rs:584-594
 
 def compile_filter(condition: str, params=(), schema: Schema | None = None) -> CompiledFilter:
     """A WHERE condition of the crate's grammar (filtering.rs:571-583: OR, AND, NOT, parentheses; ident op ?, IS [NOT] NULL,
-    [NOT] BETWEEN ? AND ?, [NOT] IN (?, ...), LIKE ? on text, and the 1=1 / 0=1 idiom) as a program for np_hip_filter_eval,
+    [NOT] BETWEEN ? AND ?, [NOT] IN (?, ...), LIKE ? on text, [NOT] REGEXP ? (filtering.rs:500) over a text column kept on
+    the device, and the 1=1 / 0=1 idiom) as a program for np_hip_filter_eval,
     with SQLite's semantics.  ? placeholders are bound in order; None is SQL NULL.  Everything the grammar does not hold is a
     FilterError (a NextPlaidError) that names the spot -- before any library call: REGEXP, unknown columns, a parameter count
     that does not match, type mismatches (a string against a numeric column, a number against text, a float against an I64
