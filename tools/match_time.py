@@ -146,6 +146,10 @@ def main():
             hx.tune("match_lds", 32)
         con.close()
     hx.close()
+    kept = ""                     # sections below the table that other measurements added by hand stay
+    if os.path.exists(args.out):
+        old = open(args.out).read()
+        kept = old[old.index("\n## "):] if "\n## " in old else ""
     with open(args.out, "w") as f:
         f.write("# np_hip_text_match beside the host loop and SQLite's LIKE\n\n")
         f.write("Written by `tools/match_time.py` (its docstring says what each column is).  One DFA over the whole dictionary per call; "
@@ -157,6 +161,7 @@ def main():
             f.write(f"| {r['dictionary']} | {r['strings']} | {r['bytes'] / 1e6:.1f} | `{r['pattern']}` ({r['kind']}) | {r['states']} x {r['classes']} | "
                     f"{r['path']} | {r['matches']} | {r['device_ms']} ({r['device_ms_min']} - {r['device_ms_max']}) | {r['calls_per_sample']} | {r['device_GBps']} | {r['host_re_ms']} | "
                     f"{'-' if r['sqlite_like_ms'] is None else r['sqlite_like_ms']} | {'yes' if r['device_beats_host_re'] else 'NO'} |\n")
+        f.write(kept)
 
 
 if __name__ == "__main__":
