@@ -472,7 +472,8 @@ int np_hip_filter_eval(const np_index* index, const np_filter* filters, int32_t 
  * query_filter[i]: -1 = no filter; a filter that selects nothing empties that query's result and no other; one that selects
  * everything is a subset of all documents, not "no subset".  A query_filter entry < -1 or >= n_filters is
  * NP_ERR_INVALID_ARGUMENT, and so is a handle opened with shard_count > 1: the crate's probe scaling needs the global subset
- * length, a collective these calls do not run (np_hip_filter_eval does work on a shard).  stats are those of the underlying
+ * length, a collective these calls do not run (np_hip_filter_eval does work on a shard; np_hip_search_batch_sharded_filtered
+ * and its kin in the sharded section run it over a communicator).  stats are those of the underlying
  * call with the filter's time added to ms_total. */
 int np_hip_search_batch_filtered(const np_index* index, const float* queries, const int32_t* q_tok_offsets,
                                  int32_t B, int32_t dim, const np_search_params* params,
@@ -562,7 +563,9 @@ int np_hip_text_match(const np_index* index, int32_t column, const np_dfa* dfas,
  * position) order or repeated, a document outside [0, num_documents), a negative position, n_rows below the number of
  * distinct documents, NULL arrays with a positive count.  NP_ERR_OUT_OF_MEMORY leaves the previous index in place.
  * A handle opened with shard_count > 1 is refused (NP_ERR_INVALID_ARGUMENT), here and in every call below: nRow, the
- * average length and a phrase's hit count are global figures and would need a collective that these calls do not run. */
+ * average length and a phrase's hit count are global figures and need a collective that these calls do not run.  The calls
+ * that run it take a communicator: np_hip_index_set_text_shard, np_hip_text_search_sharded and np_hip_search_hybrid_sharded
+ * in the sharded section below. */
 typedef struct np_text_index {
   int64_t n_terms;
   const int64_t* term_offsets;   /* [n_terms + 1] */
@@ -785,6 +788,77 @@ int np_hip_search_batch_sharded_subsets(const np_index* index, np_comm* comm, co
                                         const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
                                         int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids,
                                         float* d_out_scores, int32_t* d_out_counts, void* stream);
+
+/* ---- keyword, filtered and hybrid search over document shards (np_text.hip, np_dist.hip) ------------------------
+ * The request features of the unsharded handle -- filters evaluated on the device, FTS5-exact BM25, the hybrid request --
+ * through the communicator above, with the unsharded results bit for bit on every rank.  All ranks pass the same
+ * queries, scopes and parameters in the same order; `stream` is required; a communicator serialises its calls.  The
+ * failure rules are those of np_hip_search_batch_sharded: arguments every rank sees alike are checked before the first
+ * collective; every exchange record ends in a status word; a rank whose local work fails (no keyword index or no columns
+ * on its handle, a workspace too small) takes part in every exchange with empty data and returns its own error; its peers
+ * return NP_ERR_SEARCH naming the shard (hosted transport with the host-side check) or get every count =
+ * NP_COUNT_ABANDONED and the rank from np_hip_comm_status (RCCL, NP_COMM_DEFERRED_STATUS); the communicator serves the
+ * next batch.  The RCCL transport of these calls is the same code around ncclAllGather; only the hosted transport and the
+ * one-rank communicator can run on a box with one GPU (RCCL refuses two ranks on a device).
+ *
+ * np_hip_index_set_text_shard: np_hip_index_set_text for a handle opened with shard_count > 1, by np_hip_index_set_columns'
+ * convention -- the arrays describe the WHOLE table (global document ids in [0, num_documents of the whole index)) and
+ * the handle keeps its slice: the posting lists, positions and document lengths of the documents of its shard in HBM,
+ * under shard-local ids, and on the host the whole table's n_rows, token count and every term's document frequency.
+ * Checks, error codes and the out-of-memory rule are np_hip_index_set_text's; on an unsharded handle it IS that call.
+ * (A form that hands every rank only its own instances would have to exchange those figures at set time: not offered.)
+ *
+ * np_hip_text_search_sharded: np_hip_text_search_device over the shards; the GLOBAL result -- ids, f32 scores, counts and
+ * padding equal to the unsharded call's, bit for bit -- is left in the output buffers of every rank.  Subset ids are
+ * global; a rank ignores those of other shards.
+ *   counts   a single-token phrase takes the global document frequency kept at set time.  Only a batch with a phrase of
+ *            several known tokens (the condition under which the unsharded call synchronises; it follows from the
+ *            queries alone) counts on the shard and exchanges one record per rank: nhit [counted phrases] u64 | n_rows
+ *            i64 | status.  The sums are taken on the host (the idf needs libm's log): every rank reads the same bytes
+ *            and computes the same idf bits, the unsharded ones.  Ranks that report different n_rows were handed
+ *            different tables: NP_ERR_INVALID_ARGUMENT on every rank
+ *   scoring  the unsharded kernels on the shard with the global idf and avgdl = (double)total_tokens / (double)n_rows
+ *   merge    one all-gather of keys [B * top_k] u64 (the f64 score's bits: two scores that differ in f64 can round to one
+ *            f32, and the order is f64 score descending, ties by ascending global id) | ids [B * top_k] i64 | counts [B]
+ *            i32 | status, then one block per query places every entry by binary searches in the other ranks' sorted
+ *            lists.  No limit on nranks * top_k.  A batch whose record would exceed 4 MiB per rank is cut into runs of
+ *            floor((4 MiB - 16) / (16 * top_k + 4)) queries, one exchange each: a function of B and top_k alone, never of
+ *            a rank's workspace (how a rank chunks its local scoring stays its own business)
+ * _filtered: the scope as filters, evaluated by every rank over its own column slice into a CSR that stays in HBM (the
+ * programs are compiled against the whole-index schema, so they are the same on every rank); query_filter is a host array.
+ *
+ * np_hip_search_batch_sharded_filtered: np_hip_search_batch_filtered over the shards.  The probe of a filtered query is
+ * scaled by the GLOBAL length of its filter's id list, so every filter's local length (n_filters i64) rides behind the
+ * eligible bitmaps in the all-gather np_hip_search_batch_sharded_subsets already runs, and the pass reads the sums.  The
+ * batched probe (centroid_batch_size < K) scales nothing and exchanges neither.  A filter that selects nothing on one
+ * shard but something elsewhere empties nothing; one that selects nothing anywhere empties its queries' results only.
+ *
+ * np_hip_search_hybrid_sharded: np_hip_search_hybrid over the shards, byte for byte: the sharded semantic pass and the
+ * sharded keyword pass with top_k = fetch_k and the fusion, on one stream; every rank holds both global lists after the
+ * merges, so every rank fuses.  The scope is the subsets' CSR on the device, or -- filters != NULL -- n_filters filters
+ * with the host array query_filter as the query map (then the CSR arguments are not read). */
+int np_hip_index_set_text_shard(np_index* index, const np_text_index* text);
+int np_hip_text_search_sharded(const np_index* index, np_comm* comm, const np_text_query* queries, int32_t B, int32_t top_k,
+                               const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                               const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                               int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+int np_hip_text_search_sharded_filtered(const np_index* index, np_comm* comm, const np_text_query* queries, int32_t B,
+                                        int32_t top_k, const np_filter* filters, int32_t n_filters,
+                                        const int32_t* query_filter /* host, [B] */,
+                                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+int np_hip_search_batch_sharded_filtered(const np_index* index, np_comm* comm, const float* d_queries,
+                                         const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                         int32_t dim, const np_search_params* params, const np_filter* filters,
+                                         int32_t n_filters, const int32_t* query_filter /* host, [B] */,
+                                         int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+int np_hip_search_hybrid_sharded(const np_index* index, np_comm* comm, const float* d_queries,
+                                 const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B, int32_t dim,
+                                 const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k,
+                                 float alpha, int32_t fusion,
+                                 const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                 const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                                 const np_filter* filters, int32_t n_filters, const int32_t* query_filter /* host, [B] */,
+                                 int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
 
 /* Host-only validation of an index directory: parses and checks every file exactly as np_hip_index_open
  * does (MmapIndex::load, index.rs:1026-1139; NPY headers mmap.rs:659-749; fast-plaid dtypes mmap.rs:1780-1808)

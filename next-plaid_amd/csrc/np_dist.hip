@@ -12,12 +12,17 @@
 //   gather 2  ncclAllGather of one packed record per rank: ids | keys | scores | counts
 //   merge     top-k by (exact score desc, approx rank) == the reference's final stable sort
 //
+// np_hip_search_batch_sharded_filtered runs the same pass on a CSR every rank evaluates from its own columns; the filters' local
+// lengths ride behind the eligible bitmaps and the probe scaling reads their sums.  The keyword and hybrid calls over the shards
+// are in np_text.hip, on this communicator.
+//
 // Every buffer is preallocated in the np_comm (grow-only), every step is enqueued on the caller's stream; the two
 // payload collectives are <= 0.5 MB per rank, i.e. latency-bound on xGMI.  librccl is dlopen'ed on first use
 // (librccl.so.1 resolves to the copy a host process already loaded, e.g. torch's), so the library has no link-time
 // dependency on it and single-GPU users never load it.  next_plaid_amd/dist.py keeps the torch.distributed
 // harness of the same protocol for the gloo CPU tests.
 #include "np_internal.h"
+#include "np_dist_plan.h"
 
 #include <dlfcn.h>
 #include <string.h>
@@ -82,19 +87,6 @@ static int nccl_check(int rc, const char* what) {
 }  // namespace np
 
 using namespace np;
-
-struct np_comm {
-  NcclComm comm = nullptr;
-  np_all_gather_host_fn host_fn = nullptr;   // hosted transport (np_hip_comm_create_hosted): the host moves the bytes
-  void* host_ctx = nullptr;
-  int host_flags = 0;
-  int rank = 0, nranks = 1, device = 0;
-  DevBuf keys_local, keys_all, cut, pack_local, pack_all, elig_local, elig_all, elig_global;
-  char* h_stage = nullptr;       // pinned staging of the hosted transport: [send | recv x nranks]
-  size_t h_stage_cap = 0;
-  uint64_t* h_status = nullptr;  // pinned, device-visible: the merge kernel leaves a failed rank's status word here
-  std::mutex mu;   // one protocol pass at a time per communicator (RCCL orders a communicator's collectives)
-};
 
 static int comm_common(const np_index* ix, int32_t rank, int32_t nranks, np_comm** out, const char* who) {
   if (!ix || !out || nranks < 1 || rank < 0 || rank >= nranks) {
@@ -165,7 +157,9 @@ int np_hip_comm_create(const np_index* ix, const void* id128, int32_t rank, int3
     DeviceGuard g(ix->device);
     NcclUniqueId id;
     memcpy(id.internal, id128, 128);
-    int rc = nccl_check(a->CommInitRank(&c->comm, nranks, id, rank), "ncclCommInitRank");
+    NcclComm nc = nullptr;
+    int rc = nccl_check(a->CommInitRank(&nc, nranks, id, rank), "ncclCommInitRank");
+    c->comm = nc;
     if (rc != NP_OK) {
       c->comm = nullptr;
       np_hip_comm_destroy(c);
@@ -201,11 +195,13 @@ void np_hip_comm_destroy(np_comm* c) {
   if (!c) return;
   {
     DeviceGuard g(c->device);
-    if (c->comm) (void)nccl_api()->CommDestroy(c->comm);
-    DevBuf* all[] = {&c->keys_local, &c->keys_all, &c->cut, &c->pack_local, &c->pack_all, &c->elig_local, &c->elig_all,
-                     &c->elig_global};
+    if (c->comm) (void)nccl_api()->CommDestroy((NcclComm)c->comm);
+    DevBuf* all[] = {&c->keys_local, &c->keys_all,    &c->cut,          &c->pack_local, &c->pack_all, &c->elig_local,
+                     &c->elig_all,   &c->elig_global, &c->filt,         &c->filt_csr,   &c->glen,     &c->tx_cnt_local,
+                     &c->tx_cnt_all, &c->tx_local,    &c->tx_all,       &c->tx_src,     &c->lists};
     for (DevBuf* b : all) b->release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->h_small) (void)hipHostFree(c->h_small);
     if (c->h_status) (void)hipHostFree(c->h_status);
   }
   delete c;
@@ -226,7 +222,7 @@ int np_hip_comm_info(np_comm* c, int32_t* transport, int32_t* nranks, int32_t* r
   if (rccl_ranks) {
     int n = 0;
     NcclApi* a = c->comm ? nccl_api() : nullptr;
-    if (a && a->CommCount && a->CommCount(c->comm, &n) != kNcclSuccess) n = 0;
+    if (a && a->CommCount && a->CommCount((NcclComm)c->comm, &n) != kNcclSuccess) n = 0;
     *rccl_ranks = n;
   }
   return NP_OK;
@@ -237,7 +233,7 @@ int np_hip_comm_info(np_comm* c, int32_t* transport, int32_t* nranks, int32_t* r
 // send -> recv[nranks][bytes].  RCCL: ncclAllGather on the caller's stream.  Hosted: the bytes go through pinned host
 // staging and the host's own transport (the stream is synchronised: the callback is host code).  A communicator with
 // neither is the one-rank case (a device copy).  *h_recv (hosted only) = the gathered bytes in host memory.
-static int all_gather(np_comm* c, const void* send, void* recv, size_t bytes, hipStream_t st, const char** h_recv = nullptr) {
+int np::comm_all_gather(np_comm* c, const void* send, void* recv, size_t bytes, hipStream_t st, const char** h_recv) {
   if (h_recv) *h_recv = nullptr;
   if (c->host_fn) {
     const size_t need = bytes * ((size_t)c->nranks + 1);
@@ -263,46 +259,56 @@ static int all_gather(np_comm* c, const void* send, void* recv, size_t bytes, hi
     NP_HIP(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, st));
     return NP_OK;
   }
-  return nccl_check(nccl_api()->AllGather(send, recv, bytes, kNcclUint8, c->comm, st), "ncclAllGather");
+  return nccl_check(nccl_api()->AllGather(send, recv, bytes, kNcclUint8, (NcclComm)c->comm, st), "ncclAllGather");
 }
 
-static uint64_t status_word(int rank, int rc) { return rc == NP_OK ? 0ull : ((uint64_t)(rank + 1) << 32) | (uint32_t)rc; }
-
-// first failed rank among the gathered records (host copy of the hosted transport), or 0
-static uint64_t gathered_failure(const char* h_all, size_t rec, size_t off_status, int G) {
-  for (int g = 0; g < G; ++g) {
-    uint64_t w;
-    memcpy(&w, h_all + (size_t)g * rec + off_status, 8);
-    if (w) return w;
+int np::comm_small_pin(np_comm* c, size_t bytes, char** out) {
+  if (bytes > c->h_small_cap) {
+    if (c->h_small) (void)hipHostFree(c->h_small);
+    c->h_small = nullptr;
+    c->h_small_cap = 0;
+    NP_HIP(hipHostMalloc((void**)&c->h_small, bytes + 4096, hipHostMallocDefault));
+    c->h_small_cap = bytes + 4096;
   }
-  return 0;
+  *out = c->h_small;
+  return NP_OK;
 }
 
-// The subsets of a sharded call: the single-subset form (off == NULL: d_ids[len], len < 0 = None) or the CSR form with one
-// subset per query.  Either way the shards' eligible bitmaps -- one row per subset -- cross the ranks in ONE all-gather.
-struct ShardSubsets {
-  const int64_t* d_ids;
-  int64_t len;
-  const int64_t *d_off, *h_off;
-  int64_t n;
-  const int32_t* d_qsub;
-  int64_t rows() const { return h_off ? n : (len > 0 ? 1 : 0); }   // eligible bitmaps to exchange
-};
+static uint64_t status_word(int rank, int rc) { return dist_status_word(rank, rc); }
+static uint64_t gathered_failure(const char* h_all, size_t rec, size_t off_status, int G) {
+  return dist_first_failure(h_all, rec, off_status, G);
+}
 
-static int search_batch_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
-                                const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
-                                const ShardSubsets& ss, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
-                                void* stream) {
+// glen[s] = the sum over the ranks of the local lengths that ride behind the eligible bitmaps of a filtered call's record
+__global__ void sum_lens_kernel(const char* __restrict__ all, int64_t rec_bytes, int64_t off, int G, int64_t n,
+                                int64_t* __restrict__ out) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  int64_t v = 0;
+  for (int g = 0; g < G; ++g) v += ((const int64_t*)(all + (int64_t)g * rec_bytes + off))[s];
+  out[s] = v;
+}
+
+// the arguments of a sharded semantic pass that every rank sees alike, before any lock or collective
+static int check_sharded_call(const np_index* ix, np_comm* c, int32_t B, const np_search_params* params, const int64_t* d_out_ids,
+                              const float* d_out_scores, const int32_t* d_out_counts, void* stream) {
   if (!ix || !c || !params || !stream) {
     set_error("search_batch_sharded: NULL index / communicator / params / stream (the collectives need the caller's stream)");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  if (B == 0) return NP_OK;
-  if (B < 0 || !d_out_counts || (params->top_k > 0 && (!d_out_ids || !d_out_scores))) {
+  if (B < 0 || (B > 0 && (!d_out_counts || (params->top_k > 0 && (!d_out_ids || !d_out_scores))))) {
     set_error("search_batch_sharded: invalid argument");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  std::lock_guard<std::mutex> lk(c->mu);
+  return NP_OK;
+}
+
+int np::search_batch_sharded_locked(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                    const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                    const ShardSubsets& ss, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                    void* stream, int rc0, const char* rc0_msg) {
+  NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
+  if (B == 0) return NP_OK;
   DeviceGuard g(ix->device);
   hipStream_t st = (hipStream_t)stream;
   const int G = c->nranks;
@@ -328,21 +334,27 @@ static int search_batch_sharded(const np_index* ix, np_comm* c, const float* d_q
   const size_t o_st2 = (o_cnt + (size_t)B * 4 + 15) / 16 * 16, rec2 = o_st2 + 16;
   const size_t o_st1 = (size_t)B * ns1 * 8, rec1 = o_st1 + 16;
   const int64_t words = np_hip_elig_words(ix);
+  // a filtered call's CSR holds this shard's part of every subset: the local lengths ride behind the bitmaps (K is padded to
+  // 64: the bitmaps end on an 8-byte boundary) and the probe scaling reads their sums.  The batched probe scales nothing.
+  const bool lens = need_elig && ss.h_local_lens != nullptr;
+  const DistEligRec er = dist_elig_record(S, words, lens);
+  const size_t b_elig = er.o_lens, rec0 = er.bytes;
   {
     if (need_elig) {
-      NP_TRY(c->elig_local.reserve((size_t)S * words * 4));
-      NP_TRY(c->elig_all.reserve((size_t)G * S * words * 4));
-      NP_TRY(c->elig_global.reserve((size_t)S * words * 4));
+      NP_TRY(c->elig_local.reserve(rec0));
+      NP_TRY(c->elig_all.reserve((size_t)G * rec0));
+      NP_TRY(c->elig_global.reserve(rec0));
     }
+    if (lens) NP_TRY(c->glen.reserve((size_t)S * 8));
     NP_TRY(c->keys_local.reserve(rec1));
     NP_TRY(c->keys_all.reserve((size_t)G * rec1));
     NP_TRY(c->cut.reserve((size_t)B * 8));
     NP_TRY(c->pack_local.reserve(rec2));
     NP_TRY(c->pack_all.reserve((size_t)G * rec2));
   }
-  const bool host_check = c->host_fn && !(c->host_flags & NP_COMM_DEFERRED_STATUS);
-  int rc = NP_OK;          // this rank's first local failure
-  std::string rc_msg;      // ... and its message (later calls overwrite the thread-local one)
+  const bool host_check = c->host_check();
+  int rc = rc0;            // this rank's first local failure
+  std::string rc_msg = rc0 != NP_OK && rc0_msg ? rc0_msg : "";   // ... and its message (later calls overwrite the thread-local one)
   auto local = [&](int r) {
     if (r != NP_OK && rc == NP_OK) {
       rc = r;
@@ -357,21 +369,36 @@ static int search_batch_sharded(const np_index* ix, np_comm* c, const float* d_q
 
   // ---- eligible centroids of the subset, OR-ed over the shards (dense path only: search.rs:350-364 vs :542-545)
   const uint32_t* elig = nullptr;
+  const int64_t* glen = nullptr;
   if (need_elig) {
-    if (!local(ss.h_off ? np_hip_subsets_eligible(ix, ss.d_ids, ss.d_off, ss.h_off, ss.n, c->elig_local.as<uint32_t>(), st)
+    if (rc != NP_OK ||
+        !local(ss.h_off ? np_hip_subsets_eligible(ix, ss.d_ids, ss.d_off, ss.h_off, ss.n, c->elig_local.as<uint32_t>(), st)
                         : np_hip_subset_eligible(ix, ss.d_ids, ss.len, c->elig_local.as<uint32_t>(), st)))
-      (void)hipMemsetAsync(c->elig_local.p, 0, (size_t)S * words * 4, st);
-    NP_TRY(all_gather(c, c->elig_local.p, c->elig_all.p, (size_t)S * words * 4, st));
-    local(np_hip_or_bitmaps(ix, c->elig_all.as<uint32_t>(), G, S * words, c->elig_global.as<uint32_t>(), st));
+      (void)hipMemsetAsync(c->elig_local.p, 0, b_elig, st);
+    if (lens) {   // (the pinned area is free: the filters' evaluation synchronised the stream after its previous use)
+      char* pin = nullptr;
+      NP_TRY(comm_small_pin(c, (size_t)S * 8, &pin));
+      if (rc == NP_OK) memcpy(pin, ss.h_local_lens, (size_t)S * 8); else memset(pin, 0, (size_t)S * 8);
+      NP_HIP(hipMemcpyAsync(c->elig_local.as<char>() + b_elig, pin, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    }
+    NP_TRY(comm_all_gather(c, c->elig_local.p, c->elig_all.p, rec0, st));
+    // (the OR runs over the whole record: what it leaves behind the bitmaps is not read)
+    local(np_hip_or_bitmaps(ix, c->elig_all.as<uint32_t>(), G, (int64_t)(rec0 / 4), c->elig_global.as<uint32_t>(), st));
     elig = c->elig_global.as<uint32_t>();
+    if (lens) {
+      sum_lens_kernel<<<(unsigned)((S + 255) / 256), 256, 0, st>>>(c->elig_all.as<char>(), (int64_t)rec0, (int64_t)b_elig, G, S,
+                                                                  c->glen.as<int64_t>());
+      NP_HIP(hipGetLastError());
+      glen = c->glen.as<int64_t>();
+    }
   }
 
   // ---- phase A + gather 1 + cut
   void* state = nullptr;
   if (rc == NP_OK)
-    local(ss.h_off ? np_hip_search_phase_a_subsets(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss.d_ids,
-                                                   ss.d_off, ss.h_off, ss.n, ss.d_qsub, elig, c->keys_local.as<uint64_t>(),
-                                                   st, &state)
+    local(ss.h_off ? search_phase_a_subsets_lens(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss.d_ids,
+                                                 ss.d_off, ss.h_off, ss.n, ss.d_qsub, glen, elig,
+                                                 c->keys_local.as<uint64_t>(), st, &state)
                    : np_hip_search_phase_a(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss.d_ids, ss.len,
                                            elig, c->keys_local.as<uint64_t>(), st, &state));
   struct End {
@@ -385,7 +412,7 @@ static int search_batch_sharded(const np_index* ix, np_comm* c, const float* d_q
   if (rc != NP_OK) NP_HIP(hipMemsetAsync(kl, 0, o_st1, st));   // no keys from this rank
   NP_TRY(set_status_word(ix, (uint64_t*)(kl + o_st1), status_word(c->rank, rc), st));
   const char* h_all = nullptr;
-  NP_TRY(all_gather(c, kl, c->keys_all.p, rec1, st, &h_all));
+  NP_TRY(comm_all_gather(c, kl, c->keys_all.p, rec1, st, &h_all));
   if (host_check && h_all) {
     const uint64_t w = gathered_failure(h_all, rec1, o_st1, G);
     if (w) {   // every rank reads the same bytes: all leave here, none enters gather 2
@@ -407,7 +434,7 @@ static int search_batch_sharded(const np_index* ix, np_comm* c, const float* d_q
   if (rc != NP_OK) NP_HIP(hipMemsetAsync(pl, 0, o_st2, st));   // counts 0
   NP_TRY(set_status_word(ix, (uint64_t*)(pl + o_st2), status_word(c->rank, rc), st));
   // ---- gather 2 + merge
-  NP_TRY(all_gather(c, pl, c->pack_all.p, rec2, st, &h_all));
+  NP_TRY(comm_all_gather(c, pl, c->pack_all.p, rec2, st, &h_all));
   NP_TRY(merge_packed_status(ix, c->pack_all.p, (int64_t)rec2, (int64_t)o_keys, (int64_t)o_sc, (int64_t)o_cnt,
                              (int64_t)o_st2,
                              /* a rank that reports the failure by its return code (its own, or -- hosted transport with the
@@ -433,9 +460,11 @@ extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const
                                            int64_t subset_len, int64_t* d_out_ids, float* d_out_scores,
                                            int32_t* d_out_counts, void* stream) {
   clear_error();
-  return search_batch_sharded(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
-                              ShardSubsets{d_subset, subset_len, nullptr, nullptr, 0, nullptr}, d_out_ids, d_out_scores,
-                              d_out_counts, stream);
+  NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
+  std::lock_guard<std::mutex> lk(c->mu);
+  return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
+                                     ShardSubsets{d_subset, subset_len, nullptr, nullptr, 0, nullptr}, d_out_ids, d_out_scores,
+                                     d_out_counts, stream);
 }
 
 // Arguments every rank sees alike are checked before the first collective; `query_subset` lives on the device and is not.
@@ -450,6 +479,51 @@ extern "C" int np_hip_search_batch_sharded_subsets(const np_index* ix, np_comm* 
   NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
   const ShardSubsets ss = n_subsets > 0 ? ShardSubsets{d_subset_ids, 0, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset}
                                         : ShardSubsets{nullptr, -1, nullptr, nullptr, 0, nullptr};
-  return search_batch_sharded(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss, d_out_ids, d_out_scores,
-                              d_out_counts, stream);
+  NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
+  std::lock_guard<std::mutex> lk(c->mu);
+  return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss, d_out_ids,
+                                     d_out_scores, d_out_counts, stream);
+}
+
+// The filters of a sharded call over this shard's columns, into the communicator's own buffers (a context of the handle stays
+// free for the pass).  Synchronises the stream.
+int np::shard_filters_eval(const np_index* ix, np_comm* c, hipStream_t st, const np_filter* filters, int32_t n_filters,
+                           const int32_t* query_filter, int B, FilterCsr* csr) {
+  NP_TRY(filter_check_call(ix, filters, n_filters, query_filter, B, 2));
+  return filter_eval_resident(ix, st, c->filt, c->filt_csr, filters, n_filters, query_filter, B, csr);
+}
+
+// The filters are evaluated over the shard's own columns; what crosses the ranks beyond np_hip_search_batch_sharded_subsets'
+// exchanges is every filter's local length, behind the eligible bitmaps.  A rank whose filters fail (no columns on its handle, a
+// program its schema refuses) takes part with empty data like any other local failure.
+extern "C" int np_hip_search_batch_sharded_filtered(const np_index* ix, np_comm* c, const float* d_queries,
+                                                    const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                                    int32_t dim, const np_search_params* params, const np_filter* filters,
+                                                    int32_t n_filters, const int32_t* query_filter, int64_t* d_out_ids,
+                                                    float* d_out_scores, int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
+  if (n_filters < 0 || (n_filters > 0 && (!filters || (B > 0 && !query_filter)))) {
+    set_error("search_batch_sharded_filtered: negative n_filters, or filters without programs or a query map");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B == 0) return NP_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  bool any = false;
+  for (int b = 0; n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
+  if (!any)   // as unsharded: a batch none of whose queries has a filter is a batch without subsets
+    return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
+                                       ShardSubsets{nullptr, -1, nullptr, nullptr, 0, nullptr}, d_out_ids, d_out_scores,
+                                       d_out_counts, stream);
+  DeviceGuard g(ix->device);
+  FilterCsr csr;
+  const int rc0 = shard_filters_eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B, &csr);
+  const std::string msg0 = rc0 != NP_OK ? np_hip_last_error() : "";
+  std::vector<int64_t> zero((size_t)n_filters + 1, 0), lens((size_t)n_filters, 0);
+  if (rc0 == NP_OK)
+    for (int32_t f = 0; f < n_filters; ++f) lens[(size_t)f] = csr.h_off[(size_t)f + 1] - csr.h_off[(size_t)f];
+  ShardSubsets ss{csr.d_ids, 0, csr.d_off, rc0 == NP_OK ? csr.h_off.data() : zero.data(), n_filters, csr.d_qsub};
+  ss.h_local_lens = lens.data();
+  return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss, d_out_ids,
+                                     d_out_scores, d_out_counts, stream, rc0, msg0.c_str());
 }

@@ -226,7 +226,7 @@ __global__ void __launch_bounds__(FILTER_TPB) filter_compact_kernel(FilterCompac
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B,
-                      bool for_search) {
+                      int for_search) {
   if (!ix) {
     set_error("Filter failed: NULL index");
     return NP_ERR_INVALID_ARGUMENT;
@@ -235,9 +235,10 @@ int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n
     set_error("Filter failed: %s", n_filters < 0 ? "negative n_filters" : "n_filters > 0 but filters is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  if (for_search && ix->opts.shard_count > 1) {
+  if (for_search == 1 && ix->opts.shard_count > 1) {
     set_error("Filter failed: a filtered search needs the whole index on the handle (opened with shard_count = %d): the "
-              "probe scaling needs the global subset length; np_hip_filter_eval works on a shard",
+              "probe scaling needs the global subset length; np_hip_filter_eval works on a shard, and the sharded entries "
+              "(np_hip_search_batch_sharded_filtered and its kin) exchange the lengths over a communicator",
               ix->opts.shard_count);
     return NP_ERR_INVALID_ARGUMENT;
   }

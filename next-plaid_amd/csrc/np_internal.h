@@ -279,7 +279,12 @@ struct DeviceText {
   DevPtr<int32_t> pos;          // [n_inst] positions, ascending inside a posting
   DevPtr<int32_t> doc_len;      // [n_docs] tokens of a document (its instances)
   std::vector<int64_t> h_post_off;   // host copy: a term's document frequency is the length of its list
+  // a shard's slice of the whole table (np_hip_index_set_text_shard): the arrays above hold the shard's documents under their
+  // shard-local ids; n_rows and total_tokens stay the WHOLE table's, and so does every term's document frequency
+  std::vector<int64_t> h_df;         // [n_terms] documents of the whole table that hold the term (slices only)
+  bool slice = false;
   bool present = false;
+  int64_t df(int64_t term) const { return slice ? h_df[(size_t)term] : h_post_off[(size_t)term + 1] - h_post_off[(size_t)term]; }
 };
 
 struct DeviceIndex {
@@ -429,9 +434,10 @@ struct FilterCsr {
   std::vector<int64_t> h_off;
   float ms = 0.f;
 };
-// the checks of the filtered entry points that need no device: the programs, the query map, the handle (columns, no shards)
+// the checks of the filtered entry points that need no device: the programs, the query map, the handle (columns, no shards).
+// for_search: 0 = np_hip_filter_eval, 1 = a search without a communicator (a sharded handle is refused), 2 = a sharded search
 int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B,
-                      bool for_search);
+                      int for_search);
 // np_match.hip: the NP_F_MATCH leaves of a call's filters, whose programs filter_check_program has passed (columns, value ranges,
 // well-formed DFAs: the tables are checked there, once).  match_check_text refuses a leaf over a column without text;
 // match_collect lists the distinct (column, DFA) jobs; bit_words = what their bitmaps over codes take together, work_bytes
@@ -459,6 +465,14 @@ int search_batch_in_use(const DeviceIndex* ix, ContextUse& use, const float* d_q
                         const int64_t* h_off, int64_t n_subsets, const int32_t* d_qsub, const int32_t* h_qsub,
                         int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts);
 
+// np_search.hip: np_hip_search_phase_a_subsets with the subsets' GLOBAL lengths on the device (d_global_lens[n_subsets], NULL =
+// the CSR's own): what the probe scaling reads when the CSR holds only a shard's part of every subset
+int search_phase_a_subsets_lens(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                int64_t n_subsets, const int32_t* d_query_subset, const int64_t* d_global_lens,
+                                const uint32_t* d_elig_global, uint64_t* d_sel_keys, void* stream, void** call_state);
+
 struct DeviceGuard {
   int prev = -1;
   bool ok = false;
@@ -474,3 +488,58 @@ struct DeviceGuard {
 }  // namespace np
 
 struct np_index : np::DeviceIndex {};
+
+// The communicator of the sharded entry points (np_dist.hip; the keyword and hybrid calls of np_text.hip use it too).  Opaque
+// to the ABI.  Every buffer is grow-only and belongs to the one protocol pass the mutex admits at a time.
+struct np_comm {
+  void* comm = nullptr;                      // ncclComm_t, or NULL
+  np_all_gather_host_fn host_fn = nullptr;   // hosted transport (np_hip_comm_create_hosted): the host moves the bytes
+  void* host_ctx = nullptr;
+  int host_flags = 0;
+  int rank = 0, nranks = 1, device = 0;
+  np::DevBuf keys_local, keys_all, cut, pack_local, pack_all, elig_local, elig_all, elig_global;
+  // filters of a sharded call: the evaluation's scratch, the shard's CSR, the subsets' global lengths
+  np::DevBuf filt, filt_csr, glen;
+  // keyword search: the counting record and the result record of a rank, the gathered ones, the whole batch's local lists where
+  // it takes several exchanges; hybrid: the two global lists
+  np::DevBuf tx_cnt_local, tx_cnt_all, tx_local, tx_all, tx_src, lists;
+  char* h_stage = nullptr;       // pinned staging of the hosted transport: [send | recv x nranks]
+  size_t h_stage_cap = 0;
+  char* h_small = nullptr;       // pinned: a call's small host-side figures on their way to or from the device
+  size_t h_small_cap = 0;
+  uint64_t* h_status = nullptr;  // pinned, device-visible: the merge kernel leaves a failed rank's status word here
+  std::mutex mu;   // one protocol pass at a time per communicator (RCCL orders a communicator's collectives)
+  bool host_check() const { return host_fn && !(host_flags & NP_COMM_DEFERRED_STATUS); }
+};
+
+namespace np {
+
+// np_dist.hip, for the calls that run more than one protocol pass under the communicator's mutex
+// send -> recv[nranks][bytes] on st; *h_recv (hosted transport only, else NULL) = the gathered bytes in host memory
+int comm_all_gather(np_comm* c, const void* send, void* recv, size_t bytes, hipStream_t st, const char** h_recv = nullptr);
+int comm_small_pin(np_comm* c, size_t bytes, char** out);   // the pinned area, grown; reuse only after the stream was synchronised
+
+// The subsets of a sharded call: the single-subset form (off == NULL: d_ids[len], len < 0 = None) or the CSR form with one
+// subset per query.  Either way the shards' eligible bitmaps -- one row per subset -- cross the ranks in ONE all-gather.
+// h_local_lens (filters): the CSR holds only this shard's part of every subset; the local lengths ride in that all-gather and
+// the probe scaling reads their sums.
+struct ShardSubsets {
+  const int64_t* d_ids;
+  int64_t len;
+  const int64_t *d_off, *h_off;
+  int64_t n;
+  const int32_t* d_qsub;
+  const int64_t* h_local_lens = nullptr;
+  int64_t rows() const { return h_off ? n : (len > 0 ? 1 : 0); }   // eligible bitmaps to exchange
+};
+// np_hip_search_batch_sharded's pass; the caller holds c->mu.  rc0 / rc0_msg: a local failure the caller already met (its
+// filters did not evaluate): the rank then takes part in every exchange with empty data and returns that error.
+int search_batch_sharded_locked(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                const ShardSubsets& ss, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                void* stream, int rc0 = NP_OK, const char* rc0_msg = nullptr);
+// a sharded call's filters evaluated over this shard's columns into the communicator's CSR (np_filter.hip's checks first)
+int shard_filters_eval(const np_index* ix, np_comm* c, hipStream_t st, const np_filter* filters, int32_t n_filters,
+                       const int32_t* query_filter, int B, FilterCsr* csr);
+
+}  // namespace np

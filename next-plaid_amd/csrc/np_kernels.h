@@ -927,11 +927,14 @@ __global__ void __launch_bounds__(256) masked_gmax_kernel(const float* __restric
 // subset its queries reference: the row of the FIRST query of the pass with that subset (qrow[b] <= b), so the tables
 // are bounded by the pass's B rows however many subsets the batch has, and queries that share a subset share its row.
 // off == NULL: the one subset [0, total); qsub == NULL: every query maps to subset 0 (the single-subset entry points).
+// glen (NULL = the CSR's own lengths): every subset's GLOBAL length, where the CSR holds only a document shard's part of it
+// (the sharded filtered search): the probe scaling reads it.
 struct SubsetsP {
   const int64_t* ids;
   const int64_t* off;
   const int32_t* qsub;
   int64_t n, total;
+  const int64_t* glen;
 };
 
 // the subset of query b, -1 = none (an entry outside [0, n) counts as none: the device-side entry points cannot check it)
@@ -1015,7 +1018,7 @@ __global__ void __launch_bounds__(256) subset_kernel(SubsetsP sp, int64_t id_lo,
 }
 
 // one block per row: n_elig + effective nprobe = clamp(nprobe * N / |subset|, nprobe, n_elig) from the subset's own length as
-// given (search.rs:370-382)
+// given (search.rs:370-382), or its global length where the CSR is a shard's part
 __global__ void __launch_bounds__(256) subset_nprobe_kernel(SubsetsP sp, const int32_t* __restrict__ qrow,
                                                             const uint32_t* __restrict__ elig, int64_t words,
                                                             int nprobe, int64_t n_total,
@@ -1024,7 +1027,7 @@ __global__ void __launch_bounds__(256) subset_nprobe_kernel(SubsetsP sp, const i
   const int b = blockIdx.x;
   if (qrow[b] != b) return;
   const int64_t s = subset_of(sp, b);
-  const int64_t subset_len = sp.off ? sp.off[s + 1] - sp.off[s] : sp.total;
+  const int64_t subset_len = sp.glen ? sp.glen[s] : (sp.off ? sp.off[s + 1] - sp.off[s] : sp.total);
   if (threadIdx.x == 0) s_cnt = 0;
   __syncthreads();
   int c = 0;

@@ -2102,6 +2102,19 @@ int np_hip_search_phase_a_subsets(const np_index* ix, const float* d_queries, co
                                   const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
                                   const uint32_t* d_elig_global, uint64_t* d_sel_keys, void* stream, void** call_state) {
   clear_error();
+  return np::search_phase_a_subsets_lens(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, d_subset_ids,
+                                         d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, nullptr, d_elig_global,
+                                         d_sel_keys, stream, call_state);
+}
+
+}  // extern "C"
+
+int np::search_phase_a_subsets_lens(const np_index* ix, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                    const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                    const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                    const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                                    const int64_t* d_global_lens, const uint32_t* d_elig_global, uint64_t* d_sel_keys,
+                                    void* stream, void** call_state) {
   if (!call_state) {
     set_error("Search failed: call_state is NULL");
     return NP_ERR_INVALID_ARGUMENT;
@@ -2110,9 +2123,12 @@ int np_hip_search_phase_a_subsets(const np_index* ix, const float* d_queries, co
   NP_TRY(validate(ix, B, dim, params));
   Subsets sub;
   NP_TRY(device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B, sub));
+  if (n_subsets > 0) sub.d.glen = d_global_lens;
   return search_phase_a(ix, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, sub, d_elig_global, d_sel_keys,
                         stream, call_state);
 }
+
+extern "C" {
 
 int np_hip_search_phase_b(const np_index* ix, void* call_state, const uint64_t* d_cut, int64_t* d_out_ids,
                           float* d_out_scores, uint64_t* d_out_keys, int32_t* d_out_counts, void* stream) {

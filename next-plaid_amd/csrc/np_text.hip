@@ -13,9 +13,14 @@
 //   text_merge_kernel  per query: the lists of a chunk's slices and the result of the chunks before it, merged through a
 //                      2048-entry window in LDS by the same total order
 //   fuse_kernel        per query: the two lists in LDS, the fused scores in f32 in the reference's order, one sort
+//   text_rank_merge_kernel  per query: the sorted lists of G document shards into the global top-k by binary searches
+// Over document shards (np_hip_index_set_text_shard, np_hip_text_search_sharded, np_hip_search_hybrid_sharded; np_dist_plan.h
+// has the records): a shard keeps its slice of the table and the table's global figures, the shards' phrase hit counts are summed
+// on the host before the idf is computed, and the shards' lists cross the ranks as f64 keys and global ids.
 // The f64 arithmetic of a score is SQLite's expression, operation for operation (this file is compiled with
 // -ffp-contract=off: no product and sum may be fused); the idf needs libm's log and is computed on the host.
 #include "np_internal.h"
+#include "np_dist_plan.h"
 #include "np_text_plan.h"
 
 #include <chrono>
@@ -280,6 +285,8 @@ struct TextMergeP {
   int64_t* out_ids;          // [chunk queries][top_k]
   float* out_scores;
   int32_t* out_counts;
+  unsigned long long* out_keys;   // [chunk queries][top_k] the f64 bits behind out_scores, or NULL (a shard's list needs them)
+  int64_t id_base;           // added to the ids that leave: a shard's documents carry shard-local ids up to here
 };
 
 __global__ void __launch_bounds__(TEXT_TPB) text_merge_kernel(TextMergeP p) {
@@ -311,13 +318,87 @@ __global__ void __launch_bounds__(TEXT_TPB) text_merge_kernel(TextMergeP p) {
     const bool in = j < fill;
     p.best_keys[at] = in ? s_k[j] : 0ull;
     p.best_ids[at] = in ? s_i[j] : 0;
-    p.out_ids[at] = in ? (int64_t)s_i[j] : 0;
+    p.out_ids[at] = in ? (int64_t)s_i[j] + p.id_base : 0;
     p.out_scores[at] = in ? (float)__longlong_as_double((long long)s_k[j]) : 0.f;
+    if (p.out_keys) p.out_keys[at] = in ? s_k[j] : 0ull;
   }
   if (tid == 0) {
     p.best_cnt[b] = fill;
     p.out_counts[b] = fill;
   }
+}
+
+// ---- the merge of the shards' lists (np_hip_text_search_sharded) ------------------------------------------------------------
+// One record per rank, rec_bytes apart (np_dist_plan.h, dist_text_record): keys [B][top_k] u64 at 0, global ids [B][top_k] i64 at
+// o_ids, counts [B] i32 at o_counts, the status word at o_status.
+struct TextRankMergeP {
+  const char* rec;
+  int64_t rec_bytes, o_ids, o_counts, o_status;
+  int G, top_k;
+  int64_t* out_ids;          // [B][top_k]
+  float* out_scores;
+  int32_t* out_counts;
+  unsigned long long* host_status;   // pinned host memory or NULL: where a failed rank's word is left (np_hip_comm_status)
+};
+
+// entries of a list of n, sorted by (key descending, id ascending), that precede (key, id) under that order
+__device__ __forceinline__ int text_rank_before(const unsigned long long* __restrict__ k, const int64_t* __restrict__ ids, int n,
+                                                unsigned long long key, int64_t id) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const unsigned long long km = k[mid];
+    if (km > key || (km == key && ids[mid] < id)) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// One block per query: G lists of at most top_k entries, each already sorted by the total order (f64 score descending, global id
+// ascending; the shards' ids are disjoint), into the global top-k.  An entry's place is its own index plus, for every other
+// rank's list, the number of entries that precede it there -- one binary search per list, straight from the gathered records:
+// no LDS, no atomics, no limit on G x top_k, the same bits from run to run.  A non-zero status word of any rank abandons every
+// query of the batch (count -1) as the semantic merge does.
+__global__ void __launch_bounds__(TEXT_TPB) text_rank_merge_kernel(TextRankMergeP p) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  unsigned long long failed = 0;
+  for (int g = 0; g < p.G && !failed; ++g) failed = *(const unsigned long long*)(p.rec + (int64_t)g * p.rec_bytes + p.o_status);
+  if (failed) {   // block-uniform: every thread read the same words
+    if (tid == 0) {
+      p.out_counts[b] = NP_COUNT_ABANDONED;
+      if (b == 0 && p.host_status) *p.host_status = failed;
+    }
+    return;
+  }
+  auto count_of = [&](int g) {
+    const int c = ((const int32_t*)(p.rec + (int64_t)g * p.rec_bytes + p.o_counts))[b];
+    return max(0, min(c, p.top_k));
+  };
+  int total = 0;
+  for (int g = 0; g < p.G; ++g) total += count_of(g);
+  const int64_t row = (int64_t)b * p.top_k;
+  for (int i = tid; i < p.G * p.top_k; i += TEXT_TPB) {
+    const int g = i / p.top_k, j = i - g * p.top_k;
+    if (j >= count_of(g)) continue;
+    const char* mine = p.rec + (int64_t)g * p.rec_bytes;
+    const unsigned long long key = ((const unsigned long long*)mine)[row + j];
+    const int64_t id = ((const int64_t*)(mine + p.o_ids))[row + j];
+    int at = j;
+    for (int g2 = 0; g2 < p.G && at < p.top_k; ++g2) {
+      if (g2 == g) continue;
+      const char* other = p.rec + (int64_t)g2 * p.rec_bytes;
+      at += text_rank_before((const unsigned long long*)other + row, (const int64_t*)(other + p.o_ids) + row, count_of(g2), key, id);
+    }
+    if (at < p.top_k) {
+      p.out_ids[row + at] = id;
+      p.out_scores[row + at] = (float)__longlong_as_double((long long)key);
+    }
+  }
+  const int fill = min(total, p.top_k);
+  for (int j = fill + tid; j < p.top_k; j += TEXT_TPB) {
+    p.out_ids[row + j] = 0;
+    p.out_scores[row + j] = 0.f;
+  }
+  if (tid == 0) p.out_counts[b] = fill;
 }
 
 // ---- fusion ------------------------------------------------------------------------------------------------------------
@@ -479,7 +560,8 @@ static int text_check_handle(const DeviceIndex* ix, bool need_text) {
   }
   if (ix->opts.shard_count > 1) {
     set_error("Text search failed: the keyword index needs the whole index on the handle (opened with shard_count = %d): nRow, "
-              "the average length and the hit counts are global figures",
+              "the average length and the hit counts are global figures; np_hip_index_set_text_shard and the sharded entries "
+              "(np_hip_text_search_sharded, np_hip_search_hybrid_sharded) exchange them over a communicator",
               ix->opts.shard_count);
     return NP_ERR_INVALID_ARGUMENT;
   }
@@ -539,7 +621,9 @@ struct TextProg {
     blob.assign(bytes, 0);
     int32_t *qphr = at32(o_qphr), *ptok = at32(o_ptok), *terms = at32(o_terms), *mode = at32(o_mode), *item = at32(o_item);
     int64_t ph = 0, tk = 0;
-    const std::vector<int64_t>& off = ix->text.h_post_off;
+    // (a rank of a sharded call that holds no keyword index still lays the programs out: the exchanges follow from them)
+    const DeviceText& tx = ix->text;
+    const std::vector<int64_t>& off = tx.h_post_off;   // the handle's own lists: the counting pass walks those
     for (int q = 0; q < B; ++q) {
       qphr[q] = (int32_t)ph;
       mode[q] = qs[q].mode;
@@ -554,11 +638,11 @@ struct TextProg {
         if (!known) {
           phr_hit[ph] = 0;
         } else if (te - tb == 1) {
-          phr_hit[ph] = off[qs[q].terms[tb] + 1] - off[qs[q].terms[tb]];
+          phr_hit[ph] = tx.present ? tx.df(qs[q].terms[tb]) : 0;   // (of the whole table, also on a shard)
         } else {
           phr_hit[ph] = -1;
           item[n_items++] = (int32_t)ph;
-          max_item_df = std::max(max_item_df, off[qs[q].terms[tb] + 1] - off[qs[q].terms[tb]]);
+          if (tx.present) max_item_df = std::max(max_item_df, off[qs[q].terms[tb] + 1] - off[qs[q].terms[tb]]);
         }
       }
     }
@@ -602,12 +686,76 @@ static int text_plan_for(const DeviceIndex* ix, int64_t user, const TextProg& pr
   return NP_OK;
 }
 
+// The counting exchange of a sharded keyword search (np_dist_plan.h, dist_count_record): this rank's nHit of the counted phrases,
+// its nRow and its status word go out, the sums over the healthy ranks come back.  A rank that cannot count (no keyword index,
+// no workspace) sends zeros and its status.  Synchronises the stream: the idf is computed on the host.
+struct TextCounts {
+  const np_index* ix;
+  np_comm* c;
+  hipStream_t st;
+  int64_t n_items;
+  int rc;                 // this rank's local status as it goes out
+  bool done = false;
+  uint64_t failed = 0;    // the first non-zero status word among the gathered records
+  int mismatch = 0, rank_a = 0, rank_b = 0;
+  int run(const unsigned long long* d_nhit, int64_t n_rows, unsigned long long* h_sums) {
+    const DistCountRec r = dist_count_record(n_items);
+    const int G = c->nranks;
+    NP_TRY(c->tx_cnt_local.reserve(r.bytes));
+    NP_TRY(c->tx_cnt_all.reserve((size_t)G * r.bytes));
+    char* loc = c->tx_cnt_local.as<char>();
+    if (n_items > 0) {
+      if (d_nhit && rc == NP_OK)
+        NP_HIP(hipMemcpyAsync(loc, d_nhit, (size_t)n_items * 8, hipMemcpyDeviceToDevice, st));
+      else
+        NP_HIP(hipMemsetAsync(loc, 0, (size_t)n_items * 8, st));
+    }
+    NP_TRY(set_status_word(ix, (uint64_t*)(loc + r.o_rows), (uint64_t)n_rows, st));
+    NP_TRY(set_status_word(ix, (uint64_t*)(loc + r.o_status), dist_status_word(c->rank, rc), st));
+    const char* h_all = nullptr;
+    NP_TRY(comm_all_gather(c, loc, c->tx_cnt_all.p, r.bytes, st, &h_all));
+    std::vector<char> own;
+    if (!h_all) {
+      own.resize((size_t)G * r.bytes);
+      NP_HIP(hipMemcpyAsync(own.data(), c->tx_cnt_all.p, own.size(), hipMemcpyDeviceToHost, st));
+      NP_HIP(hipStreamSynchronize(st));
+      h_all = own.data();
+    }
+    std::vector<uint64_t> sums((size_t)std::max<int64_t>(n_items, 1));
+    int64_t rows = 0;
+    mismatch = dist_sum_counts(h_all, r, G, sums.data(), &failed, &rows, &rank_a, &rank_b);
+    if (h_sums)
+      for (int64_t i = 0; i < n_items; ++i) h_sums[i] = (unsigned long long)sums[(size_t)i];
+    done = true;
+    return NP_OK;
+  }
+  // What every rank concludes alike from the gathered bytes: different tables are an argument error everywhere; with the
+  // host-side check a failed rank ends the batch here.  (Otherwise the failure travels on to the merge.)
+  bool all_leave() const { return done && (mismatch || (failed && c->host_check())); }
+  int verdict() const {
+    if (mismatch) {
+      set_error("Text search failed: shards %d and %d report different nRow: every rank must be handed the same table "
+                "(np_hip_index_set_text_shard)", rank_a, rank_b);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    if (failed && c->host_check()) {
+      set_error("Search failed: shard %d failed with status %d; the batch was abandoned on every rank", dist_status_rank(failed),
+                dist_status_code(failed));
+      return NP_ERR_SEARCH;
+    }
+    return NP_OK;
+  }
+};
+
 // The whole batch on device buffers.  `base`: the part of the arena this function carves (text_arena_bytes).  `pin`: pinned
 // host staging of prog.bytes for the programs (the caller synchronises the stream before it reuses it), or NULL: pageable
 // copies, and the stream is synchronised after the upload.  *visited (nullable): postings the scoring pass visited
 // (synchronises).
+// Sharded (counts != NULL): the hit counts of the counted phrases cross the ranks before the idf is computed, d_out_keys receives
+// the f64 bits of the scores and the ids leave as global ids.
 static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pin, const TextPlan& plan, TextProg& prog, int top_k,
-                    const TextSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited) {
+                    const TextSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited,
+                    unsigned long long* d_out_keys = nullptr, TextCounts* counts = nullptr) {
   hipStream_t st = use.stream;
   const DeviceText& tx = ix->text;
   const int B = prog.B;
@@ -650,8 +798,13 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
       text_hit_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0)), TEXT_TPB, 0, st>>>(hp);
     }
     NP_HIP(hipGetLastError());
-    NP_HIP(hipMemcpyAsync(h_nhit, d_prog + prog.o_nhit, (size_t)prog.n_items * 8, hipMemcpyDeviceToHost, st));
-    NP_HIP(hipStreamSynchronize(st));
+    if (counts) {   // the shards' counts summed on the host, the same bytes on every rank
+      NP_TRY(counts->run((const unsigned long long*)(d_prog + prog.o_nhit), tx.n_rows, h_nhit));
+      NP_TRY(counts->verdict());
+    } else {
+      NP_HIP(hipMemcpyAsync(h_nhit, d_prog + prog.o_nhit, (size_t)prog.n_items * 8, hipMemcpyDeviceToHost, st));
+      NP_HIP(hipStreamSynchronize(st));
+    }
     const int32_t* item = (const int32_t*)(prog.blob.data() + prog.o_item);
     for (int64_t i = 0; i < prog.n_items; ++i) prog.phr_hit[(size_t)item[i]] = (int64_t)h_nhit[i];
   }
@@ -722,6 +875,8 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
       mp.out_ids = d_out_ids + (int64_t)q0 * top_k;
       mp.out_scores = d_out_scores + (int64_t)q0 * top_k;
       mp.out_counts = d_out_counts + q0;
+      mp.out_keys = d_out_keys ? d_out_keys + (int64_t)q0 * top_k : nullptr;
+      mp.id_base = counts ? ix->doc_begin : 0;
       text_merge_kernel<<<(unsigned)Qn, TEXT_TPB, 0, st>>>(mp);
       NP_HIP(hipGetLastError());
     }
@@ -825,6 +980,13 @@ static int text_host(const np_index* ix, const np_text_query* queries, int32_t B
   return NP_OK;
 }
 
+// a hybrid result over document shards: a list that came back abandoned (count -1: a peer failed) abandons the fused result too
+__global__ void hybrid_abandon_kernel(const int32_t* __restrict__ sem_cnt, const int32_t* __restrict__ kw_cnt, int B,
+                                      int32_t* __restrict__ out_cnt) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B && (sem_cnt[b] < 0 || kw_cnt[b] < 0)) out_cnt[b] = NP_COUNT_ABANDONED;
+}
+
 static int fuse_launch(hipStream_t st, int mode, float alpha, int top_k, int B, const int64_t* sem_ids, const float* sem_sc,
                        const int32_t* sem_cnt, int sem_stride, const int64_t* kw_ids, const float* kw_sc, const int32_t* kw_cnt,
                        int kw_stride, int64_t* out_ids, float* out_sc, int32_t* out_cnt) {
@@ -843,20 +1005,192 @@ static int fuse_check(int mode, float alpha, int top_k, int B, int sem_stride, i
   return NP_OK;
 }
 
+
+// ---- the keyword search over document shards (np_hip_text_search_sharded) ---------------------------------------------------
+
+// the checks of a sharded keyword call that depend on its arguments alone: every rank passes or fails them alike, so a failure
+// returns before the first collective.  (The vocabulary check needs the handle's index: a rank that fails it fails locally.)
+static int text_check_sharded_args(const np_index* ix, np_comm* c, const np_text_query* queries, int B, int top_k, const void* out_ids,
+                                   const void* out_scores, const void* out_counts, void* stream) {
+  if (!ix || !c || !stream) {
+    set_error("Text search failed: NULL index / communicator / stream (the collectives need the caller's stream)");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  const char* why = "";
+  if (text_check_call(B, top_k, &why) != 0) {
+    set_error("Text search failed: %s (B=%d top_k=%d)", why, B, top_k);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B > 0 && !queries) {
+    set_error("Text search failed: NULL queries");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  char msg[240];
+  for (int q = 0; q < B; ++q)
+    if (text_check_query(&queries[q], q, (int64_t)1 << 31, msg, sizeof msg) != 0) {
+      set_error("Text search failed: %s", msg);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  if (B > 0 && (!out_ids || !out_scores || !out_counts)) {
+    set_error("Text search failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+// phrases of several tokens, all known: the ones the counting pass counts.  Follows from the queries alone, so every rank runs the
+// counting exchange or none does.
+static int64_t text_counted_phrases(const np_text_query* queries, int B) {
+  int64_t n = 0;
+  for (int q = 0; q < B; ++q)
+    for (int i = 0; i < queries[q].n_phrases; ++i) {
+      const int tb = queries[q].phrase_offsets[i], te = queries[q].phrase_offsets[i + 1];
+      bool known = true;
+      for (int k = tb; k < te; ++k) known = known && queries[q].terms[k] >= 0;
+      n += known && te - tb > 1 ? 1 : 0;
+    }
+  return n;
+}
+
+// The sharded keyword pass; the caller holds c->mu and has checked the arguments.  `sub`: the scope on the device (global ids;
+// ids of other shards are ignored, the rest rebased).  rc0 / msg0: a local failure the caller already met.
+//   [a batch with a counted phrase]  text_hit_kernel on the shard -> all-gather of nhit | nRow | status -> sums on the host
+//   local scoring with the global idf and average length -> the shard's top-k as f64 keys and global ids
+//   per exchange (np_dist_plan.h cuts the batch by B and top_k alone): all-gather of keys | ids | counts | status,
+//   text_rank_merge_kernel into the caller's buffers
+static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_query* queries, int B, int top_k, const TextSubsets& sub,
+                               int rc0, const char* msg0, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                               hipStream_t st) {
+  DeviceGuard g(ix->device);
+  const int G = c->nranks;
+  const bool host_check = c->host_check();
+  const int Bx = dist_text_exchange_queries(B, top_k), n_ex = dist_text_exchanges(B, top_k);
+  const DistTextRec rmax = dist_text_record(Bx, top_k);
+  const size_t n_all = (size_t)B * top_k;
+  // the communicator's own buffers: fatal before the first collective, as in the semantic pass
+  NP_TRY(c->tx_local.reserve(rmax.bytes));
+  NP_TRY(c->tx_all.reserve((size_t)G * rmax.bytes));
+  if (n_ex > 1) NP_TRY(c->tx_src.reserve(n_all * 16 + (size_t)B * 4));
+  char* loc = c->tx_local.as<char>();
+  // the shard's lists of the whole batch: straight in the record where one exchange carries the batch
+  unsigned long long* l_keys = (unsigned long long*)(n_ex > 1 ? c->tx_src.as<char>() : loc);
+  int64_t* l_ids = (int64_t*)(n_ex > 1 ? c->tx_src.as<char>() + n_all * 8 : loc + rmax.o_ids);
+  int32_t* l_cnt = (int32_t*)(n_ex > 1 ? c->tx_src.as<char>() + n_all * 16 : loc + rmax.o_counts);
+  int rc = rc0;
+  std::string rc_msg = rc0 != NP_OK && msg0 ? msg0 : "";
+  auto local = [&](int r) {
+    if (r != NP_OK && rc == NP_OK) {
+      rc = r;
+      rc_msg = np_hip_last_error();
+    }
+    return r == NP_OK;
+  };
+  auto finish = [&](int r) {
+    if (r != NP_OK && !rc_msg.empty()) set_error("%s", rc_msg.c_str());
+    return r;
+  };
+  auto peer_failed = [&](uint64_t w) {
+    set_error("Search failed: shard %d failed with status %d; the batch was abandoned on every rank", dist_status_rank(w),
+              dist_status_code(w));
+    return (int)NP_ERR_SEARCH;
+  };
+  if (rc == NP_OK && !ix->text.present) {
+    set_error("Text search failed: the handle has no keyword index (np_hip_index_set_text_shard)");
+    local(NP_ERR_INVALID_ARGUMENT);
+  }
+  char msg[240];
+  for (int q = 0; rc == NP_OK && q < B; ++q)
+    if (text_check_query(&queries[q], q, ix->text.n_terms, msg, sizeof msg) != 0) {
+      set_error("Text search failed: %s", msg);
+      local(NP_ERR_INVALID_ARGUMENT);
+    }
+  TextCounts counts{ix, c, st, text_counted_phrases(queries, B), rc};
+  {
+    TextProg prog;
+    TextPlan plan;
+    ContextUse use;
+    if (rc == NP_OK) {
+      prog.build(ix, queries, B);
+      local(text_plan_for(ix, 0, prog, B, top_k, sub.n > 0, &plan));
+    }
+    if (rc == NP_OK) local(use.begin(ix, st));
+    if (rc == NP_OK) local(use.arena().reserve(text_arena_bytes(ix, plan, prog, top_k, sub.n > 0)));
+    counts.rc = rc;
+    if (rc == NP_OK) {
+      // (the f32 scores of the local lists land in the caller's score buffer: the merge below overwrites it)
+      const int r = text_run(ix, use, use.arena().as<char>(), nullptr, plan, prog, top_k, sub, l_ids, d_out_scores, l_cnt, nullptr, l_keys,
+                             &counts);
+      if (r != NP_OK && counts.all_leave()) return r;   // every rank read the same bytes and leaves here
+      local(r);
+    }
+    if (counts.n_items > 0 && !counts.done) {   // this rank could not count: it still takes part, with zeros and its status
+      counts.rc = rc;
+      NP_TRY(counts.run(nullptr, 0, nullptr));
+      if (counts.all_leave()) return rc != NP_OK ? finish(rc) : counts.verdict();
+    }
+  }
+  for (int e = 0; e < n_ex; ++e) {
+    const int q0 = e * Bx, Bl = std::min(Bx, B - q0);
+    const DistTextRec r = dist_text_record(Bl, top_k);
+    const size_t n = (size_t)Bl * top_k;
+    if (rc != NP_OK) {
+      NP_HIP(hipMemsetAsync(loc, 0, r.o_status, st));   // counts 0
+    } else if (n_ex > 1) {
+      NP_HIP(hipMemcpyAsync(loc, l_keys + (size_t)q0 * top_k, n * 8, hipMemcpyDeviceToDevice, st));
+      NP_HIP(hipMemcpyAsync(loc + r.o_ids, l_ids + (size_t)q0 * top_k, n * 8, hipMemcpyDeviceToDevice, st));
+      NP_HIP(hipMemcpyAsync(loc + r.o_counts, l_cnt + q0, (size_t)Bl * 4, hipMemcpyDeviceToDevice, st));
+    }
+    NP_TRY(set_status_word(ix, (uint64_t*)(loc + r.o_status), dist_status_word(c->rank, rc), st));
+    const char* h_all = nullptr;
+    NP_TRY(comm_all_gather(c, loc, c->tx_all.p, r.bytes, st, &h_all));
+    // (a rank that reports the failure by its return code must not also leave the word behind for the next healthy batch)
+    const TextRankMergeP mp{c->tx_all.as<char>(), (int64_t)r.bytes, (int64_t)r.o_ids, (int64_t)r.o_counts, (int64_t)r.o_status, G, top_k,
+                            d_out_ids + (size_t)q0 * top_k, d_out_scores + (size_t)q0 * top_k, d_out_counts + q0,
+                            (rc == NP_OK && !host_check) ? (unsigned long long*)c->h_status : nullptr};
+    text_rank_merge_kernel<<<(unsigned)Bl, TEXT_TPB, 0, st>>>(mp);
+    NP_HIP(hipGetLastError());
+    if (host_check && h_all) {
+      const uint64_t w = dist_first_failure(h_all, r.bytes, r.o_status, G);
+      if (w) return rc != NP_OK ? finish(rc) : peer_failed(w);
+    }
+  }
+  return finish(rc);
+}
+
+// the device CSR of a sharded call as the keyword pass takes it
+static TextSubsets text_device_subsets(const int64_t* d_ids, const int64_t* d_off, const int64_t* h_off, int64_t n_subsets,
+                                       const int32_t* d_qsub, const int32_t* h_qsub) {
+  TextSubsets sub;
+  if (n_subsets > 0) {
+    sub.d_ids = d_ids;
+    sub.d_off = d_off;
+    sub.d_qsub = d_qsub;
+    sub.n = n_subsets;
+    sub.total = h_off[n_subsets];
+    if (h_qsub) {
+      sub.h_off = h_off;
+      sub.h_qsub = h_qsub;
+    }
+  }
+  return sub;
+}
+
 }  // namespace np
 
 using namespace np;
 
 extern "C" {
 
-int np_hip_index_set_text(np_index* ix, const np_text_index* text) {
-  clear_error();
-  NP_TRY(text_check_handle(ix, false));
+// np_hip_index_set_text, and np_hip_index_set_text_shard on a sharded handle (slice): the arrays describe the whole table either
+// way; a slice keeps the postings, positions and lengths of its own documents [doc_begin, doc_begin + n_docs) under shard-local
+// ids, and the whole table's nRow, token count and document frequencies on the host.
+static int set_text_impl(np_index* ix, const np_text_index* text, bool slice) {
   DeviceGuard g(ix->device);
   DeviceText fresh;
   size_t bytes = 0;
   char why[240];
-  if (text && text_check_index(text, ix->n_docs, why, sizeof why) != 0) {
+  const int64_t n_table = slice ? ix->N_total : ix->n_docs;   // documents the table may name
+  if (text && text_check_index(text, n_table, why, sizeof why) != 0) {
     set_error("set_text: %s", why);
     return NP_ERR_INVALID_ARGUMENT;
   }
@@ -864,48 +1198,77 @@ int np_hip_index_set_text(np_index* ix, const np_text_index* text) {
   if (text && !((text->n_terms == 0 || text->term_offsets[text->n_terms] == 0) && text->n_rows == 0)) {
     // postings and document lengths, derived on the host; the new index is built beside the old one and swapped in whole
     const int64_t n_terms = text->n_terms, n_inst = n_terms > 0 ? text->term_offsets[n_terms] : 0;
-    std::vector<int64_t> post_off((size_t)n_terms + 1, 0), post_first;
-    std::vector<int32_t> post_doc, post_tf, doc_len((size_t)std::max<int64_t>(ix->n_docs, 1), 0);
+    const int64_t d_lo = slice ? ix->doc_begin : 0, d_hi = d_lo + ix->n_docs;
+    std::vector<int64_t> post_off((size_t)n_terms + 1, 0), post_first, df;
+    std::vector<int32_t> post_doc, post_tf, doc_len((size_t)std::max<int64_t>(ix->n_docs, 1), 0), own_pos;
+    if (slice) df.assign((size_t)n_terms, 0);
     for (int64_t k = 0; k < n_terms; ++k) {
+      int64_t prev = -1;
+      bool first = true;
       for (int64_t i = text->term_offsets[k]; i < text->term_offsets[k + 1]; ++i) {
-        const int32_t d = (int32_t)text->inst_doc[i];
-        if (i == text->term_offsets[k] || post_doc.back() != d) {
+        const int64_t gd = text->inst_doc[i];
+        if (slice && gd != prev) ++df[(size_t)k];
+        prev = gd;
+        if (gd < d_lo || gd >= d_hi) continue;
+        const int32_t d = (int32_t)(gd - d_lo);
+        if (first || post_doc.back() != d) {
           post_doc.push_back(d);
           post_tf.push_back(0);
-          post_first.push_back(i);
+          post_first.push_back(slice ? (int64_t)own_pos.size() : i);
+          first = false;
         }
+        if (slice) own_pos.push_back(text->inst_pos[i]);
         ++post_tf.back();
         ++doc_len[(size_t)d];
       }
       post_off[(size_t)k + 1] = (int64_t)post_doc.size();
     }
     const size_t n_post = post_doc.size();
+    const int64_t n_own = slice ? (int64_t)own_pos.size() : n_inst;
+    const int32_t* pos_src = slice ? own_pos.data() : text->inst_pos;
     NP_TRY(fresh.post_off.alloc((size_t)n_terms + 1, &bytes));
     NP_TRY(fresh.post_doc.alloc(n_post, &bytes));
     NP_TRY(fresh.post_tf.alloc(n_post, &bytes));
     NP_TRY(fresh.post_first.alloc(n_post, &bytes));
-    NP_TRY(fresh.pos.alloc((size_t)n_inst, &bytes));
+    NP_TRY(fresh.pos.alloc((size_t)n_own, &bytes));
     NP_TRY(fresh.doc_len.alloc(doc_len.size(), &bytes));
     NP_HIP(hipMemcpy(fresh.post_off.get(), post_off.data(), post_off.size() * 8, hipMemcpyHostToDevice));
     if (n_post > 0) {
       NP_HIP(hipMemcpy(fresh.post_doc.get(), post_doc.data(), n_post * 4, hipMemcpyHostToDevice));
       NP_HIP(hipMemcpy(fresh.post_tf.get(), post_tf.data(), n_post * 4, hipMemcpyHostToDevice));
       NP_HIP(hipMemcpy(fresh.post_first.get(), post_first.data(), n_post * 8, hipMemcpyHostToDevice));
-      NP_HIP(hipMemcpy(fresh.pos.get(), text->inst_pos, (size_t)n_inst * 4, hipMemcpyHostToDevice));
+      NP_HIP(hipMemcpy(fresh.pos.get(), pos_src, (size_t)n_own * 4, hipMemcpyHostToDevice));
     }
     NP_HIP(hipMemcpy(fresh.doc_len.get(), doc_len.data(), doc_len.size() * 4, hipMemcpyHostToDevice));
     fresh.n_terms = n_terms;
     fresh.n_post = (int64_t)n_post;
-    fresh.n_inst = n_inst;
+    fresh.n_inst = n_own;
     fresh.n_rows = text->n_rows;
-    fresh.total_tokens = n_inst;
+    fresh.total_tokens = n_inst;   // (the whole table's, also on a slice)
     fresh.h_post_off = std::move(post_off);
+    fresh.h_df = std::move(df);
+    fresh.slice = slice;
     fresh.present = true;
   }
   ix->text = std::move(fresh);
   ix->device_bytes = ix->device_bytes - ix->text_bytes + bytes;
   ix->text_bytes = bytes;
   return NP_OK;
+}
+
+int np_hip_index_set_text(np_index* ix, const np_text_index* text) {
+  clear_error();
+  NP_TRY(text_check_handle(ix, false));
+  return set_text_impl(ix, text, false);
+}
+
+int np_hip_index_set_text_shard(np_index* ix, const np_text_index* text) {
+  clear_error();
+  if (!ix) {
+    set_error("Text search failed: NULL index");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return set_text_impl(ix, text, ix->opts.shard_count > 1);
 }
 
 int np_hip_text_search(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k, const int64_t* subset_ids,
@@ -1176,6 +1539,137 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
     stats->n_queries = B;
     stats->n_ivf_ids = visited;
   }
+  return NP_OK;
+}
+
+int np_hip_text_search_sharded(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
+                               const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                               int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                               int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(text_check_sharded_args(ix, c, queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
+  NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
+  if (B == 0) return NP_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  return text_sharded_locked(ix, c, queries, B, top_k,
+                             text_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, nullptr),
+                             NP_OK, nullptr, d_out_ids, d_out_scores, d_out_counts, (hipStream_t)stream);
+}
+
+// the arguments of a sharded call's filters that need no handle
+static int check_sharded_filters(const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B) {
+  if (n_filters < 0 || (n_filters > 0 && (!filters || (B > 0 && !query_filter)))) {
+    set_error("Filter failed: negative n_filters, or filters without programs or a query map");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+int np_hip_text_search_sharded_filtered(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
+                                        const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream) {
+  clear_error();
+  NP_TRY(text_check_sharded_args(ix, c, queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
+  NP_TRY(check_sharded_filters(filters, n_filters, query_filter, B));
+  if (B == 0) return NP_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(ix->device);
+  bool any = false;
+  for (int b = 0; n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
+  FilterCsr csr;   // (nHit never looks at the scope: the keyword pass needs no global lengths)
+  const int rc0 = any ? shard_filters_eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B, &csr) : NP_OK;
+  const std::string msg0 = rc0 != NP_OK ? np_hip_last_error() : "";
+  const TextSubsets sub = any && rc0 == NP_OK
+                              ? text_device_subsets(csr.d_ids, csr.d_off, csr.h_off.data(), n_filters, csr.d_qsub, query_filter)
+                              : TextSubsets{};
+  return text_sharded_locked(ix, c, queries, B, top_k, sub, rc0, msg0.c_str(), d_out_ids, d_out_scores, d_out_counts,
+                             (hipStream_t)stream);
+}
+
+int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                 const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                 const np_text_query* text_queries, int32_t fetch_k, float alpha, int32_t fusion,
+                                 const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                 int64_t n_subsets, const int32_t* d_query_subset, const np_filter* filters, int32_t n_filters,
+                                 const int32_t* query_filter, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                 void* stream) {
+  clear_error();
+  if (!params) {
+    set_error("Search failed: NULL index or params");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  // arguments every rank sees alike: before the lock and the first collective
+  NP_TRY(text_check_sharded_args(ix, c, text_queries, B, fetch_k, d_out_ids, d_out_scores, d_out_counts, stream));
+  NP_TRY(fuse_check(fusion, alpha, params->top_k, B, fetch_k, fetch_k));
+  if (filters)
+    NP_TRY(check_sharded_filters(filters, n_filters, query_filter, B));
+  else
+    NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
+  if (B > 0 && (!d_queries || !d_q_tok_offsets || !h_q_tok_offsets)) {
+    set_error("Search failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B == 0) return NP_OK;
+  np_search_params sem = *params;
+  sem.top_k = fetch_k;
+  const int top_k = params->top_k;
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(ix->device);
+  // the two global lists, [B][fetch_k] each, stay in the communicator
+  const size_t l_ids = up256((size_t)B * fetch_k * 8), l_sc = up256((size_t)B * fetch_k * 4), b_cnt = up256((size_t)B * 4);
+  NP_TRY(c->lists.reserve(2 * (l_ids + l_sc + b_cnt)));
+  char* at = c->lists.as<char>();
+  auto take = [&](size_t bytes) {
+    char* r = at;
+    at += bytes;
+    return r;
+  };
+  int64_t* s_ids = (int64_t*)take(l_ids);
+  float* s_sc = (float*)take(l_sc);
+  int32_t* s_cnt = (int32_t*)take(b_cnt);
+  int64_t* k_ids = (int64_t*)take(l_ids);
+  float* k_sc = (float*)take(l_sc);
+  int32_t* k_cnt = (int32_t*)take(b_cnt);
+  // the scope: the caller's CSR, or the filters over this shard's columns with their local lengths for the probe scaling
+  bool any = false;
+  for (int b = 0; filters && n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
+  FilterCsr csr;
+  int rc0 = NP_OK;
+  std::string msg0;
+  std::vector<int64_t> zero, lens;
+  ShardSubsets ss{nullptr, -1, nullptr, nullptr, 0, nullptr};
+  TextSubsets sub;
+  if (any) {
+    rc0 = shard_filters_eval(ix, c, st, filters, n_filters, query_filter, B, &csr);
+    if (rc0 != NP_OK) msg0 = np_hip_last_error();
+    zero.assign((size_t)n_filters + 1, 0);
+    lens.assign((size_t)n_filters, 0);
+    if (rc0 == NP_OK) {
+      for (int32_t f = 0; f < n_filters; ++f) lens[(size_t)f] = csr.h_off[(size_t)f + 1] - csr.h_off[(size_t)f];
+      sub = text_device_subsets(csr.d_ids, csr.d_off, csr.h_off.data(), n_filters, csr.d_qsub, query_filter);
+    }
+    ss = ShardSubsets{csr.d_ids, 0, csr.d_off, rc0 == NP_OK ? csr.h_off.data() : zero.data(), n_filters, csr.d_qsub};
+    ss.h_local_lens = lens.data();
+  } else if (!filters && n_subsets > 0) {
+    ss = ShardSubsets{d_subset_ids, 0, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset};
+    sub = text_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, nullptr);
+  }
+  // With the host-side check a failed semantic pass has ended on every rank at the same exchange (each read the same status
+  // words): all leave.  Otherwise the failing rank has returned its own error after taking part in every exchange, while its peers
+  // carry on with an abandoned list: it still owes them the exchanges of the keyword pass, with empty data and its status.
+  const int rc_sem = search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, &sem, ss, s_ids, s_sc,
+                                                 s_cnt, stream, rc0, msg0.c_str());
+  const std::string msg_sem = rc_sem != NP_OK ? np_hip_last_error() : "";
+  if (rc_sem != NP_OK && c->host_check()) return rc_sem;
+  const int rc_kw = text_sharded_locked(ix, c, text_queries, B, fetch_k, sub, rc_sem, msg_sem.c_str(), k_ids, k_sc, k_cnt, st);
+  if (rc_kw != NP_OK) return rc_kw;
+  // every rank holds both global lists: every rank fuses.  (An abandoned list carries count -1: the fusion clamps it to an empty
+  // list, and the count that leaves is the abandoned one.)
+  NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, s_ids, s_sc, s_cnt, fetch_k, k_ids, k_sc, k_cnt, fetch_k, d_out_ids, d_out_scores,
+                     d_out_counts));
+  hybrid_abandon_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(s_cnt, k_cnt, B, d_out_counts);
+  NP_HIP(hipGetLastError());
   return NP_OK;
 }
 

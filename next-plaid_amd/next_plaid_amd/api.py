@@ -237,6 +237,8 @@ EXPORTS = [
     "np_hip_index_set_text", "np_hip_text_search", "np_hip_text_search_device", "np_hip_text_search_filtered",
     "np_hip_fuse", "np_hip_fuse_device", "np_hip_search_hybrid",
     "np_hip_index_set_column_text", "np_hip_text_match",
+    "np_hip_index_set_text_shard", "np_hip_text_search_sharded", "np_hip_text_search_sharded_filtered",
+    "np_hip_search_batch_sharded_filtered", "np_hip_search_hybrid_sharded",
 ]
 
 _lib = None
@@ -359,6 +361,15 @@ def lib():
     L.np_hip_search_hybrid.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_text_query), i32,
                                        C.c_float, i32, vp, vp, i64, vp, C.POINTER(np_filter), i32, vp, vp, vp,
                                        C.POINTER(np_stats)]
+    L.np_hip_index_set_text_shard.argtypes = [vp, C.POINTER(np_text_index)]
+    L.np_hip_text_search_sharded.argtypes = [vp, vp, C.POINTER(np_text_query), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_text_search_sharded_filtered.argtypes = [vp, vp, C.POINTER(np_text_query), i32, i32, C.POINTER(np_filter), i32, vp,
+                                                      vp, vp, vp, vp]
+    L.np_hip_search_batch_sharded_filtered.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params),
+                                                       C.POINTER(np_filter), i32, vp, vp, vp, vp, vp]
+    L.np_hip_search_hybrid_sharded.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params),
+                                               C.POINTER(np_text_query), i32, C.c_float, i32, vp, vp, vp, i64, vp,
+                                               C.POINTER(np_filter), i32, vp, vp, vp, vp, vp]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -1251,19 +1262,20 @@ class MmapIndex:
         return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
 
     # -- keyword and hybrid search ------------------------------------------------------------------------
-    def set_text(self, data):
+    def set_text(self, data, _entry="np_hip_index_set_text"):
         """np_hip_index_set_text: the handle's keyword index from a text.TextIndexData (its vocabulary stays on this object
         in self.text); None drops it.  Document i of the FTS5 table is document i of the index.  Needs exclusive access to
         the handle, as set_columns does."""
+        fn = getattr(lib(), _entry)
         if data is None:
-            _check(lib().np_hip_index_set_text(self._h, None))
+            _check(fn(self._h, None))
         else:
             off = np.ascontiguousarray(data.term_offsets, np.int64)
             doc = np.ascontiguousarray(data.inst_doc, np.int64)
             pos = np.ascontiguousarray(data.inst_pos, np.int32)
             t = np_text_index(len(data.terms), off.ctypes.data, doc.ctypes.data if doc.size else None,
                               pos.ctypes.data if pos.size else None, int(data.n_rows))
-            _check(lib().np_hip_index_set_text(self._h, C.byref(t)))
+            _check(fn(self._h, C.byref(t)))
         self.text = data
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
 
@@ -1272,6 +1284,20 @@ class MmapIndex:
         from . import text as T
         data = T.TextIndexData.from_sqlite(os.path.join(index_path or self._dir("load_text"), "metadata.db"))
         self.set_text(data)
+        return data
+
+    def set_text_shard(self, data):
+        """np_hip_index_set_text_shard: set_text for a handle that holds a document shard.  `data` is the WHOLE table's
+        TextIndexData, the same on every rank (global document ids); the handle keeps the postings of its own documents and
+        the whole table's row count, token count and document frequencies.  On an unsharded handle it is set_text.  The
+        searches over it are dist.CShardedSearcher's text_search and search_hybrid."""
+        self.set_text(data, _entry="np_hip_index_set_text_shard")
+
+    def load_text_shard(self, index_path: str | None = None):
+        """set_text_shard from the metadata.db of an index directory; returns the (whole table's) TextIndexData."""
+        from . import text as T
+        data = T.TextIndexData.from_sqlite(os.path.join(index_path or self._dir("load_text_shard"), "metadata.db"))
+        self.set_text_shard(data)
         return data
 
     def _text_queries(self, text_queries, empty_matches_nothing: bool):

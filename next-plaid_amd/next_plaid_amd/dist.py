@@ -339,7 +339,12 @@ def gloo_all_gather(group=None):
 
 class CShardedSearcher:
     """The whole two-collective protocol through ONE C call per batch (np_hip_search_batch_sharded): what a compiled
-    host uses.  Outputs are torch tensors on the shard's device; every rank gets the global top-k."""
+    host uses.  Outputs are torch tensors on the shard's device; every rank gets the global top-k.
+
+    search_batch (subset / subsets / filters), text_search and search_hybrid take the arguments of the MmapIndex methods of
+    the same name and return what those return on the unsharded handle, bit for bit, on every rank: the filters run over the
+    shard's own columns (set_columns), the keyword index is the shard's slice of the whole table (set_text_shard).  Every rank
+    makes the same calls with the same arguments in the same order."""
 
     def __init__(self, index: "api.MmapIndex", comm: ShardComm, stream=None):
         import torch
@@ -378,7 +383,145 @@ class CShardedSearcher:
             api._check(rc, msg)
         return out
 
-    def search_batch(self, queries, params, subset=None, subsets=None):
+    def _outputs(self, B, k):
+        t = self.torch
+        return (t.zeros((max(B, 1), k), dtype=t.int64, device=self.device), t.zeros((max(B, 1), k), dtype=t.float32, device=self.device),
+                t.zeros(max(B, 1), dtype=t.int32, device=self.device))
+
+    def _finish(self, rc, out, n):
+        """The end of a one-call batch: (ids, scores, counts) on the host, or the call's error / the abandoned batch raised."""
+        if rc != 0:
+            msg = api.last_error()
+            # a failed batch must not leave its status word behind for the next healthy one: drain it before raising
+            self.stream.synchronize()
+            self.comm.status()
+            api._check(rc, msg)
+        ids, sc, cnt = (o.cpu().numpy() for o in out)
+        self.stream.synchronize()
+        rank, code = self.comm.status()   # a peer's failure abandons the batch on every rank: counts = -1 (np_dist.hip)
+        if code or (cnt[:n] < 0).any():
+            raise api.SearchError(f"Search failed: shard {rank} failed with status {code}; the batch was abandoned on every rank")
+        return ids, sc, cnt
+
+    def _device_queries(self, queries):
+        t = self.torch
+        qs = [np.ascontiguousarray(q, np.float32) for q in queries]
+        d = self.index.embedding_dim()
+        for q in qs:
+            if q.ndim != 2 or q.shape[1] != d:
+                raise api.ShapeError(f"Shape error: query has shape {q.shape}, index dim is {d}")
+        off = np.zeros(len(qs) + 1, np.int32)
+        if qs:
+            off[1:] = np.cumsum([q.shape[0] for q in qs])
+        flat = np.concatenate(qs, 0) if qs else np.zeros((0, d), np.float32)
+        return t.from_numpy(np.ascontiguousarray(flat, np.float32)).to(self.device), t.from_numpy(off).to(self.device), off
+
+    def _device_scope(self, sid, soff, n_sub, qsub):
+        """The host CSR of MmapIndex._scope as the device arguments of the sharded entries."""
+        if n_sub == 0:
+            return None, (None, None, None, 0, None)
+        ds = DeviceSubsets(self.torch, self.device, sid if sid is not None else np.zeros(0, np.int64), soff, qsub)
+        return ds, ds.args()
+
+    def _search_filtered(self, queries, params, filters):
+        t = self.torch
+        queries = list(queries)
+        cf, qf = self.index._filters(filters, len(queries))
+        qf = np.ascontiguousarray(qf, np.int32)
+        B, k = len(queries), max(int(params.top_k), 1)
+        p = params._c()
+        with t.cuda.stream(self.stream):
+            dq, do, off = self._device_queries(queries)
+            out = self._outputs(B, k)
+            rc = api.lib().np_hip_search_batch_sharded_filtered(
+                self.index._h, self.comm._h, C.c_void_p(dq.data_ptr()), C.c_void_p(do.data_ptr()), off.ctypes.data_as(C.c_void_p),
+                B, self.index.embedding_dim(), C.byref(p), cf.arr, cf.n, qf.ctypes.data_as(C.c_void_p),
+                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
+                C.c_void_p(self.stream.cuda_stream))
+            ids, sc, cnt = self._finish(rc, out, B)
+        return [api.QueryResult(i, ids[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(B)]
+
+    def text_search_device(self, queries, top_k: int, d_subsets=None, filters=None, out=None):
+        """np_hip_text_search_sharded / _filtered as they are: text.TextQuery objects, the scope as a DeviceSubsets or as
+        (compiled filters, host query map); returns (np_status, (ids, scores, counts) tensors on the device).  The caller
+        synchronises the stream and reads comm.status()."""
+        t = self.torch
+        n, k = len(queries), max(int(top_k), 1)
+        tq = api._CTextQueries(list(queries))
+        with t.cuda.stream(self.stream):
+            if out is None:
+                out = self._outputs(n, k)
+            o = (C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
+                 C.c_void_p(self.stream.cuda_stream))
+            if filters is not None:
+                cf, qf = filters
+                qf = np.ascontiguousarray(qf, np.int32)
+                rc = api.lib().np_hip_text_search_sharded_filtered(self.index._h, self.comm._h, tq.arr, n, int(top_k), cf.arr, cf.n,
+                                                                   qf.ctypes.data_as(C.c_void_p), *o)
+            else:
+                a = (None, None, None, 0, None) if d_subsets is None else d_subsets.args()
+                rc = api.lib().np_hip_text_search_sharded(self.index._h, self.comm._h, tq.arr, n, int(top_k), *a, *o)
+        return rc, out
+
+    def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None):
+        """MmapIndex.text_search over the shards (np_hip_text_search_sharded, np_hip_text_search_sharded_filtered)."""
+        t = self.torch
+        if isinstance(text_queries, str):
+            text_queries = [text_queries]
+        qs = self.index._text_queries(list(text_queries), False)
+        B = len(qs)
+        live = [i for i, q in enumerate(qs) if q is not None]
+        res = [api.QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
+        sid, soff, n_sub, qsub, cf = self.index._scope(B, subset, subsets, filters, "text_search")
+        if qsub is not None:
+            qsub = np.ascontiguousarray(np.asarray(qsub)[live], np.int32) if live else np.zeros(1, np.int32)
+        n = len(live)
+        with t.cuda.stream(self.stream):
+            if cf is not None:
+                rc, out = self.text_search_device([qs[i] for i in live], top_k, filters=(cf, qsub))
+            else:
+                rc, out = self.text_search_device([qs[i] for i in live], top_k, d_subsets=self._device_scope(sid, soff, n_sub, qsub)[0])
+            ids, sc, cnt = self._finish(rc, out, n)
+        for j, i in enumerate(live):
+            res[i] = api.QueryResult(i, ids[j, : cnt[j]].copy(), sc[j, : cnt[j]].copy())
+        return res
+
+    def search_hybrid(self, queries, text_queries, params, alpha: float = 0.75, fusion: str = "relative_score",
+                      fetch_k: int | None = None, subsets=None, filters=None):
+        """MmapIndex.search_hybrid over the shards (np_hip_search_hybrid_sharded): both global lists are merged on every rank,
+        every rank fuses."""
+        from . import text as T
+        t = self.torch
+        queries = list(queries)
+        B = len(queries)
+        qs = self.index._text_queries(list(text_queries), True)
+        if len(qs) != B:
+            raise ValueError(f"{B} queries and {len(qs)} text queries")
+        fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
+        sid, soff, n_sub, qsub, cf = self.index._scope(B, None, subsets, filters, "search_hybrid")
+        tq = api._CTextQueries(qs)
+        k = max(int(params.top_k), 1)
+        p = params._c()
+        with t.cuda.stream(self.stream):
+            dq, do, off = self._device_queries(queries)
+            out = self._outputs(B, k)
+            keep, a = (None, (None, None, None, 0, None)) if cf is not None else self._device_scope(sid, soff, n_sub, qsub)
+            qf = None if cf is None else np.ascontiguousarray(qsub, np.int32)
+            rc = api.lib().np_hip_search_hybrid_sharded(
+                self.index._h, self.comm._h, C.c_void_p(dq.data_ptr()), C.c_void_p(do.data_ptr()), off.ctypes.data_as(C.c_void_p),
+                B, self.index.embedding_dim(), C.byref(p), tq.arr, fk, float(alpha),
+                T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion), *a,
+                None if cf is None else cf.arr, 0 if cf is None else cf.n, None if qf is None else qf.ctypes.data_as(C.c_void_p),
+                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
+                C.c_void_p(self.stream.cuda_stream))
+            ids, sc, cnt = self._finish(rc, out, B)
+        return [api.QueryResult(i, ids[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(B)]
+
+    def search_batch(self, queries, params, subset=None, subsets=None, filters=None):
+        if filters is not None:
+            if subset is not None or subsets is not None:
+                raise ValueError("search_batch takes filters= or subset= / subsets=, not both")
+            return self._search_filtered(queries, params, filters)
         t = self.torch
         packed = _packed_subsets(subset, subsets, len(queries))
         qs = [np.ascontiguousarray(q, np.float32) for q in queries]
