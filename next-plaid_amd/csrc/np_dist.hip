@@ -463,8 +463,7 @@ extern "C" int np_hip_search_batch_sharded(const np_index* ix, np_comm* c, const
   NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
   std::lock_guard<std::mutex> lk(c->mu);
   return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
-                                     ShardSubsets{d_subset, subset_len, nullptr, nullptr, 0, nullptr}, d_out_ids, d_out_scores,
-                                     d_out_counts, stream);
+                                     ShardSubsets::single(d_subset, subset_len), d_out_ids, d_out_scores, d_out_counts, stream);
 }
 
 // Arguments every rank sees alike are checked before the first collective; `query_subset` lives on the device and is not.
@@ -477,20 +476,47 @@ extern "C" int np_hip_search_batch_sharded_subsets(const np_index* ix, np_comm* 
                                                    int32_t* d_out_counts, void* stream) {
   clear_error();
   NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
-  const ShardSubsets ss = n_subsets > 0 ? ShardSubsets{d_subset_ids, 0, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset}
-                                        : ShardSubsets{nullptr, -1, nullptr, nullptr, 0, nullptr};
+  const ShardSubsets ss =
+      ShardSubsets::csr(CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset));
   NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
   std::lock_guard<std::mutex> lk(c->mu);
   return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss, d_out_ids,
                                      d_out_scores, d_out_counts, stream);
 }
 
-// The filters of a sharded call over this shard's columns, into the communicator's own buffers (a context of the handle stays
-// free for the pass).  Synchronises the stream.
-int np::shard_filters_eval(const np_index* ix, np_comm* c, hipStream_t st, const np_filter* filters, int32_t n_filters,
-                           const int32_t* query_filter, int B, FilterCsr* csr) {
-  NP_TRY(filter_check_call(ix, filters, n_filters, query_filter, B, 2));
-  return filter_eval_resident(ix, st, c->filt, c->filt_csr, filters, n_filters, query_filter, B, csr);
+int np::check_sharded_filters(const char* who, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B) {
+  if (n_filters < 0 || (n_filters > 0 && (!filters || (B > 0 && !query_filter)))) {
+    set_error("%s: negative n_filters, or filters without programs or a query map", who);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+void np::ShardFilterScope::eval(const np_index* ix, np_comm* c, hipStream_t st, const np_filter* filters, int32_t n_filters,
+                                const int32_t* query_filter, int B) {
+  n = n_filters;
+  any = any_scoped(query_filter, n_filters, B);
+  if (!any) return;
+  rc0 = filter_check_call(ix, filters, n_filters, query_filter, B, 2);
+  if (rc0 == NP_OK) rc0 = filter_eval_resident(ix, st, c->filt, c->filt_csr, filters, n_filters, query_filter, B, &csr);
+  zero.assign((size_t)n + 1, 0);
+  lens.assign((size_t)n, 0);
+  if (rc0 != NP_OK) {
+    msg0 = np_hip_last_error();
+    return;
+  }
+  for (int32_t f = 0; f < n; ++f) lens[(size_t)f] = csr.h_off[(size_t)f + 1] - csr.h_off[(size_t)f];
+  sub = CallSubsets::device(csr.d_ids, csr.d_off, csr.h_off.data(), n, csr.d_qsub, query_filter);
+}
+
+np::ShardSubsets np::ShardFilterScope::shard() const {
+  if (!any) return ShardSubsets::none();
+  CallSubsets s = sub;
+  if (rc0 != NP_OK) {   // the rank still exchanges one (empty) row per filter
+    s.n = n;
+    s.h_off = zero.data();
+  }
+  return ShardSubsets::csr(s).with_local_lens(lens.data());
 }
 
 // The filters are evaluated over the shard's own columns; what crosses the ranks beyond np_hip_search_batch_sharded_subsets'
@@ -503,27 +529,12 @@ extern "C" int np_hip_search_batch_sharded_filtered(const np_index* ix, np_comm*
                                                     float* d_out_scores, int32_t* d_out_counts, void* stream) {
   clear_error();
   NP_TRY(check_sharded_call(ix, c, B, params, d_out_ids, d_out_scores, d_out_counts, stream));
-  if (n_filters < 0 || (n_filters > 0 && (!filters || (B > 0 && !query_filter)))) {
-    set_error("search_batch_sharded_filtered: negative n_filters, or filters without programs or a query map");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
+  NP_TRY(check_sharded_filters("search_batch_sharded_filtered", filters, n_filters, query_filter, B));
   if (B == 0) return NP_OK;
   std::lock_guard<std::mutex> lk(c->mu);
-  bool any = false;
-  for (int b = 0; n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
-  if (!any)   // as unsharded: a batch none of whose queries has a filter is a batch without subsets
-    return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params,
-                                       ShardSubsets{nullptr, -1, nullptr, nullptr, 0, nullptr}, d_out_ids, d_out_scores,
-                                       d_out_counts, stream);
   DeviceGuard g(ix->device);
-  FilterCsr csr;
-  const int rc0 = shard_filters_eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B, &csr);
-  const std::string msg0 = rc0 != NP_OK ? np_hip_last_error() : "";
-  std::vector<int64_t> zero((size_t)n_filters + 1, 0), lens((size_t)n_filters, 0);
-  if (rc0 == NP_OK)
-    for (int32_t f = 0; f < n_filters; ++f) lens[(size_t)f] = csr.h_off[(size_t)f + 1] - csr.h_off[(size_t)f];
-  ShardSubsets ss{csr.d_ids, 0, csr.d_off, rc0 == NP_OK ? csr.h_off.data() : zero.data(), n_filters, csr.d_qsub};
-  ss.h_local_lens = lens.data();
-  return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, ss, d_out_ids,
-                                     d_out_scores, d_out_counts, stream, rc0, msg0.c_str());
+  ShardFilterScope scope;   // (as unsharded: a batch none of whose queries has a filter is a batch without subsets)
+  scope.eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B);
+  return search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, scope.shard(), d_out_ids,
+                                     d_out_scores, d_out_counts, stream, scope.rc0, scope.msg0.c_str());
 }

@@ -223,7 +223,6 @@ __global__ void __launch_bounds__(FILTER_TPB) filter_compact_kernel(FilterCompac
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int filter_check_call(const DeviceIndex* ix, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B,
                       int for_search) {
@@ -330,23 +329,18 @@ struct FilterRun {
                  b_base = up256((size_t)plan.filters * blocks * 8);
     const size_t b_stage = stage ? up256((size_t)plan.filters * plan.docs * 8) : 0;
     NP_TRY(scratch.reserve(b_prog + b_tot + b_tab + b_mask + b_cnt + b_base + b_stage + b_match));
-    char* at = scratch.as<char>();
-    auto take = [&](size_t bytes) {
-      char* r = at;
-      at += bytes;
-      return r;
-    };
-    d_ops = (np_filter_op*)take(up256((size_t)n_ops * sizeof(np_filter_op)));
-    d_op_begin = (int32_t*)take(up256((size_t)(n_filters + 1) * 4));
-    d_values = (int64_t*)take(up256((size_t)std::max<int64_t>(n_vals, 1) * 8));
-    d_totals = (int64_t*)take(b_tot);
-    d_table = (int64_t*)take(b_tab);
-    d_mask = (unsigned long long*)take(b_mask);
-    d_counts = (uint32_t*)take(b_cnt);
-    d_base = (int64_t*)take(b_base);
-    d_stage = stage ? (int64_t*)take(b_stage) : nullptr;
-    d_match_bits = (uint32_t*)take(up256((size_t)match_words * 4));
-    char* d_match_work = take(up256((size_t)match_work));
+    Carver carve{scratch.as<char>()};
+    d_ops = (np_filter_op*)carve.take((size_t)n_ops * sizeof(np_filter_op));
+    d_op_begin = (int32_t*)carve.take((size_t)(n_filters + 1) * 4);
+    d_values = (int64_t*)carve.take((size_t)std::max<int64_t>(n_vals, 1) * 8);
+    d_totals = (int64_t*)carve.take(b_tot);
+    d_table = (int64_t*)carve.take(b_tab);
+    d_mask = (unsigned long long*)carve.take(b_mask);
+    d_counts = (uint32_t*)carve.take(b_cnt);
+    d_base = (int64_t*)carve.take(b_base);
+    d_stage = stage ? (int64_t*)carve.take(b_stage) : nullptr;
+    d_match_bits = (uint32_t*)carve.take((size_t)match_words * 4);
+    char* d_match_work = carve.take((size_t)match_work);
     // the programs, with every op's constants copied behind one another and its first_value re-based to them
     std::vector<np_filter_op> ops((size_t)n_ops);
     std::vector<int32_t> begin((size_t)n_filters + 1);

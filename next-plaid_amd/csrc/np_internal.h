@@ -400,10 +400,11 @@ int merge_packed_status(const DeviceIndex* ix, const void* d_records, int64_t re
                         int top_k, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, hipStream_t st);
 int set_status_word(const DeviceIndex* ix, uint64_t* d_word, uint64_t value, hipStream_t st);
 
-// np_search.hip, for call paths outside the search pass (np_scan.hip): a context of the handle's pool checked out for one
-// call -- begin() waits for the workspace's previous use on the call's stream, the destructor records the end of this one
-// and hands the context back.  arena() is the context's one device allocation for such a call (grown on demand, never
-// shrunk, counted in the workspace like every other buffer); pin() its pinned host staging area.
+// np_search.hip, for the host entry points outside the search pass (exact scan, pair scoring, filters, keyword and hybrid
+// search): a context of the handle's pool checked out for one call -- begin() waits for the workspace's previous use on the
+// call's stream, the destructor records the end of this one and hands the context back.  arena() is the context's one device
+// allocation for such a call (grown on demand, never shrunk, counted in the workspace like every other buffer); pin() its
+// pinned host staging area.
 struct ContextUse {
   const DeviceIndex* ix = nullptr;
   Context* ctx = nullptr;
@@ -416,6 +417,50 @@ struct ContextUse {
   int pin(size_t bytes, void** out) const;
   int end();   // records the end of the use now (the destructor then only releases)
   ~ContextUse();
+};
+
+// ---- what the host entry points share: the carve-up of a reserved region, a call's scope, its result staging ---------------
+static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// a reserved region handed out in 256-byte aligned pieces
+struct Carver {
+  char* at;
+  char* take(size_t bytes) {
+    char* r = at;
+    at += up256(bytes);
+    return r;
+  }
+};
+// a batch none of whose queries has a subset (or a filter) is a batch without subsets
+static inline bool any_scoped(const int32_t* query_subset, int64_t n, int B) {
+  bool any = false;
+  for (int b = 0; n > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
+  return any;
+}
+// A call's scope -- the documents each query may see -- as every pass takes it: a CSR of subsets on the device with one
+// subset (or -1) per query, plus the host's copies of the offsets and -- where the caller has it, NULL otherwise -- of the
+// query map: with both a pass builds only the id range its own queries reference.  n == 0: no scope.
+struct CallSubsets {
+  const int64_t* d_ids = nullptr;
+  const int64_t* d_off = nullptr;
+  const int32_t* d_qsub = nullptr;
+  int64_t n = 0, total = 0;
+  const int64_t* h_off = nullptr;
+  const int32_t* h_qsub = nullptr;
+  bool any() const { return n > 0; }
+  // the checked CSR arguments of a device-side entry point; h_qsub: the host's copy of the query map, where there is one
+  static CallSubsets device(const int64_t* d_ids, const int64_t* d_off, const int64_t* h_off, int64_t n_subsets,
+                            const int32_t* d_qsub, const int32_t* h_qsub = nullptr) {
+    CallSubsets s;
+    if (n_subsets <= 0) return s;
+    s.d_ids = d_ids;
+    s.d_off = d_off;
+    s.d_qsub = d_qsub;
+    s.n = n_subsets;
+    s.total = h_off[n_subsets];
+    s.h_off = h_off;
+    s.h_qsub = h_qsub;
+    return s;
+  }
 };
 // the document bitmaps of a pass's subsets (subset_rows_kernel + subset_kernel without the eligible-centroid side):
 // qrow[B] = the row of query b (-1: no subset), docbits[row][NW] over the shard's documents.  CSR arguments on the device,
@@ -457,13 +502,62 @@ int match_run_jobs(const DeviceIndex* ix, hipStream_t st, const std::vector<Matc
 int filter_eval_resident(const DeviceIndex* ix, hipStream_t st, DevBuf& scratch, DevBuf& out, const np_filter* filters,
                          int32_t n_filters, const int32_t* h_query_filter, int B, FilterCsr* csr);
 
+// The scope of a host entry point (np_search.hip), in two steps because the arena is reserved between them.  The scope comes as
+// a host CSR, or (filters != NULL) as n_subsets filters that resolve() evaluates on the call's context into a CSR that stays on
+// the device; query_subset is the query map of either.  The object owns that evaluation's FilterCsr -- the host offsets of the
+// CallSubsets point into it -- so it lives as long as the call and is not copied.
+struct HostScope {
+  bool any = false;        // some query has a subset
+  bool resident = false;   // ... and the CSR is on the device already (filters)
+  int64_t total = 0;       // ids of all subsets together
+  int resolve(const DeviceIndex* ix, ContextUse& use, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+              const int32_t* query_subset, const np_filter* filters, int B);
+  bool staged() const { return any && !resident; }   // the CSR is copied into the arena
+  size_t stage_bytes() const {
+    return staged() ? up256((size_t)std::max<int64_t>(total, 1) * 8) + up256((size_t)(n + 1) * 8) + up256((size_t)B * 4) : 0;
+  }
+  int64_t budget_extra() const { return resident ? total * 8 : 0; }   // a filter's CSR lives outside the arena but inside the budget
+  float ms() const { return csr.ms; }   // wall time of the filters' evaluation
+  // carves stage_bytes() and enqueues the CSR's upload on st (staged), or points at the evaluated one
+  int place(Carver& carve, hipStream_t st, CallSubsets* sub) const;
+  HostScope() = default;
+  HostScope(const HostScope&) = delete;
+  HostScope& operator=(const HostScope&) = delete;
+
+ private:
+  FilterCsr csr;
+  const int64_t *ids = nullptr, *off = nullptr;
+  const int32_t* qsub = nullptr;
+  int64_t n = 0;
+  int B = 0;
+};
+
+// The results of a host entry point, [B][top_k] ids and scores and [B] counts: carved out of the arena, copied back through the
+// head of the pinned area (whatever else a call pins lies behind bytes()), handed to the caller once the stream is synchronised.
+struct ResultStage {
+  size_t n, B;                  // B * top_k, B
+  size_t o_ids, o_sc, o_cnt;    // the three regions' sizes
+  int64_t* d_ids = nullptr;
+  float* d_sc = nullptr;
+  int32_t* d_cnt = nullptr;
+  char* pin = nullptr;
+  ResultStage(int B_, int top_k)
+      : n((size_t)B_ * top_k), B((size_t)B_), o_ids(up256(n * 8)), o_sc(up256(n * 4)), o_cnt(up256(B * 4)) {}
+  size_t bytes() const { return o_ids + o_sc + o_cnt; }   // of the arena, and of the pinned area
+  void carve(Carver& c) {
+    d_ids = (int64_t*)c.take(o_ids);
+    d_sc = (float*)c.take(o_sc);
+    d_cnt = (int32_t*)c.take(o_cnt);
+  }
+  int fetch(void* pinned, hipStream_t st);   // the three copies to the host, enqueued
+  void deliver(int64_t* out_ids, float* out_scores, int32_t* out_counts) const;
+};
+
 // np_search.hip: the pass of np_hip_search_batch_subsets_device on a context the caller already holds (np_hip_search_hybrid
-// runs the semantic and the keyword pass on one context and one stream).  The CSR is on the device; h_off / h_qsub are the
-// host copies the host entry points hand their passes (NULL where there is none), n_subsets == 0 = no subsets.
+// runs the semantic and the keyword pass on one context and one stream).
 int search_batch_in_use(const DeviceIndex* ix, ContextUse& use, const float* d_q, const int32_t* d_qoff, const int32_t* h_qoff,
-                        int B, int dim, const np_search_params* prm, const int64_t* d_ids, const int64_t* d_off,
-                        const int64_t* h_off, int64_t n_subsets, const int32_t* d_qsub, const int32_t* h_qsub,
-                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts);
+                        int B, int dim, const np_search_params* prm, const CallSubsets& scope, int64_t* d_out_ids,
+                        float* d_out_scores, int32_t* d_out_counts);
 
 // np_search.hip: np_hip_search_phase_a_subsets with the subsets' GLOBAL lengths on the device (d_global_lens[n_subsets], NULL =
 // the CSR's own): what the probe scaling reads when the CSR holds only a shard's part of every subset
@@ -524,13 +618,36 @@ int comm_small_pin(np_comm* c, size_t bytes, char** out);   // the pinned area, 
 // h_local_lens (filters): the CSR holds only this shard's part of every subset; the local lengths ride in that all-gather and
 // the probe scaling reads their sums.
 struct ShardSubsets {
-  const int64_t* d_ids;
-  int64_t len;
-  const int64_t *d_off, *h_off;
-  int64_t n;
-  const int32_t* d_qsub;
+  const int64_t* d_ids = nullptr;
+  int64_t len = -1;
+  const int64_t *d_off = nullptr, *h_off = nullptr;
+  int64_t n = 0;
+  const int32_t* d_qsub = nullptr;
   const int64_t* h_local_lens = nullptr;
   int64_t rows() const { return h_off ? n : (len > 0 ? 1 : 0); }   // eligible bitmaps to exchange
+  static ShardSubsets none() { return ShardSubsets(); }
+  static ShardSubsets single(const int64_t* d_ids, int64_t len) {
+    ShardSubsets s;
+    s.d_ids = d_ids;
+    s.len = len;
+    return s;
+  }
+  static ShardSubsets csr(const CallSubsets& c) {   // (a scope without subsets is none())
+    ShardSubsets s;
+    if (!c.any()) return s;
+    s.d_ids = c.d_ids;
+    s.len = 0;
+    s.d_off = c.d_off;
+    s.h_off = c.h_off;
+    s.n = c.n;
+    s.d_qsub = c.d_qsub;
+    return s;
+  }
+  ShardSubsets with_local_lens(const int64_t* lens) const {
+    ShardSubsets s = *this;
+    s.h_local_lens = lens;
+    return s;
+  }
 };
 // np_hip_search_batch_sharded's pass; the caller holds c->mu.  rc0 / rc0_msg: a local failure the caller already met (its
 // filters did not evaluate): the rank then takes part in every exchange with empty data and returns that error.
@@ -538,8 +655,32 @@ int search_batch_sharded_locked(const np_index* ix, np_comm* c, const float* d_q
                                 const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
                                 const ShardSubsets& ss, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
                                 void* stream, int rc0 = NP_OK, const char* rc0_msg = nullptr);
-// a sharded call's filters evaluated over this shard's columns into the communicator's CSR (np_filter.hip's checks first)
-int shard_filters_eval(const np_index* ix, np_comm* c, hipStream_t st, const np_filter* filters, int32_t n_filters,
-                       const int32_t* query_filter, int B, FilterCsr* csr);
+
+// the arguments of a sharded call's filters that need no handle; `who` starts the message
+int check_sharded_filters(const char* who, const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B);
+
+// The filters of a sharded call as its scope (np_dist.hip).  eval() -- the caller holds c->mu -- evaluates them over this
+// shard's columns into the communicator's own buffers (np_filter.hip's checks first; a context of the handle stays free for
+// the pass) and synchronises the stream.  A failure stays in rc0 / msg0 for the pass to carry through its exchanges: the rank
+// then takes part with subsets that are all empty (shard()) and hands its own passes no scope (call()).  A batch none of
+// whose queries has a filter evaluates nothing and has no scope.
+struct ShardFilterScope {
+  bool any = false;
+  int rc0 = NP_OK;
+  std::string msg0;
+  void eval(const np_index* ix, np_comm* c, hipStream_t st, const np_filter* filters, int32_t n_filters,
+            const int32_t* query_filter, int B);
+  const CallSubsets& call() const { return sub; }
+  ShardSubsets shard() const;   // with every filter's local length, for the probe scaling
+  ShardFilterScope() = default;
+  ShardFilterScope(const ShardFilterScope&) = delete;
+  ShardFilterScope& operator=(const ShardFilterScope&) = delete;
+
+ private:
+  FilterCsr csr;
+  CallSubsets sub;                  // empty after a failure
+  std::vector<int64_t> zero, lens;  // offsets of a failed evaluation; the local lengths
+  int32_t n = 0;
+};
 
 }  // namespace np

@@ -92,7 +92,6 @@ __global__ void __launch_bounds__(MATCH_TPB) match_kernel(MatchP p) {
   }
 }
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // One launch group: DFAs [0, n) described by host-built images, over strings [s0, s0 + ns) of a column, verdicts to
 // d_bits[row][row_words].  d_work receives the images and the descriptor table (the caller sized it: sum of up256(image) + 4096).

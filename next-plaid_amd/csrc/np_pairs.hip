@@ -186,8 +186,6 @@ static int launch_pairs_dim(hipStream_t st, const PairsP& p, unsigned gx, int nb
   return launch_pairs_qt<DIM, 4>(st, p, gx);
 }
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // bytes of the arena that scale with the slice (per query): its staged Qt at the longest query, its two map entries
 static int64_t pairs_per_query(const DeviceIndex* ix) {
   return (int64_t)up256((size_t)ix->dim * NP_PAIRS_MAX_QUERY_TOKENS * 4) + 16;
@@ -203,15 +201,10 @@ static int pairs_run(const DeviceIndex* ix, ContextUse& use, char* base, int S, 
                      const int32_t* h_qoff, int B, const int64_t* d_pair_docs, const int64_t* d_poff, const int64_t* h_poff,
                      float* d_scores, float* d_sims, int32_t* d_pos, unsigned long long* ctr, np_stats* stats) {
   hipStream_t st = use.stream;
-  char* at = base;
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += up256(bytes);
-    return r;
-  };
-  int64_t* rowbase = (int64_t*)take((size_t)(S + 1) * 8);
-  int32_t* wgpre = (int32_t*)take((size_t)(S + 1) * 4);
-  float* Qt = (float*)take((size_t)S * up256((size_t)ix->dim * NP_PAIRS_MAX_QUERY_TOKENS * 4));
+  Carver carve{base};
+  int64_t* rowbase = (int64_t*)carve.take((size_t)(S + 1) * 8);
+  int32_t* wgpre = (int32_t*)carve.take((size_t)(S + 1) * 4);
+  float* Qt = (float*)carve.take((size_t)S * up256((size_t)ix->dim * NP_PAIRS_MAX_QUERY_TOKENS * 4));
   int64_t row0 = 0;
   for (int s0 = 0; s0 < B;) {
     int max_lq = 0;
@@ -364,18 +357,13 @@ int np_hip_score_pairs(const np_index* ix, const float* queries, const int32_t* 
   NP_TRY(use.arena().reserve(b_q + b_qoff + b_poff + run_bytes + stage));
   void* pinv = nullptr;
   NP_TRY(use.pin(b_poff + stage, &pinv));
-  char* at = use.arena().as<char>();
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += bytes;
-    return r;
-  };
-  float* d_q = (float*)take(b_q);
-  int32_t* d_qoff = (int32_t*)take(b_qoff);
-  int64_t* d_poff = (int64_t*)take(b_poff);
-  char* run_base = take(run_bytes);
+  Carver carve{use.arena().as<char>()};
+  float* d_q = (float*)carve.take(b_q);
+  int32_t* d_qoff = (int32_t*)carve.take(b_qoff);
+  int64_t* d_poff = (int64_t*)carve.take(b_poff);
+  char* run_base = carve.take(run_bytes);
   unsigned long long* ctr = (unsigned long long*)(run_base + run_bytes - 256);   // inside kPairsFixed, past the run's regions
-  char* d_stage = take(stage);
+  char* d_stage = carve.take(stage);
   int64_t* h_poff = (int64_t*)pinv;
   char* h_stage = (char*)pinv + b_poff;
   if (ntok > 0) NP_HIP(hipMemcpyAsync(d_q, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));

@@ -338,18 +338,6 @@ static int launch_scan_dim(hipStream_t st, const ScanP& p, unsigned gx, unsigned
   return bf16 ? launch_scan<DIM, 4, true>(st, p, gx, groups) : launch_scan<DIM, 4, false>(st, p, gx, groups);
 }
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// what a call carries besides the queries
-struct ScanSubsets {
-  const int64_t* d_ids = nullptr;
-  const int64_t* d_off = nullptr;
-  const int32_t* d_qsub = nullptr;
-  int64_t n = 0, total = 0;
-  const int64_t* h_off = nullptr;    // host copies where the caller has them
-  const int32_t* h_qsub = nullptr;
-};
-
 // bytes of the arena that scale with the slice (per query) -- one expression for the plan and for the carve-up
 static int64_t scan_per_query(const DeviceIndex* ix, int top_k, bool subsets) {
   const int64_t NW = (ix->n_docs + 31) / 32;
@@ -361,7 +349,7 @@ static int64_t scan_per_query(const DeviceIndex* ix, int top_k, bool subsets) {
 // The whole batch on device buffers: slices of S queries, passes of P documents.  `base` .. `base + room`: the part of the
 // arena this function may carve.  With `stats` the stream is synchronised per pass (timings), otherwise nothing waits.
 static int scan_run(const DeviceIndex* ix, ContextUse& use, char* base, const ScanPlan& plan, const float* d_q,
-                    const int32_t* d_qoff, const int32_t* h_qoff, int B, int top_k, int precision, const ScanSubsets& sub,
+                    const int32_t* d_qoff, const int32_t* h_qoff, int B, int top_k, int precision, const CallSubsets& sub,
                     int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, np_stats* stats) {
   hipStream_t st = use.stream;
   const int S = plan.S;
@@ -369,19 +357,14 @@ static int scan_run(const DeviceIndex* ix, ContextUse& use, char* base, const Sc
   const bool bf16 = precision == 3 && ix->nbits != 8;
   const bool subsets = sub.n > 0;
   // carve-up (scan_per_query's terms, times S)
-  char* at = base;
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += up256(bytes);
-    return r;
-  };
-  unsigned long long* ctr = (unsigned long long*)take(16);
-  int32_t* tile_info = (int32_t*)take((size_t)S * NP_SCAN_MAX_TILES * 4);
-  int32_t* qrow = (int32_t*)take((size_t)S * 4);
-  char* Q = take((size_t)S * up256((size_t)ix->dim * NP_SCAN_MAX_QUERY_TOKENS * 4));
-  uint64_t* best = (uint64_t*)take((size_t)S * up256((size_t)top_k * 8));
-  uint32_t* docbits = subsets ? (uint32_t*)take((size_t)S * up256((size_t)NW * 4)) : nullptr;
-  uint64_t* keys = (uint64_t*)take((size_t)S * P * 8);
+  Carver carve{base};
+  unsigned long long* ctr = (unsigned long long*)carve.take(16);
+  int32_t* tile_info = (int32_t*)carve.take((size_t)S * NP_SCAN_MAX_TILES * 4);
+  int32_t* qrow = (int32_t*)carve.take((size_t)S * 4);
+  char* Q = carve.take((size_t)S * up256((size_t)ix->dim * NP_SCAN_MAX_QUERY_TOKENS * 4));
+  uint64_t* best = (uint64_t*)carve.take((size_t)S * up256((size_t)top_k * 8));
+  uint32_t* docbits = subsets ? (uint32_t*)carve.take((size_t)S * up256((size_t)NW * 4)) : nullptr;
+  uint64_t* keys = (uint64_t*)carve.take((size_t)S * P * 8);
   int nselp = 1;
   while (nselp < top_k) nselp <<= 1;
   const size_t topk_lds = (size_t)nselp * 8;
@@ -545,14 +528,7 @@ int np_hip_search_exact_device(const np_index* ix, const float* d_queries, const
     set_error("Search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  ScanSubsets sub;
-  if (n_subsets > 0) {
-    sub.d_ids = d_subset_ids;
-    sub.d_off = d_subset_offsets;
-    sub.d_qsub = d_query_subset;
-    sub.n = n_subsets;
-    sub.total = h_subset_offsets[n_subsets];
-  }
+  const CallSubsets sub = CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset);
   DeviceGuard g(ix->device);
   ScanPlan plan;
   NP_TRY(scan_plan_for(ix, 0, B, top_k, sub.n > 0, &plan));
@@ -585,79 +561,36 @@ static int scan_host(const np_index* ix, const float* queries, const int32_t* q_
     set_error("Search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  // a batch none of whose queries has a subset is a batch without subsets
-  bool any = false;
-  for (int b = 0; n_subsets > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
-  const bool resident = any && filters;
   DeviceGuard g(ix->device);
   ContextUse use;
   NP_TRY(use.begin(ix, nullptr));
   hipStream_t st = use.stream;
-  FilterCsr csr;
-  if (resident) {
-    NP_TRY(filter_eval_resident(ix, st, use.filter_scratch(), use.filter_csr(), filters, (int32_t)n_subsets, query_subset, B, &csr));
-    subset_offsets = csr.h_off.data();
-  }
-  const int64_t total = any ? subset_offsets[n_subsets] : 0;
+  HostScope scope;
+  NP_TRY(scope.resolve(ix, use, subset_ids, subset_offsets, n_subsets, query_subset, filters, B));
   const int64_t ntok = q_tok_offsets[B];
   // behind the scan's own regions: queries, offsets, the subsets, the batch's results
   const size_t b_q = up256((size_t)std::max<int64_t>(ntok, 1) * dim * 4), b_qoff = up256((size_t)(B + 1) * 4);
-  const bool staged = any && !resident;   // the subsets' CSR is copied behind the queries; a filter's is on the device already
-  const size_t b_ids = staged ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = staged ? up256((size_t)(n_subsets + 1) * 8) : 0;
-  const size_t b_qsub = staged ? up256((size_t)B * 4) : 0;
-  const size_t o_ids = up256((size_t)B * top_k * 8), o_sc = up256((size_t)B * top_k * 4), o_cnt = up256((size_t)B * 4);
-  const size_t user = b_q + b_qoff + b_ids + b_off + b_qsub + o_ids + o_sc + o_cnt;
+  ResultStage res(B, top_k);
+  const size_t user = b_q + b_qoff + scope.stage_bytes() + res.bytes();
   ScanPlan plan;
-  // (a filter's CSR lives outside the arena but inside the budget)
-  NP_TRY(scan_plan_for(ix, (int64_t)user + (resident ? total * 8 : 0), B, top_k, any, &plan));
-  NP_TRY(use.arena().reserve(user +scan_arena_bytes(ix, plan, top_k, any)));
-  void* pinv = nullptr;
-  NP_TRY(use.pin(o_ids + o_sc + o_cnt, &pinv));
-  char* at = use.arena().as<char>();
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += bytes;
-    return r;
-  };
-  float* d_q = (float*)take(b_q);
-  int32_t* d_qoff = (int32_t*)take(b_qoff);
-  ScanSubsets sub;
-  if (resident) {
-    sub.d_ids = csr.d_ids;
-    sub.d_off = csr.d_off;
-    sub.d_qsub = csr.d_qsub;
-    sub.n = n_subsets;
-    sub.total = total;
-    sub.h_off = subset_offsets;
-    sub.h_qsub = query_subset;
-  } else if (any) {
-    sub.d_ids = (const int64_t*)take(b_ids);
-    sub.d_off = (const int64_t*)take(b_off);
-    sub.d_qsub = (const int32_t*)take(b_qsub);
-    sub.n = n_subsets;
-    sub.total = total;
-    sub.h_off = subset_offsets;
-    sub.h_qsub = query_subset;
-    if (total > 0) NP_HIP(hipMemcpyAsync((void*)sub.d_ids, subset_ids, (size_t)total * 8, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemcpyAsync((void*)sub.d_off, subset_offsets, (size_t)(n_subsets + 1) * 8, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemcpyAsync((void*)sub.d_qsub, query_subset, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  }
-  int64_t* d_ids = (int64_t*)take(o_ids);
-  float* d_sc = (float*)take(o_sc);
-  int32_t* d_cnt = (int32_t*)take(o_cnt);
+  NP_TRY(scan_plan_for(ix, (int64_t)user + scope.budget_extra(), B, top_k, scope.any, &plan));
+  NP_TRY(use.arena().reserve(user + scan_arena_bytes(ix, plan, top_k, scope.any)));
+  void* pin = nullptr;
+  NP_TRY(use.pin(res.bytes(), &pin));
+  Carver carve{use.arena().as<char>()};
+  float* d_q = (float*)carve.take(b_q);
+  int32_t* d_qoff = (int32_t*)carve.take(b_qoff);
+  CallSubsets sub;
+  NP_TRY(scope.place(carve, st, &sub));
+  res.carve(carve);
   if (ntok > 0) NP_HIP(hipMemcpyAsync(d_q, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-  NP_TRY(scan_run(ix, use, at, plan, d_q, d_qoff, q_tok_offsets, B, top_k, precision, sub, d_ids, d_sc, d_cnt, stats));
-  char* pin = (char*)pinv;
-  NP_HIP(hipMemcpyAsync(pin, d_ids, (size_t)B * top_k * 8, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_ids, d_sc, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_ids + o_sc, d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  NP_TRY(scan_run(ix, use, carve.at, plan, d_q, d_qoff, q_tok_offsets, B, top_k, precision, sub, res.d_ids, res.d_sc, res.d_cnt, stats));
+  NP_TRY(res.fetch(pin, st));
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
-  memcpy(out_ids, pin, (size_t)B * top_k * 8);
-  memcpy(out_scores, pin + o_ids, (size_t)B * top_k * 4);
-  memcpy(out_counts, pin + o_ids + o_sc, (size_t)B * 4);
-  if (stats) stats->ms_total += csr.ms;
+  res.deliver(out_ids, out_scores, out_counts);
+  if (stats) stats->ms_total += scope.ms();
   return NP_OK;
 }
 

@@ -1621,7 +1621,7 @@ static int run_device(const DeviceIndex* ix, CallState* cs, const float* d_q, co
   return NP_OK;
 }
 
-// ---- a context checked out by a call path outside the search pass (np_scan.hip) --------------------------------------
+// ---- a context checked out by a host entry point outside the search pass, its scope and its result staging -------------
 int ContextUse::begin(const DeviceIndex* index, void* user_stream) {
   ix = index;
   NP_TRY(acquire_context(ix, &ctx));
@@ -1653,6 +1653,54 @@ ContextUse::~ContextUse() {
   if (ctx) release_context(ix, ctx);
 }
 
+int HostScope::resolve(const DeviceIndex* ix, ContextUse& use, const int64_t* subset_ids, const int64_t* subset_offsets,
+                       int64_t n_subsets, const int32_t* query_subset, const np_filter* filters, int B_) {
+  ids = subset_ids;
+  off = subset_offsets;
+  qsub = query_subset;
+  n = n_subsets;
+  B = B_;
+  any = any_scoped(query_subset, n_subsets, B);
+  resident = any && filters;
+  if (resident) {
+    NP_TRY(filter_eval_resident(ix, use.stream, use.filter_scratch(), use.filter_csr(), filters, (int32_t)n, qsub, B, &csr));
+    off = csr.h_off.data();
+  }
+  total = any ? off[n] : 0;
+  return NP_OK;
+}
+
+int HostScope::place(Carver& carve, hipStream_t st, CallSubsets* sub) const {
+  *sub = CallSubsets();
+  if (!any) return NP_OK;
+  if (resident) {
+    *sub = CallSubsets::device(csr.d_ids, csr.d_off, off, n, csr.d_qsub, qsub);
+    return NP_OK;
+  }
+  int64_t* d_ids = (int64_t*)carve.take((size_t)std::max<int64_t>(total, 1) * 8);
+  int64_t* d_off = (int64_t*)carve.take((size_t)(n + 1) * 8);
+  int32_t* d_qsub = (int32_t*)carve.take((size_t)B * 4);
+  if (total > 0) NP_HIP(hipMemcpyAsync(d_ids, ids, (size_t)total * 8, hipMemcpyHostToDevice, st));
+  NP_HIP(hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+  NP_HIP(hipMemcpyAsync(d_qsub, qsub, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  *sub = CallSubsets::device(d_ids, d_off, off, n, d_qsub, qsub);
+  return NP_OK;
+}
+
+int ResultStage::fetch(void* pinned, hipStream_t st) {
+  pin = (char*)pinned;
+  NP_HIP(hipMemcpyAsync(pin, d_ids, n * 8, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_ids, d_sc, n * 4, hipMemcpyDeviceToHost, st));
+  NP_HIP(hipMemcpyAsync(pin + o_ids + o_sc, d_cnt, B * 4, hipMemcpyDeviceToHost, st));
+  return NP_OK;
+}
+
+void ResultStage::deliver(int64_t* out_ids, float* out_scores, int32_t* out_counts) const {
+  memcpy(out_ids, pin, n * 8);
+  memcpy(out_scores, pin + o_ids, n * 4);
+  memcpy(out_counts, pin + o_ids + o_sc, B * 4);
+}
+
 int subset_doc_rows(const DeviceIndex* ix, hipStream_t st, const int64_t* d_ids, const int64_t* d_off, const int32_t* d_qsub,
                     int64_t n_subsets, int64_t total, int64_t lo, int64_t hi, int B, int64_t NW, uint32_t* docbits,
                     int32_t* qrow) {
@@ -1667,19 +1715,19 @@ int subset_doc_rows(const DeviceIndex* ix, hipStream_t st, const int64_t* d_ids,
 }
 
 int search_batch_in_use(const DeviceIndex* ix, ContextUse& use, const float* d_q, const int32_t* d_qoff, const int32_t* h_qoff,
-                        int B, int dim, const np_search_params* prm, const int64_t* d_ids, const int64_t* d_off,
-                        const int64_t* h_off, int64_t n_subsets, const int32_t* d_qsub, const int32_t* h_qsub,
-                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts) {
+                        int B, int dim, const np_search_params* prm, const CallSubsets& scope, int64_t* d_out_ids,
+                        float* d_out_scores, int32_t* d_out_counts) {
   NP_TRY(validate(ix, B, dim, prm));
   if (B == 0) return NP_OK;
   Subsets sub;
-  if (n_subsets > 0) {   // what np_hip_search_batch_subsets tells its pass
-    bool all_empty = h_off && h_qsub;
-    for (int b = 0; all_empty && b < B; ++b) all_empty = h_qsub[b] >= 0 && h_off[h_qsub[b] + 1] == h_off[h_qsub[b]];
-    sub.d = SubsetsP{d_ids, d_off, d_qsub, n_subsets, h_off[n_subsets]};
+  if (scope.any()) {   // what np_hip_search_batch_subsets tells its pass
+    bool all_empty = scope.h_off && scope.h_qsub;
+    for (int b = 0; all_empty && b < B; ++b)
+      all_empty = scope.h_qsub[b] >= 0 && scope.h_off[scope.h_qsub[b] + 1] == scope.h_off[scope.h_qsub[b]];
+    sub.d = SubsetsP{scope.d_ids, scope.d_off, scope.d_qsub, scope.n, scope.total};
     sub.all_empty = all_empty;
-    sub.h_off = h_off;
-    sub.h_qsub = h_qsub;
+    sub.h_off = scope.h_off;
+    sub.h_qsub = scope.h_qsub;
   }
   CallState cs;
   cs.ctx = use.ctx;
@@ -1972,8 +2020,7 @@ int np_hip_search_batch_filtered(const np_index* ix, const float* queries, const
   NP_TRY(filter_check_call(ix, filters, n_filters, query_filter, B, true));
   if (B == 0) return NP_OK;
   // as in np_hip_search_batch_subsets: a batch none of whose queries has a filter is a batch without subsets
-  bool any = false;
-  for (int b = 0; n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
+  const bool any = any_scoped(query_filter, n_filters, B);
   const FilterCall fc{filters, n_filters, query_filter};
   return search_batch_host(ix, queries, q_tok_offsets, B, dim, params, HostSubsets{}, out_ids, out_scores, out_counts, stats,
                            any ? &fc : nullptr);
@@ -2006,13 +2053,12 @@ int np_hip_search_batch_subsets(const np_index* ix, const float* queries, const 
   HostSubsets hs;
   // what the host can see: a batch none of whose queries has a subset is a batch without subsets, and one whose queries all
   // search empty subsets has no candidates at all
-  bool any = false, all_empty = true;
+  bool all_empty = true;
   for (int b = 0; n_subsets > 0 && b < B; ++b) {
     const int32_t q = query_subset[b];
-    any = any || q >= 0;
     all_empty = all_empty && q >= 0 && subset_offsets[q + 1] == subset_offsets[q];
   }
-  if (any) {
+  if (any_scoped(query_subset, n_subsets, B)) {
     hs.sub.d = SubsetsP{subset_ids, subset_offsets, query_subset, n_subsets, subset_offsets[n_subsets]};
     hs.sub.all_empty = all_empty;
     hs.sub.h_off = subset_offsets;

@@ -551,7 +551,6 @@ __global__ void __launch_bounds__(TEXT_TPB) fuse_kernel(FuseP p) {
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static int text_check_handle(const DeviceIndex* ix, bool need_text) {
   if (!ix) {
@@ -651,15 +650,6 @@ struct TextProg {
   }
 };
 
-struct TextSubsets {
-  const int64_t* d_ids = nullptr;
-  const int64_t* d_off = nullptr;
-  const int32_t* d_qsub = nullptr;
-  int64_t n = 0, total = 0;
-  const int64_t* h_off = nullptr;    // host copies where the caller has them
-  const int32_t* h_qsub = nullptr;
-};
-
 // bytes of the arena that scale with the chunk's queries -- one expression for the plan and for the carve-up
 static int64_t text_per_query(const DeviceIndex* ix, int top_k, bool subsets) {
   const int64_t NW = std::max<int64_t>((ix->n_docs + 31) / 32, 1);
@@ -754,7 +744,7 @@ struct TextCounts {
 // Sharded (counts != NULL): the hit counts of the counted phrases cross the ranks before the idf is computed, d_out_keys receives
 // the f64 bits of the scores and the ids leave as global ids.
 static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pin, const TextPlan& plan, TextProg& prog, int top_k,
-                    const TextSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited,
+                    const CallSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited,
                     unsigned long long* d_out_keys = nullptr, TextCounts* counts = nullptr) {
   hipStream_t st = use.stream;
   const DeviceText& tx = ix->text;
@@ -764,22 +754,17 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
   const int Q = plan.queries;
   const int64_t S = plan.slices, n_slices = text_n_slices(ix);
   const int keep = (int)text_slice_keep(top_k);
-  char* at = base;
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += up256(bytes);
-    return r;
-  };
-  char* d_prog = take(prog.bytes);
-  unsigned long long* ctr = (unsigned long long*)take(8);
-  unsigned long long* best_keys = (unsigned long long*)take((size_t)Q * up256((size_t)top_k * 8));
-  int32_t* best_ids = (int32_t*)take((size_t)Q * up256((size_t)top_k * 4));
-  int32_t* best_cnt = (int32_t*)take((size_t)Q * 4);
-  int32_t* qrow = (int32_t*)take((size_t)Q * 4);
-  uint32_t* docbits = subsets ? (uint32_t*)take((size_t)Q * up256((size_t)NW * 4)) : nullptr;
-  unsigned long long* list_keys = (unsigned long long*)take((size_t)Q * S * keep * 8);
-  int32_t* list_ids = (int32_t*)take((size_t)Q * S * keep * 4);
-  int32_t* list_cnt = (int32_t*)take((size_t)Q * S * 4);
+  Carver carve{base};
+  char* d_prog = carve.take(prog.bytes);
+  unsigned long long* ctr = (unsigned long long*)carve.take(8);
+  unsigned long long* best_keys = (unsigned long long*)carve.take((size_t)Q * up256((size_t)top_k * 8));
+  int32_t* best_ids = (int32_t*)carve.take((size_t)Q * up256((size_t)top_k * 4));
+  int32_t* best_cnt = (int32_t*)carve.take((size_t)Q * 4);
+  int32_t* qrow = (int32_t*)carve.take((size_t)Q * 4);
+  uint32_t* docbits = subsets ? (uint32_t*)carve.take((size_t)Q * up256((size_t)NW * 4)) : nullptr;
+  unsigned long long* list_keys = (unsigned long long*)carve.take((size_t)Q * S * keep * 8);
+  int32_t* list_ids = (int32_t*)carve.take((size_t)Q * S * keep * 4);
+  int32_t* list_cnt = (int32_t*)carve.take((size_t)Q * S * 4);
   const TextIxP tp{tx.post_off.get(), tx.post_doc.get(), tx.post_tf.get(), tx.post_first.get(), tx.pos.get(), tx.doc_len.get()};
   // the programs (everything before the hit counts), then the idf once every nHit is known
   char* src = prog.blob.data();
@@ -908,70 +893,32 @@ static int text_host(const np_index* ix, const np_text_query* queries, int32_t B
     return NP_ERR_INVALID_ARGUMENT;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  bool any = false;
-  for (int b = 0; n_subsets > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
-  const bool resident = any && filters;
   TextProg prog;
   prog.build(ix, queries, B);
   DeviceGuard g(ix->device);
   ContextUse use;
   NP_TRY(use.begin(ix, nullptr));
   hipStream_t st = use.stream;
-  FilterCsr csr;
-  if (resident) {
-    NP_TRY(filter_eval_resident(ix, st, use.filter_scratch(), use.filter_csr(), filters, (int32_t)n_subsets, query_subset, B, &csr));
-    subset_offsets = csr.h_off.data();
-  }
-  const int64_t total = any ? subset_offsets[n_subsets] : 0;
-  const bool staged = any && !resident;
-  const size_t b_ids = staged ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = staged ? up256((size_t)(n_subsets + 1) * 8) : 0;
-  const size_t b_qsub = staged ? up256((size_t)B * 4) : 0;
-  const size_t o_ids = up256((size_t)B * top_k * 8), o_sc = up256((size_t)B * top_k * 4), o_cnt = up256((size_t)B * 4);
-  const size_t user = b_ids + b_off + b_qsub + o_ids + o_sc + o_cnt;
+  HostScope scope;
+  NP_TRY(scope.resolve(ix, use, subset_ids, subset_offsets, n_subsets, query_subset, filters, B));
+  ResultStage res(B, top_k);
+  const size_t user = scope.stage_bytes() + res.bytes();
   TextPlan plan;
-  NP_TRY(text_plan_for(ix, (int64_t)user + (resident ? total * 8 : 0), prog, B, top_k, any, &plan));
-  NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, top_k, any)));
-  void* pinv = nullptr;
-  NP_TRY(use.pin(o_ids + o_sc + o_cnt + prog.bytes, &pinv));
-  char* at = use.arena().as<char>();
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += bytes;
-    return r;
-  };
-  TextSubsets sub;
-  if (resident) {
-    sub.d_ids = csr.d_ids;
-    sub.d_off = csr.d_off;
-    sub.d_qsub = csr.d_qsub;
-  } else if (any) {
-    sub.d_ids = (const int64_t*)take(b_ids);
-    sub.d_off = (const int64_t*)take(b_off);
-    sub.d_qsub = (const int32_t*)take(b_qsub);
-    if (total > 0) NP_HIP(hipMemcpyAsync((void*)sub.d_ids, subset_ids, (size_t)total * 8, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemcpyAsync((void*)sub.d_off, subset_offsets, (size_t)(n_subsets + 1) * 8, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemcpyAsync((void*)sub.d_qsub, query_subset, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  }
-  if (any) {
-    sub.n = n_subsets;
-    sub.total = total;
-    sub.h_off = subset_offsets;
-    sub.h_qsub = query_subset;
-  }
-  int64_t* d_ids = (int64_t*)take(o_ids);
-  float* d_sc = (float*)take(o_sc);
-  int32_t* d_cnt = (int32_t*)take(o_cnt);
-  char* pin = (char*)pinv;
+  NP_TRY(text_plan_for(ix, (int64_t)user + scope.budget_extra(), prog, B, top_k, scope.any, &plan));
+  NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, top_k, scope.any)));
+  void* pin = nullptr;   // the results, the programs behind them
+  NP_TRY(use.pin(res.bytes() + prog.bytes, &pin));
+  Carver carve{use.arena().as<char>()};
+  CallSubsets sub;
+  NP_TRY(scope.place(carve, st, &sub));
+  res.carve(carve);
   int64_t visited = 0;
-  NP_TRY(text_run(ix, use, at, pin + o_ids + o_sc + o_cnt, plan, prog, top_k, sub, d_ids, d_sc, d_cnt, stats ? &visited : nullptr));
-  NP_HIP(hipMemcpyAsync(pin, d_ids, (size_t)B * top_k * 8, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_ids, d_sc, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_ids + o_sc, d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  NP_TRY(text_run(ix, use, carve.at, (char*)pin + res.bytes(), plan, prog, top_k, sub, res.d_ids, res.d_sc, res.d_cnt,
+                  stats ? &visited : nullptr));
+  NP_TRY(res.fetch(pin, st));
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
-  memcpy(out_ids, pin, (size_t)B * top_k * 8);
-  memcpy(out_scores, pin + o_ids, (size_t)B * top_k * 4);
-  memcpy(out_counts, pin + o_ids + o_sc, (size_t)B * 4);
+  res.deliver(out_ids, out_scores, out_counts);
   if (stats) {
     stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats->n_queries = B;
@@ -1058,7 +1005,7 @@ static int64_t text_counted_phrases(const np_text_query* queries, int B) {
 //   local scoring with the global idf and average length -> the shard's top-k as f64 keys and global ids
 //   per exchange (np_dist_plan.h cuts the batch by B and top_k alone): all-gather of keys | ids | counts | status,
 //   text_rank_merge_kernel into the caller's buffers
-static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_query* queries, int B, int top_k, const TextSubsets& sub,
+static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_query* queries, int B, int top_k, const CallSubsets& sub,
                                int rc0, const char* msg0, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
                                hipStream_t st) {
   DeviceGuard g(ix->device);
@@ -1155,24 +1102,6 @@ static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_que
     }
   }
   return finish(rc);
-}
-
-// the device CSR of a sharded call as the keyword pass takes it
-static TextSubsets text_device_subsets(const int64_t* d_ids, const int64_t* d_off, const int64_t* h_off, int64_t n_subsets,
-                                       const int32_t* d_qsub, const int32_t* h_qsub) {
-  TextSubsets sub;
-  if (n_subsets > 0) {
-    sub.d_ids = d_ids;
-    sub.d_off = d_off;
-    sub.d_qsub = d_qsub;
-    sub.n = n_subsets;
-    sub.total = h_off[n_subsets];
-    if (h_qsub) {
-      sub.h_off = h_off;
-      sub.h_qsub = h_qsub;
-    }
-  }
-  return sub;
 }
 
 }  // namespace np
@@ -1298,14 +1227,7 @@ int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, 
     set_error("Text search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  TextSubsets sub;
-  if (n_subsets > 0) {
-    sub.d_ids = d_subset_ids;
-    sub.d_off = d_subset_offsets;
-    sub.d_qsub = d_query_subset;
-    sub.n = n_subsets;
-    sub.total = h_subset_offsets[n_subsets];
-  }
+  const CallSubsets sub = CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset);
   TextProg prog;
   prog.build(ix, queries, B);
   DeviceGuard g(ix->device);
@@ -1358,10 +1280,10 @@ int np_hip_fuse(const np_index* ix, int32_t mode, float alpha, int32_t top_k, in
                 sem_stride, kw_stride);
       return NP_ERR_INVALID_ARGUMENT;
     }
-  const size_t n_s = (size_t)B * sem_stride, n_k = (size_t)B * kw_stride, n_o = (size_t)B * top_k;
+  const size_t n_s = (size_t)B * sem_stride, n_k = (size_t)B * kw_stride;
   const size_t b_si = up256(n_s * 8), b_ss = up256(n_s * 4), b_ki = up256(n_k * 8), b_ks = up256(n_k * 4), b_c = up256((size_t)B * 4);
-  const size_t o_i = up256(n_o * 8), o_s = up256(n_o * 4);
-  const size_t dev_bytes = b_si + b_ss + b_ki + b_ks + 3 * b_c + o_i + o_s;
+  ResultStage res(B, top_k);
+  const size_t dev_bytes = b_si + b_ss + b_ki + b_ks + 2 * b_c + res.bytes();
   // with a handle: its device, a context's stream, arena and pinned staging; without: the current device, the call's own
   int device = 0;
   if (ix) device = ix->device; else (void)hipGetDevice(&device);
@@ -1370,32 +1292,26 @@ int np_hip_fuse(const np_index* ix, int32_t mode, float alpha, int32_t top_k, in
   DevPtr<char> own;
   std::vector<char> own_host;
   hipStream_t st = nullptr;
-  void* pinv = nullptr;
-  char* at = nullptr;
+  void* pin = nullptr;
+  Carver carve{nullptr};
   if (ix) {
     NP_TRY(use.begin(ix, nullptr));
     st = use.stream;
     NP_TRY(use.arena().reserve(dev_bytes));
-    NP_TRY(use.pin(o_i + o_s + b_c, &pinv));
-    at = use.arena().as<char>();
+    NP_TRY(use.pin(res.bytes(), &pin));
+    carve.at = use.arena().as<char>();
   } else {
     NP_TRY(own.alloc(dev_bytes));
-    own_host.resize(o_i + o_s + b_c);
-    pinv = own_host.data();
-    at = own.get();
+    own_host.resize(res.bytes());
+    pin = own_host.data();
+    carve.at = own.get();
   }
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += bytes;
-    return r;
-  };
-  int64_t* d_si = (int64_t*)take(b_si);
-  float* d_ss = (float*)take(b_ss);
-  int64_t* d_ki = (int64_t*)take(b_ki);
-  float* d_ks = (float*)take(b_ks);
-  int32_t *d_sc = (int32_t*)take(b_c), *d_kc = (int32_t*)take(b_c), *d_oc = (int32_t*)take(b_c);
-  int64_t* d_oi = (int64_t*)take(o_i);
-  float* d_os = (float*)take(o_s);
+  int64_t* d_si = (int64_t*)carve.take(b_si);
+  float* d_ss = (float*)carve.take(b_ss);
+  int64_t* d_ki = (int64_t*)carve.take(b_ki);
+  float* d_ks = (float*)carve.take(b_ks);
+  int32_t *d_sc = (int32_t*)carve.take(b_c), *d_kc = (int32_t*)carve.take(b_c);
+  res.carve(carve);
   // pageable sources: the copies complete before the call returns (it synchronises below)
   if (n_s > 0) NP_HIP(hipMemcpyAsync(d_si, sem_ids, n_s * 8, hipMemcpyHostToDevice, st));
   if (n_s > 0 && sem_scores) NP_HIP(hipMemcpyAsync(d_ss, sem_scores, n_s * 4, hipMemcpyHostToDevice, st));
@@ -1404,16 +1320,11 @@ int np_hip_fuse(const np_index* ix, int32_t mode, float alpha, int32_t top_k, in
   NP_HIP(hipMemcpyAsync(d_sc, sem_counts, (size_t)B * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(d_kc, kw_counts, (size_t)B * 4, hipMemcpyHostToDevice, st));
   NP_TRY(fuse_launch(st, mode, alpha, top_k, B, d_si, sem_scores ? d_ss : nullptr, d_sc, sem_stride, d_ki, kw_scores ? d_ks : nullptr,
-                     d_kc, kw_stride, d_oi, d_os, d_oc));
-  char* pin = (char*)pinv;
-  NP_HIP(hipMemcpyAsync(pin, d_oi, n_o * 8, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_i, d_os, n_o * 4, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_i + o_s, d_oc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+                     d_kc, kw_stride, res.d_ids, res.d_sc, res.d_cnt));
+  NP_TRY(res.fetch(pin, st));
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
-  memcpy(out_ids, pin, n_o * 8);
-  memcpy(out_scores, pin + o_i, n_o * 4);
-  memcpy(out_counts, pin + o_i + o_s, (size_t)B * 4);
+  res.deliver(out_ids, out_scores, out_counts);
   return NP_OK;
 }
 
@@ -1452,88 +1363,45 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
   sem.top_k = fetch_k;
   const int top_k = params->top_k;
   const auto t0 = std::chrono::steady_clock::now();
-  bool any = false;
-  for (int b = 0; n_subsets > 0 && b < B; ++b) any = any || query_subset[b] >= 0;
-  const bool resident = any && filters;
   TextProg prog;
   prog.build(ix, text_queries, B);
   DeviceGuard g(ix->device);
   ContextUse use;
   NP_TRY(use.begin(ix, nullptr));
   hipStream_t st = use.stream;
-  if (B == 0) return search_batch_in_use(ix, use, nullptr, nullptr, nullptr, 0, dim, &sem, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                                         nullptr, nullptr, nullptr);   // (the semantic call's own checks)
-  FilterCsr csr;
-  if (resident) {
-    NP_TRY(filter_eval_resident(ix, st, use.filter_scratch(), use.filter_csr(), filters, n_filters, query_subset, B, &csr));
-    subset_offsets = csr.h_off.data();
-  }
-  const int64_t total = any ? subset_offsets[n_subsets] : 0;
+  if (B == 0)   // (the semantic call's own checks)
+    return search_batch_in_use(ix, use, nullptr, nullptr, nullptr, 0, dim, &sem, CallSubsets(), nullptr, nullptr, nullptr);
+  HostScope scope;
+  NP_TRY(scope.resolve(ix, use, subset_ids, subset_offsets, n_subsets, query_subset, filters, B));
   const int64_t ntok = q_tok_offsets[B];
-  const bool staged = any && !resident;
   const size_t b_q = up256((size_t)std::max<int64_t>(ntok, 1) * dim * 4), b_qoff = up256((size_t)(B + 1) * 4);
-  const size_t b_ids = staged ? up256((size_t)std::max<int64_t>(total, 1) * 8) : 0, b_off = staged ? up256((size_t)(n_subsets + 1) * 8) : 0;
-  const size_t b_qsub = staged ? up256((size_t)B * 4) : 0;
-  const size_t l_ids = up256((size_t)B * fetch_k * 8), l_sc = up256((size_t)B * fetch_k * 4), b_cnt = up256((size_t)B * 4);
-  const size_t o_ids = up256((size_t)B * top_k * 8), o_sc = up256((size_t)B * top_k * 4);
-  const size_t user = b_q + b_qoff + b_ids + b_off + b_qsub + 2 * (l_ids + l_sc + b_cnt) + o_ids + o_sc + b_cnt;
+  ResultStage sem_l(B, fetch_k), kw_l(B, fetch_k), res(B, top_k);   // the two lists stay on the device
+  const size_t user = b_q + b_qoff + scope.stage_bytes() + sem_l.bytes() + kw_l.bytes() + res.bytes();
   TextPlan plan;
-  NP_TRY(text_plan_for(ix, (int64_t)user + (resident ? total * 8 : 0), prog, B, fetch_k, any, &plan));
-  NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, fetch_k, any)));
-  void* pinv = nullptr;
-  NP_TRY(use.pin(o_ids + o_sc + b_cnt + prog.bytes, &pinv));
-  char* at = use.arena().as<char>();
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += bytes;
-    return r;
-  };
-  float* d_q = (float*)take(b_q);
-  int32_t* d_qoff = (int32_t*)take(b_qoff);
-  TextSubsets sub;
-  if (resident) {
-    sub.d_ids = csr.d_ids;
-    sub.d_off = csr.d_off;
-    sub.d_qsub = csr.d_qsub;
-  } else if (any) {
-    sub.d_ids = (const int64_t*)take(b_ids);
-    sub.d_off = (const int64_t*)take(b_off);
-    sub.d_qsub = (const int32_t*)take(b_qsub);
-    if (total > 0) NP_HIP(hipMemcpyAsync((void*)sub.d_ids, subset_ids, (size_t)total * 8, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemcpyAsync((void*)sub.d_off, subset_offsets, (size_t)(n_subsets + 1) * 8, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemcpyAsync((void*)sub.d_qsub, query_subset, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  }
-  if (any) {
-    sub.n = n_subsets;
-    sub.total = total;
-    sub.h_off = subset_offsets;
-    sub.h_qsub = query_subset;
-  }
-  int64_t* s_ids = (int64_t*)take(l_ids);
-  float* s_sc = (float*)take(l_sc);
-  int32_t* s_cnt = (int32_t*)take(b_cnt);
-  int64_t* k_ids = (int64_t*)take(l_ids);
-  float* k_sc = (float*)take(l_sc);
-  int32_t* k_cnt = (int32_t*)take(b_cnt);
-  int64_t* d_ids = (int64_t*)take(o_ids);
-  float* d_sc = (float*)take(o_sc);
-  int32_t* d_cnt = (int32_t*)take(b_cnt);
+  NP_TRY(text_plan_for(ix, (int64_t)user + scope.budget_extra(), prog, B, fetch_k, scope.any, &plan));
+  NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, fetch_k, scope.any)));
+  void* pin = nullptr;   // the results, the keyword programs behind them
+  NP_TRY(use.pin(res.bytes() + prog.bytes, &pin));
+  Carver carve{use.arena().as<char>()};
+  float* d_q = (float*)carve.take(b_q);
+  int32_t* d_qoff = (int32_t*)carve.take(b_qoff);
+  CallSubsets sub;
+  NP_TRY(scope.place(carve, st, &sub));
+  sem_l.carve(carve);
+  kw_l.carve(carve);
+  res.carve(carve);
   if (ntok > 0) NP_HIP(hipMemcpyAsync(d_q, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-  NP_TRY(search_batch_in_use(ix, use, d_q, d_qoff, q_tok_offsets, B, dim, &sem, sub.d_ids, sub.d_off, sub.h_off, sub.n, sub.d_qsub,
-                             sub.h_qsub, s_ids, s_sc, s_cnt));
-  char* pin = (char*)pinv;
+  NP_TRY(search_batch_in_use(ix, use, d_q, d_qoff, q_tok_offsets, B, dim, &sem, sub, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt));
   int64_t visited = 0;
-  NP_TRY(text_run(ix, use, at, pin + o_ids + o_sc + b_cnt, plan, prog, fetch_k, sub, k_ids, k_sc, k_cnt, stats ? &visited : nullptr));
-  NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, s_ids, s_sc, s_cnt, fetch_k, k_ids, k_sc, k_cnt, fetch_k, d_ids, d_sc, d_cnt));
-  NP_HIP(hipMemcpyAsync(pin, d_ids, (size_t)B * top_k * 8, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_ids, d_sc, (size_t)B * top_k * 4, hipMemcpyDeviceToHost, st));
-  NP_HIP(hipMemcpyAsync(pin + o_ids + o_sc, d_cnt, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+  NP_TRY(text_run(ix, use, carve.at, (char*)pin + res.bytes(), plan, prog, fetch_k, sub, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt,
+                  stats ? &visited : nullptr));
+  NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt, fetch_k, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, fetch_k,
+                     res.d_ids, res.d_sc, res.d_cnt));
+  NP_TRY(res.fetch(pin, st));
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
-  memcpy(out_ids, pin, (size_t)B * top_k * 8);
-  memcpy(out_scores, pin + o_ids, (size_t)B * top_k * 4);
-  memcpy(out_counts, pin + o_ids + o_sc, (size_t)B * 4);
+  res.deliver(out_ids, out_scores, out_counts);
   if (stats) {
     stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats->n_queries = B;
@@ -1552,17 +1420,8 @@ int np_hip_text_search_sharded(const np_index* ix, np_comm* c, const np_text_que
   if (B == 0) return NP_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   return text_sharded_locked(ix, c, queries, B, top_k,
-                             text_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, nullptr),
-                             NP_OK, nullptr, d_out_ids, d_out_scores, d_out_counts, (hipStream_t)stream);
-}
-
-// the arguments of a sharded call's filters that need no handle
-static int check_sharded_filters(const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int B) {
-  if (n_filters < 0 || (n_filters > 0 && (!filters || (B > 0 && !query_filter)))) {
-    set_error("Filter failed: negative n_filters, or filters without programs or a query map");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  return NP_OK;
+                             CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset), NP_OK,
+                             nullptr, d_out_ids, d_out_scores, d_out_counts, (hipStream_t)stream);
 }
 
 int np_hip_text_search_sharded_filtered(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
@@ -1570,20 +1429,14 @@ int np_hip_text_search_sharded_filtered(const np_index* ix, np_comm* c, const np
                                         int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream) {
   clear_error();
   NP_TRY(text_check_sharded_args(ix, c, queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
-  NP_TRY(check_sharded_filters(filters, n_filters, query_filter, B));
+  NP_TRY(check_sharded_filters("Filter failed", filters, n_filters, query_filter, B));
   if (B == 0) return NP_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(ix->device);
-  bool any = false;
-  for (int b = 0; n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
-  FilterCsr csr;   // (nHit never looks at the scope: the keyword pass needs no global lengths)
-  const int rc0 = any ? shard_filters_eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B, &csr) : NP_OK;
-  const std::string msg0 = rc0 != NP_OK ? np_hip_last_error() : "";
-  const TextSubsets sub = any && rc0 == NP_OK
-                              ? text_device_subsets(csr.d_ids, csr.d_off, csr.h_off.data(), n_filters, csr.d_qsub, query_filter)
-                              : TextSubsets{};
-  return text_sharded_locked(ix, c, queries, B, top_k, sub, rc0, msg0.c_str(), d_out_ids, d_out_scores, d_out_counts,
-                             (hipStream_t)stream);
+  ShardFilterScope scope;   // (nHit never looks at the scope: the keyword pass needs no global lengths)
+  scope.eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B);
+  return text_sharded_locked(ix, c, queries, B, top_k, scope.call(), scope.rc0, scope.msg0.c_str(), d_out_ids, d_out_scores,
+                             d_out_counts, (hipStream_t)stream);
 }
 
 int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
@@ -1602,7 +1455,7 @@ int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_
   NP_TRY(text_check_sharded_args(ix, c, text_queries, B, fetch_k, d_out_ids, d_out_scores, d_out_counts, stream));
   NP_TRY(fuse_check(fusion, alpha, params->top_k, B, fetch_k, fetch_k));
   if (filters)
-    NP_TRY(check_sharded_filters(filters, n_filters, query_filter, B));
+    NP_TRY(check_sharded_filters("Filter failed", filters, n_filters, query_filter, B));
   else
     NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
   if (B > 0 && (!d_queries || !d_q_tok_offsets || !h_q_tok_offsets)) {
@@ -1617,58 +1470,31 @@ int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(ix->device);
   // the two global lists, [B][fetch_k] each, stay in the communicator
-  const size_t l_ids = up256((size_t)B * fetch_k * 8), l_sc = up256((size_t)B * fetch_k * 4), b_cnt = up256((size_t)B * 4);
-  NP_TRY(c->lists.reserve(2 * (l_ids + l_sc + b_cnt)));
-  char* at = c->lists.as<char>();
-  auto take = [&](size_t bytes) {
-    char* r = at;
-    at += bytes;
-    return r;
-  };
-  int64_t* s_ids = (int64_t*)take(l_ids);
-  float* s_sc = (float*)take(l_sc);
-  int32_t* s_cnt = (int32_t*)take(b_cnt);
-  int64_t* k_ids = (int64_t*)take(l_ids);
-  float* k_sc = (float*)take(l_sc);
-  int32_t* k_cnt = (int32_t*)take(b_cnt);
+  ResultStage sem_l(B, fetch_k), kw_l(B, fetch_k);
+  NP_TRY(c->lists.reserve(sem_l.bytes() + kw_l.bytes()));
+  Carver carve{c->lists.as<char>()};
+  sem_l.carve(carve);
+  kw_l.carve(carve);
   // the scope: the caller's CSR, or the filters over this shard's columns with their local lengths for the probe scaling
-  bool any = false;
-  for (int b = 0; filters && n_filters > 0 && b < B; ++b) any = any || query_filter[b] >= 0;
-  FilterCsr csr;
-  int rc0 = NP_OK;
-  std::string msg0;
-  std::vector<int64_t> zero, lens;
-  ShardSubsets ss{nullptr, -1, nullptr, nullptr, 0, nullptr};
-  TextSubsets sub;
-  if (any) {
-    rc0 = shard_filters_eval(ix, c, st, filters, n_filters, query_filter, B, &csr);
-    if (rc0 != NP_OK) msg0 = np_hip_last_error();
-    zero.assign((size_t)n_filters + 1, 0);
-    lens.assign((size_t)n_filters, 0);
-    if (rc0 == NP_OK) {
-      for (int32_t f = 0; f < n_filters; ++f) lens[(size_t)f] = csr.h_off[(size_t)f + 1] - csr.h_off[(size_t)f];
-      sub = text_device_subsets(csr.d_ids, csr.d_off, csr.h_off.data(), n_filters, csr.d_qsub, query_filter);
-    }
-    ss = ShardSubsets{csr.d_ids, 0, csr.d_off, rc0 == NP_OK ? csr.h_off.data() : zero.data(), n_filters, csr.d_qsub};
-    ss.h_local_lens = lens.data();
-  } else if (!filters && n_subsets > 0) {
-    ss = ShardSubsets{d_subset_ids, 0, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset};
-    sub = text_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, nullptr);
-  }
+  ShardFilterScope scope;
+  if (filters) scope.eval(ix, c, st, filters, n_filters, query_filter, B);
+  const CallSubsets sub =
+      filters ? scope.call() : CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset);
+  const ShardSubsets ss = filters ? scope.shard() : ShardSubsets::csr(sub);
   // With the host-side check a failed semantic pass has ended on every rank at the same exchange (each read the same status
   // words): all leave.  Otherwise the failing rank has returned its own error after taking part in every exchange, while its peers
   // carry on with an abandoned list: it still owes them the exchanges of the keyword pass, with empty data and its status.
-  const int rc_sem = search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, &sem, ss, s_ids, s_sc,
-                                                 s_cnt, stream, rc0, msg0.c_str());
+  const int rc_sem = search_batch_sharded_locked(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, &sem, ss, sem_l.d_ids,
+                                                 sem_l.d_sc, sem_l.d_cnt, stream, scope.rc0, scope.msg0.c_str());
   const std::string msg_sem = rc_sem != NP_OK ? np_hip_last_error() : "";
   if (rc_sem != NP_OK && c->host_check()) return rc_sem;
-  const int rc_kw = text_sharded_locked(ix, c, text_queries, B, fetch_k, sub, rc_sem, msg_sem.c_str(), k_ids, k_sc, k_cnt, st);
+  const int rc_kw = text_sharded_locked(ix, c, text_queries, B, fetch_k, sub, rc_sem, msg_sem.c_str(), kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, st);
   if (rc_kw != NP_OK) return rc_kw;
   // every rank holds both global lists: every rank fuses.  (An abandoned list carries count -1: the fusion clamps it to an empty
   // list, and the count that leaves is the abandoned one.)
-  NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, s_ids, s_sc, s_cnt, fetch_k, k_ids, k_sc, k_cnt, fetch_k, d_out_ids, d_out_scores,
-                     d_out_counts));
-  hybrid_abandon_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(s_cnt, k_cnt, B, d_out_counts);
+  NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt, fetch_k, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, fetch_k,
+                     d_out_ids, d_out_scores, d_out_counts));
+  hybrid_abandon_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(sem_l.d_cnt, kw_l.d_cnt, B, d_out_counts);
   NP_HIP(hipGetLastError());
   return NP_OK;
 }
