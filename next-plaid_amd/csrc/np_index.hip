@@ -667,8 +667,15 @@ static int choose_ublock_stride(DeviceIndex* ix) {
     while (q > 0 && over + h_hist[q] <= allow) over += h_hist[q--];   // q = the smallest capacity leaving <= 0.1 % outside
     fit = std::min(fit, std::max(q, 1));
   }
-  // the stride is a multiple of 64 bytes (blocks start on 64-B sectors: a 192-B block is three sectors, a 16-B aligned
-  // 208-B one 4.1 on average), at most 256 bytes
+  // the stride is a multiple of 64 bytes, at most 256 bytes (512 with the bit-plane hot level).  What a block costs the hot
+  // level is the 128-byte LINES it touches (every miss fetches a whole line: profiles/r05_fetch_probe.md), averaged over
+  // even and odd documents -- blocks start on multiples of 64 bytes, so a stride that is an odd multiple of 64 straddles one
+  // line more on every other document:
+  //   stride (bytes)    64    128   192   256   320   384   512
+  //   lines per block   1     1     2     2     3     3     4
+  // approx_hotp_kernel stages exactly the block (the lane of an LDS row's 16 padding bytes issues no request; while it
+  // fetched the next block's first 16 bytes the figures were 1.5, 2, 2.5, 3, 3.5, 4, 5: profiles/hot_block_lines.md).  The
+  // metric corpus' 192-byte blocks sit at their two-line floor; a one-line block there needs coded lists.
   const int per64 = (int)(64 / ix->code_bytes());
   ix->ublock_stride = std::max(per64, std::min(smax, (hdr + fit + per64 - 1) / per64 * per64));
   ix->ublock_hdr = hdr;

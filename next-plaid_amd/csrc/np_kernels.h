@@ -3840,8 +3840,18 @@ __global__ void __launch_bounds__(64 * WPB) approx_hotp_kernel(
     // the rows the NEXT instruction fills, issued later (loads return in order; slack spare bytes follow a wave's
     // last row).  Masking would put the loads behind an EXEC branch, and the compiler would then have to assume at every
     // later wait that they may not have been issued: the wait for a walk step's rows would wait for these blocks too.
+    // The lane of a row's 16 PADDING bytes (spiece == LPR - 1) takes the same out-of-range offset: zeros in the padding
+    // (which is what the zeroed rows above assume), no memory request.  Its in-range offset would be the first 16 bytes of
+    // the NEXT document's block, which nothing reads (the scan stops at fit - CPI, the window re-staging writes row
+    // offsets 16 .. 16 + fit codes, the walk reads the lane's own share) -- and memory is fetched in whole 128-byte lines
+    // (profiles/r05_fetch_probe.md: every miss is one), so those 16 bytes cost a line wherever block d + 1 starts one:
+    //   stride (bytes)                  64    128   192   256   320   384   512
+    //   lines per block, pad fetched    1.5   2     2.5   3     3.5   4     5
+    //   lines per block, as staged now  1     1     2     2     3     3     4     (= the lines the block occupies, averaged
+    // over even and odd documents).  Measured at 192 bytes: profiles/hot_block_lines.md.
     const int LPR = stride_b / 16 + 1;
     const int sslot = lane / LPR, spiece = lane - sslot * LPR;
+    const bool sload = sslot < DPI && spiece < LPR - 1;   // this lane fetches a piece of a block (not padding, not idle)
     auto stage = [&](uint32_t dv) {
       if (probe & 4) return;
       uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)dv, 0), d1 = (uint32_t)__builtin_amdgcn_readlane((int)dv, 63);
@@ -3855,7 +3865,7 @@ __global__ void __launch_bounds__(64 * WPB) approx_hotp_kernel(
 #pragma unroll
         for (int k = 0; k < DPW / DPI; ++k) {
           const uint32_t dj = (uint32_t)__shfl((int)dv, LPD * (k * DPI + sslot));   // the id of this lane's document (any lane of its group)
-          const uint32_t voff = sslot < DPI ? (dj - d0) * (uint32_t)stride_b + 16u * (uint32_t)spiece : 0xFFFFFFF0u;
+          const uint32_t voff = sload ? (dj - d0) * (uint32_t)stride_b + 16u * (uint32_t)spiece : 0xFFFFFFF0u;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, (lds_ptr)(s_rows + (size_t)k * DPI * row_b), 16, (int)voff, 0, 0, 0);
         }
       } else {

@@ -122,9 +122,10 @@ def tables():
               f"{d1['index_build_s']:.2f} s (1 M); {d10['hbm_bytes_per_token']:.1f} B per token. CPU baseline (oracle C restatement, {cb10['cores']} threads, "
               f"{cb10['cpu_model']}): {cb10['value']:.1f} queries/s at 10 M, {cb1['value']:.1f} at 1 M. `roofline.traffic` (PMC, 10 M): "
               f"S4 {tr['approx(S4)']/1e9:.2f} GB, S6 {tr['exact(S6)']/1e9:.2f} GB, S3 {tr['candidates(S3)']/1e9:.2f} GB per batch.", "",
-          f"Round 5 → round 6 (this path is untouched by the round's work, which went into the regimes without a threshold): 10 M documents 20.2 k → "
-          f"{d10['value']/1e3:.1f} k queries/s (p50 3.62 → {d10['p50_batch_latency_ms']:.2f} ms, S4 2.19 → "
-          f"{s10['ms_approx']:.2f} ms); 1 M documents 41.4 k → {d1['value']/1e3:.1f} k queries/s (S4 0.72 → {s1['ms_approx']:.2f} ms).  "
+          f"Round 6 (20.4 k queries/s, p50 3.64 ms, S4 2.20 ms at 10 M documents; 41.5 k, S4 0.72 ms at 1 M) → the hot level staging exactly "
+          f"its blocks, not the line behind them (`profiles/hot_block_lines.md`: this table's two lines are the `--full` runs of that note's calls): "
+          f"10 M documents {d10['value']/1e3:.1f} k queries/s (p50 {d10['p50_batch_latency_ms']:.2f} ms, S4 "
+          f"{s10['ms_approx']:.2f} ms); 1 M documents {d1['value']/1e3:.1f} k queries/s (S4 {s1['ms_approx']:.2f} ms).  "
           f"The bench line's `roofline.frac` prices the contract's algorithmic bytes ({d10['roofline']['frac']:.2f} for S4); the bytes the stage "
           f"really moved (PMC, every kernel of the stage) give `roofline.frac_physical` = {d10['roofline'].get('frac_physical')}; the dominant kernel "
           f"alone (`approx_hotp_kernel`, {d10['roofline']['dominant_kernel']['ms_per_launch']:.3f} ms by its own HIP events): "
@@ -225,7 +226,7 @@ def tables():
                    ("round 4: two levels, bit planes (6 % hot), exact level gathers every row (`NP_S4_WARM=1000`)", r4.get("warm1000_10m")),
                    ("round 4: two levels, bit planes + floored exact level (its default)", r4.get("default")),
                    ("**round 5** (table over the positive scores): single level (`--hot 0`)", var.get("single_level_10m")),
-                   ("**round 5: two levels, bit planes (6 % hot) + floored exact level: default**", d10)):
+                   ("**now: the same with the hot level staging exactly its blocks (`profiles/hot_block_lines.md`): default** (round 5: 148 M, 2.66 M, 2.20 ms, 20414)", d10)):
         if d:
             x = d["stages"]
             hs.append(f"| {lab} | {x['n_cand_codes']/1e6:.0f} M | {(x['n_level2'] or x['n_candidates'])/1e6:.2f} M | {x['ms_approx']:.2f} | {d['value']:.0f} |")
