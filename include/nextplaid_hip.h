@@ -669,6 +669,82 @@ int np_hip_search_hybrid(const np_index* index, const float* queries, const int3
                          const int32_t* query_subset, const np_filter* filters, int32_t n_filters,
                          int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
 
+/* ---- grouped search: top_k groups with their best documents ------------------------------------------
+ * Both applications of the crate index UNITS and answer in GROUPS: code units of a file, passages of a document.  ColGREP does
+ * it on the host (colgrep/src/index/mod.rs:4093-4292, collapse_by_file at :4394-4413): it over-fetches max(20 top_k, 200)
+ * results, walks them keeping the first unit of every file as its leader, folds later units of that file into it and stops at
+ * top_k distinct files.  Here the group of every document lives in HBM and the ranked list never leaves it.
+ *
+ * np_hip_index_set_groups gives every document of the WHOLE index a dense group id in [0, n_groups): a host array of n =
+ * num_documents i32, kept in HBM (its n * 4 bytes count in np_info.device_bytes; freed at close).  n = 0 drops the groups.
+ * NP_ERR_SHAPE: n != num_documents.  NP_ERR_INVALID_ARGUMENT, before any allocation: an id outside [0, n_groups), n_groups
+ * outside 1 .. 2^31-1, or a handle opened with shard_count > 1 (see "out of scope").  NP_ERR_OUT_OF_MEMORY leaves the previous
+ * groups in place.  Needs exclusive access to the handle, as np_hip_index_set_columns does.  A handle is immutable otherwise:
+ * a reload, an update or a delete opens a new handle, which has no groups (as it has no columns) until they are set again, so
+ * an array whose length differs from num_documents is never read.  np_hip_index_group_count: n_groups, 0 without groups.
+ *
+ * np_hip_collapse takes B ranked lists in np_hip_fuse's layout -- list b is ids / scores [b * stride .. b * stride +
+ * counts[b]), scores may be NULL, 1 <= stride <= NP_GROUP_MAX_LIST -- and walks each one:
+ *     for r in 0 .. counts[b]-1:   g = group of ids[b][r]
+ *         g admitted:                 total[g] += 1; if members[g] < group_size: append (id, score) to g
+ *         fewer than top_k admitted:  admit g with (id, score) as its leader; total[g] = members[g] = 1
+ *         otherwise:                  skip
+ * No score is read: the order of the list is the order.  Duplicate ids are separate entries.  Groups come in order of
+ * admission (their leaders' ranks), a group's members in list order:
+ *   out_ids      [B][top_k][group_size], padded with id 0 as np_hip_fuse pads
+ *   out_scores   likewise, the input's bits (a NaN keeps its payload), padded with 0; NULL when scores is NULL
+ *   out_group    [B][top_k] i32 the group id        out_members  [B][top_k] i32 members written, <= group_size
+ *   out_total    [B][top_k] i32 entries of the group in the whole list (what was folded = total - members)
+ *   out_counts   [B] groups admitted
+ * NP_ERR_INVALID_ARGUMENT before any launch: no groups set, top_k < 1, group_size < 1, top_k * group_size > 16384, a stride
+ * out of range; host form only: a count outside 0 .. stride, an id outside [0, num_documents).  The device form clamps a
+ * count to its stride and treats an id out of range as absent: skipped, and counted in no total.  The same bits from run to
+ * run, alone or in any batch: one workgroup per list sorts (group, rank) keys, positions come from scans and popcounts, no
+ * output atomics.
+ *
+ * np_hip_search_batch_grouped: np_hip_search_hybrid's arguments without the text part, plus pool_k and group_size.  Runs the
+ * search pass with top_k = pool_k (1 <= pool_k <= 16384) into scratch and collapses it to params->top_k groups on the same
+ * stream; neither the pool nor the lists leave HBM.  Query i gets, byte for byte, np_hip_collapse of what
+ * np_hip_search_batch_subsets (or _filtered) returns with top_k = pool_k.  stats: ms_total and n_queries.
+ * np_hip_search_hybrid_grouped: np_hip_search_hybrid fused to pool_k (1 <= pool_k <= 2 * NP_TEXT_MAX_TOPK), then collapsed:
+ * byte for byte the two calls composed.  This is ColGREP's request: fuse into the pool, collapse to top_k files.
+ *
+ * Out of scope:
+ *   sharded handles   a group's members can lie on several shards, and a member's shard-local group can fall outside that
+ *                     shard's local top_k groups while the group is in the global top_k: per-shard grouped lists do not merge
+ *                     exactly for group_size > 1.  The handle is refused, not approximated.
+ *   grouped search_exact beyond the pool   the true grouped top-k over all documents needs a per-query, per-group maximum table
+ *                     across scan passes and a second pass for members.  np_hip_collapse of np_hip_search_exact(top_k = pool_k)
+ *                     is available.
+ *   ColGREP's score adjustments   the path penalty, the boosts and the line-span merge are application code on at most 200
+ *                     rows; out_total and a large group_size give the host what it needs for the span. */
+#define NP_GROUP_MAX_LIST 16384
+int np_hip_index_set_groups(np_index* index, const int32_t* group_ids, int64_t n, int64_t n_groups);
+int64_t np_hip_index_group_count(const np_index* index);
+int np_hip_collapse(const np_index* index, int32_t top_k, int32_t group_size, int32_t B,
+                    const int64_t* ids, const float* scores, const int32_t* counts, int32_t stride,
+                    int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members, int32_t* out_total,
+                    int32_t* out_counts);
+int np_hip_collapse_device(const np_index* index, int32_t top_k, int32_t group_size, int32_t B,
+                           const int64_t* d_ids, const float* d_scores, const int32_t* d_counts, int32_t stride,
+                           int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_group, int32_t* d_out_members,
+                           int32_t* d_out_total, int32_t* d_out_counts, void* stream);
+int np_hip_search_batch_grouped(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                                const np_search_params* params,
+                                const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                                const int32_t* query_subset, const np_filter* filters, int32_t n_filters,
+                                int32_t pool_k, int32_t group_size,
+                                int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members,
+                                int32_t* out_total, int32_t* out_counts, np_stats* stats);
+int np_hip_search_hybrid_grouped(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                                 const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
+                                 int32_t fusion,
+                                 const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                                 const int32_t* query_subset, const np_filter* filters, int32_t n_filters,
+                                 int32_t pool_k, int32_t group_size,
+                                 int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members,
+                                 int32_t* out_total, int32_t* out_counts, np_stats* stats);
+
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best
  * n_sel = min(n_full_scores, max(n_full_scores/4, top_k)) candidates as 64-bit rank keys in

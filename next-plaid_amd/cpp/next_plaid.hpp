@@ -11,6 +11,7 @@
 //   index.search_batch_subsets(queries, n, params, parallel, subsets)   one subset per query (a server's batch of requests)
 //   index.search_exact(queries, n, top_k, precision, subset) / search_exact_subsets(...)   every document scored: the exact top-k
 //   index.set_text(...) / text_search(...) / fuse(...) / search_hybrid(...)   the keyword half of a hybrid search (text_search.rs)
+//   index.set_groups(...) / collapse(...) / search_grouped(...) / search_hybrid_grouped(...)   top-k groups with their best documents
 //   SearchParameters (defaults search.rs:58-69), QueryResult (search.rs:71-80), Error (error.rs:9-66)
 //
 // Accelerator policy (the crate's precedent for its CUDA feature, lib.rs:71-84 and cuda.rs:52-182):
@@ -753,6 +754,103 @@ class MmapIndex {
     return rows(ids, sc, cnt, n, k);
   }
 
+  // ---- grouped search (np_hip_index_set_groups and its kin; ColGREP's collapse_by_file on the device) -----------------------
+  // One group of a grouped result: its id, its first documents in list order (at most group_size) with their scores, and the
+  // number of the list's entries that belong to it (total - passage_ids.size() were folded).
+  struct Group {
+    int32_t group_id = 0;
+    std::vector<int64_t> passage_ids;
+    std::vector<float> scores;   // empty where the collapsed list had none
+    int32_t total = 0;
+  };
+  using GroupedResult = std::vector<Group>;   // of one query, in order of admission
+
+  // The group of every document of the WHOLE index: dense ids in [0, n_groups), kept in HBM.  An empty vector drops them.
+  // Needs exclusive access to the handle; a sharded handle is refused.  reload() / update() leave a handle without groups, as
+  // they leave it without columns.
+  void set_groups(const std::vector<int32_t>& group_ids, int64_t n_groups) {
+    require_device("set_groups");
+    check(np_hip_index_set_groups(h_, group_ids.empty() ? nullptr : group_ids.data(), (int64_t)group_ids.size(), n_groups));
+    check(np_hip_index_info(h_, &info_));
+  }
+  int64_t group_count() const { return h_ ? np_hip_index_group_count(h_) : 0; }
+
+  // np_hip_collapse: each ranked list walked to top_k groups of at most group_size documents.  with_scores = false passes no
+  // scores (the walk never reads one).
+  std::vector<GroupedResult> collapse(const std::vector<QueryResult>& lists, size_t top_k, size_t group_size,
+                                      bool with_scores = true) const {
+    require_device("collapse");
+    const size_t n = lists.size();
+    size_t w = 1;
+    for (const QueryResult& r : lists) w = std::max(w, r.passage_ids.size());
+    std::vector<int64_t> li(std::max<size_t>(n, 1) * w, 0);
+    std::vector<float> ls(std::max<size_t>(n, 1) * w, 0.f);
+    std::vector<int32_t> lc(std::max<size_t>(n, 1), 0);
+    for (size_t i = 0; i < n; ++i) {
+      std::copy(lists[i].passage_ids.begin(), lists[i].passage_ids.end(), li.begin() + i * w);
+      std::copy(lists[i].scores.begin(), lists[i].scores.end(), ls.begin() + i * w);
+      lc[i] = (int32_t)lists[i].passage_ids.size();
+    }
+    GroupBuffers b(n, top_k, group_size);
+    check(np_hip_collapse(h_, (int32_t)top_k, (int32_t)group_size, (int32_t)n, li.data(), with_scores ? ls.data() : nullptr, lc.data(),
+                          (int32_t)w, b.ids.data(), with_scores ? b.sc.data() : nullptr, b.group.data(), b.members.data(),
+                          b.total.data(), b.cnt.data()));
+    return b.groups(n, with_scores);
+  }
+
+  // np_hip_search_batch_grouped: the top params.top_k GROUPS with their best group_size documents -- the search pass with
+  // top_k = pool_k (0: ColGREP's max(20 top_k, 200), inside the index and the limit of 16384) and the collapse of its lists,
+  // on the device.  Query i gets collapse(search_batch(top_k = pool_k)).  One scope per query as search_hybrid takes them.
+  std::vector<GroupedResult> search_grouped(const Query* queries, size_t n, const SearchParameters& params, size_t group_size = 1,
+                                            size_t pool_k = 0,
+                                            const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("search_grouped");
+    if (!subsets.empty() && subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_grouped: one subset entry per query");
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
+    std::vector<int32_t> off;
+    std::vector<float> flat;
+    pack_queries(queries, n, off, flat);
+    const np_search_params p = params.c();
+    GroupBuffers b(n, params.top_k, group_size);
+    check(np_hip_search_batch_grouped(h_, flat.data(), off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, sids.data(), soff.data(),
+                                      (int64_t)n_distinct, qsub.data(), nullptr, 0,
+                                      (int32_t)(pool_k ? pool_k : default_pool_k(params.top_k, NP_GROUP_MAX_LIST)), (int32_t)group_size,
+                                      b.ids.data(), b.sc.data(), b.group.data(), b.members.data(), b.total.data(), b.cnt.data(),
+                                      &last_stats));
+    return b.groups(n, true);
+  }
+
+  // np_hip_search_hybrid_grouped: ColGREP's request -- search_hybrid fused into a pool of pool_k (0: the default above, inside
+  // the fusion's limit of 2 * NP_TEXT_MAX_TOPK), then collapsed to params.top_k groups.  fetch_k 0: min(3 * pool_k, 1024).
+  std::vector<GroupedResult> search_hybrid_grouped(const Query* queries, const std::vector<TextQuery>& text_queries,
+                                                   const SearchParameters& params, size_t group_size = 1, size_t pool_k = 0,
+                                                   float alpha = 0.75f, int fusion = NP_FUSE_RELATIVE_SCORE, size_t fetch_k = 0,
+                                                   const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("search_hybrid_grouped");
+    const size_t n = text_queries.size();
+    if (!subsets.empty() && subsets.size() != n)
+      throw Error(NP_ERR_INVALID_ARGUMENT, "search_hybrid_grouped: one subset entry per query");
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
+    std::vector<np_text_query> q;
+    for (const TextQuery& t : text_queries) q.push_back(t.c());
+    std::vector<int32_t> off;
+    std::vector<float> flat;
+    pack_queries(queries, n, off, flat);
+    const np_search_params p = params.c();
+    const size_t pk = pool_k ? pool_k : default_pool_k(params.top_k, 2 * NP_TEXT_MAX_TOPK);
+    const size_t fk = fetch_k ? fetch_k : std::min<size_t>(3 * pk, NP_TEXT_MAX_TOPK);
+    GroupBuffers b(n, params.top_k, group_size);
+    check(np_hip_search_hybrid_grouped(h_, flat.data(), off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, q.data(), (int32_t)fk,
+                                       alpha, fusion, sids.data(), soff.data(), (int64_t)n_distinct, qsub.data(), nullptr, 0,
+                                       (int32_t)pk, (int32_t)group_size, b.ids.data(), b.sc.data(), b.group.data(), b.members.data(),
+                                       b.total.data(), b.cnt.data(), &last_stats));
+    return b.groups(n, true);
+  }
+
   // Given pairs with the per-token matches (np_hip_score_pairs; no crate counterpart, no CPU hand-off): query i against the
   // documents doc_ids[i] (global ids; duplicates allowed).  scores[p] is the S6 score of the pair -- the bits search_batch and
   // search_exact give it at precision 0 -- and, with return_matches, token_sims / token_pos hold one row of n_tokens entries
@@ -828,6 +926,47 @@ class MmapIndex {
     }
     return out;
   }
+
+  void pack_queries(const Query* queries, size_t n, std::vector<int32_t>& off, std::vector<float>& flat) const {
+    const size_t dim = embedding_dim();
+    off.assign(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
+    flat.assign(std::max<size_t>((size_t)off[n] * dim, 1), 0.f);
+    for (size_t i = 0; i < n; ++i)
+      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+  }
+
+  // ColGREP's over-fetch for top_k groups, inside what the index holds and the entry's limit
+  size_t default_pool_k(size_t top_k, size_t limit) const {
+    const size_t want = std::max<size_t>(20 * top_k, 200), have = std::max<size_t>(num_documents(), top_k);
+    return std::max<size_t>(1, std::min(std::min(want, have), limit));
+  }
+
+  // the padded outputs of a grouped call, and their unpacking
+  struct GroupBuffers {
+    size_t k, g;
+    std::vector<int64_t> ids;
+    std::vector<float> sc;
+    std::vector<int32_t> group, members, total, cnt;
+    GroupBuffers(size_t n, size_t top_k, size_t group_size)
+        : k(std::max<size_t>(top_k, 1)), g(std::max<size_t>(group_size, 1)), ids(std::max<size_t>(n * k * g, 1)),
+          sc(std::max<size_t>(n * k * g, 1)), group(std::max<size_t>(n * k, 1)), members(std::max<size_t>(n * k, 1)),
+          total(std::max<size_t>(n * k, 1)), cnt(std::max<size_t>(n, 1)) {}
+    std::vector<GroupedResult> groups(size_t n, bool with_scores) const {
+      std::vector<GroupedResult> out(n);
+      for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < (size_t)cnt[i]; ++j) {
+          Group gr;
+          gr.group_id = group[i * k + j];
+          gr.total = total[i * k + j];
+          const size_t at = (i * k + j) * g, m = (size_t)members[i * k + j];
+          gr.passage_ids.assign(ids.begin() + at, ids.begin() + at + m);
+          if (with_scores) gr.scores.assign(sc.begin() + at, sc.begin() + at + m);
+          out[i].push_back(std::move(gr));
+        }
+      return out;
+    }
+  };
 
   // The body of every batch call: pack the queries, `call` the library, apply the error and fallback policy (`cpu`: this
   // batch on the CPU hand-off), unpack.

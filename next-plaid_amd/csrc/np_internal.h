@@ -341,6 +341,9 @@ struct DeviceIndex {
   size_t coltext_bytes = 0;       // ... and that of the columns' dictionary text
   DeviceText text;                // the keyword index (np_hip_index_set_text)
   size_t text_bytes = 0;          // ... and its share of device_bytes
+  DevPtr<int32_t> d_groups;       // [n_docs] the group of every document (np_hip_index_set_groups, np_group.hip); unsharded only
+  int64_t n_groups = 0;           // 0 = no groups set
+  size_t group_bytes = 0;         // ... and their share of device_bytes
   size_t device_bytes = 0;
   np_open_opts opts{};
   // per-context scratch budget the planner uses.  A caller-given workspace_bytes is kept as it is; the default (what the device
@@ -558,6 +561,46 @@ struct ResultStage {
 int search_batch_in_use(const DeviceIndex* ix, ContextUse& use, const float* d_q, const int32_t* d_qoff, const int32_t* h_qoff,
                         int B, int dim, const np_search_params* prm, const CallSubsets& scope, int64_t* d_out_ids,
                         float* d_out_scores, int32_t* d_out_counts);
+
+// np_group.hip: the outputs of a grouped host entry point -- [B][top_k][group_size] ids and scores, [B][top_k] group, members
+// and total, [B] counts -- staged as ResultStage stages its three: carved out of the arena, copied back through the head of
+// the pinned area, handed to the caller once the stream is synchronised.  The score regions exist even where nobody asks for
+// them (a list without scores): the layout does not depend on it.
+struct GroupStage {
+  size_t n, g, B;                             // B * top_k * group_size, B * top_k, B
+  size_t o_ids, o_sc, o_g, o_cnt;             // the regions' sizes (group, members and total share o_g)
+  int64_t* d_ids = nullptr;
+  float* d_sc = nullptr;
+  int32_t *d_group = nullptr, *d_members = nullptr, *d_total = nullptr, *d_cnt = nullptr;
+  char* pin = nullptr;
+  bool scores = true;
+  GroupStage(int B_, int top_k, int group_size)
+      : n((size_t)B_ * top_k * group_size), g((size_t)B_ * top_k), B((size_t)B_), o_ids(up256(n * 8)), o_sc(up256(n * 4)),
+        o_g(up256(g * 4)), o_cnt(up256(B * 4)) {}
+  size_t bytes() const { return o_ids + o_sc + 3 * o_g + o_cnt; }
+  void carve(Carver& c) {
+    d_ids = (int64_t*)c.take(o_ids);
+    d_sc = (float*)c.take(o_sc);
+    d_group = (int32_t*)c.take(o_g);
+    d_members = (int32_t*)c.take(o_g);
+    d_total = (int32_t*)c.take(o_g);
+    d_cnt = (int32_t*)c.take(o_cnt);
+  }
+  int fetch(void* pinned, hipStream_t st, bool with_scores);
+  void deliver(int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members, int32_t* out_total,
+               int32_t* out_counts) const;
+};
+// the scalar checks of a collapse (np_group_plan.h) against the handle, with the error set; then collapse_kernel on `st`:
+// B lists [B][stride] (d_scores may be NULL, and then d_out_scores is not written) to top_k groups of at most group_size
+int collapse_check(const DeviceIndex* ix, int32_t top_k, int32_t group_size, int32_t B, int32_t stride);
+int collapse_launch(const DeviceIndex* ix, hipStream_t st, int32_t top_k, int32_t group_size, int32_t B, const int64_t* d_ids,
+                    const float* d_scores, const int32_t* d_counts, int32_t stride, int64_t* d_out_ids, float* d_out_scores,
+                    int32_t* d_out_group, int32_t* d_out_members, int32_t* d_out_total, int32_t* d_out_counts);
+// the grouped part of np_hip_search_hybrid_grouped's arguments (np_text.hip runs the hybrid request, fused to pool_k)
+struct GroupCall {
+  int32_t pool_k, group_size;
+  int32_t *out_group, *out_members, *out_total;
+};
 
 // np_search.hip: np_hip_search_phase_a_subsets with the subsets' GLOBAL lengths on the device (d_global_lens[n_subsets], NULL =
 // the CSR's own): what the probe scaling reads when the CSR holds only a shard's part of every subset

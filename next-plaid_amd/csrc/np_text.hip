@@ -1328,11 +1328,13 @@ int np_hip_fuse(const np_index* ix, int32_t mode, float alpha, int32_t top_k, in
   return NP_OK;
 }
 
-int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
-                         const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
-                         int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
-                         const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int64_t* out_ids,
-                         float* out_scores, int32_t* out_counts, np_stats* stats) {
+// The hybrid request.  grp == NULL: np_hip_search_hybrid, fused to params->top_k.  Otherwise np_hip_search_hybrid_grouped: fused
+// to grp->pool_k into a list that stays on the device, then collapsed to params->top_k groups (np_group.hip) on the same stream.
+static int hybrid_host(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                       const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
+                       int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                       const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int64_t* out_ids,
+                       float* out_scores, int32_t* out_counts, np_stats* stats, const GroupCall* grp) {
   clear_error();
   if (stats) memset(stats, 0, sizeof *stats);
   if (!params) {
@@ -1340,7 +1342,12 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
     return NP_ERR_INVALID_ARGUMENT;
   }
   NP_TRY(text_check_queries(ix, text_queries, B, fetch_k));
-  NP_TRY(fuse_check(fusion, alpha, params->top_k, B, fetch_k, fetch_k));
+  NP_TRY(fuse_check(fusion, alpha, grp ? grp->pool_k : params->top_k, B, fetch_k, fetch_k));
+  if (grp) NP_TRY(collapse_check(ix, params->top_k, grp->group_size, B, grp->pool_k));
+  if (grp && B > 0 && (!grp->out_group || !grp->out_members || !grp->out_total)) {
+    set_error("Search failed: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
   if (filters) n_subsets = n_filters;
   if (filters)
     NP_TRY(filter_check_call(ix, filters, n_filters, query_subset, B, true));
@@ -1361,7 +1368,7 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
     }
   np_search_params sem = *params;
   sem.top_k = fetch_k;
-  const int top_k = params->top_k;
+  const int top_k = grp ? grp->pool_k : params->top_k;   // of the fused list
   const auto t0 = std::chrono::steady_clock::now();
   TextProg prog;
   prog.build(ix, text_queries, B);
@@ -1376,12 +1383,14 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
   const int64_t ntok = q_tok_offsets[B];
   const size_t b_q = up256((size_t)std::max<int64_t>(ntok, 1) * dim * 4), b_qoff = up256((size_t)(B + 1) * 4);
   ResultStage sem_l(B, fetch_k), kw_l(B, fetch_k), res(B, top_k);   // the two lists stay on the device
-  const size_t user = b_q + b_qoff + scope.stage_bytes() + sem_l.bytes() + kw_l.bytes() + res.bytes();
+  GroupStage grouped(B, grp ? params->top_k : 0, grp ? grp->group_size : 0);   // (and the fused one, where it is collapsed)
+  const size_t head = grp ? grouped.bytes() : res.bytes();   // what comes back through the pinned area
+  const size_t user = b_q + b_qoff + scope.stage_bytes() + sem_l.bytes() + kw_l.bytes() + res.bytes() + (grp ? grouped.bytes() : 0);
   TextPlan plan;
   NP_TRY(text_plan_for(ix, (int64_t)user + scope.budget_extra(), prog, B, fetch_k, scope.any, &plan));
   NP_TRY(use.arena().reserve(user + text_arena_bytes(ix, plan, prog, fetch_k, scope.any)));
   void* pin = nullptr;   // the results, the keyword programs behind them
-  NP_TRY(use.pin(res.bytes() + prog.bytes, &pin));
+  NP_TRY(use.pin(head + prog.bytes, &pin));
   Carver carve{use.arena().as<char>()};
   float* d_q = (float*)carve.take(b_q);
   int32_t* d_qoff = (int32_t*)carve.take(b_qoff);
@@ -1390,24 +1399,54 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
   sem_l.carve(carve);
   kw_l.carve(carve);
   res.carve(carve);
+  if (grp) grouped.carve(carve);
   if (ntok > 0) NP_HIP(hipMemcpyAsync(d_q, queries, (size_t)ntok * dim * 4, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemcpyAsync(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
   NP_TRY(search_batch_in_use(ix, use, d_q, d_qoff, q_tok_offsets, B, dim, &sem, sub, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt));
   int64_t visited = 0;
-  NP_TRY(text_run(ix, use, carve.at, (char*)pin + res.bytes(), plan, prog, fetch_k, sub, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt,
+  NP_TRY(text_run(ix, use, carve.at, (char*)pin + head, plan, prog, fetch_k, sub, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt,
                   stats ? &visited : nullptr));
   NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt, fetch_k, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, fetch_k,
                      res.d_ids, res.d_sc, res.d_cnt));
-  NP_TRY(res.fetch(pin, st));
+  if (grp) {
+    NP_TRY(collapse_launch(ix, st, params->top_k, grp->group_size, B, res.d_ids, res.d_sc, res.d_cnt, top_k, grouped.d_ids,
+                           grouped.d_sc, grouped.d_group, grouped.d_members, grouped.d_total, grouped.d_cnt));
+    NP_TRY(grouped.fetch(pin, st, true));
+  } else {
+    NP_TRY(res.fetch(pin, st));
+  }
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
-  res.deliver(out_ids, out_scores, out_counts);
+  if (grp)
+    grouped.deliver(out_ids, out_scores, grp->out_group, grp->out_members, grp->out_total, out_counts);
+  else
+    res.deliver(out_ids, out_scores, out_counts);
   if (stats) {
     stats->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     stats->n_queries = B;
     stats->n_ivf_ids = visited;
   }
   return NP_OK;
+}
+
+int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                         const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
+                         int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                         const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int64_t* out_ids,
+                         float* out_scores, int32_t* out_counts, np_stats* stats) {
+  return hybrid_host(ix, queries, q_tok_offsets, B, dim, params, text_queries, fetch_k, alpha, fusion, subset_ids, subset_offsets,
+                     n_subsets, query_subset, filters, n_filters, out_ids, out_scores, out_counts, stats, nullptr);
+}
+
+int np_hip_search_hybrid_grouped(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                                 const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
+                                 int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                                 const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int32_t pool_k,
+                                 int32_t group_size, int64_t* out_ids, float* out_scores, int32_t* out_group,
+                                 int32_t* out_members, int32_t* out_total, int32_t* out_counts, np_stats* stats) {
+  const GroupCall grp{pool_k, group_size, out_group, out_members, out_total};
+  return hybrid_host(ix, queries, q_tok_offsets, B, dim, params, text_queries, fetch_k, alpha, fusion, subset_ids, subset_offsets,
+                     n_subsets, query_subset, filters, n_filters, out_ids, out_scores, out_counts, stats, &grp);
 }
 
 int np_hip_text_search_sharded(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,

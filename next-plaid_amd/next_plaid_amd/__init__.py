@@ -10,7 +10,7 @@ from .api import (  # noqa: F401
     ShapeError, CodecError, DeviceUnavailableError, device_count, library_path, rerank_maxsim, probe_index_dir, write_index_dir,
     IndexConfig, IndexCreationError, kmeans, kmeans_plan, compute_kmeans, estimate_num_partitions, prepare_codec_artifacts,
     UpdateConfig, update_index_dir, update_append_dir, delete_from_index_dir, pool_document_embeddings, pooled_lengths,
-    pack_filters, fuse, fuse_rrf, fuse_relative_score,
+    pack_filters, fuse, fuse_rrf, fuse_relative_score, collapse, group_ids_of_keys, default_pool_k,
 )
 from .filters import compile_filter, make_schema, CompiledFilter, FilterError, Schema  # noqa: F401
 from .regexes import compile_regex, compile_like, Dfa  # noqa: F401

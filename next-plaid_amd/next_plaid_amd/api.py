@@ -239,6 +239,8 @@ EXPORTS = [
     "np_hip_index_set_column_text", "np_hip_text_match",
     "np_hip_index_set_text_shard", "np_hip_text_search_sharded", "np_hip_text_search_sharded_filtered",
     "np_hip_search_batch_sharded_filtered", "np_hip_search_hybrid_sharded",
+    "np_hip_index_set_groups", "np_hip_index_group_count", "np_hip_collapse", "np_hip_collapse_device",
+    "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
 ]
 
 _lib = None
@@ -370,6 +372,16 @@ def lib():
     L.np_hip_search_hybrid_sharded.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params),
                                                C.POINTER(np_text_query), i32, C.c_float, i32, vp, vp, vp, i64, vp,
                                                C.POINTER(np_filter), i32, vp, vp, vp, vp, vp]
+    L.np_hip_index_set_groups.argtypes = [vp, vp, i64, i64]
+    L.np_hip_index_group_count.argtypes = [vp]
+    L.np_hip_index_group_count.restype = i64
+    L.np_hip_collapse.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.np_hip_collapse_device.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.np_hip_search_batch_grouped.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), vp, vp, i64, vp,
+                                              C.POINTER(np_filter), i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_search_hybrid_grouped.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_text_query), i32,
+                                               C.c_float, i32, vp, vp, i64, vp, C.POINTER(np_filter), i32, i32, i32,
+                                               vp, vp, vp, vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -600,6 +612,67 @@ def fuse_rrf(sem_ids, kw_ids, alpha: float, top_k: int, index=None):
 def fuse_relative_score(sem_ids, sem_scores, kw_ids, kw_scores, alpha: float, top_k: int, index=None):
     """fuse_relative_score (text_search.rs:1040-1075) with its argument order, batched."""
     return fuse("relative_score", alpha, top_k, sem_ids, sem_scores, kw_ids, kw_scores, index=index)
+
+
+# ---- grouped search ------------------------------------------------------------------------------------
+NP_GROUP_MAX_LIST = 16384
+
+
+def group_ids_of_keys(keys):
+    """One key per document (ints, strings or None) -> (dense group ids int32, the distinct non-null values sorted, n_groups).
+    Group g < len(values) holds the documents whose key is values[g]; every None entry goes to ONE group with the last id
+    (SQLite's GROUP BY puts all NULLs together).  Pure host code."""
+    keys = keys.tolist() if isinstance(keys, np.ndarray) else list(keys)
+    live = [k for k in keys if k is not None]
+    for k in live:
+        if isinstance(k, bool) or not isinstance(k, (int, str, np.integer)):
+            raise ValueError(f"a group key must be an int, a string or None, not {type(k).__name__}")
+    if len({isinstance(k, str) for k in live}) > 1:
+        raise ValueError("group keys must be all ints or all strings (None aside)")
+    values = sorted(set(live))
+    n_groups = len(values) + (1 if len(live) < len(keys) else 0)
+    if n_groups > 2 ** 31 - 1:
+        raise ValueError("more than 2^31-1 groups")
+    where = {v: i for i, v in enumerate(values)}
+    ids = np.fromiter((len(values) if k is None else where[k] for k in keys), np.int32, len(keys))
+    return ids, values, n_groups
+
+
+def default_pool_k(top_k: int, num_documents: int, limit: int = NP_GROUP_MAX_LIST) -> int:
+    """ColGREP's over-fetch for top_k groups (colgrep/src/index/mod.rs: max(20 top_k, 200)), inside what the index holds
+    and inside the entry's limit."""
+    return max(1, min(max(20 * int(top_k), 200), max(int(num_documents), int(top_k)), int(limit)))
+
+
+def _groups_of_rows(B, k, g, ids, sc, grp, mem, tot, cnt):
+    """The padded outputs of a grouped call -> per query a list of (group_id, passage_ids, scores or None, total)."""
+    if B == 0:
+        return []
+    ids = ids.reshape(B, k, g)
+    sc = None if sc is None else sc.reshape(B, k, g)
+    grp, mem, tot = (x.reshape(B, k) for x in (grp, mem, tot))
+    return [[(int(grp[i, j]), ids[i, j, : mem[i, j]].copy(), None if sc is None else sc[i, j, : mem[i, j]].copy(), int(tot[i, j]))
+             for j in range(int(cnt[i]))] for i in range(B)]
+
+
+def _group_outputs(B, k, g, scores=True):
+    n = max(B * k * g, 1)
+    return (np.zeros(n, np.int64), np.zeros(n, np.float32) if scores else None, np.zeros(max(B * k, 1), np.int32),
+            np.zeros(max(B * k, 1), np.int32), np.zeros(max(B * k, 1), np.int32), np.zeros(max(B, 1), np.int32))
+
+
+def collapse(ids, scores, top_k: int, group_size: int, index):
+    """np_hip_collapse over a batch of ranked lists (sequences of id arrays; `scores` likewise or None): walk each list, admit
+    a group -- index.set_groups -- at its first entry while fewer than top_k are admitted, keep the first group_size entries of
+    every admitted group and count them all.  Returns per query a list of groups (group_id, passage_ids, scores, total) in
+    order of admission; scores is None when none were given."""
+    B = len(ids)
+    if scores is not None and len(scores) != B:
+        raise ValueError(f"{B} id lists and {len(scores)} score lists")
+    fi, cnt, w = _pad_lists(ids, np.int64)
+    fs = None if scores is None else _pad_lists(scores, np.float32, w)[0]
+    return _groups_of_rows(B, max(int(top_k), 1), max(int(group_size), 1),
+                           *index.collapse_raw(fi, fs, cnt, w, top_k, group_size))
 
 
 # ---- crate mirror ------------------------------------------------------------------------------------
@@ -960,6 +1033,7 @@ class MmapIndex:
         self.schema = None   # set_columns: the columns' names, types and dictionaries (filters.Schema)
         self.last_match_report = None   # match_text / text_match_raw: np_match_report of the last call
         self.text = None     # set_text: the keyword index's arrays and vocabulary (text.TextIndexData)
+        self.group_values = None   # set_groups: the distinct non-null keys, sorted (group g < len: its key; the last: the NULLs)
 
     # -- constructors ---------------------------------------------------------------------------------
     @classmethod
@@ -998,6 +1072,7 @@ class MmapIndex:
         self._h = h
         self.schema = None
         self.text = None     # (and no keyword index, for the same reason: set_text / load_text again)
+        self.group_values = None   # (and no groups: set_groups again)
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         self.last_stats = None
 
@@ -1393,6 +1468,97 @@ class MmapIndex:
                                           0 if cf is None else cf.n, _ptr(ids), _ptr(sc), _ptr(cnt), C.byref(st)))
         self.last_stats = st.as_dict()
         return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+
+    # -- grouped search -----------------------------------------------------------------------------------
+    def set_groups(self, keys, n_groups: int | None = None):
+        """np_hip_index_set_groups: the group of every document of the WHOLE index, kept in HBM.  `keys` has one entry per
+        document -- ints, strings or None: dense ids follow the sorted distinct non-null values, which stay on this object as
+        self.group_values, and all None entries form one group with the last id (SQLite's GROUP BY rule) -- or, with
+        n_groups=, it is a ready int32 array of ids in [0, n_groups).  None or an empty sequence drops the groups.  A length
+        other than num_documents() is a ShapeError.  A sharded handle is refused.  reload() (and so update()) leaves the
+        handle without groups, as it leaves it without columns.  Needs exclusive access to the handle, as set_columns does."""
+        if keys is None or len(keys) == 0:
+            _check(lib().np_hip_index_set_groups(self._h, None, 0, 0))
+            self.group_values = None
+        else:
+            if n_groups is not None:
+                ids, values, n = np.ascontiguousarray(keys, np.int32).reshape(-1), None, int(n_groups)
+            else:
+                ids, values, n = group_ids_of_keys(keys)
+            _check(lib().np_hip_index_set_groups(self._h, _ptr(ids), ids.size, n))
+            self.group_values = values
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def group_count(self) -> int:
+        """np_hip_index_group_count: n_groups, 0 when no groups are set."""
+        return int(lib().np_hip_index_group_count(self._h))
+
+    def collapse_raw(self, ids, scores, counts, stride: int, top_k: int, group_size: int):
+        """np_hip_collapse as it is: ids i64 [B * stride], scores f32 likewise or None, counts i32 [B] reach the library as
+        given, so its checks answer.  Returns the padded outputs (ids, scores or None, group, members, total, counts)."""
+        cnt = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        B = cnt.size
+        fi = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        fs = None if scores is None else np.ascontiguousarray(scores, np.float32).reshape(-1)
+        if fi.size < B * max(int(stride), 0) or (fs is not None and fs.size < fi.size):
+            raise ValueError(f"{B} lists of stride {stride} need {B * stride} entries")
+        out = _group_outputs(B, max(int(top_k), 1), max(int(group_size), 1), fs is not None)
+        _check(lib().np_hip_collapse(self._h, int(top_k), int(group_size), B, _ptr(fi), _ptr(fs), _ptr(cnt), int(stride),
+                                     *[_ptr(o) for o in out]))
+        return out
+
+    def search_grouped(self, queries, params: "SearchParameters", group_size: int = 1, pool_k: int | None = None, subset=None,
+                       subsets=None, filters=None, raw: bool = False):
+        """np_hip_search_batch_grouped: the top params.top_k GROUPS (set_groups) with their best group_size documents each --
+        the search pass with top_k = pool_k and the collapse of its ranked lists, on the device; neither leaves HBM.  Query i
+        gets collapse(search_batch(top_k = pool_k)).  pool_k defaults to ColGREP's max(20 top_k, 200), inside the index and
+        the entry's limit of 16384.  Scope: `subset`, `subsets` or `filters` as search_batch takes them.  Returns per query a
+        list of groups (group_id, passage_ids, scores, total); raw=True returns the padded output arrays instead."""
+        queries = list(queries)
+        flat, off = self._pack(queries)
+        B = len(queries)
+        pk = default_pool_k(params.top_k, self.num_documents()) if pool_k is None else int(pool_k)
+        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "search_grouped")
+        k, g = max(int(params.top_k), 1), max(int(group_size), 1)
+        out = _group_outputs(B, k, g)
+        p = params._c()
+        st = np_stats()
+        _check(lib().np_hip_search_batch_grouped(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), _ptr(sid),
+                                                 _ptr(soff), n_sub, _ptr(qsub), None if cf is None else cf.arr,
+                                                 0 if cf is None else cf.n, pk, int(group_size), *[_ptr(o) for o in out],
+                                                 C.byref(st)))
+        self.last_stats = st.as_dict()
+        return out if raw else _groups_of_rows(B, k, g, *out)
+
+    def search_hybrid_grouped(self, queries, text_queries, params: "SearchParameters", group_size: int = 1,
+                              pool_k: int | None = None, alpha: float = 0.75, fusion: str = "relative_score",
+                              fetch_k: int | None = None, subset=None, subsets=None, filters=None):
+        """np_hip_search_hybrid_grouped: ColGREP's request -- search_hybrid fused into a pool of pool_k, then collapsed to
+        params.top_k groups of at most group_size documents, on the device.  Query i gets collapse(search_hybrid(top_k =
+        pool_k)).  fetch_k defaults to min(3 * pool_k, 1024), pool_k to ColGREP's max(20 top_k, 200) inside the index and the
+        fusion's limit of 2048.  Returns what search_grouped returns."""
+        from . import text as T
+        queries = list(queries)
+        flat, off = self._pack(queries)
+        B = len(queries)
+        qs = self._text_queries(list(text_queries), True)
+        if len(qs) != B:
+            raise ValueError(f"{B} queries and {len(qs)} text queries")
+        pk = default_pool_k(params.top_k, self.num_documents(), 2 * T.NP_TEXT_MAX_TOPK) if pool_k is None else int(pool_k)
+        fk = min(3 * pk, T.NP_TEXT_MAX_TOPK) if fetch_k is None else int(fetch_k)
+        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "search_hybrid_grouped")
+        tq = _CTextQueries(qs)
+        k, g = max(int(params.top_k), 1), max(int(group_size), 1)
+        out = _group_outputs(B, k, g)
+        p = params._c()
+        st = np_stats()
+        _check(lib().np_hip_search_hybrid_grouped(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), tq.arr, fk,
+                                                  float(alpha), T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion),
+                                                  _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), None if cf is None else cf.arr,
+                                                  0 if cf is None else cf.n, pk, int(group_size), *[_ptr(o) for o in out],
+                                                  C.byref(st)))
+        self.last_stats = st.as_dict()
+        return _groups_of_rows(B, k, g, *out)
 
     # -- search ------------------------------------------------------------------------------------------
     def _pack(self, queries):
