@@ -490,15 +490,12 @@ class MmapIndex {
   // built once); contents are never compared.  The CPU fallback takes one subset per call: it is called once per query.
   std::vector<QueryResult> search_batch_subsets(const Query* queries, size_t n, const SearchParameters& params, bool parallel,
                                                 const std::vector<const std::vector<int64_t>*>& subsets) const {
-    if (subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_batch_subsets: one subset entry per query");
-    std::vector<int32_t> qsub;
-    std::vector<int64_t> soff, sids;
-    const size_t n_distinct = pack_subsets(subsets, qsub, soff, sids);
+    const SubsetArgs s(subsets, n, "search_batch_subsets", /*empty_is_none=*/false);
     return run_batch(
         queries, n, params, parallel,
         [&](const float* flat, const int32_t* off, const np_search_params* p, int64_t* ids, float* sc, int32_t* cnt) {
-          return np_hip_search_batch_subsets(h_, flat, off, (int32_t)n, (int32_t)embedding_dim(), p, sids.data(), soff.data(),
-                                             (int64_t)n_distinct, qsub.data(), ids, sc, cnt, &last_stats);
+          return np_hip_search_batch_subsets(h_, flat, off, (int32_t)n, (int32_t)embedding_dim(), p, s.sids.data(), s.soff.data(),
+                                             (int64_t)s.n_distinct, s.qsub.data(), ids, sc, cnt, &last_stats);
         },
         [&] {
           std::vector<QueryResult> out;
@@ -524,29 +521,13 @@ class MmapIndex {
   std::vector<QueryResult> search_exact_subsets(const Query* queries, size_t n, size_t top_k, int precision,
                                                 const std::vector<const std::vector<int64_t>*>& subsets) const {
     require_device("search_exact");
-    if (subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_exact_subsets: one subset entry per query");
-    std::vector<int32_t> qsub;
-    std::vector<int64_t> soff, sids;
-    const size_t n_distinct = pack_subsets(subsets, qsub, soff, sids);
-    const size_t dim = embedding_dim();
-    std::vector<int32_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
-    std::vector<float> flat((size_t)off[n] * dim);
-    for (size_t i = 0; i < n; ++i)
-      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
-    const size_t k = std::max<size_t>(top_k, 1);
-    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
-    std::vector<float> sc(std::max<size_t>(n * k, 1));
-    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
-    check(np_hip_search_exact(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)top_k, (int32_t)precision, sids.data(),
-                              soff.data(), (int64_t)n_distinct, qsub.data(), ids.data(), sc.data(), cnt.data(), &last_stats));
-    std::vector<QueryResult> out(n);
-    for (size_t i = 0; i < n; ++i) {
-      out[i].query_id = i;
-      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
-      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
-    }
-    return out;
+    const SubsetArgs s(subsets, n, "search_exact_subsets", /*empty_is_none=*/false);
+    const PackedQueries q = pack_queries(queries, n);
+    RowBuffers b(n, std::max<size_t>(top_k, 1));
+    check(np_hip_search_exact(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), (int32_t)top_k, (int32_t)precision,
+                              s.sids.data(), s.soff.data(), (int64_t)s.n_distinct, s.qsub.data(), b.ids.data(), b.sc.data(),
+                              b.cnt.data(), &last_stats));
+    return b.rows(n);
   }
 
   // Metadata columns (np_hip_index_set_columns): replaces any earlier set, an empty vector drops them.  Every span covers
@@ -594,8 +575,7 @@ class MmapIndex {
   // The global ids every filter selects among this handle's documents, ascending (np_hip_filter_eval).
   std::vector<std::vector<int64_t>> filter_ids(const std::vector<FilterProgram>& filters) const {
     require_device("filter_ids");
-    std::vector<np_filter> f;
-    for (const FilterProgram& p : filters) f.push_back(p.c());
+    const std::vector<np_filter> f = c_filters(filters);
     std::vector<int64_t> off(filters.size() + 1, 0);
     check(np_hip_filter_eval(h_, f.data(), (int32_t)f.size(), nullptr, 0, off.data()));
     std::vector<int64_t> ids(std::max<size_t>((size_t)off.back(), 1));
@@ -613,8 +593,7 @@ class MmapIndex {
                                                  const std::vector<int32_t>& query_filter) const {
     require_device("search_batch_filtered");
     if (query_filter.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_batch_filtered: one query_filter entry per query");
-    std::vector<np_filter> f;
-    for (const FilterProgram& p : filters) f.push_back(p.c());
+    const std::vector<np_filter> f = c_filters(filters);
     return run_batch(
         queries, n, params, parallel,
         [&](const float* flat, const int32_t* off, const np_search_params* p, int64_t* ids, float* sc, int32_t* cnt) {
@@ -632,28 +611,13 @@ class MmapIndex {
                                                  const std::vector<int32_t>& query_filter) const {
     require_device("search_exact_filtered");
     if (query_filter.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_exact_filtered: one query_filter entry per query");
-    std::vector<np_filter> f;
-    for (const FilterProgram& p : filters) f.push_back(p.c());
-    const size_t dim = embedding_dim();
-    std::vector<int32_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
-    std::vector<float> flat((size_t)off[n] * dim);
-    for (size_t i = 0; i < n; ++i)
-      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
-    const size_t k = std::max<size_t>(top_k, 1);
-    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
-    std::vector<float> sc(std::max<size_t>(n * k, 1));
-    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
-    check(np_hip_search_exact_filtered(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)top_k, (int32_t)precision,
-                                       f.data(), (int32_t)f.size(), query_filter.data(), ids.data(), sc.data(), cnt.data(),
-                                       &last_stats));
-    std::vector<QueryResult> out(n);
-    for (size_t i = 0; i < n; ++i) {
-      out[i].query_id = i;
-      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
-      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
-    }
-    return out;
+    const std::vector<np_filter> f = c_filters(filters);
+    const PackedQueries q = pack_queries(queries, n);
+    RowBuffers b(n, std::max<size_t>(top_k, 1));
+    check(np_hip_search_exact_filtered(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), (int32_t)top_k,
+                                       (int32_t)precision, f.data(), (int32_t)f.size(), query_filter.data(), b.ids.data(),
+                                       b.sc.data(), b.cnt.data(), &last_stats));
+    return b.rows(n);
   }
 
   // The keyword index (np_hip_index_set_text): replaces any earlier one, nullptr drops it.  Needs exclusive access to the
@@ -676,19 +640,12 @@ class MmapIndex {
                                        const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
     require_device("text_search");
     const size_t n = queries.size();
-    if (!subsets.empty() && subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "text_search: one subset entry per query");
-    std::vector<int32_t> qsub;
-    std::vector<int64_t> soff, sids;
-    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
-    std::vector<np_text_query> q;
-    for (const TextQuery& t : queries) q.push_back(t.c());
-    const size_t k = std::max<size_t>(top_k, 1);
-    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
-    std::vector<float> sc(std::max<size_t>(n * k, 1));
-    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
-    check(np_hip_text_search(h_, q.data(), (int32_t)n, (int32_t)top_k, sids.data(), soff.data(), (int64_t)n_distinct, qsub.data(),
-                             ids.data(), sc.data(), cnt.data(), &last_stats));
-    return rows(ids, sc, cnt, n, k);
+    const SubsetArgs s(subsets, n, "text_search");
+    const std::vector<np_text_query> tq = c_text_queries(queries);
+    RowBuffers b(n, std::max<size_t>(top_k, 1));
+    check(np_hip_text_search(h_, tq.data(), (int32_t)n, (int32_t)top_k, s.sids.data(), s.soff.data(), (int64_t)s.n_distinct,
+                             s.qsub.data(), b.ids.data(), b.sc.data(), b.cnt.data(), &last_stats));
+    return b.rows(n);
   }
 
   // Fusion of per-query semantic and keyword lists (np_hip_fuse; text_search.rs:1006-1075): mode NP_FUSE_RRF or
@@ -698,30 +655,11 @@ class MmapIndex {
     require_device("fuse");
     const size_t n = sem.size();
     if (kw.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "fuse: one keyword list per semantic list");
-    auto pack = [n](const std::vector<QueryResult>& l, std::vector<int64_t>& ids, std::vector<float>& sc, std::vector<int32_t>& cnt) {
-      size_t w = 1;
-      for (const QueryResult& r : l) w = std::max(w, r.passage_ids.size());
-      ids.assign(std::max<size_t>(n, 1) * w, 0);
-      sc.assign(std::max<size_t>(n, 1) * w, 0.f);
-      cnt.assign(std::max<size_t>(n, 1), 0);
-      for (size_t i = 0; i < n; ++i) {
-        std::copy(l[i].passage_ids.begin(), l[i].passage_ids.end(), ids.begin() + i * w);
-        std::copy(l[i].scores.begin(), l[i].scores.end(), sc.begin() + i * w);
-        cnt[i] = (int32_t)l[i].passage_ids.size();
-      }
-      return w;
-    };
-    std::vector<int64_t> si, ki;
-    std::vector<float> ss, ks;
-    std::vector<int32_t> scnt, kcnt;
-    const size_t sw = pack(sem, si, ss, scnt), kw_w = pack(kw, ki, ks, kcnt);
-    const size_t k = std::max<size_t>(top_k, 1);
-    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
-    std::vector<float> sc(std::max<size_t>(n * k, 1));
-    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
-    check(np_hip_fuse(h_, mode, alpha, (int32_t)top_k, (int32_t)n, si.data(), ss.data(), scnt.data(), (int32_t)sw, ki.data(), ks.data(),
-                      kcnt.data(), (int32_t)kw_w, ids.data(), sc.data(), cnt.data()));
-    return rows(ids, sc, cnt, n, k);
+    const PaddedLists s(sem), w(kw);
+    RowBuffers b(n, std::max<size_t>(top_k, 1));
+    check(np_hip_fuse(h_, mode, alpha, (int32_t)top_k, (int32_t)n, s.ids.data(), s.sc.data(), s.cnt.data(), (int32_t)s.stride,
+                      w.ids.data(), w.sc.data(), w.cnt.data(), (int32_t)w.stride, b.ids.data(), b.sc.data(), b.cnt.data()));
+    return b.rows(n);
   }
 
   // The /search handler's hybrid request in one call (np_hip_search_hybrid): the semantic and the keyword pass with
@@ -731,27 +669,16 @@ class MmapIndex {
                                          const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
     require_device("search_hybrid");
     const size_t n = text_queries.size();
-    if (!subsets.empty() && subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_hybrid: one subset entry per query");
-    std::vector<int32_t> qsub;
-    std::vector<int64_t> soff, sids;
-    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
-    std::vector<np_text_query> q;
-    for (const TextQuery& t : text_queries) q.push_back(t.c());
-    const size_t dim = embedding_dim();
-    std::vector<int32_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
-    std::vector<float> flat((size_t)off[n] * dim);
-    for (size_t i = 0; i < n; ++i)
-      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+    const SubsetArgs s(subsets, n, "search_hybrid");
+    const std::vector<np_text_query> tq = c_text_queries(text_queries);
+    const PackedQueries q = pack_queries(queries, n);
     const np_search_params p = params.c();
-    const size_t k = std::max<size_t>(params.top_k, 1);
-    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
-    std::vector<float> sc(std::max<size_t>(n * k, 1));
-    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
-    check(np_hip_search_hybrid(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, &p, q.data(),
-                               (int32_t)(fetch_k ? fetch_k : 3 * params.top_k), alpha, fusion, sids.data(), soff.data(),
-                               (int64_t)n_distinct, qsub.data(), nullptr, 0, ids.data(), sc.data(), cnt.data(), &last_stats));
-    return rows(ids, sc, cnt, n, k);
+    RowBuffers b(n, std::max<size_t>(params.top_k, 1));
+    check(np_hip_search_hybrid(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, tq.data(),
+                               (int32_t)(fetch_k ? fetch_k : 3 * params.top_k), alpha, fusion, s.sids.data(), s.soff.data(),
+                               (int64_t)s.n_distinct, s.qsub.data(), nullptr, 0, b.ids.data(), b.sc.data(), b.cnt.data(),
+                               &last_stats));
+    return b.rows(n);
   }
 
   // ---- grouped search (np_hip_index_set_groups and its kin; ColGREP's collapse_by_file on the device) -----------------------
@@ -781,20 +708,11 @@ class MmapIndex {
                                       bool with_scores = true) const {
     require_device("collapse");
     const size_t n = lists.size();
-    size_t w = 1;
-    for (const QueryResult& r : lists) w = std::max(w, r.passage_ids.size());
-    std::vector<int64_t> li(std::max<size_t>(n, 1) * w, 0);
-    std::vector<float> ls(std::max<size_t>(n, 1) * w, 0.f);
-    std::vector<int32_t> lc(std::max<size_t>(n, 1), 0);
-    for (size_t i = 0; i < n; ++i) {
-      std::copy(lists[i].passage_ids.begin(), lists[i].passage_ids.end(), li.begin() + i * w);
-      std::copy(lists[i].scores.begin(), lists[i].scores.end(), ls.begin() + i * w);
-      lc[i] = (int32_t)lists[i].passage_ids.size();
-    }
+    const PaddedLists l(lists);
     GroupBuffers b(n, top_k, group_size);
-    check(np_hip_collapse(h_, (int32_t)top_k, (int32_t)group_size, (int32_t)n, li.data(), with_scores ? ls.data() : nullptr, lc.data(),
-                          (int32_t)w, b.ids.data(), with_scores ? b.sc.data() : nullptr, b.group.data(), b.members.data(),
-                          b.total.data(), b.cnt.data()));
+    check(np_hip_collapse(h_, (int32_t)top_k, (int32_t)group_size, (int32_t)n, l.ids.data(), with_scores ? l.sc.data() : nullptr,
+                          l.cnt.data(), (int32_t)l.stride, b.ids.data(), with_scores ? b.sc.data() : nullptr, b.group.data(),
+                          b.members.data(), b.total.data(), b.cnt.data()));
     return b.groups(n, with_scores);
   }
 
@@ -805,17 +723,12 @@ class MmapIndex {
                                             size_t pool_k = 0,
                                             const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
     require_device("search_grouped");
-    if (!subsets.empty() && subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "search_grouped: one subset entry per query");
-    std::vector<int32_t> qsub;
-    std::vector<int64_t> soff, sids;
-    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
-    std::vector<int32_t> off;
-    std::vector<float> flat;
-    pack_queries(queries, n, off, flat);
+    const SubsetArgs s(subsets, n, "search_grouped");
+    const PackedQueries q = pack_queries(queries, n);
     const np_search_params p = params.c();
     GroupBuffers b(n, params.top_k, group_size);
-    check(np_hip_search_batch_grouped(h_, flat.data(), off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, sids.data(), soff.data(),
-                                      (int64_t)n_distinct, qsub.data(), nullptr, 0,
+    check(np_hip_search_batch_grouped(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, s.sids.data(),
+                                      s.soff.data(), (int64_t)s.n_distinct, s.qsub.data(), nullptr, 0,
                                       (int32_t)(pool_k ? pool_k : default_pool_k(params.top_k, NP_GROUP_MAX_LIST)), (int32_t)group_size,
                                       b.ids.data(), b.sc.data(), b.group.data(), b.members.data(), b.total.data(), b.cnt.data(),
                                       &last_stats));
@@ -830,22 +743,15 @@ class MmapIndex {
                                                    const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
     require_device("search_hybrid_grouped");
     const size_t n = text_queries.size();
-    if (!subsets.empty() && subsets.size() != n)
-      throw Error(NP_ERR_INVALID_ARGUMENT, "search_hybrid_grouped: one subset entry per query");
-    std::vector<int32_t> qsub;
-    std::vector<int64_t> soff, sids;
-    const size_t n_distinct = subsets.empty() ? 0 : pack_subsets(subsets, qsub, soff, sids);
-    std::vector<np_text_query> q;
-    for (const TextQuery& t : text_queries) q.push_back(t.c());
-    std::vector<int32_t> off;
-    std::vector<float> flat;
-    pack_queries(queries, n, off, flat);
+    const SubsetArgs s(subsets, n, "search_hybrid_grouped");
+    const std::vector<np_text_query> tq = c_text_queries(text_queries);
+    const PackedQueries q = pack_queries(queries, n);
     const np_search_params p = params.c();
     const size_t pk = pool_k ? pool_k : default_pool_k(params.top_k, 2 * NP_TEXT_MAX_TOPK);
     const size_t fk = fetch_k ? fetch_k : std::min<size_t>(3 * pk, NP_TEXT_MAX_TOPK);
     GroupBuffers b(n, params.top_k, group_size);
-    check(np_hip_search_hybrid_grouped(h_, flat.data(), off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, q.data(), (int32_t)fk,
-                                       alpha, fusion, sids.data(), soff.data(), (int64_t)n_distinct, qsub.data(), nullptr, 0,
+    check(np_hip_search_hybrid_grouped(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, tq.data(), (int32_t)fk,
+                                       alpha, fusion, s.sids.data(), s.soff.data(), (int64_t)s.n_distinct, s.qsub.data(), nullptr, 0,
                                        (int32_t)pk, (int32_t)group_size, b.ids.data(), b.sc.data(), b.group.data(), b.members.data(),
                                        b.total.data(), b.cnt.data(), &last_stats));
     return b.groups(n, true);
@@ -864,23 +770,18 @@ class MmapIndex {
                                       bool return_matches = true, int precision = 0) const {
     require_device("score_pairs");
     if (doc_ids.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, "score_pairs: one list of document ids per query");
-    const size_t dim = embedding_dim();
-    std::vector<int32_t> off(n + 1, 0);
+    const PackedQueries q = pack_queries(queries, n);
     std::vector<int64_t> poff(n + 1, 0), roff(n + 1, 0), ids;
     for (size_t i = 0; i < n; ++i) {
-      off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
       poff[i + 1] = poff[i] + (int64_t)doc_ids[i].size();
       roff[i + 1] = roff[i] + (int64_t)(doc_ids[i].size() * queries[i].n_tokens);
       ids.insert(ids.end(), doc_ids[i].begin(), doc_ids[i].end());
     }
-    std::vector<float> flat((size_t)off[n] * dim);
-    for (size_t i = 0; i < n; ++i)
-      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
     std::vector<float> sc(std::max<size_t>((size_t)poff[n], 1)), sims(return_matches ? std::max<size_t>((size_t)roff[n], 1) : 0);
     std::vector<int32_t> pos(sims.size());
     ids.resize(std::max<size_t>(ids.size(), 1));
-    check(np_hip_score_pairs(h_, flat.data(), off.data(), (int32_t)n, (int32_t)dim, (int32_t)precision, ids.data(), poff.data(),
-                             sc.data(), return_matches ? sims.data() : nullptr, return_matches ? pos.data() : nullptr,
+    check(np_hip_score_pairs(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), (int32_t)precision, ids.data(),
+                             poff.data(), sc.data(), return_matches ? sims.data() : nullptr, return_matches ? pos.data() : nullptr,
                              &last_stats));
     std::vector<PairScores> out(n);
     for (size_t i = 0; i < n; ++i) {
@@ -916,25 +817,85 @@ class MmapIndex {
     return distinct.size();
   }
 
-  static std::vector<QueryResult> rows(const std::vector<int64_t>& ids, const std::vector<float>& sc, const std::vector<int32_t>& cnt,
-                                       size_t n, size_t k) {
-    std::vector<QueryResult> out(n);
-    for (size_t i = 0; i < n; ++i) {
-      out[i].query_id = i;
-      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
-      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
+  // One scope per query as the entries take it (CallSubsets on the C side): the CSR of the distinct subsets and the
+  // queries' map into them.  An empty vector of subsets means none (where the method allows it: empty_is_none); otherwise
+  // there is one entry per query, or the error names the method.
+  struct SubsetArgs {
+    std::vector<int32_t> qsub;
+    std::vector<int64_t> soff, sids;
+    size_t n_distinct = 0;
+    SubsetArgs(const std::vector<const std::vector<int64_t>*>& subsets, size_t n, const char* what, bool empty_is_none = true) {
+      if (empty_is_none && subsets.empty()) return;
+      if (subsets.size() != n) throw Error(NP_ERR_INVALID_ARGUMENT, (std::string(what) + ": one subset entry per query").c_str());
+      n_distinct = pack_subsets(subsets, qsub, soff, sids);
     }
-    return out;
+  };
+
+  static std::vector<np_filter> c_filters(const std::vector<FilterProgram>& filters) {
+    std::vector<np_filter> f;
+    for (const FilterProgram& p : filters) f.push_back(p.c());
+    return f;
+  }
+  static std::vector<np_text_query> c_text_queries(const std::vector<TextQuery>& queries) {
+    std::vector<np_text_query> q;
+    for (const TextQuery& t : queries) q.push_back(t.c());
+    return q;
   }
 
-  void pack_queries(const Query* queries, size_t n, std::vector<int32_t>& off, std::vector<float>& flat) const {
+  // Ranked lists (the inputs of fuse and collapse) as [n][stride] ids and scores and [n] counts, zero-padded
+  struct PaddedLists {
+    size_t stride = 1;
+    std::vector<int64_t> ids;
+    std::vector<float> sc;
+    std::vector<int32_t> cnt;
+    explicit PaddedLists(const std::vector<QueryResult>& l) {
+      const size_t n = l.size();
+      for (const QueryResult& r : l) stride = std::max(stride, r.passage_ids.size());
+      ids.assign(std::max<size_t>(n, 1) * stride, 0);
+      sc.assign(std::max<size_t>(n, 1) * stride, 0.f);
+      cnt.assign(std::max<size_t>(n, 1), 0);
+      for (size_t i = 0; i < n; ++i) {
+        std::copy(l[i].passage_ids.begin(), l[i].passage_ids.end(), ids.begin() + i * stride);
+        std::copy(l[i].scores.begin(), l[i].scores.end(), sc.begin() + i * stride);
+        cnt[i] = (int32_t)l[i].passage_ids.size();
+      }
+    }
+  };
+
+  // The flat [sum n_tokens][dim] queries and their [n + 1] token offsets (never empty: padded to one float)
+  struct PackedQueries {
+    std::vector<int32_t> off;
+    std::vector<float> flat;
+  };
+  PackedQueries pack_queries(const Query* queries, size_t n) const {
     const size_t dim = embedding_dim();
-    off.assign(n + 1, 0);
-    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
-    flat.assign(std::max<size_t>((size_t)off[n] * dim, 1), 0.f);
+    PackedQueries q;
+    q.off.assign(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) q.off[i + 1] = q.off[i] + (int32_t)queries[i].n_tokens;
+    q.flat.assign(std::max<size_t>((size_t)q.off[n] * dim, 1), 0.f);
     for (size_t i = 0; i < n; ++i)
-      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
+      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, q.flat.begin() + (size_t)q.off[i] * dim);
+    return q;
   }
+
+  // The [n][k] ids and scores and the [n] counts a search entry fills (ResultStage on the C side), never empty, and their
+  // unpacking.  k is the caller's: max(top_k, 1) everywhere but in run_batch.
+  struct RowBuffers {
+    size_t k;
+    std::vector<int64_t> ids;
+    std::vector<float> sc;
+    std::vector<int32_t> cnt;
+    RowBuffers(size_t n, size_t k_) : k(k_), ids(std::max<size_t>(n * k, 1)), sc(std::max<size_t>(n * k, 1)), cnt(std::max<size_t>(n, 1)) {}
+    std::vector<QueryResult> rows(size_t n) const {
+      std::vector<QueryResult> out(n);
+      for (size_t i = 0; i < n; ++i) {
+        out[i].query_id = i;
+        out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
+        out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
+      }
+      return out;
+    }
+  };
 
   // ColGREP's over-fetch for top_k groups, inside what the index holds and the entry's limit
   size_t default_pool_k(size_t top_k, size_t limit) const {
@@ -974,35 +935,22 @@ class MmapIndex {
   std::vector<QueryResult> run_batch(const Query* queries, size_t n, const SearchParameters& params, bool parallel, Call&& call,
                                      Cpu&& cpu) const {
     if (!h_) return cpu();
-    const size_t dim = embedding_dim();
-    std::vector<int32_t> off(n + 1, 0);
-    for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + (int32_t)queries[i].n_tokens;
-    std::vector<float> flat((size_t)off[n] * dim);
-    for (size_t i = 0; i < n; ++i)
-      std::copy(queries[i].data, queries[i].data + queries[i].n_tokens * dim, flat.begin() + (size_t)off[i] * dim);
-    const size_t k = params.top_k;
-    std::vector<int64_t> ids(std::max<size_t>(n * k, 1));
-    std::vector<float> sc(std::max<size_t>(n * k, 1));
-    std::vector<int32_t> cnt(std::max<size_t>(n, 1));
+    const PackedQueries q = pack_queries(queries, n);
+    RowBuffers b(n, params.top_k);   // the crate's top_k as it is: top_k = 0 is a batch of empty results
     np_search_params p = params.c();
-    int rc = call(flat.data(), off.data(), &p, ids.data(), sc.data(), cnt.data());
-    std::vector<QueryResult> out(n);
-    for (size_t i = 0; i < n; ++i) out[i].query_id = i;
+    int rc = call(q.flat.data(), q.off.data(), &p, b.ids.data(), b.sc.data(), b.cnt.data());
     if (rc != NP_OK) {
       if (is_device_failure(rc)) {   // mid-flight device loss: flag it, hand this call to the CPU unless FORCE_GPU
         if (rc == NP_ERR_DEVICE_UNAVAILABLE) mark_hip_broken();   // an OutOfMemory of one call leaves the device usable
         if (!is_force_gpu() && cpu_fallback()) return cpu();
       }
-      if (parallel && rc == NP_ERR_SEARCH) return out;
+      if (parallel && rc == NP_ERR_SEARCH) return RowBuffers(n, 0).rows(n);   // n empty results (search.rs:656-660)
       check(rc);
     }
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < n; ++i)
       // ABI v5: a negative count (NP_COUNT_ABANDONED) marks a batch a sharded peer abandoned -- never a length
-      if (cnt[i] < 0) throw Error(NP_ERR_SEARCH, "Search failed: the batch was abandoned (a peer shard failed)");
-      out[i].passage_ids.assign(ids.begin() + i * k, ids.begin() + i * k + cnt[i]);
-      out[i].scores.assign(sc.begin() + i * k, sc.begin() + i * k + cnt[i]);
-    }
-    return out;
+      if (b.cnt[i] < 0) throw Error(NP_ERR_SEARCH, "Search failed: the batch was abandoned (a peer shard failed)");
+    return b.rows(n);
   }
 
  public:

@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -518,11 +519,19 @@ def pack_subsets(subsets, n_queries: int):
     return np.ascontiguousarray(ids, np.int64), off, qsub
 
 
+def _compiled(f, schema):
+    """A filter as callers give it -- a (condition, params) pair, a bare condition string or a CompiledFilter -- compiled."""
+    from . import filters as F
+    if isinstance(f, F.CompiledFilter):
+        return f
+    cond, params = (f, ()) if isinstance(f, str) else f
+    return F.compile_filter(cond, params, schema)
+
+
 def pack_filters(filters, n_queries: int, schema):
     """One filter per query -> (compiled distinct filters, query_filter i32 [n_queries], -1 = none).  `filters` has n_queries
     entries, each None, a (condition, params) pair, a bare condition string or a CompiledFilter.  Entries that compile to the
     same program share one filter: it is evaluated once.  Pure host code."""
-    from . import filters as F
     filters = list(filters)
     if len(filters) != n_queries:
         raise ValueError(f"filters has {len(filters)} entries for {n_queries} queries")
@@ -531,9 +540,7 @@ def pack_filters(filters, n_queries: int, schema):
     for i, f in enumerate(filters):
         if f is None:
             continue
-        if not isinstance(f, F.CompiledFilter):
-            cond, params = (f, ()) if isinstance(f, str) else f
-            f = F.compile_filter(cond, params, schema)
+        f = _compiled(f, schema)
         j = slot.get(f.key())
         if j is None:
             j = slot[f.key()] = len(progs)
@@ -582,12 +589,16 @@ def _pad_lists(lists, dtype, width=None):
     return flat.reshape(-1), np.asarray([a.size for a in arrs], np.int32), width
 
 
+def _fusion_mode(fusion) -> int:
+    """"rrf" / "relative_score" (or the NP_FUSE_* value itself) -> the fusion argument of the entries"""
+    from . import text as T
+    return T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion)
+
+
 def fuse(mode, alpha: float, top_k: int, sem_ids, sem_scores, kw_ids, kw_scores, index=None):
     """np_hip_fuse over a batch: per query a semantic and a keyword list (sequences of id / score arrays; the scores may be
     None for "rrf").  mode is "rrf" or "relative_score".  Returns per query (ids int64, scores float32).  `index` names the
     device (an MmapIndex; None = the current device)."""
-    from . import text as T
-    m = T.FUSION_MODES[mode] if isinstance(mode, str) else int(mode)
     B = len(sem_ids)
     if len(kw_ids) != B:
         raise ValueError(f"{B} semantic lists and {len(kw_ids)} keyword lists")
@@ -595,13 +606,10 @@ def fuse(mode, alpha: float, top_k: int, sem_ids, sem_scores, kw_ids, kw_scores,
     ki, kc, kw = _pad_lists(kw_ids, np.int64)
     ss = None if sem_scores is None else _pad_lists(sem_scores, np.float32, sw)[0]
     ks = None if kw_scores is None else _pad_lists(kw_scores, np.float32, kw)[0]
-    k = max(int(top_k), 1)
-    ids = np.zeros(max(B * k, 1), np.int64)
-    out = np.zeros(max(B * k, 1), np.float32)
-    cnt = np.zeros(max(B, 1), np.int32)
-    _check(lib().np_hip_fuse(None if index is None else index._h, m, float(alpha), int(top_k), B, _ptr(si), _ptr(ss), _ptr(sc), sw,
-                             _ptr(ki), _ptr(ks), _ptr(kc), kw, _ptr(ids), _ptr(out), _ptr(cnt)))
-    return [(ids[i * k: i * k + cnt[i]].copy(), out[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+    rows = _ResultRows(B, max(int(top_k), 1))
+    _check(lib().np_hip_fuse(None if index is None else index._h, _fusion_mode(mode), float(alpha), int(top_k), B, _ptr(si), _ptr(ss),
+                             _ptr(sc), sw, _ptr(ki), _ptr(ks), _ptr(kc), kw, *rows.ptrs()))
+    return [(r.passage_ids, r.scores) for r in rows.results()]
 
 
 def fuse_rrf(sem_ids, kw_ids, alpha: float, top_k: int, index=None):
@@ -1014,6 +1022,103 @@ class QueryResult:
     scores: np.ndarray       # f32
 
 
+def _empty_results(B):
+    return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
+
+
+class _ResultRows:
+    """The [B][k] ids and scores and the [B] counts a search entry fills (ResultStage on the C side): no output array is ever
+    empty (the max(..., 1) padding), row j lies at stride k and holds counts[j] entries.  k is the caller's, so that
+    max(top_k, 0) of the search_batch forms and max(top_k, 1) everywhere else stay visible where they are chosen."""
+
+    def __init__(self, B: int, k: int, arrays=None):
+        self.B, self.k = B, k
+        if arrays is None:
+            arrays = np.zeros(max(B * k, 1), np.int64), np.zeros(max(B * k, 1), np.float32), np.zeros(max(B, 1), np.int32)
+        self.ids, self.sc, self.cnt = arrays
+
+    def ptrs(self):
+        """The (out_ids, out_scores, out_counts) arguments"""
+        return _ptr(self.ids), _ptr(self.sc), _ptr(self.cnt)
+
+    def results(self, live=None, n_queries=None):
+        """One QueryResult per query, its ids and scores copied out of the padded arrays.  Row j is query j, or --
+        text_search skips its empty queries -- query live[j] of n_queries; a query without a row has an empty result."""
+        ids, sc, k = self.ids, self.sc, self.k
+        rows = [QueryResult(j, ids[j * k: j * k + c].copy(), sc[j * k: j * k + c].copy())
+                for j, c in enumerate(self.cnt[: self.B].tolist())]
+        if live is None:
+            return rows
+        out = _empty_results(n_queries)
+        for row, i in zip(rows, live):
+            row.query_id = i
+            out[i] = row
+        return out
+
+
+def _failed_batch(rc, parallel, B):
+    """The error policy of the search_batch forms (search.rs:650-674): None when the call succeeded; under `parallel` a
+    failed search (rc == 2) is B empty results (search.rs:656-660: a failed query yields an empty result); any other
+    failure raises the mapped error."""
+    if rc == 0:
+        return None
+    if parallel and rc == 2:
+        return _empty_results(B)
+    _check(rc)
+
+
+class _Scope(NamedTuple):
+    """The per-query scope of a call as the entries take it (CallSubsets / HostScope on the C side): the CSR of the batch's
+    distinct subsets (sid, soff, n_sub) with the queries' map into them (qmap, -1 = none), or the compiled filters `cf`
+    with the same map -- then there is no CSR and n_sub counts the filters.  `form` is what the caller gave: None, "subset",
+    "subsets" or "filters"."""
+    form: str | None
+    sid: np.ndarray | None
+    soff: np.ndarray | None
+    n_sub: int
+    qmap: np.ndarray | None
+    cf: "_CFilters | None"
+
+    @property
+    def csr(self):
+        """The (subset_ids, subset_offsets, n_subsets, query_subset) arguments"""
+        return _ptr(self.sid), _ptr(self.soff), self.n_sub, _ptr(self.qmap)
+
+    @property
+    def filter_args(self):
+        """The (filters, n_filters) arguments"""
+        cf = self.cf
+        return (None, 0) if cf is None else (cf.arr, cf.n)
+
+    def of_rows(self, live):
+        """The scope of the queries `live` alone: their entries of the map (one padding entry when none is left)"""
+        if self.qmap is None:
+            return self
+        return self._replace(qmap=np.ascontiguousarray(self.qmap[live], np.int32) if live else np.zeros(1, np.int32))
+
+
+def _csr_as_given(subset_ids, subset_offsets, query_subset, B):
+    """The CSR arrays of the *_csr methods as a _Scope: they reach the library as given (None = NULL, n_subsets =
+    len(subset_offsets) - 1) after the two checks that keep the library from reading past them."""
+    sid = None if subset_ids is None else np.ascontiguousarray(subset_ids, np.int64)
+    soff = None if subset_offsets is None else np.ascontiguousarray(subset_offsets, np.int64)
+    qsub = None if query_subset is None else np.ascontiguousarray(query_subset, np.int32)
+    if qsub is not None and qsub.size != B:
+        raise ValueError(f"query_subset has {qsub.size} entries for {B} queries")
+    if sid is not None and soff is not None and soff.size and int(soff[-1]) > sid.size:
+        raise ValueError(f"subset_offsets count {int(soff[-1])} ids, subset_ids has {sid.size}")
+    return _Scope("subsets", sid, soff, 0 if soff is None else soff.size - 1, qsub, None)
+
+
+def _filters_as_given(compiled, query_filter, B):
+    """The CompiledFilters (or a ready _CFilters) and the queries' map of the *_filtered methods as a _Scope."""
+    cf = compiled if isinstance(compiled, _CFilters) else _CFilters(list(compiled))
+    qf = np.ascontiguousarray(query_filter, np.int32)
+    if qf.size != B:
+        raise ValueError(f"query_filter has {qf.size} entries for {B} queries")
+    return _Scope("filters", None, None, cf.n, qf, cf)
+
+
 def _opts(device=0, shard_rank=0, shard_count=1, n_contexts=2, max_batch=64, max_query_tokens=64,
           workspace_bytes=0):
     return np_open_opts(device, shard_rank, shard_count, n_contexts, max_batch, max_query_tokens, workspace_bytes)
@@ -1260,23 +1365,21 @@ class MmapIndex:
         self.last_match_report = rep.as_dict()
         return bits
 
-    def _filters(self, filters, n_queries):
+    def _schema(self):
+        """The columns filters compile against: the handle's, or none (every column name is then unknown)"""
         from . import filters as F
-        progs, qf = pack_filters(filters, n_queries, self.schema if self.schema is not None else F.Schema())
+        return self.schema if self.schema is not None else F.Schema()
+
+    def _filters(self, filters, n_queries):
+        progs, qf = pack_filters(filters, n_queries, self._schema())
         return _CFilters(progs), qf
 
     def filter_ids(self, filters, counts_only: bool = False):
         """np_hip_filter_eval: for every filter -- a (condition, params) pair, a condition string or a CompiledFilter -- the
         global ids of the documents it selects (those this handle holds), ascending, as one int64 array each.  With
         counts_only the arrays are not fetched and the counts come back instead."""
-        from . import filters as F
-        sch = self.schema if self.schema is not None else F.Schema()
-        progs = []
-        for f in filters:
-            if not isinstance(f, F.CompiledFilter):
-                cond, params = (f, ()) if isinstance(f, str) else f
-                f = F.compile_filter(cond, params, sch)
-            progs.append(f)
+        sch = self._schema()
+        progs = [_compiled(f, sch) for f in filters]
         cf = _CFilters(progs)
         off = np.zeros(len(progs) + 1, np.int64)
         _check(lib().np_hip_filter_eval(self._h, cf.arr, cf.n, None, 0, _ptr(off)))
@@ -1298,43 +1401,30 @@ class MmapIndex:
         """np_hip_search_batch_filtered as it is: CompiledFilters and the queries' map (-1 = none) reach the library as given."""
         flat, off = self._pack(queries)
         B = len(queries)
-        k = max(int(params.top_k), 0)
-        ids = np.zeros(max(B * k, 1), np.int64)
-        sc = np.zeros(max(B * k, 1), np.float32)
-        cnt = np.zeros(max(B, 1), np.int32)
+        rows = _ResultRows(B, max(int(params.top_k), 0))
         p = params._c()
-        cf = compiled if isinstance(compiled, _CFilters) else _CFilters(list(compiled))
-        qf = np.ascontiguousarray(query_filter, np.int32)
-        if qf.size != B:
-            raise ValueError(f"query_filter has {qf.size} entries for {B} queries")
+        scope = _filters_as_given(compiled, query_filter, B)
         st = np_stats()
-        rc = lib().np_hip_search_batch_filtered(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), cf.arr,
-                                                cf.n, _ptr(qf), _ptr(ids), _ptr(sc), _ptr(cnt), C.byref(st))
-        if rc:
-            if parallel and rc == 2:  # search.rs:656-660: a failed query yields an empty result
-                return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
-            _check(rc)
+        rc = lib().np_hip_search_batch_filtered(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p),
+                                                *scope.filter_args, _ptr(scope.qmap), *rows.ptrs(), C.byref(st))
+        failed = _failed_batch(rc, parallel, B)
+        if failed is not None:
+            return failed
         self.last_stats = st.as_dict()
-        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+        return rows.results()
 
     def search_exact_filtered(self, queries, top_k: int, precision: int, compiled, query_filter):
         """np_hip_search_exact_filtered as it is."""
         flat, off = self._pack(queries)
         B = len(queries)
-        k = max(int(top_k), 1)
-        ids = np.zeros(max(B * k, 1), np.int64)
-        sc = np.zeros(max(B * k, 1), np.float32)
-        cnt = np.zeros(max(B, 1), np.int32)
-        cf = compiled if isinstance(compiled, _CFilters) else _CFilters(list(compiled))
-        qf = np.ascontiguousarray(query_filter, np.int32)
-        if qf.size != B:
-            raise ValueError(f"query_filter has {qf.size} entries for {B} queries")
+        rows = _ResultRows(B, max(int(top_k), 1))
+        scope = _filters_as_given(compiled, query_filter, B)
         st = np_stats()
         _check(lib().np_hip_search_exact_filtered(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), int(top_k),
-                                                  int(precision), cf.arr, cf.n, _ptr(qf), _ptr(ids), _ptr(sc), _ptr(cnt),
+                                                  int(precision), *scope.filter_args, _ptr(scope.qmap), *rows.ptrs(),
                                                   C.byref(st)))
         self.last_stats = st.as_dict()
-        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+        return rows.results()
 
     # -- keyword and hybrid search ------------------------------------------------------------------------
     def set_text(self, data, _entry="np_hip_index_set_text"):
@@ -1354,12 +1444,15 @@ class MmapIndex:
         self.text = data
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
 
+    def _load_text(self, index_path, what, set_text):
+        from . import text as T
+        data = T.TextIndexData.from_sqlite(os.path.join(index_path or self._dir(what), "metadata.db"))
+        set_text(data)
+        return data
+
     def load_text(self, index_path: str | None = None):
         """set_text from the metadata.db of an index directory (the crate's METADATA_FTS table); returns the TextIndexData."""
-        from . import text as T
-        data = T.TextIndexData.from_sqlite(os.path.join(index_path or self._dir("load_text"), "metadata.db"))
-        self.set_text(data)
-        return data
+        return self._load_text(index_path, "load_text", self.set_text)
 
     def set_text_shard(self, data):
         """np_hip_index_set_text_shard: set_text for a handle that holds a document shard.  `data` is the WHOLE table's
@@ -1370,10 +1463,7 @@ class MmapIndex:
 
     def load_text_shard(self, index_path: str | None = None):
         """set_text_shard from the metadata.db of an index directory; returns the (whole table's) TextIndexData."""
-        from . import text as T
-        data = T.TextIndexData.from_sqlite(os.path.join(index_path or self._dir("load_text_shard"), "metadata.db"))
-        self.set_text_shard(data)
-        return data
+        return self._load_text(index_path, "load_text_shard", self.set_text_shard)
 
     def _text_queries(self, text_queries, empty_matches_nothing: bool):
         """Strings are compiled against self.text, TextQuery objects pass; '' (text_search.rs:1247: an empty query has an
@@ -1391,54 +1481,58 @@ class MmapIndex:
             out.append(q)
         return out
 
-    def _scope(self, B, subset, subsets, filters, what):
-        """(subset_ids, subset_offsets, n_subsets, query_subset, _CFilters or None) of the per-query scope arguments."""
+    def _scope(self, B, subset, subsets, filters, what) -> _Scope:
+        """The per-query scope arguments of the method `what` as a _Scope: the one place where filters= / subsets= /
+        subset= are told apart and refused together."""
         if filters is not None:
             if subset is not None or subsets is not None:
                 raise ValueError(f"{what} takes filters= or subset= / subsets=, not both")
             cf, qf = self._filters(filters, B)
-            return None, None, cf.n, qf, cf
+            return _Scope("filters", None, None, cf.n, qf, cf)
         if subsets is not None:
             if subset is not None:
                 raise ValueError(f"{what} takes subset= (one for the batch) or subsets= (one per query), not both")
             sid, soff, qsub = pack_subsets(subsets, B)
-            return sid, soff, soff.size - 1, qsub, None
+            return _Scope("subsets", sid, soff, soff.size - 1, qsub, None)
         if subset is not None:
             sid = np.ascontiguousarray(subset, np.int64).reshape(-1)
-            return sid, np.array([0, sid.size], np.int64), 1, np.zeros(max(B, 1), np.int32), None
-        return None, None, 0, None, None
+            return _Scope("subset", sid, np.array([0, sid.size], np.int64), 1, np.zeros(max(B, 1), np.int32), None)
+        return _Scope(None, None, None, 0, None, None)
+
+    def _live_text_queries(self, text_queries, subset, subsets, filters):
+        """The prologue of text_search, here and over the shards: (B, live, their compiled queries, the scope of those).  An
+        empty query is not searched: `live` lists the positions of the others, which are all the library sees."""
+        if isinstance(text_queries, str):
+            text_queries = [text_queries]
+        qs = self._text_queries(list(text_queries), False)
+        live = [i for i, q in enumerate(qs) if q is not None]
+        scope = self._scope(len(qs), subset, subsets, filters, "text_search").of_rows(live)
+        return len(qs), live, [qs[i] for i in live], scope
+
+    def _hybrid_text_queries(self, B, text_queries):
+        """The text half of the hybrid-shaped calls, one per query: an empty one matches nothing (its keyword list is empty)."""
+        qs = self._text_queries(list(text_queries), True)
+        if len(qs) != B:
+            raise ValueError(f"{B} queries and {len(qs)} text queries")
+        return _CTextQueries(qs)
 
     def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None):
         """np_hip_text_search: BM25 keyword search with SQLite FTS5's results (text_search.rs:1246-1342) -- for every query
         the top_k documents by -bm25(), f64 score descending, ties by ascending id.  A query is FTS5 text (compiled by
         text.compile_text_query against the handle's keyword index) or a text.TextQuery; '' returns an empty result.  Scope:
         `subset`, `subsets` or `filters` as search_exact takes them.  Returns QueryResults."""
-        if isinstance(text_queries, str):
-            text_queries = [text_queries]
-        qs = self._text_queries(list(text_queries), False)
-        B = len(qs)
-        live = [i for i, q in enumerate(qs) if q is not None]
-        res = [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
-        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "text_search")
-        if qsub is not None:
-            qsub = np.ascontiguousarray(qsub[live], np.int32) if live else np.zeros(1, np.int32)
+        B, live, qs, scope = self._live_text_queries(text_queries, subset, subsets, filters)
         n = len(live)
-        tq = _CTextQueries([qs[i] for i in live])
-        k = max(int(top_k), 1)
-        ids = np.zeros(max(n * k, 1), np.int64)
-        sc = np.zeros(max(n * k, 1), np.float32)
-        cnt = np.zeros(max(n, 1), np.int32)
+        tq = _CTextQueries(qs)
+        rows = _ResultRows(n, max(int(top_k), 1))
         st = np_stats()
-        if cf is not None:
-            _check(lib().np_hip_text_search_filtered(self._h, tq.arr, n, int(top_k), cf.arr, cf.n, _ptr(qsub), _ptr(ids), _ptr(sc),
-                                                     _ptr(cnt), C.byref(st)))
+        if scope.cf is not None:
+            _check(lib().np_hip_text_search_filtered(self._h, tq.arr, n, int(top_k), *scope.filter_args, _ptr(scope.qmap),
+                                                     *rows.ptrs(), C.byref(st)))
         else:
-            _check(lib().np_hip_text_search(self._h, tq.arr, n, int(top_k), _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), _ptr(ids),
-                                            _ptr(sc), _ptr(cnt), C.byref(st)))
+            _check(lib().np_hip_text_search(self._h, tq.arr, n, int(top_k), *scope.csr, *rows.ptrs(), C.byref(st)))
         self.last_stats = st.as_dict()
-        for j, i in enumerate(live):
-            res[i] = QueryResult(i, ids[j * k: j * k + cnt[j]].copy(), sc[j * k: j * k + cnt[j]].copy())
-        return res
+        return rows.results(live, B)
 
     def search_hybrid(self, queries, text_queries, params: "SearchParameters", alpha: float = 0.75,
                       fusion: str = "relative_score", fetch_k: int | None = None, subset=None, subsets=None, filters=None):
@@ -1446,28 +1540,20 @@ class MmapIndex:
         the keyword pass with top_k = fetch_k (default: the handler's 3 * params.top_k) and their fusion ("relative_score",
         the default, or "rrf") to params.top_k, on the device.  Query i gets what fuse(...) returns for search_batch and
         text_search with top_k = fetch_k.  An empty text query contributes an empty keyword list.  Returns QueryResults."""
-        from . import text as T
         queries = list(queries)
         flat, off = self._pack(queries)
         B = len(queries)
-        qs = self._text_queries(list(text_queries), True)
-        if len(qs) != B:
-            raise ValueError(f"{B} queries and {len(qs)} text queries")
+        tq = self._hybrid_text_queries(B, text_queries)
         fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
-        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "search_hybrid")
-        tq = _CTextQueries(qs)
-        k = max(int(params.top_k), 1)
-        ids = np.zeros(max(B * k, 1), np.int64)
-        sc = np.zeros(max(B * k, 1), np.float32)
-        cnt = np.zeros(max(B, 1), np.int32)
+        scope = self._scope(B, subset, subsets, filters, "search_hybrid")
+        rows = _ResultRows(B, max(int(params.top_k), 1))
         p = params._c()
         st = np_stats()
         _check(lib().np_hip_search_hybrid(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), tq.arr, fk,
-                                          float(alpha), T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion),
-                                          _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), None if cf is None else cf.arr,
-                                          0 if cf is None else cf.n, _ptr(ids), _ptr(sc), _ptr(cnt), C.byref(st)))
+                                          float(alpha), _fusion_mode(fusion), *scope.csr, *scope.filter_args, *rows.ptrs(),
+                                          C.byref(st)))
         self.last_stats = st.as_dict()
-        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+        return rows.results()
 
     # -- grouped search -----------------------------------------------------------------------------------
     def set_groups(self, keys, n_groups: int | None = None):
@@ -1518,15 +1604,13 @@ class MmapIndex:
         flat, off = self._pack(queries)
         B = len(queries)
         pk = default_pool_k(params.top_k, self.num_documents()) if pool_k is None else int(pool_k)
-        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "search_grouped")
+        scope = self._scope(B, subset, subsets, filters, "search_grouped")
         k, g = max(int(params.top_k), 1), max(int(group_size), 1)
         out = _group_outputs(B, k, g)
         p = params._c()
         st = np_stats()
-        _check(lib().np_hip_search_batch_grouped(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), _ptr(sid),
-                                                 _ptr(soff), n_sub, _ptr(qsub), None if cf is None else cf.arr,
-                                                 0 if cf is None else cf.n, pk, int(group_size), *[_ptr(o) for o in out],
-                                                 C.byref(st)))
+        _check(lib().np_hip_search_batch_grouped(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), *scope.csr,
+                                                 *scope.filter_args, pk, int(group_size), *[_ptr(o) for o in out], C.byref(st)))
         self.last_stats = st.as_dict()
         return out if raw else _groups_of_rows(B, k, g, *out)
 
@@ -1541,22 +1625,17 @@ class MmapIndex:
         queries = list(queries)
         flat, off = self._pack(queries)
         B = len(queries)
-        qs = self._text_queries(list(text_queries), True)
-        if len(qs) != B:
-            raise ValueError(f"{B} queries and {len(qs)} text queries")
+        tq = self._hybrid_text_queries(B, text_queries)
         pk = default_pool_k(params.top_k, self.num_documents(), 2 * T.NP_TEXT_MAX_TOPK) if pool_k is None else int(pool_k)
         fk = min(3 * pk, T.NP_TEXT_MAX_TOPK) if fetch_k is None else int(fetch_k)
-        sid, soff, n_sub, qsub, cf = self._scope(B, subset, subsets, filters, "search_hybrid_grouped")
-        tq = _CTextQueries(qs)
+        scope = self._scope(B, subset, subsets, filters, "search_hybrid_grouped")
         k, g = max(int(params.top_k), 1), max(int(group_size), 1)
         out = _group_outputs(B, k, g)
         p = params._c()
         st = np_stats()
         _check(lib().np_hip_search_hybrid_grouped(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), tq.arr, fk,
-                                                  float(alpha), T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion),
-                                                  _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), None if cf is None else cf.arr,
-                                                  0 if cf is None else cf.n, pk, int(group_size), *[_ptr(o) for o in out],
-                                                  C.byref(st)))
+                                                  float(alpha), _fusion_mode(fusion), *scope.csr, *scope.filter_args, pk,
+                                                  int(group_size), *[_ptr(o) for o in out], C.byref(st)))
         self.last_stats = st.as_dict()
         return _groups_of_rows(B, k, g, *out)
 
@@ -1593,35 +1672,26 @@ class MmapIndex:
         `filters` gives every query a WHERE condition over the handle's columns instead (set_columns): one entry per query,
         None or (condition, params); the ids are computed on the device and query i gets what subsets=[ids the filter
         selects, ascending] returns.  Equal entries are compiled and evaluated once.  Not together with subset / subsets."""
-        if filters is not None:
-            if subset is not None or subsets is not None:
-                raise ValueError("search_batch takes filters= or subset= / subsets=, not both")
-            queries = list(queries)
-            cf, qf = self._filters(filters, len(queries))
-            return self.search_batch_filtered(queries, params, cf, qf, parallel=parallel)
-        if subsets is not None:
-            if subset is not None:
-                raise ValueError("search_batch takes subset= (one for the batch) or subsets= (one per query), not both")
-            return self.search_batch_csr(queries, params, *pack_subsets(subsets, len(queries)), parallel=parallel)
-        flat, off = self._pack(queries)
+        queries = list(queries)
         B = len(queries)
-        k = max(int(params.top_k), 0)
-        ids = np.zeros(max(B * k, 1), np.int64)
-        sc = np.zeros(max(B * k, 1), np.float32)
-        cnt = np.zeros(max(B, 1), np.int32)
+        scope = self._scope(B, subset, subsets, filters, "search_batch")
+        if scope.form == "filters":
+            return self.search_batch_filtered(queries, params, scope.cf, scope.qmap, parallel=parallel)
+        if scope.form == "subsets":
+            return self.search_batch_csr(queries, params, scope.sid, scope.soff, scope.qmap, parallel=parallel)
+        # the crate's own argument, one subset for the batch, stays on the crate's entry: its ids alone, a length of -1 = none
+        flat, off = self._pack(queries)
+        rows = _ResultRows(B, max(int(params.top_k), 0))
         p = params._c()
-        sub = None if subset is None else np.ascontiguousarray(subset, np.int64)
+        sub = scope.sid
         st = np_stats()
         rc = lib().np_hip_search_batch(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p),
-                                       _ptr(sub), -1 if sub is None else sub.size, _ptr(ids), _ptr(sc), _ptr(cnt),
-                                       C.byref(st))
-        if rc:
-            if parallel and rc == 2:  # search.rs:656-660: a failed query yields an empty result
-                return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
-            _check(rc)
+                                       _ptr(sub), -1 if sub is None else sub.size, *rows.ptrs(), C.byref(st))
+        failed = _failed_batch(rc, parallel, B)
+        if failed is not None:
+            return failed
         self.last_stats = st.as_dict()
-        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy())
-                for i in range(B)]
+        return rows.results()
 
     def search_batch_csr(self, queries, params: SearchParameters, subset_ids, subset_offsets, query_subset,
                          parallel: bool = True):
@@ -1630,30 +1700,17 @@ class MmapIndex:
         are the ones that answer."""
         flat, off = self._pack(queries)
         B = len(queries)
-        k = max(int(params.top_k), 0)
-        ids = np.zeros(max(B * k, 1), np.int64)
-        sc = np.zeros(max(B * k, 1), np.float32)
-        cnt = np.zeros(max(B, 1), np.int32)
+        rows = _ResultRows(B, max(int(params.top_k), 0))
         p = params._c()
-        sid = None if subset_ids is None else np.ascontiguousarray(subset_ids, np.int64)
-        soff = None if subset_offsets is None else np.ascontiguousarray(subset_offsets, np.int64)
-        qsub = None if query_subset is None else np.ascontiguousarray(query_subset, np.int32)
-        if qsub is not None and qsub.size != B:
-            raise ValueError(f"query_subset has {qsub.size} entries for {B} queries")
-        n_sub = 0 if soff is None else soff.size - 1
-        if sid is not None and soff is not None and soff.size and int(soff[-1]) > sid.size:
-            raise ValueError(f"subset_offsets count {int(soff[-1])} ids, subset_ids has {sid.size}")
+        scope = _csr_as_given(subset_ids, subset_offsets, query_subset, B)
         st = np_stats()
         rc = lib().np_hip_search_batch_subsets(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p),
-                                               _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), _ptr(ids), _ptr(sc), _ptr(cnt),
-                                               C.byref(st))
-        if rc:
-            if parallel and rc == 2:  # search.rs:656-660: a failed query yields an empty result
-                return [QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
-            _check(rc)
+                                               *scope.csr, *rows.ptrs(), C.byref(st))
+        failed = _failed_batch(rc, parallel, B)
+        if failed is not None:
+            return failed
         self.last_stats = st.as_dict()
-        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy())
-                for i in range(B)]
+        return rows.results()
 
     def search_exact(self, queries, top_k: int, precision: int = 0, subset=None, subsets=None, filters=None):
         """np_hip_search_exact: for every query the true top_k of its scope by exact MaxSim over the decompressed index,
@@ -1665,44 +1722,25 @@ class MmapIndex:
             queries = [queries]
         queries = list(queries)
         B = len(queries)
-        if filters is not None:   # one WHERE condition per query (None or (condition, params)), as search_batch takes them
-            if subset is not None or subsets is not None:
-                raise ValueError("search_exact takes filters= or subset= / subsets=, not both")
-            cf, qf = self._filters(filters, B)
-            return self.search_exact_filtered(queries, top_k, precision, cf, qf)
-        if subsets is not None:
-            if subset is not None:
-                raise ValueError("search_exact takes subset= (one for the batch) or subsets= (one per query), not both")
-            sid, soff, qsub = pack_subsets(subsets, B)
-        elif subset is not None:
-            sid = np.ascontiguousarray(subset, np.int64).reshape(-1)
-            soff, qsub = np.array([0, sid.size], np.int64), np.zeros(B, np.int32)
-        else:
-            sid, soff, qsub = None, None, None
-        return self.search_exact_csr(queries, top_k, precision, sid, soff, qsub)
+        scope = self._scope(B, subset, subsets, filters, "search_exact")
+        if scope.form == "filters":   # one WHERE condition per query (None or (condition, params)), as search_batch takes them
+            return self.search_exact_filtered(queries, top_k, precision, scope.cf, scope.qmap)
+        # search_exact_csr wants exactly one map entry per query: the one-subset map, padded to one entry for an empty
+        # batch, goes without its padding
+        qsub = None if scope.qmap is None else scope.qmap[:B]
+        return self.search_exact_csr(queries, top_k, precision, scope.sid, scope.soff, qsub)
 
     def search_exact_csr(self, queries, top_k: int, precision: int, subset_ids, subset_offsets, query_subset):
         """np_hip_search_exact as it is: the CSR arrays reach the library as given (None = NULL), so its checks answer."""
         flat, off = self._pack(queries)
         B = len(queries)
-        k = max(int(top_k), 1)
-        ids = np.zeros(max(B * k, 1), np.int64)
-        sc = np.zeros(max(B * k, 1), np.float32)
-        cnt = np.zeros(max(B, 1), np.int32)
-        sid = None if subset_ids is None else np.ascontiguousarray(subset_ids, np.int64)
-        soff = None if subset_offsets is None else np.ascontiguousarray(subset_offsets, np.int64)
-        qsub = None if query_subset is None else np.ascontiguousarray(query_subset, np.int32)
-        if qsub is not None and qsub.size != B:
-            raise ValueError(f"query_subset has {qsub.size} entries for {B} queries")
-        n_sub = 0 if soff is None else soff.size - 1
-        if sid is not None and soff is not None and soff.size and int(soff[-1]) > sid.size:
-            raise ValueError(f"subset_offsets count {int(soff[-1])} ids, subset_ids has {sid.size}")
+        rows = _ResultRows(B, max(int(top_k), 1))
+        scope = _csr_as_given(subset_ids, subset_offsets, query_subset, B)
         st = np_stats()
         _check(lib().np_hip_search_exact(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), int(top_k), int(precision),
-                                         _ptr(sid), _ptr(soff), n_sub, _ptr(qsub), _ptr(ids), _ptr(sc), _ptr(cnt),
-                                         C.byref(st)))
+                                         *scope.csr, *rows.ptrs(), C.byref(st)))
         self.last_stats = st.as_dict()
-        return [QueryResult(i, ids[i * k: i * k + cnt[i]].copy(), sc[i * k: i * k + cnt[i]].copy()) for i in range(B)]
+        return rows.results()
 
     def score_pairs(self, queries, doc_ids, return_matches: bool = True, precision: int = 0):
         """np_hip_score_pairs: the exact MaxSim of given (query, document) pairs and, per query token, its best document

@@ -365,22 +365,14 @@ class CShardedSearcher:
         if isinstance(d_subset, DeviceSubsets):   # one subset per query
             rc = api.lib().np_hip_search_batch_sharded_subsets(
                 self.index._h, self.comm._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()),
-                hq.ctypes.data_as(C.c_void_p), B, self.index.embedding_dim(), C.byref(p), *d_subset.args(),
-                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
-                C.c_void_p(self.stream.cuda_stream))
+                hq.ctypes.data_as(C.c_void_p), B, self.index.embedding_dim(), C.byref(p), *d_subset.args(), *self._out_args(out))
         else:
             rc = api.lib().np_hip_search_batch_sharded(
                 self.index._h, self.comm._h, C.c_void_p(d_q.data_ptr()), C.c_void_p(d_qoff.data_ptr()),
                 hq.ctypes.data_as(C.c_void_p), B, self.index.embedding_dim(), C.byref(p),
                 None if d_subset is None else C.c_void_p(d_subset.data_ptr()), -1 if d_subset is None else d_subset.numel(),
-                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
-                C.c_void_p(self.stream.cuda_stream))
-        if rc != 0:
-            msg = api.last_error()
-            # a failed batch must not leave its status word behind for the next healthy one: drain it before raising
-            self.stream.synchronize()
-            self.comm.status()
-            api._check(rc, msg)
+                *self._out_args(out))
+        self._raise_failed(rc)
         return out
 
     def _outputs(self, B, k):
@@ -388,58 +380,57 @@ class CShardedSearcher:
         return (t.zeros((max(B, 1), k), dtype=t.int64, device=self.device), t.zeros((max(B, 1), k), dtype=t.float32, device=self.device),
                 t.zeros(max(B, 1), dtype=t.int32, device=self.device))
 
-    def _finish(self, rc, out, n):
-        """The end of a one-call batch: (ids, scores, counts) on the host, or the call's error / the abandoned batch raised."""
+    def _out_args(self, out):
+        """The (d_out_ids, d_out_scores, d_out_counts, stream) arguments every sharded entry ends with"""
+        return (C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
+                C.c_void_p(self.stream.cuda_stream))
+
+    def _raise_failed(self, rc):
+        """A sharded entry's own error, raised with its message."""
         if rc != 0:
             msg = api.last_error()
             # a failed batch must not leave its status word behind for the next healthy one: drain it before raising
             self.stream.synchronize()
             self.comm.status()
             api._check(rc, msg)
+
+    def _finish(self, rc, out, n, live=None, n_queries=None):
+        """The end of a one-call batch: the QueryResults of its n rows on the host (row j is query j, or query live[j] of
+        n_queries: api._ResultRows.results), or the call's error / the abandoned batch raised."""
+        self._raise_failed(rc)
         ids, sc, cnt = (o.cpu().numpy() for o in out)
         self.stream.synchronize()
         rank, code = self.comm.status()   # a peer's failure abandons the batch on every rank: counts = -1 (np_dist.hip)
         if code or (cnt[:n] < 0).any():
             raise api.SearchError(f"Search failed: shard {rank} failed with status {code}; the batch was abandoned on every rank")
-        return ids, sc, cnt
+        return api._ResultRows(n, ids.shape[1], (ids.reshape(-1), sc.reshape(-1), cnt)).results(live, n_queries)
 
     def _device_queries(self, queries):
+        """MmapIndex._pack, then the flat queries and their offsets on the device (and the offsets' host copy).  A query that
+        does not fit the index raises ShapeError before anything is copied."""
         t = self.torch
-        qs = [np.ascontiguousarray(q, np.float32) for q in queries]
-        d = self.index.embedding_dim()
-        for q in qs:
-            if q.ndim != 2 or q.shape[1] != d:
-                raise api.ShapeError(f"Shape error: query has shape {q.shape}, index dim is {d}")
-        off = np.zeros(len(qs) + 1, np.int32)
-        if qs:
-            off[1:] = np.cumsum([q.shape[0] for q in qs])
-        flat = np.concatenate(qs, 0) if qs else np.zeros((0, d), np.float32)
-        return t.from_numpy(np.ascontiguousarray(flat, np.float32)).to(self.device), t.from_numpy(off).to(self.device), off
+        flat, off = self.index._pack(queries)
+        with t.cuda.stream(self.stream):
+            return t.from_numpy(flat).to(self.device), t.from_numpy(off).to(self.device), off
 
-    def _device_scope(self, sid, soff, n_sub, qsub):
-        """The host CSR of MmapIndex._scope as the device arguments of the sharded entries."""
-        if n_sub == 0:
+    def _device_scope(self, scope):
+        """The host CSR of MmapIndex._scope as the device arguments of the sharded entries (none under filters)."""
+        if scope.n_sub == 0 or scope.cf is not None:
             return None, (None, None, None, 0, None)
-        ds = DeviceSubsets(self.torch, self.device, sid if sid is not None else np.zeros(0, np.int64), soff, qsub)
+        ds = DeviceSubsets(self.torch, self.device, scope.sid if scope.sid is not None else np.zeros(0, np.int64), scope.soff,
+                           scope.qmap)
         return ds, ds.args()
 
-    def _search_filtered(self, queries, params, filters):
-        t = self.torch
-        queries = list(queries)
-        cf, qf = self.index._filters(filters, len(queries))
-        qf = np.ascontiguousarray(qf, np.int32)
+    def _search_filtered(self, queries, params, scope):
         B, k = len(queries), max(int(params.top_k), 1)
         p = params._c()
-        with t.cuda.stream(self.stream):
-            dq, do, off = self._device_queries(queries)
+        dq, do, off = self._device_queries(queries)
+        with self.torch.cuda.stream(self.stream):
             out = self._outputs(B, k)
             rc = api.lib().np_hip_search_batch_sharded_filtered(
                 self.index._h, self.comm._h, C.c_void_p(dq.data_ptr()), C.c_void_p(do.data_ptr()), off.ctypes.data_as(C.c_void_p),
-                B, self.index.embedding_dim(), C.byref(p), cf.arr, cf.n, qf.ctypes.data_as(C.c_void_p),
-                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
-                C.c_void_p(self.stream.cuda_stream))
-            ids, sc, cnt = self._finish(rc, out, B)
-        return [api.QueryResult(i, ids[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(B)]
+                B, self.index.embedding_dim(), C.byref(p), *scope.filter_args, api._ptr(scope.qmap), *self._out_args(out))
+            return self._finish(rc, out, B)
 
     def text_search_device(self, queries, top_k: int, d_subsets=None, filters=None, out=None):
         """np_hip_text_search_sharded / _filtered as they are: text.TextQuery objects, the scope as a DeviceSubsets or as
@@ -451,8 +442,7 @@ class CShardedSearcher:
         with t.cuda.stream(self.stream):
             if out is None:
                 out = self._outputs(n, k)
-            o = (C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
-                 C.c_void_p(self.stream.cuda_stream))
+            o = self._out_args(out)
             if filters is not None:
                 cf, qf = filters
                 qf = np.ascontiguousarray(qf, np.int32)
@@ -465,78 +455,48 @@ class CShardedSearcher:
 
     def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None):
         """MmapIndex.text_search over the shards (np_hip_text_search_sharded, np_hip_text_search_sharded_filtered)."""
-        t = self.torch
-        if isinstance(text_queries, str):
-            text_queries = [text_queries]
-        qs = self.index._text_queries(list(text_queries), False)
-        B = len(qs)
-        live = [i for i, q in enumerate(qs) if q is not None]
-        res = [api.QueryResult(i, np.zeros(0, np.int64), np.zeros(0, np.float32)) for i in range(B)]
-        sid, soff, n_sub, qsub, cf = self.index._scope(B, subset, subsets, filters, "text_search")
-        if qsub is not None:
-            qsub = np.ascontiguousarray(np.asarray(qsub)[live], np.int32) if live else np.zeros(1, np.int32)
-        n = len(live)
-        with t.cuda.stream(self.stream):
-            if cf is not None:
-                rc, out = self.text_search_device([qs[i] for i in live], top_k, filters=(cf, qsub))
+        B, live, qs, scope = self.index._live_text_queries(text_queries, subset, subsets, filters)
+        with self.torch.cuda.stream(self.stream):
+            if scope.cf is not None:
+                rc, out = self.text_search_device(qs, top_k, filters=(scope.cf, scope.qmap))
             else:
-                rc, out = self.text_search_device([qs[i] for i in live], top_k, d_subsets=self._device_scope(sid, soff, n_sub, qsub)[0])
-            ids, sc, cnt = self._finish(rc, out, n)
-        for j, i in enumerate(live):
-            res[i] = api.QueryResult(i, ids[j, : cnt[j]].copy(), sc[j, : cnt[j]].copy())
-        return res
+                rc, out = self.text_search_device(qs, top_k, d_subsets=self._device_scope(scope)[0])
+            return self._finish(rc, out, len(live), live, B)
 
     def search_hybrid(self, queries, text_queries, params, alpha: float = 0.75, fusion: str = "relative_score",
                       fetch_k: int | None = None, subsets=None, filters=None):
         """MmapIndex.search_hybrid over the shards (np_hip_search_hybrid_sharded): both global lists are merged on every rank,
         every rank fuses."""
-        from . import text as T
+        queries = list(queries)
+        B = len(queries)
+        tq = self.index._hybrid_text_queries(B, text_queries)
+        fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
+        scope = self.index._scope(B, None, subsets, filters, "search_hybrid")
+        k = max(int(params.top_k), 1)
+        p = params._c()
+        with self.torch.cuda.stream(self.stream):
+            dq, do, off = self._device_queries(queries)
+            out = self._outputs(B, k)
+            keep, a = self._device_scope(scope)
+            qf = scope.qmap if scope.cf is not None else None   # (without filters the map travels with the CSR, on the device)
+            rc = api.lib().np_hip_search_hybrid_sharded(
+                self.index._h, self.comm._h, C.c_void_p(dq.data_ptr()), C.c_void_p(do.data_ptr()), off.ctypes.data_as(C.c_void_p),
+                B, self.index.embedding_dim(), C.byref(p), tq.arr, fk, float(alpha), api._fusion_mode(fusion), *a,
+                *scope.filter_args, api._ptr(qf), *self._out_args(out))
+            return self._finish(rc, out, B)
+
+    def search_batch(self, queries, params, subset=None, subsets=None, filters=None):
         t = self.torch
         queries = list(queries)
         B = len(queries)
-        qs = self.index._text_queries(list(text_queries), True)
-        if len(qs) != B:
-            raise ValueError(f"{B} queries and {len(qs)} text queries")
-        fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
-        sid, soff, n_sub, qsub, cf = self.index._scope(B, None, subsets, filters, "search_hybrid")
-        tq = api._CTextQueries(qs)
-        k = max(int(params.top_k), 1)
-        p = params._c()
+        scope = self.index._scope(B, subset, subsets, filters, "search_batch")
+        if scope.form == "filters":
+            return self._search_filtered(queries, params, scope)
+        dq, do, off = self._device_queries(queries)
         with t.cuda.stream(self.stream):
-            dq, do, off = self._device_queries(queries)
-            out = self._outputs(B, k)
-            keep, a = (None, (None, None, None, 0, None)) if cf is not None else self._device_scope(sid, soff, n_sub, qsub)
-            qf = None if cf is None else np.ascontiguousarray(qsub, np.int32)
-            rc = api.lib().np_hip_search_hybrid_sharded(
-                self.index._h, self.comm._h, C.c_void_p(dq.data_ptr()), C.c_void_p(do.data_ptr()), off.ctypes.data_as(C.c_void_p),
-                B, self.index.embedding_dim(), C.byref(p), tq.arr, fk, float(alpha),
-                T.FUSION_MODES[fusion] if isinstance(fusion, str) else int(fusion), *a,
-                None if cf is None else cf.arr, 0 if cf is None else cf.n, None if qf is None else qf.ctypes.data_as(C.c_void_p),
-                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(out[2].data_ptr()),
-                C.c_void_p(self.stream.cuda_stream))
-            ids, sc, cnt = self._finish(rc, out, B)
-        return [api.QueryResult(i, ids[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(B)]
-
-    def search_batch(self, queries, params, subset=None, subsets=None, filters=None):
-        if filters is not None:
-            if subset is not None or subsets is not None:
-                raise ValueError("search_batch takes filters= or subset= / subsets=, not both")
-            return self._search_filtered(queries, params, filters)
-        t = self.torch
-        packed = _packed_subsets(subset, subsets, len(queries))
-        qs = [np.ascontiguousarray(q, np.float32) for q in queries]
-        off = np.zeros(len(qs) + 1, np.int32)
-        off[1:] = np.cumsum([q.shape[0] for q in qs])
-        with t.cuda.stream(self.stream):
-            dq = t.from_numpy(np.concatenate(qs, 0)).to(self.device)
-            do = t.from_numpy(off).to(self.device)
-            ds = None if subset is None else t.from_numpy(np.ascontiguousarray(subset, np.int64)).to(self.device)
-            if packed is not None:
-                ds = DeviceSubsets(t, self.device, *packed)
-            ids, sc, cnt = self.search_batch_device(dq, do, off, params, ds)
-            ids, sc, cnt = ids.cpu().numpy(), sc.cpu().numpy(), cnt.cpu().numpy()
-        self.stream.synchronize()
-        rank, code = self.comm.status()   # a peer's failure abandons the batch on every rank: counts = -1 (np_dist.hip)
-        if code or (cnt < 0).any():
-            raise api.SearchError(f"Search failed: shard {rank} failed with status {code}; the batch was abandoned on every rank")
-        return [api.QueryResult(i, ids[i, : cnt[i]].copy(), sc[i, : cnt[i]].copy()) for i in range(len(qs))]
+            ds = None   # one subset for the batch: its ids alone; one per query: the CSR and the map
+            if scope.form == "subset":
+                ds = t.from_numpy(scope.sid).to(self.device)
+            elif scope.form == "subsets":
+                ds = DeviceSubsets(t, self.device, scope.sid, scope.soff, scope.qmap)
+            return self._finish(0, self.search_batch_device(dq, do, off, params, ds), B)
