@@ -1203,6 +1203,101 @@ int np_hip_pool_documents(int32_t device, const float* embeddings, const int64_t
                           const np_pool_opts* opts, float* out_embeddings, int64_t out_rows_capacity, int64_t* out_lengths,
                           int32_t* out_labels, double* out_linkage, np_pool_report* report);
 
+/* ---- Building the keyword index on the device (np_textbuild.hip; DESIGN.md section 4, "Building the keyword index") ----
+ * From raw document text to the arrays np_hip_index_set_text takes, equal array for array to what SQLite's FTS5 gives for
+ * the same rows (fts5vocab 'instance': every (term, document, position), terms in memcmp order, the shorter string first).
+ * Input: the documents' UTF-8 bytes concatenated and offsets[n_docs + 1] into them (host pointers, uploaded by the call);
+ * document i is the FTS5 row with rowid i.  Needs no index.
+ *
+ * The device reproduces SQLite for ASCII text only:
+ *   NP_TOK_UNICODE61  token characters are [0-9A-Za-z]; every other byte 0x00..0x7F separates (NUL too); A-Z fold to a-z;
+ *                     positions count tokens from 0
+ *   NP_TOK_TRIGRAM    every byte offset i <= len - 3 is a token: the three bytes, A-Z folded, at position i
+ * A document it cannot reproduce is a FALLBACK document: it contributes no instance, its id is listed by
+ * np_hip_text_build_fallback, and the caller tokenises it (with SQLite) and hands its instances to np_hip_text_build_add.
+ * Fallback rules: any byte >= 0x80; trigram: a NUL byte (it ends the text for SQLite); unicode61: a token longer than
+ * max_token_bytes (1..32768, 0 = 256; SQLite cuts a token at 32768).  The cap only moves documents to the list: it never
+ * changes the result.
+ *
+ * Stages (each a sequence of launches; no workgroup waits for another inside a launch, only integer atomics are used and
+ * no result depends on the order in which they arrive):
+ *   classify  one wave per document over 16-byte loads: the fallback verdict and the document's token count; an exclusive
+ *             scan of the counts places every document's first instance
+ *   emit      the same walk writes instance n = (document, byte offset in the document, length): (document, position) order
+ *             by construction
+ *   terms     unicode61: an open-addressing table of instance indexes claimed by atomicCAS; a lane that finds a slot taken
+ *             compares its token's folded bytes with the bytes of the instance in the slot (both in the immutable text), so
+ *             a hash collision never merges two terms; a table that fills up is counted, detected on the host and the stage
+ *             repeated with twice the slots (report->table_retries).  The occupied slots are compacted, the host sorts
+ *             their strings and a slot's rank is its term id.  trigram: a presence bitmap over the 21-bit folded keys and a
+ *             popcount scan give the rank directly
+ *   order     a stable LSD radix sort of (term id, instance index) by term id, 8 bits a pass (histogram, scan, scatter),
+ *             ceil(bits(n_terms - 1) / 8) passes; then a gather writes inst_doc / inst_pos and the run starts term_offsets
+ *
+ * np_hip_text_build runs the stages and returns a build.  Then, in this order: np_hip_text_build_fallback (any time before
+ * free), at most one np_hip_text_build_add, np_hip_text_build_sizes (finalises: with nothing added the device arrays are
+ * the result as they are; otherwise one linear host merge unites the vocabularies and merges, per term, the two runs by
+ * document -- their document sets are disjoint), np_hip_text_build_fetch, np_hip_text_build_free.  n_rows of the result is
+ * n_docs (FTS5's nRow counts empty rows).  A build is not shared between threads.
+ *
+ * Refused before any launch, the message naming the argument.  NP_ERR_INVALID_ARGUMENT: offsets that do not ascend from 0,
+ * an unknown tokenizer, max_token_bytes outside 0..32768, a hash_bits or tile_bytes knob out of range; for
+ * np_hip_text_build_add: instances out of (term, document, position) order, terms out of memcmp order, a document that is
+ * not on the fallback list, a second add or an add after np_hip_text_build_sizes.  NP_ERR_SHAPE: a document longer than
+ * 2^31 - 1 bytes, 2^31 documents or more, 2^31 instances or more in one call (known for unicode61 only after the counting
+ * launch: refused then, before anything is emitted).  NP_ERR_OUT_OF_MEMORY: a workspace (workspace_bytes, or the device's
+ * free memory) that does not hold the call.  It is a whole-corpus sort: building in document ranges and merging them is
+ * out of scope. */
+#define NP_TOK_UNICODE61 0
+#define NP_TOK_TRIGRAM 1
+#define NP_TEXT_BUILD_MAX_TOKEN_BYTES 32768
+
+typedef struct np_text_build_opts {
+  int32_t tokenizer;         /* NP_TOK_UNICODE61 / NP_TOK_TRIGRAM */
+  int32_t max_token_bytes;   /* unicode61: a longer token sends its document to the fallback list; 0 = 256 */
+  int64_t workspace_bytes;   /* device bytes the call may hold at once; 0 = what the device has free */
+  int32_t hash_bits;         /* test knob: log2 of the first term table, 1..31; 0 = planned from the instance count */
+  int32_t tile_bytes;        /* test knob: bytes a wave walks per step, a multiple of 16 in 16..1024; 0 = 1024 */
+  int64_t reserved[3];
+} np_text_build_opts;
+
+typedef struct np_text_build_report {
+  int64_t n_docs;
+  int64_t n_fallback;        /* documents on the fallback list */
+  int64_t n_instances;       /* instances the device emitted (the fallback documents' are not among them) */
+  int64_t n_terms;           /* distinct terms of those instances */
+  int64_t term_bytes;        /* bytes of their strings */
+  int32_t table_retries;     /* times the term table filled up and was doubled */
+  int32_t sort_passes;
+  int32_t hash_bits;         /* of the table that held the vocabulary (0 for trigram) */
+  int32_t tile_bytes;
+  double ms_upload;          /* host to device copy of the text */
+  double ms_classify;        /* classify, count and the scan */
+  double ms_emit;
+  double ms_terms;           /* table or bitmap, compaction, the host's sort of the vocabulary, term ids */
+  double ms_sort;            /* radix passes, gather, term_offsets */
+  double ms_total;           /* wall time of the call */
+  int64_t workspace_bytes;   /* device bytes held at the peak */
+  int64_t reserved[3];
+} np_text_build_report;
+
+typedef struct np_text_build np_text_build;
+
+int np_hip_text_build(int32_t device, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs,
+                      const np_text_build_opts* opts, np_text_build** out_build, np_text_build_report* report /* nullable */);
+/* The fallback documents' ids, ascending: out_doc_ids [report->n_fallback] (NULL: count only).  *out_count nullable. */
+int np_hip_text_build_fallback(const np_text_build* build, int64_t* out_doc_ids, int64_t* out_count);
+/* The fallback documents' instances, tokenised by the host: n_terms strings (bytes + offsets[n_terms + 1]) in ascending
+ * memcmp order, each with at least one instance, and n instances sorted by (term, doc, pos), inst_term indexing the strings. */
+int np_hip_text_build_add(np_text_build* build, const uint8_t* term_bytes, const int64_t* term_byte_offsets, int64_t n_terms,
+                          const int32_t* inst_term, const int64_t* inst_doc, const int32_t* inst_pos, int64_t n);
+int np_hip_text_build_sizes(np_text_build* build, int64_t* n_terms, int64_t* term_bytes, int64_t* n_instances, int64_t* n_rows);
+/* term_bytes [term_bytes], term_byte_offsets [n_terms + 1], term_offsets [n_terms + 1], inst_doc / inst_pos [n_instances];
+ * any pointer may be NULL.  After np_hip_text_build_sizes. */
+int np_hip_text_build_fetch(const np_text_build* build, uint8_t* term_bytes, int64_t* term_byte_offsets, int64_t* term_offsets,
+                            int64_t* inst_doc, int32_t* inst_pos);
+void np_hip_text_build_free(np_text_build* build);
+
 /* Stage-level debug access for parity tests: runs S1-S5 for ONE query and copies out the probed
  * cells (ascending), candidate doc ids (ascending, global), their approximate scores, and the
  * selected docs in approx-rank order with their exact scores.  Capacities are in elements;

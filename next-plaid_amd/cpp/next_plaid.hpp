@@ -1120,4 +1120,97 @@ inline PooledDocuments pool_document_embeddings(const Documents& docs, size_t po
   return r;
 }
 
+// ---- the keyword index built on the device (np_hip_text_build): the arrays np_hip_index_set_text takes, from raw text ----
+enum class Tokenizer { Unicode61 = NP_TOK_UNICODE61, Trigram = NP_TOK_TRIGRAM };
+
+// Instances tokenised by the caller (this mirror has no SQLite): the terms in memcmp order, the shorter string first, and
+// the instances sorted by (term, doc, pos), inst_term indexing `terms`.
+struct TextInstances {
+  std::vector<std::string> terms;
+  std::vector<int32_t> inst_term;
+  std::vector<int64_t> inst_doc;
+  std::vector<int32_t> inst_pos;
+};
+
+struct BuiltTextIndex {
+  std::vector<std::string> terms;          // term id -> term, in fts5vocab's order
+  std::vector<int64_t> term_offsets;       // [n_terms + 1]
+  std::vector<int64_t> inst_doc;
+  std::vector<int32_t> inst_pos;
+  int64_t n_rows = 0;
+  std::vector<int64_t> fallback_docs;      // documents the device does not reproduce (non-ASCII, ...), ascending
+  np_text_build_report report{};
+};
+
+namespace detail {
+struct TextBuildHandle {
+  np_text_build* h = nullptr;
+  ~TextBuildHandle() { np_hip_text_build_free(h); }
+};
+
+inline void text_build_start(TextBuildHandle& b, const std::vector<std::string>& texts, const np_text_build_opts& o, int device,
+                             BuiltTextIndex* r) {
+  std::vector<int64_t> off(texts.size() + 1, 0);
+  for (size_t i = 0; i < texts.size(); ++i) off[i + 1] = off[i] + (int64_t)texts[i].size();
+  std::vector<uint8_t> raw((size_t)off.back());
+  for (size_t i = 0; i < texts.size(); ++i) std::copy(texts[i].begin(), texts[i].end(), raw.begin() + off[i]);
+  check(np_hip_text_build(device, raw.empty() ? nullptr : raw.data(), off.data(), (int64_t)texts.size(), &o, &b.h, &r->report));
+  r->fallback_docs.resize((size_t)r->report.n_fallback);
+  check(np_hip_text_build_fallback(b.h, r->fallback_docs.data(), nullptr));
+}
+
+inline void text_build_finish(TextBuildHandle& b, BuiltTextIndex* r) {
+  int64_t n_terms = 0, n_bytes = 0, n_inst = 0;
+  check(np_hip_text_build_sizes(b.h, &n_terms, &n_bytes, &n_inst, &r->n_rows));
+  std::vector<uint8_t> tb((size_t)std::max<int64_t>(n_bytes, 1));
+  std::vector<int64_t> tbo((size_t)n_terms + 1);
+  r->term_offsets.resize((size_t)n_terms + 1);
+  r->inst_doc.resize((size_t)n_inst);
+  r->inst_pos.resize((size_t)n_inst);
+  check(np_hip_text_build_fetch(b.h, tb.data(), tbo.data(), r->term_offsets.data(), r->inst_doc.data(), r->inst_pos.data()));
+  r->terms.resize((size_t)n_terms);
+  for (int64_t t = 0; t < n_terms; ++t) r->terms[(size_t)t].assign((const char*)tb.data() + tbo[(size_t)t], (size_t)(tbo[(size_t)t + 1] - tbo[(size_t)t]));
+}
+}  // namespace detail
+
+inline np_text_build_opts text_build_opts(Tokenizer tokenizer, int32_t max_token_bytes = 0) {
+  np_text_build_opts o{};
+  o.tokenizer = (int32_t)tokenizer;
+  o.max_token_bytes = max_token_bytes;
+  return o;
+}
+
+// The index of the documents the device reproduces.  A non-empty fallback_docs means the arrays lack those documents: the
+// caller tokenises them and calls the overload below (nothing is dropped silently: the list is part of the result).
+inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, Tokenizer tokenizer = Tokenizer::Unicode61,
+                                       int device = 0, int32_t max_token_bytes = 0) {
+  BuiltTextIndex r;
+  detail::TextBuildHandle b;
+  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), device, &r);
+  detail::text_build_finish(b, &r);
+  return r;
+}
+
+// ... with the caller's instances for the fallback documents: tokenize(fallback_docs) is called once, when the list is not empty.
+template <class Tokenize>
+inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, Tokenizer tokenizer, Tokenize&& tokenize,
+                                       int device = 0, int32_t max_token_bytes = 0) {
+  BuiltTextIndex r;
+  detail::TextBuildHandle b;
+  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), device, &r);
+  if (!r.fallback_docs.empty()) {
+    const TextInstances inst = tokenize(r.fallback_docs);
+    std::vector<int64_t> tbo(inst.terms.size() + 1, 0);
+    for (size_t i = 0; i < inst.terms.size(); ++i) tbo[i + 1] = tbo[i] + (int64_t)inst.terms[i].size();
+    std::vector<uint8_t> tb((size_t)tbo.back());
+    for (size_t i = 0; i < inst.terms.size(); ++i) std::copy(inst.terms[i].begin(), inst.terms[i].end(), tb.begin() + tbo[i]);
+    if (inst.inst_term.size() != inst.inst_doc.size() || inst.inst_term.size() != inst.inst_pos.size())
+      throw Error(NP_ERR_INVALID_ARGUMENT, "build_text_index: the instance arrays differ in length");
+    check(np_hip_text_build_add(b.h, tb.empty() ? nullptr : tb.data(), tbo.data(), (int64_t)inst.terms.size(), inst.inst_term.data(),
+                                inst.inst_doc.data(), inst.inst_pos.data(), (int64_t)inst.inst_term.size()));
+  }
+  detail::text_build_finish(b, &r);
+  return r;
+}
+
 }  // namespace next_plaid

@@ -207,6 +207,25 @@ class np_text_index(C.Structure):
                 ("n_rows", C.c_int64)]
 
 
+class np_text_build_opts(C.Structure):
+    _fields_ = [("tokenizer", C.c_int32), ("max_token_bytes", C.c_int32), ("workspace_bytes", C.c_int64),
+                ("hash_bits", C.c_int32), ("tile_bytes", C.c_int32), ("reserved", C.c_int64 * 3)]
+
+
+class np_text_build_report(C.Structure):
+    _fields_ = [("n_docs", C.c_int64), ("n_fallback", C.c_int64), ("n_instances", C.c_int64), ("n_terms", C.c_int64),
+                ("term_bytes", C.c_int64), ("table_retries", C.c_int32), ("sort_passes", C.c_int32), ("hash_bits", C.c_int32),
+                ("tile_bytes", C.c_int32), ("ms_upload", C.c_double), ("ms_classify", C.c_double), ("ms_emit", C.c_double),
+                ("ms_terms", C.c_double), ("ms_sort", C.c_double), ("ms_total", C.c_double), ("workspace_bytes", C.c_int64),
+                ("reserved", C.c_int64 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
+NP_TOK_UNICODE61, NP_TOK_TRIGRAM = 0, 1
+
+
 class np_text_query(C.Structure):
     _fields_ = [("terms", C.c_void_p), ("phrase_offsets", C.c_void_p), ("n_phrases", C.c_int32), ("mode", C.c_int32)]
 
@@ -242,6 +261,8 @@ EXPORTS = [
     "np_hip_search_batch_sharded_filtered", "np_hip_search_hybrid_sharded",
     "np_hip_index_set_groups", "np_hip_index_group_count", "np_hip_collapse", "np_hip_collapse_device",
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
+    "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
+    "np_hip_text_build_fetch", "np_hip_text_build_free",
 ]
 
 _lib = None
@@ -408,6 +429,14 @@ def lib():
     L.np_hip_pooled_lengths.argtypes = [vp, i64, C.POINTER(np_pool_opts), vp]
     L.np_hip_pool_documents.argtypes = [i32, vp, vp, i64, i32, C.POINTER(np_pool_opts), vp, i64, vp, vp, vp,
                                         C.POINTER(np_pool_report)]
+    L.np_hip_text_build.argtypes = [i32, vp, vp, i64, C.POINTER(np_text_build_opts), C.POINTER(vp),
+                                    C.POINTER(np_text_build_report)]
+    L.np_hip_text_build_fallback.argtypes = [vp, vp, C.POINTER(i64)]
+    L.np_hip_text_build_add.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64]
+    L.np_hip_text_build_sizes.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.np_hip_text_build_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.np_hip_text_build_free.argtypes = [vp]
+    L.np_hip_text_build_free.restype = None
     _lib = L
     return L
 
@@ -869,6 +898,55 @@ def _docs(documents):
     lens = np.array([d.shape[0] for d in docs], np.int64)
     flat = np.concatenate(docs, 0) if lens.sum() > 0 else np.zeros((1, max(dim, 1)), np.float32)
     return np.ascontiguousarray(flat, np.float32), lens, dim
+
+
+def text_build(doc_bytes, offsets, tokenizer: int, tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0,
+               workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+    """np_hip_text_build and the calls that follow it: the documents' UTF-8 bytes concatenated (u8 array) and offsets i64
+    [n_docs + 1] -> a dict with term_bytes u8, term_byte_offsets / term_offsets i64 [n_terms + 1], inst_doc i64, inst_pos
+    i32, n_rows, fallback_docs i64 (ascending) and the stage report.  tokenize_fallback(ids) is called once when the device
+    hands documents back, and returns their instances as (term_bytes u8, term_byte_offsets i64, inst_term i32, inst_doc i64,
+    inst_pos i32) sorted by (term, doc, pos) with the terms in memcmp order; without it a non-empty fallback list is an
+    error, never a silently smaller index."""
+    raw = np.ascontiguousarray(doc_bytes, np.uint8).reshape(-1)
+    off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("offsets needs n_docs + 1 entries")
+    o = np_text_build_opts(int(tokenizer), int(max_token_bytes), int(workspace_bytes), int(hash_bits), int(tile_bytes))
+    rep, h = np_text_build_report(), C.c_void_p()
+    L = lib()
+    _check(L.np_hip_text_build(int(device), _ptr(raw) if raw.size else None, _ptr(off), off.size - 1, C.byref(o), C.byref(h),
+                               C.byref(rep)))
+    try:
+        fb = np.zeros(max(int(rep.n_fallback), 1), np.int64)
+        _check(L.np_hip_text_build_fallback(h, _ptr(fb), None))
+        fb = fb[: int(rep.n_fallback)]
+        if fb.size:
+            if tokenize_fallback is None:
+                raise ValueError(f"{fb.size} documents (the first: {int(fb[0])}) are not reproduced on the device and "
+                                           f"no tokenize_fallback was given")
+            tb, tbo, it, idoc, ipos = tokenize_fallback(fb)
+            tb = np.ascontiguousarray(tb, np.uint8)
+            tbo = np.ascontiguousarray(tbo, np.int64)
+            it = np.ascontiguousarray(it, np.int32)
+            idoc = np.ascontiguousarray(idoc, np.int64)
+            ipos = np.ascontiguousarray(ipos, np.int32)
+            _check(L.np_hip_text_build_add(h, _ptr(tb) if tb.size else None, _ptr(tbo), tbo.size - 1, _ptr(it), _ptr(idoc),
+                                           _ptr(ipos), it.size))
+        nt, nb, ni, nr = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(L.np_hip_text_build_sizes(h, C.byref(nt), C.byref(nb), C.byref(ni), C.byref(nr)))
+        out = dict(term_bytes=np.zeros(max(nb.value, 1), np.uint8), term_byte_offsets=np.zeros(nt.value + 1, np.int64),
+                   term_offsets=np.zeros(nt.value + 1, np.int64), inst_doc=np.zeros(max(ni.value, 1), np.int64),
+                   inst_pos=np.zeros(max(ni.value, 1), np.int32))
+        _check(L.np_hip_text_build_fetch(h, *(_ptr(out[k]) for k in ("term_bytes", "term_byte_offsets", "term_offsets",
+                                                                      "inst_doc", "inst_pos"))))
+        out["term_bytes"] = out["term_bytes"][: nb.value]
+        out["inst_doc"] = out["inst_doc"][: ni.value]
+        out["inst_pos"] = out["inst_pos"][: ni.value]
+        out.update(n_rows=int(nr.value), fallback_docs=fb, report=rep.as_dict())
+        return out
+    finally:
+        L.np_hip_text_build_free(h)
 
 
 _POOL_CUTS = {"reference": 0, "distance": 1}
@@ -1443,6 +1521,15 @@ class MmapIndex:
             _check(fn(self._h, C.byref(t)))
         self.text = data
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def build_text(self, texts, tokenizer: str = "unicode61", max_token_bytes: int | None = None):
+        """set_text from the documents' raw text, tokenised, numbered and sorted on this handle's device
+        (text.TextIndexData.from_texts_device); returns the TextIndexData, which set_text_shard takes unchanged."""
+        from . import text as T
+        data = T.TextIndexData.from_texts_device(texts, tokenizer, device=int(self._info.device),
+                                                 max_token_bytes=max_token_bytes)
+        self.set_text(data)
+        return data
 
     def _load_text(self, index_path, what, set_text):
         from . import text as T

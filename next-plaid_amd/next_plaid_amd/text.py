@@ -143,6 +143,8 @@ class TextIndexData:
     inst_pos: np.ndarray              # int32 [instances]
     n_rows: int                       # FTS5's nRow
     vocab: dict = field(default_factory=dict)
+    build_report: dict = field(default=None, repr=False, compare=False)    # from_texts_device: the stage report ...
+    fallback_docs: list = field(default=None, repr=False, compare=False)   # ... and the documents SQLite tokenised
     _scratch: object = field(default=None, repr=False, compare=False)
     _cache: dict = field(default_factory=dict, repr=False, compare=False)
 
@@ -208,6 +210,50 @@ class TextIndexData:
             return cls._read(conn, FTS_TABLE, tokenizer)
         finally:
             conn.close()
+
+    @classmethod
+    def from_texts_device(cls, texts, tokenizer: str = "unicode61", device: int = 0, max_token_bytes: int | None = None,
+                          **knobs) -> "TextIndexData":
+        """from_texts without the FTS5 table: the documents are tokenised, their terms numbered and the instances sorted on
+        the device (np_hip_text_build), and the arrays equal from_texts' one for one.  The device reproduces SQLite for
+        ASCII text (trigram: without NUL; unicode61: tokens of at most max_token_bytes, 256 unless given); the documents it
+        hands back -- fallback_docs on the result -- go through a scratch FTS5 table here and are merged in.
+        identifier_aware expands identifiers on the host first, as from_texts does.  build_report holds the stage report.
+        `knobs` are the test knobs of np_text_build_opts (hash_bits, tile_bytes, workspace_bytes)."""
+        if tokenizer not in TOKENIZERS:
+            raise ValueError(f"unknown tokenizer {tokenizer!r}")
+        from . import api   # the one module that calls the library; resolved here so that this one imports without it
+        texts = list(texts)
+        raws = [prepare_document_text(t, tokenizer).encode("utf-8") for t in texts]
+        off = np.zeros(len(raws) + 1, np.int64)
+        if raws:
+            off[1:] = np.cumsum([len(r) for r in raws])
+        raw = np.frombuffer(b"".join(raws), np.uint8)
+
+        def tokenize_fallback(ids):
+            conn = sqlite3.connect(":memory:")
+            try:
+                create_fts_tables(conn, tokenizer, content_synced=False)
+                insert_fts_rows(conn, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer, content_synced=False)
+                d = cls._read(conn, FTS_TABLE, tokenizer)
+            finally:
+                conn.close()
+            enc = [t.encode("utf-8") for t in d.terms]
+            tbo = np.zeros(len(enc) + 1, np.int64)
+            if enc:
+                tbo[1:] = np.cumsum([len(t) for t in enc])
+            inst_term = np.repeat(np.arange(len(enc), dtype=np.int32), np.diff(d.term_offsets))
+            return np.frombuffer(b"".join(enc), np.uint8), tbo, inst_term, d.inst_doc, d.inst_pos
+
+        code = api.NP_TOK_TRIGRAM if TOKENIZERS[tokenizer] == "trigram" else api.NP_TOK_UNICODE61
+        r = api.text_build(raw, off, code, tokenize_fallback, device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
+        tb, tbo = r["term_bytes"].tobytes(), r["term_byte_offsets"]
+        terms = [tb[tbo[i]: tbo[i + 1]].decode("utf-8") for i in range(tbo.size - 1)]
+        data = cls(tokenizer, terms, r["term_offsets"], r["inst_doc"], r["inst_pos"], r["n_rows"],
+                   {t: i for i, t in enumerate(terms)})
+        data.build_report = r["report"]
+        data.fallback_docs = [int(i) for i in r["fallback_docs"]]
+        return data
 
     # -- tokenising query text with the index's tokenizer -------------------------------------------------
     def tokens_of(self, phrase: str) -> list[str]:
