@@ -138,7 +138,7 @@ const char* np_hip_last_error(void);
  * refuses a library whose version differs from the header it was built with; np_hip_struct_size lets it check the two
  * layouts it allocates (which: 0 = np_info, 1 = np_stats, 2 = np_search_params, 3 = np_open_opts, 4 = np_kmeans_opts,
  * 5 = np_kmeans_report, 6 = np_index_config, 7 = np_kmeans_plan, 8 = np_update_config, 9 = np_update_report,
- * 10 = np_pool_opts, 11 = np_pool_report; -1 for an unknown id). */
+ * 10 = np_pool_opts, 11 = np_pool_report, 12 = np_text_expr; -1 for an unknown id). */
 int np_hip_abi_version(void);
 int64_t np_hip_struct_size(int32_t which);
 
@@ -668,6 +668,67 @@ int np_hip_search_hybrid(const np_index* index, const float* queries, const int3
                          const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
                          const int32_t* query_subset, const np_filter* filters, int32_t n_filters,
                          int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+
+/* ---- keyword search with the FTS5 boolean grammar and prefix queries ----------------------------------
+ * A keyword query as a TREE: phrases as np_text_query has them, every phrase optionally ending in a PREFIX, and a postfix
+ * list of nodes over them -- what FTS5 makes of `error NOT test`, `(parse OR lex) AND token`, `interceptor*`,
+ * `"http req" *` and `foo + bar` (the compiler from query text is next_plaid_amd/text.py, compile_text_expr).
+ *   phrases   terms / phrase_offsets as in np_text_query.  prefix_hi[p] = 0: the phrase's last token is the term it names;
+ *             otherwise the last token stands for every term of [last term id, prefix_hi[p]) -- fts5vocab numbers the terms
+ *             in byte order, so the terms that start with a prefix are one range.  (An empty range is written as the
+ *             unknown token -1 with prefix_hi = 0: the phrase never occurs.)  A phrase of ONE token may name any range:
+ *             its postings are one run of the instance arrays.  A phrase of several tokens that ends in a prefix may name
+ *             at most NP_TEXT_MAX_PREFIX_TERMS terms (its last position is looked up in every one of them)
+ *   nodes     postfix: NP_TEXT_NODE_PHRASE pushes phrase `a`; AND / OR / NOT pop the nodes `b` (top) and `a` (below it) --
+ *             indexes into the list, both below the node's own -- and push the result; NOT is binary, a AND NOT b.  One
+ *             node is left at the end: the last.  Every phrase is named by exactly one PHRASE node
+ *   match     the boolean value of the tree over "phrase p has frequency >= 1 in the document"
+ *   score     np_text_query's sum, IN PHRASE ORDER, over the phrases that are LIVE in the document: the phrase occurs,
+ *             every node on its path to the root is true, and the path enters no NOT from the right.  nHit and idf of a
+ *             phrase are the phrase's own, whatever stands around it; a prefix phrase's nHit counts the documents that hold
+ *             any term of the range and its frequency adds the instances of all of them.  SQLite's own bm25() differs on
+ *             a few rows of trees with a NOT below an OR or inside a NOT's right side, and with an OR below an AND next
+ *             to phrases of several tokens (leftovers of its cursors); everywhere else the bits are
+ *             SQLite's.  A flat tree (a chain of ANDs or of ORs without prefixes) returns np_hip_text_search's bytes
+ *   everything else (order, independence, subsets, filters, memory, stats, errors) is np_hip_text_search's; n_ivf_ids counts
+ *   the postings a prefix's pre-pass walks too, and every query of a chunk owns 4 bytes x num_documents of scratch per
+ *   single-token prefix phrase (of the query that has most).  A malformed tree is NP_ERR_INVALID_ARGUMENT before any launch;
+ *   the message names the query and the node or phrase.
+ * The sharded, grouped and device-pointer entries have no _expr form yet. */
+#define NP_TEXT_NODE_PHRASE 0
+#define NP_TEXT_NODE_AND 1
+#define NP_TEXT_NODE_OR 2
+#define NP_TEXT_NODE_NOT 3
+#define NP_TEXT_MAX_NODES 127
+#define NP_TEXT_MAX_PREFIX_TERMS 1024
+typedef struct np_text_node {
+  int32_t op;   /* NP_TEXT_NODE_* */
+  int32_t a;    /* PHRASE: the phrase; otherwise the left child */
+  int32_t b;    /* the right child (PHRASE: 0) */
+} np_text_node;
+typedef struct np_text_expr {
+  const int32_t* terms;            /* [phrase_offsets[n_phrases]] */
+  const int32_t* phrase_offsets;   /* [n_phrases + 1], starts at 0, strictly increasing */
+  const int32_t* prefix_hi;        /* [n_phrases] 0 = an exact last token */
+  const np_text_node* nodes;       /* [n_nodes] postfix */
+  int32_t n_phrases;
+  int32_t n_nodes;
+} np_text_expr;   /* np_hip_struct_size(12) */
+int np_hip_text_search_expr(const np_index* index, const np_text_expr* queries, int32_t B, int32_t top_k,
+                            const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                            const int32_t* query_subset,
+                            int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+int np_hip_text_search_expr_filtered(const np_index* index, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                     const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                     int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+/* np_hip_search_hybrid with tree queries: its arguments, scope forms and result, the keyword list being
+ * np_hip_text_search_expr's. */
+int np_hip_search_hybrid_expr(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                              const np_search_params* params, const np_text_expr* text_queries, int32_t fetch_k, float alpha,
+                              int32_t fusion,
+                              const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                              const int32_t* query_subset, const np_filter* filters, int32_t n_filters,
+                              int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
 
 /* ---- grouped search: top_k groups with their best documents ------------------------------------------
  * Both applications of the crate index UNITS and answer in GROUPS: code units of a file, passages of a document.  ColGREP does

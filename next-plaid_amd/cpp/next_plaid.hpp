@@ -10,7 +10,8 @@
 //   index.search_batch(queries, params, parallel, subset)  index.rs:1279  -> query_id = batch position
 //   index.search_batch_subsets(queries, n, params, parallel, subsets)   one subset per query (a server's batch of requests)
 //   index.search_exact(queries, n, top_k, precision, subset) / search_exact_subsets(...)   every document scored: the exact top-k
-//   index.set_text(...) / text_search(...) / fuse(...) / search_hybrid(...)   the keyword half of a hybrid search (text_search.rs)
+//   index.set_text(...) / text_search(...) / fuse(...) / search_hybrid(...)   the keyword half of a hybrid search (text_search.rs);
+//                                                          TextQuery = flat AND / OR, TextExpr = FTS5's NOT, parentheses, prefixes
 //   index.set_groups(...) / collapse(...) / search_grouped(...) / search_hybrid_grouped(...)   top-k groups with their best documents
 //   SearchParameters (defaults search.rs:58-69), QueryResult (search.rs:71-80), Error (error.rs:9-66)
 //
@@ -344,6 +345,38 @@ class TextQuery {
   std::vector<int32_t> terms_, off_;
 };
 
+// A compiled keyword query with FTS5's boolean operators and prefixes (np_text_expr): phrases in the order of the query text
+// and a postfix list of nodes over them.  phrase() and the operators append a node and return its index; operands are the
+// indexes of the two nodes appended last that no operator has taken yet (the stack discipline np_hip_text_search_expr
+// checks).  prefix_hi != 0: the phrase's last token stands for the terms [its id, prefix_hi).
+// Append the phrases in the order of the query text, one statement each (C++ leaves the order of arguments open):
+//   TextExpr e;  int a = e.phrase({parse}), b = e.phrase({lex}), l = e.or_(a, b);
+//   int t = e.phrase({tok}, tok_hi);  e.not_(l, t);                                                 // (parse OR lex) NOT tok*
+class TextExpr {
+ public:
+  TextExpr() : off_{0} {}
+  int phrase(const std::vector<int32_t>& term_ids, int32_t prefix_hi = 0) {
+    terms_.insert(terms_.end(), term_ids.begin(), term_ids.end());
+    off_.push_back((int32_t)terms_.size());
+    hi_.push_back(prefix_hi);
+    return node(NP_TEXT_NODE_PHRASE, (int32_t)hi_.size() - 1, 0);
+  }
+  int and_(int a, int b) { return node(NP_TEXT_NODE_AND, a, b); }
+  int or_(int a, int b) { return node(NP_TEXT_NODE_OR, a, b); }
+  int not_(int a, int b) { return node(NP_TEXT_NODE_NOT, a, b); }   // a AND NOT b
+  np_text_expr c() const {
+    return np_text_expr{terms_.data(), off_.data(), hi_.data(), nodes_.data(), (int32_t)hi_.size(), (int32_t)nodes_.size()};
+  }
+
+ private:
+  int node(int32_t op, int32_t a, int32_t b) {
+    nodes_.push_back(np_text_node{op, a, b});
+    return (int)nodes_.size() - 1;
+  }
+  std::vector<int32_t> terms_, off_, hi_;
+  std::vector<np_text_node> nodes_;
+};
+
 // The keyword index for MmapIndex::set_text: the FTS5 table's (term, document, position) instances, sorted, term t owning
 // [term_offsets[t], term_offsets[t + 1]), and the table's row count.
 struct TextIndexSpan {
@@ -648,6 +681,19 @@ class MmapIndex {
     return b.rows(n);
   }
 
+  // ... with tree queries (np_hip_text_search_expr): NOT, AND, OR, parentheses and prefixes as FTS5 reads them.
+  std::vector<QueryResult> text_search(const std::vector<TextExpr>& queries, size_t top_k,
+                                       const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("text_search");
+    const size_t n = queries.size();
+    const SubsetArgs s(subsets, n, "text_search");
+    const std::vector<np_text_expr> tq = c_text_exprs(queries);
+    RowBuffers b(n, std::max<size_t>(top_k, 1));
+    check(np_hip_text_search_expr(h_, tq.data(), (int32_t)n, (int32_t)top_k, s.sids.data(), s.soff.data(), (int64_t)s.n_distinct,
+                                  s.qsub.data(), b.ids.data(), b.sc.data(), b.cnt.data(), &last_stats));
+    return b.rows(n);
+  }
+
   // Fusion of per-query semantic and keyword lists (np_hip_fuse; text_search.rs:1006-1075): mode NP_FUSE_RRF or
   // NP_FUSE_RELATIVE_SCORE, f32 in the reference's order; fused score descending, ties by ascending id.
   std::vector<QueryResult> fuse(int mode, float alpha, size_t top_k, const std::vector<QueryResult>& sem,
@@ -678,6 +724,24 @@ class MmapIndex {
                                (int32_t)(fetch_k ? fetch_k : 3 * params.top_k), alpha, fusion, s.sids.data(), s.soff.data(),
                                (int64_t)s.n_distinct, s.qsub.data(), nullptr, 0, b.ids.data(), b.sc.data(), b.cnt.data(),
                                &last_stats));
+    return b.rows(n);
+  }
+
+  // ... with tree queries (np_hip_search_hybrid_expr)
+  std::vector<QueryResult> search_hybrid(const Query* queries, const std::vector<TextExpr>& text_queries, const SearchParameters& params,
+                                         float alpha = 0.75f, int fusion = NP_FUSE_RELATIVE_SCORE, size_t fetch_k = 0,
+                                         const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("search_hybrid");
+    const size_t n = text_queries.size();
+    const SubsetArgs s(subsets, n, "search_hybrid");
+    const std::vector<np_text_expr> tq = c_text_exprs(text_queries);
+    const PackedQueries q = pack_queries(queries, n);
+    const np_search_params p = params.c();
+    RowBuffers b(n, std::max<size_t>(params.top_k, 1));
+    check(np_hip_search_hybrid_expr(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), &p, tq.data(),
+                                    (int32_t)(fetch_k ? fetch_k : 3 * params.top_k), alpha, fusion, s.sids.data(), s.soff.data(),
+                                    (int64_t)s.n_distinct, s.qsub.data(), nullptr, 0, b.ids.data(), b.sc.data(), b.cnt.data(),
+                                    &last_stats));
     return b.rows(n);
   }
 
@@ -839,6 +903,12 @@ class MmapIndex {
   static std::vector<np_text_query> c_text_queries(const std::vector<TextQuery>& queries) {
     std::vector<np_text_query> q;
     for (const TextQuery& t : queries) q.push_back(t.c());
+    return q;
+  }
+
+  static std::vector<np_text_expr> c_text_exprs(const std::vector<TextExpr>& queries) {
+    std::vector<np_text_expr> q;
+    for (const TextExpr& t : queries) q.push_back(t.c());
     return q;
   }
 

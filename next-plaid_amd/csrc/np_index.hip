@@ -1528,6 +1528,7 @@ int64_t np_hip_struct_size(int32_t which) {
     case 9: return (int64_t)sizeof(np_update_report);
     case 10: return (int64_t)sizeof(np_pool_opts);
     case 11: return (int64_t)sizeof(np_pool_report);
+    case 12: return (int64_t)sizeof(np_text_expr);
     default: return -1;
   }
 }

@@ -238,6 +238,308 @@ __global__ void __launch_bounds__(TEXT_TPB) text_score_kernel(TextScoreP p) {
   if (tid == 0) p.list_cnt[o] = kept;
 }
 
+// ---- tree queries (np_text_expr): prefix frequencies, hit counts, and the (query, slice) kernel ----------------------------
+
+// text_phrase_freq for a phrase of several tokens whose last token stands for the terms [terms[nt - 1], hi): a position
+// holds one term, so at most one term of the range continues an occurrence.  hi = 0: the exact phrase.
+__device__ __forceinline__ int text_phrase_freq_px(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int hi, int64_t j0, int doc) {
+  if (hi == 0 || nt == 1) return text_phrase_freq(t, terms, nt, j0, doc);
+  const int tf0 = t.post_tf[j0];
+  const int64_t f0 = t.post_first[j0];
+  int freq = 0;
+  for (int x = 0; x < tf0; ++x) {
+    const int64_t p = t.pos[f0 + x];
+    bool ok = true;
+    for (int k = 1; k < nt - 1 && ok; ++k) {
+      const int term = terms[k];
+      const int64_t e = t.post_off[term + 1];
+      const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
+      if (jk >= e || t.post_doc[jk] != doc) return 0;
+      const int64_t pe = t.post_first[jk] + t.post_tf[jk];
+      const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, p + k);
+      ok = at < pe && (int64_t)t.pos[at] == p + k;
+    }
+    if (!ok) continue;
+    bool last = false;
+    for (int term = terms[nt - 1]; term < hi && !last; ++term) {
+      const int64_t e = t.post_off[term + 1];
+      const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
+      if (jk >= e || t.post_doc[jk] != doc) continue;
+      const int64_t pe = t.post_first[jk] + t.post_tf[jk];
+      const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, p + nt - 1);
+      last = at < pe && (int64_t)t.pos[at] == p + nt - 1;
+    }
+    freq += last ? 1 : 0;
+  }
+  return freq;
+}
+
+struct TextExprHitP {
+  TextIxP t;
+  const int32_t* phr_tok;
+  const int32_t* terms;
+  const int32_t* phr_hi;           // [phrases] end of the last token's term range, 0 = exact
+  const int32_t* item_phr;         // [items] phrases of several known tokens
+  unsigned long long* nhit;        // [items]
+};
+
+// text_hit_kernel for the phrases of a tree query: the same count, with a last token that may be a prefix
+__global__ void __launch_bounds__(TEXT_TPB) text_expr_hit_kernel(TextExprHitP p) {
+  __shared__ uint32_t part[TEXT_TPB / 64];
+  const int item = blockIdx.y, tid = threadIdx.x;
+  const int phr = p.item_phr[item];
+  const int tb = p.phr_tok[phr], nt = p.phr_tok[phr + 1] - tb;
+  const int32_t* terms = p.terms + tb;
+  const int hi_t = p.phr_hi[phr];
+  const int64_t lo = p.t.post_off[terms[0]], hi = p.t.post_off[terms[0] + 1];
+  uint32_t c = 0;
+  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
+    c += text_phrase_freq_px(p.t, terms, nt, hi_t, j, p.t.post_doc[j]) > 0 ? 1u : 0u;
+  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
+  if ((tid & 63) == 0) part[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t all = part[0] + part[1] + part[2] + part[3];
+    if (all) atomicAdd(&p.nhit[item], (unsigned long long)all);
+  }
+}
+
+struct TextPrefixP {
+  TextIxP t;
+  const int32_t* phr_tok;
+  const int32_t* terms;
+  const int32_t* phr_hi;
+  const int32_t* px_phr;           // [prefix phrases of the chunk] single-token phrases that end in a prefix
+  const int32_t* px_at;            // [the same] the phrase's frequency array: (query of the chunk) * slots + slot
+  uint32_t* pfreq;                 // [chunk queries * slots][stride] zeroed
+  int64_t stride;
+  unsigned long long* pxhit;       // [phrases] zeroed
+};
+
+// The pre-pass of a single-token prefix phrase: the postings of the terms [lo, hi) are ONE run of the posting arrays; a lane
+// per posting adds the term frequency to the document's entry (integer adds: order cannot show).  The lane that finds the
+// entry at zero counts the document: nHit = documents that hold any term of the range.
+__global__ void __launch_bounds__(TEXT_TPB) text_prefix_kernel(TextPrefixP p) {
+  __shared__ uint32_t part[TEXT_TPB / 64];
+  const int tid = threadIdx.x;
+  const int phr = p.px_phr[blockIdx.y];
+  const int term = p.terms[p.phr_tok[phr]];
+  uint32_t* arr = p.pfreq + (int64_t)p.px_at[blockIdx.y] * p.stride;
+  const int64_t lo = p.t.post_off[term], hi = p.t.post_off[p.phr_hi[phr]];
+  uint32_t c = 0;
+  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
+    c += atomicAdd(&arr[p.t.post_doc[j]], (uint32_t)p.t.post_tf[j]) == 0u ? 1u : 0u;   // (a posting's frequency is >= 1)
+  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
+  if ((tid & 63) == 0) part[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t all = part[0] + part[1] + part[2] + part[3];
+    if (all) atomicAdd(&p.pxhit[phr], (unsigned long long)all);
+  }
+}
+
+struct TextExprP {
+  TextScoreP s;                    // text_score_kernel's arguments (mode is not read)
+  const int32_t* phr_hi;           // [phrases]
+  const int32_t* phr_slot;         // [phrases] a single-token prefix phrase's frequency array of its query, else -1
+  const int32_t* q_node;           // [B + 1] a query's nodes
+  const int32_t* nodes;            // op | a << 8 | b << 16, postfix
+  const uint32_t* pfreq;           // [chunk queries * slots][stride]
+  int64_t stride;
+  int slots;
+};
+
+// text_score_kernel's decomposition and lists for a tree query.  Per document of the slice a 64-bit mask of the phrases that
+// occur (pass 1, a phrase at a time as the scoring pass walks them); a lane per document then evaluates the nodes bottom-up,
+// propagates liveness from the root down (a child is live if its parent is and the child is true; never the right child of a
+// NOT) and leaves the mask of the LIVE phrases; pass 2 walks the phrases again, in order, and adds the bm25 term where the
+// phrase is live -- the frequency of a phrase of several tokens is computed a second time, for live documents only.
+// LDS: 32 KB accumulators, 32 KB masks, 8 KB sort index: two workgroups per CU.
+__global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
+  __shared__ double s_acc[TEXT_SLICE];
+  __shared__ unsigned long long s_mask[TEXT_SLICE];
+  __shared__ uint16_t s_idx[TEXT_SLICE];
+  __shared__ int64_t s_lo[NP_TEXT_MAX_PHRASES], s_hi[NP_TEXT_MAX_PHRASES];
+  __shared__ int32_t s_node[NP_TEXT_MAX_NODES + 1];
+  __shared__ int s_any, s_n;
+  const TextScoreP& p = e.s;
+  const int tid = threadIdx.x, ql = blockIdx.y, q = p.q0 + ql;
+  const int64_t sl = blockIdx.x;
+  const int64_t d0 = (p.s0 + sl) * TEXT_SLICE;
+  const int n = p.n_docs - d0 < TEXT_SLICE ? (int)(p.n_docs - d0) : TEXT_SLICE;
+  const int ph0 = p.q_phr[q], nph = p.q_phr[q + 1] - ph0;
+  const int nd0 = e.q_node[q], nn = e.q_node[q + 1] - nd0;
+  const int row = p.qrow ? p.qrow[ql] : -1;
+  const int64_t o = (int64_t)ql * p.S + sl;
+  if (tid == 0) {
+    s_any = 0;
+    s_n = 0;
+  }
+  __syncthreads();
+  if (tid < nph) {
+    const int tb = p.phr_tok[ph0 + tid], te = p.phr_tok[ph0 + tid + 1];
+    bool known = true;
+    for (int k = tb; k < te; ++k) known = known && p.terms[k] >= 0;
+    int64_t lo = 0, hi = 0;
+    if (known && e.phr_slot[ph0 + tid] >= 0) {
+      atomicOr(&s_any, 1);   // (its documents are in the frequency array, not in one posting list)
+    } else if (known) {
+      const int term = p.terms[tb];
+      const int64_t end = p.t.post_off[term + 1];
+      lo = text_lower_bound(p.t.post_doc, p.t.post_off[term], end, d0);
+      hi = text_lower_bound(p.t.post_doc, lo, end, d0 + n);
+      if (hi > lo) atomicOr(&s_any, 1);
+    }
+    s_lo[tid] = lo;
+    s_hi[tid] = hi;
+  }
+  for (int i = tid; i < nn; i += TEXT_TPB) s_node[i] = e.nodes[nd0 + i];
+  __syncthreads();
+  if (!s_any) {   // (block-uniform) a match has a phrase that occurs
+    if (tid == 0) p.list_cnt[o] = 0;
+    return;
+  }
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    s_acc[i] = 0.0;
+    s_mask[i] = 0ull;
+  }
+  __syncthreads();
+  unsigned long long visited = 0;
+  // pass 1: the phrases that occur.  A document occurs once per posting list: lanes never collide inside a phrase
+  for (int ph = 0; ph < nph; ++ph) {
+    const unsigned long long bit = 1ull << ph;
+    const int slot = e.phr_slot[ph0 + ph];
+    if (slot >= 0) {
+      const uint32_t* arr = e.pfreq + ((int64_t)ql * e.slots + slot) * e.stride + d0;
+      for (int i = tid; i < n; i += TEXT_TPB)
+        if (arr[i] > 0u) s_mask[i] |= bit;
+    } else {
+      const int64_t lo = s_lo[ph], hi = s_hi[ph];
+      const int tb = p.phr_tok[ph0 + ph], nt = p.phr_tok[ph0 + ph + 1] - tb;
+      const int hi_t = e.phr_hi[ph0 + ph];
+      for (int64_t j = lo + tid; j < hi; j += TEXT_TPB) {
+        const int doc = p.t.post_doc[j];
+        if (text_phrase_freq_px(p.t, p.terms + tb, nt, hi_t, j, doc) > 0) s_mask[doc - d0] |= bit;
+      }
+      visited += (unsigned long long)(hi - lo);
+    }
+    __syncthreads();
+  }
+  if (p.ctr && tid == 0 && visited) atomicAdd(p.ctr, visited);
+  // the tree, a lane per document: node truths bottom-up, liveness top-down, the live phrases back into the mask; the
+  // matching documents in scope take their slots from a counter, the order comes from the sort below
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    const unsigned long long occ = s_mask[i];
+    unsigned long long t0 = 0, t1 = 0;   // truth of the nodes 0..63 and 64..126
+    auto truth = [&](int x) { return (int)(((x < 64 ? t0 : t1) >> (x & 63)) & 1ull); };
+    for (int x = 0; x < nn; ++x) {
+      const int32_t nd = s_node[x];
+      const int op = nd & 0xFF, a = (nd >> 8) & 0xFF, b = (nd >> 16) & 0xFF;
+      int v;
+      if (op == NP_TEXT_NODE_PHRASE) v = (int)((occ >> a) & 1ull);
+      else if (op == NP_TEXT_NODE_AND) v = truth(a) & truth(b);
+      else if (op == NP_TEXT_NODE_OR) v = truth(a) | truth(b);
+      else v = truth(a) & (truth(b) ^ 1);
+      if (v) {
+        if (x < 64) t0 |= 1ull << x; else t1 |= 1ull << (x & 63);
+      }
+    }
+    bool m = occ != 0ull && truth(nn - 1) != 0;
+    if (m && row >= 0) {
+      const int64_t d = d0 + i;
+      m = ((p.docbits[(int64_t)row * p.NW + (d >> 5)] >> (d & 31)) & 1u) != 0;
+    }
+    unsigned long long live = 0;
+    if (m) {
+      unsigned long long l0 = 0, l1 = 0;   // liveness of the nodes
+      if (nn - 1 < 64) l0 = 1ull << (nn - 1); else l1 = 1ull << ((nn - 1) & 63);
+      for (int x = nn - 1; x >= 0; --x) {
+        if (!(((x < 64 ? l0 : l1) >> (x & 63)) & 1ull)) continue;
+        const int32_t nd = s_node[x];
+        const int op = nd & 0xFF, a = (nd >> 8) & 0xFF, b = (nd >> 16) & 0xFF;
+        if (op == NP_TEXT_NODE_PHRASE) {
+          live |= 1ull << a;
+          continue;
+        }
+        if (truth(a)) {
+          if (a < 64) l0 |= 1ull << a; else l1 |= 1ull << (a & 63);
+        }
+        if (op != NP_TEXT_NODE_NOT && truth(b)) {
+          if (b < 64) l0 |= 1ull << b; else l1 |= 1ull << (b & 63);
+        }
+      }
+      s_idx[atomicAdd(&s_n, 1)] = (uint16_t)i;
+    }
+    s_mask[i] = live;
+  }
+  __syncthreads();
+  const int nm = s_n;
+  if (nm == 0) {
+    if (tid == 0) p.list_cnt[o] = 0;
+    return;
+  }
+  // pass 2: the bm25 terms of the live phrases, in phrase order
+  const double k1 = 1.2, b = 0.75;
+  for (int ph = 0; ph < nph; ++ph) {
+    const double idf = p.idf[ph0 + ph];
+    const int slot = e.phr_slot[ph0 + ph];
+    if (slot >= 0) {
+      const uint32_t* arr = e.pfreq + ((int64_t)ql * e.slots + slot) * e.stride + d0;
+      for (int i = tid; i < n; i += TEXT_TPB)
+        if ((s_mask[i] >> ph) & 1ull) {
+          const double a = (double)arr[i], D = (double)p.t.doc_len[d0 + i];
+          s_acc[i] = s_acc[i] + idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / p.avgdl)));
+        }
+    } else {
+      const int64_t lo = s_lo[ph], hi = s_hi[ph];
+      const int tb = p.phr_tok[ph0 + ph], nt = p.phr_tok[ph0 + ph + 1] - tb;
+      const int hi_t = e.phr_hi[ph0 + ph];
+      for (int64_t j = lo + tid; j < hi; j += TEXT_TPB) {
+        const int doc = p.t.post_doc[j];
+        const int l = (int)(doc - d0);
+        if ((s_mask[l] >> ph) & 1ull) {
+          const int freq = text_phrase_freq_px(p.t, p.terms + tb, nt, hi_t, j, doc);
+          const double a = (double)freq, D = (double)p.t.doc_len[doc];
+          s_acc[l] = s_acc[l] + idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / p.avgdl)));
+        }
+      }
+    }
+    __syncthreads();
+  }
+  int P2 = 1;
+  while (P2 < nm) P2 <<= 1;
+  for (int i = nm + tid; i < P2; i += TEXT_TPB) s_idx[i] = 0xFFFF;
+  // text_score_kernel's sort: score descending (a match's score is positive: a live phrase has a positive term), then id
+  auto before = [&](uint16_t x, uint16_t y) {
+    if (x == 0xFFFF) return false;
+    if (y == 0xFFFF) return true;
+    const unsigned long long kx = (unsigned long long)__double_as_longlong(s_acc[x]), ky = (unsigned long long)__double_as_longlong(s_acc[y]);
+    return kx > ky || (kx == ky && x < y);
+  };
+  for (int k = 2; k <= P2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < P2; i += TEXT_TPB) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint16_t x = s_idx[i], y = s_idx[ixj];
+          if ((i & k) == 0 ? before(y, x) : before(x, y)) {
+            s_idx[i] = y;
+            s_idx[ixj] = x;
+          }
+        }
+      }
+    }
+  __syncthreads();
+  const int kept = min(nm, p.keep);
+  for (int r = tid; r < kept; r += TEXT_TPB) {
+    const int l = s_idx[r];
+    p.list_keys[o * p.keep + r] = (unsigned long long)__double_as_longlong(s_acc[l]);
+    p.list_ids[o * p.keep + r] = (int32_t)(d0 + l);
+  }
+  if (tid == 0) p.list_cnt[o] = kept;
+}
+
 // (key descending, id ascending) over the first `fill` entries of a window; entries up to the next power of two are padded
 // with key 0 (no match has it).  Returns min(fill, top_k).  Every thread of the block calls it.
 __device__ int text_sort_cut(unsigned long long* s_k, int32_t* s_i, int fill, int top_k, int tid) {
@@ -591,11 +893,32 @@ static int text_check_queries(const DeviceIndex* ix, const np_text_query* querie
   return NP_OK;
 }
 
+static int text_check_exprs(const DeviceIndex* ix, const np_text_expr* queries, int B, int top_k) {
+  NP_TRY(text_check_handle(ix, true));
+  const char* why = "";
+  if (text_check_call(B, top_k, &why) != 0) {
+    set_error("Text search failed: %s (B=%d top_k=%d)", why, B, top_k);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (B > 0 && !queries) {
+    set_error("Text search failed: NULL queries");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  char msg[320];
+  for (int q = 0; q < B; ++q)
+    if (text_check_expr(&queries[q], q, ix->text.n_terms, msg, sizeof msg) != 0) {
+      set_error("Text search failed: %s", msg);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  return NP_OK;
+}
+
 // A batch's queries as the kernels read them, one blob: q_phr | phr_tok | terms | mode | item_phr | nhit | idf
 struct TextProg {
   int B = 0;
   int64_t n_phr = 0, n_tok = 0, n_items = 0;
   int64_t max_item_df = 0;
+  int64_t per_query_extra = 0;   // arena bytes per query of a chunk beyond text_per_query (a tree query's prefix frequencies)
   size_t o_qphr = 0, o_ptok = 0, o_terms = 0, o_mode = 0, o_item = 0, o_nhit = 0, o_idf = 0, bytes = 0;
   std::vector<char> blob;
   std::vector<int64_t> phr_hit;   // nHit where the host knows it, -1 where the counting pass says
@@ -661,20 +984,71 @@ static int64_t text_n_slices(const DeviceIndex* ix) {
 static int64_t text_fixed_bytes(const TextProg& prog) { return (int64_t)prog.bytes + 4096; }
 static size_t text_arena_bytes(const DeviceIndex* ix, const TextPlan& plan, const TextProg& prog, int top_k, bool subsets) {
   const size_t pairs = (size_t)plan.queries * (size_t)plan.slices, keep = (size_t)text_slice_keep(top_k);
-  return (size_t)text_fixed_bytes(prog) + (size_t)plan.queries * (size_t)text_per_query(ix, top_k, subsets) + up256(pairs * keep * 8) +
-         up256(pairs * keep * 4) + up256(pairs * 4);
+  return (size_t)text_fixed_bytes(prog) + (size_t)plan.queries * (size_t)(text_per_query(ix, top_k, subsets) + prog.per_query_extra) +
+         up256(pairs * keep * 8) + up256(pairs * keep * 4) + up256(pairs * 4);
 }
 static int text_plan_for(const DeviceIndex* ix, int64_t user, const TextProg& prog, int B, int top_k, bool subsets, TextPlan* plan) {
   const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
   // (the three list arrays are each rounded up to 256 bytes: 768 more than the plan's pairs)
-  if (!text_plan(budget, user + text_fixed_bytes(prog) + 1024, text_per_query(ix, top_k, subsets), text_n_slices(ix), B,
-                 ix->opts.max_batch, top_k, plan)) {
+  if (!text_plan(budget, user + text_fixed_bytes(prog) + 1024, text_per_query(ix, top_k, subsets) + prog.per_query_extra,
+                 text_n_slices(ix), B, ix->opts.max_batch, top_k, plan)) {
     set_error("Text search failed: one query over one slice of %lld documents does not fit the workspace budget of %lld bytes",
               (long long)NP_TEXT_SLICE_DOCS, (long long)budget);
     return NP_ERR_OUT_OF_MEMORY;
   }
   return NP_OK;
 }
+
+// A batch of tree queries (np_text_expr): TextProg over their phrases (which plans and counts them as it does a flat query's),
+// and behind its blob: phr_hi | phr_slot | q_node | nodes | px_phr | px_at | pxhit.  A single-token phrase that ends in a prefix
+// gets a slot: a per-document frequency array of its query, filled by text_prefix_kernel, which also counts its nHit.
+struct ExprProg : TextProg {
+  int slots = 0;             // frequency arrays a query of a chunk owns (the batch's maximum)
+  int64_t stride = 0;        // entries of one
+  int64_t n_px = 0;
+  size_t o_phi = 0, o_slot = 0, o_qnode = 0, o_nodes = 0, o_pxphr = 0, o_pxat = 0, o_pxhit = 0;
+  std::vector<int32_t> px_query;   // [n_px] the query of a prefix entry (entries ascend by query)
+  void build_expr(const DeviceIndex* ix, const np_text_expr* es, int B_) {
+    std::vector<np_text_query> flat((size_t)std::max(B_, 1));
+    int64_t n_nodes = 0;
+    for (int q = 0; q < B_; ++q) {
+      flat[(size_t)q] = np_text_query{es[q].terms, es[q].phrase_offsets, es[q].n_phrases, NP_TEXT_AND};
+      n_nodes += es[q].n_nodes;
+    }
+    build(ix, flat.data(), B_);
+    const size_t per_phr = up256((size_t)std::max<int64_t>(n_phr, 1) * 4);
+    o_phi = bytes;
+    o_slot = o_phi + per_phr;
+    o_qnode = o_slot + per_phr;
+    o_nodes = o_qnode + up256((size_t)(B + 1) * 4);
+    o_pxphr = o_nodes + up256((size_t)std::max<int64_t>(n_nodes, 1) * 4);
+    o_pxat = o_pxphr + per_phr;
+    o_pxhit = o_pxat + per_phr;
+    bytes = o_pxhit + 2 * per_phr;
+    blob.resize(bytes, 0);
+    int32_t *phi = at32(o_phi), *slot = at32(o_slot), *qnode = at32(o_qnode), *nodes = at32(o_nodes), *pxphr = at32(o_pxphr);
+    int64_t ph = 0, nd = 0;
+    for (int q = 0; q < B; ++q) {
+      int used = 0;
+      for (int i = 0; i < es[q].n_phrases; ++i, ++ph) {
+        phi[ph] = es[q].prefix_hi[i];
+        slot[ph] = -1;
+        if (es[q].prefix_hi[i] != 0 && es[q].phrase_offsets[i + 1] - es[q].phrase_offsets[i] == 1) {
+          slot[ph] = used++;
+          pxphr[n_px++] = (int32_t)ph;
+          px_query.push_back(q);
+          phr_hit[(size_t)ph] = -1;   // the pre-pass of the query's chunk says
+        }
+      }
+      slots = std::max(slots, used);
+      qnode[q] = (int32_t)nd;
+      for (int i = 0; i < es[q].n_nodes; ++i) nodes[nd++] = es[q].nodes[i].op | es[q].nodes[i].a << 8 | es[q].nodes[i].b << 16;
+    }
+    qnode[B] = (int32_t)nd;
+    stride = (std::max<int64_t>(ix->n_docs, 1) + 63) / 64 * 64;
+    per_query_extra = (int64_t)slots * stride * 4;   // (a multiple of 256)
+  }
+};
 
 // The counting exchange of a sharded keyword search (np_dist_plan.h, dist_count_record): this rank's nHit of the counted phrases,
 // its nRow and its status word go out, the sums over the healthy ranks come back.  A rank that cannot count (no keyword index,
@@ -743,9 +1117,12 @@ struct TextCounts {
 // (synchronises).
 // Sharded (counts != NULL): the hit counts of the counted phrases cross the ranks before the idf is computed, d_out_keys receives
 // the f64 bits of the scores and the ids leave as global ids.
+// Tree queries (ex != NULL, then &prog; host entries only: pin != NULL): the counting pass knows prefixes, every chunk of queries
+// first fills the frequency arrays of its single-token prefix phrases and synchronises once for their nHit, and
+// text_expr_kernel takes text_score_kernel's place.
 static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pin, const TextPlan& plan, TextProg& prog, int top_k,
                     const CallSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited,
-                    unsigned long long* d_out_keys = nullptr, TextCounts* counts = nullptr) {
+                    unsigned long long* d_out_keys = nullptr, TextCounts* counts = nullptr, ExprProg* ex = nullptr) {
   hipStream_t st = use.stream;
   const DeviceText& tx = ix->text;
   const int B = prog.B;
@@ -765,6 +1142,10 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
   unsigned long long* list_keys = (unsigned long long*)carve.take((size_t)Q * S * keep * 8);
   int32_t* list_ids = (int32_t*)carve.take((size_t)Q * S * keep * 4);
   int32_t* list_cnt = (int32_t*)carve.take((size_t)Q * S * 4);
+  uint32_t* pfreq = ex && ex->per_query_extra > 0 ? (uint32_t*)carve.take((size_t)Q * (size_t)ex->per_query_extra) : nullptr;
+  if (ex)   // a prefix entry's frequency array: the place of its query in a chunk, then its slot
+    for (int64_t i = 0; i < ex->n_px; ++i)
+      ex->at32(ex->o_pxat)[i] = (ex->px_query[(size_t)i] % Q) * ex->slots + ex->at32(ex->o_slot)[ex->at32(ex->o_pxphr)[i]];
   const TextIxP tp{tx.post_off.get(), tx.post_doc.get(), tx.post_tf.get(), tx.post_first.get(), tx.pos.get(), tx.doc_len.get()};
   // the programs (everything before the hit counts), then the idf once every nHit is known
   char* src = prog.blob.data();
@@ -773,14 +1154,26 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
     src = pin;
   }
   NP_HIP(hipMemcpyAsync(d_prog, src, prog.o_nhit, hipMemcpyHostToDevice, st));
+  if (ex) {
+    NP_HIP(hipMemcpyAsync(d_prog + ex->o_phi, src + ex->o_phi, ex->o_pxhit - ex->o_phi, hipMemcpyHostToDevice, st));
+    NP_HIP(hipMemsetAsync(d_prog + ex->o_pxhit, 0, prog.bytes - ex->o_pxhit, st));
+  }
   unsigned long long* h_nhit = (unsigned long long*)(src + prog.o_nhit);
   if (prog.n_items > 0) {
     NP_HIP(hipMemsetAsync(d_prog + prog.o_nhit, 0, (size_t)prog.n_items * 8, st));
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (prog.max_item_df + TEXT_TPB - 1) / TEXT_TPB));
     for (int64_t i0 = 0; i0 < prog.n_items; i0 += 65535) {   // (the items are a grid dimension)
+      const dim3 grid(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0));
+      if (ex) {
+        const TextExprHitP hp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
+                              (const int32_t*)(d_prog + ex->o_phi), (const int32_t*)(d_prog + prog.o_item) + i0,
+                              (unsigned long long*)(d_prog + prog.o_nhit) + i0};
+        text_expr_hit_kernel<<<grid, TEXT_TPB, 0, st>>>(hp);
+        continue;
+      }
       const TextHitP hp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
                         (const int32_t*)(d_prog + prog.o_item) + i0, (unsigned long long*)(d_prog + prog.o_nhit) + i0};
-      text_hit_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0)), TEXT_TPB, 0, st>>>(hp);
+      text_hit_kernel<<<grid, TEXT_TPB, 0, st>>>(hp);
     }
     NP_HIP(hipGetLastError());
     if (counts) {   // the shards' counts summed on the host, the same bytes on every rank
@@ -794,11 +1187,15 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
     for (int64_t i = 0; i < prog.n_items; ++i) prog.phr_hit[(size_t)item[i]] = (int64_t)h_nhit[i];
   }
   double* h_idf = (double*)(src + prog.o_idf);
-  for (int64_t ph = 0; ph < prog.n_phr; ++ph) h_idf[ph] = text_idf(tx.n_rows, prog.phr_hit[(size_t)ph]);
+  // (nHit still -1: a single-token prefix phrase of a tree query.  Its idf is 0 here, no value bm25 can have, and is set by
+  // its chunk's pre-pass below before any kernel reads it)
+  for (int64_t ph = 0; ph < prog.n_phr; ++ph)
+    h_idf[ph] = prog.phr_hit[(size_t)ph] < 0 ? 0.0 : text_idf(tx.n_rows, prog.phr_hit[(size_t)ph]);
   NP_HIP(hipMemcpyAsync(d_prog + prog.o_idf, h_idf, (size_t)std::max<int64_t>(prog.n_phr, 1) * 8, hipMemcpyHostToDevice, st));
   if (!pin) NP_HIP(hipStreamSynchronize(st));   // pageable sources: the copies complete before the blob goes out of scope
   if (visited) NP_HIP(hipMemsetAsync(ctr, 0, 8, st));
   const double avgdl = (double)tx.total_tokens / (double)tx.n_rows;
+  int64_t px_visited = 0;   // postings the prefix pre-passes walk: counted on the host, with the scoring pass's in *visited
   for (int q0 = 0; q0 < B; q0 += Q) {
     const int Qn = std::min(Q, B - q0);
     bool chunk_subsets = subsets;
@@ -820,6 +1217,43 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
       }
       if (chunk_subsets)
         NP_TRY(subset_doc_rows(ix, st, sub.d_ids, sub.d_off, sub.d_qsub + q0, sub.n, sub.total, lo, hi, Qn, NW, docbits, qrow));
+    }
+    if (ex) {   // the chunk's single-token prefix phrases: frequencies, nHit, idf
+      int64_t x0 = 0, x1 = 0;
+      while (x0 < ex->n_px && ex->px_query[(size_t)x0] < q0) ++x0;
+      for (x1 = x0; x1 < ex->n_px && ex->px_query[(size_t)x1] < q0 + Qn; ++x1) {}
+      if (x1 > x0 && ix->n_docs > 0) {
+        NP_HIP(hipMemsetAsync(pfreq, 0, (size_t)Qn * (size_t)ex->per_query_extra, st));
+        const int32_t* pxphr = ex->at32(ex->o_pxphr);
+        int64_t longest = 0;
+        for (int64_t x = x0; x < x1; ++x) {
+          const int32_t ph = pxphr[x], lo = ex->at32(prog.o_terms)[ex->at32(prog.o_ptok)[ph]], hi = ex->at32(ex->o_phi)[ph];
+          longest = std::max(longest, tx.h_post_off[(size_t)hi] - tx.h_post_off[(size_t)lo]);
+          px_visited += tx.h_post_off[(size_t)hi] - tx.h_post_off[(size_t)lo];
+        }
+        const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (longest + TEXT_TPB - 1) / TEXT_TPB));
+        const TextPrefixP pp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
+                             (const int32_t*)(d_prog + ex->o_phi), (const int32_t*)(d_prog + ex->o_pxphr) + x0,
+                             (const int32_t*)(d_prog + ex->o_pxat) + x0, pfreq, ex->stride,
+                             (unsigned long long*)(d_prog + ex->o_pxhit)};
+        for (int64_t i0 = x0; i0 < x1; i0 += 65535) {   // (the entries are a grid dimension)
+          TextPrefixP pi = pp;
+          pi.px_phr += i0 - x0;
+          pi.px_at += i0 - x0;
+          text_prefix_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, x1 - i0)), TEXT_TPB, 0, st>>>(pi);
+        }
+        NP_HIP(hipGetLastError());
+        const int32_t p0 = ex->at32(prog.o_qphr)[q0], p1 = ex->at32(prog.o_qphr)[q0 + Qn];
+        unsigned long long* h_px = (unsigned long long*)(src + ex->o_pxhit);
+        NP_HIP(hipMemcpyAsync(h_px + p0, d_prog + ex->o_pxhit + (size_t)p0 * 8, (size_t)(p1 - p0) * 8, hipMemcpyDeviceToHost, st));
+        NP_HIP(hipStreamSynchronize(st));
+        for (int64_t x = x0; x < x1; ++x) {
+          const int32_t ph = pxphr[x];
+          prog.phr_hit[(size_t)ph] = (int64_t)h_px[ph];
+          h_idf[ph] = text_idf(tx.n_rows, prog.phr_hit[(size_t)ph]);
+        }
+        NP_HIP(hipMemcpyAsync(d_prog + prog.o_idf + (size_t)p0 * 8, h_idf + p0, (size_t)(p1 - p0) * 8, hipMemcpyHostToDevice, st));
+      }
     }
     for (int64_t s0 = 0; s0 < n_slices; s0 += S) {
       const int64_t Sn = std::min(S, n_slices - s0);
@@ -843,8 +1277,14 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
       sp.list_ids = list_ids;
       sp.list_cnt = list_cnt;
       sp.ctr = visited ? ctr : nullptr;
-      if (ix->n_docs > 0)
+      if (ix->n_docs > 0 && ex) {
+        const TextExprP xp{sp, (const int32_t*)(d_prog + ex->o_phi), (const int32_t*)(d_prog + ex->o_slot),
+                           (const int32_t*)(d_prog + ex->o_qnode), (const int32_t*)(d_prog + ex->o_nodes), pfreq,
+                           ex->stride, ex->slots};
+        text_expr_kernel<<<dim3((unsigned)Sn, (unsigned)Qn), TEXT_TPB, 0, st>>>(xp);
+      } else if (ix->n_docs > 0) {
         text_score_kernel<<<dim3((unsigned)Sn, (unsigned)Qn), TEXT_TPB, 0, st>>>(sp);
+      }
       TextMergeP mp;
       mp.list_keys = list_keys;
       mp.list_ids = list_ids;
@@ -870,19 +1310,20 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
     unsigned long long h = 0;
     NP_HIP(hipMemcpyAsync(&h, ctr, 8, hipMemcpyDeviceToHost, st));
     NP_HIP(hipStreamSynchronize(st));
-    *visited = (int64_t)h;
+    *visited = (int64_t)h + px_visited;
   }
   return NP_OK;
 }
 
 // np_hip_text_search and np_hip_text_search_filtered: the subsets come as a host CSR, or (filters != NULL) are evaluated on
-// the call's context into a CSR that stays on the device; query_subset is the query map of either
-static int text_host(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k, const int64_t* subset_ids,
-                     const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset, const np_filter* filters,
-                     int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats) {
+// the call's context into a CSR that stays on the device; query_subset is the query map of either.  exprs != NULL: the _expr
+// forms, tree queries in place of `queries` (a NULL batch gets the flat form's checks: they say so)
+static int text_host(const np_index* ix, const np_text_query* queries, const np_text_expr* exprs, int32_t B, int32_t top_k,
+                     const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset,
+                     const np_filter* filters, int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats) {
   clear_error();
   if (stats) memset(stats, 0, sizeof *stats);
-  NP_TRY(text_check_queries(ix, queries, B, top_k));
+  NP_TRY(exprs ? text_check_exprs(ix, exprs, B, top_k) : text_check_queries(ix, queries, B, top_k));
   if (filters)
     NP_TRY(filter_check_call(ix, filters, (int32_t)n_subsets, query_subset, B, true));
   else
@@ -893,8 +1334,8 @@ static int text_host(const np_index* ix, const np_text_query* queries, int32_t B
     return NP_ERR_INVALID_ARGUMENT;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  TextProg prog;
-  prog.build(ix, queries, B);
+  ExprProg prog;
+  if (exprs) prog.build_expr(ix, exprs, B); else prog.build(ix, queries, B);
   DeviceGuard g(ix->device);
   ContextUse use;
   NP_TRY(use.begin(ix, nullptr));
@@ -914,7 +1355,7 @@ static int text_host(const np_index* ix, const np_text_query* queries, int32_t B
   res.carve(carve);
   int64_t visited = 0;
   NP_TRY(text_run(ix, use, carve.at, (char*)pin + res.bytes(), plan, prog, top_k, sub, res.d_ids, res.d_sc, res.d_cnt,
-                  stats ? &visited : nullptr));
+                  stats ? &visited : nullptr, nullptr, nullptr, exprs ? &prog : nullptr));
   NP_TRY(res.fetch(pin, st));
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
@@ -1203,15 +1644,30 @@ int np_hip_index_set_text_shard(np_index* ix, const np_text_index* text) {
 int np_hip_text_search(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k, const int64_t* subset_ids,
                        const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset, int64_t* out_ids,
                        float* out_scores, int32_t* out_counts, np_stats* stats) {
-  return text_host(ix, queries, B, top_k, subset_ids, subset_offsets, n_subsets, query_subset, nullptr, out_ids, out_scores,
+  return text_host(ix, queries, nullptr, B, top_k, subset_ids, subset_offsets, n_subsets, query_subset, nullptr, out_ids, out_scores,
                    out_counts, stats);
+}
+
+int np_hip_text_search_expr(const np_index* ix, const np_text_expr* queries, int32_t B, int32_t top_k, const int64_t* subset_ids,
+                            const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset, int64_t* out_ids,
+                            float* out_scores, int32_t* out_counts, np_stats* stats) {
+  return text_host(ix, nullptr, queries, B, top_k, subset_ids, subset_offsets, n_subsets, query_subset, nullptr,
+                   out_ids, out_scores, out_counts, stats);
+}
+
+int np_hip_text_search_expr_filtered(const np_index* ix, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                     const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int64_t* out_ids,
+                                     float* out_scores, int32_t* out_counts, np_stats* stats) {
+  static const np_filter none{};
+  return text_host(ix, nullptr, queries, B, top_k, nullptr, nullptr, n_filters, query_filter,
+                   filters ? filters : &none, out_ids, out_scores, out_counts, stats);
 }
 
 int np_hip_text_search_filtered(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k,
                                 const np_filter* filters, int32_t n_filters, const int32_t* query_filter, int64_t* out_ids,
                                 float* out_scores, int32_t* out_counts, np_stats* stats) {
   static const np_filter none{};   // n_filters == 0: nothing to check or evaluate, but still the filtered call's checks
-  return text_host(ix, queries, B, top_k, nullptr, nullptr, n_filters, query_filter, filters ? filters : &none, out_ids,
+  return text_host(ix, queries, nullptr, B, top_k, nullptr, nullptr, n_filters, query_filter, filters ? filters : &none, out_ids,
                    out_scores, out_counts, stats);
 }
 
@@ -1334,14 +1790,15 @@ static int hybrid_host(const np_index* ix, const float* queries, const int32_t* 
                        const np_search_params* params, const np_text_query* text_queries, int32_t fetch_k, float alpha,
                        int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
                        const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int64_t* out_ids,
-                       float* out_scores, int32_t* out_counts, np_stats* stats, const GroupCall* grp) {
+                       float* out_scores, int32_t* out_counts, np_stats* stats, const GroupCall* grp,
+                       const np_text_expr* text_exprs = nullptr) {
   clear_error();
   if (stats) memset(stats, 0, sizeof *stats);
   if (!params) {
     set_error("Search failed: NULL index or params");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  NP_TRY(text_check_queries(ix, text_queries, B, fetch_k));
+  NP_TRY(text_exprs ? text_check_exprs(ix, text_exprs, B, fetch_k) : text_check_queries(ix, text_queries, B, fetch_k));
   NP_TRY(fuse_check(fusion, alpha, grp ? grp->pool_k : params->top_k, B, fetch_k, fetch_k));
   if (grp) NP_TRY(collapse_check(ix, params->top_k, grp->group_size, B, grp->pool_k));
   if (grp && B > 0 && (!grp->out_group || !grp->out_members || !grp->out_total)) {
@@ -1370,8 +1827,8 @@ static int hybrid_host(const np_index* ix, const float* queries, const int32_t* 
   sem.top_k = fetch_k;
   const int top_k = grp ? grp->pool_k : params->top_k;   // of the fused list
   const auto t0 = std::chrono::steady_clock::now();
-  TextProg prog;
-  prog.build(ix, text_queries, B);
+  ExprProg prog;
+  if (text_exprs) prog.build_expr(ix, text_exprs, B); else prog.build(ix, text_queries, B);
   DeviceGuard g(ix->device);
   ContextUse use;
   NP_TRY(use.begin(ix, nullptr));
@@ -1405,7 +1862,7 @@ static int hybrid_host(const np_index* ix, const float* queries, const int32_t* 
   NP_TRY(search_batch_in_use(ix, use, d_q, d_qoff, q_tok_offsets, B, dim, &sem, sub, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt));
   int64_t visited = 0;
   NP_TRY(text_run(ix, use, carve.at, (char*)pin + head, plan, prog, fetch_k, sub, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt,
-                  stats ? &visited : nullptr));
+                  stats ? &visited : nullptr, nullptr, nullptr, text_exprs ? &prog : nullptr));
   NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt, fetch_k, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, fetch_k,
                      res.d_ids, res.d_sc, res.d_cnt));
   if (grp) {
@@ -1436,6 +1893,15 @@ int np_hip_search_hybrid(const np_index* ix, const float* queries, const int32_t
                          float* out_scores, int32_t* out_counts, np_stats* stats) {
   return hybrid_host(ix, queries, q_tok_offsets, B, dim, params, text_queries, fetch_k, alpha, fusion, subset_ids, subset_offsets,
                      n_subsets, query_subset, filters, n_filters, out_ids, out_scores, out_counts, stats, nullptr);
+}
+
+int np_hip_search_hybrid_expr(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                              const np_search_params* params, const np_text_expr* text_queries, int32_t fetch_k, float alpha,
+                              int32_t fusion, const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                              const int32_t* query_subset, const np_filter* filters, int32_t n_filters, int64_t* out_ids,
+                              float* out_scores, int32_t* out_counts, np_stats* stats) {
+  return hybrid_host(ix, queries, q_tok_offsets, B, dim, params, nullptr, fetch_k, alpha, fusion, subset_ids, subset_offsets,
+                     n_subsets, query_subset, filters, n_filters, out_ids, out_scores, out_counts, stats, nullptr, text_queries);
 }
 
 int np_hip_search_hybrid_grouped(const np_index* ix, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,

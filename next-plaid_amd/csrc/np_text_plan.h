@@ -87,6 +87,63 @@ inline int text_check_query(const np_text_query* tq, int32_t q, int64_t n_terms,
   return 0;
 }
 
+// One tree query (np_text_expr) against a vocabulary of n_terms: the phrases as text_check_query checks them, the prefix
+// ranges, and the postfix node list -- stack discipline, children below their parent, every phrase named exactly once, one
+// node left at the end.  `q` only labels the message.
+inline int text_check_expr(const np_text_expr* te, int32_t q, int64_t n_terms, char* why, size_t why_len) {
+  auto fail = [&](const char* what, long long a, long long b = 0) {
+    char msg[200];
+    snprintf(msg, sizeof msg, what, a, b);
+    snprintf(why, why_len, "text query %d: %s", q, msg);
+    return (int)NP_ERR_INVALID_ARGUMENT;
+  };
+  if (!te) return fail("NULL query", 0);
+  if (te->n_phrases < 1 || te->n_phrases > NP_TEXT_MAX_PHRASES) return fail("n_phrases = %lld must be in 1..64", te->n_phrases);
+  if (te->n_nodes < 1 || te->n_nodes > NP_TEXT_MAX_NODES) return fail("n_nodes = %lld must be in 1..127", te->n_nodes);
+  if (!te->phrase_offsets || !te->terms || !te->prefix_hi || !te->nodes) return fail("NULL phrase_offsets, terms, prefix_hi or nodes", 0);
+  if (te->phrase_offsets[0] != 0) return fail("phrase_offsets[0] = %lld must be 0", te->phrase_offsets[0]);
+  for (int32_t p = 0; p < te->n_phrases; ++p) {
+    if (te->phrase_offsets[p + 1] <= te->phrase_offsets[p]) return fail("phrase %lld has no token", p);
+    if (te->phrase_offsets[p + 1] > NP_TEXT_MAX_TOKENS) return fail("more than 256 tokens (at phrase %lld)", p);
+  }
+  for (int32_t i = 0; i < te->phrase_offsets[te->n_phrases]; ++i)
+    if (te->terms[i] < -1 || (int64_t)te->terms[i] >= n_terms) return fail("token %lld names no term of the vocabulary", i);
+  for (int32_t p = 0; p < te->n_phrases; ++p) {
+    const int64_t hi = te->prefix_hi[p];
+    if (hi == 0) continue;
+    const int32_t nt = te->phrase_offsets[p + 1] - te->phrase_offsets[p];
+    const int64_t lo = te->terms[te->phrase_offsets[p + 1] - 1];
+    if (lo < 0) return fail("phrase %lld: a prefix range needs a known last token to start at", p);
+    if (hi <= lo || hi > n_terms) return fail("phrase %lld: the prefix range ends at %lld, outside the vocabulary or not after its start", p, hi);
+    if (nt > 1 && hi - lo > NP_TEXT_MAX_PREFIX_TERMS)
+      return fail("phrase %lld of several tokens ends in a prefix of %lld terms, more than NP_TEXT_MAX_PREFIX_TERMS = 1024", p, hi - lo);
+  }
+  uint64_t used = 0;
+  int32_t stack[NP_TEXT_MAX_NODES];
+  int32_t depth = 0;
+  for (int32_t n = 0; n < te->n_nodes; ++n) {
+    const np_text_node& nd = te->nodes[n];
+    if (nd.op == NP_TEXT_NODE_PHRASE) {
+      if (nd.a < 0 || nd.a >= te->n_phrases) return fail("node %lld names phrase %lld, which the query does not have", n, nd.a);
+      if ((used >> nd.a) & 1) return fail("node %lld names phrase %lld a second time", n, nd.a);
+      used |= (uint64_t)1 << nd.a;
+    } else if (nd.op == NP_TEXT_NODE_AND || nd.op == NP_TEXT_NODE_OR || nd.op == NP_TEXT_NODE_NOT) {
+      if (depth < 2) return fail("node %lld: the stack holds %lld nodes, an operator needs two", n, depth);
+      if (nd.a < 0 || nd.a >= n || nd.b < 0 || nd.b >= n) return fail("node %lld: a child index is not below the node's own", n);
+      if (stack[depth - 1] != nd.b || stack[depth - 2] != nd.a)
+        return fail("node %lld: its children are not the two nodes on top of the stack (%lld below the top)", n, stack[depth - 2]);
+      depth -= 2;
+    } else {
+      return fail("node %lld: unknown op %lld", n, nd.op);
+    }
+    stack[depth++] = n;
+  }
+  if (depth != 1) return fail("%lld nodes are left on the stack at the end, not one", depth);
+  for (int32_t p = 0; p < te->n_phrases; ++p)
+    if (!((used >> p) & 1)) return fail("phrase %lld is named by no node", p);
+  return 0;
+}
+
 // B and top_k of a keyword search.  *why = a string literal.
 inline int text_check_call(int32_t B, int32_t top_k, const char** why) {
   *why = "";

@@ -230,6 +230,15 @@ class np_text_query(C.Structure):
     _fields_ = [("terms", C.c_void_p), ("phrase_offsets", C.c_void_p), ("n_phrases", C.c_int32), ("mode", C.c_int32)]
 
 
+class np_text_node(C.Structure):
+    _fields_ = [("op", C.c_int32), ("a", C.c_int32), ("b", C.c_int32)]
+
+
+class np_text_expr(C.Structure):
+    _fields_ = [("terms", C.c_void_p), ("phrase_offsets", C.c_void_p), ("prefix_hi", C.c_void_p), ("nodes", C.c_void_p),
+                ("n_phrases", C.c_int32), ("n_nodes", C.c_int32)]
+
+
 # np_all_gather_host_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes)
 ALL_GATHER_HOST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 NP_COMM_DEFERRED_STATUS = 1
@@ -256,6 +265,7 @@ EXPORTS = [
     "np_hip_index_set_columns", "np_hip_filter_eval", "np_hip_search_batch_filtered", "np_hip_search_exact_filtered",
     "np_hip_index_set_text", "np_hip_text_search", "np_hip_text_search_device", "np_hip_text_search_filtered",
     "np_hip_fuse", "np_hip_fuse_device", "np_hip_search_hybrid",
+    "np_hip_text_search_expr", "np_hip_text_search_expr_filtered", "np_hip_search_hybrid_expr",
     "np_hip_index_set_column_text", "np_hip_text_match",
     "np_hip_index_set_text_shard", "np_hip_text_search_sharded", "np_hip_text_search_sharded_filtered",
     "np_hip_search_batch_sharded_filtered", "np_hip_search_hybrid_sharded",
@@ -316,7 +326,7 @@ def lib():
         raise DeviceUnavailableError(f"{path} speaks ABI v{ver}, this mirror v{NP_ABI_VERSION}: rebuild the library")
     for which, st in ((0, np_info), (1, np_stats), (2, np_search_params), (3, np_open_opts), (4, np_kmeans_opts),
                       (5, np_kmeans_report), (6, np_index_config), (7, np_kmeans_plan), (8, np_update_config),
-                      (9, np_update_report), (10, np_pool_opts), (11, np_pool_report)):
+                      (9, np_update_report), (10, np_pool_opts), (11, np_pool_report), (12, np_text_expr)):
         if int(L.np_hip_struct_size(which)) != C.sizeof(st):
             raise DeviceUnavailableError(f"{path}: sizeof({st.__name__}) is {int(L.np_hip_struct_size(which))} in the library, "
                                          f"{C.sizeof(st)} in this mirror")
@@ -385,6 +395,12 @@ def lib():
     L.np_hip_search_hybrid.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_text_query), i32,
                                        C.c_float, i32, vp, vp, i64, vp, C.POINTER(np_filter), i32, vp, vp, vp,
                                        C.POINTER(np_stats)]
+    L.np_hip_text_search_expr.argtypes = [vp, C.POINTER(np_text_expr), i32, i32, vp, vp, i64, vp, vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_text_search_expr_filtered.argtypes = [vp, C.POINTER(np_text_expr), i32, i32, C.POINTER(np_filter), i32, vp, vp, vp,
+                                                   vp, C.POINTER(np_stats)]
+    L.np_hip_search_hybrid_expr.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_text_expr), i32,
+                                            C.c_float, i32, vp, vp, i64, vp, C.POINTER(np_filter), i32, vp, vp, vp,
+                                            C.POINTER(np_stats)]
     L.np_hip_index_set_text_shard.argtypes = [vp, C.POINTER(np_text_index)]
     L.np_hip_text_search_sharded.argtypes = [vp, vp, C.POINTER(np_text_query), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.np_hip_text_search_sharded_filtered.argtypes = [vp, vp, C.POINTER(np_text_query), i32, i32, C.POINTER(np_filter), i32, vp,
@@ -601,11 +617,43 @@ class _CTextQueries:
         self.arr = (np_text_query * max(self.n, 1))()
         self.keep = []
         for j, q in enumerate(queries):
+            if not hasattr(q, "mode"):
+                raise ValueError("a tree query (text.TextExpr) where only flat keyword queries are taken: the sharded, grouped "
+                                 "and device-pointer searches have no _expr form yet")
             terms = np.ascontiguousarray(q.terms, np.int32).reshape(-1)
             off = np.ascontiguousarray(q.phrase_offsets, np.int32).reshape(-1)
             self.keep += [terms, off]
             self.arr[j] = np_text_query(terms.ctypes.data if terms.size else None, off.ctypes.data if off.size else None,
                                         max(off.size - 1, 0), int(q.mode))
+
+
+class _CTextExprs:
+    """The ctypes form of tree queries (text.TextExpr; a flat text.TextQuery is lifted to a chain of ANDs or ORs); keeps
+    every array it points to alive."""
+
+    def __init__(self, queries):
+        from . import text as T
+        self.n = len(queries)
+        self.arr = (np_text_expr * max(self.n, 1))()
+        self.keep = []
+        for j, q in enumerate(queries):
+            if not isinstance(q, T.TextExpr):
+                q = T.TextExpr.from_query(q)
+            terms = np.ascontiguousarray(q.terms, np.int32).reshape(-1)
+            off = np.ascontiguousarray(q.phrase_offsets, np.int32).reshape(-1)
+            hi = np.ascontiguousarray(q.prefix_hi(), np.int32).reshape(-1)
+            nodes = np.ascontiguousarray(q.nodes, np.int32).reshape(-1)
+            self.keep += [terms, off, hi, nodes]
+            self.arr[j] = np_text_expr(*(a.ctypes.data if a.size else None for a in (terms, off, hi, nodes)),
+                                       max(off.size - 1, 0), nodes.size // 3)
+
+
+def _c_text_queries(queries):
+    """(the ctypes queries, "_expr" or ""): a batch that holds a text.TextExpr goes to the _expr entries as a whole."""
+    from . import text as T
+    if any(isinstance(q, T.TextExpr) for q in queries):
+        return _CTextExprs(queries), "_expr"
+    return _CTextQueries(queries), ""
 
 
 def _pad_lists(lists, dtype, width=None):
@@ -1552,9 +1600,10 @@ class MmapIndex:
         """set_text_shard from the metadata.db of an index directory; returns the (whole table's) TextIndexData."""
         return self._load_text(index_path, "load_text_shard", self.set_text_shard)
 
-    def _text_queries(self, text_queries, empty_matches_nothing: bool):
-        """Strings are compiled against self.text, TextQuery objects pass; '' (text_search.rs:1247: an empty query has an
-        empty result) -> None, or the query that matches nothing."""
+    def _text_queries(self, text_queries, empty_matches_nothing: bool, full_grammar: bool = False):
+        """Strings are compiled against self.text (full_grammar: by text.compile_text_expr, into TextExpr trees), TextQuery
+        and TextExpr objects pass; '' (text_search.rs:1247: an empty query has an empty result) -> None, or the query that
+        matches nothing."""
         from . import text as T
         out = []
         for q in text_queries:
@@ -1564,7 +1613,7 @@ class MmapIndex:
                 else:
                     if getattr(self, "text", None) is None:
                         raise ValueError("the handle has no keyword index (set_text / load_text)")
-                    q = T.compile_text_query(q, self.text)
+                    q = T.compile_text_expr(q, self.text) if full_grammar else T.compile_text_query(q, self.text)
             out.append(q)
         return out
 
@@ -1586,59 +1635,72 @@ class MmapIndex:
             return _Scope("subset", sid, np.array([0, sid.size], np.int64), 1, np.zeros(max(B, 1), np.int32), None)
         return _Scope(None, None, None, 0, None, None)
 
-    def _live_text_queries(self, text_queries, subset, subsets, filters):
+    def _live_text_queries(self, text_queries, subset, subsets, filters, full_grammar: bool = False):
         """The prologue of text_search, here and over the shards: (B, live, their compiled queries, the scope of those).  An
         empty query is not searched: `live` lists the positions of the others, which are all the library sees."""
         if isinstance(text_queries, str):
             text_queries = [text_queries]
-        qs = self._text_queries(list(text_queries), False)
+        qs = self._text_queries(list(text_queries), False, full_grammar)
         live = [i for i, q in enumerate(qs) if q is not None]
         scope = self._scope(len(qs), subset, subsets, filters, "text_search").of_rows(live)
         return len(qs), live, [qs[i] for i in live], scope
 
-    def _hybrid_text_queries(self, B, text_queries):
-        """The text half of the hybrid-shaped calls, one per query: an empty one matches nothing (its keyword list is empty)."""
-        qs = self._text_queries(list(text_queries), True)
+    def _hybrid_compiled(self, B, text_queries, full_grammar: bool = False):
+        """The text half of the hybrid-shaped calls, compiled, one per query: an empty one matches nothing (its keyword list
+        is empty)."""
+        qs = self._text_queries(list(text_queries), True, full_grammar)
         if len(qs) != B:
             raise ValueError(f"{B} queries and {len(qs)} text queries")
-        return _CTextQueries(qs)
+        return qs
 
-    def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None):
+    def _hybrid_text_queries(self, B, text_queries):
+        """... in ctypes form, for the calls that take flat queries only (a text.TextExpr is refused by name)."""
+        return _CTextQueries(self._hybrid_compiled(B, text_queries))
+
+    def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None, full_grammar: bool = False):
         """np_hip_text_search: BM25 keyword search with SQLite FTS5's results (text_search.rs:1246-1342) -- for every query
         the top_k documents by -bm25(), f64 score descending, ties by ascending id.  A query is FTS5 text (compiled by
         text.compile_text_query against the handle's keyword index) or a text.TextQuery; '' returns an empty result.  Scope:
-        `subset`, `subsets` or `filters` as search_exact takes them.  Returns QueryResults."""
-        B, live, qs, scope = self._live_text_queries(text_queries, subset, subsets, filters)
+        `subset`, `subsets` or `filters` as search_exact takes them.  Returns QueryResults.
+
+        A text.TextExpr -- a tree with FTS5's NOT, AND, OR, parentheses and prefixes -- among the queries sends the whole
+        batch to np_hip_text_search_expr (flat queries are lifted to trees and keep their bytes); full_grammar=True compiles
+        strings with text.compile_text_expr into such trees.  The default refuses what compile_text_query refuses."""
+        B, live, qs, scope = self._live_text_queries(text_queries, subset, subsets, filters, full_grammar)
         n = len(live)
-        tq = _CTextQueries(qs)
+        tq, form = _c_text_queries(qs)
         rows = _ResultRows(n, max(int(top_k), 1))
         st = np_stats()
         if scope.cf is not None:
-            _check(lib().np_hip_text_search_filtered(self._h, tq.arr, n, int(top_k), *scope.filter_args, _ptr(scope.qmap),
-                                                     *rows.ptrs(), C.byref(st)))
+            _check(getattr(lib(), f"np_hip_text_search{form}_filtered")(self._h, tq.arr, n, int(top_k), *scope.filter_args,
+                                                                        _ptr(scope.qmap), *rows.ptrs(), C.byref(st)))
         else:
-            _check(lib().np_hip_text_search(self._h, tq.arr, n, int(top_k), *scope.csr, *rows.ptrs(), C.byref(st)))
+            _check(getattr(lib(), f"np_hip_text_search{form}")(self._h, tq.arr, n, int(top_k), *scope.csr, *rows.ptrs(),
+                                                               C.byref(st)))
         self.last_stats = st.as_dict()
         return rows.results(live, B)
 
     def search_hybrid(self, queries, text_queries, params: "SearchParameters", alpha: float = 0.75,
-                      fusion: str = "relative_score", fetch_k: int | None = None, subset=None, subsets=None, filters=None):
+                      fusion: str = "relative_score", fetch_k: int | None = None, subset=None, subsets=None, filters=None,
+                      full_grammar: bool = False):
         """np_hip_search_hybrid: the /search handler's hybrid request (search.rs:134-375) in one call -- the semantic pass and
         the keyword pass with top_k = fetch_k (default: the handler's 3 * params.top_k) and their fusion ("relative_score",
         the default, or "rrf") to params.top_k, on the device.  Query i gets what fuse(...) returns for search_batch and
-        text_search with top_k = fetch_k.  An empty text query contributes an empty keyword list.  Returns QueryResults."""
+        text_search with top_k = fetch_k.  An empty text query contributes an empty keyword list.  Returns QueryResults.
+        Tree queries (a text.TextExpr among them, or strings under full_grammar=True) go to np_hip_search_hybrid_expr, as
+        text_search routes them."""
         queries = list(queries)
         flat, off = self._pack(queries)
         B = len(queries)
-        tq = self._hybrid_text_queries(B, text_queries)
+        tq, form = _c_text_queries(self._hybrid_compiled(B, text_queries, full_grammar))
         fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
         scope = self._scope(B, subset, subsets, filters, "search_hybrid")
         rows = _ResultRows(B, max(int(params.top_k), 1))
         p = params._c()
         st = np_stats()
-        _check(lib().np_hip_search_hybrid(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), tq.arr, fk,
-                                          float(alpha), _fusion_mode(fusion), *scope.csr, *scope.filter_args, *rows.ptrs(),
-                                          C.byref(st)))
+        _check(getattr(lib(), f"np_hip_search_hybrid{form}")(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p),
+                                                             tq.arr, fk, float(alpha), _fusion_mode(fusion), *scope.csr,
+                                                             *scope.filter_args, *rows.ptrs(), C.byref(st)))
         self.last_stats = st.as_dict()
         return rows.results()
 

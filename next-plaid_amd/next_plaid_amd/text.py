@@ -435,3 +435,271 @@ def compile_text_query(text: str, data: TextIndexData) -> TextQuery:
     if sum(len(p) for p in phrases) > NP_TEXT_MAX_TOKENS:
         raise TextQueryError(f"more than {NP_TEXT_MAX_TOKENS} tokens")
     return TextQuery.from_phrases(phrases, mode)
+
+
+# ---- FTS5 query text -> a tree of phrases (the boolean grammar and prefix queries) -------------------------------------------
+
+NP_TEXT_NODE_PHRASE, NP_TEXT_NODE_AND, NP_TEXT_NODE_OR, NP_TEXT_NODE_NOT = 0, 1, 2, 3
+NP_TEXT_MAX_NODES = 127
+NP_TEXT_MAX_PREFIX_TERMS = 1024   # terms a prefix may stand for at the end of a phrase of several tokens
+_NODE_OPS = {"and": NP_TEXT_NODE_AND, "or": NP_TEXT_NODE_OR, "not": NP_TEXT_NODE_NOT}
+
+
+@dataclass
+class TextExpr:
+    """A compiled keyword query with FTS5's boolean operators (np_text_expr): the phrases as TextQuery has them, in the
+    order of the query text; prefix[p] = None, or the range (lo, hi) of term ids the phrase's last token stands for (the
+    token itself is then lo, or -1 where the range is empty: such a phrase never occurs); nodes = the tree in postfix order,
+    rows of (op, a, b): NP_TEXT_NODE_PHRASE names phrase a, AND / OR / NOT name their left and right child rows.  NOT is
+    binary: a AND NOT b.  The last row is the root."""
+    terms: np.ndarray            # int32
+    phrase_offsets: np.ndarray   # int32 [n_phrases + 1]
+    prefix: list                 # [n_phrases] None | (lo, hi)
+    nodes: np.ndarray            # int32 [n_nodes, 3]
+
+    @property
+    def n_phrases(self) -> int:
+        return int(self.phrase_offsets.size) - 1
+
+    @property
+    def n_nodes(self) -> int:
+        return int(self.nodes.shape[0])
+
+    def phrases(self) -> list:
+        return [self.terms[self.phrase_offsets[i]: self.phrase_offsets[i + 1]].tolist() for i in range(self.n_phrases)]
+
+    def prefix_hi(self) -> np.ndarray:
+        """np_text_expr.prefix_hi: the end of a phrase's range, 0 for an exact last token (and for an empty range, whose
+        last token is -1)."""
+        return np.asarray([0 if r is None or r[1] <= r[0] else r[1] for r in self.prefix], np.int32).reshape(-1)
+
+    @classmethod
+    def from_tree(cls, tree) -> "TextExpr":
+        """tree = ("phrase", term ids[, (lo, hi)]) or (op, left, right) with op "and", "or" or "not".  The last token of a
+        prefix phrase is overwritten with the start of its range."""
+        phrases, prefix, nodes = [], [], []
+
+        def walk(t):
+            if t[0] == "phrase":
+                ids, rng = list(t[1]), (tuple(t[2]) if len(t) > 2 and t[2] is not None else None)
+                if rng is not None:
+                    ids[-1] = int(rng[0]) if rng[1] > rng[0] else -1
+                phrases.append(ids)
+                prefix.append(rng)
+                nodes.append((NP_TEXT_NODE_PHRASE, len(phrases) - 1, 0))
+            else:
+                a = walk(t[1])
+                b = walk(t[2])
+                nodes.append((_NODE_OPS[t[0]], a, b))
+            return len(nodes) - 1
+
+        walk(tree)
+        off = np.zeros(len(phrases) + 1, np.int32)
+        off[1:] = np.cumsum([len(p) for p in phrases])
+        flat = [x for p in phrases for x in p]
+        return cls(np.asarray(flat, np.int32).reshape(-1), off, prefix, np.asarray(nodes, np.int32).reshape(-1, 3))
+
+    @classmethod
+    def from_query(cls, query: TextQuery) -> "TextExpr":
+        """A flat TextQuery as a tree: its phrases chained from the left by AND or by OR."""
+        tree = None
+        for p in query.phrases():
+            leaf = ("phrase", p)
+            tree = leaf if tree is None else ("and" if query.mode == NP_TEXT_AND else "or", tree, leaf)
+        return cls.from_tree(tree)
+
+
+def _lex_expr(text: str):
+    """Tokens of the full grammar: ('str', value) for a double-quoted string or a bareword, ('AND' | 'OR' | 'NOT' | '(' | ')' |
+    '*' | '+', None).  NEAR, ^ and column filters raise TextQueryError by name."""
+    items, i, n = [], 0, len(text)
+    refused = {"^": "an initial-token query (^)", ":": "a column filter (:)", "{": "a column filter ({})",
+               "}": "a column filter ({})", "-": "a column filter (-)", ",": "a NEAR argument list (,)"}
+    while i < n:
+        ch = text[i]
+        if ch in " \t\n\r":
+            i += 1
+        elif ch == '"':
+            j, buf = i + 1, []
+            while True:
+                if j >= n:
+                    raise TextQueryError("an unterminated string")
+                if text[j] == '"':
+                    if j + 1 < n and text[j + 1] == '"':
+                        buf.append('"')
+                        j += 2
+                        continue
+                    break
+                buf.append(text[j])
+                j += 1
+            items.append(("str", "".join(buf)))
+            i = j + 1
+        elif _bareword_char(ch):
+            j = i
+            while j < n and _bareword_char(text[j]):
+                j += 1
+            word = text[i:j]
+            k = j
+            while k < n and text[k] in " \t\n\r":
+                k += 1
+            if word == "NEAR" and k < n and text[k] == "(":
+                raise TextQueryError("NEAR")
+            items.append((word, None) if word in ("AND", "OR", "NOT") else ("str", word))
+            i = j
+        elif ch in "()*+":
+            items.append((ch, None))
+            i += 1
+        elif ch in refused:
+            raise TextQueryError(refused[ch])
+        else:
+            raise TextQueryError(f"the character {ch!r} outside a string (an FTS5 syntax error)")
+    return items
+
+
+def parse_text_expr(text: str):
+    """The tree of an FTS5 query with SQLite's precedence: implicit AND (between phrases only) binds tightest, then NOT,
+    then AND, then OR, all from the left.  Returns nested tuples: ("phrase", [strings joined by +], prefix flag),
+    ("list", [phrases]) for a run of phrases joined by implicit AND, (op, left, right)."""
+    items = _lex_expr(text)
+    if not items:
+        raise TextQueryError("an empty query (an FTS5 syntax error)")
+    pos = 0
+
+    def peek():
+        return items[pos][0] if pos < len(items) else None
+
+    def phrase():
+        nonlocal pos
+        parts, star = [items[pos][1]], False
+        pos += 1
+        while True:
+            if peek() == "*":
+                if star:
+                    raise TextQueryError("* after * (an FTS5 syntax error)")
+                star = True
+                pos += 1
+            elif peek() == "+":
+                if star:
+                    raise TextQueryError("a prefix (*) before the end of a phrase")
+                pos += 1
+                if peek() != "str":
+                    raise TextQueryError("+ without a string after it (an FTS5 syntax error)")
+                parts.append(items[pos][1])
+                pos += 1
+            else:
+                break
+        if peek() == "(":
+            raise TextQueryError("a phrase followed by ( (an FTS5 syntax error)")
+        return ("phrase", parts, star)
+
+    def primary():
+        nonlocal pos
+        if peek() == "(":
+            pos += 1
+            e = expr(0)
+            if peek() != ")":
+                raise TextQueryError("an unbalanced ( (an FTS5 syntax error)")
+            pos += 1
+            if peek() in ("str", "("):
+                raise TextQueryError("an expression in parentheses followed by a phrase or ( (an FTS5 syntax error: implicit "
+                                     "AND joins phrases only)")
+            return e
+        if peek() != "str":
+            raise TextQueryError(f"{peek() or 'the end of the query'} where a phrase is expected (an FTS5 syntax error)")
+        run = [phrase()]
+        while peek() == "str":
+            run.append(phrase())
+        return ("list", run)
+
+    level = {"OR": 1, "AND": 2, "NOT": 3}
+
+    def expr(min_level):
+        nonlocal pos
+        left = primary()
+        while peek() in level and level[peek()] >= min_level:
+            op = peek()
+            pos += 1
+            right = expr(level[op] + 1)
+            left = (op.lower(), left, right)
+        return left
+
+    tree = expr(0)
+    if pos != len(items):
+        raise TextQueryError(f"{items[pos][0]} where the query should end (an FTS5 syntax error)")
+    return tree
+
+
+def _term_bytes(data: TextIndexData):
+    """The vocabulary as UTF-8 bytes, checked once to ascend (fts5vocab lists terms in byte order): what makes the terms
+    that start with a prefix one range of term ids."""
+    enc = data._cache.get(("term bytes",))
+    if enc is None:
+        enc = [t.encode("utf-8") for t in data.terms]
+        if any(a >= b for a, b in zip(enc, enc[1:])):
+            raise ValueError("the vocabulary is not in ascending byte order: a prefix is no range of term ids")
+        data._cache[("term bytes",)] = enc
+    return enc
+
+
+def prefix_range(token: str, data: TextIndexData):
+    """(lo, hi): the term ids whose terms start with `token`; lo == hi where none does."""
+    import bisect
+    enc, pre = _term_bytes(data), token.encode("utf-8")
+    lo = bisect.bisect_left(enc, pre)
+    end = pre.rstrip(b"\xff")
+    hi = len(enc) if not end else bisect.bisect_left(enc, end[:-1] + bytes([end[-1] + 1]))
+    return lo, max(lo, hi)
+
+
+def compile_text_expr(text: str, data: TextIndexData) -> TextExpr:
+    """FTS5 query text -> TextExpr: phrases (double-quoted or bare words, joined by + into one phrase), * after a phrase
+    (its last token becomes a prefix), implicit AND between phrases, NOT, AND, OR and parentheses, with SQLite's precedence.
+    Each phrase is tokenised by the index's own tokenizer.  NEAR, ^, column filters and FTS5 syntax errors raise
+    TextQueryError naming the construct, and so do a prefix under the trigram tokenizer, a * before the end of a phrase,
+    more than 64 phrases, more than 256 tokens, and a phrase of several tokens whose prefix stands for more than
+    NP_TEXT_MAX_PREFIX_TERMS terms.
+
+    A phrase without tokens does what SQLite 3.37 does with it: in a run of phrases joined by implicit AND it is dropped;
+    a run that holds nothing else, like an operand of AND, OR or NOT that is such a phrase, matches no document (it compiles
+    to a phrase of one unknown token)."""
+    tree = parse_text_expr(text)
+    count = {"phrases": 0, "tokens": 0}
+
+    def leaf(ids, rng=None):
+        count["phrases"] += 1
+        count["tokens"] += len(ids)
+        return ("phrase", ids, rng)
+
+    def build(t):
+        if t[0] == "list":
+            kept = []
+            for _, parts, star in t[1]:
+                if star and data.tokenize == "trigram":
+                    raise TextQueryError("a prefix query (*) under the trigram tokenizer")
+                ids, toks = [], []
+                for s in parts:
+                    toks += data.tokens_of(s)
+                ids = [data.vocab.get(x, -1) for x in toks]
+                if not ids:
+                    continue
+                rng = None
+                if star:
+                    rng = prefix_range(toks[-1], data)
+                    if len(ids) > 1 and rng[1] - rng[0] > NP_TEXT_MAX_PREFIX_TERMS:
+                        raise TextQueryError(f"a phrase of several tokens ending in a prefix of {rng[1] - rng[0]} terms (more "
+                                             f"than NP_TEXT_MAX_PREFIX_TERMS = {NP_TEXT_MAX_PREFIX_TERMS})")
+                kept.append(leaf(ids, rng))
+            if not kept:
+                return leaf([-1])
+            out = kept[0]
+            for k in kept[1:]:
+                out = ("and", out, k)
+            return out
+        return (t[0], build(t[1]), build(t[2]))
+
+    built = build(tree)
+    if count["phrases"] > NP_TEXT_MAX_PHRASES:
+        raise TextQueryError(f"more than {NP_TEXT_MAX_PHRASES} phrases")
+    if count["tokens"] > NP_TEXT_MAX_TOKENS:
+        raise TextQueryError(f"more than {NP_TEXT_MAX_TOKENS} tokens")
+    return TextExpr.from_tree(built)
