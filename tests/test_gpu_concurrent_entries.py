@@ -1,10 +1,39 @@
-"""Every entry point that checks a context out of the handle's pool, from six threads at once on one handle: search_batch (with
-and without subsets and filters), search_exact, score_pairs, filter_ids, text_search at top_k 1 and 1024, fuse and
-search_hybrid.  All of them carve the same per-context arena, pinned area, filter scratch and filter CSR, which grow on demand
--- here while other threads wait for, or run on, the other context.  Needs a real MI355X.
+"""Every host entry point that checks a context out of the handle's pool, from six threads at once on one handle.  All of them
+carve the same per-context arena, pinned area, filter scratch and filter CSR, which grow on demand -- here while other threads
+wait for, or run on, the other context.  Needs a real MI355X.
 
-Every result must be, bit for bit, what the same call gave when it ran alone; the keyword and the filter results of that
-serial run are themselves checked against tests/text_restate.py and tests/filter_restate.py."""
+The entries that check a context out (ContextUse::begin), file by file, and the call of the list that drives each:
+  np_search.hip  np_hip_search_batch, _subsets, _filtered             search_batch, with subsets, with filters
+                 np_hip_search_batch_device, _subsets_device,          not in the list: the same pass behind the staging of the
+                 np_hip_search_phase_a / _b                            host forms; the phases belong to the sharded search (ranks)
+  np_scan.hip    np_hip_search_exact, _filtered                       search_exact
+                 np_hip_search_exact_device                            not in the list: the same code behind the staging
+  np_pairs.hip   np_hip_score_pairs                                   score_pairs
+                 np_hip_score_pairs_device                             not in the list: the same code behind the staging
+  np_filter.hip  np_hip_filter_eval                                   filter_ids
+  np_match.hip   np_hip_text_match                                     not in the list: it needs a column's text in HBM
+                                                                       (text_on_device), which would change how the LIKE filters
+                                                                       of this list are evaluated
+  np_text.hip    np_hip_text_search, _filtered                        text_search at top_k 1 and 1024
+                 np_hip_text_search_expr, _expr_filtered              tree text_search at top_k 1 and 1024: single-token
+                                                                       prefixes, a prefix at the end of a phrase of several
+                                                                       tokens, NOTs.  The prefix pre-pass is the one place
+                                                                       where a call synchronises in its middle and reads
+                                                                       through the pinned area
+                 np_hip_fuse                                          fuse
+                 np_hip_search_hybrid, np_hip_search_hybrid_expr      search_hybrid, with filters, with trees
+                 np_hip_search_hybrid_grouped                         search_hybrid_grouped
+                 np_hip_text_search_device, np_hip_fuse_device         not in the list: the same code behind the staging
+                 np_hip_text_search_sharded, _sharded_filtered,        not in the list: they need ranks
+                 np_hip_search_hybrid_sharded
+  np_group.hip   np_hip_collapse                                      collapse
+                 np_hip_search_batch_grouped                          search_grouped
+                 np_hip_collapse_device                                not in the list: the same code behind the staging
+
+Every result must be, bit for bit, what the same call gave when it ran alone; the serial run is itself checked: the keyword
+results against tests/text_restate.py, the trees against tests/text_expr_restate.py, the filters against
+tests/filter_restate.py, and the grouped calls against the walk of tests/collapse_restate.py over the serial search_batch and
+search_hybrid lists."""
 import threading
 
 import numpy as np
@@ -14,8 +43,10 @@ from helpers import hip_index, make_arrays, synth
 
 import next_plaid_amd as npa
 from next_plaid_amd import text as T
+import collapse_restate as CR
 import filter_restate as FR
 import text_restate as TR
+import text_expr_restate as TX
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +92,15 @@ def test_every_entry_point_from_six_threads(material, n_contexts):
         tq = [T.compile_text_query(s, data) for s in ("wo1 wo2", "wo3 OR wo5 OR wo7", '"wo1 wo0"', "wo0", "nowhere", "wo2",
                                                        '"wo1 wo0" OR wo4', "wo5 AND wo1 AND wo0", "wo0 OR wo1")]
         rs = TR.Restated(data, N_DOCS)
+        trees = [T.compile_text_expr(s, data) for s in ("wo1*", "wo2 NOT wo1*", '"wo1 wo" *', "(wo3* OR wo5) AND wo0", "nowhere*",
+                                                         "wo1* NOT (wo2 OR wo3*)", '"wo0 wo1" * OR wo4', "wo5 AND wo1* AND wo0",
+                                                         "wo* NOT nowhere")]
+        xs = TX.RestatedExpr(data, N_DOCS)
+        groups = (np.arange(N_DOCS) * 7 % 37).astype(np.int32)
+        hx.set_groups(groups, n_groups=37)
+        pg = npa.SearchParameters(n_full_scores=128, top_k=3, n_ivf_probe=4)
+        pool = lambda k: npa.SearchParameters(n_full_scores=128, top_k=k, n_ivf_probe=4)
+        pooled = hx.search_batch(qs, pool(64))                         # the ranked lists that collapse walks
         some = np.arange(0, N_DOCS, 3)
         subsets = [None, some, some, None, np.zeros(0, np.int64), some, None, np.arange(N_DOCS), some]
         pairs = [np.array([3, 14, 15, 92, 653, 589, 793, 238][: i + 1]) for i in range(len(qs))]
@@ -78,6 +118,13 @@ def test_every_entry_point_from_six_threads(material, n_contexts):
             "fuse": lambda: npa.fuse("relative_score", 0.75, 2 * cap, fuse_in[0], fuse_in[1], fuse_in[2], fuse_in[3], index=hx),
             "search_hybrid": lambda: hx.search_hybrid(qs, tq, p, alpha=0.75, fusion="relative_score", fetch_k=40),
             "search_hybrid filters": lambda: hx.search_hybrid(qs, tq, p, alpha=0.5, fusion="rrf", filters=progs),
+            "text_search trees 1": lambda: hx.text_search(trees, 1),
+            "text_search trees 1024": lambda: hx.text_search(trees, cap),
+            "search_hybrid trees": lambda: hx.search_hybrid(qs, trees, p, alpha=0.75, fusion="relative_score", fetch_k=40),
+            "collapse": lambda: npa.collapse([r.passage_ids for r in pooled], [r.scores for r in pooled], 5, 3, hx),
+            "search_grouped": lambda: hx.search_grouped(qs, pg, group_size=2, pool_k=64),
+            "search_hybrid_grouped": lambda: hx.search_hybrid_grouped(qs, tq, pg, group_size=2, pool_k=60, alpha=0.75,
+                                                                      fusion="relative_score", fetch_k=40),
         }
         kw = hx.text_search(tq, cap)
         sem = hx.search_exact(qs, cap)
@@ -95,6 +142,22 @@ def test_every_entry_point_from_six_threads(material, n_contexts):
         by_subsets = hx.search_batch(qs, p, subsets=[None if f is None else FR.select(f, sch) for f in progs])
         assert flat(by_subsets) == serial["search_batch filters"]
         assert sum(r.passage_ids.size for r in calls["search_hybrid filters"]()) > 0
+        # ... the trees to their restatement, the grouped calls to the walk over the serial lists
+        assert [sum(1 for r in q.prefix if r is not None) for q in trees] == [1, 1, 1, 1, 1, 2, 1, 1, 1] and trees[2].phrases()[0][0] >= 0
+        for k_, name in ((1, "text_search trees 1"), (cap, "text_search trees 1024")):
+            for q, r in zip(trees, calls[name]()):
+                ids, sc = xs.expr_search(q, k_)
+                assert np.array_equal(r.passage_ids, ids) and np.array_equal(r.scores.view(np.uint32), sc.view(np.uint32)), name
+        by_tree = calls["text_search trees 1024"]()
+        assert max(r.passage_ids.size for r in by_tree) == cap and by_tree[2].passage_ids.size > 0 and by_tree[4].passage_ids.size == 0
+        assert sum(r.passage_ids.size for r in calls["search_hybrid trees"]()) > 0
+        walks = lambda base, top_k, gs: [CR.walked(CR.walk(r.passage_ids, r.scores, groups, top_k, gs)) for r in base]
+        listed = lambda got: [CR.listed(g) for g in got]
+        assert listed(calls["collapse"]()) == walks(pooled, 5, 3)
+        assert listed(calls["search_grouped"]()) == walks(pooled, 3, 2)
+        assert listed(calls["search_hybrid_grouped"]()) == walks(
+            hx.search_hybrid(qs, tq, pool(60), alpha=0.75, fusion="relative_score", fetch_k=40), 3, 2)
+        assert all(len(g) == 3 for g in calls["search_grouped"]()) and any(t > 1 for g in calls["collapse"]() for _, _, _, t in g)
 
         out, errs = {}, []
         start = threading.Barrier(N_THREADS)

@@ -5,13 +5,10 @@ fills the whole 2048-entry window (fuse_kernel).  Needs a real MI355X.
 
 The reference is tests/text_restate.py, ids equal and f32 scores equal as uint32; tests/test_text_restate_cpu.py pins it to
 SQLite on the very query shapes used here."""
-import os
-import re
-
 import numpy as np
 import pytest
 
-from helpers import ROOT, hip_index, make_arrays
+from text_limit_shapes import index_data, plan_constant, same, tiny_index
 
 import next_plaid_amd as npa
 from next_plaid_amd import text as T
@@ -24,38 +21,8 @@ CAP = T.NP_TEXT_MAX_TOPK
 WINDOW = 2 * CAP   # entries of the merge window and of a fusion
 
 
-def plan_constant(name):
-    with open(os.path.join(ROOT, "next-plaid_amd", "csrc", "np_text_plan.h")) as f:
-        return int(re.search(rf"constexpr int64_t {name} = (\d+);", f.read()).group(1))
-
-
 def test_the_constants_are_the_plans():
     assert plan_constant("NP_TEXT_SLICE_DOCS") == SLICE and T.NP_TEXT_MAX_PHRASES == 64 and T.NP_TEXT_MAX_TOKENS == 256
-
-
-def tiny_index(n_docs, **opts):
-    """An index of n_docs one-token documents: the keyword search only needs its document count."""
-    spec, a = make_arrays(num_docs=n_docs, num_centroids=16, dim=32, nbits=2, doc_len_min=1, doc_len_max=1, seed=3)
-    return a, hip_index(a, **opts)
-
-
-def same(r, ids, sc):
-    return (r.passage_ids.dtype == np.int64 and r.scores.dtype == np.float32 and np.array_equal(r.passage_ids, ids)
-            and np.array_equal(r.scores.view(np.uint32), sc.view(np.uint32)))
-
-
-def index_data(terms, per_term, n_rows):
-    """A TextIndexData from per-term (documents, positions) arrays in any order: sorted to (document, position) here."""
-    docs, poss, off = [], [], [0]
-    for d, p in per_term:
-        d, p = np.asarray(d, np.int64), np.asarray(p, np.int64)
-        o = np.argsort(d * (1 << 32) + p, kind="stable")
-        docs.append(d[o])
-        poss.append(p[o].astype(np.int32))
-        off.append(off[-1] + d.size)
-    assert list(terms) == sorted(terms)
-    return T.TextIndexData("unicode61", list(terms), np.asarray(off, np.int64), np.concatenate(docs), np.concatenate(poss), int(n_rows),
-                           {t: i for i, t in enumerate(terms)})
 
 
 # ---- 1: the limits of a query ---------------------------------------------------------------------------------------------
