@@ -1307,8 +1307,8 @@ int np_hip_pool_documents(int32_t device, const float* embeddings, const int64_t
  * not on the fallback list, a second add or an add after np_hip_text_build_sizes.  NP_ERR_SHAPE: a document longer than
  * 2^31 - 1 bytes, 2^31 documents or more, 2^31 instances or more in one call (known for unicode61 only after the counting
  * launch: refused then, before anything is emitted).  NP_ERR_OUT_OF_MEMORY: a workspace (workspace_bytes, or the device's
- * free memory) that does not hold the call.  It is a whole-corpus sort: building in document ranges and merging them is
- * out of scope. */
+ * free memory) that does not hold the call.  One call is a whole-corpus sort; a corpus that does not fit one call is built
+ * in document ranges that np_hip_text_build_merge (below) appends to one another. */
 #define NP_TOK_UNICODE61 0
 #define NP_TOK_TRIGRAM 1
 #define NP_TEXT_BUILD_MAX_TOKEN_BYTES 32768
@@ -1358,6 +1358,82 @@ int np_hip_text_build_sizes(np_text_build* build, int64_t* n_terms, int64_t* ter
 int np_hip_text_build_fetch(const np_text_build* build, uint8_t* term_bytes, int64_t* term_byte_offsets, int64_t* term_offsets,
                             int64_t* inst_doc, int32_t* inst_pos);
 void np_hip_text_build_free(np_text_build* build);
+
+/* ---- Merging keyword indexes: append, delete and replace rows (np_textmerge.hip; DESIGN.md section 4, "Keeping the keyword
+ * index current") ----
+ * The crate keeps its FTS5 table incremental: index() appends rows, delete() removes them, update_rows() replaces their text
+ * and rebuild() renumbers the survivors.  np_hip_text_build_merge is the one operation behind all four: from
+ *   the base index A   the arrays of np_text_index (host pointers) and its vocabulary: n_terms strings, bytes + offsets
+ *                      [n_terms + 1], in ascending term order (memcmp, the shorter string first)
+ *   remap [n_remap]    a verdict per old document id: -1 = removed, otherwise the id it has in the result.  The survivors'
+ *                      ids ascend strictly (renumbering keeps the order)
+ *   the batch B        the build of the new texts, as np_hip_text_build returns it, finalised by np_hip_text_build_sizes
+ *                      (so the fallback documents' instances are in it); NULL = no new text.  Its arrays are read where they
+ *                      lie in HBM; a build that np_hip_text_build_sizes merged on the host is uploaded
+ *   delta_ids [batch n_docs]   the id every batch document gets: ascending strictly, none of them a survivor's id
+ *   n_rows_out         FTS5's nRow of the result
+ * it returns the keyword index of the resulting table, equal array for array (terms, term_offsets, inst_doc, inst_pos,
+ * n_rows) to building that table from scratch with SQLite.  A term whose last instance went is not listed any more.
+ *   append (index)        remap[d] = d, delta_ids = n, n + 1, ...
+ *   delete                remap[d] = -1 for the deleted rows, d for the others (ids keep their holes); no batch
+ *   delete + rebuild      the survivors numbered 0, 1, ... in order; no batch
+ *   replace (update_rows) remap[d] = -1 for the replaced rows and the batch holds their new texts with delta_ids = those ids
+ * or any mix of them in one call.  The result is a finalised np_text_build: np_hip_text_build_sizes, _fetch and _free serve
+ * it, np_hip_text_build_fallback lists nothing and np_hip_text_build_add is refused.  No handle is involved.
+ *
+ * The host unites the two sorted vocabularies and computes bound[j], the smallest old id whose survivor id is >=
+ * delta_ids[j] (both linear).  On the device (each step a launch; no workgroup waits for another, no atomics, integers only,
+ * so the bytes are a function of the inputs alone):
+ *   keep    keep[i] = remap[doc_A[i]] >= 0, and S = its exclusive scan
+ *   count   per union term: kept instances of A's run (two reads of S) + the length of B's run; an exclusive scan places
+ *           the terms' runs, a scan of "any left" numbers the terms that stay; the flags go to the host, which compacts the strings
+ *   place   a kept A instance: its run's start + the kept instances of its run before it + the instances of B's run with a
+ *           lower new id (a binary search); a B instance: its run's start + its index in B's run + the kept instances of A's
+ *           run whose OLD id is below bound[its document] (a binary search over A's run, then S).  term_offsets are the
+ *           run starts of the terms that stay
+ *
+ * Refused before any launch, the message naming the argument.  NP_ERR_INVALID_ARGUMENT: base arrays that fail
+ * np_hip_index_set_text's checks (against n_remap documents: a base document >= n_remap is one of them), base or batch
+ * terms out of order, survivor ids that do not ascend strictly, delta_ids that do not ascend strictly or name a survivor's
+ * id, a batch that is not finalised or lives on another device, n_rows_out below the result's distinct documents.  (That the
+ * two sides were tokenised alike cannot be known here: it is the caller's check.)  NP_ERR_SHAPE: 2^31 instances or more in
+ * the base, the batch or both together.  NP_ERR_OUT_OF_MEMORY: a workspace that does not hold the call -- the need depends
+ * on the sizes alone and is report->workspace_bytes. */
+typedef struct np_text_merge_opts {
+  int64_t workspace_bytes;   /* device bytes the call may hold at once; 0 = what the device has free */
+  int64_t reserved[3];
+} np_text_merge_opts;
+
+typedef struct np_text_merge_report {
+  int64_t n_base_terms;
+  int64_t n_base_instances;
+  int64_t n_old_docs;            /* n_remap */
+  int64_t n_survivors;           /* old documents that stay */
+  int64_t n_delta_docs;
+  int64_t n_delta_terms;
+  int64_t n_delta_instances;
+  int64_t n_terms;               /* of the result */
+  int64_t n_instances;
+  int64_t n_rows;
+  int64_t n_terms_dropped;       /* terms of the union without an instance left */
+  int64_t n_instances_dropped;   /* instances of removed documents */
+  int32_t delta_uploaded;        /* 1: the batch's arrays came from the host (it held fallback documents, or was empty) */
+  int32_t reserved0;
+  double ms_check;               /* the checks, the vocabulary union and bound, on the host */
+  double ms_upload;              /* the base's arrays and the maps, host to device */
+  double ms_count;               /* keep, the scans, the terms' counts; the flags back */
+  double ms_terms;               /* the host's compaction of the strings */
+  double ms_place;               /* the two placing launches and term_offsets */
+  double ms_total;               /* wall time of the call */
+  int64_t workspace_bytes;       /* device bytes the call needs (planned from the sizes, an upper bound of what it held) */
+  int64_t reserved[3];
+} np_text_merge_report;
+
+int np_hip_text_build_merge(int32_t device, const np_text_index* base, const uint8_t* base_term_bytes,
+                            const int64_t* base_term_byte_offsets, const int64_t* remap, int64_t n_remap,
+                            const np_text_build* delta /* finalised; NULL = empty batch */, const int64_t* delta_ids /* [delta's n_docs] */,
+                            int64_t n_rows_out, const np_text_merge_opts* opts /* nullable */, np_text_build** out_build,
+                            np_text_merge_report* report /* nullable */);
 
 /* Stage-level debug access for parity tests: runs S1-S5 for ONE query and copies out the probed
  * cells (ascending), candidate doc ids (ascending, global), their approximate scores, and the

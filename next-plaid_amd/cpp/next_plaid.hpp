@@ -1283,4 +1283,134 @@ inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, To
   return r;
 }
 
+// ---- the keyword index kept current (np_hip_text_build_merge): append, delete and replace rows of a built index ----
+// What the crate's index / delete / update_rows (and rebuild) leave, without building the table again.  `replace` maps row
+// ids to their new text; the batch is the replacements in id order, then new_texts, which follow the last id.  renumber
+// numbers the surviving rows 0, 1, ... in order (delete + rebuild); otherwise every id stays.  The base is a dense table
+// (rows 0 .. base.n_rows - 1).  merge_report is the merge's report, report the batch's build.
+struct TextUpdate {
+  std::vector<std::string> new_texts;
+  std::vector<int64_t> delete_ids;
+  std::vector<std::pair<int64_t, std::string>> replace;
+  bool renumber = true;
+};
+
+struct UpdatedTextIndex : BuiltTextIndex {
+  np_text_merge_report merge_report{};
+};
+
+namespace detail {
+// remap, delta_ids, the batch's texts and the result's row count; throws on an id outside the table or named twice
+inline void text_update_plan(int64_t n_old, const TextUpdate& u, std::vector<int64_t>* remap, std::vector<int64_t>* delta_ids,
+                             std::vector<std::string>* texts, int64_t* n_rows_out) {
+  std::vector<int64_t> gone(u.delete_ids);
+  std::sort(gone.begin(), gone.end());
+  gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+  std::vector<std::pair<int64_t, std::string>> rep(u.replace);
+  std::sort(rep.begin(), rep.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+  auto inside = [&](int64_t d) {
+    if (d < 0 || d >= n_old)
+      throw Error(NP_ERR_INVALID_ARGUMENT,
+                  ("update_text_index: row " + std::to_string(d) + " is outside the table's " + std::to_string(n_old) + " row ids").c_str());
+  };
+  for (int64_t d : gone) inside(d);
+  for (size_t i = 0; i < rep.size(); ++i) {
+    inside(rep[i].first);
+    if (i > 0 && rep[i].first == rep[i - 1].first)
+      throw Error(NP_ERR_INVALID_ARGUMENT, ("update_text_index: row " + std::to_string(rep[i].first) + " is replaced twice").c_str());
+    if (std::binary_search(gone.begin(), gone.end(), rep[i].first))
+      throw Error(NP_ERR_INVALID_ARGUMENT, ("update_text_index: row " + std::to_string(rep[i].first) + " is in both delete and replace").c_str());
+  }
+  remap->assign((size_t)n_old, 0);
+  for (int64_t d = 0; d < n_old; ++d) (*remap)[(size_t)d] = d;
+  for (int64_t d : gone) (*remap)[(size_t)d] = -1;
+  int64_t top = n_old;
+  if (u.renumber) {
+    top = 0;
+    for (int64_t& v : *remap)
+      if (v >= 0) v = top++;
+  }
+  delta_ids->clear();
+  texts->clear();
+  for (const auto& r : rep) {
+    delta_ids->push_back((*remap)[(size_t)r.first]);
+    (*remap)[(size_t)r.first] = -1;
+    texts->push_back(r.second);
+  }
+  for (size_t i = 0; i < u.new_texts.size(); ++i) {
+    delta_ids->push_back(top + (int64_t)i);
+    texts->push_back(u.new_texts[i]);
+  }
+  *n_rows_out = n_old - (int64_t)gone.size() + (int64_t)u.new_texts.size();
+}
+
+template <class AddFallback>
+inline UpdatedTextIndex text_update_run(const BuiltTextIndex& base, const TextUpdate& u, Tokenizer tokenizer, int device,
+                                        int32_t max_token_bytes, AddFallback&& add_fallback) {
+  if (base.term_offsets.size() != base.terms.size() + 1)
+    throw Error(NP_ERR_INVALID_ARGUMENT, "update_text_index: base.term_offsets does not have one entry per term and one more");
+  std::vector<int64_t> remap, delta_ids;
+  std::vector<std::string> texts;
+  int64_t n_rows_out = 0;
+  text_update_plan(base.n_rows, u, &remap, &delta_ids, &texts, &n_rows_out);
+  std::vector<int64_t> tbo(base.terms.size() + 1, 0);
+  for (size_t i = 0; i < base.terms.size(); ++i) tbo[i + 1] = tbo[i] + (int64_t)base.terms[i].size();
+  std::vector<uint8_t> tb((size_t)tbo.back());
+  for (size_t i = 0; i < base.terms.size(); ++i) std::copy(base.terms[i].begin(), base.terms[i].end(), tb.begin() + tbo[i]);
+  np_text_index t{};
+  t.n_terms = (int64_t)base.terms.size();
+  t.term_offsets = base.term_offsets.data();
+  t.inst_doc = base.inst_doc.empty() ? nullptr : base.inst_doc.data();
+  t.inst_pos = base.inst_pos.empty() ? nullptr : base.inst_pos.data();
+  t.n_rows = base.n_rows;
+  UpdatedTextIndex r;
+  TextBuildHandle batch, merged;
+  if (!texts.empty()) {
+    text_build_start(batch, texts, text_build_opts(tokenizer, max_token_bytes), device, &r);
+    add_fallback(batch, r);
+    check(np_hip_text_build_sizes(batch.h, nullptr, nullptr, nullptr, nullptr));
+  }
+  np_text_merge_opts o{};
+  check(np_hip_text_build_merge(device, &t, tb.empty() ? nullptr : tb.data(), tbo.data(), remap.empty() ? nullptr : remap.data(),
+                                (int64_t)remap.size(), batch.h, delta_ids.empty() ? nullptr : delta_ids.data(), n_rows_out, &o,
+                                &merged.h, &r.merge_report));
+  text_build_finish(merged, &r);
+  return r;
+}
+
+template <class Tokenize>
+inline void text_build_add_fallback(TextBuildHandle& b, const BuiltTextIndex& r, Tokenize&& tokenize) {
+  if (r.fallback_docs.empty()) return;
+  const TextInstances inst = tokenize(r.fallback_docs);
+  std::vector<int64_t> tbo(inst.terms.size() + 1, 0);
+  for (size_t i = 0; i < inst.terms.size(); ++i) tbo[i + 1] = tbo[i] + (int64_t)inst.terms[i].size();
+  std::vector<uint8_t> tb((size_t)tbo.back());
+  for (size_t i = 0; i < inst.terms.size(); ++i) std::copy(inst.terms[i].begin(), inst.terms[i].end(), tb.begin() + tbo[i]);
+  if (inst.inst_term.size() != inst.inst_doc.size() || inst.inst_term.size() != inst.inst_pos.size())
+    throw Error(NP_ERR_INVALID_ARGUMENT, "update_text_index: the instance arrays differ in length");
+  check(np_hip_text_build_add(b.h, tb.empty() ? nullptr : tb.data(), tbo.data(), (int64_t)inst.terms.size(), inst.inst_term.data(),
+                              inst.inst_doc.data(), inst.inst_pos.data(), (int64_t)inst.inst_term.size()));
+}
+}  // namespace detail
+
+// The batch must be text the device reproduces: a fallback document in it is an error here (nothing is dropped silently);
+// the overload below takes the caller's instances for them.
+inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const TextUpdate& update, Tokenizer tokenizer = Tokenizer::Unicode61,
+                                          int device = 0, int32_t max_token_bytes = 0) {
+  return detail::text_update_run(base, update, tokenizer, device, max_token_bytes, [](detail::TextBuildHandle&, const BuiltTextIndex& r) {
+    if (!r.fallback_docs.empty())
+      throw Error(NP_ERR_INVALID_ARGUMENT, ("update_text_index: batch document " + std::to_string(r.fallback_docs[0]) +
+                                            " is not reproduced on the device and no tokenize was given").c_str());
+  });
+}
+
+// ... tokenize(fallback_docs) is called once when the batch has fallback documents; the ids index the batch (the
+// replacements in id order, then new_texts).
+template <class Tokenize>
+inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const TextUpdate& update, Tokenizer tokenizer, Tokenize&& tokenize,
+                                          int device = 0, int32_t max_token_bytes = 0) {
+  return detail::text_update_run(base, update, tokenizer, device, max_token_bytes,
+                                 [&](detail::TextBuildHandle& b, const BuiltTextIndex& r) { detail::text_build_add_fallback(b, r, tokenize); });
+}
+
 }  // namespace next_plaid

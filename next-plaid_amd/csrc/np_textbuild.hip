@@ -4,11 +4,9 @@
 // nothing a launch writes is read by another workgroup of that launch except a term-table slot (one u32 that goes from
 // empty to an instance index once, by atomicCAS, and only ever names bytes of the immutable text), and every position of
 // the result comes out of a scan, never out of an atomic counter.
-#include <chrono>
 #include <climits>
 #include <new>
-#include "np_internal.h"
-#include "np_textbuild_plan.h"
+#include "np_textbuild_dev.h"
 
 namespace np {
 namespace {
@@ -260,72 +258,6 @@ __global__ void tb_assign_unicode(uint32_t* key, uint32_t* val, int64_t n, const
   val[i] = (uint32_t)i;
 }
 
-// ---- exclusive scan of u32 counts: reduce per block, scan the block sums in one block, apply ----------------------------
-__device__ __forceinline__ uint64_t tb_block_excl_scan(uint64_t v, uint64_t* lds, uint64_t* total) {
-  const int tid = threadIdx.x;
-  lds[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const uint64_t t = tid >= d ? lds[tid - d] : 0;
-    __syncthreads();
-    lds[tid] += t;
-    __syncthreads();
-  }
-  const uint64_t incl = lds[tid];
-  *total = lds[255];
-  __syncthreads();
-  return incl - v;
-}
-
-__global__ __launch_bounds__(256) void tb_scan_reduce(const uint32_t* __restrict__ in, int64_t n, uint64_t* sums) {
-  __shared__ uint64_t lds[256];
-  const int64_t i0 = (int64_t)blockIdx.x * NP_TB_SCAN_CHUNK + threadIdx.x * 8;
-  uint64_t s = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    if (i0 + j < n) s += in[i0 + j];
-  uint64_t total;
-  (void)tb_block_excl_scan(s, lds, &total);
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void tb_scan_sums(uint64_t* sums, int64_t nb) {
-  __shared__ uint64_t lds[256];
-  uint64_t carry = 0;
-  for (int64_t c0 = 0; c0 < nb; c0 += 256) {
-    const int64_t i = c0 + threadIdx.x;
-    const uint64_t v = i < nb ? sums[i] : 0;
-    uint64_t total;
-    const uint64_t ex = tb_block_excl_scan(v, lds, &total);
-    if (i < nb) sums[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) sums[nb] = carry;
-}
-
-// out[i] = sum of in[0..i), out[n] = the total; out may be in (each block reads its items before it writes them)
-template <class T>
-__global__ __launch_bounds__(256) void tb_scan_apply(const uint32_t* in, int64_t n, const uint64_t* __restrict__ sums, int64_t nb,
-                                                      T* out) {
-  __shared__ uint64_t lds[256];
-  const int64_t i0 = (int64_t)blockIdx.x * NP_TB_SCAN_CHUNK + threadIdx.x * 8;
-  uint32_t v[8];
-  uint64_t s = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    v[j] = i0 + j < n ? in[i0 + j] : 0u;
-    s += v[j];
-  }
-  uint64_t total;
-  uint64_t run = tb_block_excl_scan(s, lds, &total) + sums[blockIdx.x];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if (i0 + j < n) out[i0 + j] = (T)run;
-    run += v[j];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = (T)sums[nb];
-}
-
 // ---- the radix pass: one wave per block of NP_TB_SORT_CHUNK keys ----------------------------------------------------------
 __global__ __launch_bounds__(64) void tb_radix_hist(const uint32_t* __restrict__ keys, int64_t n, int shift, uint32_t* hist,
                                                      int64_t nblk) {
@@ -398,43 +330,13 @@ __global__ void tb_gather(const uint32_t* __restrict__ keys, const uint32_t* __r
   if (i == n - 1) toff[n_terms] = n;
 }
 
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
-inline unsigned grid_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 }  // namespace
 }  // namespace np
 
 using namespace np;
 
-struct np_text_build {
-  int device = 0;
-  int32_t tokenizer = 0;
-  int64_t n_docs = 0, n_inst = 0, n_terms = 0;
-  std::vector<int64_t> fallback;
-  // the device's result: the strings on the host, the arrays in HBM until they are fetched or merged
-  std::vector<uint8_t> term_bytes;
-  std::vector<int64_t> term_byte_offsets;
-  DevPtr<int64_t> d_toff, d_inst_doc;
-  DevPtr<int32_t> d_inst_pos;
-  // the fallback documents' instances (np_hip_text_build_add)
-  bool added = false, finalised = false, merged = false;
-  std::vector<uint8_t> b_bytes;
-  std::vector<int64_t> b_tbo, b_doc;
-  std::vector<int32_t> b_term, b_pos;
-  TextArrays out;   // the merged result
-};
-
 namespace np {
 namespace {
-
-struct TbStream {
-  hipStream_t st = nullptr;
-  ~TbStream() {
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
 
 // the device arrays of one call, and the bytes they hold against the workspace
 struct TbWork {
@@ -444,7 +346,7 @@ struct TbWork {
     const int64_t bytes = textbuild_up256(std::max<int64_t>(n, 1) * (int64_t)sizeof(T));
     if (limit > 0 && held + bytes > limit) {
       set_error("np_hip_text_build: the workspace of %lld bytes does not hold the call: %lld held, %lld more for %s (a "
-                "whole-corpus sort; building in document ranges is out of scope)",
+                "whole-corpus sort: build in document ranges and merge them, np_hip_text_build_merge)",
                 (long long)limit, (long long)held, (long long)bytes, what);
       return NP_ERR_OUT_OF_MEMORY;
     }
@@ -453,19 +355,6 @@ struct TbWork {
     return NP_OK;
   }
 };
-
-template <class T>
-int tb_scan(hipStream_t st, const uint32_t* in, int64_t n, T* out, uint64_t* sums) {
-  const int64_t nb = (n + NP_TB_SCAN_CHUNK - 1) / NP_TB_SCAN_CHUNK;
-  if (nb > 0) hipLaunchKernelGGL(tb_scan_reduce, dim3((unsigned)nb), dim3(256), 0, st, in, n, sums);
-  hipLaunchKernelGGL(tb_scan_sums, dim3(1), dim3(256), 0, st, sums, nb);
-  if (nb > 0)
-    hipLaunchKernelGGL(tb_scan_apply<T>, dim3((unsigned)nb), dim3(256), 0, st, in, n, (const uint64_t*)sums, nb, out);
-  else
-    NP_HIP(hipMemsetAsync(out, 0, sizeof(T), st));
-  NP_HIP(hipGetLastError());
-  return NP_OK;
-}
 
 int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, int64_t n_docs, const TextBuildPlan& plan,
                     np_text_build* B, np_text_build_report* rep) {
@@ -488,7 +377,7 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
   }
   if (textbuild_bytes_docs(N, n_docs) > W.limit) {
     set_error("np_hip_text_build: the workspace of %lld bytes does not hold the text and the per-document arrays (%lld bytes; a "
-              "whole-corpus sort: building in document ranges is out of scope)",
+              "whole-corpus sort: build in document ranges and merge them, np_hip_text_build_merge)",
               (long long)W.limit, (long long)textbuild_bytes_docs(N, n_docs));
     return NP_ERR_OUT_OF_MEMORY;
   }
@@ -558,7 +447,7 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
     const int64_t need = textbuild_bytes_total(N, n_docs, n_inst, plan.tokenizer, bits);
     if (need > W.limit) {
       set_error("np_hip_text_build: the workspace of %lld bytes does not hold the call: %lld instances need %lld bytes (a "
-                "whole-corpus sort: building in document ranges is out of scope)",
+                "whole-corpus sort: build in document ranges and merge them, np_hip_text_build_merge)",
                 (long long)W.limit, (long long)n_inst, (long long)need);
       return NP_ERR_OUT_OF_MEMORY;
     }

@@ -223,6 +223,23 @@ class np_text_build_report(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class np_text_merge_opts(C.Structure):
+    _fields_ = [("workspace_bytes", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+class np_text_merge_report(C.Structure):
+    _fields_ = [("n_base_terms", C.c_int64), ("n_base_instances", C.c_int64), ("n_old_docs", C.c_int64),
+                ("n_survivors", C.c_int64), ("n_delta_docs", C.c_int64), ("n_delta_terms", C.c_int64),
+                ("n_delta_instances", C.c_int64), ("n_terms", C.c_int64), ("n_instances", C.c_int64), ("n_rows", C.c_int64),
+                ("n_terms_dropped", C.c_int64), ("n_instances_dropped", C.c_int64), ("delta_uploaded", C.c_int32),
+                ("reserved0", C.c_int32), ("ms_check", C.c_double), ("ms_upload", C.c_double), ("ms_count", C.c_double),
+                ("ms_terms", C.c_double), ("ms_place", C.c_double), ("ms_total", C.c_double), ("workspace_bytes", C.c_int64),
+                ("reserved", C.c_int64 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 NP_TOK_UNICODE61, NP_TOK_TRIGRAM = 0, 1
 
 
@@ -272,7 +289,7 @@ EXPORTS = [
     "np_hip_index_set_groups", "np_hip_index_group_count", "np_hip_collapse", "np_hip_collapse_device",
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
-    "np_hip_text_build_fetch", "np_hip_text_build_free",
+    "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
 ]
 
 _lib = None
@@ -453,6 +470,8 @@ def lib():
     L.np_hip_text_build_fetch.argtypes = [vp, vp, vp, vp, vp, vp]
     L.np_hip_text_build_free.argtypes = [vp]
     L.np_hip_text_build_free.restype = None
+    L.np_hip_text_build_merge.argtypes = [i32, C.POINTER(np_text_index), vp, vp, vp, i64, vp, vp, i64,
+                                          C.POINTER(np_text_merge_opts), C.POINTER(vp), C.POINTER(np_text_merge_report)]
     _lib = L
     return L
 
@@ -948,21 +967,15 @@ def _docs(documents):
     return np.ascontiguousarray(flat, np.float32), lens, dim
 
 
-def text_build(doc_bytes, offsets, tokenizer: int, tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0,
-               workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
-    """np_hip_text_build and the calls that follow it: the documents' UTF-8 bytes concatenated (u8 array) and offsets i64
-    [n_docs + 1] -> a dict with term_bytes u8, term_byte_offsets / term_offsets i64 [n_terms + 1], inst_doc i64, inst_pos
-    i32, n_rows, fallback_docs i64 (ascending) and the stage report.  tokenize_fallback(ids) is called once when the device
-    hands documents back, and returns their instances as (term_bytes u8, term_byte_offsets i64, inst_term i32, inst_doc i64,
-    inst_pos i32) sorted by (term, doc, pos) with the terms in memcmp order; without it a non-empty fallback list is an
-    error, never a silently smaller index."""
+def _text_build_open(L, doc_bytes, offsets, tokenizer, tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits,
+                     tile_bytes):
+    """np_hip_text_build and np_hip_text_build_add: (the build, the fallback ids, the report).  The caller frees the build."""
     raw = np.ascontiguousarray(doc_bytes, np.uint8).reshape(-1)
     off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
     if off.size < 1:
         raise ValueError("offsets needs n_docs + 1 entries")
     o = np_text_build_opts(int(tokenizer), int(max_token_bytes), int(workspace_bytes), int(hash_bits), int(tile_bytes))
     rep, h = np_text_build_report(), C.c_void_p()
-    L = lib()
     _check(L.np_hip_text_build(int(device), _ptr(raw) if raw.size else None, _ptr(off), off.size - 1, C.byref(o), C.byref(h),
                                C.byref(rep)))
     try:
@@ -981,20 +994,94 @@ def text_build(doc_bytes, offsets, tokenizer: int, tokenize_fallback=None, devic
             ipos = np.ascontiguousarray(ipos, np.int32)
             _check(L.np_hip_text_build_add(h, _ptr(tb) if tb.size else None, _ptr(tbo), tbo.size - 1, _ptr(it), _ptr(idoc),
                                            _ptr(ipos), it.size))
-        nt, nb, ni, nr = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-        _check(L.np_hip_text_build_sizes(h, C.byref(nt), C.byref(nb), C.byref(ni), C.byref(nr)))
-        out = dict(term_bytes=np.zeros(max(nb.value, 1), np.uint8), term_byte_offsets=np.zeros(nt.value + 1, np.int64),
-                   term_offsets=np.zeros(nt.value + 1, np.int64), inst_doc=np.zeros(max(ni.value, 1), np.int64),
-                   inst_pos=np.zeros(max(ni.value, 1), np.int32))
-        _check(L.np_hip_text_build_fetch(h, *(_ptr(out[k]) for k in ("term_bytes", "term_byte_offsets", "term_offsets",
-                                                                      "inst_doc", "inst_pos"))))
-        out["term_bytes"] = out["term_bytes"][: nb.value]
-        out["inst_doc"] = out["inst_doc"][: ni.value]
-        out["inst_pos"] = out["inst_pos"][: ni.value]
-        out.update(n_rows=int(nr.value), fallback_docs=fb, report=rep.as_dict())
+    except BaseException:
+        L.np_hip_text_build_free(h)
+        raise
+    return h, fb, rep
+
+
+def _text_build_read(L, h):
+    """np_hip_text_build_sizes and np_hip_text_build_fetch: the arrays of a build (sizes finalises it)."""
+    nt, nb, ni, nr = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _check(L.np_hip_text_build_sizes(h, C.byref(nt), C.byref(nb), C.byref(ni), C.byref(nr)))
+    out = dict(term_bytes=np.zeros(max(nb.value, 1), np.uint8), term_byte_offsets=np.zeros(nt.value + 1, np.int64),
+               term_offsets=np.zeros(nt.value + 1, np.int64), inst_doc=np.zeros(max(ni.value, 1), np.int64),
+               inst_pos=np.zeros(max(ni.value, 1), np.int32))
+    _check(L.np_hip_text_build_fetch(h, *(_ptr(out[k]) for k in ("term_bytes", "term_byte_offsets", "term_offsets",
+                                                                  "inst_doc", "inst_pos"))))
+    out["term_bytes"] = out["term_bytes"][: nb.value]
+    out["inst_doc"] = out["inst_doc"][: ni.value]
+    out["inst_pos"] = out["inst_pos"][: ni.value]
+    out["n_rows"] = int(nr.value)
+    return out
+
+
+def text_build(doc_bytes, offsets, tokenizer: int, tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0,
+               workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+    """np_hip_text_build and the calls that follow it: the documents' UTF-8 bytes concatenated (u8 array) and offsets i64
+    [n_docs + 1] -> a dict with term_bytes u8, term_byte_offsets / term_offsets i64 [n_terms + 1], inst_doc i64, inst_pos
+    i32, n_rows, fallback_docs i64 (ascending) and the stage report.  tokenize_fallback(ids) is called once when the device
+    hands documents back, and returns their instances as (term_bytes u8, term_byte_offsets i64, inst_term i32, inst_doc i64,
+    inst_pos i32) sorted by (term, doc, pos) with the terms in memcmp order; without it a non-empty fallback list is an
+    error, never a silently smaller index."""
+    L = lib()
+    h, fb, rep = _text_build_open(L, doc_bytes, offsets, tokenizer, tokenize_fallback, device, max_token_bytes, workspace_bytes,
+                                  hash_bits, tile_bytes)
+    try:
+        out = _text_build_read(L, h)
+        out.update(fallback_docs=fb, report=rep.as_dict())
         return out
     finally:
         L.np_hip_text_build_free(h)
+
+
+def text_merge(base_terms, base_term_offsets, base_inst_doc, base_inst_pos, base_n_rows, remap, delta_ids, n_rows_out,
+               doc_bytes=None, offsets=None, tokenizer: int = 0, tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0,
+               workspace_bytes: int = 0, merge_workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+    """np_hip_text_build_merge, the one caller of the entry: the keyword index of the table that results from a base index
+    (its terms as byte strings in term order, and the np_text_index arrays), a verdict per old document (remap i64: -1 =
+    removed, otherwise the new id) and a batch of new texts (doc_bytes / offsets as text_build takes them; offsets None = no
+    batch) whose documents get delta_ids.  The batch is built on the device first (np_hip_text_build, the fallback documents
+    added as in text_build) and merged where it lies.  Returns text_build's dict; `report` is the merge's, `build_report` the
+    batch's (None without a batch), fallback_docs index the batch."""
+    L = lib()
+    enc = [bytes(t) for t in base_terms]
+    a_tbo = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        a_tbo[1:] = np.cumsum([len(t) for t in enc])
+    a_tb = np.frombuffer(b"".join(enc), np.uint8)
+    a_off = np.ascontiguousarray(base_term_offsets, np.int64).reshape(-1)
+    a_doc = np.ascontiguousarray(base_inst_doc, np.int64).reshape(-1)
+    a_pos = np.ascontiguousarray(base_inst_pos, np.int32).reshape(-1)
+    if a_off.size != len(enc) + 1:
+        raise ValueError(f"base_term_offsets has {a_off.size} entries for {len(enc)} terms")
+    remap = np.ascontiguousarray(remap, np.int64).reshape(-1)
+    ids = np.ascontiguousarray(delta_ids, np.int64).reshape(-1)
+    n_delta = 0 if offsets is None else int(np.asarray(offsets).size) - 1
+    if ids.size != n_delta:
+        raise ValueError(f"delta_ids has {ids.size} entries for a batch of {n_delta} documents")
+    t = np_text_index(len(enc), a_off.ctypes.data, a_doc.ctypes.data if a_doc.size else None,
+                      a_pos.ctypes.data if a_pos.size else None, int(base_n_rows))
+    d, fb, brep = C.c_void_p(), np.zeros(0, np.int64), None
+    if offsets is not None:
+        d, fb, brep = _text_build_open(L, doc_bytes if doc_bytes is not None else np.zeros(0, np.uint8), offsets, tokenizer,
+                                       tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits, tile_bytes)
+    h = C.c_void_p()
+    try:
+        if d:
+            _check(L.np_hip_text_build_sizes(d, None, None, None, None))
+        o, rep = np_text_merge_opts(int(merge_workspace_bytes)), np_text_merge_report()
+        _check(L.np_hip_text_build_merge(int(device), C.byref(t), _ptr(a_tb) if a_tb.size else None, _ptr(a_tbo),
+                                         _ptr(remap) if remap.size else None, remap.size, d, _ptr(ids) if ids.size else None,
+                                         int(n_rows_out), C.byref(o), C.byref(h), C.byref(rep)))
+        out = _text_build_read(L, h)
+        out.update(fallback_docs=fb, report=rep.as_dict(), build_report=brep.as_dict() if brep is not None else None)
+        return out
+    finally:
+        if h:
+            L.np_hip_text_build_free(h)
+        if d:
+            L.np_hip_text_build_free(d)
 
 
 _POOL_CUTS = {"reference": 0, "distance": 1}
@@ -1576,6 +1663,19 @@ class MmapIndex:
         from . import text as T
         data = T.TextIndexData.from_texts_device(texts, tokenizer, device=int(self._info.device),
                                                  max_token_bytes=max_token_bytes)
+        self.set_text(data)
+        return data
+
+    def update_text(self, new_texts=(), delete=(), replace=None, renumber: bool = True, base=None):
+        """The keyword index kept current (text.TextIndexData.updated, on this handle's device): `new_texts` appended,
+        the rows `delete` removed, the rows of `replace` ({id: text}) given new text; renumber=True numbers the survivors
+        densely, as the document ids are after delete() / update().  `base` defaults to self.text; update() and reload()
+        drop it, so pass the TextIndexData kept from before them.  Calls set_text with the result and returns it
+        (set_text_shard takes it unchanged).  A refused call leaves the previous keyword index in place."""
+        base = self.text if base is None else base
+        if base is None:
+            raise ValueError("update_text: the handle has no keyword index and no base was given")
+        data = base.updated(new_texts, delete=delete, replace=replace, renumber=renumber, device=int(self._info.device))
         self.set_text(data)
         return data
 

@@ -231,28 +231,86 @@ class TextIndexData:
         raw = np.frombuffer(b"".join(raws), np.uint8)
 
         def tokenize_fallback(ids):
-            conn = sqlite3.connect(":memory:")
-            try:
-                create_fts_tables(conn, tokenizer, content_synced=False)
-                insert_fts_rows(conn, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer, content_synced=False)
-                d = cls._read(conn, FTS_TABLE, tokenizer)
-            finally:
-                conn.close()
-            enc = [t.encode("utf-8") for t in d.terms]
-            tbo = np.zeros(len(enc) + 1, np.int64)
-            if enc:
-                tbo[1:] = np.cumsum([len(t) for t in enc])
-            inst_term = np.repeat(np.arange(len(enc), dtype=np.int32), np.diff(d.term_offsets))
-            return np.frombuffer(b"".join(enc), np.uint8), tbo, inst_term, d.inst_doc, d.inst_pos
+            return _tokenize_rows(cls, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer)
 
         code = api.NP_TOK_TRIGRAM if TOKENIZERS[tokenizer] == "trigram" else api.NP_TOK_UNICODE61
         r = api.text_build(raw, off, code, tokenize_fallback, device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
+        return cls._of_build(tokenizer, r)
+
+    @classmethod
+    def _of_build(cls, tokenizer: str, r: dict) -> "TextIndexData":
         tb, tbo = r["term_bytes"].tobytes(), r["term_byte_offsets"]
         terms = [tb[tbo[i]: tbo[i + 1]].decode("utf-8") for i in range(tbo.size - 1)]
         data = cls(tokenizer, terms, r["term_offsets"], r["inst_doc"], r["inst_pos"], r["n_rows"],
                    {t: i for i, t in enumerate(terms)})
         data.build_report = r["report"]
         data.fallback_docs = [int(i) for i in r["fallback_docs"]]
+        return data
+
+    def updated(self, new_texts=(), *, delete=(), replace=None, renumber: bool = True, n_rows: int | None = None,
+                device: int = 0, max_token_bytes: int | None = None, **knobs) -> "TextIndexData":
+        """The index of the table after the crate's index / delete / update_rows (and rebuild), without building it again:
+        a new TextIndexData, equal array for array to from_texts of the resulting rows.  `delete` lists row ids that go,
+        `replace` maps row ids to their new text ({id: text} or (id, text) pairs), `new_texts` are appended behind the last
+        id.  The batch -- the replacements in id order, then new_texts -- is built on the device as from_texts_device does
+        (fallback documents through SQLite) and merged into this index there (np_hip_text_build_merge).
+        renumber=True numbers the surviving rows 0, 1, ... in order, as `delete` + `rebuild` leave them (and as the document
+        ids of the vector index are after a delete); renumber=False keeps every id, holes included.
+        The table must be dense -- rows 0 .. self.n_rows - 1, which is what from_texts and a renumbered update leave --
+        unless n_rows names the size of its id space (the ids then in use are the caller's knowledge: every id in `delete`
+        and `replace` must be a row, and renumber=True is refused).  build_report is the merge's report (under "batch": the
+        report of the batch's build, None without a batch), fallback_docs index the batch.  `knobs`: from_texts_device's, and merge_workspace_bytes."""
+        from . import api
+        tokenizer = self.tokenizer
+        n_old = int(self.n_rows) if n_rows is None else int(n_rows)
+        if n_old < int(self.n_rows):
+            raise ValueError(f"updated: n_rows {n_old} is below the table's {int(self.n_rows)} rows")
+        if n_rows is not None and renumber and n_old != int(self.n_rows):
+            raise ValueError("updated: renumber=True needs a dense table (rows 0 .. n_rows - 1); pass renumber=False")
+        if self.inst_doc.size and int(self.inst_doc.max()) >= n_old:
+            raise ValueError(f"updated: the index names document {int(self.inst_doc.max())} but the table has {n_old} row ids; "
+                             f"a table with holes needs n_rows")
+        gone = sorted(set(int(d) for d in delete))
+        rep = sorted((int(k), v) for k, v in (replace.items() if isinstance(replace, dict) else (replace or ())))
+        rep_ids = [k for k, _ in rep]
+        if len(set(rep_ids)) != len(rep_ids):
+            raise ValueError("updated: an id is replaced twice")
+        for d in gone + rep_ids:
+            if d < 0 or d >= n_old:
+                raise ValueError(f"updated: row {d} is outside the table's {n_old} row ids")
+        both = set(gone) & set(rep_ids)
+        if both:
+            raise ValueError(f"updated: row {min(both)} is in both delete and replace")
+        new_texts = list(new_texts)
+        texts = [t for _, t in rep] + new_texts
+        # the survivors' new ids; a replaced row keeps its place in the order but leaves the base
+        remap = np.arange(n_old, dtype=np.int64)
+        remap[gone] = -1
+        if renumber:
+            alive = remap >= 0
+            remap[alive] = np.arange(int(alive.sum()), dtype=np.int64)
+            top = int(alive.sum())
+        else:
+            top = n_old
+        delta_ids = np.concatenate([remap[rep_ids], top + np.arange(len(new_texts), dtype=np.int64)]).astype(np.int64)
+        remap[rep_ids] = -1
+        n_rows_out = int(self.n_rows) - len(gone) + len(new_texts)
+        raws = [prepare_document_text(t, tokenizer).encode("utf-8") for t in texts]
+        off = np.zeros(len(raws) + 1, np.int64)
+        if raws:
+            off[1:] = np.cumsum([len(r) for r in raws])
+        raw = np.frombuffer(b"".join(raws), np.uint8)
+        cls = type(self)
+
+        def tokenize_fallback(ids):
+            return _tokenize_rows(cls, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer)
+
+        code = api.NP_TOK_TRIGRAM if TOKENIZERS[tokenizer] == "trigram" else api.NP_TOK_UNICODE61
+        r = api.text_merge([t.encode("utf-8") for t in self.terms], self.term_offsets, self.inst_doc, self.inst_pos, int(self.n_rows),
+                           remap, delta_ids, n_rows_out, raw if texts else None, off if texts else None, code, tokenize_fallback,
+                           device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
+        data = cls._of_build(tokenizer, r)
+        data.build_report = dict(r["report"], batch=r["build_report"])     # the merge's report; the batch's build inside it
         return data
 
     # -- tokenising query text with the index's tokenizer -------------------------------------------------
@@ -275,6 +333,24 @@ class TextIndexData:
 
     def term_ids(self, phrase: str) -> list[int]:
         return [self.vocab.get(t, -1) for t in self.tokens_of(phrase)]
+
+
+def _tokenize_rows(cls, texts, ids, tokenizer: str):
+    """The instances SQLite makes of `texts` at rowids `ids`, as np_hip_text_build_add takes the fallback documents':
+    (term_bytes u8, term_byte_offsets i64, inst_term i32, inst_doc i64, inst_pos i32), through a scratch FTS5 table."""
+    conn = sqlite3.connect(":memory:")
+    try:
+        create_fts_tables(conn, tokenizer, content_synced=False)
+        insert_fts_rows(conn, texts, ids, tokenizer, content_synced=False)
+        d = cls._read(conn, FTS_TABLE, tokenizer)
+    finally:
+        conn.close()
+    enc = [t.encode("utf-8") for t in d.terms]
+    tbo = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        tbo[1:] = np.cumsum([len(t) for t in enc])
+    inst_term = np.repeat(np.arange(len(enc), dtype=np.int32), np.diff(d.term_offsets))
+    return np.frombuffer(b"".join(enc), np.uint8), tbo, inst_term, d.inst_doc, d.inst_pos
 
 
 def create_fts_tables(conn, tokenizer: str, content_synced: bool = True):
