@@ -15,17 +15,9 @@ from next_plaid_amd import api
 from next_plaid_amd.text import TextIndexData, compile_text_query
 
 import textbuild_restate as R
+from textbuild_limit_shapes import assert_same as _same
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(got, want):
-    assert got.terms == want.terms, ([t for t in got.terms if t not in want.vocab][:5], [t for t in want.terms if t not in got.vocab][:5])
-    assert np.array_equal(got.term_offsets, want.term_offsets)
-    assert np.array_equal(got.inst_doc, want.inst_doc)
-    assert np.array_equal(got.inst_pos, want.inst_pos)
-    assert got.n_rows == want.n_rows and got.vocab == want.vocab
-    assert got.term_offsets.dtype == np.int64 and got.inst_doc.dtype == np.int64 and got.inst_pos.dtype == np.int32
 
 
 def _reproducible(text, tokenizer):

@@ -3,7 +3,6 @@ SQLite itself: every case compares base.updated(...) with the FTS5 table of the 
 of a case comes from SQLite (from_texts) unless the case is about a base that the device built."""
 import ctypes as C
 import os
-import sqlite3
 import subprocess
 
 import numpy as np
@@ -12,47 +11,15 @@ import pytest
 from helpers import ROOT, synth
 
 import next_plaid_amd as npa
-from next_plaid_amd import api, text as T
+from next_plaid_amd import api
 from next_plaid_amd.text import TextIndexData
 
 import textbuild_restate as R
+from textbuild_limit_shapes import assert_same as _same, rows_after, sqlite_rows
 
 pytestmark = pytest.mark.gpu
 
 CHUNK = 2048   # NP_TB_SCAN_CHUNK: instances per block of a scan launch
-
-
-def _same(got, want):
-    assert got.terms == want.terms, ([t for t in got.terms if t not in want.vocab][:5], [t for t in want.terms if t not in got.vocab][:5])
-    assert np.array_equal(got.term_offsets, want.term_offsets)
-    assert np.array_equal(got.inst_doc, want.inst_doc)
-    assert np.array_equal(got.inst_pos, want.inst_pos)
-    assert got.n_rows == want.n_rows and got.vocab == want.vocab
-    assert got.term_offsets.dtype == np.int64 and got.inst_doc.dtype == np.int64 and got.inst_pos.dtype == np.int32
-
-
-def rows_after(texts, new_texts=(), delete=(), replace=None, renumber=True):
-    """{row id: text} of the table after the update, stated independently of the binding."""
-    rows = {i: t for i, t in enumerate(texts) if i not in set(delete)}
-    rows.update(replace or {})
-    if renumber:
-        rows = {n: rows[d] for n, d in enumerate(sorted(rows))}
-        top = len(rows)
-    else:
-        top = len(texts)
-    rows.update({top + i: t for i, t in enumerate(new_texts)})
-    return rows
-
-
-def sqlite_rows(rows, tokenizer="unicode61"):
-    conn = sqlite3.connect(":memory:")
-    try:
-        T.create_fts_tables(conn, tokenizer, content_synced=False)
-        ids = sorted(rows)
-        T.insert_fts_rows(conn, [rows[i] for i in ids], ids, tokenizer, content_synced=False)
-        return TextIndexData._read(conn, T.FTS_TABLE, tokenizer)
-    finally:
-        conn.close()
 
 
 def check(texts, new_texts=(), delete=(), replace=None, renumber=True, tokenizer="unicode61", base=None, fallback=(), **kw):
