@@ -2,18 +2,24 @@
 // keyword search with SQLite's bits (np_hip_text_search), the fusion of a semantic and a keyword list (np_hip_fuse) and the
 // whole hybrid request (np_hip_search_hybrid).
 //
-//   text_hit_kernel    nHit of every phrase of several tokens: the documents of the WHOLE table that hold it.  One lane per
-//                      posting of the phrase's first token; an integer atomic adds the block's count (order cannot show)
+//   text_hit_kernel<PX>  nHit of every phrase of several tokens: the documents of the WHOLE table that hold it.  One lane per
+//                      posting of the phrase's first token; text_block_count adds the block's count with one integer atomic
+//                      (order cannot show).  <false>: flat queries; <true>: tree queries, whose last token may be a prefix
+//   text_prefix_kernel a tree query's single-token prefix phrases: per-document frequencies over the term range, and nHit
 //   text_score_kernel  a workgroup takes one (query, slice of NP_TEXT_SLICE_DOCS consecutive documents).  One f64 accumulator
 //                      and one match count per document of the slice in LDS; the phrases are walked in order with a barrier
 //                      between them, each lane takes one posting of the phrase's first token inside the slice (a document
 //                      occurs once per posting list: lanes never collide, and phrase order is the summation order), reads the
 //                      stored frequency or intersects positions, and adds the bm25 term.  The slice's matching, eligible
 //                      documents are then sorted by (score, id) and the best `keep` leave as the slice's list
+//   text_expr_kernel   the same for a tree query (np_text_expr): phrase masks, the node list per document, the live phrases' terms
 //   text_merge_kernel  per query: the lists of a chunk's slices and the result of the chunks before it, merged through a
 //                      2048-entry window in LDS by the same total order
 //   fuse_kernel        per query: the two lists in LDS, the fused scores in f32 in the reference's order, one sort
 //   text_rank_merge_kernel  per query: the sorted lists of G document shards into the global top-k by binary searches
+// What must stay SQLite's bit for bit is written once and shared: text_bm25_term (the score's expression), text_probe and
+// text_phrase_walk (a phrase's occurrences), and the two slice kernels' common ends -- text_slice, text_slice_range, text_in_subset,
+// text_slice_emit.  On the host one TextProg lays out a flat or a tree batch and one text_run runs either.
 // Over document shards (np_hip_index_set_text_shard, np_hip_text_search_sharded, np_hip_search_hybrid_sharded; np_dist_plan.h
 // has the records): a shard keeps its slice of the table and the table's global figures, the shards' phrase hit counts are summed
 // on the host before the idf is computed, and the shards' lists cross the ranks as f64 keys and global ids.
@@ -50,56 +56,128 @@ __device__ __forceinline__ int64_t text_lower_bound(const int32_t* __restrict__ 
   return lo;
 }
 
-// occurrences of the phrase terms[0 .. nt) in the document of posting j0 (a posting of terms[0]): positions p of terms[0]
-// with terms[k] at p + k for every k
-__device__ __forceinline__ int text_phrase_freq(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int64_t j0, int doc) {
+// The bm25 term of a phrase that occurs freq times in a document of doc_len tokens: SQLite's expression, operation for
+// operation.  The one place where it is written: its order is the contract (the callers add it as acc = acc + term).
+__device__ __forceinline__ double text_bm25_term(double idf, double freq, double doc_len, double avgdl) {
+  const double k1 = 1.2, b = 0.75;
+  const double a = freq, D = doc_len;
+  return idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / avgdl)));
+}
+
+// does `term` occur in `doc` at position `pos`?  *in_doc: the document holds the term at all
+__device__ __forceinline__ bool text_probe(const TextIxP& t, int term, int doc, int64_t pos, bool* in_doc) {
+  const int64_t e = t.post_off[term + 1];
+  const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
+  *in_doc = jk < e && t.post_doc[jk] == doc;
+  if (!*in_doc) return false;
+  const int64_t pe = t.post_first[jk] + t.post_tf[jk];
+  const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, pos);
+  return at < pe && (int64_t)t.pos[at] == pos;
+}
+
+// occurrences of a phrase of several tokens in the document of posting j0 (a posting of terms[0]): positions p of terms[0] with
+// terms[k] at p + k for every k.  PX: the last token stands for the terms [terms[nt - 1], hi) -- a position holds one term, so
+// at most one term of the range continues an occurrence.
+template <bool PX>
+__device__ __forceinline__ int text_phrase_walk(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int hi, int64_t j0, int doc) {
   const int tf0 = t.post_tf[j0];
-  if (nt == 1) return tf0;
   const int64_t f0 = t.post_first[j0];
+  const int exact = PX ? nt - 1 : nt;   // the tokens [1, exact) are single terms
   int freq = 0;
   for (int x = 0; x < tf0; ++x) {
     const int64_t p = t.pos[f0 + x];
-    bool ok = true;
-    for (int k = 1; k < nt && ok; ++k) {
-      const int term = terms[k];
-      const int64_t e = t.post_off[term + 1];
-      const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
-      if (jk >= e || t.post_doc[jk] != doc) return 0;   // the document lacks a token of the phrase
-      const int64_t pe = t.post_first[jk] + t.post_tf[jk];
-      const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, p + k);
-      ok = at < pe && (int64_t)t.pos[at] == p + k;
+    bool ok = true, in_doc;
+    for (int k = 1; k < exact && ok; ++k) {
+      ok = text_probe(t, terms[k], doc, p + k, &in_doc);
+      if (!in_doc) return 0;   // the document lacks a token of the phrase
+    }
+    if (PX && ok) {
+      ok = false;
+      for (int term = terms[nt - 1]; term < hi && !ok; ++term) ok = text_probe(t, term, doc, p + nt - 1, &in_doc);
     }
     freq += ok ? 1 : 0;
   }
   return freq;
 }
 
-struct TextHitP {
-  TextIxP t;
-  const int32_t* phr_tok;
-  const int32_t* terms;
-  const int32_t* item_phr;         // [items] phrases of several known tokens
-  unsigned long long* nhit;        // [items]
-};
+// occurrences of the phrase terms[0 .. nt) in the document of posting j0: the stored frequency of a single token, else the walk
+__device__ __forceinline__ int text_phrase_freq(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int64_t j0, int doc) {
+  return nt == 1 ? t.post_tf[j0] : text_phrase_walk<false>(t, terms, nt, 0, j0, doc);
+}
+// ... of a tree query's phrase: hi = 0 is the exact phrase (which takes the exact walk), else the end of the last token's range
+__device__ __forceinline__ int text_phrase_freq_px(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int hi, int64_t j0, int doc) {
+  return hi == 0 || nt == 1 ? text_phrase_freq(t, terms, nt, j0, doc) : text_phrase_walk<true>(t, terms, nt, hi, j0, doc);
+}
 
-__global__ void __launch_bounds__(TEXT_TPB) text_hit_kernel(TextHitP p) {
+// The block's sum of c, added to *counter: a reduction per wave, the four waves' parts through LDS, one integer atomic (order
+// cannot show).  Every thread of the block calls it, once.
+__device__ __forceinline__ void text_block_count(uint32_t c, unsigned long long* counter) {
   __shared__ uint32_t part[TEXT_TPB / 64];
-  const int item = blockIdx.y, tid = threadIdx.x;
-  const int phr = p.item_phr[item];
-  const int tb = p.phr_tok[phr], nt = p.phr_tok[phr + 1] - tb;
-  const int32_t* terms = p.terms + tb;
-  const int64_t lo = p.t.post_off[terms[0]], hi = p.t.post_off[terms[0] + 1];
-  uint32_t c = 0;
-  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
-    c += text_phrase_freq(p.t, terms, nt, j, p.t.post_doc[j]) > 0 ? 1u : 0u;
+  const int tid = threadIdx.x;
   for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
   if ((tid & 63) == 0) part[tid >> 6] = c;
   __syncthreads();
   if (tid == 0) {
     const uint32_t all = part[0] + part[1] + part[2] + part[3];
-    if (all) atomicAdd(&p.nhit[item], (unsigned long long)all);
+    if (all) atomicAdd(counter, (unsigned long long)all);
   }
 }
+
+struct TextHitP {
+  TextIxP t;
+  const int32_t* phr_tok;
+  const int32_t* terms;
+  const int32_t* phr_hi;           // [phrases] end of the last token's term range, 0 = exact; read by text_hit_kernel<true> only
+  const int32_t* item_phr;         // [items] phrases of several known tokens
+  unsigned long long* nhit;        // [items]
+};
+
+// nHit of a phrase of several tokens: the documents of the WHOLE table that hold it.  PX: the phrases of tree queries, whose last
+// token may be a prefix; text_hit_kernel<false> is the flat queries' and knows nothing of prefixes.
+template <bool PX>
+__global__ void __launch_bounds__(TEXT_TPB) text_hit_kernel(TextHitP p) {
+  const int item = blockIdx.y, tid = threadIdx.x;
+  const int phr = p.item_phr[item];
+  const int tb = p.phr_tok[phr], nt = p.phr_tok[phr + 1] - tb;
+  const int32_t* terms = p.terms + tb;
+  const int hi_t = PX ? p.phr_hi[phr] : 0;
+  const int64_t lo = p.t.post_off[terms[0]], hi = p.t.post_off[terms[0] + 1];
+  uint32_t c = 0;
+  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB) {
+    const int doc = p.t.post_doc[j];
+    c += (PX ? text_phrase_freq_px(p.t, terms, nt, hi_t, j, doc) : text_phrase_freq(p.t, terms, nt, j, doc)) > 0 ? 1u : 0u;
+  }
+  text_block_count(c, &p.nhit[item]);
+}
+
+struct TextPrefixP {
+  TextIxP t;
+  const int32_t* phr_tok;
+  const int32_t* terms;
+  const int32_t* phr_hi;
+  const int32_t* px_phr;           // [prefix phrases of the chunk] single-token phrases that end in a prefix
+  const int32_t* px_at;            // [the same] the phrase's frequency array: (query of the chunk) * slots + slot
+  uint32_t* pfreq;                 // [chunk queries * slots][stride] zeroed
+  int64_t stride;
+  unsigned long long* pxhit;       // [phrases] zeroed
+};
+
+// The pre-pass of a single-token prefix phrase: the postings of the terms [lo, hi) are ONE run of the posting arrays; a lane
+// per posting adds the term frequency to the document's entry (integer adds: order cannot show).  The lane that finds the
+// entry at zero counts the document: nHit = documents that hold any term of the range.
+__global__ void __launch_bounds__(TEXT_TPB) text_prefix_kernel(TextPrefixP p) {
+  const int tid = threadIdx.x;
+  const int phr = p.px_phr[blockIdx.y];
+  const int term = p.terms[p.phr_tok[phr]];
+  uint32_t* arr = p.pfreq + (int64_t)p.px_at[blockIdx.y] * p.stride;
+  const int64_t lo = p.t.post_off[term], hi = p.t.post_off[p.phr_hi[phr]];
+  uint32_t c = 0;
+  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
+    c += atomicAdd(&arr[p.t.post_doc[j]], (uint32_t)p.t.post_tf[j]) == 0u ? 1u : 0u;   // (a posting's frequency is >= 1)
+  text_block_count(c, &p.pxhit[phr]);
+}
+
+// ---- the (query, slice) kernels: what the flat and the tree kernel share ------------------------------------------------------
 
 struct TextScoreP {
   TextIxP t;
@@ -108,12 +186,9 @@ struct TextScoreP {
   const int32_t* terms;
   const double* idf;         // [phrases]
   const int32_t* mode;       // [B]
-  int q0;                    // first query of the chunk
-  int64_t s0;                // first slice of the chunk
   int64_t n_docs;
   double avgdl;
   int keep;                  // entries a slice hands on
-  const int32_t* qrow;       // [chunk queries] row of docbits, -1 = no subset; NULL = no subsets at all
   const uint32_t* docbits;   // [rows][NW]
   int64_t NW;
   int64_t S;                 // slices per query in the lists (the plan's)
@@ -121,93 +196,70 @@ struct TextScoreP {
   int32_t* list_ids;
   int32_t* list_cnt;         // [chunk queries][S]
   unsigned long long* ctr;   // postings visited, or NULL
+  // what changes from launch to launch of a call
+  int q0;                    // first query of the chunk
+  int64_t s0;                // first slice of the chunk
+  const int32_t* qrow;       // [chunk queries] row of docbits, -1 = no subset; NULL = no subsets at all
 };
 
-__global__ void __launch_bounds__(TEXT_TPB) text_score_kernel(TextScoreP p) {
-  __shared__ double s_acc[TEXT_SLICE];
-  __shared__ uint8_t s_cnt[TEXT_SLICE];
-  __shared__ uint16_t s_idx[TEXT_SLICE];
-  __shared__ int64_t s_lo[NP_TEXT_MAX_PHRASES], s_hi[NP_TEXT_MAX_PHRASES];
-  __shared__ int s_any, s_all, s_n;
-  const int tid = threadIdx.x, ql = blockIdx.y, q = p.q0 + ql;
+// the workgroup's (query, slice)
+struct TextSlice {
+  int64_t d0;     // first document of the slice
+  int n;          // its documents
+  int ph0, nph;   // the query's phrases
+  int row;        // the query's row of docbits, -1 = no subset
+  int64_t o;      // the (query, slice) pair in the lists
+};
+
+__device__ __forceinline__ TextSlice text_slice(const TextScoreP& p) {
+  const int ql = blockIdx.y, q = p.q0 + ql;
   const int64_t sl = blockIdx.x;
-  const int64_t d0 = (p.s0 + sl) * TEXT_SLICE;
-  const int n = p.n_docs - d0 < TEXT_SLICE ? (int)(p.n_docs - d0) : TEXT_SLICE;
-  const int ph0 = p.q_phr[q], nph = p.q_phr[q + 1] - ph0;
-  const int row = p.qrow ? p.qrow[ql] : -1;
-  const int64_t o = (int64_t)ql * p.S + sl;
-  if (tid == 0) {
-    s_any = 0;
-    s_all = 1;
-    s_n = 0;
-  }
-  __syncthreads();
-  // the slice's part of every phrase's first posting list
-  if (tid < nph) {
-    const int tb = p.phr_tok[ph0 + tid], te = p.phr_tok[ph0 + tid + 1];
-    bool known = true;
-    for (int k = tb; k < te; ++k) known = known && p.terms[k] >= 0;
-    int64_t lo = 0, hi = 0;
-    if (known) {
-      const int term = p.terms[tb];
-      const int64_t e = p.t.post_off[term + 1];
-      lo = text_lower_bound(p.t.post_doc, p.t.post_off[term], e, d0);
-      hi = text_lower_bound(p.t.post_doc, lo, e, d0 + n);
-    }
-    s_lo[tid] = lo;
-    s_hi[tid] = hi;
-    if (hi > lo) atomicOr(&s_any, 1); else atomicAnd(&s_all, 0);
-  }
-  __syncthreads();
-  const bool is_and = p.mode[q] == NP_TEXT_AND;
-  if (!s_any || (is_and && !s_all)) {   // (block-uniform) nothing of the slice can match
-    if (tid == 0) p.list_cnt[o] = 0;
-    return;
-  }
-  for (int i = tid; i < n; i += TEXT_TPB) {
-    s_acc[i] = 0.0;
-    s_cnt[i] = 0;
-  }
-  __syncthreads();
-  const double k1 = 1.2, b = 0.75;
-  unsigned long long visited = 0;
-  for (int ph = 0; ph < nph; ++ph) {
-    const int64_t lo = s_lo[ph], hi = s_hi[ph];
-    const int tb = p.phr_tok[ph0 + ph], nt = p.phr_tok[ph0 + ph + 1] - tb;
-    const double idf = p.idf[ph0 + ph];
-    for (int64_t j = lo + tid; j < hi; j += TEXT_TPB) {
-      const int doc = p.t.post_doc[j];
-      const int freq = text_phrase_freq(p.t, p.terms + tb, nt, j, doc);
-      if (freq > 0) {
-        const int l = (int)(doc - d0);
-        const double a = (double)freq, D = (double)p.t.doc_len[doc];
-        s_acc[l] = s_acc[l] + idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / p.avgdl)));
-        s_cnt[l] = (uint8_t)(s_cnt[l] + 1);
-      }
-    }
-    visited += (unsigned long long)(hi - lo);
-    __syncthreads();
-  }
-  if (p.ctr && tid == 0 && visited) atomicAdd(p.ctr, visited);
-  // the slice's matching documents in scope: slots from a counter, the order from the sort below
-  for (int i = tid; i < n; i += TEXT_TPB) {
-    bool m = is_and ? s_cnt[i] == nph : s_cnt[i] > 0;
-    if (m && row >= 0) {
-      const int64_t d = d0 + i;
-      m = ((p.docbits[(int64_t)row * p.NW + (d >> 5)] >> (d & 31)) & 1u) != 0;
-    }
-    if (m) s_idx[atomicAdd(&s_n, 1)] = (uint16_t)i;
-  }
-  __syncthreads();
-  const int nm = s_n;
+  TextSlice s;
+  s.d0 = (p.s0 + sl) * TEXT_SLICE;
+  s.n = p.n_docs - s.d0 < TEXT_SLICE ? (int)(p.n_docs - s.d0) : TEXT_SLICE;
+  s.ph0 = p.q_phr[q];
+  s.nph = p.q_phr[q + 1] - s.ph0;
+  s.row = p.qrow ? p.qrow[ql] : -1;
+  s.o = (int64_t)ql * p.S + sl;
+  return s;
+}
+
+// every token of the phrase is in the vocabulary
+__device__ __forceinline__ bool text_phrase_known(const TextScoreP& p, int phr) {
+  bool known = true;
+  for (int k = p.phr_tok[phr]; k < p.phr_tok[phr + 1]; ++k) known = known && p.terms[k] >= 0;
+  return known;
+}
+
+// the slice's part [*lo, *hi) of the phrase's first posting list; empty where a token of the phrase is unknown
+__device__ __forceinline__ void text_slice_range(const TextScoreP& p, const TextSlice& s, int phr, int64_t* lo, int64_t* hi) {
+  *lo = *hi = 0;
+  if (!text_phrase_known(p, phr)) return;
+  const int term = p.terms[p.phr_tok[phr]];
+  const int64_t e = p.t.post_off[term + 1];
+  *lo = text_lower_bound(p.t.post_doc, p.t.post_off[term], e, s.d0);
+  *hi = text_lower_bound(p.t.post_doc, *lo, e, s.d0 + s.n);
+}
+
+// document i of the slice is in the subset of the query (one that has a subset: s.row >= 0)
+__device__ __forceinline__ bool text_in_subset(const TextScoreP& p, const TextSlice& s, int i) {
+  const int64_t d = s.d0 + i;
+  return ((p.docbits[(int64_t)s.row * p.NW + (d >> 5)] >> (d & 31)) & 1u) != 0;
+}
+
+// The slice's list leaves: s_idx[0 .. nm) holds the matching documents' indexes in any order, s_acc their scores.  Bitonic sort
+// of the indexes, padded to a power of two with 0xFFFF: score descending (a match's score is positive: its bits order as
+// integers), then id; the best `keep` are written.  nm = 0: the empty list.  Every thread of the block calls it (block-uniform
+// nm), behind a barrier after the last write to s_acc and s_idx.
+__device__ __forceinline__ void text_slice_emit(const TextScoreP& p, const TextSlice& s, const double* s_acc, uint16_t* s_idx, int nm) {
+  const int tid = threadIdx.x;
   if (nm == 0) {
-    if (tid == 0) p.list_cnt[o] = 0;
+    if (tid == 0) p.list_cnt[s.o] = 0;
     return;
   }
   int P2 = 1;
   while (P2 < nm) P2 <<= 1;
   for (int i = nm + tid; i < P2; i += TEXT_TPB) s_idx[i] = 0xFFFF;
-  // bitonic sort of the indexes: score descending (a match's score is positive: its bits order as integers), then id
   auto before = [&](uint16_t x, uint16_t y) {
     if (x == 0xFFFF) return false;
     if (y == 0xFFFF) return true;
@@ -232,111 +284,74 @@ __global__ void __launch_bounds__(TEXT_TPB) text_score_kernel(TextScoreP p) {
   const int kept = min(nm, p.keep);
   for (int r = tid; r < kept; r += TEXT_TPB) {
     const int l = s_idx[r];
-    p.list_keys[o * p.keep + r] = (unsigned long long)__double_as_longlong(s_acc[l]);
-    p.list_ids[o * p.keep + r] = (int32_t)(d0 + l);
+    p.list_keys[s.o * p.keep + r] = (unsigned long long)__double_as_longlong(s_acc[l]);
+    p.list_ids[s.o * p.keep + r] = (int32_t)(s.d0 + l);
   }
-  if (tid == 0) p.list_cnt[o] = kept;
+  if (tid == 0) p.list_cnt[s.o] = kept;
 }
 
-// ---- tree queries (np_text_expr): prefix frequencies, hit counts, and the (query, slice) kernel ----------------------------
+// ---- flat queries -----------------------------------------------------------------------------------------------------------
 
-// text_phrase_freq for a phrase of several tokens whose last token stands for the terms [terms[nt - 1], hi): a position
-// holds one term, so at most one term of the range continues an occurrence.  hi = 0: the exact phrase.
-__device__ __forceinline__ int text_phrase_freq_px(const TextIxP& t, const int32_t* __restrict__ terms, int nt, int hi, int64_t j0, int doc) {
-  if (hi == 0 || nt == 1) return text_phrase_freq(t, terms, nt, j0, doc);
-  const int tf0 = t.post_tf[j0];
-  const int64_t f0 = t.post_first[j0];
-  int freq = 0;
-  for (int x = 0; x < tf0; ++x) {
-    const int64_t p = t.pos[f0 + x];
-    bool ok = true;
-    for (int k = 1; k < nt - 1 && ok; ++k) {
-      const int term = terms[k];
-      const int64_t e = t.post_off[term + 1];
-      const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
-      if (jk >= e || t.post_doc[jk] != doc) return 0;
-      const int64_t pe = t.post_first[jk] + t.post_tf[jk];
-      const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, p + k);
-      ok = at < pe && (int64_t)t.pos[at] == p + k;
-    }
-    if (!ok) continue;
-    bool last = false;
-    for (int term = terms[nt - 1]; term < hi && !last; ++term) {
-      const int64_t e = t.post_off[term + 1];
-      const int64_t jk = text_lower_bound(t.post_doc, t.post_off[term], e, doc);
-      if (jk >= e || t.post_doc[jk] != doc) continue;
-      const int64_t pe = t.post_first[jk] + t.post_tf[jk];
-      const int64_t at = text_lower_bound(t.pos, t.post_first[jk], pe, p + nt - 1);
-      last = at < pe && (int64_t)t.pos[at] == p + nt - 1;
-    }
-    freq += last ? 1 : 0;
-  }
-  return freq;
-}
-
-struct TextExprHitP {
-  TextIxP t;
-  const int32_t* phr_tok;
-  const int32_t* terms;
-  const int32_t* phr_hi;           // [phrases] end of the last token's term range, 0 = exact
-  const int32_t* item_phr;         // [items] phrases of several known tokens
-  unsigned long long* nhit;        // [items]
-};
-
-// text_hit_kernel for the phrases of a tree query: the same count, with a last token that may be a prefix
-__global__ void __launch_bounds__(TEXT_TPB) text_expr_hit_kernel(TextExprHitP p) {
-  __shared__ uint32_t part[TEXT_TPB / 64];
-  const int item = blockIdx.y, tid = threadIdx.x;
-  const int phr = p.item_phr[item];
-  const int tb = p.phr_tok[phr], nt = p.phr_tok[phr + 1] - tb;
-  const int32_t* terms = p.terms + tb;
-  const int hi_t = p.phr_hi[phr];
-  const int64_t lo = p.t.post_off[terms[0]], hi = p.t.post_off[terms[0] + 1];
-  uint32_t c = 0;
-  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
-    c += text_phrase_freq_px(p.t, terms, nt, hi_t, j, p.t.post_doc[j]) > 0 ? 1u : 0u;
-  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
-  if ((tid & 63) == 0) part[tid >> 6] = c;
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t all = part[0] + part[1] + part[2] + part[3];
-    if (all) atomicAdd(&p.nhit[item], (unsigned long long)all);
-  }
-}
-
-struct TextPrefixP {
-  TextIxP t;
-  const int32_t* phr_tok;
-  const int32_t* terms;
-  const int32_t* phr_hi;
-  const int32_t* px_phr;           // [prefix phrases of the chunk] single-token phrases that end in a prefix
-  const int32_t* px_at;            // [the same] the phrase's frequency array: (query of the chunk) * slots + slot
-  uint32_t* pfreq;                 // [chunk queries * slots][stride] zeroed
-  int64_t stride;
-  unsigned long long* pxhit;       // [phrases] zeroed
-};
-
-// The pre-pass of a single-token prefix phrase: the postings of the terms [lo, hi) are ONE run of the posting arrays; a lane
-// per posting adds the term frequency to the document's entry (integer adds: order cannot show).  The lane that finds the
-// entry at zero counts the document: nHit = documents that hold any term of the range.
-__global__ void __launch_bounds__(TEXT_TPB) text_prefix_kernel(TextPrefixP p) {
-  __shared__ uint32_t part[TEXT_TPB / 64];
+__global__ void __launch_bounds__(TEXT_TPB) text_score_kernel(TextScoreP p) {
+  __shared__ double s_acc[TEXT_SLICE];
+  __shared__ uint8_t s_cnt[TEXT_SLICE];
+  __shared__ uint16_t s_idx[TEXT_SLICE];
+  __shared__ int64_t s_lo[NP_TEXT_MAX_PHRASES], s_hi[NP_TEXT_MAX_PHRASES];
+  __shared__ int s_any, s_all, s_n;
   const int tid = threadIdx.x;
-  const int phr = p.px_phr[blockIdx.y];
-  const int term = p.terms[p.phr_tok[phr]];
-  uint32_t* arr = p.pfreq + (int64_t)p.px_at[blockIdx.y] * p.stride;
-  const int64_t lo = p.t.post_off[term], hi = p.t.post_off[p.phr_hi[phr]];
-  uint32_t c = 0;
-  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB)
-    c += atomicAdd(&arr[p.t.post_doc[j]], (uint32_t)p.t.post_tf[j]) == 0u ? 1u : 0u;   // (a posting's frequency is >= 1)
-  for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
-  if ((tid & 63) == 0) part[tid >> 6] = c;
-  __syncthreads();
+  const TextSlice s = text_slice(p);
+  const int64_t d0 = s.d0;
+  const int n = s.n, ph0 = s.ph0, nph = s.nph;
   if (tid == 0) {
-    const uint32_t all = part[0] + part[1] + part[2] + part[3];
-    if (all) atomicAdd(&p.pxhit[phr], (unsigned long long)all);
+    s_any = 0;
+    s_all = 1;
+    s_n = 0;
   }
+  __syncthreads();
+  if (tid < nph) {
+    int64_t lo, hi;
+    text_slice_range(p, s, ph0 + tid, &lo, &hi);
+    s_lo[tid] = lo;
+    s_hi[tid] = hi;
+    if (hi > lo) atomicOr(&s_any, 1); else atomicAnd(&s_all, 0);
+  }
+  __syncthreads();
+  const bool is_and = p.mode[p.q0 + blockIdx.y] == NP_TEXT_AND;
+  if (!s_any || (is_and && !s_all)) return text_slice_emit(p, s, s_acc, s_idx, 0);   // (block-uniform) nothing of the slice can match
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    s_acc[i] = 0.0;
+    s_cnt[i] = 0;
+  }
+  __syncthreads();
+  unsigned long long visited = 0;
+  for (int ph = 0; ph < nph; ++ph) {
+    const int64_t lo = s_lo[ph], hi = s_hi[ph];
+    const int tb = p.phr_tok[ph0 + ph], nt = p.phr_tok[ph0 + ph + 1] - tb;
+    const double idf = p.idf[ph0 + ph];
+    for (int64_t j = lo + tid; j < hi; j += TEXT_TPB) {
+      const int doc = p.t.post_doc[j];
+      const int freq = text_phrase_freq(p.t, p.terms + tb, nt, j, doc);
+      if (freq > 0) {
+        const int l = (int)(doc - d0);
+        s_acc[l] = s_acc[l] + text_bm25_term(idf, (double)freq, (double)p.t.doc_len[doc], p.avgdl);
+        s_cnt[l] = (uint8_t)(s_cnt[l] + 1);
+      }
+    }
+    visited += (unsigned long long)(hi - lo);
+    __syncthreads();
+  }
+  if (p.ctr && tid == 0 && visited) atomicAdd(p.ctr, visited);
+  // the slice's matching documents in scope: slots from a counter, the order from the sort in text_slice_emit
+  for (int i = tid; i < n; i += TEXT_TPB) {
+    bool m = is_and ? s_cnt[i] == nph : s_cnt[i] > 0;
+    if (m && s.row >= 0) m = text_in_subset(p, s, i);
+    if (m) s_idx[atomicAdd(&s_n, 1)] = (uint16_t)i;
+  }
+  __syncthreads();
+  text_slice_emit(p, s, s_acc, s_idx, s_n);
 }
+
+// ---- tree queries (np_text_expr) ------------------------------------------------------------------------------------------
 
 struct TextExprP {
   TextScoreP s;                    // text_score_kernel's arguments (mode is not read)
@@ -364,30 +379,21 @@ __global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
   __shared__ int s_any, s_n;
   const TextScoreP& p = e.s;
   const int tid = threadIdx.x, ql = blockIdx.y, q = p.q0 + ql;
-  const int64_t sl = blockIdx.x;
-  const int64_t d0 = (p.s0 + sl) * TEXT_SLICE;
-  const int n = p.n_docs - d0 < TEXT_SLICE ? (int)(p.n_docs - d0) : TEXT_SLICE;
-  const int ph0 = p.q_phr[q], nph = p.q_phr[q + 1] - ph0;
+  const TextSlice s = text_slice(p);
+  const int64_t d0 = s.d0;
+  const int n = s.n, ph0 = s.ph0, nph = s.nph;
   const int nd0 = e.q_node[q], nn = e.q_node[q + 1] - nd0;
-  const int row = p.qrow ? p.qrow[ql] : -1;
-  const int64_t o = (int64_t)ql * p.S + sl;
   if (tid == 0) {
     s_any = 0;
     s_n = 0;
   }
   __syncthreads();
   if (tid < nph) {
-    const int tb = p.phr_tok[ph0 + tid], te = p.phr_tok[ph0 + tid + 1];
-    bool known = true;
-    for (int k = tb; k < te; ++k) known = known && p.terms[k] >= 0;
     int64_t lo = 0, hi = 0;
-    if (known && e.phr_slot[ph0 + tid] >= 0) {
-      atomicOr(&s_any, 1);   // (its documents are in the frequency array, not in one posting list)
-    } else if (known) {
-      const int term = p.terms[tb];
-      const int64_t end = p.t.post_off[term + 1];
-      lo = text_lower_bound(p.t.post_doc, p.t.post_off[term], end, d0);
-      hi = text_lower_bound(p.t.post_doc, lo, end, d0 + n);
+    if (e.phr_slot[ph0 + tid] >= 0) {   // (its documents are in the frequency array, not in one posting list)
+      if (text_phrase_known(p, ph0 + tid)) atomicOr(&s_any, 1);
+    } else {
+      text_slice_range(p, s, ph0 + tid, &lo, &hi);
       if (hi > lo) atomicOr(&s_any, 1);
     }
     s_lo[tid] = lo;
@@ -395,10 +401,7 @@ __global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
   }
   for (int i = tid; i < nn; i += TEXT_TPB) s_node[i] = e.nodes[nd0 + i];
   __syncthreads();
-  if (!s_any) {   // (block-uniform) a match has a phrase that occurs
-    if (tid == 0) p.list_cnt[o] = 0;
-    return;
-  }
+  if (!s_any) return text_slice_emit(p, s, s_acc, s_idx, 0);   // (block-uniform) a match has a phrase that occurs
   for (int i = tid; i < n; i += TEXT_TPB) {
     s_acc[i] = 0.0;
     s_mask[i] = 0ull;
@@ -427,7 +430,7 @@ __global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
   }
   if (p.ctr && tid == 0 && visited) atomicAdd(p.ctr, visited);
   // the tree, a lane per document: node truths bottom-up, liveness top-down, the live phrases back into the mask; the
-  // matching documents in scope take their slots from a counter, the order comes from the sort below
+  // matching documents in scope take their slots from a counter, the order comes from the sort in text_slice_emit
   for (int i = tid; i < n; i += TEXT_TPB) {
     const unsigned long long occ = s_mask[i];
     unsigned long long t0 = 0, t1 = 0;   // truth of the nodes 0..63 and 64..126
@@ -445,10 +448,7 @@ __global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
       }
     }
     bool m = occ != 0ull && truth(nn - 1) != 0;
-    if (m && row >= 0) {
-      const int64_t d = d0 + i;
-      m = ((p.docbits[(int64_t)row * p.NW + (d >> 5)] >> (d & 31)) & 1u) != 0;
-    }
+    if (m && s.row >= 0) m = text_in_subset(p, s, i);
     unsigned long long live = 0;
     if (m) {
       unsigned long long l0 = 0, l1 = 0;   // liveness of the nodes
@@ -474,22 +474,15 @@ __global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
   }
   __syncthreads();
   const int nm = s_n;
-  if (nm == 0) {
-    if (tid == 0) p.list_cnt[o] = 0;
-    return;
-  }
-  // pass 2: the bm25 terms of the live phrases, in phrase order
-  const double k1 = 1.2, b = 0.75;
+  if (nm == 0) return text_slice_emit(p, s, s_acc, s_idx, 0);
+  // pass 2: the bm25 terms of the live phrases, in phrase order (a live phrase has a positive term: a match's score is positive)
   for (int ph = 0; ph < nph; ++ph) {
     const double idf = p.idf[ph0 + ph];
     const int slot = e.phr_slot[ph0 + ph];
     if (slot >= 0) {
       const uint32_t* arr = e.pfreq + ((int64_t)ql * e.slots + slot) * e.stride + d0;
       for (int i = tid; i < n; i += TEXT_TPB)
-        if ((s_mask[i] >> ph) & 1ull) {
-          const double a = (double)arr[i], D = (double)p.t.doc_len[d0 + i];
-          s_acc[i] = s_acc[i] + idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / p.avgdl)));
-        }
+        if ((s_mask[i] >> ph) & 1ull) s_acc[i] = s_acc[i] + text_bm25_term(idf, (double)arr[i], (double)p.t.doc_len[d0 + i], p.avgdl);
     } else {
       const int64_t lo = s_lo[ph], hi = s_hi[ph];
       const int tb = p.phr_tok[ph0 + ph], nt = p.phr_tok[ph0 + ph + 1] - tb;
@@ -499,45 +492,13 @@ __global__ void __launch_bounds__(TEXT_TPB) text_expr_kernel(TextExprP e) {
         const int l = (int)(doc - d0);
         if ((s_mask[l] >> ph) & 1ull) {
           const int freq = text_phrase_freq_px(p.t, p.terms + tb, nt, hi_t, j, doc);
-          const double a = (double)freq, D = (double)p.t.doc_len[doc];
-          s_acc[l] = s_acc[l] + idf * ((a * (k1 + 1.0)) / (a + k1 * (1 - b + b * D / p.avgdl)));
+          s_acc[l] = s_acc[l] + text_bm25_term(idf, (double)freq, (double)p.t.doc_len[doc], p.avgdl);
         }
       }
     }
     __syncthreads();
   }
-  int P2 = 1;
-  while (P2 < nm) P2 <<= 1;
-  for (int i = nm + tid; i < P2; i += TEXT_TPB) s_idx[i] = 0xFFFF;
-  // text_score_kernel's sort: score descending (a match's score is positive: a live phrase has a positive term), then id
-  auto before = [&](uint16_t x, uint16_t y) {
-    if (x == 0xFFFF) return false;
-    if (y == 0xFFFF) return true;
-    const unsigned long long kx = (unsigned long long)__double_as_longlong(s_acc[x]), ky = (unsigned long long)__double_as_longlong(s_acc[y]);
-    return kx > ky || (kx == ky && x < y);
-  };
-  for (int k = 2; k <= P2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int i = tid; i < P2; i += TEXT_TPB) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const uint16_t x = s_idx[i], y = s_idx[ixj];
-          if ((i & k) == 0 ? before(y, x) : before(x, y)) {
-            s_idx[i] = y;
-            s_idx[ixj] = x;
-          }
-        }
-      }
-    }
-  __syncthreads();
-  const int kept = min(nm, p.keep);
-  for (int r = tid; r < kept; r += TEXT_TPB) {
-    const int l = s_idx[r];
-    p.list_keys[o * p.keep + r] = (unsigned long long)__double_as_longlong(s_acc[l]);
-    p.list_ids[o * p.keep + r] = (int32_t)(d0 + l);
-  }
-  if (tid == 0) p.list_cnt[o] = kept;
+  text_slice_emit(p, s, s_acc, s_idx, nm);
 }
 
 // (key descending, id ascending) over the first `fill` entries of a window; entries up to the next power of two are padded
@@ -873,28 +834,10 @@ static int text_check_handle(const DeviceIndex* ix, bool need_text) {
   return NP_OK;
 }
 
-static int text_check_queries(const DeviceIndex* ix, const np_text_query* queries, int B, int top_k) {
-  NP_TRY(text_check_handle(ix, true));
-  const char* why = "";
-  if (text_check_call(B, top_k, &why) != 0) {
-    set_error("Text search failed: %s (B=%d top_k=%d)", why, B, top_k);
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  if (B > 0 && !queries) {
-    set_error("Text search failed: NULL queries");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  char msg[240];
-  for (int q = 0; q < B; ++q)
-    if (text_check_query(&queries[q], q, ix->text.n_terms, msg, sizeof msg) != 0) {
-      set_error("Text search failed: %s", msg);
-      return NP_ERR_INVALID_ARGUMENT;
-    }
-  return NP_OK;
-}
-
-static int text_check_exprs(const DeviceIndex* ix, const np_text_expr* queries, int B, int top_k) {
-  NP_TRY(text_check_handle(ix, true));
+// The checks of a batch of flat or tree queries against a vocabulary of n_terms; `check` is the query type's own
+// (text_check_query, text_check_expr: np_text_plan.h).
+template <class Q>
+static int text_check_batch(int64_t n_terms, const Q* queries, int B, int top_k, int (*check)(const Q*, int32_t, int64_t, char*, size_t)) {
   const char* why = "";
   if (text_check_call(B, top_k, &why) != 0) {
     set_error("Text search failed: %s (B=%d top_k=%d)", why, B, top_k);
@@ -906,15 +849,27 @@ static int text_check_exprs(const DeviceIndex* ix, const np_text_expr* queries, 
   }
   char msg[320];
   for (int q = 0; q < B; ++q)
-    if (text_check_expr(&queries[q], q, ix->text.n_terms, msg, sizeof msg) != 0) {
+    if (check(&queries[q], q, n_terms, msg, sizeof msg) != 0) {
       set_error("Text search failed: %s", msg);
       return NP_ERR_INVALID_ARGUMENT;
     }
   return NP_OK;
 }
+// ... on a handle that holds the whole keyword index
+static int text_check_queries(const DeviceIndex* ix, const np_text_query* queries, int B, int top_k) {
+  NP_TRY(text_check_handle(ix, true));
+  return text_check_batch(ix->text.n_terms, queries, B, top_k, text_check_query);
+}
+static int text_check_exprs(const DeviceIndex* ix, const np_text_expr* queries, int B, int top_k) {
+  NP_TRY(text_check_handle(ix, true));
+  return text_check_batch(ix->text.n_terms, queries, B, top_k, text_check_expr);
+}
 
-// A batch's queries as the kernels read them, one blob: q_phr | phr_tok | terms | mode | item_phr | nhit | idf
+// A batch's queries as the kernels read them, one blob: q_phr | phr_tok | terms | mode | item_phr | nhit | idf, and behind them
+// for a batch of tree queries (np_text_expr; `tree`): phr_hi | phr_slot | q_node | nodes | px_phr | px_at | pxhit.  A flat batch
+// leaves the tree's fields at zero and nothing reads them.
 struct TextProg {
+  bool tree = false;
   int B = 0;
   int64_t n_phr = 0, n_tok = 0, n_items = 0;
   int64_t max_item_df = 0;
@@ -922,15 +877,25 @@ struct TextProg {
   size_t o_qphr = 0, o_ptok = 0, o_terms = 0, o_mode = 0, o_item = 0, o_nhit = 0, o_idf = 0, bytes = 0;
   std::vector<char> blob;
   std::vector<int64_t> phr_hit;   // nHit where the host knows it, -1 where the counting pass says
+  // tree only.  A single-token phrase that ends in a prefix gets a slot: a per-document frequency array of its query, filled by
+  // text_prefix_kernel, which also counts its nHit
+  int slots = 0;             // frequency arrays a query of a chunk owns (the batch's maximum)
+  int64_t stride = 0;        // entries of one
+  int64_t n_px = 0;
+  size_t o_phi = 0, o_slot = 0, o_qnode = 0, o_nodes = 0, o_pxphr = 0, o_pxat = 0, o_pxhit = 0;
+  std::vector<int32_t> px_query;   // [n_px] the query of a prefix entry (entries ascend by query)
   int32_t* at32(size_t off) { return (int32_t*)(blob.data() + off); }
-  void build(const DeviceIndex* ix, const np_text_query* qs, int B_) {
+  void build(const DeviceIndex* ix, const np_text_query* qs, int B_) { build_phrases(ix, B_, [&](int q) { return qs[q]; }); }
+  // the phrases of B_ queries; phrases_of(q): query q's terms, phrase offsets, phrase count and mode, as an np_text_query
+  template <class F>
+  void build_phrases(const DeviceIndex* ix, int B_, F phrases_of) {
     B = B_;
     for (int q = 0; q < B; ++q) {
-      n_phr += qs[q].n_phrases;
-      n_tok += qs[q].phrase_offsets[qs[q].n_phrases];
+      const np_text_query tq = phrases_of(q);
+      n_phr += tq.n_phrases;
+      n_tok += tq.phrase_offsets[tq.n_phrases];
     }
     phr_hit.assign((size_t)n_phr, 0);
-    std::vector<int32_t> items;
     // sizes first: the items are known only after a walk
     o_qphr = 0;
     o_ptok = o_qphr + up256((size_t)(B + 1) * 4);
@@ -947,75 +912,37 @@ struct TextProg {
     const DeviceText& tx = ix->text;
     const std::vector<int64_t>& off = tx.h_post_off;   // the handle's own lists: the counting pass walks those
     for (int q = 0; q < B; ++q) {
+      const np_text_query tq = phrases_of(q);
       qphr[q] = (int32_t)ph;
-      mode[q] = qs[q].mode;
-      for (int i = 0; i < qs[q].n_phrases; ++i, ++ph) {
+      mode[q] = tq.mode;
+      for (int i = 0; i < tq.n_phrases; ++i, ++ph) {
         ptok[ph] = (int32_t)tk;
-        const int tb = qs[q].phrase_offsets[i], te = qs[q].phrase_offsets[i + 1];
+        const int tb = tq.phrase_offsets[i], te = tq.phrase_offsets[i + 1];
         bool known = true;
         for (int k = tb; k < te; ++k) {
-          terms[tk++] = qs[q].terms[k];
-          known = known && qs[q].terms[k] >= 0;
+          terms[tk++] = tq.terms[k];
+          known = known && tq.terms[k] >= 0;
         }
         if (!known) {
           phr_hit[ph] = 0;
         } else if (te - tb == 1) {
-          phr_hit[ph] = tx.present ? tx.df(qs[q].terms[tb]) : 0;   // (of the whole table, also on a shard)
+          phr_hit[ph] = tx.present ? tx.df(tq.terms[tb]) : 0;   // (of the whole table, also on a shard)
         } else {
           phr_hit[ph] = -1;
           item[n_items++] = (int32_t)ph;
-          if (tx.present) max_item_df = std::max(max_item_df, off[qs[q].terms[tb] + 1] - off[qs[q].terms[tb]]);
+          if (tx.present) max_item_df = std::max(max_item_df, off[tq.terms[tb] + 1] - off[tq.terms[tb]]);
         }
       }
     }
     qphr[B] = (int32_t)ph;
     ptok[ph] = (int32_t)tk;
   }
-};
-
-// bytes of the arena that scale with the chunk's queries -- one expression for the plan and for the carve-up
-static int64_t text_per_query(const DeviceIndex* ix, int top_k, bool subsets) {
-  const int64_t NW = std::max<int64_t>((ix->n_docs + 31) / 32, 1);
-  return (int64_t)up256((size_t)top_k * 8) + (int64_t)up256((size_t)top_k * 4) + 8 + (subsets ? (int64_t)up256((size_t)NW * 4) : 0);
-}
-static int64_t text_n_slices(const DeviceIndex* ix) {
-  return std::max<int64_t>(1, (ix->n_docs + NP_TEXT_SLICE_DOCS - 1) / NP_TEXT_SLICE_DOCS);
-}
-static int64_t text_fixed_bytes(const TextProg& prog) { return (int64_t)prog.bytes + 4096; }
-static size_t text_arena_bytes(const DeviceIndex* ix, const TextPlan& plan, const TextProg& prog, int top_k, bool subsets) {
-  const size_t pairs = (size_t)plan.queries * (size_t)plan.slices, keep = (size_t)text_slice_keep(top_k);
-  return (size_t)text_fixed_bytes(prog) + (size_t)plan.queries * (size_t)(text_per_query(ix, top_k, subsets) + prog.per_query_extra) +
-         up256(pairs * keep * 8) + up256(pairs * keep * 4) + up256(pairs * 4);
-}
-static int text_plan_for(const DeviceIndex* ix, int64_t user, const TextProg& prog, int B, int top_k, bool subsets, TextPlan* plan) {
-  const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
-  // (the three list arrays are each rounded up to 256 bytes: 768 more than the plan's pairs)
-  if (!text_plan(budget, user + text_fixed_bytes(prog) + 1024, text_per_query(ix, top_k, subsets) + prog.per_query_extra,
-                 text_n_slices(ix), B, ix->opts.max_batch, top_k, plan)) {
-    set_error("Text search failed: one query over one slice of %lld documents does not fit the workspace budget of %lld bytes",
-              (long long)NP_TEXT_SLICE_DOCS, (long long)budget);
-    return NP_ERR_OUT_OF_MEMORY;
-  }
-  return NP_OK;
-}
-
-// A batch of tree queries (np_text_expr): TextProg over their phrases (which plans and counts them as it does a flat query's),
-// and behind its blob: phr_hi | phr_slot | q_node | nodes | px_phr | px_at | pxhit.  A single-token phrase that ends in a prefix
-// gets a slot: a per-document frequency array of its query, filled by text_prefix_kernel, which also counts its nHit.
-struct ExprProg : TextProg {
-  int slots = 0;             // frequency arrays a query of a chunk owns (the batch's maximum)
-  int64_t stride = 0;        // entries of one
-  int64_t n_px = 0;
-  size_t o_phi = 0, o_slot = 0, o_qnode = 0, o_nodes = 0, o_pxphr = 0, o_pxat = 0, o_pxhit = 0;
-  std::vector<int32_t> px_query;   // [n_px] the query of a prefix entry (entries ascend by query)
+  // tree queries: their phrases (planned and counted as a flat query's are), then the tree's part behind them
   void build_expr(const DeviceIndex* ix, const np_text_expr* es, int B_) {
-    std::vector<np_text_query> flat((size_t)std::max(B_, 1));
+    tree = true;
+    build_phrases(ix, B_, [&](int q) { return np_text_query{es[q].terms, es[q].phrase_offsets, es[q].n_phrases, NP_TEXT_AND}; });
     int64_t n_nodes = 0;
-    for (int q = 0; q < B_; ++q) {
-      flat[(size_t)q] = np_text_query{es[q].terms, es[q].phrase_offsets, es[q].n_phrases, NP_TEXT_AND};
-      n_nodes += es[q].n_nodes;
-    }
-    build(ix, flat.data(), B_);
+    for (int q = 0; q < B; ++q) n_nodes += es[q].n_nodes;
     const size_t per_phr = up256((size_t)std::max<int64_t>(n_phr, 1) * 4);
     o_phi = bytes;
     o_slot = o_phi + per_phr;
@@ -1049,6 +976,32 @@ struct ExprProg : TextProg {
     per_query_extra = (int64_t)slots * stride * 4;   // (a multiple of 256)
   }
 };
+
+// bytes of the arena that scale with the chunk's queries -- one expression for the plan and for the carve-up
+static int64_t text_per_query(const DeviceIndex* ix, int top_k, bool subsets) {
+  const int64_t NW = std::max<int64_t>((ix->n_docs + 31) / 32, 1);
+  return (int64_t)up256((size_t)top_k * 8) + (int64_t)up256((size_t)top_k * 4) + 8 + (subsets ? (int64_t)up256((size_t)NW * 4) : 0);
+}
+static int64_t text_n_slices(const DeviceIndex* ix) {
+  return std::max<int64_t>(1, (ix->n_docs + NP_TEXT_SLICE_DOCS - 1) / NP_TEXT_SLICE_DOCS);
+}
+static int64_t text_fixed_bytes(const TextProg& prog) { return (int64_t)prog.bytes + 4096; }
+static size_t text_arena_bytes(const DeviceIndex* ix, const TextPlan& plan, const TextProg& prog, int top_k, bool subsets) {
+  const size_t pairs = (size_t)plan.queries * (size_t)plan.slices, keep = (size_t)text_slice_keep(top_k);
+  return (size_t)text_fixed_bytes(prog) + (size_t)plan.queries * (size_t)(text_per_query(ix, top_k, subsets) + prog.per_query_extra) +
+         up256(pairs * keep * 8) + up256(pairs * keep * 4) + up256(pairs * 4);
+}
+static int text_plan_for(const DeviceIndex* ix, int64_t user, const TextProg& prog, int B, int top_k, bool subsets, TextPlan* plan) {
+  const int64_t budget = ix->ws_budget.load(std::memory_order_relaxed);
+  // (the three list arrays are each rounded up to 256 bytes: 768 more than the plan's pairs)
+  if (!text_plan(budget, user + text_fixed_bytes(prog) + 1024, text_per_query(ix, top_k, subsets) + prog.per_query_extra,
+                 text_n_slices(ix), B, ix->opts.max_batch, top_k, plan)) {
+    set_error("Text search failed: one query over one slice of %lld documents does not fit the workspace budget of %lld bytes",
+              (long long)NP_TEXT_SLICE_DOCS, (long long)budget);
+    return NP_ERR_OUT_OF_MEMORY;
+  }
+  return NP_OK;
+}
 
 // The counting exchange of a sharded keyword search (np_dist_plan.h, dist_count_record): this rank's nHit of the counted phrases,
 // its nRow and its status word go out, the sums over the healthy ranks come back.  A rank that cannot count (no keyword index,
@@ -1116,16 +1069,17 @@ struct TextCounts {
 // copies, and the stream is synchronised after the upload.  *visited (nullable): postings the scoring pass visited
 // (synchronises).
 // Sharded (counts != NULL): the hit counts of the counted phrases cross the ranks before the idf is computed, d_out_keys receives
-// the f64 bits of the scores and the ids leave as global ids.
-// Tree queries (ex != NULL, then &prog; host entries only: pin != NULL): the counting pass knows prefixes, every chunk of queries
-// first fills the frequency arrays of its single-token prefix phrases and synchronises once for their nHit, and
-// text_expr_kernel takes text_score_kernel's place.
+// the f64 bits of the scores and the ids leave as global ids; otherwise both are NULL.
+// Tree queries (prog.tree; host entries only: pin != NULL): the counting pass knows prefixes, every chunk of queries first fills
+// the frequency arrays of its single-token prefix phrases and synchronises once for their nHit, and text_expr_kernel takes
+// text_score_kernel's place.
 static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pin, const TextPlan& plan, TextProg& prog, int top_k,
                     const CallSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited,
-                    unsigned long long* d_out_keys = nullptr, TextCounts* counts = nullptr, ExprProg* ex = nullptr) {
+                    unsigned long long* d_out_keys, TextCounts* counts) {
   hipStream_t st = use.stream;
   const DeviceText& tx = ix->text;
   const int B = prog.B;
+  const bool tree = prog.tree;
   const bool subsets = sub.n > 0;
   const int64_t NW = std::max<int64_t>((ix->n_docs + 31) / 32, 1);
   const int Q = plan.queries;
@@ -1142,10 +1096,10 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
   unsigned long long* list_keys = (unsigned long long*)carve.take((size_t)Q * S * keep * 8);
   int32_t* list_ids = (int32_t*)carve.take((size_t)Q * S * keep * 4);
   int32_t* list_cnt = (int32_t*)carve.take((size_t)Q * S * 4);
-  uint32_t* pfreq = ex && ex->per_query_extra > 0 ? (uint32_t*)carve.take((size_t)Q * (size_t)ex->per_query_extra) : nullptr;
-  if (ex)   // a prefix entry's frequency array: the place of its query in a chunk, then its slot
-    for (int64_t i = 0; i < ex->n_px; ++i)
-      ex->at32(ex->o_pxat)[i] = (ex->px_query[(size_t)i] % Q) * ex->slots + ex->at32(ex->o_slot)[ex->at32(ex->o_pxphr)[i]];
+  uint32_t* pfreq = prog.per_query_extra > 0 ? (uint32_t*)carve.take((size_t)Q * (size_t)prog.per_query_extra) : nullptr;
+  // a prefix entry's frequency array: the place of its query in a chunk, then its slot
+  for (int64_t i = 0; i < prog.n_px; ++i)
+    prog.at32(prog.o_pxat)[i] = (prog.px_query[(size_t)i] % Q) * prog.slots + prog.at32(prog.o_slot)[prog.at32(prog.o_pxphr)[i]];
   const TextIxP tp{tx.post_off.get(), tx.post_doc.get(), tx.post_tf.get(), tx.post_first.get(), tx.pos.get(), tx.doc_len.get()};
   // the programs (everything before the hit counts), then the idf once every nHit is known
   char* src = prog.blob.data();
@@ -1154,33 +1108,28 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
     src = pin;
   }
   NP_HIP(hipMemcpyAsync(d_prog, src, prog.o_nhit, hipMemcpyHostToDevice, st));
-  if (ex) {
-    NP_HIP(hipMemcpyAsync(d_prog + ex->o_phi, src + ex->o_phi, ex->o_pxhit - ex->o_phi, hipMemcpyHostToDevice, st));
-    NP_HIP(hipMemsetAsync(d_prog + ex->o_pxhit, 0, prog.bytes - ex->o_pxhit, st));
+  if (tree) {
+    NP_HIP(hipMemcpyAsync(d_prog + prog.o_phi, src + prog.o_phi, prog.o_pxhit - prog.o_phi, hipMemcpyHostToDevice, st));
+    NP_HIP(hipMemsetAsync(d_prog + prog.o_pxhit, 0, prog.bytes - prog.o_pxhit, st));
   }
+  // the programs as the kernels take them
+  auto d32 = [&](size_t off) { return (const int32_t*)(d_prog + off); };
+  unsigned long long* d_nhit = (unsigned long long*)(d_prog + prog.o_nhit);
   unsigned long long* h_nhit = (unsigned long long*)(src + prog.o_nhit);
   if (prog.n_items > 0) {
-    NP_HIP(hipMemsetAsync(d_prog + prog.o_nhit, 0, (size_t)prog.n_items * 8, st));
+    NP_HIP(hipMemsetAsync(d_nhit, 0, (size_t)prog.n_items * 8, st));
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (prog.max_item_df + TEXT_TPB - 1) / TEXT_TPB));
+    const auto hit_kernel = tree ? text_hit_kernel<true> : text_hit_kernel<false>;
     for (int64_t i0 = 0; i0 < prog.n_items; i0 += 65535) {   // (the items are a grid dimension)
-      const dim3 grid(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0));
-      if (ex) {
-        const TextExprHitP hp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
-                              (const int32_t*)(d_prog + ex->o_phi), (const int32_t*)(d_prog + prog.o_item) + i0,
-                              (unsigned long long*)(d_prog + prog.o_nhit) + i0};
-        text_expr_hit_kernel<<<grid, TEXT_TPB, 0, st>>>(hp);
-        continue;
-      }
-      const TextHitP hp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
-                        (const int32_t*)(d_prog + prog.o_item) + i0, (unsigned long long*)(d_prog + prog.o_nhit) + i0};
-      text_hit_kernel<<<grid, TEXT_TPB, 0, st>>>(hp);
+      const TextHitP hp{tp, d32(prog.o_ptok), d32(prog.o_terms), tree ? d32(prog.o_phi) : nullptr, d32(prog.o_item) + i0, d_nhit + i0};
+      hit_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0)), TEXT_TPB, 0, st>>>(hp);
     }
     NP_HIP(hipGetLastError());
     if (counts) {   // the shards' counts summed on the host, the same bytes on every rank
-      NP_TRY(counts->run((const unsigned long long*)(d_prog + prog.o_nhit), tx.n_rows, h_nhit));
+      NP_TRY(counts->run(d_nhit, tx.n_rows, h_nhit));
       NP_TRY(counts->verdict());
     } else {
-      NP_HIP(hipMemcpyAsync(h_nhit, d_prog + prog.o_nhit, (size_t)prog.n_items * 8, hipMemcpyDeviceToHost, st));
+      NP_HIP(hipMemcpyAsync(h_nhit, d_nhit, (size_t)prog.n_items * 8, hipMemcpyDeviceToHost, st));
       NP_HIP(hipStreamSynchronize(st));
     }
     const int32_t* item = (const int32_t*)(prog.blob.data() + prog.o_item);
@@ -1196,6 +1145,15 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
   if (visited) NP_HIP(hipMemsetAsync(ctr, 0, 8, st));
   const double avgdl = (double)tx.total_tokens / (double)tx.n_rows;
   int64_t px_visited = 0;   // postings the prefix pre-passes walk: counted on the host, with the scoring pass's in *visited
+  // What the call fixes of the kernels' arguments, once; the loops below set the rest: q0, s0, qrow of the scoring kernels (the
+  // last fields of TextScoreP) and Sn, n_prev and the outputs of the merge (0 and NULL here).  (The tree's part of a flat batch
+  // is never read.)
+  TextExprP xp{{tp, d32(prog.o_qphr), d32(prog.o_ptok), d32(prog.o_terms), (const double*)(d_prog + prog.o_idf), d32(prog.o_mode),
+                ix->n_docs, avgdl, keep, docbits, NW, S, list_keys, list_ids, list_cnt, visited ? ctr : nullptr},
+               d32(prog.o_phi), d32(prog.o_slot), d32(prog.o_qnode), d32(prog.o_nodes), pfreq, prog.stride, prog.slots};
+  TextScoreP& sp = xp.s;
+  TextMergeP mp{list_keys, list_ids, list_cnt, S, 0, keep, 0, best_keys, best_ids, best_cnt, top_k,
+                nullptr, nullptr, nullptr, nullptr, counts ? ix->doc_begin : 0};
   for (int q0 = 0; q0 < B; q0 += Q) {
     const int Qn = std::min(Q, B - q0);
     bool chunk_subsets = subsets;
@@ -1218,34 +1176,29 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
       if (chunk_subsets)
         NP_TRY(subset_doc_rows(ix, st, sub.d_ids, sub.d_off, sub.d_qsub + q0, sub.n, sub.total, lo, hi, Qn, NW, docbits, qrow));
     }
-    if (ex) {   // the chunk's single-token prefix phrases: frequencies, nHit, idf
+    if (tree) {   // the chunk's single-token prefix phrases: frequencies, nHit, idf
       int64_t x0 = 0, x1 = 0;
-      while (x0 < ex->n_px && ex->px_query[(size_t)x0] < q0) ++x0;
-      for (x1 = x0; x1 < ex->n_px && ex->px_query[(size_t)x1] < q0 + Qn; ++x1) {}
+      while (x0 < prog.n_px && prog.px_query[(size_t)x0] < q0) ++x0;
+      for (x1 = x0; x1 < prog.n_px && prog.px_query[(size_t)x1] < q0 + Qn; ++x1) {}
       if (x1 > x0 && ix->n_docs > 0) {
-        NP_HIP(hipMemsetAsync(pfreq, 0, (size_t)Qn * (size_t)ex->per_query_extra, st));
-        const int32_t* pxphr = ex->at32(ex->o_pxphr);
+        NP_HIP(hipMemsetAsync(pfreq, 0, (size_t)Qn * (size_t)prog.per_query_extra, st));
+        const int32_t* pxphr = prog.at32(prog.o_pxphr);
         int64_t longest = 0;
         for (int64_t x = x0; x < x1; ++x) {
-          const int32_t ph = pxphr[x], lo = ex->at32(prog.o_terms)[ex->at32(prog.o_ptok)[ph]], hi = ex->at32(ex->o_phi)[ph];
+          const int32_t ph = pxphr[x], lo = prog.at32(prog.o_terms)[prog.at32(prog.o_ptok)[ph]], hi = prog.at32(prog.o_phi)[ph];
           longest = std::max(longest, tx.h_post_off[(size_t)hi] - tx.h_post_off[(size_t)lo]);
           px_visited += tx.h_post_off[(size_t)hi] - tx.h_post_off[(size_t)lo];
         }
         const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (longest + TEXT_TPB - 1) / TEXT_TPB));
-        const TextPrefixP pp{tp, (const int32_t*)(d_prog + prog.o_ptok), (const int32_t*)(d_prog + prog.o_terms),
-                             (const int32_t*)(d_prog + ex->o_phi), (const int32_t*)(d_prog + ex->o_pxphr) + x0,
-                             (const int32_t*)(d_prog + ex->o_pxat) + x0, pfreq, ex->stride,
-                             (unsigned long long*)(d_prog + ex->o_pxhit)};
         for (int64_t i0 = x0; i0 < x1; i0 += 65535) {   // (the entries are a grid dimension)
-          TextPrefixP pi = pp;
-          pi.px_phr += i0 - x0;
-          pi.px_at += i0 - x0;
-          text_prefix_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, x1 - i0)), TEXT_TPB, 0, st>>>(pi);
+          const TextPrefixP pp{tp, d32(prog.o_ptok), d32(prog.o_terms), d32(prog.o_phi), d32(prog.o_pxphr) + i0, d32(prog.o_pxat) + i0,
+                               pfreq, prog.stride, (unsigned long long*)(d_prog + prog.o_pxhit)};
+          text_prefix_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, x1 - i0)), TEXT_TPB, 0, st>>>(pp);
         }
         NP_HIP(hipGetLastError());
-        const int32_t p0 = ex->at32(prog.o_qphr)[q0], p1 = ex->at32(prog.o_qphr)[q0 + Qn];
-        unsigned long long* h_px = (unsigned long long*)(src + ex->o_pxhit);
-        NP_HIP(hipMemcpyAsync(h_px + p0, d_prog + ex->o_pxhit + (size_t)p0 * 8, (size_t)(p1 - p0) * 8, hipMemcpyDeviceToHost, st));
+        const int32_t p0 = prog.at32(prog.o_qphr)[q0], p1 = prog.at32(prog.o_qphr)[q0 + Qn];
+        unsigned long long* h_px = (unsigned long long*)(src + prog.o_pxhit);
+        NP_HIP(hipMemcpyAsync(h_px + p0, d_prog + prog.o_pxhit + (size_t)p0 * 8, (size_t)(p1 - p0) * 8, hipMemcpyDeviceToHost, st));
         NP_HIP(hipStreamSynchronize(st));
         for (int64_t x = x0; x < x1; ++x) {
           const int32_t ph = pxphr[x];
@@ -1255,53 +1208,21 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
         NP_HIP(hipMemcpyAsync(d_prog + prog.o_idf + (size_t)p0 * 8, h_idf + p0, (size_t)(p1 - p0) * 8, hipMemcpyHostToDevice, st));
       }
     }
+    sp.q0 = q0;
+    sp.qrow = chunk_subsets ? qrow : nullptr;
+    mp.out_ids = d_out_ids + (int64_t)q0 * top_k;
+    mp.out_scores = d_out_scores + (int64_t)q0 * top_k;
+    mp.out_counts = d_out_counts + q0;
+    mp.out_keys = d_out_keys ? d_out_keys + (int64_t)q0 * top_k : nullptr;
     for (int64_t s0 = 0; s0 < n_slices; s0 += S) {
       const int64_t Sn = std::min(S, n_slices - s0);
-      TextScoreP sp;
-      sp.t = tp;
-      sp.q_phr = (const int32_t*)(d_prog + prog.o_qphr);
-      sp.phr_tok = (const int32_t*)(d_prog + prog.o_ptok);
-      sp.terms = (const int32_t*)(d_prog + prog.o_terms);
-      sp.idf = (const double*)(d_prog + prog.o_idf);
-      sp.mode = (const int32_t*)(d_prog + prog.o_mode);
-      sp.q0 = q0;
       sp.s0 = s0;
-      sp.n_docs = ix->n_docs;
-      sp.avgdl = avgdl;
-      sp.keep = keep;
-      sp.qrow = chunk_subsets ? qrow : nullptr;
-      sp.docbits = docbits;
-      sp.NW = NW;
-      sp.S = S;
-      sp.list_keys = list_keys;
-      sp.list_ids = list_ids;
-      sp.list_cnt = list_cnt;
-      sp.ctr = visited ? ctr : nullptr;
-      if (ix->n_docs > 0 && ex) {
-        const TextExprP xp{sp, (const int32_t*)(d_prog + ex->o_phi), (const int32_t*)(d_prog + ex->o_slot),
-                           (const int32_t*)(d_prog + ex->o_qnode), (const int32_t*)(d_prog + ex->o_nodes), pfreq,
-                           ex->stride, ex->slots};
+      if (ix->n_docs > 0 && tree)
         text_expr_kernel<<<dim3((unsigned)Sn, (unsigned)Qn), TEXT_TPB, 0, st>>>(xp);
-      } else if (ix->n_docs > 0) {
+      else if (ix->n_docs > 0)
         text_score_kernel<<<dim3((unsigned)Sn, (unsigned)Qn), TEXT_TPB, 0, st>>>(sp);
-      }
-      TextMergeP mp;
-      mp.list_keys = list_keys;
-      mp.list_ids = list_ids;
-      mp.list_cnt = list_cnt;
-      mp.S = S;
       mp.Sn = ix->n_docs > 0 ? Sn : 0;
-      mp.keep = keep;
       mp.n_prev = s0 > 0 ? 1 : 0;
-      mp.best_keys = best_keys;
-      mp.best_ids = best_ids;
-      mp.best_cnt = best_cnt;
-      mp.top_k = top_k;
-      mp.out_ids = d_out_ids + (int64_t)q0 * top_k;
-      mp.out_scores = d_out_scores + (int64_t)q0 * top_k;
-      mp.out_counts = d_out_counts + q0;
-      mp.out_keys = d_out_keys ? d_out_keys + (int64_t)q0 * top_k : nullptr;
-      mp.id_base = counts ? ix->doc_begin : 0;
       text_merge_kernel<<<(unsigned)Qn, TEXT_TPB, 0, st>>>(mp);
       NP_HIP(hipGetLastError());
     }
@@ -1334,7 +1255,7 @@ static int text_host(const np_index* ix, const np_text_query* queries, const np_
     return NP_ERR_INVALID_ARGUMENT;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  ExprProg prog;
+  TextProg prog;
   if (exprs) prog.build_expr(ix, exprs, B); else prog.build(ix, queries, B);
   DeviceGuard g(ix->device);
   ContextUse use;
@@ -1355,7 +1276,7 @@ static int text_host(const np_index* ix, const np_text_query* queries, const np_
   res.carve(carve);
   int64_t visited = 0;
   NP_TRY(text_run(ix, use, carve.at, (char*)pin + res.bytes(), plan, prog, top_k, sub, res.d_ids, res.d_sc, res.d_cnt,
-                  stats ? &visited : nullptr, nullptr, nullptr, exprs ? &prog : nullptr));
+                  stats ? &visited : nullptr, nullptr, nullptr));
   NP_TRY(res.fetch(pin, st));
   NP_TRY(use.end());
   NP_HIP(hipStreamSynchronize(st));
@@ -1404,21 +1325,7 @@ static int text_check_sharded_args(const np_index* ix, np_comm* c, const np_text
     set_error("Text search failed: NULL index / communicator / stream (the collectives need the caller's stream)");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  const char* why = "";
-  if (text_check_call(B, top_k, &why) != 0) {
-    set_error("Text search failed: %s (B=%d top_k=%d)", why, B, top_k);
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  if (B > 0 && !queries) {
-    set_error("Text search failed: NULL queries");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  char msg[240];
-  for (int q = 0; q < B; ++q)
-    if (text_check_query(&queries[q], q, (int64_t)1 << 31, msg, sizeof msg) != 0) {
-      set_error("Text search failed: %s", msg);
-      return NP_ERR_INVALID_ARGUMENT;
-    }
+  NP_TRY(text_check_batch((int64_t)1 << 31, queries, B, top_k, text_check_query));
   if (B > 0 && (!out_ids || !out_scores || !out_counts)) {
     set_error("Text search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
@@ -1692,7 +1599,8 @@ int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, 
   ContextUse use;
   NP_TRY(use.begin(ix, stream));
   NP_TRY(use.arena().reserve(text_arena_bytes(ix, plan, prog, top_k, sub.n > 0)));
-  return text_run(ix, use, use.arena().as<char>(), nullptr, plan, prog, top_k, sub, d_out_ids, d_out_scores, d_out_counts, nullptr);
+  return text_run(ix, use, use.arena().as<char>(), nullptr, plan, prog, top_k, sub, d_out_ids, d_out_scores, d_out_counts, nullptr, nullptr,
+                  nullptr);
 }
 
 int np_hip_fuse_device(const np_index* ix, int32_t mode, float alpha, int32_t top_k, int32_t B, const int64_t* d_sem_ids,
@@ -1827,7 +1735,7 @@ static int hybrid_host(const np_index* ix, const float* queries, const int32_t* 
   sem.top_k = fetch_k;
   const int top_k = grp ? grp->pool_k : params->top_k;   // of the fused list
   const auto t0 = std::chrono::steady_clock::now();
-  ExprProg prog;
+  TextProg prog;
   if (text_exprs) prog.build_expr(ix, text_exprs, B); else prog.build(ix, text_queries, B);
   DeviceGuard g(ix->device);
   ContextUse use;
@@ -1862,7 +1770,7 @@ static int hybrid_host(const np_index* ix, const float* queries, const int32_t* 
   NP_TRY(search_batch_in_use(ix, use, d_q, d_qoff, q_tok_offsets, B, dim, &sem, sub, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt));
   int64_t visited = 0;
   NP_TRY(text_run(ix, use, carve.at, (char*)pin + head, plan, prog, fetch_k, sub, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt,
-                  stats ? &visited : nullptr, nullptr, nullptr, text_exprs ? &prog : nullptr));
+                  stats ? &visited : nullptr, nullptr, nullptr));
   NP_TRY(fuse_launch(st, fusion, alpha, top_k, B, sem_l.d_ids, sem_l.d_sc, sem_l.d_cnt, fetch_k, kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, fetch_k,
                      res.d_ids, res.d_sc, res.d_cnt));
   if (grp) {

@@ -1,8 +1,8 @@
 """Tree keyword queries at the kernels' own constants: runs longer than the counting grid (the second grid stride of
-text_prefix_kernel and text_expr_hit_kernel), 64 frequency arrays per query in uneven batches cut into chunks of queries
+text_prefix_kernel and text_hit_kernel<true>), 64 frequency arrays per query in uneven batches cut into chunks of queries
 (px_at, the skipped pre-pass, text_plan halving a chunk for per_query_extra), text_expr_kernel's own sort with 4096 equal
 scores in a slice and ties carried across chunks of slices, and more than 65 535 counted phrases and prefix entries (the
-`i0 += 65535` loops around text_hit_kernel, text_expr_hit_kernel and text_prefix_kernel).  Needs a real MI355X.
+`i0 += 65535` loops around text_hit_kernel<false>, <true> and text_prefix_kernel).  Needs a real MI355X.
 
 The reference is tests/text_expr_restate.py: ids equal and f32 scores equal as uint32, without exception.  The corpora and
 trees come from tests/text_limit_shapes.py; tests/test_text_expr_limits_cpu.py pins the restatement to SQLite on the same
@@ -50,7 +50,7 @@ def long_run():
 @pytest.mark.parametrize("top_k", [10, CAP])
 def test_runs_longer_than_the_counting_grid(long_run, top_k):
     """The run of p* holds more postings than one stride of text_prefix_kernel's grid covers, the list of "h" more than one
-    of text_expr_hit_kernel's.  The documents of "pz" have all their postings of the run behind the first stride: without
+    of text_hit_kernel<true>'s.  The documents of "pz" have all their postings of the run behind the first stride: without
     the second one they are no match and nHit, so every score, changes; under the subsets the ranking is made of documents
     from both sides of the stride."""
     grid, n, data, hx, rs, named, exprs, scores, subsets, postings = long_run
@@ -350,7 +350,7 @@ def entry_65535(lists):
 
 
 def test_more_than_65535_counted_phrases_in_a_call(wide):
-    """1100 queries of 60 two-word phrases are 66 000 counted phrases: text_hit_kernel (flat) and text_expr_hit_kernel
+    """1100 queries of 60 two-word phrases are 66 000 counted phrases: text_hit_kernel<false> (flat) and text_hit_kernel<true>
     (trees; with a prefix range at every phrase's end) take them as a grid dimension in two launches, the second one offset
     by 65 535 in item_phr and nhit.  The phrases on the two sides of that place have different nHit."""
     n, data, rs, a = wide

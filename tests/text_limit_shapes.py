@@ -127,7 +127,7 @@ def pair_bytes(top_k):
 
 
 def per_query_bytes(n_docs, top_k, subsets=False, slots=0):
-    """text_per_query + ExprProg::per_query_extra: the best-so-far list, the subset's bitmap, `slots` frequency arrays."""
+    """text_per_query + TextProg::per_query_extra: the best-so-far list, the subset's bitmap, `slots` frequency arrays."""
     nw = max((n_docs + 31) // 32, 1)
     stride = (max(n_docs, 1) + 63) // 64 * 64
     return up256(top_k * 8) + up256(top_k * 4) + 8 + (up256(nw * 4) if subsets else 0) + slots * stride * 4
@@ -176,7 +176,7 @@ def chained(op, leaves):
 
 
 def n_arrays(expr):
-    """Frequency arrays a tree owns: its single-token phrases that end in a prefix (ExprProg::build_expr)."""
+    """Frequency arrays a tree owns: its single-token phrases that end in a prefix (TextProg::build_expr)."""
     return sum(1 for p, hi in zip(expr.phrases(), expr.prefix_hi().tolist()) if hi != 0 and len(p) == 1)
 
 
