@@ -1211,6 +1211,56 @@ int np_hip_index_update_append(const char* index_dir, const float* embeddings, c
  * id shifts every entry by one and its posting lists no longer match its codes; here delete([-1, 3]) equals delete([3]). */
 int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n_ids, int64_t* out_deleted);
 
+/* ---- append to a RESIDENT index (np_index.hip) ------------------------------------------------------------------------
+ * np_hip_index_update / _update_append rewrite the directory; np_hip_index_append brings a handle that is already in HBM up to
+ * date without reading the index again: its cost follows the appended tokens plus one pass over the posting lists and the
+ * codes, not the residuals.
+ *
+ * Append n_docs documents (ids num_documents .. num_documents + n_docs - 1) to a resident, unsharded handle.
+ * doc_lengths [n_docs]; codes i64 [sum lengths] in [0, K); residuals u8 [sum lengths, dim*nbits/8] in FILE geometry
+ * (what np_hip_encode_tokens returns and {i}.residuals.npy holds).  Posting list c gains, ascending, the new documents
+ * that hold code c (update_index, update.rs:771-1120, for lists that ascend).
+ *
+ * Afterwards the handle equals one freshly opened on the resulting index (np_hip_index_from_arrays on the concatenated
+ * arrays, np_hip_index_open on the directory np_hip_index_update_append wrote): np_hip_index_export, np_hip_index_info
+ * (but device_bytes / workspace_bytes) and every search entry return the same bytes.  avg_doclen becomes (old_avg * old_n +
+ * new_tokens) / n in f64, the expression the directory update writes; a handle made from arrays, which has no stored figure,
+ * keeps reporting tokens / documents.  n_docs == 0 changes nothing.
+ *
+ * Refused with NP_ERR_INVALID_ARGUMENT or NP_ERR_SHAPE, the argument named, before any allocation or launch, the handle
+ * answering as it did: a sharded handle; a handle whose posting lists do not ascend (only such lists grow at their end); a
+ * negative length; a code outside [0, K); totals beyond the open path's limits (2^31 documents -- and, found once the new
+ * documents' distinct codes are counted, the 40-bit list offset and the 32-bit overflow index: refused then, the handle
+ * unchanged all the same).  Not covered: centroid expansion (K changes) and delete (ids are re-sequenced) -- reload.
+ *
+ * Attachments: metadata columns, the keyword index and the groups are DROPPED, as a reload leaves a handle: their rows no
+ * longer cover the documents.  np_hip_index_set_columns / _set_text / _set_groups attach the grown ones.
+ *
+ * Memory: capacity grows first and commits nothing.  Without a reservation every per-token array (codes, residuals, inverse
+ * norms) grows by allocate, copy device to device, free -- one array at a time, so the peak is the LARGEST ARRAY TWICE (the
+ * residuals: 128 bytes of the ~145 per token at dim 128, 4 bits).  On a device that full, reserve at open time
+ * (np_hip_index_reserve right after the open: later appends within the reservation move no per-token array) or reload.  The
+ * derived arrays that are laid out again -- distinct-code blocks, posting lists, range table -- are allocated BESIDE the old
+ * ones and swapped in when nothing can fail any more: NP_ERR_OUT_OF_MEMORY leaves the handle unchanged (its capacity may
+ * have grown).
+ *
+ * Concurrency: append and reserve check out EVERY context of the handle's pool: calls that run finish on the index as it
+ * was, calls that arrive wait, nobody observes a half-grown handle.  The entries that read the handle outside a context are
+ * registered from their first line to their last and waited for in the same way: np_hip_decompress_documents (it reads the
+ * token arrays an unreserved append frees) and every entry that checks columns, keyword index or groups before it takes a
+ * context (np_hip_filter_eval, np_hip_text_match, the _filtered, text, hybrid, grouped and collapse entries) -- beside an append
+ * such a call answers from the attachments it checked, or gets the error of a handle without them, never a handle that
+ * changed under it.  What may NOT run beside append or reserve, as before this call existed: np_hip_index_export,
+ * np_hip_index_set_columns, _set_column_text, _set_text and _set_groups (they change the handle themselves and need
+ * exclusive access), np_hip_index_close, and the sharded entries (a sharded handle is refused anyway).  A context between np_hip_search_phase_a and
+ * np_hip_search_end counts as running: end such calls first -- an append from the thread that holds one waits for itself.
+ * NP_APPEND_TRACE=1 prints the stages' seconds to stderr (tools/append_time.py reads them). */
+int np_hip_index_append(np_index* index, const int64_t* doc_lengths, int64_t n_docs,
+                        const int64_t* codes, const uint8_t* residuals);
+/* Room for this many MORE documents / tokens, so that later appends move no per-token array. */
+int np_hip_index_reserve(np_index* index, int64_t extra_docs, int64_t extra_tokens);
+int np_hip_index_capacity(const np_index* index, int64_t* docs, int64_t* tokens);   /* allocated, not used */
+
 /* ---- token pooling: pool_document_embeddings (np_pool.hip) --------------------------------------------------------------
  * next-plaid-onnx pools every document before it reaches the index (src/lib.rs:1632-1643 pool_document_embeddings ->
  * :2249-2317 pool_embeddings_hierarchical -> hierarchy.rs:599-653 pdist_cosine, :128-284 Ward linkage by nearest-neighbour

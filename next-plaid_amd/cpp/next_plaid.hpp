@@ -387,6 +387,120 @@ struct TextIndexSpan {
   int64_t n_rows;
 };
 
+// ---- what MmapIndex::append reads back from the directory an update_append wrote -----------------------------------------
+namespace detail {
+inline std::string read_file(const std::string& path) {
+  std::FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) throw Error(NP_ERR_IO, ("IO error: cannot open " + path).c_str());
+  std::string out;
+  char buf[1 << 16];
+  size_t n;
+  while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
+  std::fclose(f);
+  return out;
+}
+// "key": <integer> of a JSON object the library wrote (metadata.json)
+inline int64_t json_int(const std::string& j, const char* key, const std::string& path) {
+  const std::string k = std::string("\"") + key + "\"";
+  size_t at = j.find(k);
+  if (at != std::string::npos) at = j.find(':', at + k.size());
+  if (at == std::string::npos) throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: no \"" + std::string(key) + "\" in " + path).c_str());
+  return std::strtoll(j.c_str() + at + 1, nullptr, 10);
+}
+// a JSON list of integers (doclens.N.json)
+inline std::vector<int64_t> json_ints(const std::string& j) {
+  std::vector<int64_t> out;
+  const char* p = j.c_str();
+  while (*p) {
+    if (*p == '-' || (*p >= '0' && *p <= '9')) {
+      char* e = nullptr;
+      out.push_back(std::strtoll(p, &e, 10));
+      p = e;
+    } else {
+      ++p;
+    }
+  }
+  return out;
+}
+// the last n_rows rows of an NPY v1 / v2 array of the given dtype (C order); *cols = entries per row (1 for rank 1)
+inline std::string npy_tail(const std::string& path, const char* descr, size_t item, int64_t n_rows, int64_t* cols) {
+  // only the header and the tail are read: a chunk of 50 000 documents holds gigabytes of residuals
+  struct File {
+    std::FILE* f;
+    ~File() {
+      if (f) std::fclose(f);
+    }
+  } file{std::fopen(path.c_str(), "rb")};
+  if (!file.f) throw Error(NP_ERR_IO, ("IO error: cannot open " + path).c_str());
+  unsigned char b[12] = {};
+  if (std::fread(b, 1, 12, file.f) != 12 || std::memcmp(b, "\x93NUMPY", 6) != 0)
+    throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: " + path + " is not an NPY file").c_str());
+  const bool v2 = b[6] >= 2;
+  const size_t hl = v2 ? (size_t)b[8] | (size_t)b[9] << 8 | (size_t)b[10] << 16 | (size_t)b[11] << 24 : (size_t)b[8] | (size_t)b[9] << 8;
+  const size_t h0 = v2 ? 12 : 10;
+  std::string h(hl, '\0');
+  if (hl > ((size_t)1 << 24) || std::fseek(file.f, (long)h0, SEEK_SET) != 0 || std::fread(&h[0], 1, hl, file.f) != hl)
+    throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: " + path + " has a truncated header").c_str());
+  size_t sh = h.find("'shape'");
+  if (h.find(descr) == std::string::npos || h.find("'fortran_order': False") == std::string::npos || sh == std::string::npos)
+    throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: " + path + " is not a C-order " + descr + " array").c_str());
+  const std::vector<int64_t> shape = json_ints(h.substr(h.find('(', sh), h.find(')', sh) - h.find('(', sh)));
+  const int64_t rows = shape.empty() ? 0 : shape[0];
+  *cols = shape.size() > 1 ? shape[1] : 1;
+  const size_t row = (size_t)*cols * item;
+  std::string tail((size_t)std::max<int64_t>(n_rows, 0) * row, '\0');
+  if (n_rows > rows || std::fseek(file.f, (long)(h0 + hl + (size_t)(rows - n_rows) * row), SEEK_SET) != 0 ||
+      (!tail.empty() && std::fread(&tail[0], 1, tail.size(), file.f) != tail.size()))
+    throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: " + path + " holds fewer rows than its directory counts").c_str());
+  return tail;
+}
+struct DirCounts {
+  int64_t documents = 0, embeddings = 0, chunks = 0;
+};
+inline DirCounts dir_counts(const std::string& dir) {
+  const std::string p = dir + "/metadata.json", j = read_file(p);
+  return DirCounts{json_int(j, "num_documents", p), json_int(j, "num_embeddings", p), json_int(j, "num_chunks", p)};
+}
+// The documents a directory holds beyond `before`, as update_index wrote them: the tail of its last chunks (it appends to the
+// last chunk or adds chunks, update.rs:771-1120)
+struct AppendedTokens {
+  std::vector<int64_t> doc_lengths, codes;
+  std::vector<uint8_t> residuals;
+};
+inline AppendedTokens appended_tokens(const std::string& dir, const DirCounts& before) {
+  const DirCounts now = dir_counts(dir);
+  const int64_t n_new = now.documents - before.documents, t_new = now.embeddings - before.embeddings;
+  AppendedTokens out;
+  std::vector<std::vector<int64_t>> dl_parts;   // per chunk, the last chunk first: joined once below
+  std::vector<std::string> cd_parts, rs_parts;
+  int64_t have_d = 0, have_t = 0;
+  for (int64_t c = now.chunks - 1; c >= 0 && have_d < n_new; --c) {
+    const std::string stem = dir + "/" + std::to_string((long long)c);
+    const std::vector<int64_t> dl = json_ints(read_file(dir + "/doclens." + std::to_string((long long)c) + ".json"));
+    const int64_t take_d = std::min<int64_t>(n_new - have_d, (int64_t)dl.size());
+    int64_t take_t = 0, cols = 0;
+    for (int64_t d = (int64_t)dl.size() - take_d; d < (int64_t)dl.size(); ++d) take_t += dl[(size_t)d];
+    dl_parts.emplace_back(dl.end() - take_d, dl.end());
+    cd_parts.push_back(npy_tail(stem + ".codes.npy", "<i8", 8, take_t, &cols));
+    rs_parts.push_back(npy_tail(stem + ".residuals.npy", "|u1", 1, take_t, &cols));
+    have_d += take_d;
+    have_t += take_t;
+  }
+  out.codes.resize((size_t)have_t);
+  size_t at_c = 0;
+  for (size_t i = dl_parts.size(); i-- > 0;) {
+    out.doc_lengths.insert(out.doc_lengths.end(), dl_parts[i].begin(), dl_parts[i].end());
+    if (!cd_parts[i].empty()) std::memcpy((char*)out.codes.data() + at_c, cd_parts[i].data(), cd_parts[i].size());
+    at_c += cd_parts[i].size();
+    out.residuals.insert(out.residuals.end(), rs_parts[i].begin(), rs_parts[i].end());
+  }
+  if (have_d != n_new || have_t != t_new)
+    throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: the chunk files of " + dir + " hold " + std::to_string(have_d) + " new documents / " +
+                                    std::to_string(have_t) + " tokens, metadata.json counts " + std::to_string(n_new) + " / " + std::to_string(t_new)).c_str());
+  return out;
+}
+}  // namespace detail
+
 class MmapIndex {
  public:
   // MmapIndex::create_with_kmeans (index.rs:927-967): k-means and codec training on the GPU, the crate's file set written
@@ -457,6 +571,53 @@ class MmapIndex {
     check(np_hip_index_update_append(index_path.c_str(), docs.embeddings, docs.doc_lengths.data(),
                                      (int64_t)docs.doc_lengths.size(), (int32_t)docs.dim, &c, device, &r));
     return update_ids(r, docs.doc_lengths.size());
+  }
+  // ---- append to the RESIDENT index (np_hip_index_append) -- where update() reloads the whole index, these cost the new
+  // documents plus one pass over the posting lists, and searches on other threads go on meanwhile (the running ones finish on
+  // the old index).  The handle then equals one freshly opened on the grown index; columns, keyword index and groups are
+  // dropped, as reload() leaves a handle.  Unsharded handles with ascending posting lists (what this library and the crate
+  // write); centroid expansion and delete still take update() / delete_documents() + reload().
+  // Documents already encoded (codes in [0, K), residuals [tokens][dim * nbits / 8] as np_hip_encode_tokens returns them):
+  std::vector<int64_t> append_arrays(const std::vector<int64_t>& doc_lengths, const int64_t* codes, const uint8_t* residuals) {
+    require_device("append_arrays");
+    const int64_t first = info_.num_documents;
+    check(np_hip_index_append(h_, doc_lengths.data(), (int64_t)doc_lengths.size(), codes, residuals));
+    check(np_hip_index_info(h_, &info_));
+    std::vector<int64_t> ids(doc_lengths.size());
+    for (size_t i = 0; i < ids.size(); ++i) ids[i] = first + (int64_t)i;
+    return ids;
+  }
+  // update_append on the handle's directory AND on the handle: the documents are encoded once, by np_hip_index_update_append,
+  // and the codes and residuals it wrote to the chunk files are what np_hip_index_append gets
+  std::vector<int64_t> append(const Documents& docs, const UpdateConfig& cfg = {}, int device = 0, np_update_report* report = nullptr) {
+    require_device("append");
+    // whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with its
+    // directory, and (an append of no documents runs the library's checks of the handle: shards, list order)
+    const detail::DirCounts before = detail::dir_counts(path);
+    if (before.documents != info_.num_documents)
+      throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the handle is not current with its directory: reload()");
+    check(np_hip_index_append(h_, nullptr, 0, nullptr, nullptr));
+    const np_update_config c = cfg.c();
+    np_update_report r{};
+    check(np_hip_index_update_append(path.c_str(), docs.embeddings, docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(),
+                                     (int32_t)docs.dim, &c, device, &r));
+    if (report) *report = r;
+    const detail::AppendedTokens t = detail::appended_tokens(path, before);
+    (void)append_arrays(t.doc_lengths, t.codes.data(), t.residuals.data());
+    return update_ids(r, docs.doc_lengths.size());
+  }
+  // room for this many MORE documents / tokens, so that later appends move no per-token array (without it every array grows
+  // by allocate, copy, free: a peak of the largest array twice).  A service reserves right after load()
+  void reserve(int64_t extra_docs, int64_t extra_tokens) {
+    require_device("reserve");
+    check(np_hip_index_reserve(h_, extra_docs, extra_tokens));
+  }
+  // (documents, tokens) the handle's arrays are allocated for
+  std::pair<int64_t, int64_t> capacity() const {
+    require_device("capacity");
+    std::pair<int64_t, int64_t> c{0, 0};
+    check(np_hip_index_capacity(h_, &c.first, &c.second));
+    return c;
   }
   // MmapIndex::update_or_create (index.rs:1644-1673): created when metadata.json is absent, ids 0..n then
   static MmapIndex update_or_create(const Documents& docs, const std::string& index_path, std::vector<int64_t>* ids,

@@ -456,6 +456,7 @@ extern "C" {
 int np_hip_filter_eval(const np_index* ix, const np_filter* filters, int32_t n_filters, int64_t* out_ids, int64_t ids_capacity,
                        int64_t* out_offsets) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   NP_TRY(filter_check_call(ix, filters, n_filters, nullptr, 0, false));
   if (!out_offsets) {
     set_error("Filter failed: out_offsets is NULL");

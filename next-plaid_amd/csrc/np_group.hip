@@ -305,6 +305,7 @@ int np_hip_collapse_device(const np_index* ix, int32_t top_k, int32_t group_size
                            float* d_out_scores, int32_t* d_out_group, int32_t* d_out_members, int32_t* d_out_total,
                            int32_t* d_out_counts, void* stream) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   NP_TRY(collapse_check(ix, top_k, group_size, B, stride));
   if (B == 0) return NP_OK;
   if (!d_ids || !d_counts || !d_out_ids || (d_scores && !d_out_scores) || !d_out_group || !d_out_members || !d_out_total ||
@@ -323,6 +324,7 @@ int np_hip_collapse(const np_index* ix, int32_t top_k, int32_t group_size, int32
                     const int32_t* counts, int32_t stride, int64_t* out_ids, float* out_scores, int32_t* out_group,
                     int32_t* out_members, int32_t* out_total, int32_t* out_counts) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   NP_TRY(collapse_check(ix, top_k, group_size, B, stride));
   if (B == 0) return NP_OK;
   if (!ids || !counts || !out_ids || (scores && !out_scores) || !out_group || !out_members || !out_total || !out_counts) {
@@ -374,6 +376,7 @@ int np_hip_search_batch_grouped(const np_index* ix, const float* queries, const 
                                 int32_t pool_k, int32_t group_size, int64_t* out_ids, float* out_scores, int32_t* out_group,
                                 int32_t* out_members, int32_t* out_total, int32_t* out_counts, np_stats* stats) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   if (stats) memset(stats, 0, sizeof *stats);
   if (!ix || !params) {
     set_error("Search failed: NULL index or params");

@@ -429,8 +429,10 @@ __global__ void __launch_bounds__(256) sort_doc_tokens_kernel(const int64_t* __r
   }
 }
 
-static int permute_tokens(const DeviceIndex* ix, int to_sorted) {
-  if (ix->n_docs == 0 || ix->T == 0 || (ix->pd & 3)) return NP_OK;
+// documents [doc0, doc1) only: sorting a sorted document again would overwrite its tok_pos with the identity, so an append
+// (np_hip_index_append) sorts the new documents and leaves the old ones alone
+static int permute_tokens(const DeviceIndex* ix, int to_sorted, int64_t doc0, int64_t doc1) {
+  if (doc1 <= doc0 || (ix->pd & 3)) return NP_OK;
   const size_t lds = (size_t)NP_SORT_MAX * 8 + (size_t)NP_SORT_MAX * ix->pd;
   if (lds > 48 * 1024) {
     NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sort_doc_tokens_kernel<uint16_t>),
@@ -438,8 +440,8 @@ static int permute_tokens(const DeviceIndex* ix, int to_sorted) {
     NP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sort_doc_tokens_kernel<uint32_t>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
-  for (int64_t d0 = 0; d0 < ix->n_docs; d0 += (int64_t)1 << 30) {
-    const int64_t n = std::min<int64_t>((int64_t)1 << 30, ix->n_docs - d0);
+  for (int64_t d0 = doc0; d0 < doc1; d0 += (int64_t)1 << 30) {
+    const int64_t n = std::min<int64_t>((int64_t)1 << 30, doc1 - d0);
     if (ix->code_wide)
       sort_doc_tokens_kernel<uint32_t><<<(unsigned)n, 256, lds>>>(ix->d_doc_offsets.get() + d0, (uint32_t*)ix->d_codes.get(),
                                                                   ix->d_residuals.get(), ix->d_tok_pos.get(), ix->pd, to_sorted);
@@ -457,7 +459,7 @@ static int sort_tokens(DeviceIndex* ix) {
   // opt-in (NP_TOK_SORT=1): measured 1 % on S6 at 1M docs for 2 B/token of HBM, so the default keeps the on-disk order
   if (!(e && *e && atoi(e) != 0) || (ix->pd & 3)) return NP_OK;
   NP_TRY(ix->d_tok_pos.alloc((size_t)ix->T, &ix->device_bytes));
-  NP_TRY(permute_tokens(ix, 1));
+  NP_TRY(permute_tokens(ix, 1, 0, ix->n_docs));
   ix->tok_sorted = true;
   return NP_OK;
 }
@@ -556,13 +558,26 @@ __global__ void __launch_bounds__(256) ivf_cover_kernel(int64_t n_docs, const ui
   if (miss) *missing = 1;
 }
 
-static int ivf_covers_codes(const DeviceIndex* ix, bool* covers) {
+// the documents, their distinct-code lists and the posting lists that the coverage check and the range table are about: the
+// handle's own at open, the grown ones of an append before they are swapped in
+struct ListsView {
+  int64_t n_docs;
+  int ublock_stride;
+  const uint4* meta;
+  CodeArr ucodes;
+  const uint32_t* ivf;
+  const int64_t* ivf_off;
+};
+static ListsView lists_of(const DeviceIndex* ix) {
+  return ListsView{ix->n_docs, ix->ublock_stride, ix->d_doc_meta.get(), ix->ucodes(), ix->d_ivf.get(), ix->d_ivf_offsets.get()};
+}
+
+static int ivf_covers_codes(const ListsView& v, bool* covers) {
   *covers = false;
   DevPtr<int> d_missing;
   NP_TRY(d_missing.alloc(1));
   NP_HIP(hipMemset(d_missing.get(), 0, sizeof(int)));
-  ivf_cover_kernel<<<(unsigned)((ix->n_docs + 3) / 4), 256>>>(ix->n_docs, ix->d_doc_meta.get(), ix->ucodes(), ix->d_ivf.get(),
-                                                              ix->d_ivf_offsets.get(), d_missing.get());
+  ivf_cover_kernel<<<(unsigned)((v.n_docs + 3) / 4), 256>>>(v.n_docs, v.meta, v.ucodes, v.ivf, v.ivf_off, d_missing.get());
   NP_HIP(hipGetLastError());
   int missing = 1;
   NP_HIP(hipMemcpy(&missing, d_missing.get(), sizeof(int), hipMemcpyDeviceToHost));
@@ -570,23 +585,52 @@ static int ivf_covers_codes(const DeviceIndex* ix, bool* covers) {
   return NP_OK;
 }
 
-// lists_from_codes: the caller built the lists from the distinct codes (build_ivf_from_ucodes), so they cover them
-static int build_ivf_split(DeviceIndex* ix, bool lists_from_codes) {
-  ix->n_ranges = 0;
-  if (!ix->tune.s3_gain || !ix->tune.s4_planes || !ix->ivf_sorted || ix->n_docs <= 0 || ix->K <= 0 || ix->ublock_stride <= 0) return NP_OK;
-  const int R = (int)((ix->n_docs + NP_SPLIT_RANGE - 1) / NP_SPLIT_RANGE), R1 = R + 1;
+// The range table of posting lists: *split and *R (no table: empty and 0), and *cover where the coverage was looked at.
+// lists_cover: the caller knows that the lists hold every (document, distinct code) pair -- it built them from the distinct
+// codes (build_ivf_from_ucodes), or appended such pairs to lists that did (np_hip_index_append)
+static int make_ivf_split(const DeviceIndex* ix, const ListsView& v, bool lists_cover, DevPtr<uint32_t>* split, int* R, int* cover) {
+  *R = 0;
+  if (!ix->tune.s3_gain || !ix->tune.s4_planes || !ix->ivf_sorted || v.n_docs <= 0 || ix->K <= 0 || v.ublock_stride <= 0) return NP_OK;
+  const int R_all = (int)((v.n_docs + NP_SPLIT_RANGE - 1) / NP_SPLIT_RANGE), R1 = R_all + 1;
   const size_t n = (size_t)ix->K * (size_t)R1;
   if (n * 4 > ((size_t)2 << 30)) return NP_OK;   // a table beyond 2 GiB (K x n_docs both huge) is not worth its HBM: the level stays off
-  if (!lists_from_codes) {   // lists that miss a (document, code) pair: no table, so the level stays off (np_search.hip gain_possible)
-    bool covers = false;
-    NP_TRY(ivf_covers_codes(ix, &covers));
-    if (!covers) return NP_OK;
-  }
-  NP_TRY(ix->d_ivf_split.alloc(n, &ix->device_bytes));
-  ivf_split_kernel<<<(unsigned)((n + 255) / 256), 256>>>(ix->d_ivf.get(), ix->d_ivf_offsets.get(), ix->K, R1, ix->d_ivf_split.get());
+  bool covers = lists_cover;
+  if (!covers) NP_TRY(ivf_covers_codes(v, &covers));
+  *cover = covers ? 1 : 0;
+  if (!covers) return NP_OK;   // lists that miss a pair: no table, so the level stays off (np_search.hip gain_possible)
+  NP_TRY(split->alloc(n));
+  ivf_split_kernel<<<(unsigned)((n + 255) / 256), 256>>>(v.ivf, v.ivf_off, ix->K, R1, split->get());
   NP_HIP(hipGetLastError());
   NP_HIP(hipDeviceSynchronize());
+  *R = R_all;
+  return NP_OK;
+}
+
+static void install_ivf_split(DeviceIndex* ix, DevPtr<uint32_t>&& split, int R) {
+  ix->device_bytes = ix->device_bytes - ix->d_ivf_split.bytes() + split.bytes();
+  ix->d_ivf_split = std::move(split);
   ix->n_ranges = R;
+}
+
+static int build_ivf_split(DeviceIndex* ix, bool lists_cover) {
+  DevPtr<uint32_t> split;
+  int R = 0;
+  NP_TRY(make_ivf_split(ix, lists_of(ix), lists_cover, &split, &R, &ix->ivf_cover));
+  install_ivf_split(ix, std::move(split), R);
+  return NP_OK;
+}
+
+// the inverse norms of tokens [t0, t1) into the (allocated) d_inv_norm: every token is computed on its own, so a range gives
+// the same bits as the whole index does
+static int fill_inv_norm(DeviceIndex* ix, int64_t t0, int64_t t1) {
+  if (t1 > t0) {
+    const int64_t n = t1 - t0, nblk = (n + 255) / 256;
+    const CodeArr codes{ix->d_codes.get() + t0 * (int64_t)ix->code_bytes(), ix->code_wide};
+    inv_norm_kernel<<<(unsigned)nblk, 256>>>(n, ix->dim, ix->ldim, ix->nbits, ix->pd, ix->d_centroids.get(), ix->d_wlut.get(), codes,
+                                             ix->d_residuals.get() + t0 * ix->pd, ix->d_inv_norm.get() + t0);
+  }
+  NP_HIP(hipGetLastError());
+  NP_HIP(hipDeviceSynchronize());
   return NP_OK;
 }
 
@@ -596,14 +640,7 @@ static int build_inv_norm(DeviceIndex* ix) {
     return NP_ERR_INVALID_ARGUMENT;
   }
   NP_TRY(ix->d_inv_norm.alloc((size_t)ix->T, &ix->device_bytes));
-  if (ix->T > 0) {
-    const int64_t nblk = (ix->T + 255) / 256;
-    inv_norm_kernel<<<(unsigned)nblk, 256>>>(ix->T, ix->dim, ix->ldim, ix->nbits, ix->pd, ix->d_centroids.get(), ix->d_wlut.get(),
-                                             ix->codes(), ix->d_residuals.get(), ix->d_inv_norm.get());
-  }
-  NP_HIP(hipGetLastError());
-  NP_HIP(hipDeviceSynchronize());
-  return NP_OK;
+  return fill_inv_norm(ix, 0, ix->T);
 }
 
 // ---- derived: where each document's sorted distinct-code list crosses the eighths of the centroid range ----
@@ -643,9 +680,36 @@ __global__ void doc_meta_kernel(int64_t n_docs, const int64_t* __restrict__ doc_
   meta[d] = make_uint4((uint32_t)d, (uint32_t)ulen[d], (uint32_t)(o & 0xFFFFFFFFll), (uint32_t)((o >> 32) & 0xFF) | (dl << 8));
 }
 
+// The distinct-code structures of a handle (np_internal.h: d_ucodes, d_ulen, d_useg, d_doc_meta and what describes them),
+// built apart from it: an open installs them at once, an append (np_hip_index_append) builds those of the grown index beside
+// the ones that are serving and swaps them in when nothing can fail any more.  `bytes` = their share of device_bytes.
+struct Ucodes {
+  DevPtr<uint8_t> d_ucodes;
+  DevPtr<int32_t> d_ulen;
+  DevPtr<uint4> d_useg, d_doc_meta;
+  int64_t n_ucodes = 0;
+  int ublock_stride = 0, ublock_hdr = 0;
+  float ulen_mean = 0.f;
+  bool sliced_ok = false;
+  size_t bytes = 0;
+};
+
+static void install_ucodes(DeviceIndex* ix, Ucodes&& u) {
+  ix->device_bytes -= ix->d_ucodes.bytes() + ix->d_ulen.bytes() + ix->d_useg.bytes() + ix->d_doc_meta.bytes();
+  ix->device_bytes += u.bytes;
+  ix->d_ucodes = std::move(u.d_ucodes);
+  ix->d_ulen = std::move(u.d_ulen);
+  ix->d_useg = std::move(u.d_useg);
+  ix->d_doc_meta = std::move(u.d_doc_meta);
+  ix->n_ucodes = u.n_ucodes;
+  ix->ublock_stride = u.ublock_stride;
+  ix->ublock_hdr = u.ublock_hdr;
+  ix->ulen_mean = u.ulen_mean;
+  ix->sliced_ok = u.sliced_ok;
+}
+
 // block stride of the lists (ublock_stride / ublock_hdr) from a histogram of their lengths, and ulen_mean
-static int choose_ublock_stride(DeviceIndex* ix) {
-  const int64_t N = ix->n_docs;
+static int choose_ublock_stride(const DeviceIndex* ix, int64_t N, Ucodes* u) {
   // the smallest multiple of 16 bytes that holds the header and 99.9 % of the lists (at most the staging row)
   const int hdr = (int)(16 / ix->code_bytes());
   const int smax = ix->tune.s4_planes ? (ix->code_wide ? NP_UBLOCK_BIG_U32 : NP_UBLOCK_BIG_U16)
@@ -656,11 +720,11 @@ static int choose_ublock_stride(DeviceIndex* ix) {
     uint32_t h_hist[NP_ULEN_BINS];
     NP_TRY(d_hist.alloc(NP_ULEN_BINS));
     NP_HIP(hipMemset(d_hist.get(), 0, sizeof h_hist));
-    ulen_hist_kernel<<<(unsigned)std::min<int64_t>((N + 255) / 256, 1024), 256>>>(ix->d_ulen.get(), N, d_hist.get());
+    ulen_hist_kernel<<<(unsigned)std::min<int64_t>((N + 255) / 256, 1024), 256>>>(u->d_ulen.get(), N, d_hist.get());
     NP_HIP(hipMemcpy(h_hist, d_hist.get(), sizeof h_hist, hipMemcpyDeviceToHost));
     double usum = 0;
     for (int q2 = 0; q2 < NP_ULEN_BINS; ++q2) usum += (double)q2 * h_hist[q2];
-    ix->ulen_mean = (float)(usum / (double)N);
+    u->ulen_mean = (float)(usum / (double)N);
     const int64_t allow = N / 100;    // lists allowed to overflow (1 %: the filter re-reads only those)
     int64_t over = 0;
     int q = NP_ULEN_BINS - 1;
@@ -677,21 +741,20 @@ static int choose_ublock_stride(DeviceIndex* ix) {
   // fetched the next block's first 16 bytes the figures were 1.5, 2, 2.5, 3, 3.5, 4, 5: profiles/hot_block_lines.md).  The
   // metric corpus' 192-byte blocks sit at their two-line floor; a one-line block there needs coded lists.
   const int per64 = (int)(64 / ix->code_bytes());
-  ix->ublock_stride = std::max(per64, std::min(smax, (hdr + fit + per64 - 1) / per64 * per64));
-  ix->ublock_hdr = hdr;
+  u->ublock_stride = std::max(per64, std::min(smax, (hdr + fit + per64 - 1) / per64 * per64));
+  u->ublock_hdr = hdr;
   return NP_OK;
 }
 
 // inclusive scan of the overflow lists' sizes (lists longer than `fit`) into d_ovf [n_docs], and their total
-static int scan_overflow(const DeviceIndex* ix, int fit, DevPtr<int64_t>* d_ovf, int64_t* ovf_total) {
-  const int64_t N = ix->n_docs;
+static int scan_overflow(const int32_t* d_ulen, int64_t N, int fit, DevPtr<int64_t>* d_ovf, int64_t* ovf_total) {
   *ovf_total = 0;
   if (N == 0) return NP_OK;
   DevPtr<int64_t> d_pad;   // scan input; it and the scan's temp storage go before the lists are allocated
   DevPtr<uint8_t> d_temp;
   NP_TRY(d_pad.alloc((size_t)N));
   NP_TRY(d_ovf->alloc((size_t)N));
-  ulen_overflow_kernel<<<(unsigned)((N + 255) / 256), 256>>>(ix->d_ulen.get(), N, fit, d_pad.get());
+  ulen_overflow_kernel<<<(unsigned)((N + 255) / 256), 256>>>(d_ulen, N, fit, d_pad.get());
   size_t tb = 0;
   hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_pad.get(), d_ovf->get(), (int)N);
   if (e == hipSuccess) NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
@@ -704,27 +767,15 @@ static int scan_overflow(const DeviceIndex* ix, int fit, DevPtr<int64_t>* d_ovf,
   return NP_OK;
 }
 
-// d_uoff (list offsets, [n_docs + 1]) goes back to the caller: the IVF build of the synthetic path reads the lists through it
-static int build_unique_codes(DeviceIndex* ix, DevPtr<int64_t>* d_uoff) {
-  const int64_t N = ix->n_docs;
-  NP_TRY(ix->d_ulen.alloc((size_t)N, &ix->device_bytes));
-  NP_TRY(ix->d_useg.alloc((size_t)N, &ix->device_bytes));
-  NP_TRY(ix->d_doc_meta.alloc((size_t)N, &ix->device_bytes));
-  NP_TRY(d_uoff->alloc((size_t)N + 1));
-  NP_HIP(hipMemset(d_uoff->get(), 0, 8));
-  // pass 1: list lengths
-  for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
-    const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
-    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), nullptr, nullptr, ix->d_ulen.get() + d0);
+// the limits of a shard that the open path and an append share
+static int check_shard_docs(int64_t n_docs) {
+  if (n_docs >= ((int64_t)1 << 31)) {
+    set_error("Index load failed: a shard holds < 2^31 documents (got %lld); use more shards", (long long)n_docs);
+    return NP_ERR_INDEX_LOAD;
   }
-  NP_HIP(hipGetLastError());
-  NP_TRY(choose_ublock_stride(ix));
-  const int S = ix->ublock_stride, hdr = ix->ublock_hdr, fit = S - hdr;
-  const int64_t base_b = N * (int64_t)S;   // first entry of the overflow region
-  DevPtr<int64_t> d_ovf;                    // inclusive scan of the overflow sizes
-  int64_t ovf_total = 0;
-  NP_TRY(scan_overflow(ix, fit, &d_ovf, &ovf_total));
-  const int64_t total = base_b + ovf_total;
+  return NP_OK;
+}
+static int check_ucode_totals(int64_t total, int64_t ovf_total) {
   if (total >= ((int64_t)1 << 40)) {   // candidate records carry a 40-bit list offset
     set_error("Index load failed: %lld distinct-code list entries exceed the 40-bit list offset; use more shards",
               (long long)total);
@@ -735,34 +786,61 @@ static int build_unique_codes(DeviceIndex* ix, DevPtr<int64_t>* d_uoff) {
               (long long)ovf_total);
     return NP_ERR_INDEX_LOAD;
   }
-  ix->n_ucodes = total;
-  // pass 2: headers, then the lists (+8 entries: list readers fetch up to 8 bytes past a list's last code)
-  const size_t bytes = ((size_t)total + 8) * ix->code_bytes();
-  NP_TRY(ix->d_ucodes.alloc(bytes, &ix->device_bytes));
-  NP_HIP(hipMemset(ix->d_ucodes.get(), 0, bytes));
-  if (N > 0)
-    ublock_layout_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), ix->d_ulen.get(), d_ovf.get(), S, hdr,
-                                                               fit, base_b, ix->d_ucodes.get(), ix->code_wide, d_uoff->get());
+  return NP_OK;
+}
+
+// The distinct-code structures of the handle's first N documents (its n_docs at open; the grown count in an append, whose
+// doc offsets and codes are in place by then) into *u.  d_uoff (list offsets, [N + 1]) goes back to the caller: the IVF build
+// of the synthetic path and the posting-list merge of an append read the lists through it
+static int build_unique_codes(const DeviceIndex* ix, int64_t N, Ucodes* u, DevPtr<int64_t>* d_uoff) {
+  NP_TRY(u->d_ulen.alloc((size_t)N, &u->bytes));
+  NP_TRY(u->d_useg.alloc((size_t)N, &u->bytes));
+  NP_TRY(u->d_doc_meta.alloc((size_t)N, &u->bytes));
+  NP_TRY(d_uoff->alloc((size_t)N + 1));
+  NP_HIP(hipMemset(d_uoff->get(), 0, 8));
+  // pass 1: list lengths
   for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
     const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
-    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), ix->d_ucodes.get(), d_uoff->get() + d0,
-                                              ix->d_ulen.get() + d0);
+    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), nullptr, nullptr, u->d_ulen.get() + d0);
+  }
+  NP_HIP(hipGetLastError());
+  NP_TRY(choose_ublock_stride(ix, N, u));
+  const int S = u->ublock_stride, hdr = u->ublock_hdr, fit = S - hdr;
+  const int64_t base_b = N * (int64_t)S;   // first entry of the overflow region
+  DevPtr<int64_t> d_ovf;                    // inclusive scan of the overflow sizes
+  int64_t ovf_total = 0;
+  NP_TRY(scan_overflow(u->d_ulen.get(), N, fit, &d_ovf, &ovf_total));
+  const int64_t total = base_b + ovf_total;
+  NP_TRY(check_ucode_totals(total, ovf_total));
+  u->n_ucodes = total;
+  // pass 2: headers, then the lists (+8 entries: list readers fetch up to 8 bytes past a list's last code)
+  const size_t bytes = ((size_t)total + 8) * ix->code_bytes();
+  NP_TRY(u->d_ucodes.alloc(bytes, &u->bytes));
+  NP_HIP(hipMemset(u->d_ucodes.get(), 0, bytes));
+  if (N > 0)
+    ublock_layout_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), u->d_ulen.get(), d_ovf.get(), S, hdr,
+                                                               fit, base_b, u->d_ucodes.get(), ix->code_wide, d_uoff->get());
+  for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
+    const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
+    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), u->d_ucodes.get(), d_uoff->get() + d0,
+                                              u->d_ulen.get() + d0);
   }
   if (N > 0)
-    doc_meta_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(), ix->d_ulen.get(),
-                                                          ix->d_doc_meta.get());
+    doc_meta_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(), u->d_ulen.get(),
+                                                          u->d_doc_meta.get());
   NP_HIP(hipGetLastError());
-  ix->sliced_ok = false;
+  u->sliced_ok = false;
   if (N > 0) {
     DevPtr<int> d_bad;
     NP_TRY(d_bad.alloc(1));
     NP_HIP(hipMemset(d_bad.get(), 0, sizeof(int)));
     const uint32_t slice_w = (uint32_t)((ix->K + 7) / 8);
-    useg_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(), ix->ucodes(), ix->d_ulen.get(),
-                                                      slice_w, ix->d_useg.get(), d_bad.get());
+    useg_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(),
+                                                      CodeArr{u->d_ucodes.get(), ix->code_wide}, u->d_ulen.get(), slice_w,
+                                                      u->d_useg.get(), d_bad.get());
     int bad = 1;
     NP_HIP(hipMemcpy(&bad, d_bad.get(), sizeof(int), hipMemcpyDeviceToHost));
-    ix->sliced_ok = (bad == 0);
+    u->sliced_ok = (bad == 0);
   }
   NP_HIP(hipDeviceSynchronize());
   return NP_OK;
@@ -812,8 +890,11 @@ __global__ void __launch_bounds__(256) unpack_rows_kernel(const uint8_t* __restr
 
 // NP_OPEN_TRACE=1: seconds of each phase of an open to stderr (parse, token upload, posting lists, derived structures)
 struct OpenTrace {
+  const char* tag = "np open";
   bool on = getenv("NP_OPEN_TRACE") != nullptr;
   double t0 = now();
+  OpenTrace() = default;
+  OpenTrace(const char* env, const char* tag_) : tag(tag_), on(getenv(env) != nullptr) {}   // NP_APPEND_TRACE=1: an append's stages
   static double now() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -823,7 +904,7 @@ struct OpenTrace {
     if (!on) return;
     (void)hipDeviceSynchronize();
     const double t = now();
-    fprintf(stderr, "[np open] %-28s %8.3f s\n", what, t - t0);
+    fprintf(stderr, "[%s] %-28s %8.6f s\n", tag, what, t - t0);
     t0 = t;
   }
 };
@@ -843,10 +924,13 @@ struct Uploader {
   char* pin[NP_UP_SLOTS] = {};
   hipEvent_t done[NP_UP_SLOTS] = {};
   int next = 0;
-  int init() {
+  size_t piece = NP_UP_PIECE;
+  // piece_bytes: the largest piece the caller will fill (an append of a few documents pins kilobytes, not 3 x 128 MiB)
+  int init(size_t piece_bytes = NP_UP_PIECE) {
+    piece = std::min<size_t>(NP_UP_PIECE, (std::max<size_t>(piece_bytes, 1) + 4095) & ~(size_t)4095);
     NP_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (int i = 0; i < NP_UP_SLOTS; ++i) {
-      NP_HIP(hipHostMalloc((void**)&pin[i], NP_UP_PIECE, hipHostMallocDefault));
+      NP_HIP(hipHostMalloc((void**)&pin[i], piece, hipHostMallocDefault));
       NP_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
     }
     return NP_OK;
@@ -859,7 +943,7 @@ struct Uploader {
     }
     if (st) (void)hipStreamDestroy(st);
   }
-  // parallel copy of [src, src + bytes) into a pinned slot (bytes <= NP_UP_PIECE); returns the slot
+  // parallel copy of [src, src + bytes) into a pinned slot (bytes <= piece); returns the slot
   int fill(const void* src, size_t bytes, int* slot) {
     const int s = next;
     next = (next + 1) % NP_UP_SLOTS;
@@ -958,7 +1042,9 @@ static int build_derived(DeviceIndex* ix, bool lists_from_codes, OpenTrace& trac
   NP_TRY(sort_tokens(ix));
   {
     DevPtr<int64_t> d_uoff;
-    NP_TRY(build_unique_codes(ix, &d_uoff));
+    Ucodes u;
+    NP_TRY(build_unique_codes(ix, ix->n_docs, &u, &d_uoff));
+    install_ucodes(ix, std::move(u));
     trace.mark("distinct-code blocks");
     if (lists_from_codes) {
       NP_TRY(build_ivf_from_ucodes(ix, d_uoff.get()));
@@ -969,6 +1055,8 @@ static int build_derived(DeviceIndex* ix, bool lists_from_codes, OpenTrace& trac
   trace.mark("list coverage + range table");
   NP_TRY(build_inv_norm(ix));
   trace.mark("inverse norms");
+  ix->cap_docs = ix->n_docs;
+  ix->cap_tokens = ix->T;
   default_workspace(ix);
   return NP_OK;
 }
@@ -998,17 +1086,17 @@ static int doc_offsets_from_lengths(const HostIndex& h, DeviceIndex* ix, int64_t
   return NP_OK;
 }
 
-// the shard's tokens [tb, tb + T) of the host chunks -> d_codes (i64 -> u16 / u32, range-checked) and d_residuals,
-// pipelined through the Uploader
-static int upload_tokens(const HostIndex& h, DeviceIndex* ix, int64_t tb) {
-  const int64_t te = tb + ix->T;
+// tokens [tb, tb + n_tok) of the host chunks -> d_codes (i64 -> u16 / u32, range-checked) and d_residuals from token dst0 on,
+// pipelined through the Uploader.  An open sends the shard's T tokens to the arrays' start, an append the new ones behind them
+static int upload_tokens(const HostIndex& h, DeviceIndex* ix, int64_t tb, int64_t n_tok, int64_t dst0) {
+  const int64_t te = tb + n_tok;
   // device-side staging of raw pieces that need a kernel (i64 codes; residual rows in file geometry); declared before the
   // uploader, whose destructor waits for its stream, so that they outlive the work queued on them
   DevPtr<char> d_stage[NP_UP_SLOTS];
   DevPtr<long long> d_bad;
   Uploader up;
-  NP_TRY(up.init());
-  for (DevPtr<char>& st : d_stage) NP_TRY(st.alloc(NP_UP_PIECE));
+  NP_TRY(up.init((size_t)n_tok * (size_t)std::max(8, ix->lpd)));
+  for (DevPtr<char>& st : d_stage) NP_TRY(st.alloc(up.piece));
   NP_TRY(d_bad.alloc(2));
   NP_HIP(hipMemset(d_bad.get(), 0, 16));
   const bool repack = ix->pd != ix->lpd;
@@ -1017,14 +1105,14 @@ static int upload_tokens(const HostIndex& h, DeviceIndex* ix, int64_t tb) {
   for (const HostChunk& c : h.chunks) {
     const int64_t a = std::max(pos, tb), b = std::min(pos + c.n_tokens, te);
     // codes: raw i64 pieces, narrowed and range-checked on the device
-    const int64_t CP = (int64_t)(NP_UP_PIECE / 8);
+    const int64_t CP = (int64_t)(up.piece / 8);
     for (int64_t t0 = a; t0 < b; t0 += CP) {
       const int64_t n = std::min(CP, b - t0);
       int slot;
       NP_TRY(up.fill((const char*)c.codes + (t0 - pos) * 8, (size_t)n * 8, &slot));
       NP_TRY(up.send(slot, (size_t)n * 8, d_stage[slot].get(), [&](hipStream_t st) -> int {
         narrow_codes_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(
-            (const int64_t*)d_stage[slot].get(), n, ix->K, ix->d_codes.get() + (t0 - tb) * (int64_t)ix->code_bytes(), ix->code_wide,
+            (const int64_t*)d_stage[slot].get(), n, ix->K, ix->d_codes.get() + (dst0 + t0 - tb) * (int64_t)ix->code_bytes(), ix->code_wide,
             d_bad.get());
         NP_HIP(hipGetLastError());
         return (int)NP_OK;
@@ -1032,10 +1120,10 @@ static int upload_tokens(const HostIndex& h, DeviceIndex* ix, int64_t tb) {
     }
     // residuals: straight into place, or through the staging area + repack (file rows -> storage rows: zero-padded,
     // 1-bit buckets widened to 2-bit segments)
-    const int64_t RP = (int64_t)(NP_UP_PIECE / std::max(ix->lpd, 1));
+    const int64_t RP = std::max<int64_t>(1, (int64_t)(up.piece / std::max(ix->lpd, 1)));
     for (int64_t t0 = a; t0 < b; t0 += RP) {
       const int64_t n = std::min(RP, b - t0);
-      uint8_t* dst = ix->d_residuals.get() + (t0 - tb) * ix->pd;
+      uint8_t* dst = ix->d_residuals.get() + (dst0 + t0 - tb) * ix->pd;
       int slot;
       NP_TRY(up.fill(c.residuals + (t0 - pos) * ix->lpd, (size_t)n * ix->lpd, &slot));
       if (!repack) {
@@ -1167,17 +1255,14 @@ int build_device_index(const HostIndex& h, const np_open_opts* opts_in, DeviceIn
   NP_TRY(start_index(g, o, h.num_documents_total, &ix));
   ix->n_emb_total = h.num_embeddings_total;
   ix->avg_doclen = h.avg_doclen;
-  if (ix->n_docs >= ((int64_t)1 << 31)) {
-    set_error("Index load failed: a shard holds < 2^31 documents (got %lld); use more shards", (long long)ix->n_docs);
-    return NP_ERR_INDEX_LOAD;
-  }
+  NP_TRY(check_shard_docs(ix->n_docs));
   OpenTrace trace;
   NP_TRY(set_geometry(ix.get(), h.K, h.dim, h.nbits, false, h.centroids, h.bucket_weights));
   trace.mark("codec");
   int64_t tb = 0;
   NP_TRY(doc_offsets_from_lengths(h, ix.get(), &tb));
   NP_TRY(alloc_tokens(ix.get()));
-  NP_TRY(upload_tokens(h, ix.get(), tb));
+  NP_TRY(upload_tokens(h, ix.get(), tb, ix->T, 0));
   trace.mark("codes + residuals -> HBM");
   NP_TRY(build_posting_lists(h, ix.get()));
   trace.mark("posting lists");
@@ -1256,13 +1341,13 @@ __global__ void __launch_bounds__(256) synth_tokens_kernel(SynthP p, const int64
 __global__ void __launch_bounds__(256) ivf_emit_pairs_kernel(int64_t d0, int64_t d1, const int64_t* __restrict__ uoff,
                                                              CodeArr ucodes,
                                                              const int32_t* __restrict__ ulen,
-                                                             const int64_t* __restrict__ upfx /* inclusive */,
-                                                             int64_t seg_base, uint64_t* __restrict__ keys) {
+                                                             const int64_t* __restrict__ upfx /* inclusive, of documents pfx_d0 .. */,
+                                                             int64_t pfx_d0, int64_t seg_base, uint64_t* __restrict__ keys) {
   const int64_t d = d0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (d >= d1) return;
   const int n = ulen[d];
-  const int64_t pos = upfx[d] - n - seg_base;
+  const int64_t pos = upfx[d - pfx_d0] - n - seg_base;
   const int64_t off = uoff[d];
   for (int i = lane; i < n; i += 64) keys[pos + i] = ((uint64_t)ucodes[off + i] << 32) | (uint64_t)d;
 }
@@ -1356,7 +1441,7 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
       *n_out = n;
       if (n == 0) return NP_OK;
       ivf_emit_pairs_kernel<<<(unsigned)((d1 - d0 + 3) / 4), 256>>>(d0, d1, d_uoff, ix->ucodes(), ix->d_ulen.get(),
-                                                                   d_upfx.get(), base, d_k1.get());
+                                                                   d_upfx.get(), 0, base, d_k1.get());
       size_t tbs = tb;
       NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tbs, d_k1.get(), d_k2.get(), (int)n, 0, 32 + kbits));
       ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2.get(), n, K, d_start.get());
@@ -1395,6 +1480,331 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
   set_ivf_bound(ix, ioff.data());
   NP_HIP(hipDeviceSynchronize());
   ix->ivf_sorted = true;   // (code, document) pairs radix-sorted, ranges ascending: every list ascends
+  return NP_OK;
+}
+
+// ---- append to a resident index (np_hip_index_append) -----------------------------------------------------------------
+// New documents take the largest ids, so every per-token and per-document array only grows at its end and, the lists
+// ascending, posting list c only gains entries at its end.  The one array that is laid out again is d_ivf: K lists, each
+// growing at its tail.  With the new documents' (code, id) pairs sorted, start[c] = the pairs with a smaller code is at once
+// the exclusive scan of the per-list gains, so
+//   new_off[c] = old_off[c] + start[c];   old entry i of list c -> i + start[c];   pair j of code c -> old_off[c + 1] + j
+// and every entry of the new array has one source that scans alone decide: no atomics, no workgroup waits for another.
+__global__ void ivf_new_offsets_kernel(const int64_t* __restrict__ old_off, const int64_t* __restrict__ start, int64_t K,
+                                       int64_t* __restrict__ new_off) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c <= K) new_off[c] = old_off[c] + start[c];
+}
+
+// the list that holds entry o of the new array: the largest c' >= c with off[c'] <= o.  Needs off[c] <= o < off[K]; gallops from
+// c, since a thread's next entry lies in the same list or a near one (empty lists are stepped over: their offsets repeat)
+__device__ __forceinline__ int64_t ivf_list_of(const int64_t* __restrict__ off, int64_t K, int64_t c, int64_t o) {
+  int64_t lo = c, step = 1, hi = min(K, lo + step);
+  while (off[hi] <= o) {
+    lo = hi;
+    step <<= 1;
+    hi = min(K, lo + step);
+  }
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (off[mid] <= o) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The merge is a streaming move (4 bytes read and 4 written per entry; the offsets stay in the caches), balanced by ENTRIES:
+// a workgroup owns NP_MERGE_TILE consecutive entries of the NEW array whatever lists they belong to (list lengths are
+// Zipf-skewed: one thread per list would leave the longest to a single lane).  A thread owns 4 consecutive entries -- one
+// aligned 16-byte store -- and the threads of a wave consecutive quads, so inside a list segment a wave reads 1 KiB of the
+// old array (or 2 KiB of pairs) and writes 1 KiB, all contiguous.  A quad that lies inside the old part of one list -- nearly
+// all of them on long lists -- is one 16-byte load (4-byte aligned: the shift start[c] is any number of entries).  A thread
+// finds and loads its NP_MERGE_QUADS quads first and stores them afterwards, so that many loads are in flight per lane.
+#define NP_MERGE_TILE 4096
+#define NP_MERGE_QUADS (NP_MERGE_TILE / 1024)
+struct __attribute__((packed, aligned(4))) MergeQuad {
+  uint32_t v[4];
+};
+__global__ void __launch_bounds__(256) ivf_merge_kernel(const uint32_t* __restrict__ old_ivf, const int64_t* __restrict__ old_off,
+                                                        const uint64_t* __restrict__ pairs, const int64_t* __restrict__ start,
+                                                        const int64_t* __restrict__ new_off, int64_t K, int64_t total,
+                                                        uint32_t* __restrict__ out) {
+  __shared__ int64_t s_c0;
+  const int64_t o0 = (int64_t)blockIdx.x * NP_MERGE_TILE;   // < total: the grid covers [0, total)
+  if (threadIdx.x == 0) s_c0 = ivf_list_of(new_off, K, 0, o0);
+  __syncthreads();
+  int64_t c = s_c0;
+  MergeQuad q[NP_MERGE_QUADS];
+#pragma unroll
+  for (int it = 0; it < NP_MERGE_QUADS; ++it) {
+    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
+    q[it] = MergeQuad{{0u, 0u, 0u, 0u}};
+    if (o < total) {
+      const int n = (int)min((int64_t)4, total - o);
+      c = ivf_list_of(new_off, K, c, o);
+      int64_t b_new = new_off[c], e_new = new_off[c + 1], b_old = old_off[c], n_old = old_off[c + 1] - b_old, b_pair = start[c];
+      if (n == 4 && o + 4 <= b_new + n_old) {   // (b_new + n_old <= e_new)
+        q[it] = *reinterpret_cast<const MergeQuad*>(old_ivf + b_old + (o - b_new));
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k < n) {
+            const int64_t oo = o + k;
+            if (oo >= e_new) {
+              c = ivf_list_of(new_off, K, c, oo);
+              b_new = new_off[c], e_new = new_off[c + 1], b_old = old_off[c], n_old = old_off[c + 1] - b_old, b_pair = start[c];
+            }
+            const int64_t r = oo - b_new;
+            q[it].v[k] = r < n_old ? old_ivf[b_old + r] : (uint32_t)(pairs[b_pair + (r - n_old)] & 0xFFFFFFFFull);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NP_MERGE_QUADS; ++it) {
+    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
+    if (o + 4 <= total) {
+      *reinterpret_cast<uint4*>(out + o) = make_uint4(q[it].v[0], q[it].v[1], q[it].v[2], q[it].v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (o + k < total) out[o + k] = q[it].v[k];
+    }
+  }
+}
+
+// The posting lists of the handle with documents [N0, N1) added, from the distinct-code lists of the grown index (u, d_uoff):
+// *ivf / *ioff stay empty when the new documents hold no token (the lists are the handle's own then); h_ioff = the offsets.
+// raw_lists: a new document is longer than NP_UNIQ_MAX tokens, so its list is its codes as they are, duplicates included --
+// a posting list names a document once (index.rs:479-499), so equal pairs, adjacent once sorted, are dropped.
+static int merge_posting_lists(const DeviceIndex* ix, const Ucodes& u, const int64_t* d_uoff, int64_t N0, int64_t N1, bool raw_lists,
+                               DevPtr<uint32_t>* ivf, DevPtr<int64_t>* ioff, std::vector<int64_t>* h_ioff, int64_t* ivf_size,
+                               const OpenTrace& trace) {
+  const int64_t K = ix->K;
+  *ivf_size = ix->ivf_size;
+  DevPtr<int64_t> d_len64, d_upfx, d_start;
+  DevPtr<uint64_t> d_k1, d_k2;
+  DevPtr<uint8_t> d_temp;
+  // inclusive prefix of the NEW documents' list lengths: where each one's pairs go (nothing here is index-sized)
+  const int64_t n_new = N1 - N0;
+  NP_TRY(d_len64.alloc((size_t)n_new));
+  NP_TRY(d_upfx.alloc((size_t)n_new));
+  ulen_to_i64_kernel<<<(unsigned)((n_new + 255) / 256), 256>>>(u.d_ulen.get() + N0, n_new, d_len64.get());
+  size_t tb = 0;
+  NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_len64.get(), d_upfx.get(), (int)n_new));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, d_len64.get(), d_upfx.get(), (int)n_new));
+  int64_t P = 0;   // (code, document) pairs of the new documents
+  NP_HIP(hipMemcpy(&P, d_upfx.get() + (n_new - 1), 8, hipMemcpyDeviceToHost));
+  d_len64.reset();
+  d_temp.reset();
+  if (P == 0) return NP_OK;
+  if (P >= ((int64_t)1 << 31)) {   // one radix sort, as one document range of build_ivf_from_ucodes
+    set_error("np_hip_index_append: n_docs: the new documents hold %lld (code, doc) pairs, one call takes < 2^31", (long long)P);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  int kbits = 1;
+  while (((int64_t)1 << kbits) < K) ++kbits;
+  NP_TRY(d_k1.alloc((size_t)P));
+  NP_TRY(d_k2.alloc((size_t)P));
+  NP_TRY(d_start.alloc((size_t)K + 1));
+  ivf_emit_pairs_kernel<<<(unsigned)((N1 - N0 + 3) / 4), 256>>>(N0, N1, d_uoff, CodeArr{u.d_ucodes.get(), ix->code_wide},
+                                                               u.d_ulen.get(), d_upfx.get(), N0, 0, d_k1.get());
+  NP_HIP(hipGetLastError());
+  tb = 0;
+  NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
+  if (raw_lists) {
+    DevPtr<int64_t> d_n;
+    NP_TRY(d_n.alloc(1));
+    tb = 0;
+    NP_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
+    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+    NP_HIP(hipcub::DeviceSelect::Unique(d_temp.get(), tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
+    NP_HIP(hipMemcpy(&P, d_n.get(), 8, hipMemcpyDeviceToHost));
+    std::swap(d_k1, d_k2);   // d_k2 = the sorted pairs, each once
+  }
+  ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2.get(), P, K, d_start.get());
+  NP_HIP(hipGetLastError());
+  const int64_t total = ix->ivf_size + P;
+  NP_TRY(ioff->alloc((size_t)K + 1));
+  NP_TRY(ivf->alloc((size_t)total));   // the new array beside the old one: the merge reads the one and writes the other
+  ivf_new_offsets_kernel<<<(unsigned)((K + 256) / 256), 256>>>(ix->d_ivf_offsets.get(), d_start.get(), K, ioff->get());
+  hipEvent_t ev[2] = {nullptr, nullptr};   // NP_APPEND_TRACE: the merge kernel alone, for its bytes per second
+  if (trace.on && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[0], nullptr);
+  ivf_merge_kernel<<<(unsigned)((total + NP_MERGE_TILE - 1) / NP_MERGE_TILE), 256>>>(
+      ix->d_ivf.get(), ix->d_ivf_offsets.get(), d_k2.get(), d_start.get(), ioff->get(), K, total, ivf->get());
+  NP_HIP(hipGetLastError());
+  if (ev[0] && ev[1]) {
+    float ms = 0.f;
+    (void)hipEventRecord(ev[1], nullptr);
+    if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+      fprintf(stderr, "[%s] %-28s %8.6f s  %lld entries %lld new\n", trace.tag, "merge kernel", ms * 1e-3, (long long)total, (long long)P);
+  }
+  for (hipEvent_t e : ev)
+    if (e) (void)hipEventDestroy(e);
+  h_ioff->resize((size_t)K + 1);
+  NP_HIP(hipMemcpy(h_ioff->data(), ioff->get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
+  NP_HIP(hipDeviceSynchronize());
+  *ivf_size = total;
+  return NP_OK;
+}
+
+// every context of the handle's pool checked out (np_internal.h DeviceIndex::exclusive): running calls finish on the index as
+// it was, calls that arrive wait in acquire_context, and nobody sees a half-grown handle
+struct HoldContexts {
+  const DeviceIndex* ix;
+  explicit HoldContexts(const DeviceIndex* i) : ix(i) {
+    std::unique_lock<std::mutex> lk(ix->mu);
+    ix->cv.wait(lk, [&] { return !ix->exclusive; });
+    ix->exclusive = true;
+    ix->cv.wait(lk, [&] {   // the calls registered outside a context (IndexRead) end, then the contexts fall idle
+      if (ix->readers > 0) return false;
+      for (const Context* c : ix->contexts)
+        if (c->busy) return false;
+      return true;
+    });
+    for (Context* c : ix->contexts) c->busy = true;
+  }
+  ~HoldContexts() {
+    {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      for (Context* c : ix->contexts) c->busy = false;
+      ix->exclusive = false;
+    }
+    ix->cv.notify_all();
+  }
+};
+
+template <class T>
+static int grow_array(DeviceIndex* ix, DevPtr<T>& a, size_t used, size_t want) {
+  DevPtr<T> f;
+  NP_TRY(f.alloc(want));
+  if (used > 0) NP_HIP(hipMemcpy(f.get(), a.get(), used * sizeof(T), hipMemcpyDeviceToDevice));
+  ix->device_bytes = ix->device_bytes - a.bytes() + f.bytes();
+  a = std::move(f);   // frees the old array: one array at a time is held twice
+  return NP_OK;
+}
+
+// room for need_docs documents and need_tokens tokens in the arrays that only grow at their end.  A failed allocation leaves
+// every array that did not grow yet, and the capacities, as they were.
+static int grow_capacity(DeviceIndex* ix, int64_t need_docs, int64_t need_tokens) {
+  if (need_tokens > ix->cap_tokens) {
+    const size_t T = (size_t)ix->T, W = (size_t)need_tokens;
+    NP_TRY(grow_array(ix, ix->d_residuals, T * ix->pd, W * ix->pd));
+    NP_TRY(grow_array(ix, ix->d_codes, T * ix->code_bytes(), std::max<size_t>(W, 1) * ix->code_bytes()));
+    NP_TRY(grow_array(ix, ix->d_inv_norm, T, W));
+    if (ix->tok_sorted) NP_TRY(grow_array(ix, ix->d_tok_pos, T, W));
+    ix->cap_tokens = need_tokens;
+  }
+  if (need_docs > ix->cap_docs) {
+    NP_TRY(grow_array(ix, ix->d_doc_offsets, (size_t)ix->n_docs + 1, (size_t)need_docs + 1));
+    ix->cap_docs = need_docs;
+  }
+  return NP_OK;
+}
+
+// columns, keyword index and groups cover the documents the handle had: gone, as after a reload
+static void drop_attachments(DeviceIndex* ix) {
+  ix->columns.clear();
+  ix->d_coltab.reset();
+  ix->text = DeviceText();
+  ix->d_groups.reset();
+  ix->n_groups = 0;
+  ix->device_bytes -= ix->column_bytes + ix->coltext_bytes + ix->text_bytes + ix->group_bytes;
+  ix->column_bytes = ix->coltext_bytes = ix->text_bytes = ix->group_bytes = 0;
+}
+
+// a limit of the open path met by an append: the same check, reported as the append's argument
+static int as_append_argument(int rc, const char* arg) {
+  if (rc == NP_OK || rc == NP_ERR_OUT_OF_MEMORY || rc == NP_ERR_DEVICE_UNAVAILABLE) return rc;
+  const std::string msg = last_error();
+  set_error("np_hip_index_append: %s: %s", arg, msg.c_str());
+  return NP_ERR_INVALID_ARGUMENT;
+}
+
+static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, const int64_t* codes, const uint8_t* residuals,
+                            int64_t Tn, int64_t maxlen) {
+  HoldContexts hold(ix);
+  DeviceGuard g(ix->device);
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", ix->device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  const int64_t N0 = ix->n_docs, N1 = N0 + n, T0 = ix->T, T1 = T0 + Tn;
+  NP_TRY(as_append_argument(check_shard_docs(N1), "n_docs"));
+  NP_HIP(hipDeviceSynchronize());   // device-side calls that returned may still be running on their streams
+  OpenTrace trace("NP_APPEND_TRACE", "np append");
+  // 1. capacity first: commits nothing
+  NP_TRY(grow_capacity(ix, N1, T1));
+  trace.mark("grow");
+  // 2. the new documents behind the old ones -- outside what any kernel reads until the counts move -- and the per-token
+  //    stages over them alone
+  {
+    std::vector<int64_t> off((size_t)n);
+    int64_t t = T0;
+    for (int64_t d = 0; d < n; ++d) off[(size_t)d] = (t += lens[d]);
+    NP_HIP(hipMemcpy(ix->d_doc_offsets.get() + N0 + 1, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  if (Tn > 0) {
+    HostIndex h;
+    HostChunk c;
+    c.codes = codes;
+    c.residuals = residuals;
+    c.n_tokens = Tn;
+    h.chunks.push_back(c);
+    NP_TRY(as_append_argument(upload_tokens(h, ix, 0, Tn, T0), "codes"));
+    if (ix->tok_sorted) NP_TRY(permute_tokens(ix, 1, N0, N1));
+    NP_TRY(fill_inv_norm(ix, T0, T1));
+  }
+  trace.mark("upload + token stages");
+  // 3. the distinct-code structures of the grown index, beside the ones that serve
+  Ucodes u;
+  DevPtr<int64_t> d_uoff;
+  NP_TRY(as_append_argument(build_unique_codes(ix, N1, &u, &d_uoff), "n_docs"));
+  trace.mark("distinct-code rebuild");
+  // 4. the posting lists
+  DevPtr<uint32_t> ivf;
+  DevPtr<int64_t> ioff;
+  std::vector<int64_t> h_ioff;
+  int64_t ivf_size = 0;
+  NP_TRY(merge_posting_lists(ix, u, d_uoff.get(), N0, N1, maxlen > NP_UNIQ_MAX, &ivf, &ioff, &h_ioff, &ivf_size, trace));
+  d_uoff.reset();
+  trace.mark("posting-list merge");
+  // 5. their range table.  Lists that held every (document, code) pair still do: the new entries are such pairs
+  DevPtr<uint32_t> split;
+  int R = 0, cover = ix->ivf_cover;
+  const bool merged = ivf.get() != nullptr;
+  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide},
+                    merged ? ivf.get() : ix->d_ivf.get(), merged ? ioff.get() : ix->d_ivf_offsets.get()};
+  NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
+  trace.mark("range table");
+  // ---- nothing below can fail: the handle becomes the grown index ----
+  install_ucodes(ix, std::move(u));
+  if (merged) {
+    ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
+    ix->d_ivf = std::move(ivf);
+    ix->d_ivf_offsets = std::move(ioff);
+    ix->ivf_size = ivf_size;
+    set_ivf_bound(ix, h_ioff.data());
+  }
+  install_ivf_split(ix, std::move(split), R);
+  ix->ivf_cover = cover;
+  // (old_avg * old_n + new_tokens) / n, the expression the directory update writes (np_update.cpp); a handle made from arrays
+  // has no stored figure and reports tokens / documents, as a fresh one of the grown arrays does
+  ix->avg_doclen = ix->avg_from_counts ? (double)(ix->n_emb_total + Tn) / (double)N1
+                                       : (ix->avg_doclen * (double)ix->N_total + (double)Tn) / (double)N1;
+  ix->n_docs = ix->N_total = N1;
+  ix->T = T1;
+  ix->n_emb_total += Tn;
+  ix->max_doc_len = std::max(ix->max_doc_len, maxlen);
+  drop_attachments(ix);
+  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
+  ix->gain_run.store(0, std::memory_order_relaxed);
+  ix->gain_skip.store(0, std::memory_order_relaxed);
+  contexts_forget_index(ix);
   return NP_OK;
 }
 
@@ -1608,6 +2018,7 @@ int np_hip_index_from_arrays(const np_index_arrays* a, const np_open_opts* opts,
   h.avg_doclen = a->num_docs > 0 ? (double)c.n_tokens / (double)a->num_docs : 0.0;
   DeviceIndex* ix = nullptr;
   NP_TRY(build_device_index(h, opts, &ix));
+  ix->avg_from_counts = true;
   *out = static_cast<np_index*>(ix);
   return NP_OK;
 }
@@ -1620,6 +2031,7 @@ int np_hip_index_synth(const np_synth_spec* spec, const np_open_opts* opts, np_i
   }
   DeviceIndex* ix = nullptr;
   NP_TRY(synth_build(spec, opts, &ix));
+  ix->avg_from_counts = true;
   *out = static_cast<np_index*>(ix);
   return NP_OK;
 }
@@ -1658,11 +2070,11 @@ int np_hip_index_export(const np_index* ix, int64_t* doc_lengths, int64_t* codes
     const np_index* ix;
     bool active;
     ~Resort() {
-      if (active) (void)permute_tokens(ix, 1);
+      if (active) (void)permute_tokens(ix, 1, 0, ix->n_docs);
     }
   } resort{ix, false};
   if ((codes || residuals) && ix->tok_sorted && ix->T > 0) {
-    NP_TRY(permute_tokens(ix, 0));
+    NP_TRY(permute_tokens(ix, 0, 0, ix->n_docs));
     resort.active = true;
   }
   if (codes && ix->T > 0) {
@@ -1835,6 +2247,81 @@ int np_hip_index_probe_dir(const char* index_dir, np_info* out) {
   out->device_bytes = 0;
   out->device = -1;
   out->abi_version = NP_ABI_VERSION;
+  return NP_OK;
+}
+
+int np_hip_index_append(np_index* ix, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals) {
+  clear_error();
+  if (!ix) {
+    set_error("np_hip_index_append: index is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (ix->opts.shard_count > 1) {
+    set_error("np_hip_index_append: index is a shard (%d of %d): a sharded index is reloaded", ix->opts.shard_rank, ix->opts.shard_count);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (!ix->ivf_sorted) {
+    set_error("np_hip_index_append: index has posting lists that do not ascend: only such lists grow at their end");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (n_docs < 0 || (n_docs > 0 && !doc_lengths)) {
+    set_error("np_hip_index_append: %s", n_docs < 0 ? "n_docs is negative" : "doc_lengths is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (n_docs == 0) return NP_OK;
+  int64_t Tn = 0, maxlen = 0;
+  for (int64_t d = 0; d < n_docs; ++d) {
+    if (doc_lengths[d] < 0) {
+      set_error("np_hip_index_append: doc_lengths[%lld] is negative (%lld)", (long long)d, (long long)doc_lengths[d]);
+      return NP_ERR_SHAPE;
+    }
+    Tn += doc_lengths[d];
+    maxlen = std::max(maxlen, doc_lengths[d]);
+  }
+  if (Tn > 0 && (!codes || !residuals)) {
+    set_error("np_hip_index_append: %s is NULL", !codes ? "codes" : "residuals");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (int64_t t = 0; t < Tn; ++t)
+    if (codes[t] < 0 || codes[t] >= ix->K) {
+      set_error("np_hip_index_append: codes[%lld] = %lld is outside [0, %lld)", (long long)t, (long long)codes[t], (long long)ix->K);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  return append_documents(ix, doc_lengths, n_docs, codes, residuals, Tn, maxlen);
+}
+
+int np_hip_index_reserve(np_index* ix, int64_t extra_docs, int64_t extra_tokens) {
+  clear_error();
+  if (!ix || extra_docs < 0 || extra_tokens < 0) {
+    set_error("np_hip_index_reserve: %s", !ix ? "index is NULL" : extra_docs < 0 ? "extra_docs is negative" : "extra_tokens is negative");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (ix->opts.shard_count > 1) {
+    set_error("np_hip_index_reserve: index is a shard (%d of %d)", ix->opts.shard_rank, ix->opts.shard_count);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  HoldContexts hold(ix);
+  DeviceGuard g(ix->device);
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", ix->device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  if (check_shard_docs(ix->n_docs + extra_docs) != NP_OK) {
+    set_error("np_hip_index_reserve: extra_docs: a shard holds < 2^31 documents");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  NP_HIP(hipDeviceSynchronize());
+  return grow_capacity(ix, ix->n_docs + extra_docs, ix->T + extra_tokens);
+}
+
+int np_hip_index_capacity(const np_index* ix, int64_t* docs, int64_t* tokens) {
+  clear_error();
+  if (!ix) {
+    set_error("np_hip_index_capacity: index is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (docs) *docs = ix->cap_docs;
+  if (tokens) *tokens = ix->cap_tokens;
   return NP_OK;
 }
 

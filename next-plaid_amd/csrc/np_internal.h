@@ -132,12 +132,17 @@ template <class T>
 class DevPtr {
  public:
   DevPtr() = default;
-  DevPtr(DevPtr&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevPtr(DevPtr&& o) noexcept : p_(o.p_), bytes_(o.bytes_) {
+    o.p_ = nullptr;
+    o.bytes_ = 0;
+  }
   DevPtr& operator=(DevPtr&& o) noexcept {
     if (this != &o) {
       reset();
       p_ = o.p_;
+      bytes_ = o.bytes_;
       o.p_ = nullptr;
+      o.bytes_ = 0;
     }
     return *this;
   }
@@ -151,17 +156,21 @@ class DevPtr {
       set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
       return NP_ERR_OUT_OF_MEMORY;
     }
+    bytes_ = bytes;
     if (acct) *acct += bytes;
     return NP_OK;
   }
   T* get() const { return p_; }
+  size_t bytes() const { return bytes_; }   // of the allocation (0 when empty): what alloc() added to *acct
   void reset() {
     if (p_) (void)hipFree(p_);
     p_ = nullptr;
+    bytes_ = 0;
   }
 
  private:
   T* p_ = nullptr;
+  size_t bytes_ = 0;
 };
 
 struct DevBuf {
@@ -298,6 +307,10 @@ struct DeviceIndex {
   float pad_ss = 0.f;                     // (dim - ldim) * wlut[0]^2, see ExactP::pad_ss
   int64_t T = 0;
   int64_t max_doc_len = 0;
+  // what the per-document (d_doc_offsets) and the per-token arrays (d_codes, d_residuals, d_inv_norm, d_tok_pos) are
+  // ALLOCATED for: n_docs / T at open, more after np_hip_index_reserve -- an append within them moves none of these arrays
+  int64_t cap_docs = 0, cap_tokens = 0;
+  bool avg_from_counts = false;   // avg_doclen is num_embeddings / num_documents (arrays, synth), not a directory's stored figure
   // device arrays: owned, freed when destroy_device_index deletes the handle
   DevPtr<float> d_centroids;
   DevPtr<float> d_wlut;
@@ -329,6 +342,7 @@ struct DeviceIndex {
   DevPtr<uint32_t> d_ivf_split;   // [K][n_ranges + 1] (derived, ascending lists only): entries of list c with id < 32768 r -- the
                                   // zeroth filter level's blocks read their range's part of a posting list without a bisection
   int n_ranges = 0;               // ceil(n_docs / 32768)
+  int ivf_cover = -1;             // the lists hold every (document, distinct code) pair: 1 yes, 0 no, -1 never looked at
   // ivf_top_prefix[i] = entries of the i longest posting lists together (host side, i <= K): a query that probes c cells cannot
   // have more candidates than ivf_top_prefix[c] (search.rs:427-452 unions the probed cells' lists), which is what the workspace
   // planner sizes the candidate pool and the number of pool rounds for -- n_docs per query only when the lists do not say less
@@ -366,6 +380,8 @@ struct DeviceIndex {
   mutable std::condition_variable cv;
   mutable std::vector<Context*> contexts;
   mutable uint64_t use_clock = 0;
+  mutable bool exclusive = false;   // np_hip_index_append / _reserve hold every context: acquire_context waits (under mu)
+  mutable int readers = 0;          // calls registered with IndexRead (under mu): an append waits for them too
 };
 
 // Any index the crate can write is searchable up to dim 128: rows are stored zero-padded to the next instantiated width
@@ -385,7 +401,21 @@ bool set_tuning(Tuning* t, const std::string& name, int value);   // shared clam
 void shard_range(int64_t n_total, int rank, int count, int64_t* b, int64_t* e);
 
 // np_search.hip
+// A call that reads the handle OUTSIDE a context -- the checks of its columns, keyword index and groups before it takes one,
+// the keyword index's host tables, the token arrays np_hip_decompress_documents reads -- registered from its first line to its
+// last: np_hip_index_append / _reserve wait until no such call runs and, once they hold the handle, later ones wait here.  So
+// a call sees the attachments it checked, or none; never a handle that changed under it.  Re-entrant per thread; a registered
+// thread's acquire_context does not wait for the append that is waiting for it.
+struct IndexRead {
+  const DeviceIndex* ix = nullptr;
+  explicit IndexRead(const DeviceIndex* index);
+  ~IndexRead();
+  IndexRead(const IndexRead&) = delete;
+  IndexRead& operator=(const IndexRead&) = delete;
+};
 void destroy_context(Context* c);
+// after np_hip_index_append (every context held): the contexts forget what they learnt about the index they served
+void contexts_forget_index(const DeviceIndex* ix);
 // np_hip_encode_tokens with an optional third output: norms[t] = |x_t - c[code_t]| (sequential f32 sum, no contraction)
 int encode_tokens_impl(const np_index* index, const float* embeddings, int64_t n_tokens, int32_t dim,
                        const float* bucket_cutoffs, int64_t* out_codes, uint8_t* out_packed, float* out_norms);

@@ -296,6 +296,7 @@ int np_hip_index_set_column_text(np_index* ix, int32_t column, const uint8_t* by
 int np_hip_text_match(const np_index* ix, int32_t column, const np_dfa* dfas, int32_t n_dfas, uint32_t* out_bits,
                       np_match_report* report) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   const auto t_begin = std::chrono::steady_clock::now();
   if (report) memset(report, 0, sizeof *report);
   if (!ix) {

@@ -546,6 +546,7 @@ static int scan_host(const np_index* ix, const float* queries, const int32_t* q_
                      int64_t n_subsets, const int32_t* query_subset, const np_filter* filters, int64_t* out_ids,
                      float* out_scores, int32_t* out_counts, np_stats* stats) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   if (stats) memset(stats, 0, sizeof *stats);
   if (B > 0 && !q_tok_offsets) {
     set_error("Search failed: NULL buffer");

@@ -85,9 +85,33 @@ void destroy_context(Context* c) {
   delete c;
 }
 
+static thread_local const DeviceIndex* tls_reading = nullptr;   // the handle this thread is registered on (IndexRead)
+
+IndexRead::IndexRead(const DeviceIndex* index) {
+  if (!index || tls_reading == index) return;   // (nested in a registered call: nothing to add)
+  std::unique_lock<std::mutex> lk(index->mu);
+  index->cv.wait(lk, [&] { return !index->exclusive; });
+  ++index->readers;
+  tls_reading = ix = index;
+}
+IndexRead::~IndexRead() {
+  if (!ix) return;
+  {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    --ix->readers;
+  }
+  tls_reading = nullptr;
+  ix->cv.notify_all();
+}
+
 static int acquire_context(const DeviceIndex* ix, Context** out) {
   std::unique_lock<std::mutex> lk(ix->mu);
   for (;;) {
+    // an append holds the whole pool, the contexts not yet created included -- but not yet while it waits for this call
+    if (ix->exclusive && tls_reading != ix) {
+      ix->cv.wait(lk);
+      continue;
+    }
     // Prefer growing the pool, then the least recently used idle context: back-to-back device-side calls
     // on different streams then land on different workspaces and their kernels can overlap on the GPU
     // (a context's workspace is guarded by its `done` event, so reuse is always safe, just serialising).
@@ -127,7 +151,14 @@ static void release_context(const DeviceIndex* ix, Context* c) {
     std::lock_guard<std::mutex> lk(ix->mu);
     c->busy = false;
   }
-  ix->cv.notify_one();
+  ix->cv.notify_all();   // callers waiting for a context and an append waiting for all of them share the condition
+}
+
+void contexts_forget_index(const DeviceIndex* ix) {
+  for (Context* c : ix->contexts) {   // the zeroth level's reports are about the index before the append
+    if (c->ws->h_gain) c->ws->h_gain[0] = c->ws->h_gain[1] = 0;
+    c->ws->h_gain_key = 0;
+  }
 }
 
 // ---- one pipeline pass over a slice of the batch --------------------------------------------------
@@ -2015,6 +2046,7 @@ int np_hip_search_batch_filtered(const np_index* ix, const float* queries, const
                                  const int32_t* query_filter, int64_t* out_ids, float* out_scores, int32_t* out_counts,
                                  np_stats* stats) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   if (stats) memset(stats, 0, sizeof *stats);
   NP_TRY(validate(ix, B, dim, params));
   NP_TRY(filter_check_call(ix, filters, n_filters, query_filter, B, true));
@@ -2297,6 +2329,7 @@ int np_hip_merge_packed(const np_index* ix, const void* d_records, int64_t recor
 int np_hip_decompress_documents(const np_index* ix, const int64_t* doc_ids, int64_t n_docs, float* out_embeddings,
                                 int64_t out_capacity_rows, int64_t* out_lengths) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   if (!ix || (n_docs > 0 && (!doc_ids || !out_lengths)) || n_docs < 0) {
     set_error("decompress_documents: invalid argument");
     return NP_ERR_INVALID_ARGUMENT;

@@ -1243,6 +1243,7 @@ static int text_host(const np_index* ix, const np_text_query* queries, const np_
                      const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets, const int32_t* query_subset,
                      const np_filter* filters, int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   if (stats) memset(stats, 0, sizeof *stats);
   NP_TRY(exprs ? text_check_exprs(ix, exprs, B, top_k) : text_check_queries(ix, queries, B, top_k));
   if (filters)
@@ -1583,6 +1584,7 @@ int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, 
                               int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
                               int32_t* d_out_counts, void* stream) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   NP_TRY(text_check_queries(ix, queries, B, top_k));
   NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
   if (B == 0) return NP_OK;
@@ -1701,6 +1703,7 @@ static int hybrid_host(const np_index* ix, const float* queries, const int32_t* 
                        float* out_scores, int32_t* out_counts, np_stats* stats, const GroupCall* grp,
                        const np_text_expr* text_exprs = nullptr) {
   clear_error();
+  IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
   if (stats) memset(stats, 0, sizeof *stats);
   if (!params) {
     set_error("Search failed: NULL index or params");

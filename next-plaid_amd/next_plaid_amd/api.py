@@ -10,6 +10,7 @@ Rust wrapper is where a CPU fallback would live.
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 from dataclasses import dataclass
 from typing import NamedTuple
@@ -290,6 +291,7 @@ EXPORTS = [
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
     "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
+    "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity",
 ]
 
 _lib = None
@@ -459,6 +461,9 @@ def lib():
     for f in (L.np_hip_index_update, L.np_hip_index_update_append):
         f.argtypes = [C.c_char_p, vp, vp, i64, i32, C.POINTER(np_update_config), i32, C.POINTER(np_update_report)]
     L.np_hip_index_delete.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
+    L.np_hip_index_append.argtypes = [vp, vp, i64, vp, vp]
+    L.np_hip_index_reserve.argtypes = [vp, i64, i64]
+    L.np_hip_index_capacity.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.np_hip_pooled_lengths.argtypes = [vp, i64, C.POINTER(np_pool_opts), vp]
     L.np_hip_pool_documents.argtypes = [i32, vp, vp, i64, i32, C.POINTER(np_pool_opts), vp, i64, vp, vp, vp,
                                         C.POINTER(np_pool_report)]
@@ -942,6 +947,46 @@ def update_index_dir(index_path: str, documents, config: UpdateConfig | None = N
 def update_append_dir(index_path: str, documents, config: UpdateConfig | None = None, device: int = 0):
     """MmapIndex::update_append (index.rs:1675-1700): returns (new document ids, report dict)."""
     return _update_call(lib().np_hip_index_update_append, index_path, documents, config, device)
+
+
+def _dir_counts(index_path: str):
+    """(num_documents, num_embeddings) of an index directory's metadata.json"""
+    with open(os.path.join(index_path, "metadata.json"), "rb") as f:
+        m = json.loads(f.read())
+    return int(m["num_documents"]), int(m["num_embeddings"])
+
+
+def _appended_tokens(index_path: str, before):
+    """What an update_append wrote for its documents, read back from the chunk files: (doc_lengths, codes, residuals) of the
+    documents the directory holds beyond the counts `before` -- the tail of its last chunks (update_index appends to the last
+    chunk or adds chunks, update.rs:771-1120)."""
+    with open(os.path.join(index_path, "metadata.json"), "rb") as f:
+        m = json.loads(f.read())
+    n_new, t_new = int(m["num_documents"]) - before[0], int(m["num_embeddings"]) - before[1]
+    lens, codes, res = [], [], []
+    have_d = have_t = 0
+    c = int(m["num_chunks"]) - 1
+    while have_d < n_new and c >= 0:
+        with open(os.path.join(index_path, f"doclens.{c}.json"), "rb") as f:
+            dl = np.asarray(json.loads(f.read()), np.int64).reshape(-1)
+        take_d = min(n_new - have_d, dl.size)
+        tail = dl[dl.size - take_d:]
+        take_t = int(tail.sum())
+        cd = np.load(os.path.join(index_path, f"{c}.codes.npy"), mmap_mode="r")
+        rs = np.load(os.path.join(index_path, f"{c}.residuals.npy"), mmap_mode="r")
+        lens.insert(0, tail)
+        codes.insert(0, np.asarray(cd[cd.shape[0] - take_t:], np.int64))
+        res.insert(0, np.asarray(rs[rs.shape[0] - take_t:], np.uint8))
+        have_d += take_d
+        have_t += take_t
+        c -= 1
+    if have_d != n_new or have_t != t_new:
+        raise IndexLoadError(f"Index load failed: the chunk files hold {have_d} new documents / {have_t} tokens, "
+                             f"metadata.json counts {n_new} / {t_new}")
+    pd = res[0].shape[1] if res else 0
+    return (np.concatenate(lens) if lens else np.zeros(0, np.int64),
+            np.concatenate(codes) if codes else np.zeros(0, np.int64),
+            np.concatenate(res) if res else np.zeros((0, pd), np.uint8))
 
 
 def delete_from_index_dir(index_path: str, doc_ids) -> int:
@@ -1428,6 +1473,63 @@ class MmapIndex:
         """MmapIndex::delete (index.rs:1731-1765): rewrites the directory and returns the count removed; like the crate
         it does not reload (call reload(); that drops the metadata columns, whose rows no longer match the new ids)."""
         return delete_from_index_dir(self._dir("delete"), doc_ids)
+
+    # -- append to the resident index (np_hip_index_append) ------------------------------------------------
+    def append_arrays(self, doc_lengths, codes, residuals):
+        """np_hip_index_append on any unsharded handle: documents already encoded (codes i64 in [0, K), residuals u8
+        [tokens, dim * nbits / 8] as np_hip_encode_tokens returns them) take the ids num_documents() .. and are served from
+        the next call on, without reading the index again.  The handle then equals one freshly opened on the grown index.
+        Metadata columns, the keyword index and the groups are dropped, as reload() leaves a handle (set_columns / set_text /
+        set_groups attach the grown ones).  Searches on other threads go on: the running ones finish on the old index, the
+        next ones see the new.  Returns the new documents' ids."""
+        dl = np.ascontiguousarray(np.asarray(doc_lengths, np.int64).reshape(-1))
+        cd = np.ascontiguousarray(np.asarray(codes, np.int64).reshape(-1))
+        rs = np.ascontiguousarray(residuals, np.uint8)
+        tokens = int(dl.sum()) if dl.size and (dl >= 0).all() else 0
+        pd = self.embedding_dim() * int(self._info.nbits) // 8
+        if cd.size < tokens or rs.size < tokens * pd:
+            raise ShapeError(f"Shape error: {tokens} tokens need {tokens} codes and {tokens * pd} residual bytes, got "
+                             f"{cd.size} and {rs.size}")
+        first = self.num_documents()
+        _check(lib().np_hip_index_append(self._h, _ptr(dl) if dl.size else None, dl.size, _ptr(cd) if cd.size else None,
+                                         _ptr(rs) if rs.size else None))
+        if dl.size:
+            self.schema = None
+            self.text = None
+            self.group_values = None
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+        return np.arange(first, first + dl.size, dtype=np.int64)
+
+    def append(self, documents, config: UpdateConfig | None = None) -> np.ndarray:
+        """update_append on the handle's directory AND on the handle: the documents are encoded once, by update_append_dir,
+        and the codes and residuals it wrote to the chunk files go to np_hip_index_append -- where update() reloads the whole
+        index, this costs the new documents plus one pass over the posting lists.  The handle equals MmapIndex.load of the
+        directory afterwards (no columns, keyword index or groups: attach them again).  Not for centroid expansion or
+        delete: those change K or re-sequence the ids, so update() / delete() + reload() remain.  Returns the new ids."""
+        path = self._dir("append")
+        # whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with
+        # its directory, and (an append of no documents runs the library's checks of the handle: shards, list order)
+        n_before = _dir_counts(path)
+        if n_before[0] != self.num_documents():
+            raise IndexLoadError(f"Index load failed: the directory holds {n_before[0]} documents, the handle "
+                                 f"{self.num_documents()}: the handle is not current, reload()")
+        _check(lib().np_hip_index_append(self._h, None, 0, None, None))
+        ids, self.last_update = update_append_dir(path, documents, config, self._open_opts.get("device", 0))
+        lens, codes, residuals = _appended_tokens(path, n_before)
+        self.append_arrays(lens, codes, residuals)
+        return ids
+
+    def reserve(self, extra_docs: int, extra_tokens: int):
+        """np_hip_index_reserve: room for this many MORE documents / tokens, so that later appends move no per-token array
+        (without it every array grows by allocate, copy, free: a peak of the largest array twice).  A service reserves
+        right after the open."""
+        _check(lib().np_hip_index_reserve(self._h, int(extra_docs), int(extra_tokens)))
+
+    def capacity(self):
+        """np_hip_index_capacity: (documents, tokens) the handle's arrays are allocated for."""
+        d, t = C.c_int64(0), C.c_int64(0)
+        _check(lib().np_hip_index_capacity(self._h, C.byref(d), C.byref(t)))
+        return int(d.value), int(t.value)
 
     @classmethod
     def from_arrays(cls, centroids, bucket_weights, ivf, ivf_lengths, doc_lengths, codes, residuals, nbits,
