@@ -1,6 +1,7 @@
 """numpy restatement of the crate's index update and delete (test infrastructure): delete_from_index (delete.rs:43-398, with
 the documented rule that ids outside [0, num_documents) are ignored), update_index (update.rs:771-1120), the mode choice
-of MmapIndex::update (index.rs:1431-1590) and find_outliers (update.rs:490-619) with its f64 distances.  It reads and
+of MmapIndex::update (index.rs:1431-1590) and find_outliers (update.rs:490-619) with its f64 distances, the device's
+recheck window in f64 (outlier_window) and an f32 emulation of its first pass (min_dist_sq_f32).  It reads and
 writes directories with numpy and json only (oracle.npy_index.read_index, oracle.encode_tokens) and none of the
 product's code."""
 import json
@@ -223,6 +224,51 @@ def find_outliers(flat, centroids, thr):
     """the outlier set this library computes: f32(min_c f64 |x - c|^2) > thr^2 (f32)"""
     thr2 = np.float32(thr) * np.float32(thr)
     return np.nonzero(min_dist_sq_precise(flat, centroids) > thr2)[0]
+
+
+def storage_dim(dim):
+    """the device's row width: dim rounded up to a multiple of 32 (zero padded)"""
+    return (dim + 31) // 32 * 32
+
+
+def min_dist_sq_f64(flat, centroids, block=256):
+    """min_c |x - c|^2 in f64, not rounded to f32: the quantity the outlier window is measured around"""
+    c = centroids.astype(np.float64)
+    out = np.empty(flat.shape[0], np.float64)
+    for i in range(0, flat.shape[0], block):
+        diff = flat[i:i + block].astype(np.float64)[:, None, :] - c[None, :, :]
+        out[i:i + block] = (diff * diff).sum(2).min(1)
+    return out
+
+
+def outlier_window(flat, centroids, thr):
+    """The window of the device's first pass, restated in f64: a token whose f32 minimum d has |d - thr^2| <= w goes to
+    the f64 recheck.  w = max(max(thr^2, 1) 1e-5, 4 (Dp + 2) 2^-24 (|x|^2 + 1.001 max |c|^2)), Dp the storage dim."""
+    thr2 = float(np.float32(thr) * np.float32(thr))
+    xn = (flat.astype(np.float64) ** 2).sum(1)
+    cn = (centroids.astype(np.float64) ** 2).sum(1).max() * (1.0 + 1e-3)
+    rel = 4.0 * (storage_dim(flat.shape[1]) + 2) * 2.0 ** -24
+    return np.maximum(max(abs(thr2), 1.0) * 1e-5, rel * (xn + cn))
+
+
+def _fma32(a, b, c):
+    """fmaf on f32 arrays: the product of two f32 values is exact in f64, so one f64 addition and one rounding follow"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def min_dist_sq_f32(flat, centroids):
+    """An f32 emulation of the first pass, min_c max(fma(-2, x.c, |x|^2 + |c|^2), 0), with |x|^2, |c|^2 and x.c as
+    sequential FMA chains over the dims.  The kernel sums x.c in the MFMA's order, so this is the formula and the
+    precision, not the kernel."""
+    x, c = flat.astype(np.float32), centroids.astype(np.float32)
+    xn, cn = np.zeros(x.shape[0], np.float32), np.zeros(c.shape[0], np.float32)
+    dot = np.zeros((x.shape[0], c.shape[0]), np.float32)
+    for j in range(x.shape[1]):
+        xn = _fma32(x[:, j], x[:, j], xn)
+        cn = _fma32(c[:, j], c[:, j], cn)
+        dot = _fma32(x[:, j, None], c[None, :, j], dot)
+    s = (xn[:, None] + cn[None, :]).astype(np.float32)
+    return np.maximum(_fma32(np.float32(-2), dot, s), np.float32(0)).min(1)
 
 
 def k_update(n_out, max_points_per_centroid):
