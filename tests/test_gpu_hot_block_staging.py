@@ -13,6 +13,7 @@ by choose_ublock_stride's rule and asserted, so that a generator change cannot s
 import numpy as np
 import pytest
 
+from append_restate import host_stride_bytes   # choose_ublock_stride's rule
 from helpers import RTOL_F32, assert_ranking_close, hip_index, make_arrays, oracle_index, synth, to_oracle_params
 
 import next_plaid_amd as npa
@@ -38,27 +39,6 @@ CASES = {
 
 def P(**kw):
     return npa.SearchParameters(**kw)
-
-
-def host_stride_bytes(a, code_bytes):
-    """choose_ublock_stride: the block holds the 16-byte header and the smallest capacity that at most 1 % of the distinct-code
-    lists exceed (list lengths are counted up to 256, longer ones in one bin), rounded up to a multiple of 64 bytes, at most
-    512.  Returns (stride in bytes, lists that overflow it)."""
-    lens = np.asarray(a["doc_lengths"], np.int64)
-    codes = np.asarray(a["codes"], np.int64)
-    n = lens.size
-    K = int(a["centroids"].shape[0])
-    doc = np.repeat(np.arange(n, dtype=np.int64), lens)
-    ulen = np.bincount(np.unique(doc * K + codes) // K, minlength=n)
-    hdr, per64, smax = 16 // code_bytes, 64 // code_bytes, 512 // code_bytes
-    hist = np.bincount(np.minimum(ulen, 257), minlength=258)
-    allow, over, q = n // 100, 0, 257
-    while q > 0 and over + hist[q] <= allow:
-        over += hist[q]
-        q -= 1
-    fit = min(smax - hdr, max(q, 1))
-    stride = max(per64, min(smax, (hdr + fit + per64 - 1) // per64 * per64))
-    return stride * code_bytes, int((ulen > stride - hdr).sum())
 
 
 def check_trace(hx, ox, q, p, what=""):

@@ -110,7 +110,16 @@ def _assert_equal_to_fresh(hx, fresh, queries, n_old, what=""):
         assert got[k] == want[k], f"{what}: {k}"
 
 
-def _check_append(base, new, n_appends=1, reserve=None, queries=None, **opts):
+def _level_ran(hx, queries):
+    """the zeroth level, the range table's only reader, ran: s3_gain = 2 (whenever it applies) without a threshold"""
+    p0 = npa.SearchParameters(n_full_scores=128, top_k=10, n_ivf_probe=8, centroid_score_threshold=None)
+    hx.tune("s3_gain", 2)
+    hx.search_batch(queries, p0)
+    hx.tune("s3_gain", 1)
+    return hx.last_stats["n_level0"] > 0
+
+
+def _check_append(base, new, n_appends=1, reserve=None, queries=None, level_runs=False, **opts):
     """append `new` to a handle of `base` in n_appends calls and compare with a fresh handle of the concatenation"""
     n_old = base["doc_lengths"].size
     lens, codes, res = new
@@ -129,7 +138,10 @@ def _check_append(base, new, n_appends=1, reserve=None, queries=None, **opts):
             assert hx.capacity() == cap, "an append within the reservation reallocated"
         else:
             assert hx.capacity() == (n_old + len(lens), int(base["doc_lengths"].sum() + np.sum(lens)))
-        _assert_equal_to_fresh(hx, fresh, _queries(base, new) if queries is None else queries, n_old)
+        queries = _queries(base, new) if queries is None else queries
+        _assert_equal_to_fresh(hx, fresh, queries, n_old)
+        if level_runs:
+            assert _level_ran(fresh, queries) and _level_ran(hx, queries), "the zeroth level did not run: nothing read the range table"
     finally:
         hx.close()
         fresh.close()
@@ -206,9 +218,9 @@ def test_append_refused_before_the_directory_is_touched(tmp_path):
 
 # ---- the edges of the kernels -------------------------------------------------------------------------------------------------
 def test_range_table_gains_a_range():
-    """32 760 + 20 documents: n_ranges goes from 1 to 2 (NP_IVF_SPLIT_RANGE = 32768)"""
+    """32 760 + 20 documents: n_ranges goes from 1 to 2 (NP_IVF_SPLIT_RANGE = 32768); the zeroth level reads the table"""
     _, base, new = _split(32760, 20)
-    _check_append(base, new)
+    _check_append(base, new, level_runs=True)
 
 
 def test_bitmap_word_crossed():
