@@ -1231,7 +1231,7 @@ int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n
  * answering as it did: a sharded handle; a handle whose posting lists do not ascend (only such lists grow at their end); a
  * negative length; a code outside [0, K); totals beyond the open path's limits (2^31 documents -- and, found once the new
  * documents' distinct codes are counted, the 40-bit list offset and the 32-bit overflow index: refused then, the handle
- * unchanged all the same).  Not covered: centroid expansion (K changes) and delete (ids are re-sequenced) -- reload.
+ * unchanged all the same).  Not covered: centroid expansion (K changes) -- reload.  Delete: np_hip_index_remove (below).
  *
  * Attachments: metadata columns, the keyword index and the groups are DROPPED, as a reload leaves a handle: their rows no
  * longer cover the documents.  np_hip_index_set_columns / _set_text / _set_groups attach the grown ones.
@@ -1244,7 +1244,7 @@ int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n
  * ones and swapped in when nothing can fail any more: NP_ERR_OUT_OF_MEMORY leaves the handle unchanged (its capacity may
  * have grown).
  *
- * Concurrency: append and reserve check out EVERY context of the handle's pool: calls that run finish on the index as it
+ * Concurrency: append, remove and reserve check out EVERY context of the handle's pool: calls that run finish on the index as it
  * was, calls that arrive wait, nobody observes a half-grown handle.  The entries that read the handle outside a context are
  * registered from their first line to their last and waited for in the same way: np_hip_decompress_documents (it reads the
  * token arrays an unreserved append frees) and every entry that checks columns, keyword index or groups before it takes a
@@ -1254,12 +1254,49 @@ int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n
  * np_hip_index_set_columns, _set_column_text, _set_text and _set_groups (they change the handle themselves and need
  * exclusive access), np_hip_index_close, and the sharded entries (a sharded handle is refused anyway).  A context between np_hip_search_phase_a and
  * np_hip_search_end counts as running: end such calls first -- an append from the thread that holds one waits for itself.
+ * np_hip_index_remove is exactly the same: it waits for the same calls, and the same entries may not run beside it.
  * NP_APPEND_TRACE=1 prints the stages' seconds to stderr (tools/append_time.py reads them). */
 int np_hip_index_append(np_index* index, const int64_t* doc_lengths, int64_t n_docs,
                         const int64_t* codes, const uint8_t* residuals);
 /* Room for this many MORE documents / tokens, so that later appends move no per-token array. */
 int np_hip_index_reserve(np_index* index, int64_t extra_docs, int64_t extra_tokens);
 int np_hip_index_capacity(const np_index* index, int64_t* docs, int64_t* tokens);   /* allocated, not used */
+
+/* ---- remove from a RESIDENT index (np_index.hip) -----------------------------------------------------------------------
+ * np_hip_index_delete rewrites the directory; np_hip_index_remove takes the same documents out of a handle that is already
+ * in HBM without reading the index again: one pass over the posting lists, one move of the tokens behind the first removed
+ * document.
+ *
+ * The semantics are np_hip_index_delete's (delete.rs:43-268), applied to the handle: ids outside [0, num_documents) are
+ * ignored, duplicates count once, *out_removed (nullable) = the distinct documents removed.  Surviving document d gets the id
+ * d - |{removed ids < d}|; each posting list keeps its surviving entries in its own order, renumbered.
+ *
+ * Afterwards the handle equals one freshly opened on the resulting index (np_hip_index_from_arrays on the shrunk arrays,
+ * np_hip_index_open on the directory np_hip_index_delete wrote): np_hip_index_export, np_hip_index_info (but device_bytes /
+ * workspace_bytes) and every search entry return the same bytes.  avg_doclen becomes tokens / documents in f64 (0.0 without
+ * documents), what the directory delete writes; num_embeddings follows; max_doc_len is that of the survivors.  If no listed
+ * id is in range nothing changes and the attachments stay.  Removing EVERY document leaves the handle that
+ * np_hip_index_from_arrays makes of the empty arrays (it opens: an index without documents answers every search with no rows).
+ *
+ * Refused with NP_ERR_INVALID_ARGUMENT, by name, before any allocation or launch, the handle answering as it did: a NULL
+ * handle, n_ids < 0, NULL doc_ids with n_ids > 0, a sharded handle.  Posting lists that do not ascend are NOT refused (the
+ * filter keeps a list's own order, as the directory delete does): they stay flagged as not ascending -- even where the
+ * removal leaves them ascending -- and the zeroth filter level stays off.
+ *
+ * Capacity (np_hip_index_capacity) does not shrink: the freed room is a reservation, an append that fits in it moves no
+ * per-token array.  Attachments -- metadata columns, the keyword index, the groups -- are DROPPED, as a reload leaves a
+ * handle; compacting them is out of scope: attach the survivors' rows again.
+ *
+ * Memory: everything that allocates happens before anything that serves is overwritten -- the survivor bitmap and the new
+ * doc offsets, the codes compacted BESIDE the old ones (2 to 4 of the ~145 bytes per token), the distinct-code blocks built
+ * from them, the filtered posting lists and their offsets, the range table, and one staging buffer of fixed size
+ * (np_hip_index_tune "remove_slab" tokens, 0 = the default 2^21, times the residual row).  NP_ERR_OUT_OF_MEMORY up to there
+ * leaves the handle unchanged.  Residuals, inverse norms and token positions are then compacted IN PLACE, slab by slab in
+ * ascending order (np_remove_plan.h): no second copy of the residuals exists at any time.
+ *
+ * Concurrency: as np_hip_index_append (above).  NP_REMOVE_TRACE=1 prints the stages' seconds and the two kernels' own times
+ * to stderr (tools/remove_time.py reads them). */
+int np_hip_index_remove(np_index* index, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed);
 
 /* ---- token pooling: pool_document_embeddings (np_pool.hip) --------------------------------------------------------------
  * next-plaid-onnx pools every document before it reaches the index (src/lib.rs:1632-1643 pool_document_embeddings ->

@@ -576,7 +576,7 @@ class MmapIndex {
   // documents plus one pass over the posting lists, and searches on other threads go on meanwhile (the running ones finish on
   // the old index).  The handle then equals one freshly opened on the grown index; columns, keyword index and groups are
   // dropped, as reload() leaves a handle.  Unsharded handles with ascending posting lists (what this library and the crate
-  // write); centroid expansion and delete still take update() / delete_documents() + reload().
+  // write); centroid expansion still takes update(); for delete see remove() below.
   // Documents already encoded (codes in [0, K), residuals [tokens][dim * nbits / 8] as np_hip_encode_tokens returns them):
   std::vector<int64_t> append_arrays(const std::vector<int64_t>& doc_lengths, const int64_t* codes, const uint8_t* residuals) {
     require_device("append_arrays");
@@ -634,7 +634,35 @@ class MmapIndex {
     if (ids) *ids = update_ids(np_update_report{}, docs.doc_lengths.size());
     return ix;
   }
-  // MmapIndex::delete (delete.rs:43-268): the count removed; no reload, as the crate (ids outside the index are ignored)
+  // ---- remove from the RESIDENT index (np_hip_index_remove) -- where delete_documents() + reload() read the whole index
+  // again, these cost one pass over the posting lists and one move of the tokens behind the first removed document.  The
+  // semantics are delete_documents': ids outside the index are ignored, duplicates count once, the survivors are renumbered.
+  // The handle then equals one freshly opened on the shrunk index; columns, keyword index and groups are dropped, as reload()
+  // leaves a handle; capacity() does not shrink.  Unsharded handles.  The handle alone:
+  int64_t remove_ids(const std::vector<int64_t>& doc_ids) {
+    require_device("remove_ids");
+    int64_t n = 0;
+    check(np_hip_index_remove(h_, doc_ids.data(), (int64_t)doc_ids.size(), &n));
+    check(np_hip_index_info(h_, &info_));
+    return n;
+  }
+  // delete_documents() on the handle's directory AND np_hip_index_remove on the handle: it equals load() of the directory then
+  int64_t remove(const std::vector<int64_t>& doc_ids) {
+    require_device("remove");
+    // whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with its
+    // directory, and (a remove of no ids runs the library's checks of the handle: shards)
+    const detail::DirCounts before = detail::dir_counts(path);
+    if (before.documents != info_.num_documents)
+      throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the handle is not current with its directory: reload()");
+    check(np_hip_index_remove(h_, nullptr, 0, nullptr));
+    int64_t n = 0;
+    check(np_hip_index_delete(path.c_str(), doc_ids.data(), (int64_t)doc_ids.size(), &n));
+    const int64_t m = remove_ids(doc_ids);
+    if (m != n) throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the directory lost another number of documents than the handle: reload()");
+    return n;
+  }
+  // MmapIndex::delete (delete.rs:43-268): the count removed; no reload, as the crate (ids outside the index are ignored).
+  // remove() does the same and brings the handle along
   int64_t delete_documents(const std::vector<int64_t>& doc_ids) {
     check_abi();
     int64_t n = 0;

@@ -5,6 +5,7 @@
 // merged_codes/merged_residuals -- device arrays laid out for the search kernels (np_internal.h).
 // Also: the seeded synthetic corpus generator (bench / scale tests) and export back to host.
 #include "np_internal.h"
+#include "np_remove_plan.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -106,6 +107,7 @@ bool set_tuning(Tuning* t, const std::string& n, int value) {
   else if (n == "scan_tiles") t->scan_tiles = clamp(value, 1, 8);
   else if (n == "scan_docs") t->scan_docs = std::max(value, 0);
   else if (n == "match_lds") t->match_lds = clamp(value, 0, 40);
+  else if (n == "remove_slab") t->remove_slab = std::max(value, 0);
   else return false;
   return true;
 }
@@ -789,10 +791,19 @@ static int check_ucode_totals(int64_t total, int64_t ovf_total) {
   return NP_OK;
 }
 
-// The distinct-code structures of the handle's first N documents (its n_docs at open; the grown count in an append, whose
-// doc offsets and codes are in place by then) into *u.  d_uoff (list offsets, [N + 1]) goes back to the caller: the IVF build
-// of the synthetic path and the posting-list merge of an append read the lists through it
-static int build_unique_codes(const DeviceIndex* ix, int64_t N, Ucodes* u, DevPtr<int64_t>* d_uoff) {
+// the doc offsets and codes the distinct-code lists are built from: the handle's own (tokens_of), or -- np_hip_index_remove --
+// the compacted ones while the old arrays still serve
+struct TokensView {
+  const int64_t* doc_off;
+  CodeArr codes;
+};
+static TokensView tokens_of(const DeviceIndex* ix) { return TokensView{ix->d_doc_offsets.get(), ix->codes()}; }
+
+// The distinct-code structures of the first N documents of tv (the handle's n_docs at open; the grown count in an append, whose
+// doc offsets and codes are in place by then; the shrunk count and the compacted arrays in a remove) into *u.  d_uoff (list
+// offsets, [N + 1]) goes back to the caller: the IVF build of the synthetic path and the posting-list merge of an append read
+// the lists through it
+static int build_unique_codes(const DeviceIndex* ix, const TokensView& tv, int64_t N, Ucodes* u, DevPtr<int64_t>* d_uoff) {
   NP_TRY(u->d_ulen.alloc((size_t)N, &u->bytes));
   NP_TRY(u->d_useg.alloc((size_t)N, &u->bytes));
   NP_TRY(u->d_doc_meta.alloc((size_t)N, &u->bytes));
@@ -801,7 +812,7 @@ static int build_unique_codes(const DeviceIndex* ix, int64_t N, Ucodes* u, DevPt
   // pass 1: list lengths
   for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
     const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
-    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), nullptr, nullptr, u->d_ulen.get() + d0);
+    unique_codes_kernel<<<(unsigned)n, 256>>>(tv.doc_off + d0, tv.codes, nullptr, nullptr, u->d_ulen.get() + d0);
   }
   NP_HIP(hipGetLastError());
   NP_TRY(choose_ublock_stride(ix, N, u));
@@ -818,15 +829,15 @@ static int build_unique_codes(const DeviceIndex* ix, int64_t N, Ucodes* u, DevPt
   NP_TRY(u->d_ucodes.alloc(bytes, &u->bytes));
   NP_HIP(hipMemset(u->d_ucodes.get(), 0, bytes));
   if (N > 0)
-    ublock_layout_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), u->d_ulen.get(), d_ovf.get(), S, hdr,
+    ublock_layout_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, tv.doc_off, u->d_ulen.get(), d_ovf.get(), S, hdr,
                                                                fit, base_b, u->d_ucodes.get(), ix->code_wide, d_uoff->get());
   for (int64_t d0 = 0; d0 < N; d0 += (int64_t)1 << 30) {
     const int64_t n = std::min<int64_t>((int64_t)1 << 30, N - d0);
-    unique_codes_kernel<<<(unsigned)n, 256>>>(ix->d_doc_offsets.get() + d0, ix->codes(), u->d_ucodes.get(), d_uoff->get() + d0,
+    unique_codes_kernel<<<(unsigned)n, 256>>>(tv.doc_off + d0, tv.codes, u->d_ucodes.get(), d_uoff->get() + d0,
                                               u->d_ulen.get() + d0);
   }
   if (N > 0)
-    doc_meta_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(), u->d_ulen.get(),
+    doc_meta_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, tv.doc_off, d_uoff->get(), u->d_ulen.get(),
                                                           u->d_doc_meta.get());
   NP_HIP(hipGetLastError());
   u->sliced_ok = false;
@@ -835,7 +846,7 @@ static int build_unique_codes(const DeviceIndex* ix, int64_t N, Ucodes* u, DevPt
     NP_TRY(d_bad.alloc(1));
     NP_HIP(hipMemset(d_bad.get(), 0, sizeof(int)));
     const uint32_t slice_w = (uint32_t)((ix->K + 7) / 8);
-    useg_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, ix->d_doc_offsets.get(), d_uoff->get(),
+    useg_kernel<<<(unsigned)((N + 255) / 256), 256>>>(N, tv.doc_off, d_uoff->get(),
                                                       CodeArr{u->d_ucodes.get(), ix->code_wide}, u->d_ulen.get(), slice_w,
                                                       u->d_useg.get(), d_bad.get());
     int bad = 1;
@@ -1043,7 +1054,7 @@ static int build_derived(DeviceIndex* ix, bool lists_from_codes, OpenTrace& trac
   {
     DevPtr<int64_t> d_uoff;
     Ucodes u;
-    NP_TRY(build_unique_codes(ix, ix->n_docs, &u, &d_uoff));
+    NP_TRY(build_unique_codes(ix, tokens_of(ix), ix->n_docs, &u, &d_uoff));
     install_ucodes(ix, std::move(u));
     trace.mark("distinct-code blocks");
     if (lists_from_codes) {
@@ -1763,7 +1774,7 @@ static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, con
   // 3. the distinct-code structures of the grown index, beside the ones that serve
   Ucodes u;
   DevPtr<int64_t> d_uoff;
-  NP_TRY(as_append_argument(build_unique_codes(ix, N1, &u, &d_uoff), "n_docs"));
+  NP_TRY(as_append_argument(build_unique_codes(ix, tokens_of(ix), N1, &u, &d_uoff), "n_docs"));
   trace.mark("distinct-code rebuild");
   // 4. the posting lists
   DevPtr<uint32_t> ivf;
@@ -1805,6 +1816,463 @@ static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, con
   ix->gain_run.store(0, std::memory_order_relaxed);
   ix->gain_skip.store(0, std::memory_order_relaxed);
   contexts_forget_index(ix);
+  return NP_OK;
+}
+
+// ---- remove from a resident index (np_hip_index_remove) ----------------------------------------------------------------
+// Survivors keep their order, so document d becomes d - rank(d) with rank(d) = the removed ids below d, every per-token array
+// is an order-preserving compaction towards lower addresses, and every posting list is a filter plus that renumbering.
+//
+// The survivors: one ballot word per 64 documents (bit = the document stays) and the removed documents in front of each word,
+// so that rank(d) is one popcount and one add on 1.4 MB at 10 M documents -- they stay in the L2 under the posting-list pass.
+struct KeepMap {
+  const uint64_t* bits;     // [ceil(n_docs / 64)]; bits past n_docs are set
+  const uint32_t* wrank;    // [same] removed documents with an id below 64 w
+};
+__device__ __forceinline__ bool doc_kept(const KeepMap& k, uint32_t d) { return (k.bits[d >> 6] >> (d & 63)) & 1ull; }
+__device__ __forceinline__ uint32_t doc_rank(const KeepMap& k, uint32_t d) {
+  return k.wrank[d >> 6] + (uint32_t)__popcll(~k.bits[d >> 6] & ((1ull << (d & 63)) - 1ull));
+}
+
+// removed: the ids to remove, ascending, each once (m > 0).  gone[w] = removed documents of word w
+__global__ void __launch_bounds__(256) keep_bitmap_kernel(const int64_t* __restrict__ removed, int64_t m, int64_t n_docs,
+                                                          int64_t n_words, uint64_t* __restrict__ bits, uint32_t* __restrict__ gone) {
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool keep = true;
+  if (d < n_docs) {
+    int64_t a = 0, z = m;
+    while (a < z) {
+      const int64_t mid = (a + z) >> 1;
+      if (removed[mid] < d) a = mid + 1;
+      else z = mid;
+    }
+    keep = !(a < m && removed[a] == d);
+  }
+  const unsigned long long word = __ballot(keep);
+  if ((threadIdx.x & 63) == 0 && (d >> 6) < n_words) {
+    bits[d >> 6] = word;
+    gone[d >> 6] = 64u - (uint32_t)__popcll(word);
+  }
+}
+
+// per survivor, under its NEW id: its length (the scan's input, the max-reduction's too) and where its tokens lie in the old arrays
+__global__ void __launch_bounds__(256) survivor_docs_kernel(int64_t n_docs, KeepMap km, const int64_t* __restrict__ old_off,
+                                                            int64_t* __restrict__ klen, int64_t* __restrict__ src_start) {
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (d >= n_docs || !doc_kept(km, (uint32_t)d)) return;
+  const int64_t nd = d - doc_rank(km, (uint32_t)d);
+  klen[nd] = old_off[d + 1] - old_off[d];
+  src_start[nd] = old_off[d];
+}
+
+// The posting lists, balanced by ENTRIES like the merge of an append: a workgroup owns NP_FILTER_TILE consecutive entries of the
+// OLD array whatever lists they belong to, a thread 4 consecutive ones per step (one aligned 16-byte load).  A count pass gives
+// every tile's survivors, a scan over the tiles their first destination, and the placement pass -- the same kernel, the same
+// ballots -- puts an entry at the tile's base + the survivors of the waves before its own + those of the lanes before its own +
+// those before it in its quad.  The value written is id - rank(id).  No atomics, no workgroup waits for another, the same
+// bytes from run to run.
+#define NP_FILTER_TILE 4096
+#define NP_FILTER_STEPS (NP_FILTER_TILE / 1024)
+template <bool PLACE>
+__global__ void __launch_bounds__(256) ivf_filter_kernel(const uint32_t* __restrict__ old_ivf, int64_t total, KeepMap km,
+                                                         const int64_t* __restrict__ tile_base, int64_t* __restrict__ tile_count,
+                                                         uint32_t* __restrict__ out) {
+  __shared__ uint32_t s_wave[NP_FILTER_STEPS * 4];
+  const int64_t o0 = (int64_t)blockIdx.x * NP_FILTER_TILE;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long before = (1ull << lane) - 1ull;
+  uint32_t id[NP_FILTER_STEPS][4], mask[NP_FILTER_STEPS], pre[NP_FILTER_STEPS];
+#pragma unroll
+  for (int it = 0; it < NP_FILTER_STEPS; ++it) {
+    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
+    const int n = (int)max((int64_t)0, min((int64_t)4, total - o));
+    if (n == 4) {
+      const uint4 q = *reinterpret_cast<const uint4*>(old_ivf + o);   // o is a multiple of 4
+      id[it][0] = q.x, id[it][1] = q.y, id[it][2] = q.z, id[it][3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) id[it][k] = k < n ? old_ivf[o + k] : 0u;
+    }
+    uint32_t mk = 0, p = 0, tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool keep = k < n && doc_kept(km, id[it][k]);
+      const unsigned long long b = __ballot(keep);
+      mk |= keep ? 1u << k : 0u;
+      p += (uint32_t)__popcll(b & before);
+      tot += (uint32_t)__popcll(b);
+    }
+    mask[it] = mk;
+    pre[it] = p;
+    if (lane == 0) s_wave[it * 4 + wave] = tot;
+  }
+  __syncthreads();
+  if (!PLACE) {
+    if (threadIdx.x == 0) {
+      int64_t c = 0;
+      for (int i = 0; i < NP_FILTER_STEPS * 4; ++i) c += s_wave[i];
+      tile_count[blockIdx.x] = c;
+    }
+    return;
+  }
+  int64_t at = tile_base[blockIdx.x];
+#pragma unroll
+  for (int it = 0; it < NP_FILTER_STEPS; ++it) {
+    int64_t w = at;
+    for (int i = 0; i < 4; ++i) {
+      if (i < wave) w += s_wave[it * 4 + i];
+      at += s_wave[it * 4 + i];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (mask[it] & (1u << k))
+        out[w + pre[it] + (uint32_t)__popc(mask[it] & ((1u << k) - 1u))] = id[it][k] - doc_rank(km, id[it][k]);
+  }
+}
+
+// new_off[c] = the survivors in front of old_off[c]: the base of the tile that holds it + the survivors of that tile in front of
+// it.  One wave per list boundary (c = 0 .. K), at most 64 coalesced steps.  tile_base has one entry past the last tile.
+__global__ void __launch_bounds__(256) ivf_filter_offsets_kernel(const uint32_t* __restrict__ old_ivf, const int64_t* __restrict__ old_off,
+                                                                 int64_t K, KeepMap km, const int64_t* __restrict__ tile_base,
+                                                                 int64_t* __restrict__ new_off) {
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c > K) return;   // the whole wave
+  const int lane = threadIdx.x & 63;
+  const int64_t o = old_off[c], tile = o / NP_FILTER_TILE;
+  int64_t cnt = 0;
+  for (int64_t base = tile * NP_FILTER_TILE; base < o; base += 64) {
+    const int64_t i = base + lane;
+    cnt += __popcll(__ballot(i < o && doc_kept(km, old_ivf[i])));
+  }
+  if (lane == 0) new_off[c] = tile_base[tile] + cnt;
+}
+
+// The token move, balanced by destination BYTES (documents have 0 to 2049+ tokens): a workgroup owns NP_COMPACT_TILE bytes of the
+// destination, cut at multiples of 16 bytes of the destination's address, a thread one 16-byte piece per step.  One thread
+// bisects the new offsets for the tile's first document; lanes gallop from there (ivf_list_of).  Destination token n of new
+// document j comes from old token src_start[j] + (n - new_off[j]).  A piece whose 16 source bytes are contiguous -- all of them
+// but those that hold a removed document's edge -- is one load, as wide as the source ADDRESS allows (16-byte aligned: one
+// 16-byte load; 4-byte aligned: the packed quad of the merge; else 2-byte loads: a shift of one 2-byte code allows no more);
+// the others, and the ragged pieces at the ends of the range, go byte by byte.  A thread loads all its pieces
+// before it stores any.  src and dst may be the same array: the caller's schedule (np_remove_plan.h) sees to it that no
+// launch reads a byte it writes.
+#define NP_COMPACT_TILE 16384
+#define NP_COMPACT_STEPS (NP_COMPACT_TILE / 4096)
+struct TokenMove {
+  const int64_t* new_off;     // [n_new + 1]
+  const int64_t* src_start;   // [n_new]
+  int64_t n_new;
+  int64_t b0, b1;             // the destination bytes, in the array's coordinates: [dst0 * row, dst1 * row), not empty
+  int64_t dshift;             // destination byte b is written at dst + (b - dshift): 0 in place, b0 into the staging buffer
+  int32_t row;                // bytes per token
+};
+__global__ void __launch_bounds__(256) token_compact_kernel(TokenMove m, const uint8_t* src, uint8_t* dst) {
+  __shared__ int64_t s_j, s_tok;
+  __shared__ uint32_t s_rem;
+  const int64_t v_lo = m.b0 - m.dshift, v_hi = m.b1 - m.dshift;   // the destination relative to dst
+  const int64_t tile0 = (v_lo & ~(int64_t)15) + (int64_t)blockIdx.x * NP_COMPACT_TILE;
+  const int64_t vbase = max(tile0, v_lo);                          // < v_hi: the grid covers the range
+  if (threadIdx.x == 0) {
+    const int64_t b = vbase + m.dshift;
+    s_tok = b / m.row;
+    s_rem = (uint32_t)(b - s_tok * m.row);
+    s_j = ivf_list_of(m.new_off, m.n_new, 0, s_tok);
+  }
+  __syncthreads();
+  const int64_t tok0 = s_tok;
+  const uint32_t rem0 = s_rem, row = (uint32_t)m.row;
+  int64_t j = s_j;
+  // the source byte of destination byte v (>= vbase); j only moves forward
+  auto source = [&](int64_t v) -> int64_t {
+    const uint32_t r = rem0 + (uint32_t)(v - vbase), q = r / row;
+    const int64_t n = tok0 + q;
+    j = ivf_list_of(m.new_off, m.n_new, j, n);
+    return (m.src_start[j] + (n - m.new_off[j])) * (int64_t)row + (r - q * row);
+  };
+  uint32_t w[NP_COMPACT_STEPS][4];
+#pragma unroll
+  for (int it = 0; it < NP_COMPACT_STEPS; ++it) {
+    const int64_t v = tile0 + it * 4096 + (int64_t)threadIdx.x * 16;
+    const int64_t lo = max(v, v_lo), hi = min(v + 16, v_hi);
+    w[it][0] = w[it][1] = w[it][2] = w[it][3] = 0u;
+    if (hi <= lo) continue;
+    bool whole = hi - lo == 16;
+    if (whole) {
+      const int64_t sa = source(v);
+      const int64_t j_a = j;
+      const int64_t sb = source(v + 15);
+      j = j_a;   // the next piece of this thread lies behind, but keep the start for the byte path
+      whole = sb - sa == 15;
+      if (whole) {
+        const uint8_t* p = src + sa;
+        const uintptr_t al = reinterpret_cast<uintptr_t>(p);
+        if ((al & 15) == 0) {
+          const uint4 q = *reinterpret_cast<const uint4*>(p);
+          w[it][0] = q.x, w[it][1] = q.y, w[it][2] = q.z, w[it][3] = q.w;
+          continue;
+        }
+        if ((al & 3) == 0) {
+          const MergeQuad q = *reinterpret_cast<const MergeQuad*>(p);
+          w[it][0] = q.v[0], w[it][1] = q.v[1], w[it][2] = q.v[2], w[it][3] = q.v[3];
+          continue;
+        }
+        if ((al & 1) == 0) {
+          const uint16_t* p2 = reinterpret_cast<const uint16_t*>(p);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) w[it][k >> 1] |= (uint32_t)p2[k] << ((k & 1) * 16);
+          continue;
+        }
+      }   // (an odd address, which the handle's row sizes -- 2, 4 and multiples of 8 bytes -- never give: byte by byte, below)
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (v + k >= lo && v + k < hi) w[it][k >> 2] |= (uint32_t)src[source(v + k)] << ((k & 3) * 8);
+  }
+#pragma unroll
+  for (int it = 0; it < NP_COMPACT_STEPS; ++it) {
+    const int64_t v = tile0 + it * 4096 + (int64_t)threadIdx.x * 16;
+    const int64_t lo = max(v, v_lo), hi = min(v + 16, v_hi);
+    if (hi <= lo) continue;
+    if (hi - lo == 16) {
+      *reinterpret_cast<uint4*>(dst + v) = make_uint4(w[it][0], w[it][1], w[it][2], w[it][3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k)
+        if (v + k >= lo && v + k < hi) dst[v + k] = (uint8_t)(w[it][k >> 2] >> ((k & 3) * 8));
+    }
+  }
+}
+
+// the survivors among the tokens behind destination token dst0 -> tokens [dst0, dst1) of dst (in place: dst == src), or -- to_staging --
+// rows [0, dst1 - dst0) of dst
+static void launch_token_compact(const int64_t* new_off, const int64_t* src_start, int64_t n_new, int64_t dst0, int64_t dst1, int row,
+                                 bool to_staging, const void* src, void* dst) {
+  if (dst1 <= dst0) return;
+  TokenMove m{new_off, src_start, n_new, dst0 * row, dst1 * row, to_staging ? dst0 * row : 0, row};
+  const int64_t v_lo = m.b0 - m.dshift, v_hi = m.b1 - m.dshift;
+  const int64_t tiles = (v_hi - (v_lo & ~(int64_t)15) + NP_COMPACT_TILE - 1) / NP_COMPACT_TILE;
+  token_compact_kernel<<<(unsigned)tiles, 256>>>(m, static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst));
+}
+
+// a pair of device events around a kernel, when a trace asks for the kernel's own time
+struct KernelClock {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool on = false;
+  explicit KernelClock(bool want) { on = want && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess; }
+  ~KernelClock() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void start() {
+    if (on) (void)hipEventRecord(ev[0], nullptr);
+  }
+  double stop() {   // seconds
+    float ms = 0.f;
+    if (!on) return 0.0;
+    (void)hipEventRecord(ev[1], nullptr);
+    if (hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return 0.0;
+    return ms * 1e-3;
+  }
+};
+
+template <class T>
+static int device_scan_inclusive(const T* in, T* out, int64_t n) {
+  DevPtr<uint8_t> d_temp;
+  size_t tb = 0;
+  NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, in, out, (int)n));
+  return NP_OK;
+}
+template <class T>
+static int device_scan_exclusive(const T* in, T* out, int64_t n) {
+  DevPtr<uint8_t> d_temp;
+  size_t tb = 0;
+  NP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), tb, in, out, (int)n));
+  return NP_OK;
+}
+
+// the handle's posting lists without the removed documents, the rest renumbered: *ivf [*ivf_size], *ioff / *h_ioff [K + 1]
+static int filter_posting_lists(const DeviceIndex* ix, const KeepMap& km, DevPtr<uint32_t>* ivf, DevPtr<int64_t>* ioff,
+                                std::vector<int64_t>* h_ioff, int64_t* ivf_size, const OpenTrace& trace) {
+  const int64_t K = ix->K, total = ix->ivf_size, tiles = (total + NP_FILTER_TILE - 1) / NP_FILTER_TILE;
+  if (tiles >= ((int64_t)1 << 31)) {
+    set_error("np_hip_index_remove: %lld posting-list entries are more than one pass takes", (long long)total);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  DevPtr<int64_t> d_count, d_base;
+  NP_TRY(d_count.alloc((size_t)tiles + 1));
+  NP_TRY(d_base.alloc((size_t)tiles + 1));
+  NP_HIP(hipMemset(d_count.get() + tiles, 0, 8));
+  KernelClock clock(trace.on);
+  clock.start();
+  if (tiles > 0)
+    ivf_filter_kernel<false><<<(unsigned)tiles, 256>>>(ix->d_ivf.get(), total, km, nullptr, d_count.get(), nullptr);
+  NP_HIP(hipGetLastError());
+  double sec = clock.stop();
+  NP_TRY(device_scan_exclusive(d_count.get(), d_base.get(), tiles + 1));
+  int64_t kept = 0;
+  NP_HIP(hipMemcpy(&kept, d_base.get() + tiles, 8, hipMemcpyDeviceToHost));
+  NP_TRY(ioff->alloc((size_t)K + 1));
+  NP_TRY(ivf->alloc((size_t)kept));   // the new array beside the old one
+  clock.start();
+  if (tiles > 0)
+    ivf_filter_kernel<true><<<(unsigned)tiles, 256>>>(ix->d_ivf.get(), total, km, d_base.get(), nullptr, ivf->get());
+  ivf_filter_offsets_kernel<<<(unsigned)((K + 4) / 4), 256>>>(ix->d_ivf.get(), ix->d_ivf_offsets.get(), K, km, d_base.get(), ioff->get());
+  NP_HIP(hipGetLastError());
+  sec += clock.stop();
+  if (trace.on)
+    fprintf(stderr, "[%s] %-28s %8.6f s  %lld entries %lld kept\n", trace.tag, "filter kernel", sec, (long long)total, (long long)kept);
+  h_ioff->resize((size_t)K + 1);
+  NP_HIP(hipMemcpy(h_ioff->data(), ioff->get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
+  NP_HIP(hipDeviceSynchronize());
+  *ivf_size = kept;
+  return NP_OK;
+}
+
+// removed: the ids to remove -- in range, ascending, each once, not empty
+static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed) {
+  HoldContexts hold(ix);
+  DeviceGuard g(ix->device);
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", ix->device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  const int64_t N0 = ix->n_docs, m = (int64_t)removed.size(), N1 = N0 - m, T0 = ix->T, W = (N0 + 63) / 64;
+  NP_HIP(hipDeviceSynchronize());   // device-side calls that returned may still be running on their streams
+  OpenTrace trace("NP_REMOVE_TRACE", "np remove");
+  // 1. the survivors: bitmap, ranks, the new doc offsets (at the capacity the old ones have) and the longest survivor
+  DevPtr<int64_t> d_removed, d_klen, d_src, d_newoff, d_max;
+  DevPtr<uint64_t> d_bits;
+  DevPtr<uint32_t> d_gone, d_wrank;
+  NP_TRY(d_removed.alloc((size_t)m));
+  NP_TRY(d_bits.alloc((size_t)W));
+  NP_TRY(d_gone.alloc((size_t)W));
+  NP_TRY(d_wrank.alloc((size_t)W));
+  NP_TRY(d_klen.alloc((size_t)N1));
+  NP_TRY(d_src.alloc((size_t)N1));
+  NP_TRY(d_max.alloc(1));
+  NP_TRY(d_newoff.alloc((size_t)ix->cap_docs + 1));
+  NP_HIP(hipMemcpy(d_removed.get(), removed.data(), (size_t)m * 8, hipMemcpyHostToDevice));
+  keep_bitmap_kernel<<<(unsigned)((N0 + 255) / 256), 256>>>(d_removed.get(), m, N0, W, d_bits.get(), d_gone.get());
+  NP_HIP(hipGetLastError());
+  NP_TRY(device_scan_exclusive(d_gone.get(), d_wrank.get(), W));
+  const KeepMap km{d_bits.get(), d_wrank.get()};
+  survivor_docs_kernel<<<(unsigned)((N0 + 255) / 256), 256>>>(N0, km, ix->d_doc_offsets.get(), d_klen.get(), d_src.get());
+  NP_HIP(hipGetLastError());
+  NP_HIP(hipMemset(d_newoff.get(), 0, 8));
+  int64_t maxlen = 0, T1 = 0;
+  if (N1 > 0) {
+    NP_TRY(device_scan_inclusive(d_klen.get(), d_newoff.get() + 1, N1));
+    DevPtr<uint8_t> d_temp;
+    size_t tb = 0;
+    NP_HIP(hipcub::DeviceReduce::Max(nullptr, tb, d_klen.get(), d_max.get(), (int)N1));
+    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+    NP_HIP(hipcub::DeviceReduce::Max(d_temp.get(), tb, d_klen.get(), d_max.get(), (int)N1));
+    NP_HIP(hipMemcpy(&maxlen, d_max.get(), 8, hipMemcpyDeviceToHost));
+    NP_HIP(hipMemcpy(&T1, d_newoff.get() + N1, 8, hipMemcpyDeviceToHost));
+  }
+  // the schedule of the in-place moves, from the host's copy of the old offsets
+  std::vector<int64_t> h_off((size_t)N0 + 1);
+  NP_HIP(hipMemcpy(h_off.data(), ix->d_doc_offsets.get(), h_off.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<uint8_t> h_keep((size_t)N0, 1);
+  for (int64_t d : removed) h_keep[(size_t)d] = 0;
+  const RemovePlan plan = remove_plan(h_off.data(), h_keep.data(), N0, ix->pd, ix->tune.remove_slab);
+  if (plan.new_tokens != T1) {
+    set_error("internal: the remove plan counts %lld tokens, the device %lld", (long long)plan.new_tokens, (long long)T1);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  const int64_t first = plan.first_moved;   // tokens in front of it stay where they are
+  trace.mark("survivors");
+  // 2. the codes, compacted BESIDE the old ones: the distinct-code structures are built from them while the old arrays serve
+  const int cb = (int)ix->code_bytes();
+  DevPtr<uint8_t> codes;
+  NP_TRY(codes.alloc((size_t)std::max<int64_t>(ix->cap_tokens, 1) * cb));
+  if (first > 0) NP_HIP(hipMemcpy(codes.get(), ix->d_codes.get(), (size_t)first * cb, hipMemcpyDeviceToDevice));
+  launch_token_compact(d_newoff.get(), d_src.get(), N1, first, T1, cb, false, ix->d_codes.get(), codes.get());
+  NP_HIP(hipGetLastError());
+  trace.mark("codes beside");
+  // 3. the distinct-code structures of the shrunk index
+  Ucodes u;
+  DevPtr<int64_t> d_uoff;
+  NP_TRY(build_unique_codes(ix, TokensView{d_newoff.get(), CodeArr{codes.get(), ix->code_wide}}, N1, &u, &d_uoff));
+  d_uoff.reset();
+  trace.mark("distinct-code rebuild");
+  // 4. the posting lists
+  DevPtr<uint32_t> ivf;
+  DevPtr<int64_t> ioff;
+  std::vector<int64_t> h_ioff;
+  int64_t ivf_size = 0;
+  NP_TRY(filter_posting_lists(ix, km, &ivf, &ioff, &h_ioff, &ivf_size, trace));
+  trace.mark("posting-list filter");
+  // 5. their range table.  Lists that held every (document, code) pair still do: a survivor's entries all stay
+  DevPtr<uint32_t> split;
+  int R = 0, cover = N1 > 0 ? ix->ivf_cover : -1;
+  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide}, ivf.get(), ioff.get()};
+  NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
+  trace.mark("range table");
+  // 6. the staging buffer of the in-place moves: the last thing that can fail
+  DevPtr<uint8_t> staging;
+  if (plan.staging_bytes > 0) NP_TRY(staging.alloc((size_t)plan.staging_bytes));
+  // ---- nothing below can fail: the handle becomes the shrunk index ----
+  struct Moved {
+    void* p;
+    int row;
+  };
+  const Moved arrays[3] = {{ix->d_residuals.get(), ix->pd}, {ix->d_inv_norm.get(), 4}, {ix->tok_sorted ? ix->d_tok_pos.get() : nullptr, 2}};
+  KernelClock clock(trace.on);
+  double sec_direct = 0, sec_staged = 0;
+  for (const RemoveLaunch& l : plan.launches) {
+    clock.start();
+    for (const Moved& a : arrays) {
+      if (!a.p) continue;
+      if (l.mode == NP_REMOVE_DIRECT) launch_token_compact(d_newoff.get(), d_src.get(), N1, l.dst0, l.dst1, a.row, false, a.p, a.p);
+      else if (l.mode == NP_REMOVE_GATHER) launch_token_compact(d_newoff.get(), d_src.get(), N1, l.dst0, l.dst1, a.row, true, a.p, staging.get());
+      if (l.mode == NP_REMOVE_GATHER)   // ... and the copy out of it, behind the gather in stream order
+        (void)hipMemcpyAsync(static_cast<uint8_t*>(a.p) + l.dst0 * a.row, staging.get(), (size_t)(l.dst1 - l.dst0) * a.row,
+                             hipMemcpyDeviceToDevice, nullptr);
+    }
+    (l.mode == NP_REMOVE_DIRECT ? sec_direct : sec_staged) += clock.stop();
+  }
+  const hipError_t moved = hipDeviceSynchronize();
+  if (trace.on) {
+    const double per_token = (double)ix->pd + 4 + (ix->tok_sorted ? 2 : 0);
+    fprintf(stderr, "[%s] %-28s %8.6f s  %lld tokens %.0f bytes each\n", trace.tag, "move kernel direct", sec_direct,
+            (long long)plan.direct_tokens, per_token);
+    fprintf(stderr, "[%s] %-28s %8.6f s  %lld tokens %.0f bytes each\n", trace.tag, "move kernel staged", sec_staged,
+            (long long)plan.staged_tokens, per_token);
+  }
+  trace.mark("token move");
+  staging.reset();
+  ix->device_bytes = ix->device_bytes - ix->d_codes.bytes() - ix->d_doc_offsets.bytes() + codes.bytes() + d_newoff.bytes();
+  ix->d_codes = std::move(codes);
+  ix->d_doc_offsets = std::move(d_newoff);
+  install_ucodes(ix, std::move(u));
+  ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
+  ix->d_ivf = std::move(ivf);
+  ix->d_ivf_offsets = std::move(ioff);
+  ix->ivf_size = ivf_size;
+  set_ivf_bound(ix, h_ioff.data());
+  install_ivf_split(ix, std::move(split), R);
+  ix->ivf_cover = cover;
+  // tokens / documents, what the directory delete writes (np_update.cpp delete_impl) and a handle made from arrays reports
+  ix->avg_doclen = N1 > 0 ? (double)T1 / (double)N1 : 0.0;
+  ix->n_docs = ix->N_total = N1;
+  ix->T = T1;
+  ix->n_emb_total -= T0 - T1;
+  ix->max_doc_len = maxlen;
+  drop_attachments(ix);
+  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
+  ix->gain_run.store(0, std::memory_order_relaxed);
+  ix->gain_skip.store(0, std::memory_order_relaxed);
+  contexts_forget_index(ix);
+  trace.mark("swap");
+  if (moved != hipSuccess) {   // not an allocation: a device that stopped answering
+    set_error("np_hip_index_remove: the token move failed: %s", hipGetErrorString(moved));
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
   return NP_OK;
 }
 
@@ -2288,6 +2756,26 @@ int np_hip_index_append(np_index* ix, const int64_t* doc_lengths, int64_t n_docs
       return NP_ERR_INVALID_ARGUMENT;
     }
   return append_documents(ix, doc_lengths, n_docs, codes, residuals, Tn, maxlen);
+}
+
+int np_hip_index_remove(np_index* ix, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed) {
+  clear_error();
+  if (!ix) {
+    set_error("np_hip_index_remove: index is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (n_ids < 0 || (n_ids > 0 && !doc_ids)) {
+    set_error("np_hip_index_remove: %s", n_ids < 0 ? "n_ids is negative" : "doc_ids is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (ix->opts.shard_count > 1) {
+    set_error("np_hip_index_remove: index is a shard (%d of %d): a sharded index is reloaded", ix->opts.shard_rank, ix->opts.shard_count);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  const std::vector<int64_t> removed = remove_ids_in_range(doc_ids, n_ids, ix->n_docs);
+  if (!removed.empty()) NP_TRY(remove_documents(ix, removed));   // none in range: nothing changes, the attachments stay
+  if (out_removed) *out_removed = (int64_t)removed.size();
+  return NP_OK;
 }
 
 int np_hip_index_reserve(np_index* ix, int64_t extra_docs, int64_t extra_tokens) {

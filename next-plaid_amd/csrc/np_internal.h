@@ -253,6 +253,8 @@ struct Tuning {
   int match_lds = 32;    // np_hip_text_match / NP_F_MATCH: KiB of LDS a DFA table may take; a larger table is read from global
                          // memory through the caches (0 = every table; at most 40: tile + classes + table stay within 64 KiB)
   int scan_docs = 0;     // ... documents per pass over the index; 0 = as many as the key table's share of the workspace budget holds
+  int remove_slab = 0;   // np_hip_index_remove: source tokens per slab of the in-place token move (np_remove_plan.h) = rows of its
+                         // staging buffer; 0 = NP_REMOVE_SLAB_DEFAULT.  np_hip_index_tune only: tests cross slab edges with a few thousand tokens
 };
 
 // documents per range of the posting lists' range table (d_ivf_split) = per block of the zeroth filter level's sweep (np_kernels.h)
@@ -380,7 +382,7 @@ struct DeviceIndex {
   mutable std::condition_variable cv;
   mutable std::vector<Context*> contexts;
   mutable uint64_t use_clock = 0;
-  mutable bool exclusive = false;   // np_hip_index_append / _reserve hold every context: acquire_context waits (under mu)
+  mutable bool exclusive = false;   // np_hip_index_append / _remove / _reserve hold every context: acquire_context waits (under mu)
   mutable int readers = 0;          // calls registered with IndexRead (under mu): an append waits for them too
 };
 

@@ -291,7 +291,7 @@ EXPORTS = [
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
     "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
-    "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity",
+    "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity", "np_hip_index_remove",
 ]
 
 _lib = None
@@ -462,6 +462,7 @@ def lib():
         f.argtypes = [C.c_char_p, vp, vp, i64, i32, C.POINTER(np_update_config), i32, C.POINTER(np_update_report)]
     L.np_hip_index_delete.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     L.np_hip_index_append.argtypes = [vp, vp, i64, vp, vp]
+    L.np_hip_index_remove.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.np_hip_index_reserve.argtypes = [vp, i64, i64]
     L.np_hip_index_capacity.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.np_hip_pooled_lengths.argtypes = [vp, i64, C.POINTER(np_pool_opts), vp]
@@ -1471,8 +1472,46 @@ class MmapIndex:
 
     def delete(self, doc_ids) -> int:
         """MmapIndex::delete (index.rs:1731-1765): rewrites the directory and returns the count removed; like the crate
-        it does not reload (call reload(); that drops the metadata columns, whose rows no longer match the new ids)."""
+        it does not reload (call reload(); that drops the metadata columns, whose rows no longer match the new ids).
+        remove() does the same and brings the resident handle along, without the reload."""
         return delete_from_index_dir(self._dir("delete"), doc_ids)
+
+    # -- remove from the resident index (np_hip_index_remove) ----------------------------------------------
+    def remove_ids(self, doc_ids) -> int:
+        """np_hip_index_remove on any unsharded handle: the listed documents leave the handle without the index being read
+        again.  delete()'s semantics: ids outside [0, num_documents()) are ignored, duplicates count once, surviving document
+        d becomes d minus the removed ids below it.  The handle then equals one freshly opened on the shrunk index.  Metadata
+        columns, the keyword index and the groups are dropped when something was removed, as reload() leaves a handle;
+        capacity() does not shrink.  Searches on other threads go on: the running ones finish on the old index, the next ones
+        see the new.  Returns the number of documents removed."""
+        ids = np.ascontiguousarray(np.asarray(doc_ids, np.int64).reshape(-1))
+        out = C.c_int64(0)
+        _check(lib().np_hip_index_remove(self._h, _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
+        if out.value:
+            self.schema = None
+            self.text = None
+            self.group_values = None
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+        return int(out.value)
+
+    def remove(self, doc_ids) -> int:
+        """delete() on the handle's directory AND np_hip_index_remove on the handle: where delete() + reload() read the whole
+        index again, this costs one pass over the posting lists and one move of the tokens behind the first removed
+        document.  The handle equals MmapIndex.load of the directory afterwards (no columns, keyword index or groups: attach
+        them again).  Returns the number of documents removed."""
+        path = self._dir("remove")
+        # whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with
+        # its directory, and (a remove of no ids runs the library's checks of the handle: shards)
+        n_before = _dir_counts(path)
+        if n_before[0] != self.num_documents():
+            raise IndexLoadError(f"Index load failed: the directory holds {n_before[0]} documents, the handle "
+                                 f"{self.num_documents()}: the handle is not current, reload()")
+        _check(lib().np_hip_index_remove(self._h, None, 0, None))
+        n = delete_from_index_dir(path, doc_ids)
+        m = self.remove_ids(doc_ids)
+        if m != n:
+            raise IndexLoadError(f"Index load failed: the directory lost {n} documents, the handle {m}: reload()")
+        return n
 
     # -- append to the resident index (np_hip_index_append) ------------------------------------------------
     def append_arrays(self, doc_lengths, codes, residuals):
@@ -1504,8 +1543,8 @@ class MmapIndex:
         """update_append on the handle's directory AND on the handle: the documents are encoded once, by update_append_dir,
         and the codes and residuals it wrote to the chunk files go to np_hip_index_append -- where update() reloads the whole
         index, this costs the new documents plus one pass over the posting lists.  The handle equals MmapIndex.load of the
-        directory afterwards (no columns, keyword index or groups: attach them again).  Not for centroid expansion or
-        delete: those change K or re-sequence the ids, so update() / delete() + reload() remain.  Returns the new ids."""
+        directory afterwards (no columns, keyword index or groups: attach them again).  Not for centroid expansion: that
+        changes K, so update() remains; for delete see remove().  Returns the new ids."""
         path = self._dir("append")
         # whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with
         # its directory, and (an append of no documents runs the library's checks of the handle: shards, list order)
