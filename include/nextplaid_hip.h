@@ -1234,7 +1234,8 @@ int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n
  * unchanged all the same).  Not covered: centroid expansion (K changes) -- reload.  Delete: np_hip_index_remove (below).
  *
  * Attachments: metadata columns, the keyword index and the groups are DROPPED, as a reload leaves a handle: their rows no
- * longer cover the documents.  np_hip_index_set_columns / _set_text / _set_groups attach the grown ones.
+ * longer cover the documents.  np_hip_index_set_columns / _set_text / _set_groups attach the grown ones, or
+ * np_hip_index_append_rows (below) takes the new documents' rows and keeps columns and groups.
  *
  * Memory: capacity grows first and commits nothing.  Without a reservation every per-token array (codes, residuals, inverse
  * norms) grows by allocate, copy device to device, free -- one array at a time, so the peak is the LARGEST ARRAY TWICE (the
@@ -1285,7 +1286,7 @@ int np_hip_index_capacity(const np_index* index, int64_t* docs, int64_t* tokens)
  *
  * Capacity (np_hip_index_capacity) does not shrink: the freed room is a reservation, an append that fits in it moves no
  * per-token array.  Attachments -- metadata columns, the keyword index, the groups -- are DROPPED, as a reload leaves a
- * handle; compacting them is out of scope: attach the survivors' rows again.
+ * handle: attach the survivors' rows again, or call np_hip_index_remove_keep (below), which compacts columns and groups.
  *
  * Memory: everything that allocates happens before anything that serves is overwritten -- the survivor bitmap and the new
  * doc offsets, the codes compacted BESIDE the old ones (2 to 4 of the ~145 bytes per token), the distinct-code blocks built
@@ -1297,6 +1298,68 @@ int np_hip_index_capacity(const np_index* index, int64_t* docs, int64_t* tokens)
  * Concurrency: as np_hip_index_append (above).  NP_REMOVE_TRACE=1 prints the stages' seconds and the two kernels' own times
  * to stderr (tools/remove_time.py reads them). */
 int np_hip_index_remove(np_index* index, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed);
+
+/* ---- remove from a RESIDENT index and KEEP its columns and groups (np_index.hip) -----------------------------------------
+ * np_hip_index_remove_keep is np_hip_index_remove with one difference: the metadata columns (with their dictionary text) and
+ * the groups are compacted and renumbered with the documents, on the device, and stay attached.  Afterwards the handle equals
+ * a fresh one of the shrunk arrays with np_hip_index_set_columns / _set_column_text / _set_groups of the surviving rows:
+ *  - a column keeps its type; the survivor with new id j has the value and the validity of its old row; a column whose
+ *    surviving rows hold no NULL has no validity bitmap (as set_columns leaves it), one without a bitmap stays without;
+ *  - the code range of a CODE column that np_hip_index_set_column_text checks is that of the surviving rows, so a shorter
+ *    dictionary is accepted exactly as on a fresh handle; the text on the device is per code, not per document, and stays;
+ *  - the groups keep n_groups: an emptied group is a group without members;
+ *  - np_info.device_bytes follows the new sizes.
+ * The keyword index is DROPPED: its term numbering follows the vocabulary, and a term whose last row is removed renumbers the
+ * rest.  np_hip_text_build_merge computes the index of the surviving rows; the host mirrors compose the two calls.
+ *
+ * Removing nothing changes nothing.  Removing EVERY document leaves what the setters make of an empty handle: columns without
+ * rows (no bitmap, the empty code range), and NO groups -- np_hip_index_set_groups takes no ids as "drop the groups".
+ *
+ * Memory: the new column, validity and group arrays (at most 8 bytes per document and column) are allocated and filled BESIDE
+ * the old ones before anything that serves is overwritten, in the remove's own order: NP_ERR_OUT_OF_MEMORY up to there leaves
+ * the index and its attachments unchanged.  Refusals and concurrency are np_hip_index_remove's: a filtered or grouped call that
+ * runs beside it sees the old index with the old attachments or the new with the new, never a mixture.  NP_REMOVE_TRACE=1
+ * also prints the compaction kernels' own time and rate. */
+int np_hip_index_remove_keep(np_index* index, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed);
+
+/* ---- append to a RESIDENT index WITH the new documents' rows (np_index.hip) --------------------------------------------------
+ * np_hip_index_append_rows is np_hip_index_append (its first five arguments, its checks, its memory and failure order, its
+ * concurrency) with the new documents' rows: the columns and the groups stay attached and grow with the index.  Afterwards the
+ * handle equals a fresh one of the grown arrays with np_hip_index_set_columns / _set_groups of all rows.
+ *  - new_cols[i] holds the n_docs NEW entries of column i (data, valid: bytes over the new documents alone).  n_cols must equal
+ *    the handle's column count and every type its column's type.  A column without a validity bitmap gets one only if a new
+ *    row is NULL (all earlier rows are then valid); an f64 NaN is NULL, as in set_columns.
+ *  - code_remap (nullable) has one entry per column, each NULL or, for a CODE column, an i32 table old code -> new code over
+ *    the codes 0 .. the largest code the handle's rows hold: the case of a dictionary that grew -- it is sorted by bytes, so
+ *    new strings shift codes.  It must be strictly increasing and not negative.  It is applied on the device to the old rows
+ *    that are not NULL (a NULL row's code means nothing and keeps its bytes); the new rows come in new codes.  The column's
+ *    text on the device, if any, is DROPPED with a remap: np_hip_index_set_column_text sets the grown dictionary.
+ *  - new_groups: n_docs ids in [0, n_groups), n_groups >= the handle's.  Required when the handle has groups, refused when it
+ *    has none; in the same way n_cols = 0 is required of a handle without columns.
+ *  - The keyword index is DROPPED, as by np_hip_index_remove_keep: the host mirrors compose np_hip_text_build_merge.
+ * Every violation is NP_ERR_INVALID_ARGUMENT, by name, before any allocation, the handle answering as it did with the
+ * attachments it had.  n_docs == 0 runs the checks and changes nothing (no remap either).
+ *
+ * Memory: the per-document attachment arrays grow to the handle's document capacity with d_doc_offsets -- in this call and in
+ * np_hip_index_reserve -- so an append inside a reservation moves none of them (np_hip_index_set_columns itself allocates
+ * for the documents the handle has: reserve after it).  The new rows are staged on the device, and a first validity bitmap
+ * allocated, before anything that serves is touched: NP_ERR_OUT_OF_MEMORY up to there leaves index and attachments as they
+ * were.  The validity bits of the new rows are merged at the word that holds the old last document.  What comes after --
+ * the remap, the rows' move, the merge, the code range read back -- allocates nothing; if the device stops answering there the
+ * call returns NP_ERR_DEVICE_UNAVAILABLE with the handle already grown, as np_hip_index_remove does for its token move. */
+int np_hip_index_append_rows(np_index* index, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes,
+                             const uint8_t* residuals, const np_column* new_cols, int32_t n_cols,
+                             const int32_t* const* code_remap, const int32_t* new_groups, int64_t n_groups);
+
+/* Read the handle's attachments back to the host, array for array.  np_hip_index_get_column: `data` (nullable) takes the
+ * column's rows over the documents this handle holds (i64 / f64 / i32 by *type), `valid` (nullable) one byte per document, 0 =
+ * NULL (all 1 where the column has no bitmap); *type and *has_valid (nullable) report the column's type and whether it holds
+ * a validity bitmap.  np_hip_index_get_groups: `out` takes the group of every document.  NP_ERR_INVALID_ARGUMENT, by name: a
+ * NULL handle, a column outside the handle's, a handle without groups.  Both are registered like the entries that check the
+ * attachments before they take a context: an append or a remove waits for them. */
+int np_hip_index_get_column(const np_index* index, int32_t column, void* data, uint8_t* valid, int32_t* type,
+                            int32_t* has_valid);
+int np_hip_index_get_groups(const np_index* index, int32_t* out);
 
 /* ---- token pooling: pool_document_embeddings (np_pool.hip) --------------------------------------------------------------
  * next-plaid-onnx pools every document before it reaches the index (src/lib.rs:1632-1643 pool_document_embeddings ->

@@ -587,25 +587,94 @@ class MmapIndex {
     for (size_t i = 0; i < ids.size(); ++i) ids[i] = first + (int64_t)i;
     return ids;
   }
+  // ... with the new documents' rows (np_hip_index_append_rows): columns and groups stay attached and grow with the index.
+  // `columns` holds one span per column of the handle over the NEW documents; `code_remap` is empty or has one entry per
+  // column, each nullptr or the table old code -> new code of a dictionary that grew (its text on the device is then dropped:
+  // set_column_text sets the grown dictionary); `groups` one id per new document in [0, n_groups), empty where the handle has
+  // no groups.  The keyword index is dropped by the library: update_text_index(base, {add = the new texts}) and set_text
+  // bring it along.
+  struct AppendedRows {
+    std::vector<ColumnSpan> columns;
+    std::vector<const int32_t*> code_remap;
+    std::vector<int32_t> groups;
+    int64_t n_groups = 0;
+  };
+  std::vector<int64_t> append_arrays(const std::vector<int64_t>& doc_lengths, const int64_t* codes, const uint8_t* residuals,
+                                     const AppendedRows& rows) {
+    require_device("append_arrays");
+    std::vector<np_column> c;
+    for (const ColumnSpan& s : rows.columns) {
+      if (s.size != doc_lengths.size()) throw Error(NP_ERR_SHAPE, "Shape error: a column needs one new entry per new document");
+      c.push_back(np_column{s.type, 0, s.data, s.valid});
+    }
+    if (!rows.code_remap.empty() && rows.code_remap.size() != rows.columns.size())
+      throw Error(NP_ERR_SHAPE, "Shape error: code_remap needs one entry per column, or none");
+    if (!rows.groups.empty() && rows.groups.size() != doc_lengths.size())
+      throw Error(NP_ERR_SHAPE, "Shape error: groups needs one id per new document");
+    const int64_t first = info_.num_documents;
+    check(np_hip_index_append_rows(h_, doc_lengths.data(), (int64_t)doc_lengths.size(), codes, residuals, c.data(), (int32_t)c.size(),
+                                   rows.code_remap.empty() ? nullptr : rows.code_remap.data(),
+                                   rows.groups.empty() ? nullptr : rows.groups.data(), rows.n_groups));
+    check(np_hip_index_info(h_, &info_));
+    std::vector<int64_t> ids(doc_lengths.size());
+    for (size_t i = 0; i < ids.size(); ++i) ids[i] = first + (int64_t)i;
+    return ids;
+  }
   // update_append on the handle's directory AND on the handle: the documents are encoded once, by np_hip_index_update_append,
   // and the codes and residuals it wrote to the chunk files are what np_hip_index_append gets
   std::vector<int64_t> append(const Documents& docs, const UpdateConfig& cfg = {}, int device = 0, np_update_report* report = nullptr) {
+    return append_by(
+        docs, cfg, device, report, [&] { check(np_hip_index_append(h_, nullptr, 0, nullptr, nullptr)); },
+        [&](const detail::AppendedTokens& t) { (void)append_arrays(t.doc_lengths, t.codes.data(), t.residuals.data()); });
+  }
+  // ... with the new documents' rows (its own name: append(docs, {}) keeps meaning a default UpdateConfig).  What the library
+  // refuses of the rows is found before the directory is touched
+  std::vector<int64_t> append_with_rows(const Documents& docs, const AppendedRows& rows, const UpdateConfig& cfg = {}, int device = 0,
+                                        np_update_report* report = nullptr) {
+    if (!rows.code_remap.empty() && rows.code_remap.size() != rows.columns.size())
+      throw Error(NP_ERR_SHAPE, "Shape error: code_remap needs one entry per column, or none");
+    for (const ColumnSpan& s : rows.columns)
+      if (s.size != docs.doc_lengths.size()) throw Error(NP_ERR_SHAPE, "Shape error: a column needs one new entry per new document");
+    if (!rows.groups.empty() && rows.groups.size() != docs.doc_lengths.size())
+      throw Error(NP_ERR_SHAPE, "Shape error: groups needs one id per new document");
+    return append_by(
+        docs, cfg, device, report,
+        [&] {   // an append of no documents runs the library's checks of the rows too: column count, types, remaps, group presence
+          if (!docs.doc_lengths.empty() && (np_hip_index_group_count(h_) > 0) != !rows.groups.empty())
+            throw Error(NP_ERR_INVALID_ARGUMENT, "Invalid argument: append: groups are needed of a handle with groups, and of no other");
+          std::vector<np_column> c;
+          for (const ColumnSpan& s : rows.columns) c.push_back(np_column{s.type, 0, s.data, s.valid});
+          check(np_hip_index_append_rows(h_, nullptr, 0, nullptr, nullptr, c.data(), (int32_t)c.size(),
+                                         rows.code_remap.empty() ? nullptr : rows.code_remap.data(),
+                                         rows.groups.empty() ? nullptr : rows.groups.data(), rows.n_groups));
+        },
+        [&](const detail::AppendedTokens& t) { (void)append_arrays(t.doc_lengths, t.codes.data(), t.residuals.data(), rows); });
+  }
+
+ private:
+  // the two appends differ in the check of the handle before the directory is touched and in the entry the tokens go to (a
+  // program that never appends rows never names the entry that takes them)
+  template <class Check, class Put>
+  std::vector<int64_t> append_by(const Documents& docs, const UpdateConfig& cfg, int device, np_update_report* report, Check&& check_handle,
+                                 Put&& put) {
     require_device("append");
     // whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with its
     // directory, and (an append of no documents runs the library's checks of the handle: shards, list order)
     const detail::DirCounts before = detail::dir_counts(path);
     if (before.documents != info_.num_documents)
       throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the handle is not current with its directory: reload()");
-    check(np_hip_index_append(h_, nullptr, 0, nullptr, nullptr));
+    check_handle();
     const np_update_config c = cfg.c();
     np_update_report r{};
     check(np_hip_index_update_append(path.c_str(), docs.embeddings, docs.doc_lengths.data(), (int64_t)docs.doc_lengths.size(),
                                      (int32_t)docs.dim, &c, device, &r));
     if (report) *report = r;
     const detail::AppendedTokens t = detail::appended_tokens(path, before);
-    (void)append_arrays(t.doc_lengths, t.codes.data(), t.residuals.data());
+    put(t);
     return update_ids(r, docs.doc_lengths.size());
   }
+
+ public:
   // room for this many MORE documents / tokens, so that later appends move no per-token array (without it every array grows
   // by allocate, copy, free: a peak of the largest array twice).  A service reserves right after load()
   void reserve(int64_t extra_docs, int64_t extra_tokens) {
@@ -638,29 +707,71 @@ class MmapIndex {
   // again, these cost one pass over the posting lists and one move of the tokens behind the first removed document.  The
   // semantics are delete_documents': ids outside the index are ignored, duplicates count once, the survivors are renumbered.
   // The handle then equals one freshly opened on the shrunk index; columns, keyword index and groups are dropped, as reload()
-  // leaves a handle; capacity() does not shrink.  Unsharded handles.  The handle alone:
-  int64_t remove_ids(const std::vector<int64_t>& doc_ids) {
+  // leaves a handle; capacity() does not shrink.  Unsharded handles.  keep_attachments goes through np_hip_index_remove_keep:
+  // columns (with their dictionary text) and groups are compacted with the documents on the device and stay attached; the
+  // keyword index is dropped by the library all the same -- update_text_index(base, {delete = the removed ids}) and set_text
+  // bring it along.  The handle alone:
+  int64_t remove_ids(const std::vector<int64_t>& doc_ids) { return remove_ids_by(np_hip_index_remove, doc_ids); }
+  int64_t remove_ids(const std::vector<int64_t>& doc_ids, bool keep_attachments) {
+    return keep_attachments ? remove_ids_by(np_hip_index_remove_keep, doc_ids) : remove_ids(doc_ids);
+  }
+  // A column / the groups as the handle holds them, read back from HBM (np_hip_index_get_column / _get_groups).  `data` takes
+  // the rows' bytes (8 per row for I64 and F64, 4 for CODE), `valid` one byte per row (all 1 where the column has no bitmap)
+  struct ColumnRows {
+    int32_t type = 0;
+    bool has_valid = false;
+    std::vector<uint8_t> data, valid;
+  };
+  ColumnRows get_column(int column) const {
+    require_device("get_column");
+    ColumnRows r;
+    int32_t has = 0;
+    check(np_hip_index_get_column(h_, column, nullptr, nullptr, &r.type, &has));
+    const size_t n = (size_t)(info_.shard_doc_end - info_.shard_doc_begin);
+    r.data.resize(n * (r.type == NP_COL_CODE ? 4 : 8));
+    r.valid.resize(n);
+    check(np_hip_index_get_column(h_, column, r.data.data(), r.valid.data(), &r.type, &has));
+    r.has_valid = has != 0;
+    return r;
+  }
+  std::vector<int32_t> get_groups() const {
+    require_device("get_groups");
+    std::vector<int32_t> g((size_t)num_documents());
+    check(np_hip_index_get_groups(h_, g.data()));
+    return g;
+  }
+  // delete_documents() on the handle's directory AND np_hip_index_remove on the handle: it equals load() of the directory then
+  int64_t remove(const std::vector<int64_t>& doc_ids) { return remove_by(np_hip_index_remove, doc_ids); }
+  int64_t remove(const std::vector<int64_t>& doc_ids, bool keep_attachments) {
+    return keep_attachments ? remove_by(np_hip_index_remove_keep, doc_ids) : remove(doc_ids);
+  }
+
+ private:
+  // the two removes differ in the entry alone (a program that never keeps attachments never names the keeping entry)
+  using RemoveEntry = int (*)(np_index*, const int64_t*, int64_t, int64_t*);
+  int64_t remove_ids_by(RemoveEntry entry, const std::vector<int64_t>& doc_ids) {
     require_device("remove_ids");
     int64_t n = 0;
-    check(np_hip_index_remove(h_, doc_ids.data(), (int64_t)doc_ids.size(), &n));
+    check(entry(h_, doc_ids.data(), (int64_t)doc_ids.size(), &n));
     check(np_hip_index_info(h_, &info_));
     return n;
   }
-  // delete_documents() on the handle's directory AND np_hip_index_remove on the handle: it equals load() of the directory then
-  int64_t remove(const std::vector<int64_t>& doc_ids) {
+  int64_t remove_by(RemoveEntry entry, const std::vector<int64_t>& doc_ids) {
     require_device("remove");
     // whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with its
     // directory, and (a remove of no ids runs the library's checks of the handle: shards)
     const detail::DirCounts before = detail::dir_counts(path);
     if (before.documents != info_.num_documents)
       throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the handle is not current with its directory: reload()");
-    check(np_hip_index_remove(h_, nullptr, 0, nullptr));
+    check(entry(h_, nullptr, 0, nullptr));
     int64_t n = 0;
     check(np_hip_index_delete(path.c_str(), doc_ids.data(), (int64_t)doc_ids.size(), &n));
-    const int64_t m = remove_ids(doc_ids);
+    const int64_t m = remove_ids_by(entry, doc_ids);
     if (m != n) throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the directory lost another number of documents than the handle: reload()");
     return n;
   }
+
+ public:
   // MmapIndex::delete (delete.rs:43-268): the count removed; no reload, as the crate (ids outside the index are ignored).
   // remove() does the same and brings the handle along
   int64_t delete_documents(const std::vector<int64_t>& doc_ids) {

@@ -6,6 +6,7 @@
 // Also: the seeded synthetic corpus generator (bench / scale tests) and export back to host.
 #include "np_internal.h"
 #include "np_remove_plan.h"
+#include "np_attach_plan.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -1728,6 +1729,75 @@ static void drop_attachments(DeviceIndex* ix) {
   ix->column_bytes = ix->coltext_bytes = ix->text_bytes = ix->group_bytes = 0;
 }
 
+// room for need_docs rows in the per-document attachment arrays (columns, validity, groups): grown to the handle's document
+// capacity, like d_doc_offsets, so that an append inside a reservation moves none of them.  The filter kernels' table follows
+// the arrays that moved, also where a later one failed to grow.
+static int grow_attachments(DeviceIndex* ix, int64_t need_docs) {
+  const size_t cap = (size_t)std::max(ix->cap_docs, need_docs), n = (size_t)ix->n_docs, need = (size_t)need_docs;
+  int rc = NP_OK;
+  bool moved = false;
+  for (size_t c = 0; c < ix->columns.size() && rc == NP_OK; ++c) {
+    DeviceColumn& col = ix->columns[c];
+    const size_t esz = col.type == NP_COL_CODE ? 4 : 8, before = ix->device_bytes;
+    if (col.data.bytes() < need * esz) {
+      rc = grow_array(ix, col.data, n * esz, cap * esz);
+      moved = moved || rc == NP_OK;
+    }
+    if (rc == NP_OK && col.has_valid && col.valid.bytes() < (need + 31) / 32 * 4) {
+      rc = grow_array(ix, col.valid, (n + 31) / 32, (cap + 31) / 32);
+      moved = moved || rc == NP_OK;
+    }
+    ix->column_bytes += ix->device_bytes - before;
+  }
+  if (moved) {
+    std::vector<FilterCol> tab;
+    for (const DeviceColumn& col : ix->columns)
+      tab.push_back(FilterCol{col.data.get(), col.has_valid ? col.valid.get() : nullptr, col.type, 0});
+    const hipError_t e = hipMemcpy(ix->d_coltab.get(), tab.data(), tab.size() * sizeof(FilterCol), hipMemcpyHostToDevice);
+    if (e != hipSuccess && rc == NP_OK) {
+      set_error("HIP error: %s", hipGetErrorString(e));
+      rc = NP_ERR_DEVICE_UNAVAILABLE;
+    }
+  }
+  if (rc == NP_OK && ix->n_groups > 0 && ix->d_groups.bytes() < need * 4) {
+    const size_t before = ix->device_bytes;
+    rc = grow_array(ix, ix->d_groups, n, cap);
+    ix->group_bytes += ix->device_bytes - before;
+  }
+  return rc;
+}
+
+// the rows of the new documents that np_hip_index_append_rows takes, as its arguments give them
+struct AppendRows {
+  const np_column* cols;
+  int32_t n_cols;
+  const int32_t* const* remap;   // nullable, and so is every entry
+  const int32_t* groups;
+  int64_t n_groups;
+};
+// one workgroup's share of what np_hip_index_set_columns derives from a column's rows (attach_stats_kernel)
+struct AttachStats {
+  int32_t min_code, max_code;
+  long long valid;
+};
+// ... and staged on the device, with everything that has to be allocated for them, before anything that serves is touched
+struct StagedRows {
+  struct Col {
+    DevPtr<uint8_t> rows;          // the new rows' values
+    DevPtr<uint32_t> tail;         // their validity bits at their final positions, from the word of document N0 on
+    DevPtr<uint32_t> fresh_valid;  // the bitmap of a column that had none and gains its first NULL
+    DevPtr<int32_t> remap;
+    int64_t n_remap = 0;
+    bool remapped = false;         // a remap is given, also one over no codes at all
+    bool any_null = false;
+  };
+  std::vector<Col> cols;
+  DevPtr<int32_t> groups;
+  DevPtr<AttachStats> d_stats;
+};
+static int stage_appended_rows(const DeviceIndex* ix, const AppendRows& rows, int64_t N0, int64_t N1, StagedRows* st);
+static int install_appended_rows(DeviceIndex* ix, const AppendRows& rows, StagedRows&& st, int64_t N0, int64_t N1);
+
 // a limit of the open path met by an append: the same check, reported as the append's argument
 static int as_append_argument(int rc, const char* arg) {
   if (rc == NP_OK || rc == NP_ERR_OUT_OF_MEMORY || rc == NP_ERR_DEVICE_UNAVAILABLE) return rc;
@@ -1736,8 +1806,9 @@ static int as_append_argument(int rc, const char* arg) {
   return NP_ERR_INVALID_ARGUMENT;
 }
 
+// rows: the new documents' column rows and groups (np_hip_index_append_rows), where the plain append drops the attachments
 static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, const int64_t* codes, const uint8_t* residuals,
-                            int64_t Tn, int64_t maxlen) {
+                            int64_t Tn, int64_t maxlen, const AppendRows* rows) {
   HoldContexts hold(ix);
   DeviceGuard g(ix->device);
   if (!g.ok) {
@@ -1750,6 +1821,7 @@ static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, con
   OpenTrace trace("NP_APPEND_TRACE", "np append");
   // 1. capacity first: commits nothing
   NP_TRY(grow_capacity(ix, N1, T1));
+  if (rows) NP_TRY(grow_attachments(ix, N1));
   trace.mark("grow");
   // 2. the new documents behind the old ones -- outside what any kernel reads until the counts move -- and the per-token
   //    stages over them alone
@@ -1792,7 +1864,16 @@ static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, con
                     merged ? ivf.get() : ix->d_ivf.get(), merged ? ioff.get() : ix->d_ivf_offsets.get()};
   NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
   trace.mark("range table");
+  // 6. the new documents' rows, staged beside the attachments that serve
+  StagedRows staged;
+  if (rows) {
+    NP_TRY(stage_appended_rows(ix, *rows, N0, N1, &staged));
+    trace.mark("rows staged");
+  }
   // ---- nothing below can fail: the handle becomes the grown index ----
+  int rows_rc = NP_OK;
+  if (rows) rows_rc = install_appended_rows(ix, *rows, std::move(staged), N0, N1);   // (not an allocation: a device that stopped answering)
+  else drop_attachments(ix);
   install_ucodes(ix, std::move(u));
   if (merged) {
     ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
@@ -1811,12 +1892,11 @@ static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, con
   ix->T = T1;
   ix->n_emb_total += Tn;
   ix->max_doc_len = std::max(ix->max_doc_len, maxlen);
-  drop_attachments(ix);
   ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
   ix->gain_run.store(0, std::memory_order_relaxed);
   ix->gain_skip.store(0, std::memory_order_relaxed);
   contexts_forget_index(ix);
-  return NP_OK;
+  return rows_rc;
 }
 
 // ---- remove from a resident index (np_hip_index_remove) ----------------------------------------------------------------
@@ -2132,8 +2212,327 @@ static int filter_posting_lists(const DeviceIndex* ix, const KeepMap& km, DevPtr
   return NP_OK;
 }
 
-// removed: the ids to remove -- in range, ascending, each once, not empty
-static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed) {
+// ---- the attachments through a remove (np_hip_index_remove_keep) ---------------------------------------------------------
+// A column is one array over the documents plus validity bits, the groups one i32 per document: each is an order-preserving
+// compaction by the same keep bitmap.  Output-driven: a wave owns 64 consecutive NEW ids, a lane finds its source document by
+// select over the bitmap (np_attach_plan.h: a bisection of the words' kept-count prefix, then the k-th set bit of the word)
+// -- once for all arrays, attach_select_kernel leaves the source ids in HBM --, loads the value and stores it coalesced; the
+// source's validity bit is read in the same lane and the wave's 64 bits leave as one ballot = two words of the new bitmap.
+// Lanes past the last survivor vote 0, so the bits past n_docs in the last word are zero, as np_hip_index_set_columns leaves
+// them.  No atomics, no workgroup waits for another, the same bytes from run to run.
+__global__ void __launch_bounds__(256) attach_select_kernel(KeepMap km, int64_t n_words, int64_t n_new, uint32_t* __restrict__ src_of) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n_new) src_of[j] = (uint32_t)attach_select(km.bits, km.wrank, n_words, j);
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) attach_compact_kernel(const uint32_t* __restrict__ src_of, int64_t n_old, int64_t n_new,
+                                                             const T* __restrict__ src, const uint32_t* __restrict__ src_valid,
+                                                             T* __restrict__ dst, uint32_t* __restrict__ dst_valid) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool ok = false;
+  if (j < n_new) {
+    const int64_t d = src_of[j];
+    if (d < n_old) {   // always, with a bitmap and ranks that agree
+      dst[j] = src[d];
+      ok = !src_valid || ((src_valid[d >> 5] >> (d & 31)) & 1u);
+    }
+  }
+  const unsigned long long word = __ballot(ok);
+  if (dst_valid && (threadIdx.x & 63) == 0) {
+    const int64_t v = j >> 5, nvw = (n_new + 31) >> 5;
+    if (v < nvw) dst_valid[v] = attach_ballot_word(word, 0);
+    if (v + 1 < nvw) dst_valid[v + 1] = attach_ballot_word(word, 1);
+  }
+}
+
+// what np_hip_index_set_columns derives from a column's rows, for the surviving ones: the range of a CODE column's codes (from
+// its start values 0 and -1) and the rows that are not NULL.  Every workgroup leaves one partial, the host folds them.
+#define NP_ATTACH_STAT_BLOCKS 128
+__global__ void __launch_bounds__(256) attach_stats_kernel(const int32_t* __restrict__ codes, const uint32_t* __restrict__ valid,
+                                                           int64_t n, AttachStats* __restrict__ out) {
+  __shared__ AttachStats part[4];
+  const int64_t stride = (int64_t)gridDim.x * 256, first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  AttachStats s{0, -1, 0};
+  if (codes)
+    for (int64_t i = first; i < n; i += stride) {
+      const int32_t c = codes[i];
+      s.min_code = min(s.min_code, c);
+      s.max_code = max(s.max_code, c);
+    }
+  if (valid)
+    for (int64_t i = first, nvw = (n + 31) >> 5; i < nvw; i += stride) s.valid += __popc(valid[i]);   // the tail bits are zero
+  for (int o = 32; o > 0; o >>= 1) {
+    s.min_code = min(s.min_code, __shfl_down(s.min_code, o));
+    s.max_code = max(s.max_code, __shfl_down(s.max_code, o));
+    s.valid += __shfl_down(s.valid, o);
+  }
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      s.min_code = min(s.min_code, part[w].min_code);
+      s.max_code = max(s.max_code, part[w].max_code);
+      s.valid += part[w].valid;
+    }
+    out[blockIdx.x] = s;
+  }
+}
+
+// the compacted attachments, built beside the ones that serve
+struct KeptAttachments {
+  std::vector<DeviceColumn> columns;   // data, validity and what is derived from the rows; the dictionary text stays where it is
+  DevPtr<FilterCol> d_coltab;
+  size_t column_bytes = 0;
+  DevPtr<int32_t> d_groups;
+  size_t group_bytes = 0;
+};
+
+static int compact_attachments(const DeviceIndex* ix, const KeepMap& km, int64_t W, int64_t N0, int64_t N1, KeptAttachments* k,
+                               const OpenTrace& trace) {
+  const size_t nc = ix->columns.size();
+  const int64_t nvw = (N1 + 31) / 32;
+  const size_t cap = (size_t)ix->cap_docs;   // the arrays keep the handle's document capacity: a later append moves none of them
+  const unsigned grid = (unsigned)((N1 + 255) / 256);
+  const int sblocks = (int)std::min<int64_t>(NP_ATTACH_STAT_BLOCKS, grid);
+  DevPtr<AttachStats> d_stats;
+  DevPtr<uint32_t> d_src;   // the old id of every survivor, by new id
+  NP_TRY(d_src.alloc((size_t)N1));
+  k->columns.resize(nc);
+  for (size_t c = 0; c < nc; ++c) {   // every allocation first: nothing is launched when one fails
+    const DeviceColumn& o = ix->columns[c];
+    DeviceColumn& f = k->columns[c];
+    f.type = o.type;
+    f.has_valid = o.has_valid && N1 > 0;
+    NP_TRY(f.data.alloc(cap * (o.type == NP_COL_CODE ? 4 : 8), &k->column_bytes));
+    if (f.has_valid) NP_TRY(f.valid.alloc((cap + 31) / 32, &k->column_bytes));
+  }
+  if (nc > 0) {
+    NP_TRY(k->d_coltab.alloc(nc, &k->column_bytes));
+    NP_TRY(d_stats.alloc(nc * NP_ATTACH_STAT_BLOCKS));
+  }
+  if (ix->n_groups > 0 && N1 > 0) NP_TRY(k->d_groups.alloc(cap, &k->group_bytes));
+  KernelClock clock(trace.on);
+  clock.start();
+  double bytes = 0;   // what the kernels read and write: the bitmap and the ranks, the source ids, rows and validity words
+  if (N1 > 0 && (nc > 0 || k->d_groups.get())) {
+    attach_select_kernel<<<grid, 256>>>(km, W, N1, d_src.get());
+    bytes += 12.0 * (double)W + 4.0 * (double)N1;
+  }
+  for (size_t c = 0; c < nc && N1 > 0; ++c) {
+    const DeviceColumn& o = ix->columns[c];
+    DeviceColumn& f = k->columns[c];
+    if (o.type == NP_COL_CODE)
+      attach_compact_kernel<uint32_t><<<grid, 256>>>(d_src.get(), N0, N1, reinterpret_cast<const uint32_t*>(o.data.get()),
+                                                     o.has_valid ? o.valid.get() : nullptr,
+                                                     reinterpret_cast<uint32_t*>(f.data.get()), f.valid.get());
+    else
+      attach_compact_kernel<uint64_t><<<grid, 256>>>(d_src.get(), N0, N1, reinterpret_cast<const uint64_t*>(o.data.get()),
+                                                     o.has_valid ? o.valid.get() : nullptr,
+                                                     reinterpret_cast<uint64_t*>(f.data.get()), f.valid.get());
+    bytes += (double)N1 * (4 + 2 * (o.type == NP_COL_CODE ? 4 : 8)) + (f.has_valid ? (double)nvw * 4 + (double)((N0 + 31) / 32) * 4 : 0);
+  }
+  if (k->d_groups.get()) {
+    attach_compact_kernel<uint32_t><<<grid, 256>>>(d_src.get(), N0, N1, reinterpret_cast<const uint32_t*>(ix->d_groups.get()), nullptr,
+                                                   reinterpret_cast<uint32_t*>(k->d_groups.get()), nullptr);
+    bytes += 3.0 * (double)N1 * 4;
+  }
+  NP_HIP(hipGetLastError());
+  const double sec = clock.stop();
+  if (trace.on)
+    fprintf(stderr, "[%s] %-28s %8.6f s  %.0f bytes %.1f GB/s\n", trace.tag, "attach kernel", sec, bytes,
+            sec > 0 ? bytes / sec * 1e-9 : 0.0);
+  // what set_columns derives from the rows: the code range, and no bitmap at all where no survivor is NULL
+  std::vector<AttachStats> h_stats(nc * NP_ATTACH_STAT_BLOCKS);
+  for (size_t c = 0; c < nc && N1 > 0; ++c) {
+    const DeviceColumn& f = k->columns[c];
+    if (f.type == NP_COL_CODE || f.has_valid)
+      attach_stats_kernel<<<(unsigned)sblocks, 256>>>(f.type == NP_COL_CODE ? reinterpret_cast<const int32_t*>(f.data.get()) : nullptr,
+                                                      f.valid.get(), N1, d_stats.get() + c * NP_ATTACH_STAT_BLOCKS);
+  }
+  NP_HIP(hipGetLastError());
+  if (nc > 0 && N1 > 0) NP_HIP(hipMemcpy(h_stats.data(), d_stats.get(), h_stats.size() * sizeof(AttachStats), hipMemcpyDeviceToHost));
+  std::vector<FilterCol> tab(nc);
+  for (size_t c = 0; c < nc; ++c) {
+    DeviceColumn& f = k->columns[c];
+    long long valid = 0;
+    for (int b = 0; b < sblocks && N1 > 0 && (f.type == NP_COL_CODE || f.has_valid); ++b) {
+      const AttachStats& s = h_stats[c * NP_ATTACH_STAT_BLOCKS + (size_t)b];
+      f.min_code = std::min(f.min_code, s.min_code);
+      f.max_code = std::max(f.max_code, s.max_code);
+      valid += s.valid;
+    }
+    if (f.has_valid && valid == N1) {
+      k->column_bytes -= f.valid.bytes();
+      f.valid.reset();
+      f.has_valid = false;
+    }
+    tab[c] = FilterCol{f.data.get(), f.has_valid ? f.valid.get() : nullptr, f.type, 0};
+  }
+  if (nc > 0) NP_HIP(hipMemcpy(k->d_coltab.get(), tab.data(), nc * sizeof(FilterCol), hipMemcpyHostToDevice));
+  NP_HIP(hipDeviceSynchronize());
+  return NP_OK;
+}
+
+// the handle's attachments become the compacted ones; the keyword index, whose term numbering a removed row can change, goes
+static void install_kept_attachments(DeviceIndex* ix, KeptAttachments&& k) {
+  for (size_t c = 0; c < ix->columns.size(); ++c) {
+    DeviceColumn& col = ix->columns[c];
+    DeviceColumn& f = k.columns[c];
+    col.data = std::move(f.data);
+    col.valid = std::move(f.valid);
+    col.has_valid = f.has_valid;
+    col.min_code = f.min_code;
+    col.max_code = f.max_code;
+  }
+  ix->d_coltab = std::move(k.d_coltab);
+  if (!k.d_groups.get()) ix->n_groups = 0;   // no document left: what np_hip_index_set_groups makes of no ids
+  ix->d_groups = std::move(k.d_groups);
+  ix->text = DeviceText();
+  ix->device_bytes = ix->device_bytes - ix->column_bytes - ix->group_bytes - ix->text_bytes + k.column_bytes + k.group_bytes;
+  ix->column_bytes = k.column_bytes;
+  ix->group_bytes = k.group_bytes;
+  ix->text_bytes = 0;
+}
+
+// ---- the attachments through an append (np_hip_index_append_rows) ----------------------------------------------------------
+// The new rows go behind the old ones in arrays that have the room (grow_attachments): outside what any kernel reads until
+// the counts move.  What does touch serving rows -- a dictionary remap over the old codes, the validity word the old last
+// document shares with the first new one -- happens once nothing can fail any more.
+
+// old code -> new code over the rows that are not NULL (a NULL row's code means nothing and keeps its bytes)
+__global__ void __launch_bounds__(256) attach_remap_kernel(int32_t* __restrict__ codes, const uint32_t* __restrict__ valid, int64_t n,
+                                                           const int32_t* __restrict__ remap, int64_t n_remap) {
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (d >= n || (valid && !((valid[d >> 5] >> (d & 31)) & 1u))) return;
+  const int32_t c = codes[d];
+  if (c >= 0 && c < n_remap) codes[d] = remap[c];
+}
+
+// valid[w0 + i] = tail[i], the first word merged with the old rows' bits (np_attach_plan.h attach_merge_word)
+__global__ void __launch_bounds__(256) attach_tail_merge_kernel(uint32_t* __restrict__ valid, const uint32_t* __restrict__ tail,
+                                                                int64_t w0, int64_t n_tail, int shared_bits, bool fresh) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_tail) return;
+  valid[w0 + i] = i == 0 ? attach_merge_word(fresh ? 0u : valid[w0], tail[0], shared_bits, fresh) : tail[i];
+}
+
+static int stage_appended_rows(const DeviceIndex* ix, const AppendRows& rows, int64_t N0, int64_t N1, StagedRows* st) {
+  const int64_t n = N1 - N0, w0 = N0 >> 5, n_tail = ((N1 + 31) >> 5) - w0;
+  const size_t cap_words = ((size_t)std::max(ix->cap_docs, N1) + 31) / 32;
+  st->cols.resize(ix->columns.size());
+  std::vector<uint32_t> bits;
+  for (size_t c = 0; c < ix->columns.size(); ++c) {
+    const DeviceColumn& col = ix->columns[c];
+    const np_column& in = rows.cols[c];
+    StagedRows::Col& s = st->cols[c];
+    const size_t esz = col.type == NP_COL_CODE ? 4 : 8;
+    NP_TRY(s.rows.alloc((size_t)n * esz));
+    NP_HIP(hipMemcpy(s.rows.get(), in.data, (size_t)n * esz, hipMemcpyHostToDevice));
+    // validity as np_hip_index_set_columns reads it: the caller's bytes, and an f64 NaN is NULL whatever they say
+    bits.assign((size_t)n_tail, 0u);
+    const double* f64 = col.type == NP_COL_F64 ? (const double*)in.data : nullptr;
+    for (int64_t i = 0; i < n; ++i) {
+      const bool ok = (!in.valid || in.valid[i] != 0) && (!f64 || f64[i] == f64[i]);
+      if (ok) bits[(size_t)(((N0 + i) >> 5) - w0)] |= 1u << ((N0 + i) & 31); else s.any_null = true;
+    }
+    if (col.has_valid || s.any_null) {
+      NP_TRY(s.tail.alloc((size_t)n_tail));
+      NP_HIP(hipMemcpy(s.tail.get(), bits.data(), (size_t)n_tail * 4, hipMemcpyHostToDevice));
+    }
+    if (!col.has_valid && s.any_null) NP_TRY(s.fresh_valid.alloc(cap_words));
+    if (rows.remap && rows.remap[c]) {
+      s.remapped = true;
+      s.n_remap = (int64_t)col.max_code + 1;
+      NP_TRY(s.remap.alloc((size_t)s.n_remap));
+      if (s.n_remap > 0) NP_HIP(hipMemcpy(s.remap.get(), rows.remap[c], (size_t)s.n_remap * 4, hipMemcpyHostToDevice));
+    }
+  }
+  if (ix->n_groups > 0) {
+    NP_TRY(st->groups.alloc((size_t)n));
+    NP_HIP(hipMemcpy(st->groups.get(), rows.groups, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  if (!ix->columns.empty()) NP_TRY(st->d_stats.alloc(ix->columns.size() * NP_ATTACH_STAT_BLOCKS));
+  return NP_OK;
+}
+
+// every context is held and every allocation is made: the rows join the handle's.  The keyword index, whose vocabulary the new
+// rows' text changes, goes.  An error here is a device that stopped answering.
+static int install_appended_rows(DeviceIndex* ix, const AppendRows& rows, StagedRows&& st, int64_t N0, int64_t N1) {
+  const int64_t n = N1 - N0, w0 = N0 >> 5, n_tail = ((N1 + 31) >> 5) - w0;
+  const size_t nc = ix->columns.size();
+  const int sblocks = (int)std::min<int64_t>(NP_ATTACH_STAT_BLOCKS, (N1 + 255) / 256);
+  bool table_changed = false;
+  for (size_t c = 0; c < nc; ++c) {
+    DeviceColumn& col = ix->columns[c];
+    StagedRows::Col& s = st.cols[c];
+    const size_t esz = col.type == NP_COL_CODE ? 4 : 8;
+    if (s.remapped) {
+      if (N0 > 0 && s.n_remap > 0)
+        attach_remap_kernel<<<(unsigned)((N0 + 255) / 256), 256>>>(reinterpret_cast<int32_t*>(col.data.get()),
+                                                                   col.has_valid ? col.valid.get() : nullptr, N0, s.remap.get(), s.n_remap);
+      col.text.reset();   // the text was the old dictionary's: np_hip_index_set_column_text sets the grown one
+      col.text_off.reset();
+      ix->device_bytes -= col.text_acct;
+      ix->coltext_bytes -= col.text_acct;
+      col.text_acct = 0;
+      col.n_strings = col.n_text_bytes = 0;
+    }
+    (void)hipMemcpyAsync(col.data.get() + (size_t)N0 * esz, s.rows.get(), (size_t)n * esz, hipMemcpyDeviceToDevice, nullptr);
+    if (s.tail.get()) {
+      const bool fresh = !col.has_valid;
+      if (fresh) {
+        (void)hipMemsetAsync(s.fresh_valid.get(), 0xff, (size_t)w0 * 4, nullptr);
+        ix->device_bytes += s.fresh_valid.bytes();
+        ix->column_bytes += s.fresh_valid.bytes();
+        col.valid = std::move(s.fresh_valid);
+        col.has_valid = true;
+        table_changed = true;
+      }
+      attach_tail_merge_kernel<<<(unsigned)((n_tail + 255) / 256), 256>>>(col.valid.get(), s.tail.get(), w0, n_tail, (int)(N0 & 31), fresh);
+    }
+    if (col.type == NP_COL_CODE)   // the code range of all rows, as np_hip_index_set_columns takes it
+      attach_stats_kernel<<<(unsigned)sblocks, 256>>>(reinterpret_cast<const int32_t*>(col.data.get()), nullptr, N1,
+                                                      st.d_stats.get() + c * NP_ATTACH_STAT_BLOCKS);
+  }
+  if (ix->n_groups > 0) {
+    (void)hipMemcpyAsync(ix->d_groups.get() + N0, st.groups.get(), (size_t)n * 4, hipMemcpyDeviceToDevice, nullptr);
+    ix->n_groups = rows.n_groups;
+  }
+  ix->text = DeviceText();
+  ix->device_bytes -= ix->text_bytes;
+  ix->text_bytes = 0;
+  std::vector<AttachStats> h_stats(nc * NP_ATTACH_STAT_BLOCKS);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && nc > 0)
+    e = hipMemcpy(h_stats.data(), st.d_stats.get(), h_stats.size() * sizeof(AttachStats), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && table_changed) {
+    std::vector<FilterCol> tab;
+    for (const DeviceColumn& col : ix->columns)
+      tab.push_back(FilterCol{col.data.get(), col.has_valid ? col.valid.get() : nullptr, col.type, 0});
+    e = hipMemcpy(ix->d_coltab.get(), tab.data(), nc * sizeof(FilterCol), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // the staged rows are freed when this returns
+  if (e != hipSuccess) {
+    set_error("np_hip_index_append_rows: the rows' move failed: %s", hipGetErrorString(e));
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  for (size_t c = 0; c < nc; ++c) {
+    DeviceColumn& col = ix->columns[c];
+    if (col.type != NP_COL_CODE) continue;
+    col.min_code = 0;
+    col.max_code = -1;
+    for (int b = 0; b < sblocks; ++b) {
+      col.min_code = std::min(col.min_code, h_stats[c * NP_ATTACH_STAT_BLOCKS + (size_t)b].min_code);
+      col.max_code = std::max(col.max_code, h_stats[c * NP_ATTACH_STAT_BLOCKS + (size_t)b].max_code);
+    }
+  }
+  return NP_OK;
+}
+
+// removed: the ids to remove -- in range, ascending, each once, not empty.  keep: columns and groups are compacted with the
+// documents (np_hip_index_remove_keep), where the plain remove drops them
+static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed, bool keep, const char* entry) {
   HoldContexts hold(ix);
   DeviceGuard g(ix->device);
   if (!g.ok) {
@@ -2213,6 +2612,12 @@ static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed
   const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide}, ivf.get(), ioff.get()};
   NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
   trace.mark("range table");
+  // 5b. columns and groups of the survivors, beside the ones that serve
+  KeptAttachments kept;
+  if (keep) {
+    NP_TRY(compact_attachments(ix, km, W, N0, N1, &kept, trace));
+    trace.mark("attachments");
+  }
   // 6. the staging buffer of the in-place moves: the last thing that can fail
   DevPtr<uint8_t> staging;
   if (plan.staging_bytes > 0) NP_TRY(staging.alloc((size_t)plan.staging_bytes));
@@ -2263,14 +2668,15 @@ static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed
   ix->T = T1;
   ix->n_emb_total -= T0 - T1;
   ix->max_doc_len = maxlen;
-  drop_attachments(ix);
+  if (keep) install_kept_attachments(ix, std::move(kept));
+  else drop_attachments(ix);
   ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
   ix->gain_run.store(0, std::memory_order_relaxed);
   ix->gain_skip.store(0, std::memory_order_relaxed);
   contexts_forget_index(ix);
   trace.mark("swap");
   if (moved != hipSuccess) {   // not an allocation: a device that stopped answering
-    set_error("np_hip_index_remove: the token move failed: %s", hipGetErrorString(moved));
+    set_error("%s: the token move failed: %s", entry, hipGetErrorString(moved));
     return NP_ERR_DEVICE_UNAVAILABLE;
   }
   return NP_OK;
@@ -2718,63 +3124,203 @@ int np_hip_index_probe_dir(const char* index_dir, np_info* out) {
   return NP_OK;
 }
 
-int np_hip_index_append(np_index* ix, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals) {
+// the new documents' rows against the handle's attachments: refused by name, before any allocation
+static int check_append_rows(const DeviceIndex* ix, const AppendRows& r, int64_t n_docs) {
+  const char* const e = "np_hip_index_append_rows";
+  const size_t nc = ix->columns.size();
+  if (r.n_cols < 0 || (size_t)r.n_cols != nc) {
+    set_error("%s: n_cols is %d, the handle has %zu columns", e, r.n_cols, nc);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (nc > 0 && n_docs > 0 && !r.cols) {
+    set_error("%s: new_cols is NULL, the handle has %zu columns", e, nc);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (size_t c = 0; c < nc && r.cols; ++c) {
+    const DeviceColumn& col = ix->columns[c];
+    if (r.cols[c].type != col.type) {
+      set_error("%s: new_cols[%zu] has type %d, column %zu of the handle type %d", e, c, r.cols[c].type, c, col.type);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    if (n_docs > 0 && !r.cols[c].data) {
+      set_error("%s: new_cols[%zu] has NULL data", e, c);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  }
+  for (size_t c = 0; c < nc && r.remap; ++c) {
+    if (!r.remap[c]) continue;
+    const DeviceColumn& col = ix->columns[c];
+    if (col.type != NP_COL_CODE) {
+      set_error("%s: code_remap[%zu] is given, column %zu is no CODE column", e, c, c);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    if (col.min_code < 0) {
+      set_error("%s: code_remap[%zu]: column %zu holds the negative code %d, which no table maps", e, c, c, col.min_code);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    const int64_t bad = attach_remap_check(r.remap[c], (int64_t)col.max_code + 1);
+    if (bad >= 0) {
+      set_error("%s: code_remap[%zu][%lld] = %d: a remap is not negative and strictly increasing (the dictionary stays sorted)", e, c,
+                (long long)bad, r.remap[c][bad]);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (ix->n_groups > 0) {
+    if (n_docs > 0 && !r.groups) {
+      set_error("%s: new_groups is NULL, the handle has groups", e);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    if (r.n_groups < ix->n_groups || r.n_groups > (int64_t)0x7FFFFFFF) {
+      set_error("%s: n_groups is %lld, the handle has %lld groups (and at most 2^31-1 fit)", e, (long long)r.n_groups, (long long)ix->n_groups);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    for (int64_t d = 0; d < n_docs; ++d)
+      if (r.groups[d] < 0 || (int64_t)r.groups[d] >= r.n_groups) {
+        set_error("%s: new_groups[%lld] = %d is outside [0, %lld)", e, (long long)d, r.groups[d], (long long)r.n_groups);
+        return NP_ERR_INVALID_ARGUMENT;
+      }
+  } else if (r.groups) {
+    set_error("%s: new_groups is given, the handle has no groups (np_hip_index_set_groups)", e);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+// np_hip_index_append and np_hip_index_append_rows: the same checks under the entry's own name
+static int append_entry(const char* entry, np_index* ix, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes,
+                        const uint8_t* residuals, const AppendRows* rows) {
   clear_error();
   if (!ix) {
-    set_error("np_hip_index_append: index is NULL");
+    set_error("%s: index is NULL", entry);
     return NP_ERR_INVALID_ARGUMENT;
   }
   if (ix->opts.shard_count > 1) {
-    set_error("np_hip_index_append: index is a shard (%d of %d): a sharded index is reloaded", ix->opts.shard_rank, ix->opts.shard_count);
+    set_error("%s: index is a shard (%d of %d): a sharded index is reloaded", entry, ix->opts.shard_rank, ix->opts.shard_count);
     return NP_ERR_INVALID_ARGUMENT;
   }
   if (!ix->ivf_sorted) {
-    set_error("np_hip_index_append: index has posting lists that do not ascend: only such lists grow at their end");
+    set_error("%s: index has posting lists that do not ascend: only such lists grow at their end", entry);
     return NP_ERR_INVALID_ARGUMENT;
   }
   if (n_docs < 0 || (n_docs > 0 && !doc_lengths)) {
-    set_error("np_hip_index_append: %s", n_docs < 0 ? "n_docs is negative" : "doc_lengths is NULL");
+    set_error("%s: %s", entry, n_docs < 0 ? "n_docs is negative" : "doc_lengths is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
+  if (rows) NP_TRY(check_append_rows(ix, *rows, n_docs));
   if (n_docs == 0) return NP_OK;
   int64_t Tn = 0, maxlen = 0;
   for (int64_t d = 0; d < n_docs; ++d) {
     if (doc_lengths[d] < 0) {
-      set_error("np_hip_index_append: doc_lengths[%lld] is negative (%lld)", (long long)d, (long long)doc_lengths[d]);
+      set_error("%s: doc_lengths[%lld] is negative (%lld)", entry, (long long)d, (long long)doc_lengths[d]);
       return NP_ERR_SHAPE;
     }
     Tn += doc_lengths[d];
     maxlen = std::max(maxlen, doc_lengths[d]);
   }
   if (Tn > 0 && (!codes || !residuals)) {
-    set_error("np_hip_index_append: %s is NULL", !codes ? "codes" : "residuals");
+    set_error("%s: %s is NULL", entry, !codes ? "codes" : "residuals");
     return NP_ERR_INVALID_ARGUMENT;
   }
   for (int64_t t = 0; t < Tn; ++t)
     if (codes[t] < 0 || codes[t] >= ix->K) {
-      set_error("np_hip_index_append: codes[%lld] = %lld is outside [0, %lld)", (long long)t, (long long)codes[t], (long long)ix->K);
+      set_error("%s: codes[%lld] = %lld is outside [0, %lld)", entry, (long long)t, (long long)codes[t], (long long)ix->K);
       return NP_ERR_INVALID_ARGUMENT;
     }
-  return append_documents(ix, doc_lengths, n_docs, codes, residuals, Tn, maxlen);
+  return append_documents(ix, doc_lengths, n_docs, codes, residuals, Tn, maxlen, rows);
 }
 
-int np_hip_index_remove(np_index* ix, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed) {
+int np_hip_index_append(np_index* ix, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals) {
+  return append_entry("np_hip_index_append", ix, doc_lengths, n_docs, codes, residuals, nullptr);
+}
+
+int np_hip_index_append_rows(np_index* ix, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals,
+                             const np_column* new_cols, int32_t n_cols, const int32_t* const* code_remap, const int32_t* new_groups,
+                             int64_t n_groups) {
+  const AppendRows rows{new_cols, n_cols, code_remap, new_groups, n_groups};
+  return append_entry("np_hip_index_append_rows", ix, doc_lengths, n_docs, codes, residuals, &rows);
+}
+
+// np_hip_index_remove and np_hip_index_remove_keep: the same checks under the entry's own name
+static int remove_entry(const char* entry, np_index* ix, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed, bool keep) {
   clear_error();
   if (!ix) {
-    set_error("np_hip_index_remove: index is NULL");
+    set_error("%s: index is NULL", entry);
     return NP_ERR_INVALID_ARGUMENT;
   }
   if (n_ids < 0 || (n_ids > 0 && !doc_ids)) {
-    set_error("np_hip_index_remove: %s", n_ids < 0 ? "n_ids is negative" : "doc_ids is NULL");
+    set_error("%s: %s", entry, n_ids < 0 ? "n_ids is negative" : "doc_ids is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
   if (ix->opts.shard_count > 1) {
-    set_error("np_hip_index_remove: index is a shard (%d of %d): a sharded index is reloaded", ix->opts.shard_rank, ix->opts.shard_count);
+    set_error("%s: index is a shard (%d of %d): a sharded index is reloaded", entry, ix->opts.shard_rank, ix->opts.shard_count);
     return NP_ERR_INVALID_ARGUMENT;
   }
   const std::vector<int64_t> removed = remove_ids_in_range(doc_ids, n_ids, ix->n_docs);
-  if (!removed.empty()) NP_TRY(remove_documents(ix, removed));   // none in range: nothing changes, the attachments stay
+  if (!removed.empty()) NP_TRY(remove_documents(ix, removed, keep, entry));   // none in range: nothing changes, the attachments stay
   if (out_removed) *out_removed = (int64_t)removed.size();
+  return NP_OK;
+}
+
+int np_hip_index_remove(np_index* ix, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed) {
+  return remove_entry("np_hip_index_remove", ix, doc_ids, n_ids, out_removed, false);
+}
+
+int np_hip_index_remove_keep(np_index* ix, const int64_t* doc_ids, int64_t n_ids, int64_t* out_removed) {
+  return remove_entry("np_hip_index_remove_keep", ix, doc_ids, n_ids, out_removed, true);
+}
+
+int np_hip_index_get_column(const np_index* ix, int32_t column, void* data, uint8_t* valid, int32_t* type, int32_t* has_valid) {
+  clear_error();
+  IndexRead reading(ix);   // an append or a remove waits for this call and holds later ones back (np_internal.h)
+  if (!ix) {
+    set_error("np_hip_index_get_column: index is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (column < 0 || (size_t)column >= ix->columns.size()) {
+    set_error("np_hip_index_get_column: column %d is outside the handle's %zu columns", column, ix->columns.size());
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  const DeviceColumn& col = ix->columns[(size_t)column];
+  if (type) *type = col.type;
+  if (has_valid) *has_valid = col.has_valid ? 1 : 0;
+  const int64_t n = ix->n_docs;
+  if (n == 0 || (!data && !valid)) return NP_OK;
+  DeviceGuard g(ix->device);
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", ix->device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  if (data) NP_HIP(hipMemcpy(data, col.data.get(), (size_t)n * (col.type == NP_COL_CODE ? 4 : 8), hipMemcpyDeviceToHost));
+  if (valid && !col.has_valid) memset(valid, 1, (size_t)n);
+  if (valid && col.has_valid) {
+    std::vector<uint32_t> bits((size_t)((n + 31) / 32));
+    NP_HIP(hipMemcpy(bits.data(), col.valid.get(), bits.size() * 4, hipMemcpyDeviceToHost));
+    for (int64_t d = 0; d < n; ++d) valid[d] = (uint8_t)((bits[(size_t)(d >> 5)] >> (d & 31)) & 1u);
+  }
+  return NP_OK;
+}
+
+int np_hip_index_get_groups(const np_index* ix, int32_t* out) {
+  clear_error();
+  IndexRead reading(ix);
+  if (!ix) {
+    set_error("np_hip_index_get_groups: index is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (ix->n_groups <= 0) {
+    set_error("np_hip_index_get_groups: the handle has no groups (np_hip_index_set_groups)");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (!out) {
+    set_error("np_hip_index_get_groups: out is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  DeviceGuard g(ix->device);
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", ix->device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  NP_HIP(hipMemcpy(out, ix->d_groups.get(), (size_t)ix->n_docs * 4, hipMemcpyDeviceToHost));
   return NP_OK;
 }
 
@@ -2799,7 +3345,8 @@ int np_hip_index_reserve(np_index* ix, int64_t extra_docs, int64_t extra_tokens)
     return NP_ERR_INVALID_ARGUMENT;
   }
   NP_HIP(hipDeviceSynchronize());
-  return grow_capacity(ix, ix->n_docs + extra_docs, ix->T + extra_tokens);
+  NP_TRY(grow_capacity(ix, ix->n_docs + extra_docs, ix->T + extra_tokens));
+  return grow_attachments(ix, ix->cap_docs);   // the columns' and the groups' arrays follow d_doc_offsets
 }
 
 int np_hip_index_capacity(const np_index* ix, int64_t* docs, int64_t* tokens) {

@@ -292,6 +292,7 @@ EXPORTS = [
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
     "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
     "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity", "np_hip_index_remove",
+    "np_hip_index_remove_keep", "np_hip_index_append_rows", "np_hip_index_get_column", "np_hip_index_get_groups",
 ]
 
 _lib = None
@@ -463,6 +464,10 @@ def lib():
     L.np_hip_index_delete.argtypes = [C.c_char_p, vp, i64, C.POINTER(i64)]
     L.np_hip_index_append.argtypes = [vp, vp, i64, vp, vp]
     L.np_hip_index_remove.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.np_hip_index_remove_keep.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.np_hip_index_append_rows.argtypes = [vp, vp, i64, vp, vp, C.POINTER(np_column), i32, vp, vp, i64]
+    L.np_hip_index_get_column.argtypes =[vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.np_hip_index_get_groups.argtypes = [vp, vp]
     L.np_hip_index_reserve.argtypes = [vp, i64, i64]
     L.np_hip_index_capacity.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.np_hip_pooled_lengths.argtypes = [vp, i64, C.POINTER(np_pool_opts), vp]
@@ -919,6 +924,18 @@ class UpdateConfig:
                                 int(self.n_samples_kmeans or 0), int(self.seed) & (2**64 - 1),
                                 -1 if int(self.start_from_scratch) == 0 else int(self.start_from_scratch),
                                 -1 if int(self.buffer_size) == 0 else int(self.buffer_size))
+
+
+@dataclass
+class AppendRows:
+    """What MmapIndex.append / append_arrays take with rows=: the new documents' attachment rows.  `columns`: name -> the new
+    entries, under exactly the names of the handle's columns (None where it has none); `groups`: one key per new document, as
+    set_groups takes them (ready int32 ids where the handle's groups were set with n_groups=, then with `n_groups`; None
+    where the handle has no groups); `texts`: the new documents' text for the keyword index (None where it has none)."""
+    columns: dict | None = None
+    groups: object = None
+    texts: object = None
+    n_groups: int | None = None
 
 
 def _update_docs(documents):
@@ -1477,15 +1494,36 @@ class MmapIndex:
         return delete_from_index_dir(self._dir("delete"), doc_ids)
 
     # -- remove from the resident index (np_hip_index_remove) ----------------------------------------------
-    def remove_ids(self, doc_ids) -> int:
+    def remove_ids(self, doc_ids, keep_attachments: bool = False) -> int:
         """np_hip_index_remove on any unsharded handle: the listed documents leave the handle without the index being read
         again.  delete()'s semantics: ids outside [0, num_documents()) are ignored, duplicates count once, surviving document
         d becomes d minus the removed ids below it.  The handle then equals one freshly opened on the shrunk index.  Metadata
         columns, the keyword index and the groups are dropped when something was removed, as reload() leaves a handle;
         capacity() does not shrink.  Searches on other threads go on: the running ones finish on the old index, the next ones
-        see the new.  Returns the number of documents removed."""
+        see the new.  Returns the number of documents removed.
+
+        keep_attachments=True goes through np_hip_index_remove_keep: columns and groups are compacted on the device and stay
+        attached -- self.schema keeps its dictionaries and has its row arrays shrunk, self.group_values stays -- and the
+        keyword index, which the library drops, is brought along by update_text(delete=<the removed ids>) from the one the
+        handle had."""
         ids = np.ascontiguousarray(np.asarray(doc_ids, np.int64).reshape(-1))
         out = C.c_int64(0)
+        if keep_attachments:
+            n0, saved = self.num_documents(), self.text
+            _check(lib().np_hip_index_remove_keep(self._h, _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
+            _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+            if out.value:
+                removed = np.unique(ids[(ids >= 0) & (ids < n0)])
+                if self.schema is not None:
+                    keep = np.ones(n0, bool)
+                    keep[removed] = False
+                    self.schema = self.schema.shrunk(keep)
+                if self.num_documents() == 0:
+                    self.group_values = None   # no document, no groups: what set_groups makes of no keys
+                self.text = None
+                if saved is not None:
+                    self.update_text(delete=removed, renumber=True, base=saved)
+            return int(out.value)
         _check(lib().np_hip_index_remove(self._h, _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
         if out.value:
             self.schema = None
@@ -1494,11 +1532,11 @@ class MmapIndex:
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         return int(out.value)
 
-    def remove(self, doc_ids) -> int:
+    def remove(self, doc_ids, keep_attachments: bool = False) -> int:
         """delete() on the handle's directory AND np_hip_index_remove on the handle: where delete() + reload() read the whole
         index again, this costs one pass over the posting lists and one move of the tokens behind the first removed
         document.  The handle equals MmapIndex.load of the directory afterwards (no columns, keyword index or groups: attach
-        them again).  Returns the number of documents removed."""
+        them again -- or pass keep_attachments=True, see remove_ids).  Returns the number of documents removed."""
         path = self._dir("remove")
         # whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with
         # its directory, and (a remove of no ids runs the library's checks of the handle: shards)
@@ -1506,22 +1544,79 @@ class MmapIndex:
         if n_before[0] != self.num_documents():
             raise IndexLoadError(f"Index load failed: the directory holds {n_before[0]} documents, the handle "
                                  f"{self.num_documents()}: the handle is not current, reload()")
-        _check(lib().np_hip_index_remove(self._h, None, 0, None))
+        _check((lib().np_hip_index_remove_keep if keep_attachments else lib().np_hip_index_remove)(self._h, None, 0, None))
         n = delete_from_index_dir(path, doc_ids)
-        m = self.remove_ids(doc_ids)
+        m = self.remove_ids(doc_ids, keep_attachments)
         if m != n:
             raise IndexLoadError(f"Index load failed: the directory lost {n} documents, the handle {m}: reload()")
         return n
 
     # -- append to the resident index (np_hip_index_append) ------------------------------------------------
-    def append_arrays(self, doc_lengths, codes, residuals):
+    def _plan_rows(self, rows: "AppendRows", n_new: int):
+        """The checks of an append with rows that need no library call but the group count, and the arrays the entry takes:
+        (schema, new columns, remaps, group ids, n_groups, group_values).  Raises before anything is touched."""
+        from . import filters as F
+        if not isinstance(rows, AppendRows):
+            raise TypeError("rows must be an AppendRows")
+        if self.text is not None and rows.texts is None:
+            raise ValueError("append: the handle has a keyword index and rows.texts is None: pass the new documents' text")
+        if self.text is None and rows.texts is not None:
+            raise ValueError("append: rows.texts is given and the handle has no keyword index (set_text / build_text)")
+        if rows.texts is not None and len(rows.texts) != n_new:
+            raise ShapeError(f"Shape error: rows.texts has {len(rows.texts)} entries for {n_new} new documents")
+        if (self.schema is None) != (not rows.columns):
+            raise F.FilterError("append: rows.columns must hold the new rows of exactly the handle's columns"
+                                if self.schema is not None else "append: rows.columns is given and the handle has no columns")
+        sch = new = remaps = None
+        if self.schema is not None:
+            sch, new, remaps = self.schema.extended(dict(rows.columns))
+            for c in new.values():
+                if c.data.shape[0] != n_new:
+                    raise ShapeError(f"Shape error: column '{c.name}' has {c.data.shape[0]} new entries for {n_new} new documents")
+        have = self.group_count()
+        if (have > 0) != (rows.groups is not None):
+            raise ValueError("append: the handle has groups and rows.groups is None" if have > 0 else
+                             "append: rows.groups is given and the handle has no groups (set_groups)")
+        gids, n_groups, values = None, 0, self.group_values
+        if have > 0:
+            if len(rows.groups) != n_new:
+                raise ShapeError(f"Shape error: rows.groups has {len(rows.groups)} entries for {n_new} new documents")
+            if values is None:   # ready ids
+                gids = np.ascontiguousarray(rows.groups, np.int32).reshape(-1)
+                n_groups = max(have, int(rows.n_groups or 0), int(gids.max()) + 1 if gids.size else 0)
+            else:                # keys: an existing key keeps its id, new keys take the next ids in the order they come
+                keys = rows.groups.tolist() if isinstance(rows.groups, np.ndarray) else list(rows.groups)
+                values = list(values) + ([None] if have == len(values) + 1 else [])   # (the NULLs' group, by its id)
+                where = {v: i for i, v in enumerate(values)}
+                for k in keys:
+                    if k is not None and (isinstance(k, bool) or not isinstance(k, (int, str, np.integer))):
+                        raise ValueError(f"a group key must be an int, a string or None, not {type(k).__name__}")
+                if len({isinstance(k, str) for k in list(values) + keys if k is not None}) > 1:   # set_groups' own rule
+                    raise ValueError("group keys must be all ints or all strings (None aside), the handle's and the new ones together")
+                for k in keys:
+                    if k not in where:
+                        where[k] = len(values)
+                        values.append(k)
+                gids, n_groups = np.fromiter((where[k] for k in keys), np.int32, len(keys)), len(values)
+        return sch, new, remaps, gids, n_groups, values
+
+    def append_arrays(self, doc_lengths, codes, residuals, rows: "AppendRows | None" = None):
         """np_hip_index_append on any unsharded handle: documents already encoded (codes i64 in [0, K), residuals u8
         [tokens, dim * nbits / 8] as np_hip_encode_tokens returns them) take the ids num_documents() .. and are served from
         the next call on, without reading the index again.  The handle then equals one freshly opened on the grown index.
         Metadata columns, the keyword index and the groups are dropped, as reload() leaves a handle (set_columns / set_text /
         set_groups attach the grown ones).  Searches on other threads go on: the running ones finish on the old index, the
-        next ones see the new.  Returns the new documents' ids."""
+        next ones see the new.  Returns the new documents' ids.
+
+        rows=AppendRows(...) goes through np_hip_index_append_rows instead: columns and groups stay attached and take the
+        new documents' rows.  self.schema becomes Schema.extended's (a text column's new strings join its sorted dictionary,
+        the old rows' codes move on the device, the dictionary text of text_on_device columns is sent again); new group keys
+        extend self.group_values at its end, existing ids never move (the NULLs' group, if any, is then the entry None); the
+        keyword index is brought along by update_text(new_texts=rows.texts) from the one the handle had.  A handle with a
+        keyword index and rows.texts=None is refused before anything is touched."""
         dl = np.ascontiguousarray(np.asarray(doc_lengths, np.int64).reshape(-1))
+        if rows is not None:
+            return self._append_arrays_rows(dl, codes, residuals, rows)
         cd = np.ascontiguousarray(np.asarray(codes, np.int64).reshape(-1))
         rs = np.ascontiguousarray(residuals, np.uint8)
         tokens = int(dl.sum()) if dl.size and (dl >= 0).all() else 0
@@ -1539,13 +1634,48 @@ class MmapIndex:
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         return np.arange(first, first + dl.size, dtype=np.int64)
 
-    def append(self, documents, config: UpdateConfig | None = None) -> np.ndarray:
+    def _append_arrays_rows(self, dl, codes, residuals, rows, plan=None):
+        sch, new, remaps, gids, n_groups, values = plan if plan is not None else self._plan_rows(rows, dl.size)
+        cd = np.ascontiguousarray(np.asarray(codes, np.int64).reshape(-1))
+        rs = np.ascontiguousarray(residuals, np.uint8)
+        tokens = int(dl.sum()) if dl.size and (dl >= 0).all() else 0
+        pd = self.embedding_dim() * int(self._info.nbits) // 8
+        if cd.size < tokens or rs.size < tokens * pd:
+            raise ShapeError(f"Shape error: {tokens} tokens need {tokens} codes and {tokens * pd} residual bytes, got "
+                             f"{cd.size} and {rs.size}")
+        n_cols = len(sch) if sch is not None else 0
+        cols = (np_column * max(n_cols, 1))()
+        tables = (C.c_void_p * max(n_cols, 1))()
+        for c in (new or {}).values():
+            cols[c.index] = np_column(c.type, 0, c.data.ctypes.data, None if c.valid is None else c.valid.ctypes.data)
+            tables[c.index] = None if remaps[c.name] is None else remaps[c.name].ctypes.data
+        first, saved = self.num_documents(), self.text
+        _check(lib().np_hip_index_append_rows(self._h, _ptr(dl) if dl.size else None, dl.size, _ptr(cd) if cd.size else None,
+                                              _ptr(rs) if rs.size else None, cols, n_cols,
+                                              C.cast(tables, C.c_void_p) if n_cols else None,
+                                              _ptr(gids) if gids is not None and gids.size else None, n_groups))
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+        if dl.size:
+            self.schema, self.group_values, self.text = sch, values, None
+            for c in (sch.columns.values() if sch is not None else ()):
+                if c.text_on_device and remaps[c.name] is not None:   # the library dropped the old dictionary's text
+                    text, off = c.text_arrays()
+                    _check(lib().np_hip_index_set_column_text(self._h, c.index, text.ctypes.data if text.size else None,
+                                                              _ptr(off), len(c.dictionary)))
+            if saved is not None:
+                self.update_text(new_texts=list(rows.texts), base=saved)
+            _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+        return np.arange(first, first + dl.size, dtype=np.int64)
+
+    def append(self, documents, config: UpdateConfig | None = None, rows: "AppendRows | None" = None) -> np.ndarray:
         """update_append on the handle's directory AND on the handle: the documents are encoded once, by update_append_dir,
         and the codes and residuals it wrote to the chunk files go to np_hip_index_append -- where update() reloads the whole
         index, this costs the new documents plus one pass over the posting lists.  The handle equals MmapIndex.load of the
-        directory afterwards (no columns, keyword index or groups: attach them again).  Not for centroid expansion: that
-        changes K, so update() remains; for delete see remove().  Returns the new ids."""
+        directory afterwards (no columns, keyword index or groups: attach them again -- or pass rows=AppendRows(...), see
+        append_arrays: they stay and take the new rows).  Not for centroid expansion: that changes K, so update() remains;
+        for delete see remove().  Returns the new ids."""
         path = self._dir("append")
+        plan = None if rows is None else self._plan_rows(rows, len(documents))   # refused before the directory is touched
         # whatever would refuse the handle's half is found BEFORE the directory is touched: a handle that is not current with
         # its directory, and (an append of no documents runs the library's checks of the handle: shards, list order)
         n_before = _dir_counts(path)
@@ -1555,7 +1685,10 @@ class MmapIndex:
         _check(lib().np_hip_index_append(self._h, None, 0, None, None))
         ids, self.last_update = update_append_dir(path, documents, config, self._open_opts.get("device", 0))
         lens, codes, residuals = _appended_tokens(path, n_before)
-        self.append_arrays(lens, codes, residuals)
+        if rows is None:
+            self.append_arrays(lens, codes, residuals)
+        else:
+            self._append_arrays_rows(np.ascontiguousarray(np.asarray(lens, np.int64).reshape(-1)), codes, residuals, rows, plan)
         return ids
 
     def reserve(self, extra_docs: int, extra_tokens: int):
@@ -1679,6 +1812,30 @@ class MmapIndex:
             raise
         self.schema = sch if len(sch) else None
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+
+    def get_column(self, name: str):
+        """np_hip_index_get_column: the rows of column `name` as the handle holds them, read back from HBM: (data, valid) with
+        data int64 / float64 / int32 codes by the column's type and valid a uint8 array, 0 = NULL, or None where the column
+        has no validity bitmap."""
+        from . import filters as F
+        if self.schema is None or name not in self.schema:
+            raise F.FilterError(f"unknown column '{name}'")
+        col = self.schema[name]
+        dtype = {F.NP_COL_I64: np.int64, F.NP_COL_F64: np.float64, F.NP_COL_CODE: np.int32}[col.type]
+        n = int(self._info.shard_doc_end - self._info.shard_doc_begin)
+        data, valid = np.zeros(n, dtype), np.zeros(n, np.uint8)
+        typ, has = C.c_int32(-1), C.c_int32(0)
+        _check(lib().np_hip_index_get_column(self._h, col.index, _ptr(data) if n else None, _ptr(valid) if n else None,
+                                             C.byref(typ), C.byref(has)))
+        if typ.value != col.type:
+            raise NextPlaidError(f"column '{name}' has type {typ.value} on the handle, {col.type} in the schema")
+        return data, (valid if has.value else None)
+
+    def get_groups(self) -> np.ndarray:
+        """np_hip_index_get_groups: the group id of every document, int32, read back from HBM."""
+        out = np.zeros(self.num_documents(), np.int32)
+        _check(lib().np_hip_index_get_groups(self._h, _ptr(out) if out.size else None))
+        return out
 
     def match_text(self, column: str, patterns, like: bool = False):
         """np_hip_text_match: for every pattern (a REGEXP pattern of regexes.py's dialect, a LIKE pattern with like=True, or a

@@ -61,6 +61,68 @@ class Schema:
     def __contains__(self, name):
         return name in self.columns
 
+    def shrunk(self, keep) -> "Schema":
+        """The schema of the rows `keep` (a boolean array over the documents) selects, in their order: what a handle holds
+        after MmapIndex.remove(..., keep_attachments=True).  Names, types, dictionaries (a code keeps its string, also one no
+        surviving row uses) and text_on_device stay; a column whose surviving rows hold no NULL has no validity array."""
+        keep = np.asarray(keep, bool)
+        out = Schema()
+        for name, c in self.columns.items():
+            valid = None if c.valid is None else np.ascontiguousarray(c.valid[keep])
+            out.columns[name] = Column(name, c.index, c.type, np.ascontiguousarray(c.data[keep]),
+                                       None if valid is None or valid.all() else valid, c.dictionary, c.text_on_device,
+                                       c.first_non_ascii)
+        return out
+
+    def extended(self, new_columns: dict):
+        """The schema after MmapIndex.append(..., rows=): `new_columns` holds, under exactly this schema's names, the new
+        documents' entries (as set_columns takes them).  Returns (schema, rows, remaps):
+          schema  all rows -- each text column's new strings merged into its sorted dictionary, the old rows' codes moved
+                  with it; it equals make_schema of the concatenated columns when every old string is still in use;
+          rows    name -> Column of the NEW rows alone, text coded against the merged dictionary;
+          remaps  name -> int32 table old code -> new code (strictly increasing), or None when no string is new."""
+        if set(new_columns) != set(self.columns) or len(new_columns) != len(self.columns):
+            raise FilterError(f"the rows' columns {sorted(map(str, new_columns))} are not exactly the schema's {sorted(self.columns)}")
+        n_new = None
+        out, rows, remaps = Schema(), {}, {}
+        for name, c in self.columns.items():
+            new = _column(name, c.index, new_columns[name], n_new)
+            n_new = new.data.shape[0]
+            if n_new == 0 or (new.valid is not None and not new.valid.any()):   # no row, or all NULL: the column's own type
+                new = Column(name, c.index, c.type, np.zeros(n_new, c.data.dtype), new.valid, [] if c.type == NP_COL_CODE else None)
+            if c.type == NP_COL_F64 and new.type == NP_COL_I64:
+                new = Column(name, c.index, NP_COL_F64, new.data.astype(np.float64), new.valid)
+            if new.type != c.type:
+                raise FilterError(f"column '{name}' has type {c.type}, its new rows type {new.type}")
+            data, remap, dic, first = c.data, None, c.dictionary, c.first_non_ascii
+            if c.type == NP_COL_CODE:
+                have = set(c.dictionary)
+                if any(s not in have for s in new.dictionary):
+                    dic = sorted(have | set(new.dictionary))
+                    remap = np.array([bisect.bisect_left(dic, s) for s in c.dictionary], np.int32)
+                    live = np.ones(data.shape[0], bool) if c.valid is None else c.valid.astype(bool)
+                    data = np.where(live, remap[np.where(live, data, 0)] if len(remap) else 0, data).astype(np.int32)
+                code = np.array([bisect.bisect_left(dic, s) for s in new.dictionary], np.int32)
+                live = np.ones(n_new, bool) if new.valid is None else new.valid.astype(bool)
+                new.data = np.ascontiguousarray(np.where(live, code[np.where(live, new.data, 0)] if len(code) else 0, 0).astype(np.int32))
+                new.dictionary = dic
+                if c.text_on_device:
+                    for s in dic:
+                        try:
+                            s.decode("utf-8")
+                        except UnicodeDecodeError:
+                            raise FilterError(f"text_on_device: column '{name}': a new string is not UTF-8") from None
+                    first = next((i for i, s in enumerate(dic) if not s.isascii()), None)
+                    new.text_on_device, new.first_non_ascii = True, first
+            valid = None
+            if c.valid is not None or new.valid is not None:
+                valid = np.concatenate([np.ones(c.data.shape[0], np.uint8) if c.valid is None else c.valid,
+                                        np.ones(n_new, np.uint8) if new.valid is None else new.valid])
+            out.columns[name] = Column(name, c.index, c.type, np.ascontiguousarray(np.concatenate([data, new.data])), valid, dic,
+                                       c.text_on_device, first)
+            rows[name], remaps[name] = new, remap
+        return out, rows, remaps
+
 
 @dataclass
 class CompiledFilter:
