@@ -1231,7 +1231,7 @@ int np_hip_index_delete(const char* index_dir, const int64_t* doc_ids, int64_t n
  * answering as it did: a sharded handle; a handle whose posting lists do not ascend (only such lists grow at their end); a
  * negative length; a code outside [0, K); totals beyond the open path's limits (2^31 documents -- and, found once the new
  * documents' distinct codes are counted, the 40-bit list offset and the 32-bit overflow index: refused then, the handle
- * unchanged all the same).  Not covered: centroid expansion (K changes) -- reload.  Delete: np_hip_index_remove (below).
+ * unchanged all the same).  Centroid expansion (K changes): np_hip_index_expand (below).  Delete: np_hip_index_remove (below).
  *
  * Attachments: metadata columns, the keyword index and the groups are DROPPED, as a reload leaves a handle: their rows no
  * longer cover the documents.  np_hip_index_set_columns / _set_text / _set_groups attach the grown ones, or
@@ -1350,6 +1350,60 @@ int np_hip_index_remove_keep(np_index* index, const int64_t* doc_ids, int64_t n_
 int np_hip_index_append_rows(np_index* index, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes,
                              const uint8_t* residuals, const np_column* new_cols, int32_t n_cols,
                              const int32_t* const* code_remap, const int32_t* new_groups, int64_t n_groups);
+
+/* ---- expand a RESIDENT index: new centroids, the buffered tail re-encoded, new documents (np_index.hip) --------------------
+ * The crate's usual update (MmapIndex::update above its buffer size, np_hip_index_update in expansion mode) deletes the
+ * buffered documents from the tail, appends new centroids to centroids.npy and appends buffer ++ new documents encoded
+ * against the grown codec.  np_hip_index_expand brings a handle that is already in HBM along, without reading the index again.
+ *
+ *  - new_centroids f32 [k_new][dim], FILE geometry (rows are padded to the storage width as the open path pads them): they
+ *    become centroids K .. K + k_new - 1; K1 = K + k_new.
+ *  - the first n_replace of the n_docs documents REPLACE the handle's last n_replace documents: the same ids, new lengths,
+ *    codes and residuals.  The other n_docs - n_replace take the ids num_documents .. as an append's do.
+ *  - codes i64 in [0, K1); residuals in file geometry, as for np_hip_index_append.
+ *
+ * Afterwards the handle equals one freshly opened on the resulting index (np_hip_index_from_arrays on old centroids ++ new and
+ * the old documents without their last n_replace ++ the given ones; np_hip_index_open on the directory np_hip_index_update wrote
+ * in expansion mode): np_hip_index_export, np_hip_index_info (but device_bytes / workspace_bytes) and every search entry return
+ * the same bytes.  avg_doclen follows the directory's arithmetic, delete and then append: tokens / documents in f64 after the
+ * tail drop (n_replace > 0), then (avg * n + new_tokens) / n1; a handle made from arrays keeps reporting tokens / documents.
+ * k_new == 0 && n_replace == 0 is np_hip_index_append; n_docs == 0 && k_new > 0 adds centroids with empty posting lists; all
+ * three zero changes nothing.
+ *
+ * What follows K1: the centroid table, cmax / filter_ok / s6_fast_ok over ALL K1 rows (non-finite values are accepted as the
+ * open path accepts them), the code width (K <= 65536 < K1: the u16 codes are widened to u32 by one streaming kernel into an
+ * array beside the narrow one), the eighths of the centroid range in every document's distinct-code record, the list offsets,
+ * the range table (whose range count follows the NEW document count, down as well as up) and the planner's candidate bound.
+ * The distinct-code blocks are built once over the final documents; the posting lists are rewritten in one streaming pass:
+ * list c keeps its entries below the first replaced id (the lists ascend: one bisection) and gains, ascending, the given
+ * documents that hold code c; lists K .. K1 - 1 start empty.
+ *
+ * One exclusive section (Concurrency: as np_hip_index_append): a search beside it sees the old index or the new one, never the
+ * index without its tail and never K1 centroids without their documents.
+ *
+ * Memory and failure order: capacity grows first and commits nothing.  The grown centroid table, the wide codes, the
+ * distinct-code blocks, the posting lists and the range table are allocated BESIDE what serves.  The given documents' tokens
+ * land where the replaced tail was: the tail's per-token bytes and doc offsets are saved in a side buffer first and put back,
+ * with K, the code width and the bounds, on any failure before the swap.  NP_ERR_OUT_OF_MEMORY leaves the handle answering as
+ * it did (its capacity may have grown).
+ *
+ * Refused with NP_ERR_INVALID_ARGUMENT or NP_ERR_SHAPE, the argument named, before any allocation or launch, the handle
+ * answering as it did: a NULL or sharded handle; posting lists that do not ascend; k_new < 0, or NULL new_centroids with
+ * k_new > 0; n_replace < 0, > n_docs or > the handle's documents; a negative length (NP_ERR_SHAPE); a code outside [0, K1);
+ * totals beyond the open path's limits (2^31 documents, K1 >= 2^31 -- and, found once the distinct codes are counted, the
+ * 40-bit list offset and the 32-bit overflow index: refused then, the handle restored).
+ *
+ * Attachments: np_hip_index_expand DROPS columns, keyword index and groups, as np_hip_index_append does.
+ * np_hip_index_expand_rows keeps columns and groups: the replaced documents keep their ids, so their rows STAY, and new_cols /
+ * new_groups cover only the n_docs - n_replace NEW documents.  Apart from that it has the arguments, checks, remap, memory order
+ * and keyword-index rule of np_hip_index_append_rows; with no new document the attachments stay as they are.
+ * NP_APPEND_TRACE=1 prints this call's stages too (tag "np expand"; tools/expand_time.py reads them). */
+int np_hip_index_expand(np_index* index, const float* new_centroids, int64_t k_new, int64_t n_replace,
+                        const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals);
+int np_hip_index_expand_rows(np_index* index, const float* new_centroids, int64_t k_new, int64_t n_replace,
+                             const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals,
+                             const np_column* new_cols, int32_t n_cols, const int32_t* const* code_remap,
+                             const int32_t* new_groups, int64_t n_groups);
 
 /* Read the handle's attachments back to the host, array for array.  np_hip_index_get_column: `data` (nullable) takes the
  * column's rows over the documents this handle holds (i64 / f64 / i32 by *type), `valid` (nullable) one byte per document, 0 =

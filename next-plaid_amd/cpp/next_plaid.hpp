@@ -499,6 +499,39 @@ inline AppendedTokens appended_tokens(const std::string& dir, const DirCounts& b
                                     std::to_string(have_t) + " tokens, metadata.json counts " + std::to_string(n_new) + " / " + std::to_string(t_new)).c_str());
   return out;
 }
+// appended_tokens' reading for a given count: the directory's LAST n_tail documents, what an update in expansion mode wrote
+// behind the documents it kept
+inline AppendedTokens tail_documents(const std::string& dir, int64_t n_tail) {
+  const DirCounts now = dir_counts(dir);
+  AppendedTokens out;
+  std::vector<std::vector<int64_t>> dl_parts;   // per chunk, the last chunk first: joined once below
+  std::vector<std::string> cd_parts, rs_parts;
+  int64_t have_d = 0, have_t = 0;
+  for (int64_t c = now.chunks - 1; c >= 0 && have_d < n_tail; --c) {
+    const std::string stem = dir + "/" + std::to_string((long long)c);
+    const std::vector<int64_t> dl = json_ints(read_file(dir + "/doclens." + std::to_string((long long)c) + ".json"));
+    const int64_t take_d = std::min<int64_t>(n_tail - have_d, (int64_t)dl.size());
+    int64_t take_t = 0, cols = 0;
+    for (int64_t d = (int64_t)dl.size() - take_d; d < (int64_t)dl.size(); ++d) take_t += dl[(size_t)d];
+    dl_parts.emplace_back(dl.end() - take_d, dl.end());
+    cd_parts.push_back(npy_tail(stem + ".codes.npy", "<i8", 8, take_t, &cols));
+    rs_parts.push_back(npy_tail(stem + ".residuals.npy", "|u1", 1, take_t, &cols));
+    have_d += take_d;
+    have_t += take_t;
+  }
+  out.codes.resize((size_t)have_t);
+  size_t at_c = 0;
+  for (size_t i = dl_parts.size(); i-- > 0;) {
+    out.doc_lengths.insert(out.doc_lengths.end(), dl_parts[i].begin(), dl_parts[i].end());
+    if (!cd_parts[i].empty()) std::memcpy((char*)out.codes.data() + at_c, cd_parts[i].data(), cd_parts[i].size());
+    at_c += cd_parts[i].size();
+    out.residuals.insert(out.residuals.end(), rs_parts[i].begin(), rs_parts[i].end());
+  }
+  if (have_d != n_tail)
+    throw Error(NP_ERR_INDEX_LOAD, ("Index load failed: the chunk files of " + dir + " hold " + std::to_string(have_d) + " documents, " +
+                                    std::to_string(n_tail) + " were written").c_str());
+  return out;
+}
 }  // namespace detail
 
 class MmapIndex {
@@ -576,7 +609,7 @@ class MmapIndex {
   // documents plus one pass over the posting lists, and searches on other threads go on meanwhile (the running ones finish on
   // the old index).  The handle then equals one freshly opened on the grown index; columns, keyword index and groups are
   // dropped, as reload() leaves a handle.  Unsharded handles with ascending posting lists (what this library and the crate
-  // write); centroid expansion still takes update(); for delete see remove() below.
+  // write); an update that may add centroids: update_resident() below; for delete see remove() below.
   // Documents already encoded (codes in [0, K), residuals [tokens][dim * nbits / 8] as np_hip_encode_tokens returns them):
   std::vector<int64_t> append_arrays(const std::vector<int64_t>& doc_lengths, const int64_t* codes, const uint8_t* residuals) {
     require_device("append_arrays");
@@ -675,6 +708,86 @@ class MmapIndex {
   }
 
  public:
+  // ---- expand the RESIDENT index (np_hip_index_expand): new_centroids [k_new][dim] join the codec as centroids K .., the first
+  // n_replace of the given documents REPLACE the handle's last n_replace documents (same ids) and the others take the ids
+  // num_documents() .. -- the crate's update in expansion mode, on the handle, in one exclusive section.  codes lie in
+  // [0, K + k_new).  The handle then equals one freshly opened on the resulting index; columns, keyword index and groups are
+  // dropped.  Returns the given documents' ids, the replaced ones first.
+  std::vector<int64_t> expand_arrays(const float* new_centroids, int64_t k_new, const std::vector<int64_t>& doc_lengths, const int64_t* codes,
+                                     const uint8_t* residuals, int64_t n_replace = 0) {
+    require_device("expand_arrays");
+    const int64_t first = info_.num_documents - std::max<int64_t>(n_replace, 0);
+    check(np_hip_index_expand(h_, new_centroids, k_new, n_replace, doc_lengths.data(), (int64_t)doc_lengths.size(), codes, residuals));
+    check(np_hip_index_info(h_, &info_));
+    std::vector<int64_t> ids(doc_lengths.size());
+    for (size_t i = 0; i < ids.size(); ++i) ids[i] = first + (int64_t)i;
+    return ids;
+  }
+  // ... with the rows of the doc_lengths.size() - n_replace NEW documents (np_hip_index_expand_rows): the replaced documents keep
+  // their rows, columns and groups stay attached; everything else as append_arrays with rows
+  std::vector<int64_t> expand_arrays(const float* new_centroids, int64_t k_new, const std::vector<int64_t>& doc_lengths, const int64_t* codes,
+                                     const uint8_t* residuals, int64_t n_replace, const AppendedRows& rows) {
+    require_device("expand_arrays");
+    const size_t n_new = doc_lengths.size() - (size_t)std::min<int64_t>(std::max<int64_t>(n_replace, 0), (int64_t)doc_lengths.size());
+    std::vector<np_column> c;
+    for (const ColumnSpan& s : rows.columns) {
+      if (s.size != n_new) throw Error(NP_ERR_SHAPE, "Shape error: a column needs one new entry per new document");
+      c.push_back(np_column{s.type, 0, s.data, s.valid});
+    }
+    if (!rows.code_remap.empty() && rows.code_remap.size() != rows.columns.size())
+      throw Error(NP_ERR_SHAPE, "Shape error: code_remap needs one entry per column, or none");
+    if (!rows.groups.empty() && rows.groups.size() != n_new) throw Error(NP_ERR_SHAPE, "Shape error: groups needs one id per new document");
+    const int64_t first = info_.num_documents - std::max<int64_t>(n_replace, 0);
+    check(np_hip_index_expand_rows(h_, new_centroids, k_new, n_replace, doc_lengths.data(), (int64_t)doc_lengths.size(), codes, residuals,
+                                   c.data(), (int32_t)c.size(), rows.code_remap.empty() ? nullptr : rows.code_remap.data(),
+                                   rows.groups.empty() ? nullptr : rows.groups.data(), rows.n_groups));
+    check(np_hip_index_info(h_, &info_));
+    std::vector<int64_t> ids(doc_lengths.size());
+    for (size_t i = 0; i < ids.size(); ++i) ids[i] = first + (int64_t)i;
+    return ids;
+  }
+  // update() on the handle's directory AND on the handle, without the reload: np_hip_index_update chooses the mode as the crate
+  // does and the handle follows the report -- buffer mode: append_arrays of what the directory gained; expansion mode:
+  // expand_arrays with the centroids.npy rows the update added, n_replace = the buffered documents it deleted from the tail and
+  // the tokens the chunk files hold beyond the kept documents; start-from-scratch mode: reload().  The handle equals load() of
+  // the directory afterwards.  update() itself still reloads.
+  std::vector<int64_t> update_resident(const Documents& docs, const UpdateConfig& cfg = {}, const np_open_opts* opts = nullptr,
+                                       np_update_report* report = nullptr) {
+    require_device("update_resident");
+    const detail::DirCounts before = detail::dir_counts(path);
+    if (before.documents != info_.num_documents)
+      throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the handle is not current with its directory: reload()");
+    check(np_hip_index_expand(h_, nullptr, 0, 0, nullptr, 0, nullptr, nullptr));   // the library's checks of the handle
+    const np_update_config c = cfg.c();
+    np_update_report r{};
+    const int64_t n = (int64_t)docs.doc_lengths.size();
+    check(np_hip_index_update(path.c_str(), docs.embeddings, docs.doc_lengths.data(), n, (int32_t)docs.dim, &c, opts ? opts->device : 0, &r));
+    if (report) *report = r;
+    if (r.mode == NP_UPDATE_NONE) return update_ids(r, docs.doc_lengths.size());
+    if (r.mode == NP_UPDATE_SCRATCH) {
+      reload(opts);
+      return update_ids(r, docs.doc_lengths.size());
+    }
+    const detail::DirCounts after = detail::dir_counts(path);
+    if (r.mode == NP_UPDATE_EXPAND) {
+      const int64_t n_given = r.n_reindexed + n, n_replace = before.documents - (after.documents - n_given);
+      if (n_replace < 0 || n_replace > n_given)
+        throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the directory gained another number of documents than the update wrote: reload()");
+      const detail::AppendedTokens t = detail::tail_documents(path, n_given);
+      int64_t cols = 0;
+      const std::string cen = detail::npy_tail(path + "/centroids.npy", "<f4", 4, r.n_new_centroids, &cols);
+      if (r.n_new_centroids > 0 && cols != info_.embedding_dim)
+        throw Error(NP_ERR_INDEX_LOAD, "Index load failed: centroids.npy has another dim than the handle: reload()");
+      (void)expand_arrays(reinterpret_cast<const float*>(cen.data()), r.n_new_centroids, t.doc_lengths, t.codes.data(), t.residuals.data(),
+                          n_replace);
+    } else {
+      const detail::AppendedTokens t = detail::appended_tokens(path, before);
+      (void)append_arrays(t.doc_lengths, t.codes.data(), t.residuals.data());
+    }
+    if (info_.num_documents != after.documents)
+      throw Error(NP_ERR_INDEX_LOAD, "Index load failed: the directory gained another number of documents than the handle: reload()");
+    return update_ids(r, docs.doc_lengths.size());
+  }
   // room for this many MORE documents / tokens, so that later appends move no per-token array (without it every array grows
   // by allocate, copy, free: a peak of the largest array twice).  A service reserves right after load()
   void reserve(int64_t extra_docs, int64_t extra_tokens) {

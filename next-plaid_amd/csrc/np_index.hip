@@ -109,6 +109,7 @@ bool set_tuning(Tuning* t, const std::string& n, int value) {
   else if (n == "scan_docs") t->scan_docs = std::max(value, 0);
   else if (n == "match_lds") t->match_lds = clamp(value, 0, 40);
   else if (n == "remove_slab") t->remove_slab = std::max(value, 0);
+  else if (n == "expand_fail") t->expand_fail = clamp(value, 0, 4);
   else return false;
   return true;
 }
@@ -222,27 +223,38 @@ __global__ void __launch_bounds__(256) centroid_bound_kernel(const float* __rest
   }
 }
 
+// k rows of the caller's centroids (file geometry) into storage rows at dst
+static int upload_centroid_rows(const DeviceIndex* ix, const float* centroids, int64_t k, float* dst) {
+  if (k <= 0) return NP_OK;
+  if (ix->ldim == ix->dim) {
+    NP_HIP(hipMemcpy(dst, centroids, (size_t)k * ix->dim * sizeof(float), hipMemcpyHostToDevice));
+  } else {   // rows zero-padded to the storage width (np_internal.h storage_dim)
+    NP_HIP(hipMemset(dst, 0, (size_t)k * ix->dim * sizeof(float)));
+    NP_HIP(hipMemcpy2D(dst, (size_t)ix->dim * sizeof(float), centroids, (size_t)ix->ldim * sizeof(float),
+                       (size_t)ix->ldim * sizeof(float), (size_t)k, hipMemcpyHostToDevice));
+  }
+  return NP_OK;
+}
+
+// cmax and filter_ok of a centroid table in storage rows (a maximum and an OR: the same for any order of the rows' visits)
+static int centroid_bounds(const float* d_centroids, int64_t K, int dim, float* cmax, bool* filter_ok) {
+  DevPtr<uint32_t> d_b;
+  uint32_t h_b[2] = {0, 0};
+  NP_TRY(d_b.alloc(2));
+  NP_HIP(hipMemset(d_b.get(), 0, 8));
+  centroid_bound_kernel<<<(unsigned)((K + 3) / 4), 256>>>(d_centroids, K, dim, d_b.get());
+  NP_HIP(hipMemcpy(h_b, d_b.get(), 8, hipMemcpyDeviceToHost));
+  float ss;
+  memcpy(&ss, &h_b[0], 4);
+  *cmax = sqrtf(ss) * 1.0001f;   // the f32 sum of squares is within ~dim * 2^-24 of the real one
+  *filter_ok = h_b[1] == 0;
+  return NP_OK;
+}
+
 static int upload_codec(DeviceIndex* ix, const float* centroids, const float* bucket_weights) {
   NP_TRY(ix->d_centroids.alloc((size_t)ix->K * ix->dim, &ix->device_bytes));
-  if (ix->ldim == ix->dim) {
-    NP_HIP(hipMemcpy(ix->d_centroids.get(), centroids, (size_t)ix->K * ix->dim * sizeof(float), hipMemcpyHostToDevice));
-  } else {   // rows zero-padded to the storage width (np_internal.h storage_dim)
-    NP_HIP(hipMemset(ix->d_centroids.get(), 0, (size_t)ix->K * ix->dim * sizeof(float)));
-    NP_HIP(hipMemcpy2D(ix->d_centroids.get(), (size_t)ix->dim * sizeof(float), centroids, (size_t)ix->ldim * sizeof(float),
-                       (size_t)ix->ldim * sizeof(float), (size_t)ix->K, hipMemcpyHostToDevice));
-  }
-  {
-    DevPtr<uint32_t> d_b;
-    uint32_t h_b[2] = {0, 0};
-    NP_TRY(d_b.alloc(2));
-    NP_HIP(hipMemset(d_b.get(), 0, 8));
-    centroid_bound_kernel<<<(unsigned)((ix->K + 3) / 4), 256>>>(ix->d_centroids.get(), ix->K, ix->dim, d_b.get());
-    NP_HIP(hipMemcpy(h_b, d_b.get(), 8, hipMemcpyDeviceToHost));
-    float ss;
-    memcpy(&ss, &h_b[0], 4);
-    ix->cmax = sqrtf(ss) * 1.0001f;   // the f32 sum of squares is within ~dim * 2^-24 of the real one
-    ix->filter_ok = h_b[1] == 0;
-  }
+  NP_TRY(upload_centroid_rows(ix, centroids, ix->K, ix->d_centroids.get()));
+  NP_TRY(centroid_bounds(ix->d_centroids.get(), ix->K, ix->dim, &ix->cmax, &ix->filter_ok));
   const int nb = 1 << ix->nbits, lnb = 1 << ix->lnbits;
   std::vector<float> wl(nb);
   for (int s = 0; s < nb; ++s) {   // 1-bit files stored as 2-bit: buckets 2 and 3 never occur
@@ -2682,6 +2694,433 @@ static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed
   return NP_OK;
 }
 
+// ---- expand a resident index (np_hip_index_expand) --------------------------------------------------------------------
+// The crate's usual update (index.rs:1515-1562, np_update.cpp update_impl): the buffered documents leave the tail, new centroids
+// join the codec, and buffer ++ new documents are appended against the grown codec.  On the handle that is ONE exclusive
+// section: the dropped tokens are the last ones, so nothing is compacted -- the new tokens land where the tail was (saved
+// beside, and put back when anything fails before the swap); the distinct-code structures are built once over the final
+// documents; and the posting lists are rewritten in one streaming pass that cuts every old list at the first dropped id and
+// hangs the given documents' pairs behind it.  What depends on K follows K1 = K + k_new: the centroid table and its bounds, the
+// code width, the eighths of the centroid range in d_useg, the list offsets, the range table and the planner's bound.
+
+// u16 codes -> u32: a lane takes 8 codes with one 16-byte load and leaves them with two 16-byte stores; the last n % 8 codes go
+// one by one.  Both arrays are hipMalloc'ed (256-byte aligned), dst holds at least n entries.
+__global__ void __launch_bounds__(256) widen_codes_kernel(const uint16_t* __restrict__ src, int64_t n, uint32_t* __restrict__ dst) {
+  const int64_t n8 = n >> 3, tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = tid; i < n8; i += stride) {
+    const uint4 v = reinterpret_cast<const uint4*>(src)[i];
+    reinterpret_cast<uint4*>(dst)[2 * i] = make_uint4(v.x & 0xFFFFu, v.x >> 16, v.y & 0xFFFFu, v.y >> 16);
+    reinterpret_cast<uint4*>(dst)[2 * i + 1] = make_uint4(v.z & 0xFFFFu, v.z >> 16, v.w & 0xFFFFu, v.w >> 16);
+  }
+  const int64_t t = (n8 << 3) + tid;
+  if (tid < 8 && t < n) dst[t] = src[t];
+}
+
+// what list c of the K1 lists keeps of the old array: old_begin[c] and n_keep[c] = its entries with id < n_keep_docs (the lists
+// ascend: one bisection); lists K0 .. K1 - 1 are new and keep nothing.  Entry K1 is the scan's closing zero.
+__global__ void __launch_bounds__(256) ivf_keep_kernel(const uint32_t* __restrict__ ivf, const int64_t* __restrict__ old_off, int64_t K0,
+                                                       int64_t K1, int64_t n_keep_docs, int64_t* __restrict__ old_begin,
+                                                       int64_t* __restrict__ n_keep) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c > K1) return;
+  if (c >= K0) {
+    old_begin[c] = 0;
+    n_keep[c] = 0;
+    return;
+  }
+  const int64_t s0 = old_off[c];
+  const uint32_t* L = ivf + s0;
+  int64_t a = 0, z = old_off[c + 1] - s0;
+  while (a < z) {
+    const int64_t mid = (a + z) >> 1;
+    if ((int64_t)L[mid] < n_keep_docs) a = mid + 1;
+    else z = mid;
+  }
+  old_begin[c] = s0;
+  n_keep[c] = a;
+}
+
+__global__ void ivf_cut_offsets_kernel(const int64_t* __restrict__ kept_pfx, const int64_t* __restrict__ start, int64_t K,
+                                       int64_t* __restrict__ new_off) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c <= K) new_off[c] = kept_pfx[c] + start[c];
+}
+
+// ivf_merge_kernel's sibling: the same entry-balanced stream over the NEW array (a workgroup owns NP_MERGE_TILE consecutive
+// entries, a thread quads of them, every entry has one source that scans alone decide: no atomics, no workgroup waits for
+// another), but list c's old part is old_ivf[old_begin[c] .. + kept_pfx[c + 1] - kept_pfx[c]) -- the list cut at the first
+// dropped document -- and there are K lists where the old array had fewer.
+__global__ void __launch_bounds__(256) ivf_cut_merge_kernel(const uint32_t* __restrict__ old_ivf, const int64_t* __restrict__ old_begin,
+                                                            const int64_t* __restrict__ kept_pfx, const uint64_t* __restrict__ pairs,
+                                                            const int64_t* __restrict__ start, const int64_t* __restrict__ new_off,
+                                                            int64_t K, int64_t total, uint32_t* __restrict__ out) {
+  __shared__ int64_t s_c0;
+  const int64_t o0 = (int64_t)blockIdx.x * NP_MERGE_TILE;   // < total: the grid covers [0, total)
+  if (threadIdx.x == 0) s_c0 = ivf_list_of(new_off, K, 0, o0);
+  __syncthreads();
+  int64_t c = s_c0;
+  MergeQuad q[NP_MERGE_QUADS];
+#pragma unroll
+  for (int it = 0; it < NP_MERGE_QUADS; ++it) {
+    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
+    q[it] = MergeQuad{{0u, 0u, 0u, 0u}};
+    if (o < total) {
+      const int n = (int)min((int64_t)4, total - o);
+      c = ivf_list_of(new_off, K, c, o);
+      int64_t b_new = new_off[c], e_new = new_off[c + 1], b_old = old_begin[c], n_old = kept_pfx[c + 1] - kept_pfx[c], b_pair = start[c];
+      if (n == 4 && o + 4 <= b_new + n_old) {   // (b_new + n_old <= e_new)
+        q[it] = *reinterpret_cast<const MergeQuad*>(old_ivf + b_old + (o - b_new));
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k < n) {
+            const int64_t oo = o + k;
+            if (oo >= e_new) {
+              c = ivf_list_of(new_off, K, c, oo);
+              b_new = new_off[c], e_new = new_off[c + 1], b_old = old_begin[c], n_old = kept_pfx[c + 1] - kept_pfx[c], b_pair = start[c];
+            }
+            const int64_t r = oo - b_new;
+            q[it].v[k] = r < n_old ? old_ivf[b_old + r] : (uint32_t)(pairs[b_pair + (r - n_old)] & 0xFFFFFFFFull);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < NP_MERGE_QUADS; ++it) {
+    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
+    if (o + 4 <= total) {
+      *reinterpret_cast<uint4*>(out + o) = make_uint4(q[it].v[0], q[it].v[1], q[it].v[2], q[it].v[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (o + k < total) out[o + k] = q[it].v[k];
+    }
+  }
+}
+
+static int as_expand_argument(const char* entry, int rc, const char* arg) {
+  if (rc == NP_OK || rc == NP_ERR_OUT_OF_MEMORY || rc == NP_ERR_DEVICE_UNAVAILABLE) return rc;
+  const std::string msg = last_error();
+  set_error("%s: %s: %s", entry, arg, msg.c_str());
+  return NP_ERR_INVALID_ARGUMENT;
+}
+
+// The K1 = ix->K posting lists (the handle's K-dependent scalars are the grown ones by now; its d_ivf / d_ivf_offsets still the
+// K0 old lists): every old list cut at document Nk, then the pairs of documents [Nk, N1) from the distinct-code lists of the
+// final index (u, d_uoff).  Always a new array and new offsets.  raw_lists: as merge_posting_lists.
+static int cut_merge_posting_lists(const DeviceIndex* ix, int64_t K0, const Ucodes& u, const int64_t* d_uoff, int64_t Nk, int64_t N1,
+                                   bool raw_lists, DevPtr<uint32_t>* ivf, DevPtr<int64_t>* ioff, std::vector<int64_t>* h_ioff,
+                                   int64_t* ivf_size, const char* entry, const OpenTrace& trace) {
+  const int64_t K = ix->K, n_new = N1 - Nk;
+  DevPtr<int64_t> d_len64, d_upfx, d_start, d_begin, d_keep, d_kpfx;
+  DevPtr<uint64_t> d_k1, d_k2;
+  DevPtr<uint8_t> d_temp;
+  int64_t P = 0;   // (code, document) pairs of the given documents
+  if (n_new > 0) {
+    NP_TRY(d_len64.alloc((size_t)n_new));
+    NP_TRY(d_upfx.alloc((size_t)n_new));
+    ulen_to_i64_kernel<<<(unsigned)((n_new + 255) / 256), 256>>>(u.d_ulen.get() + Nk, n_new, d_len64.get());
+    NP_TRY(device_scan_inclusive(d_len64.get(), d_upfx.get(), n_new));
+    NP_HIP(hipMemcpy(&P, d_upfx.get() + (n_new - 1), 8, hipMemcpyDeviceToHost));
+    d_len64.reset();
+  }
+  if (P >= ((int64_t)1 << 31)) {
+    set_error("%s: n_docs: the given documents hold %lld (code, doc) pairs, one call takes < 2^31", entry, (long long)P);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  NP_TRY(d_start.alloc((size_t)K + 1));
+  NP_TRY(d_k1.alloc((size_t)P));
+  NP_TRY(d_k2.alloc((size_t)P));
+  if (P > 0) {
+    int kbits = 1;
+    while (((int64_t)1 << kbits) < K) ++kbits;
+    ivf_emit_pairs_kernel<<<(unsigned)((n_new + 3) / 4), 256>>>(Nk, N1, d_uoff, CodeArr{u.d_ucodes.get(), ix->code_wide}, u.d_ulen.get(),
+                                                              d_upfx.get(), Nk, 0, d_k1.get());
+    NP_HIP(hipGetLastError());
+    size_t tb = 0;
+    NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
+    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+    NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
+    if (raw_lists) {
+      DevPtr<int64_t> d_n;
+      NP_TRY(d_n.alloc(1));
+      tb = 0;
+      NP_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
+      NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+      NP_HIP(hipcub::DeviceSelect::Unique(d_temp.get(), tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
+      NP_HIP(hipMemcpy(&P, d_n.get(), 8, hipMemcpyDeviceToHost));
+      std::swap(d_k1, d_k2);   // d_k2 = the sorted pairs, each once
+    }
+  }
+  ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2.get(), P, K, d_start.get());
+  NP_HIP(hipGetLastError());
+  // the cut: what every list keeps, and where the kept parts begin in an array of them alone
+  NP_TRY(d_begin.alloc((size_t)K + 1));
+  NP_TRY(d_keep.alloc((size_t)K + 1));
+  NP_TRY(d_kpfx.alloc((size_t)K + 1));
+  ivf_keep_kernel<<<(unsigned)((K + 256) / 256), 256>>>(ix->d_ivf.get(), ix->d_ivf_offsets.get(), K0, K, Nk, d_begin.get(), d_keep.get());
+  NP_HIP(hipGetLastError());
+  NP_TRY(device_scan_exclusive(d_keep.get(), d_kpfx.get(), K + 1));
+  int64_t kept = 0;
+  NP_HIP(hipMemcpy(&kept, d_kpfx.get() + K, 8, hipMemcpyDeviceToHost));
+  const int64_t total = kept + P;
+  NP_TRY(ioff->alloc((size_t)K + 1));
+  NP_TRY(ivf->alloc((size_t)total));   // the new array beside the old one: the pass reads the one and writes the other
+  ivf_cut_offsets_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_kpfx.get(), d_start.get(), K, ioff->get());
+  NP_HIP(hipGetLastError());
+  KernelClock clock(trace.on);
+  clock.start();
+  if (total > 0)
+    ivf_cut_merge_kernel<<<(unsigned)((total + NP_MERGE_TILE - 1) / NP_MERGE_TILE), 256>>>(
+        ix->d_ivf.get(), d_begin.get(), d_kpfx.get(), d_k2.get(), d_start.get(), ioff->get(), K, total, ivf->get());
+  NP_HIP(hipGetLastError());
+  if (trace.on)
+    fprintf(stderr, "[%s] %-28s %8.6f s  %lld entries %lld new %lld cut\n", trace.tag, "cut-merge kernel", clock.stop(), (long long)total,
+            (long long)P, (long long)(ix->ivf_size - kept));
+  h_ioff->resize((size_t)K + 1);
+  NP_HIP(hipMemcpy(h_ioff->data(), ioff->get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
+  NP_HIP(hipDeviceSynchronize());
+  *ivf_size = total;
+  return NP_OK;
+}
+
+// What an expand flips or overwrites before its swap, and the way back: the K-dependent scalars and the two arrays that are
+// replaced whole (centroids; the codes when they widen) are exchanged early so that the shared open stages run on the grown
+// geometry, and the tail of the per-token arrays and of the doc offsets is overwritten by the given documents.  Every context
+// is held meanwhile.  Unless commit() is reached the destructor puts all of it back: the handle answers as it did.
+struct ExpandUndo {
+  DeviceIndex* ix;
+  bool armed = false, committed = false;
+  int64_t K = 0, KP = 0;
+  int code_wide = 0;
+  float cmax = 0.f;
+  bool filter_ok = false, s6_fast_ok = false;
+  DevPtr<float> centroids;   // armed: the table that served (when one was built), else the grown one
+  DevPtr<uint8_t> codes;     // armed: the narrow array that served (when the codes widen), else the wide one
+  bool has_centroids = false, has_codes = false;
+  int64_t Nk = 0, N0 = 0, Tk = 0, T0 = 0;   // the tail: documents [Nk, N0), tokens [Tk, T0)
+  DevPtr<uint8_t> t_codes, t_res;
+  DevPtr<float> t_inv;
+  DevPtr<uint16_t> t_pos;
+  DevPtr<int64_t> t_off;
+  explicit ExpandUndo(DeviceIndex* i) : ix(i) {}
+  int save_tail(int64_t Nk_, int64_t N0_, int64_t Tk_, int64_t T0_) {
+    Nk = Nk_, N0 = N0_, Tk = Tk_, T0 = T0_;
+    const size_t nt = (size_t)(T0 - Tk), nd = (size_t)(N0 - Nk), cb = ix->code_bytes();
+    if (nd == 0) return NP_OK;
+    NP_TRY(t_off.alloc(nd));
+    NP_HIP(hipMemcpy(t_off.get(), ix->d_doc_offsets.get() + Nk + 1, nd * 8, hipMemcpyDeviceToDevice));
+    if (nt == 0) return NP_OK;
+    NP_TRY(t_codes.alloc(nt * cb));
+    NP_TRY(t_res.alloc(nt * ix->pd));
+    NP_TRY(t_inv.alloc(nt));
+    if (ix->tok_sorted) NP_TRY(t_pos.alloc(nt));
+    NP_HIP(hipMemcpy(t_codes.get(), ix->d_codes.get() + (size_t)Tk * cb, nt * cb, hipMemcpyDeviceToDevice));
+    NP_HIP(hipMemcpy(t_res.get(), ix->d_residuals.get() + (size_t)Tk * ix->pd, nt * ix->pd, hipMemcpyDeviceToDevice));
+    NP_HIP(hipMemcpy(t_inv.get(), ix->d_inv_norm.get() + Tk, nt * 4, hipMemcpyDeviceToDevice));
+    if (ix->tok_sorted) NP_HIP(hipMemcpy(t_pos.get(), ix->d_tok_pos.get() + Tk, nt * 2, hipMemcpyDeviceToDevice));
+    return NP_OK;
+  }
+  void exchange() {   // the handle's arrays <-> the ones held here, with their share of device_bytes
+    if (has_centroids) {
+      ix->device_bytes = ix->device_bytes - ix->d_centroids.bytes() + centroids.bytes();
+      std::swap(ix->d_centroids, centroids);
+    }
+    if (has_codes) {
+      ix->device_bytes = ix->device_bytes - ix->d_codes.bytes() + codes.bytes();
+      std::swap(ix->d_codes, codes);
+    }
+  }
+  // the grown geometry goes live for the stages (nobody else looks: every context is held)
+  void flip(int64_t K1, float cmax1, bool filter_ok1, bool s6_fast_ok1) {
+    K = ix->K, KP = ix->KP, code_wide = ix->code_wide, cmax = ix->cmax, filter_ok = ix->filter_ok, s6_fast_ok = ix->s6_fast_ok;
+    exchange();
+    ix->K = K1;
+    ix->KP = (K1 + 63) / 64 * 64;
+    ix->code_wide = K1 > 65536 ? 1 : 0;
+    ix->cmax = cmax1, ix->filter_ok = filter_ok1, ix->s6_fast_ok = s6_fast_ok1;
+    armed = true;
+  }
+  void commit() { committed = true; }
+  ~ExpandUndo() {
+    if (!armed || committed) return;
+    (void)hipDeviceSynchronize();
+    exchange();
+    ix->K = K, ix->KP = KP, ix->code_wide = code_wide, ix->cmax = cmax, ix->filter_ok = filter_ok, ix->s6_fast_ok = s6_fast_ok;
+    const size_t nt = (size_t)(T0 - Tk), nd = (size_t)(N0 - Nk), cb = ix->code_bytes();
+    if (nd > 0 && t_off.get()) (void)hipMemcpy(ix->d_doc_offsets.get() + Nk + 1, t_off.get(), nd * 8, hipMemcpyDeviceToDevice);
+    if (nt > 0 && t_codes.get()) {
+      (void)hipMemcpy(ix->d_codes.get() + (size_t)Tk * cb, t_codes.get(), nt * cb, hipMemcpyDeviceToDevice);
+      (void)hipMemcpy(ix->d_residuals.get() + (size_t)Tk * ix->pd, t_res.get(), nt * ix->pd, hipMemcpyDeviceToDevice);
+      (void)hipMemcpy(ix->d_inv_norm.get() + Tk, t_inv.get(), nt * 4, hipMemcpyDeviceToDevice);
+      if (ix->tok_sorted && t_pos.get()) (void)hipMemcpy(ix->d_tok_pos.get() + Tk, t_pos.get(), nt * 2, hipMemcpyDeviceToDevice);
+    }
+    (void)hipDeviceSynchronize();
+  }
+};
+
+// np_hip_index_expand / _expand_rows once the arguments are checked.  rows: the rows of the n - n_replace NEW documents (the
+// replaced ones keep their ids and their rows), where the plain entry drops the attachments.
+static int expand_documents(const char* entry, DeviceIndex* ix, const float* new_centroids, int64_t k_new, int64_t n_replace,
+                            const int64_t* lens, int64_t n, const int64_t* codes, const uint8_t* residuals, int64_t Tn, int64_t maxlen,
+                            const AppendRows* rows) {
+  HoldContexts hold(ix);
+  DeviceGuard g(ix->device);
+  if (!g.ok) {
+    set_error("hipSetDevice(%d) failed", ix->device);
+    return NP_ERR_DEVICE_UNAVAILABLE;
+  }
+  const int64_t N0 = ix->n_docs, Nk = N0 - n_replace, N1 = Nk + n, K0 = ix->K, K1 = K0 + k_new, T0 = ix->T;
+  if (n_replace > N0) {   // (checked by the entry; the handle may have shrunk since)
+    set_error("%s: n_replace is %lld, the handle has %lld documents", entry, (long long)n_replace, (long long)N0);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  NP_TRY(as_expand_argument(entry, check_shard_docs(N1), "n_docs"));
+  NP_TRY(as_expand_argument(entry, check_geometry(K1, ix->ldim, ix->lnbits, N1), "k_new"));
+  NP_HIP(hipDeviceSynchronize());   // device-side calls that returned may still be running on their streams
+  OpenTrace trace("NP_APPEND_TRACE", "np expand");
+  // the tail that goes: its first token, its longest document
+  std::vector<int64_t> h_tail((size_t)n_replace + 1);
+  NP_HIP(hipMemcpy(h_tail.data(), ix->d_doc_offsets.get() + Nk, h_tail.size() * 8, hipMemcpyDeviceToHost));
+  const int64_t Tk = h_tail[0], T1 = Tk + Tn;
+  int64_t kept_max = ix->max_doc_len, tail_max = 0;
+  for (int64_t d = 0; d < n_replace; ++d) tail_max = std::max(tail_max, h_tail[(size_t)d + 1] - h_tail[(size_t)d]);
+  if (n_replace > 0 && tail_max >= ix->max_doc_len) {   // the longest document may be leaving: the kept ones are looked at
+    std::vector<int64_t> off((size_t)Nk + 1);
+    NP_HIP(hipMemcpy(off.data(), ix->d_doc_offsets.get(), off.size() * 8, hipMemcpyDeviceToHost));
+    kept_max = 0;
+    for (int64_t d = 0; d < Nk; ++d) kept_max = std::max(kept_max, off[(size_t)d + 1] - off[(size_t)d]);
+  }
+  // 1. capacity first: commits nothing
+  NP_TRY(grow_capacity(ix, N1, T1));
+  const bool with_rows = rows && n > n_replace;
+  if (with_rows) NP_TRY(grow_attachments(ix, N1));
+  trace.mark("grow");
+  // 2. the grown centroid table and its bounds over all K1 rows, the wide codes of the kept tokens: beside what serves
+  ExpandUndo undo(ix);
+  float cmax1 = ix->cmax;
+  bool filter_ok1 = ix->filter_ok, s6_fast_ok1 = ix->s6_fast_ok;
+  if (k_new > 0) {
+    NP_TRY(undo.centroids.alloc((size_t)K1 * ix->dim));
+    undo.has_centroids = true;
+    NP_HIP(hipMemcpy(undo.centroids.get(), ix->d_centroids.get(), (size_t)K0 * ix->dim * sizeof(float), hipMemcpyDeviceToDevice));
+    NP_TRY(upload_centroid_rows(ix, new_centroids, k_new, undo.centroids.get() + (size_t)K0 * ix->dim));
+    NP_TRY(centroid_bounds(undo.centroids.get(), K1, ix->dim, &cmax1, &filter_ok1));
+    const int nb = 1 << ix->nbits;
+    std::vector<float> wl((size_t)nb);
+    NP_HIP(hipMemcpy(wl.data(), ix->d_wlut.get(), (size_t)nb * sizeof(float), hipMemcpyDeviceToHost));
+    bool wok = true;
+    for (int s = 0; s < nb; ++s) wok = wok && std::isfinite(wl[(size_t)s]) && std::fabs(wl[(size_t)s]) < 1e6f;
+    s6_fast_ok1 = filter_ok1 && cmax1 < 1e6f && wok;
+    trace.mark("centroids + bounds");
+  }
+  if (!ix->code_wide && K1 > 65536) {
+    NP_TRY(undo.codes.alloc((size_t)std::max<int64_t>(ix->cap_tokens, 1) * 4));
+    undo.has_codes = true;
+    KernelClock clock(trace.on);
+    clock.start();
+    widen_codes_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>(((Tk >> 3) + 255) / 256, 8192)), 256>>>(
+        reinterpret_cast<const uint16_t*>(ix->d_codes.get()), Tk, reinterpret_cast<uint32_t*>(undo.codes.get()));
+    NP_HIP(hipGetLastError());
+    if (trace.on) fprintf(stderr, "[%s] %-28s %8.6f s  %lld codes\n", trace.tag, "widen kernel", clock.stop(), (long long)Tk);
+    NP_HIP(hipDeviceSynchronize());
+    trace.mark("codes widened");
+  }
+  // 3. the tail's bytes beside, then the grown geometry goes live for the stages below; from here on a failure restores
+  NP_TRY(undo.save_tail(Nk, N0, Tk, T0));
+  undo.flip(K1, cmax1, filter_ok1, s6_fast_ok1);
+  trace.mark("tail saved");
+  auto refused_after = [&](int stage) {   // Tuning::expand_fail: a test's stand-in for an allocation the device refuses here
+    if (ix->tune.expand_fail != stage) return false;
+    set_error("%s: out of memory after stage %d (np_hip_index_tune \"expand_fail\")", entry, stage);
+    return true;
+  };
+  // 4. the given documents from the first dropped token on, and the per-token stages over them alone
+  if (n > 0) {
+    std::vector<int64_t> off((size_t)n);
+    int64_t t = Tk;
+    for (int64_t d = 0; d < n; ++d) off[(size_t)d] = (t += lens[d]);
+    NP_HIP(hipMemcpy(ix->d_doc_offsets.get() + Nk + 1, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  if (Tn > 0) {
+    HostIndex h;
+    HostChunk c;
+    c.codes = codes;
+    c.residuals = residuals;
+    c.n_tokens = Tn;
+    h.chunks.push_back(c);
+    NP_TRY(as_expand_argument(entry, upload_tokens(h, ix, 0, Tn, Tk), "codes"));
+    if (ix->tok_sorted) NP_TRY(permute_tokens(ix, 1, Nk, N1));
+    NP_TRY(fill_inv_norm(ix, Tk, T1));
+  }
+  trace.mark("upload + token stages");
+  if (refused_after(1)) return NP_ERR_OUT_OF_MEMORY;
+  // 5. the distinct-code structures of the final documents, once: the eighths of the centroid range moved for all of them
+  Ucodes u;
+  DevPtr<int64_t> d_uoff;
+  NP_TRY(as_expand_argument(entry, build_unique_codes(ix, tokens_of(ix), N1, &u, &d_uoff), "n_docs"));
+  trace.mark("distinct-code rebuild");
+  if (refused_after(2)) return NP_ERR_OUT_OF_MEMORY;
+  // 6. the posting lists, one pass
+  DevPtr<uint32_t> ivf;
+  DevPtr<int64_t> ioff;
+  std::vector<int64_t> h_ioff;
+  int64_t ivf_size = 0;
+  NP_TRY(cut_merge_posting_lists(ix, K0, u, d_uoff.get(), Nk, N1, maxlen > NP_UNIQ_MAX, &ivf, &ioff, &h_ioff, &ivf_size, entry, trace));
+  d_uoff.reset();
+  trace.mark("posting-list cut + merge");
+  if (refused_after(3)) return NP_ERR_OUT_OF_MEMORY;
+  // 7. their range table.  Lists that held every (document, code) pair still do: a kept document's entries all stay, the
+  //    given documents' pairs are all there
+  DevPtr<uint32_t> split;
+  int R = 0, cover = N1 > 0 ? ix->ivf_cover : -1;
+  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide}, ivf.get(), ioff.get()};
+  NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
+  trace.mark("range table");
+  if (refused_after(4)) return NP_ERR_OUT_OF_MEMORY;
+  // 8. the new documents' rows, staged beside the attachments that serve
+  StagedRows staged;
+  if (with_rows) {
+    NP_TRY(stage_appended_rows(ix, *rows, N0, N1, &staged));
+    trace.mark("rows staged");
+  }
+  // ---- nothing below can fail: the handle becomes the expanded index ----
+  undo.commit();
+  int rows_rc = NP_OK;
+  if (with_rows) rows_rc = install_appended_rows(ix, *rows, std::move(staged), N0, N1);   // (not an allocation: a device that stopped answering)
+  else if (!rows) drop_attachments(ix);
+  install_ucodes(ix, std::move(u));
+  ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
+  ix->d_ivf = std::move(ivf);
+  ix->d_ivf_offsets = std::move(ioff);
+  ix->ivf_size = ivf_size;
+  set_ivf_bound(ix, h_ioff.data());
+  install_ivf_split(ix, std::move(split), R);
+  ix->ivf_cover = cover;
+  // the directory's arithmetic, delete and then append (np_update.cpp delete_impl, update_index_files): tokens / documents
+  // after the tail drop, then (avg * n + new_tokens) / n1; a handle made from arrays reports tokens / documents
+  const int64_t emb_k = ix->n_emb_total - (T0 - Tk);
+  if (n > 0 || n_replace > 0) {
+    if (ix->avg_from_counts) {
+      ix->avg_doclen = N1 > 0 ? (double)(emb_k + Tn) / (double)N1 : 0.0;
+    } else {
+      const double a = n_replace > 0 ? (Nk > 0 ? (double)emb_k / (double)Nk : 0.0) : ix->avg_doclen;
+      ix->avg_doclen = N1 > 0 ? (a * (double)Nk + (double)Tn) / (double)N1 : 0.0;
+    }
+  }
+  ix->n_docs = ix->N_total = N1;
+  ix->T = T1;
+  ix->n_emb_total = emb_k + Tn;
+  ix->max_doc_len = std::max(kept_max, maxlen);
+  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
+  ix->gain_run.store(0, std::memory_order_relaxed);
+  ix->gain_skip.store(0, std::memory_order_relaxed);
+  contexts_forget_index(ix);
+  trace.mark("swap");
+  return rows_rc;
+}
+
 // doc lengths -> d_doc_offsets (an inclusive scan written one entry in)
 static int synth_doc_offsets(const np_synth_spec* s, const SynthP& p, DeviceIndex* ix) {
   NP_TRY(ix->d_doc_offsets.alloc((size_t)ix->n_docs + 1, &ix->device_bytes));
@@ -3125,8 +3564,7 @@ int np_hip_index_probe_dir(const char* index_dir, np_info* out) {
 }
 
 // the new documents' rows against the handle's attachments: refused by name, before any allocation
-static int check_append_rows(const DeviceIndex* ix, const AppendRows& r, int64_t n_docs) {
-  const char* const e = "np_hip_index_append_rows";
+static int check_append_rows(const DeviceIndex* ix, const AppendRows& r, int64_t n_docs, const char* e) {
   const size_t nc = ix->columns.size();
   if (r.n_cols < 0 || (size_t)r.n_cols != nc) {
     set_error("%s: n_cols is %d, the handle has %zu columns", e, r.n_cols, nc);
@@ -3206,7 +3644,7 @@ static int append_entry(const char* entry, np_index* ix, const int64_t* doc_leng
     set_error("%s: %s", entry, n_docs < 0 ? "n_docs is negative" : "doc_lengths is NULL");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  if (rows) NP_TRY(check_append_rows(ix, *rows, n_docs));
+  if (rows) NP_TRY(check_append_rows(ix, *rows, n_docs, entry));
   if (n_docs == 0) return NP_OK;
   int64_t Tn = 0, maxlen = 0;
   for (int64_t d = 0; d < n_docs; ++d) {
@@ -3238,6 +3676,79 @@ int np_hip_index_append_rows(np_index* ix, const int64_t* doc_lengths, int64_t n
                              int64_t n_groups) {
   const AppendRows rows{new_cols, n_cols, code_remap, new_groups, n_groups};
   return append_entry("np_hip_index_append_rows", ix, doc_lengths, n_docs, codes, residuals, &rows);
+}
+
+// np_hip_index_expand and np_hip_index_expand_rows: the same checks under the entry's own name, all before any allocation
+static int expand_entry(const char* entry, np_index* ix, const float* new_centroids, int64_t k_new, int64_t n_replace,
+                        const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals, const AppendRows* rows) {
+  clear_error();
+  if (!ix) {
+    set_error("%s: index is NULL", entry);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (ix->opts.shard_count > 1) {
+    set_error("%s: index is a shard (%d of %d): a sharded index is reloaded", entry, ix->opts.shard_rank, ix->opts.shard_count);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (!ix->ivf_sorted) {
+    set_error("%s: index has posting lists that do not ascend: only such lists are cut and grown at their end", entry);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (k_new < 0 || (k_new > 0 && !new_centroids)) {
+    set_error("%s: %s", entry, k_new < 0 ? "k_new is negative" : "new_centroids is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (n_docs < 0 || (n_docs > 0 && !doc_lengths)) {
+    set_error("%s: %s", entry, n_docs < 0 ? "n_docs is negative" : "doc_lengths is NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (n_replace < 0 || n_replace > n_docs || n_replace > ix->n_docs) {
+    set_error("%s: n_replace is %lld: it lies in [0, n_docs = %lld] and within the handle's %lld documents", entry, (long long)n_replace,
+              (long long)n_docs, (long long)ix->n_docs);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (k_new == 0 && n_replace == 0) return append_entry(entry, ix, doc_lengths, n_docs, codes, residuals, rows);
+  const int64_t K1 = ix->K + k_new, N1 = ix->n_docs - n_replace + n_docs;
+  if (k_new >= ((int64_t)1 << 31) || K1 >= ((int64_t)1 << 31)) {   // check_geometry's limit on K
+    set_error("%s: k_new: %lld centroids and the handle's %lld exceed the 32-bit device id space", entry, (long long)k_new, (long long)ix->K);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (check_shard_docs(N1) != NP_OK || N1 >= ((int64_t)1 << 32) - 1) {
+    set_error("%s: n_docs: a shard holds < 2^31 documents (would be %lld)", entry, (long long)N1);
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  if (rows) NP_TRY(check_append_rows(ix, *rows, n_docs - n_replace, entry));
+  int64_t Tn = 0, maxlen = 0;
+  for (int64_t d = 0; d < n_docs; ++d) {
+    if (doc_lengths[d] < 0) {
+      set_error("%s: doc_lengths[%lld] is negative (%lld)", entry, (long long)d, (long long)doc_lengths[d]);
+      return NP_ERR_SHAPE;
+    }
+    Tn += doc_lengths[d];
+    maxlen = std::max(maxlen, doc_lengths[d]);
+  }
+  if (Tn > 0 && (!codes || !residuals)) {
+    set_error("%s: %s is NULL", entry, !codes ? "codes" : "residuals");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  for (int64_t t = 0; t < Tn; ++t)
+    if (codes[t] < 0 || codes[t] >= K1) {
+      set_error("%s: codes[%lld] = %lld is outside [0, %lld)", entry, (long long)t, (long long)codes[t], (long long)K1);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+  return expand_documents(entry, ix, new_centroids, k_new, n_replace, doc_lengths, n_docs, codes, residuals, Tn, maxlen, rows);
+}
+
+int np_hip_index_expand(np_index* ix, const float* new_centroids, int64_t k_new, int64_t n_replace, const int64_t* doc_lengths,
+                        int64_t n_docs, const int64_t* codes, const uint8_t* residuals) {
+  return expand_entry("np_hip_index_expand", ix, new_centroids, k_new, n_replace, doc_lengths, n_docs, codes, residuals, nullptr);
+}
+
+int np_hip_index_expand_rows(np_index* ix, const float* new_centroids, int64_t k_new, int64_t n_replace, const int64_t* doc_lengths,
+                             int64_t n_docs, const int64_t* codes, const uint8_t* residuals, const np_column* new_cols, int32_t n_cols,
+                             const int32_t* const* code_remap, const int32_t* new_groups, int64_t n_groups) {
+  const AppendRows rows{new_cols, n_cols, code_remap, new_groups, n_groups};
+  return expand_entry("np_hip_index_expand_rows", ix, new_centroids, k_new, n_replace, doc_lengths, n_docs, codes, residuals, &rows);
 }
 
 // np_hip_index_remove and np_hip_index_remove_keep: the same checks under the entry's own name

@@ -293,6 +293,7 @@ EXPORTS = [
     "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
     "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity", "np_hip_index_remove",
     "np_hip_index_remove_keep", "np_hip_index_append_rows", "np_hip_index_get_column", "np_hip_index_get_groups",
+    "np_hip_index_expand", "np_hip_index_expand_rows",
 ]
 
 _lib = None
@@ -466,6 +467,8 @@ def lib():
     L.np_hip_index_remove.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.np_hip_index_remove_keep.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.np_hip_index_append_rows.argtypes = [vp, vp, i64, vp, vp, C.POINTER(np_column), i32, vp, vp, i64]
+    L.np_hip_index_expand.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp]
+    L.np_hip_index_expand_rows.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, C.POINTER(np_column), i32, vp, vp, i64]
     L.np_hip_index_get_column.argtypes =[vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     L.np_hip_index_get_groups.argtypes = [vp, vp]
     L.np_hip_index_reserve.argtypes = [vp, i64, i64]
@@ -1001,6 +1004,35 @@ def _appended_tokens(index_path: str, before):
     if have_d != n_new or have_t != t_new:
         raise IndexLoadError(f"Index load failed: the chunk files hold {have_d} new documents / {have_t} tokens, "
                              f"metadata.json counts {n_new} / {t_new}")
+    pd = res[0].shape[1] if res else 0
+    return (np.concatenate(lens) if lens else np.zeros(0, np.int64),
+            np.concatenate(codes) if codes else np.zeros(0, np.int64),
+            np.concatenate(res) if res else np.zeros((0, pd), np.uint8))
+
+
+def _tail_documents(index_path: str, n_tail: int):
+    """_appended_tokens' reading for a given count: (doc_lengths, codes, residuals) of the directory's LAST n_tail documents,
+    from the tail of its last chunks -- what an update in expansion mode wrote behind the documents it kept."""
+    with open(os.path.join(index_path, "metadata.json"), "rb") as f:
+        m = json.loads(f.read())
+    lens, codes, res = [], [], []
+    have_d = 0
+    c = int(m["num_chunks"]) - 1
+    while have_d < n_tail and c >= 0:
+        with open(os.path.join(index_path, f"doclens.{c}.json"), "rb") as f:
+            dl = np.asarray(json.loads(f.read()), np.int64).reshape(-1)
+        take_d = min(n_tail - have_d, dl.size)
+        tail = dl[dl.size - take_d:]
+        take_t = int(tail.sum())
+        cd = np.load(os.path.join(index_path, f"{c}.codes.npy"), mmap_mode="r")
+        rs = np.load(os.path.join(index_path, f"{c}.residuals.npy"), mmap_mode="r")
+        lens.insert(0, tail)
+        codes.insert(0, np.asarray(cd[cd.shape[0] - take_t:], np.int64))
+        res.insert(0, np.asarray(rs[rs.shape[0] - take_t:], np.uint8))
+        have_d += take_d
+        c -= 1
+    if have_d != n_tail:
+        raise IndexLoadError(f"Index load failed: the chunk files hold {have_d} documents, {n_tail} were written")
     pd = res[0].shape[1] if res else 0
     return (np.concatenate(lens) if lens else np.zeros(0, np.int64),
             np.concatenate(codes) if codes else np.zeros(0, np.int64),
@@ -1672,7 +1704,7 @@ class MmapIndex:
         and the codes and residuals it wrote to the chunk files go to np_hip_index_append -- where update() reloads the whole
         index, this costs the new documents plus one pass over the posting lists.  The handle equals MmapIndex.load of the
         directory afterwards (no columns, keyword index or groups: attach them again -- or pass rows=AppendRows(...), see
-        append_arrays: they stay and take the new rows).  Not for centroid expansion: that changes K, so update() remains;
+        append_arrays: they stay and take the new rows).  For an update that may add centroids see update_resident();
         for delete see remove().  Returns the new ids."""
         path = self._dir("append")
         plan = None if rows is None else self._plan_rows(rows, len(documents))   # refused before the directory is touched
@@ -1689,6 +1721,113 @@ class MmapIndex:
             self.append_arrays(lens, codes, residuals)
         else:
             self._append_arrays_rows(np.ascontiguousarray(np.asarray(lens, np.int64).reshape(-1)), codes, residuals, rows, plan)
+        return ids
+
+    # -- expand the resident index (np_hip_index_expand) ----------------------------------------------------
+    def expand_arrays(self, new_centroids, doc_lengths, codes, residuals, n_replace: int = 0,
+                      rows: "AppendRows | None" = None, _plan=None):
+        """np_hip_index_expand on any unsharded handle: new_centroids [k_new, dim] join the codec as centroids K .., the
+        first n_replace of the given documents REPLACE the handle's last n_replace documents (same ids; new lengths, codes
+        and residuals) and the others take the ids num_documents() .. -- the crate's update in expansion mode, on the
+        handle, in one exclusive section and without reading the index again.  codes lie in [0, K + k_new).  The handle then
+        equals one freshly opened on the resulting index.  Columns, keyword index and groups are dropped as append_arrays
+        drops them; rows=AppendRows(...) (np_hip_index_expand_rows) keeps them: the replaced documents keep their rows, the
+        rows given cover the len(doc_lengths) - n_replace NEW documents, everything else as in append_arrays.  Returns the
+        given documents' ids, the replaced ones first."""
+        dim = self.embedding_dim()
+        cen = np.ascontiguousarray(np.asarray(new_centroids, np.float32))
+        if cen.size == 0:
+            cen = np.zeros((0, dim), np.float32)
+        if cen.ndim != 2 or cen.shape[1] != dim:
+            raise ShapeError(f"Shape error: new_centroids has shape {cen.shape}, expected [k_new, {dim}]")
+        dl = np.ascontiguousarray(np.asarray(doc_lengths, np.int64).reshape(-1))
+        cd = np.ascontiguousarray(np.asarray(codes, np.int64).reshape(-1))
+        rs = np.ascontiguousarray(residuals, np.uint8)
+        n_replace = int(n_replace)
+        tokens = int(dl.sum()) if dl.size and (dl >= 0).all() else 0
+        pd = dim * int(self._info.nbits) // 8
+        if cd.size < tokens or rs.size < tokens * pd:
+            raise ShapeError(f"Shape error: {tokens} tokens need {tokens} codes and {tokens * pd} residual bytes, got "
+                             f"{cd.size} and {rs.size}")
+        first = self.num_documents() - max(n_replace, 0)
+        head = (self._h, _ptr(cen) if cen.size else None, cen.shape[0], n_replace, _ptr(dl) if dl.size else None, dl.size,
+                _ptr(cd) if cd.size else None, _ptr(rs) if rs.size else None)
+        if rows is None:
+            _check(lib().np_hip_index_expand(*head))
+            if dl.size or cen.shape[0]:
+                self.schema = None
+                self.text = None
+                self.group_values = None
+            _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+            return np.arange(first, first + dl.size, dtype=np.int64)
+        n_new = max(dl.size - max(n_replace, 0), 0)
+        sch, new, remaps, gids, n_groups, values = _plan if _plan is not None else self._plan_rows(rows, n_new)
+        n_cols = len(sch) if sch is not None else 0
+        cols = (np_column * max(n_cols, 1))()
+        tables = (C.c_void_p * max(n_cols, 1))()
+        for c in (new or {}).values():
+            cols[c.index] = np_column(c.type, 0, c.data.ctypes.data, None if c.valid is None else c.valid.ctypes.data)
+            tables[c.index] = None if remaps[c.name] is None else remaps[c.name].ctypes.data
+        saved = self.text
+        _check(lib().np_hip_index_expand_rows(*head, cols, n_cols, C.cast(tables, C.c_void_p) if n_cols else None,
+                                              _ptr(gids) if gids is not None and gids.size else None, n_groups))
+        _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+        if n_new:
+            self.schema, self.group_values, self.text = sch, values, None
+            for c in (sch.columns.values() if sch is not None else ()):
+                if c.text_on_device and remaps[c.name] is not None:   # the library dropped the old dictionary's text
+                    text, off = c.text_arrays()
+                    _check(lib().np_hip_index_set_column_text(self._h, c.index, text.ctypes.data if text.size else None,
+                                                              _ptr(off), len(c.dictionary)))
+            if saved is not None:
+                self.update_text(new_texts=list(rows.texts), base=saved)
+            _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
+        return np.arange(first, first + dl.size, dtype=np.int64)
+
+    def update_resident(self, documents, config: UpdateConfig | None = None, rows: "AppendRows | None" = None) -> np.ndarray:
+        """update() on the handle's directory AND on the handle, without the reload: update_index_dir chooses the mode as the
+        crate does, and the handle follows the report -- buffer mode: append_arrays of what the directory gained; expansion
+        mode: expand_arrays with the centroids.npy rows the update added, n_replace = the buffered documents it re-indexed and
+        the tokens the chunk files hold beyond the kept documents; start-from-scratch mode (a small index is rebuilt whole):
+        reload(), which drops the attachments.  The handle equals MmapIndex.load of the directory afterwards.  rows: the
+        attachment rows of `documents`, as in append().  Returns the new ids; update() itself still reloads."""
+        path = self._dir("update_resident")
+        plan = None if rows is None else self._plan_rows(rows, len(documents))   # refused before the directory is touched
+        n_before = _dir_counts(path)
+        if n_before[0] != self.num_documents():
+            raise IndexLoadError(f"Index load failed: the directory holds {n_before[0]} documents, the handle "
+                                 f"{self.num_documents()}: the handle is not current, reload()")
+        _check(lib().np_hip_index_expand(self._h, None, 0, 0, None, 0, None, None))   # the library's checks of the handle
+        ids, self.last_update = update_index_dir(path, documents, config, self._open_opts.get("device", 0))
+        mode = self.last_update["mode"]
+        if mode == "none":
+            return ids
+        if mode == "start_from_scratch":
+            self.reload()
+            return ids
+        n_after = _dir_counts(path)
+        if mode == "expansion":
+            k_new = int(self.last_update["n_new_centroids"])
+            n_given = int(self.last_update["n_reindexed"]) + len(documents)
+            n_replace = n_before[0] - (n_after[0] - n_given)   # the buffered documents the update deleted from the tail
+            if n_replace < 0 or n_replace > n_given:
+                raise IndexLoadError(f"Index load failed: the directory gained {n_after[0] - n_before[0]} documents, the update "
+                                     f"wrote {n_given}: reload()")
+            lens, codes, residuals = _tail_documents(path, n_given)
+            cen = np.load(os.path.join(path, "centroids.npy"), mmap_mode="r")
+            if cen.shape[0] != self.num_partitions() + k_new:
+                raise IndexLoadError(f"Index load failed: the directory holds {cen.shape[0]} centroids, the handle "
+                                     f"{self.num_partitions()} and {k_new} new ones: the handle is not current, reload()")
+            self.expand_arrays(np.asarray(cen[cen.shape[0] - k_new:], np.float32), lens, codes, residuals, n_replace, rows, plan)
+        else:
+            lens, codes, residuals = _appended_tokens(path, n_before)
+            if rows is None:
+                self.append_arrays(lens, codes, residuals)
+            else:
+                self._append_arrays_rows(np.ascontiguousarray(np.asarray(lens, np.int64).reshape(-1)), codes, residuals, rows, plan)
+        if self.num_documents() != n_after[0]:
+            raise IndexLoadError(f"Index load failed: the directory gained {n_after[0] - n_before[0]} documents, the handle "
+                                 f"{self.num_documents() - n_before[0]}: reload()")
         return ids
 
     def reserve(self, extra_docs: int, extra_tokens: int):
