@@ -1639,6 +1639,69 @@ int np_hip_text_build_merge(int32_t device, const np_text_index* base, const uin
                             int64_t n_rows_out, const np_text_merge_opts* opts /* nullable */, np_text_build** out_build,
                             np_text_merge_report* report /* nullable */);
 
+/* ---- The resident keyword index: built and updated without leaving HBM (np_textres.hip; DESIGN.md section 4, "The resident
+ * keyword index") ----
+ * np_hip_text_build and np_hip_text_build_merge leave their result in HBM; these entries keep it there.  Only the vocabulary
+ * strings and a few counts cross the bus.
+ *
+ * np_hip_index_set_text_build installs a finalised build (np_hip_text_build + _add + _sizes, or a merge's result) as the
+ * handle's keyword index.  The result equals, array for array, np_hip_index_set_text given the arrays
+ * np_hip_text_build_fetch would return.  On the device (each step a launch; no workgroup waits for another; integers only;
+ * the one atomic is the integer add into a document's length, whose sum does not depend on the order of arrival):
+ *   check     np_hip_index_set_text's checks per instance -- the document inside [0, n_docs), the position >= 0, (document,
+ *             position) ascending strictly inside a term; every block reports its lowest offender, the host takes the minimum
+ *             and names that instance and its rule
+ *   heads     instance i starts a posting when it is the first of its term (the term starts come from term_offsets) or names
+ *             another document than instance i - 1: two neighbouring terms that end and begin with one document stay apart
+ *   postings  an exclusive scan of the heads numbers the postings; a head writes its document and its own index (the
+ *             posting's first position); the term frequency is the distance to the next head; a term's list starts at the
+ *             rank of its first instance (a term without instances has an empty list)
+ *   doc_len   every posting adds its term frequency to its document; n_rows must not be below the nonzero entries
+ * The positions are inst_pos verbatim: the handle takes the build's array instead of copying it, and inst_doc is freed once
+ * the postings exist.  The build is then CONSUMED: np_hip_text_build_sizes and the vocabulary half of np_hip_text_build_fetch
+ * (term_bytes, term_byte_offsets) still serve it and np_hip_text_build_free frees it; the instance half of _fetch, a second
+ * install and a merge that takes it as its batch are refused by name.  A build that np_hip_text_build_sizes merged on the host
+ * (fallback documents) is uploaded first.  The new index is built beside the old one and swapped in whole: a refused call, and
+ * NP_ERR_OUT_OF_MEMORY, leave the handle AND the build as they were.  The peak device bytes depend on the sizes alone:
+ * np_hip_index_set_text_build_bytes(n_terms, n_instances, n_docs of the handle), the build's own arrays included.  A build
+ * without instances and rows drops the handle's keyword index, as np_hip_index_set_text does.
+ * The call takes the handle as np_hip_index_append does: searches that run finish on the old keyword index, later ones see
+ * the new one, and the caller needs no lock of its own (np_hip_index_set_text does).
+ * NP_ERR_INVALID_ARGUMENT, by name: a NULL index or build, a build that is not finalised, lies on another device or is
+ * consumed, a handle opened with shard_count > 1 (a slice needs the whole table's document frequencies:
+ * np_hip_index_set_text_shard), an instance that fails the checks, n_rows below the documents that hold a token (a backstop: no build the library
+ * makes can meet it -- np_hip_text_build's n_rows is its document count and the merges check n_rows_out first -- so no test
+ * reaches it).  The call also compares what it held with np_hip_index_set_text_build_bytes and fails if the plan was exceeded.
+ *
+ * np_hip_index_text_merge is np_hip_text_build_merge whose base A is the handle's keyword index, read where it lies: the
+ * result is a finalised device build, byte-equal to that call's on the fetched base, and every rule of remap, delta_ids and
+ * n_rows_out holds.  The handle is not modified (the call registers like a search: an append or an install waits for it).
+ * The base is not uploaded and not checked instance by instance again -- it was when it was installed.  Its term_offsets and
+ * inst_doc are regenerated from the postings into the call's workspace by one launch (term_offsets[k] = the first position
+ * of term k's first posting; an instance's document = that of the last posting that starts at or before it), pos_A is the
+ * handle's array, and the merge's kernels run unchanged.  Where n_rows_out is below survivors plus batch, the survivors that
+ * hold a token are counted from the documents' lengths and remap by one reduction on the device.  base_term_bytes /
+ * base_term_byte_offsets are the handle's vocabulary: exactly its n_terms strings (the host mirrors, which hold the arrays,
+ * refuse another length).  Documents of the handle at or behind n_remap must hold no token.  report->ms_upload covers the
+ * maps, the regenerating launch and the two counts over the handle's documents where they run; report->workspace_bytes is the planned need, np_hip_text_build_merge's without pos_A
+ * plus the reduction's flags.  Refusals: np_hip_text_build_merge's, a handle without a keyword index, a sharded handle.
+ *
+ * np_hip_index_text_sizes, np_hip_index_get_text and np_hip_index_get_text_layout read the handle's keyword index back, as
+ * np_hip_index_get_column does a column: the sizes; the table regenerated from HBM (term_offsets [n_terms + 1], inst_doc /
+ * inst_pos [n_instances]); the layout as it lies (post_off [n_terms + 1], post_doc / post_tf / post_first [n_postings],
+ * doc_len [n_docs]).  Any pointer may be NULL.  Unsharded handles with a keyword index only. */
+int np_hip_index_set_text_build(np_index* index, np_text_build* build);
+int64_t np_hip_index_set_text_build_bytes(int64_t n_terms, int64_t n_instances, int64_t n_docs);
+int np_hip_index_text_merge(const np_index* index, const uint8_t* base_term_bytes, const int64_t* base_term_byte_offsets,
+                            const int64_t* remap, int64_t n_remap, const np_text_build* delta /* finalised; NULL = empty batch */,
+                            const int64_t* delta_ids, int64_t n_rows_out, const np_text_merge_opts* opts /* nullable */,
+                            np_text_build** out_build, np_text_merge_report* report /* nullable */);
+int np_hip_index_text_sizes(const np_index* index, int64_t* n_terms, int64_t* n_postings, int64_t* n_instances, int64_t* n_rows,
+                            int64_t* n_docs);
+int np_hip_index_get_text(const np_index* index, int64_t* term_offsets, int64_t* inst_doc, int32_t* inst_pos);
+int np_hip_index_get_text_layout(const np_index* index, int64_t* post_off, int32_t* post_doc, int32_t* post_tf,
+                                 int64_t* post_first, int32_t* doc_len);
+
 /* Stage-level debug access for parity tests: runs S1-S5 for ONE query and copies out the probed
  * cells (ascending), candidate doc ids (ascending, global), their approximate scores, and the
  * selected docs in approx-rank order with their exact scores.  Capacities are in elements;

@@ -38,6 +38,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1474,6 +1475,11 @@ class MmapIndex {
   size_t embedding_dim() const { return (size_t)info_.embedding_dim; }
   const np_info& info() const { return info_; }
   np_index* handle() const { return h_; }
+  // info() again from the library: after a call on handle() that changed what the handle holds (the resident keyword index)
+  void refresh_info() {
+    require_device("refresh_info");
+    check(np_hip_index_info(h_, &info_));
+  }
 
   std::string path;
   mutable np_stats last_stats{};
@@ -1824,6 +1830,169 @@ inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const Text
                                           int device = 0, int32_t max_token_bytes = 0) {
   return detail::text_update_run(base, update, tokenizer, device, max_token_bytes,
                                  [&](detail::TextBuildHandle& b, const BuiltTextIndex& r) { detail::text_build_add_fallback(b, r, tokenize); });
+}
+
+// ---- the resident keyword index (np_hip_index_set_text_build, np_hip_index_text_merge): built and updated in HBM ----
+// What a handle's keyword index is to the host when its arrays stay on the device: the vocabulary and the counts.  The
+// arrays come back with get_text (np_hip_index_get_text) when they are wanted.
+struct ResidentTextIndex {
+  std::vector<std::string> terms;          // term id -> term, in fts5vocab's order
+  int64_t n_rows = 0;
+  int64_t n_instances = 0;
+  std::vector<int64_t> fallback_docs;      // of the build, or of the update's batch
+  np_text_build_report report{};           // the build's, or the batch's
+  np_text_merge_report merge_report{};     // the merge's (update_text_resident)
+};
+
+namespace detail {
+// np_hip_text_build_sizes, np_hip_index_set_text_build and the vocabulary half of np_hip_text_build_fetch
+inline void text_install(MmapIndex& ix, TextBuildHandle& b, ResidentTextIndex* r) {
+  check(np_hip_text_build_sizes(b.h, nullptr, nullptr, nullptr, nullptr));
+  check(np_hip_index_set_text_build(ix.handle(), b.h));
+  int64_t n_terms = 0, n_bytes = 0;
+  check(np_hip_text_build_sizes(b.h, &n_terms, &n_bytes, &r->n_instances, &r->n_rows));
+  std::vector<uint8_t> tb((size_t)std::max<int64_t>(n_bytes, 1));
+  std::vector<int64_t> tbo((size_t)n_terms + 1);
+  check(np_hip_text_build_fetch(b.h, tb.data(), tbo.data(), nullptr, nullptr, nullptr));
+  r->terms.resize((size_t)n_terms);
+  for (int64_t t = 0; t < n_terms; ++t) r->terms[(size_t)t].assign((const char*)tb.data() + tbo[(size_t)t], (size_t)(tbo[(size_t)t + 1] - tbo[(size_t)t]));
+  ix.refresh_info();
+}
+
+// np_hip_index_text_merge of the handle's keyword index (whose vocabulary is cur.terms) with the update's batch
+template <class AddFallback>
+inline void text_merge_resident(const MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& u, Tokenizer tokenizer,
+                                int32_t max_token_bytes, AddFallback&& add_fallback, TextBuildHandle* merged, ResidentTextIndex* r) {
+  int64_t have = 0;
+  check(np_hip_index_text_sizes(ix.handle(), &have, nullptr, nullptr, nullptr, nullptr));
+  if (have != (int64_t)cur.terms.size())
+    throw Error(NP_ERR_INVALID_ARGUMENT, ("base_term_byte_offsets describes " + std::to_string(cur.terms.size()) +
+                                          " terms, the handle's keyword index holds " + std::to_string(have)).c_str());
+  std::vector<int64_t> remap, delta_ids;
+  std::vector<std::string> texts;
+  int64_t n_rows_out = 0;
+  text_update_plan(cur.n_rows, u, &remap, &delta_ids, &texts, &n_rows_out);
+  std::vector<int64_t> tbo(cur.terms.size() + 1, 0);
+  for (size_t i = 0; i < cur.terms.size(); ++i) tbo[i + 1] = tbo[i] + (int64_t)cur.terms[i].size();
+  std::vector<uint8_t> tb((size_t)tbo.back());
+  for (size_t i = 0; i < cur.terms.size(); ++i) std::copy(cur.terms[i].begin(), cur.terms[i].end(), tb.begin() + tbo[i]);
+  TextBuildHandle batch;
+  if (!texts.empty()) {
+    BuiltTextIndex built;
+    text_build_start(batch, texts, text_build_opts(tokenizer, max_token_bytes), ix.info().device, &built);
+    add_fallback(batch, built);
+    check(np_hip_text_build_sizes(batch.h, nullptr, nullptr, nullptr, nullptr));
+    r->fallback_docs = built.fallback_docs;
+    r->report = built.report;
+  }
+  np_text_merge_opts o{};
+  check(np_hip_index_text_merge(ix.handle(), tb.empty() ? nullptr : tb.data(), tbo.data(), remap.empty() ? nullptr : remap.data(),
+                                (int64_t)remap.size(), batch.h, delta_ids.empty() ? nullptr : delta_ids.data(), n_rows_out, &o,
+                                &merged->h, &r->merge_report));
+}
+
+inline void text_no_fallback(TextBuildHandle&, const BuiltTextIndex& r) {
+  if (!r.fallback_docs.empty())
+    throw Error(NP_ERR_INVALID_ARGUMENT, ("update_text_resident: batch document " + std::to_string(r.fallback_docs[0]) +
+                                          " is not reproduced on the device and no tokenize was given").c_str());
+}
+}  // namespace detail
+
+// build_text_index whose result stays in HBM and becomes the handle's keyword index: build -> (fallback -> add) -> sizes ->
+// np_hip_index_set_text_build.  Only the vocabulary is fetched.  Searches beside the call go on; no lock is needed.
+inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<std::string>& texts, Tokenizer tokenizer = Tokenizer::Unicode61,
+                                             int32_t max_token_bytes = 0) {
+  ResidentTextIndex r;
+  BuiltTextIndex built;
+  detail::TextBuildHandle b;
+  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), ix.info().device, &built);
+  if (!built.fallback_docs.empty())
+    throw Error(NP_ERR_INVALID_ARGUMENT, ("build_text_resident: document " + std::to_string(built.fallback_docs[0]) +
+                                          " is not reproduced on the device and no tokenize was given").c_str());
+  r.report = built.report;
+  detail::text_install(ix, b, &r);
+  return r;
+}
+template <class Tokenize>
+inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<std::string>& texts, Tokenizer tokenizer, Tokenize&& tokenize,
+                                             int32_t max_token_bytes = 0) {
+  ResidentTextIndex r;
+  BuiltTextIndex built;
+  detail::TextBuildHandle b;
+  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), ix.info().device, &built);
+  detail::text_build_add_fallback(b, built, tokenize);
+  r.report = built.report;
+  r.fallback_docs = built.fallback_docs;
+  detail::text_install(ix, b, &r);
+  return r;
+}
+
+// The handle's keyword index updated from itself: the batch is built on the device, np_hip_index_text_merge reads the base
+// where it lies and np_hip_index_set_text_build installs the result.  `cur` is what the last resident call returned (its
+// vocabulary and row count are the base's).  `step` runs between the merge and the install: the vector-index call that
+// drops the handle's keyword index (append_arrays with rows, remove_ids with keep_attachments, expand_arrays with rows), so
+// that the order is merge, vector call, install.  If it throws, the handle keeps its old keyword index and the result is freed.
+template <class Step>
+inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update, Step&& step,
+                                              Tokenizer tokenizer = Tokenizer::Unicode61, int32_t max_token_bytes = 0) {
+  ResidentTextIndex r;
+  detail::TextBuildHandle merged;
+  detail::text_merge_resident(ix, cur, update, tokenizer, max_token_bytes, detail::text_no_fallback, &merged, &r);
+  step();
+  detail::text_install(ix, merged, &r);
+  return r;
+}
+inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update,
+                                              Tokenizer tokenizer = Tokenizer::Unicode61, int32_t max_token_bytes = 0) {
+  return update_text_resident(ix, cur, update, [] {}, tokenizer, max_token_bytes);
+}
+// ... tokenize(fallback_docs) is called once when the batch has fallback documents (a byte >= 0x80, ...); the ids index the
+// batch (the replacements in id order, then new_texts), as in update_text_index.
+template <class Step, class Tokenize, class = typename std::enable_if<!std::is_integral<typename std::decay<Tokenize>::type>::value>::type>
+inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update, Step&& step,
+                                              Tokenizer tokenizer, Tokenize&& tokenize, int32_t max_token_bytes = 0) {
+  ResidentTextIndex r;
+  detail::TextBuildHandle merged;
+  detail::text_merge_resident(ix, cur, update, tokenizer, max_token_bytes,
+                              [&](detail::TextBuildHandle& b, const BuiltTextIndex& built) { detail::text_build_add_fallback(b, built, tokenize); },
+                              &merged, &r);
+  step();
+  detail::text_install(ix, merged, &r);
+  return r;
+}
+
+// The handle's keyword index read back from HBM (np_hip_index_get_text) with the vocabulary the host kept.
+inline BuiltTextIndex get_text(const MmapIndex& ix, const std::vector<std::string>& terms) {
+  BuiltTextIndex r;
+  int64_t n_terms = 0, n_inst = 0;
+  check(np_hip_index_text_sizes(ix.handle(), &n_terms, nullptr, &n_inst, &r.n_rows, nullptr));
+  if (n_terms != (int64_t)terms.size())
+    throw Error(NP_ERR_INVALID_ARGUMENT, ("get_text: the handle's keyword index holds " + std::to_string(n_terms) + " terms, the vocabulary " +
+                                          std::to_string(terms.size())).c_str());
+  r.terms = terms;
+  r.term_offsets.resize((size_t)n_terms + 1);
+  r.inst_doc.resize((size_t)n_inst);
+  r.inst_pos.resize((size_t)n_inst);
+  check(np_hip_index_get_text(ix.handle(), r.term_offsets.data(), r.inst_doc.data(), r.inst_pos.data()));
+  return r;
+}
+
+// ... and as it lies (np_hip_index_get_text_layout)
+struct TextLayout {
+  std::vector<int64_t> post_off, post_first;
+  std::vector<int32_t> post_doc, post_tf, doc_len;
+};
+inline TextLayout get_text_layout(const MmapIndex& ix) {
+  TextLayout l;
+  int64_t n_terms = 0, n_post = 0, n_docs = 0;
+  check(np_hip_index_text_sizes(ix.handle(), &n_terms, &n_post, nullptr, nullptr, &n_docs));
+  l.post_off.resize((size_t)n_terms + 1);
+  l.post_doc.resize((size_t)n_post);
+  l.post_tf.resize((size_t)n_post);
+  l.post_first.resize((size_t)n_post);
+  l.doc_len.resize((size_t)n_docs);
+  check(np_hip_index_get_text_layout(ix.handle(), l.post_off.data(), l.post_doc.data(), l.post_tf.data(), l.post_first.data(), l.doc_len.data()));
+  return l;
 }
 
 }  // namespace next_plaid

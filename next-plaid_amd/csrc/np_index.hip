@@ -1676,32 +1676,6 @@ static int merge_posting_lists(const DeviceIndex* ix, const Ucodes& u, const int
   return NP_OK;
 }
 
-// every context of the handle's pool checked out (np_internal.h DeviceIndex::exclusive): running calls finish on the index as
-// it was, calls that arrive wait in acquire_context, and nobody sees a half-grown handle
-struct HoldContexts {
-  const DeviceIndex* ix;
-  explicit HoldContexts(const DeviceIndex* i) : ix(i) {
-    std::unique_lock<std::mutex> lk(ix->mu);
-    ix->cv.wait(lk, [&] { return !ix->exclusive; });
-    ix->exclusive = true;
-    ix->cv.wait(lk, [&] {   // the calls registered outside a context (IndexRead) end, then the contexts fall idle
-      if (ix->readers > 0) return false;
-      for (const Context* c : ix->contexts)
-        if (c->busy) return false;
-      return true;
-    });
-    for (Context* c : ix->contexts) c->busy = true;
-  }
-  ~HoldContexts() {
-    {
-      std::lock_guard<std::mutex> lk(ix->mu);
-      for (Context* c : ix->contexts) c->busy = false;
-      ix->exclusive = false;
-    }
-    ix->cv.notify_all();
-  }
-};
-
 template <class T>
 static int grow_array(DeviceIndex* ix, DevPtr<T>& a, size_t used, size_t want) {
   DevPtr<T> f;

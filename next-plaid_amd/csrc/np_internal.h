@@ -419,6 +419,32 @@ struct IndexRead {
   IndexRead(const IndexRead&) = delete;
   IndexRead& operator=(const IndexRead&) = delete;
 };
+// every context of the handle's pool checked out (DeviceIndex::exclusive; np_hip_index_append / _remove / _expand / _reserve and
+// np_hip_index_set_text_build): running calls finish on the index as it was, calls that arrive wait in acquire_context, and
+// nobody sees a half-changed handle
+struct HoldContexts {
+  const DeviceIndex* ix;
+  explicit HoldContexts(const DeviceIndex* i) : ix(i) {
+    std::unique_lock<std::mutex> lk(ix->mu);
+    ix->cv.wait(lk, [&] { return !ix->exclusive; });
+    ix->exclusive = true;
+    ix->cv.wait(lk, [&] {   // the calls registered outside a context (IndexRead) end, then the contexts fall idle
+      if (ix->readers > 0) return false;
+      for (const Context* c : ix->contexts)
+        if (c->busy) return false;
+      return true;
+    });
+    for (Context* c : ix->contexts) c->busy = true;
+  }
+  ~HoldContexts() {
+    {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      for (Context* c : ix->contexts) c->busy = false;
+      ix->exclusive = false;
+    }
+    ix->cv.notify_all();
+  }
+};
 void destroy_context(Context* c);
 // after np_hip_index_append (every context held): the contexts forget what they learnt about the index they served
 void contexts_forget_index(const DeviceIndex* ix);

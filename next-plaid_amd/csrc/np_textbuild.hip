@@ -779,6 +779,12 @@ int np_hip_text_build_fetch(const np_text_build* build, uint8_t* term_bytes, int
   const std::vector<int64_t>& tbo = build->merged ? build->out.term_byte_offsets : build->term_byte_offsets;
   if (term_bytes && !tb.empty()) memcpy(term_bytes, tb.data(), tb.size());
   if (term_byte_offsets) memcpy(term_byte_offsets, tbo.data(), tbo.size() * 8);
+  if (build->consumed && (term_offsets || inst_doc || inst_pos)) {
+    set_error("np_hip_text_build_fetch: %s: the build is consumed, np_hip_index_set_text_build gave its instance arrays to a handle "
+              "(np_hip_index_get_text reads them back)",
+              term_offsets ? "term_offsets" : inst_doc ? "inst_doc" : "inst_pos");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
   if (!build->merged) return tb_download(build, term_offsets, inst_doc, inst_pos);
   const TextArrays& o = build->out;
   if (term_offsets) memcpy(term_offsets, o.term_offsets.data(), o.term_offsets.size() * 8);

@@ -18,6 +18,9 @@ struct np_text_build {
   np::DevPtr<int32_t> d_inst_pos;
   // the fallback documents' instances (np_hip_text_build_add)
   bool added = false, finalised = false, merged = false;
+  // np_hip_index_set_text_build installed it: inst_pos belongs to the handle, inst_doc and term_offsets are freed; the sizes
+  // and the vocabulary stay
+  bool consumed = false;
   std::vector<uint8_t> b_bytes;
   std::vector<int64_t> b_tbo, b_doc;
   std::vector<int32_t> b_term, b_pos;
@@ -25,6 +28,23 @@ struct np_text_build {
 };
 
 namespace np {
+
+// The base of a merge that lies in a handle (np_hip_index_text_merge, np_textres.hip): term_offsets and inst_doc regenerated
+// from the postings into the call's workspace, pos read where it lies.  Without one the base comes from the host.
+struct TextMergeResident {
+  const DeviceIndex* ix = nullptr;
+  int64_t n_docs = 0;       // the handle's documents: doc_len's entries
+};
+// np_textmerge.hip: np_hip_text_build_merge, and with `res` np_hip_index_text_merge (`base` is then NULL)
+int text_merge_impl(const char* entry, int device, const np_text_index* base, const TextMergeResident* res, const uint8_t* a_bytes,
+                    const int64_t* a_tbo, const int64_t* remap, int64_t n_remap, const np_text_build* delta, const int64_t* delta_ids,
+                    int64_t n_rows_out, const np_text_merge_opts* opts, np_text_build* R, np_text_merge_report* rep);
+// np_textres.hip: term_offsets [n_terms + 1] and inst_doc [n_inst] of a handle's keyword index, from its postings
+int textres_expand(hipStream_t st, const DeviceText& t, int64_t* toff, int64_t* inst_doc);
+// np_textres.hip: entries d < n of doc_len with doc_len[d] > 0 and (remap given) remap[d] >= 0; flags and scan hold n + 1 each
+int textres_count_docs(hipStream_t st, const int32_t* doc_len, int64_t n, const int64_t* d_remap, uint32_t* flags, uint32_t* scan,
+                       uint64_t* sums, int64_t* out);
+
 namespace {
 
 // ---- exclusive scan of u32 counts: reduce per block, scan the block sums in one block, apply ----------------------------

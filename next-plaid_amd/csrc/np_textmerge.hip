@@ -7,6 +7,7 @@
 #include <new>
 #include "np_textbuild_dev.h"
 #include "np_textmerge_plan.h"
+#include "np_textres_plan.h"
 
 namespace np {
 namespace {
@@ -125,9 +126,11 @@ int tm_alloc(DevPtr<T>& p, int64_t n) {
   return p.alloc((size_t)std::max<int64_t>(n, 1));
 }
 
-int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_bytes, const int64_t* a_tbo, const int64_t* remap,
-                    int64_t n_remap, const np_text_build* delta, const int64_t* delta_ids, int64_t n_rows_out,
-                    const np_text_merge_opts* opts, np_text_build* R, np_text_merge_report* rep) {
+}  // namespace
+
+int text_merge_impl(const char* entry, int device, const np_text_index* base, const TextMergeResident* res, const uint8_t* a_bytes,
+                    const int64_t* a_tbo, const int64_t* remap, int64_t n_remap, const np_text_build* delta, const int64_t* delta_ids,
+                    int64_t n_rows_out, const np_text_merge_opts* opts, np_text_build* R, np_text_merge_report* rep) {
   const auto t_all = Clock::now();
   auto t0 = t_all;
   // ---- the batch: where its arrays lie
@@ -138,11 +141,16 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   const int32_t* b_pos_host = nullptr;
   if (delta) {
     if (!delta->finalised) {
-      set_error("np_hip_text_build_merge: delta is not finalised: call np_hip_text_build_sizes on it first");
+      set_error("%s: delta is not finalised: call np_hip_text_build_sizes on it first", entry);
+      return NP_ERR_INVALID_ARGUMENT;
+    }
+    if (delta->consumed) {
+      set_error("%s: delta is consumed: np_hip_index_set_text_build installed it and its instance arrays belong to that handle", entry);
       return NP_ERR_INVALID_ARGUMENT;
     }
     if (delta->device != device) {
-      set_error("np_hip_text_build_merge: delta was built on device %d, the call names device %d", delta->device, device);
+      set_error(res ? "%s: delta was built on device %d, the index lies on device %d" : "%s: delta was built on device %d, the call names device %d",
+                entry, delta->device, device);
       return NP_ERR_INVALID_ARGUMENT;
     }
     const std::vector<uint8_t>& tb = upload_b ? delta->out.term_bytes : delta->term_bytes;
@@ -171,11 +179,25 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   // ---- every check, with or without a device
   TextMergePlan P;
   char why[320];
+  bool need_distinct = false;   // (resident base) the survivors that hold a token are counted on the device
   {
-    const int rc = textmerge_plan(base, a_bytes, a_tbo, remap, n_remap, D, delta_ids, n_rows_out, upload_b || !delta,
-                                  opts ? opts->workspace_bytes : 0, &P, why, sizeof(why));
+    int rc;
+    if (res) {
+      TextResBase hb;
+      hb.present = res->ix->text.present;
+      hb.shard_count = res->ix->opts.shard_count > 1 || res->ix->text.slice ? std::max(res->ix->opts.shard_count, 2) : 1;
+      hb.n_terms = res->ix->text.n_terms;
+      hb.n_inst = res->ix->text.n_inst;
+      hb.n_docs = res->n_docs;
+      rc = textres_merge_plan(hb, a_bytes, a_tbo, remap, n_remap, D, delta_ids, n_rows_out, upload_b || !delta,
+                              opts ? opts->workspace_bytes : 0, &P, &need_distinct, why, sizeof(why));
+    } else {
+      rc = textmerge_plan(base, a_bytes, a_tbo, remap, n_remap, D, delta_ids, n_rows_out, upload_b || !delta,
+                          opts ? opts->workspace_bytes : 0, &P, why, sizeof(why));
+    }
     if (rc != NP_OK) {
-      set_error(rc == NP_ERR_SHAPE ? "%s" : "np_hip_text_build_merge: %s", why);
+      if (rc == NP_ERR_SHAPE) set_error("%s", why);
+      else set_error("%s: %s", entry, why);
       return rc;
     }
   }
@@ -185,7 +207,7 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
     size_t free_b = 0, total_b = 0;
     NP_HIP(hipMemGetInfo(&free_b, &total_b));
     if (P.workspace_bytes > (int64_t)(free_b - free_b / 16)) {
-      set_error("np_hip_text_build_merge: the device's free memory of %zu bytes does not hold the call: it needs %lld", free_b,
+      set_error("%s: the device's free memory of %zu bytes does not hold the call: it needs %lld", entry, free_b,
                 (long long)P.workspace_bytes);
       return NP_ERR_OUT_OF_MEMORY;
     }
@@ -203,9 +225,18 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   DevPtr<uint32_t> d_keep, d_S, d_ua, d_ub, d_cnt, d_alive, d_rank;
   DevPtr<uint64_t> d_sums;
   const int64_t zero = 0;
-  NP_TRY(tm_upload(d_toff_a, Ta > 0 ? base->term_offsets : &zero, Ta + 1, 0, st));
-  NP_TRY(tm_upload(d_doc_a, base->inst_doc, na, 1, st));
-  NP_TRY(tm_upload(d_pos_a, base->inst_pos, na, 1, st));
+  const int32_t* pos_a = nullptr;
+  if (res) {   // the base is read where it lies: term_offsets and inst_doc regenerated from the postings, pos as it is
+    NP_TRY(tm_alloc(d_toff_a, Ta + 1));
+    NP_TRY(tm_alloc(d_doc_a, na + 1));
+    NP_TRY(textres_expand(st, res->ix->text, d_toff_a.get(), d_doc_a.get()));
+    pos_a = res->ix->text.pos.get();
+  } else {
+    NP_TRY(tm_upload(d_toff_a, Ta > 0 ? base->term_offsets : &zero, Ta + 1, 0, st));
+    NP_TRY(tm_upload(d_doc_a, base->inst_doc, na, 1, st));
+    NP_TRY(tm_upload(d_pos_a, base->inst_pos, na, 1, st));
+    pos_a = d_pos_a.get();
+  }
   NP_TRY(tm_upload(d_remap, remap, n_remap, 1, st));
   NP_TRY(tm_upload(d_ua, (const uint32_t*)P.ua.data(), Ta, 1, st));
   NP_TRY(tm_upload(d_ub, (const uint32_t*)P.ub.data(), Tb, 1, st));
@@ -237,6 +268,38 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   NP_TRY(tm_alloc(d_rank, U + 1));
   NP_TRY(tm_alloc(d_sums, textbuild_scan_sums(std::max(na, U) + 1)));
   NP_HIP(hipStreamSynchronize(st));
+  // (resident base) the counts over the handle's documents belong to this stage too: ms_upload is taken behind them
+  if (res && (need_distinct || n_remap < res->n_docs)) {
+    DevPtr<uint32_t> d_flag, d_scan;
+    DevPtr<uint64_t> d_fsums;
+    NP_TRY(tm_alloc(d_flag, res->n_docs + 1));
+    NP_TRY(tm_alloc(d_scan, res->n_docs + 1));
+    NP_TRY(tm_alloc(d_fsums, textbuild_scan_sums(res->n_docs + 1)));
+    const int32_t* doc_len = res->ix->text.doc_len.get();
+    const int64_t n_told = std::min(n_remap, res->n_docs);   // the handle's documents that have a verdict
+    if (n_told < res->n_docs) {   // a base document >= n_remap: the documents behind remap must hold no token
+      int64_t beyond = 0;
+      NP_TRY(textres_count_docs(st, doc_len + n_told, res->n_docs - n_told, nullptr, d_flag.get(), d_scan.get(), d_fsums.get(), &beyond));
+      if (beyond > 0) {
+        set_error("%s: base: %lld documents of the handle's keyword index hold a token and lie outside the index (the index is n_remap = "
+                  "%lld old documents)", entry, (long long)beyond, (long long)n_remap);
+        return NP_ERR_INVALID_ARGUMENT;
+      }
+    }
+    if (need_distinct) {   // n_rows_out against the documents of the result that hold a token: the batch's plus the survivors'
+      int64_t distinct = 0;
+      NP_TRY(textres_count_docs(st, doc_len, n_told, d_remap.get(), d_flag.get(), d_scan.get(), d_fsums.get(), &distinct));
+      std::vector<bool> seen_b((size_t)D.n_docs, false);
+      for (int64_t k = 0; k < D.n_inst; ++k)
+        if (!seen_b[(size_t)D.inst_doc[k]]) seen_b[(size_t)D.inst_doc[k]] = true, ++distinct;
+      if (n_rows_out < distinct) {
+        set_error("%s: n_rows_out %lld is below the %lld documents of the result that hold a token", entry, (long long)n_rows_out,
+                  (long long)distinct);
+        return NP_ERR_INVALID_ARGUMENT;
+      }
+    }
+  }
+
   const double ms_upload = ms_since(t0);
 
   // ---- keep, S; the terms' counts, off and the alive terms' numbers
@@ -263,7 +326,7 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   NP_HIP(hipStreamSynchronize(st));
   const double ms_count = ms_since(t0);
   if (total < 0 || total > na + nb || (int64_t)n_alive > U) {
-    set_error("np_hip_text_build_merge: the device counted %lld instances and %u terms from %lld + %lld instances and %lld terms",
+    set_error("%s: the device counted %lld instances and %u terms from %lld + %lld instances and %lld terms", entry,
               (long long)total, n_alive, (long long)na, (long long)nb, (long long)U);
     return NP_ERR_DEVICE_UNAVAILABLE;
   }
@@ -280,7 +343,7 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   NP_TRY(tm_alloc(R->d_inst_pos, total));
   if (na > 0 && total > 0) {
     hipLaunchKernelGGL(tm_place_a, dim3(grid_of(na, 256)), dim3(256), 0, st, (const int64_t*)d_toff_a.get(), Ta,
-                       (const int64_t*)d_doc_a.get(), (const int32_t*)d_pos_a.get(), na, (const int64_t*)d_remap.get(),
+                       (const int64_t*)d_doc_a.get(), pos_a, na, (const int64_t*)d_remap.get(),
                        (const uint32_t*)d_keep.get(), (const uint32_t*)d_S.get(), (const uint32_t*)d_ua.get(), (const int32_t*)d_b_of.get(),
                        toff_b, doc_b, (const int64_t*)d_ids.get(), (const int64_t*)d_off.get(), total, R->d_inst_doc.get(),
                        R->d_inst_pos.get());
@@ -331,7 +394,6 @@ int text_merge_impl(int device, const np_text_index* base, const uint8_t* a_byte
   return NP_OK;
 }
 
-}  // namespace
 }  // namespace np
 
 using namespace np;
@@ -353,7 +415,7 @@ extern "C" int np_hip_text_build_merge(int32_t device, const np_text_index* base
   }
   int rc;
   try {
-    rc = text_merge_impl(device, base, base_term_bytes, base_term_byte_offsets, remap, n_remap, delta, delta_ids, n_rows_out, opts, b,
+    rc = text_merge_impl("np_hip_text_build_merge", device, base, nullptr, base_term_bytes, base_term_byte_offsets, remap, n_remap, delta, delta_ids, n_rows_out, opts, b,
                          report);
   } catch (const std::bad_alloc&) {
     set_error("np_hip_text_build_merge: out of host memory");

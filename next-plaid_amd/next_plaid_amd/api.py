@@ -291,6 +291,8 @@ EXPORTS = [
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
     "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
+    "np_hip_index_set_text_build", "np_hip_index_set_text_build_bytes", "np_hip_index_text_merge", "np_hip_index_text_sizes",
+    "np_hip_index_get_text", "np_hip_index_get_text_layout",
     "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity", "np_hip_index_remove",
     "np_hip_index_remove_keep", "np_hip_index_append_rows", "np_hip_index_get_column", "np_hip_index_get_groups",
     "np_hip_index_expand", "np_hip_index_expand_rows",
@@ -486,6 +488,14 @@ def lib():
     L.np_hip_text_build_free.restype = None
     L.np_hip_text_build_merge.argtypes = [i32, C.POINTER(np_text_index), vp, vp, vp, i64, vp, vp, i64,
                                           C.POINTER(np_text_merge_opts), C.POINTER(vp), C.POINTER(np_text_merge_report)]
+    L.np_hip_index_set_text_build.argtypes = [vp, vp]
+    L.np_hip_index_set_text_build_bytes.argtypes = [i64, i64, i64]
+    L.np_hip_index_set_text_build_bytes.restype = i64
+    L.np_hip_index_text_merge.argtypes = [vp, vp, vp, vp, i64, vp, vp, i64, C.POINTER(np_text_merge_opts), C.POINTER(vp),
+                                          C.POINTER(np_text_merge_report)]
+    L.np_hip_index_text_sizes.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.np_hip_index_get_text.argtypes = [vp, vp, vp, vp]
+    L.np_hip_index_get_text_layout.argtypes = [vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1179,6 +1189,57 @@ def text_merge(base_terms, base_term_offsets, base_inst_doc, base_inst_pos, base
             L.np_hip_text_build_free(d)
 
 
+def _text_build_vocab(L, h):
+    """np_hip_text_build_sizes and the vocabulary half of np_hip_text_build_fetch: (the terms as strings, n_rows, the
+    instance count).  No instance array crosses the bus; a consumed build still answers."""
+    nt, nb, ni, nr = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _check(L.np_hip_text_build_sizes(h, C.byref(nt), C.byref(nb), C.byref(ni), C.byref(nr)))
+    tb, tbo = np.zeros(max(nb.value, 1), np.uint8), np.zeros(nt.value + 1, np.int64)
+    _check(L.np_hip_text_build_fetch(h, _ptr(tb), _ptr(tbo), None, None, None))
+    raw = tb[: nb.value].tobytes()
+    return [raw[tbo[i]: tbo[i + 1]].decode("utf-8") for i in range(nt.value)], int(nr.value), int(ni.value)
+
+
+def text_merge_resident(index_handle, base_terms, remap, delta_ids, n_rows_out, doc_bytes=None, offsets=None, tokenizer: int = 0,
+                        tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0, workspace_bytes: int = 0,
+                        merge_workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+    """np_hip_index_text_merge, the one caller of the entry: text_merge whose base is the keyword index of the handle
+    `index_handle`, read where it lies.  base_terms are the handle's terms as byte strings, in term order.  Returns (the
+    result, a finalised device build that the caller installs with np_hip_index_set_text_build or frees; the merge's report
+    as a dict, the batch's under "batch"; the batch's fallback ids)."""
+    L = lib()
+    enc = [bytes(t) for t in base_terms]
+    nt = C.c_int64()
+    _check(L.np_hip_index_text_sizes(index_handle, C.byref(nt), None, None, None, None))
+    if len(enc) != nt.value:
+        raise ValueError(f"base_term_byte_offsets describes {len(enc)} terms, the handle's keyword index holds {nt.value}")
+    a_tbo = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        a_tbo[1:] = np.cumsum([len(t) for t in enc])
+    a_tb = np.frombuffer(b"".join(enc), np.uint8)
+    remap = np.ascontiguousarray(remap, np.int64).reshape(-1)
+    ids = np.ascontiguousarray(delta_ids, np.int64).reshape(-1)
+    n_delta = 0 if offsets is None else int(np.asarray(offsets).size) - 1
+    if ids.size != n_delta:
+        raise ValueError(f"delta_ids has {ids.size} entries for a batch of {n_delta} documents")
+    d, fb, brep = C.c_void_p(), np.zeros(0, np.int64), None
+    if offsets is not None:
+        d, fb, brep = _text_build_open(L, doc_bytes if doc_bytes is not None else np.zeros(0, np.uint8), offsets, tokenizer,
+                                       tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits, tile_bytes)
+    h = C.c_void_p()
+    try:
+        if d:
+            _check(L.np_hip_text_build_sizes(d, None, None, None, None))
+        o, rep = np_text_merge_opts(int(merge_workspace_bytes)), np_text_merge_report()
+        _check(L.np_hip_index_text_merge(index_handle, _ptr(a_tb) if a_tb.size else None, _ptr(a_tbo),
+                                         _ptr(remap) if remap.size else None, remap.size, d, _ptr(ids) if ids.size else None,
+                                         int(n_rows_out), C.byref(o), C.byref(h), C.byref(rep)))
+    finally:
+        if d:
+            L.np_hip_text_build_free(d)
+    return h, dict(rep.as_dict(), batch=brep.as_dict() if brep is not None else None), fb
+
+
 _POOL_CUTS = {"reference": 0, "distance": 1}
 
 
@@ -1542,10 +1603,18 @@ class MmapIndex:
         out = C.c_int64(0)
         if keep_attachments:
             n0, saved = self.num_documents(), self.text
-            _check(lib().np_hip_index_remove_keep(self._h, _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
+            removed = np.unique(ids[(ids >= 0) & (ids < n0)])
+            merged = None   # a resident keyword index: merged while the handle still has it, installed after the vector call
+            if getattr(saved, "resident", False) and removed.size:
+                merged = self._merge_text_resident(delete=removed, renumber=True)
+            try:
+                _check(lib().np_hip_index_remove_keep(self._h, _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
+            except BaseException:
+                if merged is not None:
+                    lib().np_hip_text_build_free(merged[0])   # refused: the handle keeps its old keyword index
+                raise
             _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
             if out.value:
-                removed = np.unique(ids[(ids >= 0) & (ids < n0)])
                 if self.schema is not None:
                     keep = np.ones(n0, bool)
                     keep[removed] = False
@@ -1553,8 +1622,13 @@ class MmapIndex:
                 if self.num_documents() == 0:
                     self.group_values = None   # no document, no groups: what set_groups makes of no keys
                 self.text = None
-                if saved is not None:
+                if merged is not None:
+                    saved.invalidate()
+                    self._install_text_build(merged[0], saved.tokenizer, merged[1], merged[2])
+                elif saved is not None:
                     self.update_text(delete=removed, renumber=True, base=saved)
+            elif merged is not None:
+                lib().np_hip_text_build_free(merged[0])
             return int(out.value)
         _check(lib().np_hip_index_remove(self._h, _ptr(ids) if ids.size else None, ids.size, C.byref(out)))
         if out.value:
@@ -1682,10 +1756,18 @@ class MmapIndex:
             cols[c.index] = np_column(c.type, 0, c.data.ctypes.data, None if c.valid is None else c.valid.ctypes.data)
             tables[c.index] = None if remaps[c.name] is None else remaps[c.name].ctypes.data
         first, saved = self.num_documents(), self.text
-        _check(lib().np_hip_index_append_rows(self._h, _ptr(dl) if dl.size else None, dl.size, _ptr(cd) if cd.size else None,
-                                              _ptr(rs) if rs.size else None, cols, n_cols,
-                                              C.cast(tables, C.c_void_p) if n_cols else None,
-                                              _ptr(gids) if gids is not None and gids.size else None, n_groups))
+        merged = None   # a resident keyword index: merged while the handle still has it, installed after the vector call
+        if getattr(saved, "resident", False) and dl.size:
+            merged = self._merge_text_resident(new_texts=list(rows.texts))
+        try:
+            _check(lib().np_hip_index_append_rows(self._h, _ptr(dl) if dl.size else None, dl.size, _ptr(cd) if cd.size else None,
+                                                  _ptr(rs) if rs.size else None, cols, n_cols,
+                                                  C.cast(tables, C.c_void_p) if n_cols else None,
+                                                  _ptr(gids) if gids is not None and gids.size else None, n_groups))
+        except BaseException:
+            if merged is not None:
+                lib().np_hip_text_build_free(merged[0])   # refused: the handle keeps its old keyword index
+            raise
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         if dl.size:
             self.schema, self.group_values, self.text = sch, values, None
@@ -1694,7 +1776,10 @@ class MmapIndex:
                     text, off = c.text_arrays()
                     _check(lib().np_hip_index_set_column_text(self._h, c.index, text.ctypes.data if text.size else None,
                                                               _ptr(off), len(c.dictionary)))
-            if saved is not None:
+            if merged is not None:
+                saved.invalidate()
+                self._install_text_build(merged[0], saved.tokenizer, merged[1], merged[2])
+            elif saved is not None:
                 self.update_text(new_texts=list(rows.texts), base=saved)
             _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         return np.arange(first, first + dl.size, dtype=np.int64)
@@ -1769,8 +1854,16 @@ class MmapIndex:
             cols[c.index] = np_column(c.type, 0, c.data.ctypes.data, None if c.valid is None else c.valid.ctypes.data)
             tables[c.index] = None if remaps[c.name] is None else remaps[c.name].ctypes.data
         saved = self.text
-        _check(lib().np_hip_index_expand_rows(*head, cols, n_cols, C.cast(tables, C.c_void_p) if n_cols else None,
-                                              _ptr(gids) if gids is not None and gids.size else None, n_groups))
+        merged = None   # a resident keyword index: merged while the handle still has it, installed after the vector call
+        if getattr(saved, "resident", False) and n_new:
+            merged = self._merge_text_resident(new_texts=list(rows.texts))
+        try:
+            _check(lib().np_hip_index_expand_rows(*head, cols, n_cols, C.cast(tables, C.c_void_p) if n_cols else None,
+                                                  _ptr(gids) if gids is not None and gids.size else None, n_groups))
+        except BaseException:
+            if merged is not None:
+                lib().np_hip_text_build_free(merged[0])   # refused: the handle keeps its old keyword index
+            raise
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         if n_new:
             self.schema, self.group_values, self.text = sch, values, None
@@ -1779,7 +1872,10 @@ class MmapIndex:
                     text, off = c.text_arrays()
                     _check(lib().np_hip_index_set_column_text(self._h, c.index, text.ctypes.data if text.size else None,
                                                               _ptr(off), len(c.dictionary)))
-            if saved is not None:
+            if merged is not None:
+                saved.invalidate()
+                self._install_text_build(merged[0], saved.tokenizer, merged[1], merged[2])
+            elif saved is not None:
                 self.update_text(new_texts=list(rows.texts), base=saved)
             _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
         return np.arange(first, first + dl.size, dtype=np.int64)
@@ -2091,24 +2187,146 @@ class MmapIndex:
             t = np_text_index(len(data.terms), off.ctypes.data, doc.ctypes.data if doc.size else None,
                               pos.ctypes.data if pos.size else None, int(data.n_rows))
             _check(fn(self._h, C.byref(t)))
+        old = getattr(self, "text", None)
+        if getattr(old, "resident", False) and old is not data:
+            old.invalidate()
         self.text = data
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
 
-    def build_text(self, texts, tokenizer: str = "unicode61", max_token_bytes: int | None = None):
+    def build_text(self, texts, tokenizer: str = "unicode61", max_token_bytes: int | None = None, resident: bool = False):
         """set_text from the documents' raw text, tokenised, numbered and sorted on this handle's device
-        (text.TextIndexData.from_texts_device); returns the TextIndexData, which set_text_shard takes unchanged."""
-        from . import text as T
-        data = T.TextIndexData.from_texts_device(texts, tokenizer, device=int(self._info.device),
-                                                 max_token_bytes=max_token_bytes)
-        self.set_text(data)
-        return data
+        (text.TextIndexData.from_texts_device); returns the TextIndexData, which set_text_shard takes unchanged.
 
-    def update_text(self, new_texts=(), delete=(), replace=None, renumber: bool = True, base=None):
+        resident=True keeps the build in HBM: np_hip_text_build (the fallback documents through SQLite, as ever),
+        np_hip_text_build_sizes and np_hip_index_set_text_build, which derives the postings by kernels and takes the
+        positions as they lie.  Only the vocabulary is fetched.  Returns (and leaves in self.text) a
+        text.ResidentTextIndexData: terms, vocab, n_rows and tokenizer as before, term_offsets / inst_doc / inst_pos
+        fetched from the handle on first access.  Searches on other threads go on; the caller needs no lock."""
+        from . import text as T
+        if not resident:
+            data = T.TextIndexData.from_texts_device(texts, tokenizer, device=int(self._info.device),
+                                                     max_token_bytes=max_token_bytes)
+            self.set_text(data)
+            return data
+        if tokenizer not in T.TOKENIZERS:
+            raise ValueError(f"unknown tokenizer {tokenizer!r}")
+        L = lib()
+        texts = list(texts)
+        raws = [T.prepare_document_text(t, tokenizer).encode("utf-8") for t in texts]
+        off = np.zeros(len(raws) + 1, np.int64)
+        if raws:
+            off[1:] = np.cumsum([len(r) for r in raws])
+        raw = np.frombuffer(b"".join(raws), np.uint8)
+
+        def tokenize_fallback(ids):
+            return T._tokenize_rows(T.TextIndexData, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer)
+
+        code = NP_TOK_TRIGRAM if T.TOKENIZERS[tokenizer] == "trigram" else NP_TOK_UNICODE61
+        h, fb, rep = _text_build_open(L, raw, off, code, tokenize_fallback, int(self._info.device), int(max_token_bytes or 0), 0, 0, 0)
+        return self._install_text_build(h, tokenizer, rep.as_dict(), fb)
+
+    def _install_text_build(self, h, tokenizer, report, fallback):
+        """np_hip_text_build_sizes, np_hip_index_set_text_build and the vocabulary of a build; frees it either way."""
+        from . import text as T
+        L = lib()
+        try:
+            _check(L.np_hip_text_build_sizes(h, None, None, None, None))
+            _check(L.np_hip_index_set_text_build(self._h, h))
+            terms, n_rows, n_inst = _text_build_vocab(L, h)
+        finally:
+            L.np_hip_text_build_free(h)
+        old = getattr(self, "text", None)
+        if getattr(old, "resident", False):
+            old.invalidate()
+        if n_inst == 0 and n_rows == 0:   # (no instances and no rows drop the keyword index, as set_text does)
+            self.text = None
+        else:
+            self.text = T.ResidentTextIndexData(tokenizer, terms, n_rows, self._text_fetcher(), report,
+                                                [int(i) for i in fallback])
+        _check(L.np_hip_index_info(self._h, C.byref(self._info)))
+        return self.text
+
+    def text_sizes(self) -> dict:
+        """np_hip_index_text_sizes: n_terms, n_postings, n_instances, n_rows and n_docs of the handle's keyword index."""
+        v = [C.c_int64() for _ in range(5)]
+        _check(lib().np_hip_index_text_sizes(self._h, *(C.byref(x) for x in v)))
+        return dict(zip(("n_terms", "n_postings", "n_instances", "n_rows", "n_docs"), (int(x.value) for x in v)))
+
+    def _fetch_text_arrays(self):
+        """np_hip_index_get_text: (term_offsets, inst_doc, inst_pos) regenerated from the handle's keyword index."""
+        z = self.text_sizes()
+        off = np.zeros(z["n_terms"] + 1, np.int64)
+        doc, pos = np.zeros(max(z["n_instances"], 1), np.int64), np.zeros(max(z["n_instances"], 1), np.int32)
+        _check(lib().np_hip_index_get_text(self._h, _ptr(off), _ptr(doc), _ptr(pos)))
+        return off, doc[: z["n_instances"]], pos[: z["n_instances"]]
+
+    def _text_fetcher(self):
+        """_fetch_text_arrays for a ResidentTextIndexData to keep: it holds the handle weakly, so that self.text and the
+        handle form no cycle and the handle closes when its last owner lets go."""
+        import weakref
+        ref = weakref.ref(self)
+
+        def fetch():
+            ix = ref()
+            if ix is None or not ix._h:
+                raise ValueError("the handle of this keyword index is closed: its arrays cannot be fetched any more")
+            return ix._fetch_text_arrays()
+        return fetch
+
+    def get_text(self):
+        """The handle's keyword index read back from HBM (np_hip_index_get_text) as a plain text.TextIndexData with the
+        handle's vocabulary (self.text's)."""
+        from . import text as T
+        if self.text is None:
+            raise ValueError("get_text: the handle has no keyword index")
+        z = self.text_sizes()
+        if z["n_terms"] != len(self.text.terms):
+            raise ValueError(f"get_text: the handle's keyword index holds {z['n_terms']} terms, self.text {len(self.text.terms)}")
+        off, doc, pos = self._fetch_text_arrays()
+        return T.TextIndexData(self.text.tokenizer, list(self.text.terms), off, doc, pos, z["n_rows"], dict(self.text.vocab))
+
+    def get_text_layout(self) -> dict:
+        """np_hip_index_get_text_layout: the keyword index as it lies in HBM -- post_off i64 [n_terms + 1], post_doc /
+        post_tf i32 and post_first i64 [n_postings], doc_len i32 [n_docs]."""
+        z = self.text_sizes()
+        P, N = z["n_postings"], z["n_docs"]
+        out = dict(post_off=np.zeros(z["n_terms"] + 1, np.int64), post_doc=np.zeros(max(P, 1), np.int32),
+                   post_tf=np.zeros(max(P, 1), np.int32), post_first=np.zeros(max(P, 1), np.int64),
+                   doc_len=np.zeros(max(N, 1), np.int32))
+        _check(lib().np_hip_index_get_text_layout(self._h, *(_ptr(out[k]) for k in ("post_off", "post_doc", "post_tf",
+                                                                                    "post_first", "doc_len"))))
+        for k in ("post_doc", "post_tf", "post_first"):
+            out[k] = out[k][:P]
+        out["doc_len"] = out["doc_len"][:N]
+        return out
+
+    def _merge_text_resident(self, new_texts=(), delete=(), replace=None, renumber: bool = True):
+        """The first half of a resident update: np_hip_index_text_merge of the handle's keyword index with the batch.
+        Returns (the result build, the report, the fallback ids); the handle is untouched.  The caller installs or frees."""
+        base = self.text
+        remap, delta_ids, n_rows_out, raw, off, code, tokenize_fallback = base._update_plan(new_texts, delete, replace, renumber, None)
+        return text_merge_resident(self._h, [t.encode("utf-8") for t in base.terms], remap, delta_ids, n_rows_out, raw, off, code,
+                                   tokenize_fallback, device=int(self._info.device))
+
+    def update_text(self, new_texts=(), delete=(), replace=None, renumber: bool = True, base=None, resident: bool = False):
         """The keyword index kept current (text.TextIndexData.updated, on this handle's device): `new_texts` appended,
         the rows `delete` removed, the rows of `replace` ({id: text}) given new text; renumber=True numbers the survivors
         densely, as the document ids are after delete() / update().  `base` defaults to self.text; update() and reload()
         drop it, so pass the TextIndexData kept from before them.  Calls set_text with the result and returns it
-        (set_text_shard takes it unchanged).  A refused call leaves the previous keyword index in place."""
+        (set_text_shard takes it unchanged).  A refused call leaves the previous keyword index in place.
+
+        resident=True updates the handle's keyword index from itself: the batch is built on the device,
+        np_hip_index_text_merge reads the base where it lies and np_hip_index_set_text_build installs the result; no
+        instance array crosses the bus.  The base IS the handle, so `base=` is refused.  Returns a
+        text.ResidentTextIndexData (see build_text); the arrays of the object it replaces are INVALIDATED unless they were
+        fetched before."""
+        if resident:
+            if base is not None:
+                raise ValueError("update_text: base= is refused with resident=True: the base is the handle's keyword index")
+            if self.text is None:
+                raise ValueError("update_text: the handle has no keyword index")
+            h, rep, fb = self._merge_text_resident(new_texts, delete, replace, renumber)
+            return self._install_text_build(h, self.text.tokenizer, rep, fb)
         base = self.text if base is None else base
         if base is None:
             raise ValueError("update_text: the handle has no keyword index and no base was given")

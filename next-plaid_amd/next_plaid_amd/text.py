@@ -148,6 +148,8 @@ class TextIndexData:
     _scratch: object = field(default=None, repr=False, compare=False)
     _cache: dict = field(default_factory=dict, repr=False, compare=False)
 
+    resident = False                  # ResidentTextIndexData: the arrays lie in a handle's HBM
+
     @property
     def tokenize(self) -> str:
         return TOKENIZERS[self.tokenizer]
@@ -261,13 +263,26 @@ class TextIndexData:
         and `replace` must be a row, and renumber=True is refused).  build_report is the merge's report (under "batch": the
         report of the batch's build, None without a batch), fallback_docs index the batch.  `knobs`: from_texts_device's, and merge_workspace_bytes."""
         from . import api
+        remap, delta_ids, n_rows_out, raw, off, code, tokenize_fallback = self._update_plan(new_texts, delete, replace, renumber, n_rows)
+        tokenizer, cls = self.tokenizer, type(self)
+        r = api.text_merge([t.encode("utf-8") for t in self.terms], self.term_offsets, self.inst_doc, self.inst_pos, int(self.n_rows),
+                           remap, delta_ids, n_rows_out, raw, off, code, tokenize_fallback,
+                           device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
+        data = cls._of_build(tokenizer, r)
+        data.build_report = dict(r["report"], batch=r["build_report"])     # the merge's report; the batch's build inside it
+        return data
+
+    def _update_plan(self, new_texts, delete, replace, renumber, n_rows):
+        """updated()'s arguments checked and turned into what the merge entries take: (remap, delta_ids, n_rows_out, the
+        batch's bytes and offsets or None, the tokenizer code, tokenize_fallback).  A resident index's arrays are not read."""
+        from . import api
         tokenizer = self.tokenizer
         n_old = int(self.n_rows) if n_rows is None else int(n_rows)
         if n_old < int(self.n_rows):
             raise ValueError(f"updated: n_rows {n_old} is below the table's {int(self.n_rows)} rows")
         if n_rows is not None and renumber and n_old != int(self.n_rows):
             raise ValueError("updated: renumber=True needs a dense table (rows 0 .. n_rows - 1); pass renumber=False")
-        if self.inst_doc.size and int(self.inst_doc.max()) >= n_old:
+        if not self.resident and self.inst_doc.size and int(self.inst_doc.max()) >= n_old:
             raise ValueError(f"updated: the index names document {int(self.inst_doc.max())} but the table has {n_old} row ids; "
                              f"a table with holes needs n_rows")
         gone = sorted(set(int(d) for d in delete))
@@ -300,18 +315,13 @@ class TextIndexData:
         if raws:
             off[1:] = np.cumsum([len(r) for r in raws])
         raw = np.frombuffer(b"".join(raws), np.uint8)
-        cls = type(self)
+        cls = TextIndexData if self.resident else type(self)
 
         def tokenize_fallback(ids):
             return _tokenize_rows(cls, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer)
 
         code = api.NP_TOK_TRIGRAM if TOKENIZERS[tokenizer] == "trigram" else api.NP_TOK_UNICODE61
-        r = api.text_merge([t.encode("utf-8") for t in self.terms], self.term_offsets, self.inst_doc, self.inst_pos, int(self.n_rows),
-                           remap, delta_ids, n_rows_out, raw if texts else None, off if texts else None, code, tokenize_fallback,
-                           device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
-        data = cls._of_build(tokenizer, r)
-        data.build_report = dict(r["report"], batch=r["build_report"])     # the merge's report; the batch's build inside it
-        return data
+        return remap, delta_ids, n_rows_out, raw if texts else None, off if texts else None, code, tokenize_fallback
 
     # -- tokenising query text with the index's tokenizer -------------------------------------------------
     def tokens_of(self, phrase: str) -> list[str]:
@@ -333,6 +343,47 @@ class TextIndexData:
 
     def term_ids(self, phrase: str) -> list[int]:
         return [self.vocab.get(t, -1) for t in self.tokens_of(phrase)]
+
+
+class ResidentTextIndexData(TextIndexData):
+    """The keyword index of a handle that was built or updated in HBM (MmapIndex.build_text / update_text with
+    resident=True): terms, vocab, n_rows and tokenizer as on any TextIndexData, so that compile_text_query,
+    compile_text_expr, prefix_range and set_text_shard work on it; term_offsets, inst_doc and inst_pos are fetched from the
+    handle on first access (np_hip_index_get_text) and then kept.  A later resident update of the handle gives it a new
+    object and INVALIDATES the arrays of the one it replaces unless they were fetched before: reading them then raises."""
+    resident = True
+
+    def __init__(self, tokenizer, terms, n_rows, fetch, build_report=None, fallback_docs=None):
+        self.tokenizer, self.terms, self.n_rows = tokenizer, terms, int(n_rows)
+        self.vocab = {t: i for i, t in enumerate(terms)}
+        self.build_report, self.fallback_docs = build_report, fallback_docs
+        self._scratch, self._cache = None, {}
+        self._fetch, self._arrays = fetch, None
+
+    def _get(self, i):
+        if self._arrays is None:
+            if self._fetch is None:
+                raise ValueError("this keyword index was replaced by a later resident update before its arrays were fetched: "
+                                 "read MmapIndex.text (or get_text()) instead")
+            self._arrays = self._fetch()
+            self._fetch = None
+        return self._arrays[i]
+
+    def invalidate(self):
+        """The handle holds another keyword index now: arrays that were not fetched cannot be any more."""
+        self._fetch = None
+
+    term_offsets = property(lambda self: self._get(0))
+    inst_doc = property(lambda self: self._get(1))
+    inst_pos = property(lambda self: self._get(2))
+
+    def __repr__(self):
+        return f"ResidentTextIndexData(tokenizer={self.tokenizer!r}, n_terms={len(self.terms)}, n_rows={self.n_rows})"
+
+    def __eq__(self, other):
+        return self is other
+
+    __hash__ = object.__hash__
 
 
 def _tokenize_rows(cls, texts, ids, tokenizer: str):
