@@ -763,7 +763,8 @@ int np_hip_text_build_sizes(np_text_build* build, int64_t* n_terms, int64_t* ter
   }
   if (n_terms) *n_terms = build->merged ? build->out.n_terms() : build->n_terms;
   if (term_bytes) *term_bytes = (int64_t)(build->merged ? build->out.term_bytes.size() : build->term_bytes.size());
-  if (n_instances) *n_instances = build->merged ? (int64_t)build->out.inst_doc.size() : build->n_inst;
+  // (a consumed build gave its instance arrays away: the install left their count in n_inst)
+  if (n_instances) *n_instances = build->merged && !build->consumed ? (int64_t)build->out.inst_doc.size() : build->n_inst;
   if (n_rows) *n_rows = build->n_docs;
   return NP_OK;
 }

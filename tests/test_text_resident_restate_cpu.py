@@ -46,7 +46,7 @@ def test_the_layout_is_the_host_loops_and_the_round_trip_is_the_identity(name):
     assert X.first_offender(toff, doc, pos, n_docs) is None
 
 
-@pytest.mark.parametrize("defect", X.DEFECTS)
+@pytest.mark.parametrize("defect", X.LAYOUT_DEFECTS)   # (the check's and the counts': tests/test_textres_limits_cpu.py)
 def test_every_planted_defect_shows_on_a_listed_shape(defect):
     hit = []
     for name, (toff, doc, pos, n_docs) in SHAPES.items():

@@ -1,14 +1,25 @@
 """The resident keyword index (np_textres.hip) restated in numpy: heads, postings and doc_len of an instance table as
 np_hip_index_set_text_build derives them, the device check's first offender, and the way back from the postings to the
 instances as np_hip_index_text_merge and np_hip_index_get_text take it.  `defect` plants one of DEFECTS; the shape generators
-are the ones the device tests install."""
+are the ones the device tests install.
+
+For tests/test_textres_limits_cpu.py and tests/test_gpu_textres_limits.py also: the check's reduction as tr_check_heads and the
+host form it (block_offenders: CHUNK instances per block, eight per thread, a thread's first offender, the block's lowest;
+reduced_offender: the minimum over the blocks, named as name_offender names it from two fetched instances), and the two counts
+over the handle's documents that np_hip_index_text_merge takes (count_docs, beyond, distinct_result)."""
 import numpy as np
 
 CHUNK = 2048           # NP_TB_SCAN_CHUNK: instances per block of the check / heads launch and of a scan launch
 SCAN_ROUND = 256       # block sums that tb_scan_sums takes per round
 
-DEFECTS = ("head_on_document_change_only", "tf_off_by_one_at_term_end", "post_off_of_empty_term", "doc_len_per_posting",
-           "bisection_off_by_one")
+LAYOUT_DEFECTS = ("head_on_document_change_only", "tf_off_by_one_at_term_end", "post_off_of_empty_term", "doc_len_per_posting",
+                  "bisection_off_by_one")                      # of layout() and instances()
+CHECK_DEFECTS = ("min_over_the_first_block_only", "thread_keeps_its_last_offender", "block_start_has_no_predecessor")
+COUNT_DEFECTS = ("count_ignores_remap", "count_ignores_doc_len", "beyond_counts_from_zero", "beyond_skips_its_first_document",
+                 "batch_documents_counted_per_instance", "batch_empty_rows_counted")
+DEFECTS = LAYOUT_DEFECTS + CHECK_DEFECTS + COUNT_DEFECTS
+THREAD = 8            # instances per thread of the check / heads launch
+NO_OFFENDER = np.iinfo(np.int64).max
 
 
 def layout(term_offsets, inst_doc, n_docs, defect=None):
@@ -55,24 +66,112 @@ def instances(post_off, post_doc, post_first, n_inst, defect=None):
     return toff, inst_doc.astype(np.int64)
 
 
-def first_offender(term_offsets, inst_doc, inst_pos, n_docs):
-    """(instance, rule) of the lowest instance that fails np_hip_index_set_text's checks, or None.  Rules: 1 = document
-    outside [0, n_docs), 2 = negative position, 3 = not after its predecessor in (document, position) order."""
+def _rules(term_offsets, inst_doc, inst_pos, n_docs, block_starts_are_first=False):
+    """Per instance the rule it fails (0 = none), and whether it is the first of its term."""
     toff = np.asarray(term_offsets, np.int64)
     doc, pos = np.asarray(inst_doc, np.int64), np.asarray(inst_pos, np.int64)
     n = doc.size
-    if n == 0:
-        return None
     first = np.zeros(n, bool)
+    if n == 0:
+        return np.zeros(0, np.int64), first
     first[toff[:-1][toff[:-1] < toff[1:]]] = True
     first[0] = True
+    if block_starts_are_first:
+        first[::CHUNK] = True
     pd, pp = np.concatenate([[0], doc[:-1]]), np.concatenate([[0], pos[:-1]])
     r1 = (doc < 0) | (doc >= n_docs)
     r2 = pos < 0
     r3 = ~first & ((pd > doc) | ((pd == doc) & (pp >= pos)))
-    rule = np.where(r1, 1, np.where(r2, 2, np.where(r3, 3, 0)))
+    return np.where(r1, 1, np.where(r2, 2, np.where(r3, 3, 0))).astype(np.int64), first
+
+
+def first_offender(term_offsets, inst_doc, inst_pos, n_docs):
+    """(instance, rule) of the lowest instance that fails np_hip_index_set_text's checks, or None.  Rules: 1 = document
+    outside [0, n_docs), 2 = negative position, 3 = not after its predecessor in (document, position) order."""
+    rule, _ = _rules(term_offsets, inst_doc, inst_pos, n_docs)
     bad = np.nonzero(rule)[0]
     return None if bad.size == 0 else (int(bad[0]), int(rule[bad[0]]))
+
+
+def blocks(n, per=CHUNK):
+    return -(-int(n) // per)
+
+
+def block_offenders(term_offsets, inst_doc, inst_pos, n_docs, defect=None):
+    """bad[block] as tr_check_heads leaves it: every thread keeps the first offender of its THREAD instances, the block takes
+    the lowest of its threads; NO_OFFENDER where a block is clean.  int64 [blocks(n_inst)]."""
+    rule, _ = _rules(term_offsets, inst_doc, inst_pos, n_docs, defect == "block_start_has_no_predecessor")
+    n = rule.size
+    nb = blocks(n)
+    padded = np.zeros(nb * CHUNK, np.int64)
+    padded[:n] = rule
+    bad = padded.reshape(nb, CHUNK // THREAD, THREAD) != 0
+    at = np.arange(nb * CHUNK, dtype=np.int64).reshape(bad.shape)
+    if defect == "thread_keeps_its_last_offender":
+        per_thread = np.where(bad, at, -1).max(axis=2)
+        per_thread = np.where(per_thread < 0, NO_OFFENDER, per_thread)
+    else:
+        per_thread = np.where(bad, at, NO_OFFENDER).min(axis=2)
+    return per_thread.min(axis=1).astype(np.int64) if nb else np.zeros(0, np.int64)
+
+
+def reduced_offender(term_offsets, inst_doc, inst_pos, n_docs, defect=None):
+    """(instance, rule) as install_impl and name_offender give it: the minimum of block_offenders, its term from the term
+    starts, its rule recomputed from the instance and -- unless it starts its term -- its predecessor.  None = accepted."""
+    per_block = block_offenders(term_offsets, inst_doc, inst_pos, n_docs, defect)
+    if defect == "min_over_the_first_block_only":
+        per_block = per_block[:1]
+    low = int(per_block.min()) if per_block.size else NO_OFFENDER
+    if low == NO_OFFENDER:
+        return None
+    toff = np.asarray(term_offsets, np.int64)
+    doc, pos = np.asarray(inst_doc, np.int64), np.asarray(inst_pos, np.int64)
+    term = int(np.searchsorted(toff, low, side="right")) - 1
+    first = (term >= 0 and int(toff[term]) == low) or low == 0
+    d, p = int(doc[low]), int(pos[low])
+    pd, pp = (0, 0) if first else (int(doc[low - 1]), int(pos[low - 1]))
+    if d < 0 or d >= n_docs:
+        return low, 1
+    if p < 0:
+        return low, 2
+    return (low, 3) if not first and (pd > d or (pd == d and pp >= p)) else (low, 0)
+
+
+# ---- the counts over the handle's documents (np_hip_index_text_merge) ----------------------------------------------------------
+def count_docs(doc_len, remap=None, defect=None):
+    """The number of d with doc_len[d] > 0 and, where remap is given, remap[d] >= 0 (tr_doc_flags and the scan's total)."""
+    doc_len = np.asarray(doc_len, np.int64)
+    flag = np.ones(doc_len.size, bool) if defect == "count_ignores_doc_len" else doc_len > 0
+    if remap is not None and defect != "count_ignores_remap":
+        flag = flag & (np.asarray(remap, np.int64)[: doc_len.size] >= 0)
+    return int(np.count_nonzero(flag))
+
+
+def beyond(doc_len, n_remap, defect=None):
+    """The documents of the handle at or behind n_remap that hold a token: the merge refuses any."""
+    doc_len = np.asarray(doc_len, np.int64)
+    told = min(int(n_remap), doc_len.size)
+    if defect == "beyond_counts_from_zero":
+        told = 0
+    if defect == "beyond_skips_its_first_document":
+        told += 1
+    return count_docs(doc_len[told:])
+
+
+def distinct_result(doc_len, remap, n_remap, delta_inst_doc, n_delta_docs=None, defect=None):
+    """The documents of the merge's result that hold a token: the survivors among the handle's first n_remap documents that
+    hold one, plus the distinct documents of the batch that do (a batch row without a token is no instance's document)."""
+    doc_len = np.asarray(doc_len, np.int64)
+    told = min(int(n_remap), doc_len.size)
+    survivors = count_docs(doc_len[:told], np.asarray(remap, np.int64)[:told], defect)
+    b = np.asarray(delta_inst_doc, np.int64).reshape(-1)
+    if defect == "batch_documents_counted_per_instance":
+        batch = int(b.size)
+    elif defect == "batch_empty_rows_counted":
+        batch = int(n_delta_docs)
+    else:
+        batch = int(np.unique(b).size)
+    return survivors + batch
 
 
 # ---- shapes: (term_offsets, inst_doc, inst_pos, n_docs), every one a well-formed table ----------------------------------------
