@@ -723,6 +723,65 @@ static void install_ucodes(DeviceIndex* ix, Ucodes&& u) {
   ix->sliced_ok = u.sliced_ok;
 }
 
+// ---- what np_hip_index_append, _remove and _expand share: one exclusive section, one staged list state, one commit ----
+// every context held and the handle's device current; begin() also waits for the device-side calls that returned but may
+// still be running on their streams
+struct UpdateSection {
+  HoldContexts hold;
+  DeviceGuard g;
+  int device;
+  explicit UpdateSection(DeviceIndex* ix) : hold(ix), g(ix->device), device(ix->device) {}
+  int begin() {
+    if (!g.ok) {
+      set_error("hipSetDevice(%d) failed", device);
+      return NP_ERR_DEVICE_UNAVAILABLE;
+    }
+    NP_HIP(hipDeviceSynchronize());
+    return NP_OK;
+  }
+};
+
+// The posting lists of the updated index and their range table, staged beside the ones that serve.  replaced == false: the
+// handle's own lists stay (an append whose documents hold no token), and only the table and the coverage are new.
+struct StagedLists {
+  DevPtr<uint32_t> ivf;
+  DevPtr<int64_t> ioff;
+  std::vector<int64_t> h_ioff;
+  int64_t ivf_size = 0;
+  bool replaced = false;
+  DevPtr<uint32_t> split;
+  int R = 0, cover = 0;
+};
+
+// the range table of the staged lists over the N1 documents of u.  Lists that held every (document, code) pair still do: an
+// update takes a document's entries away all at once, and the pairs it adds are all of the given documents'
+static int stage_ivf_split(const DeviceIndex* ix, const Ucodes& u, int64_t N1, StagedLists* st) {
+  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide},
+                    st->replaced ? st->ivf.get() : ix->d_ivf.get(), st->replaced ? st->ioff.get() : ix->d_ivf_offsets.get()};
+  st->cover = N1 > 0 ? ix->ivf_cover : -1;
+  return make_ivf_split(ix, v, ix->ivf_cover == 1, &st->split, &st->R, &st->cover);
+}
+
+static void install_lists(DeviceIndex* ix, StagedLists&& st) {
+  if (st.replaced) {
+    ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + st.ivf.bytes() + st.ioff.bytes();
+    ix->d_ivf = std::move(st.ivf);
+    ix->d_ivf_offsets = std::move(st.ioff);
+    ix->ivf_size = st.ivf_size;
+    set_ivf_bound(ix, st.h_ioff.data());
+  }
+  install_ivf_split(ix, std::move(st.split), st.R);
+  ix->ivf_cover = st.cover;
+}
+
+// the last step of an update, every context still held
+static void finish_update(DeviceIndex* ix) {
+  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
+  ix->gain_run.store(0, std::memory_order_relaxed);
+  ix->gain_skip.store(0, std::memory_order_relaxed);
+  contexts_forget_index(ix);
+}
+
 // block stride of the lists (ublock_stride / ublock_hdr) from a histogram of their lengths, and ulen_mean
 static int choose_ublock_stride(const DeviceIndex* ix, int64_t N, Ucodes* u) {
   // the smallest multiple of 16 bytes that holds the header and 99.9 % of the lists (at most the staging row)
@@ -1406,6 +1465,67 @@ __global__ void ulen_to_i64_kernel(const int32_t* __restrict__ ulen, int64_t n, 
   if (i < n) out[i] = ulen[i];
 }
 
+// a pair of device events around a kernel, when a trace asks for the kernel's own time
+struct KernelClock {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool on = false;
+  explicit KernelClock(bool want) { on = want && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess; }
+  ~KernelClock() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void start() {
+    if (on) (void)hipEventRecord(ev[0], nullptr);
+  }
+  double stop() {   // seconds
+    float ms = 0.f;
+    if (!on) return 0.0;
+    (void)hipEventRecord(ev[1], nullptr);
+    if (hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return 0.0;
+    return ms * 1e-3;
+  }
+};
+
+template <class T>
+static int device_scan_inclusive(const T* in, T* out, int64_t n) {
+  DevPtr<uint8_t> d_temp;
+  size_t tb = 0;
+  NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, in, out, (int)n));
+  return NP_OK;
+}
+template <class T>
+static int device_scan_exclusive(const T* in, T* out, int64_t n) {
+  DevPtr<uint8_t> d_temp;
+  size_t tb = 0;
+  NP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), tb, in, out, (int)n));
+  return NP_OK;
+}
+// n (code << 32 | document) keys by their low 32 + code_bits bits
+static int device_sort_pairs(const uint64_t* in, uint64_t* out, int64_t n, int code_bits) {
+  DevPtr<uint8_t> d_temp;
+  size_t tb = 0;
+  NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, in, out, (int)n, 0, 32 + code_bits));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tb, in, out, (int)n, 0, 32 + code_bits));
+  return NP_OK;
+}
+// sorted keys, each once: *n_out of them in out
+static int device_unique(const uint64_t* in, uint64_t* out, int64_t n, int64_t* n_out) {
+  DevPtr<uint8_t> d_temp;
+  DevPtr<int64_t> d_n;
+  size_t tb = 0;
+  NP_TRY(d_n.alloc(1));
+  NP_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, in, out, d_n.get(), (int)n));
+  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
+  NP_HIP(hipcub::DeviceSelect::Unique(d_temp.get(), tb, in, out, d_n.get(), (int)n));
+  NP_HIP(hipMemcpy(n_out, d_n.get(), 8, hipMemcpyDeviceToHost));
+  return NP_OK;
+}
+
 static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
   const int64_t K = ix->K, N = ix->n_docs;
   std::vector<int64_t> ioff((size_t)K + 1, 0);
@@ -1418,12 +1538,8 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
     NP_TRY(d_upfx.alloc((size_t)N));
     NP_TRY(d_start.alloc((size_t)N));   // scan input (released below; d_start is re-allocated per code later)
     ulen_to_i64_kernel<<<(unsigned)((N + 255) / 256), 256>>>(ix->d_ulen.get(), N, d_start.get());
-    size_t tb = 0;
-    NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_start.get(), d_upfx.get(), (int)N));
-    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-    NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, d_start.get(), d_upfx.get(), (int)N));
+    NP_TRY(device_scan_inclusive(d_start.get(), d_upfx.get(), N));
     NP_HIP(hipMemcpy(upfx.data(), d_upfx.get(), (size_t)N * 8, hipMemcpyDeviceToHost));
-    d_temp.reset();
     d_start.reset();
   }
   const int64_t total = N > 0 ? upfx[(size_t)N - 1] : 0;
@@ -1507,17 +1623,20 @@ static int build_ivf_from_ucodes(DeviceIndex* ix, const int64_t* d_uoff) {
   return NP_OK;
 }
 
-// ---- append to a resident index (np_hip_index_append) -----------------------------------------------------------------
+// ---- append to and expand a resident index: the posting-list rewrite ----------------------------------------------------
 // New documents take the largest ids, so every per-token and per-document array only grows at its end and, the lists
 // ascending, posting list c only gains entries at its end.  The one array that is laid out again is d_ivf: K lists, each
-// growing at its tail.  With the new documents' (code, id) pairs sorted, start[c] = the pairs with a smaller code is at once
-// the exclusive scan of the per-list gains, so
-//   new_off[c] = old_off[c] + start[c];   old entry i of list c -> i + start[c];   pair j of code c -> old_off[c + 1] + j
+// keeping a front part of what it held -- old_ivf[old_begin[c] .. + kept_pfx[c + 1] - kept_pfx[c]) -- and growing at its tail.
+// With the given documents' (code, id) pairs sorted, start[c] = the pairs with a smaller code is at once the exclusive scan of
+// the per-list gains, as kept_pfx is that of the kept lengths, so
+//   new_off[c] = kept_pfx[c] + start[c];   kept entry i of list c -> new_off[c] + i;   pair j of code c -> new_off[c] + kept[c] + j
 // and every entry of the new array has one source that scans alone decide: no atomics, no workgroup waits for another.
-__global__ void ivf_new_offsets_kernel(const int64_t* __restrict__ old_off, const int64_t* __restrict__ start, int64_t K,
+// An append (np_hip_index_append) keeps every list whole: the old offsets are old_begin and kept_pfx at once.  An expand
+// (np_hip_index_expand, below) cuts every list at the first dropped document and may add lists: ivf_keep_kernel and a scan.
+__global__ void ivf_cut_offsets_kernel(const int64_t* __restrict__ kept_pfx, const int64_t* __restrict__ start, int64_t K,
                                        int64_t* __restrict__ new_off) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c <= K) new_off[c] = old_off[c] + start[c];
+  if (c <= K) new_off[c] = kept_pfx[c] + start[c];
 }
 
 // the list that holds entry o of the new array: the largest c' >= c with off[c'] <= o.  Needs off[c] <= o < off[K]; gallops from
@@ -1537,22 +1656,22 @@ __device__ __forceinline__ int64_t ivf_list_of(const int64_t* __restrict__ off, 
   return lo;
 }
 
-// The merge is a streaming move (4 bytes read and 4 written per entry; the offsets stay in the caches), balanced by ENTRIES:
+// The rewrite is a streaming move (4 bytes read and 4 written per entry; the offsets stay in the caches), balanced by ENTRIES:
 // a workgroup owns NP_MERGE_TILE consecutive entries of the NEW array whatever lists they belong to (list lengths are
 // Zipf-skewed: one thread per list would leave the longest to a single lane).  A thread owns 4 consecutive entries -- one
 // aligned 16-byte store -- and the threads of a wave consecutive quads, so inside a list segment a wave reads 1 KiB of the
 // old array (or 2 KiB of pairs) and writes 1 KiB, all contiguous.  A quad that lies inside the old part of one list -- nearly
-// all of them on long lists -- is one 16-byte load (4-byte aligned: the shift start[c] is any number of entries).  A thread
+// all of them on long lists -- is one 16-byte load (4-byte aligned: the shift between old and new position is any number of entries).  A thread
 // finds and loads its NP_MERGE_QUADS quads first and stores them afterwards, so that many loads are in flight per lane.
 #define NP_MERGE_TILE 4096
 #define NP_MERGE_QUADS (NP_MERGE_TILE / 1024)
 struct __attribute__((packed, aligned(4))) MergeQuad {
   uint32_t v[4];
 };
-__global__ void __launch_bounds__(256) ivf_merge_kernel(const uint32_t* __restrict__ old_ivf, const int64_t* __restrict__ old_off,
-                                                        const uint64_t* __restrict__ pairs, const int64_t* __restrict__ start,
-                                                        const int64_t* __restrict__ new_off, int64_t K, int64_t total,
-                                                        uint32_t* __restrict__ out) {
+__global__ void __launch_bounds__(256) ivf_cut_merge_kernel(const uint32_t* __restrict__ old_ivf, const int64_t* __restrict__ old_begin,
+                                                            const int64_t* __restrict__ kept_pfx, const uint64_t* __restrict__ pairs,
+                                                            const int64_t* __restrict__ start, const int64_t* __restrict__ new_off,
+                                                            int64_t K, int64_t total, uint32_t* __restrict__ out) {
   __shared__ int64_t s_c0;
   const int64_t o0 = (int64_t)blockIdx.x * NP_MERGE_TILE;   // < total: the grid covers [0, total)
   if (threadIdx.x == 0) s_c0 = ivf_list_of(new_off, K, 0, o0);
@@ -1566,7 +1685,7 @@ __global__ void __launch_bounds__(256) ivf_merge_kernel(const uint32_t* __restri
     if (o < total) {
       const int n = (int)min((int64_t)4, total - o);
       c = ivf_list_of(new_off, K, c, o);
-      int64_t b_new = new_off[c], e_new = new_off[c + 1], b_old = old_off[c], n_old = old_off[c + 1] - b_old, b_pair = start[c];
+      int64_t b_new = new_off[c], e_new = new_off[c + 1], b_old = old_begin[c], n_old = kept_pfx[c + 1] - kept_pfx[c], b_pair = start[c];
       if (n == 4 && o + 4 <= b_new + n_old) {   // (b_new + n_old <= e_new)
         q[it] = *reinterpret_cast<const MergeQuad*>(old_ivf + b_old + (o - b_new));
       } else {
@@ -1576,7 +1695,7 @@ __global__ void __launch_bounds__(256) ivf_merge_kernel(const uint32_t* __restri
             const int64_t oo = o + k;
             if (oo >= e_new) {
               c = ivf_list_of(new_off, K, c, oo);
-              b_new = new_off[c], e_new = new_off[c + 1], b_old = old_off[c], n_old = old_off[c + 1] - b_old, b_pair = start[c];
+              b_new = new_off[c], e_new = new_off[c + 1], b_old = old_begin[c], n_old = kept_pfx[c + 1] - kept_pfx[c], b_pair = start[c];
             }
             const int64_t r = oo - b_new;
             q[it].v[k] = r < n_old ? old_ivf[b_old + r] : (uint32_t)(pairs[b_pair + (r - n_old)] & 0xFFFFFFFFull);
@@ -1596,84 +1715,6 @@ __global__ void __launch_bounds__(256) ivf_merge_kernel(const uint32_t* __restri
         if (o + k < total) out[o + k] = q[it].v[k];
     }
   }
-}
-
-// The posting lists of the handle with documents [N0, N1) added, from the distinct-code lists of the grown index (u, d_uoff):
-// *ivf / *ioff stay empty when the new documents hold no token (the lists are the handle's own then); h_ioff = the offsets.
-// raw_lists: a new document is longer than NP_UNIQ_MAX tokens, so its list is its codes as they are, duplicates included --
-// a posting list names a document once (index.rs:479-499), so equal pairs, adjacent once sorted, are dropped.
-static int merge_posting_lists(const DeviceIndex* ix, const Ucodes& u, const int64_t* d_uoff, int64_t N0, int64_t N1, bool raw_lists,
-                               DevPtr<uint32_t>* ivf, DevPtr<int64_t>* ioff, std::vector<int64_t>* h_ioff, int64_t* ivf_size,
-                               const OpenTrace& trace) {
-  const int64_t K = ix->K;
-  *ivf_size = ix->ivf_size;
-  DevPtr<int64_t> d_len64, d_upfx, d_start;
-  DevPtr<uint64_t> d_k1, d_k2;
-  DevPtr<uint8_t> d_temp;
-  // inclusive prefix of the NEW documents' list lengths: where each one's pairs go (nothing here is index-sized)
-  const int64_t n_new = N1 - N0;
-  NP_TRY(d_len64.alloc((size_t)n_new));
-  NP_TRY(d_upfx.alloc((size_t)n_new));
-  ulen_to_i64_kernel<<<(unsigned)((n_new + 255) / 256), 256>>>(u.d_ulen.get() + N0, n_new, d_len64.get());
-  size_t tb = 0;
-  NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, d_len64.get(), d_upfx.get(), (int)n_new));
-  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-  NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, d_len64.get(), d_upfx.get(), (int)n_new));
-  int64_t P = 0;   // (code, document) pairs of the new documents
-  NP_HIP(hipMemcpy(&P, d_upfx.get() + (n_new - 1), 8, hipMemcpyDeviceToHost));
-  d_len64.reset();
-  d_temp.reset();
-  if (P == 0) return NP_OK;
-  if (P >= ((int64_t)1 << 31)) {   // one radix sort, as one document range of build_ivf_from_ucodes
-    set_error("np_hip_index_append: n_docs: the new documents hold %lld (code, doc) pairs, one call takes < 2^31", (long long)P);
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  int kbits = 1;
-  while (((int64_t)1 << kbits) < K) ++kbits;
-  NP_TRY(d_k1.alloc((size_t)P));
-  NP_TRY(d_k2.alloc((size_t)P));
-  NP_TRY(d_start.alloc((size_t)K + 1));
-  ivf_emit_pairs_kernel<<<(unsigned)((N1 - N0 + 3) / 4), 256>>>(N0, N1, d_uoff, CodeArr{u.d_ucodes.get(), ix->code_wide},
-                                                               u.d_ulen.get(), d_upfx.get(), N0, 0, d_k1.get());
-  NP_HIP(hipGetLastError());
-  tb = 0;
-  NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
-  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-  NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
-  if (raw_lists) {
-    DevPtr<int64_t> d_n;
-    NP_TRY(d_n.alloc(1));
-    tb = 0;
-    NP_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
-    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-    NP_HIP(hipcub::DeviceSelect::Unique(d_temp.get(), tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
-    NP_HIP(hipMemcpy(&P, d_n.get(), 8, hipMemcpyDeviceToHost));
-    std::swap(d_k1, d_k2);   // d_k2 = the sorted pairs, each once
-  }
-  ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2.get(), P, K, d_start.get());
-  NP_HIP(hipGetLastError());
-  const int64_t total = ix->ivf_size + P;
-  NP_TRY(ioff->alloc((size_t)K + 1));
-  NP_TRY(ivf->alloc((size_t)total));   // the new array beside the old one: the merge reads the one and writes the other
-  ivf_new_offsets_kernel<<<(unsigned)((K + 256) / 256), 256>>>(ix->d_ivf_offsets.get(), d_start.get(), K, ioff->get());
-  hipEvent_t ev[2] = {nullptr, nullptr};   // NP_APPEND_TRACE: the merge kernel alone, for its bytes per second
-  if (trace.on && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) (void)hipEventRecord(ev[0], nullptr);
-  ivf_merge_kernel<<<(unsigned)((total + NP_MERGE_TILE - 1) / NP_MERGE_TILE), 256>>>(
-      ix->d_ivf.get(), ix->d_ivf_offsets.get(), d_k2.get(), d_start.get(), ioff->get(), K, total, ivf->get());
-  NP_HIP(hipGetLastError());
-  if (ev[0] && ev[1]) {
-    float ms = 0.f;
-    (void)hipEventRecord(ev[1], nullptr);
-    if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-      fprintf(stderr, "[%s] %-28s %8.6f s  %lld entries %lld new\n", trace.tag, "merge kernel", ms * 1e-3, (long long)total, (long long)P);
-  }
-  for (hipEvent_t e : ev)
-    if (e) (void)hipEventDestroy(e);
-  h_ioff->resize((size_t)K + 1);
-  NP_HIP(hipMemcpy(h_ioff->data(), ioff->get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
-  NP_HIP(hipDeviceSynchronize());
-  *ivf_size = total;
-  return NP_OK;
 }
 
 template <class T>
@@ -1783,107 +1824,6 @@ struct StagedRows {
 };
 static int stage_appended_rows(const DeviceIndex* ix, const AppendRows& rows, int64_t N0, int64_t N1, StagedRows* st);
 static int install_appended_rows(DeviceIndex* ix, const AppendRows& rows, StagedRows&& st, int64_t N0, int64_t N1);
-
-// a limit of the open path met by an append: the same check, reported as the append's argument
-static int as_append_argument(int rc, const char* arg) {
-  if (rc == NP_OK || rc == NP_ERR_OUT_OF_MEMORY || rc == NP_ERR_DEVICE_UNAVAILABLE) return rc;
-  const std::string msg = last_error();
-  set_error("np_hip_index_append: %s: %s", arg, msg.c_str());
-  return NP_ERR_INVALID_ARGUMENT;
-}
-
-// rows: the new documents' column rows and groups (np_hip_index_append_rows), where the plain append drops the attachments
-static int append_documents(DeviceIndex* ix, const int64_t* lens, int64_t n, const int64_t* codes, const uint8_t* residuals,
-                            int64_t Tn, int64_t maxlen, const AppendRows* rows) {
-  HoldContexts hold(ix);
-  DeviceGuard g(ix->device);
-  if (!g.ok) {
-    set_error("hipSetDevice(%d) failed", ix->device);
-    return NP_ERR_DEVICE_UNAVAILABLE;
-  }
-  const int64_t N0 = ix->n_docs, N1 = N0 + n, T0 = ix->T, T1 = T0 + Tn;
-  NP_TRY(as_append_argument(check_shard_docs(N1), "n_docs"));
-  NP_HIP(hipDeviceSynchronize());   // device-side calls that returned may still be running on their streams
-  OpenTrace trace("NP_APPEND_TRACE", "np append");
-  // 1. capacity first: commits nothing
-  NP_TRY(grow_capacity(ix, N1, T1));
-  if (rows) NP_TRY(grow_attachments(ix, N1));
-  trace.mark("grow");
-  // 2. the new documents behind the old ones -- outside what any kernel reads until the counts move -- and the per-token
-  //    stages over them alone
-  {
-    std::vector<int64_t> off((size_t)n);
-    int64_t t = T0;
-    for (int64_t d = 0; d < n; ++d) off[(size_t)d] = (t += lens[d]);
-    NP_HIP(hipMemcpy(ix->d_doc_offsets.get() + N0 + 1, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  }
-  if (Tn > 0) {
-    HostIndex h;
-    HostChunk c;
-    c.codes = codes;
-    c.residuals = residuals;
-    c.n_tokens = Tn;
-    h.chunks.push_back(c);
-    NP_TRY(as_append_argument(upload_tokens(h, ix, 0, Tn, T0), "codes"));
-    if (ix->tok_sorted) NP_TRY(permute_tokens(ix, 1, N0, N1));
-    NP_TRY(fill_inv_norm(ix, T0, T1));
-  }
-  trace.mark("upload + token stages");
-  // 3. the distinct-code structures of the grown index, beside the ones that serve
-  Ucodes u;
-  DevPtr<int64_t> d_uoff;
-  NP_TRY(as_append_argument(build_unique_codes(ix, tokens_of(ix), N1, &u, &d_uoff), "n_docs"));
-  trace.mark("distinct-code rebuild");
-  // 4. the posting lists
-  DevPtr<uint32_t> ivf;
-  DevPtr<int64_t> ioff;
-  std::vector<int64_t> h_ioff;
-  int64_t ivf_size = 0;
-  NP_TRY(merge_posting_lists(ix, u, d_uoff.get(), N0, N1, maxlen > NP_UNIQ_MAX, &ivf, &ioff, &h_ioff, &ivf_size, trace));
-  d_uoff.reset();
-  trace.mark("posting-list merge");
-  // 5. their range table.  Lists that held every (document, code) pair still do: the new entries are such pairs
-  DevPtr<uint32_t> split;
-  int R = 0, cover = ix->ivf_cover;
-  const bool merged = ivf.get() != nullptr;
-  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide},
-                    merged ? ivf.get() : ix->d_ivf.get(), merged ? ioff.get() : ix->d_ivf_offsets.get()};
-  NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
-  trace.mark("range table");
-  // 6. the new documents' rows, staged beside the attachments that serve
-  StagedRows staged;
-  if (rows) {
-    NP_TRY(stage_appended_rows(ix, *rows, N0, N1, &staged));
-    trace.mark("rows staged");
-  }
-  // ---- nothing below can fail: the handle becomes the grown index ----
-  int rows_rc = NP_OK;
-  if (rows) rows_rc = install_appended_rows(ix, *rows, std::move(staged), N0, N1);   // (not an allocation: a device that stopped answering)
-  else drop_attachments(ix);
-  install_ucodes(ix, std::move(u));
-  if (merged) {
-    ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
-    ix->d_ivf = std::move(ivf);
-    ix->d_ivf_offsets = std::move(ioff);
-    ix->ivf_size = ivf_size;
-    set_ivf_bound(ix, h_ioff.data());
-  }
-  install_ivf_split(ix, std::move(split), R);
-  ix->ivf_cover = cover;
-  // (old_avg * old_n + new_tokens) / n, the expression the directory update writes (np_update.cpp); a handle made from arrays
-  // has no stored figure and reports tokens / documents, as a fresh one of the grown arrays does
-  ix->avg_doclen = ix->avg_from_counts ? (double)(ix->n_emb_total + Tn) / (double)N1
-                                       : (ix->avg_doclen * (double)ix->N_total + (double)Tn) / (double)N1;
-  ix->n_docs = ix->N_total = N1;
-  ix->T = T1;
-  ix->n_emb_total += Tn;
-  ix->max_doc_len = std::max(ix->max_doc_len, maxlen);
-  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
-  ix->gain_run.store(0, std::memory_order_relaxed);
-  ix->gain_skip.store(0, std::memory_order_relaxed);
-  contexts_forget_index(ix);
-  return rows_rc;
-}
 
 // ---- remove from a resident index (np_hip_index_remove) ----------------------------------------------------------------
 // Survivors keep their order, so document d becomes d - rank(d) with rank(d) = the removed ids below d, every per-token array
@@ -2118,46 +2058,6 @@ static void launch_token_compact(const int64_t* new_off, const int64_t* src_star
   const int64_t v_lo = m.b0 - m.dshift, v_hi = m.b1 - m.dshift;
   const int64_t tiles = (v_hi - (v_lo & ~(int64_t)15) + NP_COMPACT_TILE - 1) / NP_COMPACT_TILE;
   token_compact_kernel<<<(unsigned)tiles, 256>>>(m, static_cast<const uint8_t*>(src), static_cast<uint8_t*>(dst));
-}
-
-// a pair of device events around a kernel, when a trace asks for the kernel's own time
-struct KernelClock {
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool on = false;
-  explicit KernelClock(bool want) { on = want && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess; }
-  ~KernelClock() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  void start() {
-    if (on) (void)hipEventRecord(ev[0], nullptr);
-  }
-  double stop() {   // seconds
-    float ms = 0.f;
-    if (!on) return 0.0;
-    (void)hipEventRecord(ev[1], nullptr);
-    if (hipEventSynchronize(ev[1]) != hipSuccess || hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) return 0.0;
-    return ms * 1e-3;
-  }
-};
-
-template <class T>
-static int device_scan_inclusive(const T* in, T* out, int64_t n) {
-  DevPtr<uint8_t> d_temp;
-  size_t tb = 0;
-  NP_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out, (int)n));
-  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-  NP_HIP(hipcub::DeviceScan::InclusiveSum(d_temp.get(), tb, in, out, (int)n));
-  return NP_OK;
-}
-template <class T>
-static int device_scan_exclusive(const T* in, T* out, int64_t n) {
-  DevPtr<uint8_t> d_temp;
-  size_t tb = 0;
-  NP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n));
-  NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-  NP_HIP(hipcub::DeviceScan::ExclusiveSum(d_temp.get(), tb, in, out, (int)n));
-  return NP_OK;
 }
 
 // the handle's posting lists without the removed documents, the rest renumbered: *ivf [*ivf_size], *ioff / *h_ioff [K + 1]
@@ -2519,14 +2419,9 @@ static int install_appended_rows(DeviceIndex* ix, const AppendRows& rows, Staged
 // removed: the ids to remove -- in range, ascending, each once, not empty.  keep: columns and groups are compacted with the
 // documents (np_hip_index_remove_keep), where the plain remove drops them
 static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed, bool keep, const char* entry) {
-  HoldContexts hold(ix);
-  DeviceGuard g(ix->device);
-  if (!g.ok) {
-    set_error("hipSetDevice(%d) failed", ix->device);
-    return NP_ERR_DEVICE_UNAVAILABLE;
-  }
+  UpdateSection section(ix);
+  NP_TRY(section.begin());
   const int64_t N0 = ix->n_docs, m = (int64_t)removed.size(), N1 = N0 - m, T0 = ix->T, W = (N0 + 63) / 64;
-  NP_HIP(hipDeviceSynchronize());   // device-side calls that returned may still be running on their streams
   OpenTrace trace("NP_REMOVE_TRACE", "np remove");
   // 1. the survivors: bitmap, ranks, the new doc offsets (at the capacity the old ones have) and the longest survivor
   DevPtr<int64_t> d_removed, d_klen, d_src, d_newoff, d_max;
@@ -2586,17 +2481,12 @@ static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed
   d_uoff.reset();
   trace.mark("distinct-code rebuild");
   // 4. the posting lists
-  DevPtr<uint32_t> ivf;
-  DevPtr<int64_t> ioff;
-  std::vector<int64_t> h_ioff;
-  int64_t ivf_size = 0;
-  NP_TRY(filter_posting_lists(ix, km, &ivf, &ioff, &h_ioff, &ivf_size, trace));
+  StagedLists lists;
+  NP_TRY(filter_posting_lists(ix, km, &lists.ivf, &lists.ioff, &lists.h_ioff, &lists.ivf_size, trace));
+  lists.replaced = true;
   trace.mark("posting-list filter");
-  // 5. their range table.  Lists that held every (document, code) pair still do: a survivor's entries all stay
-  DevPtr<uint32_t> split;
-  int R = 0, cover = N1 > 0 ? ix->ivf_cover : -1;
-  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide}, ivf.get(), ioff.get()};
-  NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
+  // 5. their range table
+  NP_TRY(stage_ivf_split(ix, u, N1, &lists));
   trace.mark("range table");
   // 5b. columns and groups of the survivors, beside the ones that serve
   KeptAttachments kept;
@@ -2641,13 +2531,7 @@ static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed
   ix->d_codes = std::move(codes);
   ix->d_doc_offsets = std::move(d_newoff);
   install_ucodes(ix, std::move(u));
-  ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
-  ix->d_ivf = std::move(ivf);
-  ix->d_ivf_offsets = std::move(ioff);
-  ix->ivf_size = ivf_size;
-  set_ivf_bound(ix, h_ioff.data());
-  install_ivf_split(ix, std::move(split), R);
-  ix->ivf_cover = cover;
+  install_lists(ix, std::move(lists));
   // tokens / documents, what the directory delete writes (np_update.cpp delete_impl) and a handle made from arrays reports
   ix->avg_doclen = N1 > 0 ? (double)T1 / (double)N1 : 0.0;
   ix->n_docs = ix->N_total = N1;
@@ -2656,10 +2540,7 @@ static int remove_documents(DeviceIndex* ix, const std::vector<int64_t>& removed
   ix->max_doc_len = maxlen;
   if (keep) install_kept_attachments(ix, std::move(kept));
   else drop_attachments(ix);
-  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
-  ix->gain_run.store(0, std::memory_order_relaxed);
-  ix->gain_skip.store(0, std::memory_order_relaxed);
-  contexts_forget_index(ix);
+  finish_update(ix);
   trace.mark("swap");
   if (moved != hipSuccess) {   // not an allocation: a device that stopped answering
     set_error("%s: the token move failed: %s", entry, hipGetErrorString(moved));
@@ -2714,65 +2595,6 @@ __global__ void __launch_bounds__(256) ivf_keep_kernel(const uint32_t* __restric
   n_keep[c] = a;
 }
 
-__global__ void ivf_cut_offsets_kernel(const int64_t* __restrict__ kept_pfx, const int64_t* __restrict__ start, int64_t K,
-                                       int64_t* __restrict__ new_off) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c <= K) new_off[c] = kept_pfx[c] + start[c];
-}
-
-// ivf_merge_kernel's sibling: the same entry-balanced stream over the NEW array (a workgroup owns NP_MERGE_TILE consecutive
-// entries, a thread quads of them, every entry has one source that scans alone decide: no atomics, no workgroup waits for
-// another), but list c's old part is old_ivf[old_begin[c] .. + kept_pfx[c + 1] - kept_pfx[c]) -- the list cut at the first
-// dropped document -- and there are K lists where the old array had fewer.
-__global__ void __launch_bounds__(256) ivf_cut_merge_kernel(const uint32_t* __restrict__ old_ivf, const int64_t* __restrict__ old_begin,
-                                                            const int64_t* __restrict__ kept_pfx, const uint64_t* __restrict__ pairs,
-                                                            const int64_t* __restrict__ start, const int64_t* __restrict__ new_off,
-                                                            int64_t K, int64_t total, uint32_t* __restrict__ out) {
-  __shared__ int64_t s_c0;
-  const int64_t o0 = (int64_t)blockIdx.x * NP_MERGE_TILE;   // < total: the grid covers [0, total)
-  if (threadIdx.x == 0) s_c0 = ivf_list_of(new_off, K, 0, o0);
-  __syncthreads();
-  int64_t c = s_c0;
-  MergeQuad q[NP_MERGE_QUADS];
-#pragma unroll
-  for (int it = 0; it < NP_MERGE_QUADS; ++it) {
-    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
-    q[it] = MergeQuad{{0u, 0u, 0u, 0u}};
-    if (o < total) {
-      const int n = (int)min((int64_t)4, total - o);
-      c = ivf_list_of(new_off, K, c, o);
-      int64_t b_new = new_off[c], e_new = new_off[c + 1], b_old = old_begin[c], n_old = kept_pfx[c + 1] - kept_pfx[c], b_pair = start[c];
-      if (n == 4 && o + 4 <= b_new + n_old) {   // (b_new + n_old <= e_new)
-        q[it] = *reinterpret_cast<const MergeQuad*>(old_ivf + b_old + (o - b_new));
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (k < n) {
-            const int64_t oo = o + k;
-            if (oo >= e_new) {
-              c = ivf_list_of(new_off, K, c, oo);
-              b_new = new_off[c], e_new = new_off[c + 1], b_old = old_begin[c], n_old = kept_pfx[c + 1] - kept_pfx[c], b_pair = start[c];
-            }
-            const int64_t r = oo - b_new;
-            q[it].v[k] = r < n_old ? old_ivf[b_old + r] : (uint32_t)(pairs[b_pair + (r - n_old)] & 0xFFFFFFFFull);
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < NP_MERGE_QUADS; ++it) {
-    const int64_t o = o0 + it * 1024 + (int64_t)threadIdx.x * 4;
-    if (o + 4 <= total) {
-      *reinterpret_cast<uint4*>(out + o) = make_uint4(q[it].v[0], q[it].v[1], q[it].v[2], q[it].v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (o + k < total) out[o + k] = q[it].v[k];
-    }
-  }
-}
-
 static int as_expand_argument(const char* entry, int rc, const char* arg) {
   if (rc == NP_OK || rc == NP_ERR_OUT_OF_MEMORY || rc == NP_ERR_DEVICE_UNAVAILABLE) return rc;
   const std::string msg = last_error();
@@ -2782,15 +2604,18 @@ static int as_expand_argument(const char* entry, int rc, const char* arg) {
 
 // The K1 = ix->K posting lists (the handle's K-dependent scalars are the grown ones by now; its d_ivf / d_ivf_offsets still the
 // K0 old lists): every old list cut at document Nk, then the pairs of documents [Nk, N1) from the distinct-code lists of the
-// final index (u, d_uoff).  Always a new array and new offsets.  raw_lists: as merge_posting_lists.
-static int cut_merge_posting_lists(const DeviceIndex* ix, int64_t K0, const Ucodes& u, const int64_t* d_uoff, int64_t Nk, int64_t N1,
-                                   bool raw_lists, DevPtr<uint32_t>* ivf, DevPtr<int64_t>* ioff, std::vector<int64_t>* h_ioff,
-                                   int64_t* ivf_size, const char* entry, const OpenTrace& trace) {
+// final index (u, d_uoff).  A call that cuts nothing and adds no list -- an append -- hands the kernel the handle's own offsets
+// and, when the given documents hold no pair either, leaves the handle's lists where they are (st->replaced stays false).
+// raw_lists: a given document is longer than NP_UNIQ_MAX tokens, so its list is its codes as they are, duplicates included --
+// a posting list names a document once (index.rs:479-499), so equal pairs, adjacent once sorted, are dropped.
+static int rewrite_posting_lists(const DeviceIndex* ix, int64_t K0, const Ucodes& u, const int64_t* d_uoff, int64_t Nk, int64_t N1,
+                                   bool raw_lists, StagedLists* st, const char* entry, const OpenTrace& trace) {
   const int64_t K = ix->K, n_new = N1 - Nk;
+  const bool cuts = K0 != K || Nk != ix->n_docs;
   DevPtr<int64_t> d_len64, d_upfx, d_start, d_begin, d_keep, d_kpfx;
   DevPtr<uint64_t> d_k1, d_k2;
-  DevPtr<uint8_t> d_temp;
   int64_t P = 0;   // (code, document) pairs of the given documents
+  st->ivf_size = ix->ivf_size;
   if (n_new > 0) {
     NP_TRY(d_len64.alloc((size_t)n_new));
     NP_TRY(d_upfx.alloc((size_t)n_new));
@@ -2799,8 +2624,9 @@ static int cut_merge_posting_lists(const DeviceIndex* ix, int64_t K0, const Ucod
     NP_HIP(hipMemcpy(&P, d_upfx.get() + (n_new - 1), 8, hipMemcpyDeviceToHost));
     d_len64.reset();
   }
-  if (P >= ((int64_t)1 << 31)) {
-    set_error("%s: n_docs: the given documents hold %lld (code, doc) pairs, one call takes < 2^31", entry, (long long)P);
+  if (P == 0 && !cuts) return NP_OK;
+  if (P >= ((int64_t)1 << 31)) {   // one radix sort, as one document range of build_ivf_from_ucodes
+    set_error("%s: n_docs: the %s documents hold %lld (code, doc) pairs, one call takes < 2^31", entry, cuts ? "given" : "new", (long long)P);
     return NP_ERR_INVALID_ARGUMENT;
   }
   NP_TRY(d_start.alloc((size_t)K + 1));
@@ -2812,50 +2638,48 @@ static int cut_merge_posting_lists(const DeviceIndex* ix, int64_t K0, const Ucod
     ivf_emit_pairs_kernel<<<(unsigned)((n_new + 3) / 4), 256>>>(Nk, N1, d_uoff, CodeArr{u.d_ucodes.get(), ix->code_wide}, u.d_ulen.get(),
                                                               d_upfx.get(), Nk, 0, d_k1.get());
     NP_HIP(hipGetLastError());
-    size_t tb = 0;
-    NP_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
-    NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-    NP_HIP(hipcub::DeviceRadixSort::SortKeys(d_temp.get(), tb, d_k1.get(), d_k2.get(), (int)P, 0, 32 + kbits));
+    NP_TRY(device_sort_pairs(d_k1.get(), d_k2.get(), P, kbits));
     if (raw_lists) {
-      DevPtr<int64_t> d_n;
-      NP_TRY(d_n.alloc(1));
-      tb = 0;
-      NP_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
-      NP_TRY(d_temp.alloc(std::max<size_t>(tb, 16)));
-      NP_HIP(hipcub::DeviceSelect::Unique(d_temp.get(), tb, d_k2.get(), d_k1.get(), d_n.get(), (int)P));
-      NP_HIP(hipMemcpy(&P, d_n.get(), 8, hipMemcpyDeviceToHost));
+      NP_TRY(device_unique(d_k2.get(), d_k1.get(), P, &P));
       std::swap(d_k1, d_k2);   // d_k2 = the sorted pairs, each once
     }
   }
   ivf_code_starts_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_k2.get(), P, K, d_start.get());
   NP_HIP(hipGetLastError());
   // the cut: what every list keeps, and where the kept parts begin in an array of them alone
-  NP_TRY(d_begin.alloc((size_t)K + 1));
-  NP_TRY(d_keep.alloc((size_t)K + 1));
-  NP_TRY(d_kpfx.alloc((size_t)K + 1));
-  ivf_keep_kernel<<<(unsigned)((K + 256) / 256), 256>>>(ix->d_ivf.get(), ix->d_ivf_offsets.get(), K0, K, Nk, d_begin.get(), d_keep.get());
-  NP_HIP(hipGetLastError());
-  NP_TRY(device_scan_exclusive(d_keep.get(), d_kpfx.get(), K + 1));
-  int64_t kept = 0;
-  NP_HIP(hipMemcpy(&kept, d_kpfx.get() + K, 8, hipMemcpyDeviceToHost));
+  const int64_t *old_begin = ix->d_ivf_offsets.get(), *kept_pfx = ix->d_ivf_offsets.get();
+  int64_t kept = ix->ivf_size;
+  if (cuts) {
+    NP_TRY(d_begin.alloc((size_t)K + 1));
+    NP_TRY(d_keep.alloc((size_t)K + 1));
+    NP_TRY(d_kpfx.alloc((size_t)K + 1));
+    ivf_keep_kernel<<<(unsigned)((K + 256) / 256), 256>>>(ix->d_ivf.get(), ix->d_ivf_offsets.get(), K0, K, Nk, d_begin.get(), d_keep.get());
+    NP_HIP(hipGetLastError());
+    NP_TRY(device_scan_exclusive(d_keep.get(), d_kpfx.get(), K + 1));
+    NP_HIP(hipMemcpy(&kept, d_kpfx.get() + K, 8, hipMemcpyDeviceToHost));
+    old_begin = d_begin.get(), kept_pfx = d_kpfx.get();
+  }
   const int64_t total = kept + P;
-  NP_TRY(ioff->alloc((size_t)K + 1));
-  NP_TRY(ivf->alloc((size_t)total));   // the new array beside the old one: the pass reads the one and writes the other
-  ivf_cut_offsets_kernel<<<(unsigned)((K + 256) / 256), 256>>>(d_kpfx.get(), d_start.get(), K, ioff->get());
+  NP_TRY(st->ioff.alloc((size_t)K + 1));
+  NP_TRY(st->ivf.alloc((size_t)total));   // the new array beside the old one: the pass reads the one and writes the other
+  ivf_cut_offsets_kernel<<<(unsigned)((K + 256) / 256), 256>>>(kept_pfx, d_start.get(), K, st->ioff.get());
   NP_HIP(hipGetLastError());
-  KernelClock clock(trace.on);
+  KernelClock clock(trace.on);   // NP_APPEND_TRACE: the kernel alone, for its bytes per second
   clock.start();
   if (total > 0)
     ivf_cut_merge_kernel<<<(unsigned)((total + NP_MERGE_TILE - 1) / NP_MERGE_TILE), 256>>>(
-        ix->d_ivf.get(), d_begin.get(), d_kpfx.get(), d_k2.get(), d_start.get(), ioff->get(), K, total, ivf->get());
+        ix->d_ivf.get(), old_begin, kept_pfx, d_k2.get(), d_start.get(), st->ioff.get(), K, total, st->ivf.get());
   NP_HIP(hipGetLastError());
-  if (trace.on)
+  if (trace.on && cuts)
     fprintf(stderr, "[%s] %-28s %8.6f s  %lld entries %lld new %lld cut\n", trace.tag, "cut-merge kernel", clock.stop(), (long long)total,
             (long long)P, (long long)(ix->ivf_size - kept));
-  h_ioff->resize((size_t)K + 1);
-  NP_HIP(hipMemcpy(h_ioff->data(), ioff->get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
+  else if (trace.on)
+    fprintf(stderr, "[%s] %-28s %8.6f s  %lld entries %lld new\n", trace.tag, "merge kernel", clock.stop(), (long long)total, (long long)P);
+  st->h_ioff.resize((size_t)K + 1);
+  NP_HIP(hipMemcpy(st->h_ioff.data(), st->ioff.get(), ((size_t)K + 1) * 8, hipMemcpyDeviceToHost));
   NP_HIP(hipDeviceSynchronize());
-  *ivf_size = total;
+  st->ivf_size = total;
+  st->replaced = true;
   return NP_OK;
 }
 
@@ -2934,29 +2758,50 @@ struct ExpandUndo {
   }
 };
 
-// np_hip_index_expand / _expand_rows once the arguments are checked.  rows: the rows of the n - n_replace NEW documents (the
-// replaced ones keep their ids and their rows), where the plain entry drops the attachments.
+// the n given documents behind document Nk and token Tk -- outside what any kernel reads until the counts move, or saved by
+// ExpandUndo -- and the per-token stages over them alone
+static int place_given_documents(const char* entry, DeviceIndex* ix, const int64_t* lens, int64_t n, const int64_t* codes,
+                                 const uint8_t* residuals, int64_t Tn, int64_t Nk, int64_t Tk) {
+  if (n > 0) {
+    std::vector<int64_t> off((size_t)n);
+    int64_t t = Tk;
+    for (int64_t d = 0; d < n; ++d) off[(size_t)d] = (t += lens[d]);
+    NP_HIP(hipMemcpy(ix->d_doc_offsets.get() + Nk + 1, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  if (Tn > 0) {
+    HostIndex h;
+    HostChunk c;
+    c.codes = codes;
+    c.residuals = residuals;
+    c.n_tokens = Tn;
+    h.chunks.push_back(c);
+    NP_TRY(as_expand_argument(entry, upload_tokens(h, ix, 0, Tn, Tk), "codes"));
+    if (ix->tok_sorted) NP_TRY(permute_tokens(ix, 1, Nk, Nk + n));
+    NP_TRY(fill_inv_norm(ix, Tk, Tk + Tn));
+  }
+  return NP_OK;
+}
+
+// np_hip_index_append / _append_rows (k_new == 0 and n_replace == 0: nothing is cut, widened or saved, and ExpandUndo has
+// nothing to put back) and np_hip_index_expand / _expand_rows, once the arguments are checked.  rows: the rows of the
+// n - n_replace NEW documents (the replaced ones keep their ids and their rows), where the plain entry drops the attachments.
 static int expand_documents(const char* entry, DeviceIndex* ix, const float* new_centroids, int64_t k_new, int64_t n_replace,
                             const int64_t* lens, int64_t n, const int64_t* codes, const uint8_t* residuals, int64_t Tn, int64_t maxlen,
                             const AppendRows* rows) {
-  HoldContexts hold(ix);
-  DeviceGuard g(ix->device);
-  if (!g.ok) {
-    set_error("hipSetDevice(%d) failed", ix->device);
-    return NP_ERR_DEVICE_UNAVAILABLE;
-  }
+  UpdateSection section(ix);
+  NP_TRY(section.begin());
   const int64_t N0 = ix->n_docs, Nk = N0 - n_replace, N1 = Nk + n, K0 = ix->K, K1 = K0 + k_new, T0 = ix->T;
+  const bool expands = k_new > 0 || n_replace > 0;   // else an append: its trace keeps its own tag and stage names
   if (n_replace > N0) {   // (checked by the entry; the handle may have shrunk since)
     set_error("%s: n_replace is %lld, the handle has %lld documents", entry, (long long)n_replace, (long long)N0);
     return NP_ERR_INVALID_ARGUMENT;
   }
   NP_TRY(as_expand_argument(entry, check_shard_docs(N1), "n_docs"));
   NP_TRY(as_expand_argument(entry, check_geometry(K1, ix->ldim, ix->lnbits, N1), "k_new"));
-  NP_HIP(hipDeviceSynchronize());   // device-side calls that returned may still be running on their streams
-  OpenTrace trace("NP_APPEND_TRACE", "np expand");
+  OpenTrace trace("NP_APPEND_TRACE", expands ? "np expand" : "np append");
   // the tail that goes: its first token, its longest document
-  std::vector<int64_t> h_tail((size_t)n_replace + 1);
-  NP_HIP(hipMemcpy(h_tail.data(), ix->d_doc_offsets.get() + Nk, h_tail.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<int64_t> h_tail((size_t)n_replace + 1, T0);
+  if (n_replace > 0) NP_HIP(hipMemcpy(h_tail.data(), ix->d_doc_offsets.get() + Nk, h_tail.size() * 8, hipMemcpyDeviceToHost));
   const int64_t Tk = h_tail[0], T1 = Tk + Tn;
   int64_t kept_max = ix->max_doc_len, tail_max = 0;
   for (int64_t d = 0; d < n_replace; ++d) tail_max = std::max(tail_max, h_tail[(size_t)d + 1] - h_tail[(size_t)d]);
@@ -3004,30 +2849,14 @@ static int expand_documents(const char* entry, DeviceIndex* ix, const float* new
   // 3. the tail's bytes beside, then the grown geometry goes live for the stages below; from here on a failure restores
   NP_TRY(undo.save_tail(Nk, N0, Tk, T0));
   undo.flip(K1, cmax1, filter_ok1, s6_fast_ok1);
-  trace.mark("tail saved");
+  if (expands) trace.mark("tail saved");
   auto refused_after = [&](int stage) {   // Tuning::expand_fail: a test's stand-in for an allocation the device refuses here
     if (ix->tune.expand_fail != stage) return false;
     set_error("%s: out of memory after stage %d (np_hip_index_tune \"expand_fail\")", entry, stage);
     return true;
   };
-  // 4. the given documents from the first dropped token on, and the per-token stages over them alone
-  if (n > 0) {
-    std::vector<int64_t> off((size_t)n);
-    int64_t t = Tk;
-    for (int64_t d = 0; d < n; ++d) off[(size_t)d] = (t += lens[d]);
-    NP_HIP(hipMemcpy(ix->d_doc_offsets.get() + Nk + 1, off.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  }
-  if (Tn > 0) {
-    HostIndex h;
-    HostChunk c;
-    c.codes = codes;
-    c.residuals = residuals;
-    c.n_tokens = Tn;
-    h.chunks.push_back(c);
-    NP_TRY(as_expand_argument(entry, upload_tokens(h, ix, 0, Tn, Tk), "codes"));
-    if (ix->tok_sorted) NP_TRY(permute_tokens(ix, 1, Nk, N1));
-    NP_TRY(fill_inv_norm(ix, Tk, T1));
-  }
+  // 4. the given documents from the first dropped token on
+  NP_TRY(place_given_documents(entry, ix, lens, n, codes, residuals, Tn, Nk, Tk));
   trace.mark("upload + token stages");
   if (refused_after(1)) return NP_ERR_OUT_OF_MEMORY;
   // 5. the distinct-code structures of the final documents, once: the eighths of the centroid range moved for all of them
@@ -3037,20 +2866,13 @@ static int expand_documents(const char* entry, DeviceIndex* ix, const float* new
   trace.mark("distinct-code rebuild");
   if (refused_after(2)) return NP_ERR_OUT_OF_MEMORY;
   // 6. the posting lists, one pass
-  DevPtr<uint32_t> ivf;
-  DevPtr<int64_t> ioff;
-  std::vector<int64_t> h_ioff;
-  int64_t ivf_size = 0;
-  NP_TRY(cut_merge_posting_lists(ix, K0, u, d_uoff.get(), Nk, N1, maxlen > NP_UNIQ_MAX, &ivf, &ioff, &h_ioff, &ivf_size, entry, trace));
+  StagedLists lists;
+  NP_TRY(rewrite_posting_lists(ix, K0, u, d_uoff.get(), Nk, N1, maxlen > NP_UNIQ_MAX, &lists, entry, trace));
   d_uoff.reset();
-  trace.mark("posting-list cut + merge");
+  trace.mark(expands ? "posting-list cut + merge" : "posting-list merge");
   if (refused_after(3)) return NP_ERR_OUT_OF_MEMORY;
-  // 7. their range table.  Lists that held every (document, code) pair still do: a kept document's entries all stay, the
-  //    given documents' pairs are all there
-  DevPtr<uint32_t> split;
-  int R = 0, cover = N1 > 0 ? ix->ivf_cover : -1;
-  const ListsView v{N1, u.ublock_stride, u.d_doc_meta.get(), CodeArr{u.d_ucodes.get(), ix->code_wide}, ivf.get(), ioff.get()};
-  NP_TRY(make_ivf_split(ix, v, ix->ivf_cover == 1, &split, &R, &cover));
+  // 7. their range table
+  NP_TRY(stage_ivf_split(ix, u, N1, &lists));
   trace.mark("range table");
   if (refused_after(4)) return NP_ERR_OUT_OF_MEMORY;
   // 8. the new documents' rows, staged beside the attachments that serve
@@ -3065,13 +2887,7 @@ static int expand_documents(const char* entry, DeviceIndex* ix, const float* new
   if (with_rows) rows_rc = install_appended_rows(ix, *rows, std::move(staged), N0, N1);   // (not an allocation: a device that stopped answering)
   else if (!rows) drop_attachments(ix);
   install_ucodes(ix, std::move(u));
-  ix->device_bytes = ix->device_bytes - ix->d_ivf.bytes() - ix->d_ivf_offsets.bytes() + ivf.bytes() + ioff.bytes();
-  ix->d_ivf = std::move(ivf);
-  ix->d_ivf_offsets = std::move(ioff);
-  ix->ivf_size = ivf_size;
-  set_ivf_bound(ix, h_ioff.data());
-  install_ivf_split(ix, std::move(split), R);
-  ix->ivf_cover = cover;
+  install_lists(ix, std::move(lists));
   // the directory's arithmetic, delete and then append (np_update.cpp delete_impl, update_index_files): tokens / documents
   // after the tail drop, then (avg * n + new_tokens) / n1; a handle made from arrays reports tokens / documents
   const int64_t emb_k = ix->n_emb_total - (T0 - Tk);
@@ -3087,11 +2903,8 @@ static int expand_documents(const char* entry, DeviceIndex* ix, const float* new
   ix->T = T1;
   ix->n_emb_total = emb_k + Tn;
   ix->max_doc_len = std::max(kept_max, maxlen);
-  ix->gain_key.store(0, std::memory_order_relaxed);   // the zeroth level's run / skip policy starts over, as on a fresh handle
-  ix->gain_run.store(0, std::memory_order_relaxed);
-  ix->gain_skip.store(0, std::memory_order_relaxed);
-  contexts_forget_index(ix);
-  trace.mark("swap");
+  finish_update(ix);
+  if (expands) trace.mark("swap");
   return rows_rc;
 }
 
@@ -3638,7 +3451,7 @@ static int append_entry(const char* entry, np_index* ix, const int64_t* doc_leng
       set_error("%s: codes[%lld] = %lld is outside [0, %lld)", entry, (long long)t, (long long)codes[t], (long long)ix->K);
       return NP_ERR_INVALID_ARGUMENT;
     }
-  return append_documents(ix, doc_lengths, n_docs, codes, residuals, Tn, maxlen, rows);
+  return expand_documents(entry, ix, nullptr, 0, 0, doc_lengths, n_docs, codes, residuals, Tn, maxlen, rows);
 }
 
 int np_hip_index_append(np_index* ix, const int64_t* doc_lengths, int64_t n_docs, const int64_t* codes, const uint8_t* residuals) {

@@ -255,8 +255,9 @@ struct Tuning {
   int scan_docs = 0;     // ... documents per pass over the index; 0 = as many as the key table's share of the workspace budget holds
   int remove_slab = 0;   // np_hip_index_remove: source tokens per slab of the in-place token move (np_remove_plan.h) = rows of its
                          // staging buffer; 0 = NP_REMOVE_SLAB_DEFAULT.  np_hip_index_tune only: tests cross slab edges with a few thousand tokens
-  int expand_fail = 0;   // np_hip_index_expand: the stage after which the call returns NP_ERR_OUT_OF_MEMORY as a refused allocation there
-                         // would (1 token stages, 2 distinct-code rebuild, 3 posting lists, 4 range table; 0 = never).  No device
+  int expand_fail = 0;   // np_hip_index_expand and, sharing its body, np_hip_index_append (both with their _rows entries): the stage
+                         // after which the call returns NP_ERR_OUT_OF_MEMORY as a refused allocation there would (1 token
+                         // stages, 2 distinct-code rebuild, 3 posting lists, 4 range table; 0 = never).  No device
                          // error is involved: the call ends early and its undo runs.  np_hip_index_tune only: tests check that the
                          // handle is put back -- a real refusal needs a full device
 };

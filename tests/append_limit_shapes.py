@@ -1,5 +1,5 @@
 """The cases of tests/test_append_limits_cpu.py and tests/test_gpu_append_limits.py: np_hip_index_append at the edges of
-ivf_merge_kernel (a tile of 4096 entries, a quad of 4 per thread) and of the layouts it rebuilds (test infrastructure; numpy
+ivf_cut_merge_kernel (a tile of 4096 entries, a quad of 4 per thread) and of the layouts it rebuilds (test infrastructure; numpy
 and next_plaid_amd.synth only).
 
 A case is a base index, the documents appended to it in one or more calls, and one line that names the edge it is for.  Every

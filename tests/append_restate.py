@@ -3,11 +3,12 @@ nor the oracle).
 
     grown_arrays   the arrays of the index after an append, STARTING FROM THE BASE'S GIVEN LISTS: list c is old list c followed
                    by the ascending ids of the new documents that hold c, each once (index.rs:479-499 for the new entries)
-    new_pairs      the sorted (code << 32 | id) pairs merge_posting_lists makes of the new documents: a document of more than
+    new_pairs      the sorted (code << 32 | id) pairs rewrite_posting_lists makes of the new documents: a document of more than
                    NP_UNIQ_MAX tokens contributes every token (its distinct-code list is its codes as they are), and the
                    sorted pairs are then made unique
-    merge_route    ivf_merge_kernel's own route in plain Python, thread by thread, with a census of the paths it took and the
-                   planted defects of tests/test_append_limits_cpu.py
+    merge_route    ivf_cut_merge_kernel's route on an append's arguments (nothing cut, no list added: the old offsets are
+                   old_begin and kept_pfx at once) in plain Python, thread by thread, with a census of the paths it took and
+                   the planted defects of tests/test_append_limits_cpu.py
     expected_*     the same facts from array arithmetic alone, without the route: what the census is held against
     stride_bytes   choose_ublock_stride's rule (host_stride_bytes)
     n_ranges       ceil(n_docs / NP_SPLIT_RANGE)
@@ -90,7 +91,7 @@ def new_pairs(n_old, new, unique=True):
     # a document within NP_UNIQ_MAX has a sorted list of DISTINCT codes; a longer one lists every token
     pairs = np.sort(np.concatenate([np.unique(key[~raw]), key[raw]]))
     p_before = int(pairs.size)
-    if unique and raw.any():   # (merge_posting_lists runs DeviceSelect::Unique only when some document is that long)
+    if unique and raw.any():   # (rewrite_posting_lists runs DeviceSelect::Unique only when some document is that long)
         pairs = np.unique(pairs)
     return pairs.astype(np.int64), p_before
 
@@ -144,7 +145,7 @@ def _list_of(off, K, c, o, defect, census):
 
 
 def merge_route(old_ivf, old_off, pairs, K, tile=NP_MERGE_TILE, defect=None):
-    """ivf_merge_kernel over the grid merge_posting_lists launches.  Returns (new array, new offsets, census).  A read or a
+    """ivf_cut_merge_kernel over the grid rewrite_posting_lists launches for an append.  Returns (new array, new offsets, census).  A read or a
     write outside an array raises RouteFault."""
     assert defect is None or defect in DEFECTS
     old_ivf = np.asarray(old_ivf, np.int64)
@@ -153,7 +154,7 @@ def merge_route(old_ivf, old_off, pairs, K, tile=NP_MERGE_TILE, defect=None):
     P = int(pairs.size)
     # ivf_code_starts_kernel: start[c] = the first sorted pair whose code is >= c, by bisection
     start = [int(x) for x in np.searchsorted(pairs, np.arange(K + 1, dtype=np.int64) << 32, side="left")]
-    new_off = [a + b for a, b in zip(old_off, start)]                  # ivf_new_offsets_kernel
+    new_off = [a + b for a, b in zip(old_off, start)]                  # ivf_cut_offsets_kernel on the old offsets
     total = old_off[K] + P
     out = np.full(total, -1, np.int64)
     census = dict(fast=0, slow=0, whole_stores=0, partial_stores=0, max_lists_in_quad=0, alternates=False, longest_gallop=0,

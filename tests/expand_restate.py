@@ -120,10 +120,13 @@ def expected_widen(n, grid=None):
 
 
 # ---- the cut and the merge ---------------------------------------------------------------------------------------------------------
-def cut_merge_route(old_ivf, old_off, K0, K1, Nk, pairs, tile=NP_MERGE_TILE, defect=None):
-    """cut_merge_posting_lists' kernels over the grids it launches.  Returns (new array, new offsets, census).  A read or a
-    write outside an array raises RouteFault; so does a read of an old entry at or behind its list's cut ("dropped")."""
+def cut_merge_route(old_ivf, old_off, K0, K1, Nk, pairs, tile=NP_MERGE_TILE, defect=None, uncut=False):
+    """rewrite_posting_lists' kernels over the grids it launches.  Returns (new array, new offsets, census).  A read or a
+    write outside an array raises RouteFault; so does a read of an old entry at or behind its list's cut ("dropped").
+    uncut: the append's call, which cuts nothing and adds no list (K0 == K1, every old id < Nk) -- ivf_keep_kernel and its
+    scan do not run, the old offsets themselves are old_begin and kept_pfx."""
     assert defect is None or defect in CUT_DEFECTS
+    assert not uncut or (defect is None and K0 == K1)
     old_ivf = np.asarray(old_ivf, np.int64)
     old_off = [int(x) for x in old_off]
     pairs = np.asarray(pairs, np.int64)
@@ -145,7 +148,10 @@ def cut_merge_route(old_ivf, old_off, K0, K1, Nk, pairs, tile=NP_MERGE_TILE, def
     start = [int(x) for x in np.searchsorted(pairs, np.arange(K + 1, dtype=np.int64) << 32, side="left")]
     # ivf_keep_kernel: (K + 256) / 256 blocks of 256
     old_begin, n_keep, klass = [None] * (K + 1), [None] * (K + 1), [None] * K
-    keep_threads = (K + 256) // 256 * 256
+    keep_threads = 0 if uncut else (K + 256) // 256 * 256
+    if uncut:
+        old_begin, n_keep = list(old_off), il0.tolist() + [0]
+        klass = ["keeps all" if n else "empty" for n in n_keep[:K]]
     for c in range(keep_threads):
         if c > K:
             continue
@@ -170,7 +176,7 @@ def cut_merge_route(old_ivf, old_off, K0, K1, Nk, pairs, tile=NP_MERGE_TILE, def
         klass[c] = "empty" if n == 0 else "keeps all" if a == n else "keeps none" if a == 0 else "cut inside"
     assert None not in old_begin and None not in n_keep, "the keep kernel's grid left a list out"
     # device_scan_exclusive over K + 1 entries
-    kept_pfx = (np.cumsum(n_keep) if defect == "pfx_inclusive" else offsets(n_keep)[:-1]).tolist()
+    kept_pfx = list(old_off) if uncut else (np.cumsum(n_keep) if defect == "pfx_inclusive" else offsets(n_keep)[:-1]).tolist()
     new_off = [a + b for a, b in zip(kept_pfx, start)]                 # ivf_cut_offsets_kernel
     total = kept_pfx[K] + P
     out = np.full(total, -1, np.int64)

@@ -1,6 +1,6 @@
 """tests/append_limit_shapes.py bites: on the numpy restatement alone (no device) every case reaches the edge it names, the
-route of ivf_merge_kernel restated in tests/append_restate.py gives the lists grown_arrays states, and each planted defect of
-that route is rejected by a named case.  tests/test_gpu_append_limits.py then holds the device to the same arrays.
+route of ivf_cut_merge_kernel on an append's arguments, restated in tests/append_restate.py, gives the lists grown_arrays
+states, and each planted defect of that route is rejected by a named case.tests/test_gpu_append_limits.py then holds the device to the same arrays.
 
 Two of the planted defects cannot change the merged array, and the test says so instead of pretending: a fast-path bound that
 is one entry too STRICT only sends a quad down the entry-by-entry path, and a tile whose first list is found from entry o0 - 1
@@ -12,6 +12,7 @@ import pytest
 
 import append_limit_shapes as S
 import append_restate as A
+import expand_restate as X
 from test_gpu_index_append import _concat
 
 MERGE = [c for c in S.all_cases() if c.merge]
@@ -53,6 +54,20 @@ def test_route_equals_the_stated_lists(case, routed):
     assert census["tile_first_list"] == A.expected_tile_first_lists(*_arith(case))
     assert census["fast"] + census["slow"] == census["whole_stores"] + census["partial_stores"] == -(-census["total"] // 4)
     assert census["partial_stores"] == (census["total"] % 4 != 0) and census["last_quad"] == (census["total"] - 1) % 4 + 1
+
+
+@pytest.mark.parametrize("case", S.all_cases(), ids=lambda c: c.name)
+def test_an_append_is_the_cut_merge_that_cuts_nothing(case, routed):
+    """what folding the append's kernel into the expand's rests on: the cut-merge route with K0 = K1 = K, Nk = the old
+    documents and the old offsets themselves as old_begin and kept_pfx writes, entry for entry, the array and the offsets of
+    merge_route.  ivf_keep_kernel and its scan, which the append's call leaves out, would have given the same two arrays."""
+    old_ivf, old_off, pairs = case.base["ivf"], A.offsets(case.base["ivf_lengths"]), case.pairs()[0]
+    want = routed[case.name] if case.name in routed else _route(case)
+    for uncut in (True, False):
+        out, new_off, census = X.cut_merge_route(old_ivf, old_off, case.K, case.K, case.n_old, pairs, uncut=uncut)
+        assert np.array_equal(out, want[0]) and np.array_equal(new_off, want[1])
+        assert all(census[k] == want[2][k] for k in ("fast", "slow", "whole_stores", "partial_stores", "tile_first_list", "total", "P"))
+        assert set(census["classes"]) <= {"keeps all", "empty"} and census["kept"] == old_off[-1]
 
 
 @pytest.mark.parametrize("case", S.all_cases(), ids=lambda c: c.name)

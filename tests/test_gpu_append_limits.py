@@ -1,4 +1,4 @@
-"""np_hip_index_append at the limits of ivf_merge_kernel and of the layouts it rebuilds (tests/append_limit_shapes.py holds the
+"""np_hip_index_append at the limits of ivf_cut_merge_kernel and of the layouts it rebuilds (tests/append_limit_shapes.py holds the
 cases, tests/test_append_limits_cpu.py proves that each reaches its edge).  Needs a real MI355X.
 
 Per case the base is opened, the case's documents are appended in its stated calls, and the grown handle is held to
@@ -170,3 +170,122 @@ def test_several_appends_on_a_directory(tmp_path):
             fresh.close()
     finally:
         hx.close()
+
+
+# ---- the append under the expand's body: its way back, and a call with nothing to merge -------------------------------------
+def _state(hx, queries):
+    """what a refused append must leave as it was: the export, the info and the answers to the query set, as bytes"""
+    a = hx.export()
+    return ({k: np.ascontiguousarray(a[k]).tobytes() for k in ("doc_lengths", "codes", "residuals", "ivf", "ivf_lengths")}, _info(hx),
+            [(r.passage_ids.tobytes(), np.asarray(r.scores, np.float32).tobytes()) for r in hx.search_batch(queries, P(None))])
+
+
+WAY_BACK = [next(c for c in S.all_cases() if c.notes.get("residue") == 1), S.case("raw list over a tile edge")]
+
+
+@pytest.mark.parametrize("case", WAY_BACK, ids=lambda c: c.name)
+def test_a_refused_append_puts_the_handle_back(case):
+    """np_hip_index_tune "expand_fail" governs the body that the append shares with the expand: after the token stages (the new
+    tokens and doc offsets already lie behind the old ones), the distinct-code rebuild, the posting lists and the range table
+    the call returns OutOfMemory as a refused allocation there would.  After each refusal the handle's export, info and
+    answers are byte for byte what they were; with the knob back at 0 the same append succeeds and equals the fresh handle.
+    The second case appends a document of more than NP_UNIQ_MAX = 4096 tokens, the raw-list path."""
+    assert case.name.startswith("residue") or case.new[0].max() > A.NP_UNIQ_MAX
+    base, n_old, new, g = case.base, case.n_old, case.new, case.grown()
+    queries = _queries(base, new)
+    hx, fresh = hip_index(base), hip_index(g)
+    try:
+        before = _state(hx, queries)
+        for stage in (1, 2, 3, 4):
+            hx.tune("expand_fail", stage)
+            with pytest.raises(MemoryError, match=f"np_hip_index_append: out of memory after stage {stage}"):
+                hx.append_arrays(*new)
+            after = _state(hx, queries)
+            for part, (x, y) in zip(("export", "info", "answers"), zip(before, after)):
+                assert x == y, f"{case.name}: {part} changed by an append refused after stage {stage}"
+        hx.tune("expand_fail", 0)
+        assert hx.append_arrays(*new).tolist() == list(range(n_old, n_old + len(new[0])))
+        got = hx.export()
+        for k in ("doc_lengths", "codes", "residuals", "ivf", "ivf_lengths"):
+            assert np.array_equal(got[k], g[k]), f"{case.name}: export()[{k!r}] against grown_arrays"
+        _assert_equal_to_fresh(hx, fresh, queries, n_old, case.name)
+    finally:
+        hx.close()
+        fresh.close()
+
+
+def test_a_refused_append_rows_keeps_columns_and_groups():
+    """the same four refusals through np_hip_index_append_rows: get_column / get_groups give the bytes they gave before, and
+    the append that then succeeds leaves the old rows in front of the new ones"""
+    case = WAY_BACK[0]
+    base, n_old, new = case.base, case.n_old, case.new
+    n_new = len(new[0])
+    rng = np.random.default_rng(7300)
+    langs = ["de", "en", "fr"]
+
+    def values(n):
+        r = rng.random(n)
+        return ({"i": rng.integers(-5, 50, n), "f": np.where(r < 0.25, np.nan, rng.standard_normal(n)),
+                 "s": [None if r[d] > 0.8 else langs[j] for d, j in enumerate(rng.integers(0, 3, n))]},
+                [None if r[d] < 0.1 else int(k) for d, k in enumerate(rng.integers(0, 40, n))])
+
+    (old_vals, old_keys), (new_vals, new_keys) = values(n_old), values(n_new)
+    queries = _queries(base, new)
+
+    def read_back(hx):
+        out = {}
+        for name in old_vals:
+            data, valid = hx.get_column(name)
+            out[name] = (data.tobytes(), None if valid is None else np.asarray(valid).tobytes())
+        out["groups"] = hx.get_groups().tobytes()
+        return out
+
+    hx = hip_index(base)
+    try:
+        hx.set_columns(old_vals)
+        hx.set_groups(old_keys)
+        before, rows_before = _state(hx, queries), read_back(hx)
+        for stage in (1, 2, 3, 4):
+            hx.tune("expand_fail", stage)
+            with pytest.raises(MemoryError, match=f"np_hip_index_append_rows: out of memory after stage {stage}"):
+                hx.append_arrays(*new, rows=npa.api.AppendRows(columns=new_vals, groups=new_keys))
+            assert read_back(hx) == rows_before, f"columns or groups changed by an append refused after stage {stage}"
+            assert _state(hx, queries) == before, f"the handle changed by an append refused after stage {stage}"
+        hx.tune("expand_fail", 0)
+        ids = hx.append_arrays(*new, rows=npa.api.AppendRows(columns=new_vals, groups=new_keys))
+        assert ids.tolist() == list(range(n_old, n_old + n_new))
+        data, _ = hx.get_column("i")
+        assert np.array_equal(data, np.concatenate([old_vals["i"], new_vals["i"]]))
+        gids = hx.get_groups()
+        assert gids.size == n_old + n_new and gids[:n_old].tobytes() == rows_before["groups"]
+        got, g = hx.export(), case.grown()
+        for k in ("doc_lengths", "codes", "residuals", "ivf", "ivf_lengths"):
+            assert np.array_equal(got[k], g[k]), f"export()[{k!r}] against grown_arrays"
+    finally:
+        hx.close()
+
+
+def test_documents_without_a_token_leave_the_lists_alone():
+    """three documents of length 0 add no (code, document) pair: the append writes no new list array -- the export's lists
+    are the base's, and np_hip_index_info reports the device bytes of a fresh handle of the same arrays.  np_hip_index_expand
+    with k_new = 0 and n_replace = 0 of the same documents is the same call under the other entry's name."""
+    base = S.short_base(np.random.default_rng(7301), 300)
+    empty = (np.zeros(3, np.int64), np.zeros(0, np.int64), np.zeros((0, S.PD), np.uint8))
+    g = A.grown_arrays(base, empty)
+    assert np.array_equal(g["ivf"], base["ivf"]) and np.array_equal(g["ivf_lengths"], base["ivf_lengths"])
+    queries = _queries(base, S.rand_docs(np.random.default_rng(7302), [8, 8, 8, 8], 256))
+    hx, ex, fresh = hip_index(base), hip_index(base), hip_index(g)
+    try:
+        assert hx.append_arrays(*empty).tolist() == [300, 301, 302]
+        assert ex.expand_arrays(np.zeros((0, S.DIM), np.float32), *empty, n_replace=0).tolist() == [300, 301, 302]
+        for h, what in ((hx, "append"), (ex, "expand(0, 0)")):
+            got = h.export()
+            for k in ("doc_lengths", "codes", "residuals", "ivf", "ivf_lengths"):
+                assert np.array_equal(got[k], g[k]), f"{what}: export()[{k!r}]"
+            assert h.num_documents() == 303 and _info(h) == _info(fresh), what
+            assert int(h.info.device_bytes) == int(fresh.info.device_bytes), (what, int(h.info.device_bytes), int(fresh.info.device_bytes))
+        assert _state(hx, queries) == _state(ex, queries) == _state(fresh, queries)
+    finally:
+        hx.close()
+        ex.close()
+        fresh.close()
