@@ -1474,15 +1474,28 @@ int np_hip_pool_documents(int32_t device, const float* embeddings, const int64_t
  * Input: the documents' UTF-8 bytes concatenated and offsets[n_docs + 1] into them (host pointers, uploaded by the call);
  * document i is the FTS5 row with rowid i.  Needs no index.
  *
- * The device reproduces SQLite for ASCII text only:
+ * By default the device reproduces SQLite for ASCII text only:
  *   NP_TOK_UNICODE61  token characters are [0-9A-Za-z]; every other byte 0x00..0x7F separates (NUL too); A-Z fold to a-z;
  *                     positions count tokens from 0
  *   NP_TOK_TRIGRAM    every byte offset i <= len - 3 is a token: the three bytes, A-Z folded, at position i
+ * UTF-8 mode (opt-in: NP_TOK_UNICODE61 with opts->unicode_table set; NP_TOK_TRIGRAM ignores the table) reproduces unicode61
+ * (remove_diacritics=1) for every code point the caller's table covers.  The table has one uint32 per code point of its
+ * planes (unicode_table_len = planes * 65536, 1..17 planes): bits 0-20 the folded code point, bits 30-31 the class -- 0 a
+ * separator, 1 a token character (the term gets its fold, always one code point), 2 a mark: it continues a token that is
+ * open and contributes nothing to the term, and separates otherwise.  The rule is SQLite's, so the table is probed from
+ * SQLite by the caller (text.unicode61_table); none of it is compiled in.  Checked before any launch (np_textbuild_plan.h,
+ * textbuild_check_table): the length, classes <= 2, folds below 0x110000 and no surrogates, entries 0..127 exactly the
+ * ASCII rule above (a separator's entry is 0), no fold whose UTF-8 form is more than one byte longer than its source.
+ * Instances still name raw byte ranges of the text; two tokens are one term when their folded code points, marks skipped,
+ * are equal, whatever their raw lengths, and the vocabulary holds the folded strings.
  * A document it cannot reproduce is a FALLBACK document: it contributes no instance, its id is listed by
  * np_hip_text_build_fallback, and the caller tokenises it (with SQLite) and hands its instances to np_hip_text_build_add.
  * Fallback rules: any byte >= 0x80; trigram: a NUL byte (it ends the text for SQLite); unicode61: a token longer than
  * max_token_bytes (1..32768, 0 = 256; SQLite cuts a token at 32768).  The cap only moves documents to the list: it never
- * changes the result.
+ * changes the result.  UTF-8 mode replaces the first rule: a malformed sequence (a stray continuation byte, an overlong
+ * form, a surrogate, a value above U+10FFFF, F8..FF, a lead whose continuation bytes are missing at the document's end --
+ * the next document's bytes never complete it), a code point at or beyond the table's length.  There the cap counts the
+ * token's raw bytes, marks included, and max_token_bytes above 21845 is refused (a fold grows a token by at most 3/2).
  *
  * Stages (each a sequence of launches; no workgroup waits for another inside a launch, only integer atomics are used and
  * no result depends on the order in which they arrive):
@@ -1506,7 +1519,8 @@ int np_hip_pool_documents(int32_t device, const float* embeddings, const int64_t
  * n_docs (FTS5's nRow counts empty rows).  A build is not shared between threads.
  *
  * Refused before any launch, the message naming the argument.  NP_ERR_INVALID_ARGUMENT: offsets that do not ascend from 0,
- * an unknown tokenizer, max_token_bytes outside 0..32768, a hash_bits or tile_bytes knob out of range; for
+ * an unknown tokenizer, max_token_bytes outside 0..32768 (UTF-8 mode: 0..21845), a unicode_table that fails its checks, a
+ * hash_bits or tile_bytes knob out of range; for
  * np_hip_text_build_add: instances out of (term, document, position) order, terms out of memcmp order, a document that is
  * not on the fallback list, a second add or an add after np_hip_text_build_sizes.  NP_ERR_SHAPE: a document longer than
  * 2^31 - 1 bytes, 2^31 documents or more, 2^31 instances or more in one call (known for unicode61 only after the counting
@@ -1523,7 +1537,9 @@ typedef struct np_text_build_opts {
   int64_t workspace_bytes;   /* device bytes the call may hold at once; 0 = what the device has free */
   int32_t hash_bits;         /* test knob: log2 of the first term table, 1..31; 0 = planned from the instance count */
   int32_t tile_bytes;        /* test knob: bytes a wave walks per step, a multiple of 16 in 16..1024; 0 = 1024 */
-  int64_t reserved[3];
+  const uint32_t* unicode_table;   /* host pointer; non-NULL with NP_TOK_UNICODE61 = UTF-8 mode (see above); NULL = ASCII */
+  int64_t unicode_table_len;       /* entries: a multiple of 65536 in 65536 .. 17 * 65536 */
+  int64_t reserved[1];
 } np_text_build_opts;
 
 typedef struct np_text_build_report {

@@ -1669,6 +1669,29 @@ inline np_text_build_opts text_build_opts(Tokenizer tokenizer, int32_t max_token
   return o;
 }
 
+// UTF-8 mode: the overloads below that take a `unicode_table` hand it to the library (np_text_build_opts.unicode_table:
+// SQLite's unicode61 rule, one uint32 per code point of 1..17 planes), which then reproduces unicode61 for well-formed
+// UTF-8 inside the table instead of ASCII alone.  This mirror has no SQLite, so the caller supplies the table -- for
+// example the file next_plaid_amd.text.unicode61_table(planes).tofile(path) wrote, read by load_unicode_table.  The
+// vector must live until the call returns.
+inline np_text_build_opts text_build_opts(Tokenizer tokenizer, int32_t max_token_bytes, const std::vector<uint32_t>& unicode_table) {
+  np_text_build_opts o = text_build_opts(tokenizer, max_token_bytes);
+  o.unicode_table = unicode_table.data();
+  o.unicode_table_len = (int64_t)unicode_table.size();
+  return o;
+}
+
+inline std::vector<uint32_t> load_unicode_table(const std::string& path) {
+  std::vector<uint32_t> t;
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) throw Error(NP_ERR_INVALID_ARGUMENT, ("load_unicode_table: cannot open " + path).c_str());
+  uint32_t buf[4096];
+  size_t n;
+  while ((n = std::fread(buf, sizeof(uint32_t), 4096, f)) > 0) t.insert(t.end(), buf, buf + n);
+  std::fclose(f);
+  return t;
+}
+
 // The index of the documents the device reproduces.  A non-empty fallback_docs means the arrays lack those documents: the
 // caller tokenises them and calls the overload below (nothing is dropped silently: the list is part of the result).
 inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, Tokenizer tokenizer = Tokenizer::Unicode61,
@@ -1681,12 +1704,39 @@ inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, To
 }
 
 // ... with the caller's instances for the fallback documents: tokenize(fallback_docs) is called once, when the list is not empty.
+namespace detail {
+template <class Tokenize>
+inline BuiltTextIndex build_text_index_with(const std::vector<std::string>& texts, const np_text_build_opts& o, Tokenize&& tokenize,
+                                            int device);
+}
 template <class Tokenize>
 inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, Tokenizer tokenizer, Tokenize&& tokenize,
                                        int device = 0, int32_t max_token_bytes = 0) {
+  return detail::build_text_index_with(texts, text_build_opts(tokenizer, max_token_bytes), tokenize, device);
+}
+
+// ... in UTF-8 mode (see text_build_opts): fallback_docs then lists only malformed text, code points beyond the table and
+// overlong tokens.
+inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, const std::vector<uint32_t>& unicode_table,
+                                       Tokenizer tokenizer = Tokenizer::Unicode61, int device = 0, int32_t max_token_bytes = 0) {
   BuiltTextIndex r;
   detail::TextBuildHandle b;
-  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), device, &r);
+  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes, unicode_table), device, &r);
+  detail::text_build_finish(b, &r);
+  return r;
+}
+template <class Tokenize>
+inline BuiltTextIndex build_text_index(const std::vector<std::string>& texts, const std::vector<uint32_t>& unicode_table,
+                                       Tokenizer tokenizer, Tokenize&& tokenize, int device = 0, int32_t max_token_bytes = 0) {
+  return detail::build_text_index_with(texts, text_build_opts(tokenizer, max_token_bytes, unicode_table), tokenize, device);
+}
+
+template <class Tokenize>
+inline BuiltTextIndex detail::build_text_index_with(const std::vector<std::string>& texts, const np_text_build_opts& o,
+                                                    Tokenize&& tokenize, int device) {
+  BuiltTextIndex r;
+  detail::TextBuildHandle b;
+  detail::text_build_start(b, texts, o, device, &r);
   if (!r.fallback_docs.empty()) {
     const TextInstances inst = tokenize(r.fallback_docs);
     std::vector<int64_t> tbo(inst.terms.size() + 1, 0);
@@ -1764,8 +1814,8 @@ inline void text_update_plan(int64_t n_old, const TextUpdate& u, std::vector<int
 }
 
 template <class AddFallback>
-inline UpdatedTextIndex text_update_run(const BuiltTextIndex& base, const TextUpdate& u, Tokenizer tokenizer, int device,
-                                        int32_t max_token_bytes, AddFallback&& add_fallback) {
+inline UpdatedTextIndex text_update_run(const BuiltTextIndex& base, const TextUpdate& u, const np_text_build_opts& opts, int device,
+                                        AddFallback&& add_fallback) {
   if (base.term_offsets.size() != base.terms.size() + 1)
     throw Error(NP_ERR_INVALID_ARGUMENT, "update_text_index: base.term_offsets does not have one entry per term and one more");
   std::vector<int64_t> remap, delta_ids;
@@ -1785,7 +1835,7 @@ inline UpdatedTextIndex text_update_run(const BuiltTextIndex& base, const TextUp
   UpdatedTextIndex r;
   TextBuildHandle batch, merged;
   if (!texts.empty()) {
-    text_build_start(batch, texts, text_build_opts(tokenizer, max_token_bytes), device, &r);
+    text_build_start(batch, texts, opts, device, &r);
     add_fallback(batch, r);
     check(np_hip_text_build_sizes(batch.h, nullptr, nullptr, nullptr, nullptr));
   }
@@ -1814,13 +1864,22 @@ inline void text_build_add_fallback(TextBuildHandle& b, const BuiltTextIndex& r,
 
 // The batch must be text the device reproduces: a fallback document in it is an error here (nothing is dropped silently);
 // the overload below takes the caller's instances for them.
+namespace detail {
+inline void text_update_no_fallback(TextBuildHandle&, const BuiltTextIndex& r) {
+  if (!r.fallback_docs.empty())
+    throw Error(NP_ERR_INVALID_ARGUMENT, ("update_text_index: batch document " + std::to_string(r.fallback_docs[0]) +
+                                          " is not reproduced on the device and no tokenize was given").c_str());
+}
+}  // namespace detail
 inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const TextUpdate& update, Tokenizer tokenizer = Tokenizer::Unicode61,
                                           int device = 0, int32_t max_token_bytes = 0) {
-  return detail::text_update_run(base, update, tokenizer, device, max_token_bytes, [](detail::TextBuildHandle&, const BuiltTextIndex& r) {
-    if (!r.fallback_docs.empty())
-      throw Error(NP_ERR_INVALID_ARGUMENT, ("update_text_index: batch document " + std::to_string(r.fallback_docs[0]) +
-                                            " is not reproduced on the device and no tokenize was given").c_str());
-  });
+  return detail::text_update_run(base, update, text_build_opts(tokenizer, max_token_bytes), device, detail::text_update_no_fallback);
+}
+// ... the batch tokenised in UTF-8 mode (see text_build_opts)
+inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const TextUpdate& update, const std::vector<uint32_t>& unicode_table,
+                                          Tokenizer tokenizer = Tokenizer::Unicode61, int device = 0, int32_t max_token_bytes = 0) {
+  return detail::text_update_run(base, update, text_build_opts(tokenizer, max_token_bytes, unicode_table), device,
+                                 detail::text_update_no_fallback);
 }
 
 // ... tokenize(fallback_docs) is called once when the batch has fallback documents; the ids index the batch (the
@@ -1828,7 +1887,13 @@ inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const Text
 template <class Tokenize>
 inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const TextUpdate& update, Tokenizer tokenizer, Tokenize&& tokenize,
                                           int device = 0, int32_t max_token_bytes = 0) {
-  return detail::text_update_run(base, update, tokenizer, device, max_token_bytes,
+  return detail::text_update_run(base, update, text_build_opts(tokenizer, max_token_bytes), device,
+                                 [&](detail::TextBuildHandle& b, const BuiltTextIndex& r) { detail::text_build_add_fallback(b, r, tokenize); });
+}
+template <class Tokenize>
+inline UpdatedTextIndex update_text_index(const BuiltTextIndex& base, const TextUpdate& update, const std::vector<uint32_t>& unicode_table,
+                                          Tokenizer tokenizer, Tokenize&& tokenize, int device = 0, int32_t max_token_bytes = 0) {
+  return detail::text_update_run(base, update, text_build_opts(tokenizer, max_token_bytes, unicode_table), device,
                                  [&](detail::TextBuildHandle& b, const BuiltTextIndex& r) { detail::text_build_add_fallback(b, r, tokenize); });
 }
 
@@ -1861,8 +1926,8 @@ inline void text_install(MmapIndex& ix, TextBuildHandle& b, ResidentTextIndex* r
 
 // np_hip_index_text_merge of the handle's keyword index (whose vocabulary is cur.terms) with the update's batch
 template <class AddFallback>
-inline void text_merge_resident(const MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& u, Tokenizer tokenizer,
-                                int32_t max_token_bytes, AddFallback&& add_fallback, TextBuildHandle* merged, ResidentTextIndex* r) {
+inline void text_merge_resident(const MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& u, const np_text_build_opts& opts,
+                                AddFallback&& add_fallback, TextBuildHandle* merged, ResidentTextIndex* r) {
   int64_t have = 0;
   check(np_hip_index_text_sizes(ix.handle(), &have, nullptr, nullptr, nullptr, nullptr));
   if (have != (int64_t)cur.terms.size())
@@ -1879,7 +1944,7 @@ inline void text_merge_resident(const MmapIndex& ix, const ResidentTextIndex& cu
   TextBuildHandle batch;
   if (!texts.empty()) {
     BuiltTextIndex built;
-    text_build_start(batch, texts, text_build_opts(tokenizer, max_token_bytes), ix.info().device, &built);
+    text_build_start(batch, texts, opts, ix.info().device, &built);
     add_fallback(batch, built);
     check(np_hip_text_build_sizes(batch.h, nullptr, nullptr, nullptr, nullptr));
     r->fallback_docs = built.fallback_docs;
@@ -1900,12 +1965,40 @@ inline void text_no_fallback(TextBuildHandle&, const BuiltTextIndex& r) {
 
 // build_text_index whose result stays in HBM and becomes the handle's keyword index: build -> (fallback -> add) -> sizes ->
 // np_hip_index_set_text_build.  Only the vocabulary is fetched.  Searches beside the call go on; no lock is needed.
+namespace detail {
+inline ResidentTextIndex build_text_resident_with(MmapIndex& ix, const std::vector<std::string>& texts, const np_text_build_opts& o);
+template <class Tokenize>
+inline ResidentTextIndex build_text_resident_with(MmapIndex& ix, const std::vector<std::string>& texts, const np_text_build_opts& o,
+                                                  Tokenize&& tokenize) {
+  ResidentTextIndex r;
+  BuiltTextIndex built;
+  TextBuildHandle b;
+  text_build_start(b, texts, o, ix.info().device, &built);
+  text_build_add_fallback(b, built, tokenize);
+  r.report = built.report;
+  r.fallback_docs = built.fallback_docs;
+  text_install(ix, b, &r);
+  return r;
+}
+// true for what may stand where update_text_resident takes its `step`: anything but a unicode_table, so that a table the
+// caller holds as a plain (non-const) vector selects the table overloads and is never deduced as the step
+template <class T>
+using is_step = std::integral_constant<bool, !std::is_same<typename std::decay<T>::type, std::vector<uint32_t>>::value>;
+}
 inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<std::string>& texts, Tokenizer tokenizer = Tokenizer::Unicode61,
                                              int32_t max_token_bytes = 0) {
+  return detail::build_text_resident_with(ix, texts, text_build_opts(tokenizer, max_token_bytes));
+}
+// ... in UTF-8 mode (see text_build_opts)
+inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<std::string>& texts, const std::vector<uint32_t>& unicode_table,
+                                             Tokenizer tokenizer = Tokenizer::Unicode61, int32_t max_token_bytes = 0) {
+  return detail::build_text_resident_with(ix, texts, text_build_opts(tokenizer, max_token_bytes, unicode_table));
+}
+inline ResidentTextIndex detail::build_text_resident_with(MmapIndex& ix, const std::vector<std::string>& texts, const np_text_build_opts& o) {
   ResidentTextIndex r;
   BuiltTextIndex built;
   detail::TextBuildHandle b;
-  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), ix.info().device, &built);
+  detail::text_build_start(b, texts, o, ix.info().device, &built);
   if (!built.fallback_docs.empty())
     throw Error(NP_ERR_INVALID_ARGUMENT, ("build_text_resident: document " + std::to_string(built.fallback_docs[0]) +
                                           " is not reproduced on the device and no tokenize was given").c_str());
@@ -1916,15 +2009,13 @@ inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<st
 template <class Tokenize>
 inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<std::string>& texts, Tokenizer tokenizer, Tokenize&& tokenize,
                                              int32_t max_token_bytes = 0) {
-  ResidentTextIndex r;
-  BuiltTextIndex built;
-  detail::TextBuildHandle b;
-  detail::text_build_start(b, texts, text_build_opts(tokenizer, max_token_bytes), ix.info().device, &built);
-  detail::text_build_add_fallback(b, built, tokenize);
-  r.report = built.report;
-  r.fallback_docs = built.fallback_docs;
-  detail::text_install(ix, b, &r);
-  return r;
+  return detail::build_text_resident_with(ix, texts, text_build_opts(tokenizer, max_token_bytes), tokenize);
+}
+// ... in UTF-8 mode with the caller's tokenizer for what still falls back (code points beyond the table, overlong tokens)
+template <class Tokenize>
+inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<std::string>& texts, const std::vector<uint32_t>& unicode_table,
+                                             Tokenizer tokenizer, Tokenize&& tokenize, int32_t max_token_bytes = 0) {
+  return detail::build_text_resident_with(ix, texts, text_build_opts(tokenizer, max_token_bytes, unicode_table), tokenize);
 }
 
 // The handle's keyword index updated from itself: the batch is built on the device, np_hip_index_text_merge reads the base
@@ -1932,12 +2023,12 @@ inline ResidentTextIndex build_text_resident(MmapIndex& ix, const std::vector<st
 // vocabulary and row count are the base's).  `step` runs between the merge and the install: the vector-index call that
 // drops the handle's keyword index (append_arrays with rows, remove_ids with keep_attachments, expand_arrays with rows), so
 // that the order is merge, vector call, install.  If it throws, the handle keeps its old keyword index and the result is freed.
-template <class Step>
+template <class Step, class = typename std::enable_if<detail::is_step<Step>::value>::type>
 inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update, Step&& step,
                                               Tokenizer tokenizer = Tokenizer::Unicode61, int32_t max_token_bytes = 0) {
   ResidentTextIndex r;
   detail::TextBuildHandle merged;
-  detail::text_merge_resident(ix, cur, update, tokenizer, max_token_bytes, detail::text_no_fallback, &merged, &r);
+  detail::text_merge_resident(ix, cur, update, text_build_opts(tokenizer, max_token_bytes), detail::text_no_fallback, &merged, &r);
   step();
   detail::text_install(ix, merged, &r);
   return r;
@@ -1946,14 +2037,47 @@ inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextI
                                               Tokenizer tokenizer = Tokenizer::Unicode61, int32_t max_token_bytes = 0) {
   return update_text_resident(ix, cur, update, [] {}, tokenizer, max_token_bytes);
 }
+// ... the batch tokenised in UTF-8 mode (see text_build_opts)
+template <class Step>
+inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update,
+                                              const std::vector<uint32_t>& unicode_table, Step&& step,
+                                              Tokenizer tokenizer = Tokenizer::Unicode61, int32_t max_token_bytes = 0) {
+  ResidentTextIndex r;
+  detail::TextBuildHandle merged;
+  detail::text_merge_resident(ix, cur, update, text_build_opts(tokenizer, max_token_bytes, unicode_table), detail::text_no_fallback,
+                              &merged, &r);
+  step();
+  detail::text_install(ix, merged, &r);
+  return r;
+}
+inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update,
+                                              const std::vector<uint32_t>& unicode_table, Tokenizer tokenizer = Tokenizer::Unicode61,
+                                              int32_t max_token_bytes = 0) {
+  return update_text_resident(ix, cur, update, unicode_table, [] {}, tokenizer, max_token_bytes);
+}
 // ... tokenize(fallback_docs) is called once when the batch has fallback documents (a byte >= 0x80, ...); the ids index the
 // batch (the replacements in id order, then new_texts), as in update_text_index.
-template <class Step, class Tokenize, class = typename std::enable_if<!std::is_integral<typename std::decay<Tokenize>::type>::value>::type>
+template <class Step, class Tokenize,
+          class = typename std::enable_if<detail::is_step<Step>::value && !std::is_integral<typename std::decay<Tokenize>::type>::value>::type>
 inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update, Step&& step,
                                               Tokenizer tokenizer, Tokenize&& tokenize, int32_t max_token_bytes = 0) {
   ResidentTextIndex r;
   detail::TextBuildHandle merged;
-  detail::text_merge_resident(ix, cur, update, tokenizer, max_token_bytes,
+  detail::text_merge_resident(ix, cur, update, text_build_opts(tokenizer, max_token_bytes),
+                              [&](detail::TextBuildHandle& b, const BuiltTextIndex& built) { detail::text_build_add_fallback(b, built, tokenize); },
+                              &merged, &r);
+  step();
+  detail::text_install(ix, merged, &r);
+  return r;
+}
+// ... in UTF-8 mode with the caller's tokenizer for what still falls back
+template <class Step, class Tokenize, class = typename std::enable_if<!std::is_integral<typename std::decay<Tokenize>::type>::value>::type>
+inline ResidentTextIndex update_text_resident(MmapIndex& ix, const ResidentTextIndex& cur, const TextUpdate& update,
+                                              const std::vector<uint32_t>& unicode_table, Step&& step, Tokenizer tokenizer,
+                                              Tokenize&& tokenize, int32_t max_token_bytes = 0) {
+  ResidentTextIndex r;
+  detail::TextBuildHandle merged;
+  detail::text_merge_resident(ix, cur, update, text_build_opts(tokenizer, max_token_bytes, unicode_table),
                               [&](detail::TextBuildHandle& b, const BuiltTextIndex& built) { detail::text_build_add_fallback(b, built, tokenize); },
                               &merged, &r);
   step();

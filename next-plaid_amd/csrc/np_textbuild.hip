@@ -1,5 +1,6 @@
 // np_textbuild.hip -- the keyword index built on the device from raw document text (include/nextplaid_hip.h, "Building the
-// keyword index on the device").  Stages: classify + count, scan, emit, term numbering, a stable LSD
+// keyword index on the device"): unicode61 over ASCII, or -- with the caller's table of SQLite's
+// classes and folds -- over UTF-8, and trigram.  Stages: classify + count, scan, emit, term numbering, a stable LSD
 // radix sort by term id, gather.  Every stage is a sequence of launches: no workgroup waits for another inside a launch,
 // nothing a launch writes is read by another workgroup of that launch except a term-table slot (one u32 that goes from
 // empty to an instance index once, by atomicCAS, and only ever names bytes of the immutable text), and every position of
@@ -107,6 +108,137 @@ __global__ __launch_bounds__(256) void tb_walk_unicode(const uint8_t* __restrict
     ntok += __shfl(incf, 63);
     open = max(open, __shfl(inc, 63));
     carry = (__shfl(m, tile_lanes - 1) >> 15) & 1u;
+    if (!EMIT && __any(bad)) break;
+  }
+  if (!EMIT) {
+    const bool fall = __any(bad);
+    if (lane == 0) count[doc] = fall ? 0u : ntok, fb[doc] = fall ? 1u : 0u;
+  }
+}
+
+// ---- unicode61 over UTF-8: the same walk, a class per code point out of the caller's table ------------------------------
+// Every byte takes the class of the code point it belongs to.  A lane decodes the sequences whose lead byte lies in its
+// line -- out of a window of 20 bytes, the line and the four behind it, so a sequence may run into the next lane's line or
+// the next tile -- and hands the up to three bits that leave its line to the next lane.  A mark takes the token bit of the
+// byte before it: inside a lane one carry-propagating add resolves every run of marks, and a lane's last bit is 0, 1 or, for
+// a lane of marks alone, "what came in", so one scan of {0, 1, pass} over the lanes and one carried bit per tile give every
+// lane its incoming bit.  Starts and ends then come out of tb_walk_unicode's mask arithmetic; a token's length is its raw
+// bytes, marks included.  Bytes below 0x80 take the ASCII rule without a table read (the host checked entries 0..127).
+constexpr uint32_t TB_PASS = 2u;
+
+// bit k of the result: byte k is a token byte -- tok | the marks that a token bit (or `in`, before bit 0) runs into
+__device__ __forceinline__ uint32_t tb_resolve_marks(uint32_t tok, uint32_t mark, uint32_t in) {
+  const uint32_t hit = ((tok << 1) | in) & mark;   // the first mark of every run that continues a token
+  return tok | (mark & ~(mark + hit));             // the add carries through exactly those runs
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(256) void tb_walk_utf8(const uint8_t* __restrict__ text, const int64_t* __restrict__ offs,
+                                                     int64_t n_docs, int tile_lanes, int max_tok,
+                                                     const uint32_t* __restrict__ utab, uint32_t utab_len, uint32_t* count,
+                                                     uint32_t* fb, const int64_t* __restrict__ first, uint32_t* i_doc,
+                                                     uint32_t* i_rel, uint32_t* i_len) {
+  const int lane = threadIdx.x & 63;
+  const int64_t doc = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (doc >= n_docs) return;   // wave-uniform, as every exit and trip count below
+  const int64_t b = offs[doc], e = offs[doc + 1];
+  if (EMIT) {
+    if (fb[doc] || count[doc] == 0) return;
+  } else if (b == e) {
+    if (lane == 0) count[doc] = 0, fb[doc] = 0;
+    return;
+  }
+  const int64_t base = EMIT ? first[doc] : 0;
+  const int64_t len = e - b;
+  const int64_t r0 = (b & ~(int64_t)15) - b;
+  int open = TB_NONE;
+  uint32_t carry = 0, ntok = 0;   // the token bit of the previous tile's last byte; tokens ended so far
+  uint32_t carry_spill = 0;       // what the previous tile's last lane hands on: token, mark and covered bits, 4 each
+  bool bad = false;
+  for (int64_t rt = r0; rt <= len; rt += (int64_t)tile_lanes * 16) {
+    const int64_t r = rt + lane * 16;
+    uint32_t tok = 0, mark = 0, cover = 0, cont = 0;   // 20 bits each: bit k is byte r + k; cover = bytes behind a lead
+    if (lane < tile_lanes && r <= len) {
+      const uint4 v = *reinterpret_cast<const uint4*>(text + b + r);   // at most 19 bytes past the text: it is padded
+      const uint32_t w[5] = {v.x, v.y, v.z, v.w, *reinterpret_cast<const uint32_t*>(text + b + r + 16)};
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const uint32_t c = tb_byte(w, k);
+        if (r + k < 0 || r + k >= len) continue;
+        if (c < 0x80u) {
+          tok |= tb_tok(c) ? (1u << k) : 0u;
+        } else if (c < 0xC0u) {
+          cont |= 1u << k;
+        } else {
+          const uint32_t c1 = tb_byte(w, k + 1), c2 = tb_byte(w, k + 2), c3 = tb_byte(w, k + 3);
+          const int n = c < 0xE0u ? 2 : c < 0xF0u ? 3 : 4;
+          bool ok = (c1 & 0xC0u) == 0x80u && r + k + n <= len;   // the next document's bytes never complete a sequence
+          uint32_t cp;
+          if (n == 2) {
+            cp = ((c & 0x1Fu) << 6) | (c1 & 0x3Fu);
+            ok = ok && cp >= 0x80u;
+          } else if (n == 3) {
+            cp = ((c & 0x0Fu) << 12) | ((c1 & 0x3Fu) << 6) | (c2 & 0x3Fu);
+            ok = ok && (c2 & 0xC0u) == 0x80u && cp >= 0x800u && cp - 0xD800u >= 0x800u;
+          } else {
+            cp = ((c & 0x07u) << 18) | ((c1 & 0x3Fu) << 12) | ((c2 & 0x3Fu) << 6) | (c3 & 0x3Fu);
+            ok = ok && c < 0xF8u && (c2 & 0xC0u) == 0x80u && (c3 & 0xC0u) == 0x80u && cp - 0x10000u < 0x100000u;
+          }
+          ok = ok && cp < utab_len;
+          if (ok) {
+            const uint32_t cls = utab[cp] >> 30, bits = ((1u << n) - 1u) << k;
+            tok |= cls == 1u ? bits : 0u;
+            mark |= cls == 2u ? bits : 0u;
+            cover |= bits & ~(1u << k);
+          } else {
+            bad = true;
+          }
+        }
+      }
+    }
+    const uint32_t spill = (tok >> 16) | ((mark >> 16) << 4) | ((cover >> 16) << 8);
+    const uint32_t ps = __shfl_up(spill, 1);
+    const uint32_t from = lane == 0 ? carry_spill : (lane < tile_lanes ? ps : 0u);
+    tok = (tok & 0xFFFFu) | (from & 15u);
+    mark = (mark & 0xFFFFu) | ((from >> 4) & 15u);
+    cover = (cover & 0xFFFFu) | ((from >> 8) & 15u);
+    bad |= (cont & ~cover) != 0;   // a continuation byte that no lead covers
+    // the token bit behind this lane's line as a function of the one before it: 0, 1 or pass
+    uint32_t out = mark == 0xFFFFu ? TB_PASS : (tb_resolve_marks(tok, mark, 0u) >> 15) & 1u;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t o = __shfl_up(out, d);
+      if (lane >= d && out == TB_PASS) out = o;
+    }
+    const uint32_t po = __shfl_up(out, 1);
+    const uint32_t prevc = lane == 0 ? carry : (lane < tile_lanes ? (po == TB_PASS ? carry : po) : 0u);
+    const uint32_t m = tb_resolve_marks(tok, mark, prevc) & 0xFFFFu;
+    const uint32_t sh = ((m << 1) | prevc) & 0xFFFFu;
+    const uint32_t s = m & ~sh, f = ~m & sh;
+    const int ls = s ? (int)r + (31 - __clz(s)) : TB_NONE;
+    const int inc = tb_wave_incl_max(ls, lane);
+    int exc = __shfl_up(inc, 1);
+    exc = lane == 0 ? open : max(exc, open);
+    const uint32_t nf = __popc(f);
+    const uint32_t incf = tb_wave_incl_sum(nf, lane);
+    uint32_t k = ntok + incf - nf;
+    for (uint32_t ff = f; ff; ff &= ff - 1, ++k) {
+      const int j = __ffs(ff) - 1;
+      const uint32_t sj = s & ((1u << j) - 1u);
+      const int st = sj ? (int)r + (31 - __clz(sj)) : exc;
+      const int tl = (int)r + j - st;
+      bad |= tl > max_tok;
+      if (EMIT) {
+        const int64_t n = base + k;
+        i_doc[n] = (uint32_t)doc;
+        i_rel[n] = (uint32_t)st;
+        i_len[n] = (uint32_t)tl;
+      }
+    }
+    ntok += __shfl(incf, 63);
+    open = max(open, __shfl(inc, 63));
+    carry = (__shfl(m, tile_lanes - 1) >> 15) & 1u;
+    carry_spill = __shfl(spill, tile_lanes - 1);
     if (!EMIT && __any(bad)) break;
   }
   if (!EMIT) {
@@ -224,6 +356,70 @@ __global__ __launch_bounds__(256) void tb_insert(const uint8_t* __restrict__ tex
         slot_of[n] = slot;
         return;
       }
+    }
+  }
+  slot_of[n] = TB_EMPTY;
+  atomicAdd(overflow, 1u);
+}
+
+// The next folded code point of the token p[0, len) from byte i on, marks skipped; TB_EMPTY behind the last.  The token
+// passed the walk: its sequences are well formed and inside the table, and each is a token character or a mark.
+__device__ __forceinline__ uint32_t tb_next_folded(const uint8_t* p, uint32_t& i, uint32_t len, const uint32_t* __restrict__ utab) {
+  while (i < len) {
+    const uint32_t c = p[i];
+    if (c < 0x80u) {
+      ++i;
+      return tb_fold(c);
+    }
+    uint32_t cp;
+    if (c < 0xE0u) cp = ((c & 0x1Fu) << 6) | (p[i + 1] & 0x3Fu), i += 2;
+    else if (c < 0xF0u) cp = ((c & 0x0Fu) << 12) | ((p[i + 1] & 0x3Fu) << 6) | (p[i + 2] & 0x3Fu), i += 3;
+    else cp = ((c & 0x07u) << 18) | ((p[i + 1] & 0x3Fu) << 12) | ((p[i + 2] & 0x3Fu) << 6) | (p[i + 3] & 0x3Fu), i += 4;
+    const uint32_t e = utab[cp];
+    if ((e >> 30) == 1u) return e & 0x1FFFFFu;
+  }
+  return TB_EMPTY;
+}
+
+// tb_insert over folded code points: two instances of different raw lengths may be one term (a precomposed letter, the
+// plain one, the plain one and a mark), so a taken slot is compared stream against stream, never by length first.
+__global__ __launch_bounds__(256) void tb_insert_utf8(const uint8_t* __restrict__ text, const int64_t* __restrict__ offs,
+                                                       const uint32_t* __restrict__ i_doc, const uint32_t* __restrict__ i_rel,
+                                                       const uint32_t* __restrict__ i_len, int64_t n_inst,
+                                                       const uint32_t* __restrict__ utab, uint32_t* tab, uint32_t mask,
+                                                       uint32_t* slot_of, uint32_t* overflow) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= n_inst) return;
+  const uint8_t* p = text + offs[i_doc[n]] + i_rel[n];
+  const uint32_t len = i_len[n];
+  uint32_t h = 2166136261u;
+  for (uint32_t i = 0;;) {
+    const uint32_t cp = tb_next_folded(p, i, len, utab);
+    if (cp == TB_EMPTY) break;
+    h = (h ^ cp) * 16777619u;
+  }
+  h ^= h >> 15;
+  h *= 0x2C1B3C6Du;
+  h ^= h >> 12;
+  uint32_t slot = h & mask;
+  const uint32_t probes = mask < (uint32_t)TB_MAX_PROBES ? mask + 1u : (uint32_t)TB_MAX_PROBES;
+  for (uint32_t t = 0; t < probes; ++t, slot = (slot + 1u) & mask) {
+    uint32_t old = __hip_atomic_load(&tab[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == TB_EMPTY) old = atomicCAS(&tab[slot], TB_EMPTY, (uint32_t)n);
+    if (old == TB_EMPTY) {
+      slot_of[n] = slot;
+      return;
+    }
+    const uint8_t* q = text + offs[i_doc[old]] + i_rel[old];
+    const uint32_t qlen = i_len[old];
+    uint32_t i = 0, j = 0, a, c;
+    do {
+      a = tb_next_folded(p, i, len, utab);
+      c = tb_next_folded(q, j, qlen, utab);
+    } while (a == c && a != TB_EMPTY);
+    if (a == c) {
+      slot_of[n] = slot;
+      return;
     }
   }
   slot_of[n] = TB_EMPTY;
@@ -360,6 +556,8 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
                     np_text_build* B, np_text_build_report* rep) {
   const auto t_all = Clock::now();
   const bool unicode = plan.tokenizer == NP_TOK_UNICODE61;
+  const bool utf8 = unicode && plan.unicode_table != nullptr;
+  const int64_t utab_len = utf8 ? plan.unicode_table_len : 0;
   const int64_t N = plan.text_bytes;
   const int tile_lanes = plan.tile_bytes / 16;
   char why[256];
@@ -375,10 +573,10 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
     NP_HIP(hipMemGetInfo(&free_b, &total_b));
     W.limit = plan.workspace_bytes > 0 ? plan.workspace_bytes : (int64_t)(free_b - free_b / 16);
   }
-  if (textbuild_bytes_docs(N, n_docs) > W.limit) {
+  if (textbuild_bytes_docs(N, n_docs, utab_len) > W.limit) {
     set_error("np_hip_text_build: the workspace of %lld bytes does not hold the text and the per-document arrays (%lld bytes; a "
               "whole-corpus sort: build in document ranges and merge them, np_hip_text_build_merge)",
-              (long long)W.limit, (long long)textbuild_bytes_docs(N, n_docs));
+              (long long)W.limit, (long long)textbuild_bytes_docs(N, n_docs, utab_len));
     return NP_ERR_OUT_OF_MEMORY;
   }
   TbStream S;
@@ -392,7 +590,7 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
   auto t0 = Clock::now();
   DevPtr<uint8_t> d_text;
   DevPtr<int64_t> d_offs, d_first;
-  DevPtr<uint32_t> d_count, d_fb;
+  DevPtr<uint32_t> d_count, d_fb, d_utab;
   DevPtr<uint64_t> d_sums;
   int64_t sums_cap = 0;
   auto need_sums = [&](int64_t n) -> int {
@@ -409,6 +607,10 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
   NP_TRY(W.take(d_count, n_docs + 1, "the documents' token counts"));
   NP_TRY(W.take(d_fb, n_docs + 1, "the fallback flags"));
   NP_TRY(need_sums(n_docs + 1));
+  if (utf8) {
+    NP_TRY(W.take(d_utab, utab_len, "the unicode61 table"));
+    NP_HIP(hipMemcpyAsync(d_utab.get(), plan.unicode_table, (size_t)utab_len * 4, hipMemcpyHostToDevice, st));
+  }
   if (N > 0) NP_HIP(hipMemcpyAsync(d_text.get(), bytes, (size_t)N, hipMemcpyHostToDevice, st));
   NP_HIP(hipMemsetAsync(d_text.get() + N, 0, (size_t)NP_TB_TEXT_PAD, st));
   NP_HIP(hipMemcpyAsync(d_offs.get(), offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, st));
@@ -419,7 +621,12 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
   t0 = Clock::now();
   const unsigned doc_grid = grid_of(n_docs, 4);
   if (n_docs > 0) {
-    if (unicode)
+    if (utf8)
+      hipLaunchKernelGGL(tb_walk_utf8<false>, dim3(doc_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(),
+                         (const int64_t*)d_offs.get(), n_docs, tile_lanes, plan.max_token, (const uint32_t*)d_utab.get(),
+                         (uint32_t)utab_len, d_count.get(), d_fb.get(), (const int64_t*)nullptr, (uint32_t*)nullptr,
+                         (uint32_t*)nullptr, (uint32_t*)nullptr);
+    else if (unicode)
       hipLaunchKernelGGL(tb_walk_unicode<false>, dim3(doc_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(),
                          (const int64_t*)d_offs.get(), n_docs, tile_lanes, plan.max_token, d_count.get(), d_fb.get(),
                          (const int64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
@@ -444,7 +651,7 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
   }
   int32_t bits = unicode ? textbuild_hash_bits(n_inst, plan.hash_bits_forced) : 0;
   {
-    const int64_t need = textbuild_bytes_total(N, n_docs, n_inst, plan.tokenizer, bits);
+    const int64_t need = textbuild_bytes_total(N, n_docs, n_inst, plan.tokenizer, bits, utab_len);
     if (need > W.limit) {
       set_error("np_hip_text_build: the workspace of %lld bytes does not hold the call: %lld instances need %lld bytes (a "
                 "whole-corpus sort: build in document ranges and merge them, np_hip_text_build_merge)",
@@ -477,7 +684,13 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
     const int64_t bm_words = NP_TB_TRIGRAM_KEYS / 32;
     if (unicode) {
       NP_TRY(W.take(i_len, n_inst, "the instances' lengths"));
-      hipLaunchKernelGGL(tb_walk_unicode<true>, dim3(doc_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(),
+      if (utf8)
+        hipLaunchKernelGGL(tb_walk_utf8<true>, dim3(doc_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(),
+                           (const int64_t*)d_offs.get(), n_docs, tile_lanes, plan.max_token, (const uint32_t*)d_utab.get(),
+                           (uint32_t)utab_len, d_count.get(), d_fb.get(), (const int64_t*)d_first.get(), i_doc.get(), i_rel.get(),
+                           i_len.get());
+      else
+        hipLaunchKernelGGL(tb_walk_unicode<true>, dim3(doc_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(),
                          (const int64_t*)d_offs.get(), n_docs, tile_lanes, plan.max_token, d_count.get(), d_fb.get(),
                          (const int64_t*)d_first.get(), i_doc.get(), i_rel.get(), i_len.get());
     } else {
@@ -504,9 +717,15 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
         NP_TRY(W.take(d_tab, slots, "the term table"));
         NP_HIP(hipMemsetAsync(d_tab.get(), 0xFF, (size_t)slots * 4, st));
         NP_HIP(hipMemsetAsync(d_ovf.get(), 0, 4, st));
-        hipLaunchKernelGGL(tb_insert, dim3(inst_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(), (const int64_t*)d_offs.get(),
-                           (const uint32_t*)i_doc.get(), (const uint32_t*)i_rel.get(), (const uint32_t*)i_len.get(), n_inst,
-                           d_tab.get(), (uint32_t)(slots - 1), key_a.get(), d_ovf.get());
+        if (utf8)
+          hipLaunchKernelGGL(tb_insert_utf8, dim3(inst_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(),
+                             (const int64_t*)d_offs.get(), (const uint32_t*)i_doc.get(), (const uint32_t*)i_rel.get(),
+                             (const uint32_t*)i_len.get(), n_inst, (const uint32_t*)d_utab.get(), d_tab.get(), (uint32_t)(slots - 1),
+                             key_a.get(), d_ovf.get());
+        else
+          hipLaunchKernelGGL(tb_insert, dim3(inst_grid), dim3(256), 0, st, (const uint8_t*)d_text.get(), (const int64_t*)d_offs.get(),
+                             (const uint32_t*)i_doc.get(), (const uint32_t*)i_rel.get(), (const uint32_t*)i_len.get(), n_inst,
+                             d_tab.get(), (uint32_t)(slots - 1), key_a.get(), d_ovf.get());
         NP_HIP(hipGetLastError());
         uint32_t ovf = 0;
         NP_HIP(hipMemcpyAsync(&ovf, d_ovf.get(), 4, hipMemcpyDeviceToHost, st));
@@ -546,12 +765,19 @@ int text_build_impl(int device, const uint8_t* bytes, const int64_t* offsets, in
       // the folded strings, out of the caller's own copy of the text, in the compacted order; then fts5vocab's order
       std::vector<uint8_t> raw;
       std::vector<int64_t> raw_off((size_t)n_terms + 1, 0);
-      for (int64_t c = 0; c < n_terms; ++c) raw_off[(size_t)c + 1] = raw_off[(size_t)c] + h_len[(size_t)c];
-      raw.resize((size_t)raw_off[(size_t)n_terms]);
-      for (int64_t c = 0; c < n_terms; ++c) {
-        const uint8_t* p = bytes + offsets[h_doc[(size_t)c]] + h_rel[(size_t)c];
-        uint8_t* q = raw.data() + raw_off[(size_t)c];
-        for (uint32_t i = 0; i < h_len[(size_t)c]; ++i) q[i] = textbuild_fold(p[i]);
+      if (utf8) {   // through the caller's table, as the device compared them: marks go, a fold may change the length
+        for (int64_t c = 0; c < n_terms; ++c) {
+          textbuild_fold_utf8(bytes + offsets[h_doc[(size_t)c]] + h_rel[(size_t)c], h_len[(size_t)c], plan.unicode_table, &raw);
+          raw_off[(size_t)c + 1] = (int64_t)raw.size();
+        }
+      } else {
+        for (int64_t c = 0; c < n_terms; ++c) raw_off[(size_t)c + 1] = raw_off[(size_t)c] + h_len[(size_t)c];
+        raw.resize((size_t)raw_off[(size_t)n_terms]);
+        for (int64_t c = 0; c < n_terms; ++c) {
+          const uint8_t* p = bytes + offsets[h_doc[(size_t)c]] + h_rel[(size_t)c];
+          uint8_t* q = raw.data() + raw_off[(size_t)c];
+          for (uint32_t i = 0; i < h_len[(size_t)c]; ++i) q[i] = textbuild_fold(p[i]);
+        }
       }
       textbuild_sort_terms(raw.data(), raw_off.data(), n_terms, &rank, &B->term_bytes, &B->term_byte_offsets);
       NP_HIP(hipMemcpyAsync(d_rank.get(), rank.data(), (size_t)n_terms * 4, hipMemcpyHostToDevice, st));

@@ -22,15 +22,85 @@ constexpr int32_t NP_TB_HASH_BITS_MIN = 10, NP_TB_HASH_BITS_PLANNED_MAX = 26, NP
 constexpr int32_t NP_TB_SORT_CHUNK = 2048;         // keys per block of a radix pass (one wave, 32 rounds)
 constexpr int32_t NP_TB_SCAN_CHUNK = 2048;         // items per block of a scan launch
 
+constexpr int64_t NP_TB_PLANE = 65536;              // code points per plane of the unicode61 table; 1..17 planes
+constexpr int32_t NP_TB_UTF8_MAX_TOKEN = 21845;     // UTF-8 mode: 3/2 of it is SQLite's own cut at 32768
+constexpr uint32_t NP_TB_CLASS_SEP = 0, NP_TB_CLASS_TOKEN = 1, NP_TB_CLASS_MARK = 2;   // bits 30-31 of a table entry
+constexpr uint32_t NP_TB_FOLD_MASK = 0x1FFFFFu;     // bits 0-20: the folded code point
+
 struct TextBuildPlan {
   int32_t tokenizer = 0, max_token = 0, tile_bytes = 0, hash_bits_forced = 0;
   int64_t text_bytes = 0, workspace_bytes = 0;
+  const uint32_t* unicode_table = nullptr;   // UTF-8 mode when set (unicode61 only)
+  int64_t unicode_table_len = 0;
 };
 
 // A-Z -> a-z; every other byte as it is
 static inline uint8_t textbuild_fold(uint8_t c) { return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c; }
 static inline bool textbuild_token_char(uint8_t c) {
   return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z');
+}
+
+static inline int textbuild_utf8_len(uint32_t cp) { return cp < 0x80u ? 1 : cp < 0x800u ? 2 : cp < 0x10000u ? 3 : 4; }
+
+// The checks of np_text_build_opts.unicode_table, before any launch: what the kernels rely on (they index the table with
+// any code point below its length and take the ASCII rule for bytes below 0x80 without reading it).  One pass over the
+// whole table on EVERY call, 131 072 entries for two planes and 1.1 M for seventeen: a fixed cost per call that a small
+// batch pays in full.  It has not been measured on its own.
+inline int textbuild_check_table(const uint32_t* table, int64_t len, char* why, size_t why_len) {
+  if (len < NP_TB_PLANE || len > 17 * NP_TB_PLANE || len % NP_TB_PLANE != 0)
+    return snprintf(why, why_len, "unicode_table_len %lld is not a multiple of 65536 in 65536..%lld", (long long)len,
+                    (long long)(17 * NP_TB_PLANE)),
+           (int)NP_ERR_INVALID_ARGUMENT;
+  for (int64_t cp = 0; cp < len; ++cp) {
+    const uint32_t e = table[cp], cls = e >> 30, fold = e & NP_TB_FOLD_MASK;
+    if (cls > NP_TB_CLASS_MARK)
+      return snprintf(why, why_len, "unicode_table[0x%llX] has class %u; the classes are 0, 1 and 2", (long long)cp, cls),
+             (int)NP_ERR_INVALID_ARGUMENT;
+    if (fold >= 0x110000u || (fold >= 0xD800u && fold < 0xE000u))
+      return snprintf(why, why_len, "unicode_table[0x%llX] folds to 0x%X, which is no code point", (long long)cp, fold),
+             (int)NP_ERR_INVALID_ARGUMENT;
+    if (cp < 128) {
+      const uint32_t want = textbuild_token_char((uint8_t)cp) ? (NP_TB_CLASS_TOKEN << 30) | textbuild_fold((uint8_t)cp) : 0u;
+      if (e != want)
+        return snprintf(why, why_len, "unicode_table[0x%llX] is 0x%08X; the ASCII rule is 0x%08X", (long long)cp, e, want),
+               (int)NP_ERR_INVALID_ARGUMENT;
+    }
+    if (cls == NP_TB_CLASS_TOKEN && textbuild_utf8_len(fold) > textbuild_utf8_len((uint32_t)cp) + 1)
+      return snprintf(why, why_len, "unicode_table[0x%llX] folds to 0x%X, more than one byte longer in UTF-8", (long long)cp, fold),
+             (int)NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
+}
+
+// The term of a token in UTF-8 mode: the folds of its code points, marks skipped, as UTF-8.  The token passed the walk, so
+// every sequence is well formed and inside the table.  At most 3/2 of the raw length comes out.
+inline void textbuild_fold_utf8(const uint8_t* p, int64_t len, const uint32_t* table, std::vector<uint8_t>* out) {
+  for (int64_t i = 0; i < len;) {
+    const uint32_t c = p[i];
+    uint32_t cp;
+    if (c < 0x80u) cp = c, i += 1;
+    else if (c < 0xE0u) cp = ((c & 0x1Fu) << 6) | (p[i + 1] & 0x3Fu), i += 2;
+    else if (c < 0xF0u) cp = ((c & 0x0Fu) << 12) | ((p[i + 1] & 0x3Fu) << 6) | (p[i + 2] & 0x3Fu), i += 3;
+    else cp = ((c & 0x07u) << 18) | ((p[i + 1] & 0x3Fu) << 12) | ((p[i + 2] & 0x3Fu) << 6) | (p[i + 3] & 0x3Fu), i += 4;
+    const uint32_t e = table[cp];
+    if ((e >> 30) != NP_TB_CLASS_TOKEN) continue;
+    const uint32_t f = e & NP_TB_FOLD_MASK;
+    if (f < 0x80u) {
+      out->push_back((uint8_t)f);
+    } else if (f < 0x800u) {
+      out->push_back((uint8_t)(0xC0u | (f >> 6)));
+      out->push_back((uint8_t)(0x80u | (f & 0x3Fu)));
+    } else if (f < 0x10000u) {
+      out->push_back((uint8_t)(0xE0u | (f >> 12)));
+      out->push_back((uint8_t)(0x80u | ((f >> 6) & 0x3Fu)));
+      out->push_back((uint8_t)(0x80u | (f & 0x3Fu)));
+    } else {
+      out->push_back((uint8_t)(0xF0u | (f >> 18)));
+      out->push_back((uint8_t)(0x80u | ((f >> 12) & 0x3Fu)));
+      out->push_back((uint8_t)(0x80u | ((f >> 6) & 0x3Fu)));
+      out->push_back((uint8_t)(0x80u | (f & 0x3Fu)));
+    }
+  }
 }
 
 // The checks of np_hip_text_build, before any launch.  `why` (at least 200 bytes) names the argument.
@@ -54,6 +124,16 @@ inline int textbuild_check_args(const int64_t* offsets, int64_t n_docs, const np
   if (opts->workspace_bytes < 0)
     return snprintf(why, why_len, "workspace_bytes %lld is negative", (long long)opts->workspace_bytes),
            (int)NP_ERR_INVALID_ARGUMENT;
+  const bool utf8 = opts->tokenizer == NP_TOK_UNICODE61 && opts->unicode_table != nullptr;   // trigram ignores the table
+  if (utf8) {
+    const int rc = textbuild_check_table(opts->unicode_table, opts->unicode_table_len, why, why_len);
+    if (rc != NP_OK) return rc;
+    if (opts->max_token_bytes > NP_TB_UTF8_MAX_TOKEN)
+      return snprintf(why, why_len, "max_token_bytes %d outside 1..%d with a unicode_table (0 = %d): a longer token could fold "
+                                    "past SQLite's cut at %d", opts->max_token_bytes, NP_TB_UTF8_MAX_TOKEN, NP_TB_DEFAULT_MAX_TOKEN,
+                      NP_TEXT_BUILD_MAX_TOKEN_BYTES),
+             (int)NP_ERR_INVALID_ARGUMENT;
+  }
   if (n_docs < 0) return snprintf(why, why_len, "n_docs %lld is negative", (long long)n_docs), (int)NP_ERR_INVALID_ARGUMENT;
   if (n_docs > NP_TB_MAX_INSTANCES)
     return snprintf(why, why_len, "Shape error: n_docs %lld; the limit is 2^31 - 1", (long long)n_docs), (int)NP_ERR_SHAPE;
@@ -78,6 +158,8 @@ inline int textbuild_check_args(const int64_t* offsets, int64_t n_docs, const np
     plan->hash_bits_forced = opts->hash_bits;
     plan->text_bytes = offsets[n_docs];
     plan->workspace_bytes = opts->workspace_bytes;
+    plan->unicode_table = utf8 ? opts->unicode_table : nullptr;
+    plan->unicode_table_len = utf8 ? opts->unicode_table_len : 0;
   }
   return NP_OK;
 }
@@ -118,14 +200,15 @@ static inline int32_t textbuild_hash_bits(int64_t n_instances, int32_t forced) {
 static inline int64_t textbuild_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 static inline int64_t textbuild_scan_sums(int64_t n) { return (n + NP_TB_SCAN_CHUNK - 1) / NP_TB_SCAN_CHUNK + 1; }
 
-// device bytes of the first phase (text, offsets, per-document arrays) ...
-static inline int64_t textbuild_bytes_docs(int64_t text_bytes, int64_t n_docs) {
+// device bytes of the first phase (text, offsets, per-document arrays; UTF-8 mode: the table's device copy) ...
+static inline int64_t textbuild_bytes_docs(int64_t text_bytes, int64_t n_docs, int64_t table_len = 0) {
   return textbuild_up256(text_bytes + NP_TB_TEXT_PAD) + 2 * textbuild_up256((n_docs + 1) * 8) + 2 * textbuild_up256((n_docs + 1) * 4) +
-         textbuild_up256(textbuild_scan_sums(n_docs + 1) * 8) + 256;
+         textbuild_up256(textbuild_scan_sums(n_docs + 1) * 8) + 256 + (table_len > 0 ? textbuild_up256(table_len * 4) : 0);
 }
 // ... and of everything a call holds at its peak: per instance doc, offset, length, two key and two value arrays, then
 // inst_doc and inst_pos; the term table with its flags and ranks (trigram: bitmap, counts and prefix); the histograms
-static inline int64_t textbuild_bytes_total(int64_t text_bytes, int64_t n_docs, int64_t n_inst, int32_t tokenizer, int32_t hash_bits) {
+static inline int64_t textbuild_bytes_total(int64_t text_bytes, int64_t n_docs, int64_t n_inst, int32_t tokenizer, int32_t hash_bits,
+                                            int64_t table_len = 0) {
   const int64_t per_inst = 7 * textbuild_up256(n_inst * 4 + 4) + textbuild_up256(n_inst * 8 + 8) + textbuild_up256(n_inst * 4 + 4);
   const int64_t slots = tokenizer == NP_TOK_TRIGRAM ? NP_TB_TRIGRAM_KEYS / 32 : (int64_t)1 << hash_bits;
   const int64_t table = 3 * textbuild_up256(slots * 4 + 4) + textbuild_up256(textbuild_scan_sums(slots + 1) * 8);
@@ -133,7 +216,7 @@ static inline int64_t textbuild_bytes_total(int64_t text_bytes, int64_t n_docs, 
   const int64_t hist = textbuild_up256((256 * blocks + 1) * 4) + textbuild_up256(textbuild_scan_sums(256 * blocks + 1) * 8);
   const int64_t max_terms = std::min<int64_t>(n_inst, tokenizer == NP_TOK_TRIGRAM ? (int64_t)NP_TB_TRIGRAM_KEYS : slots);
   const int64_t terms = 5 * textbuild_up256(max_terms * 4 + 4) + textbuild_up256((max_terms + 1) * 8);   // their places, ranks, term_offsets
-  return textbuild_bytes_docs(text_bytes, n_docs) + per_inst + table + hist + terms;
+  return textbuild_bytes_docs(text_bytes, n_docs, table_len) + per_inst + table + hist + terms;
 }
 
 // ---- the vocabulary ------------------------------------------------------------------------------------------------------

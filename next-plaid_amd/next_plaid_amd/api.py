@@ -210,7 +210,8 @@ class np_text_index(C.Structure):
 
 class np_text_build_opts(C.Structure):
     _fields_ = [("tokenizer", C.c_int32), ("max_token_bytes", C.c_int32), ("workspace_bytes", C.c_int64),
-                ("hash_bits", C.c_int32), ("tile_bytes", C.c_int32), ("reserved", C.c_int64 * 3)]
+                ("hash_bits", C.c_int32), ("tile_bytes", C.c_int32), ("unicode_table", C.c_void_p),
+                ("unicode_table_len", C.c_int64), ("reserved", C.c_int64 * 1)]
 
 
 class np_text_build_report(C.Structure):
@@ -944,7 +945,8 @@ class AppendRows:
     """What MmapIndex.append / append_arrays take with rows=: the new documents' attachment rows.  `columns`: name -> the new
     entries, under exactly the names of the handle's columns (None where it has none); `groups`: one key per new document, as
     set_groups takes them (ready int32 ids where the handle's groups were set with n_groups=, then with `n_groups`; None
-    where the handle has no groups); `texts`: the new documents' text for the keyword index (None where it has none)."""
+    where the handle has no groups); `texts`: the new documents' text for the keyword index (None where it has none),
+    tokenised as the handle's text_utf8 / text_unicode_planes say (MmapIndex)."""
     columns: dict | None = None
     groups: object = None
     texts: object = None
@@ -1073,13 +1075,20 @@ def _docs(documents):
 
 
 def _text_build_open(L, doc_bytes, offsets, tokenizer, tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits,
-                     tile_bytes):
-    """np_hip_text_build and np_hip_text_build_add: (the build, the fallback ids, the report).  The caller frees the build."""
+                     tile_bytes, utf8=False, unicode_planes=2):
+    """np_hip_text_build and np_hip_text_build_add: (the build, the fallback ids, the report).  The caller frees the build.
+    utf8: opts->unicode_table is text.unicode61_table(unicode_planes), SQLite's rule probed from SQLite (the library reads
+    it during the call only); otherwise the table is NULL and the device reproduces ASCII text alone."""
     raw = np.ascontiguousarray(doc_bytes, np.uint8).reshape(-1)
     off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
     if off.size < 1:
         raise ValueError("offsets needs n_docs + 1 entries")
     o = np_text_build_opts(int(tokenizer), int(max_token_bytes), int(workspace_bytes), int(hash_bits), int(tile_bytes))
+    table = None
+    if utf8:
+        from . import text as T
+        table = T.unicode61_table(unicode_planes)
+        o.unicode_table, o.unicode_table_len = table.ctypes.data, table.size
     rep, h = np_text_build_report(), C.c_void_p()
     _check(L.np_hip_text_build(int(device), _ptr(raw) if raw.size else None, _ptr(off), off.size - 1, C.byref(o), C.byref(h),
                                C.byref(rep)))
@@ -1122,16 +1131,17 @@ def _text_build_read(L, h):
 
 
 def text_build(doc_bytes, offsets, tokenizer: int, tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0,
-               workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+               workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0, utf8: bool = False, unicode_planes: int = 2):
     """np_hip_text_build and the calls that follow it: the documents' UTF-8 bytes concatenated (u8 array) and offsets i64
     [n_docs + 1] -> a dict with term_bytes u8, term_byte_offsets / term_offsets i64 [n_terms + 1], inst_doc i64, inst_pos
     i32, n_rows, fallback_docs i64 (ascending) and the stage report.  tokenize_fallback(ids) is called once when the device
     hands documents back, and returns their instances as (term_bytes u8, term_byte_offsets i64, inst_term i32, inst_doc i64,
     inst_pos i32) sorted by (term, doc, pos) with the terms in memcmp order; without it a non-empty fallback list is an
-    error, never a silently smaller index."""
+    error, never a silently smaller index.  utf8=True is the library's UTF-8 mode with text.unicode61_table(unicode_planes)
+    (unicode61 only; trigram ignores it)."""
     L = lib()
     h, fb, rep = _text_build_open(L, doc_bytes, offsets, tokenizer, tokenize_fallback, device, max_token_bytes, workspace_bytes,
-                                  hash_bits, tile_bytes)
+                                  hash_bits, tile_bytes, utf8, unicode_planes)
     try:
         out = _text_build_read(L, h)
         out.update(fallback_docs=fb, report=rep.as_dict())
@@ -1142,13 +1152,14 @@ def text_build(doc_bytes, offsets, tokenizer: int, tokenize_fallback=None, devic
 
 def text_merge(base_terms, base_term_offsets, base_inst_doc, base_inst_pos, base_n_rows, remap, delta_ids, n_rows_out,
                doc_bytes=None, offsets=None, tokenizer: int = 0, tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0,
-               workspace_bytes: int = 0, merge_workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+               workspace_bytes: int = 0, merge_workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0,
+               utf8: bool = False, unicode_planes: int = 2):
     """np_hip_text_build_merge, the one caller of the entry: the keyword index of the table that results from a base index
     (its terms as byte strings in term order, and the np_text_index arrays), a verdict per old document (remap i64: -1 =
     removed, otherwise the new id) and a batch of new texts (doc_bytes / offsets as text_build takes them; offsets None = no
     batch) whose documents get delta_ids.  The batch is built on the device first (np_hip_text_build, the fallback documents
     added as in text_build) and merged where it lies.  Returns text_build's dict; `report` is the merge's, `build_report` the
-    batch's (None without a batch), fallback_docs index the batch."""
+    batch's (None without a batch), fallback_docs index the batch.  utf8 / unicode_planes: text_build's, for the batch."""
     L = lib()
     enc = [bytes(t) for t in base_terms]
     a_tbo = np.zeros(len(enc) + 1, np.int64)
@@ -1170,7 +1181,8 @@ def text_merge(base_terms, base_term_offsets, base_inst_doc, base_inst_pos, base
     d, fb, brep = C.c_void_p(), np.zeros(0, np.int64), None
     if offsets is not None:
         d, fb, brep = _text_build_open(L, doc_bytes if doc_bytes is not None else np.zeros(0, np.uint8), offsets, tokenizer,
-                                       tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits, tile_bytes)
+                                       tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits, tile_bytes,
+                                       utf8, unicode_planes)
     h = C.c_void_p()
     try:
         if d:
@@ -1202,7 +1214,8 @@ def _text_build_vocab(L, h):
 
 def text_merge_resident(index_handle, base_terms, remap, delta_ids, n_rows_out, doc_bytes=None, offsets=None, tokenizer: int = 0,
                         tokenize_fallback=None, device: int = 0, max_token_bytes: int = 0, workspace_bytes: int = 0,
-                        merge_workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0):
+                        merge_workspace_bytes: int = 0, hash_bits: int = 0, tile_bytes: int = 0, utf8: bool = False,
+                        unicode_planes: int = 2):
     """np_hip_index_text_merge, the one caller of the entry: text_merge whose base is the keyword index of the handle
     `index_handle`, read where it lies.  base_terms are the handle's terms as byte strings, in term order.  Returns (the
     result, a finalised device build that the caller installs with np_hip_index_set_text_build or frees; the merge's report
@@ -1225,7 +1238,8 @@ def text_merge_resident(index_handle, base_terms, remap, delta_ids, n_rows_out, 
     d, fb, brep = C.c_void_p(), np.zeros(0, np.int64), None
     if offsets is not None:
         d, fb, brep = _text_build_open(L, doc_bytes if doc_bytes is not None else np.zeros(0, np.uint8), offsets, tokenizer,
-                                       tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits, tile_bytes)
+                                       tokenize_fallback, device, max_token_bytes, workspace_bytes, hash_bits, tile_bytes,
+                                       utf8, unicode_planes)
     h = C.c_void_p()
     try:
         if d:
@@ -1495,6 +1509,12 @@ def _opts(device=0, shard_rank=0, shard_count=1, n_contexts=2, max_batch=64, max
 
 class MmapIndex:
     """Device-resident PLAID index; mirror of next_plaid::MmapIndex (index.rs:995-1312)."""
+
+    # How this handle tokenises text for its keyword index where a call has no argument of its own -- build_text /
+    # update_text with utf8=None, and the rows.texts of append / append_arrays / update_resident: True = UTF-8 on the
+    # device with text.unicode61_table(text_unicode_planes); False = ASCII on the device, the rest through SQLite.
+    text_utf8 = False
+    text_unicode_planes = 2
 
     def __init__(self, handle, path="", open_opts=None):
         self._h = handle
@@ -2193,7 +2213,8 @@ class MmapIndex:
         self.text = data
         _check(lib().np_hip_index_info(self._h, C.byref(self._info)))
 
-    def build_text(self, texts, tokenizer: str = "unicode61", max_token_bytes: int | None = None, resident: bool = False):
+    def build_text(self, texts, tokenizer: str = "unicode61", max_token_bytes: int | None = None, resident: bool = False,
+                   utf8: bool | None = None, unicode_planes: int | None = None):
         """set_text from the documents' raw text, tokenised, numbered and sorted on this handle's device
         (text.TextIndexData.from_texts_device); returns the TextIndexData, which set_text_shard takes unchanged.
 
@@ -2201,11 +2222,17 @@ class MmapIndex:
         np_hip_text_build_sizes and np_hip_index_set_text_build, which derives the postings by kernels and takes the
         positions as they lie.  Only the vocabulary is fetched.  Returns (and leaves in self.text) a
         text.ResidentTextIndexData: terms, vocab, n_rows and tokenizer as before, term_offsets / inst_doc / inst_pos
-        fetched from the handle on first access.  Searches on other threads go on; the caller needs no lock."""
+        fetched from the handle on first access.  Searches on other threads go on; the caller needs no lock.
+
+        utf8=True tokenises UTF-8 text on the device (text.unicode61_table(unicode_planes), see from_texts_device); None
+        takes the handle's text_utf8 / text_unicode_planes, which every update of the keyword index that has no argument
+        of its own uses too (append / append_arrays / update_resident with rows.texts)."""
         from . import text as T
+        utf8 = self.text_utf8 if utf8 is None else bool(utf8)
+        unicode_planes = self.text_unicode_planes if unicode_planes is None else int(unicode_planes)
         if not resident:
             data = T.TextIndexData.from_texts_device(texts, tokenizer, device=int(self._info.device),
-                                                     max_token_bytes=max_token_bytes)
+                                                     max_token_bytes=max_token_bytes, utf8=utf8, unicode_planes=unicode_planes)
             self.set_text(data)
             return data
         if tokenizer not in T.TOKENIZERS:
@@ -2222,7 +2249,8 @@ class MmapIndex:
             return T._tokenize_rows(T.TextIndexData, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer)
 
         code = NP_TOK_TRIGRAM if T.TOKENIZERS[tokenizer] == "trigram" else NP_TOK_UNICODE61
-        h, fb, rep = _text_build_open(L, raw, off, code, tokenize_fallback, int(self._info.device), int(max_token_bytes or 0), 0, 0, 0)
+        h, fb, rep = _text_build_open(L, raw, off, code, tokenize_fallback, int(self._info.device), int(max_token_bytes or 0), 0, 0, 0,
+                                      utf8, unicode_planes)
         return self._install_text_build(h, tokenizer, rep.as_dict(), fb)
 
     def _install_text_build(self, h, tokenizer, report, fallback):
@@ -2300,15 +2328,18 @@ class MmapIndex:
         out["doc_len"] = out["doc_len"][:N]
         return out
 
-    def _merge_text_resident(self, new_texts=(), delete=(), replace=None, renumber: bool = True):
+    def _merge_text_resident(self, new_texts=(), delete=(), replace=None, renumber: bool = True, utf8=None, unicode_planes=None):
         """The first half of a resident update: np_hip_index_text_merge of the handle's keyword index with the batch.
         Returns (the result build, the report, the fallback ids); the handle is untouched.  The caller installs or frees."""
         base = self.text
         remap, delta_ids, n_rows_out, raw, off, code, tokenize_fallback = base._update_plan(new_texts, delete, replace, renumber, None)
         return text_merge_resident(self._h, [t.encode("utf-8") for t in base.terms], remap, delta_ids, n_rows_out, raw, off, code,
-                                   tokenize_fallback, device=int(self._info.device))
+                                   tokenize_fallback, device=int(self._info.device),
+                                   utf8=self.text_utf8 if utf8 is None else bool(utf8),
+                                   unicode_planes=self.text_unicode_planes if unicode_planes is None else int(unicode_planes))
 
-    def update_text(self, new_texts=(), delete=(), replace=None, renumber: bool = True, base=None, resident: bool = False):
+    def update_text(self, new_texts=(), delete=(), replace=None, renumber: bool = True, base=None, resident: bool = False,
+                    utf8: bool | None = None, unicode_planes: int | None = None):
         """The keyword index kept current (text.TextIndexData.updated, on this handle's device): `new_texts` appended,
         the rows `delete` removed, the rows of `replace` ({id: text}) given new text; renumber=True numbers the survivors
         densely, as the document ids are after delete() / update().  `base` defaults to self.text; update() and reload()
@@ -2319,18 +2350,22 @@ class MmapIndex:
         np_hip_index_text_merge reads the base where it lies and np_hip_index_set_text_build installs the result; no
         instance array crosses the bus.  The base IS the handle, so `base=` is refused.  Returns a
         text.ResidentTextIndexData (see build_text); the arrays of the object it replaces are INVALIDATED unless they were
-        fetched before."""
+        fetched before.
+
+        utf8 / unicode_planes: build_text's, for the batch (None = the handle's text_utf8 / text_unicode_planes)."""
         if resident:
             if base is not None:
                 raise ValueError("update_text: base= is refused with resident=True: the base is the handle's keyword index")
             if self.text is None:
                 raise ValueError("update_text: the handle has no keyword index")
-            h, rep, fb = self._merge_text_resident(new_texts, delete, replace, renumber)
+            h, rep, fb = self._merge_text_resident(new_texts, delete, replace, renumber, utf8, unicode_planes)
             return self._install_text_build(h, self.text.tokenizer, rep, fb)
         base = self.text if base is None else base
         if base is None:
             raise ValueError("update_text: the handle has no keyword index and no base was given")
-        data = base.updated(new_texts, delete=delete, replace=replace, renumber=renumber, device=int(self._info.device))
+        data = base.updated(new_texts, delete=delete, replace=replace, renumber=renumber, device=int(self._info.device),
+                            utf8=self.text_utf8 if utf8 is None else bool(utf8),
+                            unicode_planes=self.text_unicode_planes if unicode_planes is None else int(unicode_planes))
         self.set_text(data)
         return data
 

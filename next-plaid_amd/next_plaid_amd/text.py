@@ -130,6 +130,73 @@ def sanitize_fts5_query_or(query: str) -> str:
     return " OR ".join(out)
 
 
+# ---- unicode61 beyond ASCII: SQLite's own rule as a table ------------------------------------------------------------------
+# unicode61 (remove_diacritics=1, the default) is context-free per code point but for one thing: a combining mark continues
+# a token that is open and separates otherwise.  So three classes and one folded code point per code point describe it, and
+# probing the SQLite that from_texts itself uses gives them: the document 'x' + chr(cp) + 'y' comes back as the tokens
+# ['x', 'y'] (cp separates), ['x?y'] (a token character; ? is its fold, always one code point) or ['xy'] (a mark: it
+# continued the token and left nothing in the term).  Nothing of SQLite's source tables is written down here.
+UNICODE_PLANE = 65536
+UNICODE_SEPARATOR, UNICODE_TOKEN, UNICODE_MARK = 0, 1, 2
+UNICODE_FOLD_MASK = 0x1FFFFF
+# plane -> its 65536 entries, and planes -> the table of that many planes: filled once per process.  Two threads that ask
+# first at the same time may both probe a plane; the results are equal and the last one stored stays, which is harmless.
+_UNICODE61_PLANES: dict = {}
+_UNICODE61_TABLES: dict = {}
+unicode61_probe_seconds: dict = {}    # plane -> what its probe took (tools/textbuild_time.py --utf8 reports it)
+
+
+def _probe_unicode61_plane(plane: int) -> np.ndarray:
+    import time
+    t0 = time.perf_counter()
+    out = np.zeros(UNICODE_PLANE, np.uint32)
+    first = plane * UNICODE_PLANE
+    cps = [cp for cp in range(first, first + UNICODE_PLANE) if cp != 0 and not 0xD800 <= cp < 0xE000]
+    conn = sqlite3.connect(":memory:")
+    try:
+        conn.execute("CREATE VIRTUAL TABLE s USING fts5(c, tokenize='unicode61')")
+        conn.execute("CREATE VIRTUAL TABLE sv USING fts5vocab('s', 'instance')")
+        conn.executemany("INSERT INTO s(rowid, c) VALUES (?, ?)", ((cp, "x" + chr(cp) + "y") for cp in cps))
+        toks: dict = {}
+        for term, doc, _ in conn.execute("SELECT term, doc, offset FROM sv ORDER BY doc, offset"):
+            toks.setdefault(doc, []).append(term)
+    finally:
+        conn.close()
+    for cp in cps:
+        got = toks.get(cp, [])
+        if got == ["x", "y"]:
+            continue                                   # class 0, fold 0
+        if got == ["xy"]:
+            out[cp - first] = UNICODE_MARK << 30
+        elif len(got) == 1 and len(got[0]) == 3 and got[0][0] == "x" and got[0][2] == "y":
+            out[cp - first] = (UNICODE_TOKEN << 30) | ord(got[0][1])
+        else:
+            raise ValueError(f"unicode61_table: SQLite {sqlite3.sqlite_version} tokenises 'x' + U+{cp:04X} + 'y' as {got!r}, "
+                             f"which the three classes do not describe")
+    unicode61_probe_seconds[plane] = time.perf_counter() - t0
+    return out
+
+
+def unicode61_table(planes: int = 2) -> np.ndarray:
+    """SQLite's unicode61 rule for the code points of the first `planes` planes (1..17), as np_text_build_opts.unicode_table
+    takes it: uint32 [planes * 65536], bits 0-20 the folded code point, bits 30-31 the class -- 0 a separator (the whole
+    entry is 0; code point 0 and the surrogates among them), 1 a token character, 2 a mark (it continues an open token,
+    contributes nothing to the term and separates otherwise).  Probed from the SQLite of this process one plane at a time
+    (a fraction of a second each) and cached per process; the result is read-only."""
+    planes = int(planes)
+    if not 1 <= planes <= 17:
+        raise ValueError(f"unicode61_table: planes {planes} outside 1..17")
+    got = _UNICODE61_TABLES.get(planes)
+    if got is None:
+        for p in range(planes):
+            if p not in _UNICODE61_PLANES:
+                _UNICODE61_PLANES[p] = _probe_unicode61_plane(p)
+        got = np.concatenate([_UNICODE61_PLANES[p] for p in range(planes)])
+        got.setflags(write=False)
+        _UNICODE61_TABLES[planes] = got
+    return got
+
+
 # ---- the keyword index as arrays -----------------------------------------------------------------------------------------
 
 @dataclass
@@ -215,12 +282,15 @@ class TextIndexData:
 
     @classmethod
     def from_texts_device(cls, texts, tokenizer: str = "unicode61", device: int = 0, max_token_bytes: int | None = None,
-                          **knobs) -> "TextIndexData":
+                          utf8: bool = False, unicode_planes: int = 2, **knobs) -> "TextIndexData":
         """from_texts without the FTS5 table: the documents are tokenised, their terms numbered and the instances sorted on
         the device (np_hip_text_build), and the arrays equal from_texts' one for one.  The device reproduces SQLite for
         ASCII text (trigram: without NUL; unicode61: tokens of at most max_token_bytes, 256 unless given); the documents it
         hands back -- fallback_docs on the result -- go through a scratch FTS5 table here and are merged in.
         identifier_aware expands identifiers on the host first, as from_texts does.  build_report holds the stage report.
+        utf8=True hands the library unicode61_table(unicode_planes): unicode61 and identifier_aware are then reproduced for
+        all well-formed UTF-8 inside those planes (max_token_bytes counts raw bytes, at most 21845), and only documents with
+        a code point beyond them or an overlong token fall back; trigram is as without it.
         `knobs` are the test knobs of np_text_build_opts (hash_bits, tile_bytes, workspace_bytes)."""
         if tokenizer not in TOKENIZERS:
             raise ValueError(f"unknown tokenizer {tokenizer!r}")
@@ -236,7 +306,8 @@ class TextIndexData:
             return _tokenize_rows(cls, [texts[int(i)] for i in ids], [int(i) for i in ids], tokenizer)
 
         code = api.NP_TOK_TRIGRAM if TOKENIZERS[tokenizer] == "trigram" else api.NP_TOK_UNICODE61
-        r = api.text_build(raw, off, code, tokenize_fallback, device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
+        r = api.text_build(raw, off, code, tokenize_fallback, device=device, max_token_bytes=int(max_token_bytes or 0),
+                           utf8=utf8, unicode_planes=unicode_planes, **knobs)
         return cls._of_build(tokenizer, r)
 
     @classmethod
@@ -250,7 +321,8 @@ class TextIndexData:
         return data
 
     def updated(self, new_texts=(), *, delete=(), replace=None, renumber: bool = True, n_rows: int | None = None,
-                device: int = 0, max_token_bytes: int | None = None, **knobs) -> "TextIndexData":
+                device: int = 0, max_token_bytes: int | None = None, utf8: bool = False, unicode_planes: int = 2,
+                **knobs) -> "TextIndexData":
         """The index of the table after the crate's index / delete / update_rows (and rebuild), without building it again:
         a new TextIndexData, equal array for array to from_texts of the resulting rows.  `delete` lists row ids that go,
         `replace` maps row ids to their new text ({id: text} or (id, text) pairs), `new_texts` are appended behind the last
@@ -261,13 +333,15 @@ class TextIndexData:
         The table must be dense -- rows 0 .. self.n_rows - 1, which is what from_texts and a renumbered update leave --
         unless n_rows names the size of its id space (the ids then in use are the caller's knowledge: every id in `delete`
         and `replace` must be a row, and renumber=True is refused).  build_report is the merge's report (under "batch": the
-        report of the batch's build, None without a batch), fallback_docs index the batch.  `knobs`: from_texts_device's, and merge_workspace_bytes."""
+        report of the batch's build, None without a batch), fallback_docs index the batch.  utf8 / unicode_planes: as
+        from_texts_device takes them, for the batch.  `knobs`: from_texts_device's, and merge_workspace_bytes."""
         from . import api
         remap, delta_ids, n_rows_out, raw, off, code, tokenize_fallback = self._update_plan(new_texts, delete, replace, renumber, n_rows)
         tokenizer, cls = self.tokenizer, type(self)
         r = api.text_merge([t.encode("utf-8") for t in self.terms], self.term_offsets, self.inst_doc, self.inst_pos, int(self.n_rows),
                            remap, delta_ids, n_rows_out, raw, off, code, tokenize_fallback,
-                           device=device, max_token_bytes=int(max_token_bytes or 0), **knobs)
+                           device=device, max_token_bytes=int(max_token_bytes or 0), utf8=utf8, unicode_planes=unicode_planes,
+                           **knobs)
         data = cls._of_build(tokenizer, r)
         data.build_report = dict(r["report"], batch=r["build_report"])     # the merge's report; the batch's build inside it
         return data
