@@ -694,7 +694,9 @@ int np_hip_search_hybrid(const np_index* index, const float* queries, const int3
  *   the postings a prefix's pre-pass walks too, and every query of a chunk owns 4 bytes x num_documents of scratch per
  *   single-token prefix phrase (of the query that has most).  A malformed tree is NP_ERR_INVALID_ARGUMENT before any launch;
  *   the message names the query and the node or phrase.
- * The sharded, grouped and device-pointer entries have no _expr form yet. */
+ * The device-pointer form is np_hip_text_search_expr_device below, the sharded forms np_hip_text_search_sharded_expr,
+ * _sharded_expr_filtered and np_hip_search_hybrid_sharded_expr (with the sharded entries).  The grouped entries have no _expr
+ * form yet. */
 #define NP_TEXT_NODE_PHRASE 0
 #define NP_TEXT_NODE_AND 1
 #define NP_TEXT_NODE_OR 2
@@ -721,6 +723,13 @@ int np_hip_text_search_expr(const np_index* index, const np_text_expr* queries, 
 int np_hip_text_search_expr_filtered(const np_index* index, const np_text_expr* queries, int32_t B, int32_t top_k,
                                      const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
                                      int64_t* out_ids, float* out_scores, int32_t* out_counts, np_stats* stats);
+/* np_hip_text_search_device with tree queries: np_hip_text_search_expr's bytes in device buffers, enqueued on `stream`.  It
+ * synchronises the stream where np_hip_text_search_device does (once, for the idf, in a batch with a phrase of several
+ * tokens) and once more per chunk of queries that holds a single-token prefix phrase (that chunk's prefix counts). */
+int np_hip_text_search_expr_device(const np_index* index, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                   const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                   const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                                   int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
 /* np_hip_search_hybrid with tree queries: its arguments, scope forms and result, the keyword list being
  * np_hip_text_search_expr's. */
 int np_hip_search_hybrid_expr(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
@@ -973,7 +982,20 @@ int np_hip_search_batch_sharded_subsets(const np_index* index, np_comm* comm, co
  * np_hip_search_hybrid_sharded: np_hip_search_hybrid over the shards, byte for byte: the sharded semantic pass and the
  * sharded keyword pass with top_k = fetch_k and the fusion, on one stream; every rank holds both global lists after the
  * merges, so every rank fuses.  The scope is the subsets' CSR on the device, or -- filters != NULL -- n_filters filters
- * with the host array query_filter as the query map (then the CSR arguments are not read). */
+ * with the host array query_filter as the query map (then the CSR arguments are not read).
+ *
+ * np_hip_text_search_sharded_expr, np_hip_text_search_sharded_expr_filtered, np_hip_search_hybrid_sharded_expr: the three
+ * calls above with tree queries (np_text_expr) in place of the flat ones; every rank holds, bit for bit, what
+ * np_hip_text_search_expr / np_hip_search_hybrid_expr return on the unsharded handle for the same scope, and a flat query
+ * lifted to a tree keeps the flat sharded entry's bytes.  The argument-only checks are the tree's own against a vocabulary
+ * of 2^31 terms, before the first collective; the check against the handle's vocabulary is a local failure.  Limits are
+ * np_text_expr's.  Failure rules, exchanges of lists and scopes are the flat calls'.
+ *   counts   the counting exchange carries, in query and phrase order, first the phrases of several known tokens (their
+ *            last token may be a prefix range), then the single-token prefix phrases: the shard's documents that hold any
+ *            term of the range, counted for the WHOLE batch ahead of the local chunks by a pass over one bitmap of a bit
+ *            per document and phrase (in groups that fit the rank's workspace).  The record's size follows from the
+ *            queries alone; a batch without such a phrase exchanges no counts.  The chunks then fill their frequency
+ *            arrays as the unsharded call does, without its synchronisation per chunk */
 int np_hip_index_set_text_shard(np_index* index, const np_text_index* text);
 int np_hip_text_search_sharded(const np_index* index, np_comm* comm, const np_text_query* queries, int32_t B, int32_t top_k,
                                const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
@@ -983,6 +1005,14 @@ int np_hip_text_search_sharded_filtered(const np_index* index, np_comm* comm, co
                                         int32_t top_k, const np_filter* filters, int32_t n_filters,
                                         const int32_t* query_filter /* host, [B] */,
                                         int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+int np_hip_text_search_sharded_expr(const np_index* index, np_comm* comm, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                    const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                    const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                                    int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+int np_hip_text_search_sharded_expr_filtered(const np_index* index, np_comm* comm, const np_text_expr* queries, int32_t B,
+                                             int32_t top_k, const np_filter* filters, int32_t n_filters,
+                                             const int32_t* query_filter /* host, [B] */,
+                                             int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
 int np_hip_search_batch_sharded_filtered(const np_index* index, np_comm* comm, const float* d_queries,
                                          const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
                                          int32_t dim, const np_search_params* params, const np_filter* filters,
@@ -996,6 +1026,14 @@ int np_hip_search_hybrid_sharded(const np_index* index, np_comm* comm, const flo
                                  const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
                                  const np_filter* filters, int32_t n_filters, const int32_t* query_filter /* host, [B] */,
                                  int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
+int np_hip_search_hybrid_sharded_expr(const np_index* index, np_comm* comm, const float* d_queries,
+                                      const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B, int32_t dim,
+                                      const np_search_params* params, const np_text_expr* text_queries, int32_t fetch_k,
+                                      float alpha, int32_t fusion,
+                                      const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                                      const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset,
+                                      const np_filter* filters, int32_t n_filters, const int32_t* query_filter /* host, [B] */,
+                                      int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream);
 
 /* Host-only validation of an index directory: parses and checks every file exactly as np_hip_index_open
  * does (MmapIndex::load, index.rs:1026-1139; NPY headers mmap.rs:659-749; fast-plaid dtypes mmap.rs:1780-1808)

@@ -177,6 +177,38 @@ __global__ void __launch_bounds__(TEXT_TPB) text_prefix_kernel(TextPrefixP p) {
   text_block_count(c, &p.pxhit[phr]);
 }
 
+struct TextPrefixCountP {
+  TextIxP t;
+  const int32_t* phr_tok;
+  const int32_t* terms;
+  const int32_t* phr_hi;
+  const int32_t* px_phr;           // [prefix phrases of the group]
+  uint32_t* bits;                  // [group][words] zeroed: one bit per document of the shard
+  int64_t words;
+  unsigned long long* nhit;        // [group] zeroed
+};
+
+// nHit of a single-token prefix phrase and nothing else: the counting pre-pass of a sharded tree batch, which runs for the
+// whole batch ahead of the chunk loop (the counts cross the ranks before any idf is computed; text_prefix_kernel still fills
+// the frequency arrays per chunk).  A lane per posting of the run [post_off[lo], post_off[hi]) sets its document's bit; the
+// lane that finds it clear counts the document.  The words are global: a run is sorted by document inside a term only, so a
+// workgroup's postings spread over the whole shard and no slice of the bitmap fits LDS; the L2 resolves the atomics, and a
+// bit per document keeps a group's bitmaps inside it.  Integer atomics only: order cannot show.  No workgroup waits for another.
+__global__ void __launch_bounds__(TEXT_TPB) text_prefix_count_kernel(TextPrefixCountP p) {
+  const int tid = threadIdx.x;
+  const int phr = p.px_phr[blockIdx.y];
+  const int term = p.terms[p.phr_tok[phr]];
+  uint32_t* bits = p.bits + (int64_t)blockIdx.y * p.words;
+  const int64_t lo = p.t.post_off[term], hi = p.t.post_off[p.phr_hi[phr]];
+  uint32_t c = 0;
+  for (int64_t j = lo + (int64_t)blockIdx.x * TEXT_TPB + tid; j < hi; j += (int64_t)gridDim.x * TEXT_TPB) {
+    const int doc = p.t.post_doc[j];
+    const uint32_t bit = 1u << (doc & 31);
+    c += (atomicOr(&bits[doc >> 5], bit) & bit) == 0u ? 1u : 0u;
+  }
+  text_block_count(c, &p.nhit[blockIdx.y]);
+}
+
 // ---- the (query, slice) kernels: what the flat and the tree kernel share ------------------------------------------------------
 
 struct TextScoreP {
@@ -1070,9 +1102,11 @@ struct TextCounts {
 // (synchronises).
 // Sharded (counts != NULL): the hit counts of the counted phrases cross the ranks before the idf is computed, d_out_keys receives
 // the f64 bits of the scores and the ids leave as global ids; otherwise both are NULL.
-// Tree queries (prog.tree; host entries only: pin != NULL): the counting pass knows prefixes, every chunk of queries first fills
-// the frequency arrays of its single-token prefix phrases and synchronises once for their nHit, and text_expr_kernel takes
-// text_score_kernel's place.
+// Tree queries (prog.tree): the counting pass knows prefixes, every chunk of queries first fills the frequency arrays of its
+// single-token prefix phrases and synchronises once for their nHit, and text_expr_kernel takes text_score_kernel's place.
+// Sharded tree queries: text_prefix_count_kernel counts those phrases for the whole batch ahead of the chunk loop, in groups of
+// bitmaps that fit the arena, so that their counts cross the ranks in the one counting exchange with the items'; the chunks
+// then fill their frequency arrays without a synchronisation.  What crosses the ranks follows from the queries alone.
 static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pin, const TextPlan& plan, TextProg& prog, int top_k,
                     const CallSubsets& sub, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, int64_t* visited,
                     unsigned long long* d_out_keys, TextCounts* counts) {
@@ -1116,13 +1150,46 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
   auto d32 = [&](size_t off) { return (const int32_t*)(d_prog + off); };
   unsigned long long* d_nhit = (unsigned long long*)(d_prog + prog.o_nhit);
   unsigned long long* h_nhit = (unsigned long long*)(src + prog.o_nhit);
-  if (prog.n_items > 0) {
-    NP_HIP(hipMemsetAsync(d_nhit, 0, (size_t)prog.n_items * 8, st));
+  // Over shards the single-token prefix phrases of a tree batch are counted here too, behind the items in the same vector:
+  // their nHit must be summed over the ranks, and a collective cannot wait for a rank's own chunks
+  const int64_t n_pre = counts && tree ? prog.n_px : 0;
+  if (counts && counts->n_items != prog.n_items + n_pre) {   // (the record's size came from the queries alone: the same phrases)
+    set_error("Text search failed: the counting exchange was sized for %lld phrases, the programs count %lld", (long long)counts->n_items,
+              (long long)(prog.n_items + n_pre));
+    return NP_ERR_SEARCH;
+  }
+  if (prog.n_items + n_pre > 0) {
+    NP_HIP(hipMemsetAsync(d_nhit, 0, (size_t)(prog.n_items + n_pre) * 8, st));
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (prog.max_item_df + TEXT_TPB - 1) / TEXT_TPB));
     const auto hit_kernel = tree ? text_hit_kernel<true> : text_hit_kernel<false>;
     for (int64_t i0 = 0; i0 < prog.n_items; i0 += 65535) {   // (the items are a grid dimension)
       const TextHitP hp{tp, d32(prog.o_ptok), d32(prog.o_terms), tree ? d32(prog.o_phi) : nullptr, d32(prog.o_item) + i0, d_nhit + i0};
       hit_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, prog.n_items - i0)), TEXT_TPB, 0, st>>>(hp);
+    }
+    if (n_pre > 0 && ix->n_docs > 0) {
+      // the bitmaps lie where the chunk loop's buffers will: nothing of those is live yet.  Groups of as many as fit
+      const int64_t words = text_prefix_bitmap_bytes(ix->n_docs) / 4;
+      const size_t arena_bytes = text_arena_bytes(ix, plan, prog, top_k, subsets);   // (what the caller reserved behind `base`)
+      const int64_t group = text_prefix_group((int64_t)(base + arena_bytes - (char*)best_keys), ix->n_docs, n_pre);
+      if (group < 1) {
+        set_error("Text search failed: one bitmap of %lld documents does not fit the workspace", (long long)ix->n_docs);
+        return NP_ERR_OUT_OF_MEMORY;
+      }
+      const int32_t* pxphr = prog.at32(prog.o_pxphr);
+      for (int64_t x0 = 0; x0 < n_pre; x0 += group) {
+        const int64_t xn = std::min(group, n_pre - x0);
+        int64_t longest = 0;
+        for (int64_t x = x0; x < x0 + xn; ++x) {
+          const int32_t ph = pxphr[x], lo = prog.at32(prog.o_terms)[prog.at32(prog.o_ptok)[ph]], hi = prog.at32(prog.o_phi)[ph];
+          longest = std::max(longest, tx.h_post_off[(size_t)hi] - tx.h_post_off[(size_t)lo]);
+        }
+        if (longest == 0) continue;   // no term of these ranges occurs on this shard: the counts stay 0
+        NP_HIP(hipMemsetAsync(best_keys, 0, (size_t)xn * (size_t)words * 4, st));
+        const unsigned gp = (unsigned)std::min<int64_t>(NP_TEXT_HIT_BLOCKS, (longest + TEXT_TPB - 1) / TEXT_TPB);
+        const TextPrefixCountP cp{tp, d32(prog.o_ptok), d32(prog.o_terms), d32(prog.o_phi), d32(prog.o_pxphr) + x0, (uint32_t*)best_keys,
+                                  words, d_nhit + prog.n_items + x0};
+        text_prefix_count_kernel<<<dim3(gp, (unsigned)xn), TEXT_TPB, 0, st>>>(cp);
+      }
     }
     NP_HIP(hipGetLastError());
     if (counts) {   // the shards' counts summed on the host, the same bytes on every rank
@@ -1134,6 +1201,7 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
     }
     const int32_t* item = (const int32_t*)(prog.blob.data() + prog.o_item);
     for (int64_t i = 0; i < prog.n_items; ++i) prog.phr_hit[(size_t)item[i]] = (int64_t)h_nhit[i];
+    for (int64_t x = 0; x < n_pre; ++x) prog.phr_hit[(size_t)prog.at32(prog.o_pxphr)[x]] = (int64_t)h_nhit[prog.n_items + x];
   }
   double* h_idf = (double*)(src + prog.o_idf);
   // (nHit still -1: a single-token prefix phrase of a tree query.  Its idf is 0 here, no value bm25 can have, and is set by
@@ -1196,16 +1264,19 @@ static int text_run(const DeviceIndex* ix, ContextUse& use, char* base, char* pi
           text_prefix_kernel<<<dim3(gx, (unsigned)std::min<int64_t>(65535, x1 - i0)), TEXT_TPB, 0, st>>>(pp);
         }
         NP_HIP(hipGetLastError());
-        const int32_t p0 = prog.at32(prog.o_qphr)[q0], p1 = prog.at32(prog.o_qphr)[q0 + Qn];
-        unsigned long long* h_px = (unsigned long long*)(src + prog.o_pxhit);
-        NP_HIP(hipMemcpyAsync(h_px + p0, d_prog + prog.o_pxhit + (size_t)p0 * 8, (size_t)(p1 - p0) * 8, hipMemcpyDeviceToHost, st));
-        NP_HIP(hipStreamSynchronize(st));
-        for (int64_t x = x0; x < x1; ++x) {
-          const int32_t ph = pxphr[x];
-          prog.phr_hit[(size_t)ph] = (int64_t)h_px[ph];
-          h_idf[ph] = text_idf(tx.n_rows, prog.phr_hit[(size_t)ph]);
+        if (!counts) {   // (over shards the counting pre-pass has summed these counts: the chunk's own is not used)
+          const int32_t p0 = prog.at32(prog.o_qphr)[q0], p1 = prog.at32(prog.o_qphr)[q0 + Qn];
+          unsigned long long* h_px = (unsigned long long*)(src + prog.o_pxhit);
+          NP_HIP(hipMemcpyAsync(h_px + p0, d_prog + prog.o_pxhit + (size_t)p0 * 8, (size_t)(p1 - p0) * 8, hipMemcpyDeviceToHost, st));
+          NP_HIP(hipStreamSynchronize(st));
+          for (int64_t x = x0; x < x1; ++x) {
+            const int32_t ph = pxphr[x];
+            prog.phr_hit[(size_t)ph] = (int64_t)h_px[ph];
+            h_idf[ph] = text_idf(tx.n_rows, prog.phr_hit[(size_t)ph]);
+          }
+          NP_HIP(hipMemcpyAsync(d_prog + prog.o_idf + (size_t)p0 * 8, h_idf + p0, (size_t)(p1 - p0) * 8, hipMemcpyHostToDevice, st));
+          if (!pin) NP_HIP(hipStreamSynchronize(st));   // a pageable source: the copy completes before the blob goes out of scope
         }
-        NP_HIP(hipMemcpyAsync(d_prog + prog.o_idf + (size_t)p0 * 8, h_idf + p0, (size_t)(p1 - p0) * 8, hipMemcpyHostToDevice, st));
       }
     }
     sp.q0 = q0;
@@ -1320,13 +1391,16 @@ static int fuse_check(int mode, float alpha, int top_k, int B, int sem_stride, i
 
 // the checks of a sharded keyword call that depend on its arguments alone: every rank passes or fails them alike, so a failure
 // returns before the first collective.  (The vocabulary check needs the handle's index: a rank that fails it fails locally.)
-static int text_check_sharded_args(const np_index* ix, np_comm* c, const np_text_query* queries, int B, int top_k, const void* out_ids,
-                                   const void* out_scores, const void* out_counts, void* stream) {
+static int text_check_sharded_args(const np_index* ix, np_comm* c, const np_text_query* queries, const np_text_expr* exprs, int B, int top_k,
+                                   const void* out_ids, const void* out_scores, const void* out_counts, void* stream) {
   if (!ix || !c || !stream) {
     set_error("Text search failed: NULL index / communicator / stream (the collectives need the caller's stream)");
     return NP_ERR_INVALID_ARGUMENT;
   }
-  NP_TRY(text_check_batch((int64_t)1 << 31, queries, B, top_k, text_check_query));
+  if (exprs)
+    NP_TRY(text_check_batch((int64_t)1 << 31, exprs, B, top_k, text_check_expr));
+  else
+    NP_TRY(text_check_batch((int64_t)1 << 31, queries, B, top_k, text_check_query));
   if (B > 0 && (!out_ids || !out_scores || !out_counts)) {
     set_error("Text search failed: NULL buffer");
     return NP_ERR_INVALID_ARGUMENT;
@@ -1348,15 +1422,16 @@ static int64_t text_counted_phrases(const np_text_query* queries, int B) {
   return n;
 }
 
-// The sharded keyword pass; the caller holds c->mu and has checked the arguments.  `sub`: the scope on the device (global ids;
-// ids of other shards are ignored, the rest rebased).  rc0 / msg0: a local failure the caller already met.
-//   [a batch with a counted phrase]  text_hit_kernel on the shard -> all-gather of nhit | nRow | status -> sums on the host
+// The sharded keyword pass; the caller holds c->mu and has checked the arguments.  `exprs` != NULL: tree queries in place of
+// `queries`.  `sub`: the scope on the device (global ids; ids of other shards are ignored, the rest rebased).  rc0 / msg0: a local failure the caller already met.
+//   [a batch with a counted phrase]  text_hit_kernel (and, for the single-token prefix phrases of tree queries,
+//   text_prefix_count_kernel) on the shard -> all-gather of nhit | nRow | status -> sums on the host
 //   local scoring with the global idf and average length -> the shard's top-k as f64 keys and global ids
 //   per exchange (np_dist_plan.h cuts the batch by B and top_k alone): all-gather of keys | ids | counts | status,
 //   text_rank_merge_kernel into the caller's buffers
-static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_query* queries, int B, int top_k, const CallSubsets& sub,
-                               int rc0, const char* msg0, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
-                               hipStream_t st) {
+static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_query* queries, const np_text_expr* exprs, int B, int top_k,
+                               const CallSubsets& sub, int rc0, const char* msg0, int64_t* d_out_ids, float* d_out_scores,
+                               int32_t* d_out_counts, hipStream_t st) {
   DeviceGuard g(ix->device);
   const int G = c->nranks;
   const bool host_check = c->host_check();
@@ -1394,19 +1469,20 @@ static int text_sharded_locked(const np_index* ix, np_comm* c, const np_text_que
     set_error("Text search failed: the handle has no keyword index (np_hip_index_set_text_shard)");
     local(NP_ERR_INVALID_ARGUMENT);
   }
-  char msg[240];
+  char msg[320];
   for (int q = 0; rc == NP_OK && q < B; ++q)
-    if (text_check_query(&queries[q], q, ix->text.n_terms, msg, sizeof msg) != 0) {
+    if ((exprs ? text_check_expr(&exprs[q], q, ix->text.n_terms, msg, sizeof msg)
+               : text_check_query(&queries[q], q, ix->text.n_terms, msg, sizeof msg)) != 0) {
       set_error("Text search failed: %s", msg);
       local(NP_ERR_INVALID_ARGUMENT);
     }
-  TextCounts counts{ix, c, st, text_counted_phrases(queries, B), rc};
+  TextCounts counts{ix, c, st, exprs ? text_counted_expr_phrases(exprs, B) : text_counted_phrases(queries, B), rc};
   {
     TextProg prog;
     TextPlan plan;
     ContextUse use;
     if (rc == NP_OK) {
-      prog.build(ix, queries, B);
+      if (exprs) prog.build_expr(ix, exprs, B); else prog.build(ix, queries, B);
       local(text_plan_for(ix, 0, prog, B, top_k, sub.n > 0, &plan));
     }
     if (rc == NP_OK) local(use.begin(ix, st));
@@ -1579,13 +1655,15 @@ int np_hip_text_search_filtered(const np_index* ix, const np_text_query* queries
                    out_scores, out_counts, stats);
 }
 
-int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k,
-                              const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
-                              int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
-                              int32_t* d_out_counts, void* stream) {
+// np_hip_text_search_device, and with exprs != NULL np_hip_text_search_expr_device (a NULL batch gets the flat form's checks: they
+// say so)
+static int text_device(const np_index* ix, const np_text_query* queries, const np_text_expr* exprs, int32_t B, int32_t top_k,
+                       const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                       int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                       int32_t* d_out_counts, void* stream) {
   clear_error();
   IndexRead reading(ix);   // an append waits for this call and holds later ones back (np_internal.h)
-  NP_TRY(text_check_queries(ix, queries, B, top_k));
+  NP_TRY(exprs ? text_check_exprs(ix, exprs, B, top_k) : text_check_queries(ix, queries, B, top_k));
   NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
   if (B == 0) return NP_OK;
   if (!d_out_ids || !d_out_scores || !d_out_counts) {
@@ -1594,7 +1672,7 @@ int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, 
   }
   const CallSubsets sub = CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset);
   TextProg prog;
-  prog.build(ix, queries, B);
+  if (exprs) prog.build_expr(ix, exprs, B); else prog.build(ix, queries, B);
   DeviceGuard g(ix->device);
   TextPlan plan;
   NP_TRY(text_plan_for(ix, 0, prog, B, top_k, sub.n > 0, &plan));
@@ -1603,6 +1681,22 @@ int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, 
   NP_TRY(use.arena().reserve(text_arena_bytes(ix, plan, prog, top_k, sub.n > 0)));
   return text_run(ix, use, use.arena().as<char>(), nullptr, plan, prog, top_k, sub, d_out_ids, d_out_scores, d_out_counts, nullptr, nullptr,
                   nullptr);
+}
+
+int np_hip_text_search_device(const np_index* ix, const np_text_query* queries, int32_t B, int32_t top_k,
+                              const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                              int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                              int32_t* d_out_counts, void* stream) {
+  return text_device(ix, queries, nullptr, B, top_k, d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset,
+                     d_out_ids, d_out_scores, d_out_counts, stream);
+}
+
+int np_hip_text_search_expr_device(const np_index* ix, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                   const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                   int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                                   int32_t* d_out_counts, void* stream) {
+  return text_device(ix, nullptr, queries, B, top_k, d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset,
+                     d_out_ids, d_out_scores, d_out_counts, stream);
 }
 
 int np_hip_fuse_device(const np_index* ix, int32_t mode, float alpha, int32_t top_k, int32_t B, const int64_t* d_sem_ids,
@@ -1826,49 +1920,81 @@ int np_hip_search_hybrid_grouped(const np_index* ix, const float* queries, const
                      n_subsets, query_subset, filters, n_filters, out_ids, out_scores, out_counts, stats, &grp);
 }
 
-int np_hip_text_search_sharded(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
-                               const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
-                               int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
-                               int32_t* d_out_counts, void* stream) {
+// the three sharded entries and their _expr forms (exprs != NULL: tree queries in place of `queries`; a NULL batch gets the flat
+// form's checks, as in text_host)
+static int text_sharded(const np_index* ix, np_comm* c, const np_text_query* queries, const np_text_expr* exprs, int32_t B, int32_t top_k,
+                        const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                        int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                        int32_t* d_out_counts, void* stream) {
   clear_error();
-  NP_TRY(text_check_sharded_args(ix, c, queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
+  NP_TRY(text_check_sharded_args(ix, c, queries, exprs, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
   NP_TRY(check_device_subsets(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, B));
   if (B == 0) return NP_OK;
   std::lock_guard<std::mutex> lk(c->mu);
-  return text_sharded_locked(ix, c, queries, B, top_k,
+  return text_sharded_locked(ix, c, queries, exprs, B, top_k,
                              CallSubsets::device(d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset), NP_OK,
                              nullptr, d_out_ids, d_out_scores, d_out_counts, (hipStream_t)stream);
 }
 
-int np_hip_text_search_sharded_filtered(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
-                                        const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
-                                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream) {
+static int text_sharded_filtered(const np_index* ix, np_comm* c, const np_text_query* queries, const np_text_expr* exprs, int32_t B,
+                                 int32_t top_k, const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                 int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream) {
   clear_error();
-  NP_TRY(text_check_sharded_args(ix, c, queries, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
+  NP_TRY(text_check_sharded_args(ix, c, queries, exprs, B, top_k, d_out_ids, d_out_scores, d_out_counts, stream));
   NP_TRY(check_sharded_filters("Filter failed", filters, n_filters, query_filter, B));
   if (B == 0) return NP_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(ix->device);
   ShardFilterScope scope;   // (nHit never looks at the scope: the keyword pass needs no global lengths)
   scope.eval(ix, c, (hipStream_t)stream, filters, n_filters, query_filter, B);
-  return text_sharded_locked(ix, c, queries, B, top_k, scope.call(), scope.rc0, scope.msg0.c_str(), d_out_ids, d_out_scores,
+  return text_sharded_locked(ix, c, queries, exprs, B, top_k, scope.call(), scope.rc0, scope.msg0.c_str(), d_out_ids, d_out_scores,
                              d_out_counts, (hipStream_t)stream);
 }
 
-int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
-                                 const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
-                                 const np_text_query* text_queries, int32_t fetch_k, float alpha, int32_t fusion,
-                                 const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
-                                 int64_t n_subsets, const int32_t* d_query_subset, const np_filter* filters, int32_t n_filters,
-                                 const int32_t* query_filter, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
-                                 void* stream) {
+int np_hip_text_search_sharded(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
+                               const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                               int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                               int32_t* d_out_counts, void* stream) {
+  return text_sharded(ix, c, queries, nullptr, B, top_k, d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset,
+                      d_out_ids, d_out_scores, d_out_counts, stream);
+}
+
+int np_hip_text_search_sharded_expr(const np_index* ix, np_comm* c, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                    const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                    int64_t n_subsets, const int32_t* d_query_subset, int64_t* d_out_ids, float* d_out_scores,
+                                    int32_t* d_out_counts, void* stream) {
+  return text_sharded(ix, c, nullptr, queries, B, top_k, d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets,
+                      d_query_subset, d_out_ids, d_out_scores, d_out_counts, stream);
+}
+
+int np_hip_text_search_sharded_filtered(const np_index* ix, np_comm* c, const np_text_query* queries, int32_t B, int32_t top_k,
+                                        const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                        int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream) {
+  return text_sharded_filtered(ix, c, queries, nullptr, B, top_k, filters, n_filters, query_filter, d_out_ids, d_out_scores,
+                               d_out_counts, stream);
+}
+
+int np_hip_text_search_sharded_expr_filtered(const np_index* ix, np_comm* c, const np_text_expr* queries, int32_t B, int32_t top_k,
+                                             const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                             int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts, void* stream) {
+  return text_sharded_filtered(ix, c, nullptr, queries, B, top_k, filters, n_filters, query_filter, d_out_ids,
+                               d_out_scores, d_out_counts, stream);
+}
+
+static int hybrid_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                          const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                          const np_text_query* text_queries, const np_text_expr* text_exprs, int32_t fetch_k, float alpha,
+                          int32_t fusion, const int64_t* d_subset_ids, const int64_t* d_subset_offsets,
+                          const int64_t* h_subset_offsets, int64_t n_subsets, const int32_t* d_query_subset, const np_filter* filters,
+                          int32_t n_filters, const int32_t* query_filter, int64_t* d_out_ids, float* d_out_scores,
+                          int32_t* d_out_counts, void* stream) {
   clear_error();
   if (!params) {
     set_error("Search failed: NULL index or params");
     return NP_ERR_INVALID_ARGUMENT;
   }
   // arguments every rank sees alike: before the lock and the first collective
-  NP_TRY(text_check_sharded_args(ix, c, text_queries, B, fetch_k, d_out_ids, d_out_scores, d_out_counts, stream));
+  NP_TRY(text_check_sharded_args(ix, c, text_queries, text_exprs, B, fetch_k, d_out_ids, d_out_scores, d_out_counts, stream));
   NP_TRY(fuse_check(fusion, alpha, params->top_k, B, fetch_k, fetch_k));
   if (filters)
     NP_TRY(check_sharded_filters("Filter failed", filters, n_filters, query_filter, B));
@@ -1904,7 +2030,7 @@ int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_
                                                  sem_l.d_sc, sem_l.d_cnt, stream, scope.rc0, scope.msg0.c_str());
   const std::string msg_sem = rc_sem != NP_OK ? np_hip_last_error() : "";
   if (rc_sem != NP_OK && c->host_check()) return rc_sem;
-  const int rc_kw = text_sharded_locked(ix, c, text_queries, B, fetch_k, sub, rc_sem, msg_sem.c_str(), kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, st);
+  const int rc_kw = text_sharded_locked(ix, c, text_queries, text_exprs, B, fetch_k, sub, rc_sem, msg_sem.c_str(), kw_l.d_ids, kw_l.d_sc, kw_l.d_cnt, st);
   if (rc_kw != NP_OK) return rc_kw;
   // every rank holds both global lists: every rank fuses.  (An abandoned list carries count -1: the fusion clamps it to an empty
   // list, and the count that leaves is the abandoned one.)
@@ -1913,6 +2039,30 @@ int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_
   hybrid_abandon_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(sem_l.d_cnt, kw_l.d_cnt, B, d_out_counts);
   NP_HIP(hipGetLastError());
   return NP_OK;
+}
+
+int np_hip_search_hybrid_sharded(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                 const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                 const np_text_query* text_queries, int32_t fetch_k, float alpha, int32_t fusion,
+                                 const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                 int64_t n_subsets, const int32_t* d_query_subset, const np_filter* filters, int32_t n_filters,
+                                 const int32_t* query_filter, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                 void* stream) {
+  return hybrid_sharded(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, text_queries, nullptr, fetch_k, alpha,
+                        fusion, d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, filters, n_filters,
+                        query_filter, d_out_ids, d_out_scores, d_out_counts, stream);
+}
+
+int np_hip_search_hybrid_sharded_expr(const np_index* ix, np_comm* c, const float* d_queries, const int32_t* d_q_tok_offsets,
+                                      const int32_t* h_q_tok_offsets, int32_t B, int32_t dim, const np_search_params* params,
+                                      const np_text_expr* text_queries, int32_t fetch_k, float alpha, int32_t fusion,
+                                      const int64_t* d_subset_ids, const int64_t* d_subset_offsets, const int64_t* h_subset_offsets,
+                                      int64_t n_subsets, const int32_t* d_query_subset, const np_filter* filters, int32_t n_filters,
+                                      const int32_t* query_filter, int64_t* d_out_ids, float* d_out_scores, int32_t* d_out_counts,
+                                      void* stream) {
+  return hybrid_sharded(ix, c, d_queries, d_q_tok_offsets, h_q_tok_offsets, B, dim, params, nullptr, text_queries,
+                        fetch_k, alpha, fusion, d_subset_ids, d_subset_offsets, h_subset_offsets, n_subsets, d_query_subset, filters,
+                        n_filters, query_filter, d_out_ids, d_out_scores, d_out_counts, stream);
 }
 
 }  // extern "C"

@@ -144,6 +144,42 @@ inline int text_check_expr(const np_text_expr* te, int32_t q, int64_t n_terms, c
   return 0;
 }
 
+// The phrases of a batch of tree queries whose nHit crosses the ranks of a sharded call, in the order of the count vector: first
+// the phrases of several tokens, all known (their last token may be a prefix range), in query and phrase order, then the
+// single-token prefix phrases, likewise.  Follows from the queries alone (which have passed text_check_expr: a prefix range
+// starts at a known term and is not empty), so every rank runs the same counting exchange of the same size.  An exact single
+// token is not counted: its document frequency is the table's on every shard.  *n_multi, *n_prefix: nullable.
+inline int64_t text_counted_expr_phrases(const np_text_expr* queries, int32_t B, int64_t* n_multi = nullptr, int64_t* n_prefix = nullptr) {
+  int64_t multi = 0, prefix = 0;
+  for (int32_t q = 0; q < B; ++q)
+    for (int32_t i = 0; i < queries[q].n_phrases; ++i) {
+      const int32_t tb = queries[q].phrase_offsets[i], te = queries[q].phrase_offsets[i + 1];
+      bool known = true;
+      for (int32_t k = tb; k < te; ++k) known = known && queries[q].terms[k] >= 0;
+      if (!known) continue;
+      if (te - tb > 1) ++multi;
+      else if (queries[q].prefix_hi[i] != 0) ++prefix;
+    }
+  if (n_multi) *n_multi = multi;
+  if (n_prefix) *n_prefix = prefix;
+  return multi + prefix;
+}
+
+// The counting pre-pass of a sharded tree batch marks a prefix phrase's documents in a bitmap of one bit per document, padded
+// to whole 256-byte lines; the phrases are counted in groups of as many bitmaps as `scratch` bytes hold, at most 65535 (the
+// group is a grid dimension).  How a rank groups is its own business: only the complete count vector leaves the pre-pass.
+inline int64_t text_prefix_bitmap_bytes(int64_t n_docs) {
+  const int64_t bits = n_docs < 1 ? 1 : n_docs;
+  return (bits + 2047) / 2048 * 256;
+}
+// phrases per group: 0 = not even one bitmap fits
+inline int64_t text_prefix_group(int64_t scratch, int64_t n_docs, int64_t n_prefix) {
+  int64_t g = scratch > 0 ? scratch / text_prefix_bitmap_bytes(n_docs) : 0;
+  if (g > 65535) g = 65535;
+  if (g > n_prefix) g = n_prefix;
+  return g < 0 ? 0 : g;
+}
+
 // B and top_k of a keyword search.  *why = a string literal.
 inline int text_check_call(int32_t B, int32_t top_k, const char** why) {
   *why = "";

@@ -288,6 +288,8 @@ EXPORTS = [
     "np_hip_index_set_column_text", "np_hip_text_match",
     "np_hip_index_set_text_shard", "np_hip_text_search_sharded", "np_hip_text_search_sharded_filtered",
     "np_hip_search_batch_sharded_filtered", "np_hip_search_hybrid_sharded",
+    "np_hip_text_search_expr_device", "np_hip_text_search_sharded_expr", "np_hip_text_search_sharded_expr_filtered",
+    "np_hip_search_hybrid_sharded_expr",
     "np_hip_index_set_groups", "np_hip_index_group_count", "np_hip_collapse", "np_hip_collapse_device",
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
@@ -434,6 +436,13 @@ def lib():
     L.np_hip_search_hybrid_sharded.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params),
                                                C.POINTER(np_text_query), i32, C.c_float, i32, vp, vp, vp, i64, vp,
                                                C.POINTER(np_filter), i32, vp, vp, vp, vp, vp]
+    L.np_hip_text_search_expr_device.argtypes = [vp, C.POINTER(np_text_expr), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_text_search_sharded_expr.argtypes = [vp, vp, C.POINTER(np_text_expr), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_text_search_sharded_expr_filtered.argtypes = [vp, vp, C.POINTER(np_text_expr), i32, i32, C.POINTER(np_filter), i32,
+                                                           vp, vp, vp, vp, vp]
+    L.np_hip_search_hybrid_sharded_expr.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.POINTER(np_search_params),
+                                                    C.POINTER(np_text_expr), i32, C.c_float, i32, vp, vp, vp, i64, vp,
+                                                    C.POINTER(np_filter), i32, vp, vp, vp, vp, vp]
     L.np_hip_index_set_groups.argtypes = [vp, vp, i64, i64]
     L.np_hip_index_group_count.argtypes = [vp]
     L.np_hip_index_group_count.restype = i64
@@ -662,8 +671,8 @@ class _CTextQueries:
         self.keep = []
         for j, q in enumerate(queries):
             if not hasattr(q, "mode"):
-                raise ValueError("a tree query (text.TextExpr) where only flat keyword queries are taken: the sharded, grouped "
-                                 "and device-pointer searches have no _expr form yet")
+                raise ValueError("a tree query (text.TextExpr) where only flat keyword queries are taken: the grouped searches "
+                                 "have no _expr form yet")
             terms = np.ascontiguousarray(q.terms, np.int32).reshape(-1)
             off = np.ascontiguousarray(q.phrase_offsets, np.int32).reshape(-1)
             self.keep += [terms, off]
@@ -2444,7 +2453,8 @@ class MmapIndex:
         return qs
 
     def _hybrid_text_queries(self, B, text_queries):
-        """... in ctypes form, for the calls that take flat queries only (a text.TextExpr is refused by name)."""
+        """... in ctypes form, for the calls that take flat queries only: the grouped ones (a text.TextExpr is refused by
+        name)."""
         return _CTextQueries(self._hybrid_compiled(B, text_queries))
 
     def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None, full_grammar: bool = False):

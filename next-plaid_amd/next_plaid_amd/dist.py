@@ -435,10 +435,11 @@ class CShardedSearcher:
     def text_search_device(self, queries, top_k: int, d_subsets=None, filters=None, out=None):
         """np_hip_text_search_sharded / _filtered as they are: text.TextQuery objects, the scope as a DeviceSubsets or as
         (compiled filters, host query map); returns (np_status, (ids, scores, counts) tensors on the device).  The caller
-        synchronises the stream and reads comm.status()."""
+        synchronises the stream and reads comm.status().  A text.TextExpr among the queries sends the whole batch to
+        np_hip_text_search_sharded_expr / _expr_filtered (flat queries are lifted to trees and keep their bytes)."""
         t = self.torch
         n, k = len(queries), max(int(top_k), 1)
-        tq = api._CTextQueries(list(queries))
+        tq, form = api._c_text_queries(list(queries))
         with t.cuda.stream(self.stream):
             if out is None:
                 out = self._outputs(n, k)
@@ -446,16 +447,18 @@ class CShardedSearcher:
             if filters is not None:
                 cf, qf = filters
                 qf = np.ascontiguousarray(qf, np.int32)
-                rc = api.lib().np_hip_text_search_sharded_filtered(self.index._h, self.comm._h, tq.arr, n, int(top_k), cf.arr, cf.n,
-                                                                   qf.ctypes.data_as(C.c_void_p), *o)
+                rc = getattr(api.lib(), f"np_hip_text_search_sharded{form}_filtered")(
+                    self.index._h, self.comm._h, tq.arr, n, int(top_k), cf.arr, cf.n, qf.ctypes.data_as(C.c_void_p), *o)
             else:
                 a = (None, None, None, 0, None) if d_subsets is None else d_subsets.args()
-                rc = api.lib().np_hip_text_search_sharded(self.index._h, self.comm._h, tq.arr, n, int(top_k), *a, *o)
+                rc = getattr(api.lib(), f"np_hip_text_search_sharded{form}")(self.index._h, self.comm._h, tq.arr, n, int(top_k),
+                                                                             *a, *o)
         return rc, out
 
-    def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None):
-        """MmapIndex.text_search over the shards (np_hip_text_search_sharded, np_hip_text_search_sharded_filtered)."""
-        B, live, qs, scope = self.index._live_text_queries(text_queries, subset, subsets, filters)
+    def text_search(self, text_queries, top_k: int, subset=None, subsets=None, filters=None, full_grammar: bool = False):
+        """MmapIndex.text_search over the shards (np_hip_text_search_sharded, np_hip_text_search_sharded_filtered and their
+        _expr forms: tree queries and full_grammar=True route as MmapIndex.text_search routes them)."""
+        B, live, qs, scope = self.index._live_text_queries(text_queries, subset, subsets, filters, full_grammar)
         with self.torch.cuda.stream(self.stream):
             if scope.cf is not None:
                 rc, out = self.text_search_device(qs, top_k, filters=(scope.cf, scope.qmap))
@@ -464,12 +467,13 @@ class CShardedSearcher:
             return self._finish(rc, out, len(live), live, B)
 
     def search_hybrid(self, queries, text_queries, params, alpha: float = 0.75, fusion: str = "relative_score",
-                      fetch_k: int | None = None, subsets=None, filters=None):
+                      fetch_k: int | None = None, subsets=None, filters=None, full_grammar: bool = False):
         """MmapIndex.search_hybrid over the shards (np_hip_search_hybrid_sharded): both global lists are merged on every rank,
-        every rank fuses."""
+        every rank fuses.  Tree queries (a text.TextExpr among them, or strings under full_grammar=True) go to
+        np_hip_search_hybrid_sharded_expr, as MmapIndex.search_hybrid routes them."""
         queries = list(queries)
         B = len(queries)
-        tq = self.index._hybrid_text_queries(B, text_queries)
+        tq, form = api._c_text_queries(self.index._hybrid_compiled(B, text_queries, full_grammar))
         fk = 3 * int(params.top_k) if fetch_k is None else int(fetch_k)
         scope = self.index._scope(B, None, subsets, filters, "search_hybrid")
         k = max(int(params.top_k), 1)
@@ -479,7 +483,7 @@ class CShardedSearcher:
             out = self._outputs(B, k)
             keep, a = self._device_scope(scope)
             qf = scope.qmap if scope.cf is not None else None   # (without filters the map travels with the CSR, on the device)
-            rc = api.lib().np_hip_search_hybrid_sharded(
+            rc = getattr(api.lib(), f"np_hip_search_hybrid_sharded{form}")(
                 self.index._h, self.comm._h, C.c_void_p(dq.data_ptr()), C.c_void_p(do.data_ptr()), off.ctypes.data_as(C.c_void_p),
                 B, self.index.embedding_dim(), C.byref(p), tq.arr, fk, float(alpha), api._fusion_mode(fusion), *a,
                 *scope.filter_args, api._ptr(qf), *self._out_args(out))
