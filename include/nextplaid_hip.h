@@ -783,9 +783,9 @@ int np_hip_search_hybrid_expr(const np_index* index, const float* queries, const
  *   sharded handles   a group's members can lie on several shards, and a member's shard-local group can fall outside that
  *                     shard's local top_k groups while the group is in the global top_k: per-shard grouped lists do not merge
  *                     exactly for group_size > 1.  The handle is refused, not approximated.
- *   grouped search_exact beyond the pool   the true grouped top-k over all documents needs a per-query, per-group maximum table
- *                     across scan passes and a second pass for members.  np_hip_collapse of np_hip_search_exact(top_k = pool_k)
- *                     is available.
+ *   hybrid grouped search beyond the pool   np_hip_search_hybrid_grouped stays pool-bound: the fused score of a document depends
+ *                     on both ranked lists, so there is no per-document key to fold.  (The semantic side has an exact form:
+ *                     np_hip_search_exact_grouped below.)
  *   ColGREP's score adjustments   the path penalty, the boosts and the line-span merge are application code on at most 200
  *                     rows; out_total and a large group_size give the host what it needs for the span. */
 #define NP_GROUP_MAX_LIST 16384
@@ -814,6 +814,38 @@ int np_hip_search_hybrid_grouped(const np_index* index, const float* queries, co
                                  int32_t pool_k, int32_t group_size,
                                  int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members,
                                  int32_t* out_total, int32_t* out_counts, np_stats* stats);
+
+/* ---- exact grouped search: the true top_k groups over every document --------------------------------
+ * The grouped entries above rank a pool and collapse it: a group whose best member lies beyond pool_k is lost, and total counts
+ * only what reached the pool.  This entry has no pool.  Let L be the COMPLETE ranked list of query i's scope -- what
+ * np_hip_search_exact returns when top_k covers every document in scope: score descending, ties by ascending id, a non-finite
+ * score last and returned as NaN, empty documents absent.  Query i gets np_hip_collapse of L with (top_k, group_size), byte for
+ * byte in all six regions (the layout and padding of np_hip_collapse): the first top_k distinct groups of L, of each its
+ * first group_size members with np_hip_search_exact's score bits, members, and total = the in-scope (non-empty) documents of
+ * the group.  L itself is never formed.
+ *   arguments   queries, precision (0 or 3), the CSR scope and its checks: np_hip_search_exact's; the filtered form takes
+ *               np_hip_search_exact_filtered's (filters, n_filters, query_filter[B])
+ *   limits      1 <= top_k, 1 <= group_size, top_k * group_size <= NP_GROUP_MAX_LIST (the slots of an output row); at most 256
+ *               tokens per query.  NP_ERR_INVALID_ARGUMENT before any allocation or launch: no groups set, a sharded handle
+ *               (see "out of scope" above), top_k or group_size out of range.
+ *   independent query i's result is the same, bit for bit, alone, in any batch, under any "scan_tiles", "scan_docs", max_batch or
+ *               workspace_bytes, and from run to run: maxima and sums are the only things reduced with atomics
+ *   memory      12 bytes per (query, group) -- the group's best key and its count -- from the context's workspace budget; the
+ *               batch runs in chunks of as many queries as it holds.  One query's row not fitting is NP_ERR_OUT_OF_MEMORY.
+ *   cost        one exact scan of the scope, plus -- for group_size > 1 -- a second walk that re-scores only the documents of
+ *               the selected groups
+ *   stats       ms_total and n_queries */
+int np_hip_search_exact_grouped(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B, int32_t dim,
+                                int32_t top_k, int32_t group_size, int32_t precision,
+                                const int64_t* subset_ids, const int64_t* subset_offsets, int64_t n_subsets,
+                                const int32_t* query_subset,
+                                int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members,
+                                int32_t* out_total, int32_t* out_counts, np_stats* stats);
+int np_hip_search_exact_grouped_filtered(const np_index* index, const float* queries, const int32_t* q_tok_offsets, int32_t B,
+                                         int32_t dim, int32_t top_k, int32_t group_size, int32_t precision,
+                                         const np_filter* filters, int32_t n_filters, const int32_t* query_filter,
+                                         int64_t* out_ids, float* out_scores, int32_t* out_group, int32_t* out_members,
+                                         int32_t* out_total, int32_t* out_counts, np_stats* stats);
 
 /* ---- document-sharded search (one process per GPU) -------------------------
  * Phase A runs S1-S5 on the local shard and leaves, per query, the shard's best

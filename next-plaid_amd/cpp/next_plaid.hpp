@@ -13,6 +13,7 @@
 //   index.set_text(...) / text_search(...) / fuse(...) / search_hybrid(...)   the keyword half of a hybrid search (text_search.rs);
 //                                                          TextQuery = flat AND / OR, TextExpr = FTS5's NOT, parentheses, prefixes
 //   index.set_groups(...) / collapse(...) / search_grouped(...) / search_hybrid_grouped(...)   top-k groups with their best documents
+//   index.search_exact_grouped(queries, n, top_k, group_size, precision, subsets)   the true top-k groups: every document scored
 //   SearchParameters (defaults search.rs:58-69), QueryResult (search.rs:71-80), Error (error.rs:9-66)
 //
 // Accelerator policy (the crate's precedent for its CUDA feature, lib.rs:71-84 and cuda.rs:52-182):
@@ -1210,6 +1211,23 @@ class MmapIndex {
                                       (int32_t)(pool_k ? pool_k : default_pool_k(params.top_k, NP_GROUP_MAX_LIST)), (int32_t)group_size,
                                       b.ids.data(), b.sc.data(), b.group.data(), b.members.data(), b.total.data(), b.cnt.data(),
                                       &last_stats));
+    return b.groups(n, true);
+  }
+
+  // np_hip_search_exact_grouped: the TRUE top_k groups over every document of the scope, no pool -- query i gets
+  // collapse(search_exact(top_k = every document in scope)), so no group is lost beyond a pool and `total` counts every
+  // in-scope document of the group.  precision and one scope per query as search_exact_subsets takes them.
+  std::vector<GroupedResult> search_exact_grouped(const Query* queries, size_t n, size_t top_k, size_t group_size = 1,
+                                                  int precision = 0,
+                                                  const std::vector<const std::vector<int64_t>*>& subsets = {}) const {
+    require_device("search_exact_grouped");
+    const SubsetArgs s(subsets, n, "search_exact_grouped");
+    const PackedQueries q = pack_queries(queries, n);
+    GroupBuffers b(n, top_k, group_size);
+    check(np_hip_search_exact_grouped(h_, q.flat.data(), q.off.data(), (int32_t)n, (int32_t)embedding_dim(), (int32_t)top_k,
+                                      (int32_t)group_size, (int32_t)precision, s.sids.data(), s.soff.data(), (int64_t)s.n_distinct,
+                                      s.qsub.data(), b.ids.data(), b.sc.data(), b.group.data(), b.members.data(), b.total.data(),
+                                      b.cnt.data(), &last_stats));
     return b.groups(n, true);
   }
 

@@ -292,6 +292,7 @@ EXPORTS = [
     "np_hip_search_hybrid_sharded_expr",
     "np_hip_index_set_groups", "np_hip_index_group_count", "np_hip_collapse", "np_hip_collapse_device",
     "np_hip_search_batch_grouped", "np_hip_search_hybrid_grouped",
+    "np_hip_search_exact_grouped", "np_hip_search_exact_grouped_filtered",
     "np_hip_text_build", "np_hip_text_build_fallback", "np_hip_text_build_add", "np_hip_text_build_sizes",
     "np_hip_text_build_fetch", "np_hip_text_build_free", "np_hip_text_build_merge",
     "np_hip_index_set_text_build", "np_hip_index_set_text_build_bytes", "np_hip_index_text_merge", "np_hip_index_text_sizes",
@@ -453,6 +454,10 @@ def lib():
     L.np_hip_search_hybrid_grouped.argtypes = [vp, vp, vp, i32, i32, C.POINTER(np_search_params), C.POINTER(np_text_query), i32,
                                                C.c_float, i32, vp, vp, i64, vp, C.POINTER(np_filter), i32, i32, i32,
                                                vp, vp, vp, vp, vp, vp, C.POINTER(np_stats)]
+    L.np_hip_search_exact_grouped.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                              C.POINTER(np_stats)]
+    L.np_hip_search_exact_grouped_filtered.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(np_filter), i32, vp,
+                                                       vp, vp, vp, vp, vp, vp, C.POINTER(np_stats)]
     L.np_hip_search_phase_b.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_search_end.argtypes = [vp, vp]
     L.np_hip_search_end.restype = None
@@ -2560,6 +2565,30 @@ class MmapIndex:
         st = np_stats()
         _check(lib().np_hip_search_batch_grouped(self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), C.byref(p), *scope.csr,
                                                  *scope.filter_args, pk, int(group_size), *[_ptr(o) for o in out], C.byref(st)))
+        self.last_stats = st.as_dict()
+        return out if raw else _groups_of_rows(B, k, g, *out)
+
+    def search_exact_grouped(self, queries, top_k: int, group_size: int = 1, precision: int = 0, subset=None, subsets=None,
+                             filters=None, raw: bool = False):
+        """np_hip_search_exact_grouped: the TRUE top_k groups (set_groups) over every document of the scope, each with its best
+        group_size documents -- query i gets collapse(search_exact(top_k = every document in scope)) without that list being
+        formed: no pool, so no group is lost beyond one and `total` counts every in-scope document of the group.  Scores are
+        search_exact's bits.  Scope and precision as search_exact takes them.  Returns what search_grouped returns."""
+        if isinstance(queries, np.ndarray) and queries.ndim == 2:
+            queries = [queries]
+        queries = list(queries)
+        flat, off = self._pack(queries)
+        B = len(queries)
+        scope = self._scope(B, subset, subsets, filters, "search_exact_grouped")
+        k, g = max(int(top_k), 1), max(int(group_size), 1)
+        out = _group_outputs(B, k, g)
+        st = np_stats()
+        head = (self._h, _ptr(flat), _ptr(off), B, self.embedding_dim(), int(top_k), int(group_size), int(precision))
+        if scope.form == "filters":
+            _check(lib().np_hip_search_exact_grouped_filtered(*head, *scope.filter_args, _ptr(scope.qmap), *[_ptr(o) for o in out],
+                                                              C.byref(st)))
+        else:
+            _check(lib().np_hip_search_exact_grouped(*head, *scope.csr, *[_ptr(o) for o in out], C.byref(st)))
         self.last_stats = st.as_dict()
         return out if raw else _groups_of_rows(B, k, g, *out)
 
