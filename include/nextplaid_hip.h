@@ -1099,6 +1099,51 @@ int np_hip_rerank_maxsim(int32_t device, const float* query, int32_t n_query_tok
                          const float* doc_embeddings, const int64_t* doc_tok_offsets, int64_t n_docs,
                          float* out_scores, int64_t* out_order);
 
+/* ---- batched MaxSim on caller-supplied embeddings (np_maxsim.hip) --------------------------------------------
+ * maxsim::maxsim_score (maxsim.rs:270-294) for many queries at once, on matrix instructions, for rows of any width up to
+ * 1024: what np_hip_rerank_maxsim's scalar loop (one query, host pointers, the REST handler's operation order) is not
+ * meant for.  Needs no index.  queries: [q_tok_offsets[B]][dim] rows, query i owns rows q_tok_offsets[i] ..
+ * q_tok_offsets[i+1]; documents likewise with doc_tok_offsets [n_docs + 1].  Rows are `dim` elements apart, unpadded.
+ *   dtype       NP_DT_F32 (f32 rows) or NP_DT_BF16 (rows as raw 16-bit words); it applies to queries and documents
+ *   precision   0 = f32 MFMA (v_mfma_f32_32x32x2f32), NP_DT_F32 only; 3 = bf16 MFMA (v_mfma_f32_32x32x16_bf16): f32 rows
+ *               are rounded to bf16 in the kernel (nearest, ties to even), bf16 rows are used as they are.  Any other
+ *               combination: NP_ERR_INVALID_ARGUMENT
+ *   pairs       pair_docs / pair_offsets [B + 1]: query i is scored against documents pair_docs[pair_offsets[i] ..
+ *               pair_offsets[i+1]) (any order, repeats allowed), out_scores [pair_offsets[B]] in list order.  Both NULL:
+ *               all pairs, out_scores [B][n_docs] query-major
+ *   semantics   rows are taken as given, nothing is normalised.  sim[q][t] = the row dot product, accumulated in f32 in
+ *               ascending dim order; per query token the maximum over the document's tokens, non-finite sims ignored; the
+ *               score is the f32 sum of those maxima in query-token order starting from 0.0f, a token without a finite
+ *               sim adding nothing.  An empty document or an empty query scores 0.
+ *   matches     out_match_sims / out_match_pos (each nullable; precision 0 only: a position has no meaning under bf16
+ *               rounding, see np_hip_score_pairs): one entry per (pair, query token), pair after pair in the order of
+ *               out_scores, a pair's row in query-token order.  The maximum and the lowest document-token index that
+ *               reaches it; 0.0 and -1 where no sim is finite.  The score equals the ordered f32 sum of its row, bit for
+ *               bit, and is the same bits with and without the match outputs.
+ *   independent a pair's score and matches depend on its two matrices only: the same bits alone or in any batch, listed
+ *               or through all pairs, at any place in the list, through either entry, from run to run
+ *   limits      checked before any allocation or launch, the message naming the argument: 1 <= dim <= 1024 and at most 256
+ *               tokens per query (NP_ERR_SHAPE); offsets start at 0 and do not decrease, pair ids lie in [0, n_docs)
+ *               (NP_ERR_INVALID_ARGUMENT).  Document length is unbounded (positions are i32).  B = 0 or no pairs: NP_OK,
+ *               nothing written.
+ *   memory      the host entry stages the call through ONE device allocation and frees it.  The device entry allocates
+ *               nothing and needs no scratch. */
+#define NP_DT_F32 0
+#define NP_DT_BF16 1
+int np_hip_maxsim_batch(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
+                        const int32_t* q_tok_offsets, int32_t B, const void* documents, const int64_t* doc_tok_offsets,
+                        int64_t n_docs, const int64_t* pair_docs, const int64_t* pair_offsets /* [B+1]; both NULL = all pairs */,
+                        float* out_scores, float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+/* The same with every array in HBM and the three offset arrays also as host copies (which must agree with the device
+ * copies; h_pair_offsets NULL with the two device pair arrays NULL = all pairs); enqueues on `stream` and returns.  The pair
+ * ids cannot be checked here: one outside [0, n_docs) scores NaN with matches 0.0 / -1. */
+int np_hip_maxsim_batch_device(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
+                               const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                               const void* d_documents, const int64_t* d_doc_tok_offsets, const int64_t* h_doc_tok_offsets,
+                               int64_t n_docs, const int64_t* d_pair_docs, const int64_t* d_pair_offsets,
+                               const int64_t* h_pair_offsets, float* d_out_scores, float* d_out_match_sims,
+                               int32_t* d_out_match_pos, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

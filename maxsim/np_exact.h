@@ -2,7 +2,7 @@
 // decompression of one 32-token tile straight into MFMA A fragments, the row scales and the masked row maximum.
 // exact_f32_kernel / exact_bf16_kernel (np_kernels.h, S6: one query, its selected documents) and scan_kernel (np_scan.hip:
 // every document, many queries) call these same definitions, so a (query, document) pair gets the same bits from both.
-// Included after np_internal.h (CodeArr).
+// Included after np_internal.h (CodeArr).  Lives in maxsim/ beside np_maxsim.hip, which uses its index-free part.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,0 +1,94 @@
+// np_maxsim_plan.h -- the host side of np_hip_maxsim_batch that needs no device: the constants of the kernel's tiling, the
+// argument checks and the split of a call into workgroups.  Plain C++; np_maxsim.hip includes it for the same constants.
+#pragma once
+#include <stdint.h>
+
+namespace np {
+
+constexpr int NP_MS_DT_F32 = 0, NP_MS_DT_BF16 = 1;   // NP_DT_F32 / NP_DT_BF16 of the public header
+constexpr int NP_MS_MAX_DIM = 1024;
+constexpr int NP_MS_MAX_QUERY_TOKENS = 256;   // eight 32-token query tiles, as S6
+constexpr int NP_MS_KC_F32 = 32;              // dims per LDS chunk, f32 MFMA (16 steps of 32x32x2)
+constexpr int NP_MS_KC_BF16 = 64;             // dims per LDS chunk, bf16 MFMA (4 steps of 32x32x16)
+constexpr int NP_MS_WG_DOCS = 4;              // documents a workgroup scores at most (one per wave when they are short)
+constexpr int NP_MS_MAX_SLOTS = 8;            // 32-token query tiles a workgroup holds accumulators for
+constexpr int64_t NP_MS_MAX_GRID_X = 0x7FFFFFFF;
+constexpr int NP_MS_MAX_GRID_Y = 65535;
+
+// The checks that need only host arrays.  0 = fine, 1 = shape error, 2 = invalid argument; *why names the argument (a
+// string literal).  pair_docs may be NULL with a list (the device entry cannot see the ids); *bad_pair = the first pair
+// whose id lies outside [0, n_docs), when the return value is 2 because of one (-1 otherwise).
+inline int maxsim_check_args(int32_t dtype, int32_t precision, int32_t dim, int32_t B, const int32_t* q_tok_offsets,
+                             int64_t n_docs, const int64_t* doc_tok_offsets, bool listed, const int64_t* pair_docs,
+                             const int64_t* pair_offsets, bool want_matches, const char** why, int64_t* bad_pair) {
+  *why = "";
+  *bad_pair = -1;
+  if (dim < 1 || dim > NP_MS_MAX_DIM) return *why = "dim must lie in 1 .. 1024", 1;
+  if (dtype != NP_MS_DT_F32 && dtype != NP_MS_DT_BF16) return *why = "dtype must be NP_DT_F32 (0) or NP_DT_BF16 (1)", 2;
+  if (precision != 0 && precision != 3) return *why = "precision must be 0 (f32 MFMA) or 3 (bf16 MFMA)", 2;
+  if (precision == 0 && dtype != NP_MS_DT_F32) return *why = "dtype NP_DT_BF16 needs precision 3", 2;
+  if (want_matches && precision != 0)
+    return *why = "out_match_sims / out_match_pos need precision 0: a position has no meaning under bf16 rounding", 2;
+  if (B < 0) return *why = "B is negative", 2;
+  if (n_docs < 0) return *why = "n_docs is negative", 2;
+  if (B > 0 && !q_tok_offsets) return *why = "q_tok_offsets is NULL", 2;
+  if (n_docs > 0 && !doc_tok_offsets) return *why = "doc_tok_offsets is NULL", 2;
+  if (B > 0 && q_tok_offsets[0] != 0) return *why = "q_tok_offsets must start at 0", 2;
+  for (int b = 0; b < B; ++b) {
+    const int64_t lq = (int64_t)q_tok_offsets[b + 1] - q_tok_offsets[b];
+    if (lq < 0) return *why = "q_tok_offsets must not decrease", 2;
+    if (lq > NP_MS_MAX_QUERY_TOKENS) return *why = "q_tok_offsets: a query has more than 256 tokens", 1;
+  }
+  if (n_docs > 0 && doc_tok_offsets[0] != 0) return *why = "doc_tok_offsets must start at 0", 2;
+  for (int64_t i = 0; i < n_docs; ++i)
+    if (doc_tok_offsets[i + 1] < doc_tok_offsets[i]) return *why = "doc_tok_offsets must not decrease", 2;
+  if (!listed) {
+    if ((n_docs + NP_MS_WG_DOCS - 1) / NP_MS_WG_DOCS > NP_MS_MAX_GRID_X) return *why = "n_docs exceeds one launch", 2;
+    return 0;
+  }
+  if (B > 0 && !pair_offsets) return *why = "pair_offsets is NULL", 2;
+  if (B > 0 && pair_offsets[0] != 0) return *why = "pair_offsets must start at 0", 2;
+  for (int b = 0; b < B; ++b) {
+    if (pair_offsets[b + 1] < pair_offsets[b]) return *why = "pair_offsets must not decrease", 2;
+    if (pair_offsets[b + 1] - pair_offsets[b] > NP_MS_MAX_GRID_X) return *why = "pair_offsets: a query has more pairs than one launch takes", 2;
+  }
+  if (B > 0 && pair_offsets[B] > 0 && n_docs == 0) return *why = "pair_docs names documents but n_docs is 0", 2;
+  if (pair_docs && B > 0)
+    for (int64_t i = 0; i < pair_offsets[B]; ++i)
+      if (pair_docs[i] < 0 || pair_docs[i] >= n_docs) return *bad_pair = i, *why = "pair_docs names a document outside [0, n_docs)", 2;
+  return 0;
+}
+
+// How a call maps to workgroups.  A workgroup holds `slots` = G * nqt query tiles (nqt = tiles of the call's longest query;
+// G queries of a group in all-pairs form, 1 in listed form) and walks the 32-token tiles of WD documents with its 4 waves.
+// Both shrink while the grid would leave compute units idle: a pair's bits do not depend on either (np_maxsim.hip).
+// NQT = the kernel instantiation (1, 2, 4 or 8 accumulator tiles) that holds the slots.
+struct MaxsimPlan {
+  int nqt = 1, G = 1, WD = NP_MS_WG_DOCS, NQT = 1;
+  int64_t gx = 0;   // workgroups along x: document groups (all pairs) or the longest list's groups (listed)
+  int64_t gy = 0;   // along y: query groups (all pairs) or queries (listed); launched in slices of NP_MS_MAX_GRID_Y
+};
+inline MaxsimPlan maxsim_plan(bool listed, const int32_t* q_tok_offsets, int32_t B, int64_t n_docs,
+                              const int64_t* pair_offsets, int compute_units) {
+  MaxsimPlan p;
+  int max_lq = 1;
+  int64_t max_n = listed ? 0 : n_docs;
+  for (int b = 0; b < B; ++b) {
+    if (q_tok_offsets[b + 1] - q_tok_offsets[b] > max_lq) max_lq = q_tok_offsets[b + 1] - q_tok_offsets[b];
+    if (listed && pair_offsets[b + 1] - pair_offsets[b] > max_n) max_n = pair_offsets[b + 1] - pair_offsets[b];
+  }
+  p.nqt = (max_lq + 31) / 32;
+  p.G = listed ? 1 : (NP_MS_MAX_SLOTS / p.nqt < B ? NP_MS_MAX_SLOTS / p.nqt : B);
+  if (p.G < 1) p.G = 1;
+  const int64_t want = 2 * (int64_t)(compute_units > 0 ? compute_units : 256);
+  auto wgs = [&]() { return ((B + p.G - 1) / p.G) * ((max_n + p.WD - 1) / p.WD); };
+  while (p.WD > 1 && wgs() < want) p.WD /= 2;
+  while (p.G > 1 && wgs() < want) p.G = (p.G + 1) / 2;
+  const int slots = p.G * p.nqt;
+  p.NQT = slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : 8;
+  p.gx = (max_n + p.WD - 1) / p.WD;
+  p.gy = (B + p.G - 1) / p.G;
+  return p;
+}
+
+}  // namespace np

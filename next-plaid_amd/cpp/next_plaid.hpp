@@ -1580,6 +1580,50 @@ inline std::pair<std::vector<int64_t>, std::vector<float>> rerank_maxsim(const f
   return {std::move(order), std::move(scores)};
 }
 
+// np_hip_maxsim_batch: MaxSim of caller-supplied f32 embeddings on the MFMA kernel (dim <= 1024, at most 256 tokens per
+// query; the library refuses the rest and `check` throws).  queries / docs are flat [tokens][dim] rows with their token
+// offsets; `pairs` holds one id list per query, or is empty for all pairs (scores [B][n_docs], query-major).  precision 0 =
+// f32 MFMA, 3 = bf16 MFMA (rows rounded in the kernel).  With want_matches (precision 0) every (pair, query token) also
+// gets its best document token: sims / positions, pair after pair in the order of the scores.
+struct MaxsimScores {
+  std::vector<float> scores, sims;
+  std::vector<int32_t> positions;
+};
+inline MaxsimScores maxsim_scores(const float* queries, const std::vector<int32_t>& q_tok_offsets, const float* docs,
+                                  const std::vector<int64_t>& doc_tok_offsets, size_t dim,
+                                  const std::vector<std::vector<int64_t>>& pairs = {}, int precision = 0,
+                                  bool want_matches = false, int device = 0) {
+  const size_t B = q_tok_offsets.empty() ? 0 : q_tok_offsets.size() - 1;
+  const size_t n = doc_tok_offsets.empty() ? 0 : doc_tok_offsets.size() - 1;
+  const bool listed = !pairs.empty();
+  if (listed && pairs.size() != B) throw Error(NP_ERR_INVALID_ARGUMENT, "maxsim_scores: one list of document ids per query");
+  std::vector<int64_t> ids, poff(B + 1, 0);
+  size_t rows = 0;
+  for (size_t b = 0; b < B; ++b) {
+    const size_t nb = listed ? pairs[b].size() : n;
+    if (listed) ids.insert(ids.end(), pairs[b].begin(), pairs[b].end());
+    poff[b + 1] = poff[b] + (int64_t)nb;
+    rows += nb * (size_t)std::max(q_tok_offsets[b + 1] - q_tok_offsets[b], 0);
+  }
+  MaxsimScores out;
+  out.scores.assign(std::max<size_t>((size_t)poff[B], 1), 0.f);
+  if (want_matches) {
+    out.sims.assign(std::max<size_t>(rows, 1), 0.f);
+    out.positions.assign(std::max<size_t>(rows, 1), -1);
+  }
+  if (listed && ids.empty()) ids.push_back(0);
+  check(np_hip_maxsim_batch(device, NP_DT_F32, (int32_t)precision, (int32_t)dim, queries, q_tok_offsets.data(), (int32_t)B, docs,
+                            doc_tok_offsets.data(), (int64_t)n, listed ? ids.data() : nullptr, listed ? poff.data() : nullptr,
+                            out.scores.data(), want_matches ? out.sims.data() : nullptr,
+                            want_matches ? out.positions.data() : nullptr));
+  out.scores.resize((size_t)poff[B]);
+  if (want_matches) {
+    out.sims.resize(rows);
+    out.positions.resize(rows);
+  }
+  return out;
+}
+
 // ---- token pooling: next-plaid-onnx src/lib.rs:1632-1643 pool_document_embeddings, :2249-2317, hierarchy.rs ------------
 enum class PoolCut { Reference = 0, Distance = 1 };   // chain order (the crate) / stable order by merge distance (scipy, PyLate)
 

@@ -300,6 +300,7 @@ EXPORTS = [
     "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity", "np_hip_index_remove",
     "np_hip_index_remove_keep", "np_hip_index_append_rows", "np_hip_index_get_column", "np_hip_index_get_groups",
     "np_hip_index_expand", "np_hip_index_expand_rows",
+    "np_hip_maxsim_batch", "np_hip_maxsim_batch_device",
 ]
 
 _lib = None
@@ -468,6 +469,8 @@ def lib():
     L.np_hip_decompress_documents.argtypes = [vp, vp, i64, vp, i64, vp]
     L.np_hip_encode_tokens.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.np_hip_rerank_maxsim.argtypes = [i32, vp, i32, i32, vp, vp, i64, vp, vp]
+    L.np_hip_maxsim_batch.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_maxsim_batch_device.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.np_hip_debug_trace.argtypes = [vp, vp, i32, i32, C.POINTER(np_search_params), vp, i64,
                                      vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]
     L.np_hip_kmeans_plan.argtypes = [vp, i64, C.POINTER(np_index_config), C.POINTER(np_kmeans_plan), vp]
@@ -583,6 +586,110 @@ def rerank_maxsim(query, documents, device: int = 0):
     _check(lib().np_hip_rerank_maxsim(int(device), _ptr(q), q.shape[0], q.shape[1], _ptr(flat), _ptr(off), len(docs),
                                       _ptr(scores), _ptr(order)))
     return order[: len(docs)], scores[: len(docs)]
+
+
+NP_DT_F32, NP_DT_BF16 = 0, 1
+MAXSIM_CHUNK_F32, MAXSIM_CHUNK_BF16 = 32, 64     # NP_MS_KC_F32 / NP_MS_KC_BF16 of np_maxsim_plan.h: dims per LDS chunk
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _maxsim_pack(mats, offsets, what):
+    """(flat [tokens, dim], offsets i64) of a list of 2-D arrays, or of a flat array plus offsets (handed on as given)."""
+    if offsets is not None:
+        return mats, np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    mats = list(mats)
+    for m in mats:
+        if m.ndim != 2:
+            raise ShapeError(f"Shape error: a {what} has shape {tuple(m.shape)}")
+    off = np.zeros(len(mats) + 1, np.int64)
+    if mats:
+        off[1:] = np.cumsum([m.shape[0] for m in mats])
+    if mats and _is_torch(mats[0]):
+        import torch
+        return torch.cat(mats, 0).contiguous(), off
+    width = mats[0].shape[1] if mats else 1
+    dt = mats[0].dtype if mats else np.float32
+    flat = np.concatenate(mats, 0) if mats else np.zeros((0, width), dt)
+    return np.ascontiguousarray(flat), off
+
+
+def maxsim_scores(queries, documents, pairs=None, precision: int = 0, return_matches: bool = False, device: int = 0,
+                  query_offsets=None, document_offsets=None):
+    """np_hip_maxsim_batch: MaxSim (maxsim.rs:270-294) of caller-supplied multi-vector embeddings on the MFMA kernel of
+    np_maxsim.hip, dim up to 1024, rows taken as given (nothing is normalised).
+
+    queries / documents: lists of [tokens, dim] arrays, or one flat [tokens, dim] array each with query_offsets /
+    document_offsets.  numpy arrays (float32; anything else is converted) go through the host entry; torch tensors on the
+    device (float32 or bfloat16) go through np_hip_maxsim_batch_device on torch's current stream, with no host copy, and
+    the results come back as tensors on that device.  pairs: one list of document ids per query (any order, repeats
+    allowed); None = all pairs.  precision 0 = f32 MFMA, 3 = bf16 MFMA (bfloat16 tensors need 3).
+
+    Returns, per query, its scores (f32 [n_i]); with return_matches (precision 0) a tuple (scores, sims [n_i, Lq_i],
+    positions i32 [n_i, Lq_i]): per query token the best document token's similarity and the lowest index reaching it
+    (0.0 and -1 where no similarity is finite); a score is the ordered f32 sum of its row of sims."""
+    qf, qoff = _maxsim_pack(queries, query_offsets, "query")
+    df, doff = _maxsim_pack(documents, document_offsets, "document")
+    if qoff.size <= 1:
+        return []
+    on_dev = _is_torch(qf)
+    if on_dev != _is_torch(df):
+        raise ValueError("maxsim_scores: queries and documents must both be numpy arrays or both torch tensors")
+    if qf.ndim != 2 or df.ndim != 2 or qf.shape[1] != df.shape[1]:
+        raise ShapeError(f"Shape error: queries {tuple(qf.shape)} and documents {tuple(df.shape)} must be [tokens, dim] of one dim")
+    dim = int(qf.shape[1])
+    B, n_docs = qoff.size - 1, doff.size - 1
+    qoff32 = np.ascontiguousarray(qoff, np.int32)
+    if pairs is None:
+        ids = poff = None
+        n = np.full(B, n_docs, np.int64)
+    else:
+        lists = [np.ascontiguousarray(x, np.int64).reshape(-1) for x in pairs]
+        if len(lists) != B:
+            raise ValueError(f"pairs has {len(lists)} entries for {B} queries")
+        n = np.array([x.size for x in lists], np.int64)
+        poff = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        ids = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        if ids.size == 0:
+            ids = np.zeros(1, np.int64)
+    lq = np.maximum(np.diff(qoff), 0)
+    P, R = int(n.sum()), int((n * lq).sum())
+    L = lib()
+    if on_dev:
+        import torch
+        if qf.dtype != df.dtype or qf.dtype not in (torch.float32, torch.bfloat16) or not qf.is_cuda or not df.is_cuda:
+            raise ValueError("maxsim_scores: device tensors must both be float32 or both bfloat16, on the GPU")
+        dev = qf.device
+        dtype = NP_DT_BF16 if qf.dtype == torch.bfloat16 else NP_DT_F32
+        qf, df = qf.contiguous(), df.contiguous()
+        t = lambda a: None if a is None else torch.from_numpy(a).to(dev)   # noqa: E731
+        tp = lambda x: None if x is None else C.c_void_p(x.data_ptr())    # noqa: E731
+        d_qoff, d_doff, d_ids, d_poff = t(qoff32), t(doff), t(ids), t(poff)
+        sc = torch.zeros(max(P, 1), dtype=torch.float32, device=dev)
+        sims = torch.zeros(max(R, 1), dtype=torch.float32, device=dev) if return_matches else None
+        pos = torch.zeros(max(R, 1), dtype=torch.int32, device=dev) if return_matches else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(L.np_hip_maxsim_batch_device(dev.index or 0, dtype, int(precision), dim, tp(qf), tp(d_qoff), _ptr(qoff32), B,
+                                            tp(df), tp(d_doff), _ptr(doff), n_docs, tp(d_ids), tp(d_poff), _ptr(poff), tp(sc),
+                                            tp(sims), tp(pos), C.c_void_p(stream)))
+    else:
+        qf, df = np.ascontiguousarray(qf, np.float32), np.ascontiguousarray(df, np.float32)
+        sc = np.zeros(max(P, 1), np.float32)
+        sims = np.zeros(max(R, 1), np.float32) if return_matches else None
+        pos = np.zeros(max(R, 1), np.int32) if return_matches else None
+        _check(L.np_hip_maxsim_batch(int(device), NP_DT_F32, int(precision), dim, _ptr(qf), _ptr(qoff32), B, _ptr(df),
+                                     _ptr(doff), n_docs, _ptr(ids), _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos)))
+    out, p0, r0 = [], 0, 0
+    for i in range(B):
+        ni, li = int(n[i]), int(lq[i])
+        if return_matches:
+            out.append((sc[p0:p0 + ni], sims[r0:r0 + ni * li].reshape(ni, li), pos[r0:r0 + ni * li].reshape(ni, li)))
+        else:
+            out.append(sc[p0:p0 + ni])
+        p0, r0 = p0 + ni, r0 + ni * li
+    return out
 
 
 def device_count() -> int:

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Print VGPR/AGPR/scratch/occupancy/LDS per kernel of a .hip file (hipcc -Rpass-analysis)."""
+"""Print VGPR/AGPR/scratch/occupancy/LDS per kernel of a .hip file (hipcc -Rpass-analysis).  Arguments after the file are
+handed to hipcc: a rule of the Makefile that adds flags (np_maxsim.o) is reproduced by repeating them here."""
+import os
 import re
 import subprocess
 import sys
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = sys.argv[1]
-out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src,
+inc = ["-I" + os.path.join(ROOT, "next-plaid_amd", "csrc"), "-I" + os.path.join(ROOT, "maxsim")]   # the Makefile's include paths
+out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *inc, *sys.argv[2:], "-c", src,
                       "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True).stderr
 keys = {"VGPRs": "V", "AGPRs": "A", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occ",
         "LDS Size [bytes/block]": "lds", "TotalSGPRs": "S"}

@@ -1,0 +1,94 @@
+"""Times np_hip_maxsim_batch (maxsim_scores on device tensors) against rerank_maxsim called once per query and against
+torch (matmul + amax + sum on the device), alternating in one process, and writes profiles/maxsim_time.md.
+
+    python tools/maxsim_time.py [--rounds 5] [--out profiles/maxsim_time.md]
+
+Call time is device-synchronised wall time; a window repeats a call until it is at least 0.2 s long (after a warm-up
+call).  FLOP/s = 2 * query tokens * document tokens * dim per pair; bytes/s = ALL rows of the call's arrays once plus the
+scores (listed shapes read fewer documents than that).  These are call figures, not kernel figures: a maxsim_batch call
+includes maxsim_scores' packing of the pair lists and its host-to-device copies of the offsets and ids."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "next-plaid_amd"))
+import next_plaid_amd as npa  # noqa: E402
+
+# (name, queries, query tokens, documents, document tokens, dim, listed documents per query or None = all pairs)
+SHAPES = [("64 x 1000 listed x 300 tok, dim 128", 64, 32, 4000, 300, 128, 1000),
+          ("32 x 32 all pairs, 1030-tok pages, dim 128", 32, 24, 32, 1030, 128, None),
+          ("16 x 200 listed x 300 tok, dim 1024", 16, 32, 800, 300, 1024, 200)]
+
+
+def window(fn, sync):
+    fn(); sync()
+    n, t0 = 0, time.perf_counter()
+    while True:
+        fn(); sync()
+        n += 1
+        dt = time.perf_counter() - t0
+        if dt >= 0.2:
+            return dt / n
+
+
+def main():
+    import torch
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "maxsim_time.md"))
+    a = ap.parse_args()
+    sync = torch.cuda.synchronize
+    lines = ["# np_hip_maxsim_batch against rerank_maxsim per query and torch", "",
+             "Median call time over %d alternating rounds (min .. max), device-synchronised.  Call figures, not kernel" % a.rounds,
+             "figures: maxsim_batch includes the Python packing of the pair lists and the copies of offsets and ids; bytes count",
+             "every row of the call's arrays once, also where a list names only some documents.", "",
+             "| shape | path | ms | spread ms | TFLOP/s | GB/s |", "|---|---|---|---|---|---|"]
+    g = np.random.default_rng(1)
+    for name, B, lq, nd, ld, dim, k in SHAPES:
+        q = g.standard_normal((B * lq, dim)).astype(np.float32)
+        d = g.standard_normal((nd * ld, dim)).astype(np.float32)
+        qoff, doff = np.arange(B + 1) * lq, np.arange(nd + 1) * ld
+        pairs = None if k is None else [g.choice(nd, k, replace=False) for _ in range(B)]
+        npairs = B * (nd if k is None else k)
+        flop = 2.0 * npairs * lq * ld * dim
+        tq, td = torch.from_numpy(q).cuda(), torch.from_numpy(d).cuda()
+        hq, hd = tq.to(torch.bfloat16), td.to(torch.bfloat16)
+        td3 = td.view(nd, ld, dim)
+        idx = None if pairs is None else torch.from_numpy(np.stack(pairs)).cuda()
+
+        def ours(x, y, prec):
+            return lambda: npa.maxsim_scores(x, y, pairs=pairs, precision=prec, query_offsets=qoff, document_offsets=doff)
+
+        def torch_ref(x, y3):
+            def f():
+                for b in range(B):      # one query at a time keeps the [docs, lq, ld] intermediate small
+                    docs = y3 if idx is None else y3[idx[b]]
+                    (docs @ x[b * lq:(b + 1) * lq].T).amax(1).sum(1)
+            return f
+
+        def rerank():
+            for b in range(B):
+                ids = range(nd) if pairs is None else pairs[b]
+                npa.rerank_maxsim(q[b * lq:(b + 1) * lq], [d[i * ld:(i + 1) * ld] for i in ids])
+        paths = [("maxsim_batch f32, precision 0", ours(tq, td, 0), 4), ("maxsim_batch bf16 rows, precision 3", ours(hq, hd, 3), 2),
+                 ("torch f32 matmul+amax+sum", torch_ref(tq, td3), 4), ("torch bf16 matmul+amax+sum", torch_ref(hq, hd.view(nd, ld, dim)), 2),
+                 ("rerank_maxsim per query (host arrays)", rerank, 4)]
+        times = {p[0]: [] for p in paths}
+        for _ in range(a.rounds):
+            for pname, fn, _ in paths:
+                times[pname].append(window(fn, sync))
+        for pname, _, es in paths:
+            t = np.array(times[pname])
+            byts = (q.size + d.size) * es + npairs * 4
+            lines.append(f"| {name} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | "
+                         f"{flop / np.median(t) / 1e12:.2f} | {byts / np.median(t) / 1e9:.1f} |")
+    open(a.out, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
