@@ -1144,6 +1144,45 @@ int np_hip_maxsim_batch_device(int32_t device, int32_t dtype, int32_t precision,
                                const int64_t* h_pair_offsets, float* d_out_scores, float* d_out_match_sims,
                                int32_t* d_out_match_pos, void* stream);
 
+/* ---- int8 rows for batched MaxSim (np_maxsim.hip MODE 3, np_quant.hip) ----------------------------------------------
+ * NP_DT_I8: rows of signed 8-bit codes, `dim` bytes apart, unpadded, with one f32 scale per row -- queries and documents
+ * alike.  The two entries above keep refusing it; the _i8 entries below take nothing else.  The product runs on
+ * v_mfma_i32_32x32x32_i8 and every step is exact or a single f32 rounding, so the whole path is bit for bit a few lines of
+ * numpy (tests/maxsim_i8_restate.py):
+ *   dot         sum_d cq[q][d] * cd[t][d] in i32, exact for every code value (-128 included): |dot| <= 1024 * 128 * 128 = 2^24,
+ *               which f32 holds exactly
+ *   maximum     m[q] = max_t f32(dot) * sd[t], one f32 multiplication each; non-finite products are ignored, equal products
+ *               go to the lowest t, the order is that of the finite f32 values (-0.0 below +0.0)
+ *   similarity  sim[q] = m[q] * sq[q], one more f32 multiplication.  No finite product, or a sim[q] that is not finite: the
+ *               token adds nothing and its match is 0.0 / -1
+ *   score       the f32 sum of sim[q] in query-token order from 0.0f; an empty query or document scores 0
+ *   scales      taken as given (any f32; a NaN scale removes its row).  The quantiser emits finite scales >= 0, or NaN.
+ *   matches     allowed, the layout of precision 0; positions are exact because the arithmetic is
+ *   independent a pair's bits depend on its two code matrices and their scale vectors only (the promise made above)
+ * Shapes, offsets, the host copies of the device entry, the limits and the one-allocation rule are those of
+ * np_hip_maxsim_batch / np_hip_maxsim_batch_device; in addition NULL scales are refused (NP_ERR_INVALID_ARGUMENT). */
+#define NP_DT_I8 2
+int np_hip_maxsim_batch_i8(int32_t device, int32_t dim, const int8_t* queries, const float* q_scales /* [q tokens] */,
+                           const int32_t* q_tok_offsets, int32_t B, const int8_t* documents, const float* d_scales /* [d tokens] */,
+                           const int64_t* doc_tok_offsets, int64_t n_docs, const int64_t* pair_docs, const int64_t* pair_offsets,
+                           float* out_scores, float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+int np_hip_maxsim_batch_i8_device(int32_t device, int32_t dim, const int8_t* d_queries, const float* d_q_scales,
+                                  const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                  const int8_t* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
+                                  const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                                  const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                                  float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
+/* The quantiser that makes such rows on the device.  rows: [n_rows][dim] of dtype NP_DT_F32 or NP_DT_BF16 (bf16 is widened
+ * exactly; any other dtype is refused), 1 <= dim <= 1024.  Per row: a = max_d |x_d|, scale = a / 127 and inv = 127 / a (both
+ * correctly rounded f32 divisions), code_d = clamp(rintf(x_d * inv), -127, 127) with one f32 product and ties to even.
+ * a == 0: scale 0 and codes 0.  A row with a non-finite element: scale NaN and codes 0, so every similarity of that row is
+ * ignored as a NaN row's is at precision 0.  out_codes [n_rows][dim], out_scales [n_rows].  The host entry stages the call
+ * through one device allocation; the device entry allocates nothing, enqueues on `stream` and returns. */
+int np_hip_quantize_rows_i8(int32_t device, int32_t dtype, int32_t dim, const void* rows, int64_t n_rows, int8_t* out_codes,
+                            float* out_scales);
+int np_hip_quantize_rows_i8_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
+                                   int8_t* d_out_codes, float* d_out_scales, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

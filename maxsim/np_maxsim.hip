@@ -38,11 +38,26 @@
 //   independence  one (slot, document tile) accumulator sees the dims in ascending order whatever surrounds it; the key
 //                 maximum does not depend on which wave brought what; the sum runs in the query's own order.  A pair's
 //                 bits therefore depend on its two matrices only -- not on WD, G, the grid, the list or the entry.
+//
+// np_hip_maxsim_batch_i8 (MODE 3): rows of int8 codes with one f32 scale per row, v_mfma_i32_32x32x32_i8.
+//   chunk         128 dims = 128 bytes a row: byte for byte the bf16 geometry above (144-byte pitch, eight 16-byte staging
+//                 units a row, a fragment = 16 bytes per lane at row li, byte 16 kk + 32 s; four MFMA steps a chunk and slot).
+//                 Which 16 of a step's 32 dims a half-wave holds does not matter: both operands split alike and the i32
+//                 sum is exact (|dot| <= 1024 * 128 * 128 = 2^24, which f32 also holds exactly).
+//   scales        a wave writes the scales of its tile's 32 document tokens into the 16 pad bytes of its own LDS rows; the
+//                 epilogue forms f32(acc) * scale[row], one multiplication, and compares the okey of the products (strict >
+//                 over ascending rows, then the same key atomicMax).  The finishing wave multiplies each maximum by the
+//                 query token's scale, once; a product that is not finite reports no match.
+//   resident      dim <= 128 is a single chunk: the slots' query rows are then staged ONCE, before the round loop, and since
+//                 a document tile is its wave's own, the rounds need no barrier at all -- the four waves stream their tiles
+//                 independently (a 1030-token page: 9 rounds, 1 staging of the slots instead of 9, 1 barrier instead of 18).
+//                 MODE 3 only; the other modes keep their loop.
 #include "np_internal.h"
 #include "np_exact.h"
 #include "np_maxsim_plan.h"
 
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 namespace np {
@@ -61,16 +76,22 @@ struct MaxsimP {
   int B, dim, G, nqt, WD;
   int y0;                    // blockIdx.y of this launch starts here (launches are slices of NP_MS_MAX_GRID_Y)
   int vecq, vecd;            // 16-byte loads are legal for every row of Q / D
+  const float* qscale;       // MODE 3: [q tokens], [d tokens]
+  const float* dscale;
 };
 
 constexpr int NP_MS_BROW = 72;                         // bf16 LDS row pitch in elements
 constexpr int NP_MS_META = 128;                        // bytes: the row base, the documents' offsets, lengths and flags
 
-// MODE 0: f32 rows, f32 MFMA.  1: f32 rows rounded to bf16, bf16 MFMA.  2: bf16 rows, bf16 MFMA.
+// MODE 0: f32 rows, f32 MFMA.  1: f32 rows rounded to bf16, bf16 MFMA.  2: bf16 rows, bf16 MFMA.  3: int8 rows, i8 MFMA, in
+// the bf16 modes' LDS geometry (a row's 128 bytes are 128 dims instead of 64).
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+constexpr int NP_MS_SCALE_AT = 128;                    // MODE 3: a document row's scale, in the pad bytes of its LDS row
 template <int MODE> struct MsRaw { uint4 v[MODE == 1 ? 2 : 1]; };   // one staging unit on its way from HBM to LDS
 
 template <int MODE, int NQT> struct MsLds {
-  static constexpr int KC = MODE == 0 ? NP_MS_KC_F32 : NP_MS_KC_BF16;
+  static constexpr int KC = MODE == 0 ? NP_MS_KC_F32 : MODE == 3 ? NP_MS_KC_I8 : NP_MS_KC_BF16;
   static constexpr int R = NQT * 32;                               // slot rows
   static constexpr int SQ = (NQT & 1) ? R : R + 32;                // f32: floats between two k rows of the slots
   static constexpr size_t Q_BYTES = MODE == 0 ? (size_t)KC * SQ * 4 : (size_t)R * NP_MS_BROW * 2;
@@ -104,10 +125,24 @@ __device__ __forceinline__ uint4 ms_load8h(const uint16_t* rowp, int k0, int dim
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// sixteen int8 dims k0 .. k0 + 15 of a row
+__device__ __forceinline__ uint4 ms_load16b(const uint8_t* rowp, int k0, int dim, bool vec) {
+  uint4 r = make_uint4(0u, 0u, 0u, 0u);
+  if (!rowp || k0 >= dim) return r;
+  if (vec) return *reinterpret_cast<const uint4*>(rowp + k0);   // dim % 16 == 0: k0 + 16 <= dim
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (k0 + i < dim) w[i >> 2] |= (uint32_t)rowp[k0 + i] << (8 * (i & 3));
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 template <int MODE>
 __device__ __forceinline__ MsRaw<MODE> ms_load(const void* base, int64_t row, int dim, int k0, bool vec) {
   MsRaw<MODE> r;
-  if (MODE == 2) {
+  if (MODE == 3) {
+    r.v[0] = ms_load16b(row < 0 ? nullptr : static_cast<const uint8_t*>(base) + row * dim, k0, dim, vec);
+  } else if (MODE == 2) {
     r.v[0] = ms_load8h(row < 0 ? nullptr : static_cast<const uint16_t*>(base) + row * dim, k0, dim, vec);
   } else {
     const float* rp = row < 0 ? nullptr : static_cast<const float*>(base) + row * dim;
@@ -123,7 +158,7 @@ __device__ __forceinline__ uint32_t ms_bf16_pair(uint32_t lo_f32, uint32_t hi_f3
   return (uint32_t)a | ((uint32_t)b << 16);
 }
 
-// unit (row, g) of a region to LDS.  f32: `S` floats between k rows, the unit's dims are k rows 4g .. 4g + 3, written in
+// unit (row, g) of a region to LDS (int8 units are 16 bytes at 16 g like bf16 ones).  f32: `S` floats between k rows, the unit's dims are k rows 4g .. 4g + 3, written in
 // opposite order by even and odd g (the two halves of a wave differ in g's parity or in the bank of `row`).
 template <int MODE>
 __device__ __forceinline__ void ms_store(unsigned char* region, int S, int row, int g, const MsRaw<MODE>& r) {
@@ -173,13 +208,31 @@ __device__ __forceinline__ void ms_row_argmax(const f32x16& acc, int64_t t0, int
   }
 }
 
+// MODE 3: the same walk over f32(acc[r]) * sc[r] (sc = the scales of rows mfma_row(r, kk)), compared as keys: okey is 0 for
+// a non-finite product and grows with a finite one, so `best` ends as the key the workgroup's atomicMax takes.
+__device__ __forceinline__ void ms_row_argmax_i8(const i32x16& acc, const float (&sc)[16], int64_t t0, int64_t len, int kk,
+                                                 uint32_t& best, int& pos) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t trow = t0 + mfma_row(r, kk);
+    const uint32_t k = okey((float)acc[r] * sc[r]);
+    if (trow < len && k > best) {
+      best = k;
+      pos = (int)trow;
+    }
+  }
+}
+
 template <int MODE, int NQT>
 __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
   using L = MsLds<MODE, NQT>;
   constexpr int KC = L::KC, R = L::R, SQ = L::SQ;
-  constexpr int EPU = MODE == 0 ? 4 : 8;    // elements per staging unit; a chunk is 8 units per row either way
+  constexpr int EPU = MODE == 0 ? 4 : MODE == 3 ? 16 : 8;   // elements per staging unit; a chunk is 8 units per row either way
+  using Acc = typename std::conditional<MODE == 3, i32x16, f32x16>::type;
   extern __shared__ __align__(16) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, kk = lane >> 5, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, kk = lane >> 5;
+  // MODE 3 keeps the wave index in a scalar register (the other modes keep the code they had)
+  const int wave = MODE == 3 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   unsigned char* sQ = smem;
   unsigned char* sD = smem + L::Q_BYTES + (size_t)wave * L::D_BYTES;
   unsigned long long* sKey = reinterpret_cast<unsigned long long*>(smem + L::KEY_OFF);   // [NP_MS_WG_DOCS][R]
@@ -243,6 +296,17 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
   const int64_t T = tpre[NP_MS_WG_DOCS];
   const int64_t rounds = (T + 3) / 4;
   const int nchunks = (p.dim + KC - 1) / KC;
+  // MODE 3 with a single chunk: the slots are staged here, once; the rounds then touch only each wave's own tile
+  const bool resident = MODE == 3 && nchunks == 1;
+  if (resident) {
+#pragma unroll
+    for (int i = 0; i < NQT; ++i) {
+      int row, g;
+      ms_unit<MODE>(tid + 256 * i, R, row, g);
+      ms_store<MODE>(sQ, SQ, row, g, ms_load<MODE>(p.Q, sQrow[row], p.dim, g * EPU, p.vecq != 0));
+    }
+    __syncthreads();
+  }
 
   for (int64_t rd = 0; rd < rounds; ++rd) {
     const int64_t ti = rd * 4 + wave;       // this wave's tile of the round
@@ -259,20 +323,24 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
     const int64_t len = has ? sDlen[e] : 0;
     const int64_t drow0 = sDoff[e] + t0;
 
-    f32x16 acc[NQT];
+    Acc acc[NQT];
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[qt][r] = 0.f;
+      for (int r = 0; r < 16; ++r) acc[qt][r] = 0;
+    if (MODE == 3 && has && lane < 32)      // this tile's scales, read back in the epilogue (rows past the end are masked there)
+      *reinterpret_cast<float*>(sD + lane * NP_MS_BROW * 2 + NP_MS_SCALE_AT) = t0 + lane < len ? p.dscale[drow0 + lane] : 0.f;
 
     MsRaw<MODE> rq[NQT], rdoc[4];
     auto load_chunk = [&](int c) {
       const int kc0 = c * KC;
+      if (!resident) {
 #pragma unroll
-      for (int i = 0; i < NQT; ++i) {
-        int row, g;
-        ms_unit<MODE>(tid + 256 * i, R, row, g);
-        rq[i] = ms_load<MODE>(p.Q, sQrow[row], p.dim, kc0 + g * EPU, p.vecq != 0);
+        for (int i = 0; i < NQT; ++i) {
+          int row, g;
+          ms_unit<MODE>(tid + 256 * i, R, row, g);
+          rq[i] = ms_load<MODE>(p.Q, sQrow[row], p.dim, kc0 + g * EPU, p.vecq != 0);
+        }
       }
       if (has) {
 #pragma unroll
@@ -285,12 +353,14 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
     };
     load_chunk(0);
     for (int c = 0; c < nchunks; ++c) {
-      __syncthreads();                      // the previous chunk's fragments have been read
+      if (!resident) {
+        __syncthreads();                    // the previous chunk's fragments have been read
 #pragma unroll
-      for (int i = 0; i < NQT; ++i) {
-        int row, g;
-        ms_unit<MODE>(tid + 256 * i, R, row, g);
-        ms_store<MODE>(sQ, SQ, row, g, rq[i]);
+        for (int i = 0; i < NQT; ++i) {
+          int row, g;
+          ms_unit<MODE>(tid + 256 * i, R, row, g);
+          ms_store<MODE>(sQ, SQ, row, g, rq[i]);
+        }
       }
       if (has) {
 #pragma unroll
@@ -300,7 +370,7 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
           ms_store<MODE>(sD, 32, row, g, rdoc[i]);
         }
       }
-      __syncthreads();
+      if (!resident) __syncthreads();       // (resident: a wave reads the tile it wrote itself, and slots nobody writes)
       if (c + 1 < nchunks) load_chunk(c + 1);   // in flight during this chunk's MFMAs
       if (!has) continue;
       // the steps of this chunk in ascending dim order
@@ -309,11 +379,18 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
       const unsigned char* dh = sD + ((size_t)li * NP_MS_BROW + 8 * kk) * 2;
       const unsigned char* qh = sQ + ((size_t)li * NP_MS_BROW + 8 * kk) * 2;
       auto step = [&](int s) {
-        if (MODE == 0) {
+        if constexpr (MODE == 0) {
           const float a = df[2 * s * 32];
 #pragma unroll
           for (int qt = 0; qt < NQT; ++qt)
             if (qt < nslots) acc[qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, qf[2 * s * SQ + qt * 32], acc[qt], 0, 0, 0);
+        } else if constexpr (MODE == 3) {
+          const i32x4 a = *reinterpret_cast<const i32x4*>(dh + 32 * s);
+#pragma unroll
+          for (int qt = 0; qt < NQT; ++qt)
+            if (qt < nslots)
+              acc[qt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(
+                  a, *reinterpret_cast<const i32x4*>(qh + (size_t)qt * 32 * NP_MS_BROW * 2 + 32 * s), acc[qt], 0, 0, 0);
         } else {
           const bf16x8 a = *reinterpret_cast<const bf16x8*>(dh + 32 * s);
 #pragma unroll
@@ -325,7 +402,7 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
       };
       // four steps at a time (more fragments in flight than that only cost registers); dims past `dim` are zeros on both
       // sides, so the steps past dim's own last one add exact zeros
-      constexpr int STEP = MODE == 0 ? 2 : 16;
+      constexpr int STEP = MODE == 0 ? 2 : MODE == 3 ? 32 : 16;
       constexpr int GS = 4;   // steps per group
       const int ng = (min(KC, p.dim - c * KC) + GS * STEP - 1) / (GS * STEP);
 #pragma unroll 1
@@ -334,7 +411,24 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
         for (int s = 0; s < GS; ++s) step(GS * s4 + s);
       }
     }
-    if (has) {
+    if constexpr (MODE == 3) {
+      if (has) {
+        float sc[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          sc[r] = *reinterpret_cast<const float*>(sD + mfma_row(r, kk) * NP_MS_BROW * 2 + NP_MS_SCALE_AT);
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+          if (qt < nslots) {
+            uint32_t best = 0u;
+            int ps = -1;
+            ms_row_argmax_i8(acc[qt], sc, t0, len, kk, best, ps);
+            if (best) atomicMax(&sKey[e * R + qt * 32 + li], ((unsigned long long)best << 32) | (0xFFFFFFFFu - (uint32_t)ps));
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    } else if (has) {
 #pragma unroll
       for (int qt = 0; qt < NQT; ++qt) {
         if (qt < nslots) {
@@ -360,10 +454,14 @@ __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
     const int64_t rowb = (listed ? (int64_t)*sRow : p.n_docs * (int64_t)qb) + (j0 + e) * (int64_t)Lq;
     float total = 0.f;
     for (int t = 0; t * 32 < Lq; ++t) {
-      const unsigned long long key = sKey[e * R + (s * p.nqt + t) * 32 + li];
-      const float m = key ? unkey((uint32_t)(key >> 32)) : NP_NEG_INF;
-      total = tile_sum(m, min(32, Lq - t * 32), total);
+      unsigned long long key = sKey[e * R + (s * p.nqt + t) * 32 + li];
+      float m = key ? unkey((uint32_t)(key >> 32)) : NP_NEG_INF;
       const int tq = t * 32 + li;
+      if (MODE == 3 && key) {               // the query token's scale, one multiplication; not finite = no match
+        m *= p.qscale[qb + min(tq, Lq - 1)];
+        if (!finitef(m)) key = 0ull, m = NP_NEG_INF;
+      }
+      total = tile_sum(m, min(32, Lq - t * 32), total);
       if (kk == 0 && tq < Lq) {
         if (p.sims) p.sims[rowb + tq] = key ? m : 0.0f;
         if (p.pos) p.pos[rowb + tq] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
@@ -416,7 +514,7 @@ static int maxsim_validate(int32_t dtype, int32_t precision, int32_t dim, int32_
   return c == 1 ? NP_ERR_SHAPE : NP_ERR_INVALID_ARGUMENT;
 }
 
-static int maxsim_device_ok(int32_t device, int* compute_units) {
+int maxsim_device_ok(int32_t device, int* compute_units) {   // np_quant.hip calls it too
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     (void)hipGetLastError();
@@ -434,11 +532,11 @@ static int maxsim_device_ok(int32_t device, int* compute_units) {
 static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t precision, int32_t dim, const void* d_q,
                       const int32_t* d_qoff, const int32_t* h_qoff, int32_t B, const void* d_d, const int64_t* d_doff,
                       int64_t n_docs, const int64_t* d_pair_docs, const int64_t* d_poff, const int64_t* h_poff, float* d_scores,
-                      float* d_sims, int32_t* d_pos) {
+                      float* d_sims, int32_t* d_pos, const float* d_qscale = nullptr, const float* d_dscale = nullptr) {
   const bool listed = d_pair_docs != nullptr;
   const MaxsimPlan plan = maxsim_plan(listed, h_qoff, B, n_docs, h_poff, compute_units);
   if (plan.gx <= 0 || plan.gy <= 0) return NP_OK;
-  const size_t pitch = (size_t)dim * (dtype == NP_MS_DT_BF16 ? 2 : 4);
+  const size_t pitch = (size_t)dim * (dtype == NP_MS_DT_I8 ? 1 : dtype == NP_MS_DT_BF16 ? 2 : 4);
   MaxsimP p;
   p.Q = d_q;
   p.qoff = d_qoff;
@@ -458,9 +556,123 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
   p.y0 = 0;
   p.vecq = pitch % 16 == 0 && (uintptr_t)d_q % 16 == 0;
   p.vecd = pitch % 16 == 0 && (uintptr_t)d_d % 16 == 0;
+  p.qscale = d_qscale;
+  p.dscale = d_dscale;
+  if (dtype == NP_MS_DT_I8) return maxsim_launch_mode<3>(st, p, plan);
   if (precision == 0) return maxsim_launch_mode<0>(st, p, plan);
   if (dtype == NP_MS_DT_F32) return maxsim_launch_mode<1>(st, p, plan);
   return maxsim_launch_mode<2>(st, p, plan);
+}
+
+// the int8 entries' checks (q_scales / d_scales non-NULL = the call is one of them)
+static int maxsim_validate_i8(int32_t dim, const void* q_scales, int32_t B, const int32_t* h_qoff, const void* d_scales,
+                              int64_t n_docs, const int64_t* h_doff, bool listed, const int64_t* h_pair_docs,
+                              const int64_t* h_poff) {
+  const char* why = "";
+  int64_t bad = -1;
+  const int c = maxsim_check_args_i8(dim, q_scales, B, h_qoff, d_scales, n_docs, h_doff, listed, h_pair_docs, h_poff, &why, &bad);
+  if (c == 0) return NP_OK;
+  if (bad >= 0)
+    set_error("maxsim_batch_i8: %s (pair %lld names document %lld, n_docs %lld)", why, (long long)bad,
+              (long long)h_pair_docs[bad], (long long)n_docs);
+  else
+    set_error("%s: maxsim_batch_i8: %s (dim=%d)", c == 1 ? "Shape error" : "Search failed", why, dim);
+  return c == 1 ? NP_ERR_SHAPE : NP_ERR_INVALID_ARGUMENT;
+}
+
+// The device entries after their checks: every array in HBM.  d_q_scales / d_d_scales: the int8 entry's, NULL otherwise.
+static int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
+                              const float* d_q_scales, const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                              const void* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
+                              const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                              const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                              float* d_out_match_sims, int32_t* d_out_match_pos, void* stream) {
+  const bool listed = d_pair_docs != nullptr;
+  const int64_t P = B <= 0 ? 0 : (listed ? h_pair_offsets[B] : (int64_t)B * n_docs);
+  if (P == 0) return NP_OK;
+  if (!d_q_tok_offsets || !d_doc_tok_offsets || !d_out_scores || (h_q_tok_offsets[B] > 0 && !d_queries) ||
+      (h_doc_tok_offsets[n_docs] > 0 && !d_documents)) {
+    set_error("Search failed: maxsim_batch: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  int cus = 0;
+  NP_TRY(maxsim_device_ok(device, &cus));
+  DeviceGuard g(device);
+  return maxsim_run((hipStream_t)stream, cus, dtype, precision, dim, d_queries, d_q_tok_offsets, h_q_tok_offsets, B,
+                    d_documents, d_doc_tok_offsets, n_docs, d_pair_docs, d_pair_offsets, h_pair_offsets, d_out_scores,
+                    d_out_match_sims, d_out_match_pos, d_q_scales, d_d_scales);
+}
+
+// The host entries after their checks: the call staged through one allocation.
+static int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
+                            const float* q_scales, const int32_t* q_tok_offsets, int32_t B, const void* documents,
+                            const float* d_scales, const int64_t* doc_tok_offsets, int64_t n_docs, const int64_t* pair_docs,
+                            const int64_t* pair_offsets, float* out_scores, float* out_match_sims, int32_t* out_match_pos) {
+  const bool listed = pair_docs != nullptr;
+  const bool rows = out_match_sims || out_match_pos;
+  const int64_t P = B <= 0 ? 0 : (listed ? pair_offsets[B] : (int64_t)B * n_docs);
+  if (P == 0) return NP_OK;
+  const int64_t qtok = q_tok_offsets[B], dtok = doc_tok_offsets[n_docs];
+  if (!out_scores || (qtok > 0 && !queries) || (dtok > 0 && !documents)) {
+    set_error("Search failed: maxsim_batch: NULL buffer");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  int64_t R = 0;   // row entries
+  if (rows)
+    for (int b = 0; b < B; ++b)
+      R += (listed ? pair_offsets[b + 1] - pair_offsets[b] : n_docs) * (int64_t)(q_tok_offsets[b + 1] - q_tok_offsets[b]);
+  int cus = 0;
+  NP_TRY(maxsim_device_ok(device, &cus));
+  DeviceGuard g(device);
+  // one allocation for the call: inputs (int8: and their scales), offsets, outputs, each on a 256-byte boundary
+  const size_t es = dtype == NP_MS_DT_I8 ? 1 : dtype == NP_MS_DT_BF16 ? 2 : 4;
+  const size_t b_q = up256((size_t)qtok * dim * es), b_d = up256((size_t)dtok * dim * es);
+  const size_t b_qs = q_scales ? up256((size_t)qtok * 4) : 0, b_ds = d_scales ? up256((size_t)dtok * 4) : 0;
+  const size_t b_qoff = up256((size_t)(B + 1) * 4), b_doff = up256((size_t)(n_docs + 1) * 8);
+  const size_t b_ids = listed ? up256((size_t)P * 8) : 0, b_poff = listed ? up256((size_t)(B + 1) * 8) : 0;
+  const size_t b_sc = up256((size_t)P * 4), b_sim = out_match_sims ? up256((size_t)R * 4) : 0;
+  const size_t b_pos = out_match_pos ? up256((size_t)R * 4) : 0;
+  DevPtr<char> buf;
+  NP_TRY(buf.alloc(b_q + b_d + b_qs + b_ds + b_qoff + b_doff + b_ids + b_poff + b_sc + b_sim + b_pos));
+  Carver carve{buf.get()};
+  char* d_q = carve.take(b_q);
+  char* d_d = carve.take(b_d);
+  float* d_qs = q_scales ? (float*)carve.take(b_qs) : nullptr;
+  float* d_ds = d_scales ? (float*)carve.take(b_ds) : nullptr;
+  int32_t* d_qoff = (int32_t*)carve.take(b_qoff);
+  int64_t* d_doff = (int64_t*)carve.take(b_doff);
+  int64_t* d_ids = listed ? (int64_t*)carve.take(b_ids) : nullptr;
+  int64_t* d_poff = listed ? (int64_t*)carve.take(b_poff) : nullptr;
+  float* d_sc = (float*)carve.take(b_sc);
+  float* d_sim = out_match_sims ? (float*)carve.take(b_sim) : nullptr;
+  int32_t* d_pos = out_match_pos ? (int32_t*)carve.take(b_pos) : nullptr;
+  if (qtok > 0) NP_HIP(hipMemcpy(d_q, queries, (size_t)qtok * dim * es, hipMemcpyHostToDevice));
+  if (dtok > 0) NP_HIP(hipMemcpy(d_d, documents, (size_t)dtok * dim * es, hipMemcpyHostToDevice));
+  if (d_qs && qtok > 0) NP_HIP(hipMemcpy(d_qs, q_scales, (size_t)qtok * 4, hipMemcpyHostToDevice));
+  if (d_ds && dtok > 0) NP_HIP(hipMemcpy(d_ds, d_scales, (size_t)dtok * 4, hipMemcpyHostToDevice));
+  NP_HIP(hipMemcpy(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice));
+  NP_HIP(hipMemcpy(d_doff, doc_tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
+  if (listed) {
+    NP_HIP(hipMemcpy(d_ids, pair_docs, (size_t)P * 8, hipMemcpyHostToDevice));
+    NP_HIP(hipMemcpy(d_poff, pair_offsets, (size_t)(B + 1) * 8, hipMemcpyHostToDevice));
+  }
+  NP_TRY(maxsim_run(nullptr, cus, dtype, precision, dim, d_q, d_qoff, q_tok_offsets, B, d_d, d_doff, n_docs, d_ids, d_poff,
+                    pair_offsets, d_sc, d_sim, d_pos, d_qs, d_ds));
+  NP_HIP(hipMemcpy(out_scores, d_sc, (size_t)P * 4, hipMemcpyDeviceToHost));
+  if (d_sim && R > 0) NP_HIP(hipMemcpy(out_match_sims, d_sim, (size_t)R * 4, hipMemcpyDeviceToHost));
+  if (d_pos && R > 0) NP_HIP(hipMemcpy(out_match_pos, d_pos, (size_t)R * 4, hipMemcpyDeviceToHost));
+  return NP_OK;
+}
+
+// pair_docs and pair_offsets (the device entries: and the host copy) go together; *listed = they are there
+static int maxsim_pair_args(bool all, bool any, bool device_entry, bool* listed) {
+  *listed = any;
+  if (any && !all) {
+    set_error(device_entry ? "Search failed: maxsim_batch: pair_docs and pair_offsets (device and host copy) go together, or all NULL"
+                           : "Search failed: maxsim_batch: pair_docs and pair_offsets go together, or both NULL");
+    return NP_ERR_INVALID_ARGUMENT;
+  }
+  return NP_OK;
 }
 
 }  // namespace np
@@ -476,26 +688,14 @@ int np_hip_maxsim_batch_device(int32_t device, int32_t dtype, int32_t precision,
                                const int64_t* h_pair_offsets, float* d_out_scores, float* d_out_match_sims,
                                int32_t* d_out_match_pos, void* stream) {
   clear_error();
-  const bool listed = d_pair_docs || d_pair_offsets || h_pair_offsets;
-  if (listed && !(d_pair_docs && d_pair_offsets && h_pair_offsets)) {
-    set_error("Search failed: maxsim_batch: pair_docs and pair_offsets (device and host copy) go together, or all NULL");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
+  bool listed;
+  NP_TRY(maxsim_pair_args(d_pair_docs && d_pair_offsets && h_pair_offsets, d_pair_docs || d_pair_offsets || h_pair_offsets, true,
+                          &listed));
   NP_TRY(maxsim_validate(dtype, precision, dim, B, h_q_tok_offsets, n_docs, h_doc_tok_offsets, listed, nullptr, h_pair_offsets,
                          d_out_match_sims || d_out_match_pos));
-  const int64_t P = B <= 0 ? 0 : (listed ? h_pair_offsets[B] : (int64_t)B * n_docs);
-  if (P == 0) return NP_OK;
-  if (!d_q_tok_offsets || !d_doc_tok_offsets || !d_out_scores || (h_q_tok_offsets[B] > 0 && !d_queries) ||
-      (h_doc_tok_offsets[n_docs] > 0 && !d_documents)) {
-    set_error("Search failed: maxsim_batch: NULL buffer");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  int cus = 0;
-  NP_TRY(maxsim_device_ok(device, &cus));
-  DeviceGuard g(device);
-  return maxsim_run((hipStream_t)stream, cus, dtype, precision, dim, d_queries, d_q_tok_offsets, h_q_tok_offsets, B,
-                    d_documents, d_doc_tok_offsets, n_docs, d_pair_docs, d_pair_offsets, h_pair_offsets, d_out_scores,
-                    d_out_match_sims, d_out_match_pos);
+  return maxsim_device_call(device, dtype, precision, dim, d_queries, nullptr, d_q_tok_offsets, h_q_tok_offsets, B, d_documents,
+                            nullptr, d_doc_tok_offsets, h_doc_tok_offsets, n_docs, d_pair_docs, d_pair_offsets, h_pair_offsets,
+                            d_out_scores, d_out_match_sims, d_out_match_pos, stream);
 }
 
 int np_hip_maxsim_batch(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
@@ -503,60 +703,41 @@ int np_hip_maxsim_batch(int32_t device, int32_t dtype, int32_t precision, int32_
                         int64_t n_docs, const int64_t* pair_docs, const int64_t* pair_offsets, float* out_scores,
                         float* out_match_sims, int32_t* out_match_pos) {
   clear_error();
-  const bool listed = pair_docs || pair_offsets;
-  if (listed && !(pair_docs && pair_offsets)) {
-    set_error("Search failed: maxsim_batch: pair_docs and pair_offsets go together, or both NULL");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  const bool rows = out_match_sims || out_match_pos;
-  NP_TRY(maxsim_validate(dtype, precision, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed, pair_docs, pair_offsets, rows));
-  const int64_t P = B <= 0 ? 0 : (listed ? pair_offsets[B] : (int64_t)B * n_docs);
-  if (P == 0) return NP_OK;
-  const int64_t qtok = q_tok_offsets[B], dtok = doc_tok_offsets[n_docs];
-  if (!out_scores || (qtok > 0 && !queries) || (dtok > 0 && !documents)) {
-    set_error("Search failed: maxsim_batch: NULL buffer");
-    return NP_ERR_INVALID_ARGUMENT;
-  }
-  int64_t R = 0;   // row entries
-  if (rows)
-    for (int b = 0; b < B; ++b)
-      R += (listed ? pair_offsets[b + 1] - pair_offsets[b] : n_docs) * (int64_t)(q_tok_offsets[b + 1] - q_tok_offsets[b]);
-  int cus = 0;
-  NP_TRY(maxsim_device_ok(device, &cus));
-  DeviceGuard g(device);
-  // one allocation for the call: inputs, offsets, outputs, each on a 256-byte boundary
-  const size_t es = dtype == NP_MS_DT_BF16 ? 2 : 4;
-  const size_t b_q = up256((size_t)qtok * dim * es), b_d = up256((size_t)dtok * dim * es);
-  const size_t b_qoff = up256((size_t)(B + 1) * 4), b_doff = up256((size_t)(n_docs + 1) * 8);
-  const size_t b_ids = listed ? up256((size_t)P * 8) : 0, b_poff = listed ? up256((size_t)(B + 1) * 8) : 0;
-  const size_t b_sc = up256((size_t)P * 4), b_sim = out_match_sims ? up256((size_t)R * 4) : 0;
-  const size_t b_pos = out_match_pos ? up256((size_t)R * 4) : 0;
-  DevPtr<char> buf;
-  NP_TRY(buf.alloc(b_q + b_d + b_qoff + b_doff + b_ids + b_poff + b_sc + b_sim + b_pos));
-  Carver carve{buf.get()};
-  char* d_q = carve.take(b_q);
-  char* d_d = carve.take(b_d);
-  int32_t* d_qoff = (int32_t*)carve.take(b_qoff);
-  int64_t* d_doff = (int64_t*)carve.take(b_doff);
-  int64_t* d_ids = listed ? (int64_t*)carve.take(b_ids) : nullptr;
-  int64_t* d_poff = listed ? (int64_t*)carve.take(b_poff) : nullptr;
-  float* d_sc = (float*)carve.take(b_sc);
-  float* d_sim = out_match_sims ? (float*)carve.take(b_sim) : nullptr;
-  int32_t* d_pos = out_match_pos ? (int32_t*)carve.take(b_pos) : nullptr;
-  if (qtok > 0) NP_HIP(hipMemcpy(d_q, queries, (size_t)qtok * dim * es, hipMemcpyHostToDevice));
-  if (dtok > 0) NP_HIP(hipMemcpy(d_d, documents, (size_t)dtok * dim * es, hipMemcpyHostToDevice));
-  NP_HIP(hipMemcpy(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice));
-  NP_HIP(hipMemcpy(d_doff, doc_tok_offsets, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice));
-  if (listed) {
-    NP_HIP(hipMemcpy(d_ids, pair_docs, (size_t)P * 8, hipMemcpyHostToDevice));
-    NP_HIP(hipMemcpy(d_poff, pair_offsets, (size_t)(B + 1) * 8, hipMemcpyHostToDevice));
-  }
-  NP_TRY(maxsim_run(nullptr, cus, dtype, precision, dim, d_q, d_qoff, q_tok_offsets, B, d_d, d_doff, n_docs, d_ids, d_poff,
-                    pair_offsets, d_sc, d_sim, d_pos));
-  NP_HIP(hipMemcpy(out_scores, d_sc, (size_t)P * 4, hipMemcpyDeviceToHost));
-  if (d_sim && R > 0) NP_HIP(hipMemcpy(out_match_sims, d_sim, (size_t)R * 4, hipMemcpyDeviceToHost));
-  if (d_pos && R > 0) NP_HIP(hipMemcpy(out_match_pos, d_pos, (size_t)R * 4, hipMemcpyDeviceToHost));
-  return NP_OK;
+  bool listed;
+  NP_TRY(maxsim_pair_args(pair_docs && pair_offsets, pair_docs || pair_offsets, false, &listed));
+  NP_TRY(maxsim_validate(dtype, precision, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed, pair_docs, pair_offsets,
+                         out_match_sims || out_match_pos));
+  return maxsim_host_call(device, dtype, precision, dim, queries, nullptr, q_tok_offsets, B, documents, nullptr, doc_tok_offsets,
+                          n_docs, pair_docs, pair_offsets, out_scores, out_match_sims, out_match_pos);
+}
+
+int np_hip_maxsim_batch_i8_device(int32_t device, int32_t dim, const int8_t* d_queries, const float* d_q_scales,
+                                  const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                  const int8_t* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
+                                  const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                                  const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                                  float* d_out_match_sims, int32_t* d_out_match_pos, void* stream) {
+  clear_error();
+  bool listed;
+  NP_TRY(maxsim_pair_args(d_pair_docs && d_pair_offsets && h_pair_offsets, d_pair_docs || d_pair_offsets || h_pair_offsets, true,
+                          &listed));
+  NP_TRY(maxsim_validate_i8(dim, d_q_scales, B, h_q_tok_offsets, d_d_scales, n_docs, h_doc_tok_offsets, listed, nullptr,
+                            h_pair_offsets));
+  return maxsim_device_call(device, NP_MS_DT_I8, 0, dim, d_queries, d_q_scales, d_q_tok_offsets, h_q_tok_offsets, B, d_documents,
+                            d_d_scales, d_doc_tok_offsets, h_doc_tok_offsets, n_docs, d_pair_docs, d_pair_offsets, h_pair_offsets,
+                            d_out_scores, d_out_match_sims, d_out_match_pos, stream);
+}
+
+int np_hip_maxsim_batch_i8(int32_t device, int32_t dim, const int8_t* queries, const float* q_scales,
+                           const int32_t* q_tok_offsets, int32_t B, const int8_t* documents, const float* d_scales,
+                           const int64_t* doc_tok_offsets, int64_t n_docs, const int64_t* pair_docs, const int64_t* pair_offsets,
+                           float* out_scores, float* out_match_sims, int32_t* out_match_pos) {
+  clear_error();
+  bool listed;
+  NP_TRY(maxsim_pair_args(pair_docs && pair_offsets, pair_docs || pair_offsets, false, &listed));
+  NP_TRY(maxsim_validate_i8(dim, q_scales, B, q_tok_offsets, d_scales, n_docs, doc_tok_offsets, listed, pair_docs, pair_offsets));
+  return maxsim_host_call(device, NP_MS_DT_I8, 0, dim, queries, q_scales, q_tok_offsets, B, documents, d_scales, doc_tok_offsets,
+                          n_docs, pair_docs, pair_offsets, out_scores, out_match_sims, out_match_pos);
 }
 
 }  // extern "C"

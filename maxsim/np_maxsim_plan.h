@@ -6,10 +6,12 @@
 namespace np {
 
 constexpr int NP_MS_DT_F32 = 0, NP_MS_DT_BF16 = 1;   // NP_DT_F32 / NP_DT_BF16 of the public header
+constexpr int NP_MS_DT_I8 = 2;                // NP_DT_I8: int8 codes with one f32 scale per row (the _i8 entries only)
 constexpr int NP_MS_MAX_DIM = 1024;
 constexpr int NP_MS_MAX_QUERY_TOKENS = 256;   // eight 32-token query tiles, as S6
 constexpr int NP_MS_KC_F32 = 32;              // dims per LDS chunk, f32 MFMA (16 steps of 32x32x2)
 constexpr int NP_MS_KC_BF16 = 64;             // dims per LDS chunk, bf16 MFMA (4 steps of 32x32x16)
+constexpr int NP_MS_KC_I8 = 128;              // dims per LDS chunk, i8 MFMA (4 steps of 32x32x32): the bf16 chunk's bytes
 constexpr int NP_MS_WG_DOCS = 4;              // documents a workgroup scores at most (one per wave when they are short)
 constexpr int NP_MS_MAX_SLOTS = 8;            // 32-token query tiles a workgroup holds accumulators for
 constexpr int64_t NP_MS_MAX_GRID_X = 0x7FFFFFFF;
@@ -56,6 +58,32 @@ inline int maxsim_check_args(int32_t dtype, int32_t precision, int32_t dim, int3
   if (pair_docs && B > 0)
     for (int64_t i = 0; i < pair_offsets[B]; ++i)
       if (pair_docs[i] < 0 || pair_docs[i] >= n_docs) return *bad_pair = i, *why = "pair_docs names a document outside [0, n_docs)", 2;
+  return 0;
+}
+
+// np_hip_maxsim_batch_i8: the same limits (rows of int8 codes multiply exactly, so matches are allowed as at precision 0),
+// and both scale vectors must be there.
+inline int maxsim_check_args_i8(int32_t dim, const void* q_scales, int32_t B, const int32_t* q_tok_offsets, const void* d_scales,
+                                int64_t n_docs, const int64_t* doc_tok_offsets, bool listed, const int64_t* pair_docs,
+                                const int64_t* pair_offsets, const char** why, int64_t* bad_pair) {
+  *bad_pair = -1;
+  if (!q_scales) return *why = "q_scales is NULL", 2;
+  if (!d_scales) return *why = "d_scales is NULL", 2;
+  return maxsim_check_args(NP_MS_DT_F32, 0, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed, pair_docs, pair_offsets, true,
+                           why, bad_pair);
+}
+
+// np_hip_quantize_rows_i8: one wave takes a whole row, 16 elements a lane, so dim has maxsim's limit.  0 / 1 / 2 as above.
+inline int quantize_check_args(int32_t dtype, int32_t dim, int64_t n_rows, const void* rows, const void* out_codes,
+                               const void* out_scales, const char** why) {
+  *why = "";
+  if (dim < 1 || dim > NP_MS_MAX_DIM) return *why = "dim must lie in 1 .. 1024", 1;
+  if (dtype != NP_MS_DT_F32 && dtype != NP_MS_DT_BF16) return *why = "dtype must be NP_DT_F32 (0) or NP_DT_BF16 (1)", 2;
+  if (n_rows < 0) return *why = "n_rows is negative", 2;
+  if (n_rows > 4 * NP_MS_MAX_GRID_X) return *why = "n_rows exceeds one launch", 2;
+  if (n_rows > 0 && !rows) return *why = "rows is NULL", 2;
+  if (n_rows > 0 && !out_codes) return *why = "out_codes is NULL", 2;
+  if (n_rows > 0 && !out_scales) return *why = "out_scales is NULL", 2;
   return 0;
 }
 

@@ -7,7 +7,7 @@ There is no CPU fallback in this package: if the HIP library or a GPU is missing
 """
 from .api import (  # noqa: F401
     MmapIndex, SearchParameters, QueryResult, NextPlaidError, IndexLoadError, SearchError,
-    ShapeError, CodecError, DeviceUnavailableError, device_count, library_path, rerank_maxsim, maxsim_scores, probe_index_dir, write_index_dir,
+    ShapeError, CodecError, DeviceUnavailableError, device_count, library_path, rerank_maxsim, maxsim_scores, quantize_rows, probe_index_dir, write_index_dir,
     IndexConfig, IndexCreationError, kmeans, kmeans_plan, compute_kmeans, estimate_num_partitions, prepare_codec_artifacts,
     UpdateConfig, update_index_dir, update_append_dir, delete_from_index_dir, pool_document_embeddings, pooled_lengths,
     pack_filters, fuse, fuse_rrf, fuse_relative_score, collapse, group_ids_of_keys, default_pool_k,

@@ -300,7 +300,8 @@ EXPORTS = [
     "np_hip_index_append", "np_hip_index_reserve", "np_hip_index_capacity", "np_hip_index_remove",
     "np_hip_index_remove_keep", "np_hip_index_append_rows", "np_hip_index_get_column", "np_hip_index_get_groups",
     "np_hip_index_expand", "np_hip_index_expand_rows",
-    "np_hip_maxsim_batch", "np_hip_maxsim_batch_device",
+    "np_hip_maxsim_batch", "np_hip_maxsim_batch_device", "np_hip_maxsim_batch_i8", "np_hip_maxsim_batch_i8_device",
+    "np_hip_quantize_rows_i8", "np_hip_quantize_rows_i8_device",
 ]
 
 _lib = None
@@ -471,6 +472,10 @@ def lib():
     L.np_hip_rerank_maxsim.argtypes = [i32, vp, i32, i32, vp, vp, i64, vp, vp]
     L.np_hip_maxsim_batch.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
     L.np_hip_maxsim_batch_device.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.np_hip_maxsim_batch_i8.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.np_hip_maxsim_batch_i8_device.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.np_hip_quantize_rows_i8.argtypes = [i32, i32, i32, vp, i64, vp, vp]
+    L.np_hip_quantize_rows_i8_device.argtypes = [i32, i32, i32, vp, i64, vp, vp, vp]
     L.np_hip_debug_trace.argtypes = [vp, vp, i32, i32, C.POINTER(np_search_params), vp, i64,
                                      vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]
     L.np_hip_kmeans_plan.argtypes = [vp, i64, C.POINTER(np_index_config), C.POINTER(np_kmeans_plan), vp]
@@ -588,8 +593,9 @@ def rerank_maxsim(query, documents, device: int = 0):
     return order[: len(docs)], scores[: len(docs)]
 
 
-NP_DT_F32, NP_DT_BF16 = 0, 1
+NP_DT_F32, NP_DT_BF16, NP_DT_I8 = 0, 1, 2
 MAXSIM_CHUNK_F32, MAXSIM_CHUNK_BF16 = 32, 64     # NP_MS_KC_F32 / NP_MS_KC_BF16 of np_maxsim_plan.h: dims per LDS chunk
+MAXSIM_CHUNK_I8 = 128                            # NP_MS_KC_I8
 
 
 def _is_torch(x):
@@ -616,8 +622,47 @@ def _maxsim_pack(mats, offsets, what):
     return np.ascontiguousarray(flat), off
 
 
+def quantize_rows(rows, device: int = 0):
+    """np_hip_quantize_rows_i8: [n, dim] rows -> (codes int8 [n, dim], scales f32 [n]), scale = max|x| / 127 per row and
+    codes = rint(x * (127 / max|x|)); a row with a non-finite element gets scale NaN and codes 0.  numpy (float32; anything
+    else is converted) goes through the host entry; a float32 or bfloat16 torch tensor on the device through the device
+    entry on torch's current stream, and tensors come back."""
+    if rows.ndim != 2:
+        raise ShapeError(f"Shape error: rows has shape {tuple(rows.shape)}")
+    n, dim = int(rows.shape[0]), int(rows.shape[1])
+    if _is_torch(rows):
+        import torch
+        if rows.dtype not in (torch.float32, torch.bfloat16) or not rows.is_cuda:
+            raise ValueError("quantize_rows: a tensor must be float32 or bfloat16, on the GPU")
+        rows = rows.contiguous()
+        codes = torch.zeros((n, dim), dtype=torch.int8, device=rows.device)
+        scales = torch.zeros(n, dtype=torch.float32, device=rows.device)
+        tp = lambda x: C.c_void_p(x.data_ptr())    # noqa: E731
+        _check(lib().np_hip_quantize_rows_i8_device(
+            rows.device.index or 0, NP_DT_BF16 if rows.dtype == torch.bfloat16 else NP_DT_F32, dim, tp(rows), n, tp(codes),
+            tp(scales), C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)))
+        return codes, scales
+    rows = np.ascontiguousarray(rows, np.float32)
+    codes, scales = np.zeros((n, dim), np.int8), np.zeros(n, np.float32)
+    _check(lib().np_hip_quantize_rows_i8(int(device), NP_DT_F32, dim, _ptr(rows), n, _ptr(codes), _ptr(scales)))
+    return codes, scales
+
+
+def _maxsim_scales(s, rows, what):
+    """One f32 scale per row of `rows`, flat, where the rows are (a list that parallels the row list is concatenated)."""
+    if _is_torch(rows):
+        import torch
+        s = s if _is_torch(s) else torch.cat([x.reshape(-1) for x in s] + [torch.zeros(0, device=rows.device)])
+        s = torch.cat([s.to(rows.device, torch.float32).reshape(-1), torch.zeros(1, device=rows.device)])   # never NULL
+    else:
+        s = np.concatenate([np.ravel(x) for x in ([s] if isinstance(s, np.ndarray) else s)] + [np.zeros(1)]).astype(np.float32)
+    if s.shape[0] - 1 != rows.shape[0] or "int8" not in str(rows.dtype) or "uint8" in str(rows.dtype):
+        raise ValueError(f"maxsim_scores: {what}_scales go with int8 {what} rows, one scale per row")
+    return s
+
+
 def maxsim_scores(queries, documents, pairs=None, precision: int = 0, return_matches: bool = False, device: int = 0,
-                  query_offsets=None, document_offsets=None):
+                  query_offsets=None, document_offsets=None, query_scales=None, document_scales=None):
     """np_hip_maxsim_batch: MaxSim (maxsim.rs:270-294) of caller-supplied multi-vector embeddings on the MFMA kernel of
     np_maxsim.hip, dim up to 1024, rows taken as given (nothing is normalised).
 
@@ -629,11 +674,20 @@ def maxsim_scores(queries, documents, pairs=None, precision: int = 0, return_mat
 
     Returns, per query, its scores (f32 [n_i]); with return_matches (precision 0) a tuple (scores, sims [n_i, Lq_i],
     positions i32 [n_i, Lq_i]): per query token the best document token's similarity and the lowest index reaching it
-    (0.0 and -1 where no similarity is finite); a score is the ordered f32 sum of its row of sims."""
+    (0.0 and -1 where no similarity is finite); a score is the ordered f32 sum of its row of sims.
+
+    query_scales / document_scales (both or neither; lists that parallel the row lists, or flat arrays): the rows are int8
+    codes (numpy or torch.int8, see quantize_rows) with one f32 scale per row, scored by np_hip_maxsim_batch_i8 on the i8
+    MFMA: exact integer dot products, sim = dot * document scale * query scale.  precision stays 0; matches are allowed."""
+    i8 = query_scales is not None or document_scales is not None
+    if i8 and (query_scales is None or document_scales is None or precision != 0):
+        raise ValueError("maxsim_scores: query_scales and document_scales go together, with precision 0 (int8 rows are exact)")
     qf, qoff = _maxsim_pack(queries, query_offsets, "query")
     df, doff = _maxsim_pack(documents, document_offsets, "document")
     if qoff.size <= 1:
         return []
+    if i8:
+        qs, ds = _maxsim_scales(query_scales, qf, "query"), _maxsim_scales(document_scales, df, "document")
     on_dev = _is_torch(qf)
     if on_dev != _is_torch(df):
         raise ValueError("maxsim_scores: queries and documents must both be numpy arrays or both torch tensors")
@@ -659,8 +713,9 @@ def maxsim_scores(queries, documents, pairs=None, precision: int = 0, return_mat
     L = lib()
     if on_dev:
         import torch
-        if qf.dtype != df.dtype or qf.dtype not in (torch.float32, torch.bfloat16) or not qf.is_cuda or not df.is_cuda:
-            raise ValueError("maxsim_scores: device tensors must both be float32 or both bfloat16, on the GPU")
+        if qf.dtype != df.dtype or qf.dtype not in (torch.float32, torch.bfloat16, torch.int8) or not qf.is_cuda or not df.is_cuda or \
+                (qf.dtype == torch.int8) != i8:
+            raise ValueError("maxsim_scores: device tensors must both be float32 or both bfloat16 (int8 with scales), on the GPU")
         dev = qf.device
         dtype = NP_DT_BF16 if qf.dtype == torch.bfloat16 else NP_DT_F32
         qf, df = qf.contiguous(), df.contiguous()
@@ -671,16 +726,25 @@ def maxsim_scores(queries, documents, pairs=None, precision: int = 0, return_mat
         sims = torch.zeros(max(R, 1), dtype=torch.float32, device=dev) if return_matches else None
         pos = torch.zeros(max(R, 1), dtype=torch.int32, device=dev) if return_matches else None
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(L.np_hip_maxsim_batch_device(dev.index or 0, dtype, int(precision), dim, tp(qf), tp(d_qoff), _ptr(qoff32), B,
-                                            tp(df), tp(d_doff), _ptr(doff), n_docs, tp(d_ids), tp(d_poff), _ptr(poff), tp(sc),
-                                            tp(sims), tp(pos), C.c_void_p(stream)))
+        if i8:
+            _check(L.np_hip_maxsim_batch_i8_device(dev.index or 0, dim, tp(qf), tp(qs), tp(d_qoff), _ptr(qoff32), B, tp(df), tp(ds),
+                                                   tp(d_doff), _ptr(doff), n_docs, tp(d_ids), tp(d_poff), _ptr(poff), tp(sc),
+                                                   tp(sims), tp(pos), C.c_void_p(stream)))
+        else:
+            _check(L.np_hip_maxsim_batch_device(dev.index or 0, dtype, int(precision), dim, tp(qf), tp(d_qoff), _ptr(qoff32), B,
+                                                tp(df), tp(d_doff), _ptr(doff), n_docs, tp(d_ids), tp(d_poff), _ptr(poff), tp(sc),
+                                                tp(sims), tp(pos), C.c_void_p(stream)))
     else:
-        qf, df = np.ascontiguousarray(qf, np.float32), np.ascontiguousarray(df, np.float32)
+        qf, df = (np.ascontiguousarray(x, np.int8 if i8 else np.float32) for x in (qf, df))
         sc = np.zeros(max(P, 1), np.float32)
         sims = np.zeros(max(R, 1), np.float32) if return_matches else None
         pos = np.zeros(max(R, 1), np.int32) if return_matches else None
-        _check(L.np_hip_maxsim_batch(int(device), NP_DT_F32, int(precision), dim, _ptr(qf), _ptr(qoff32), B, _ptr(df),
-                                     _ptr(doff), n_docs, _ptr(ids), _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos)))
+        if i8:
+            _check(L.np_hip_maxsim_batch_i8(int(device), dim, _ptr(qf), _ptr(qs), _ptr(qoff32), B, _ptr(df), _ptr(ds), _ptr(doff),
+                                            n_docs, _ptr(ids), _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos)))
+        else:
+            _check(L.np_hip_maxsim_batch(int(device), NP_DT_F32, int(precision), dim, _ptr(qf), _ptr(qoff32), B, _ptr(df),
+                                         _ptr(doff), n_docs, _ptr(ids), _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos)))
     out, p0, r0 = [], 0, 0
     for i in range(B):
         ni, li = int(n[i]), int(lq[i])

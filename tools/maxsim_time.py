@@ -1,5 +1,6 @@
-"""Times np_hip_maxsim_batch (maxsim_scores on device tensors) against rerank_maxsim called once per query and against
-torch (matmul + amax + sum on the device), alternating in one process, and writes profiles/maxsim_time.md.
+"""Times np_hip_maxsim_batch (maxsim_scores on device tensors: f32, bf16 and int8 rows) against rerank_maxsim called once per
+query and against torch (matmul + amax + sum on the device), and quantize_rows against a device-to-device copy of its input
+bytes, alternating in one process, and writes profiles/maxsim_time.md.
 
     python tools/maxsim_time.py [--rounds 5] [--out profiles/maxsim_time.md]
 
@@ -57,11 +58,15 @@ def main():
         flop = 2.0 * npairs * lq * ld * dim
         tq, td = torch.from_numpy(q).cuda(), torch.from_numpy(d).cuda()
         hq, hd = tq.to(torch.bfloat16), td.to(torch.bfloat16)
+        (cq, sq), (cd, sd) = npa.quantize_rows(tq), npa.quantize_rows(td)
         td3 = td.view(nd, ld, dim)
         idx = None if pairs is None else torch.from_numpy(np.stack(pairs)).cuda()
 
         def ours(x, y, prec):
             return lambda: npa.maxsim_scores(x, y, pairs=pairs, precision=prec, query_offsets=qoff, document_offsets=doff)
+
+        def ours_i8():
+            return npa.maxsim_scores(cq, cd, pairs=pairs, query_offsets=qoff, document_offsets=doff, query_scales=sq, document_scales=sd)
 
         def torch_ref(x, y3):
             def f():
@@ -75,6 +80,7 @@ def main():
                 ids = range(nd) if pairs is None else pairs[b]
                 npa.rerank_maxsim(q[b * lq:(b + 1) * lq], [d[i * ld:(i + 1) * ld] for i in ids])
         paths = [("maxsim_batch f32, precision 0", ours(tq, td, 0), 4), ("maxsim_batch bf16 rows, precision 3", ours(hq, hd, 3), 2),
+                 ("maxsim_batch f32 rows, precision 3", ours(tq, td, 3), 4), ("maxsim_batch int8 rows (+ f32 row scales)", ours_i8, 1),
                  ("torch f32 matmul+amax+sum", torch_ref(tq, td3), 4), ("torch bf16 matmul+amax+sum", torch_ref(hq, hd.view(nd, ld, dim)), 2),
                  ("rerank_maxsim per query (host arrays)", rerank, 4)]
         times = {p[0]: [] for p in paths}
@@ -86,6 +92,21 @@ def main():
             byts = (q.size + d.size) * es + npairs * 4
             lines.append(f"| {name} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | "
                          f"{flop / np.median(t) / 1e12:.2f} | {byts / np.median(t) / 1e9:.1f} |")
+    lines += ["", "## quantize_rows against a device-to-device copy of the same input bytes", "",
+              "GB/s counts the input rows once (the quantiser also writes a quarter (f32) or half (bf16) as many bytes of codes; the copy",
+              "writes as many as it reads).", "", "| rows x dim, input | path | ms | spread ms | input GB/s |", "|---|---|---|---|---|"]
+    for n, dim, dt in ((1 << 20, 128, torch.float32), (1 << 20, 128, torch.bfloat16), (1 << 17, 1024, torch.float32)):
+        x = torch.randn((n, dim), device="cuda").to(dt)
+        y = torch.empty_like(x)
+        paths = [("quantize_rows", lambda: npa.quantize_rows(x)), ("torch copy_ (device to device)", lambda: y.copy_(x))]
+        times = {p[0]: [] for p in paths}
+        for _ in range(a.rounds):
+            for pname, fn in paths:
+                times[pname].append(window(fn, sync))
+        for pname, _ in paths:
+            t = np.array(times[pname])
+            lines.append(f"| {n} x {dim}, {str(dt).split('.')[-1]} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | "
+                         f"{x.numel() * x.element_size() / np.median(t) / 1e9:.1f} |")
     open(a.out, "w").write("\n".join(lines) + "\n")
     print("\n".join(lines))
 
