@@ -1183,6 +1183,41 @@ int np_hip_quantize_rows_i8(int32_t device, int32_t dtype, int32_t dim, const vo
 int np_hip_quantize_rows_i8_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
                                    int8_t* d_out_codes, float* d_out_scales, void* stream);
 
+/* ---- binary document rows for batched MaxSim (np_maxsim_b1.hip, np_quant.hip) ----------------------------------------
+ * The asymmetric binary form: query rows are what the _i8 entries take (int8 codes, `dim` bytes apart, one f32 scale per
+ * row); a document row is W = ceil(dim / 32) little-endian 32-bit words, W words apart, with one f32 scale per row.  Bit j
+ * of word w is dim 32 w + j; a set bit is +1, a clear bit -1; bits past `dim` in the last word may hold anything and change
+ * no output.  The rule is that of the _i8 entries with the document codes +-1 (tests/maxsim_i8_restate.py pair() on the
+ * unpacked bits), bit for bit:
+ *   dot         sum_{d < dim} cq[q][d] * (2 bit[t][d] - 1) in i32, exact: |dot| <= 1024 * 128 = 2^17
+ *   then        maximum over t of f32(dot) * sd[t] (non-finite products ignored, equal ones to the lowest t), one more
+ *               multiplication by sq[q] (a non-finite result: no match, 0.0 / -1), the q-ordered f32 sum: as above
+ * The document rows go from global memory to registers and are expanded there; they are never staged in LDS.  Shapes,
+ * offsets, pairs, matches, the host copies of the device entry, the limits and the one-allocation rule are those of the _i8
+ * entries; in addition NULL doc_bits with a document token is refused (NP_ERR_INVALID_ARGUMENT). */
+int np_hip_maxsim_batch_b1(int32_t device, int32_t dim, const int8_t* queries, const float* q_scales /* [q tokens] */,
+                           const int32_t* q_tok_offsets, int32_t B, const uint32_t* doc_bits /* [d tokens][W] */,
+                           const float* d_scales /* [d tokens] */, const int64_t* doc_tok_offsets, int64_t n_docs,
+                           const int64_t* pair_docs, const int64_t* pair_offsets, float* out_scores,
+                           float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+int np_hip_maxsim_batch_b1_device(int32_t device, int32_t dim, const int8_t* d_queries, const float* d_q_scales,
+                                  const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                  const uint32_t* d_doc_bits, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
+                                  const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                                  const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                                  float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
+/* The packer that makes such rows on the device.  rows: [n_rows][dim] of dtype NP_DT_F32 or NP_DT_BF16 (widened exactly; any
+ * other dtype is refused), 1 <= dim <= 1024.  Per row: bit_d = x_d >= 0 (+-0.0 set, NaN clear), pad bits 0; scale = (sum_d
+ * |x_d|) / dim, the least-squares scale of s * sign(x).  The sum is f32 in a fixed order: the row is cut into units of 4 (f32)
+ * or 8 (bf16) dims, unit u belongs to lane u mod 64, a lane adds its |x| in ascending dim order to 0.0f, then s = s + s[lane
+ * xor d] for d = 32, 16, .., 1; the division by f32(dim) is correctly rounded.  A row with a non-finite element: scale NaN
+ * (its bits are still written), so every similarity of that row is ignored.  out_bits [n_rows][W], out_scales [n_rows].
+ * The host entry stages the call through one device allocation; the device entry allocates nothing. */
+int np_hip_pack_rows_b1(int32_t device, int32_t dtype, int32_t dim, const void* rows, int64_t n_rows, uint32_t* out_bits,
+                        float* out_scales);
+int np_hip_pack_rows_b1_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
+                               uint32_t* d_out_bits, float* d_out_scales, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

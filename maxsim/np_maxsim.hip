@@ -55,6 +55,7 @@
 #include "np_internal.h"
 #include "np_exact.h"
 #include "np_maxsim_plan.h"
+#include "np_maxsim_dev.h"
 
 #include <string.h>
 #include <type_traits>
@@ -62,31 +63,9 @@
 
 namespace np {
 
-struct MaxsimP {
-  const void* Q;             // [q tokens][dim]
-  const int32_t* qoff;       // [B + 1]
-  const void* D;             // [d tokens][dim]
-  const int64_t* doff;       // [n_docs + 1]
-  const int64_t* pair_docs;  // NULL = all pairs
-  const int64_t* poff;       // [B + 1] (listed form)
-  float* scores;
-  float* sims;               // NULL, or a row entry per (pair, query token)
-  int32_t* pos;              // ...
-  int64_t n_docs;
-  int B, dim, G, nqt, WD;
-  int y0;                    // blockIdx.y of this launch starts here (launches are slices of NP_MS_MAX_GRID_Y)
-  int vecq, vecd;            // 16-byte loads are legal for every row of Q / D
-  const float* qscale;       // MODE 3: [q tokens], [d tokens]
-  const float* dscale;
-};
-
-constexpr int NP_MS_BROW = 72;                         // bf16 LDS row pitch in elements
-constexpr int NP_MS_META = 128;                        // bytes: the row base, the documents' offsets, lengths and flags
 
 // MODE 0: f32 rows, f32 MFMA.  1: f32 rows rounded to bf16, bf16 MFMA.  2: bf16 rows, bf16 MFMA.  3: int8 rows, i8 MFMA, in
 // the bf16 modes' LDS geometry (a row's 128 bytes are 128 dims instead of 64).
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
 constexpr int NP_MS_SCALE_AT = 128;                    // MODE 3: a document row's scale, in the pad bytes of its LDS row
 template <int MODE> struct MsRaw { uint4 v[MODE == 1 ? 2 : 1]; };   // one staging unit on its way from HBM to LDS
 
@@ -122,18 +101,6 @@ __device__ __forceinline__ uint4 ms_load8h(const uint16_t* rowp, int k0, int dim
 #pragma unroll
   for (int i = 0; i < 8; ++i)
     if (k0 + i < dim) w[i >> 1] |= (uint32_t)rowp[k0 + i] << (16 * (i & 1));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// sixteen int8 dims k0 .. k0 + 15 of a row
-__device__ __forceinline__ uint4 ms_load16b(const uint8_t* rowp, int k0, int dim, bool vec) {
-  uint4 r = make_uint4(0u, 0u, 0u, 0u);
-  if (!rowp || k0 >= dim) return r;
-  if (vec) return *reinterpret_cast<const uint4*>(rowp + k0);   // dim % 16 == 0: k0 + 16 <= dim
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-    if (k0 + i < dim) w[i >> 2] |= (uint32_t)rowp[k0 + i] << (8 * (i & 3));
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
@@ -204,21 +171,6 @@ __device__ __forceinline__ void ms_row_argmax(const f32x16& acc, int64_t t0, int
     if (trow < len && finitef(x)) {
       pos = x > mm ? (int)trow : pos;
       mm = fmaxf(mm, x);
-    }
-  }
-}
-
-// MODE 3: the same walk over f32(acc[r]) * sc[r] (sc = the scales of rows mfma_row(r, kk)), compared as keys: okey is 0 for
-// a non-finite product and grows with a finite one, so `best` ends as the key the workgroup's atomicMax takes.
-__device__ __forceinline__ void ms_row_argmax_i8(const i32x16& acc, const float (&sc)[16], int64_t t0, int64_t len, int kk,
-                                                 uint32_t& best, int& pos) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t trow = t0 + mfma_row(r, kk);
-    const uint32_t k = okey((float)acc[r] * sc[r]);
-    if (trow < len && k > best) {
-      best = k;
-      pos = (int)trow;
     }
   }
 }
@@ -514,7 +466,7 @@ static int maxsim_validate(int32_t dtype, int32_t precision, int32_t dim, int32_
   return c == 1 ? NP_ERR_SHAPE : NP_ERR_INVALID_ARGUMENT;
 }
 
-int maxsim_device_ok(int32_t device, int* compute_units) {   // np_quant.hip calls it too
+int maxsim_device_ok(int32_t device, int* compute_units) {   // np_quant.hip and np_maxsim_b1.hip call it too
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     (void)hipGetLastError();
@@ -536,7 +488,7 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
   const bool listed = d_pair_docs != nullptr;
   const MaxsimPlan plan = maxsim_plan(listed, h_qoff, B, n_docs, h_poff, compute_units);
   if (plan.gx <= 0 || plan.gy <= 0) return NP_OK;
-  const size_t pitch = (size_t)dim * (dtype == NP_MS_DT_I8 ? 1 : dtype == NP_MS_DT_BF16 ? 2 : 4);
+  const size_t pitch = maxsim_row_bytes(dtype, dim, false), dpitch = maxsim_row_bytes(dtype, dim, true);
   MaxsimP p;
   p.Q = d_q;
   p.qoff = d_qoff;
@@ -555,9 +507,10 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
   p.WD = plan.WD;
   p.y0 = 0;
   p.vecq = pitch % 16 == 0 && (uintptr_t)d_q % 16 == 0;
-  p.vecd = pitch % 16 == 0 && (uintptr_t)d_d % 16 == 0;
+  p.vecd = dpitch % 16 == 0 && (uintptr_t)d_d % 16 == 0;
   p.qscale = d_qscale;
   p.dscale = d_dscale;
+  if (dtype == NP_MS_DT_B1) return maxsim_b1_launch(st, p, plan);
   if (dtype == NP_MS_DT_I8) return maxsim_launch_mode<3>(st, p, plan);
   if (precision == 0) return maxsim_launch_mode<0>(st, p, plan);
   if (dtype == NP_MS_DT_F32) return maxsim_launch_mode<1>(st, p, plan);
@@ -580,8 +533,8 @@ static int maxsim_validate_i8(int32_t dim, const void* q_scales, int32_t B, cons
   return c == 1 ? NP_ERR_SHAPE : NP_ERR_INVALID_ARGUMENT;
 }
 
-// The device entries after their checks: every array in HBM.  d_q_scales / d_d_scales: the int8 entry's, NULL otherwise.
-static int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
+// The device entries after their checks: every array in HBM.  d_q_scales / d_d_scales: the int8 and binary entries', NULL otherwise.
+int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
                               const float* d_q_scales, const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
                               const void* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
                               const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
@@ -604,7 +557,7 @@ static int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, 
 }
 
 // The host entries after their checks: the call staged through one allocation.
-static int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
+int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
                             const float* q_scales, const int32_t* q_tok_offsets, int32_t B, const void* documents,
                             const float* d_scales, const int64_t* doc_tok_offsets, int64_t n_docs, const int64_t* pair_docs,
                             const int64_t* pair_offsets, float* out_scores, float* out_match_sims, int32_t* out_match_pos) {
@@ -625,8 +578,8 @@ static int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, in
   NP_TRY(maxsim_device_ok(device, &cus));
   DeviceGuard g(device);
   // one allocation for the call: inputs (int8: and their scales), offsets, outputs, each on a 256-byte boundary
-  const size_t es = dtype == NP_MS_DT_I8 ? 1 : dtype == NP_MS_DT_BF16 ? 2 : 4;
-  const size_t b_q = up256((size_t)qtok * dim * es), b_d = up256((size_t)dtok * dim * es);
+  const size_t n_q = (size_t)qtok * maxsim_row_bytes(dtype, dim, false), n_d = (size_t)dtok * maxsim_row_bytes(dtype, dim, true);
+  const size_t b_q = up256(n_q), b_d = up256(n_d);
   const size_t b_qs = q_scales ? up256((size_t)qtok * 4) : 0, b_ds = d_scales ? up256((size_t)dtok * 4) : 0;
   const size_t b_qoff = up256((size_t)(B + 1) * 4), b_doff = up256((size_t)(n_docs + 1) * 8);
   const size_t b_ids = listed ? up256((size_t)P * 8) : 0, b_poff = listed ? up256((size_t)(B + 1) * 8) : 0;
@@ -646,8 +599,8 @@ static int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, in
   float* d_sc = (float*)carve.take(b_sc);
   float* d_sim = out_match_sims ? (float*)carve.take(b_sim) : nullptr;
   int32_t* d_pos = out_match_pos ? (int32_t*)carve.take(b_pos) : nullptr;
-  if (qtok > 0) NP_HIP(hipMemcpy(d_q, queries, (size_t)qtok * dim * es, hipMemcpyHostToDevice));
-  if (dtok > 0) NP_HIP(hipMemcpy(d_d, documents, (size_t)dtok * dim * es, hipMemcpyHostToDevice));
+  if (qtok > 0) NP_HIP(hipMemcpy(d_q, queries, n_q, hipMemcpyHostToDevice));
+  if (dtok > 0) NP_HIP(hipMemcpy(d_d, documents, n_d, hipMemcpyHostToDevice));
   if (d_qs && qtok > 0) NP_HIP(hipMemcpy(d_qs, q_scales, (size_t)qtok * 4, hipMemcpyHostToDevice));
   if (d_ds && dtok > 0) NP_HIP(hipMemcpy(d_ds, d_scales, (size_t)dtok * 4, hipMemcpyHostToDevice));
   NP_HIP(hipMemcpy(d_qoff, q_tok_offsets, (size_t)(B + 1) * 4, hipMemcpyHostToDevice));
@@ -665,7 +618,7 @@ static int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, in
 }
 
 // pair_docs and pair_offsets (the device entries: and the host copy) go together; *listed = they are there
-static int maxsim_pair_args(bool all, bool any, bool device_entry, bool* listed) {
+int maxsim_pair_args(bool all, bool any, bool device_entry, bool* listed) {
   *listed = any;
   if (any && !all) {
     set_error(device_entry ? "Search failed: maxsim_batch: pair_docs and pair_offsets (device and host copy) go together, or all NULL"
