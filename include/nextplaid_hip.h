@@ -1218,6 +1218,43 @@ int np_hip_pack_rows_b1(int32_t device, int32_t dtype, int32_t dim, const void* 
 int np_hip_pack_rows_b1_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
                                uint32_t* d_out_bits, float* d_out_scales, void* stream);
 
+/* ---- int4 document rows for batched MaxSim (np_maxsim_i4.hip, np_quant.hip) -------------------------------------------
+ * Query rows are what the _i8 and _b1 entries take (int8 codes, `dim` bytes apart, one f32 scale per row); a document row
+ * is W = ceil(dim / 8) little-endian 32-bit words, W words apart, with one f32 scale per row.  Nibble j of word w is bits
+ * 4 j .. 4 j + 3 and holds dim 8 w + j as a two's-complement code in -8 .. 7 (every value is legal); nibbles past `dim` in
+ * the last word may hold anything and change no output.  The rule is that of the _i8 entries on the unpacked codes
+ * (tests/maxsim_i8_restate.py pair() on tests/maxsim_i4_restate.py unpack()), bit for bit:
+ *   dot         sum_{d < dim} cq[q][d] * code[t][d] in i32, exact: |dot| <= 1024 * 128 * 8 = 2^20
+ *   then        maximum over t of f32(dot) * sd[t] (one rounding; non-finite products ignored, the okey order, equal ones to
+ *               the lowest t), one more multiplication by sq[q] (a non-finite result: no match, 0.0 / -1), the f32 sum in
+ *               query-token order from 0.0f; an empty query or document scores 0
+ *   scales      taken as given (any f32; a NaN scale removes its row)
+ * The document rows go from global memory to registers and are expanded there; they are never staged in LDS.  Shapes,
+ * offsets, pairs or all pairs, matches, the independence promise, the host copies of the device entry, the limits
+ * (1 <= dim <= 1024, at most 256 tokens per query) and the one-allocation rule are those of the _i8 entries; in addition
+ * NULL doc_words with a document token is refused (NP_ERR_INVALID_ARGUMENT). */
+int np_hip_maxsim_batch_i4(int32_t device, int32_t dim, const int8_t* queries, const float* q_scales /* [q tokens] */,
+                           const int32_t* q_tok_offsets, int32_t B, const uint32_t* doc_words /* [d tokens][W] */,
+                           const float* d_scales /* [d tokens] */, const int64_t* doc_tok_offsets, int64_t n_docs,
+                           const int64_t* pair_docs, const int64_t* pair_offsets, float* out_scores,
+                           float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+int np_hip_maxsim_batch_i4_device(int32_t device, int32_t dim, const int8_t* d_queries, const float* d_q_scales,
+                                  const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                  const uint32_t* d_doc_words, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
+                                  const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                                  const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                                  float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
+/* The quantiser that makes such rows on the device: the int8 quantiser's rule with 7 for 127.  rows: [n_rows][dim] of dtype
+ * NP_DT_F32 or NP_DT_BF16 (widened exactly; any other dtype is refused), 1 <= dim <= 1024.  Per row: a = max_d |x_d|, scale =
+ * a / 7 and inv = 7 / a (both correctly rounded f32 divisions), code_d = clamp(rintf(x_d * inv), -7, 7) with one f32 product
+ * and ties to even; pad nibbles are 0.  a == 0: scale 0 and codes 0.  A row with a non-finite element: scale NaN and codes
+ * 0.  out_words [n_rows][W], out_scales [n_rows].  The host entry stages the call through one device allocation; the
+ * device entry allocates nothing, enqueues on `stream` and returns. */
+int np_hip_quantize_rows_i4(int32_t device, int32_t dtype, int32_t dim, const void* rows, int64_t n_rows, uint32_t* out_words,
+                            float* out_scales);
+int np_hip_quantize_rows_i4_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
+                                   uint32_t* d_out_words, float* d_out_scales, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

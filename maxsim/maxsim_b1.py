@@ -51,7 +51,7 @@ def pack_rows_b1(rows, device: int = 0):
     return bits, scales
 
 
-def _scales(s, rows, what):
+def _scales(s, rows, what, name):
     """One f32 scale per row of `rows`, flat and where the rows are (a list that parallels the row list is concatenated)."""
     if _is_torch(rows):
         import torch
@@ -60,7 +60,7 @@ def _scales(s, rows, what):
     else:
         s = np.concatenate([np.ravel(x) for x in ([s] if isinstance(s, np.ndarray) else s)] + [np.zeros(1)]).astype(np.float32)
     if s.shape[0] - 1 != rows.shape[0]:
-        raise ValueError(f"maxsim_scores_b1: {what}_scales holds one scale per {what} row")
+        raise ValueError(f"{name}: {what}_scales holds one scale per {what} row")
     return s
 
 
@@ -72,16 +72,25 @@ def maxsim_scores_b1(queries, query_scales, doc_bits, document_scales, pairs=Non
     as lists that parallel them or flat.  numpy (int8 / uint32) or torch device tensors (int8 / int32).  pairs: one list of
     document ids per query, None = all pairs.  Returns what api.maxsim_scores returns: per query its scores, with
     return_matches a tuple (scores, sims [n_i, Lq_i], positions i32 [n_i, Lq_i])."""
+    L = lib()
+    return _scores_words("maxsim_scores_b1", "doc_bits", 32, L.np_hip_maxsim_batch_b1, L.np_hip_maxsim_batch_b1_device, queries,
+                         query_scales, doc_bits, document_scales, pairs, return_matches, device, query_offsets, document_offsets)
+
+
+def _scores_words(name, words, per_word, host_entry, device_entry, queries, query_scales, doc_bits, document_scales, pairs,
+                  return_matches, device, query_offsets, document_offsets):
+    """maxsim_scores_b1 for any form whose document rows are 32-bit words of `per_word` dims (maxsim_i4.py: 8) and whose two C
+    entries take the _b1 argument lists; `name` and `words` are what the messages call the function and the rows."""
     qf, qoff = _maxsim_pack(queries, query_offsets, "query")
     df, doff = _maxsim_pack(doc_bits, document_offsets, "document")
     if qoff.size <= 1:
         return []
     on_dev = _is_torch(qf)
     if on_dev != _is_torch(df):
-        raise ValueError("maxsim_scores_b1: queries and doc_bits must both be numpy arrays or both torch tensors")
-    if qf.ndim != 2 or df.ndim != 2 or df.shape[1] != (qf.shape[1] + 31) // 32:
-        raise ShapeError(f"Shape error: queries {tuple(qf.shape)} must be [tokens, dim] and doc_bits {tuple(df.shape)} [tokens, ceil(dim / 32)]")
-    qs, ds = _scales(query_scales, qf, "query"), _scales(document_scales, df, "document")
+        raise ValueError(f"{name}: queries and {words} must both be numpy arrays or both torch tensors")
+    if qf.ndim != 2 or df.ndim != 2 or df.shape[1] != (qf.shape[1] + per_word - 1) // per_word:
+        raise ShapeError(f"Shape error: queries {tuple(qf.shape)} must be [tokens, dim] and {words} {tuple(df.shape)} [tokens, ceil(dim / {per_word})]")
+    qs, ds = _scales(query_scales, qf, "query", name), _scales(document_scales, df, "document", name)
     dim = int(qf.shape[1])
     B, n_docs = qoff.size - 1, doff.size - 1
     qoff32 = np.ascontiguousarray(qoff, np.int32)
@@ -100,7 +109,7 @@ def maxsim_scores_b1(queries, query_scales, doc_bits, document_scales, pairs=Non
     if on_dev:
         import torch
         if qf.dtype != torch.int8 or df.dtype != torch.int32 or not qf.is_cuda or not df.is_cuda:
-            raise ValueError("maxsim_scores_b1: device tensors must be int8 queries and int32 bit words, on the GPU")
+            raise ValueError(f"{name}: device tensors must be int8 queries and int32 words, on the GPU")
         dev = qf.device
         qf, df = qf.contiguous(), df.contiguous()
         t = lambda a: None if a is None else torch.from_numpy(a).to(dev)   # noqa: E731
@@ -109,16 +118,16 @@ def maxsim_scores_b1(queries, query_scales, doc_bits, document_scales, pairs=Non
         sc = torch.zeros(max(P, 1), dtype=torch.float32, device=dev)
         sims = torch.zeros(max(R, 1), dtype=torch.float32, device=dev) if return_matches else None
         pos = torch.zeros(max(R, 1), dtype=torch.int32, device=dev) if return_matches else None
-        _check(lib().np_hip_maxsim_batch_b1_device(dev.index or 0, dim, tp(qf), tp(qs), tp(d_qoff), _ptr(qoff32), B, tp(df), tp(ds),
-                                                   tp(d_doff), _ptr(doff), n_docs, tp(d_ids), tp(d_poff), _ptr(poff), tp(sc),
-                                                   tp(sims), tp(pos), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _check(device_entry(dev.index or 0, dim, tp(qf), tp(qs), tp(d_qoff), _ptr(qoff32), B, tp(df), tp(ds), tp(d_doff), _ptr(doff),
+                            n_docs, tp(d_ids), tp(d_poff), _ptr(poff), tp(sc), tp(sims), tp(pos),
+                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     else:
         qf, df = np.ascontiguousarray(qf, np.int8), np.ascontiguousarray(df, np.uint32)
         sc = np.zeros(max(P, 1), np.float32)
         sims = np.zeros(max(R, 1), np.float32) if return_matches else None
         pos = np.zeros(max(R, 1), np.int32) if return_matches else None
-        _check(lib().np_hip_maxsim_batch_b1(int(device), dim, _ptr(qf), _ptr(qs), _ptr(qoff32), B, _ptr(df), _ptr(ds), _ptr(doff),
-                                            n_docs, _ptr(ids), _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos)))
+        _check(host_entry(int(device), dim, _ptr(qf), _ptr(qs), _ptr(qoff32), B, _ptr(df), _ptr(ds), _ptr(doff), n_docs, _ptr(ids),
+                          _ptr(poff), _ptr(sc), _ptr(sims), _ptr(pos)))
     out, p0, r0 = [], 0, 0
     for i in range(B):
         ni, li = int(n[i]), int(lq[i])

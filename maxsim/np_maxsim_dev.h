@@ -1,5 +1,5 @@
-// np_maxsim_dev.h -- what the batched-MaxSim kernels share: maxsim_kernel (np_maxsim.hip) and maxsim_b1_kernel
-// (np_maxsim_b1.hip) take the same launch arguments, the int8 LDS geometry and the scaled argmax walk; the entries of both
+// np_maxsim_dev.h -- what the batched-MaxSim kernels share: maxsim_kernel (np_maxsim.hip), maxsim_b1_kernel
+// (np_maxsim_b1.hip) and maxsim_i4_kernel (np_maxsim_i4.hip) take the same launch arguments, the int8 LDS geometry and the scaled argmax walk; the entries of both
 // files go through the same staging (np_maxsim.hip defines it).
 #pragma once
 #include "np_internal.h"
@@ -11,7 +11,7 @@ namespace np {
 struct MaxsimP {
   const void* Q;             // [q tokens][dim]
   const int32_t* qoff;       // [B + 1]
-  const void* D;             // [d tokens][dim]; binary rows: [d tokens][ceil(dim / 32)] words
+  const void* D;             // [d tokens][dim]; binary / int4 rows: [d tokens][ceil(dim / 32 or 8)] words
   const int64_t* doff;       // [n_docs + 1]
   const int64_t* pair_docs;  // NULL = all pairs
   const int64_t* poff;       // [B + 1] (listed form)
@@ -22,7 +22,7 @@ struct MaxsimP {
   int B, dim, G, nqt, WD;
   int y0;                    // blockIdx.y of this launch starts here (launches are slices of NP_MS_MAX_GRID_Y)
   int vecq, vecd;            // 16-byte loads are legal for every row of Q / D
-  const float* qscale;       // int8 and binary rows: [q tokens], [d tokens]
+  const float* qscale;       // int8, binary and int4 rows: [q tokens], [d tokens]
   const float* dscale;
 };
 
@@ -62,7 +62,7 @@ __device__ __forceinline__ void ms_row_argmax_i8(const i32x16& acc, const float 
 int maxsim_device_ok(int32_t device, int* compute_units);
 // pair_docs and pair_offsets (the device entries: and the host copy) go together; *listed = they are there
 int maxsim_pair_args(bool all, bool any, bool device_entry, bool* listed);
-// The entries after their checks.  dtype NP_MS_DT_B1: queries are int8 rows, documents rows of bit words.
+// The entries after their checks.  dtype NP_MS_DT_B1 / NP_MS_DT_I4: queries are int8 rows, documents rows of bit / nibble words.
 int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
                        const float* d_q_scales, const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
                        const void* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
@@ -75,5 +75,7 @@ int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t d
                      float* out_scores, float* out_match_sims, int32_t* out_match_pos);
 // np_maxsim_b1.hip: the launches of maxsim_b1_kernel for a filled MaxsimP
 int maxsim_b1_launch(hipStream_t st, MaxsimP p, const MaxsimPlan& plan);
+// np_maxsim_i4.hip: the launches of maxsim_i4_kernel
+int maxsim_i4_launch(hipStream_t st, MaxsimP p, const MaxsimPlan& plan);
 
 }  // namespace np

@@ -9,6 +9,7 @@ namespace np {
 constexpr int NP_MS_DT_F32 = 0, NP_MS_DT_BF16 = 1;   // NP_DT_F32 / NP_DT_BF16 of the public header
 constexpr int NP_MS_DT_I8 = 2;                // NP_DT_I8: int8 codes with one f32 scale per row (the _i8 entries only)
 constexpr int NP_MS_DT_B1 = 3;                // inside the library only: int8 query rows against document rows of one bit per dim (the _b1 entries)
+constexpr int NP_MS_DT_I4 = 4;                // inside the library only: int8 query rows against document rows of one nibble per dim (the _i4 entries)
 constexpr int NP_MS_MAX_DIM = 1024;
 constexpr int NP_MS_MAX_QUERY_TOKENS = 256;   // eight 32-token query tiles, as S6
 constexpr int NP_MS_KC_F32 = 32;              // dims per LDS chunk, f32 MFMA (16 steps of 32x32x2)
@@ -85,15 +86,26 @@ inline int maxsim_check_args_b1(int32_t dim, const void* q_scales, int32_t B, co
   return c;
 }
 
-// bytes of one row: f32 / bf16 / int8 rows are `dim` elements; a binary document row is ceil(dim / 32) 32-bit words and
-// its queries are int8 rows
+// np_hip_maxsim_batch_i4: the binary entry's checks; doc_words are the nibble rows.
+inline int maxsim_check_args_i4(int32_t dim, const void* q_scales, int32_t B, const int32_t* q_tok_offsets, const void* doc_words,
+                                const void* d_scales, int64_t n_docs, const int64_t* doc_tok_offsets, bool listed,
+                                const int64_t* pair_docs, const int64_t* pair_offsets, const char** why, int64_t* bad_pair) {
+  const int c = maxsim_check_args_i8(dim, q_scales, B, q_tok_offsets, d_scales, n_docs, doc_tok_offsets, listed, pair_docs,
+                                     pair_offsets, why, bad_pair);
+  if (c == 0 && n_docs > 0 && doc_tok_offsets[n_docs] > 0 && !doc_words) return *why = "doc_words is NULL", 2;
+  return c;
+}
+
+// bytes of one row: f32 / bf16 / int8 rows are `dim` elements; a binary document row is ceil(dim / 32) 32-bit words, an
+// int4 document row ceil(dim / 8) words, and the queries of both are int8 rows
 inline size_t maxsim_row_bytes(int32_t dtype, int32_t dim, bool document) {
   if (dtype == NP_MS_DT_B1) return document ? (size_t)((dim + 31) / 32) * 4 : (size_t)dim;
+  if (dtype == NP_MS_DT_I4) return document ? (size_t)((dim + 7) / 8) * 4 : (size_t)dim;
   return (size_t)dim * (dtype == NP_MS_DT_I8 ? 1 : dtype == NP_MS_DT_BF16 ? 2 : 4);
 }
 
 // np_hip_quantize_rows_i8: one wave takes a whole row, 16 elements a lane, so dim has maxsim's limit.  0 / 1 / 2 as above.
-// np_hip_pack_rows_b1 has the same limits (out_codes = its bit words).
+// np_hip_pack_rows_b1 and np_hip_quantize_rows_i4 have the same limits (out_codes = their words).
 inline int quantize_check_args(int32_t dtype, int32_t dim, int64_t n_rows, const void* rows, const void* out_codes,
                                const void* out_scales, const char** why) {
   *why = "";

@@ -1,5 +1,6 @@
 // np_quant.hip -- np_hip_quantize_rows_i8: f32 or bf16 rows to int8 codes with one f32 scale per row, the operands of
-// np_hip_maxsim_batch_i8 (np_maxsim.hip, MODE 3); and np_hip_pack_rows_b1 (further down): the same rows to one bit per dim.
+// np_hip_maxsim_batch_i8 (np_maxsim.hip, MODE 3); np_hip_pack_rows_b1 (further down): the same rows to one bit per dim; and
+// np_hip_quantize_rows_i4 (after it): the same rows to one nibble per dim.
 //
 //   rule          per row: a = max_d |x_d|, scale = a / 127, inv = 127 / a (both correctly rounded f32 divisions),
 //                 code_d = clamp(rintf(x_d * inv), -127, 127) (one f32 product, nearest with ties to even).  a == 0: scale 0,
@@ -221,6 +222,119 @@ static int pack_run(hipStream_t st, int32_t dtype, int32_t dim, const void* d_ro
   return NP_OK;
 }
 
+// ---- np_hip_quantize_rows_i4: rows to one two's-complement nibble per dim and one f32 scale per row (np_maxsim_i4.hip's
+// documents) ------------------------------------------------------------------------------------------------------------
+//   rule          the int8 quantiser's with 7 for 127: a = max_d |x_d|, scale = a / 7, inv = 7 / a (correctly rounded),
+//                 code_d = clamp(rintf(x_d * inv), -7, 7); nibble j of word w is dim 8 w + j and the pad nibbles are 0.
+//                 a == 0: scale 0, codes 0.  A row with a non-finite element: scale NaN, codes 0.
+//   work split    the int8 quantiser's: one wave per row, lane l takes the 16-byte units l, l + 64, ..., which stay in
+//                 registers between the absmax pass and the rounding pass.  A bf16 unit is 8 dims, a whole word, which its
+//                 lane stores; an f32 unit is 4 dims, half a word, shifted into place and OR-ed with the neighbour lane's
+//                 half by one xor shuffle, and the even lane stores.  Consecutive words across the wave; no LDS, no atomics.
+struct Quant4P {
+  const void* rows;   // [n_rows][dim] f32 or bf16
+  uint32_t* words;    // [n_rows][ceil(dim / 8)]
+  float* scales;      // [n_rows]
+  int64_t n_rows;
+  int dim;
+  int vec_in;         // 16-byte loads are legal for every row
+};
+
+template <bool BF>
+__global__ void __launch_bounds__(256) quantize_rows_i4_kernel(Quant4P p) {
+  constexpr int EL = BF ? 8 : 4, NU = NP_MS_MAX_DIM / (64 * EL);
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= p.n_rows) return;   // a whole wave; the kernel has no barrier
+  const int dim = p.dim;
+  float x[NU][EL];
+  uint32_t amax = 0u, bad = 0u;   // |x| as bits: for finite values the integer order is the f32 order
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    const int k0 = (u * 64 + lane) * EL;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};   // the unit's 16 bytes, zeros past dim
+    if (k0 < dim) {
+      if (p.vec_in) {
+        const uint4 v = *reinterpret_cast<const uint4*>(static_cast<const char*>(p.rows) + ((size_t)row * dim + k0) * (BF ? 2 : 4));
+        w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+      } else if (BF) {
+        const uint16_t* rp = static_cast<const uint16_t*>(p.rows) + (size_t)row * dim;
+#pragma unroll
+        for (int i = 0; i < EL; ++i)
+          if (k0 + i < dim) w[i >> 1] |= (uint32_t)rp[k0 + i] << (16 * (i & 1));
+      } else {
+        const uint32_t* rp = static_cast<const uint32_t*>(p.rows) + (size_t)row * dim;
+#pragma unroll
+        for (int i = 0; i < EL; ++i)
+          if (k0 + i < dim) w[i] = rp[k0 + i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < EL; ++i) {
+      const uint32_t b = BF ? (w[i >> 1] >> (16 * (i & 1))) << 16 : w[i];
+      x[u][i] = __uint_as_float(b);
+      const uint32_t mag = b & 0x7FFFFFFFu;
+      bad |= mag >= 0x7F800000u ? 1u : 0u;
+      amax = mag > amax ? mag : amax;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)amax, d);
+    amax = o > amax ? o : amax;
+    bad |= (uint32_t)__shfl_xor((int)bad, d);
+  }
+  const float a = __uint_as_float(amax);
+  const bool zero = bad || amax == 0u;            // every code is 0
+  const float inv = zero ? 0.f : __fdiv_rn(7.0f, a);
+  if (lane == 0) p.scales[row] = bad ? __uint_as_float(0x7FC00000u) : __fdiv_rn(a, 7.0f);
+  uint32_t* out = p.words + (size_t)row * ((dim + 7) / 8);
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    if (u * 64 * EL >= dim) break;                // the whole wave: the shuffle below has every lane
+    const int k0 = (u * 64 + lane) * EL;
+    uint32_t nib = 0u;
+#pragma unroll
+    for (int i = 0; i < EL; ++i) {
+      const float r = zero || k0 + i >= dim ? 0.f : fminf(fmaxf(rintf(x[u][i] * inv), -7.0f), 7.0f);
+      nib |= ((uint32_t)(int)r & 0xFu) << (4 * i);
+    }
+    if (BF) {
+      if (k0 < dim) out[k0 >> 3] = nib;
+    } else {
+      uint32_t word = nib << (16 * (lane & 1));
+      word |= (uint32_t)__shfl_xor((int)word, 1);
+      if ((lane & 1) == 0 && k0 < dim) out[k0 >> 3] = word;
+    }
+  }
+}
+
+static int quantize4_validate(int32_t dtype, int32_t dim, int64_t n_rows, const void* rows, const void* words, const void* scales) {
+  const char* why = "";
+  const int c = quantize_check_args(dtype, dim, n_rows, rows, words, scales, &why);
+  if (c == 0) return NP_OK;
+  set_error("%s: quantize_rows_i4: %s (dtype=%d dim=%d)", c == 1 ? "Shape error" : "Search failed", why, dtype, dim);
+  return c == 1 ? NP_ERR_SHAPE : NP_ERR_INVALID_ARGUMENT;
+}
+
+// every array on the device; enqueues and returns
+static int quantize4_run(hipStream_t st, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows, uint32_t* d_words,
+                         float* d_scales) {
+  const bool bf = dtype == NP_MS_DT_BF16;
+  Quant4P p;
+  p.rows = d_rows;
+  p.words = d_words;
+  p.scales = d_scales;
+  p.n_rows = n_rows;
+  p.dim = dim;
+  p.vec_in = ((size_t)dim * (bf ? 2 : 4)) % 16 == 0 && (uintptr_t)d_rows % 16 == 0;
+  const unsigned grid = (unsigned)((n_rows + 3) / 4);
+  if (bf) quantize_rows_i4_kernel<true><<<grid, 256, 0, st>>>(p);
+  else quantize_rows_i4_kernel<false><<<grid, 256, 0, st>>>(p);
+  NP_HIP(hipGetLastError());
+  return NP_OK;
+}
+
 int maxsim_device_ok(int32_t device, int* compute_units);   // np_maxsim.hip
 
 }  // namespace np
@@ -293,6 +407,40 @@ int np_hip_pack_rows_b1(int32_t device, int32_t dtype, int32_t dim, const void* 
   NP_HIP(hipMemcpy(d_in, rows, n_in, hipMemcpyHostToDevice));
   NP_TRY(pack_run(nullptr, dtype, dim, d_in, n_rows, d_bits, d_scales));
   NP_HIP(hipMemcpy(out_bits, d_bits, n_bits, hipMemcpyDeviceToHost));
+  NP_HIP(hipMemcpy(out_scales, d_scales, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+  return NP_OK;
+}
+
+int np_hip_quantize_rows_i4_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
+                                   uint32_t* d_out_words, float* d_out_scales, void* stream) {
+  clear_error();
+  NP_TRY(quantize4_validate(dtype, dim, n_rows, d_rows, d_out_words, d_out_scales));
+  if (n_rows == 0) return NP_OK;
+  int cus = 0;
+  NP_TRY(maxsim_device_ok(device, &cus));
+  DeviceGuard g(device);
+  return quantize4_run((hipStream_t)stream, dtype, dim, d_rows, n_rows, d_out_words, d_out_scales);
+}
+
+int np_hip_quantize_rows_i4(int32_t device, int32_t dtype, int32_t dim, const void* rows, int64_t n_rows, uint32_t* out_words,
+                            float* out_scales) {
+  clear_error();
+  NP_TRY(quantize4_validate(dtype, dim, n_rows, rows, out_words, out_scales));
+  if (n_rows == 0) return NP_OK;
+  int cus = 0;
+  NP_TRY(maxsim_device_ok(device, &cus));
+  DeviceGuard g(device);
+  // one allocation for the call: rows, nibble words, scales, each on a 256-byte boundary
+  const size_t n_in = (size_t)n_rows * dim * (dtype == NP_MS_DT_BF16 ? 2 : 4), n_words = (size_t)n_rows * ((dim + 7) / 8) * 4;
+  DevPtr<char> buf;
+  NP_TRY(buf.alloc(up256(n_in) + up256(n_words) + up256((size_t)n_rows * 4)));
+  Carver carve{buf.get()};
+  char* d_in = carve.take(up256(n_in));
+  uint32_t* d_words = (uint32_t*)carve.take(up256(n_words));
+  float* d_scales = (float*)carve.take((size_t)n_rows * 4);
+  NP_HIP(hipMemcpy(d_in, rows, n_in, hipMemcpyHostToDevice));
+  NP_TRY(quantize4_run(nullptr, dtype, dim, d_in, n_rows, d_words, d_scales));
+  NP_HIP(hipMemcpy(out_words, d_words, n_words, hipMemcpyDeviceToHost));
   NP_HIP(hipMemcpy(out_scales, d_scales, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
   return NP_OK;
 }

@@ -1,5 +1,5 @@
-"""Times np_hip_maxsim_batch (maxsim_scores on device tensors: f32, bf16, int8 and binary document rows) against rerank_maxsim
-called once per query and against torch (matmul + amax + sum on the device), and quantize_rows / pack_rows_b1 against a
+"""Times np_hip_maxsim_batch (maxsim_scores on device tensors: f32, bf16, int8, binary and int4 document rows) against rerank_maxsim
+called once per query and against torch (matmul + amax + sum on the device), and quantize_rows / pack_rows_b1 / quantize_rows_i4 against a
 device-to-device copy of their input bytes, alternating in one process, and writes profiles/maxsim_time.md.
 
     python tools/maxsim_time.py [--rounds 5] [--out profiles/maxsim_time.md]
@@ -19,12 +19,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "next-plaid_amd"), ROOT]
 import next_plaid_amd as npa  # noqa: E402
 from maxsim import maxsim_b1 as B1  # noqa: E402
+from maxsim import maxsim_i4 as I4  # noqa: E402
 
 # (name, queries, query tokens, documents, document tokens, dim, listed documents per query or None = all pairs)
 SHAPES = [("64 x 1000 listed x 300 tok, dim 128", 64, 32, 4000, 300, 128, 1000),
           ("32 x 32 all pairs, 1030-tok pages, dim 128", 32, 24, 32, 1030, 128, None),
           ("16 x 200 listed x 300 tok, dim 1024", 16, 32, 800, 300, 1024, 200)]
-# all pairs, large enough that the document bytes matter: int8 and binary rows only, made on the device
+# all pairs, large enough that the document bytes matter: int8, binary and int4 rows only, made on the device
 BIG = ("64 x 20000 all pairs, 1030-tok pages, dim 128", 64, 32, 20000, 1030, 128)
 
 
@@ -63,6 +64,7 @@ def main():
         hq, hd = tq.to(torch.bfloat16), td.to(torch.bfloat16)
         (cq, sq), (cd, sd) = npa.quantize_rows(tq), npa.quantize_rows(td)
         bd, sb = B1.pack_rows_b1(td)
+        wd, sw = I4.quantize_rows_i4(td)
         td3 = td.view(nd, ld, dim)
         idx = None if pairs is None else torch.from_numpy(np.stack(pairs)).cuda()
 
@@ -74,6 +76,9 @@ def main():
 
         def ours_b1():
             return B1.maxsim_scores_b1(cq, sq, bd, sb, pairs=pairs, query_offsets=qoff, document_offsets=doff)
+
+        def ours_i4():
+            return I4.maxsim_scores_i4(cq, sq, wd, sw, pairs=pairs, query_offsets=qoff, document_offsets=doff)
 
         def torch_ref(x, y3):
             def f():
@@ -89,6 +94,7 @@ def main():
         paths = [("maxsim_batch f32, precision 0", ours(tq, td, 0), 4), ("maxsim_batch bf16 rows, precision 3", ours(hq, hd, 3), 2),
                  ("maxsim_batch f32 rows, precision 3", ours(tq, td, 3), 4), ("maxsim_batch int8 rows (+ f32 row scales)", ours_i8, 1),
                  ("maxsim_batch_b1 int8 queries, binary documents (+ f32 row scales)", ours_b1, (1, 1 / 8)),
+                 ("maxsim_batch_i4 int8 queries, int4 documents (+ f32 row scales)", ours_i4, (1, 1 / 2)),
                  ("torch f32 matmul+amax+sum", torch_ref(tq, td3), 4), ("torch bf16 matmul+amax+sum", torch_ref(hq, hd.view(nd, ld, dim)), 2),
                  ("rerank_maxsim per query (host arrays)", rerank, 4)]
         times = {p[0]: [] for p in paths}
@@ -105,12 +111,15 @@ def main():
     cq = torch.randint(-128, 128, (B * lq, dim), dtype=torch.int8, device="cuda")
     cd = torch.randint(-128, 128, (nd * ld, dim), dtype=torch.int8, device="cuda")
     bd = torch.randint(-2 ** 31, 2 ** 31, (nd * ld, dim // 32), dtype=torch.int32, device="cuda")
+    wd = torch.randint(-2 ** 31, 2 ** 31, (nd * ld, dim // 8), dtype=torch.int32, device="cuda")
     sq, sd = torch.rand(B * lq, device="cuda") + 0.5, torch.rand(nd * ld, device="cuda") + 0.5
     qoff, doff = np.arange(B + 1) * lq, np.arange(nd + 1) * ld
     paths = [("maxsim_batch int8 rows (+ f32 row scales)",
               lambda: npa.maxsim_scores(cq, cd, query_offsets=qoff, document_offsets=doff, query_scales=sq, document_scales=sd), cd.numel()),
              ("maxsim_batch_b1 int8 queries, binary documents (+ f32 row scales)",
-              lambda: B1.maxsim_scores_b1(cq, sq, bd, sd, query_offsets=qoff, document_offsets=doff), bd.numel() * 4)]
+              lambda: B1.maxsim_scores_b1(cq, sq, bd, sd, query_offsets=qoff, document_offsets=doff), bd.numel() * 4),
+             ("maxsim_batch_i4 int8 queries, int4 documents (+ f32 row scales)",
+              lambda: I4.maxsim_scores_i4(cq, sq, wd, sd, query_offsets=qoff, document_offsets=doff), wd.numel() * 4)]
     times = {p[0]: [] for p in paths}
     for _ in range(a.rounds):
         for pname, fn, _ in paths:
@@ -119,15 +128,17 @@ def main():
         t = np.array(times[pname])
         lines.append(f"| {name} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | "
                      f"{2.0 * B * nd * lq * ld * dim / np.median(t) / 1e12:.2f} | {(cq.numel() + dbytes + B * nd * 4) / np.median(t) / 1e9:.1f} |")
-    del cd, bd, sd
-    lines += ["", "## quantize_rows and pack_rows_b1 against a device-to-device copy of the same input bytes", "",
+    del cd, bd, wd, sd
+    lines += ["", "## quantize_rows, pack_rows_b1 and quantize_rows_i4 against a device-to-device copy of the same input bytes", "",
               "GB/s counts the input rows once (the quantiser also writes a quarter (f32) or half (bf16) as many bytes of codes, the packer a",
-              "32nd or a 16th as many of bit words; the copy writes as many as it reads).", "",
+              "32nd or a 16th as many of bit words, the int4 quantiser an 8th or a quarter as many of nibble words; the copy writes as many",
+              "as it reads).", "",
               "| rows x dim, input | path | ms | spread ms | input GB/s |", "|---|---|---|---|---|"]
     for n, dim, dt in ((1 << 20, 128, torch.float32), (1 << 20, 128, torch.bfloat16), (1 << 17, 1024, torch.float32)):
         x = torch.randn((n, dim), device="cuda").to(dt)
         y = torch.empty_like(x)
         paths = [("quantize_rows", lambda: npa.quantize_rows(x)), ("pack_rows_b1", lambda: B1.pack_rows_b1(x)),
+                 ("quantize_rows_i4", lambda: I4.quantize_rows_i4(x)),
                  ("torch copy_ (device to device)", lambda: y.copy_(x))]
         times = {p[0]: [] for p in paths}
         for _ in range(a.rounds):
