@@ -1255,6 +1255,31 @@ int np_hip_quantize_rows_i4(int32_t device, int32_t dtype, int32_t dim, const vo
 int np_hip_quantize_rows_i4_device(int32_t device, int32_t dtype, int32_t dim, const void* d_rows, int64_t n_rows,
                                    uint32_t* d_out_words, float* d_out_scales, void* stream);
 
+/* ---- f16 rows for batched MaxSim (np_maxsim_f16.hip) --------------------------------------------------------------------
+ * NP_DT_F16: rows of raw IEEE binary16 words, `dim` elements apart, unpadded -- queries and documents alike.  The entries
+ * above keep refusing it; the _f16 entries below take nothing else.  The product runs on v_mfma_f32_32x32x16_f16; a product
+ * of two f16 values is exact in f32, so the only roundings are those of the f32 accumulation.
+ *   semantics   those of np_hip_maxsim_batch with the rows used as given (nothing is rounded or normalised; subnormal
+ *               elements count with their value): sim[q][t] = the f32-accumulated row dot product, per query token the
+ *               maximum over the document's tokens with non-finite sims ignored and equal ones to the lowest t, the score
+ *               the f32 sum of the maxima in query-token order from 0.0f; an empty query or document scores 0
+ *   matches     allowed, with precision 0's layout and meaning: the rows are not rounded, so a position means what it means
+ *               there.  The score equals the ordered f32 sum of its row, bit for bit
+ *   independent a pair's bits depend on its two matrices only (the promise made above)
+ * Shapes, offsets, pairs or all pairs, the host copies of the device entry, the limits (1 <= dim <= 1024, at most 256 tokens
+ * per query; checked before any allocation or device lookup) and the one-allocation rule are those of np_hip_maxsim_batch /
+ * np_hip_maxsim_batch_device. */
+#define NP_DT_F16 5 /* 3 and 4 are used inside the library for the binary and int4 forms */
+int np_hip_maxsim_batch_f16(int32_t device, int32_t dim, const uint16_t* queries, const int32_t* q_tok_offsets, int32_t B,
+                            const uint16_t* documents, const int64_t* doc_tok_offsets, int64_t n_docs, const int64_t* pair_docs,
+                            const int64_t* pair_offsets /* [B+1]; both NULL = all pairs */, float* out_scores,
+                            float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+int np_hip_maxsim_batch_f16_device(int32_t device, int32_t dim, const uint16_t* d_queries, const int32_t* d_q_tok_offsets,
+                                   const int32_t* h_q_tok_offsets, int32_t B, const uint16_t* d_documents,
+                                   const int64_t* d_doc_tok_offsets, const int64_t* h_doc_tok_offsets, int64_t n_docs,
+                                   const int64_t* d_pair_docs, const int64_t* d_pair_offsets, const int64_t* h_pair_offsets,
+                                   float* d_out_scores, float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

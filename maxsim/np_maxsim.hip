@@ -512,6 +512,7 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
   p.dscale = d_dscale;
   if (dtype == NP_MS_DT_B1) return maxsim_b1_launch(st, p, plan);
   if (dtype == NP_MS_DT_I4) return maxsim_i4_launch(st, p, plan);
+  if (dtype == NP_MS_DT_F16) return maxsim_f16_launch(st, p, plan);
   if (dtype == NP_MS_DT_I8) return maxsim_launch_mode<3>(st, p, plan);
   if (precision == 0) return maxsim_launch_mode<0>(st, p, plan);
   if (dtype == NP_MS_DT_F32) return maxsim_launch_mode<1>(st, p, plan);

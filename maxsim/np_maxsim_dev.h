@@ -1,5 +1,5 @@
 // np_maxsim_dev.h -- what the batched-MaxSim kernels share: maxsim_kernel (np_maxsim.hip), maxsim_b1_kernel
-// (np_maxsim_b1.hip) and maxsim_i4_kernel (np_maxsim_i4.hip) take the same launch arguments, the int8 LDS geometry and the scaled argmax walk; the entries of both
+// (np_maxsim_b1.hip), maxsim_i4_kernel (np_maxsim_i4.hip) and maxsim_f16_kernel (np_maxsim_f16.hip) take the same launch arguments, the int8 LDS geometry and the scaled argmax walk; the entries of both
 // files go through the same staging (np_maxsim.hip defines it).
 #pragma once
 #include "np_internal.h"
@@ -77,5 +77,7 @@ int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t d
 int maxsim_b1_launch(hipStream_t st, MaxsimP p, const MaxsimPlan& plan);
 // np_maxsim_i4.hip: the launches of maxsim_i4_kernel
 int maxsim_i4_launch(hipStream_t st, MaxsimP p, const MaxsimPlan& plan);
+// np_maxsim_f16.hip: the launches of maxsim_f16_kernel (Q and D are f16 rows; no scales)
+int maxsim_f16_launch(hipStream_t st, MaxsimP p, const MaxsimPlan& plan);
 
 }  // namespace np

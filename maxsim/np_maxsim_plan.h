@@ -10,6 +10,7 @@ constexpr int NP_MS_DT_F32 = 0, NP_MS_DT_BF16 = 1;   // NP_DT_F32 / NP_DT_BF16 o
 constexpr int NP_MS_DT_I8 = 2;                // NP_DT_I8: int8 codes with one f32 scale per row (the _i8 entries only)
 constexpr int NP_MS_DT_B1 = 3;                // inside the library only: int8 query rows against document rows of one bit per dim (the _b1 entries)
 constexpr int NP_MS_DT_I4 = 4;                // inside the library only: int8 query rows against document rows of one nibble per dim (the _i4 entries)
+constexpr int NP_MS_DT_F16 = 5;               // NP_DT_F16: rows as raw IEEE binary16 words on both sides (the _f16 entries only)
 constexpr int NP_MS_MAX_DIM = 1024;
 constexpr int NP_MS_MAX_QUERY_TOKENS = 256;   // eight 32-token query tiles, as S6
 constexpr int NP_MS_KC_F32 = 32;              // dims per LDS chunk, f32 MFMA (16 steps of 32x32x2)
@@ -96,11 +97,21 @@ inline int maxsim_check_args_i4(int32_t dim, const void* q_scales, int32_t B, co
   return c;
 }
 
-// bytes of one row: f32 / bf16 / int8 rows are `dim` elements; a binary document row is ceil(dim / 32) 32-bit words, an
+// np_hip_maxsim_batch_f16: np_hip_maxsim_batch's limits (f16 products are exact in f32 and the rows are not rounded, so
+// matches are allowed as at precision 0)
+inline int maxsim_check_args_f16(int32_t dim, int32_t B, const int32_t* q_tok_offsets, int64_t n_docs, const int64_t* doc_tok_offsets,
+                                 bool listed, const int64_t* pair_docs, const int64_t* pair_offsets, const char** why,
+                                 int64_t* bad_pair) {
+  return maxsim_check_args(NP_MS_DT_F32, 0, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed, pair_docs, pair_offsets, true,
+                           why, bad_pair);
+}
+
+// bytes of one row: f32 / bf16 / f16 / int8 rows are `dim` elements; a binary document row is ceil(dim / 32) 32-bit words, an
 // int4 document row ceil(dim / 8) words, and the queries of both are int8 rows
 inline size_t maxsim_row_bytes(int32_t dtype, int32_t dim, bool document) {
   if (dtype == NP_MS_DT_B1) return document ? (size_t)((dim + 31) / 32) * 4 : (size_t)dim;
   if (dtype == NP_MS_DT_I4) return document ? (size_t)((dim + 7) / 8) * 4 : (size_t)dim;
+  if (dtype == NP_MS_DT_F16) return (size_t)dim * 2;
   return (size_t)dim * (dtype == NP_MS_DT_I8 ? 1 : dtype == NP_MS_DT_BF16 ? 2 : 4);
 }
 

@@ -1,4 +1,4 @@
-"""Times np_hip_maxsim_batch (maxsim_scores on device tensors: f32, bf16, int8, binary and int4 document rows) against rerank_maxsim
+"""Times np_hip_maxsim_batch (maxsim_scores on device tensors: f32, bf16, f16, int8, binary and int4 document rows) against rerank_maxsim
 called once per query and against torch (matmul + amax + sum on the device), and quantize_rows / pack_rows_b1 / quantize_rows_i4 against a
 device-to-device copy of their input bytes, alternating in one process, and writes profiles/maxsim_time.md.
 
@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "next-plaid_amd"), ROOT]
 import next_plaid_amd as npa  # noqa: E402
 from maxsim import maxsim_b1 as B1  # noqa: E402
+from maxsim import maxsim_f16 as F16  # noqa: E402
 from maxsim import maxsim_i4 as I4  # noqa: E402
 
 # (name, queries, query tokens, documents, document tokens, dim, listed documents per query or None = all pairs)
@@ -62,6 +63,7 @@ def main():
         flop = 2.0 * npairs * lq * ld * dim
         tq, td = torch.from_numpy(q).cuda(), torch.from_numpy(d).cuda()
         hq, hd = tq.to(torch.bfloat16), td.to(torch.bfloat16)
+        fq, fd = tq.to(torch.float16), td.to(torch.float16)
         (cq, sq), (cd, sd) = npa.quantize_rows(tq), npa.quantize_rows(td)
         bd, sb = B1.pack_rows_b1(td)
         wd, sw = I4.quantize_rows_i4(td)
@@ -73,6 +75,9 @@ def main():
 
         def ours_i8():
             return npa.maxsim_scores(cq, cd, pairs=pairs, query_offsets=qoff, document_offsets=doff, query_scales=sq, document_scales=sd)
+
+        def ours_f16():
+            return F16.maxsim_scores_f16(fq, fd, pairs=pairs, query_offsets=qoff, document_offsets=doff)
 
         def ours_b1():
             return B1.maxsim_scores_b1(cq, sq, bd, sb, pairs=pairs, query_offsets=qoff, document_offsets=doff)
@@ -92,6 +97,7 @@ def main():
                 ids = range(nd) if pairs is None else pairs[b]
                 npa.rerank_maxsim(q[b * lq:(b + 1) * lq], [d[i * ld:(i + 1) * ld] for i in ids])
         paths = [("maxsim_batch f32, precision 0", ours(tq, td, 0), 4), ("maxsim_batch bf16 rows, precision 3", ours(hq, hd, 3), 2),
+                 ("maxsim_batch_f16 f16 rows", ours_f16, 2),
                  ("maxsim_batch f32 rows, precision 3", ours(tq, td, 3), 4), ("maxsim_batch int8 rows (+ f32 row scales)", ours_i8, 1),
                  ("maxsim_batch_b1 int8 queries, binary documents (+ f32 row scales)", ours_b1, (1, 1 / 8)),
                  ("maxsim_batch_i4 int8 queries, int4 documents (+ f32 row scales)", ours_i4, (1, 1 / 2)),
