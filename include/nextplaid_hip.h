@@ -1280,6 +1280,26 @@ int np_hip_maxsim_batch_f16_device(int32_t device, int32_t dim, const uint16_t* 
                                    const int64_t* d_pair_docs, const int64_t* d_pair_offsets, const int64_t* h_pair_offsets,
                                    float* d_out_scores, float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
 
+/* ---- queries of any length for batched MaxSim (np_maxsim_long.hip) ------------------------------------------------------
+ * np_hip_maxsim_batch / np_hip_maxsim_batch_device without the limit on a query's tokens: a page scored against pages, a
+ * document against documents, a long text query.  The argument lists are those two entries': dtype NP_DT_F32 or NP_DT_BF16,
+ * precision 0 or 3, listed pairs or all pairs, nullable match outputs at precision 0.  Everything said there under
+ * semantics, matches, independent, limits and memory holds, with one change: THERE IS NO LIMIT ON TOKENS PER QUERY (the
+ * int32 q_tok_offsets are the only bound).  Every other refusal answers before any allocation or device lookup, its message
+ * naming maxsim_batch_long.  The kernel walks a query in passes of at most 8 (precision 0: 4) 32-token tiles and carries the
+ * ordered f32 sum from pass to pass, so a pair's bits do not depend on the split: a query of at most 256 tokens gets the
+ * same bits from these entries and from np_hip_maxsim_batch.  The entries above keep refusing 257 tokens. */
+int np_hip_maxsim_batch_long(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
+                             const int32_t* q_tok_offsets, int32_t B, const void* documents, const int64_t* doc_tok_offsets,
+                             int64_t n_docs, const int64_t* pair_docs, const int64_t* pair_offsets /* [B+1]; both NULL = all pairs */,
+                             float* out_scores, float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+int np_hip_maxsim_batch_long_device(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
+                                    const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                    const void* d_documents, const int64_t* d_doc_tok_offsets,
+                                    const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                                    const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                                    float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

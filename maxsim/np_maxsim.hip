@@ -67,113 +67,8 @@ namespace np {
 // MODE 0: f32 rows, f32 MFMA.  1: f32 rows rounded to bf16, bf16 MFMA.  2: bf16 rows, bf16 MFMA.  3: int8 rows, i8 MFMA, in
 // the bf16 modes' LDS geometry (a row's 128 bytes are 128 dims instead of 64).
 constexpr int NP_MS_SCALE_AT = 128;                    // MODE 3: a document row's scale, in the pad bytes of its LDS row
-template <int MODE> struct MsRaw { uint4 v[MODE == 1 ? 2 : 1]; };   // one staging unit on its way from HBM to LDS
-
-template <int MODE, int NQT> struct MsLds {
-  static constexpr int KC = MODE == 0 ? NP_MS_KC_F32 : MODE == 3 ? NP_MS_KC_I8 : NP_MS_KC_BF16;
-  static constexpr int R = NQT * 32;                               // slot rows
-  static constexpr int SQ = (NQT & 1) ? R : R + 32;                // f32: floats between two k rows of the slots
-  static constexpr size_t Q_BYTES = MODE == 0 ? (size_t)KC * SQ * 4 : (size_t)R * NP_MS_BROW * 2;
-  static constexpr size_t D_BYTES = MODE == 0 ? (size_t)KC * 32 * 4 : (size_t)32 * NP_MS_BROW * 2;
-  static constexpr size_t KEY_OFF = Q_BYTES + 4 * D_BYTES;
-  static constexpr size_t QROW_OFF = KEY_OFF + (size_t)NP_MS_WG_DOCS * R * 8;
-  static constexpr size_t META_OFF = QROW_OFF + (size_t)R * 8;
-  static constexpr size_t BYTES = META_OFF + NP_MS_META;
-};
-
-// four f32 dims k0 .. k0 + 3 of a row (NULL = a row past the end), zeros past `dim`
-__device__ __forceinline__ uint4 ms_load4f(const float* rowp, int k0, int dim, bool vec) {
-  uint4 r = make_uint4(0u, 0u, 0u, 0u);
-  if (!rowp || k0 >= dim) return r;
-  if (vec) return *reinterpret_cast<const uint4*>(rowp + k0);   // dim % 4 == 0: k0 + 4 <= dim
-  r.x = __float_as_uint(rowp[k0]);
-  if (k0 + 1 < dim) r.y = __float_as_uint(rowp[k0 + 1]);
-  if (k0 + 2 < dim) r.z = __float_as_uint(rowp[k0 + 2]);
-  if (k0 + 3 < dim) r.w = __float_as_uint(rowp[k0 + 3]);
-  return r;
-}
-// eight bf16 dims k0 .. k0 + 7 of a row
-__device__ __forceinline__ uint4 ms_load8h(const uint16_t* rowp, int k0, int dim, bool vec) {
-  uint4 r = make_uint4(0u, 0u, 0u, 0u);
-  if (!rowp || k0 >= dim) return r;
-  if (vec) return *reinterpret_cast<const uint4*>(rowp + k0);   // dim % 8 == 0: k0 + 8 <= dim
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (k0 + i < dim) w[i >> 1] |= (uint32_t)rowp[k0 + i] << (16 * (i & 1));
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-template <int MODE>
-__device__ __forceinline__ MsRaw<MODE> ms_load(const void* base, int64_t row, int dim, int k0, bool vec) {
-  MsRaw<MODE> r;
-  if (MODE == 3) {
-    r.v[0] = ms_load16b(row < 0 ? nullptr : static_cast<const uint8_t*>(base) + row * dim, k0, dim, vec);
-  } else if (MODE == 2) {
-    r.v[0] = ms_load8h(row < 0 ? nullptr : static_cast<const uint16_t*>(base) + row * dim, k0, dim, vec);
-  } else {
-    const float* rp = row < 0 ? nullptr : static_cast<const float*>(base) + row * dim;
-    r.v[0] = ms_load4f(rp, k0, dim, vec);
-    if (MODE == 1) r.v[MODE == 1 ? 1 : 0] = ms_load4f(rp, k0 + 4, dim, vec);
-  }
-  return r;
-}
-
-__device__ __forceinline__ uint32_t ms_bf16_pair(uint32_t lo_f32, uint32_t hi_f32) {   // nearest, ties to even
-  const uint16_t a = __builtin_bit_cast(uint16_t, (__bf16)__uint_as_float(lo_f32));
-  const uint16_t b = __builtin_bit_cast(uint16_t, (__bf16)__uint_as_float(hi_f32));
-  return (uint32_t)a | ((uint32_t)b << 16);
-}
-
-// unit (row, g) of a region to LDS (int8 units are 16 bytes at 16 g like bf16 ones).  f32: `S` floats between k rows, the unit's dims are k rows 4g .. 4g + 3, written in
-// opposite order by even and odd g (the two halves of a wave differ in g's parity or in the bank of `row`).
-template <int MODE>
-__device__ __forceinline__ void ms_store(unsigned char* region, int S, int row, int g, const MsRaw<MODE>& r) {
-  if (MODE == 0) {
-    float* s = reinterpret_cast<float*>(region);
-    const uint32_t v[4] = {r.v[0].x, r.v[0].y, r.v[0].z, r.v[0].w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int a = (4 * g + i) * S + row, b = (4 * g + (i ^ 1)) * S + row;
-      s[(g & 1) ? b : a] = __uint_as_float((g & 1) ? v[i ^ 1] : v[i]);
-    }
-  } else {
-    uint4 w = r.v[0];
-    if (MODE == 1) {
-      const uint4 hi = r.v[MODE == 1 ? 1 : 0];
-      w = make_uint4(ms_bf16_pair(r.v[0].x, r.v[0].y), ms_bf16_pair(r.v[0].z, r.v[0].w), ms_bf16_pair(hi.x, hi.y),
-                     ms_bf16_pair(hi.z, hi.w));
-    }
-    *reinterpret_cast<uint4*>(region + ((size_t)row * NP_MS_BROW + 8 * g) * 2) = w;
-  }
-}
-
-// unit u of a region of `rows` rows (a power of two >= 32): f32 walks the rows first (consecutive banks on the transposed
-// write), bf16 the eight 16-byte units of a row first (a row's 128 bytes per eight lanes, on the load and on the write)
-template <int MODE>
-__device__ __forceinline__ void ms_unit(int u, int rows, int& row, int& g) {
-  if (MODE == 0) {
-    row = u & (rows - 1);
-    g = u / rows;
-  } else {
-    g = u & 7;
-    row = u >> 3;
-  }
-}
-
-// tile_row_argmax's shape without row scales: rows t0 + mfma_row(r, kk) of one accumulator, entries of rows past `len`
-// and non-finite entries ignored; ascending rows and the strict `>` keep the lowest position of this lane's rows.
-__device__ __forceinline__ void ms_row_argmax(const f32x16& acc, int64_t t0, int64_t len, int kk, float& mm, int& pos) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t trow = t0 + mfma_row(r, kk);
-    const float x = acc[r];
-    if (trow < len && finitef(x)) {
-      pos = x > mm ? (int)trow : pos;
-      mm = fmaxf(mm, x);
-    }
-  }
-}
+// MsRaw, MsLds and the staging helpers (ms_load, ms_store, ms_unit, ms_row_argmax): np_maxsim_dev.h, shared with
+// maxsim_long_kernel (np_maxsim_long.hip).
 
 template <int MODE, int NQT>
 __global__ void __launch_bounds__(256) maxsim_kernel(MaxsimP p) {
@@ -484,9 +379,13 @@ int maxsim_device_ok(int32_t device, int* compute_units) {   // np_quant.hip and
 static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t precision, int32_t dim, const void* d_q,
                       const int32_t* d_qoff, const int32_t* h_qoff, int32_t B, const void* d_d, const int64_t* d_doff,
                       int64_t n_docs, const int64_t* d_pair_docs, const int64_t* d_poff, const int64_t* h_poff, float* d_scores,
-                      float* d_sims, int32_t* d_pos, const float* d_qscale = nullptr, const float* d_dscale = nullptr) {
+                      float* d_sims, int32_t* d_pos, const float* d_qscale = nullptr, const float* d_dscale = nullptr,
+                      bool long_queries = false) {
   const bool listed = d_pair_docs != nullptr;
-  const MaxsimPlan plan = maxsim_plan(listed, h_qoff, B, n_docs, h_poff, compute_units);
+  const int mode = precision == 0 ? 0 : dtype == NP_MS_DT_F32 ? 1 : 2;   // the _long entries take f32 / bf16 rows only
+  const MaxsimLongPlan lplan =
+      long_queries ? maxsim_long_plan(mode, listed, h_qoff, B, n_docs, h_poff, compute_units) : MaxsimLongPlan();
+  const MaxsimPlan plan = long_queries ? MaxsimPlan(lplan) : maxsim_plan(listed, h_qoff, B, n_docs, h_poff, compute_units);
   if (plan.gx <= 0 || plan.gy <= 0) return NP_OK;
   const size_t pitch = maxsim_row_bytes(dtype, dim, false), dpitch = maxsim_row_bytes(dtype, dim, true);
   MaxsimP p;
@@ -510,6 +409,7 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
   p.vecd = dpitch % 16 == 0 && (uintptr_t)d_d % 16 == 0;
   p.qscale = d_qscale;
   p.dscale = d_dscale;
+  if (long_queries) return maxsim_long_launch(st, p, lplan, mode);
   if (dtype == NP_MS_DT_B1) return maxsim_b1_launch(st, p, plan);
   if (dtype == NP_MS_DT_I4) return maxsim_i4_launch(st, p, plan);
   if (dtype == NP_MS_DT_F16) return maxsim_f16_launch(st, p, plan);
@@ -541,7 +441,7 @@ int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t
                               const void* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
                               const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
                               const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
-                              float* d_out_match_sims, int32_t* d_out_match_pos, void* stream) {
+                              float* d_out_match_sims, int32_t* d_out_match_pos, void* stream, bool long_queries) {
   const bool listed = d_pair_docs != nullptr;
   const int64_t P = B <= 0 ? 0 : (listed ? h_pair_offsets[B] : (int64_t)B * n_docs);
   if (P == 0) return NP_OK;
@@ -555,14 +455,15 @@ int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t
   DeviceGuard g(device);
   return maxsim_run((hipStream_t)stream, cus, dtype, precision, dim, d_queries, d_q_tok_offsets, h_q_tok_offsets, B,
                     d_documents, d_doc_tok_offsets, n_docs, d_pair_docs, d_pair_offsets, h_pair_offsets, d_out_scores,
-                    d_out_match_sims, d_out_match_pos, d_q_scales, d_d_scales);
+                    d_out_match_sims, d_out_match_pos, d_q_scales, d_d_scales, long_queries);
 }
 
 // The host entries after their checks: the call staged through one allocation.
 int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* queries,
                             const float* q_scales, const int32_t* q_tok_offsets, int32_t B, const void* documents,
                             const float* d_scales, const int64_t* doc_tok_offsets, int64_t n_docs, const int64_t* pair_docs,
-                            const int64_t* pair_offsets, float* out_scores, float* out_match_sims, int32_t* out_match_pos) {
+                            const int64_t* pair_offsets, float* out_scores, float* out_match_sims, int32_t* out_match_pos,
+                            bool long_queries) {
   const bool listed = pair_docs != nullptr;
   const bool rows = out_match_sims || out_match_pos;
   const int64_t P = B <= 0 ? 0 : (listed ? pair_offsets[B] : (int64_t)B * n_docs);
@@ -612,7 +513,7 @@ int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t d
     NP_HIP(hipMemcpy(d_poff, pair_offsets, (size_t)(B + 1) * 8, hipMemcpyHostToDevice));
   }
   NP_TRY(maxsim_run(nullptr, cus, dtype, precision, dim, d_q, d_qoff, q_tok_offsets, B, d_d, d_doff, n_docs, d_ids, d_poff,
-                    pair_offsets, d_sc, d_sim, d_pos, d_qs, d_ds));
+                    pair_offsets, d_sc, d_sim, d_pos, d_qs, d_ds, long_queries));
   NP_HIP(hipMemcpy(out_scores, d_sc, (size_t)P * 4, hipMemcpyDeviceToHost));
   if (d_sim && R > 0) NP_HIP(hipMemcpy(out_match_sims, d_sim, (size_t)R * 4, hipMemcpyDeviceToHost));
   if (d_pos && R > 0) NP_HIP(hipMemcpy(out_match_pos, d_pos, (size_t)R * 4, hipMemcpyDeviceToHost));

@@ -24,9 +24,11 @@ constexpr int NP_MS_MAX_GRID_Y = 65535;
 // The checks that need only host arrays.  0 = fine, 1 = shape error, 2 = invalid argument; *why names the argument (a
 // string literal).  pair_docs may be NULL with a list (the device entry cannot see the ids); *bad_pair = the first pair
 // whose id lies outside [0, n_docs), when the return value is 2 because of one (-1 otherwise).
-inline int maxsim_check_args(int32_t dtype, int32_t precision, int32_t dim, int32_t B, const int32_t* q_tok_offsets,
-                             int64_t n_docs, const int64_t* doc_tok_offsets, bool listed, const int64_t* pair_docs,
-                             const int64_t* pair_offsets, bool want_matches, const char** why, int64_t* bad_pair) {
+// max_query_tokens: NP_MS_MAX_QUERY_TOKENS for every entry but the _long ones, which have no limit (maxsim_check_args_long).
+inline int maxsim_check_args_upto(int64_t max_query_tokens, int32_t dtype, int32_t precision, int32_t dim, int32_t B,
+                                  const int32_t* q_tok_offsets, int64_t n_docs, const int64_t* doc_tok_offsets, bool listed,
+                                  const int64_t* pair_docs, const int64_t* pair_offsets, bool want_matches, const char** why,
+                                  int64_t* bad_pair) {
   *why = "";
   *bad_pair = -1;
   if (dim < 1 || dim > NP_MS_MAX_DIM) return *why = "dim must lie in 1 .. 1024", 1;
@@ -43,7 +45,7 @@ inline int maxsim_check_args(int32_t dtype, int32_t precision, int32_t dim, int3
   for (int b = 0; b < B; ++b) {
     const int64_t lq = (int64_t)q_tok_offsets[b + 1] - q_tok_offsets[b];
     if (lq < 0) return *why = "q_tok_offsets must not decrease", 2;
-    if (lq > NP_MS_MAX_QUERY_TOKENS) return *why = "q_tok_offsets: a query has more than 256 tokens", 1;
+    if (lq > max_query_tokens) return *why = "q_tok_offsets: a query has more than 256 tokens", 1;
   }
   if (n_docs > 0 && doc_tok_offsets[0] != 0) return *why = "doc_tok_offsets must start at 0", 2;
   for (int64_t i = 0; i < n_docs; ++i)
@@ -63,6 +65,19 @@ inline int maxsim_check_args(int32_t dtype, int32_t precision, int32_t dim, int3
     for (int64_t i = 0; i < pair_offsets[B]; ++i)
       if (pair_docs[i] < 0 || pair_docs[i] >= n_docs) return *bad_pair = i, *why = "pair_docs names a document outside [0, n_docs)", 2;
   return 0;
+}
+inline int maxsim_check_args(int32_t dtype, int32_t precision, int32_t dim, int32_t B, const int32_t* q_tok_offsets,
+                             int64_t n_docs, const int64_t* doc_tok_offsets, bool listed, const int64_t* pair_docs,
+                             const int64_t* pair_offsets, bool want_matches, const char** why, int64_t* bad_pair) {
+  return maxsim_check_args_upto(NP_MS_MAX_QUERY_TOKENS, dtype, precision, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed,
+                                pair_docs, pair_offsets, want_matches, why, bad_pair);
+}
+// np_hip_maxsim_batch_long: the same tests without the one on a query's tokens (the int32 q_tok_offsets are the only bound)
+inline int maxsim_check_args_long(int32_t dtype, int32_t precision, int32_t dim, int32_t B, const int32_t* q_tok_offsets,
+                                  int64_t n_docs, const int64_t* doc_tok_offsets, bool listed, const int64_t* pair_docs,
+                                  const int64_t* pair_offsets, bool want_matches, const char** why, int64_t* bad_pair) {
+  return maxsim_check_args_upto(INT64_MAX, dtype, precision, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed, pair_docs,
+                                pair_offsets, want_matches, why, bad_pair);
 }
 
 // np_hip_maxsim_batch_i8: the same limits (rows of int8 codes multiply exactly, so matches are allowed as at precision 0),
@@ -159,6 +174,47 @@ inline MaxsimPlan maxsim_plan(bool listed, const int32_t* q_tok_offsets, int32_t
   p.NQT = slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : 8;
   p.gx = (max_n + p.WD - 1) / p.WD;
   p.gy = (B + p.G - 1) / p.G;
+  return p;
+}
+
+// np_hip_maxsim_batch_long (np_maxsim_long.hip): a query of nqt 32-token tiles is walked in `passes` passes of at most SP tiles,
+// so that the accumulators and the key table are one pass wide whatever the query's length.  The passes are even: the first
+// nqt % passes of them take one tile more than the others (33 tiles at 8 a pass: 7, 7, 7, 6, 6).  SPmax: 8 for the bf16 MFMA
+// modes; 4 for mode 0, where 8 accumulator tiles beside the f32 staging registers do not fit the register file without
+// spills (profiles/maxsim_kernel_resources.md).  constexpr: the kernel evaluates the same three formulas per query.
+constexpr int NP_MS_LONG_SPMAX_F32 = 4, NP_MS_LONG_SPMAX_BF16 = 8;
+constexpr int maxsim_long_passes(int nqt, int spmax) { return (nqt + spmax - 1) / spmax; }
+constexpr int maxsim_long_sp(int nqt, int passes) { return passes > 0 ? (nqt + passes - 1) / passes : 0; }
+// first tile of pass ps (ps = passes: nqt); passes > 0
+constexpr int maxsim_long_first(int nqt, int passes, int ps) {
+  return ps * (nqt / passes) + (ps < nqt % passes ? ps : nqt % passes);
+}
+
+// blockIdx.y = one query in both forms (G = 1), blockIdx.x = WD documents or WD consecutive pairs of the query's list; WD
+// halves while the grid would leave compute units idle.  nqt, passes and SP are those of the call's longest query; NQT = the
+// instantiation (1, 2, 4 or 8 slots >= SP).  In the kernel a query's own passes = ceil(its tiles / NQT): for the longest
+// query that is `passes` (SP <= NQT <= SPmax), and a pair's bits do not depend on the split anyway.
+struct MaxsimLongPlan : MaxsimPlan {
+  int passes = 0, SP = 0;
+};
+inline MaxsimLongPlan maxsim_long_plan(int mode, bool listed, const int32_t* q_tok_offsets, int32_t B, int64_t n_docs,
+                                       const int64_t* pair_offsets, int compute_units) {
+  MaxsimLongPlan p;
+  int max_lq = 0;
+  int64_t max_n = listed ? 0 : n_docs;
+  for (int b = 0; b < B; ++b) {
+    if (q_tok_offsets[b + 1] - q_tok_offsets[b] > max_lq) max_lq = q_tok_offsets[b + 1] - q_tok_offsets[b];
+    if (listed && pair_offsets[b + 1] - pair_offsets[b] > max_n) max_n = pair_offsets[b + 1] - pair_offsets[b];
+  }
+  p.nqt = (int)(((int64_t)max_lq + 31) / 32);
+  p.passes = maxsim_long_passes(p.nqt, mode == 0 ? NP_MS_LONG_SPMAX_F32 : NP_MS_LONG_SPMAX_BF16);
+  p.SP = maxsim_long_sp(p.nqt, p.passes);
+  p.NQT = p.SP <= 1 ? 1 : p.SP <= 2 ? 2 : p.SP <= 4 ? 4 : 8;
+  p.G = 1;
+  const int64_t want = 2 * (int64_t)(compute_units > 0 ? compute_units : 256);
+  while (p.WD > 1 && (int64_t)B * ((max_n + p.WD - 1) / p.WD) < want) p.WD /= 2;
+  p.gx = (max_n + p.WD - 1) / p.WD;
+  p.gy = B;
   return p;
 }
 

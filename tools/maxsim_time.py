@@ -2,7 +2,10 @@
 called once per query and against torch (matmul + amax + sum on the device), and quantize_rows / pack_rows_b1 / quantize_rows_i4 against a
 device-to-device copy of their input bytes, alternating in one process, and writes profiles/maxsim_time.md.
 
-    python tools/maxsim_time.py [--rounds 5] [--out profiles/maxsim_time.md]
+    python tools/maxsim_time.py [--rounds 5] [--out profiles/maxsim_time.md] [--long-only]
+
+The last section times np_hip_maxsim_batch_long (maxsim/maxsim_long.py) on queries past 256 tokens beside torch, and a
+256-token call through both entries; --long-only times that section alone and replaces it in --out.
 
 Call time is device-synchronised wall time; a window repeats a call until it is at least 0.2 s long (after a warm-up
 call).  FLOP/s = 2 * query tokens * document tokens * dim per pair; bytes/s = ALL rows of the call's arrays once plus the
@@ -21,6 +24,7 @@ import next_plaid_amd as npa  # noqa: E402
 from maxsim import maxsim_b1 as B1  # noqa: E402
 from maxsim import maxsim_f16 as F16  # noqa: E402
 from maxsim import maxsim_i4 as I4  # noqa: E402
+from maxsim import maxsim_long as ML  # noqa: E402
 
 # (name, queries, query tokens, documents, document tokens, dim, listed documents per query or None = all pairs)
 SHAPES = [("64 x 1000 listed x 300 tok, dim 128", 64, 32, 4000, 300, 128, 1000),
@@ -41,13 +45,70 @@ def window(fn, sync):
             return dt / n
 
 
+LONG_HEAD = "## np_hip_maxsim_batch_long: queries past 256 tokens, and what the pass loop costs at 256"
+# (name, queries, query tokens, documents, document tokens, dim, listed documents per query or None, also through np_hip_maxsim_batch)
+LONG_SHAPES = [("32 x 32 all pairs, 1030-tok pages against 1030-tok pages, dim 128", 32, 1030, 32, 1030, 128, None, False),
+               ("8 x 200 listed x 300 tok, 2048-tok queries, dim 128", 8, 2048, 800, 300, 128, 200, False),
+               ("64 x 1000 listed x 300 tok, 256-tok queries, dim 128", 64, 256, 4000, 300, 128, 1000, True)]
+
+
+def long_section(rounds, sync):
+    """maxsim_scores_long on device tensors beside torch's einsum -> amax -> sum on the same tensors; the 256-token shape goes
+    through api.maxsim_scores too (the same bits): the difference is what the pass loop and one query per workgroup cost."""
+    import torch
+    lines = ["", LONG_HEAD, "",
+             "The protocol above: one process, %d alternating rounds, call times.  torch = per query `einsum('dtk,qk->dtq')`," % rounds,
+             "`amax(1)`, `sum(1)` on the same device tensors.", "",
+             "| shape | path | ms | spread ms | TFLOP/s |", "|---|---|---|---|---|"]
+    g = np.random.default_rng(2)
+    for name, B, lq, nd, ld, dim, k, both in LONG_SHAPES:
+        tq = torch.from_numpy(g.standard_normal((B * lq, dim)).astype(np.float32)).cuda()
+        td = torch.from_numpy(g.standard_normal((nd * ld, dim)).astype(np.float32)).cuda()
+        hq, hd = tq.to(torch.bfloat16), td.to(torch.bfloat16)
+        qoff, doff = np.arange(B + 1) * lq, np.arange(nd + 1) * ld
+        pairs = None if k is None else [g.choice(nd, k, replace=False) for _ in range(B)]
+        idx = None if pairs is None else torch.from_numpy(np.stack(pairs)).cuda()
+        flop = 2.0 * B * (nd if k is None else k) * lq * ld * dim
+
+        def call(fn, x, y, prec):
+            return lambda: fn(x, y, pairs=pairs, precision=prec, query_offsets=qoff, document_offsets=doff)
+
+        def torch_ref(x, y3):
+            def f():
+                for b in range(B):
+                    torch.einsum("dtk,qk->dtq", y3 if idx is None else y3[idx[b]], x[b * lq:(b + 1) * lq]).amax(1).sum(1)
+            return f
+        paths = []
+        for label, x, y, prec in (("f32, precision 0", tq, td, 0), ("bf16 rows, precision 3", hq, hd, 3), ("f32 rows, precision 3", tq, td, 3)):
+            paths.append(("maxsim_batch_long " + label, call(ML.maxsim_scores_long, x, y, prec)))
+            if both:
+                paths.append(("maxsim_batch " + label, call(npa.maxsim_scores, x, y, prec)))
+        paths += [("torch f32 einsum+amax+sum", torch_ref(tq, td.view(nd, ld, dim))),
+                  ("torch bf16 einsum+amax+sum", torch_ref(hq, hd.view(nd, ld, dim)))]
+        times = {p[0]: [] for p in paths}
+        for _ in range(rounds):
+            for pname, fn in paths:
+                times[pname].append(window(fn, sync))
+        for pname, _ in paths:
+            t = np.array(times[pname])
+            lines.append(f"| {name} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | {flop / np.median(t) / 1e12:.2f} |")
+    return lines
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "maxsim_time.md"))
+    ap.add_argument("--long-only", action="store_true", help="time only the long-query section and replace it in --out")
     a = ap.parse_args()
     sync = torch.cuda.synchronize
+    if a.long_only:
+        kept = open(a.out).read().split("\n" + LONG_HEAD)[0].rstrip("\n").split("\n")
+        lines = kept + long_section(a.rounds, sync)
+        open(a.out, "w").write("\n".join(lines) + "\n")
+        print("\n".join(lines[len(kept):]))
+        return
     lines = ["# np_hip_maxsim_batch against rerank_maxsim per query and torch", "",
              "Median call time over %d alternating rounds (min .. max), device-synchronised.  Call figures, not kernel" % a.rounds,
              "figures: maxsim_batch includes the Python packing of the pair lists and the copies of offsets and ids; bytes count",
@@ -154,6 +215,7 @@ def main():
             t = np.array(times[pname])
             lines.append(f"| {n} x {dim}, {str(dt).split('.')[-1]} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | "
                          f"{x.numel() * x.element_size() / np.median(t) / 1e9:.1f} |")
+    lines += long_section(a.rounds, sync)
     open(a.out, "w").write("\n".join(lines) + "\n")
     print("\n".join(lines))
 
