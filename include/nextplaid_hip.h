@@ -1300,6 +1300,32 @@ int np_hip_maxsim_batch_long_device(int32_t device, int32_t dtype, int32_t preci
                                     const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
                                     float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
 
+/* ---- int8 rows for queries of any length (np_maxsim_long_i8.hip) --------------------------------------------------------
+ * np_hip_maxsim_batch_i8 / np_hip_maxsim_batch_i8_device without the limit on a query's tokens: a page of int8 codes scored
+ * against pages of int8 codes, in the format such corpora are stored in, without widening a row.  The argument lists are
+ * those two entries'; the rule is theirs, bit for bit (tests/maxsim_i8_restate.py pair(), which has no token limit): the
+ * exact i32 dot, f32(dot) * d_scales[t] with one rounding, the maximum in the order of the finite f32 values with equal ones
+ * to the lowest t, one more multiplication by q_scales[q] (a non-finite result: no match, 0.0 / -1, nothing added), the f32
+ * sum in query-token order from 0.0f.  Matches are allowed.  A query of at most 256 tokens gets the same bits from these
+ * entries and from np_hip_maxsim_batch_i8, and a pair's bits depend on its two code matrices and their scale vectors only.
+ * Refused before any allocation or device lookup, the message naming maxsim_batch_long_i8: dim outside 1 .. 1024
+ * (NP_ERR_SHAPE); NULL scales, offsets that do not start at 0 or decrease, a pair id outside [0, n_docs)
+ * (NP_ERR_INVALID_ARGUMENT; the device entry cannot see the ids: such a pair scores NaN).  B = 0 or no pairs: NP_OK, nothing
+ * written.  The kernel keeps a pass of the query's rows in LDS at their whole width -- 8 tiles of 32 tokens up to dim 224, 4
+ * up to 544, 2 up to 1024 -- and reads the documents from global memory into registers.  The _i8 entries above keep refusing
+ * 257 tokens, and np_hip_maxsim_batch_long keeps refusing NP_DT_I8. */
+int np_hip_maxsim_batch_long_i8(int32_t device, int32_t dim, const int8_t* queries, const float* q_scales /* [q tokens] */,
+                                const int32_t* q_tok_offsets, int32_t B, const int8_t* documents,
+                                const float* d_scales /* [d tokens] */, const int64_t* doc_tok_offsets, int64_t n_docs,
+                                const int64_t* pair_docs, const int64_t* pair_offsets /* [B+1]; both NULL = all pairs */,
+                                float* out_scores, float* out_match_sims /* nullable */, int32_t* out_match_pos /* nullable */);
+int np_hip_maxsim_batch_long_i8_device(int32_t device, int32_t dim, const int8_t* d_queries, const float* d_q_scales,
+                                       const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
+                                       const int8_t* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
+                                       const int64_t* h_doc_tok_offsets, int64_t n_docs, const int64_t* d_pair_docs,
+                                       const int64_t* d_pair_offsets, const int64_t* h_pair_offsets, float* d_out_scores,
+                                       float* d_out_match_sims, int32_t* d_out_match_pos, void* stream);
+
 /* ---- index creation: k-means and codec training (np_build.hip) --------------------------------------------------
  * The crate's create path (index.rs:927-967 create_index_with_kmeans_files -> kmeans.rs:261-421 compute_kmeans ->
  * index.rs:182-287 prepare_codec_artifacts / index.rs:551-... create_index_files), with Lloyd's iterations on the GPU.

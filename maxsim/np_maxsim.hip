@@ -382,9 +382,11 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
                       float* d_sims, int32_t* d_pos, const float* d_qscale = nullptr, const float* d_dscale = nullptr,
                       bool long_queries = false) {
   const bool listed = d_pair_docs != nullptr;
-  const int mode = precision == 0 ? 0 : dtype == NP_MS_DT_F32 ? 1 : 2;   // the _long entries take f32 / bf16 rows only
-  const MaxsimLongPlan lplan =
-      long_queries ? maxsim_long_plan(mode, listed, h_qoff, B, n_docs, h_poff, compute_units) : MaxsimLongPlan();
+  const int mode = precision == 0 ? 0 : dtype == NP_MS_DT_F32 ? 1 : 2;   // the _long entries take f32 / bf16 rows, or int8 rows
+  const bool long_i8 = long_queries && dtype == NP_MS_DT_I8;
+  const MaxsimLongPlan lplan = long_i8        ? maxsim_long_i8_plan(dim, listed, h_qoff, B, n_docs, h_poff, compute_units)
+                               : long_queries ? maxsim_long_plan(mode, listed, h_qoff, B, n_docs, h_poff, compute_units)
+                                              : MaxsimLongPlan();
   const MaxsimPlan plan = long_queries ? MaxsimPlan(lplan) : maxsim_plan(listed, h_qoff, B, n_docs, h_poff, compute_units);
   if (plan.gx <= 0 || plan.gy <= 0) return NP_OK;
   const size_t pitch = maxsim_row_bytes(dtype, dim, false), dpitch = maxsim_row_bytes(dtype, dim, true);
@@ -409,6 +411,7 @@ static int maxsim_run(hipStream_t st, int compute_units, int32_t dtype, int32_t 
   p.vecd = dpitch % 16 == 0 && (uintptr_t)d_d % 16 == 0;
   p.qscale = d_qscale;
   p.dscale = d_dscale;
+  if (long_i8) return maxsim_long_i8_launch(st, p, lplan);
   if (long_queries) return maxsim_long_launch(st, p, lplan, mode);
   if (dtype == NP_MS_DT_B1) return maxsim_b1_launch(st, p, plan);
   if (dtype == NP_MS_DT_I4) return maxsim_i4_launch(st, p, plan);

@@ -173,7 +173,8 @@ int maxsim_device_ok(int32_t device, int* compute_units);
 // pair_docs and pair_offsets (the device entries: and the host copy) go together; *listed = they are there
 int maxsim_pair_args(bool all, bool any, bool device_entry, bool* listed);
 // The entries after their checks.  dtype NP_MS_DT_B1 / NP_MS_DT_I4: queries are int8 rows, documents rows of bit / nibble words.
-// long_queries: the _long entries (f32 / bf16 rows): maxsim_long_plan and maxsim_long_kernel instead of maxsim_plan's kernels.
+// long_queries: the _long entries: maxsim_long_plan and maxsim_long_kernel (f32 / bf16 rows) or maxsim_long_i8_plan and
+// maxsim_long_i8_kernel (NP_MS_DT_I8) instead of maxsim_plan's kernels.
 int maxsim_device_call(int32_t device, int32_t dtype, int32_t precision, int32_t dim, const void* d_queries,
                        const float* d_q_scales, const int32_t* d_q_tok_offsets, const int32_t* h_q_tok_offsets, int32_t B,
                        const void* d_documents, const float* d_d_scales, const int64_t* d_doc_tok_offsets,
@@ -186,6 +187,8 @@ int maxsim_host_call(int32_t device, int32_t dtype, int32_t precision, int32_t d
                      float* out_scores, float* out_match_sims, int32_t* out_match_pos, bool long_queries = false);
 // np_maxsim_long.hip: the launches of maxsim_long_kernel<mode, plan.NQT> (mode 0, 1 or 2 of np_maxsim.hip)
 int maxsim_long_launch(hipStream_t st, MaxsimP p, const MaxsimLongPlan& plan, int mode);
+// np_maxsim_long_i8.hip: the launches of maxsim_long_i8_kernel<plan.NQT> (long_queries with NP_MS_DT_I8; maxsim_long_i8_plan)
+int maxsim_long_i8_launch(hipStream_t st, MaxsimP p, const MaxsimLongPlan& plan);
 // np_maxsim_b1.hip: the launches of maxsim_b1_kernel for a filled MaxsimP
 int maxsim_b1_launch(hipStream_t st, MaxsimP p, const MaxsimPlan& plan);
 // np_maxsim_i4.hip: the launches of maxsim_i4_kernel

@@ -197,8 +197,9 @@ constexpr int maxsim_long_first(int nqt, int passes, int ps) {
 struct MaxsimLongPlan : MaxsimPlan {
   int passes = 0, SP = 0;
 };
-inline MaxsimLongPlan maxsim_long_plan(int mode, bool listed, const int32_t* q_tok_offsets, int32_t B, int64_t n_docs,
-                                       const int64_t* pair_offsets, int compute_units) {
+// the plan for passes of at most `spmax` tiles (1, 2, 4 or 8)
+inline MaxsimLongPlan maxsim_long_plan_upto(int spmax, bool listed, const int32_t* q_tok_offsets, int32_t B, int64_t n_docs,
+                                            const int64_t* pair_offsets, int compute_units) {
   MaxsimLongPlan p;
   int max_lq = 0;
   int64_t max_n = listed ? 0 : n_docs;
@@ -207,7 +208,7 @@ inline MaxsimLongPlan maxsim_long_plan(int mode, bool listed, const int32_t* q_t
     if (listed && pair_offsets[b + 1] - pair_offsets[b] > max_n) max_n = pair_offsets[b + 1] - pair_offsets[b];
   }
   p.nqt = (int)(((int64_t)max_lq + 31) / 32);
-  p.passes = maxsim_long_passes(p.nqt, mode == 0 ? NP_MS_LONG_SPMAX_F32 : NP_MS_LONG_SPMAX_BF16);
+  p.passes = maxsim_long_passes(p.nqt, spmax);
   p.SP = maxsim_long_sp(p.nqt, p.passes);
   p.NQT = p.SP <= 1 ? 1 : p.SP <= 2 ? 2 : p.SP <= 4 ? 4 : 8;
   p.G = 1;
@@ -216,6 +217,45 @@ inline MaxsimLongPlan maxsim_long_plan(int mode, bool listed, const int32_t* q_t
   p.gx = (max_n + p.WD - 1) / p.WD;
   p.gy = B;
   return p;
+}
+inline MaxsimLongPlan maxsim_long_plan(int mode, bool listed, const int32_t* q_tok_offsets, int32_t B, int64_t n_docs,
+                                       const int64_t* pair_offsets, int compute_units) {
+  return maxsim_long_plan_upto(mode == 0 ? NP_MS_LONG_SPMAX_F32 : NP_MS_LONG_SPMAX_BF16, listed, q_tok_offsets, B, n_docs,
+                               pair_offsets, compute_units);
+}
+
+// np_hip_maxsim_batch_long_i8 (np_maxsim_long_i8.hip): int8 rows for the _long entries.  The int8 entry's checks without the
+// one on a query's tokens.
+inline int maxsim_check_args_long_i8(int32_t dim, const void* q_scales, int32_t B, const int32_t* q_tok_offsets,
+                                     const void* d_scales, int64_t n_docs, const int64_t* doc_tok_offsets, bool listed,
+                                     const int64_t* pair_docs, const int64_t* pair_offsets, const char** why, int64_t* bad_pair) {
+  *bad_pair = -1;
+  if (!q_scales) return *why = "q_scales is NULL", 2;
+  if (!d_scales) return *why = "d_scales is NULL", 2;
+  return maxsim_check_args_upto(INT64_MAX, NP_MS_DT_F32, 0, dim, B, q_tok_offsets, n_docs, doc_tok_offsets, listed, pair_docs,
+                                pair_offsets, true, why, bad_pair);
+}
+// A pass's query rows stay in LDS at their whole width: a row is `dim` bytes, rows maxsim_long_i8_pitch(dim) bytes apart -- an
+// ODD number of 16-byte units (consecutive rows start in different bank groups) that covers dim rounded up to the 32 dims of an
+// MFMA step, so a step's fragment never leaves its row.  Beside the rows: the two key tables and the meta block.  SPmax(dim) is
+// the widest pass (8, 4, 2 or 1 tiles) that fits NP_MS_LONG_I8_BUDGET: half of a compute unit's 160 KB, so that two workgroups
+// share one and one's staging hides behind the other's MFMAs.  dim 128: 8 tiles in 52.1 KB; dim 512: 4 tiles in 74.1 KB;
+// dim 1024 (pitch 1040): 2 tiles in 69.1 KB.  constexpr: the kernel evaluates the pitch and the offsets from the same formulas.
+constexpr int NP_MS_LONG_I8_BUDGET = 80 * 1024;
+constexpr int NP_MS_LONG_I8_META = 128;       // NP_MS_META of np_maxsim_dev.h
+constexpr int maxsim_long_i8_pitch(int dim) { return 16 * (2 * ((dim + 31) / 32) + 1); }
+constexpr size_t maxsim_long_i8_key_off(int dim, int nqt) { return (size_t)nqt * 32 * maxsim_long_i8_pitch(dim); }
+constexpr size_t maxsim_long_i8_meta_off(int dim, int nqt) {
+  return maxsim_long_i8_key_off(dim, nqt) + 2 * (size_t)NP_MS_WG_DOCS * nqt * 32 * 8;
+}
+constexpr size_t maxsim_long_i8_lds(int dim, int nqt) { return maxsim_long_i8_meta_off(dim, nqt) + NP_MS_LONG_I8_META; }
+constexpr int maxsim_long_i8_spmax(int dim) {
+  return maxsim_long_i8_lds(dim, 8) <= NP_MS_LONG_I8_BUDGET ? 8 : maxsim_long_i8_lds(dim, 4) <= NP_MS_LONG_I8_BUDGET ? 4
+       : maxsim_long_i8_lds(dim, 2) <= NP_MS_LONG_I8_BUDGET ? 2 : 1;
+}
+inline MaxsimLongPlan maxsim_long_i8_plan(int dim, bool listed, const int32_t* q_tok_offsets, int32_t B, int64_t n_docs,
+                                          const int64_t* pair_offsets, int compute_units) {
+  return maxsim_long_plan_upto(maxsim_long_i8_spmax(dim), listed, q_tok_offsets, B, n_docs, pair_offsets, compute_units);
 }
 
 }  // namespace np

@@ -303,7 +303,7 @@ EXPORTS = [
     "np_hip_maxsim_batch", "np_hip_maxsim_batch_device", "np_hip_maxsim_batch_i8", "np_hip_maxsim_batch_i8_device",
     "np_hip_quantize_rows_i8", "np_hip_quantize_rows_i8_device", "np_hip_maxsim_batch_f16", "np_hip_maxsim_batch_f16_device",   # maxsim/maxsim_f16.py
     "np_hip_maxsim_batch_b1", "np_hip_maxsim_batch_b1_device", "np_hip_pack_rows_b1", "np_hip_pack_rows_b1_device",   # maxsim/maxsim_b1.py
-    "np_hip_maxsim_batch_i4", "np_hip_maxsim_batch_i4_device", "np_hip_quantize_rows_i4", "np_hip_quantize_rows_i4_device", "np_hip_maxsim_batch_long", "np_hip_maxsim_batch_long_device",   # maxsim/maxsim_i4.py, maxsim_long.py
+    "np_hip_maxsim_batch_i4", "np_hip_maxsim_batch_i4_device", "np_hip_quantize_rows_i4", "np_hip_quantize_rows_i4_device", "np_hip_maxsim_batch_long", "np_hip_maxsim_batch_long_device", "np_hip_maxsim_batch_long_i8", "np_hip_maxsim_batch_long_i8_device",   # maxsim/maxsim_i4.py, maxsim_long.py
 ]
 
 _lib = None

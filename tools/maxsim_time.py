@@ -4,8 +4,8 @@ device-to-device copy of their input bytes, alternating in one process, and writ
 
     python tools/maxsim_time.py [--rounds 5] [--out profiles/maxsim_time.md] [--long-only]
 
-The last section times np_hip_maxsim_batch_long (maxsim/maxsim_long.py) on queries past 256 tokens beside torch, and a
-256-token call through both entries; --long-only times that section alone and replaces it in --out.
+The last section times np_hip_maxsim_batch_long and np_hip_maxsim_batch_long_i8 (maxsim/maxsim_long.py) on queries past 256
+tokens beside torch, and a 256-token call through both entries; --long-only times that section alone and replaces it in --out.
 
 Call time is device-synchronised wall time; a window repeats a call until it is at least 0.2 s long (after a warm-up
 call).  FLOP/s = 2 * query tokens * document tokens * dim per pair; bytes/s = ALL rows of the call's arrays once plus the
@@ -50,16 +50,22 @@ LONG_HEAD = "## np_hip_maxsim_batch_long: queries past 256 tokens, and what the 
 LONG_SHAPES = [("32 x 32 all pairs, 1030-tok pages against 1030-tok pages, dim 128", 32, 1030, 32, 1030, 128, None, False),
                ("8 x 200 listed x 300 tok, 2048-tok queries, dim 128", 8, 2048, 800, 300, 128, 200, False),
                ("64 x 1000 listed x 300 tok, 256-tok queries, dim 128", 64, 256, 4000, 300, 128, 1000, True)]
+# int8 rows through np_hip_maxsim_batch_long_i8, and the other ways to score the same codes: widened (code * scale) to bf16
+# through np_hip_maxsim_batch_long -- the only way for a long query without the entry -- and, at 256 tokens, np_hip_maxsim_batch_i8
+LONG_I8 = "maxsim_batch_long_i8 int8 rows (+ f32 row scales)"
+LONG_I8_OTHERS = ("maxsim_batch_long the int8 rows widened to bf16, precision 3", "maxsim_batch int8 rows (+ f32 row scales)")
 
 
 def long_section(rounds, sync):
     """maxsim_scores_long on device tensors beside torch's einsum -> amax -> sum on the same tensors; the 256-token shape goes
-    through api.maxsim_scores too (the same bits): the difference is what the pass loop and one query per workgroup cost."""
+    through api.maxsim_scores too (the same bits): the difference is what the pass loop and one query per workgroup cost.
+    The same rows quantised to int8 go through maxsim_scores_long_i8, beside those codes widened to bf16 through maxsim_scores_long."""
     import torch
     lines = ["", LONG_HEAD, "",
              "The protocol above: one process, %d alternating rounds, call times.  torch = per query `einsum('dtk,qk->dtq')`," % rounds,
              "`amax(1)`, `sum(1)` on the same device tensors.", "",
              "| shape | path | ms | spread ms | TFLOP/s |", "|---|---|---|---|---|"]
+    notes = ["", "The int8 entry against the other ways to score the same codes (medians of the table):"]
     g = np.random.default_rng(2)
     for name, B, lq, nd, ld, dim, k, both in LONG_SHAPES:
         tq = torch.from_numpy(g.standard_normal((B * lq, dim)).astype(np.float32)).cuda()
@@ -83,6 +89,13 @@ def long_section(rounds, sync):
             paths.append(("maxsim_batch_long " + label, call(ML.maxsim_scores_long, x, y, prec)))
             if both:
                 paths.append(("maxsim_batch " + label, call(npa.maxsim_scores, x, y, prec)))
+        (cq, sq), (cd, sd) = npa.quantize_rows(tq), npa.quantize_rows(td)
+        wq, wd = ((c.float() * s[:, None]).to(torch.bfloat16) for c, s in ((cq, sq), (cd, sd)))
+        i8 = dict(pairs=pairs, query_offsets=qoff, document_offsets=doff)
+        paths += [(LONG_I8, lambda: ML.maxsim_scores_long_i8(cq, cd, sq, sd, **i8)),
+                  (LONG_I8_OTHERS[0], call(ML.maxsim_scores_long, wq, wd, 3))]
+        if both:
+            paths.append((LONG_I8_OTHERS[1], lambda: npa.maxsim_scores(cq, cd, query_scales=sq, document_scales=sd, **i8)))
         paths += [("torch f32 einsum+amax+sum", torch_ref(tq, td.view(nd, ld, dim))),
                   ("torch bf16 einsum+amax+sum", torch_ref(hq, hd.view(nd, ld, dim)))]
         times = {p[0]: [] for p in paths}
@@ -92,7 +105,14 @@ def long_section(rounds, sync):
         for pname, _ in paths:
             t = np.array(times[pname])
             lines.append(f"| {name} | {pname} | {np.median(t) * 1e3:.3f} | {t.min() * 1e3:.3f} .. {t.max() * 1e3:.3f} | {flop / np.median(t) / 1e12:.2f} |")
-    return lines
+        a = np.array(times[LONG_I8]) * 1e3
+        for other in LONG_I8_OTHERS:
+            if other in times:
+                b = np.array(times[other]) * 1e3
+                notes.append(f"- {name}: {np.median(a):.3f} ms against {np.median(b):.3f} ms of `{other}`: {abs(np.median(a) / np.median(b) - 1) * 100:.1f} % "
+                             f"{'faster' if np.median(a) < np.median(b) else 'SLOWER'}; the two spreads (max - min) are {np.ptp(a):.3f} and {np.ptp(b):.3f} ms.")
+    return lines + notes + ["", "Not measured: kernel time apart from call time; any LDS budget of the int8 kernel other than its 80 KB; the LDS bank",
+                            "conflicts of its fragment reads; int8 rows at any dim but 128."]
 
 
 def main():
